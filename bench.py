@@ -32,7 +32,8 @@ insertion searches of each batch are split over the ranks and their edge records
 value is points inserted per second, with recall and the search rate of the built index beside it.
 `--n-points` scales either down to what one GPU box builds in its time limit (say so in the line).
 
-One JSON line on stdout (rank 0); progress on stderr.
+One JSON line on stdout (rank 0); progress on stderr.  `--dump-outputs DIR` writes the results of the last timed
+step as .npy files (rank 0).
 """
 import argparse
 import json
@@ -107,7 +108,13 @@ def parse():
                         "per GPU, query batch sharded; 4 = 50M x 256d index BUILD sharded over the GPUs")
     p.add_argument("--no-extras", action="store_true",
                    help="skip the PCIe-inclusive rate and the recipe-B efSearch sweep (profiling passes)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path returned for its last step to DIR/<name>.npy "
+                        "(ids, distances, counts, stats; float64 / float32) so that two builds can be compared output "
+                        "for output: the inputs are seeded and identical from run to run")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     if a.config == 2:  # configs[2]; explicit flags still win
         argv = " ".join(sys.argv[1:])
         if "--n-points" not in argv:
@@ -375,6 +382,19 @@ def time_local(c, local_search, steps, warmup):
     torch.cuda.synchronize()  # ... and close the bracket as the contract asks
     elapsed = time.perf_counter() - t0
     return elapsed, r0.elapsed_time(r1) / steps
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the results of the last timed step as DIR/<name>.npy.  Ids, counts and counters go out as
+    float64 (exact for every uint32, UINT32_MAX padding included), distances as the float32 the kernel wrote."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        x = t.cpu().numpy()
+        if name == "ids":
+            x = x.view(np.uint32)
+        x = x.astype(np.float32 if name == "distances" else np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), x)
+        log("dumped %s %s %s to %s" % (name, x.shape, x.dtype, dirname))
 
 
 def analyse(c, index, kind_name, tag, ef, recall_by_ef, local_search, kern_ms):
@@ -784,6 +804,12 @@ def main():
 
     if pipe is None:
         elapsed, kern_ms = time_local(c, local_search, K, W)
+        if args.dump_outputs:
+            # the buffers still hold the last timed launch; check() completes it as a caller of the entry would
+            # (hnsw_search_batch_device_finish: re-runs overflowed queries, raises on a failed one)
+            ids, dists = local_search.check()
+            dump_outputs(args.dump_outputs, {"ids": ids, "distances": dists, "counts": local_search.counts[:B],
+                                             "stats": local_search.stats[:B]})
     else:
         g_last = run_dist(0, W) if W > 0 else 0
         pipe.finish()
@@ -796,7 +822,7 @@ def main():
         torch.cuda.synchronize()
         dist.barrier()
         t_start = time.perf_counter()
-        run_dist(W, K)  # exactly K steps
+        g_last = run_dist(W, K)  # exactly K steps
         t_a = time.perf_counter()
         pipe.finish()
         t_b = time.perf_counter()
@@ -812,6 +838,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+        if args.dump_outputs and rank == 0:  # the gathered ids / distances of the last step, all ranks' slices
+            ids, dists = pipe.results(pipe.n_groups - 1, g_last - 1)
+            dump_outputs(args.dump_outputs, {"ids": ids, "distances": dists})
         kern_ms = None
         if rank == 0:
             _, kern_ms = time_local(c, local_search, 20, 2)  # the search launch alone, this rank's slice

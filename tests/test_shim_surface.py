@@ -2,14 +2,15 @@
 item of the reference's `hnsw` crate that its callers can reach: every `pub fn` of
 hnsw/src/template.rs, and every `use hnsw::...` path of eval_glove/src/main.rs and
 hnsw/benches/hnsw_benchmarks.rs.  The lists below are data read off the reference (file:line in the
-comments); when the reference tree is present (this container, not the GPU box) the test also checks
-that the lists themselves are complete."""
+comments); the last test checks that the lists themselves are complete against the names read off the
+reference tree into tests/golden/reference_public_items.json (tests/golden/make_public_items_fixture.py)."""
+import json
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM = os.path.join(ROOT, "shim-rust", "src")
-REF = "/root/reference"
+REF_ITEMS = os.path.join(ROOT, "tests", "golden", "reference_public_items.json")
 
 # hnsw/src/template.rs: save :43, load :75, new :133, len :146, distance :150, get_point :154,
 # layer_degrees :158, insert_vec :165, get_layer :192, ann_by_vector :306, assert_param_compliance :341,
@@ -101,16 +102,7 @@ def test_ffi_block_names_only_exported_symbols():
 
 
 def test_lists_are_complete_against_the_reference_tree():
-    if not os.path.isdir(REF):
-        import pytest
-        pytest.skip("reference tree not present (GPU box)")
-    tmpl = open(os.path.join(REF, "hnsw/src/template.rs")).read()
-    assert pub_fns(tmpl) == set(TEMPLATE_PUB_FNS)
-    assert pub_fns(open(os.path.join(REF, "hnsw/src/helpers/args.rs")).read()) == set(ARGS_PUB_FNS)
-    imports = set()
-    for f in ("eval_glove/src/main.rs", "hnsw/benches/hnsw_benchmarks.rs"):
-        for line in open(os.path.join(REF, f)):
-            m = re.match(r"\s*use (hnsw::[A-Za-z_:0-9]+);", line)
-            if m:
-                imports.add(m.group(1))
-    assert imports == set(CALLER_IMPORTS)
+    ref = json.load(open(REF_ITEMS))
+    assert set(ref["template_pub_fns"]) == set(TEMPLATE_PUB_FNS)
+    assert set(ref["args_pub_fns"]) == set(ARGS_PUB_FNS)
+    assert set(ref["caller_imports"]) == set(CALLER_IMPORTS)
