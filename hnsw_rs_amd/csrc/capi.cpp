@@ -24,10 +24,12 @@
 #include <thread>
 #include <vector>
 
+#include "device_build.h"
 #include "device_index.h"
-#include "shard_exchange.h"
+#include "hip_util.h"
 #include "host_index.h"
 
+using hx::DevBuf;
 using hx::set_error;
 
 // Per-call scratch of the host-pointer search entry points: one device arena, one pinned host arena
@@ -143,40 +145,15 @@ struct hnsw_index {
     Coalescer co;
     // counters behind hnsw_get_stat
     std::atomic<uint64_t> n_uploads{0}, n_point_patches{0}, n_patch_fallbacks{0};
-    // the on-device builds of this handle, summed (hnsw_get_stat "build_*"): what the insert kernel read -- the
-    // build's algorithmic bytes -- and how long it and the connect phases ran
-    struct BuildStats {
-        uint64_t points = 0, batches = 0, rows_read = 0, adj_rows = 0, adj_ids = 0, records = 0, removals = 0;
-        uint64_t rows_owned = 0, rows_received = 0, exchange_bytes = 0;  // sharded build, phases 2 / 3 by row ownership
-        double insert_kernel_s = 0, insert_phase_s = 0, connect_s = 0, exchange_s = 0, connect_kernel_s = 0;
-    } build;
+    hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")
 };
 
 namespace {
 
-#define HIP_TRY(expr)                                                         \
-    do {                                                                      \
-        hipError_t e_ = (expr);                                               \
-        if (e_ != hipSuccess) {                                               \
-            set_error("%s failed: %s", #expr, hipGetErrorString(e_));         \
-            return e_ == hipErrorOutOfMemory ? HNSW_ERR_OOM : HNSW_ERR_HIP;   \
-        }                                                                     \
-    } while (0)
-
-struct DevBuf {  // RAII device allocation
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n) {
-        HIP_TRY(hipMalloc(&p, n ? n : 1));
-        return HNSW_OK;
-    }
-    template <class T>
-    T *as() {
-        return static_cast<T *>(p);
-    }
-};
+// what the on-device builds read and change
+hx::BuildTarget build_target(hnsw_index *h) {
+    return {*h->host, h->dev, h->device, {h->build_batch_max, h->build_batch_div}, h->build};
+}
 
 // a device-only replica (hnsw_snapshot_adopt / _commit) has no host index behind its snapshot
 inline bool is_replica(const hnsw_index *h) { return h->dev.replica; }
@@ -767,984 +744,6 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
     return my;
 }
 
-// ---------------------------------------------------------------------------------------------
-// On-device index build: batch-synchronous insert_bulk.
-//   per batch:  GPU  hx_insert_kernel -- one wave per point: entry point, greedy descent, and for
-//                    every layer of the point search_layer(ef_cons) + select_heuristic
-//                    (inserter.rs:40-126) against the graph as it stands in HBM
-//               host connect_point   -- the reference's make_connections / prune_connections /
-//                    make_pruned_connections (template.rs:196-251) on `nb_threads` threads with the
-//                    per-row locks of the CPU build
-//               GPU  hx_scatter_rows -- the adjacency rows that changed go back to HBM
-// The first points (and any point whose search reports an error) take the CPU path, batches grow
-// with the graph (a batch never exceeds 1/8 of the points already connected, at most 4096): points
-// of one batch do not see each other, like the racing threads of the reference's own multi-threaded
-// insert_bulk.  The result is a valid HNSW graph judged by recall, not by identity.
-// ---------------------------------------------------------------------------------------------
-// Insertion order of the reference: layers top-down, ids ascending inside a level (template.rs:403-416); the
-// entry point is already in.  Levels are bytes: one counting pass instead of a sort of tens of millions of ids.
-std::vector<hx::NodeID> insertion_order(const hx::HostIndex &host, const std::vector<hx::NodeID> &ids) {
-    size_t count[257] = {0};
-    for (hx::NodeID id : ids)
-        if (id != host.params.ep) count[host.levels[id]]++;
-    size_t start[256], at = 0;
-    for (int l = 255; l >= 0; l--) {
-        start[l] = at;
-        at += count[l];
-    }
-    std::vector<hx::NodeID> order(at);
-    for (hx::NodeID id : ids)
-        if (id != host.params.ep) order[start[host.levels[id]]++] = id;
-    return order;
-}
-
-int gpu_insert_bulk(hnsw_index *h, const float *rows, uint64_t n, uint32_t nb_threads, int verbose,
-                    const uint8_t *levels) {
-    using hx::NodeID;
-    hx::HostIndex &host = *h->host;
-    if (nb_threads == 0) nb_threads = 1;
-    if (host.params.m > 128 || host.params.ef_cons > 512) {
-        set_error("on-device build supports m <= 128 and ef_construction <= 512");
-        return HNSW_ERR_ARG;
-    }
-    const uint64_t n_before = host.len();
-    std::vector<NodeID> ids;
-    int rc = host.store_points(rows, n, levels, &ids, nb_threads);
-    if (rc != HNSW_OK) return rc;
-    host.prepare_build();
-    // insertion order of the reference: layers top-down, ids ascending inside a level (template.rs:403-416)
-    const std::vector<NodeID> order = insertion_order(host, ids);
-
-    // ---- seed on the CPU: the first points must be inserted one after the other ----
-    const uint64_t SEED = 2048;
-    size_t pos = 0;
-    if (n_before < SEED) {
-        const size_t take = std::min<size_t>(order.size(), SEED - n_before);
-        std::vector<NodeID> seed(order.begin(), order.begin() + take);
-        // sequential (one Inserter) so that the seed graph is the reference's single-thread graph
-        std::unique_ptr<hx::Inserter, void (*)(hx::Inserter *)> ins(hx::new_inserter(host.len()),
-                                                                     hx::free_inserter);
-        for (NodeID id : seed) {
-            rc = host.insert(id, *ins);
-            if (rc != HNSW_OK) return rc;
-        }
-        pos = take;
-    }
-    if (pos == order.size()) {
-        host.version++;
-        return HNSW_OK;
-    }
-
-    // ---- device snapshot without the search-only extras ----
-    const int saved_inline = h->dev.inline_rows;
-    h->dev.inline_rows = 0;
-    h->dev.release();
-    rc = h->dev.upload(host, h->device);
-    h->dev.inline_rows = saved_inline;
-    if (rc != HNSW_OK) return rc;
-    h->device = h->dev.device;
-    HIP_TRY(hipSetDevice(h->dev.device));
-    hx::DevView v = h->dev.view;
-    const uint32_t m = (uint32_t)host.params.m, L = host.nb_layers();
-    const uint32_t BMAX = 4096;
-    DevBuf dLevels, dIds, dOutIds, dOutD, dStatus, dRowIdx, dRowData;
-    if ((rc = dLevels.alloc(host.len())) || (rc = dIds.alloc(BMAX * 4)) ||
-        (rc = dOutIds.alloc((size_t)BMAX * L * m * 4)) || (rc = dOutD.alloc((size_t)BMAX * L * m * 4)) ||
-        (rc = dStatus.alloc(BMAX * 4)))
-        return rc;
-    HIP_TRY(hipMemcpy(dLevels.p, host.levels.data(), host.len(), hipMemcpyHostToDevice));
-    std::vector<uint32_t> o_ids((size_t)BMAX * L * m);
-    std::vector<float> o_d((size_t)BMAX * L * m);
-    std::vector<int32_t> o_st(BMAX);
-    size_t row_cap = 0;
-    std::vector<uint32_t> row_idx, row_data;
-    std::vector<std::vector<uint64_t>> dirty_t(nb_threads);
-    hx::DirtyStamps stamps(host.adj0.size(), host.adj_up.size());
-    uint64_t connected = n_before + pos;
-    const auto t_start = std::chrono::steady_clock::now();
-    double t_gpu = 0, t_host = 0, t_sync = 0;
-    size_t n_fallback = 0, n_batches = 0;
-
-    while (pos < order.size()) {
-        const size_t B = std::min<size_t>(order.size() - pos,
-                                          std::min<uint64_t>(std::min<uint64_t>(BMAX, h->build_batch_max), std::max<uint64_t>(64, connected / h->build_batch_div)));
-        const NodeID *batch = &order[pos];
-        auto t0 = std::chrono::steady_clock::now();
-        HIP_TRY(hipMemcpy(dIds.p, batch, B * 4, hipMemcpyHostToDevice));
-        hx::InsertArgs a{};
-        a.point_ids = dIds.as<uint32_t>();
-        a.levels = dLevels.as<uint8_t>();
-        a.ef_cons = (uint32_t)host.params.ef_cons;
-        a.m = m;
-        a.max_layers = L;
-        a.out_ids = dOutIds.as<uint32_t>();
-        a.out_dists = dOutD.as<float>();
-        a.out_status = dStatus.as<int32_t>();
-        rc = hx::launch_insert(v, a, (uint32_t)B, nullptr);
-        if (rc != HNSW_OK) return rc;
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(o_ids.data(), dOutIds.p, B * L * m * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(o_d.data(), dOutD.p, B * L * m * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(o_st.data(), dStatus.p, B * 4, hipMemcpyDeviceToHost));
-        auto t1 = std::chrono::steady_clock::now();
-
-        // ---- host: connect the batch (reference semantics), collect the rows that changed ----
-        std::atomic<size_t> next{0};
-        std::atomic<int> err{HNSW_OK};
-        std::vector<NodeID> fallback;
-        std::mutex fb_mu;
-        for (auto &dv : dirty_t) dv.clear();
-        stamps.next_batch();
-        auto work = [&](unsigned t) {
-            std::vector<std::vector<hx::Dist>> nbrs(L);
-            for (size_t i = next.fetch_add(1); i < B && err.load() == HNSW_OK; i = next.fetch_add(1)) {
-                const NodeID p = batch[i];
-                if (o_st[i] != HNSW_OK) {
-                    std::lock_guard<std::mutex> g(fb_mu);
-                    fallback.push_back(p);
-                    continue;
-                }
-                for (uint32_t l = 0; l < L; l++) {
-                    nbrs[l].clear();
-                    for (uint32_t k = 0; k < m; k++) {
-                        const uint32_t id = o_ids[(i * L + l) * m + k];
-                        if (id != UINT32_MAX) nbrs[l].push_back(hx::Dist{id, o_d[(i * L + l) * m + k]});
-                    }
-                }
-                const int r = host.connect_point(p, nbrs, &dirty_t[t], &stamps);
-                if (r != HNSW_OK) err.store(r);
-            }
-        };
-        {
-            const unsigned nt = (unsigned)std::min<size_t>(nb_threads, B);
-            if (nt <= 1) {
-                work(0);
-            } else {
-                std::vector<std::thread> th;
-                for (unsigned t = 0; t < nt; t++) th.emplace_back(work, t);
-                for (auto &t : th) t.join();
-            }
-        }
-        if (err.load() != HNSW_OK) return err.load();
-        if (!fallback.empty()) {  // e.g. visited-table overflow: the CPU path serves those points
-            n_fallback += fallback.size();
-            std::sort(fallback.begin(), fallback.end());
-            std::unique_ptr<hx::Inserter, void (*)(hx::Inserter *)> ins(hx::new_inserter(host.len()),
-                                                                         hx::free_inserter);
-            hx::DirtyScope scope(&dirty_t[0], &stamps);
-            for (NodeID p : fallback) {
-                rc = host.insert(p, *ins);
-                if (rc != HNSW_OK) return rc;
-            }
-        }
-        auto t2 = std::chrono::steady_clock::now();
-
-        // ---- changed rows back to HBM (truncated to the stride; the final upload is exact) ----
-        std::vector<uint64_t> dirty0, dirty_up;  // already unique (per-row stamps)
-        for (auto &dv : dirty_t)
-            for (uint64_t key : dv) ((key >> 32) == 0 ? dirty0 : dirty_up).push_back(key);
-        for (int pass = 0; pass < 2; pass++) {  // pass 0: layer 0 rows, pass 1: upper-layer rows
-            const std::vector<uint64_t> &dirty = pass == 0 ? dirty0 : dirty_up;
-            if (dirty.empty()) continue;
-            const uint32_t S = pass == 0 ? v.S0 : v.S1;
-            row_idx.resize(dirty.size());
-            row_data.resize(dirty.size() * (size_t)S);
-            auto pack = [&](size_t lo, size_t hi) {
-                for (size_t i = lo; i < hi; i++) {
-                    const uint32_t layer = (uint32_t)(dirty[i] >> 32);
-                    const NodeID id = (NodeID)dirty[i];
-                    const std::vector<NodeID> &r = host.row(layer, id);
-                    row_idx[i] = layer == 0 ? id : host.upper_base[id] + layer - 1;
-                    uint32_t *o = &row_data[i * (size_t)S];
-                    const size_t k = std::min<size_t>(r.size(), S);
-                    std::copy(r.begin(), r.begin() + k, o);
-                    std::fill(o + k, o + S, UINT32_MAX);
-                }
-            };
-            const unsigned nt = (unsigned)std::min<size_t>(nb_threads, std::max<size_t>(1, dirty.size() / 4096));
-            if (nt <= 1) {
-                pack(0, dirty.size());
-            } else {
-                std::vector<std::thread> th;
-                for (unsigned t = 0; t < nt; t++)
-                    th.emplace_back(pack, dirty.size() * t / nt, dirty.size() * (t + 1) / nt);
-                for (auto &t : th) t.join();
-            }
-            if (row_idx.size() > row_cap) {
-                row_cap = row_idx.size() * 2;
-                if (dRowIdx.p) (void)hipFree(dRowIdx.p);
-                if (dRowData.p) (void)hipFree(dRowData.p);
-                dRowIdx.p = dRowData.p = nullptr;
-                if ((rc = dRowIdx.alloc(row_cap * 4)) ||
-                    (rc = dRowData.alloc(row_cap * (size_t)std::max(v.S0, v.S1) * 4)))
-                    return rc;
-            }
-            HIP_TRY(hipMemcpy(dRowIdx.p, row_idx.data(), row_idx.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(dRowData.p, row_data.data(), row_data.size() * 4, hipMemcpyHostToDevice));
-            rc = hx::launch_scatter_rows(pass == 0 ? h->dev.adj0_mut() : h->dev.adj_up_mut(), S,
-                                         dRowIdx.as<uint32_t>(), dRowData.as<uint32_t>(),
-                                         (uint32_t)row_idx.size(), nullptr);
-            if (rc != HNSW_OK) return rc;
-            HIP_TRY(hipDeviceSynchronize());  // the staging buffers are reused by the next pass
-        }
-        HIP_TRY(hipDeviceSynchronize());
-        auto t3 = std::chrono::steady_clock::now();
-        t_gpu += std::chrono::duration<double>(t1 - t0).count();
-        t_host += std::chrono::duration<double>(t2 - t1).count();
-        t_sync += std::chrono::duration<double>(t3 - t2).count();
-        pos += B;
-        connected += B;
-        n_batches++;
-        if (verbose && (n_batches % 16 == 0 || pos == order.size()))
-            fprintf(stderr, "\rBuilding HNSW index on the GPU %zu/%zu", pos, order.size());
-    }
-    if (verbose) {
-        const double tot = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-        fprintf(stderr,
-                "\non-device build: %zu batches in %.2f s (insert kernel + copies %.2f s, host connect %.2f s, "
-                "row scatter %.2f s), %zu points took the CPU path\n",
-                n_batches, tot, t_gpu, t_host, t_sync, n_fallback);
-    }
-    host.version++;  // the search snapshot (overflow CSR, inline rows) is rebuilt by the next upload
-    return HNSW_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// On-device build, connect step on the GPU as well (option "gpu_build" = 2).  Per batch:
-//   phase 1  hx_insert_kernel  -- as above; additionally writes the new point's own rows and appends
-//                                 one reverse-edge request (target n, source p, layer, d) per selected
-//                                 neighbour
-//   host     sort the requests by (layer, target)                       [a few ms per batch]
-//   phase 2  hx_connect_kernel -- one wave per target row: append, or prune to the cap's nearest;
-//                                 reports the edges that fell out
-//   host     sort the removals by (layer, x)
-//   phase 3  hx_remove_kernel  -- one wave per row that lost a reverse edge (keeps a last edge)
-// Every adjacency row is owned by one wave per phase: no locks, deterministic for a given batch
-// schedule.  The host graph is rebuilt from the device arrays once, at the end.
-// ---------------------------------------------------------------------------------------------
-// The device rows of the full on-device build hold at most `cap` neighbours.  A row the CPU path left
-// longer than that (the reference's transient overflow) is pruned here the way the next
-// prune_connections would: nearest `cap` by (dist, id), reverse edges removed.  Where the dropped
-// edge is the other node's last one it stays on that side (graph.rs:85-94); the pruned side gets it
-// back after the build (`restore`: hx_edge_key(layer, x, node)), exactly like a refusal of hx_remove_kernel.
-void clamp_rows_to_cap(hx::HostIndex &host, std::vector<uint64_t> *restore) {
-    using hx::NodeID;
-    for (uint32_t l = 0; l < host.nb_layers(); l++) {
-        const size_t cap = (size_t)host.layer_m(l);
-        for (NodeID id : host.layer_nodes[l]) {
-            std::vector<NodeID> &row = host.row(l, id);
-            if (row.size() <= cap) continue;
-            hx::PointView a, b;
-            host.get_point(id, &a);
-            std::vector<hx::Dist> ds;
-            for (NodeID x : row) {
-                host.get_point(x, &b);
-                ds.push_back(hx::Dist{x, host.dist2other(a, b)});
-            }
-            std::sort(ds.begin(), ds.end(), hx::dist_lt);
-            for (size_t i = cap; i < ds.size(); i++) {
-                std::vector<NodeID> &back = host.row(l, ds[i].id);
-                if (back.size() == 1 && back[0] == id)
-                    restore->push_back(hx::hx_edge_key(l, ds[i].id, id));
-                else
-                    back.erase(std::remove(back.begin(), back.end(), id), back.end());
-            }
-            row.clear();
-            for (size_t i = 0; i < cap; i++) row.push_back(ds[i].id);
-        }
-    }
-}
-
-// Sharded build (BASELINE configs[4]): every rank holds the full replica.  The insertion searches of a batch are
-// split over the ranks by position, and what they produce travels as edge records through an all-gather (the
-// caller's collective, RCCL in production); the record list carries the whole batch (own rows included,
-// InsertArgs::emit_own) and its sort makes the order canonical.  Phases 2 / 3 are split by ROW: every rank sees
-// every record, the rank that owns a row (node id % world) appends / prunes / drops in it -- each row's outcome
-// depends on that row and its records alone, so the split changes nothing -- the removals phase 2 files are
-// all-gathered between the two phases, and the rows an owner changed travel to the other replicas as whole rows of
-// ids at the end of the batch (hx_pack_rows_kernel / hx_apply_rows_kernel).  Five collectives per batch (records;
-// removal counts + removals; row counts + rows -- the count exchanges are 64 B per rank and carry the rank's status,
-// so the ranks stop together), the replicas identical after each.  HNSW_MI355X_SHARD_CONNECT=0: phases 2 / 3 on
-// every rank in full, as before round 4 (one collective per batch).
-struct ShardCtx {
-    uint32_t rank, world;
-    unsigned char *d_send, *d_recv;  // one slot / world slots of slot_bytes
-    uint64_t slot_bytes;
-    hnsw_allgather_fn allgather;
-    void *ctx;
-};
-// SH_BCAP: the largest batch (option gpu_build_batch_max, default 8192); buffers and exchange slots are sized for it
-constexpr uint32_t SH_HEADER = 64, SH_FAILCAP = 1024, SH_BCAP = 32768;
-inline uint32_t shard_slot_records(uint32_t m, uint32_t world) {
-    return ((SH_BCAP + world - 1) / world) * m * 4;  // both directions, 2 x slack for upper layers
-}
-inline uint64_t shard_record_bytes(uint32_t m, uint32_t world) {  // the records' part of a slot: [header][failed ids][keys][vals]
-    return ((uint64_t)SH_HEADER + SH_FAILCAP * 4 + (uint64_t)shard_slot_records(m, world) * 12 + 255) & ~255ull;
-}
-// rows one rank may change in a batch (its share of the targets of every rank's records, plus the rows it drops from)
-inline uint32_t shard_slot_rows(uint32_t m, uint32_t world) { return 2 * shard_slot_records(m, world); }
-inline uint32_t shard_ship_slots(uint32_t m) { return hx::adj_stride(2ull * m, 32); }  // ids per shipped row: a layer-0 row
-inline uint64_t shard_slot_bytes(uint32_t m, uint32_t world) {
-    const uint64_t rows = (uint64_t)SH_HEADER + (uint64_t)shard_slot_rows(m, world) * (8 + 4ull * shard_ship_slots(m));
-    return (std::max(shard_record_bytes(m, world), rows) + 255) & ~255ull;
-}
-
-int gpu_insert_bulk_full(hnsw_index *h, const float *rows, uint64_t n, uint32_t nb_threads, int verbose,
-                         const uint8_t *levels, const ShardCtx *sh = nullptr) {
-    using hx::NodeID;
-    hx::HostIndex &host = *h->host;
-    if (nb_threads == 0) nb_threads = 1;
-    if (host.params.m > 128 || host.params.ef_cons > 512) {
-        set_error("on-device build supports m <= 128 and ef_construction <= 512");
-        return HNSW_ERR_ARG;
-    }
-    if (host.len() + n >= (1ull << hx::HX_EDGE_ID_BITS)) {  // edge records carry 30-bit ids
-        if (sh) {
-            set_error("sharded build: ids must stay below 2^30");
-            return HNSW_ERR_ARG;
-        }
-        return gpu_insert_bulk(h, rows, n, nb_threads, verbose, levels);
-    }
-    const uint64_t n_before = host.len();
-    std::vector<NodeID> ids;
-    const auto t_enter = std::chrono::steady_clock::now();
-    int rc = host.store_points(rows, n, levels, &ids, nb_threads, /*reserve_rows=*/false);
-    if (rc != HNSW_OK) return rc;
-    const auto t_stored = std::chrono::steady_clock::now();
-    host.prepare_build();
-    const auto t_prep = std::chrono::steady_clock::now();
-    const std::vector<NodeID> order = insertion_order(host, ids);
-    const auto t_ordered = std::chrono::steady_clock::now();
-    const uint64_t SEED = 2048;
-    size_t pos = 0;
-    std::unique_ptr<hx::Inserter, void (*)(hx::Inserter *)> ins(hx::new_inserter(host.len()), hx::free_inserter);
-    if (verbose)
-        fprintf(stderr, "host phases before the seed: store_points %.2f s, locks %.2f s, order %.2f s, inserter %.2f s\n",
-                std::chrono::duration<double>(t_stored - t_enter).count(), std::chrono::duration<double>(t_prep - t_stored).count(),
-                std::chrono::duration<double>(t_ordered - t_prep).count(),
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t_ordered).count());
-    // The first points are inserted one after the other on the host (the graph depends on it).  Unless they are all
-    // there is to insert, that runs WHILE the vector rows travel to HBM (DeviceIndex::upload's side job): the rows are
-    // immutable once stored, the adjacency -- which the seed writes -- is packed after the seed has finished.
-    const size_t take = n_before < SEED ? std::min<size_t>(order.size(), SEED - n_before) : 0;
-    std::vector<uint64_t> restore;
-    auto seed_and_clamp = [&]() -> int {
-        for (size_t i = 0; i < take; i++) {
-            const int r = host.insert(order[i], *ins);
-            if (r != HNSW_OK) return r;
-        }
-        clamp_rows_to_cap(host, &restore);
-        return HNSW_OK;
-    };
-    if (take == order.size() || host.nb_layers() > 16) {  // nothing for the device (edge records carry 4-bit layers)
-        for (; pos < order.size(); pos++) {
-            rc = host.insert(order[pos], *ins);
-            if (rc != HNSW_OK) return rc;
-        }
-        host.version++;
-        return HNSW_OK;
-    }
-    pos = take;
-    const auto t_start = std::chrono::steady_clock::now();
-    const auto t_clamped = t_start;
-    const int saved_inline = h->dev.inline_rows;
-    h->dev.inline_rows = 0;
-    h->dev.release();
-    rc = h->dev.upload(host, h->device, seed_and_clamp);
-    h->dev.inline_rows = saved_inline;
-    if (rc != HNSW_OK) return rc;
-    h->device = h->dev.device;
-    HIP_TRY(hipSetDevice(h->dev.device));
-    const auto t_uploaded = std::chrono::steady_clock::now();
-    hx::DevView v = h->dev.view;
-    const uint32_t m = (uint32_t)host.params.m, L = host.nb_layers();
-    const uint32_t BMAX = SH_BCAP;
-    // a point has 1 + 1/(m-1) layers on average; sharded: records in both directions
-    const uint32_t W = sh ? sh->world : 1, SLOT_REC = sh ? shard_slot_records(m, W) : 0;
-    // Record capacity: what the largest batch of this build can file, (level + 1) * m per point (twice
-    // that with records in both directions) -- not an average: a batch of high-level points files more than
-    // 2 m each.  Sharded: the caller's slots are sized by m and the world alone; a point whose records do
-    // not fit its rank's slot fails cleanly on the device (nothing reserved) and takes the CPU path.
-    uint64_t need_max = 0;
-    if (!sh) {
-        uint64_t c = n_before + pos;
-        for (size_t q = pos; q < order.size();) {
-            const size_t Bq = std::min<size_t>(order.size() - q, std::min<uint64_t>(std::min<uint64_t>(BMAX, h->build_batch_max), std::max<uint64_t>(64, c / h->build_batch_div)));
-            uint64_t need = 0;
-            for (size_t i = 0; i < Bq; i++) need += ((uint64_t)host.levels[order[q + i]] + 1) * m;
-            need_max = std::max(need_max, need);
-            q += Bq;
-            c += Bq;
-        }
-        if (need_max >= (1ull << 31)) {
-            set_error("on-device build: a batch would file %llu edge records", (unsigned long long)need_max);
-            return HNSW_ERR_ARG;
-        }
-    }
-    const uint32_t REQ_CAP = sh ? W * SLOT_REC : (uint32_t)std::max<uint64_t>(need_max, (uint64_t)BMAX * m * 2);
-    if (sh && (sh->slot_bytes < shard_slot_bytes(m, W) || sh->rank >= W || !sh->d_send || !sh->d_recv || !sh->allgather)) {
-        set_error("sharded build: exchange buffers too small or bad rank / world");
-        return HNSW_ERR_ARG;
-    }
-    const uint32_t REF_CAP = 1u << 20;      // kept-last-edge records of the whole build
-    const size_t temp_bytes = hx::sort_temp_bytes(REQ_CAP);
-    const uint64_t REC_BYTES = sh ? shard_record_bytes(m, W) : 0;
-    // phases 2 / 3 split by row ownership (ShardCtx above)
-    static const bool shard_connect_on = !(getenv("HNSW_MI355X_SHARD_CONNECT") && atoi(getenv("HNSW_MI355X_SHARD_CONNECT")) == 0);
-    const bool own_rows = sh && W > 1 && shard_connect_on;
-    const uint32_t CHG_CAP = own_rows ? shard_slot_rows(m, W) : 0, SHIP = shard_ship_slots(m);
-    const uint64_t SHIP_UNIT = 8 + 4ull * SHIP;
-    if (own_rows && (v.S0 > SHIP || v.S1 > SHIP)) {
-        set_error("sharded build: adjacency rows of %u / %u slots, exchange entries of %u", v.S0, v.S1, SHIP);
-        return HNSW_ERR_ARG;
-    }
-    // the file of changed rows: HX_CHG_LISTS lists (ConnectArgs), each with room for twice its even share
-    const uint32_t CHG_LIST_CAP = own_rows ? 2 * ((CHG_CAP + hx::HX_CHG_LISTS - 1) / hx::HX_CHG_LISTS) : 0;
-    DevBuf dLevels, dIds, dOutIds, dOutD, dStatus, dCnt, dKeyA, dKeyB, dValA, dValB, dTemp, dRef, dRead, dChg, dChgCnt;
-    if (own_rows && ((rc = dChg.alloc((size_t)CHG_LIST_CAP * hx::HX_CHG_LISTS * 8)) || (rc = dChgCnt.alloc(hx::HX_CHG_LISTS * 4)))) return rc;
-    // One variable-size exchange: 64 B per rank first ([count, status]: every rank learns every count and stops
-    // with the others when one of them failed), then the largest count's worth of bytes per rank.  `d_src` is copied
-    // behind the header (nullptr: the data is in the slot already).  Rank r's data: d_recv + r * stride + SH_HEADER.
-    std::vector<uint32_t> x_counts(W);
-    uint64_t x_stride = 0;
-    double t_exchange = 0;
-    uint64_t x_bytes = 0;
-    auto exchange = [&](uint32_t count, uint64_t unit, int32_t status, const void *d_src, const char *what) -> int {
-        const auto tx0 = std::chrono::steady_clock::now();
-        if ((uint64_t)SH_HEADER + count * unit > sh->slot_bytes && status == 0) status = HNSW_ERR_OVERFLOW;
-        uint32_t hdr[SH_HEADER / 4] = {0};
-        hdr[0] = status ? 0 : count;
-        hdr[1] = (uint32_t)status;
-        HIP_TRY(hipMemcpy(sh->d_send, hdr, SH_HEADER, hipMemcpyHostToDevice));
-        if (d_src && hdr[0])
-            HIP_TRY(hipMemcpyAsync(sh->d_send + SH_HEADER, d_src, hdr[0] * unit, hipMemcpyDeviceToDevice, nullptr));
-        HIP_TRY(hipDeviceSynchronize());
-        int r = sh->allgather(sh->ctx, SH_HEADER);
-        if (r != 0) {
-            set_error("sharded build: the all-gather callback failed (%d) on the %s counts", r, what);
-            return HNSW_ERR_RCCL;
-        }
-        std::vector<uint32_t> all((size_t)W * SH_HEADER / 4);
-        HIP_TRY(hipMemcpy(all.data(), sh->d_recv, (size_t)W * SH_HEADER, hipMemcpyDeviceToHost));
-        uint32_t maxc = 0;
-        for (uint32_t k = 0; k < W; k++) {
-            if (all[k * (SH_HEADER / 4) + 1] != 0) {
-                set_error("sharded build: rank %u reported status %d in the %s phase", k, (int)all[k * (SH_HEADER / 4) + 1], what);
-                return (int)all[k * (SH_HEADER / 4) + 1];
-            }
-            x_counts[k] = all[k * (SH_HEADER / 4)];
-            maxc = std::max(maxc, x_counts[k]);
-        }
-        x_stride = (SH_HEADER + maxc * unit + 63) & ~63ull;
-        if (x_stride > sh->slot_bytes) {  // cannot happen with honest peers (each checked its own count above)
-            set_error("sharded build: a rank announced %u %s, beyond the slot", maxc, what);
-            return HNSW_ERR_OVERFLOW;
-        }
-        if (maxc) {
-            r = sh->allgather(sh->ctx, x_stride);
-            if (r != 0) {
-                set_error("sharded build: the all-gather callback failed (%d) on the %s", r, what);
-                return HNSW_ERR_RCCL;
-            }
-            x_bytes += x_stride * W;
-        }
-        t_exchange += std::chrono::duration<double>(std::chrono::steady_clock::now() - tx0).count();
-        return HNSW_OK;
-    };
-    struct EvPair {  // the insert kernel's launches are timed with HIP events on their stream
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EvPair() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } ev, ev_conn, ev_rem;
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventCreate(&ev_conn.a));
-    HIP_TRY(hipEventCreate(&ev_conn.b));
-    HIP_TRY(hipEventCreate(&ev_rem.a));
-    HIP_TRY(hipEventCreate(&ev_rem.b));
-    double t_kernel_ms = 0, t_conn_kernel_ms = 0;
-    bool rem_pending = false;
-    auto collect_remove_time = [&]() -> int {  // the drop kernel of the previous batch (nothing waits for it in-batch)
-        if (!rem_pending) return HNSW_OK;
-        HIP_TRY(hipEventSynchronize(ev_rem.b));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev_rem.a, ev_rem.b));
-        t_conn_kernel_ms += ms;
-        rem_pending = false;
-        return HNSW_OK;
-    };
-    if ((rc = dRead.alloc(32))) return rc;
-    HIP_TRY(hipMemset(dRead.p, 0, 32));
-    if ((rc = dLevels.alloc(host.len())) || (rc = dIds.alloc(BMAX * 4)) ||
-        (rc = dOutIds.alloc((size_t)BMAX * L * m * 4)) || (rc = dOutD.alloc((size_t)BMAX * L * m * 4)) ||
-        (rc = dStatus.alloc(BMAX * 4)) || (rc = dCnt.alloc(64)) || (rc = dKeyA.alloc((size_t)REQ_CAP * 8)) ||
-        (rc = dKeyB.alloc((size_t)REQ_CAP * 8)) || (rc = dValA.alloc((size_t)REQ_CAP * 4)) ||
-        (rc = dValB.alloc((size_t)REQ_CAP * 4)) || (rc = dTemp.alloc(temp_bytes)) ||
-        (rc = dRef.alloc((size_t)REF_CAP * 8)))
-        return rc;
-    HIP_TRY(hipMemcpy(dLevels.p, host.levels.data(), host.len(), hipMemcpyHostToDevice));
-    // the edges' distances beside the adjacency for the length of this build (ConnectArgs: a prune then evaluates
-    // nothing); 0xFFFFFFFF = not known yet (the rows that predate this build: evaluated at their first prune).  128 B
-    // per point at m = 16; without the memory for it the build runs as before
-    DevBuf dAdjD0, dAdjDUp;
-    uint32_t *adjd0 = nullptr, *adjd_up = nullptr;
-    {
-        static const bool keep_dists = !(getenv("HNSW_MI355X_BUILD_EDGE_DISTS") && atoi(getenv("HNSW_MI355X_BUILD_EDGE_DISTS")) == 0);
-        const size_t b0 = (size_t)host.len() * v.S0 * 4, b1 = std::max<size_t>(1, host.adj_up.size()) * v.S1 * 4;
-        if (keep_dists && hipMalloc(&dAdjD0.p, b0) == hipSuccess && hipMalloc(&dAdjDUp.p, b1) == hipSuccess &&
-            hipMemset(dAdjD0.p, 0xFF, b0) == hipSuccess && hipMemset(dAdjDUp.p, 0xFF, b1) == hipSuccess) {
-            adjd0 = dAdjD0.as<uint32_t>();
-            adjd_up = dAdjDUp.as<uint32_t>();
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    // counters: [0] requests, [1] removals, [2] refusals (accumulate over the build), [3] status
-    uint32_t *cnt = dCnt.as<uint32_t>();
-    HIP_TRY(hipMemset(dCnt.p, 0, 64));
-    std::vector<int32_t> o_st(BMAX);
-    std::vector<NodeID> failed;
-    uint64_t connected = n_before + pos;
-    double t_ins = 0, t_conn = 0;
-    size_t n_batches = 0, n_req = 0, n_rem = 0, n_again = 0, n_shipped = 0, n_owned = 0;
-    uint32_t counts[4];
-    // the capacity of the new points' host rows (one small allocation each) is reserved by other threads while the
-    // GPU runs the batches: nothing touches the host graph until the read-back below
-    struct RowReserve {
-        std::thread t;
-        ~RowReserve() {
-            if (t.joinable()) t.join();
-        }
-    } row_reserve;
-    {
-        hx::HostIndex *hp = &host;
-        const NodeID first_new = (NodeID)n_before;
-        const uint32_t threads = std::max(1u, nb_threads / 2);
-        row_reserve.t = std::thread([hp, first_new, n, threads] { hp->reserve_layer0_rows(first_new, n, threads); });
-    }
-    const auto t_loop0 = std::chrono::steady_clock::now();
-
-    while (pos < order.size()) {
-        const size_t B = std::min<size_t>(order.size() - pos,
-                                          std::min<uint64_t>(std::min<uint64_t>(BMAX, h->build_batch_max), std::max<uint64_t>(64, connected / h->build_batch_div)));
-        const NodeID *batch = &order[pos];
-        auto t0 = std::chrono::steady_clock::now();
-        if ((rc = collect_remove_time())) return rc;
-        // this rank's slice of the batch (everything when not sharded)
-        const size_t s_lo = sh ? B * sh->rank / W : 0, s_hi = sh ? B * (sh->rank + 1) / W : B, nb = s_hi - s_lo;
-        if (nb) HIP_TRY(hipMemcpy(dIds.p, batch + s_lo, nb * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(dCnt.p, 0, 8));  // requests, removals
-        if (own_rows) HIP_TRY(hipMemset(dChgCnt.p, 0, hx::HX_CHG_LISTS * 4));  // rows this rank changed
-        // ---- phase 1: searches + heuristic, own rows, requests ----
-        hx::InsertArgs a{};
-        a.point_ids = dIds.as<uint32_t>();
-        a.levels = dLevels.as<uint8_t>();
-        a.ef_cons = (uint32_t)host.params.ef_cons;
-        a.m = m;
-        a.max_layers = L;
-        a.out_ids = dOutIds.as<uint32_t>();
-        a.out_dists = dOutD.as<float>();
-        a.out_status = dStatus.as<int32_t>();
-        a.adj0_mut = h->dev.adj0_mut();
-        a.adj_up_mut = h->dev.adj_up_mut();
-        a.adjd0_mut = adjd0;
-        a.adjd_up_mut = adjd_up;
-        a.counters = dRead.as<unsigned long long>();
-        uint32_t nreq = 0, nreq_all = 0;  // records this rank sorts and applies; records of the batch
-        auto timed_insert = [&](uint32_t nblocks, int adjust) -> int {
-            HIP_TRY(hipEventRecord(ev.a, nullptr));
-            const int r = hx::launch_insert(v, a, nblocks, nullptr, adjust);
-            if (r != HNSW_OK) return r;
-            HIP_TRY(hipEventRecord(ev.b, nullptr));
-            HIP_TRY(hipEventSynchronize(ev.b));
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-            t_kernel_ms += ms;
-            return HNSW_OK;
-        };
-        if (!sh) {
-            a.req_keys = dKeyA.as<uint64_t>();
-            a.req_vals = dValA.as<uint32_t>();
-            a.req_count = cnt + 0;
-            a.req_fail_base = cnt + 4;
-            a.req_cap = REQ_CAP;
-            HIP_TRY(hipMemset(cnt + 4, 0xFF, 4));  // no reservation has failed yet
-            const int first_adjust = hx::insert_table_first_adjust(v, a);
-            rc = timed_insert((uint32_t)nb, first_adjust);
-            if (rc != HNSW_OK) return rc;
-            uint32_t c5[5];
-            HIP_TRY(hipMemcpy(c5, dCnt.p, 20, hipMemcpyDeviceToHost));  // synchronises
-            HIP_TRY(hipMemcpy(o_st.data(), dStatus.p, nb * 4, hipMemcpyDeviceToHost));
-            // A point that filled its visited table filed nothing: it runs again in this batch with a larger
-            // table (the result of a search does not depend on the table's size, and the points of a batch do
-            // not see each other anyway).  Not when a reservation failed: then the counter is past the capacity.
-            std::vector<NodeID> again;
-            for (size_t i = 0; i < nb; i++) {
-                if (o_st[i] == HNSW_OK) continue;
-                if (o_st[i] == HNSW_ERR_OVERFLOW && c5[4] == UINT32_MAX) {
-                    again.push_back(batch[i]);
-                } else {
-                    failed.push_back(batch[i]);  // filed nothing; CPU path after the build
-                }
-            }
-            if (!again.empty()) {
-                HIP_TRY(hipMemcpy(dIds.p, again.data(), again.size() * 4, hipMemcpyHostToDevice));
-                rc = timed_insert((uint32_t)again.size(), std::max(first_adjust, 0) + 1);
-                if (rc != HNSW_OK) return rc;
-                HIP_TRY(hipMemcpy(c5, dCnt.p, 20, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(o_st.data(), dStatus.p, again.size() * 4, hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < again.size(); i++)
-                    if (o_st[i] != HNSW_OK) failed.push_back(again[i]);
-                n_again += again.size();
-            }
-            memcpy(counts, c5, 16);
-            // the records written: everything reserved, or the prefix below the first reservation that did not fit
-            nreq = std::min(c5[0], c5[4]);
-            if (nreq > REQ_CAP) {
-                set_error("on-device build: record counter %u beyond the capacity %u", nreq, REQ_CAP);
-                return HNSW_ERR_OVERFLOW;
-            }
-            nreq_all = nreq;
-        } else {
-            // the slot: [count, nfail, ...64 B][failed ids][keys][vals]
-            unsigned char *slot = sh->d_send;
-            uint32_t *hdr = reinterpret_cast<uint32_t *>(slot);
-            uint32_t *fail_ids = reinterpret_cast<uint32_t *>(slot + SH_HEADER);
-            const size_t o_keys = SH_HEADER + SH_FAILCAP * 4, o_vals = o_keys + (size_t)SLOT_REC * 8;
-            HIP_TRY(hipMemset(slot, 0, SH_HEADER));
-            HIP_TRY(hipMemset(hdr + 2, 0xFF, 4));  // header: [count, nfail, first failing base, ...]
-            a.req_keys = reinterpret_cast<uint64_t *>(slot + o_keys);
-            a.req_vals = reinterpret_cast<uint32_t *>(slot + o_vals);
-            a.req_count = hdr;
-            a.req_fail_base = hdr + 2;
-            a.req_cap = SLOT_REC;
-            a.emit_own = 1;
-            const int first_adjust = hx::insert_table_first_adjust(v, a);
-            if (nb) rc = timed_insert((uint32_t)nb, first_adjust);
-            if (rc != HNSW_OK) return rc;
-            if (nb) HIP_TRY(hipMemcpy(o_st.data(), dStatus.p, nb * 4, hipMemcpyDeviceToHost));  // synchronises
-            std::vector<uint32_t> myfail, again;
-            uint32_t h3a[3] = {0, 0, UINT32_MAX};
-            if (nb) HIP_TRY(hipMemcpy(h3a, hdr, 12, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < nb; i++) {
-                if (o_st[i] == HNSW_OK) continue;
-                if (o_st[i] == HNSW_ERR_OVERFLOW && h3a[2] == UINT32_MAX) {
-                    again.push_back(batch[s_lo + i]);  // filled its visited table: once more with a larger one
-                } else {
-                    myfail.push_back(batch[s_lo + i]);
-                }
-            }
-            if (!again.empty()) {
-                HIP_TRY(hipMemcpy(dIds.p, again.data(), again.size() * 4, hipMemcpyHostToDevice));
-                rc = timed_insert((uint32_t)again.size(), std::max(first_adjust, 0) + 1);
-                if (rc != HNSW_OK) return rc;
-                HIP_TRY(hipMemcpy(o_st.data(), dStatus.p, again.size() * 4, hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < again.size(); i++)
-                    if (o_st[i] != HNSW_OK) myfail.push_back(again[i]);
-                n_again += again.size();
-            }
-            if (myfail.size() > SH_FAILCAP) {
-                set_error("sharded build: %zu points of one batch failed on the device", myfail.size());
-                return HNSW_ERR_OVERFLOW;
-            }
-            const uint32_t nf = (uint32_t)myfail.size();
-            {  // the count the other ranks read: the records really written (see hx_insert_kernel's reservation)
-                uint32_t h3[3];
-                HIP_TRY(hipMemcpy(h3, hdr, 12, hipMemcpyDeviceToHost));
-                const uint32_t written = std::min(h3[0], h3[2]);
-                if (written != h3[0]) HIP_TRY(hipMemcpy(hdr, &written, 4, hipMemcpyHostToDevice));
-            }
-            HIP_TRY(hipMemcpy(hdr + 1, &nf, 4, hipMemcpyHostToDevice));
-            if (nf) HIP_TRY(hipMemcpy(fail_ids, myfail.data(), nf * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipDeviceSynchronize());
-            // ---- the one exchange of the batch ----
-            rc = sh->allgather(sh->ctx, REC_BYTES);
-            if (rc != 0) {
-                set_error("sharded build: the all-gather callback failed (%d)", rc);
-                return HNSW_ERR_RCCL;
-            }
-            // concatenate the slots' records; every rank sees the same list
-            for (uint32_t r = 0; r < W; r++) {
-                const unsigned char *rs = sh->d_recv + (size_t)r * REC_BYTES;
-                uint32_t rh[2];
-                HIP_TRY(hipMemcpy(rh, rs, 8, hipMemcpyDeviceToHost));
-                if (rh[0] > SLOT_REC || rh[1] > SH_FAILCAP || nreq + rh[0] > REQ_CAP) {
-                    set_error("sharded build: malformed slot from rank %u", r);
-                    return HNSW_ERR_ARG;
-                }
-                if (rh[1]) {
-                    std::vector<uint32_t> f(rh[1]);
-                    HIP_TRY(hipMemcpy(f.data(), rs + SH_HEADER, rh[1] * 4, hipMemcpyDeviceToHost));
-                    failed.insert(failed.end(), f.begin(), f.end());
-                }
-                if (rh[0] && own_rows) {
-                    // this rank's share of the slot's records: the rows it owns (the others' never reach its sort)
-                    rc = hx::filter_edge_records(reinterpret_cast<const uint64_t *>(rs + o_keys), reinterpret_cast<const uint32_t *>(rs + o_vals),
-                                                 rh[0], sh->rank, W, dKeyA.as<uint64_t>(), dValA.as<uint32_t>(), cnt + 0, REQ_CAP,
-                                                 reinterpret_cast<int32_t *>(cnt + 3), nullptr);
-                    if (rc != HNSW_OK) return rc;
-                } else if (rh[0]) {
-                    HIP_TRY(hipMemcpyAsync(dKeyA.as<uint64_t>() + nreq, rs + o_keys, (size_t)rh[0] * 8,
-                                           hipMemcpyDeviceToDevice, nullptr));
-                    HIP_TRY(hipMemcpyAsync(dValA.as<uint32_t>() + nreq, rs + o_vals, (size_t)rh[0] * 4,
-                                           hipMemcpyDeviceToDevice, nullptr));
-                }
-                nreq += rh[0];
-            }
-            nreq_all = nreq;
-            if (own_rows) HIP_TRY(hipMemcpy(&nreq, cnt + 0, 4, hipMemcpyDeviceToHost));  // (the counter was zeroed with the batch)
-        }
-        auto t1 = std::chrono::steady_clock::now();
-        // ---- phase 2: group by target row (radix sort), append / prune ----
-        rc = hx::sort_edge_pairs(dTemp.p, temp_bytes, dKeyA.as<uint64_t>(), dKeyB.as<uint64_t>(),
-                                 dValA.as<uint32_t>(), dValB.as<uint32_t>(), nreq, L, nullptr);
-        if (rc != HNSW_OK) return rc;
-        hx::ConnectArgs ca{};
-        ca.keys = dKeyB.as<uint64_t>();
-        ca.vals = dValB.as<uint32_t>();
-        ca.count = nreq;
-        ca.m = m;
-        ca.adj0_mut = h->dev.adj0_mut();
-        ca.adj_up_mut = h->dev.adj_up_mut();
-        ca.adjd0_mut = adjd0;
-        ca.adjd_up_mut = adjd_up;
-        ca.out_keys = dKeyA.as<uint64_t>();  // the unsorted requests are dead by now
-        ca.out_count = cnt + 1;
-        ca.out_cap = REQ_CAP;
-        ca.status = reinterpret_cast<int32_t *>(cnt + 3);
-        if (own_rows) {
-            ca.own_rank = sh->rank;
-            ca.own_world = W;
-            ca.chg_keys = dChg.as<uint64_t>();
-            ca.chg_count = dChgCnt.as<uint32_t>();
-            ca.chg_cap = CHG_LIST_CAP;
-        }
-        HIP_TRY(hipEventRecord(ev_conn.a, nullptr));
-        rc = hx::launch_connect(v, ca, nullptr);
-        if (rc != HNSW_OK) return rc;
-        HIP_TRY(hipEventRecord(ev_conn.b, nullptr));
-        HIP_TRY(hipMemcpy(counts, dCnt.p, 16, hipMemcpyDeviceToHost));
-        {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ev_conn.a, ev_conn.b));
-            t_conn_kernel_ms += ms;
-        }
-        if (counts[3] != 0 && !own_rows) {
-            set_error("on-device build: connect kernel reported status %d in batch %zu", (int)counts[3], n_batches);
-            return (int)counts[3];
-        }
-        uint32_t nrem = counts[1], nrem_all = counts[1];
-        if (own_rows) {
-            // the removals of every owner's prunes, in every rank's list (phase 3 filters by the owner of the row
-            // that loses the edge); the sort below makes the order canonical
-            const int32_t st = counts[3] != 0 ? (int32_t)counts[3] : (nrem > REQ_CAP ? HNSW_ERR_OVERFLOW : 0);
-            rc = exchange(st ? 0 : nrem, 8, st, dKeyA.p, "removals");
-            if (rc != HNSW_OK) return rc;
-            uint64_t tot = 0;
-            for (uint32_t r = 0; r < W; r++) tot += x_counts[r];
-            if (tot > REQ_CAP) {
-                set_error("sharded build: %llu removals in one batch, room for %u", (unsigned long long)tot, REQ_CAP);
-                return HNSW_ERR_OVERFLOW;
-            }
-            // ... of which this rank sorts and applies those that drop from a row it owns
-            HIP_TRY(hipMemset(cnt + 1, 0, 4));
-            for (uint32_t r = 0; r < W; r++) {
-                if (x_counts[r] == 0) continue;
-                rc = hx::filter_edge_records(reinterpret_cast<const uint64_t *>(sh->d_recv + (size_t)r * x_stride + SH_HEADER), nullptr,
-                                             x_counts[r], sh->rank, W, dKeyA.as<uint64_t>(), nullptr, cnt + 1, REQ_CAP,
-                                             reinterpret_cast<int32_t *>(cnt + 3), nullptr);
-                if (rc != HNSW_OK) return rc;
-            }
-            nrem_all = (uint32_t)tot;
-            HIP_TRY(hipMemcpy(&nrem, cnt + 1, 4, hipMemcpyDeviceToHost));
-        }
-        // ---- phase 3: group the removals by row, drop the reverse edges ----
-        rc = hx::sort_edge_keys(dTemp.p, temp_bytes, dKeyA.as<uint64_t>(), dKeyB.as<uint64_t>(), nrem, L, nullptr);
-        if (rc != HNSW_OK) return rc;
-        ca.keys = dKeyB.as<uint64_t>();
-        ca.vals = nullptr;
-        ca.count = nrem;
-        ca.out_keys = dRef.as<uint64_t>();
-        ca.out_count = cnt + 2;
-        ca.out_cap = REF_CAP;
-        HIP_TRY(hipEventRecord(ev_rem.a, nullptr));
-        rc = hx::launch_remove(v, ca, nullptr);
-        if (rc != HNSW_OK) return rc;
-        HIP_TRY(hipEventRecord(ev_rem.b, nullptr));
-        rem_pending = true;
-        if (own_rows) {
-            // ---- the rows this rank changed, to the other replicas ----
-            uint32_t c4[4], lists[hx::HX_CHG_LISTS];
-            HIP_TRY(hipMemcpy(lists, dChgCnt.p, sizeof(lists), hipMemcpyDeviceToHost));  // synchronises
-            HIP_TRY(hipMemcpy(c4, dCnt.p, 16, hipMemcpyDeviceToHost));
-            int32_t st = (int32_t)c4[3];
-            uint64_t nchg64 = 0;
-            uint32_t longest = 0;
-            for (uint32_t c : lists) {
-                nchg64 += c;
-                longest = std::max(longest, c);
-            }
-            if (st == 0 && (longest > CHG_LIST_CAP || nchg64 > CHG_CAP || (uint64_t)SH_HEADER + nchg64 * SHIP_UNIT > sh->slot_bytes))
-                st = HNSW_ERR_OVERFLOW;
-            const uint32_t nchg = st ? 0 : (uint32_t)nchg64;
-            if (st == 0) {
-                rc = hx::launch_pack_rows(v, h->dev.adj0_mut(), h->dev.adj_up_mut(), dChg.as<uint64_t>(), dChgCnt.as<uint32_t>(),
-                                          CHG_LIST_CAP, longest, SHIP, sh->d_send + SH_HEADER, nullptr);
-                if (rc != HNSW_OK) st = rc;
-            }
-            rc = exchange(st ? 0 : nchg, SHIP_UNIT, st, nullptr, "changed rows");
-            if (rc != HNSW_OK) return rc;
-            n_owned += nchg;
-            for (uint32_t r = 0; r < W; r++) {
-                if (r == sh->rank || x_counts[r] == 0) continue;
-                rc = hx::launch_apply_rows(v, h->dev.adj0_mut(), h->dev.adj_up_mut(), sh->d_recv + (size_t)r * x_stride + SH_HEADER,
-                                           x_counts[r], SHIP, reinterpret_cast<int32_t *>(cnt + 3), nullptr);
-                if (rc != HNSW_OK) return rc;
-                n_shipped += x_counts[r];
-            }
-            // the receive buffer is read by those launches: they finish before the next batch's exchange overwrites it
-            HIP_TRY(hipDeviceSynchronize());
-        }
-        if (verbose) HIP_TRY(hipDeviceSynchronize());  // only to attribute the time
-        auto t2 = std::chrono::steady_clock::now();
-        t_ins += std::chrono::duration<double>(t1 - t0).count();
-        t_conn += std::chrono::duration<double>(t2 - t1).count();
-        n_req += nreq_all;
-        n_rem += nrem_all;
-        pos += B;
-        connected += B;
-        n_batches++;
-        if (verbose && (n_batches % 64 == 0 || pos == order.size()))
-            fprintf(stderr, "\rBuilding HNSW index on the GPU %zu/%zu", pos, order.size());
-    }
-
-    if ((rc = collect_remove_time())) return rc;
-    {  // what the build read and how long its kernels ran (hnsw_get_stat "build_*")
-        unsigned long long rd[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpy(rd, dRead.p, 32, hipMemcpyDeviceToHost));
-        hnsw_index::BuildStats &bs = h->build;
-        bs.points += order.size();
-        bs.batches += n_batches;
-        bs.rows_read += rd[0];
-        bs.adj_rows += rd[1];
-        bs.adj_ids += rd[2];
-        bs.records += n_req;
-        bs.removals += n_rem;
-        bs.insert_kernel_s += t_kernel_ms * 1e-3;
-        bs.connect_kernel_s += t_conn_kernel_ms * 1e-3;
-        bs.insert_phase_s += t_ins;
-        bs.connect_s += t_conn;
-        bs.rows_owned += n_owned;
-        bs.rows_received += n_shipped;
-        bs.exchange_bytes += x_bytes;
-        bs.exchange_s += t_exchange;
-    }
-    // ---- the host graph from the device arrays ----
-    if (row_reserve.t.joinable()) row_reserve.t.join();
-    const auto t_sync0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpy(counts, dCnt.p, 16, hipMemcpyDeviceToHost));
-    if (counts[3] != 0 || counts[2] > REF_CAP) {
-        set_error("on-device build: status %d, %u kept-last-edge records", (int)counts[3], counts[2]);
-        return HNSW_ERR_OVERFLOW;
-    }
-    std::vector<uint64_t> refusals(counts[2]);
-    if (counts[2]) HIP_TRY(hipMemcpy(refusals.data(), dRef.p, (size_t)counts[2] * 8, hipMemcpyDeviceToHost));
-    if (own_rows) {  // every owner's kept-last-edge records, on every rank (the host restores the mirror edges below)
-        rc = exchange(counts[2], 8, 0, dRef.p, "kept-last-edge records");
-        if (rc != HNSW_OK) return rc;
-        refusals.clear();
-        for (uint32_t r = 0; r < W; r++) {
-            if (x_counts[r] == 0) continue;
-            const size_t at = refusals.size();
-            refusals.resize(at + x_counts[r]);
-            HIP_TRY(hipMemcpy(refusals.data() + at, sh->d_recv + (size_t)r * x_stride + SH_HEADER, (size_t)x_counts[r] * 8,
-                              hipMemcpyDeviceToHost));
-        }
-        if (verbose)
-            fprintf(stderr, "\nsharded build, rank %u of %u: phases 2 / 3 on the rows it owns; %zu rows received, %.1f MB through the "
-                            "variable-size exchanges in %.2f s\n", sh->rank, W, n_shipped, x_bytes / 1e6, t_exchange);
-    }
-    for (int pass = 0; pass < 2; pass++) {
-        std::vector<std::vector<NodeID>> &rowsv = pass == 0 ? host.adj0 : host.adj_up;
-        const uint32_t S = pass == 0 ? v.S0 : v.S1;
-        const size_t R = rowsv.size();
-        if (R == 0) continue;
-        // pieces of the array arrive through pinned buffers; the threads turn each into the host's rows while
-        // the next one is on the wire
-        rc = h->dev.read_adjacency(pass, R, [&](uint64_t plo, uint64_t phi, const uint32_t *data) {
-            auto fill = [&](uint64_t lo, uint64_t hi) {
-                std::vector<NodeID> ids_of_row(S);
-                for (uint64_t r = lo; r < hi; r++) {
-                    const uint32_t *src = data + (r - plo) * (size_t)S;
-                    uint32_t deg = 0;
-                    for (uint32_t k = 0; k < S; k++)
-                        if (src[k] != UINT32_MAX) ids_of_row[deg++] = src[k];
-                    rowsv[r].assign(ids_of_row.begin(), ids_of_row.begin() + deg);  // one allocation of the row's size
-                }
-            };
-            const uint64_t cnt = phi - plo;
-            const unsigned nt = (unsigned)std::min<uint64_t>(nb_threads, std::max<uint64_t>(1, cnt / 16384));
-            if (nt <= 1) {
-                fill(plo, phi);
-            } else {
-                std::vector<std::thread> th;
-                for (unsigned t = 0; t < nt; t++) th.emplace_back(fill, plo + cnt * t / nt, plo + cnt * (t + 1) / nt);
-                for (auto &t : th) t.join();
-            }
-        });
-        if (rc != HNSW_OK) return rc;
-    }
-    // an edge x -> nb that stayed because it was x's last one: restore nb -> x (graph.rs:85-94 keeps both)
-    refusals.insert(refusals.end(), restore.begin(), restore.end());
-    const uint64_t id_mask = (1ull << hx::HX_EDGE_ID_BITS) - 1;
-    std::vector<uint64_t> touched;  // rows the host changes after the read-back: (layer << 32) | id
-    for (uint64_t key : refusals) {
-        const uint32_t layer = (uint32_t)(key >> (2 * hx::HX_EDGE_ID_BITS));
-        const NodeID x = (NodeID)((key >> hx::HX_EDGE_ID_BITS) & id_mask), nb = (NodeID)(key & id_mask);
-        std::vector<NodeID> &row = host.row(layer, nb);
-        const std::vector<NodeID> &back = host.row(layer, x);
-        if (std::find(back.begin(), back.end(), nb) != back.end() &&
-            std::find(row.begin(), row.end(), x) == row.end()) {
-            row.push_back(x);
-            touched.push_back(((uint64_t)layer << 32) | nb);
-        }
-    }
-    const bool device_is_the_graph = failed.empty();
-    // points the kernel could not serve take the CPU path
-    if (!failed.empty()) {
-        std::sort(failed.begin(), failed.end());
-        for (NodeID p : failed) {
-            rc = host.insert(p, *ins);
-            if (rc != HNSW_OK) return rc;
-        }
-    }
-    if (verbose) {
-        const double tot = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-        const double t_sync = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_sync0).count();
-        fprintf(stderr,
-                "\non-device build (device connect): %zu batches in %.2f s (insert kernel %.2f s, sort + connect + "
-                "remove %.2f s, graph read-back %.2f s); %zu requests, %zu removals, %u kept-last-edge, %zu points "
-                "ran again with a larger visited table, %zu took the CPU path\n",
-                n_batches, tot, t_ins, t_conn, t_sync, n_req, n_rem, counts[2], n_again, failed.size());
-        auto secs = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) {
-            return std::chrono::duration<double>(y - x).count();
-        };
-        fprintf(stderr,
-                "host phases: store_points %.2f s, levels + order %.2f s, (row clamp %.2f s,) first %llu points on the CPU beside the "
-                "upload %.2f s, buffers %.2f s, batch loop %.2f s\n",
-                secs(t_enter, t_stored), secs(t_stored, t_start), secs(t_start, t_clamped), (unsigned long long)SEED,
-                secs(t_clamped, t_uploaded), secs(t_uploaded, t_loop0), secs(t_loop0, t_sync0));
-    }
-    host.version++;
-    // the adjacency in HBM is the graph just read back: patch the few rows changed since and keep the snapshot
-    // (a build of tens of GB is otherwise followed by an upload of the same tens of GB)
-    if (device_is_the_graph && !(getenv("HNSW_MI355X_REUPLOAD") && atoi(getenv("HNSW_MI355X_REUPLOAD")) != 0))
-        (void)h->dev.refresh_rows(host, touched);
-    return HNSW_OK;
-}
-
 // An on-device build that returns an error after it stored the points leaves some of them unconnected
 // (and, in the device-connect form, the graph only in HBM): the handle is marked and refuses further use.
 // Errors raised before anything was stored (bad rows, bad arguments) leave the index as it was.
@@ -1835,13 +834,13 @@ int hnsw_insert_bulk_levels(hnsw_index *h, const float *rows, uint64_t n, uint32
     if (h->incomplete_build) return check_search_args(h, 1);
     std::vector<float> unit;
     if (int crc = cosine_rows(h, rows, n, unit, nb_threads)) return crc;
-    if (h->gpu_build == 2) return device_build_guard(h, [&] { return gpu_insert_bulk_full(h, rows, n, nb_threads, verbose, levels); });
-    if (h->gpu_build) return device_build_guard(h, [&] { return gpu_insert_bulk(h, rows, n, nb_threads, verbose, levels); });
+    if (h->gpu_build == 2) return device_build_guard(h, [&] { return hx::gpu_insert_bulk_full(build_target(h), rows, n, nb_threads, verbose, levels); });
+    if (h->gpu_build) return device_build_guard(h, [&] { return hx::gpu_insert_bulk(build_target(h), rows, n, nb_threads, verbose, levels); });
     return h->host->insert_bulk(rows, n, nb_threads, verbose != 0, levels);
 }
 uint64_t hnsw_sharded_slot_bytes(const hnsw_index *h, uint32_t world) {
     if (!h || world == 0) return 0;
-    return shard_slot_bytes((uint32_t)h->host->params.m, world);
+    return hx::shard_slot_bytes((uint32_t)h->host->params.m, world);
 }
 int hnsw_insert_bulk_sharded(hnsw_index *h, const float *rows, uint64_t n, uint32_t nb_threads, int verbose,
                              const uint8_t *levels, uint32_t rank, uint32_t world, void *d_send, void *d_recv,
@@ -1850,10 +849,10 @@ int hnsw_insert_bulk_sharded(hnsw_index *h, const float *rows, uint64_t n, uint3
     if (is_replica(h)) return reject_replica(h, "hnsw_insert_bulk_sharded");
     std::vector<float> unit;
     if (int crc = cosine_rows(h, rows, n, unit, nb_threads)) return crc;
-    ShardCtx sh{rank, world, static_cast<unsigned char *>(d_send), static_cast<unsigned char *>(d_recv), slot_bytes,
+    hx::ShardCtx sh{rank, world, static_cast<unsigned char *>(d_send), static_cast<unsigned char *>(d_recv), slot_bytes,
                 allgather, ctx};
     if (h->incomplete_build) return check_search_args(h, 1);
-    return device_build_guard(h, [&] { return gpu_insert_bulk_full(h, rows, n, nb_threads, verbose, levels, &sh); });
+    return device_build_guard(h, [&] { return hx::gpu_insert_bulk_full(build_target(h), rows, n, nb_threads, verbose, levels, &sh); });
 }
 int hnsw_insert_bulk_device(hnsw_index *h, const float *rows, uint64_t n, uint32_t nb_threads,
                             int verbose, const uint8_t *levels) {
@@ -1862,8 +861,8 @@ int hnsw_insert_bulk_device(hnsw_index *h, const float *rows, uint64_t n, uint32
     if (h->incomplete_build) return check_search_args(h, 1);
     std::vector<float> unit;
     if (int crc = cosine_rows(h, rows, n, unit, nb_threads)) return crc;
-    if (h->gpu_build == 1) return device_build_guard(h, [&] { return gpu_insert_bulk(h, rows, n, nb_threads, verbose, levels); });
-    return device_build_guard(h, [&] { return gpu_insert_bulk_full(h, rows, n, nb_threads, verbose, levels); });
+    if (h->gpu_build == 1) return device_build_guard(h, [&] { return hx::gpu_insert_bulk(build_target(h), rows, n, nb_threads, verbose, levels); });
+    return device_build_guard(h, [&] { return hx::gpu_insert_bulk_full(build_target(h), rows, n, nb_threads, verbose, levels); });
 }
 int hnsw_insert_vec(hnsw_index *h, const float *v, uint32_t *out_id) {
     return hnsw_insert_vec_level(h, v, -1, out_id);
@@ -2471,7 +1470,7 @@ int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
     } else if (!strcmp(key, "patch_fallbacks")) {
         *out = h->n_patch_fallbacks.load();
     } else if (!strncmp(key, "build_", 6)) {
-        const hnsw_index::BuildStats &bs = h->build;
+        const hx::BuildStats &bs = h->build;
         const char *k = key + 6;
         if (!strcmp(k, "points")) *out = bs.points;
         else if (!strcmp(k, "batches")) *out = bs.batches;

@@ -2,6 +2,7 @@
 // uploads it.  Host code only (HIP runtime API); the kernels are in search_kernels.hip.
 
 #include "device_index.h"
+#include "hip_util.h"
 
 #include <algorithm>
 #include <atomic>
@@ -14,15 +15,6 @@
 #include <vector>
 
 namespace hx {
-
-#define HIP_TRY(expr)                                                                    \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess) {                                                          \
-            set_error("%s failed: %s", #expr, hipGetErrorString(e_));                    \
-            return e_ == hipErrorOutOfMemory ? HNSW_ERR_OOM : HNSW_ERR_HIP;              \
-        }                                                                                \
-    } while (0)
 
 uint32_t quant_half_bytes(uint32_t dim) {
     const uint32_t need = 8 + 4 * (dim / 8) + (dim % 8);

@@ -1,4 +1,4 @@
-// shard_exchange.h -- helpers of the sharded on-device build (capi.cpp, gpu_insert_bulk_full with a ShardCtx) that are
+// shard_exchange.h -- helpers of the sharded on-device build (device_build.cpp, gpu_insert_bulk_full with a ShardCtx) that are
 // not kernels of the search or of the single-GPU build.
 #pragma once
 #include <cstdint>
