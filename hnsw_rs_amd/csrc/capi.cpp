@@ -1487,6 +1487,9 @@ int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
         else if (!strcmp(k, "rows_received")) *out = bs.rows_received;
         else if (!strcmp(k, "exchange_bytes")) *out = bs.exchange_bytes;
         else if (!strcmp(k, "exchange_us")) *out = (uint64_t)(bs.exchange_s * 1e6);
+        else if (!strcmp(k, "cpu_path_points")) *out = bs.cpu_path_points;
+        else if (!strcmp(k, "rerun_points")) *out = bs.rerun_points;
+        else if (!strcmp(k, "kept_last_edges")) *out = bs.kept_last_edges;
         else {
             set_error("unknown statistic %s", key);
             return HNSW_ERR_ARG;

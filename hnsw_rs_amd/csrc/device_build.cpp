@@ -988,6 +988,9 @@ int gpu_insert_bulk_full(const BuildTarget &t, const float *rows, uint64_t n, ui
     const auto t_sync0 = Clock::now();
     std::vector<uint64_t> refusals, touched;
     if ((rc = b.kept_last_edges(st, refusals))) return rc;
+    t.stats.cpu_path_points += b.failed.size();
+    t.stats.rerun_points += b.n_again;
+    t.stats.kept_last_edges += refusals.size() + restore.size();  // sharded: every owner's refusals, on every rank
     refusals.insert(refusals.end(), restore.begin(), restore.end());
     if ((rc = b.read_graph(refusals, touched))) return rc;
     const bool device_is_the_graph = b.failed.empty();

@@ -14,6 +14,9 @@ namespace hx {
 struct BuildStats {
     uint64_t points = 0, batches = 0, rows_read = 0, adj_rows = 0, adj_ids = 0, records = 0, removals = 0;
     uint64_t rows_owned = 0, rows_received = 0, exchange_bytes = 0;  // sharded build, phases 2 / 3 by row ownership
+    // the device-connect build's paths: points that took the CPU path after it, points whose insertion search ran again
+    // with a larger visited table, edges kept because they were a row's last one (phase 3 refusals + seed clamp restores)
+    uint64_t cpu_path_points = 0, rerun_points = 0, kept_last_edges = 0;
     double insert_kernel_s = 0, insert_phase_s = 0, connect_s = 0, exchange_s = 0, connect_kernel_s = 0;
 };
 

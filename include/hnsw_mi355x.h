@@ -286,7 +286,12 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * (host clock: phase 1 with its copies, sort + connect + remove), "build_connect_kernel_us" (hx_connect_kernel +
  * hx_remove_kernel, HIP events), and for the sharded build "build_rows_owned" /
  * "build_rows_received" (rows this rank changed as their owner and shipped; rows it received from the other owners),
- * "build_exchange_bytes" / "build_exchange_us" (the variable-size all-gathers: bytes received, host clock) */
+ * "build_exchange_bytes" / "build_exchange_us" (the variable-size all-gathers: bytes received, host clock), and for the
+ * device-connect build "build_cpu_path_points" (points its kernels could not serve: inserted on the CPU after it),
+ * "build_rerun_points" (points whose insertion search filled the first, smaller visited table and ran again with a
+ * larger one) and "build_kept_last_edges" (edges a prune dropped on one side only because they were the other
+ * node's last edge -- the drop kernel's refusals plus the seed's clamp restores -- mirrored after the build; in the
+ * sharded build every rank reports the whole build's, like "build_points") */
 int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out);
 
 /* ---- replication of the HBM snapshot over the GPUs of a node ----------------------------------- */

@@ -76,6 +76,16 @@ orc_index *orc_clone(const orc_index *);
  * ascending id; the entry point is the smallest id on the top layer (documented defaults for
  * the reference's hash-iteration order). */
 int orc_insert_bulk(orc_index *, const float *rows, uint64_t n, const uint8_t *levels);
+/* The product's batch-synchronous on-device build ("gpu_build" = 2) restated on the CPU from the
+ * functions above (batched_build.cpp, whose header states its rules): seed, clamp, batches of
+ * min(rest, batch_max, max(64, connected / batch_div)) points searched against the graph at the
+ * batch's start, rows pruned to their cap, reverse edges dropped, kept-last-edges mirrored.
+ * Works on an empty index and on one that already holds points.  nthreads does not change the
+ * result.  stats (optional, 6 x u64): points inserted sequentially, batches, kept-last-edges (phase 3
+ * refusals + clamp restores), clamp restores alone, heuristic calls whose candidate set was cut to
+ * 512, heuristic calls that popped more than 128 candidates. */
+int orc_insert_bulk_batched(orc_index *, const float *rows, uint64_t n, const uint8_t *levels,
+                            uint32_t batch_max, uint32_t batch_div, int nthreads, uint64_t *stats);
 /* HNSW::insert_vec, hnsw/src/template.rs:165-173 */
 int orc_insert_vec(orc_index *, const float *v, uint8_t level, uint32_t *out_id);
 

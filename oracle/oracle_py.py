@@ -69,6 +69,8 @@ def lib():
     L.orc_clone.restype = C.c_void_p
     L.orc_insert_bulk.argtypes = [C.c_void_p, f32p, C.c_uint64, u8p]
     L.orc_insert_bulk.restype = C.c_int
+    L.orc_insert_bulk_batched.argtypes = [C.c_void_p, f32p, C.c_uint64, u8p, C.c_uint32, C.c_uint32, C.c_int, u64p]
+    L.orc_insert_bulk_batched.restype = C.c_int
     L.orc_insert_vec.argtypes = [C.c_void_p, f32p, C.c_uint8, u32p]
     L.orc_insert_vec.restype = C.c_int
     L.orc_import_points.argtypes = [C.c_void_p, f32p, C.c_uint64, u8p]
@@ -212,6 +214,21 @@ class OracleHNSW:
         assert lv.shape[0] == v.shape[0]
         _check(self.L.orc_insert_bulk(self.h, _p(v, f32p), v.shape[0], _p(lv, u8p)))
         return self
+
+    def insert_bulk_batched(self, vectors, levels, batch_max=8192, batch_div=8, nthreads=8):
+        """The product's on-device build (batched_build.cpp) restated: -> dict of its counts
+        (seed_points: inserted sequentially, batches, kept_last_edges: phase 3 refusals + clamp restores,
+        clamp_restores, heuristic_cut: heuristic calls whose candidate set was cut to 512,
+        heuristic_past_window: heuristic calls that popped more than 128 candidates)"""
+        v = _f32(vectors)
+        assert v.ndim == 2 and v.shape[1] == self.dim
+        lv = np.ascontiguousarray(levels, dtype=np.uint8)
+        assert lv.shape[0] == v.shape[0]
+        st = np.zeros(6, dtype=np.uint64)
+        _check(self.L.orc_insert_bulk_batched(self.h, _p(v, f32p), v.shape[0], _p(lv, u8p), batch_max, batch_div,
+                                              nthreads, _p(st, u64p)))
+        keys = ("seed_points", "batches", "kept_last_edges", "clamp_restores", "heuristic_cut", "heuristic_past_window")
+        return {k: int(x) for k, x in zip(keys, st)}
 
     def insert_vec(self, vector, level):
         v = _f32(vector)

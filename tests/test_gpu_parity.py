@@ -7,7 +7,8 @@ import pytest
 import hnsw_rs_amd as H
 from hnsw_rs_amd import _lib
 from oracle import oracle_py as O
-from tests.util import (assert_search_equal, oracle_from_product, product_from_oracle, rand_vectors)
+from tests.util import (assert_search_equal, graph_difference, oracle_from_product, product_from_oracle,
+                        rand_vectors)
 
 pytestmark = pytest.mark.gpu
 
@@ -613,3 +614,9 @@ def test_sharded_device_build_two_ranks(tmp_path, world):
         rows = [np.sort(nbrs[int(offs[k]):int(offs[k + 1])]) for k in range(len(ids))]
         assert np.array_equal(r0["offs%d" % layer.level], offs)
         assert np.array_equal(r0["nbrs%d" % layer.level], np.concatenate(rows))
+    # which is the batch-synchronous build restated on the CPU, edge for edge (oracle/batched_build.cpp): that
+    # pins the sharded builds transitively
+    orc = O.OracleHNSW(m, 32, d)
+    orc.insert_bulk_batched(vs, H.draw_levels(m, n), nthreads=8)
+    diff = graph_difference(one, orc)
+    assert diff is None, diff

@@ -37,6 +37,35 @@ def same_graph(index, orc):
     return True
 
 
+def graph_difference(idx, orc):
+    """None if the product index and the oracle index hold the same graph, else a message naming the first differing
+    (layer, node), its missing and extra neighbours and their dist2other to the node (near-tie or real error?)"""
+    if int(idx.params.ep) != orc.ep:
+        return "entry point %d, restatement %d" % (int(idx.params.ep), orc.ep)
+    if idx.nb_layers() != orc.nb_layers:
+        return "%d layers, restatement %d" % (idx.nb_layers(), orc.nb_layers)
+    for l in range(orc.nb_layers):
+        ids, offs, nbrs = idx.get_layer(l).csr()
+        o_ids, o_offs, o_nbrs = orc.layer_csr(l)
+        if not np.array_equal(ids, o_ids):
+            return "layer %d: node ids differ (%d vs %d nodes)" % (l, len(ids), len(o_ids))
+        if np.array_equal(offs, o_offs) and np.array_equal(nbrs, o_nbrs):
+            continue
+        for k, node in enumerate(ids.tolist()):
+            got = set(nbrs[int(offs[k]):int(offs[k + 1])].tolist())
+            want = set(o_nbrs[int(o_offs[k]):int(o_offs[k + 1])].tolist())
+            if got == want:
+                continue
+            fmt = lambda xs: ", ".join("%d (d=%r)" % (x, float(orc.distance(node, x))) for x in sorted(xs))
+            n_rows = sum(1 for j in range(len(ids)) if not np.array_equal(
+                np.asarray(nbrs[int(offs[j]):int(offs[j + 1])]), np.asarray(o_nbrs[int(o_offs[j]):int(o_offs[j + 1])])))
+            return ("layer %d, node %d (of %d differing rows on the layer): missing [%s], extra [%s]; the row's "
+                    "largest kept distance in the restatement %r" %
+                    (l, node, n_rows, fmt(want - got), fmt(got - want),
+                     max((float(orc.distance(node, x)) for x in want), default=None)))
+    return None
+
+
 def rand_vectors(n, d, seed):
     """make_rand_vectors (hnsw/src/template.rs:630-638): U[0,1)"""
     return np.random.Generator(np.random.PCG64(seed)).random((n, d), dtype=np.float32)
