@@ -85,6 +85,11 @@ SYMBOLS = {
                                     C.POINTER(QueryStats)]),
     "hnsw_brute_force": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, u32p, f32p]),
     "hnsw_brute_force_fast": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, u32p, f32p]),
+    "hnsw_mark_deleted": (C.c_int, [vp, u32p, C.c_uint64]),
+    "hnsw_unmark_deleted": (C.c_int, [vp, u32p, C.c_uint64]),
+    "hnsw_is_deleted": (C.c_int, [vp, C.c_uint32, C.POINTER(C.c_int)]),
+    "hnsw_deleted_count": (C.c_uint64, [vp]),
+    "hnsw_get_deleted": (C.c_int, [vp, u32p, C.c_uint64, u64p]),
     "hnsw_len": (C.c_uint64, [vp]),
     "hnsw_distance": (C.c_int, [vp, C.c_uint32, C.c_uint32, f32p]),
     "hnsw_get_vector": (C.c_int, [vp, C.c_uint32, f32p]),

@@ -24,6 +24,7 @@
 #include <thread>
 #include <vector>
 
+#include "deleted.h"
 #include "device_build.h"
 #include "device_index.h"
 #include "hip_util.h"
@@ -150,6 +151,10 @@ struct hnsw_index {
     // answered by the exact scan ("Filtered search", for the measured crossover); queries per path
     int64_t filter_exact_max = 65536;
     std::atomic<uint64_t> n_filt_graph{0}, n_filt_exact{0}, n_filt_overflow{0};
+    // deleted ids (hnsw_mark_deleted), on the host and in HBM; while any is deleted the unfiltered entry points answer
+    // by the filtered search over the undeleted ids and count their queries per path here
+    hx::DeletedSet del;
+    std::atomic<uint64_t> n_del_graph{0}, n_del_exact{0}, n_del_overflow{0};
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")
 };
 
@@ -492,6 +497,307 @@ int search_host(hnsw_index *h, hx::SearchArgs a_host, const float *Q, uint64_t n
 }
 
 
+// ---- filtered search, and the unfiltered entry points while ids are deleted --------------------------------------
+// queries per path (0 graph, 1 exact, 2 exact after an overflow): the filtered_* or the deleted_* counters
+struct PathCounters {
+    std::atomic<uint64_t> *graph, *exact, *overflow;
+};
+const uint64_t kNoWords = 0;  // the mask of a filtered call with allow_bits 0 (never read)
+
+PathCounters filt_counters(hnsw_index *h) { return {&h->n_filt_graph, &h->n_filt_exact, &h->n_filt_overflow}; }
+PathCounters del_counters(hnsw_index *h) { return {&h->n_del_graph, &h->n_del_exact, &h->n_del_overflow}; }
+
+// brings the deleted set's HBM copy up to date on the snapshot's device (on a stream of the handle's own, so that a
+// caller's stream is not synchronised); a no-op while nothing is deleted
+int sync_deleted(hnsw_index *h) {
+    if (h->del.count == 0) return HNSW_OK;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (h->del.d_words && h->del.d_device == h->dev.device && h->del.dirty.empty()) return HNSW_OK;
+    ScratchLease lease(h);
+    int rc = lease.prepare(h->dev.device, 0, 0);
+    if (rc != HNSW_OK) return rc;
+    return h->del.sync(h->dev.device, lease.s->stream);
+}
+
+// The admissible ids of a call: below bits = min(allow_bits, len), allowed by `allow` (nullptr: all), not deleted.
+// -> A, and the admissible ids before every block of 64 words (the compaction kernel's offsets)
+uint64_t count_admissible(const hnsw_index *h, const uint64_t *allow, uint64_t bits, std::vector<uint32_t> &wbase) {
+    const uint64_t n_words = (bits + 63) / 64, n_wblk = (n_words + 63) / 64;
+    const std::vector<uint64_t> &deny = h->del.words;
+    const bool denies = h->del.count > 0;
+    wbase.assign(std::max<uint64_t>(1, n_wblk), 0);
+    uint64_t A = 0;
+    for (uint64_t w = 0; w < n_words; w++) {
+        if (w % 64 == 0) wbase[w / 64] = (uint32_t)A;
+        uint64_t x = allow ? allow[w] : ~0ull;
+        if (w == n_words - 1 && bits % 64) x &= (1ull << (bits % 64)) - 1;
+        if (denies && w < deny.size()) x &= ~deny[w];
+        A += (uint64_t)__builtin_popcountll(x);
+    }
+    return A;
+}
+
+// the exact path for nsel queries: those of d_sel, or the first nsel of the call; `chunk` queries per launch
+int filtered_exact(const hx::DevView &v, const hx::FilterArgs &a, uint64_t nsel, const uint32_t *d_sel, uint64_t n_words,
+                   const uint32_t *d_wb, uint32_t *d_ids, uint64_t A, uint32_t chunk, uint32_t nseg, void *part,
+                   void *pst, hipStream_t stream) {
+    int r = hx::launch_filter_compact(a, n_words, d_wb, d_ids, stream);
+    for (uint64_t c = 0; r == HNSW_OK && c < nsel; c += chunk) {
+        hx::FilterArgs ac = a;
+        if (d_sel) {
+            ac.qsel = d_sel + c;
+        } else {
+            ac.qsel = nullptr;
+            ac.Q += c * v.dim;
+            ac.out_ids += c * a.n;
+            ac.out_dists += c * a.n;
+            ac.out_counts += c;
+            ac.out_stats += c;
+        }
+        r = hx::launch_filtered_exact(v, ac, (uint32_t)std::min<uint64_t>(chunk, nsel - c), d_ids, (uint32_t)A, nseg,
+                                      static_cast<unsigned long long *>(part), static_cast<int32_t *>(pst), stream);
+    }
+    return r;
+}
+
+// k-NN among the admissible ids (hnsw_search_batch_filtered's contract).  exact_only: every query by the exact path
+// (hnsw_brute_force).  Per-query statuses are left in stats (required); returns argument and launch errors only.
+int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const uint64_t *allow,
+                    uint64_t allow_bits, bool exact_only, uint32_t *ids, float *dists, uint32_t *counts,
+                    hnsw_query_stats *stats, uint8_t *paths, const PathCounters *ctr) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK) return rc;
+    if (nq == 0) return HNSW_OK;
+    if (!Q || !ids || nq > 0x7FFFFFFFull || n > HX_FILT_MAX_N) {
+        set_error("filtered search: needs queries, an id buffer, a mask when allow_bits > 0 and n <= %d",
+                  HX_FILT_MAX_N);
+        return HNSW_ERR_ARG;
+    }
+    if (n == 0) {  // nothing returned, nothing launched
+        if (counts) memset(counts, 0, nq * 4);
+        return HNSW_OK;
+    }
+    const uint32_t efp = std::max(std::max(ef, n), 1u);
+    const uint64_t bits = std::min<uint64_t>(allow_bits, index_len(h));
+    const uint64_t n_words = (bits + 63) / 64;
+    std::vector<uint32_t> wbase;
+    const uint64_t A = count_admissible(h, allow, bits, wbase);
+    const bool exact_all = exact_only || (int64_t)A <= h->filter_exact_max;
+    if (!exact_all && efp > HX_FILT_MAX_EF) {
+        set_error("filtered search: ef' = max(ef, n) = %u is above the graph path's maximum of %d", efp, HX_FILT_MAX_EF);
+        return HNSW_ERR_ARG;
+    }
+    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h))) return rc;
+    const hx::DevView &v = h->dev.view;
+    const uint32_t d = v.dim;
+    // device arena: [queries | mask | word offsets | admissible ids | selection | partial keys | partial statuses |
+    // result block]; the result block [ids | dists | counts | stats] comes back in one copy to the pinned arena
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(nq, 65535);  // queries per exact launch
+    const uint32_t nseg = hx::filt_exact_segments(A, chunk);
+    const size_t o_q = 0, o_mask = o_q + align256(nq * d * 4), o_wb = o_mask + align256(allow ? n_words * 8 : 0),
+                 o_ids = o_wb + align256(wbase.size() * 4), o_sel = o_ids + align256(A * 4),
+                 o_part = o_sel + align256(nq * 4), o_pst = o_part + align256((size_t)chunk * nseg * n * 8),
+                 o_out = o_pst + align256((size_t)chunk * nseg * 4);
+    const size_t r_ids = 0, r_dists = align256(nq * n * 4), r_counts = r_dists + align256(nq * n * 4),
+                 r_stats = r_counts + align256(nq * 4), out_bytes = r_stats + align256(nq * sizeof(hnsw_query_stats));
+    ScratchLease lease(h);
+    if ((rc = lease.prepare(h->dev.device, o_out + out_bytes, out_bytes))) return rc;
+    SearchScratch &s = *lease.s;
+    unsigned char *dv = static_cast<unsigned char *>(s.dev), *hv = static_cast<unsigned char *>(s.pin);
+    HIP_TRY(hipMemcpyAsync(dv + o_q, Q, nq * d * 4, hipMemcpyHostToDevice, s.stream));
+    if ((rc = cosine_queries(h, dv + o_q, nq, s.stream))) return rc;
+    if (n_words) {
+        if (allow) HIP_TRY(hipMemcpyAsync(dv + o_mask, allow, n_words * 8, hipMemcpyHostToDevice, s.stream));
+        HIP_TRY(hipMemcpyAsync(dv + o_wb, wbase.data(), wbase.size() * 4, hipMemcpyHostToDevice, s.stream));
+    }
+    hx::FilterArgs a{};
+    a.Q = reinterpret_cast<const float *>(dv + o_q);
+    a.allow = allow ? reinterpret_cast<const uint64_t *>(dv + o_mask) : nullptr;
+    a.allow_bits = bits;
+    a.deny = h->del.count ? h->del.d_words : nullptr;
+    a.deny_bits = h->del.count ? h->del.deny_bits() : 0;
+    a.n = n;
+    a.ef = efp;
+    a.out_ids = reinterpret_cast<uint32_t *>(dv + o_out + r_ids);
+    a.out_dists = reinterpret_cast<float *>(dv + o_out + r_dists);
+    a.out_counts = reinterpret_cast<uint32_t *>(dv + o_out + r_counts);
+    a.out_stats = reinterpret_cast<hnsw_query_stats *>(dv + o_out + r_stats);
+    uint32_t *d_sel = reinterpret_cast<uint32_t *>(dv + o_sel);
+    auto exact = [&](uint64_t nsel, bool selected) -> int {
+        return filtered_exact(v, a, nsel, selected ? d_sel : nullptr, n_words,
+                              reinterpret_cast<const uint32_t *>(dv + o_wb), reinterpret_cast<uint32_t *>(dv + o_ids), A,
+                              chunk, nseg, dv + o_part, dv + o_pst, s.stream);
+    };
+    const hnsw_query_stats *st = reinterpret_cast<const hnsw_query_stats *>(hv + r_stats);
+    std::vector<uint8_t> path(nq, exact_all ? 1 : 0);
+    if (exact_all) {
+        if ((rc = exact(nq, false))) return rc;
+        HIP_TRY(hipMemcpyAsync(hv, dv + o_out, out_bytes, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(hipStreamSynchronize(s.stream));
+    } else {
+        // graph path; queries whose visited table filled up run again with a table twice the size, and those
+        // that fill the largest one are answered by the exact path
+        uint32_t slots = hx::filt_first_slots_log2(v, efp);
+        const uint32_t max_slots = hx::filt_max_slots_log2(v);
+        uint64_t nrun = nq;
+        std::vector<uint32_t> sel;
+        while (true) {
+            if ((rc = hx::launch_filtered_graph(v, a, (uint32_t)nrun, slots, s.stream))) return rc;
+            HIP_TRY(hipMemcpyAsync(hv, dv + o_out, out_bytes, hipMemcpyDeviceToHost, s.stream));
+            HIP_TRY(hipStreamSynchronize(s.stream));
+            sel.clear();
+            for (uint64_t i = 0; i < nq; i++)
+                if (st[i].status == HNSW_ERR_OVERFLOW) sel.push_back((uint32_t)i);
+            if (sel.empty()) break;
+            HIP_TRY(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s.stream));
+            if (slots >= max_slots) {
+                for (uint32_t i : sel) path[i] = 2;
+                if ((rc = exact(sel.size(), true))) return rc;
+                HIP_TRY(hipMemcpyAsync(hv, dv + o_out, out_bytes, hipMemcpyDeviceToHost, s.stream));
+                HIP_TRY(hipStreamSynchronize(s.stream));
+                break;
+            }
+            HIP_TRY(hipStreamSynchronize(s.stream));  // `sel` is reused by the next round
+            slots++;
+            a.qsel = d_sel;
+            nrun = sel.size();
+        }
+    }
+    uint64_t n2 = 0;
+    for (uint64_t i = 0; i < nq; i++) n2 += path[i] == 2;
+    if (ctr) {
+        if (exact_all)
+            ctr->exact->fetch_add(nq, std::memory_order_relaxed);
+        else
+            ctr->graph->fetch_add(nq - n2, std::memory_order_relaxed);
+        ctr->overflow->fetch_add(n2, std::memory_order_relaxed);
+    }
+    memcpy(ids, hv + r_ids, nq * n * 4);
+    if (dists) memcpy(dists, hv + r_dists, nq * n * 4);
+    if (counts) memcpy(counts, hv + r_counts, nq * 4);
+    memcpy(stats, st, nq * sizeof(hnsw_query_stats));
+    if (paths) memcpy(paths, path.data(), nq);
+    return HNSW_OK;
+}
+
+// ... with the first per-query error as the status (stats may be NULL)
+int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const uint64_t *allow,
+                            uint64_t allow_bits, bool exact_only, uint32_t *ids, float *dists, uint32_t *counts,
+                            hnsw_query_stats *stats, uint8_t *paths, const PathCounters *ctr) {
+    std::vector<hnsw_query_stats> local;
+    if (!stats) {
+        local.resize(nq);
+        stats = local.data();
+    }
+    int rc = search_filtered(h, Q, nq, n, ef, allow, allow_bits, exact_only, ids, dists, counts, stats, paths, ctr);
+    if (rc != HNSW_OK || n == 0) return rc;
+    for (uint64_t i = 0; i < nq; i++)
+        if (stats[i].status != HNSW_OK) return query_status_error(i, stats[i].status);
+    return HNSW_OK;
+}
+
+// hnsw_search_batch_device (finish = false) and _finish while ids are deleted: the filtered graph path over the
+// undeleted ids on the caller's stream; _finish re-runs the queries whose visited table filled up with larger tables,
+// up to the graph path's largest, and answers those that fill it by the exact path.  Equals the host form with
+// filter_exact_max = -1.
+int search_device_deleted(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t *d_ids,
+                          float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, hipStream_t stream, bool finish) {
+    const uint32_t efp = std::max(std::max(ef, n), 1u);
+    if (n > HX_FILT_MAX_N || efp > HX_FILT_MAX_EF) {
+        set_error("search with deleted ids: needs n <= %d and ef' = max(ef, n) <= %d", HX_FILT_MAX_N, HX_FILT_MAX_EF);
+        return HNSW_ERR_ARG;
+    }
+    int rc;
+    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h))) return rc;
+    const hx::DevView &v = h->dev.view;
+    DeviceQueries dq;
+    if ((rc = dq.prepare(h, d_Q, nq, stream))) return rc;
+    // the kernels write distances and counts: stream-ordered stand-ins for the optional outputs
+    struct Tmp {
+        void *p = nullptr;
+        hipStream_t st = nullptr;
+        ~Tmp() {
+            if (p) (void)hipFreeAsync(p, st);
+        }
+    } t_dists, t_counts;
+    if (!d_dists) {
+        HIP_TRY(hipMallocAsync(&t_dists.p, nq * n * 4, stream));
+        t_dists.st = stream;
+        d_dists = static_cast<float *>(t_dists.p);
+    }
+    if (!d_counts) {
+        HIP_TRY(hipMallocAsync(&t_counts.p, nq * 4, stream));
+        t_counts.st = stream;
+        d_counts = static_cast<uint32_t *>(t_counts.p);
+    }
+    hx::FilterArgs a{};
+    a.Q = dq.q;
+    a.allow = nullptr;
+    a.allow_bits = index_len(h);
+    a.deny = h->del.d_words;
+    a.deny_bits = h->del.deny_bits();
+    a.n = n;
+    a.ef = efp;
+    a.out_ids = d_ids;
+    a.out_dists = d_dists;
+    a.out_counts = d_counts;
+    a.out_stats = d_stats;
+    uint32_t slots = hx::filt_first_slots_log2(v, efp);
+    if (!finish) return hx::launch_filtered_graph(v, a, (uint32_t)nq, slots, stream);
+
+    const uint32_t max_slots = hx::filt_max_slots_log2(v);
+    // scratch: [selection | word offsets | admissible ids | partial keys | partial statuses] on the device, the
+    // statuses on the host; the exact path's part is sized only when a query reaches it
+    const size_t st_bytes = nq * sizeof(hnsw_query_stats);
+    ScratchLease lease(h);
+    if ((rc = lease.prepare(h->dev.device, align256(nq * 4), st_bytes))) return rc;
+    hnsw_query_stats *st = static_cast<hnsw_query_stats *>(lease.s->pin);
+    uint32_t *d_sel = static_cast<uint32_t *>(lease.s->dev);
+    std::vector<uint32_t> sel;
+    uint64_t n2 = 0;
+    while (true) {
+        HIP_TRY(hipMemcpyAsync(st, d_stats, st_bytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        sel.clear();
+        for (uint64_t i = 0; i < nq; i++)
+            if (st[i].status == HNSW_ERR_OVERFLOW) sel.push_back((uint32_t)i);
+        if (sel.empty()) break;
+        if (slots >= max_slots) {  // path 2
+            n2 = sel.size();
+            std::vector<uint32_t> wbase;
+            const uint64_t bits = a.allow_bits, n_words = (bits + 63) / 64;
+            const uint64_t A = count_admissible(h, nullptr, bits, wbase);
+            const uint32_t chunk = (uint32_t)std::min<uint64_t>(n2, 65535);
+            const uint32_t nseg = hx::filt_exact_segments(A, chunk);
+            const size_t o_sel = 0, o_wb = align256(n2 * 4), o_ids = o_wb + align256(wbase.size() * 4),
+                         o_part = o_ids + align256(A * 4), o_pst = o_part + align256((size_t)chunk * nseg * n * 8),
+                         bytes = o_pst + align256((size_t)chunk * nseg * 4);
+            if ((rc = lease.prepare(h->dev.device, bytes, st_bytes))) return rc;
+            unsigned char *dv = static_cast<unsigned char *>(lease.s->dev);
+            st = static_cast<hnsw_query_stats *>(lease.s->pin);
+            HIP_TRY(hipMemcpyAsync(dv + o_sel, sel.data(), n2 * 4, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(dv + o_wb, wbase.data(), wbase.size() * 4, hipMemcpyHostToDevice, stream));
+            if ((rc = filtered_exact(v, a, n2, reinterpret_cast<const uint32_t *>(dv + o_sel), n_words,
+                                     reinterpret_cast<const uint32_t *>(dv + o_wb), reinterpret_cast<uint32_t *>(dv + o_ids),
+                                     A, chunk, nseg, dv + o_part, dv + o_pst, stream)))
+                return rc;
+            HIP_TRY(hipMemcpyAsync(st, d_stats, st_bytes, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));  // (`sel` and `wbase` are locals)
+            break;
+        }
+        HIP_TRY(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));  // `sel` is reused by the next round
+        slots++;
+        a.qsel = d_sel;
+        if ((rc = hx::launch_filtered_graph(v, a, (uint32_t)sel.size(), slots, stream))) return rc;
+    }
+    h->n_del_graph.fetch_add(nq - n2, std::memory_order_relaxed);
+    h->n_del_overflow.fetch_add(n2, std::memory_order_relaxed);
+    for (uint64_t i = 0; i < nq; i++)
+        if (st[i].status != HNSW_OK) return query_status_error(i, st[i].status);
+    return HNSW_OK;
+}
+
 // ---- hnsw_search through the coalescer ---------------------------------------------------------------------------
 inline void futex_wait(std::atomic<uint32_t> *w, uint32_t while_equals) {
     while (w->load(std::memory_order_acquire) == while_equals)
@@ -710,7 +1016,17 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
     const auto t_gpu = sclk::now();
     rc = hipSetDevice(h->dev.device) == hipSuccess ? HNSW_OK : HNSW_ERR_HIP;
     if (rc != HNSW_OK) set_error("hipSetDevice(%d) failed", h->dev.device);
-    if (rc == HNSW_OK) rc = search_staged(h, b->s, p, a, nq, nullptr, nullptr);
+    if (rc == HNSW_OK && h->del.count) {
+        // ids are deleted: the batch is answered as hnsw_search_batch answers it then, into the same result block
+        unsigned char *pin = static_cast<unsigned char *>(b->s.pin), *ob = pin + p.p_out;
+        const PathCounters ctr = del_counters(h);
+        rc = search_filtered(h, reinterpret_cast<const float *>(pin + p.p_q), nq, n, ef, nullptr, index_len(h), false,
+                             reinterpret_cast<uint32_t *>(ob + p.r_ids), reinterpret_cast<float *>(ob + p.r_dists),
+                             reinterpret_cast<uint32_t *>(ob + p.r_counts),
+                             reinterpret_cast<hnsw_query_stats *>(ob + p.r_stats), nullptr, &ctr);
+    } else if (rc == HNSW_OK) {
+        rc = search_staged(h, b->s, p, a, nq, nullptr, nullptr);
+    }
     co.ns_gpu.fetch_add(ns_since(t_gpu), std::memory_order_relaxed);
     const auto t_hand = sclk::now();
     {
@@ -800,6 +1116,7 @@ int hnsw_clone(const hnsw_index *h, hnsw_index **out) {
     c->co.depth = h->co.depth;
     c->co.cap = h->co.cap;
     c->filter_exact_max = h->filter_exact_max;
+    c->del.assign_host(h->del.words);
     *out = c;
     return HNSW_OK;
 }
@@ -939,6 +1256,11 @@ int hnsw_search_batch(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, ui
         if (counts) memset(counts, 0, nq * 4);
         return HNSW_OK;
     }
+    if (h->del.count) {  // ids are deleted: the filtered search over the undeleted ones (include/hnsw_mi355x.h)
+        const PathCounters ctr = del_counters(h);
+        return search_filtered_checked(h, Q, nq, n, ef, nullptr, index_len(h), false, ids, dists, counts, stats,
+                                       nullptr, &ctr);
+    }
     hx::DevView dummy{};
     dummy.nb_layers = hnsw_layer_count(h);  // the host index's, or the adopted snapshot's for a replica
     hx::SearchArgs a = ann_args(dummy, nullptr, n, ef, nullptr, nullptr, nullptr, nullptr);
@@ -951,140 +1273,15 @@ int hnsw_search_batch_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint3
     int rc = check_search_args(h, ef);
     if (rc != HNSW_OK) return rc;
     if (nq == 0) return HNSW_OK;
-    if (!Q || !ids || (!allow && allow_bits != 0) || nq > 0x7FFFFFFFull || n > HX_FILT_MAX_N) {
+    if (!allow && allow_bits != 0) {
         set_error("filtered search: needs queries, an id buffer, a mask when allow_bits > 0 and n <= %d",
                   HX_FILT_MAX_N);
         return HNSW_ERR_ARG;
     }
-    if (n == 0) {  // nothing returned, nothing launched
-        if (counts) memset(counts, 0, nq * 4);
-        return HNSW_OK;
-    }
-    const uint32_t efp = std::max(std::max(ef, n), 1u);
-    // the mask over [0, min(allow_bits, len)): A and the allowed ids before every block of 64 words (the
-    // compaction kernel's offsets)
-    const uint64_t bits = std::min<uint64_t>(allow_bits, index_len(h));
-    const uint64_t n_words = (bits + 63) / 64, n_wblk = (n_words + 63) / 64;
-    std::vector<uint32_t> wbase(std::max<uint64_t>(1, n_wblk));
-    uint64_t A = 0;
-    for (uint64_t w = 0; w < n_words; w++) {
-        if (w % 64 == 0) wbase[w / 64] = (uint32_t)A;
-        uint64_t x = allow[w];
-        if (w == n_words - 1 && bits % 64) x &= (1ull << (bits % 64)) - 1;
-        A += (uint64_t)__builtin_popcountll(x);
-    }
-    const bool exact_all = (int64_t)A <= h->filter_exact_max;
-    if (!exact_all && efp > HX_FILT_MAX_EF) {
-        set_error("filtered search: ef' = max(ef, n) = %u is above the graph path's maximum of %d", efp, HX_FILT_MAX_EF);
-        return HNSW_ERR_ARG;
-    }
-    if ((rc = ensure_uploaded(h))) return rc;
-    const hx::DevView &v = h->dev.view;
-    const uint32_t d = v.dim;
-    // device arena: [queries | mask | word offsets | allowed ids | selection | partial keys | partial statuses |
-    // result block]; the result block [ids | dists | counts | stats] comes back in one copy to the pinned arena
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(nq, 65535);  // queries per exact launch
-    const uint32_t nseg = hx::filt_exact_segments(A, chunk);
-    const size_t o_q = 0, o_mask = o_q + align256(nq * d * 4), o_wb = o_mask + align256(n_words * 8),
-                 o_ids = o_wb + align256(wbase.size() * 4), o_sel = o_ids + align256(A * 4),
-                 o_part = o_sel + align256(nq * 4), o_pst = o_part + align256((size_t)chunk * nseg * n * 8),
-                 o_out = o_pst + align256((size_t)chunk * nseg * 4);
-    const size_t r_ids = 0, r_dists = align256(nq * n * 4), r_counts = r_dists + align256(nq * n * 4),
-                 r_stats = r_counts + align256(nq * 4), out_bytes = r_stats + align256(nq * sizeof(hnsw_query_stats));
-    ScratchLease lease(h);
-    if ((rc = lease.prepare(h->dev.device, o_out + out_bytes, out_bytes))) return rc;
-    SearchScratch &s = *lease.s;
-    unsigned char *dv = static_cast<unsigned char *>(s.dev), *hv = static_cast<unsigned char *>(s.pin);
-    HIP_TRY(hipMemcpyAsync(dv + o_q, Q, nq * d * 4, hipMemcpyHostToDevice, s.stream));
-    if ((rc = cosine_queries(h, dv + o_q, nq, s.stream))) return rc;
-    if (n_words) {
-        HIP_TRY(hipMemcpyAsync(dv + o_mask, allow, n_words * 8, hipMemcpyHostToDevice, s.stream));
-        HIP_TRY(hipMemcpyAsync(dv + o_wb, wbase.data(), n_wblk * 4, hipMemcpyHostToDevice, s.stream));
-    }
-    hx::FilterArgs a{};
-    a.Q = reinterpret_cast<const float *>(dv + o_q);
-    a.allow = reinterpret_cast<const uint64_t *>(dv + o_mask);
-    a.allow_bits = bits;
-    a.n = n;
-    a.ef = efp;
-    a.out_ids = reinterpret_cast<uint32_t *>(dv + o_out + r_ids);
-    a.out_dists = reinterpret_cast<float *>(dv + o_out + r_dists);
-    a.out_counts = reinterpret_cast<uint32_t *>(dv + o_out + r_counts);
-    a.out_stats = reinterpret_cast<hnsw_query_stats *>(dv + o_out + r_stats);
-    uint32_t *d_sel = reinterpret_cast<uint32_t *>(dv + o_sel);
-    const uint32_t *d_ids = reinterpret_cast<const uint32_t *>(dv + o_ids);
-    // the exact path for nsel queries: those of `sel` (uploaded to d_sel), or all of them
-    auto exact = [&](uint64_t nsel, bool selected) -> int {
-        int r = hx::launch_filter_compact(a.allow, n_words, bits, reinterpret_cast<const uint32_t *>(dv + o_wb),
-                                          reinterpret_cast<uint32_t *>(dv + o_ids), s.stream);
-        for (uint64_t c = 0; r == HNSW_OK && c < nsel; c += chunk) {
-            hx::FilterArgs ac = a;
-            if (selected) {
-                ac.qsel = d_sel + c;
-            } else {
-                ac.qsel = nullptr;
-                ac.Q += c * d;
-                ac.out_ids += c * n;
-                ac.out_dists += c * n;
-                ac.out_counts += c;
-                ac.out_stats += c;
-            }
-            r = hx::launch_filtered_exact(v, ac, (uint32_t)std::min<uint64_t>(chunk, nsel - c), d_ids, (uint32_t)A,
-                                          nseg, reinterpret_cast<unsigned long long *>(dv + o_part),
-                                          reinterpret_cast<int32_t *>(dv + o_pst), s.stream);
-        }
-        return r;
-    };
-    const hnsw_query_stats *st = reinterpret_cast<const hnsw_query_stats *>(hv + r_stats);
-    std::vector<uint8_t> path(nq, exact_all ? 1 : 0);
-    if (exact_all) {
-        if ((rc = exact(nq, false))) return rc;
-        HIP_TRY(hipMemcpyAsync(hv, dv + o_out, out_bytes, hipMemcpyDeviceToHost, s.stream));
-        HIP_TRY(hipStreamSynchronize(s.stream));
-    } else {
-        // graph path; queries whose visited table filled up run again with a table twice the size, and those
-        // that fill the largest one are answered by the exact path
-        uint32_t slots = hx::filt_first_slots_log2(v, efp);
-        const uint32_t max_slots = hx::filt_max_slots_log2(v);
-        uint64_t nrun = nq;
-        std::vector<uint32_t> sel;
-        while (true) {
-            if ((rc = hx::launch_filtered_graph(v, a, (uint32_t)nrun, slots, s.stream))) return rc;
-            HIP_TRY(hipMemcpyAsync(hv, dv + o_out, out_bytes, hipMemcpyDeviceToHost, s.stream));
-            HIP_TRY(hipStreamSynchronize(s.stream));
-            sel.clear();
-            for (uint64_t i = 0; i < nq; i++)
-                if (st[i].status == HNSW_ERR_OVERFLOW) sel.push_back((uint32_t)i);
-            if (sel.empty()) break;
-            HIP_TRY(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s.stream));
-            if (slots >= max_slots) {
-                for (uint32_t i : sel) path[i] = 2;
-                if ((rc = exact(sel.size(), true))) return rc;
-                HIP_TRY(hipMemcpyAsync(hv, dv + o_out, out_bytes, hipMemcpyDeviceToHost, s.stream));
-                HIP_TRY(hipStreamSynchronize(s.stream));
-                break;
-            }
-            HIP_TRY(hipStreamSynchronize(s.stream));  // `sel` is reused by the next round
-            slots++;
-            a.qsel = d_sel;
-            nrun = sel.size();
-        }
-    }
-    uint64_t n2 = 0;
-    for (uint64_t i = 0; i < nq; i++) n2 += path[i] == 2;
-    if (exact_all)
-        h->n_filt_exact.fetch_add(nq, std::memory_order_relaxed);
-    else
-        h->n_filt_graph.fetch_add(nq - n2, std::memory_order_relaxed);
-    h->n_filt_overflow.fetch_add(n2, std::memory_order_relaxed);
-    memcpy(ids, hv + r_ids, nq * n * 4);
-    if (dists) memcpy(dists, hv + r_dists, nq * n * 4);
-    if (counts) memcpy(counts, hv + r_counts, nq * 4);
-    if (stats) memcpy(stats, st, nq * sizeof(hnsw_query_stats));
-    if (paths) memcpy(paths, path.data(), nq);
-    for (uint64_t i = 0; i < nq; i++)
-        if (st[i].status != HNSW_OK) return query_status_error(i, st[i].status);
-    return HNSW_OK;
+    // (a call without a mask allows nothing: kNoWords stands for its empty mask, nullptr would allow every id)
+    const PathCounters ctr = filt_counters(h);
+    return search_filtered_checked(h, Q, nq, n, ef, allow ? allow : &kNoWords, allow ? allow_bits : 0, false, ids,
+                                   dists, counts, stats, paths, &ctr);
 }
 
 int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
@@ -1094,6 +1291,9 @@ int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint3
     if (rc != HNSW_OK) return rc;
     if (nq == 0 || n == 0) return HNSW_OK;
     if (!d_Q || !d_ids || !d_stats || nq > 0x7FFFFFFFull) return HNSW_ERR_ARG;
+    if (h->del.count)
+        return search_device_deleted(h, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats, static_cast<hipStream_t>(stream),
+                                     false);
     rc = ensure_uploaded(h);
     if (rc != HNSW_OK) return rc;
     DeviceQueries dq;
@@ -1115,6 +1315,9 @@ int hnsw_search_batch_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq
     if (rc != HNSW_OK) return rc;
     if (nq == 0 || n == 0) return HNSW_OK;
     if (!d_Q || !d_ids || !d_stats || nq > 0x7FFFFFFFull) return HNSW_ERR_ARG;
+    if (h->del.count)
+        return search_device_deleted(h, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats, static_cast<hipStream_t>(stream_v),
+                                     true);
     rc = ensure_uploaded(h);
     if (rc != HNSW_OK) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
@@ -1241,6 +1444,18 @@ int hnsw_brute_force(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uin
         set_error("brute force supports 1 <= k <= 64");
         return HNSW_ERR_ARG;
     }
+    if (h->del.count) {
+        // the top k of the undeleted ids: the filtered search's exact path, in the same arithmetic and (dist, id) order
+        std::vector<hnsw_query_stats> st(nq);
+        rc = search_filtered(h, Q, nq, k, k, nullptr, index_len(h), true, ids, dists, nullptr, st.data(), nullptr, nullptr);
+        if (rc != HNSW_OK) return rc;
+        for (uint64_t i = 0; i < nq; i++)
+            if (st[i].status != HNSW_OK) {
+                set_error("NaN in a query or a distance");
+                return st[i].status;
+            }
+        return HNSW_OK;
+    }
     rc = ensure_uploaded(h);
     if (rc != HNSW_OK) return rc;
     const hx::DevView &v = h->dev.view;
@@ -1298,6 +1513,11 @@ int hnsw_brute_force_fast(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k
     const uint32_t K2 = hx::brute_mfma_k2();
     if (!Q || !ids || k == 0 || k + 8 > K2) {
         set_error("the MFMA scan supports 1 <= k <= %u", K2 - 8);
+        return HNSW_ERR_ARG;
+    }
+    if (h->del.count) {  // the k + 8 re-rank cannot promise k undeleted ids: no ground truth rather than a wrong one
+        set_error("hnsw_brute_force_fast refuses while ids are deleted (%llu); hnsw_brute_force excludes them",
+                  (unsigned long long)h->del.count);
         return HNSW_ERR_ARG;
     }
     rc = ensure_uploaded(h);
@@ -1495,6 +1715,42 @@ int hnsw_check_param_compliance(const hnsw_index *h, int *ok) {
     return HNSW_OK;
 }
 
+// ---- deletion ---------------------------------------------------------------------------------------------
+static int set_deleted(hnsw_index *h, const uint32_t *ids, uint64_t k, bool on) {
+    if (!h || (k && !ids)) return HNSW_ERR_ARG;
+    const uint64_t len = index_len(h);
+    for (uint64_t i = 0; i < k; i++)  // every id checked before anything changes
+        if (ids[i] >= len) {
+            set_error("id %u is not a point of the index (len %llu)", ids[i], (unsigned long long)len);
+            return HNSW_ERR_ARG;
+        }
+    std::lock_guard<std::mutex> g(h->mu);
+    h->del.set(ids, k, on, len);
+    return HNSW_OK;
+}
+int hnsw_mark_deleted(hnsw_index *h, const uint32_t *ids, uint64_t k) { return set_deleted(h, ids, k, true); }
+int hnsw_unmark_deleted(hnsw_index *h, const uint32_t *ids, uint64_t k) { return set_deleted(h, ids, k, false); }
+int hnsw_is_deleted(const hnsw_index *h, uint32_t id, int *out) {
+    if (!h || !out) return HNSW_ERR_ARG;
+    if (id >= index_len(h)) {
+        set_error("id %u is not a point of the index", id);
+        return HNSW_ERR_ARG;
+    }
+    *out = h->del.test(id) ? 1 : 0;
+    return HNSW_OK;
+}
+uint64_t hnsw_deleted_count(const hnsw_index *h) { return h ? h->del.count : 0; }
+int hnsw_get_deleted(const hnsw_index *h, uint32_t *ids, uint64_t cap, uint64_t *n) {
+    if (!h) return HNSW_ERR_ARG;
+    if (n) *n = h->del.count;
+    if (ids && cap) {
+        uint64_t j = 0;
+        for (uint64_t w = 0; w < h->del.words.size() && j < cap; w++)
+            for (uint64_t x = h->del.words[w]; x && j < cap; x &= x - 1) ids[j++] = (uint32_t)(w * 64 + __builtin_ctzll(x));
+    }
+    return HNSW_OK;
+}
+
 // ---- persistence -----------------------------------------------------------------------------------
 int hnsw_save(const hnsw_index *h, const char *dir) {
     if (!h || !dir) return HNSW_ERR_ARG;
@@ -1503,16 +1759,21 @@ int hnsw_save(const hnsw_index *h, const char *dir) {
         set_error("an on-device build on this handle failed half way; the index is incomplete, not saved");
         return HNSW_ERR_ARG;
     }
-    return hx::save_index(*h->host, dir);
+    int rc = hx::save_index(*h->host, dir);
+    if (rc != HNSW_OK) return rc;
+    return hx::save_deleted(dir, h->del.ids());
 }
 int hnsw_load(const char *dir, hnsw_index **out) {
     if (!dir || !out) return HNSW_ERR_ARG;
     std::unique_ptr<hx::HostIndex> idx;
     int rc = hx::load_index(dir, &idx);
     if (rc != HNSW_OK) return rc;
+    std::vector<uint64_t> deleted;
+    if ((rc = hx::load_deleted(dir, idx->len(), &deleted))) return rc;
     hnsw_index *h = new (std::nothrow) hnsw_index();
     if (!h) return HNSW_ERR_OOM;
     h->host = std::move(idx);
+    h->del.assign_host(deleted);
     *out = h;
     return HNSW_OK;
 }
@@ -1531,6 +1792,7 @@ int hnsw_set_device(hnsw_index *h, int device) {
     if (is_replica(h) && device != h->device) return reject_replica(h, "hnsw_set_device (a replica stays on the device it was received on)");
     if (device != h->device) {
         h->dev.release();
+        h->del.release_device();  // (the host set stays; the next search copies it to the new device)
         // a leaderless batch the coalescer keeps open was made ready for the old device (stream, device arena): retire
         // it; the next caller opens one on the new device (no search may be in flight during this call)
         Coalescer &co = h->co;
@@ -1651,6 +1913,16 @@ int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
         *out = h->n_filt_exact.load();
     } else if (!strcmp(key, "filtered_overflow_exact")) {
         *out = h->n_filt_overflow.load();
+    } else if (!strcmp(key, "deleted")) {
+        *out = h->del.count;
+    } else if (!strcmp(key, "deleted_mask_words_uploaded")) {
+        *out = h->del.words_uploaded;
+    } else if (!strcmp(key, "deleted_queries_graph")) {
+        *out = h->n_del_graph.load();
+    } else if (!strcmp(key, "deleted_queries_exact")) {
+        *out = h->n_del_exact.load();
+    } else if (!strcmp(key, "deleted_overflow_exact")) {
+        *out = h->n_del_overflow.load();
     } else if (!strcmp(key, "coalesced_batches")) {
         *out = h->co.n_batches.load();
     } else if (!strcmp(key, "coalesced_queries")) {

@@ -10,17 +10,23 @@
 //                  FullVec  = dim x f32                         (vectors/src/full.rs:54-69)
 //   <dir>/layers/<n>  level u8, nb_nodes u32, m u16, then per node: id u32 + m x u32 neighbour
 //                  slots padded with 0xFFFFFFFF (graph/src/graph.rs:168-251)
+//   <dir>/deleted  an extension (hnsw_mark_deleted), written only when ids are deleted: count u64, then count
+//                  ids u32 in strictly ascending order.  The reference's load reads points, params and layers/*
+//                  only, so it ignores this file (which is why it is not under layers/, whose names it parses).
 // Deviation, documented: the reference writes deg > m rows longer than m slots, which corrupts
 // the file (graph.rs:172-178).  The writer here stores max(m, max degree) in the m field so
 // that every row fits and the file stays readable by the reference's own reader.
 
 #include <dirent.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <cstdio>
+#include <cerrno>
 #include <cstring>
 
+#include "deleted.h"
 #include "host_index.h"
 
 namespace hx {
@@ -308,6 +314,54 @@ int load_index(const std::string &dir, std::unique_ptr<HostIndex> *out) {
     }
     idx->version = 1;
     *out = std::move(idx);
+    return HNSW_OK;
+}
+
+int save_deleted(const std::string &dir, const std::vector<uint32_t> &ids) {
+    const std::string path = dir + "/deleted";
+    if (ids.empty()) {  // nothing deleted: exactly the reference's files, no stale sidecar from an earlier save
+        if (unlink(path.c_str()) != 0 && errno != ENOENT) {
+            set_error("Could not remove %s", path.c_str());
+            return HNSW_ERR_IO;
+        }
+        return HNSW_OK;
+    }
+    std::vector<uint8_t> b;
+    b.reserve(8 + ids.size() * 4);
+    put_u64(b, ids.size());
+    for (uint32_t id : ids) put_u32(b, id);
+    if (!write_file(path, b)) {
+        set_error("Could not write bytes to the deleted file");
+        return HNSW_ERR_IO;
+    }
+    return HNSW_OK;
+}
+
+int load_deleted(const std::string &dir, uint64_t n_points, std::vector<uint64_t> *words) {
+    words->clear();
+    const std::string path = dir + "/deleted";
+    struct stat st;
+    if (stat(path.c_str(), &st) != 0) return HNSW_OK;  // no file: nothing deleted
+    std::vector<uint8_t> b;
+    if (!read_file(path, &b) || b.size() < 8) {
+        set_error("Problem reading the deleted file");
+        return HNSW_ERR_IO;
+    }
+    const uint64_t count = get_u64(&b[0]);
+    if (count > n_points || b.size() != 8 + count * 4) {
+        set_error("deleted file: %llu ids in %zu bytes", (unsigned long long)count, b.size());
+        return HNSW_ERR_IO;
+    }
+    words->assign((n_points + 63) / 64, 0);
+    for (uint64_t i = 0; i < count; i++) {
+        const uint32_t id = get_u32(&b[8 + 4 * i]);
+        if (id >= n_points || (i > 0 && id <= get_u32(&b[4 + 4 * i]))) {
+            words->clear();
+            set_error("deleted file: id %u at position %llu is out of range or out of order", id, (unsigned long long)i);
+            return HNSW_ERR_IO;
+        }
+        (*words)[id >> 6] |= 1ull << (id & 63);
+    }
     return HNSW_OK;
 }
 

@@ -2,7 +2,9 @@
 // search_filtered.hip and their launchers.  gfx950 only.
 //
 // One allow-list per call, a bitmask over ids: id i is allowed iff i < allow_bits and bit i & 63 of
-// word i >> 6 is set (allow_bits is already clamped to the index length by the caller).
+// word i >> 6 is set (allow_bits is already clamped to the index length by the caller); without a mask
+// (allow == nullptr) every id below allow_bits is.  The handle's deleted set (hnsw_mark_deleted) is a second
+// mask of the same layout, deny: an id is admissible iff it is allowed and not denied.
 #pragma once
 
 #include "device_index.h"
@@ -16,8 +18,10 @@ namespace hx {
 struct FilterArgs {
     const float *Q;            // nq x dim (device)
     const uint32_t *qsel;      // optional: launch block b serves query qsel[b]
-    const uint64_t *allow;     // mask words (device)
+    const uint64_t *allow;     // mask words (device), or nullptr: every id < allow_bits
     uint64_t allow_bits;       // min(caller's allow_bits, index length)
+    const uint64_t *deny;      // the deleted ids' mask words (device), or nullptr: nothing deleted
+    uint64_t deny_bits;        // ids the deny mask covers (a multiple of 64); ids beyond it are not denied
     uint32_t n, ef;            // results per query, ef' = max(ef, n, 1)
     uint32_t *out_ids;         // nq x n
     float *out_dists;          // nq x n
@@ -35,10 +39,11 @@ uint32_t filt_max_slots_log2(const DevView &v);
 // status HNSW_ERR_OVERFLOW and is run again by the caller with a larger table or answered by the exact path
 int launch_filtered_graph(const DevView &v, const FilterArgs &a, uint32_t nblocks, uint32_t slots_log2,
                           hipStream_t stream);
-// exact path, step 1: the ascending list of allowed ids.  word_base[b] = allowed ids in words [0, 64 b)
-// (computed by the caller, who counts A anyway); ids[A]
-int launch_filter_compact(const uint64_t *allow, uint64_t n_words, uint64_t allow_bits, const uint32_t *word_base,
-                          uint32_t *ids, hipStream_t stream);
+// exact path, step 1: the ascending list of admissible ids (a.allow, a.allow_bits, a.deny, a.deny_bits) in the
+// n_words words below allow_bits.  word_base[b] = admissible ids in words [0, 64 b) (computed by the caller, who
+// counts A anyway); ids[A]
+int launch_filter_compact(const FilterArgs &a, uint64_t n_words, const uint32_t *word_base, uint32_t *ids,
+                          hipStream_t stream);
 // exact path, step 2: top-n of the `nsel` queries (a.qsel, or the first nsel) over the A listed ids; part holds
 // nsel x nseg x n keys of scratch.  Writes ids, dists, counts and stats (n_dist = A, n_exp = sum_deg = 0).
 uint32_t filt_exact_segments(uint64_t A, uint32_t nsel);

@@ -6,13 +6,14 @@
 //   F, the frontier: unexpanded keys only, capacity ef' -- popping its head shifts the list one lane left;
 //   R, the results: allowed keys only, capacity ef'.
 // A key is admitted when R is not full or it is below R's largest; an admitted key enters F, and R as well
-// when its id is allowed (one mask word is read per admitted key).  The loop stops when F is empty or its
+// when its id is allowed (one mask word is read per admitted key, and one word of the deleted set's mask when
+// the handle has deleted ids and the key got past the allow test).  The loop stops when F is empty or its
 // head lies above a full R's largest.  Keys of one pass over a row are admitted against the bound at the
 // start of the pass and merged at once; that gives the expansions, counters and R of the one-key-at-a-time
 // loop ("Filtered search").  One row per pass, read from the compact layout (adj0 + rows), so
 // the inline-rows copy does not matter.
 //
-// Exact path: hx_filt_compact_kernel lists the allowed ids in ascending order; hx_filt_scan_kernel scans
+// Exact path: hx_filt_compact_kernel lists the allowed, undeleted ids in ascending order; hx_filt_scan_kernel scans
 // one segment of that list per block and keeps its n best (the shape of hx_brute_kernel),
 // hx_filt_merge_kernel merges a query's segments.
 //
@@ -154,8 +155,12 @@ __device__ __forceinline__ bool filt_visit(uint32_t *tab, uint32_t slots_log2, u
     }
 }
 
+// admissible: allowed (below allow_bits, and its bit set when there is a mask) and not deleted.  The two pointer
+// tests are uniform over the wave (kernel arguments); a mask word is read only for an id that got that far.
 __device__ __forceinline__ bool filt_allowed(const FilterArgs &a, uint32_t id) {
-    return (uint64_t)id < a.allow_bits && ((a.allow[id >> 6] >> (id & 63)) & 1ull) != 0;
+    if ((uint64_t)id >= a.allow_bits) return false;
+    if (a.allow && ((a.allow[id >> 6] >> (id & 63)) & 1ull) == 0) return false;
+    return !(a.deny && (uint64_t)id < a.deny_bits && ((a.deny[id >> 6] >> (id & 63)) & 1ull) != 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -429,19 +434,19 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
 }
 
 // ---------------------------------------------------------------------------------------------
-// Exact path.  Compaction: one wave per 64 mask words; lane l owns word 64 b + l and writes its set bits'
-// ids at word_base[b] + (allowed ids of the wave's lower lanes).
+// Exact path.  Compaction: one wave per 64 mask words; lane l owns word 64 b + l and writes its admissible ids at
+// word_base[b] + (admissible ids of the wave's lower lanes).
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) hx_filt_compact_kernel(const uint64_t *allow, uint64_t n_words,
-                                                             uint64_t allow_bits, const uint32_t *word_base,
-                                                             uint32_t *ids) {
+__global__ void __launch_bounds__(64) hx_filt_compact_kernel(const FilterArgs a, uint64_t n_words,
+                                                             const uint32_t *word_base, uint32_t *ids) {
     const int lane = threadIdx.x;
     const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
-    u64 bits = w < n_words ? allow[w] : 0;
-    if (w * 64 + 64 > allow_bits) {  // ids at and beyond allow_bits are not allowed
-        const uint64_t keep = allow_bits > w * 64 ? allow_bits - w * 64 : 0;
+    u64 bits = w < n_words ? (a.allow ? a.allow[w] : ~0ull) : 0;
+    if (w * 64 + 64 > a.allow_bits) {  // ids at and beyond allow_bits are not allowed
+        const uint64_t keep = a.allow_bits > w * 64 ? a.allow_bits - w * 64 : 0;
         bits &= keep >= 64 ? ~0ull : ((1ull << keep) - 1);
     }
+    if (a.deny && w * 64 < a.deny_bits) bits &= ~a.deny[w];  // (deny_bits is a multiple of 64)
     const uint32_t c = (uint32_t)__popcll(bits);
     uint32_t incl = c;  // inclusive prefix over the lanes
 #pragma unroll
@@ -587,12 +592,11 @@ int launch_filtered_graph(const DevView &v, const FilterArgs &a, uint32_t nblock
     return launch_graph<HNSW_VEC_F32, 0, 0>(v, a, nblocks, slots_log2, stream);
 }
 
-int launch_filter_compact(const uint64_t *allow, uint64_t n_words, uint64_t allow_bits, const uint32_t *word_base,
-                          uint32_t *ids, hipStream_t stream) {
+int launch_filter_compact(const FilterArgs &a, uint64_t n_words, const uint32_t *word_base, uint32_t *ids,
+                          hipStream_t stream) {
     if (n_words == 0) return HNSW_OK;
     const uint64_t nb = (n_words + 63) / 64;
-    hipLaunchKernelGGL(hx_filt_compact_kernel, dim3((uint32_t)nb), dim3(64), 0, stream, allow, n_words, allow_bits,
-                       word_base, ids);
+    hipLaunchKernelGGL(hx_filt_compact_kernel, dim3((uint32_t)nb), dim3(64), 0, stream, a, n_words, word_base, ids);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("filter compaction kernel launch: %s", hipGetErrorString(e));

@@ -12,6 +12,10 @@ search by running on its own stream.
 
 `local_search` is a callable so that the plumbing can be exercised with gloo on CPU (tests) while
 production passes the HIP search (`make_device_search`).
+
+Deleted ids (HNSW.mark_deleted) are not part of a replica: the set belongs to each handle, and neither
+HNSW.replicate nor hnsw_snapshot_describe / _adopt carries it.  A caller that deletes ids marks the same ids on
+every rank's replica.
 """
 import torch
 import torch.distributed as dist

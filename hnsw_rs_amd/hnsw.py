@@ -339,6 +339,38 @@ class HNSW:
         check(self._L.hnsw_brute_force_fast(self._h, _p(Q, _f32p), nq, k, _p(ids, _u32p), _p(dists, _f32p)))
         return ids, dists
 
+    # ---- deletion (include/hnsw_mi355x.h: deleted ids stay in the graph, no search returns them) ---------------
+    def _ids(self, ids):
+        a = np.asarray(ids).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() > _lib.UINT32_MAX):
+            raise HnswError(_lib.ERR_ARG, "ids must be in [0, 2^32)")
+        return np.ascontiguousarray(a, dtype=np.uint32)
+
+    def mark_deleted(self, ids):
+        """hnswlib's mark_deleted for an id or an array of ids; every id must be < len (else nothing changes)"""
+        a = self._ids(ids)
+        check(self._L.hnsw_mark_deleted(self._h, _p(a, _u32p), a.shape[0]))
+
+    def unmark_deleted(self, ids):
+        a = self._ids(ids)
+        check(self._L.hnsw_unmark_deleted(self._h, _p(a, _u32p), a.shape[0]))
+
+    def is_deleted(self, node):
+        out = C.c_int()
+        check(self._L.hnsw_is_deleted(self._h, int(node), C.byref(out)))
+        return bool(out.value)
+
+    def deleted_count(self):
+        return int(self._L.hnsw_deleted_count(self._h))
+
+    def deleted_ids(self):
+        """-> the deleted ids, ascending (uint32)"""
+        n = C.c_uint64()
+        check(self._L.hnsw_get_deleted(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        check(self._L.hnsw_get_deleted(self._h, _p(out, _u32p), out.shape[0], C.byref(n)))
+        return out
+
     # ---- accessors ------------------------------------------------------------------------------
     def len(self):
         return int(self._L.hnsw_len(self._h))
@@ -404,7 +436,7 @@ class HNSW:
 
     def stat(self, key):
         """hnsw_get_stat: "uploads", "point_patches", "patch_fallbacks", "coalesced_batches", "coalesced_queries",
-        "coalesced_max_batch" """
+        "coalesced_max_batch", "deleted", "deleted_mask_words_uploaded", "deleted_queries_graph", ... (the header) """
         b = C.c_uint64()
         check(self._L.hnsw_get_stat(self._h, key.encode(), C.byref(b)))
         return b.value

@@ -186,8 +186,10 @@ int hnsw_search_batch(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, ui
  *   2  the exact path for a graph-path query whose visited set filled the largest table (32768 slots, 24576 ids,
  *      checked before each pass of up to 64 (f32) / 32 (8-bit) ids), instead of HNSW_ERR_OVERFLOW.
  * A == 0 gives count 0 for every query.  The cosine option applies to the queries first.  Per-query errors
- * (HNSW_ERR_NAN_INPUT) as hnsw_search_batch.  Not provided: per-query masks, a device-pointer form, coalescing of
- * one-query calls, filtered sharded search, the Rust shim's binding, and a mask stored with the index (deletion). */
+ * (HNSW_ERR_NAN_INPUT) as hnsw_search_batch.  The handle's deleted ids (hnsw_mark_deleted) are never allowed: the
+ * effective mask is allow AND NOT deleted, and the result equals the same call with that mask on a handle with
+ * nothing deleted.  Not provided: per-query masks, a device-pointer form of a filtered call, coalescing of one-query
+ * filtered calls, filtered sharded search and the Rust shim's binding. */
 int hnsw_search_batch_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
                                const uint64_t *allow, uint64_t allow_bits, uint32_t *ids, float *dists,
                                uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths /* 0/1/2 or NULL */);
@@ -230,6 +232,39 @@ int hnsw_brute_force(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uin
 int hnsw_brute_force_fast(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids,
                           float *dists);
 
+/* ---- deletion (an extension: the reference has none; hnswlib's mark_deleted / unmark_deleted) -------------------
+ * A deleted id stays a node of the graph: it is still traversed, still an entry point and still linked by later
+ * builds (a tombstone), but NO SEARCH RETURNS IT.  hnsw_get_vector, hnsw_distance, the layer accessors,
+ * hnsw_search_layer and hnsw_distance_batch (seams that mirror the reference's units) do not change.
+ *   - Nothing deleted (hnsw_deleted_count == 0, also after every marked id was unmarked): every entry point takes
+ *     exactly the code path, results and counters it takes without this feature.
+ *   - Ids deleted: hnsw_search_batch (and hnsw_search, still coalesced: each caller gets what a lone
+ *     hnsw_search_batch of its query returns) answers as hnsw_search_batch_filtered with every id < hnsw_len allowed
+ *     and the deleted ids taken out -- ids, dists, counts and stats, path chosen by "filter_exact_max".  So n <= 64,
+ *     ef' = max(ef, n, 1) <= 256 when the graph path is taken (else HNSW_ERR_ARG), and when ef < n the call returns
+ *     up to n ids, not ef as without deletions.  Queries per path: hnsw_get_stat "deleted_queries_graph",
+ *     "deleted_queries_exact", "deleted_overflow_exact".
+ *     hnsw_search_batch_device always takes the graph path (enqueued on `stream`, no synchronisation) and _finish
+ *     re-runs overflowing queries with larger tables, up to the graph path's largest, then answers those still
+ *     overflowing by the exact path: the results of the host form with "filter_exact_max" = -1.
+ *     hnsw_brute_force returns the top k of the undeleted ids (the filtered exact path: same arithmetic, same (dist,
+ *     id) order, k <= 64); hnsw_brute_force_fast returns HNSW_ERR_ARG (its k + 8 re-rank cannot promise k live ids).
+ *   - Marking and unmarking need no GPU: they change the host set and note the 64-id words they touched; the next
+ *     search that needs the HBM copy sends only those words (no snapshot upload; "deleted_mask_words_uploaded").
+ *     Like insert_*, they must not run concurrently with anything else on the handle.
+ *   - hnsw_clone and hnsw_set_device carry the set; insert_*, import_points leave it as it is (new ids are live).
+ *     hnsw_save writes it as the file `deleted` (see hnsw_save); hnsw_snapshot_describe / _adopt do not carry it:
+ *     the set is per handle, a caller marks the same ids on every replica.
+ * Not provided: reuse or compaction of deleted slots (hnswlib's replace_deleted), removal of nodes from the graph,
+ * the Rust shim's binding. */
+/* ids[k], each < hnsw_len (else HNSW_ERR_ARG and the set is unchanged); marking a deleted id again is a no-op */
+int hnsw_mark_deleted(hnsw_index *h, const uint32_t *ids, uint64_t k);
+int hnsw_unmark_deleted(hnsw_index *h, const uint32_t *ids, uint64_t k);
+int hnsw_is_deleted(const hnsw_index *h, uint32_t id, int *out);
+uint64_t hnsw_deleted_count(const hnsw_index *h);
+/* the deleted ids, ascending, up to cap of them; *n receives the count (like hnsw_layer_nodes) */
+int hnsw_get_deleted(const hnsw_index *h, uint32_t *ids, uint64_t cap, uint64_t *n);
+
 /* ---- accessors ----------------------------------------------------------------------------- */
 uint64_t hnsw_len(const hnsw_index *h);                                   /* template.rs:146 */
 /* HNSW::distance(a, b) -> Option<f32>, template.rs:150-152: HNSW_ERR_ARG stands for None */
@@ -258,7 +293,10 @@ int hnsw_check_param_compliance(const hnsw_index *h, int *ok);
 /* ---- persistence ---------------------------------------------------------------------------- */
 /* HNSW::save / HNSW::load, template.rs:43-131: directory with `points`, `params`, `layers/<n>`,
  * all big-endian, byte-compatible with the reference's Serializer impls (params.rs:78-114,
- * points.rs:124-145, point.rs:57-75, quant.rs:102-124, graph.rs:168-251). */
+ * points.rs:124-145, point.rs:57-75, quant.rs:102-124, graph.rs:168-251).  With ids deleted, save also writes
+ * the file `deleted` (count u64, then count ids u32 in strictly ascending order, big-endian), which the reference's
+ * load ignores; with none it writes exactly the files above and removes a stale `deleted`.  load restores the set
+ * and returns HNSW_ERR_IO for a `deleted` that is short, longer than its count, unsorted or holds an id >= len. */
 int hnsw_save(const hnsw_index *h, const char *dir);
 int hnsw_load(const char *dir, hnsw_index **out);
 
@@ -315,7 +353,10 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * larger one) and "build_kept_last_edges" (edges a prune dropped on one side only because they were the other
  * node's last edge -- the drop kernel's refusals plus the seed's clamp restores -- mirrored after the build; in the
  * sharded build every rank reports the whole build's, like "build_points"); hnsw_search_batch_filtered's queries by
- * path: "filtered_queries_graph" (0), "filtered_queries_exact" (1), "filtered_overflow_exact" (2) */
+ * path: "filtered_queries_graph" (0), "filtered_queries_exact" (1), "filtered_overflow_exact" (2); deletion:
+ * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
+ * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
+ * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
 int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out);
 
 /* ---- replication of the HBM snapshot over the GPUs of a node ----------------------------------- */
