@@ -117,6 +117,9 @@ SYMBOLS = {
     "hnsw_snapshot_commit": (C.c_int, [vp]),
     "hnsw_bench_batch_threads": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                            C.POINTER(C.c_double)]),
+    "hnsw_kernel_log": (C.c_int, [C.c_int]),
+    "hnsw_kernel_log_get": (C.c_int, [C.c_char_p, C.c_uint64, u64p]),
+    "hnsw_kernel_name": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64, u64p]),
     "hnsw_synth_rows": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, f32p, C.c_uint32]),
     "hnsw_draw_levels": (C.c_int, [C.c_uint32, C.c_uint64, u8p]),
 }

@@ -169,7 +169,7 @@ hx_pair_distance_kernel(const float *X, uint32_t d, const float *Q, const uint32
 }
 
 int launch_row_norms(const DevView &v, float *d_xn, hipStream_t stream) {
-    hipLaunchKernelGGL(hx_row_norms_kernel, dim3((v.n_points + 255) / 256), dim3(256), 0, stream,
+    HX_LAUNCH(hx_row_norms_kernel, dim3((v.n_points + 255) / 256), dim3(256), 0, stream,
                        reinterpret_cast<const float *>(v.rows), v.n_points, v.dim, d_xn);
     return hipGetLastError() == hipSuccess ? HNSW_OK : HNSW_ERR_HIP;
 }
@@ -198,7 +198,7 @@ int launch_brute_mfma(const DevView &v, const float *d_xn, const float *d_Q, uin
         }
     }
     const uint32_t ntiles = (nq + MF_QT - 1) / MF_QT;
-    hipLaunchKernelGGL(kern, dim3(nseg, ntiles), dim3(256), lds, stream, reinterpret_cast<const float *>(v.rows), d_xn,
+    HX_LAUNCH(kern, dim3(nseg, ntiles), dim3(256), lds, stream, reinterpret_cast<const float *>(v.rows), d_xn,
                        v.n_points, v.dim, d_Q, nq, nseg, out_s, out_i);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -211,7 +211,7 @@ int launch_brute_mfma(const DevView &v, const float *d_xn, const float *d_Q, uin
 int launch_pair_distance(const DevView &v, const float *d_Q, const uint32_t *d_qidx, const uint32_t *d_pidx, uint64_t n,
                          float *d_out, hipStream_t stream) {
     if (n == 0) return HNSW_OK;
-    hipLaunchKernelGGL(hx_pair_distance_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream,
+    HX_LAUNCH(hx_pair_distance_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream,
                        reinterpret_cast<const float *>(v.rows), v.dim, d_Q, d_qidx, d_pidx, n, d_out);
     return hipGetLastError() == hipSuccess ? HNSW_OK : HNSW_ERR_HIP;
 }

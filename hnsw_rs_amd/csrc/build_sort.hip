@@ -82,7 +82,7 @@ int filter_edge_records(const uint64_t *keys, const uint32_t *vals, uint32_t n, 
                         uint64_t *out_keys, uint32_t *out_vals, uint32_t *out_count, uint32_t out_cap, int32_t *status,
                         hipStream_t stream) {
     if (n == 0) return HNSW_OK;
-    hipLaunchKernelGGL(hx_filter_records_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, keys, vals, n, rank, world, out_keys,
+    HX_LAUNCH(hx_filter_records_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, keys, vals, n, rank, world, out_keys,
                        out_vals, out_count, out_cap, status);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -6,6 +6,7 @@
 
 #include "deleted.h"
 #include "hip_util.h"
+#include "kernel_log.h"
 
 namespace hx {
 
@@ -98,7 +99,7 @@ int DeletedSet::sync(int device, hipStream_t stream) {
             pairs[2 * i + 1] = words[dirty[i]];
         }
         HIP_TRY(hipMemcpyAsync(d_stage, pairs.data(), np * 16, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(hx_deleted_scatter_kernel, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, stream, d_words,
+        HX_LAUNCH(hx_deleted_scatter_kernel, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, stream, d_words,
                            (const uint64_t *)d_stage, np);
         HIP_TRY(hipGetLastError());
         words_uploaded += np;

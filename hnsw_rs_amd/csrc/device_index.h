@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "host_index.h"
+#include "kernel_log.h"
 
 namespace hx {
 

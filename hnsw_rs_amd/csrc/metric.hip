@@ -31,7 +31,7 @@ __global__ void __launch_bounds__(64) hx_normalise_rows_kernel(float *rows, uint
 
 int launch_normalise_rows(float *d_rows, uint64_t n, uint32_t d, hipStream_t stream) {
     if (n == 0) return HNSW_OK;
-    hipLaunchKernelGGL(hx_normalise_rows_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, d_rows, n, d);
+    HX_LAUNCH(hx_normalise_rows_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, d_rows, n, d);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("normalise kernel launch: %s", hipGetErrorString(e));

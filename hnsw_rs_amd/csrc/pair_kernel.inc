@@ -592,7 +592,7 @@ int launch_pair(const LeanArgs &a, uint32_t nblocks, hipStream_t stream) {
             return HNSW_ERR_HIP;
         }
     }
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(128), lds, stream, a);
+    HX_LAUNCH(kern, dim3(nblocks), dim3(128), lds, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("search kernel launch: %s", hipGetErrorString(e));

@@ -547,7 +547,7 @@ int launch_graph_r(const DevView &v, const FilterArgs &a, uint32_t nblocks, uint
             return HNSW_ERR_HIP;
         }
     }
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
+    HX_LAUNCH(kern, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("filtered search kernel launch: %s", hipGetErrorString(e));
@@ -596,7 +596,7 @@ int launch_filter_compact(const FilterArgs &a, uint64_t n_words, const uint32_t 
                           hipStream_t stream) {
     if (n_words == 0) return HNSW_OK;
     const uint64_t nb = (n_words + 63) / 64;
-    hipLaunchKernelGGL(hx_filt_compact_kernel, dim3((uint32_t)nb), dim3(64), 0, stream, a, n_words, word_base, ids);
+    HX_LAUNCH(hx_filt_compact_kernel, dim3((uint32_t)nb), dim3(64), 0, stream, a, n_words, word_base, ids);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("filter compaction kernel launch: %s", hipGetErrorString(e));
@@ -621,14 +621,14 @@ int launch_filtered_exact(const DevView &v, const FilterArgs &a, uint32_t nsel, 
     }
     const size_t lds = 64 * 8 + (((v.kind == HNSW_VEC_QUANT8 ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4) + 15) & ~15ull);
     if (v.kind == HNSW_VEC_QUANT8)
-        hipLaunchKernelGGL(hx_filt_scan_kernel<HNSW_VEC_QUANT8>, dim3(nseg, nsel), dim3(64), lds, stream, v, a, ids, A,
+        HX_LAUNCH(hx_filt_scan_kernel<HNSW_VEC_QUANT8>, dim3(nseg, nsel), dim3(64), lds, stream, v, a, ids, A,
                            nseg, part, part_status);
     else
-        hipLaunchKernelGGL(hx_filt_scan_kernel<HNSW_VEC_F32>, dim3(nseg, nsel), dim3(64), lds, stream, v, a, ids, A,
+        HX_LAUNCH(hx_filt_scan_kernel<HNSW_VEC_F32>, dim3(nseg, nsel), dim3(64), lds, stream, v, a, ids, A,
                            nseg, part, part_status);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(hx_filt_merge_kernel, dim3(nsel), dim3(64), 0, stream, a, A, nseg, part, part_status);
+        HX_LAUNCH(hx_filt_merge_kernel, dim3(nsel), dim3(64), 0, stream, a, A, nseg, part, part_status);
         e = hipGetLastError();
     }
     if (e != hipSuccess) {

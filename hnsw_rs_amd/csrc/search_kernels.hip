@@ -2462,7 +2462,7 @@ int launch_insert(const DevView &v, const InsertArgs &a, uint32_t nblocks, hipSt
             return HNSW_ERR_HIP;
         }
     }
-    hipLaunchKernelGGL(kfn, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
+    HX_LAUNCH(kfn, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("insert kernel launch: %s", hipGetErrorString(e));
@@ -2755,7 +2755,7 @@ static int launch_connect_rs(const DevView &v, const ConnectArgs &a, hipStream_t
         kfn = v.dim == 100   ? hx_connect_kernel<HNSW_VEC_F32, 100, RS>
               : v.dim == 128 ? hx_connect_kernel<HNSW_VEC_F32, 128, RS>
                              : hx_connect_kernel<HNSW_VEC_F32, 0, RS>;
-    hipLaunchKernelGGL(kfn, dim3(a.count), dim3(64), lds, stream, v, a);
+    HX_LAUNCH(kfn, dim3(a.count), dim3(64), lds, stream, v, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("connect kernel launch: %s", hipGetErrorString(e));
@@ -2772,9 +2772,9 @@ static int launch_connect_wide(const DevView &v, const ConnectArgs &a, hipStream
         ((v.kind == HNSW_VEC_QUANT8 ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4) + 15) & ~15ull;
     const size_t lds = 2 * 64 * RS * 8 + yq_bytes;
     if (v.kind == HNSW_VEC_QUANT8)
-        hipLaunchKernelGGL((hx_connect_kernel<HNSW_VEC_QUANT8, 0, RS>), dim3(a.count), dim3(64), lds, stream, v, a);
+        HX_LAUNCH((hx_connect_kernel<HNSW_VEC_QUANT8, 0, RS>), dim3(a.count), dim3(64), lds, stream, v, a);
     else
-        hipLaunchKernelGGL((hx_connect_kernel<HNSW_VEC_F32, 0, RS>), dim3(a.count), dim3(64), lds, stream, v, a);
+        HX_LAUNCH((hx_connect_kernel<HNSW_VEC_F32, 0, RS>), dim3(a.count), dim3(64), lds, stream, v, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("connect kernel launch: %s", hipGetErrorString(e));
@@ -2797,11 +2797,11 @@ int launch_remove(const DevView &v, const ConnectArgs &a, hipStream_t stream) {
     if (a.count == 0) return HNSW_OK;
     const uint32_t S = std::max(v.S0, v.S1);
     if (S <= 64)
-        hipLaunchKernelGGL(hx_remove_kernel<1>, dim3(a.count), dim3(64), 0, stream, v, a);
+        HX_LAUNCH(hx_remove_kernel<1>, dim3(a.count), dim3(64), 0, stream, v, a);
     else if (S <= 128)
-        hipLaunchKernelGGL(hx_remove_kernel<2>, dim3(a.count), dim3(64), 0, stream, v, a);
+        HX_LAUNCH(hx_remove_kernel<2>, dim3(a.count), dim3(64), 0, stream, v, a);
     else if (S <= 256)
-        hipLaunchKernelGGL(hx_remove_kernel<4>, dim3(a.count), dim3(64), 0, stream, v, a);
+        HX_LAUNCH(hx_remove_kernel<4>, dim3(a.count), dim3(64), 0, stream, v, a);
     else {
         set_error("on-device build: adjacency rows of %u slots (m > 128)", S);
         return HNSW_ERR_ARG;
@@ -2817,7 +2817,7 @@ int launch_remove(const DevView &v, const ConnectArgs &a, hipStream_t stream) {
 int launch_scatter_rows(uint32_t *dst, uint32_t S, const uint32_t *d_row_index, const uint32_t *d_data,
                         uint32_t n, hipStream_t stream) {
     if (n == 0) return HNSW_OK;
-    hipLaunchKernelGGL(hx_scatter_rows_kernel, dim3(n), dim3(64), 0, stream, dst, S, d_row_index, d_data, n);
+    HX_LAUNCH(hx_scatter_rows_kernel, dim3(n), dim3(64), 0, stream, dst, S, d_row_index, d_data, n);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("scatter kernel launch: %s", hipGetErrorString(e));
@@ -2899,7 +2899,7 @@ static int launch_one(const DevView &v, const SearchArgs &a_in, uint32_t nblocks
             return HNSW_ERR_HIP;
         }
     }
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
+    HX_LAUNCH(kern, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("search kernel launch: %s", hipGetErrorString(e));
@@ -2924,7 +2924,7 @@ static int launch_two(const DevView &v, const SearchArgs &a, uint32_t nblocks, u
             return HNSW_ERR_HIP;
         }
     }
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(128), lds, stream, v, a, slots_log2);
+    HX_LAUNCH(kern, dim3(nblocks), dim3(128), lds, stream, v, a, slots_log2);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("two-wave search kernel launch: %s", hipGetErrorString(e));
@@ -2953,7 +2953,8 @@ static int launch_r(const DevView &v, const SearchArgs &a, uint32_t nblocks, uin
     // the inline-rows variant needs one pass to cover a whole layer-0 row
     // (block images of rows wider than 5 pieces per half would not leave 4 waves per CU: not built)
     constexpr bool CAN_FAT = (KIND == HNSW_VEC_QUANT8 && P > 0 && P <= 5);
-    if constexpr (CAN_FAT) {
+    // (row_stride == 32 P and 16 row_stride % 1024 == 0 together need an even P: the odd ones are not built)
+    if constexpr (CAN_FAT && P % 2 == 0) {
         // 16 rows per wave must be whole 1-KiB DMA pieces: row_stride * 16 % 1024 == 0
         if (v.fat != nullptr && v.S0 == 32 && a.layer_lo == 0 && a.entries == nullptr &&
             a.layer_hi == (int32_t)v.nb_layers - 1 && a.ef_upper == 1 && (16u * v.row_stride) % 1024u == 0 &&
@@ -2979,12 +2980,18 @@ static int launch_r(const DevView &v, const SearchArgs &a, uint32_t nblocks, uin
             cus = 256;
         return (uint32_t)cus;
     }();
+    // (every caller's table has at least default_slots_log2(ef_max) slots -- 2^13 above ef 112 at S0 = 32 -- so
+    // fat_lds fits at four list registers only for P <= 2 and at eight only for P = 1: the others are not built)
+    constexpr bool FAT4 = CAN_FAT && P <= 2, FAT8 = CAN_FAT && P <= 1;
     if (CAN_FAT && v.fat != nullptr && v.S0 == 32 && a.layer_lo == 0 && fat_lds <= 40 * 1024 &&
         nblocks <= 4 * n_cu) {
         if (ef_max <= 64) return launch_one<KIND, P, DS, 1, CAN_FAT>(v, a, nblocks, slots_log2, stream);
         if (ef_max <= 128) return launch_one<KIND, P, DS, 2, CAN_FAT>(v, a, nblocks, slots_log2, stream);
-        if (ef_max <= 256) return launch_one<KIND, P, DS, 4, CAN_FAT>(v, a, nblocks, slots_log2, stream);
-        if (ef_max <= 512) return launch_one<KIND, P, DS, 8, CAN_FAT>(v, a, nblocks, slots_log2, stream);
+        if (ef_max <= 256) {
+            if constexpr (FAT4) return launch_one<KIND, P, DS, 4, true>(v, a, nblocks, slots_log2, stream);
+        } else if (ef_max <= 512) {
+            if constexpr (FAT8) return launch_one<KIND, P, DS, 8, true>(v, a, nblocks, slots_log2, stream);
+        }
     }
     if (ef_max <= 64) return launch_one<KIND, P, DS, 1, false>(v, a, nblocks, slots_log2, stream);
     if (ef_max <= 128) return launch_one<KIND, P, DS, 2, false>(v, a, nblocks, slots_log2, stream);
@@ -3292,9 +3299,9 @@ static int launch_spill(const DevView &v, const SearchArgs &a, uint32_t nblocks,
         sp.tab_log2 = tab_log2;
         sp.q_first = first;
         if (v.kind == HNSW_VEC_QUANT8)
-            hipLaunchKernelGGL(hx_search_spill_kernel<HNSW_VEC_QUANT8>, dim3(n), dim3(64), yq_bytes, stream, v, a, sp);
+            HX_LAUNCH(hx_search_spill_kernel<HNSW_VEC_QUANT8>, dim3(n), dim3(64), yq_bytes, stream, v, a, sp);
         else
-            hipLaunchKernelGGL(hx_search_spill_kernel<HNSW_VEC_F32>, dim3(n), dim3(64), yq_bytes, stream, v, a, sp);
+            HX_LAUNCH(hx_search_spill_kernel<HNSW_VEC_F32>, dim3(n), dim3(64), yq_bytes, stream, v, a, sp);
         hipError_t e = hipGetLastError();
         if (async) {
             (void)hipFreeAsync(mem, stream);
@@ -3447,10 +3454,10 @@ int launch_brute_force(const DevView &v, const float *d_Q, uint64_t nq, uint32_t
     const size_t lds =
         64 * 8 + (((v.kind == HNSW_VEC_QUANT8 ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4) + 15) & ~15ull);
     if (v.kind == HNSW_VEC_QUANT8)
-        hipLaunchKernelGGL(hx_brute_kernel<HNSW_VEC_QUANT8>, dim3(nseg, (uint32_t)nq), dim3(64), lds,
+        HX_LAUNCH(hx_brute_kernel<HNSW_VEC_QUANT8>, dim3(nseg, (uint32_t)nq), dim3(64), lds,
                            stream, v, d_Q, k, nseg, part_ids, part_dists, d_status);
     else
-        hipLaunchKernelGGL(hx_brute_kernel<HNSW_VEC_F32>, dim3(nseg, (uint32_t)nq), dim3(64), lds,
+        HX_LAUNCH(hx_brute_kernel<HNSW_VEC_F32>, dim3(nseg, (uint32_t)nq), dim3(64), lds,
                            stream, v, d_Q, k, nseg, part_ids, part_dists, d_status);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -3467,10 +3474,10 @@ int launch_distance_batch(const DevView &v, const float *d_q, const uint32_t *d_
         ((v.kind == HNSW_VEC_QUANT8 ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4) + 15) & ~15ull;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(2048, (k + 31) / 32);
     if (v.kind == HNSW_VEC_QUANT8)
-        hipLaunchKernelGGL(hx_distance_kernel<HNSW_VEC_QUANT8>, dim3(grid), dim3(64), lds, stream, v,
+        HX_LAUNCH(hx_distance_kernel<HNSW_VEC_QUANT8>, dim3(grid), dim3(64), lds, stream, v,
                            d_q, d_ids, k, d_out, d_status);
     else
-        hipLaunchKernelGGL(hx_distance_kernel<HNSW_VEC_F32>, dim3(grid), dim3(64), lds, stream, v,
+        HX_LAUNCH(hx_distance_kernel<HNSW_VEC_F32>, dim3(grid), dim3(64), lds, stream, v,
                            d_q, d_ids, k, d_out, d_status);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -1504,7 +1504,7 @@ int launch_lean_q8(const LeanArgs &a_in, uint32_t nblocks, hipStream_t stream) {
             return HNSW_ERR_HIP;
         }
     }
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), lds, stream, a);
+    HX_LAUNCH(kern, dim3(nblocks), dim3(64), lds, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("search kernel launch: %s", hipGetErrorString(e));
@@ -1555,7 +1555,7 @@ int launch_lean_one(const LeanArgs &a_in, uint32_t nblocks, hipStream_t stream) 
             return HNSW_ERR_HIP;
         }
     }
-    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(64), lds, stream, a);
+    HX_LAUNCH(kern, dim3(nblocks), dim3(64), lds, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error("search kernel launch: %s", hipGetErrorString(e));

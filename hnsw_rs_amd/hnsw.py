@@ -9,6 +9,7 @@ HIP kernels behind `hnsw_search_batch*` (there is no Python / CPU search path).
     ids = index.ann_by_vector(query, 10, 100)          # template.rs:306
     index.save(path); index = HNSW.load(path)          # template.rs:43,75
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -571,3 +572,42 @@ def device_count():
     c = C.c_int()
     check(_lib.lib().hnsw_device_count(C.byref(c)))
     return c.value
+
+
+def kernel_name(name):
+    """the kernel launch log's name for a kernel symbol (mangled or not): hnsw_kernel_name"""
+    raw = name.encode() if isinstance(name, str) else name
+    need = C.c_uint64()
+    check(_lib.lib().hnsw_kernel_name(raw, None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value)
+    check(_lib.lib().hnsw_kernel_name(raw, buf, need.value, C.byref(need)))
+    return buf.value.decode()
+
+
+class KernelLog(dict):
+    """{kernel instantiation name: launches} recorded while the `kernel_log()` block ran (a test seam)"""
+
+
+@contextlib.contextmanager
+def kernel_log():
+    """Record every kernel launch of the process for the duration of the block:
+
+        with H.kernel_log() as log:
+            index.search_batch(Q, 10, 64)
+        assert set(log) == {"hx_lean_f32_kernel<100, Lst<1>, 4>"}
+
+    The log is process-wide (launches from other threads count too) and is filled in when the block ends."""
+    L = _lib.lib()
+    log = KernelLog()
+    check(L.hnsw_kernel_log(1))
+    try:
+        yield log
+    finally:
+        check(L.hnsw_kernel_log(0))
+        need = C.c_uint64()
+        check(L.hnsw_kernel_log_get(None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        check(L.hnsw_kernel_log_get(buf, need.value, C.byref(need)))
+        for line in buf.value.decode().splitlines():
+            name, _, count = line.rpartition(" ")
+            log[name] = int(count)

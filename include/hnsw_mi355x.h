@@ -382,6 +382,19 @@ int hnsw_snapshot_describe(hnsw_index *h, hnsw_snapshot_desc *out);
 int hnsw_snapshot_adopt(hnsw_index *h, hnsw_snapshot_desc *inout);
 int hnsw_snapshot_commit(hnsw_index *h);
 
+/* ---- kernel launch log: a test seam, off by default ------------------------------------------- */
+/* Which kernel instantiations this process launched.  hnsw_kernel_log(1) clears the log and starts recording,
+ * hnsw_kernel_log(0) stops.  While recording, every launch of every kernel (search, filtered, distance, brute
+ * force, build) counts under the kernel it passed to the HIP runtime; the log is process-wide and thread-safe.
+ * Off, a launch pays one relaxed atomic load.  hnsw_kernel_log_get writes one line per instantiation launched
+ * since recording started, "<name> <count>\n", sorted by name; *needed = bytes including the terminating 0 (call
+ * with buf = NULL, cap = 0 to size it; HNSW_ERR_ARG when cap is too small).  Names are hnsw_kernel_name's. */
+int hnsw_kernel_log(int on);
+int hnsw_kernel_log_get(char *buf, uint64_t cap, uint64_t *needed);
+/* The name the log uses for a kernel symbol: demangled (when it is a mangled name), without the project's
+ * namespaces, the return type and the parameter list, e.g. "hx_search_kernel<1, 64, 256, 4, false>". */
+int hnsw_kernel_name(const char *name, char *buf, uint64_t cap, uint64_t *needed);
+
 /* ---- harness helpers (not part of the reference's API) --------------------------------------- */
 /* Synthetic "GloVe-shaped" data, counter-based so any row can be generated independently:
  * recipe 0 = low intrinsic dimension clusters (A), 1 = isotropic mixture (B), 2 = U[0,1)

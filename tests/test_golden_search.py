@@ -129,6 +129,34 @@ def test_two_restatements_agree_on_fresh_inputs(kind):
             assert np.array_equal(bf_ids[qi], i2) and np.array_equal(bf_d[qi].view(np.uint32), d2.view(np.uint32))
 
 
+@pytest.mark.parametrize("kind", [O.VEC_QUANT8, O.VEC_F32])
+def test_two_restatements_agree_on_edge_queries(kind):
+    """the kernel matrix's edge queries (tests/kernel_matrix.py): stored rows (distance 0 at the head of the list), a
+    constant row, rows plus a large offset and, f32, a row whose every distance overflows to +inf (ordered by id)"""
+    from tests.kernel_matrix import edge_queries
+    vs = rand_vectors(800, 40, 93)
+    lv = O.draw_levels(800, 8, 6)
+    orc = O.OracleHNSW(8, 20, 40, kind).insert_bulk(vs, lv)
+    idx = R.Index.from_csr(vs, kind, [orc.layer_csr(l) for l in range(orc.nb_layers)], orc.ep)
+    qs = edge_queries(vs, kind)
+    for n, ef in ((10, 10), (10, 100), (64, 300)):
+        ids, dists, counts, stats = orc.search_batch(qs, n, ef)
+        for qi in range(qs.shape[0]):
+            i2, d2, cn = R.ann_by_vector(idx, qs[qi], n, ef)
+            k = len(i2)
+            assert counts[qi] == k and np.array_equal(ids[qi, :k], i2), (n, ef, qi)
+            assert np.array_equal(dists[qi, :k].view(np.uint32), d2.view(np.uint32)), (n, ef, qi)
+            assert tuple(int(x) for x in stats[qi]) == cn, (n, ef, qi)
+        assert dists[0, 0] == 0 and ids[0, 0] == 3  # a stored row finds itself first
+        if kind == O.VEC_F32:  # every distance +inf: the list is the visited ids in id order
+            assert np.isinf(dists[-1, :counts[-1]]).all()
+            assert np.array_equal(ids[-1, :counts[-1]], np.sort(ids[-1, :counts[-1]]))
+    bf_ids, bf_d = orc.brute_force(qs, 7)
+    for qi in range(qs.shape[0]):
+        i2, d2 = R.brute_force(idx, qs[qi], 7)
+        assert np.array_equal(bf_ids[qi], i2) and np.array_equal(bf_d[qi].view(np.uint32), d2.view(np.uint32))
+
+
 # ---- the HIP path against the frozen vectors ----------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["search_testdata.npz", "search_synth10k.npz"])

@@ -44,35 +44,61 @@ def check_same(idx, orc, st, what):
     assert idx.stat("build_kept_last_edges") == st["kept_last_edges"], (what, idx.stat("build_kept_last_edges"), st)
 
 
-# (kind, d, m, ef_cons, n): every hx_insert_kernel<KIND, DS> that launch_insert picks (d = 100, 128, 256, 768 and the
-# generic DS = 0, both kinds), every hx_connect_kernel<KIND, DS, RS> (RS = 1 at d = 100, 128, 256, 768 and generic;
-# RS = 2 / 4 -- m = 64 / 128 -- generic, both kinds) and hx_remove_kernel<1 / 2 / 4>
+def I(kind, ds):
+    return "hx_insert_kernel<%d, %d>" % (kind, ds)
+
+
+def C(kind, ds, rs):
+    return "hx_connect_kernel<%d, %d, %d>" % (kind, ds, rs)
+
+
+Q8, F32 = H.VEC_QUANT8, H.VEC_F32
+REMOVE = {1: "hx_remove_kernel<1>", 2: "hx_remove_kernel<2>", 4: "hx_remove_kernel<4>"}
+
+# (kind, d, m, ef_cons, n, kernels): every hx_insert_kernel<KIND, DS> that launch_insert picks (d = 100, 128, 256, 768
+# and the generic DS = 0, both kinds), every hx_connect_kernel<KIND, DS, RS> (RS = 1 at d = 100, 128, 256, 768 and
+# generic; RS = 2 / 4 -- m = 64 / 128 -- generic, both kinds) and hx_remove_kernel<1 / 2 / 4>.  `kernels` names the
+# insert and connect instantiations the build must launch (the kernel log holds exactly these of the two templates)
+# and the remove instantiation it may launch
 CASES = [
-    pytest.param(H.VEC_QUANT8, 100, 16, 32, 20000, id="quant8-d100-default-schedule"),
-    pytest.param(H.VEC_F32, 100, 16, 32, 20000, id="f32-d100-default-schedule"),
-    pytest.param(H.VEC_QUANT8, 128, 16, 32, 4000, id="quant8-d128"),
-    pytest.param(H.VEC_QUANT8, 256, 16, 32, 4000, id="quant8-d256"),
-    pytest.param(H.VEC_QUANT8, 768, 16, 32, 4000, id="quant8-d768"),
-    pytest.param(H.VEC_F32, 128, 16, 32, 5000, id="f32-d128-coop-rows"),
-    pytest.param(H.VEC_F32, 256, 16, 32, 5000, id="f32-d256-row-stride-1024"),
-    pytest.param(H.VEC_F32, 768, 16, 32, 5000, id="f32-d768-row-stride-3072"),
-    pytest.param(H.VEC_F32, 33, 16, 32, 6000, id="f32-d33-generic"),
-    pytest.param(H.VEC_QUANT8, 60, 16, 32, 6000, id="quant8-d60-generic"),
-    pytest.param(H.VEC_QUANT8, 100, 24, 48, 8000, id="m24-64-slot-rows"),
-    pytest.param(H.VEC_F32, 48, 64, 48, 5000, id="f32-m64-128-slot-rows"),
-    pytest.param(H.VEC_QUANT8, 48, 64, 48, 5000, id="quant8-m64-128-slot-rows"),
-    pytest.param(H.VEC_F32, 60, 128, 48, 4000, id="f32-m128-256-slot-rows"),
-    pytest.param(H.VEC_QUANT8, 60, 128, 48, 4000, id="quant8-m128-256-slot-rows"),
-    pytest.param(H.VEC_QUANT8, 100, 16, 100, 6000, id="ef100-table-2-13"),
-    pytest.param(H.VEC_F32, 64, 16, 200, 6000, id="ef200-table-2-14"),
+    pytest.param(Q8, 100, 16, 32, 20000, (I(Q8, 100), C(Q8, 100, 1), REMOVE[1]), id="quant8-d100-default-schedule"),
+    pytest.param(F32, 100, 16, 32, 20000, (I(F32, 100), C(F32, 100, 1), REMOVE[1]), id="f32-d100-default-schedule"),
+    pytest.param(Q8, 128, 16, 32, 4000, (I(Q8, 128), C(Q8, 128, 1), REMOVE[1]), id="quant8-d128"),
+    pytest.param(Q8, 256, 16, 32, 4000, (I(Q8, 256), C(Q8, 256, 1), REMOVE[1]), id="quant8-d256"),
+    pytest.param(Q8, 768, 16, 32, 4000, (I(Q8, 768), C(Q8, 768, 1), REMOVE[1]), id="quant8-d768"),
+    pytest.param(F32, 128, 16, 32, 5000, (I(F32, 128), C(F32, 128, 1), REMOVE[1]), id="f32-d128-coop-rows"),
+    pytest.param(F32, 256, 16, 32, 5000, (I(F32, 256), C(F32, 0, 1), REMOVE[1]), id="f32-d256-row-stride-1024"),
+    pytest.param(F32, 768, 16, 32, 5000, (I(F32, 768), C(F32, 0, 1), REMOVE[1]), id="f32-d768-row-stride-3072"),
+    pytest.param(F32, 33, 16, 32, 6000, (I(F32, 0), C(F32, 0, 1), REMOVE[1]), id="f32-d33-generic"),
+    pytest.param(Q8, 60, 16, 32, 6000, (I(Q8, 0), C(Q8, 0, 1), REMOVE[1]), id="quant8-d60-generic"),
+    pytest.param(Q8, 100, 24, 48, 8000, (I(Q8, 100), C(Q8, 100, 1), REMOVE[1]), id="m24-64-slot-rows"),
+    pytest.param(F32, 48, 64, 48, 5000, (I(F32, 0), C(F32, 0, 2), REMOVE[2]), id="f32-m64-128-slot-rows"),
+    pytest.param(Q8, 48, 64, 48, 5000, (I(Q8, 0), C(Q8, 0, 2), REMOVE[2]), id="quant8-m64-128-slot-rows"),
+    pytest.param(F32, 60, 128, 48, 4000, (I(F32, 0), C(F32, 0, 4), REMOVE[4]), id="f32-m128-256-slot-rows"),
+    pytest.param(Q8, 60, 128, 48, 4000, (I(Q8, 0), C(Q8, 0, 4), REMOVE[4]), id="quant8-m128-256-slot-rows"),
+    pytest.param(Q8, 100, 16, 100, 6000, (I(Q8, 100), C(Q8, 100, 1), REMOVE[1]), id="ef100-table-2-13"),
+    pytest.param(F32, 64, 16, 200, 6000, (I(F32, 0), C(F32, 0, 1), REMOVE[1]), id="ef200-table-2-14"),
 ]
+# what these cases launch, for tests/test_kernel_matrix_complete.py
+BUILD_KERNELS = sorted({k for c in CASES for k in c.values[5]})
 
 
-@pytest.mark.parametrize("kind,d,m,ef_cons,n", CASES)
-def test_device_build_equals_the_restatement(kind, d, m, ef_cons, n):
+def check_kernels(log, kernels, what):
+    """the insert and connect instantiations are exactly `kernels`' ones, a remove (if any) is `kernels`' one"""
+    got = {k for k in log if k.startswith(("hx_insert_kernel<", "hx_connect_kernel<"))}
+    want = {k for k in kernels if not k.startswith("hx_remove_kernel<")}
+    assert got == want, (what, dict(log))
+    removes = {k for k in log if k.startswith("hx_remove_kernel<")}
+    assert removes <= set(kernels), (what, dict(log))
+
+
+@pytest.mark.parametrize("kind,d,m,ef_cons,n,kernels", CASES)
+def test_device_build_equals_the_restatement(kind, d, m, ef_cons, n, kernels):
     vs = H.synth_rows(0, 0xB17D0000 + d * 1000 + m, 0, n, d)
     lv = O.draw_levels(n, m, 0xB17D + m)
-    idx, orc, st = build_both(vs, lv, m, ef_cons, kind)
+    with H.kernel_log() as log:
+        idx, orc, st = build_both(vs, lv, m, ef_cons, kind)
+    check_kernels(log, kernels, "kind=%d d=%d m=%d" % (kind, d, m))
     # phase 1 reached the heuristic's special paths: a candidate set cut to its 512 nearest, and more than 128
     # candidates popped (the kernel's sweep window grows past its first 128)
     assert st["batches"] > 0 and st["heuristic_cut"] > 0 and st["heuristic_past_window"] > 0, st

@@ -127,13 +127,15 @@ def test_insert_vec_then_search_patches_the_live_snapshot(kind, d, n0, steps):
     nl[steps // 2] = index.nb_layers() + 1  # one insertion opens two new top layers and moves the entry point
     index.upload()
     up0, bytes0 = index.stat("uploads"), index.device_bytes()
-    for i in range(steps):
-        node = index.insert_vec(new[i], level=int(nl[i]))
-        assert node == orc.insert_vec(new[i], int(nl[i])) == n0 + i
-        got = index.ann_by_vector(qs[i], 10, 48)
-        assert got == [int(x) for x in orc.ann_by_vector(qs[i], 10, 48)], "step %d" % i
-        if i % 97 == 0:  # ... and the new point is found from its own vector
-            assert index.ann_by_vector(new[i], 1, 48) == [node]
+    with H.kernel_log() as log:
+        for i in range(steps):
+            node = index.insert_vec(new[i], level=int(nl[i]))
+            assert node == orc.insert_vec(new[i], int(nl[i])) == n0 + i
+            got = index.ann_by_vector(qs[i], 10, 48)
+            assert got == [int(x) for x in orc.ann_by_vector(qs[i], 10, 48)], "step %d" % i
+            if i % 97 == 0:  # ... and the new point is found from its own vector
+                assert index.ann_by_vector(new[i], 1, 48) == [node]
+    assert "hx_patch_kernel" in log, dict(log)  # the snapshot was patched in HBM
     assert index.stat("uploads") == up0, "an insert_vec threw the snapshot away"
     assert index.stat("point_patches") == steps and index.stat("patch_fallbacks") == 0
     assert index.device_bytes() < bytes0 * 1.3 + (1 << 20)
@@ -173,9 +175,11 @@ def test_insert_vec_with_overflowing_rows_and_inline_rows():
     up0 = index.stat("uploads")
     new = rand_vectors(60, d, 22)
     qs = rand_vectors(60, d, 23)
-    for i in range(60):
-        assert index.insert_vec(new[i], level=0) == orc.insert_vec(new[i], 0)
-        assert index.ann_by_vector(qs[i], 5, 30) == [int(x) for x in orc.ann_by_vector(qs[i], 5, 30)], "step %d" % i
+    with H.kernel_log() as log:
+        for i in range(60):
+            assert index.insert_vec(new[i], level=0) == orc.insert_vec(new[i], 0)
+            assert index.ann_by_vector(qs[i], 5, 30) == [int(x) for x in orc.ann_by_vector(qs[i], 5, 30)], "step %d" % i
+    assert {"hx_patch_kernel", "hx_fat_rebuild_kernel"} <= set(log), dict(log)  # rows and their inline copies patched
     assert index.stat("uploads") == up0 and index.stat("patch_fallbacks") == 0
     assert same_graph(index, orc)
     assert max(index.get_layer(0).degree(i) for i in range(n0)) > 32

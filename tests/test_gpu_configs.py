@@ -56,8 +56,12 @@ def test_the_generic_f32_kernel_still_agrees(f32_100d):
         "lv = O.draw_levels(n, m, 7)\n"
         "idx = H.HNSW.new(m, 32, d, H.VEC_F32); idx.insert_bulk_device(vs, 8, False, levels=lv)\n"
         "orc = oracle_from_product(idx, vs, lv)\n"
+        "idx.search_batch(qs[:1], 10, 1)\n"
         "for ef in (64, 68, 128, 192, 256):\n"
-        "    assert_search_equal(idx.search_batch(qs, 10, ef), orc.search_batch(qs, 10, ef, nthreads=8), 'generic ef=%%d' %% ef)\n"
+        "    with H.kernel_log() as log:\n"
+        "        got = idx.search_batch(qs, 10, ef)\n"
+        "    assert set(log) == {'hx_search_kernel<1, 25, 100, %%d, false>' %% (1 if ef <= 64 else 2 if ef <= 128 else 4)}, dict(log)\n"
+        "    assert_search_equal(got, orc.search_batch(qs, 10, ef, nthreads=8), 'generic ef=%%d' %% ef)\n"
         "print('generic ok')\n" % ROOT)
     out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, HNSW_MI355X_LEAN="0"),
                          capture_output=True, text=True, timeout=300)
@@ -103,8 +107,12 @@ def test_two_level_visited_set_of_the_eight_register_kernel(limit, kind):
         "lv = O.draw_levels(n, m, 7)\n"
         "idx = H.HNSW.new(m, 32, d, %d); idx.insert_bulk_device(vs, 8, False, levels=lv)\n"
         "orc = oracle_from_product(idx, vs, lv)\n"
+        "lst = {321: 6, 384: 6, 448: 7, 512: 8}  # the lean kernel's interleaved registers\n"
+        "name = 'hx_lean_f32_kernel<100, Lst<%%d>, 4>' if idx.vec_kind == H.VEC_F32 else 'hx_lean_q8_kernel<Lst<%%d> >'\n"
         "for ef in (321, 384, 448, 512):\n"
-        "    got = idx.search_batch(qs, 10, ef)\n"
+        "    with H.kernel_log() as log:\n"
+        "        got = idx.search_batch(qs, 10, ef)\n"
+        "    assert set(log) == {name %% lst[ef]}, dict(log)\n"
         "    assert_search_equal(got, orc.search_batch(qs, 10, ef, nthreads=8), 'two-level ef=%%d' %% ef)\n"
         "    assert int(np.asarray(got[3])[:, 0].max()) > 2500  # (the searches do reach past the early limits)\n"
         "assert_search_equal(idx.search_batch(qs[:64], 400, 512), orc.search_batch(qs[:64], 400, 512, nthreads=8), 'n=400')\n"
@@ -145,8 +153,13 @@ def test_two_level_visited_set_of_the_generic_kernel(limit):
         "    idx = H.HNSW.new(m, 32, d, kind); idx.insert_bulk_device(vs, 8, False, levels=lv)\n"
         "    idx.set_option('inline_rows', 0)\n"
         "    orc = oracle_from_product(idx, vs, lv)\n"
+        "    r8 = {(0, 36): '0, 2, 0', (1, 256): '1, 64, 256', (1, 52): '1, 0, 0', (0, 128): '0, 5, 128'}[(kind, d)]\n"
         "    for ef in (321, 400, 512, 700, 1024):\n"
-        "        assert_search_equal(idx.search_batch(qs, 10, ef), orc.search_batch(qs, 10, ef, nthreads=8), 'generic two-level kind %%d d %%d ef %%d' %% (kind, d, ef))\n"
+        "        with H.kernel_log() as log:\n"
+        "            got = idx.search_batch(qs, 10, ef)\n"
+        "        want = 'hx_search_kernel<%%s, 8, false>' %% r8 if ef <= 512 else 'hx_search_kernel<%%d, 0, 0, 16, false>' %% kind\n"
+        "        assert set(log) == {want}, (want, dict(log))\n"
+        "        assert_search_equal(got, orc.search_batch(qs, 10, ef, nthreads=8), 'generic two-level kind %%d d %%d ef %%d' %% (kind, d, ef))\n"
         "    g, w = idx.search_layer(0, qs[0], np.arange(5, dtype=np.uint32), 600), orc.search_layer(0, qs[0], np.arange(5, dtype=np.uint32), 600)\n"
         "    assert np.array_equal(g[0], w[0]) and np.array_equal(g[1].view(np.uint32), w[1].view(np.uint32)) and tuple(int(x) for x in g[2]) == tuple(int(x) for x in w[2]), 'search_layer seam'\n"
         "print('generic two-level ok')\n" % ROOT)
@@ -446,7 +459,9 @@ def test_cosine_option_is_l2_on_unit_vectors(kind):
     # (numpy float32, one left-to-right sum of squares: tests/test_host_build.py::_unit_rows), holding the same graph
     orc = oracle_from_product(cos, _unit_rows(vs), lv)
     for ef in (16, 64):
-        got = cos.search_batch(qs, 10, ef)
+        with H.kernel_log() as log:
+            got = cos.search_batch(qs, 10, ef)
+        assert "hx_normalise_rows_kernel" in log, dict(log)  # the queries are normalised on the device
         assert_search_equal(got, orc.search_batch(uq, 10, ef), "cosine vs oracle on unit rows, ef=%d" % ef)
         assert_search_equal(got, ref.search_batch(uq, 10, ef), "cosine ef=%d" % ef)
     for i in range(4):  # the one-query entry (coalescer path) normalises too

@@ -118,12 +118,17 @@ def test_search_batch_under_deletions(kind, d, cosine):
     Qr = unit(qs) if cosine else qs
     ep = int(index.params.ep)
     plain = index.search_batch(qs, 10, 64)
+    launched = set()
     for name, dead in patterns(index.len(), ep, d):
         index.mark_deleted(dead)
         for n, ef in ((10, 64), (64, 128), (10, 5)):
-            paths = check_batch(index, ridx, qs, n, ef, dead, Qr=Qr, what="%s n=%d ef=%d" % (name, n, ef))
+            with H.kernel_log() as log:
+                paths = check_batch(index, ridx, qs, n, ef, dead, Qr=Qr, what="%s n=%d ef=%d" % (name, n, ef))
             assert (paths == 0).all()
+            launched |= set(log)
         index.unmark_deleted(dead)
+    # once the mask is on the device, a search after (un)marking sends the touched words through the scatter kernel
+    assert "hx_deleted_scatter_kernel" in launched, launched
     # all but a handful: the exact path at the default filter_exact_max
     keep = [7, 1500, 2999, 640, 12]
     dead = [i for i in range(index.len()) if i not in keep]

@@ -271,11 +271,18 @@ def test_two_wave_kernel_is_parity_exact(synth20k):
         "vs = H.synth_rows(0, 0x5EED0001, 0, n, d); qs = H.synth_rows(0, 0x5EED0002, 0, 128, d)\n"
         "lv = O.draw_levels(n, m, 7)\n"
         "idx = H.HNSW.new(m, 32, d).insert_bulk(vs, 4, False, levels=lv)\n"
+        "idx.set_option('inline_rows', 1)\n"
         "orc = oracle_from_product(idx, vs, lv)\n"
+        "idx.search_batch(qs[:1], 10, 1)\n"
         "for ef in (1, 64, 100):\n"
-        "    assert_search_equal(idx.search_batch(qs, 10, ef), orc.search_batch(qs, 10, ef, nthreads=4), 'w2 ef=%%d' %% ef)\n"
+        "    with H.kernel_log() as log:\n"
+        "        got = idx.search_batch(qs, 10, ef)\n"
+        "    assert set(log) == {'hx_search2_kernel<4, 100, %%d>' %% (1 if ef <= 64 else 2)}, dict(log)\n"
+        "    assert_search_equal(got, orc.search_batch(qs, 10, ef, nthreads=4), 'w2 ef=%%d' %% ef)\n"
         "print('two-wave ok')\n" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    env = dict(os.environ, HNSW_MI355X_WAVES="2")
+    # inline rows and the lean 8-bit kernel off: the two-wave kernel serves only the inline-rows layout, and at
+    # d = 100 the lean kernel would take the search first
+    env = dict(os.environ, HNSW_MI355X_WAVES="2", HNSW_MI355X_LEAN_Q8="0")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "two-wave ok" in out.stdout, out.stdout + out.stderr
 
@@ -449,13 +456,18 @@ def gpu_built(request, build_inputs):
     cpu, vs, qs, lv = build_inputs
     dev = H.HNSW.new(16, 32, 100)
     dev.set_option("gpu_build", request.param)
-    dev.insert_bulk_device(vs, 8, False, levels=lv)
+    with H.kernel_log() as log:
+        dev.insert_bulk_device(vs, 8, False, levels=lv)
+    dev.build_mode, dev.build_kernels = request.param, dict(log)
     return dev, cpu, vs, qs, lv
 
 
 def test_device_build_makes_a_valid_graph(gpu_built):
     dev, _, vs, _, _ = gpu_built
     assert dev.len() == len(vs) and dev.assert_param_compliance()
+    # host connect: the changed rows go back to HBM through the row scatter; device connect: the connect kernel
+    want = "hx_scatter_rows_kernel" if dev.build_mode == 1 else "hx_connect_kernel<0, 100, 1>"
+    assert want in dev.build_kernels and "hx_insert_kernel<0, 100>" in dev.build_kernels, dev.build_kernels
     for layer in dev.iter_layers():
         ids, offs, nbrs = layer.csr()
         adj = {int(i): set(int(x) for x in nbrs[int(offs[k]):int(offs[k + 1])]) for k, i in enumerate(ids)}
@@ -560,7 +572,9 @@ def _sharded_build_worker(rank, world, port, outdir):
     vs = HH.synth_rows(0, 0x5EED0001, 0, n, d)
     lv = HH.draw_levels(m, n)
     idx = HH.HNSW.new(m, 32, d)
-    idx.insert_bulk_sharded(vs, 4, False, levels=lv)
+    with HH.kernel_log() as klog:
+        idx.insert_bulk_sharded(vs, 4, False, levels=lv)
+    np.save(os.path.join(outdir, "kernels%d.npy" % rank), np.array(sorted(klog)))
     out = {}
     for layer in idx.iter_layers():
         ids, offs, nbrs = layer.csr()
@@ -599,6 +613,10 @@ def test_sharded_device_build_two_ranks(tmp_path, world):
         for k in r0.files:  # identical replicas, edge for edge
             assert np.array_equal(r0[k], r1[k]), (r, k)
     assert r0["recall"][0] > 0.97 and r0["compliant"][0] == 1
+    # every rank ran the sharded build's own kernels: record filter, row packing, row application
+    for r in range(world):
+        ks = set(np.load(tmp_path / ("kernels%d.npy" % r)).tolist())
+        assert {"hx_filter_records_kernel", "hx_pack_rows_kernel", "hx_apply_rows_kernel"} <= ks, (r, ks)
     # every rank connected / pruned only the rows it owns and received the others: the rows owned sum to the rows
     # received by any one rank plus its own
     st = np.stack([np.load(tmp_path / ("stats%d.npy" % r)) for r in range(world)])

@@ -20,8 +20,20 @@ qs = H.synth_rows(0, 0x5EED0002, 0, nq, d, 8)
 lv = H.draw_levels(m, N)
 idx = H.HNSW.new(m, 32, d, H.VEC_F32).insert_bulk_device(vs, 8, False, levels=lv)
 orc = oracle_from_product(idx, vs, lv)
+
+
+def kernels(ef):
+    """the two-wave kernel of ef's list, and the one-wave kernel that re-runs the queries it gives up"""
+    lst = "Lst<1>" if ef <= 64 else "LstHT"
+    return "hx_pair_f32_kernel<100, %s>" % (lst + " " if lst.endswith(">") else lst), "hx_lean_f32_kernel<100, %s, 4>" % lst
+
+
 for ef in (1, 7, 10, 40, 64, 65, 68, 100, 128):
-    assert_search_equal(idx.search_batch(qs, 10, ef), orc.search_batch(qs, 10, ef, nthreads=8), "two-wave kernel, ef %d" % ef)
+    with H.kernel_log() as log:
+        got = idx.search_batch(qs, 10, ef)
+    pair, one = kernels(ef)
+    assert pair in log and set(log) <= {pair, one}, (ef, dict(log))
+    assert_search_equal(got, orc.search_batch(qs, 10, ef, nthreads=8), "two-wave kernel, ef %d" % ef)
 # one query per call (the reference's ann_by_vector) goes the same way
 for i in range(8):
     want = orc.search_batch(qs[i:i + 1], 10, 68, nthreads=1)[0][0]
@@ -50,6 +62,13 @@ for l in range(1, o1.nb_layers):
 o2.set_ep(o1.ep)
 p2 = product_from_oracle(o2, vs2, lv2)
 assert p2.get_layer(0).degree(5) > 64
+reran = set()
 for ef in (16, 64, 100):
-    assert_search_equal(p2.search_batch(q2, 10, ef), o2.search_batch(q2, 10, ef), "two-wave kernel, overflowing rows, ef %d" % ef)
+    with H.kernel_log() as log:
+        got = p2.search_batch(q2, 10, ef)
+    pair, one = kernels(ef)
+    assert pair in log and set(log) <= {pair, one}, (ef, dict(log))
+    reran |= set(log) & {one}
+    assert_search_equal(got, o2.search_batch(q2, 10, ef), "two-wave kernel, overflowing rows, ef %d" % ef)
+assert reran, "no query met an overflowing row: the one-wave re-run was not reached"
 print("PAIR PARITY OK")
