@@ -1,0 +1,106 @@
+// search_host.h -- the host side of the search entry points (search_host.cpp): the host-pointer path, the
+// filtered / deleted orchestration and the completion of a device-pointer call (internal)
+#pragma once
+
+#include <cstring>
+
+#include "handle.h"
+#include "search_filtered.h"
+
+namespace hx {
+
+// The result block of nq queries x n results: [ids | dists | counts | stats], the same layout in the device arena
+// and in pinned memory, so it comes back in ONE copy.
+struct ResultBlock {
+    uint64_t nq = 0;
+    uint32_t n = 0;
+    size_t ids = 0, dists = 0, counts = 0, stats = 0, bytes = 0;  // offsets from the block's base
+    ResultBlock() = default;
+    ResultBlock(uint64_t nq_, uint32_t n_) : nq(nq_), n(n_) {
+        dists = ids + align256(nq * n * 4);
+        counts = dists + align256(nq * n * 4);
+        stats = counts + align256(nq * 4);
+        bytes = stats + align256(nq * sizeof(hnsw_query_stats));
+    }
+    struct Ptrs {
+        uint32_t *ids;
+        float *dists;
+        uint32_t *counts;
+        hnsw_query_stats *stats;
+    };
+    Ptrs at(void *base) const {
+        unsigned char *b = static_cast<unsigned char *>(base);
+        return {reinterpret_cast<uint32_t *>(b + ids), reinterpret_cast<float *>(b + dists),
+                reinterpret_cast<uint32_t *>(b + counts), reinterpret_cast<hnsw_query_stats *>(b + stats)};
+    }
+    template <class Args>  // SearchArgs / FilterArgs: the kernel writes the block at `base`
+    void bind(Args &a, void *base) const {
+        const Ptrs p = at(base);
+        a.out_ids = p.ids;
+        a.out_dists = p.dists;
+        a.out_counts = p.counts;
+        a.out_stats = p.stats;
+    }
+    // a block in host memory to the caller's buffers (all but o_ids optional)
+    void copy_out(void *base, uint32_t *o_ids, float *o_dists, uint32_t *o_counts, hnsw_query_stats *o_stats) const {
+        const Ptrs p = at(base);
+        memcpy(o_ids, p.ids, nq * n * 4);
+        if (o_dists) memcpy(o_dists, p.dists, nq * n * 4);
+        if (o_counts) memcpy(o_counts, p.counts, nq * 4);
+        if (o_stats) memcpy(o_stats, p.stats, nq * sizeof(hnsw_query_stats));
+    }
+};
+
+// One search of nq queries in a scratch.  Pinned arena: [queries | result block]; device arena:
+// [queries | selection | entries | result block].  The queries reach the device by a true asynchronous copy out of
+// pinned memory (a hipMemcpyAsync out of pageable user memory is staged by the runtime and does not overlap anything).
+struct HostSearchPlan {
+    size_t o_q, o_sel, o_ent, o_out, dev_bytes;  // device arena
+    ResultBlock out;
+    size_t p_q, p_out, pin_bytes;  // pinned arena
+};
+HostSearchPlan plan_host_search(uint64_t nq, uint32_t d, uint32_t n, uint32_t n_entry);
+
+// the arguments of hnsw_search* (template.rs:322-326: layers L-1..1 with ef = 1, then layer 0 with ef)
+SearchArgs ann_args(const DevView &v, const float *dQ, uint32_t n, uint32_t ef, uint32_t *ids, float *dists,
+                    uint32_t *counts, hnsw_query_stats *stats);
+
+// text of a per-query failure on the calling thread; returns the status
+int query_status_error(uint64_t i, int32_t status);
+
+// The search itself: the queries are in s.pin + p.p_q (or, for a large call, still in the caller's memory: Q_user),
+// the results are left in s.pin + p.p_out.  Queries whose visited table filled up are run again with a table twice
+// the size.  Returns launch-level errors only; per-query statuses stay in the result block.
+int search_staged(hnsw_index *h, SearchScratch &s, const HostSearchPlan &p, SearchArgs a_host, uint64_t nq,
+                  const uint32_t *entries, const float *Q_user);
+
+// host-pointer search (hnsw_search_batch, hnsw_search_layer): user buffers in, user buffers out
+int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, uint32_t *ids, float *dists,
+                uint32_t *counts, hnsw_query_stats *stats, const uint32_t *entries);
+
+// k-NN among the admissible ids (hnsw_search_batch_filtered's contract).  exact_only: every query by the exact path
+// (hnsw_brute_force).  The results go to the caller's buffers (per-query statuses in stats: required), or, when
+// pin_block is given, straight into that pinned ResultBlock(nq, n) and the buffers are not read.  Returns argument and
+// launch errors only.
+int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const uint64_t *allow,
+                    uint64_t allow_bits, bool exact_only, uint32_t *ids, float *dists, uint32_t *counts,
+                    hnsw_query_stats *stats, uint8_t *paths, const PathCounters *ctr, void *pin_block = nullptr);
+// ... with the first per-query error as the status (stats may be NULL)
+int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const uint64_t *allow,
+                            uint64_t allow_bits, bool exact_only, uint32_t *ids, float *dists, uint32_t *counts,
+                            hnsw_query_stats *stats, uint8_t *paths, const PathCounters *ctr);
+
+// hnsw_search_batch_device (finish = false) and _finish while ids are deleted: the filtered graph path over the
+// undeleted ids on the caller's stream; _finish re-runs the queries whose visited table filled up with larger tables,
+// up to the graph path's largest, and answers those that fill it by the exact path.  Equals the host form with
+// filter_exact_max = -1.
+int search_device_deleted(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t *d_ids,
+                          float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, hipStream_t stream, bool finish);
+
+// hnsw_search_batch_device_finish while nothing is deleted: waits for the stream, reads the per-query statuses,
+// re-runs the queries whose visited table filled up with a table twice the size (same arithmetic, same result as
+// if the larger table had been used from the start) and reports the first remaining per-query error.
+int search_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t *d_ids,
+                         float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, hipStream_t stream);
+
+}  // namespace hx

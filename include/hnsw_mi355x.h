@@ -161,7 +161,7 @@ int hnsw_import_layer(hnsw_index *h, uint32_t layer, uint64_t n_nodes, const uin
  * all of them and wakes them with their ids.  Every query is still answered by its own wave, so a call returns
  * exactly what it would return alone.  A lone caller launches at once; a leader that has seen concurrency waits up
  * to "coalesce_us" (hnsw_set_option; default 30, 0 = never wait, < 0 = coalescing off) for the callers that were
- * woken together to come back; at most "coalesce_depth" (2) batches are on the GPU at a time and a batch holds at
+ * woken together to come back; at most "coalesce_depth" (3) batches are on the GPU at a time and a batch holds at
  * most "coalesce_max" (1024) queries. */
 int hnsw_search(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uint32_t *ids,
                 uint32_t *count);

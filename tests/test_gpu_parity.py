@@ -377,6 +377,12 @@ def test_device_pointer_entry_recovers_from_a_full_visited_table(kind):
     assert_search_equal(got, want, "after finish")
     # the host-pointer entry does the same by itself
     assert_search_equal(index.search_batch(qs, topn, ef), want, "host entry")
+    # ... also on its copying branch (calls of more than 512 queries: the result block comes back by a D2H copy)
+    reps = 512 // nq + 1
+    tiled = np.ascontiguousarray(np.tile(qs, (reps, 1)))
+    assert tiled.shape[0] > 512
+    want_tiled = tuple(np.concatenate([np.asarray(w)] * reps) for w in want)
+    assert_search_equal(index.search_batch(tiled, topn, ef), want_tiled, "host entry, copying branch")
 
 
 @pytest.mark.parametrize("kind", [H.VEC_QUANT8, H.VEC_F32])
