@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("HNSW_MI355X_LIB") or os.path.join(_HERE, "libhnsw_mi3
 VEC_QUANT8 = 0
 VEC_F32 = 1
 UINT32_MAX = 0xFFFFFFFF
+MASK_NONE = 0xFFFFFFFF  # HNSW_MASK_NONE: a query of hnsw_search_batch_filtered_multi without an allow-list
 
 OK = 0
 ERR_BAD_DIM = -1
@@ -78,6 +79,8 @@ SYMBOLS = {
                                     C.POINTER(QueryStats)]),
     "hnsw_search_batch_filtered": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, u64p, C.c_uint64, u32p,
                                              f32p, u32p, C.POINTER(QueryStats), u8p]),
+    "hnsw_search_batch_filtered_multi": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, u64p, C.c_uint32,
+                                                   C.c_uint64, u32p, u32p, f32p, u32p, C.POINTER(QueryStats), u8p]),
     "hnsw_search_batch_device": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
     "hnsw_search_batch_device_finish": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
     "hnsw_distance_batch": (C.c_int, [vp, f32p, u32p, C.c_uint64, f32p]),

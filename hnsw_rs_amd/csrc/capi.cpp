@@ -339,8 +339,8 @@ int hnsw_search_batch(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, ui
     }
     if (h->del.count) {  // ids are deleted: the filtered search over the undeleted ones (include/hnsw_mi355x.h)
         const hx::PathCounters ctr = hx::del_counters(h);
-        return hx::search_filtered_checked(h, Q, nq, n, ef, nullptr, index_len(h), false, ids, dists, counts, stats,
-                                           nullptr, &ctr);
+        return hx::search_filtered_checked(h, Q, nq, n, ef, hx::MaskSpec{nullptr, index_len(h)}, false, ids, dists, counts,
+                                           stats, nullptr, &ctr);
     }
     hx::DevView dummy{};
     dummy.nb_layers = hnsw_layer_count(h);  // the host index's, or the adopted snapshot's for a replica
@@ -361,7 +361,23 @@ int hnsw_search_batch_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint3
     }
     // (a call without a mask allows nothing: kNoWords stands for its empty mask, nullptr would allow every id)
     const hx::PathCounters ctr = hx::filt_counters(h);
-    return hx::search_filtered_checked(h, Q, nq, n, ef, allow ? allow : &kNoWords, allow ? allow_bits : 0, false, ids,
+    return hx::search_filtered_checked(h, Q, nq, n, ef, hx::MaskSpec{allow ? allow : &kNoWords, allow ? allow_bits : 0},
+                                       false, ids, dists, counts, stats, paths, &ctr);
+}
+
+int hnsw_search_batch_filtered_multi(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                     const uint64_t *masks, uint32_t n_masks, uint64_t allow_bits,
+                                     const uint32_t *mask_of, uint32_t *ids, float *dists, uint32_t *counts,
+                                     hnsw_query_stats *stats, uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK) return rc;
+    if (nq == 0) return HNSW_OK;
+    if (!mask_of) {
+        set_error("filtered search: needs the mask of every query");
+        return HNSW_ERR_ARG;
+    }
+    const hx::PathCounters ctr = hx::filt_counters(h);
+    return hx::search_filtered_checked(h, Q, nq, n, ef, hx::MaskSpec{masks, allow_bits, n_masks, mask_of}, false, ids,
                                        dists, counts, stats, paths, &ctr);
 }
 
@@ -488,7 +504,8 @@ int hnsw_brute_force(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uin
     if (h->del.count) {
         // the top k of the undeleted ids: the filtered search's exact path, in the same arithmetic and (dist, id) order
         std::vector<hnsw_query_stats> st(nq);
-        rc = hx::search_filtered(h, Q, nq, k, k, nullptr, index_len(h), true, ids, dists, nullptr, st.data(), nullptr, nullptr);
+        rc = hx::search_filtered(h, Q, nq, k, k, hx::MaskSpec{nullptr, index_len(h)}, true, ids, dists, nullptr, st.data(),
+                                 nullptr, nullptr);
         if (rc != HNSW_OK) return rc;
         for (uint64_t i = 0; i < nq; i++)
             if (st[i].status != HNSW_OK) {
@@ -944,6 +961,10 @@ int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
         *out = h->n_filt_exact.load();
     } else if (!strcmp(key, "filtered_overflow_exact")) {
         *out = h->n_filt_overflow.load();
+    } else if (!strcmp(key, "filtered_multi_calls")) {
+        *out = h->n_filt_multi_calls.load();
+    } else if (!strcmp(key, "filtered_multi_masks")) {
+        *out = h->n_filt_multi_masks.load();
     } else if (!strcmp(key, "deleted")) {
         *out = h->del.count;
     } else if (!strcmp(key, "deleted_mask_words_uploaded")) {

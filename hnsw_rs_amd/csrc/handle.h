@@ -45,6 +45,8 @@ struct hnsw_index {
     // answered by the exact scan ("Filtered search", for the measured crossover); queries per path
     int64_t filter_exact_max = 65536;
     std::atomic<uint64_t> n_filt_graph{0}, n_filt_exact{0}, n_filt_overflow{0};
+    // hnsw_search_batch_filtered_multi: calls, and the masks their queries referenced (no mask counts as one)
+    std::atomic<uint64_t> n_filt_multi_calls{0}, n_filt_multi_masks{0};
     // deleted ids (hnsw_mark_deleted), on the host and in HBM; while any is deleted the unfiltered entry points answer
     // by the filtered search over the undeleted ids and count their queries per path here
     hx::DeletedSet del;

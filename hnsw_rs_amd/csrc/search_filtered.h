@@ -1,10 +1,13 @@
 // search_filtered.h -- filtered k-NN (hnsw_search_batch_filtered): the arguments of the kernels in
 // search_filtered.hip and their launchers.  gfx950 only.
 //
-// One allow-list per call, a bitmask over ids: id i is allowed iff i < allow_bits and bit i & 63 of
-// word i >> 6 is set (allow_bits is already clamped to the index length by the caller); without a mask
-// (allow == nullptr) every id below allow_bits is.  The handle's deleted set (hnsw_mark_deleted) is a second
-// mask of the same layout, deny: an id is admissible iff it is allowed and not denied.
+// An allow-list is a bitmask over ids: id i is allowed iff i < allow_bits and bit i & 63 of word i >> 6 is set
+// (allow_bits is already clamped to the index length by the caller); without a mask (allow == nullptr) every id
+// below allow_bits is.  One mask serves the call (mask_of == nullptr), or allow holds rows of mask_words words
+// and query q walks under row mask_of[q] (hnsw_search_batch_filtered_multi); HNSW_MASK_NONE there means no mask:
+// every id below none_bits.  Only the graph kernel reads mask_of: the exact path's kernels are launched per mask
+// with allow at that mask's row.  The handle's deleted set (hnsw_mark_deleted) is a second mask of the same
+// layout, deny: an id is admissible iff it is allowed and not denied.
 #pragma once
 
 #include "device_index.h"
@@ -20,6 +23,9 @@ struct FilterArgs {
     const uint32_t *qsel;      // optional: launch block b serves query qsel[b]
     const uint64_t *allow;     // mask words (device), or nullptr: every id < allow_bits
     uint64_t allow_bits;       // min(caller's allow_bits, index length)
+    const uint32_t *mask_of;   // optional (device): query q's row of allow, or HNSW_MASK_NONE; nullptr: row 0
+    uint64_t mask_words;       // words per row of allow (read with mask_of only)
+    uint64_t none_bits;        // the id bound of a HNSW_MASK_NONE query: the index length
     const uint64_t *deny;      // the deleted ids' mask words (device), or nullptr: nothing deleted
     uint64_t deny_bits;        // ids the deny mask covers (a multiple of 64); ids beyond it are not denied
     uint32_t n, ef;            // results per query, ef' = max(ef, n, 1)

@@ -155,11 +155,12 @@ __device__ __forceinline__ bool filt_visit(uint32_t *tab, uint32_t slots_log2, u
     }
 }
 
-// admissible: allowed (below allow_bits, and its bit set when there is a mask) and not deleted.  The two pointer
-// tests are uniform over the wave (kernel arguments); a mask word is read only for an id that got that far.
-__device__ __forceinline__ bool filt_allowed(const FilterArgs &a, uint32_t id) {
-    if ((uint64_t)id >= a.allow_bits) return false;
-    if (a.allow && ((a.allow[id >> 6] >> (id & 63)) & 1ull) == 0) return false;
+// admissible: allowed (below the query's bound, and its bit set when the query has a mask) and not deleted.  The two
+// pointer tests are uniform over the wave (a kernel argument, and the wave's own mask: one query per wave); a mask
+// word is read only for an id that got that far.
+__device__ __forceinline__ bool filt_allowed(const FilterArgs &a, const uint64_t *allow, uint64_t bound, uint32_t id) {
+    if ((uint64_t)id >= bound) return false;
+    if (allow && ((allow[id >> 6] >> (id & 63)) & 1ull) == 0) return false;
     return !(a.deny && (uint64_t)id < a.deny_bits && ((a.deny[id >> 6] >> (id & 63)) & 1ull) != 0);
 }
 
@@ -282,6 +283,10 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
     const uint32_t q = a.qsel ? a.qsel[blockIdx.x] : blockIdx.x;
+    // the wave's mask and id bound, picked once (scalar: q is the block's)
+    const uint32_t g = a.mask_of ? a.mask_of[q] : 0;
+    const uint64_t *allow = g == HNSW_MASK_NONE ? nullptr : a.allow + (size_t)g * a.mask_words;
+    const uint64_t bound = g == HNSW_MASK_NONE ? a.none_bits : a.allow_bits;
     uint32_t *htab = reinterpret_cast<uint32_t *>(smem);
     u64 *perm = reinterpret_cast<u64 *>(smem + (4ull << slots_log2));
     float *yq = reinterpret_cast<float *>(perm + 64 * R);
@@ -398,7 +403,7 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
             wave_fence();
             n_vis = 1;
             F.merge(lane == 0 ? best : FKEY_INVALID, ef, perm, lane);
-            Rl.merge(lane == 0 && filt_allowed(a, (uint32_t)best) ? best : FKEY_INVALID, ef, perm, lane);
+            Rl.merge(lane == 0 && filt_allowed(a, allow, bound, (uint32_t)best) ? best : FKEY_INVALID, ef, perm, lane);
         }
         while (status == HNSW_OK && F.n_cur > 0) {
             const u64 c = F.front();
@@ -407,7 +412,7 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
             expand((uint32_t)c, 0, [&](u64 key) {
                 // admitted against the bound at the start of the pass; R takes the allowed ones
                 const bool adm = key != FKEY_INVALID && (!Rl.full(ef) || key < Rl.last);
-                const bool alw = adm && filt_allowed(a, (uint32_t)key);
+                const bool alw = adm && filt_allowed(a, allow, bound, (uint32_t)key);
                 F.merge(adm ? key : FKEY_INVALID, ef, perm, lane);
                 Rl.merge(alw ? key : FKEY_INVALID, ef, perm, lane);
             });

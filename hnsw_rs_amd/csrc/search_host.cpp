@@ -210,27 +210,33 @@ uint64_t count_admissible(const hnsw_index *h, const uint64_t *allow, uint64_t b
     return A;
 }
 
-// The exact path's scratch for up to nsel queries over A admissible ids, from `base` in a device arena:
-// [word offsets | admissible ids | partial keys | partial statuses]; `chunk` queries per launch, `nseg` segments each
+// The exact path's scratch from `base` in a device arena: [word offsets | admissible ids | partial keys | partial
+// statuses], for launches of up to nsel_max queries over up to A_max admissible ids (n_wbase word offsets in all)
 struct ExactScratch {
-    uint32_t chunk, nseg;
     size_t o_wb, o_ids, o_part, o_pst, end;
-    ExactScratch(size_t base, uint64_t nsel, uint32_t n, uint64_t A, size_t n_wbase)
-        : chunk((uint32_t)std::min<uint64_t>(nsel, 65535)), nseg(filt_exact_segments(A, chunk)) {
+    ExactScratch(size_t base, uint64_t nsel_max, uint32_t n, uint64_t A_max, size_t n_wbase) {
+        // chunk x nseg of any launch within those limits (filt_exact_segments: at most 256 segments, and at most
+        // 262144 blocks unless the queries alone are more)
+        const uint64_t N = std::min<uint64_t>(nsel_max, 65535), s = filt_exact_segments(A_max, 1);
+        const uint64_t rows = std::min<uint64_t>(N * s, std::max<uint64_t>(262144, N));
         o_wb = base;
         o_ids = o_wb + align256(n_wbase * 4);
-        o_part = o_ids + align256(A * 4);
-        o_pst = o_part + align256((size_t)chunk * nseg * n * 8);
-        end = o_pst + align256((size_t)chunk * nseg * 4);
+        o_part = o_ids + align256(A_max * 4);
+        o_pst = o_part + align256((size_t)rows * n * 8);
+        end = o_pst + align256((size_t)rows * 4);
     }
 };
 
-// the exact path for nsel queries: those of d_sel, or the first nsel of the call; the word offsets are in place
+// the exact path for nsel queries under ONE mask (a.allow, a.allow_bits; a.mask_of is not read): those of d_sel, or
+// the first nsel of the call; the mask's word offsets are at d_wb.  shape_nsel: the query count the launch shape
+// (queries per launch, segments) is chosen for
 int filtered_exact(const DevView &v, const FilterArgs &a, uint64_t nsel, const uint32_t *d_sel, uint64_t A,
-                   const ExactScratch &x, unsigned char *dv, hipStream_t stream) {
+                   const uint32_t *d_wb, uint64_t shape_nsel, const ExactScratch &x, unsigned char *dv,
+                   hipStream_t stream) {
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(shape_nsel, 65535), nseg = filt_exact_segments(A, chunk);
     uint32_t *d_ids = reinterpret_cast<uint32_t *>(dv + x.o_ids);
-    int r = launch_filter_compact(a, (a.allow_bits + 63) / 64, reinterpret_cast<const uint32_t *>(dv + x.o_wb), d_ids, stream);
-    for (uint64_t c = 0; r == HNSW_OK && c < nsel; c += x.chunk) {
+    int r = launch_filter_compact(a, (a.allow_bits + 63) / 64, d_wb, d_ids, stream);
+    for (uint64_t c = 0; r == HNSW_OK && c < nsel; c += chunk) {
         FilterArgs ac = a;
         if (d_sel) {
             ac.qsel = d_sel + c;
@@ -242,18 +248,29 @@ int filtered_exact(const DevView &v, const FilterArgs &a, uint64_t nsel, const u
             ac.out_counts += c;
             ac.out_stats += c;
         }
-        r = launch_filtered_exact(v, ac, (uint32_t)std::min<uint64_t>(x.chunk, nsel - c), d_ids, (uint32_t)A, x.nseg,
+        r = launch_filtered_exact(v, ac, (uint32_t)std::min<uint64_t>(chunk, nsel - c), d_ids, (uint32_t)A, nseg,
                                   reinterpret_cast<unsigned long long *>(dv + x.o_part),
                                   reinterpret_cast<int32_t *>(dv + x.o_pst), stream);
     }
     return r;
 }
 
+// One referenced allow-list of a call: the planner's unit.  A call with one mask has one group and every query in it.
+struct MaskGroup {
+    const uint64_t *allow;  // the caller's words (nullptr: every id below bits)
+    uint64_t row;           // first word of the mask in the call's uploaded masks
+    uint64_t bits;          // its id bound: min(allow_bits, len), or len without a mask
+    uint64_t A = 0;         // admissible ids
+    bool exact = false;     // A <= filter_exact_max
+    size_t wb = 0;            // its word offsets in the call's list: from wb_all[wb]
+    size_t q0 = 0, nq = 0;    // its queries: order[q0 .. q0 + nq)
+};
+
 }  // namespace
 
-int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const uint64_t *allow,
-                    uint64_t allow_bits, bool exact_only, uint32_t *ids, float *dists, uint32_t *counts,
-                    hnsw_query_stats *stats, uint8_t *paths, const PathCounters *ctr, void *pin_block) {
+int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const MaskSpec &m,
+                    bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
+                    uint8_t *paths, const PathCounters *ctr, void *pin_block) {
     int rc = check_search_args(h, ef);
     if (rc != HNSW_OK) return rc;
     if (nq == 0) return HNSW_OK;
@@ -262,27 +279,92 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
                   HX_FILT_MAX_N);
         return HNSW_ERR_ARG;
     }
+    const bool multi = m.mask_of != nullptr;
+    if (multi) {
+        bool masked = false;
+        for (uint64_t i = 0; i < nq; i++) {
+            if (m.mask_of[i] == HNSW_MASK_NONE) continue;
+            if (m.mask_of[i] >= m.n_masks) {
+                set_error("filtered search: query %llu names mask %u of %u", (unsigned long long)i, m.mask_of[i], m.n_masks);
+                return HNSW_ERR_ARG;
+            }
+            masked = true;
+        }
+        if (masked && !m.masks && m.allow_bits != 0) {
+            set_error("filtered search: needs the masks its queries name when allow_bits > 0");
+            return HNSW_ERR_ARG;
+        }
+    }
     if (n == 0) {  // nothing returned, nothing launched
         if (counts) memset(counts, 0, nq * 4);
         return HNSW_OK;
     }
     const uint32_t efp = std::max(std::max(ef, n), 1u);
-    const uint64_t bits = std::min<uint64_t>(allow_bits, index_len(h));
-    const uint64_t n_words = (bits + 63) / 64;
-    std::vector<uint32_t> wbase;
-    const uint64_t A = count_admissible(h, allow, bits, wbase);
-    const bool exact_all = exact_only || (int64_t)A <= h->filter_exact_max;
-    if (!exact_all && efp > HX_FILT_MAX_EF) {
+    const uint64_t len = index_len(h), bits = std::min<uint64_t>(m.allow_bits, len);
+    const uint64_t row_words = (m.allow_bits + 63) / 64;  // a row of the caller's masks
+    // ---- the planner, per referenced mask: its admissible ids decide its queries' path ----
+    std::vector<uint32_t> order;  // the queries, mask by mask (HNSW_MASK_NONE last); a one-mask call has no use for it
+    std::vector<MaskGroup> groups;
+    if (!multi) {
+        groups.push_back(MaskGroup{m.masks, 0, bits});
+        groups[0].nq = nq;
+    } else {
+        order.resize(nq);
+        for (uint64_t i = 0; i < nq; i++) order[i] = (uint32_t)i;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t i, uint32_t j) { return m.mask_of[i] < m.mask_of[j]; });
+        for (uint64_t i = 0; i < nq; i++) {
+            const uint32_t g = m.mask_of[order[i]];
+            if (i == 0 || g != m.mask_of[order[i - 1]]) {
+                if (g == HNSW_MASK_NONE)
+                    groups.push_back(MaskGroup{nullptr, 0, len});
+                else  // (masks may be NULL when allow_bits is 0: nothing is allowed, no word is read)
+                    groups.push_back(MaskGroup{m.masks ? m.masks + g * row_words : nullptr, g * row_words, bits});
+                groups.back().q0 = i;
+            }
+            groups.back().nq++;
+        }
+    }
+    std::vector<uint32_t> wb_all, wb;
+    uint64_t A_max = 0, n_graph = 0, n_exact = 0;
+    for (MaskGroup &g : groups) {
+        g.A = count_admissible(h, g.allow, g.bits, wb);
+        g.exact = exact_only || (int64_t)g.A <= h->filter_exact_max;
+        g.wb = wb_all.size();
+        wb_all.insert(wb_all.end(), wb.begin(), wb.end());
+        A_max = std::max(A_max, g.A);
+        (g.exact ? n_exact : n_graph) += g.nq;
+    }
+    if (n_graph && efp > HX_FILT_MAX_EF) {
         set_error("filtered search: ef' = max(ef, n) = %u is above the graph path's maximum of %d", efp, HX_FILT_MAX_EF);
         return HNSW_ERR_ARG;
+    }
+    // the selections: the graph path's queries in one list (none when every query takes it), the exact path's mask by
+    // mask (order itself when every query takes it)
+    std::vector<uint32_t> gsel, group_of;
+    std::vector<uint8_t> path(nq, groups[0].exact ? 1 : 0);
+    if (multi) {
+        group_of.resize(nq);
+        for (size_t k = 0; k < groups.size(); k++)
+            for (size_t i = groups[k].q0; i < groups[k].q0 + groups[k].nq; i++) {
+                group_of[order[i]] = (uint32_t)k;
+                path[order[i]] = groups[k].exact ? 1 : 0;
+            }
+        if (n_graph && n_exact) {
+            for (uint64_t i = 0; i < nq; i++)
+                if (!groups[group_of[i]].exact) gsel.push_back((uint32_t)i);
+        }
     }
     if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h))) return rc;
     const DevView &v = h->dev.view;
     const uint32_t d = v.dim;
-    // device arena: [queries | mask | selection | the exact path's scratch | result block]; the result block comes
-    // back in one copy to pinned memory: the caller's block, or the scratch's and from there to the caller's buffers
-    const size_t o_q = 0, o_mask = o_q + align256(nq * d * 4), o_sel = o_mask + align256(allow ? n_words * 8 : 0);
-    const ExactScratch x(o_sel + align256(nq * 4), nq, n, A, wbase.size());
+    // device arena: [queries | masks | mask of every query | selection | the exact path's selection | the exact path's
+    // scratch | result block].  All n_masks rows go up in one copy (a one-mask call sends the words below `bits` only).
+    // The result block comes back in one copy to pinned memory: the caller's block, or the scratch's and from there to
+    // the caller's buffers
+    const uint64_t up_words = !m.masks ? 0 : multi ? (uint64_t)m.n_masks * row_words : (bits + 63) / 64;
+    const size_t o_q = 0, o_mask = o_q + align256(nq * d * 4), o_mof = o_mask + align256(up_words * 8);
+    const size_t o_sel = o_mof + align256(multi ? nq * 4 : 0), o_xsel = o_sel + align256(nq * 4);
+    const ExactScratch x(o_xsel + align256(multi ? nq * 4 : 0), nq, n, A_max, wb_all.size());
     const size_t o_out = x.end;
     const ResultBlock out(nq, n);
     ScratchLease lease(h);
@@ -290,70 +372,100 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     SearchScratch &s = *lease.s;
     unsigned char *dv = static_cast<unsigned char *>(s.dev);
     void *hv = pin_block ? pin_block : s.pin;
+    uint32_t *d_sel = reinterpret_cast<uint32_t *>(dv + o_sel), *d_xsel = reinterpret_cast<uint32_t *>(dv + o_xsel);
+    const uint64_t *d_masks = up_words ? reinterpret_cast<const uint64_t *>(dv + o_mask) : nullptr;
+    const uint32_t *d_wb = reinterpret_cast<const uint32_t *>(dv + x.o_wb);
     HIP_TRY(hipMemcpyAsync(dv + o_q, Q, nq * d * 4, hipMemcpyHostToDevice, s.stream));
     if ((rc = cosine_queries(h, dv + o_q, nq, s.stream))) return rc;
-    if (n_words) {
-        if (allow) HIP_TRY(hipMemcpyAsync(dv + o_mask, allow, n_words * 8, hipMemcpyHostToDevice, s.stream));
-        HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wbase.data(), wbase.size() * 4, hipMemcpyHostToDevice, s.stream));
+    if (up_words) HIP_TRY(hipMemcpyAsync(dv + o_mask, m.masks, up_words * 8, hipMemcpyHostToDevice, s.stream));
+    if (bits || multi) HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, s.stream));
+    if (multi) {
+        HIP_TRY(hipMemcpyAsync(dv + o_mof, m.mask_of, nq * 4, hipMemcpyHostToDevice, s.stream));
+        if (!gsel.empty()) HIP_TRY(hipMemcpyAsync(d_sel, gsel.data(), gsel.size() * 4, hipMemcpyHostToDevice, s.stream));
+        if (n_exact) HIP_TRY(hipMemcpyAsync(d_xsel, order.data(), nq * 4, hipMemcpyHostToDevice, s.stream));
     }
-    FilterArgs a{};
+    FilterArgs a{};  // the graph path's arguments: every mask, the wave picks its query's
     a.Q = reinterpret_cast<const float *>(dv + o_q);
-    a.allow = allow ? reinterpret_cast<const uint64_t *>(dv + o_mask) : nullptr;
+    a.qsel = gsel.empty() ? nullptr : d_sel;
+    a.allow = d_masks;
     a.allow_bits = bits;
+    a.mask_of = multi ? reinterpret_cast<const uint32_t *>(dv + o_mof) : nullptr;
+    a.mask_words = row_words;
+    a.none_bits = len;
     a.deny = h->del.count ? h->del.d_words : nullptr;
     a.deny_bits = h->del.count ? h->del.deny_bits() : 0;
     a.n = n;
     a.ef = efp;
     out.bind(a, dv + o_out);
-    uint32_t *d_sel = reinterpret_cast<uint32_t *>(dv + o_sel);
+    // the exact path for nsel queries of one mask (sel on the device; nullptr: the first nsel of the call)
+    auto exact = [&](const MaskGroup &g, uint64_t nsel, const uint32_t *sel) -> int {
+        FilterArgs ax = a;
+        ax.mask_of = nullptr;
+        ax.allow = g.allow ? d_masks + g.row : nullptr;
+        ax.allow_bits = g.bits;
+        return filtered_exact(v, ax, nsel, sel, g.A, d_wb + g.wb, multi ? nsel : nq, x, dv, s.stream);
+    };
     auto fetch = [&](const hnsw_query_stats *&st) -> int {
         HIP_TRY(hipMemcpyAsync(hv, dv + o_out, out.bytes, hipMemcpyDeviceToHost, s.stream));
         HIP_TRY(hipStreamSynchronize(s.stream));
         st = out.at(hv).stats;
         return HNSW_OK;
     };
-    std::vector<uint8_t> path(nq, exact_all ? 1 : 0);
+    // ONE launch of the graph path for the queries of every mask planned on it, then the exact path mask by mask (its
+    // scratch reused in stream order), then the result block in one copy
+    const uint32_t slots = filt_first_slots_log2(v, efp);
+    if (n_graph && (rc = launch_filtered_graph(v, a, (uint32_t)n_graph, slots, s.stream))) return rc;
+    for (const MaskGroup &g : groups)
+        if (g.exact && (rc = exact(g, g.nq, multi ? d_xsel + g.q0 : nullptr))) return rc;
     uint64_t n2 = 0;
     const hnsw_query_stats *st;
-    if (exact_all) {
-        if ((rc = filtered_exact(v, a, nq, nullptr, A, x, dv, s.stream)) || (rc = fetch(st))) return rc;
+    if (!n_graph) {
+        if ((rc = fetch(st))) return rc;
     } else {
-        // graph path; queries whose visited table filled up run again with a table twice the size, and those
-        // that fill the largest one are answered by the exact path
-        const uint32_t slots = filt_first_slots_log2(v, efp);
-        if ((rc = launch_filtered_graph(v, a, (uint32_t)nq, slots, s.stream))) return rc;
+        // queries whose visited table filled up run again with a table twice the size, all masks together, and those
+        // that fill the largest one are answered by the exact path, each under its own mask
+        std::vector<uint32_t> sel2;
         rc = rerun_overflowed(
             v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v), d_sel, s.stream, fetch,
             [&](const std::vector<uint32_t> &sel) -> int {
                 for (uint32_t i : sel) path[i] = 2;
-                HIP_TRY(hipMemcpyAsync(d_sel, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, s.stream));
-                int r = filtered_exact(v, a, sel.size(), d_sel, A, x, dv, s.stream);
-                return r != HNSW_OK ? r : fetch(st);  // (synchronises: `sel` lives until then)
+                sel2 = sel;
+                if (multi) std::stable_sort(sel2.begin(), sel2.end(), [&](uint32_t i, uint32_t j) { return group_of[i] < group_of[j]; });
+                HIP_TRY(hipMemcpyAsync(d_sel, sel2.data(), sel2.size() * 4, hipMemcpyHostToDevice, s.stream));
+                int r = HNSW_OK;
+                for (size_t lo = 0, hi; r == HNSW_OK && lo < sel2.size(); lo = hi) {
+                    const uint32_t k = multi ? group_of[sel2[lo]] : 0;
+                    for (hi = lo + 1; hi < sel2.size() && (!multi || group_of[sel2[hi]] == k);) hi++;
+                    r = exact(groups[k], hi - lo, d_sel + lo);
+                }
+                return r != HNSW_OK ? r : fetch(st);  // (synchronises: `sel2` lives until then)
             },
             &n2);
         if (rc != HNSW_OK) return rc;
     }
     if (ctr) {
-        if (exact_all)
-            ctr->exact->fetch_add(nq, std::memory_order_relaxed);
-        else
-            ctr->graph->fetch_add(nq - n2, std::memory_order_relaxed);
+        ctr->exact->fetch_add(n_exact, std::memory_order_relaxed);
+        ctr->graph->fetch_add(n_graph - n2, std::memory_order_relaxed);
         ctr->overflow->fetch_add(n2, std::memory_order_relaxed);
+    }
+    if (multi) {
+        h->n_filt_multi_calls.fetch_add(1, std::memory_order_relaxed);
+        h->n_filt_multi_masks.fetch_add(groups.size(), std::memory_order_relaxed);
     }
     if (!pin_block) out.copy_out(hv, ids, dists, counts, stats);
     if (paths) memcpy(paths, path.data(), nq);
     return HNSW_OK;
 }
 
-int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const uint64_t *allow,
-                            uint64_t allow_bits, bool exact_only, uint32_t *ids, float *dists, uint32_t *counts,
-                            hnsw_query_stats *stats, uint8_t *paths, const PathCounters *ctr) {
+int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const MaskSpec &m,
+                            bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
+                            uint8_t *paths, const PathCounters *ctr) {
     std::vector<hnsw_query_stats> local;
-    if (!stats) {
+    if (!stats && nq <= 0x7FFFFFFFull) {  // (more queries are refused below, before anything is allocated for them)
         local.resize(nq);
         stats = local.data();
     }
-    int rc = search_filtered(h, Q, nq, n, ef, allow, allow_bits, exact_only, ids, dists, counts, stats, paths, ctr);
+    int rc = search_filtered(h, Q, nq, n, ef, m, exact_only, ids, dists, counts, stats, paths, ctr);
     if (rc != HNSW_OK || n == 0) return rc;
     return first_query_error(stats, nq);
 }
@@ -427,7 +539,8 @@ int search_device_deleted(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t
             unsigned char *dv = static_cast<unsigned char *>(lease.s->dev);
             HIP_TRY(hipMemcpyAsync(dv, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, stream));
             HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wbase.data(), wbase.size() * 4, hipMemcpyHostToDevice, stream));
-            r = filtered_exact(v, a, sel.size(), reinterpret_cast<const uint32_t *>(dv), A, x, dv, stream);
+            r = filtered_exact(v, a, sel.size(), reinterpret_cast<const uint32_t *>(dv), A,
+                               reinterpret_cast<const uint32_t *>(dv + x.o_wb), sel.size(), x, dv, stream);
             const hnsw_query_stats *unused;
             return r != HNSW_OK ? r : fetch(unused);  // (synchronises: `sel` and `wbase` live until then)
         },

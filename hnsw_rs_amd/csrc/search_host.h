@@ -78,17 +78,27 @@ int search_staged(hnsw_index *h, SearchScratch &s, const HostSearchPlan &p, Sear
 int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, uint32_t *ids, float *dists,
                 uint32_t *counts, hnsw_query_stats *stats, const uint32_t *entries);
 
-// k-NN among the admissible ids (hnsw_search_batch_filtered's contract).  exact_only: every query by the exact path
-// (hnsw_brute_force).  The results go to the caller's buffers (per-query statuses in stats: required), or, when
-// pin_block is given, straight into that pinned ResultBlock(nq, n) and the buffers are not read.  Returns argument and
-// launch errors only.
-int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const uint64_t *allow,
-                    uint64_t allow_bits, bool exact_only, uint32_t *ids, float *dists, uint32_t *counts,
-                    hnsw_query_stats *stats, uint8_t *paths, const PathCounters *ctr, void *pin_block = nullptr);
+// The allow-lists of a filtered call.  One mask for every query (mask_of == nullptr; masks == nullptr: every id below
+// allow_bits), or n_masks rows of ceil(allow_bits / 64) words and a row (or HNSW_MASK_NONE) per query.
+struct MaskSpec {
+    const uint64_t *masks = nullptr;
+    uint64_t allow_bits = 0;
+    uint32_t n_masks = 1;
+    const uint32_t *mask_of = nullptr;  // nq entries
+};
+
+// k-NN among the admissible ids (hnsw_search_batch_filtered's and _multi's contract): the planner runs per referenced
+// mask, the graph path's queries of all masks share one launch and one re-run loop, the exact path runs mask by mask.
+// exact_only: every query by the exact path (hnsw_brute_force).  The results go to the caller's buffers (per-query
+// statuses in stats: required), or, when pin_block is given, straight into that pinned ResultBlock(nq, n) and the
+// buffers are not read.  Returns argument and launch errors only.
+int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const MaskSpec &m,
+                    bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
+                    uint8_t *paths, const PathCounters *ctr, void *pin_block = nullptr);
 // ... with the first per-query error as the status (stats may be NULL)
-int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const uint64_t *allow,
-                            uint64_t allow_bits, bool exact_only, uint32_t *ids, float *dists, uint32_t *counts,
-                            hnsw_query_stats *stats, uint8_t *paths, const PathCounters *ctr);
+int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const MaskSpec &m,
+                            bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
+                            uint8_t *paths, const PathCounters *ctr);
 
 // hnsw_search_batch_device (finish = false) and _finish while ids are deleted: the filtered graph path over the
 // undeleted ids on the caller's stream; _finish re-runs the queries whose visited table filled up with larger tables,

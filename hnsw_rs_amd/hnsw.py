@@ -283,6 +283,36 @@ class HNSW:
                                                  C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
         return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
 
+    def search_batch_filtered_multi(self, Q, n, ef, masks, mask_of):
+        """k-NN with an allow-list per query (include/hnsw_mi355x.h, hnsw_search_batch_filtered_multi).  masks: what
+        pack_allow_many takes (None or empty when no query names a mask); mask_of [nq]: the row of masks each query
+        searches under, -1 or MASK_NONE for no allow-list.  -> as search_batch_filtered"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        nq = Q.shape[0]
+        mo = np.asarray(mask_of).reshape(-1).astype(np.int64)
+        if mo.shape[0] != nq:
+            raise ValueError("mask_of must hold one entry per query")
+        if ((mo < -1) | (mo > _lib.MASK_NONE)).any():
+            raise ValueError("mask_of entries are rows of masks, -1 or MASK_NONE")
+        mo = np.ascontiguousarray(np.where(mo < 0, _lib.MASK_NONE, mo).astype(np.uint32))
+        if masks is None or len(masks) == 0:
+            words, bits, n_masks = None, 0, 0
+        else:
+            words, bits = pack_allow_many(masks, self.len())
+            n_masks = words.shape[0]
+        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        paths = np.zeros(nq, dtype=np.uint8)
+        check(self._L.hnsw_search_batch_filtered_multi(
+            self._h, _p(Q, _f32p), nq, n, ef, None if words is None else _p(words, _u64p), n_masks, bits,
+            _p(mo, _u32p), _p(ids, _u32p), _p(dists, _f32p), _p(counts, _u32p),
+            C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
+        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+
     def ann_by_vector_filtered(self, vector, n, ef, allow):
         """ann_by_vector restricted to the allowed ids -> list of ids"""
         q = np.ascontiguousarray(vector, dtype=np.float32).reshape(1, -1)
@@ -554,6 +584,19 @@ def pack_allow(allow, n_points=None):
     if words.size == 0:
         words = np.zeros(1, dtype=np.uint64)
     return words, nbits
+
+
+def pack_allow_many(masks, n_points=None):
+    """-> (words [G, W] uint64, C-contiguous, allow_bits): the masks of hnsw_search_batch_filtered_multi.  masks: a 2-D
+    bool array [G, bits], or a sequence whose items are each what pack_allow takes (bool arrays of one common length,
+    or id arrays); row g is pack_allow(masks[g], n_points)[0] word for word."""
+    packed = [pack_allow(m, n_points) for m in masks]
+    if not packed:
+        raise ValueError("pack_allow_many needs at least one mask")
+    bits = {b for _, b in packed}
+    if len(bits) != 1:
+        raise ValueError("the masks of one call share allow_bits: got %s" % sorted(bits))
+    return np.ascontiguousarray(np.stack([w for w, _ in packed])), bits.pop()
 
 
 def synth_rows(recipe, seed, first_row, n, d, nb_threads=8):

@@ -188,11 +188,35 @@ int hnsw_search_batch(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, ui
  * A == 0 gives count 0 for every query.  The cosine option applies to the queries first.  Per-query errors
  * (HNSW_ERR_NAN_INPUT) as hnsw_search_batch.  The handle's deleted ids (hnsw_mark_deleted) are never allowed: the
  * effective mask is allow AND NOT deleted, and the result equals the same call with that mask on a handle with
- * nothing deleted.  Not provided: per-query masks, a device-pointer form of a filtered call, coalescing of one-query
- * filtered calls, filtered sharded search and the Rust shim's binding. */
+ * nothing deleted.  Not provided: masks resident in HBM across calls, a device-pointer form of a filtered call,
+ * coalescing of one-query filtered calls, filtered sharded search and the Rust shim's binding. */
 int hnsw_search_batch_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
                                const uint64_t *allow, uint64_t allow_bits, uint32_t *ids, float *dists,
                                uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths /* 0/1/2 or NULL */);
+/* The same with an allow-list PER QUERY: a batch whose requests carry different filters in one call.  masks is
+ * n_masks rows of W = ceil(allow_bits / 64) words, row-major and contiguous, each row a mask in the layout above (all
+ * share allow_bits); mask_of[i] names query i's row, or is HNSW_MASK_NONE: no allow-list, every id < hnsw_len is
+ * allowed (no all-ones mask is built for it).  n_masks == 0 with masks == NULL is legal when every query is
+ * HNSW_MASK_NONE.  Query i's ids, distance bits, count, stats (status included) and path are exactly what
+ * hnsw_search_batch_filtered returns for that query alone under mask mask_of[i] (HNSW_MASK_NONE: under an all-ones
+ * mask over hnsw_len bits) on the same handle with the same options: n, ef', deleted ids, the cosine option and
+ * per-query errors as there (the call returns the first per-query error, every other row is filled in).
+ * The planner runs per mask: the host counts the admissible ids A_g of every mask some query names; the queries of a
+ * mask with A_g <= "filter_exact_max" take the exact path (1), the others the graph path (0), and a graph-path query
+ * that fills the largest visited table is answered by the exact path under its own mask (2).  ef' > 256 is
+ * HNSW_ERR_ARG when at least one named mask takes the graph path.  Masks no query names are neither counted nor
+ * compacted.  All graph-path queries of all masks share ONE kernel launch (one wave per query, each wave reads its own
+ * mask); the exact path runs once per named exact-path mask over that mask's queries.
+ * HNSW_ERR_ARG, decided before the device is touched: Q, ids or mask_of NULL; masks NULL while allow_bits > 0 and some
+ * query names a mask; a mask_of[i] that is neither < n_masks nor HNSW_MASK_NONE; n > 64; nq > 2^31 - 1.  nq == 0 is
+ * HNSW_OK; n == 0 zeroes counts and launches nothing.  hnsw_get_stat: the three "filtered_*" counters advance by the
+ * queries answered on each path, "filtered_multi_calls" by one and "filtered_multi_masks" by the masks named
+ * (HNSW_MASK_NONE counts as one). */
+#define HNSW_MASK_NONE 0xFFFFFFFFu
+int hnsw_search_batch_filtered_multi(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                     const uint64_t *masks, uint32_t n_masks, uint64_t allow_bits,
+                                     const uint32_t *mask_of /* nq */, uint32_t *ids, float *dists, uint32_t *counts,
+                                     hnsw_query_stats *stats, uint8_t *paths /* 0/1/2 or NULL */);
 /* Same with every buffer already resident in HBM on the handle's device; enqueues on `stream`
  * (a hipStream_t, NULL = default stream) and returns without synchronising.  d_stats is
  * required (its status field carries per-query errors); d_dists / d_counts may be NULL. */
@@ -352,8 +376,9 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * "build_rerun_points" (points whose insertion search filled the first, smaller visited table and ran again with a
  * larger one) and "build_kept_last_edges" (edges a prune dropped on one side only because they were the other
  * node's last edge -- the drop kernel's refusals plus the seed's clamp restores -- mirrored after the build; in the
- * sharded build every rank reports the whole build's, like "build_points"); hnsw_search_batch_filtered's queries by
- * path: "filtered_queries_graph" (0), "filtered_queries_exact" (1), "filtered_overflow_exact" (2); deletion:
+ * sharded build every rank reports the whole build's, like "build_points"); hnsw_search_batch_filtered's (and
+ * _multi's) queries by path: "filtered_queries_graph" (0), "filtered_queries_exact" (1), "filtered_overflow_exact" (2);
+ * hnsw_search_batch_filtered_multi's calls and named masks: "filtered_multi_calls", "filtered_multi_masks"; deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
