@@ -81,6 +81,19 @@ SYMBOLS = {
                                              f32p, u32p, C.POINTER(QueryStats), u8p]),
     "hnsw_search_batch_filtered_multi": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, u64p, C.c_uint32,
                                                    C.c_uint64, u32p, u32p, f32p, u32p, C.POINTER(QueryStats), u8p]),
+    "hnsw_mask_set_create": (C.c_int, [vp, C.c_uint32, C.c_uint64, u64p, C.POINTER(vp)]),
+    "hnsw_mask_set_free": (None, [vp]),
+    "hnsw_mask_set_info": (C.c_int, [vp, u32p, u64p]),
+    "hnsw_mask_set_write": (C.c_int, [vp, C.c_uint32, u64p]),
+    "hnsw_mask_set_update": (C.c_int, [vp, C.c_uint32, u32p, C.c_uint64, C.c_int]),
+    "hnsw_mask_set_read": (C.c_int, [vp, C.c_uint32, u64p]),
+    "hnsw_mask_set_count": (C.c_int, [vp, C.c_uint32, u64p]),
+    "hnsw_search_batch_filtered_set": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, vp, u32p, u32p, f32p,
+                                                 u32p, C.POINTER(QueryStats), u8p]),
+    "hnsw_search_batch_filtered_device": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp,
+                                                    vp]),
+    "hnsw_search_batch_filtered_device_finish": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp,
+                                                           vp, vp, vp, u8p]),
     "hnsw_search_batch_device": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
     "hnsw_search_batch_device_finish": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
     "hnsw_distance_batch": (C.c_int, [vp, f32p, u32p, C.c_uint64, f32p]),

@@ -381,6 +381,59 @@ int hnsw_search_batch_filtered_multi(hnsw_index *h, const float *Q, uint64_t nq,
                                        dists, counts, stats, paths, &ctr);
 }
 
+// ---- searches under a resident mask set (mask_set.h) --------------------------------------------------------
+static int check_set(const hnsw_index *h, const hnsw_mask_set *set) {
+    if (!set || set->owner != h) {
+        set_error(set ? "filtered search: the mask set belongs to another handle" : "filtered search: needs a mask set");
+        return HNSW_ERR_ARG;
+    }
+    return HNSW_OK;
+}
+
+int hnsw_search_batch_filtered_set(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                   hnsw_mask_set *set, const uint32_t *mask_of, uint32_t *ids, float *dists,
+                                   uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK || (rc = check_set(h, set))) return rc;
+    if (nq == 0) return HNSW_OK;
+    std::vector<uint32_t> row0;
+    if (!mask_of && nq <= 0x7FFFFFFFull) {  // every query under row 0 (more queries are refused below)
+        row0.assign(nq, 0);
+        mask_of = row0.data();
+    }
+    const hx::PathCounters ctr = hx::filt_counters(h);
+    return hx::search_filtered_checked(h, Q, nq, n, ef,
+                                       hx::MaskSpec{set->words.data(), set->allow_bits, set->n_masks, mask_of, set}, false,
+                                       ids, dists, counts, stats, paths, &ctr);
+}
+
+static int filtered_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, hnsw_mask_set *set,
+                           const uint32_t *d_mask_of, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                           hnsw_query_stats *d_stats, void *stream, bool finish, uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK || (rc = check_set(h, set))) return rc;
+    if (nq == 0 || n == 0) return HNSW_OK;
+    if (!d_Q || !d_ids || !d_stats || nq > 0x7FFFFFFFull) {
+        set_error("filtered device search: needs queries, an id buffer and a stats buffer in HBM");
+        return HNSW_ERR_ARG;
+    }
+    return hx::search_device_set(h, set, d_Q, nq, n, ef, d_mask_of, d_ids, d_dists, d_counts, d_stats,
+                                 static_cast<hipStream_t>(stream), finish, paths);
+}
+
+int hnsw_search_batch_filtered_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                      hnsw_mask_set *set, const uint32_t *d_mask_of, uint32_t *d_ids, float *d_dists,
+                                      uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream) {
+    return filtered_device(h, d_Q, nq, n, ef, set, d_mask_of, d_ids, d_dists, d_counts, d_stats, stream, false, nullptr);
+}
+
+int hnsw_search_batch_filtered_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                             hnsw_mask_set *set, const uint32_t *d_mask_of, uint32_t *d_ids,
+                                             float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream,
+                                             uint8_t *paths) {
+    return filtered_device(h, d_Q, nq, n, ef, set, d_mask_of, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
+}
+
 int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
                              uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
                              hnsw_query_stats *d_stats, void *stream) {
@@ -883,6 +936,13 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value) {
     } else if (!strcmp(key, "filter_exact_max")) {
         h->filter_exact_max = value;
         return HNSW_OK;
+    } else if (!strcmp(key, "mask_set_cache_mb")) {
+        if (value < 0) {
+            set_error("mask_set_cache_mb must not be negative");
+            return HNSW_ERR_ARG;
+        }
+        h->mask_set_cache_mb = std::min<int64_t>(value, 1 << 20);
+        return HNSW_OK;
     } else if (!strcmp(key, "gpu_build_batch_max")) {
         if (value < 1) {
             set_error("gpu_build_batch_max must be positive");
@@ -965,6 +1025,14 @@ int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
         *out = h->n_filt_multi_calls.load();
     } else if (!strcmp(key, "filtered_multi_masks")) {
         *out = h->n_filt_multi_masks.load();
+    } else if (!strcmp(key, "mask_set_words_uploaded")) {
+        *out = h->n_set_words_uploaded.load();
+    } else if (!strcmp(key, "mask_set_recounts")) {
+        *out = h->n_set_recounts.load();
+    } else if (!strcmp(key, "mask_set_compactions")) {
+        *out = h->n_set_compactions.load();
+    } else if (!strcmp(key, "filtered_set_calls")) {
+        *out = h->n_filt_set_calls.load();
     } else if (!strcmp(key, "deleted")) {
         *out = h->del.count;
     } else if (!strcmp(key, "deleted_mask_words_uploaded")) {

@@ -5,7 +5,8 @@
 // Marking and unmarking touch the host words only and list the words they changed; the next search that needs
 // the HBM copy brings it up to date (DeletedSet::sync): the changed words travel as (word index, value) pairs in
 // one copy and are scattered by a small kernel (deleted_mask.hip), or, when many words changed or the copy does
-// not exist yet, the whole mask is copied.
+// not exist yet, the whole mask is copied.  That mechanism is HbmWords, which the resident mask sets (mask_set.h)
+// share.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,22 +17,44 @@
 
 namespace hx {
 
-struct DeletedSet {
-    std::vector<uint64_t> words;  // id i is deleted iff bit i & 63 of words[i >> 6] is set; covers every marked id
-    uint64_t count = 0;           // ids deleted
+// The HBM copy of an array of 64-bit words the host owns, and the list of words the host changed since the copy was
+// last brought up to date.
+struct HbmWords {
     // words changed since the HBM copy was last brought up to date, each listed once
     std::vector<uint32_t> dirty;
-    std::vector<uint8_t> dirty_flag;
+    std::vector<uint8_t> dirty_flag;  // one per host word (the owner sizes it)
     // the HBM copy: d_cap words on device d_device; d_stage holds the pairs of one scatter
     uint64_t *d_words = nullptr, *d_stage = nullptr;
     uint64_t d_cap = 0, d_stage_cap = 0;
     int d_device = -1;
-    uint64_t words_uploaded = 0;  // words copied to HBM so far (hnsw_get_stat "deleted_mask_words_uploaded")
+    uint64_t words_uploaded = 0;  // words copied to HBM so far
 
-    DeletedSet() = default;
-    DeletedSet(const DeletedSet &) = delete;
-    DeletedSet &operator=(const DeletedSet &) = delete;
-    ~DeletedSet() { release_device(); }
+    HbmWords() = default;
+    HbmWords(const HbmWords &) = delete;
+    HbmWords &operator=(const HbmWords &) = delete;
+    ~HbmWords() { release_device(); }
+
+    void touch(uint64_t w) {  // host word w changed
+        if (!dirty_flag[w]) {
+            dirty_flag[w] = 1;
+            dirty.push_back((uint32_t)w);
+        }
+    }
+    bool current(int device) const { return d_words && d_device == device && dirty.empty(); }
+    // brings the HBM copy of host[nw] on `device` up to date: the changed words as (index, value) pairs scattered by
+    // hx_deleted_scatter_kernel, or one whole copy when there is no copy yet (made with room for `slack` more words,
+    // zeroed), the device changed or more than an eighth of the words changed.  Synchronises `stream` before
+    // returning.
+    int sync_words(const uint64_t *host, uint64_t nw, uint64_t slack, int device, hipStream_t stream);
+    void release_device();
+};
+
+struct DeletedSet : HbmWords {
+    std::vector<uint64_t> words;  // id i is deleted iff bit i & 63 of words[i >> 6] is set; covers every marked id
+    uint64_t count = 0;           // ids deleted
+    // advances whenever the set of deleted ids changes: what a cache over the admissible ids (mask_set.h) is valid for
+    uint64_t version = 0;
+    // (HbmWords::words_uploaded is hnsw_get_stat "deleted_mask_words_uploaded")
 
     bool test(uint64_t id) const { return (id >> 6) < words.size() && ((words[id >> 6] >> (id & 63)) & 1ull) != 0; }
     // marks (on) or unmarks k ids, all below n_points (checked by the caller); the mask grows to cover n_points
@@ -43,8 +66,9 @@ struct DeletedSet {
     // ids the mask covers (FilterArgs::deny_bits): ids beyond it are not deleted
     uint64_t deny_bits() const { return (uint64_t)words.size() * 64; }
     // brings the HBM copy on `device` up to date; synchronises `stream` before returning
-    int sync(int device, hipStream_t stream);
-    void release_device();
+    int sync(int device, hipStream_t stream) {
+        return sync_words(words.data(), words.size(), words.size() / 8 + 16, device, stream);  // room for later inserts
+    }
 };
 
 // the sidecar file <dir>/deleted: u64 count, then that many u32 ids in strictly ascending order, big-endian.

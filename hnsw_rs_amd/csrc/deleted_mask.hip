@@ -1,5 +1,6 @@
-// deleted_mask.hip -- the deleted set of a handle (deleted.h): host bookkeeping and the HBM copy's update, with
-// its one kernel, hx_deleted_scatter_kernel (gfx950).
+// deleted_mask.hip -- the deleted set of a handle (deleted.h): host bookkeeping and the update of an HBM copy of
+// host words (HbmWords: the deleted set's, and the resident mask sets'), with its one kernel,
+// hx_deleted_scatter_kernel (gfx950).
 
 #include <algorithm>
 #include <cstring>
@@ -33,10 +34,8 @@ void DeletedSet::set(const uint32_t *ids, uint64_t k, bool on, uint64_t n_points
         if (((w & bit) != 0) == on) continue;  // idempotent: an unchanged word is not listed
         w ^= bit;
         count = on ? count + 1 : count - 1;
-        if (!dirty_flag[id >> 6]) {
-            dirty_flag[id >> 6] = 1;
-            dirty.push_back(id >> 6);
-        }
+        version++;
+        touch(id >> 6);
     }
 }
 
@@ -52,12 +51,13 @@ void DeletedSet::assign_host(const std::vector<uint64_t> &w) {
     release_device();
     words = w;
     count = 0;
+    version++;
     for (uint64_t x : words) count += (uint64_t)__builtin_popcountll(x);
     dirty.clear();
     dirty_flag.assign(words.size(), 0);
 }
 
-void DeletedSet::release_device() {
+void HbmWords::release_device() {
     if (d_words) (void)hipFree(d_words);
     if (d_stage) (void)hipFree(d_stage);
     d_words = d_stage = nullptr;
@@ -65,14 +65,13 @@ void DeletedSet::release_device() {
     d_device = -1;
 }
 
-int DeletedSet::sync(int device, hipStream_t stream) {
-    const uint64_t nw = words.size();
+int HbmWords::sync_words(const uint64_t *words, uint64_t nw, uint64_t slack, int device, hipStream_t stream) {
     if (d_words && (d_device != device || d_cap < nw)) release_device();
     // a whole copy when there is no HBM copy yet, or when more than an eighth of the words changed (a pair is
     // twice a word's bytes, and the scatter is one more launch)
     const bool whole = !d_words || dirty.size() * 8 > nw;
     if (!d_words) {
-        const uint64_t cap = std::max<uint64_t>(1, nw + nw / 8 + 16);  // room for the ids of later inserts
+        const uint64_t cap = std::max<uint64_t>(1, nw + slack);
         HIP_TRY(hipMalloc(&d_words, cap * 8));
         d_cap = cap;
         d_device = device;
@@ -81,7 +80,7 @@ int DeletedSet::sync(int device, hipStream_t stream) {
         return HNSW_OK;
     }
     if (whole) {
-        if (nw) HIP_TRY(hipMemcpyAsync(d_words, words.data(), nw * 8, hipMemcpyHostToDevice, stream));
+        if (nw) HIP_TRY(hipMemcpyAsync(d_words, words, nw * 8, hipMemcpyHostToDevice, stream));
         words_uploaded += nw;
     } else {
         const uint64_t np = dirty.size();

@@ -51,6 +51,11 @@ struct hnsw_index {
     // by the filtered search over the undeleted ids and count their queries per path here
     hx::DeletedSet del;
     std::atomic<uint64_t> n_del_graph{0}, n_del_exact{0}, n_del_overflow{0};
+    // resident mask sets (hnsw_mask_set, mask_set.h) of this handle, summed: words of any set copied to HBM, rows whose
+    // admissible ids the host counted, compactions launched for rows of a set, searches under a set; the budget of a
+    // set's compacted lists in HBM (option "mask_set_cache_mb")
+    std::atomic<uint64_t> n_set_words_uploaded{0}, n_set_recounts{0}, n_set_compactions{0}, n_filt_set_calls{0};
+    int64_t mask_set_cache_mb = 64;
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")
 };
 

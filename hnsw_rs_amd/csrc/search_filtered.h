@@ -5,8 +5,10 @@
 // (allow_bits is already clamped to the index length by the caller); without a mask (allow == nullptr) every id
 // below allow_bits is.  One mask serves the call (mask_of == nullptr), or allow holds rows of mask_words words
 // and query q walks under row mask_of[q] (hnsw_search_batch_filtered_multi); HNSW_MASK_NONE there means no mask:
-// every id below none_bits.  Only the graph kernel reads mask_of: the exact path's kernels are launched per mask
-// with allow at that mask's row.  The handle's deleted set (hnsw_mark_deleted) is a second mask of the same
+// every id below none_bits.  The rows may be a resident mask set's (mask_set.h), and mask_of may then come from the
+// caller's device memory, unseen by the host: the graph kernel checks it against n_masks and answers a query that
+// names a row beyond it with status HNSW_ERR_ARG before it reads a mask word.  Only the graph kernel reads mask_of: the
+// exact path's kernels are launched per mask with allow at that mask's row.  The handle's deleted set (hnsw_mark_deleted) is a second mask of the same
 // layout, deny: an id is admissible iff it is allowed and not denied.
 #pragma once
 
@@ -29,6 +31,7 @@ struct FilterArgs {
     const uint64_t *deny;      // the deleted ids' mask words (device), or nullptr: nothing deleted
     uint64_t deny_bits;        // ids the deny mask covers (a multiple of 64); ids beyond it are not denied
     uint32_t n, ef;            // results per query, ef' = max(ef, n, 1)
+    uint32_t n_masks;          // rows of allow (read with mask_of only): a mask_of entry is below it or HNSW_MASK_NONE
     uint32_t *out_ids;         // nq x n
     float *out_dists;          // nq x n
     uint32_t *out_counts;      // nq

@@ -285,8 +285,12 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
     const uint32_t q = a.qsel ? a.qsel[blockIdx.x] : blockIdx.x;
     // the wave's mask and id bound, picked once (scalar: q is the block's)
     const uint32_t g = a.mask_of ? a.mask_of[q] : 0;
+    // a row the set does not have (mask_of may be the caller's device memory, which the host never saw): the query's
+    // own error, decided for the whole wave before a mask word is read: no walk (the status below), padded outputs,
+    // and an id bound of 0, under which filt_allowed refuses every id before it touches the row pointer
+    const bool bad_row = a.mask_of && g != HNSW_MASK_NONE && g >= a.n_masks;
     const uint64_t *allow = g == HNSW_MASK_NONE ? nullptr : a.allow + (size_t)g * a.mask_words;
-    const uint64_t bound = g == HNSW_MASK_NONE ? a.none_bits : a.allow_bits;
+    const uint64_t bound = bad_row ? 0 : g == HNSW_MASK_NONE ? a.none_bits : a.allow_bits;
     uint32_t *htab = reinterpret_cast<uint32_t *>(smem);
     u64 *perm = reinterpret_cast<u64 *>(smem + (4ull << slots_log2));
     float *yq = reinterpret_cast<float *>(perm + 64 * R);
@@ -300,6 +304,7 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
 
     uint32_t n_dist = 0, n_exp = 0, sum_deg = 0, n_vis = 0;
     int32_t status = stage_query<KIND>(v, a.Q + (size_t)q * v.dim, yq, lane) ? HNSW_OK : HNSW_ERR_NAN_INPUT;
+    if (bad_row) status = HNSW_ERR_ARG;
 
     auto clear_visited = [&]() {
         for (uint32_t s = lane; s < (1u << (slots_log2 - 2)); s += 64)

@@ -178,22 +178,6 @@ int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, u
 }
 
 // ---- filtered search, and the unfiltered entry points while ids are deleted --------------------------------------
-namespace {
-
-// brings the deleted set's HBM copy up to date on the snapshot's device (on a stream of the handle's own, so that a
-// caller's stream is not synchronised); a no-op while nothing is deleted
-int sync_deleted(hnsw_index *h) {
-    if (h->del.count == 0) return HNSW_OK;
-    std::lock_guard<std::mutex> g(h->mu);
-    if (h->del.d_words && h->del.d_device == h->dev.device && h->del.dirty.empty()) return HNSW_OK;
-    ScratchLease lease(h);
-    int rc = lease.prepare(h->dev.device, 0, 0);
-    if (rc != HNSW_OK) return rc;
-    return h->del.sync(h->dev.device, lease.s->stream);
-}
-
-// The admissible ids of a call: below bits = min(allow_bits, len), allowed by `allow` (nullptr: all), not deleted.
-// -> A, and the admissible ids before every block of 64 words (the compaction kernel's offsets)
 uint64_t count_admissible(const hnsw_index *h, const uint64_t *allow, uint64_t bits, std::vector<uint32_t> &wbase) {
     const uint64_t n_words = (bits + 63) / 64, n_wblk = (n_words + 63) / 64;
     const std::vector<uint64_t> &deny = h->del.words;
@@ -208,6 +192,20 @@ uint64_t count_admissible(const hnsw_index *h, const uint64_t *allow, uint64_t b
         A += (uint64_t)__builtin_popcountll(x);
     }
     return A;
+}
+
+namespace {
+
+// brings the deleted set's HBM copy up to date on the snapshot's device (on a stream of the handle's own, so that a
+// caller's stream is not synchronised); a no-op while nothing is deleted
+int sync_deleted(hnsw_index *h) {
+    if (h->del.count == 0) return HNSW_OK;
+    std::lock_guard<std::mutex> g(h->mu);
+    if (h->del.d_words && h->del.d_device == h->dev.device && h->del.dirty.empty()) return HNSW_OK;
+    ScratchLease lease(h);
+    int rc = lease.prepare(h->dev.device, 0, 0);
+    if (rc != HNSW_OK) return rc;
+    return h->del.sync(h->dev.device, lease.s->stream);
 }
 
 // The exact path's scratch from `base` in a device arena: [word offsets | admissible ids | partial keys | partial
@@ -229,13 +227,19 @@ struct ExactScratch {
 
 // the exact path for nsel queries under ONE mask (a.allow, a.allow_bits; a.mask_of is not read): those of d_sel, or
 // the first nsel of the call; the mask's word offsets are at d_wb.  shape_nsel: the query count the launch shape
-// (queries per launch, segments) is chosen for
+// (queries per launch, segments) is chosen for.  d_list: the mask's admissible ids, already compacted (a resident
+// set's cached list) -- no compaction is launched and d_wb is not read; nullptr: compacted into the scratch
 int filtered_exact(const DevView &v, const FilterArgs &a, uint64_t nsel, const uint32_t *d_sel, uint64_t A,
                    const uint32_t *d_wb, uint64_t shape_nsel, const ExactScratch &x, unsigned char *dv,
-                   hipStream_t stream) {
+                   hipStream_t stream, const uint32_t *d_list = nullptr) {
     const uint32_t chunk = (uint32_t)std::min<uint64_t>(shape_nsel, 65535), nseg = filt_exact_segments(A, chunk);
-    uint32_t *d_ids = reinterpret_cast<uint32_t *>(dv + x.o_ids);
-    int r = launch_filter_compact(a, (a.allow_bits + 63) / 64, d_wb, d_ids, stream);
+    const uint32_t *d_ids = d_list;
+    int r = HNSW_OK;
+    if (!d_list) {
+        uint32_t *d_scratch_ids = reinterpret_cast<uint32_t *>(dv + x.o_ids);
+        r = launch_filter_compact(a, (a.allow_bits + 63) / 64, d_wb, d_scratch_ids, stream);
+        d_ids = d_scratch_ids;
+    }
     for (uint64_t c = 0; r == HNSW_OK && c < nsel; c += chunk) {
         FilterArgs ac = a;
         if (d_sel) {
@@ -264,6 +268,8 @@ struct MaskGroup {
     bool exact = false;     // A <= filter_exact_max
     size_t wb = 0;            // its word offsets in the call's list: from wb_all[wb]
     size_t q0 = 0, nq = 0;    // its queries: order[q0 .. q0 + nq)
+    int64_t srow = -1;        // its row of the call's resident set (-1: the call has none, or HNSW_MASK_NONE)
+    const uint32_t *d_list = nullptr;  // ... and that row's cached list of admissible ids in HBM, when it is valid
 };
 
 }  // namespace
@@ -280,6 +286,7 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         return HNSW_ERR_ARG;
     }
     const bool multi = m.mask_of != nullptr;
+    hnsw_mask_set *const set = m.set;  // (a call under a set is a multi call: the entry point sees to mask_of)
     if (multi) {
         bool masked = false;
         for (uint64_t i = 0; i < nq; i++) {
@@ -319,6 +326,7 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
                     groups.push_back(MaskGroup{nullptr, 0, len});
                 else  // (masks may be NULL when allow_bits is 0: nothing is allowed, no word is read)
                     groups.push_back(MaskGroup{m.masks ? m.masks + g * row_words : nullptr, g * row_words, bits});
+                if (set && g != HNSW_MASK_NONE && groups.back().allow) groups.back().srow = g;
                 groups.back().q0 = i;
             }
             groups.back().nq++;
@@ -326,8 +334,18 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     }
     std::vector<uint32_t> wb_all, wb;
     uint64_t A_max = 0, n_graph = 0, n_exact = 0;
+    // under a set the counts come from its caches (a row is counted when it, the deleted set or the length changed);
+    // the set stays locked until its HBM copy is up to date and the lists this call needs are made
+    std::unique_lock<std::mutex> set_lock;
+    if (set) set_lock = std::unique_lock<std::mutex>(set->mu);
     for (MaskGroup &g : groups) {
-        g.A = count_admissible(h, g.allow, g.bits, wb);
+        if (g.srow >= 0) {
+            const hnsw_mask_set::Row &r = set->counted(h, (uint32_t)g.srow);
+            g.A = r.A;
+            wb = r.wbase;
+        } else {
+            g.A = count_admissible(h, g.allow, g.bits, wb);
+        }
         g.exact = exact_only || (int64_t)g.A <= h->filter_exact_max;
         g.wb = wb_all.size();
         wb_all.insert(wb_all.end(), wb.begin(), wb.end());
@@ -354,14 +372,15 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
                 if (!groups[group_of[i]].exact) gsel.push_back((uint32_t)i);
         }
     }
-    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h))) return rc;
+    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h)) || (set && (rc = set->sync(h)))) return rc;
     const DevView &v = h->dev.view;
     const uint32_t d = v.dim;
     // device arena: [queries | masks | mask of every query | selection | the exact path's selection | the exact path's
     // scratch | result block].  All n_masks rows go up in one copy (a one-mask call sends the words below `bits` only).
     // The result block comes back in one copy to pinned memory: the caller's block, or the scratch's and from there to
     // the caller's buffers
-    const uint64_t up_words = !m.masks ? 0 : multi ? (uint64_t)m.n_masks * row_words : (bits + 63) / 64;
+    // (a set's rows are in HBM already: nothing goes up, and the arena has no masks)
+    const uint64_t up_words = !m.masks || set ? 0 : multi ? (uint64_t)m.n_masks * row_words : (bits + 63) / 64;
     const size_t o_q = 0, o_mask = o_q + align256(nq * d * 4), o_mof = o_mask + align256(up_words * 8);
     const size_t o_sel = o_mof + align256(multi ? nq * 4 : 0), o_xsel = o_sel + align256(nq * 4);
     const ExactScratch x(o_xsel + align256(multi ? nq * 4 : 0), nq, n, A_max, wb_all.size());
@@ -373,12 +392,18 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     unsigned char *dv = static_cast<unsigned char *>(s.dev);
     void *hv = pin_block ? pin_block : s.pin;
     uint32_t *d_sel = reinterpret_cast<uint32_t *>(dv + o_sel), *d_xsel = reinterpret_cast<uint32_t *>(dv + o_xsel);
-    const uint64_t *d_masks = up_words ? reinterpret_cast<const uint64_t *>(dv + o_mask) : nullptr;
+    const uint64_t *d_masks = set ? set->d_rows() : up_words ? reinterpret_cast<const uint64_t *>(dv + o_mask) : nullptr;
     const uint32_t *d_wb = reinterpret_cast<const uint32_t *>(dv + x.o_wb);
     HIP_TRY(hipMemcpyAsync(dv + o_q, Q, nq * d * 4, hipMemcpyHostToDevice, s.stream));
     if ((rc = cosine_queries(h, dv + o_q, nq, s.stream))) return rc;
     if (up_words) HIP_TRY(hipMemcpyAsync(dv + o_mask, m.masks, up_words * 8, hipMemcpyHostToDevice, s.stream));
-    if (bits || multi) HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, s.stream));
+    // (under a set the word offsets of a mask go up only when a compaction of it runs)
+    auto upload_wb = [&](const MaskGroup &g) -> int {
+        const size_t n_wb = (&g == &groups.back() ? wb_all.size() : (&g)[1].wb) - g.wb;
+        HIP_TRY(hipMemcpyAsync(dv + x.o_wb + g.wb * 4, wb_all.data() + g.wb, n_wb * 4, hipMemcpyHostToDevice, s.stream));
+        return HNSW_OK;
+    };
+    if (!set && (bits || multi)) HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, s.stream));
     if (multi) {
         HIP_TRY(hipMemcpyAsync(dv + o_mof, m.mask_of, nq * 4, hipMemcpyHostToDevice, s.stream));
         if (!gsel.empty()) HIP_TRY(hipMemcpyAsync(d_sel, gsel.data(), gsel.size() * 4, hipMemcpyHostToDevice, s.stream));
@@ -396,14 +421,46 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     a.deny_bits = h->del.count ? h->del.deny_bits() : 0;
     a.n = n;
     a.ef = efp;
+    a.n_masks = m.n_masks;  // (every mask_of entry was checked against it above)
     out.bind(a, dv + o_out);
-    // the exact path for nsel queries of one mask (sel on the device; nullptr: the first nsel of the call)
-    auto exact = [&](const MaskGroup &g, uint64_t nsel, const uint32_t *sel) -> int {
+    auto group_args = [&](const MaskGroup &g) {
         FilterArgs ax = a;
         ax.mask_of = nullptr;
         ax.allow = g.allow ? d_masks + g.row : nullptr;
         ax.allow_bits = g.bits;
-        return filtered_exact(v, ax, nsel, sel, g.A, d_wb + g.wb, multi ? nsel : nq, x, dv, s.stream);
+        return ax;
+    };
+    if (set) {
+        // the lists of the rows planned on the exact path: a valid one is used as it is, the others are compacted
+        // into the set (while its budget lasts) here, once, for this call and the ones after it
+        const uint64_t budget = h->mask_set_cache_mb > 0 ? (uint64_t)h->mask_set_cache_mb << 20 : 0;
+        std::vector<hnsw_mask_set::Row *> made;
+        for (MaskGroup &g : groups) {
+            if (g.srow < 0) continue;
+            hnsw_mask_set::Row &r = set->rows[(size_t)g.srow];
+            if (!r.list_valid && g.exact && set->reserve_list(r, budget)) {
+                if ((rc = upload_wb(g)) ||
+                    (rc = launch_filter_compact(group_args(g), (g.bits + 63) / 64, d_wb + g.wb, r.d_ids, s.stream)))
+                    return rc;
+                h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
+                made.push_back(&r);
+            }
+            if (r.list_valid || (!made.empty() && made.back() == &r)) g.d_list = r.d_ids;
+        }
+        if (!made.empty()) {  // (searches on other streams read the lists next)
+            HIP_TRY(hipStreamSynchronize(s.stream));
+            for (hnsw_mask_set::Row *r : made) r->list_valid = true;
+        }
+        set_lock.unlock();
+    }
+    // the exact path for nsel queries of one mask (sel on the device; nullptr: the first nsel of the call)
+    auto exact = [&](const MaskGroup &g, uint64_t nsel, const uint32_t *sel) -> int {
+        if (set && !g.d_list) {  // a row beyond the set's budget, or no row of the set: compacted in the scratch
+            int r = upload_wb(g);
+            if (r != HNSW_OK) return r;
+            if (g.srow >= 0) h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
+        }
+        return filtered_exact(v, group_args(g), nsel, sel, g.A, d_wb + g.wb, multi ? nsel : nq, x, dv, s.stream, g.d_list);
     };
     auto fetch = [&](const hnsw_query_stats *&st) -> int {
         HIP_TRY(hipMemcpyAsync(hv, dv + o_out, out.bytes, hipMemcpyDeviceToHost, s.stream));
@@ -448,7 +505,9 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         ctr->graph->fetch_add(n_graph - n2, std::memory_order_relaxed);
         ctr->overflow->fetch_add(n2, std::memory_order_relaxed);
     }
-    if (multi) {
+    if (set) {
+        h->n_filt_set_calls.fetch_add(1, std::memory_order_relaxed);
+    } else if (multi) {
         h->n_filt_multi_calls.fetch_add(1, std::memory_order_relaxed);
         h->n_filt_multi_masks.fetch_add(groups.size(), std::memory_order_relaxed);
     }
@@ -549,6 +608,158 @@ int search_device_deleted(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t
     h->n_del_graph.fetch_add(nq - n2, std::memory_order_relaxed);
     h->n_del_overflow.fetch_add(n2, std::memory_order_relaxed);
     return first_query_error(st, nq);
+}
+
+int search_device_set(hnsw_index *h, hnsw_mask_set *set, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                      const uint32_t *d_mask_of, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                      hnsw_query_stats *d_stats, hipStream_t stream, bool finish, uint8_t *paths) {
+    const uint32_t efp = std::max(std::max(ef, n), 1u);
+    if (n > HX_FILT_MAX_N || efp > HX_FILT_MAX_EF) {
+        set_error("filtered device search: needs n <= %d and ef' = max(ef, n) <= %d", HX_FILT_MAX_N, HX_FILT_MAX_EF);
+        return HNSW_ERR_ARG;
+    }
+    if (!d_mask_of && set->n_masks == 0) {
+        set_error("filtered device search: every query names row 0 of a set without rows");
+        return HNSW_ERR_ARG;
+    }
+    int rc;
+    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h))) return rc;
+    {
+        std::lock_guard<std::mutex> g(set->mu);
+        if ((rc = set->sync(h))) return rc;
+    }
+    const DevView &v = h->dev.view;
+    DeviceQueries dq;
+    if ((rc = dq.prepare(h, d_Q, nq, stream))) return rc;
+    // the kernels write distances and counts: stream-ordered stand-ins for the optional outputs
+    struct Tmp {
+        void *p = nullptr;
+        hipStream_t st = nullptr;
+        ~Tmp() {
+            if (p) (void)hipFreeAsync(p, st);
+        }
+    } t_dists, t_counts;
+    if (!d_dists) {
+        HIP_TRY(hipMallocAsync(&t_dists.p, nq * n * 4, stream));
+        t_dists.st = stream;
+        d_dists = static_cast<float *>(t_dists.p);
+    }
+    if (!d_counts) {
+        HIP_TRY(hipMallocAsync(&t_counts.p, nq * 4, stream));
+        t_counts.st = stream;
+        d_counts = static_cast<uint32_t *>(t_counts.p);
+    }
+    const uint64_t len = index_len(h), bits = std::min<uint64_t>(set->allow_bits, len);
+    FilterArgs a{};
+    a.Q = dq.q;
+    a.allow = set->d_rows();
+    a.allow_bits = bits;
+    a.mask_of = d_mask_of;
+    a.mask_words = set->W;
+    a.none_bits = len;
+    a.n_masks = set->n_masks;  // the kernel checks d_mask_of against it: the host has not seen those words
+    a.deny = h->del.count ? h->del.d_words : nullptr;
+    a.deny_bits = h->del.count ? h->del.deny_bits() : 0;
+    a.n = n;
+    a.ef = efp;
+    a.out_ids = d_ids;
+    a.out_dists = d_dists;
+    a.out_counts = d_counts;
+    a.out_stats = d_stats;
+    const uint32_t slots = filt_first_slots_log2(v, efp);
+    if (!finish) return launch_filtered_graph(v, a, (uint32_t)nq, slots, stream);
+
+    // scratch: the selection on the device; the statuses and the rows the queries name on the host; the exact path's
+    // part ([selection | its scratch]) is sized only when a query reaches it
+    const size_t st_bytes = align256(nq * sizeof(hnsw_query_stats)), pin_bytes = st_bytes + nq * 4;
+    ScratchLease lease(h);
+    if ((rc = lease.prepare(h->dev.device, align256(nq * 4), pin_bytes))) return rc;
+    const hnsw_query_stats *st = nullptr;
+    const uint32_t *mask_of = nullptr;
+    bool have_rows = false;
+    auto fetch = [&](const hnsw_query_stats *&out) -> int {
+        unsigned char *pin = static_cast<unsigned char *>(lease.s->pin);
+        HIP_TRY(hipMemcpyAsync(pin, d_stats, nq * sizeof(hnsw_query_stats), hipMemcpyDeviceToHost, stream));
+        if (d_mask_of && !have_rows) HIP_TRY(hipMemcpyAsync(pin + st_bytes, d_mask_of, nq * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        have_rows = true;
+        out = st = reinterpret_cast<const hnsw_query_stats *>(pin);
+        mask_of = d_mask_of ? reinterpret_cast<const uint32_t *>(pin + st_bytes) : nullptr;
+        return HNSW_OK;
+    };
+    std::vector<uint8_t> path(nq, 0);
+    uint64_t n2 = 0;
+    rc = rerun_overflowed(
+        v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v), static_cast<uint32_t *>(lease.s->dev), stream, fetch,
+        [&](const std::vector<uint32_t> &sel) -> int {  // path 2, row by row
+            // (a query that names no row of the set ended with HNSW_ERR_ARG, not with an overflow: every row here exists)
+            auto row_of = [&](uint32_t i) { return mask_of ? mask_of[i] : 0u; };
+            std::vector<uint32_t> rows(sel.size()), sel2 = sel;
+            std::stable_sort(sel2.begin(), sel2.end(), [&](uint32_t i, uint32_t j) { return row_of(i) < row_of(j); });
+            for (size_t k = 0; k < sel2.size(); k++) rows[k] = row_of(sel2[k]);
+            for (uint32_t i : sel) path[i] = 2;
+            std::lock_guard<std::mutex> g(set->mu);  // the set's caches: counts, word offsets, valid lists
+            struct Part {
+                size_t lo, hi, wb;
+                uint64_t A;
+                const uint32_t *d_list;
+                bool of_set;
+            };
+            std::vector<Part> parts;
+            std::vector<uint32_t> wb_all, wb;
+            uint64_t A_max = 0;
+            for (size_t lo = 0, hi; lo < sel2.size(); lo = hi) {
+                for (hi = lo + 1; hi < sel2.size() && rows[hi] == rows[lo];) hi++;
+                Part p{lo, hi, wb_all.size(), 0, nullptr, false};
+                if (rows[lo] != HNSW_MASK_NONE && set->W) {
+                    const hnsw_mask_set::Row &r = set->counted(h, rows[lo]);
+                    p.A = r.A;
+                    p.of_set = true;
+                    if (r.list_valid) p.d_list = r.d_ids;
+                    else wb_all.insert(wb_all.end(), r.wbase.begin(), r.wbase.end());
+                } else {
+                    p.A = count_admissible(h, nullptr, rows[lo] == HNSW_MASK_NONE ? len : bits, wb);
+                    wb_all.insert(wb_all.end(), wb.begin(), wb.end());
+                }
+                A_max = std::max(A_max, p.A);
+                parts.push_back(p);
+            }
+            const ExactScratch x(align256(sel2.size() * 4), sel2.size(), n, A_max, wb_all.size());
+            int r = lease.prepare(h->dev.device, x.end, pin_bytes);
+            if (r != HNSW_OK) return r;
+            unsigned char *dv = static_cast<unsigned char *>(lease.s->dev);
+            const uint32_t *d_sel = reinterpret_cast<const uint32_t *>(dv);
+            HIP_TRY(hipMemcpyAsync(dv, sel2.data(), sel2.size() * 4, hipMemcpyHostToDevice, stream));
+            if (!wb_all.empty()) HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, stream));
+            for (const Part &p : parts) {
+                FilterArgs ax = a;
+                ax.mask_of = nullptr;
+                const uint32_t row = rows[p.lo];
+                ax.allow = p.of_set ? a.allow + (size_t)row * set->W : nullptr;
+                ax.allow_bits = row == HNSW_MASK_NONE ? len : bits;
+                if (p.of_set && !p.d_list) h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
+                r = filtered_exact(v, ax, p.hi - p.lo, d_sel + p.lo, p.A, reinterpret_cast<const uint32_t *>(dv + x.o_wb) + p.wb,
+                                   p.hi - p.lo, x, dv, stream, p.d_list);
+                if (r != HNSW_OK) return r;
+            }
+            const hnsw_query_stats *unused;
+            return fetch(unused);  // (synchronises: `sel2` and `wb_all` live until then)
+        },
+        &n2);
+    if (rc != HNSW_OK) return rc;
+    h->n_filt_graph.fetch_add(nq - n2, std::memory_order_relaxed);
+    h->n_filt_overflow.fetch_add(n2, std::memory_order_relaxed);
+    h->n_filt_set_calls.fetch_add(1, std::memory_order_relaxed);
+    if (paths) memcpy(paths, path.data(), nq);
+    for (uint64_t i = 0; i < nq; i++)
+        if (st[i].status == HNSW_ERR_ARG) {
+            set_error("filtered device search: query %llu names mask %u of %u", (unsigned long long)i,
+                      mask_of ? mask_of[i] : 0u, set->n_masks);
+            return HNSW_ERR_ARG;
+        } else if (st[i].status != HNSW_OK) {
+            return query_status_error(i, st[i].status);
+        }
+    return HNSW_OK;
 }
 
 int search_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t *d_ids,

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "handle.h"
+#include "mask_set.h"
 #include "search_filtered.h"
 
 namespace hx {
@@ -79,13 +80,21 @@ int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, u
                 uint32_t *counts, hnsw_query_stats *stats, const uint32_t *entries);
 
 // The allow-lists of a filtered call.  One mask for every query (mask_of == nullptr; masks == nullptr: every id below
-// allow_bits), or n_masks rows of ceil(allow_bits / 64) words and a row (or HNSW_MASK_NONE) per query.
+// allow_bits), or n_masks rows of ceil(allow_bits / 64) words and a row (or HNSW_MASK_NONE) per query.  The rows are
+// the caller's and go up with the call, or they are a resident set's (masks, allow_bits and n_masks are then the
+// set's host words, mask_of is required): nothing is uploaded, the kernels read the set's HBM copy, and the admissible
+// ids of a row come from the set's caches.
 struct MaskSpec {
     const uint64_t *masks = nullptr;
     uint64_t allow_bits = 0;
     uint32_t n_masks = 1;
     const uint32_t *mask_of = nullptr;  // nq entries
+    hnsw_mask_set *set = nullptr;
 };
+
+// The admissible ids of a mask: below bits = min(allow_bits, len), allowed by `allow` (nullptr: all), not deleted.
+// -> A, and the admissible ids before every block of 64 words (the compaction kernel's offsets)
+uint64_t count_admissible(const hnsw_index *h, const uint64_t *allow, uint64_t bits, std::vector<uint32_t> &wbase);
 
 // k-NN among the admissible ids (hnsw_search_batch_filtered's and _multi's contract): the planner runs per referenced
 // mask, the graph path's queries of all masks share one launch and one re-run loop, the exact path runs mask by mask.
@@ -106,6 +115,15 @@ int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t
 // filter_exact_max = -1.
 int search_device_deleted(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t *d_ids,
                           float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, hipStream_t stream, bool finish);
+
+// hnsw_search_batch_filtered_device (finish = false) and _finish: every query by the filtered graph path under its row
+// of a resident set, d_mask_of read on the device (nullptr: row 0); the set is brought up to date on a stream of the
+// handle's own, then ONE launch goes to the caller's stream.  _finish waits, reads the statuses and d_mask_of back,
+// re-runs the queries whose visited table filled up, answers those that fill the largest by the exact path, each under
+// its own row, and returns the first per-query error.  Equals search_filtered under the set with filter_exact_max = -1.
+int search_device_set(hnsw_index *h, hnsw_mask_set *set, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                      const uint32_t *d_mask_of, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                      hnsw_query_stats *d_stats, hipStream_t stream, bool finish, uint8_t *paths);
 
 // hnsw_search_batch_device_finish while nothing is deleted: waits for the stream, reads the per-query statuses,
 // re-runs the queries whose visited table filled up with a table twice the size (same arithmetic, same result as

@@ -313,6 +313,66 @@ class HNSW:
             C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
         return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
 
+    def mask_set(self, masks_or_n_masks, n_points=None):
+        """-> MaskSet: allow-lists resident with this index (include/hnsw_mi355x.h, hnsw_mask_set).  Either what
+        pack_allow_many takes (id arrays give allow_bits = n_points, default len()), or a number of empty rows of
+        n_points bits (default len(); it may exceed len() to leave room for later inserts)."""
+        if isinstance(masks_or_n_masks, (int, np.integer)):
+            n_masks, bits, words = int(masks_or_n_masks), int(self.len() if n_points is None else n_points), None
+        else:
+            words, bits = pack_allow_many(masks_or_n_masks, self.len() if n_points is None else n_points)
+            n_masks = words.shape[0]
+        s = C.c_void_p()
+        check(self._L.hnsw_mask_set_create(self._h, n_masks, bits, None if words is None or bits == 0 else _p(words, _u64p),
+                                           C.byref(s)))
+        return MaskSet(self, s)
+
+    def _mask_of(self, mask_of, nq):
+        if mask_of is None:
+            return None
+        mo = np.asarray(mask_of).reshape(-1).astype(np.int64)
+        if mo.shape[0] != nq:
+            raise ValueError("mask_of must hold one entry per query")
+        if ((mo < -1) | (mo > _lib.MASK_NONE)).any():
+            raise ValueError("mask_of entries are rows of masks, -1 or MASK_NONE")
+        return np.ascontiguousarray(np.where(mo < 0, _lib.MASK_NONE, mo).astype(np.uint32))
+
+    def search_batch_filtered_set(self, Q, n, ef, mask_set, mask_of=None):
+        """search_batch_filtered_multi with the masks of a resident MaskSet (hnsw_search_batch_filtered_set): nothing
+        is packed or uploaded per call.  mask_of [nq]: rows of the set, -1 or MASK_NONE; None: every query under row 0.
+        -> as search_batch_filtered"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        nq = Q.shape[0]
+        mo = self._mask_of(mask_of, nq)
+        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        paths = np.zeros(nq, dtype=np.uint8)
+        check(self._L.hnsw_search_batch_filtered_set(
+            self._h, _p(Q, _f32p), nq, n, ef, mask_set._s, None if mo is None else _p(mo, _u32p), _p(ids, _u32p),
+            _p(dists, _f32p), _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
+        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+
+    def search_batch_filtered_device(self, d_Q, nq, n, ef, mask_set, d_mask_of, d_ids, d_dists, d_counts, d_stats,
+                                     stream=0):
+        """hnsw_search_batch_filtered_device: raw device pointers (ints; d_mask_of 0 / None: row 0), one launch
+        enqueued on `stream`, no sync."""
+        check(self._L.hnsw_search_batch_filtered_device(self._h, d_Q, nq, n, ef, mask_set._s, d_mask_of or None, d_ids,
+                                                        d_dists or None, d_counts or None, d_stats, stream or None))
+
+    def search_batch_filtered_device_finish(self, d_Q, nq, n, ef, mask_set, d_mask_of, d_ids, d_dists, d_counts, d_stats,
+                                            stream=0, paths=False):
+        """Completes search_batch_filtered_device: synchronises, re-runs overflowed queries, answers those that fill
+        the largest table by the exact path, raises the first per-query error.  paths=True -> uint8 [nq] (0 / 2)"""
+        out = np.zeros(nq, dtype=np.uint8) if paths else None
+        check(self._L.hnsw_search_batch_filtered_device_finish(
+            self._h, d_Q, nq, n, ef, mask_set._s, d_mask_of or None, d_ids, d_dists or None, d_counts or None, d_stats,
+            stream or None, None if out is None else _p(out, _u8p)))
+        return out
+
     def ann_by_vector_filtered(self, vector, n, ef, allow):
         """ann_by_vector restricted to the allowed ids -> list of ids"""
         q = np.ascontiguousarray(vector, dtype=np.float32).reshape(1, -1)
@@ -560,6 +620,62 @@ class HNSW:
         if rank != src:
             check(L.hnsw_snapshot_commit(out._h))
         return out
+
+
+class MaskSet:
+    """hnsw_mask_set: n_masks allow-lists of allow_bits bits that live with an index (HNSW.mask_set makes one).  Managing
+    it needs no GPU; the next search that names it brings its HBM copy up to date.  Keeps its index alive; close() (or
+    garbage collection) frees it."""
+
+    def __init__(self, index, handle):
+        self._index = index
+        self._L = index._L
+        self._s = handle
+        n, b = C.c_uint32(), C.c_uint64()
+        check(self._L.hnsw_mask_set_info(self._s, C.byref(n), C.byref(b)))
+        self.n_masks, self.allow_bits = n.value, b.value
+        self._W = (self.allow_bits + 63) // 64
+
+    def close(self):
+        if getattr(self, "_s", None):
+            self._L.hnsw_mask_set_free(self._s)
+            self._s = None
+            self._index = None
+
+    __del__ = close
+
+    def write(self, row, allow):
+        """replaces a row: a bool array of allow_bits entries, an array of allowed ids, or W packed uint64 words"""
+        a = np.asarray(allow)
+        if a.dtype == np.uint64:
+            words = np.ascontiguousarray(a.reshape(-1))
+        else:
+            words, bits = pack_allow(a, self.allow_bits)
+            if bits != self.allow_bits:
+                raise ValueError("a bool row has allow_bits = %d entries, got %d" % (self.allow_bits, bits))
+        if words.shape[0] < self._W:
+            raise ValueError("a row has %d words, got %d" % (self._W, words.shape[0]))
+        check(self._L.hnsw_mask_set_write(self._s, int(row), _p(words, _u64p)))
+
+    def update(self, row, ids, allow=True):
+        """sets (allow) or clears the bits of `ids` in one row; an id >= allow_bits changes nothing and raises"""
+        a = np.asarray(ids).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() > _lib.UINT32_MAX):
+            raise HnswError(_lib.ERR_ARG, "ids must be in [0, 2^32)")
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        check(self._L.hnsw_mask_set_update(self._s, int(row), _p(a, _u32p), a.shape[0], 1 if allow else 0))
+
+    def read(self, row):
+        """-> the row's W words (uint64)"""
+        words = np.zeros(max(self._W, 1), dtype=np.uint64)
+        check(self._L.hnsw_mask_set_read(self._s, int(row), _p(words, _u64p)))
+        return words[: self._W]
+
+    def count(self, row):
+        """-> the row's set bits (below allow_bits; deleted ids are not taken out)"""
+        c = C.c_uint64()
+        check(self._L.hnsw_mask_set_count(self._s, int(row), C.byref(c)))
+        return c.value
 
 
 def pack_allow(allow, n_points=None):

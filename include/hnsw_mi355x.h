@@ -188,8 +188,8 @@ int hnsw_search_batch(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, ui
  * A == 0 gives count 0 for every query.  The cosine option applies to the queries first.  Per-query errors
  * (HNSW_ERR_NAN_INPUT) as hnsw_search_batch.  The handle's deleted ids (hnsw_mark_deleted) are never allowed: the
  * effective mask is allow AND NOT deleted, and the result equals the same call with that mask on a handle with
- * nothing deleted.  Not provided: masks resident in HBM across calls, a device-pointer form of a filtered call,
- * coalescing of one-query filtered calls, filtered sharded search and the Rust shim's binding. */
+ * nothing deleted.  Masks resident in HBM across calls and a device-pointer form are hnsw_mask_set's, below.  Not
+ * provided: coalescing of one-query filtered calls, filtered sharded search and the Rust shim's binding. */
 int hnsw_search_batch_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
                                const uint64_t *allow, uint64_t allow_bits, uint32_t *ids, float *dists,
                                uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths /* 0/1/2 or NULL */);
@@ -217,7 +217,75 @@ int hnsw_search_batch_filtered_multi(hnsw_index *h, const float *Q, uint64_t nq,
                                      const uint64_t *masks, uint32_t n_masks, uint64_t allow_bits,
                                      const uint32_t *mask_of /* nq */, uint32_t *ids, float *dists, uint32_t *counts,
                                      hnsw_query_stats *stats, uint8_t *paths /* 0/1/2 or NULL */);
-/* Same with every buffer already resident in HBM on the handle's device; enqueues on `stream`
+
+/* ---- resident mask sets ------------------------------------------------------------------------------------------
+ * Allow-lists that live with the index: n_masks rows of W = ceil(allow_bits / 64) words in the layout above, created
+ * once, updated in place, named by searches and read in HBM -- the filter-side counterpart of hnsw_mark_deleted's
+ * resident deny mask.  allow_bits is fixed at creation and may exceed hnsw_len (room for the ids of later inserts); an
+ * id is admissible iff it is below min(allow_bits, hnsw_len), its bit is set and it is not deleted.  Bits of a row's
+ * last word beyond allow_bits are ignored on input and read back as 0.
+ *   create   masks: n_masks x W words, or NULL: every row clear
+ *   write    replaces a whole row by words[W]
+ *   update   sets (allow != 0) or clears the bits of ids[k] in one row; idempotent; an id >= allow_bits or a row >=
+ *            n_masks is HNSW_ERR_ARG and the set stays as it was
+ *   read     the row's words[W];   count: its set bits (below allow_bits);   info: n_masks and allow_bits
+ * None of these needs a GPU: they work on a host mirror and note the words they changed.  The next search that names
+ * the set brings the HBM copy up to date on the snapshot's device, by the deleted set's mechanism: the changed words
+ * travel as (index, value) pairs and are scattered by one small kernel, or the whole set is copied when there is no
+ * HBM copy yet, the device changed or more than an eighth of its words changed ("mask_set_words_uploaded").
+ * A set belongs to the handle that created it (any other handle passed with it: HNSW_ERR_ARG); hnsw_clone, hnsw_save
+ * and snapshot replication do not carry it; it must not be used after hnsw_free and is freed by its creator.  A
+ * device-only replica may create sets (its length is the header's).  Concurrent searches that name one set are safe;
+ * write and update must not run concurrently with a search on that set.
+ * The set also keeps, per row, what a filtered call otherwise works out every time, valid while the row, the
+ * handle's deleted set and hnsw_len are unchanged: the row's admissible count and word offsets (counted on the host
+ * when a search first names the row: "mask_set_recounts"), and, for a row planned on the exact path, its compacted
+ * ascending id list in HBM -- while that is valid a call launches the scan and the merge for the row and NO
+ * compaction ("mask_set_compactions" counts the compactions that do run).  The lists of a set are bounded by the
+ * option "mask_set_cache_mb"; when that is used up further rows are compacted per call as without a set, and nothing
+ * is evicted. */
+typedef struct hnsw_mask_set hnsw_mask_set;
+int hnsw_mask_set_create(hnsw_index *h, uint32_t n_masks, uint64_t allow_bits,
+                         const uint64_t *masks /* n_masks x W, or NULL: all clear */, hnsw_mask_set **out);
+void hnsw_mask_set_free(hnsw_mask_set *s);
+int hnsw_mask_set_info(const hnsw_mask_set *s, uint32_t *n_masks, uint64_t *allow_bits);
+int hnsw_mask_set_write(hnsw_mask_set *s, uint32_t row, const uint64_t *words /* W */);
+int hnsw_mask_set_update(hnsw_mask_set *s, uint32_t row, const uint32_t *ids, uint64_t k, int allow);
+int hnsw_mask_set_read(const hnsw_mask_set *s, uint32_t row, uint64_t *words /* W */);
+int hnsw_mask_set_count(const hnsw_mask_set *s, uint32_t row, uint64_t *allowed /* set bits below allow_bits */);
+/* hnsw_search_batch_filtered_multi with the masks taken from a set: query i's ids, distance bits, count, stats (status
+ * included) and path are exactly what that call returns for the same Q, n, ef and mask_of on the same handle with the
+ * same options, its masks being the set's current rows (as hnsw_mask_set_read gives them) and its allow_bits the
+ * set's -- HNSW_MASK_NONE, the per-mask planner, "filter_exact_max", ef' > 256, deleted ids, the cosine option and
+ * per-query errors included.  mask_of == NULL: every query under row 0.  No mask is uploaded and no row the set has
+ * counted is counted again; an exact-path row with a valid list is not compacted.  Argument errors as there, decided
+ * before the device is touched, and HNSW_ERR_ARG for a NULL set or a set of another handle.  The three "filtered_*"
+ * path counters advance as there, and "filtered_set_calls" by one. */
+int hnsw_search_batch_filtered_set(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                   hnsw_mask_set *set, const uint32_t *mask_of /* nq; NULL: every query row 0 */,
+                                   uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
+                                   uint8_t *paths /* 0/1/2 or NULL */);
+/* The same with every buffer in HBM on the handle's device (d_mask_of too; NULL: row 0).  The set is brought up to
+ * date on a stream of the handle's own, so `stream` is not synchronised; then ONE launch of the filtered graph kernel
+ * for all queries is enqueued on `stream` and the call returns.  Every query takes the graph path: n <= 64 and
+ * ef' <= 256, else HNSW_ERR_ARG.  d_stats is required; d_dists / d_counts may be NULL.  The host never sees d_mask_of
+ * before the launch, so the kernel checks it: a query whose entry is neither < n_masks nor HNSW_MASK_NONE gets status
+ * HNSW_ERR_ARG, count 0 and padded outputs without a mask word being read; every other query is answered as usual.
+ * _finish (same arguments, and paths: host, nq, or NULL) waits for `stream`, reads the statuses and d_mask_of back,
+ * re-runs the queries whose visited table filled up with larger tables, answers those that fill the largest by the
+ * exact path under their own rows (path 2, with the set's caches) and returns the first per-query error.  After it the
+ * buffers hold what hnsw_search_batch_filtered_set returns with "filter_exact_max" = -1 (paths 0 or 2); the counters
+ * advance at _finish. */
+int hnsw_search_batch_filtered_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                      hnsw_mask_set *set, const uint32_t *d_mask_of /* device, nq; NULL: row 0 */,
+                                      uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                                      hnsw_query_stats *d_stats, void *stream);
+int hnsw_search_batch_filtered_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                             hnsw_mask_set *set, const uint32_t *d_mask_of, uint32_t *d_ids,
+                                             float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
+                                             void *stream, uint8_t *paths /* host, nq, or NULL */);
+
+/* hnsw_search_batch with every buffer already resident in HBM on the handle's device; enqueues on `stream`
  * (a hipStream_t, NULL = default stream) and returns without synchronising.  d_stats is
  * required (its status field carries per-query errors); d_dists / d_counts may be NULL. */
 int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
@@ -358,7 +426,10 @@ int hnsw_device_bytes(const hnsw_index *h, uint64_t *bytes);
  *   "coalesce_us", "coalesce_depth", "coalesce_max"
  *                      the gathering of concurrent hnsw_search calls into one launch, see hnsw_search
  *   "filter_exact_max" hnsw_search_batch_filtered answers a call by the exact scan when its mask allows at most
- *                      this many ids (default 65536, from the crossover measured in DESIGN.md section 12; < 0: never) */
+ *                      this many ids (default 65536, from the crossover measured in DESIGN.md section 12; < 0: never)
+ *   "mask_set_cache_mb" HBM a resident mask set may hold in compacted id lists of its exact-path rows (per set,
+ *                      default 64 -- a design choice, not a measurement; at the default "filter_exact_max" a list is
+ *                      at most 256 KiB; 0: no list is kept) */
 int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
 /* counters of the handle: "uploads" (whole-snapshot uploads), "point_patches" (insert_vec calls that patched the
  * live snapshot), "patch_fallbacks" (those that could not: the next search uploads), "coalesced_batches" /
@@ -378,7 +449,11 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * node's last edge -- the drop kernel's refusals plus the seed's clamp restores -- mirrored after the build; in the
  * sharded build every rank reports the whole build's, like "build_points"); hnsw_search_batch_filtered's (and
  * _multi's) queries by path: "filtered_queries_graph" (0), "filtered_queries_exact" (1), "filtered_overflow_exact" (2);
- * hnsw_search_batch_filtered_multi's calls and named masks: "filtered_multi_calls", "filtered_multi_masks"; deletion:
+ * hnsw_search_batch_filtered_multi's calls and named masks: "filtered_multi_calls", "filtered_multi_masks"; resident
+ * mask sets of the handle, summed: "mask_set_words_uploaded" (words of any set copied to HBM, by whole copies and by
+ * scatters), "mask_set_recounts" (rows whose admissible ids the host counted), "mask_set_compactions" (compactions
+ * launched for rows of a set), "filtered_set_calls" (hnsw_search_batch_filtered_set calls and completed
+ * hnsw_search_batch_filtered_device calls); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
