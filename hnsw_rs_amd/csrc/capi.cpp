@@ -198,6 +198,7 @@ int hnsw_clone(const hnsw_index *h, hnsw_index **out) {
     c->co.cap = h->co.cap;
     c->filter_exact_max = h->filter_exact_max;
     c->del.assign_host(h->del.words);
+    c->lab.assign_host(h->lab.labels);
     *out = c;
     return HNSW_OK;
 }
@@ -432,6 +433,52 @@ int hnsw_search_batch_filtered_device_finish(hnsw_index *h, const float *d_Q, ui
                                              float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream,
                                              uint8_t *paths) {
     return filtered_device(h, d_Q, nq, n, ef, set, d_mask_of, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
+}
+
+// ---- searches under a label range (labels.h) -----------------------------------------------------------------
+int hnsw_search_batch_filtered_range(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                     const uint32_t *lo, const uint32_t *hi, uint32_t *ids, float *dists,
+                                     uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK) return rc;
+    if (nq == 0) return HNSW_OK;
+    if (!lo || !hi) {
+        set_error("filtered search: needs the label range (lo and hi) of every query");
+        return HNSW_ERR_ARG;
+    }
+    hx::MaskSpec m{nullptr, index_len(h)};
+    m.lo = lo;
+    m.hi = hi;
+    const hx::PathCounters ctr = hx::filt_counters(h);
+    return hx::search_filtered_checked(h, Q, nq, n, ef, m, false, ids, dists, counts, stats, paths, &ctr);
+}
+
+static int range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, const uint32_t *d_lo,
+                        const uint32_t *d_hi, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                        hnsw_query_stats *d_stats, void *stream, bool finish, uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK) return rc;
+    if (nq == 0 || n == 0) return HNSW_OK;
+    if (!d_Q || !d_ids || !d_stats || !d_lo || !d_hi || nq > 0x7FFFFFFFull) {
+        set_error("filtered device search: needs queries, their label ranges, an id buffer and a stats buffer in HBM");
+        return HNSW_ERR_ARG;
+    }
+    return hx::search_device_range(h, d_Q, nq, n, ef, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats,
+                                   static_cast<hipStream_t>(stream), finish, paths);
+}
+
+int hnsw_search_batch_filtered_range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                            const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
+                                            float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
+                                            void *stream) {
+    return range_device(h, d_Q, nq, n, ef, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, false, nullptr);
+}
+
+int hnsw_search_batch_filtered_range_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n,
+                                                   uint32_t ef, const uint32_t *d_lo, const uint32_t *d_hi,
+                                                   uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                                                   hnsw_query_stats *d_stats, void *stream, uint8_t *paths) {
+    return range_device(h, d_Q, nq, n, ef, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
 }
 
 int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
@@ -862,6 +909,41 @@ int hnsw_get_deleted(const hnsw_index *h, uint32_t *ids, uint64_t cap, uint64_t 
     return HNSW_OK;
 }
 
+// ---- labels -------------------------------------------------------------------------------------------------
+int hnsw_set_labels(hnsw_index *h, const uint32_t *ids, const uint32_t *labels, uint64_t k) {
+    if (!h || (k && !labels)) return HNSW_ERR_ARG;
+    const uint64_t len = index_len(h);
+    if (!ids && k > len) {
+        set_error("%llu labels for the ids 0..k-1 of an index of %llu points", (unsigned long long)k, (unsigned long long)len);
+        return HNSW_ERR_ARG;
+    }
+    for (uint64_t i = 0; ids && i < k; i++)  // every id checked before anything changes
+        if (ids[i] >= len) {
+            set_error("id %u is not a point of the index (len %llu)", ids[i], (unsigned long long)len);
+            return HNSW_ERR_ARG;
+        }
+    std::lock_guard<std::mutex> g(h->mu);
+    std::lock_guard<std::mutex> lg(h->lab.mu);
+    h->lab.set(ids, labels, k, len);
+    return HNSW_OK;
+}
+int hnsw_get_labels(const hnsw_index *h, const uint32_t *ids, uint64_t k, uint32_t *out) {
+    if (!h || (k && !out)) return HNSW_ERR_ARG;
+    const uint64_t len = index_len(h);
+    if (!ids && k > len) {
+        set_error("%llu labels asked of an index of %llu points", (unsigned long long)k, (unsigned long long)len);
+        return HNSW_ERR_ARG;
+    }
+    for (uint64_t i = 0; ids && i < k; i++)
+        if (ids[i] >= len) {
+            set_error("id %u is not a point of the index (len %llu)", ids[i], (unsigned long long)len);
+            return HNSW_ERR_ARG;
+        }
+    std::lock_guard<std::mutex> lg(h->lab.mu);  // (a range search may be growing the mirror to the index length)
+    for (uint64_t i = 0; i < k; i++) out[i] = h->lab.get(ids ? ids[i] : i);
+    return HNSW_OK;
+}
+
 // ---- persistence -----------------------------------------------------------------------------------
 int hnsw_save(const hnsw_index *h, const char *dir) {
     if (!h || !dir) return HNSW_ERR_ARG;
@@ -872,7 +954,8 @@ int hnsw_save(const hnsw_index *h, const char *dir) {
     }
     int rc = hx::save_index(*h->host, dir);
     if (rc != HNSW_OK) return rc;
-    return hx::save_deleted(dir, h->del.ids());
+    if ((rc = hx::save_deleted(dir, h->del.ids()))) return rc;
+    return hx::save_labels(dir, h->lab.labels);
 }
 int hnsw_load(const char *dir, hnsw_index **out) {
     if (!dir || !out) return HNSW_ERR_ARG;
@@ -881,10 +964,13 @@ int hnsw_load(const char *dir, hnsw_index **out) {
     if (rc != HNSW_OK) return rc;
     std::vector<uint64_t> deleted;
     if ((rc = hx::load_deleted(dir, idx->len(), &deleted))) return rc;
+    std::vector<uint32_t> labels;
+    if ((rc = hx::load_labels(dir, idx->len(), &labels))) return rc;
     hnsw_index *h = new (std::nothrow) hnsw_index();
     if (!h) return HNSW_ERR_OOM;
     h->host = std::move(idx);
     h->del.assign_host(deleted);
+    h->lab.assign_host(labels);
     *out = h;
     return HNSW_OK;
 }
@@ -904,6 +990,7 @@ int hnsw_set_device(hnsw_index *h, int device) {
     if (device != h->device) {
         h->dev.release();
         h->del.release_device();  // (the host set stays; the next search copies it to the new device)
+        h->lab.release_device();  // (and so the label column)
         // a leaderless batch the coalescer keeps open was made ready for the old device (stream, device arena): retire
         // it; the next caller opens one on the new device (no search may be in flight during this call)
         hx::Coalescer &co = h->co;
@@ -1021,6 +1108,12 @@ int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
         *out = h->n_filt_exact.load();
     } else if (!strcmp(key, "filtered_overflow_exact")) {
         *out = h->n_filt_overflow.load();
+    } else if (!strcmp(key, "label_words_uploaded")) {
+        *out = h->lab.words_uploaded;
+    } else if (!strcmp(key, "filtered_range_calls")) {
+        *out = h->n_filt_range_calls.load();
+    } else if (!strcmp(key, "filtered_range_ranges")) {
+        *out = h->n_filt_range_ranges.load();
     } else if (!strcmp(key, "filtered_multi_calls")) {
         *out = h->n_filt_multi_calls.load();
     } else if (!strcmp(key, "filtered_multi_masks")) {

@@ -15,6 +15,7 @@
 #include "device_index.h"
 #include "hip_util.h"
 #include "host_index.h"
+#include "labels.h"
 #include "scratch.h"
 
 struct hnsw_index {
@@ -56,6 +57,10 @@ struct hnsw_index {
     // set's compacted lists in HBM (option "mask_set_cache_mb")
     std::atomic<uint64_t> n_set_words_uploaded{0}, n_set_recounts{0}, n_set_compactions{0}, n_filt_set_calls{0};
     int64_t mask_set_cache_mb = 64;
+    // the label column (hnsw_set_labels, labels.h), on the host and in HBM, and hnsw_search_batch_filtered_range's
+    // calls (host calls and completed device calls) and the distinct ranges they named
+    hx::LabelColumn lab;
+    std::atomic<uint64_t> n_filt_range_calls{0}, n_filt_range_ranges{0};
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")
 };
 

@@ -365,4 +365,47 @@ int load_deleted(const std::string &dir, uint64_t n_points, std::vector<uint64_t
     return HNSW_OK;
 }
 
+int save_labels(const std::string &dir, const std::vector<uint32_t> &labels) {
+    const std::string path = dir + "/labels";
+    uint64_t count = labels.size();
+    while (count > 0 && labels[count - 1] == 0) count--;  // trailing zero labels are what an absent label is
+    if (count == 0) {  // every label zero: exactly the files of an index without labels, no stale sidecar
+        if (unlink(path.c_str()) != 0 && errno != ENOENT) {
+            set_error("Could not remove %s", path.c_str());
+            return HNSW_ERR_IO;
+        }
+        return HNSW_OK;
+    }
+    std::vector<uint8_t> b;
+    b.reserve(8 + count * 4);
+    put_u64(b, count);
+    for (uint64_t i = 0; i < count; i++) put_u32(b, labels[i]);
+    if (!write_file(path, b)) {
+        set_error("Could not write bytes to the labels file");
+        return HNSW_ERR_IO;
+    }
+    return HNSW_OK;
+}
+
+int load_labels(const std::string &dir, uint64_t n_points, std::vector<uint32_t> *labels) {
+    labels->clear();
+    const std::string path = dir + "/labels";
+    struct stat st;
+    if (stat(path.c_str(), &st) != 0) return HNSW_OK;  // no file: every label 0
+    std::vector<uint8_t> b;
+    if (!read_file(path, &b) || b.size() < 8) {
+        set_error("Problem reading the labels file");
+        return HNSW_ERR_IO;
+    }
+    const uint64_t count = get_u64(&b[0]);
+    if (count > n_points || b.size() != 8 + count * 4) {
+        set_error("labels file: %llu labels in %zu bytes (index length %llu)", (unsigned long long)count, b.size(),
+                  (unsigned long long)n_points);
+        return HNSW_ERR_IO;
+    }
+    labels->resize(count);
+    for (uint64_t i = 0; i < count; i++) (*labels)[i] = get_u32(&b[8 + 4 * i]);
+    return HNSW_OK;
+}
+
 }  // namespace hx

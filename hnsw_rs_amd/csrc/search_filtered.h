@@ -10,6 +10,14 @@
 // names a row beyond it with status HNSW_ERR_ARG before it reads a mask word.  Only the graph kernel reads mask_of: the
 // exact path's kernels are launched per mask with allow at that mask's row.  The handle's deleted set (hnsw_mark_deleted) is a second mask of the same
 // layout, deny: an id is admissible iff it is allowed and not denied.
+//
+// A label range (hnsw_search_batch_filtered_range) is a third filter, in place of the allow-list: labels is the handle's
+// resident label column (labels.h), one uint32 per id, and id i is allowed iff i < allow_bits and lo <= label(i) <= hi,
+// where label(i) is labels[i] for i < label_len and 0 beyond it (the host keeps label_len at or above the index length,
+// with zeros beyond the labels that were set: the graph kernel has one bound for the id and for the label read).  The
+// graph kernel's wave takes its query's range from range_lo[q] / range_hi[q] (they may be the caller's device memory);
+// the exact path's kernels are launched per range with the scalars lo and hi.  lo > hi is an empty range: nothing is allowed and no label is read.  A call
+// has a column or masks, not both (allow and mask_of are nullptr with a column).
 #pragma once
 
 #include "device_index.h"
@@ -18,6 +26,7 @@ namespace hx {
 
 #define HX_FILT_MAX_EF 256  // ef' on the graph path: F and R are four registers per lane at most
 #define HX_FILT_MAX_N 64    // results per query (both paths)
+#define HX_FILT_RANGE_LDS 16  // bytes of LDS a wave under a label range keeps its range in
 #define HX_FILT_MAX_SLOTS_LOG2 15  // the largest visited table: 32768 slots, at most 24576 ids (75 %)
 
 struct FilterArgs {
@@ -32,6 +41,11 @@ struct FilterArgs {
     uint64_t deny_bits;        // ids the deny mask covers (a multiple of 64); ids beyond it are not denied
     uint32_t n, ef;            // results per query, ef' = max(ef, n, 1)
     uint32_t n_masks;          // rows of allow (read with mask_of only): a mask_of entry is below it or HNSW_MASK_NONE
+    const uint32_t *labels;    // the label column (device), or nullptr: the call has no label range
+    uint64_t label_len;        // labels the column holds; an id at or beyond it has label 0
+    const uint32_t *range_lo;  // with labels, the graph kernel (device): query q is under [range_lo[q], range_hi[q]] ...
+    const uint32_t *range_hi;
+    uint32_t lo, hi;           // ... and the compaction of an exact-path launch under [lo, hi]
     uint32_t *out_ids;         // nq x n
     float *out_dists;          // nq x n
     uint32_t *out_counts;      // nq
@@ -41,16 +55,18 @@ struct FilterArgs {
 // ids a layer-0 visited table of 2^slots_log2 slots holds before the graph path reports HNSW_ERR_OVERFLOW
 __host__ __device__ inline uint32_t filt_visited_limit(uint32_t slots_log2) { return (1u << slots_log2) - (1u << (slots_log2 - 2)); }
 // first table size for ef' (the generic kernel's choice) and the largest one the dimension leaves room for in LDS
-uint32_t filt_first_slots_log2(const DevView &v, uint32_t ef);
-uint32_t filt_max_slots_log2(const DevView &v);
+// (ranged: a call under a label range, whose waves keep HX_FILT_RANGE_LDS bytes more)
+uint32_t filt_first_slots_log2(const DevView &v, uint32_t ef, bool ranged = false);
+uint32_t filt_max_slots_log2(const DevView &v, bool ranged = false);
 
 // graph path: `nblocks` queries (a.qsel selects them when set); a query whose visited table fills up ends with
 // status HNSW_ERR_OVERFLOW and is run again by the caller with a larger table or answered by the exact path
 int launch_filtered_graph(const DevView &v, const FilterArgs &a, uint32_t nblocks, uint32_t slots_log2,
                           hipStream_t stream);
 // exact path, step 1: the ascending list of admissible ids (a.allow, a.allow_bits, a.deny, a.deny_bits) in the
-// n_words words below allow_bits.  word_base[b] = admissible ids in words [0, 64 b) (computed by the caller, who
-// counts A anyway); ids[A]
+// n_words words below allow_bits; with a.labels, "allowed" is the range [a.lo, a.hi] over the column and the kernel
+// makes the words itself.  word_base[b] = admissible ids in words [0, 64 b) (computed by the caller, who counts A
+// anyway); ids[A]
 int launch_filter_compact(const FilterArgs &a, uint64_t n_words, const uint32_t *word_base, uint32_t *ids,
                           hipStream_t stream);
 // exact path, step 2: top-n of the `nsel` queries (a.qsel, or the first nsel) over the A listed ids; part holds

@@ -13,7 +13,12 @@
 // loop ("Filtered search").  One row per pass, read from the compact layout (adj0 + rows), so
 // the inline-rows copy does not matter.
 //
-// Exact path: hx_filt_compact_kernel lists the allowed, undeleted ids in ascending order; hx_filt_scan_kernel scans
+// With a label range instead of an allow-list (FilterArgs::labels) the allow test of a key is lo <= label(id) <= hi
+// over the resident column, lo and hi the wave's own (picked once, as its mask pointer, and kept in LDS), one 4-byte
+// read per key that got as far as a mask word is read otherwise.
+//
+// Exact path: hx_filt_compact_kernel lists the allowed, undeleted ids in ascending order (the allowed bits of a word
+// read from the mask, or, under a label range, made from 64 coalesced reads of the column); hx_filt_scan_kernel scans
 // one segment of that list per block and keeps its n best (the shape of hx_brute_kernel),
 // hx_filt_merge_kernel merges a query's segments.
 //
@@ -155,12 +160,24 @@ __device__ __forceinline__ bool filt_visit(uint32_t *tab, uint32_t slots_log2, u
     }
 }
 
-// admissible: allowed (below the query's bound, and its bit set when the query has a mask) and not deleted.  The two
-// pointer tests are uniform over the wave (a kernel argument, and the wave's own mask: one query per wave); a mask
-// word is read only for an id that got that far.
-__device__ __forceinline__ bool filt_allowed(const FilterArgs &a, const uint64_t *allow, uint64_t bound, uint32_t id) {
+// admissible: allowed (below the query's bound, its label in the query's range when the call has a label column, and
+// its bit set when the query has a mask) and not deleted.  The pointer tests are uniform over the wave (a kernel
+// argument, and the wave's own filter: one query per wave); a label or a mask word is read only for an id that got
+// that far.  `filt` is the wave's one filter pointer: its mask row, or, with bit 0 set, the label column -- a call has
+// masks or a column, and the kernel has no scalar register to spare for a second pointer or for the range, which the
+// wave keeps in LDS (`range`: lo, hi - lo) and reads next to the label.  (Measured: the range in two more scalar
+// registers costs the f32 100d and 128d kernels with one list register 6 and 2 vector registers, and the 128d one a wave of
+// occupancy)  The bound of an empty range is 0: no label is read under it.
+__device__ __forceinline__ bool filt_allowed(const FilterArgs &a, const uint64_t *filt, uint64_t bound,
+                                             const uint32_t *range, uint32_t id) {
     if ((uint64_t)id >= bound) return false;
-    if (allow && ((allow[id >> 6] >> (id & 63)) & 1ull) == 0) return false;
+    if ((uintptr_t)filt & 1) {
+        const uint2 r = *reinterpret_cast<const uint2 *>(range);
+        const uint32_t label = reinterpret_cast<const uint32_t *>((uintptr_t)filt - 1)[id];
+        if (label - r.x > r.y) return false;  // lo <= label <= hi in one unsigned compare
+    } else if (filt && ((filt[id >> 6] >> (id & 63)) & 1ull) == 0) {
+        return false;
+    }
     return !(a.deny && (uint64_t)id < a.deny_bits && ((a.deny[id >> 6] >> (id & 63)) & 1ull) != 0);
 }
 
@@ -276,7 +293,8 @@ __host__ __device__ inline uint32_t yq_bytes_of(const DevView &v) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Graph path.  LDS: visited table (4 << slots_log2 bytes) | merge buffer (64 R keys) | query.
+// Graph path.  LDS: visited table (4 << slots_log2 bytes) | merge buffer (64 R keys) | query | under a label range,
+// the wave's range (HX_FILT_RANGE_LDS bytes).
 // ---------------------------------------------------------------------------------------------
 template <int KIND, int P, int DS, int R>
 __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, const FilterArgs a, const uint32_t slots_log2) {
@@ -289,11 +307,25 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
     // own error, decided for the whole wave before a mask word is read: no walk (the status below), padded outputs,
     // and an id bound of 0, under which filt_allowed refuses every id before it touches the row pointer
     const bool bad_row = a.mask_of && g != HNSW_MASK_NONE && g >= a.n_masks;
-    const uint64_t *allow = g == HNSW_MASK_NONE ? nullptr : a.allow + (size_t)g * a.mask_words;
-    const uint64_t bound = bad_row ? 0 : g == HNSW_MASK_NONE ? a.none_bits : a.allow_bits;
+    const uint64_t *allow = a.labels              ? reinterpret_cast<const uint64_t *>((uintptr_t)a.labels | 1)
+                            : g == HNSW_MASK_NONE ? nullptr
+                                                  : a.allow + (size_t)g * a.mask_words;
+    // the wave's label range, picked once as well; an empty one (lo > hi) allows nothing: an id bound of 0.  Under a
+    // column the bound is also the bound of the label read: the host keeps the HBM copy at least as long as the index
+    // (zeros beyond the labels that were set), so label_len never is the smaller one
+    const uint32_t lo = a.labels ? a.range_lo[q] : 0u, hi = a.labels ? a.range_hi[q] : 0u;
+    const uint64_t bound = bad_row || lo > hi      ? 0
+                           : a.labels              ? min(a.allow_bits, a.label_len)
+                           : g == HNSW_MASK_NONE ? a.none_bits
+                                                   : a.allow_bits;
     uint32_t *htab = reinterpret_cast<uint32_t *>(smem);
     u64 *perm = reinterpret_cast<u64 *>(smem + (4ull << slots_log2));
     float *yq = reinterpret_cast<float *>(perm + 64 * R);
+    uint32_t *range = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(yq) + yq_bytes_of(v));
+    if (a.labels && lane == 0) {  // (read after the wave_fence of the first clear_visited)
+        range[0] = lo;
+        range[1] = hi - lo;
+    }
     const uint32_t vis_limit = filt_visited_limit(slots_log2);
 
     constexpr int LPC = (KIND == HNSW_VEC_QUANT8) ? 2 : 1;  // lanes per candidate
@@ -408,7 +440,7 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
             wave_fence();
             n_vis = 1;
             F.merge(lane == 0 ? best : FKEY_INVALID, ef, perm, lane);
-            Rl.merge(lane == 0 && filt_allowed(a, allow, bound, (uint32_t)best) ? best : FKEY_INVALID, ef, perm, lane);
+            Rl.merge(lane == 0 && filt_allowed(a, allow, bound, range, (uint32_t)best) ? best : FKEY_INVALID, ef, perm, lane);
         }
         while (status == HNSW_OK && F.n_cur > 0) {
             const u64 c = F.front();
@@ -417,7 +449,7 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
             expand((uint32_t)c, 0, [&](u64 key) {
                 // admitted against the bound at the start of the pass; R takes the allowed ones
                 const bool adm = key != FKEY_INVALID && (!Rl.full(ef) || key < Rl.last);
-                const bool alw = adm && filt_allowed(a, allow, bound, (uint32_t)key);
+                const bool alw = adm && filt_allowed(a, allow, bound, range, (uint32_t)key);
                 F.merge(adm ? key : FKEY_INVALID, ef, perm, lane);
                 Rl.merge(alw ? key : FKEY_INVALID, ef, perm, lane);
             });
@@ -445,13 +477,31 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
 
 // ---------------------------------------------------------------------------------------------
 // Exact path.  Compaction: one wave per 64 mask words; lane l owns word 64 b + l and writes its admissible ids at
-// word_base[b] + (admissible ids of the wave's lower lanes).
+// word_base[b] + (admissible ids of the wave's lower lanes).  Under a label range there is no mask word to read: the
+// wave makes its 64 words together, word 64 b + j from the 64 consecutive labels of its ids -- one coalesced 256-byte
+// read by the 64 lanes, the range test balloted, the ballot kept by lane j.  (A lane that read the 64 labels of its
+// own word would touch 64 lines per wave instruction: the gather shape of DESIGN.md section 10.)
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) hx_filt_compact_kernel(const FilterArgs a, uint64_t n_words,
                                                              const uint32_t *word_base, uint32_t *ids) {
     const int lane = threadIdx.x;
     const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
-    u64 bits = w < n_words ? (a.allow ? a.allow[w] : ~0ull) : 0;
+    u64 bits = 0;
+    if (a.labels) {
+        if (a.lo <= a.hi) {  // (an empty range reads no label)
+            const uint64_t id0 = (uint64_t)blockIdx.x * 4096 + lane;
+#pragma unroll 8
+            for (int j = 0; j < 64; j++) {
+                const uint64_t id = id0 + 64 * j;
+                const uint32_t label = id < a.label_len ? a.labels[id] : 0u;
+                const u64 in = __ballot(label >= a.lo && label <= a.hi);
+                if (lane == j) bits = in;
+            }
+        }
+        if (w >= n_words) bits = 0;
+    } else {
+        bits = w < n_words ? (a.allow ? a.allow[w] : ~0ull) : 0;
+    }
     if (w * 64 + 64 > a.allow_bits) {  // ids at and beyond allow_bits are not allowed
         const uint64_t keep = a.allow_bits > w * 64 ? a.allow_bits - w * 64 : 0;
         bits &= keep >= 64 ? ~0ull : ((1ull << keep) - 1);
@@ -544,7 +594,7 @@ __global__ void __launch_bounds__(64) hx_filt_merge_kernel(const FilterArgs a, u
 template <int KIND, int P, int DS, int R>
 int launch_graph_r(const DevView &v, const FilterArgs &a, uint32_t nblocks, uint32_t slots_log2, hipStream_t stream) {
     auto kern = hx_filt_graph_kernel<KIND, P, DS, R>;
-    const size_t lds = (4ull << slots_log2) + 64ull * R * 8 + yq_bytes_of(v);
+    const size_t lds = (4ull << slots_log2) + 64ull * R * 8 + yq_bytes_of(v) + (a.labels ? HX_FILT_RANGE_LDS : 0);
     if (lds > 160 * 1024) {
         set_error("filtered search needs %zu bytes of LDS (> 160 KiB)", lds);
         return HNSW_ERR_ARG;
@@ -575,14 +625,14 @@ int launch_graph(const DevView &v, const FilterArgs &a, uint32_t nblocks, uint32
 
 }  // namespace
 
-uint32_t filt_first_slots_log2(const DevView &v, uint32_t ef) {
-    return std::min(default_slots_log2(ef, v.S0), filt_max_slots_log2(v));
+uint32_t filt_first_slots_log2(const DevView &v, uint32_t ef, bool ranged) {
+    return std::min(default_slots_log2(ef, v.S0), filt_max_slots_log2(v, ranged));
 }
 
-uint32_t filt_max_slots_log2(const DevView &v) {
+uint32_t filt_max_slots_log2(const DevView &v, bool ranged) {
     const uint32_t yqb = ((v.kind == HNSW_VEC_QUANT8 ? 2u * (v.half_bytes - 8) * 4u : v.dim * 4u) + 15u) & ~15u;
     uint32_t s = HX_FILT_MAX_SLOTS_LOG2;
-    while (s > 12 && (4ull << s) + 64ull * 4 * 8 + yqb > 160 * 1024) s--;
+    while (s > 12 && (4ull << s) + 64ull * 4 * 8 + yqb + (ranged ? HX_FILT_RANGE_LDS : 0) > 160 * 1024) s--;
     return s;
 }
 

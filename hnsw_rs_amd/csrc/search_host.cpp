@@ -208,6 +208,27 @@ int sync_deleted(hnsw_index *h) {
     return h->del.sync(h->dev.device, lease.s->stream);
 }
 
+// ... and the label column's, for a range search.  (A column no label was ever set in gets a copy too: the kernels
+// take the pointer as "this call has a label range" and read nothing beyond label_len.)
+int sync_labels(hnsw_index *h) {
+    std::lock_guard<std::mutex> g(h->mu);
+    {  // the mirror, and so the copy, covers every id of the index: the points inserted since have label 0
+        std::lock_guard<std::mutex> lg(h->lab.mu);
+        h->lab.cover(index_len(h));
+    }
+    if (h->lab.current(h->dev.device) && h->lab.n_words() <= h->lab.d_cap) return HNSW_OK;
+    ScratchLease lease(h);
+    int rc = lease.prepare(h->dev.device, 0, 0);
+    if (rc != HNSW_OK) return rc;
+    return h->lab.sync(h->dev.device, lease.s->stream);
+}
+
+// the column as the kernels see it (after sync_labels: at least the index length; never more than the copy holds)
+void bind_labels(const hnsw_index *h, FilterArgs &a) {
+    a.labels = h->lab.d_labels();
+    a.label_len = std::min<uint64_t>(h->lab.labels.size(), 2 * h->lab.d_cap);
+}
+
 // The exact path's scratch from `base` in a device arena: [word offsets | admissible ids | partial keys | partial
 // statuses], for launches of up to nsel_max queries over up to A_max admissible ids (n_wbase word offsets in all)
 struct ExactScratch {
@@ -269,6 +290,8 @@ struct MaskGroup {
     size_t wb = 0;            // its word offsets in the call's list: from wb_all[wb]
     size_t q0 = 0, nq = 0;    // its queries: order[q0 .. q0 + nq)
     int64_t srow = -1;        // its row of the call's resident set (-1: the call has none, or HNSW_MASK_NONE)
+    uint32_t lo = 0, hi = 0;  // a range call: the group is the queries under [lo, hi] of the label column
+    bool lazy_wb = false;     // ... planned on the graph path: its word offsets are counted only if a query reaches path 2
     const uint32_t *d_list = nullptr;  // ... and that row's cached list of admissible ids in HBM, when it is valid
 };
 
@@ -285,9 +308,10 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
                   HX_FILT_MAX_N);
         return HNSW_ERR_ARG;
     }
-    const bool multi = m.mask_of != nullptr;
+    const bool ranged = m.lo != nullptr;  // (the entry point sees to hi)
+    const bool multi = m.mask_of != nullptr || ranged;
     hnsw_mask_set *const set = m.set;  // (a call under a set is a multi call: the entry point sees to mask_of)
-    if (multi) {
+    if (m.mask_of) {
         bool masked = false;
         for (uint64_t i = 0; i < nq; i++) {
             if (m.mask_of[i] == HNSW_MASK_NONE) continue;
@@ -315,6 +339,20 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     if (!multi) {
         groups.push_back(MaskGroup{m.masks, 0, bits});
         groups[0].nq = nq;
+    } else if (ranged) {  // the queries range by range: a group per distinct (lo, hi) pair
+        order.resize(nq);
+        for (uint64_t i = 0; i < nq; i++) order[i] = (uint32_t)i;
+        auto key = [&](uint32_t i) { return ((uint64_t)m.lo[i] << 32) | m.hi[i]; };
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t i, uint32_t j) { return key(i) < key(j); });
+        for (uint64_t i = 0; i < nq; i++) {
+            if (i == 0 || key(order[i]) != key(order[i - 1])) {
+                groups.push_back(MaskGroup{nullptr, 0, len});
+                groups.back().lo = m.lo[order[i]];
+                groups.back().hi = m.hi[order[i]];
+                groups.back().q0 = i;
+            }
+            groups.back().nq++;
+        }
     } else {
         order.resize(nq);
         for (uint64_t i = 0; i < nq; i++) order[i] = (uint32_t)i;
@@ -338,8 +376,21 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     // the set stays locked until its HBM copy is up to date and the lists this call needs are made
     std::unique_lock<std::mutex> set_lock;
     if (set) set_lock = std::unique_lock<std::mutex>(set->mu);
+    // a range's admissible ids are a slice of the label column's sorted copy (made here when the column, the deleted
+    // set or the length changed): two binary searches per range, and the word offsets only for an exact-path range
+    std::unique_lock<std::mutex> lab_lock;
+    if (ranged) {
+        lab_lock = std::unique_lock<std::mutex>(h->lab.mu);
+        h->lab.sort_for(h->del, len);
+    }
     for (MaskGroup &g : groups) {
-        if (g.srow >= 0) {
+        if (ranged) {
+            uint64_t first;
+            g.A = h->lab.count(g.lo, g.hi, &first);
+            wb.clear();
+            if (exact_only || (int64_t)g.A <= h->filter_exact_max) h->lab.word_base(first, g.A, len, wb);
+            else g.lazy_wb = true;
+        } else if (g.srow >= 0) {
             const hnsw_mask_set::Row &r = set->counted(h, (uint32_t)g.srow);
             g.A = r.A;
             wb = r.wbase;
@@ -352,6 +403,7 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         A_max = std::max(A_max, g.A);
         (g.exact ? n_exact : n_graph) += g.nq;
     }
+    if (ranged) lab_lock.unlock();
     if (n_graph && efp > HX_FILT_MAX_EF) {
         set_error("filtered search: ef' = max(ef, n) = %u is above the graph path's maximum of %d", efp, HX_FILT_MAX_EF);
         return HNSW_ERR_ARG;
@@ -372,18 +424,23 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
                 if (!groups[group_of[i]].exact) gsel.push_back((uint32_t)i);
         }
     }
-    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h)) || (set && (rc = set->sync(h)))) return rc;
+    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h)) || (set && (rc = set->sync(h))) ||
+        (ranged && (rc = sync_labels(h))))
+        return rc;
     const DevView &v = h->dev.view;
     const uint32_t d = v.dim;
     // device arena: [queries | masks | mask of every query | selection | the exact path's selection | the exact path's
     // scratch | result block].  All n_masks rows go up in one copy (a one-mask call sends the words below `bits` only).
     // The result block comes back in one copy to pinned memory: the caller's block, or the scratch's and from there to
     // the caller's buffers
-    // (a set's rows are in HBM already: nothing goes up, and the arena has no masks)
+    // (a set's rows are in HBM already: nothing goes up, and the arena has no masks; a range call has no masks
+    // either: its "mask of every query" is the two arrays lo and hi, and its word offsets have room for one more range,
+    // that of a path 2 group, counted when a query gets there)
     const uint64_t up_words = !m.masks || set ? 0 : multi ? (uint64_t)m.n_masks * row_words : (bits + 63) / 64;
     const size_t o_q = 0, o_mask = o_q + align256(nq * d * 4), o_mof = o_mask + align256(up_words * 8);
-    const size_t o_sel = o_mof + align256(multi ? nq * 4 : 0), o_xsel = o_sel + align256(nq * 4);
-    const ExactScratch x(o_xsel + align256(multi ? nq * 4 : 0), nq, n, A_max, wb_all.size());
+    const size_t o_sel = o_mof + (ranged ? 2 : 1) * align256(multi ? nq * 4 : 0), o_xsel = o_sel + align256(nq * 4);
+    const size_t wb_lazy = ranged ? std::max<uint64_t>(1, ((len + 63) / 64 + 63) / 64) : 0;
+    const ExactScratch x(o_xsel + align256(multi ? nq * 4 : 0), nq, n, A_max, wb_all.size() + wb_lazy);
     const size_t o_out = x.end;
     const ResultBlock out(nq, n);
     ScratchLease lease(h);
@@ -403,9 +460,15 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         HIP_TRY(hipMemcpyAsync(dv + x.o_wb + g.wb * 4, wb_all.data() + g.wb, n_wb * 4, hipMemcpyHostToDevice, s.stream));
         return HNSW_OK;
     };
-    if (!set && (bits || multi)) HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, s.stream));
+    if (!set && (bits || multi) && !wb_all.empty())
+        HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, s.stream));
     if (multi) {
-        HIP_TRY(hipMemcpyAsync(dv + o_mof, m.mask_of, nq * 4, hipMemcpyHostToDevice, s.stream));
+        if (ranged) {
+            HIP_TRY(hipMemcpyAsync(dv + o_mof, m.lo, nq * 4, hipMemcpyHostToDevice, s.stream));
+            HIP_TRY(hipMemcpyAsync(dv + o_mof + align256(nq * 4), m.hi, nq * 4, hipMemcpyHostToDevice, s.stream));
+        } else {
+            HIP_TRY(hipMemcpyAsync(dv + o_mof, m.mask_of, nq * 4, hipMemcpyHostToDevice, s.stream));
+        }
         if (!gsel.empty()) HIP_TRY(hipMemcpyAsync(d_sel, gsel.data(), gsel.size() * 4, hipMemcpyHostToDevice, s.stream));
         if (n_exact) HIP_TRY(hipMemcpyAsync(d_xsel, order.data(), nq * 4, hipMemcpyHostToDevice, s.stream));
     }
@@ -414,7 +477,12 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     a.qsel = gsel.empty() ? nullptr : d_sel;
     a.allow = d_masks;
     a.allow_bits = bits;
-    a.mask_of = multi ? reinterpret_cast<const uint32_t *>(dv + o_mof) : nullptr;
+    a.mask_of = multi && !ranged ? reinterpret_cast<const uint32_t *>(dv + o_mof) : nullptr;
+    if (ranged) {  // the label column and every query's range, the wave picks its own
+        bind_labels(h, a);
+        a.range_lo = reinterpret_cast<const uint32_t *>(dv + o_mof);
+        a.range_hi = reinterpret_cast<const uint32_t *>(dv + o_mof + align256(nq * 4));
+    }
     a.mask_words = row_words;
     a.none_bits = len;
     a.deny = h->del.count ? h->del.d_words : nullptr;
@@ -428,6 +496,9 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         ax.mask_of = nullptr;
         ax.allow = g.allow ? d_masks + g.row : nullptr;
         ax.allow_bits = g.bits;
+        ax.range_lo = ax.range_hi = nullptr;  // (a range call: the group's range as scalars)
+        ax.lo = g.lo;
+        ax.hi = g.hi;
         return ax;
     };
     if (set) {
@@ -454,7 +525,22 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         set_lock.unlock();
     }
     // the exact path for nsel queries of one mask (sel on the device; nullptr: the first nsel of the call)
+    std::vector<std::vector<uint32_t>> wb_kept;  // the word offsets of path 2 ranges, alive until the stream is waited for
     auto exact = [&](const MaskGroup &g, uint64_t nsel, const uint32_t *sel) -> int {
+        if (g.lazy_wb) {  // a graph-path range whose query filled the largest table: its offsets now, in the spare room
+            wb_kept.emplace_back();
+            {
+                std::lock_guard<std::mutex> lg(h->lab.mu);
+                h->lab.sort_for(h->del, len);
+                uint64_t first;
+                h->lab.count(g.lo, g.hi, &first);
+                h->lab.word_base(first, g.A, len, wb_kept.back());
+            }
+            const uint32_t *d_lazy = d_wb + wb_all.size();
+            HIP_TRY(hipMemcpyAsync(dv + x.o_wb + wb_all.size() * 4, wb_kept.back().data(), wb_kept.back().size() * 4,
+                                   hipMemcpyHostToDevice, s.stream));
+            return filtered_exact(v, group_args(g), nsel, sel, g.A, d_lazy, nsel, x, dv, s.stream);
+        }
         if (set && !g.d_list) {  // a row beyond the set's budget, or no row of the set: compacted in the scratch
             int r = upload_wb(g);
             if (r != HNSW_OK) return r;
@@ -470,7 +556,7 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     };
     // ONE launch of the graph path for the queries of every mask planned on it, then the exact path mask by mask (its
     // scratch reused in stream order), then the result block in one copy
-    const uint32_t slots = filt_first_slots_log2(v, efp);
+    const uint32_t slots = filt_first_slots_log2(v, efp, ranged);
     if (n_graph && (rc = launch_filtered_graph(v, a, (uint32_t)n_graph, slots, s.stream))) return rc;
     for (const MaskGroup &g : groups)
         if (g.exact && (rc = exact(g, g.nq, multi ? d_xsel + g.q0 : nullptr))) return rc;
@@ -483,7 +569,7 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         // that fill the largest one are answered by the exact path, each under its own mask
         std::vector<uint32_t> sel2;
         rc = rerun_overflowed(
-            v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v), d_sel, s.stream, fetch,
+            v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v, ranged), d_sel, s.stream, fetch,
             [&](const std::vector<uint32_t> &sel) -> int {
                 for (uint32_t i : sel) path[i] = 2;
                 sel2 = sel;
@@ -507,6 +593,9 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     }
     if (set) {
         h->n_filt_set_calls.fetch_add(1, std::memory_order_relaxed);
+    } else if (ranged) {
+        h->n_filt_range_calls.fetch_add(1, std::memory_order_relaxed);
+        h->n_filt_range_ranges.fetch_add(groups.size(), std::memory_order_relaxed);
     } else if (multi) {
         h->n_filt_multi_calls.fetch_add(1, std::memory_order_relaxed);
         h->n_filt_multi_masks.fetch_add(groups.size(), std::memory_order_relaxed);
@@ -760,6 +849,141 @@ int search_device_set(hnsw_index *h, hnsw_mask_set *set, const float *d_Q, uint6
             return query_status_error(i, st[i].status);
         }
     return HNSW_OK;
+}
+
+int search_device_range(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, const uint32_t *d_lo,
+                        const uint32_t *d_hi, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                        hnsw_query_stats *d_stats, hipStream_t stream, bool finish, uint8_t *paths) {
+    const uint32_t efp = std::max(std::max(ef, n), 1u);
+    if (n > HX_FILT_MAX_N || efp > HX_FILT_MAX_EF) {
+        set_error("filtered device search: needs n <= %d and ef' = max(ef, n) <= %d", HX_FILT_MAX_N, HX_FILT_MAX_EF);
+        return HNSW_ERR_ARG;
+    }
+    int rc;
+    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h)) || (rc = sync_labels(h))) return rc;
+    const DevView &v = h->dev.view;
+    DeviceQueries dq;
+    if ((rc = dq.prepare(h, d_Q, nq, stream))) return rc;
+    // the kernels write distances and counts: stream-ordered stand-ins for the optional outputs
+    struct Tmp {
+        void *p = nullptr;
+        hipStream_t st = nullptr;
+        ~Tmp() {
+            if (p) (void)hipFreeAsync(p, st);
+        }
+    } t_dists, t_counts;
+    if (!d_dists) {
+        HIP_TRY(hipMallocAsync(&t_dists.p, nq * n * 4, stream));
+        t_dists.st = stream;
+        d_dists = static_cast<float *>(t_dists.p);
+    }
+    if (!d_counts) {
+        HIP_TRY(hipMallocAsync(&t_counts.p, nq * 4, stream));
+        t_counts.st = stream;
+        d_counts = static_cast<uint32_t *>(t_counts.p);
+    }
+    const uint64_t len = index_len(h);
+    FilterArgs a{};
+    a.Q = dq.q;
+    a.allow = nullptr;
+    a.allow_bits = len;
+    a.none_bits = len;
+    bind_labels(h, a);
+    a.range_lo = d_lo;
+    a.range_hi = d_hi;
+    a.deny = h->del.count ? h->del.d_words : nullptr;
+    a.deny_bits = h->del.count ? h->del.deny_bits() : 0;
+    a.n = n;
+    a.ef = efp;
+    a.out_ids = d_ids;
+    a.out_dists = d_dists;
+    a.out_counts = d_counts;
+    a.out_stats = d_stats;
+    const uint32_t slots = filt_first_slots_log2(v, efp, true);
+    if (!finish) return launch_filtered_graph(v, a, (uint32_t)nq, slots, stream);
+
+    // scratch: the selection on the device; the statuses and the ranges of the queries on the host; the exact path's
+    // part ([selection | its scratch]) is sized only when a query reaches it
+    const size_t st_bytes = align256(nq * sizeof(hnsw_query_stats)), r_bytes = align256(nq * 4);
+    const size_t pin_bytes = st_bytes + 2 * r_bytes;
+    ScratchLease lease(h);
+    if ((rc = lease.prepare(h->dev.device, align256(nq * 4), pin_bytes))) return rc;
+    const hnsw_query_stats *st = nullptr;
+    const uint32_t *lo = nullptr, *hi = nullptr;
+    auto fetch = [&](const hnsw_query_stats *&out) -> int {
+        unsigned char *pin = static_cast<unsigned char *>(lease.s->pin);
+        HIP_TRY(hipMemcpyAsync(pin, d_stats, nq * sizeof(hnsw_query_stats), hipMemcpyDeviceToHost, stream));
+        if (!lo) {
+            HIP_TRY(hipMemcpyAsync(pin + st_bytes, d_lo, nq * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(pin + st_bytes + r_bytes, d_hi, nq * 4, hipMemcpyDeviceToHost, stream));
+        }
+        HIP_TRY(hipStreamSynchronize(stream));
+        out = st = reinterpret_cast<const hnsw_query_stats *>(pin);
+        lo = reinterpret_cast<const uint32_t *>(pin + st_bytes);
+        hi = reinterpret_cast<const uint32_t *>(pin + st_bytes + r_bytes);
+        return HNSW_OK;
+    };
+    auto key = [&](uint32_t i) { return ((uint64_t)lo[i] << 32) | hi[i]; };
+    std::vector<uint8_t> path(nq, 0);
+    uint64_t n2 = 0;
+    rc = rerun_overflowed(
+        v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v, true), static_cast<uint32_t *>(lease.s->dev), stream, fetch,
+        [&](const std::vector<uint32_t> &sel) -> int {  // path 2, range by range
+            std::vector<uint32_t> sel2 = sel;
+            std::stable_sort(sel2.begin(), sel2.end(), [&](uint32_t i, uint32_t j) { return key(i) < key(j); });
+            std::vector<uint64_t> keys(sel2.size());
+            for (size_t k = 0; k < sel2.size(); k++) keys[k] = key(sel2[k]);
+            for (uint32_t i : sel) path[i] = 2;
+            struct Part {
+                size_t lo, hi, wb;
+                uint64_t A;
+            };
+            std::vector<Part> parts;
+            std::vector<uint32_t> wb_all, wb;
+            uint64_t A_max = 0;
+            {
+                std::lock_guard<std::mutex> g(h->lab.mu);
+                h->lab.sort_for(h->del, len);
+                for (size_t p0 = 0, p1; p0 < sel2.size(); p0 = p1) {
+                    for (p1 = p0 + 1; p1 < sel2.size() && keys[p1] == keys[p0];) p1++;
+                    uint64_t first;
+                    const uint64_t A = h->lab.count((uint32_t)(keys[p0] >> 32), (uint32_t)keys[p0], &first);
+                    h->lab.word_base(first, A, len, wb);
+                    parts.push_back(Part{p0, p1, wb_all.size(), A});
+                    wb_all.insert(wb_all.end(), wb.begin(), wb.end());
+                    A_max = std::max(A_max, A);
+                }
+            }
+            const ExactScratch x(align256(sel2.size() * 4), sel2.size(), n, A_max, wb_all.size());
+            int r = lease.prepare(h->dev.device, x.end, pin_bytes);
+            if (r != HNSW_OK) return r;
+            unsigned char *dv = static_cast<unsigned char *>(lease.s->dev);
+            const uint32_t *d_sel = reinterpret_cast<const uint32_t *>(dv);
+            HIP_TRY(hipMemcpyAsync(dv, sel2.data(), sel2.size() * 4, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, stream));
+            for (const Part &p : parts) {
+                FilterArgs ax = a;
+                ax.range_lo = ax.range_hi = nullptr;
+                ax.lo = (uint32_t)(keys[p.lo] >> 32);
+                ax.hi = (uint32_t)keys[p.lo];
+                r = filtered_exact(v, ax, p.hi - p.lo, d_sel + p.lo, p.A, reinterpret_cast<const uint32_t *>(dv + x.o_wb) + p.wb,
+                                   p.hi - p.lo, x, dv, stream);
+                if (r != HNSW_OK) return r;
+            }
+            const hnsw_query_stats *unused;
+            return fetch(unused);  // (synchronises: `sel2` and `wb_all` live until then)
+        },
+        &n2);
+    if (rc != HNSW_OK) return rc;
+    std::vector<uint64_t> named(nq);
+    for (uint64_t i = 0; i < nq; i++) named[i] = key((uint32_t)i);
+    std::sort(named.begin(), named.end());
+    h->n_filt_graph.fetch_add(nq - n2, std::memory_order_relaxed);
+    h->n_filt_overflow.fetch_add(n2, std::memory_order_relaxed);
+    h->n_filt_range_calls.fetch_add(1, std::memory_order_relaxed);
+    h->n_filt_range_ranges.fetch_add((uint64_t)(std::unique(named.begin(), named.end()) - named.begin()), std::memory_order_relaxed);
+    if (paths) memcpy(paths, path.data(), nq);
+    return first_query_error(st, nq);
 }
 
 int search_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t *d_ids,

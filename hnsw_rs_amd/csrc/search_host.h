@@ -83,13 +83,16 @@ int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, u
 // allow_bits), or n_masks rows of ceil(allow_bits / 64) words and a row (or HNSW_MASK_NONE) per query.  The rows are
 // the caller's and go up with the call, or they are a resident set's (masks, allow_bits and n_masks are then the
 // set's host words, mask_of is required): nothing is uploaded, the kernels read the set's HBM copy, and the admissible
-// ids of a row come from the set's caches.
+// ids of a row come from the set's caches.  Or the call has no masks but a closed range [lo[i], hi[i]] per query over
+// the handle's label column (hnsw_search_batch_filtered_range; allow_bits is the index length): the planner's unit is
+// then a distinct (lo, hi) pair, counted with the column's sorted copy.
 struct MaskSpec {
     const uint64_t *masks = nullptr;
     uint64_t allow_bits = 0;
     uint32_t n_masks = 1;
     const uint32_t *mask_of = nullptr;  // nq entries
     hnsw_mask_set *set = nullptr;
+    const uint32_t *lo = nullptr, *hi = nullptr;  // nq entries each
 };
 
 // The admissible ids of a mask: below bits = min(allow_bits, len), allowed by `allow` (nullptr: all), not deleted.
@@ -124,6 +127,15 @@ int search_device_deleted(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t
 int search_device_set(hnsw_index *h, hnsw_mask_set *set, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
                       const uint32_t *d_mask_of, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
                       hnsw_query_stats *d_stats, hipStream_t stream, bool finish, uint8_t *paths);
+
+// hnsw_search_batch_filtered_range_device (finish = false) and _finish: the same under the label column, every query's
+// range read on the device from d_lo / d_hi.  The column is brought up to date on a stream of the handle's own, then ONE
+// launch goes to the caller's stream.  _finish reads d_lo / d_hi back with the statuses and answers the queries that
+// fill the largest table by the exact path, range by range.  Equals search_filtered under the ranges with
+// filter_exact_max = -1.
+int search_device_range(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, const uint32_t *d_lo,
+                        const uint32_t *d_hi, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                        hnsw_query_stats *d_stats, hipStream_t stream, bool finish, uint8_t *paths);
 
 // hnsw_search_batch_device_finish while nothing is deleted: waits for the stream, reads the per-query statuses,
 // re-runs the queries whose visited table filled up with a table twice the size (same arithmetic, same result as

@@ -373,6 +373,80 @@ class HNSW:
             stream or None, None if out is None else _p(out, _u8p)))
         return out
 
+    # ---- labels and label-range filtered search (include/hnsw_mi355x.h) ------------------------------------------
+    def set_labels(self, labels, ids=None):
+        """hnsw_set_labels: one uint32 label per id; ids None: labels[i] is id i's.  Every id must be < len (else
+        nothing changes); an id never set has label 0.  Needs no GPU."""
+        lab = self._ids(labels)
+        a = None if ids is None else self._ids(ids)
+        if a is not None and a.shape[0] != lab.shape[0]:
+            raise ValueError("one label per id")
+        check(self._L.hnsw_set_labels(self._h, None if a is None else _p(a, _u32p), _p(lab, _u32p), lab.shape[0]))
+
+    def get_labels(self, ids=None):
+        """-> the labels (uint32) of ids, or of every id 0..len-1"""
+        a = None if ids is None else self._ids(ids)
+        out = np.zeros(self.len() if a is None else a.shape[0], dtype=np.uint32)
+        check(self._L.hnsw_get_labels(self._h, None if a is None else _p(a, _u32p), out.shape[0], _p(out, _u32p)))
+        return out
+
+    def _range(self, lo, hi, nq):
+        out = []
+        for x in (lo, hi):
+            x = np.asarray(x)
+            if x.size and (x.min() < 0 or x.max() > _lib.UINT32_MAX):
+                raise ValueError("range bounds are labels: in [0, 2^32)")
+            x = np.ascontiguousarray(np.broadcast_to(x.astype(np.uint32).reshape(-1), (nq,))) if x.size == 1 else \
+                np.ascontiguousarray(x.reshape(-1), dtype=np.uint32)
+            if x.shape[0] != nq:
+                raise ValueError("lo and hi hold one entry per query (or are scalars)")
+            out.append(x)
+        return out
+
+    def search_batch_filtered_range(self, Q, n, ef, lo, hi):
+        """k-NN among the ids whose label lies in [lo[i], hi[i]] (hnsw_search_batch_filtered_range); scalars broadcast,
+        lo > hi is an empty range.  -> as search_batch_filtered"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        nq = Q.shape[0]
+        lo, hi = self._range(lo, hi, nq)
+        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        paths = np.zeros(nq, dtype=np.uint8)
+        check(self._L.hnsw_search_batch_filtered_range(
+            self._h, _p(Q, _f32p), nq, n, ef, _p(lo, _u32p), _p(hi, _u32p), _p(ids, _u32p), _p(dists, _f32p),
+            _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
+        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+
+    @staticmethod
+    def _dptr(t):
+        """a torch device tensor (or a raw device pointer, or None) -> the pointer as an int or None"""
+        if t is None or isinstance(t, (int, np.integer)):
+            return int(t) if t else None
+        return t.data_ptr()
+
+    def search_batch_filtered_range_device(self, d_Q, nq, n, ef, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats,
+                                           stream=0):
+        """hnsw_search_batch_filtered_range_device over torch device tensors (or raw device pointers): d_lo / d_hi
+        uint32 [nq] in HBM; one launch enqueued on `stream`, no sync."""
+        p = self._dptr
+        check(self._L.hnsw_search_batch_filtered_range_device(self._h, p(d_Q), nq, n, ef, p(d_lo), p(d_hi), p(d_ids),
+                                                              p(d_dists), p(d_counts), p(d_stats), stream or None))
+
+    def search_batch_filtered_range_device_finish(self, d_Q, nq, n, ef, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats,
+                                                  stream=0, paths=False):
+        """Completes search_batch_filtered_range_device: synchronises, re-runs overflowed queries, answers those that
+        fill the largest table by the exact path, raises the first per-query error.  paths=True -> uint8 [nq] (0 / 2)"""
+        p = self._dptr
+        out = np.zeros(nq, dtype=np.uint8) if paths else None
+        check(self._L.hnsw_search_batch_filtered_range_device_finish(
+            self._h, p(d_Q), nq, n, ef, p(d_lo), p(d_hi), p(d_ids), p(d_dists), p(d_counts), p(d_stats), stream or None,
+            None if out is None else _p(out, _u8p)))
+        return out
+
     def ann_by_vector_filtered(self, vector, n, ef, allow):
         """ann_by_vector restricted to the allowed ids -> list of ids"""
         q = np.ascontiguousarray(vector, dtype=np.float32).reshape(1, -1)

@@ -189,7 +189,8 @@ int hnsw_search_batch(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, ui
  * (HNSW_ERR_NAN_INPUT) as hnsw_search_batch.  The handle's deleted ids (hnsw_mark_deleted) are never allowed: the
  * effective mask is allow AND NOT deleted, and the result equals the same call with that mask on a handle with
  * nothing deleted.  Masks resident in HBM across calls and a device-pointer form are hnsw_mask_set's, below.  Not
- * provided: coalescing of one-query filtered calls, filtered sharded search and the Rust shim's binding. */
+ * provided: coalescing of one-query filtered calls, filtered sharded search, the Rust shim's binding, and a label
+ * range (hnsw_search_batch_filtered_range, below) combined with a mask or a mask set in one call. */
 int hnsw_search_batch_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
                                const uint64_t *allow, uint64_t allow_bits, uint32_t *ids, float *dists,
                                uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths /* 0/1/2 or NULL */);
@@ -284,6 +285,61 @@ int hnsw_search_batch_filtered_device_finish(hnsw_index *h, const float *d_Q, ui
                                              hnsw_mask_set *set, const uint32_t *d_mask_of, uint32_t *d_ids,
                                              float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
                                              void *stream, uint8_t *paths /* host, nq, or NULL */);
+
+/* ---- labels and label-range filtered search ----------------------------------------------------------------------
+ * A resident LABEL COLUMN: one uint32 per id (a tenant, a category, a timestamp), kept with the handle on the host and
+ * in HBM, and searches filtered by a closed range over it -- the form a filter usually arrives in, with no mask built,
+ * uploaded or stored for it (4 bytes per id, whatever the number of distinct predicates).  An id
+ * whose label was never set has label 0, ids added by later inserts included.  Setting labels touches the host
+ * mirror only and needs no GPU; the next range search brings the HBM copy up to date by the deleted set's mechanism:
+ * the changed 64-bit words (two labels each) scattered by one small kernel, or one whole copy when there is no copy
+ * yet, the device changed or more than an eighth of the words changed ("label_words_uploaded").  hnsw_clone and
+ * hnsw_set_device carry the column, hnsw_save writes it as the file `labels` (see hnsw_save); hnsw_snapshot_describe /
+ * _adopt do not carry it, but a device-only replica may set labels of its own (its length is the header's).
+ * hnsw_set_labels must not run concurrently with a range search on the handle.
+ * Not provided: a range combined with a mask set in one call, several label columns or labels that are not integers,
+ * the Rust shim's binding, filtered sharded search. */
+/* labels[k] for ids[k]; ids == NULL: ids 0..k-1.  An id >= hnsw_len is HNSW_ERR_ARG and nothing changes.  Needs no GPU. */
+int hnsw_set_labels(hnsw_index *h, const uint32_t *ids, const uint32_t *labels, uint64_t k);
+/* out[k]: the labels of ids[k] (NULL: of ids 0..k-1); an id >= hnsw_len is HNSW_ERR_ARG */
+int hnsw_get_labels(const hnsw_index *h, const uint32_t *ids /* NULL: 0..k-1 */, uint64_t k, uint32_t *out);
+/* k-NN among the ids whose label lies in the query's own closed range: query i's ids, distance bits, count, stats
+ * (status included) and path are exactly what hnsw_search_batch_filtered returns for that query alone, on the same
+ * handle with the same options, under the mask {id < hnsw_len : lo[i] <= label(id) <= hi[i]} -- n <= 64,
+ * ef' = max(ef, n, 1), deleted ids, the cosine option, per-query errors, path 2 on a visited-table overflow and
+ * A == 0 giving count 0 as there.  Equality is [x, x], no filter is [0, UINT32_MAX]; lo[i] > hi[i] is an empty range:
+ * count 0, status HNSW_OK, not an error.
+ * The planner runs per distinct (lo, hi) pair named in the call: the host determines the range's admissible count A
+ * exactly (two binary searches in a sorted copy of the column, which is made again when a label, the deleted set or
+ * hnsw_len changed); a range with A <= "filter_exact_max" takes the exact path (1) once, over its queries, the others
+ * the graph path (0), so the paths are those of the equivalent hnsw_search_batch_filtered_multi call.  ef' > 256 is
+ * HNSW_ERR_ARG when some range takes the graph path.  All graph-path queries of all ranges share ONE launch of the
+ * filtered graph kernel, each wave testing labels against its own range.
+ * HNSW_ERR_ARG, decided before the device is touched: Q, ids, lo or hi NULL; n > 64; nq > 2^31 - 1.  nq == 0 is
+ * HNSW_OK; n == 0 zeroes counts and launches nothing.  hnsw_get_stat: the three "filtered_*" path counters advance as
+ * for _multi, "filtered_range_calls" by one and "filtered_range_ranges" by the distinct ranges named. */
+int hnsw_search_batch_filtered_range(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                     const uint32_t *lo /* nq */, const uint32_t *hi /* nq */,
+                                     uint32_t *ids, float *dists, uint32_t *counts,
+                                     hnsw_query_stats *stats, uint8_t *paths /* 0/1/2 or NULL */);
+/* The same with every buffer in HBM on the handle's device, d_lo and d_hi too (both required), after
+ * hnsw_search_batch_filtered_device: the column is brought up to date on a stream of the handle's own, then ONE launch
+ * of the filtered graph kernel is enqueued on `stream` and the call returns without synchronising.  Every query takes
+ * the graph path: n <= 64 and ef' <= 256, else HNSW_ERR_ARG.  d_stats is required; d_dists / d_counts may be NULL.
+ * _finish (same arguments, and paths: host, nq, or NULL) waits for `stream`, reads the statuses and d_lo / d_hi back,
+ * re-runs the queries whose visited table filled up with larger tables, answers those that fill the largest by the
+ * exact path under their own range (path 2) and returns the first per-query error.  After it the buffers hold what
+ * hnsw_search_batch_filtered_range returns with "filter_exact_max" = -1 (paths 0 or 2); the counters advance at
+ * _finish. */
+int hnsw_search_batch_filtered_range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                            const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
+                                            float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
+                                            void *stream);
+int hnsw_search_batch_filtered_range_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n,
+                                                   uint32_t ef, const uint32_t *d_lo, const uint32_t *d_hi,
+                                                   uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                                                   hnsw_query_stats *d_stats, void *stream,
+                                                   uint8_t *paths /* host, nq, or NULL */);
 
 /* hnsw_search_batch with every buffer already resident in HBM on the handle's device; enqueues on `stream`
  * (a hipStream_t, NULL = default stream) and returns without synchronising.  d_stats is
@@ -388,7 +444,11 @@ int hnsw_check_param_compliance(const hnsw_index *h, int *ok);
  * points.rs:124-145, point.rs:57-75, quant.rs:102-124, graph.rs:168-251).  With ids deleted, save also writes
  * the file `deleted` (count u64, then count ids u32 in strictly ascending order, big-endian), which the reference's
  * load ignores; with none it writes exactly the files above and removes a stale `deleted`.  load restores the set
- * and returns HNSW_ERR_IO for a `deleted` that is short, longer than its count, unsorted or holds an id >= len. */
+ * and returns HNSW_ERR_IO for a `deleted` that is short, longer than its count, unsorted or holds an id >= len.
+ * With some label nonzero (hnsw_set_labels), save also writes the file `labels` (count u64, then the labels of ids
+ * 0..count-1 as u32, big-endian; trailing zero labels may be dropped); with every label zero it writes exactly the
+ * files above and removes a stale `labels`.  load restores the column and returns HNSW_ERR_IO for a `labels` that is
+ * short, longer than its count or has count > len. */
 int hnsw_save(const hnsw_index *h, const char *dir);
 int hnsw_load(const char *dir, hnsw_index **out);
 
@@ -453,7 +513,9 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * mask sets of the handle, summed: "mask_set_words_uploaded" (words of any set copied to HBM, by whole copies and by
  * scatters), "mask_set_recounts" (rows whose admissible ids the host counted), "mask_set_compactions" (compactions
  * launched for rows of a set), "filtered_set_calls" (hnsw_search_batch_filtered_set calls and completed
- * hnsw_search_batch_filtered_device calls); deletion:
+ * hnsw_search_batch_filtered_device calls); labels: "label_words_uploaded" (64-bit words of the label column copied
+ * to HBM), "filtered_range_calls" (hnsw_search_batch_filtered_range calls and completed _range_device calls),
+ * "filtered_range_ranges" (the distinct ranges they named); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
