@@ -7,9 +7,16 @@
 // reference's distance in the last bits.  It is therefore used as a SCREEN: per query the k + 8 best
 // points by score s(x) = |x|^2 - 2 x.q (the query's own norm does not change the order) are kept, and
 // their distances are then recomputed in the reference's exact arithmetic and order (hx_pair_distance_kernel)
-// and sorted by (dist, id).  The result equals the exact scan's unless rounding moved a true top-k member
-// below k + 8 others, which the tests check does not happen on the test sets; hnsw_brute_force stays the
-// exact, bit-for-bit one.  FullVec (f32) rows only.
+// and sorted by (dist, id).  Every list on the way (a lane's, the host's) is ordered by (score, id), so equal
+// scores are ordered as equal distances are.  The guarantee: every rounding error of a score, in any order
+// of summation, is below E = 1.01 (d + 2) 2^-24 max_x (|x|^2 + 2 sum|x_i||q_i|); a query's result is the
+// exact scan's, ids and distance bits, whenever for each of its true k neighbours x at most k + 8 points
+// (x included) have a true score <= s(x) + 2 E -- in particular whenever the scores are exact in f32.  Where
+// the gaps are smaller a neighbour can be missing; what is returned is still k distinct stored ids with the
+// reference's distances in (dist, id) order.  tests/test_gpu_ground_truth.py holds the scan to the oracle on
+// every query that tests/ground_truth_inputs.py proves safe (and asserts that at least 0.9 of them are), on
+// tie-heavy integer rows on every query, and to that weaker contract beyond the bound.  hnsw_brute_force
+// stays the unconditionally exact, bit-for-bit one.  FullVec (f32) rows only.
 //
 // Shape: a 256-thread workgroup owns a tile of 32 queries (staged once in LDS, rows padded by 16 B so that
 // the 16-byte operand reads are bank-conflict free) and one segment of the points; each of its four waves
@@ -121,11 +128,18 @@ hx_brute_mfma_kernel(const float *X, const float *xn, uint32_t N, uint32_t d, co
                 const float sc = n4[u] - 2.0f * acc[4 * g + u];
                 if (sc < thr) {
                     const uint32_t id = (uint32_t)(p0 + 8 * g + 4 * hi + u);
-                    // replace the current worst, then find the new worst
+                    // replace the current worst by (score, id) -- of the slots that tie at the threshold the one
+                    // with the largest id (an empty slot holds the largest of all) -- then find the new worst.
+                    // Ids arrive in increasing order and an equal score is not taken, so the list stays the
+                    // lane's MF_K2 best by (score, id): among equal scores the lowest ids, as the exact order.
+                    uint32_t worst = 0;
+#pragma unroll
+                    for (int t = 0; t < MF_K2; t++)
+                        if (bs[t] == thr) worst = max(worst, bi[t]);
                     bool done = false;
 #pragma unroll
                     for (int t = 0; t < MF_K2; t++) {
-                        if (!done && bs[t] == thr) {
+                        if (!done && bs[t] == thr && bi[t] == worst) {
                             bs[t] = sc;
                             bi[t] = id;
                             done = true;

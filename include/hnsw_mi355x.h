@@ -374,9 +374,16 @@ int hnsw_brute_force(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uin
  * dimension a multiple of 4, k <= 12): every point is screened by an MFMA score |x|^2 - 2 x.q
  * (v_mfma_f32_32x32x2_f32: f32 products and sums, but not FullVec::distance's summation order,
  * vectors/src/full.rs:23-29), the k + 8 best per query are re-evaluated in the reference's exact
- * arithmetic and sorted by (dist, id).  NOT bit-exact by construction -- rounding in the screen could in
- * principle lose a true neighbour; hnsw_brute_force is the exact scan.  An extension: the reference has
- * no counterpart. */
+ * arithmetic and sorted by (dist, id); equal scores are ordered by id, as equal distances are.  The
+ * guarantee: with E = 1.01 (d + 2) 2^-24 max_x (|x|^2 + 2 sum|x_i||q_i|), the bound on the rounding error of
+ * a score in any summation order, a query's result is hnsw_brute_force's, ids and distance bits, whenever for
+ * each of its true k neighbours x at most k + 8 points (x included) have a true score within 2 E above
+ * x's or below -- in particular whenever every score is exact in f32 (small integers).  Where the gaps are
+ * smaller than that (rows far from the origin relative to their spread) the result is still k distinct
+ * stored ids with the reference's own distances in (dist, id) order, but a neighbour can be missing.
+ * tests/test_gpu_ground_truth.py holds both halves to the oracle, tests/ground_truth_inputs.py derives the
+ * bound.  hnsw_brute_force is the unconditionally exact scan.  An extension: the reference has no
+ * counterpart. */
 int hnsw_brute_force_fast(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids,
                           float *dists);
 
