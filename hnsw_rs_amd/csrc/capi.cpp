@@ -418,8 +418,8 @@ static int filtered_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_
         set_error("filtered device search: needs queries, an id buffer and a stats buffer in HBM");
         return HNSW_ERR_ARG;
     }
-    return hx::search_device_set(h, set, d_Q, nq, n, ef, d_mask_of, d_ids, d_dists, d_counts, d_stats,
-                                 static_cast<hipStream_t>(stream), finish, paths);
+    return hx::search_device_filtered(h, hx::DeviceFilter{set, d_mask_of}, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats,
+                                      static_cast<hipStream_t>(stream), finish, paths);
 }
 
 int hnsw_search_batch_filtered_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
@@ -463,8 +463,8 @@ static int range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n
         set_error("filtered device search: needs queries, their label ranges, an id buffer and a stats buffer in HBM");
         return HNSW_ERR_ARG;
     }
-    return hx::search_device_range(h, d_Q, nq, n, ef, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats,
-                                   static_cast<hipStream_t>(stream), finish, paths);
+    return hx::search_device_filtered(h, hx::DeviceFilter{nullptr, nullptr, d_lo, d_hi}, d_Q, nq, n, ef, d_ids, d_dists,
+                                      d_counts, d_stats, static_cast<hipStream_t>(stream), finish, paths);
 }
 
 int hnsw_search_batch_filtered_range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
@@ -489,8 +489,8 @@ int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint3
     if (nq == 0 || n == 0) return HNSW_OK;
     if (!d_Q || !d_ids || !d_stats || nq > 0x7FFFFFFFull) return HNSW_ERR_ARG;
     if (h->del.count)
-        return hx::search_device_deleted(h, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats,
-                                         static_cast<hipStream_t>(stream), false);
+        return hx::search_device_filtered(h, hx::DeviceFilter{}, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats,
+                                          static_cast<hipStream_t>(stream), false, nullptr);
     rc = ensure_uploaded(h);
     if (rc != HNSW_OK) return rc;
     hx::DeviceQueries dq;
@@ -502,7 +502,7 @@ int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint3
     return hx::launch_search(h->dev.view, a, (uint32_t)nq, 0, static_cast<hipStream_t>(stream));
 }
 
-// Completes a hnsw_search_batch_device call (search_host.h: search_device_finish, search_device_deleted)
+// Completes a hnsw_search_batch_device call (search_host.h: search_device_finish, search_device_filtered)
 int hnsw_search_batch_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
                                     uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
                                     hnsw_query_stats *d_stats, void *stream_v) {
@@ -511,7 +511,8 @@ int hnsw_search_batch_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq
     if (nq == 0 || n == 0) return HNSW_OK;
     if (!d_Q || !d_ids || !d_stats || nq > 0x7FFFFFFFull) return HNSW_ERR_ARG;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    if (h->del.count) return hx::search_device_deleted(h, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats, stream, true);
+    if (h->del.count)
+        return hx::search_device_filtered(h, hx::DeviceFilter{}, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats, stream, true, nullptr);
     return hx::search_device_finish(h, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats, stream);
 }
 

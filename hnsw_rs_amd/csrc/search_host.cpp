@@ -6,7 +6,9 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
 #include <cstdlib>
+#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -232,7 +234,8 @@ void bind_labels(const hnsw_index *h, FilterArgs &a) {
 // The exact path's scratch from `base` in a device arena: [word offsets | admissible ids | partial keys | partial
 // statuses], for launches of up to nsel_max queries over up to A_max admissible ids (n_wbase word offsets in all)
 struct ExactScratch {
-    size_t o_wb, o_ids, o_part, o_pst, end;
+    size_t o_wb = 0, o_ids = 0, o_part = 0, o_pst = 0, end = 0;
+    ExactScratch() = default;
     ExactScratch(size_t base, uint64_t nsel_max, uint32_t n, uint64_t A_max, size_t n_wbase) {
         // chunk x nseg of any launch within those limits (filt_exact_segments: at most 256 segments, and at most
         // 262144 blocks unless the queries alone are more)
@@ -280,20 +283,216 @@ int filtered_exact(const DevView &v, const FilterArgs &a, uint64_t nsel, const u
     return r;
 }
 
-// One referenced allow-list of a call: the planner's unit.  A call with one mask has one group and every query in it.
-struct MaskGroup {
-    const uint64_t *allow;  // the caller's words (nullptr: every id below bits)
-    uint64_t row;           // first word of the mask in the call's uploaded masks
-    uint64_t bits;          // its id bound: min(allow_bits, len), or len without a mask
-    uint64_t A = 0;         // admissible ids
-    bool exact = false;     // A <= filter_exact_max
-    size_t wb = 0;            // its word offsets in the call's list: from wb_all[wb]
-    size_t q0 = 0, nq = 0;    // its queries: order[q0 .. q0 + nq)
-    int64_t srow = -1;        // its row of the call's resident set (-1: the call has none, or HNSW_MASK_NONE)
-    uint32_t lo = 0, hi = 0;  // a range call: the group is the queries under [lo, hi] of the label column
-    bool lazy_wb = false;     // ... planned on the graph path: its word offsets are counted only if a query reaches path 2
-    const uint32_t *d_list = nullptr;  // ... and that row's cached list of admissible ids in HBM, when it is valid
+// ---- the filter of a call --------------------------------------------------------------------------------------
+// A query's filter is named by one 64-bit key: 0 in a call with one mask (or with none: the undeleted ids), the row or
+// HNSW_MASK_NONE in a call with rows (the caller's or a resident set's), (lo << 32) | hi in a call with label ranges.
+// The queries under one key are a group: the planner's unit, and that of the exact path's launches.
+constexpr uint64_t UNCOUNTED = ~0ull;
+constexpr size_t NO_WB = ~(size_t)0;
+struct Group {
+    uint64_t key = 0;
+    size_t q0 = 0, nq = 0;             // its queries: [q0, q0 + nq) of the sorted list it was cut from
+    uint64_t A = UNCOUNTED;            // admissible ids
+    bool exact = false;                // A <= filter_exact_max: planned on the exact path
+    size_t wb = NO_WB, n_wb = 0;       // its word offsets in the list they were counted into (NO_WB: not counted yet)
+    const uint32_t *d_list = nullptr;  // a set row's cached list of admissible ids in HBM, when it is valid
 };
+
+// What turns a key into what the exact path needs, one per call: the masks, set or label column behind the keys, the
+// key of every query (host memory) and the call's own arguments.
+struct FilterSource {
+    enum Kind { ONE, ROWS, SET, RANGE } kind;
+    hnsw_index *h;
+    const uint64_t *masks;  // ONE, ROWS: the caller's words (nullptr: every id below bits)
+    hnsw_mask_set *set;     // SET
+    uint64_t len, bits, row_words;  // the index length, min(allow_bits, len), words of a row
+    const uint32_t *mask_of = nullptr, *lo = nullptr, *hi = nullptr;  // per query: ROWS and SET (nullptr: row 0), RANGE
+    FilterArgs base{};      // every mask or range: the graph kernel's wave picks its query's
+
+    FilterSource(hnsw_index *h_, Kind k, const uint64_t *masks_, hnsw_mask_set *set_, uint64_t allow_bits)
+        : kind(k), h(h_), masks(masks_), set(set_), len(index_len(h_)), bits(std::min<uint64_t>(allow_bits, len)),
+          row_words((allow_bits + 63) / 64) {}
+
+    uint64_t key(uint32_t i) const {
+        if (kind == RANGE) return ((uint64_t)lo[i] << 32) | hi[i];
+        return mask_of ? mask_of[i] : 0;
+    }
+    // the key names a row with words (masks may be NULL when allow_bits is 0: nothing is allowed, no word is read)
+    bool has_words(uint64_t key) const {
+        if (kind == ONE) return masks != nullptr;
+        return key != HNSW_MASK_NONE && (kind == ROWS ? masks != nullptr : kind == SET && set->W != 0);
+    }
+    // its id bound (a range call's bits are the index length)
+    uint64_t bound(uint64_t key) const { return key == HNSW_MASK_NONE ? len : bits; }
+
+    // base, but for the outputs and the selection; d_*: what the kernels read, on the device
+    void bind(const float *d_Q, const uint64_t *d_allow, const uint32_t *d_mask_of, const uint32_t *d_lo,
+              const uint32_t *d_hi, uint32_t n_masks, uint32_t n, uint32_t efp) {
+        base.Q = d_Q;
+        base.allow = d_allow;
+        base.allow_bits = bits;
+        base.mask_of = d_mask_of;
+        base.mask_words = row_words;
+        base.none_bits = len;
+        base.n_masks = n_masks;  // the kernel checks mask_of against it (the host may not have seen those words)
+        base.deny = h->del.count ? h->del.d_words : nullptr;
+        base.deny_bits = h->del.count ? h->del.deny_bits() : 0;
+        if (kind == RANGE) bind_labels(h, base);
+        base.range_lo = d_lo;
+        base.range_hi = d_hi;
+        base.n = n;
+        base.ef = efp;
+    }
+    // the arguments of an exact-path launch: the group's mask or range alone
+    FilterArgs args(const Group &g) const {
+        FilterArgs ax = base;
+        ax.mask_of = nullptr;
+        ax.allow = has_words(g.key) ? base.allow + g.key * row_words : nullptr;
+        ax.allow_bits = bound(g.key);
+        ax.range_lo = ax.range_hi = nullptr;  // (a range call: the group's range as scalars)
+        ax.lo = kind == RANGE ? (uint32_t)(g.key >> 32) : 0;
+        ax.hi = kind == RANGE ? (uint32_t)g.key : 0;
+        return ax;
+    }
+
+    // What `resolve` reads is locked by this: a set's caches (a row is counted when it, the deleted set or the length
+    // changed), or the label column's sorted copy (made here when the column, the deleted set or the length changed)
+    std::unique_lock<std::mutex> lock() const {
+        std::unique_lock<std::mutex> l;
+        if (kind == SET) l = std::unique_lock<std::mutex>(set->mu);
+        if (kind == RANGE) {
+            l = std::unique_lock<std::mutex>(h->lab.mu);
+            h->lab.sort_for(h->del, len);
+        }
+        return l;
+    }
+    // Counts a group: A (kept when it is known already), exact = A <= exact_max, a set row's list while it is valid, and
+    // its word offsets, appended to wbs.  A range's admissible ids are a slice of the sorted copy, found by two binary
+    // searches; its offsets cost a pass over the slice and are counted only when it is exact
+    void resolve(Group &g, int64_t exact_max, std::vector<uint32_t> &wbs) const {
+        std::vector<uint32_t> own;
+        const std::vector<uint32_t> *wb = &own;
+        uint64_t A, first = 0;
+        if (kind == RANGE) {
+            A = h->lab.count((uint32_t)(g.key >> 32), (uint32_t)g.key, &first);
+        } else if (kind == SET && has_words(g.key)) {
+            const hnsw_mask_set::Row &r = set->counted(h, (uint32_t)g.key);
+            A = r.A;
+            wb = &r.wbase;
+            g.d_list = r.list_valid ? r.d_ids : nullptr;
+        } else {
+            A = count_admissible(h, has_words(g.key) ? masks + g.key * row_words : nullptr, bound(g.key), own);
+        }
+        if (g.A == UNCOUNTED) g.A = A;
+        g.exact = (int64_t)g.A <= exact_max;
+        if (kind == RANGE) {
+            if (!g.exact) return;
+            h->lab.word_base(first, g.A, len, own);
+        }
+        g.wb = wbs.size();
+        g.n_wb = wb->size();
+        wbs.insert(wbs.end(), wb->begin(), wb->end());
+    }
+};
+
+// stable-sorts query indices by key and cuts them into runs: ascending key (HNSW_MASK_NONE last among rows), the
+// caller's order within a key
+std::vector<Group> group_by_key(std::vector<uint32_t> &idx, const FilterSource &src) {
+    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t i, uint32_t j) { return src.key(i) < src.key(j); });
+    std::vector<Group> runs;
+    for (size_t k = 0; k < idx.size(); k++) {
+        const uint64_t key = src.key(idx[k]);
+        if (k == 0 || key != runs.back().key) {
+            runs.emplace_back();
+            runs.back().key = key;
+            runs.back().q0 = k;
+        }
+        runs.back().nq++;
+    }
+    return runs;
+}
+
+// Where a call's exact path runs: a device arena with its scratch, a stream, and the word offsets on the host (wbs)
+// and on the device (d_wb, where group g's are at d_wb + g.wb).  send: they are not there yet and go up group by group
+// (under a set, where most groups have a list and need none).
+struct ExactPlace {
+    unsigned char *dv;
+    ExactScratch x;
+    hipStream_t stream;
+    const uint32_t *wbs;
+    uint32_t *d_wb;
+    bool send;
+};
+
+// the exact path for the g.nq queries of one group: those of d_sel, or the first g.nq of the call
+int exact_group(const FilterSource &src, const Group &g, const uint32_t *d_sel, uint64_t shape_nsel, const ExactPlace &at) {
+    if (!g.d_list && at.send) {  // compacted in the scratch: a row beyond the set's budget, or no row of the set
+        HIP_TRY(hipMemcpyAsync(at.d_wb + g.wb, at.wbs + g.wb, g.n_wb * 4, hipMemcpyHostToDevice, at.stream));
+        if (src.kind == FilterSource::SET && src.has_words(g.key)) src.h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
+    }
+    return filtered_exact(src.h->dev.view, src.args(g), g.nq, d_sel, g.A, at.d_wb + g.wb, shape_nsel, at.x, at.dv, at.stream,
+                          g.d_list);
+}
+
+// Path 2: the queries of `sel` filled the largest visited table and are answered by the exact path, each under its own
+// filter, group by group; then `fetch`, which synchronises.  The host form comes with its plan (`planned`, ascending
+// key; shape_nsel; `at`: its arena, laid out up front because the queries and the result block live in it, with the
+// selection at d_sel and room for one group's offsets at at.d_wb + spare) and nothing is allocated; a device form
+// (`grow`) has counted nothing yet and sizes [selection | exact scratch] in its lease only now.  A group that is not
+// counted yet -- every group of a device form, a graph-planned range of the host form -- is counted here, and its
+// offsets go up to that one room just before its launches (the scratch is reused in stream order).
+template <class Fetch>
+int path2(const FilterSource &src, const std::vector<uint32_t> &sel, std::vector<uint8_t> &path,
+          const std::vector<Group> *planned, uint64_t shape_nsel, ExactPlace at, uint32_t *d_sel, size_t spare,
+          ScratchLease *grow, size_t pin_bytes, Fetch fetch) {
+    std::vector<uint32_t> sel2 = sel, wb_late;
+    std::vector<Group> runs = group_by_key(sel2, src);
+    for (uint32_t i : sel) path[i] = 2;
+    std::unique_lock<std::mutex> lock;  // (a set's stays until the end: its lists are read by the launches)
+    std::vector<bool> late(runs.size(), false);
+    uint64_t A_max = 0;
+    size_t n_wb = 0;
+    for (size_t k = 0; k < runs.size(); k++) {
+        Group &g = runs[k];
+        if (planned) {
+            const Group &p = *std::lower_bound(planned->begin(), planned->end(), g.key,
+                                               [](const Group &x, uint64_t key) { return x.key < key; });
+            g.A = p.A, g.wb = p.wb, g.n_wb = p.n_wb, g.d_list = p.d_list;
+        }
+        if (g.wb == NO_WB) {
+            if (!lock.owns_lock()) lock = src.lock();
+            src.resolve(g, INT64_MAX, wb_late);
+            late[k] = true;
+        }
+        A_max = std::max(A_max, g.A);
+        n_wb = std::max(n_wb, g.n_wb);
+    }
+    if (src.kind == FilterSource::RANGE && lock.owns_lock()) lock.unlock();  // (the column's: never across a sync)
+    if (grow) {
+        at.x = ExactScratch(align256(sel2.size() * 4), sel2.size(), src.base.n, A_max, n_wb);
+        int r = grow->prepare(src.h->dev.device, at.x.end, pin_bytes);
+        if (r != HNSW_OK) return r;
+        at.dv = static_cast<unsigned char *>(grow->s->dev);
+        d_sel = reinterpret_cast<uint32_t *>(at.dv);
+        at.d_wb = reinterpret_cast<uint32_t *>(at.dv + at.x.o_wb);
+        spare = 0;
+    }
+    HIP_TRY(hipMemcpyAsync(d_sel, sel2.data(), sel2.size() * 4, hipMemcpyHostToDevice, at.stream));
+    for (size_t k = 0; k < runs.size(); k++) {
+        Group g = runs[k];
+        ExactPlace p = at;
+        if (late[k]) {  // its offsets: from wb_late to the one room
+            p.wbs = wb_late.data() + g.wb;
+            p.d_wb = at.d_wb + spare;
+            p.send = true;
+            g.wb = 0;
+        }
+        int r = exact_group(src, g, d_sel + g.q0, shape_nsel ? shape_nsel : g.nq, p);
+        if (r != HNSW_OK) return r;
+    }
+    const hnsw_query_stats *unused;
+    return fetch(unused);  // (synchronises: `sel2` and `wb_late` live until then)
+}
 
 }  // namespace
 
@@ -308,9 +507,6 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
                   HX_FILT_MAX_N);
         return HNSW_ERR_ARG;
     }
-    const bool ranged = m.lo != nullptr;  // (the entry point sees to hi)
-    const bool multi = m.mask_of != nullptr || ranged;
-    hnsw_mask_set *const set = m.set;  // (a call under a set is a multi call: the entry point sees to mask_of)
     if (m.mask_of) {
         bool masked = false;
         for (uint64_t i = 0; i < nq; i++) {
@@ -331,97 +527,46 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         return HNSW_OK;
     }
     const uint32_t efp = std::max(std::max(ef, n), 1u);
-    const uint64_t len = index_len(h), bits = std::min<uint64_t>(m.allow_bits, len);
-    const uint64_t row_words = (m.allow_bits + 63) / 64;  // a row of the caller's masks
-    // ---- the planner, per referenced mask: its admissible ids decide its queries' path ----
-    std::vector<uint32_t> order;  // the queries, mask by mask (HNSW_MASK_NONE last); a one-mask call has no use for it
-    std::vector<MaskGroup> groups;
-    if (!multi) {
-        groups.push_back(MaskGroup{m.masks, 0, bits});
-        groups[0].nq = nq;
-    } else if (ranged) {  // the queries range by range: a group per distinct (lo, hi) pair
+    // (the entry points see to hi with lo, and to mask_of with a set)
+    FilterSource src(h, m.lo ? FilterSource::RANGE : m.set ? FilterSource::SET : m.mask_of ? FilterSource::ROWS : FilterSource::ONE,
+                     m.masks, m.set, m.allow_bits);
+    src.mask_of = m.mask_of, src.lo = m.lo, src.hi = m.hi;
+    hnsw_mask_set *const set = m.set;
+    const bool ranged = src.kind == FilterSource::RANGE, multi = src.kind != FilterSource::ONE;
+    const uint64_t len = src.len, bits = src.bits, row_words = src.row_words;
+    // ---- the planner, per group: its admissible ids decide its queries' path.  A set stays locked until its HBM copy
+    // is up to date and the lists this call needs are made; the label column only while the ranges are counted ----
+    std::vector<uint32_t> order;  // the queries, group by group; a one-mask call has one group and no use for it
+    std::vector<Group> groups(1);
+    groups[0].nq = nq;
+    if (multi) {
         order.resize(nq);
         for (uint64_t i = 0; i < nq; i++) order[i] = (uint32_t)i;
-        auto key = [&](uint32_t i) { return ((uint64_t)m.lo[i] << 32) | m.hi[i]; };
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t i, uint32_t j) { return key(i) < key(j); });
-        for (uint64_t i = 0; i < nq; i++) {
-            if (i == 0 || key(order[i]) != key(order[i - 1])) {
-                groups.push_back(MaskGroup{nullptr, 0, len});
-                groups.back().lo = m.lo[order[i]];
-                groups.back().hi = m.hi[order[i]];
-                groups.back().q0 = i;
-            }
-            groups.back().nq++;
-        }
-    } else {
-        order.resize(nq);
-        for (uint64_t i = 0; i < nq; i++) order[i] = (uint32_t)i;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t i, uint32_t j) { return m.mask_of[i] < m.mask_of[j]; });
-        for (uint64_t i = 0; i < nq; i++) {
-            const uint32_t g = m.mask_of[order[i]];
-            if (i == 0 || g != m.mask_of[order[i - 1]]) {
-                if (g == HNSW_MASK_NONE)
-                    groups.push_back(MaskGroup{nullptr, 0, len});
-                else  // (masks may be NULL when allow_bits is 0: nothing is allowed, no word is read)
-                    groups.push_back(MaskGroup{m.masks ? m.masks + g * row_words : nullptr, g * row_words, bits});
-                if (set && g != HNSW_MASK_NONE && groups.back().allow) groups.back().srow = g;
-                groups.back().q0 = i;
-            }
-            groups.back().nq++;
-        }
+        groups = group_by_key(order, src);
     }
-    std::vector<uint32_t> wb_all, wb;
+    std::vector<uint32_t> wb_all;
     uint64_t A_max = 0, n_graph = 0, n_exact = 0;
-    // under a set the counts come from its caches (a row is counted when it, the deleted set or the length changed);
-    // the set stays locked until its HBM copy is up to date and the lists this call needs are made
-    std::unique_lock<std::mutex> set_lock;
-    if (set) set_lock = std::unique_lock<std::mutex>(set->mu);
-    // a range's admissible ids are a slice of the label column's sorted copy (made here when the column, the deleted
-    // set or the length changed): two binary searches per range, and the word offsets only for an exact-path range
-    std::unique_lock<std::mutex> lab_lock;
-    if (ranged) {
-        lab_lock = std::unique_lock<std::mutex>(h->lab.mu);
-        h->lab.sort_for(h->del, len);
-    }
-    for (MaskGroup &g : groups) {
-        if (ranged) {
-            uint64_t first;
-            g.A = h->lab.count(g.lo, g.hi, &first);
-            wb.clear();
-            if (exact_only || (int64_t)g.A <= h->filter_exact_max) h->lab.word_base(first, g.A, len, wb);
-            else g.lazy_wb = true;
-        } else if (g.srow >= 0) {
-            const hnsw_mask_set::Row &r = set->counted(h, (uint32_t)g.srow);
-            g.A = r.A;
-            wb = r.wbase;
-        } else {
-            g.A = count_admissible(h, g.allow, g.bits, wb);
-        }
-        g.exact = exact_only || (int64_t)g.A <= h->filter_exact_max;
-        g.wb = wb_all.size();
-        wb_all.insert(wb_all.end(), wb.begin(), wb.end());
+    std::unique_lock<std::mutex> lock = src.lock();
+    for (Group &g : groups) {
+        src.resolve(g, exact_only ? INT64_MAX : h->filter_exact_max, wb_all);
         A_max = std::max(A_max, g.A);
         (g.exact ? n_exact : n_graph) += g.nq;
     }
-    if (ranged) lab_lock.unlock();
+    if (ranged) lock.unlock();
     if (n_graph && efp > HX_FILT_MAX_EF) {
         set_error("filtered search: ef' = max(ef, n) = %u is above the graph path's maximum of %d", efp, HX_FILT_MAX_EF);
         return HNSW_ERR_ARG;
     }
-    // the selections: the graph path's queries in one list (none when every query takes it), the exact path's mask by
-    // mask (order itself when every query takes it)
-    std::vector<uint32_t> gsel, group_of;
+    // the selections: the graph path's queries in one list (none when every query takes it), the exact path's group by
+    // group (order itself when every query takes it)
+    std::vector<uint32_t> gsel;
     std::vector<uint8_t> path(nq, groups[0].exact ? 1 : 0);
     if (multi) {
-        group_of.resize(nq);
-        for (size_t k = 0; k < groups.size(); k++)
-            for (size_t i = groups[k].q0; i < groups[k].q0 + groups[k].nq; i++) {
-                group_of[order[i]] = (uint32_t)k;
-                path[order[i]] = groups[k].exact ? 1 : 0;
-            }
+        for (const Group &g : groups)
+            for (size_t i = g.q0; i < g.q0 + g.nq; i++) path[order[i]] = g.exact ? 1 : 0;
         if (n_graph && n_exact) {
             for (uint64_t i = 0; i < nq; i++)
-                if (!groups[group_of[i]].exact) gsel.push_back((uint32_t)i);
+                if (!path[i]) gsel.push_back((uint32_t)i);
         }
     }
     if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h)) || (set && (rc = set->sync(h))) ||
@@ -449,139 +594,75 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     unsigned char *dv = static_cast<unsigned char *>(s.dev);
     void *hv = pin_block ? pin_block : s.pin;
     uint32_t *d_sel = reinterpret_cast<uint32_t *>(dv + o_sel), *d_xsel = reinterpret_cast<uint32_t *>(dv + o_xsel);
-    const uint64_t *d_masks = set ? set->d_rows() : up_words ? reinterpret_cast<const uint64_t *>(dv + o_mask) : nullptr;
-    const uint32_t *d_wb = reinterpret_cast<const uint32_t *>(dv + x.o_wb);
+    uint32_t *d_mof = reinterpret_cast<uint32_t *>(dv + o_mof), *d_mof2 = reinterpret_cast<uint32_t *>(dv + o_mof + align256(nq * 4));
     HIP_TRY(hipMemcpyAsync(dv + o_q, Q, nq * d * 4, hipMemcpyHostToDevice, s.stream));
     if ((rc = cosine_queries(h, dv + o_q, nq, s.stream))) return rc;
     if (up_words) HIP_TRY(hipMemcpyAsync(dv + o_mask, m.masks, up_words * 8, hipMemcpyHostToDevice, s.stream));
-    // (under a set the word offsets of a mask go up only when a compaction of it runs)
-    auto upload_wb = [&](const MaskGroup &g) -> int {
-        const size_t n_wb = (&g == &groups.back() ? wb_all.size() : (&g)[1].wb) - g.wb;
-        HIP_TRY(hipMemcpyAsync(dv + x.o_wb + g.wb * 4, wb_all.data() + g.wb, n_wb * 4, hipMemcpyHostToDevice, s.stream));
-        return HNSW_OK;
-    };
+    // (under a set the word offsets of a group go up only when a compaction of it runs)
+    const ExactPlace at{dv, x, s.stream, wb_all.data(), reinterpret_cast<uint32_t *>(dv + x.o_wb), set != nullptr};
     if (!set && (bits || multi) && !wb_all.empty())
-        HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, s.stream));
+        HIP_TRY(hipMemcpyAsync(at.d_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, s.stream));
     if (multi) {
         if (ranged) {
-            HIP_TRY(hipMemcpyAsync(dv + o_mof, m.lo, nq * 4, hipMemcpyHostToDevice, s.stream));
-            HIP_TRY(hipMemcpyAsync(dv + o_mof + align256(nq * 4), m.hi, nq * 4, hipMemcpyHostToDevice, s.stream));
+            HIP_TRY(hipMemcpyAsync(d_mof, m.lo, nq * 4, hipMemcpyHostToDevice, s.stream));
+            HIP_TRY(hipMemcpyAsync(d_mof2, m.hi, nq * 4, hipMemcpyHostToDevice, s.stream));
         } else {
-            HIP_TRY(hipMemcpyAsync(dv + o_mof, m.mask_of, nq * 4, hipMemcpyHostToDevice, s.stream));
+            HIP_TRY(hipMemcpyAsync(d_mof, m.mask_of, nq * 4, hipMemcpyHostToDevice, s.stream));
         }
         if (!gsel.empty()) HIP_TRY(hipMemcpyAsync(d_sel, gsel.data(), gsel.size() * 4, hipMemcpyHostToDevice, s.stream));
         if (n_exact) HIP_TRY(hipMemcpyAsync(d_xsel, order.data(), nq * 4, hipMemcpyHostToDevice, s.stream));
     }
-    FilterArgs a{};  // the graph path's arguments: every mask, the wave picks its query's
-    a.Q = reinterpret_cast<const float *>(dv + o_q);
+    src.bind(reinterpret_cast<const float *>(dv + o_q),
+             set ? set->d_rows() : up_words ? reinterpret_cast<const uint64_t *>(dv + o_mask) : nullptr,
+             multi && !ranged ? d_mof : nullptr, ranged ? d_mof : nullptr, ranged ? d_mof2 : nullptr, m.n_masks, n, efp);
+    FilterArgs &a = src.base;
     a.qsel = gsel.empty() ? nullptr : d_sel;
-    a.allow = d_masks;
-    a.allow_bits = bits;
-    a.mask_of = multi && !ranged ? reinterpret_cast<const uint32_t *>(dv + o_mof) : nullptr;
-    if (ranged) {  // the label column and every query's range, the wave picks its own
-        bind_labels(h, a);
-        a.range_lo = reinterpret_cast<const uint32_t *>(dv + o_mof);
-        a.range_hi = reinterpret_cast<const uint32_t *>(dv + o_mof + align256(nq * 4));
-    }
-    a.mask_words = row_words;
-    a.none_bits = len;
-    a.deny = h->del.count ? h->del.d_words : nullptr;
-    a.deny_bits = h->del.count ? h->del.deny_bits() : 0;
-    a.n = n;
-    a.ef = efp;
-    a.n_masks = m.n_masks;  // (every mask_of entry was checked against it above)
     out.bind(a, dv + o_out);
-    auto group_args = [&](const MaskGroup &g) {
-        FilterArgs ax = a;
-        ax.mask_of = nullptr;
-        ax.allow = g.allow ? d_masks + g.row : nullptr;
-        ax.allow_bits = g.bits;
-        ax.range_lo = ax.range_hi = nullptr;  // (a range call: the group's range as scalars)
-        ax.lo = g.lo;
-        ax.hi = g.hi;
-        return ax;
-    };
     if (set) {
         // the lists of the rows planned on the exact path: a valid one is used as it is, the others are compacted
         // into the set (while its budget lasts) here, once, for this call and the ones after it
         const uint64_t budget = h->mask_set_cache_mb > 0 ? (uint64_t)h->mask_set_cache_mb << 20 : 0;
         std::vector<hnsw_mask_set::Row *> made;
-        for (MaskGroup &g : groups) {
-            if (g.srow < 0) continue;
-            hnsw_mask_set::Row &r = set->rows[(size_t)g.srow];
+        for (Group &g : groups) {
+            if (!src.has_words(g.key)) continue;
+            hnsw_mask_set::Row &r = set->rows[(size_t)g.key];
             if (!r.list_valid && g.exact && set->reserve_list(r, budget)) {
-                if ((rc = upload_wb(g)) ||
-                    (rc = launch_filter_compact(group_args(g), (g.bits + 63) / 64, d_wb + g.wb, r.d_ids, s.stream)))
-                    return rc;
+                HIP_TRY(hipMemcpyAsync(at.d_wb + g.wb, at.wbs + g.wb, g.n_wb * 4, hipMemcpyHostToDevice, s.stream));
+                if ((rc = launch_filter_compact(src.args(g), (bits + 63) / 64, at.d_wb + g.wb, r.d_ids, s.stream))) return rc;
                 h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
                 made.push_back(&r);
             }
-            if (r.list_valid || (!made.empty() && made.back() == &r)) g.d_list = r.d_ids;
+            g.d_list = r.list_valid || (!made.empty() && made.back() == &r) ? r.d_ids : nullptr;
         }
         if (!made.empty()) {  // (searches on other streams read the lists next)
             HIP_TRY(hipStreamSynchronize(s.stream));
             for (hnsw_mask_set::Row *r : made) r->list_valid = true;
         }
-        set_lock.unlock();
+        lock.unlock();
     }
-    // the exact path for nsel queries of one mask (sel on the device; nullptr: the first nsel of the call)
-    std::vector<std::vector<uint32_t>> wb_kept;  // the word offsets of path 2 ranges, alive until the stream is waited for
-    auto exact = [&](const MaskGroup &g, uint64_t nsel, const uint32_t *sel) -> int {
-        if (g.lazy_wb) {  // a graph-path range whose query filled the largest table: its offsets now, in the spare room
-            wb_kept.emplace_back();
-            {
-                std::lock_guard<std::mutex> lg(h->lab.mu);
-                h->lab.sort_for(h->del, len);
-                uint64_t first;
-                h->lab.count(g.lo, g.hi, &first);
-                h->lab.word_base(first, g.A, len, wb_kept.back());
-            }
-            const uint32_t *d_lazy = d_wb + wb_all.size();
-            HIP_TRY(hipMemcpyAsync(dv + x.o_wb + wb_all.size() * 4, wb_kept.back().data(), wb_kept.back().size() * 4,
-                                   hipMemcpyHostToDevice, s.stream));
-            return filtered_exact(v, group_args(g), nsel, sel, g.A, d_lazy, nsel, x, dv, s.stream);
-        }
-        if (set && !g.d_list) {  // a row beyond the set's budget, or no row of the set: compacted in the scratch
-            int r = upload_wb(g);
-            if (r != HNSW_OK) return r;
-            if (g.srow >= 0) h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
-        }
-        return filtered_exact(v, group_args(g), nsel, sel, g.A, d_wb + g.wb, multi ? nsel : nq, x, dv, s.stream, g.d_list);
-    };
     auto fetch = [&](const hnsw_query_stats *&st) -> int {
         HIP_TRY(hipMemcpyAsync(hv, dv + o_out, out.bytes, hipMemcpyDeviceToHost, s.stream));
         HIP_TRY(hipStreamSynchronize(s.stream));
         st = out.at(hv).stats;
         return HNSW_OK;
     };
-    // ONE launch of the graph path for the queries of every mask planned on it, then the exact path mask by mask (its
-    // scratch reused in stream order), then the result block in one copy
+    // ONE launch of the graph path for the queries of every group planned on it, then the exact path group by group
+    // (its scratch reused in stream order), then the result block in one copy
     const uint32_t slots = filt_first_slots_log2(v, efp, ranged);
     if (n_graph && (rc = launch_filtered_graph(v, a, (uint32_t)n_graph, slots, s.stream))) return rc;
-    for (const MaskGroup &g : groups)
-        if (g.exact && (rc = exact(g, g.nq, multi ? d_xsel + g.q0 : nullptr))) return rc;
+    for (const Group &g : groups)
+        if (g.exact && (rc = exact_group(src, g, multi ? d_xsel + g.q0 : nullptr, g.nq, at))) return rc;
     uint64_t n2 = 0;
     const hnsw_query_stats *st;
     if (!n_graph) {
         if ((rc = fetch(st))) return rc;
     } else {
-        // queries whose visited table filled up run again with a table twice the size, all masks together, and those
-        // that fill the largest one are answered by the exact path, each under its own mask
-        std::vector<uint32_t> sel2;
+        // queries whose visited table filled up run again with a table twice the size, all groups together, and those
+        // that fill the largest one take path 2
         rc = rerun_overflowed(
             v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v, ranged), d_sel, s.stream, fetch,
             [&](const std::vector<uint32_t> &sel) -> int {
-                for (uint32_t i : sel) path[i] = 2;
-                sel2 = sel;
-                if (multi) std::stable_sort(sel2.begin(), sel2.end(), [&](uint32_t i, uint32_t j) { return group_of[i] < group_of[j]; });
-                HIP_TRY(hipMemcpyAsync(d_sel, sel2.data(), sel2.size() * 4, hipMemcpyHostToDevice, s.stream));
-                int r = HNSW_OK;
-                for (size_t lo = 0, hi; r == HNSW_OK && lo < sel2.size(); lo = hi) {
-                    const uint32_t k = multi ? group_of[sel2[lo]] : 0;
-                    for (hi = lo + 1; hi < sel2.size() && (!multi || group_of[sel2[hi]] == k);) hi++;
-                    r = exact(groups[k], hi - lo, d_sel + lo);
-                }
-                return r != HNSW_OK ? r : fetch(st);  // (synchronises: `sel2` lives until then)
+                return path2(src, sel, path, &groups, multi ? 0 : nq, at, d_sel, wb_all.size(), nullptr, 0, fetch);
             },
             &n2);
         if (rc != HNSW_OK) return rc;
@@ -618,102 +699,24 @@ int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t
     return first_query_error(stats, nq);
 }
 
-int search_device_deleted(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t *d_ids,
-                          float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, hipStream_t stream, bool finish) {
+int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                           uint32_t *d_ids, float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
+                           hipStream_t stream, bool finish, uint8_t *paths) {
+    hnsw_mask_set *const set = f.set;
+    const bool ranged = f.d_lo != nullptr, deleted = !set && !ranged;
     const uint32_t efp = std::max(std::max(ef, n), 1u);
     if (n > HX_FILT_MAX_N || efp > HX_FILT_MAX_EF) {
-        set_error("search with deleted ids: needs n <= %d and ef' = max(ef, n) <= %d", HX_FILT_MAX_N, HX_FILT_MAX_EF);
+        set_error("%s: needs n <= %d and ef' = max(ef, n) <= %d", deleted ? "search with deleted ids" : "filtered device search",
+                  HX_FILT_MAX_N, HX_FILT_MAX_EF);
         return HNSW_ERR_ARG;
     }
-    int rc;
-    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h))) return rc;
-    const DevView &v = h->dev.view;
-    DeviceQueries dq;
-    if ((rc = dq.prepare(h, d_Q, nq, stream))) return rc;
-    // the kernels write distances and counts: stream-ordered stand-ins for the optional outputs
-    struct Tmp {
-        void *p = nullptr;
-        hipStream_t st = nullptr;
-        ~Tmp() {
-            if (p) (void)hipFreeAsync(p, st);
-        }
-    } t_dists, t_counts;
-    if (!d_dists) {
-        HIP_TRY(hipMallocAsync(&t_dists.p, nq * n * 4, stream));
-        t_dists.st = stream;
-        d_dists = static_cast<float *>(t_dists.p);
-    }
-    if (!d_counts) {
-        HIP_TRY(hipMallocAsync(&t_counts.p, nq * 4, stream));
-        t_counts.st = stream;
-        d_counts = static_cast<uint32_t *>(t_counts.p);
-    }
-    FilterArgs a{};
-    a.Q = dq.q;
-    a.allow = nullptr;
-    a.allow_bits = index_len(h);
-    a.deny = h->del.d_words;
-    a.deny_bits = h->del.deny_bits();
-    a.n = n;
-    a.ef = efp;
-    a.out_ids = d_ids;
-    a.out_dists = d_dists;
-    a.out_counts = d_counts;
-    a.out_stats = d_stats;
-    const uint32_t slots = filt_first_slots_log2(v, efp);
-    if (!finish) return launch_filtered_graph(v, a, (uint32_t)nq, slots, stream);
-
-    // scratch: the selection on the device, the statuses on the host; the exact path's part ([selection | its
-    // scratch]) is sized only when a query reaches it
-    const size_t st_bytes = nq * sizeof(hnsw_query_stats);
-    ScratchLease lease(h);
-    if ((rc = lease.prepare(h->dev.device, align256(nq * 4), st_bytes))) return rc;
-    const hnsw_query_stats *st = nullptr;
-    auto fetch = [&](const hnsw_query_stats *&out) -> int {
-        HIP_TRY(hipMemcpyAsync(lease.s->pin, d_stats, st_bytes, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        out = st = static_cast<const hnsw_query_stats *>(lease.s->pin);
-        return HNSW_OK;
-    };
-    uint64_t n2 = 0;
-    rc = rerun_overflowed(
-        v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v), static_cast<uint32_t *>(lease.s->dev), stream, fetch,
-        [&](const std::vector<uint32_t> &sel) -> int {  // path 2
-            std::vector<uint32_t> wbase;
-            const uint64_t A = count_admissible(h, nullptr, a.allow_bits, wbase);
-            const ExactScratch x(align256(sel.size() * 4), sel.size(), n, A, wbase.size());
-            int r = lease.prepare(h->dev.device, x.end, st_bytes);
-            if (r != HNSW_OK) return r;
-            unsigned char *dv = static_cast<unsigned char *>(lease.s->dev);
-            HIP_TRY(hipMemcpyAsync(dv, sel.data(), sel.size() * 4, hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wbase.data(), wbase.size() * 4, hipMemcpyHostToDevice, stream));
-            r = filtered_exact(v, a, sel.size(), reinterpret_cast<const uint32_t *>(dv), A,
-                               reinterpret_cast<const uint32_t *>(dv + x.o_wb), sel.size(), x, dv, stream);
-            const hnsw_query_stats *unused;
-            return r != HNSW_OK ? r : fetch(unused);  // (synchronises: `sel` and `wbase` live until then)
-        },
-        &n2);
-    if (rc != HNSW_OK) return rc;
-    h->n_del_graph.fetch_add(nq - n2, std::memory_order_relaxed);
-    h->n_del_overflow.fetch_add(n2, std::memory_order_relaxed);
-    return first_query_error(st, nq);
-}
-
-int search_device_set(hnsw_index *h, hnsw_mask_set *set, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
-                      const uint32_t *d_mask_of, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
-                      hnsw_query_stats *d_stats, hipStream_t stream, bool finish, uint8_t *paths) {
-    const uint32_t efp = std::max(std::max(ef, n), 1u);
-    if (n > HX_FILT_MAX_N || efp > HX_FILT_MAX_EF) {
-        set_error("filtered device search: needs n <= %d and ef' = max(ef, n) <= %d", HX_FILT_MAX_N, HX_FILT_MAX_EF);
-        return HNSW_ERR_ARG;
-    }
-    if (!d_mask_of && set->n_masks == 0) {
+    if (set && !f.d_mask_of && set->n_masks == 0) {
         set_error("filtered device search: every query names row 0 of a set without rows");
         return HNSW_ERR_ARG;
     }
     int rc;
-    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h))) return rc;
-    {
+    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h)) || (ranged && (rc = sync_labels(h)))) return rc;
+    if (set) {
         std::lock_guard<std::mutex> g(set->mu);
         if ((rc = set->sync(h))) return rc;
     }
@@ -738,252 +741,73 @@ int search_device_set(hnsw_index *h, hnsw_mask_set *set, const float *d_Q, uint6
         t_counts.st = stream;
         d_counts = static_cast<uint32_t *>(t_counts.p);
     }
-    const uint64_t len = index_len(h), bits = std::min<uint64_t>(set->allow_bits, len);
-    FilterArgs a{};
-    a.Q = dq.q;
-    a.allow = set->d_rows();
-    a.allow_bits = bits;
-    a.mask_of = d_mask_of;
-    a.mask_words = set->W;
-    a.none_bits = len;
-    a.n_masks = set->n_masks;  // the kernel checks d_mask_of against it: the host has not seen those words
-    a.deny = h->del.count ? h->del.d_words : nullptr;
-    a.deny_bits = h->del.count ? h->del.deny_bits() : 0;
-    a.n = n;
-    a.ef = efp;
+    FilterSource src(h, set ? FilterSource::SET : ranged ? FilterSource::RANGE : FilterSource::ONE, nullptr, set,
+                     set ? set->allow_bits : index_len(h));
+    src.bind(dq.q, set ? set->d_rows() : nullptr, f.d_mask_of, f.d_lo, f.d_hi, set ? set->n_masks : 0, n, efp);
+    FilterArgs &a = src.base;
     a.out_ids = d_ids;
     a.out_dists = d_dists;
     a.out_counts = d_counts;
     a.out_stats = d_stats;
-    const uint32_t slots = filt_first_slots_log2(v, efp);
+    const uint32_t slots = filt_first_slots_log2(v, efp, ranged);
     if (!finish) return launch_filtered_graph(v, a, (uint32_t)nq, slots, stream);
 
-    // scratch: the selection on the device; the statuses and the rows the queries name on the host; the exact path's
-    // part ([selection | its scratch]) is sized only when a query reaches it
-    const size_t st_bytes = align256(nq * sizeof(hnsw_query_stats)), pin_bytes = st_bytes + nq * 4;
+    // scratch: the selection on the device; the statuses and the keys of the queries (the rows or ranges they name) on
+    // the host; the exact path's part ([selection | its scratch]) is sized only when a query reaches it
+    const size_t st_bytes = nq * sizeof(hnsw_query_stats), o_keys = align256(st_bytes), r_bytes = align256(nq * 4);
+    const size_t pin_bytes = deleted ? st_bytes : set ? o_keys + nq * 4 : o_keys + 2 * r_bytes;
     ScratchLease lease(h);
     if ((rc = lease.prepare(h->dev.device, align256(nq * 4), pin_bytes))) return rc;
     const hnsw_query_stats *st = nullptr;
-    const uint32_t *mask_of = nullptr;
-    bool have_rows = false;
+    bool have_keys = false;  // they come back once, with the first fetch
     auto fetch = [&](const hnsw_query_stats *&out) -> int {
         unsigned char *pin = static_cast<unsigned char *>(lease.s->pin);
-        HIP_TRY(hipMemcpyAsync(pin, d_stats, nq * sizeof(hnsw_query_stats), hipMemcpyDeviceToHost, stream));
-        if (d_mask_of && !have_rows) HIP_TRY(hipMemcpyAsync(pin + st_bytes, d_mask_of, nq * 4, hipMemcpyDeviceToHost, stream));
+        uint32_t *k0 = reinterpret_cast<uint32_t *>(pin + o_keys), *k1 = reinterpret_cast<uint32_t *>(pin + o_keys + r_bytes);
+        HIP_TRY(hipMemcpyAsync(pin, d_stats, st_bytes, hipMemcpyDeviceToHost, stream));
+        if (f.d_mask_of && !have_keys) HIP_TRY(hipMemcpyAsync(k0, f.d_mask_of, nq * 4, hipMemcpyDeviceToHost, stream));
+        if (ranged && !have_keys) {
+            HIP_TRY(hipMemcpyAsync(k0, f.d_lo, nq * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(k1, f.d_hi, nq * 4, hipMemcpyDeviceToHost, stream));
+        }
         HIP_TRY(hipStreamSynchronize(stream));
-        have_rows = true;
+        have_keys = true;
         out = st = reinterpret_cast<const hnsw_query_stats *>(pin);
-        mask_of = d_mask_of ? reinterpret_cast<const uint32_t *>(pin + st_bytes) : nullptr;
+        if (f.d_mask_of) src.mask_of = k0;
+        if (ranged) src.lo = k0, src.hi = k1;
         return HNSW_OK;
     };
     std::vector<uint8_t> path(nq, 0);
     uint64_t n2 = 0;
     rc = rerun_overflowed(
-        v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v), static_cast<uint32_t *>(lease.s->dev), stream, fetch,
-        [&](const std::vector<uint32_t> &sel) -> int {  // path 2, row by row
+        v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v, ranged), static_cast<uint32_t *>(lease.s->dev), stream,
+        fetch,
+        [&](const std::vector<uint32_t> &sel) -> int {
             // (a query that names no row of the set ended with HNSW_ERR_ARG, not with an overflow: every row here exists)
-            auto row_of = [&](uint32_t i) { return mask_of ? mask_of[i] : 0u; };
-            std::vector<uint32_t> rows(sel.size()), sel2 = sel;
-            std::stable_sort(sel2.begin(), sel2.end(), [&](uint32_t i, uint32_t j) { return row_of(i) < row_of(j); });
-            for (size_t k = 0; k < sel2.size(); k++) rows[k] = row_of(sel2[k]);
-            for (uint32_t i : sel) path[i] = 2;
-            std::lock_guard<std::mutex> g(set->mu);  // the set's caches: counts, word offsets, valid lists
-            struct Part {
-                size_t lo, hi, wb;
-                uint64_t A;
-                const uint32_t *d_list;
-                bool of_set;
-            };
-            std::vector<Part> parts;
-            std::vector<uint32_t> wb_all, wb;
-            uint64_t A_max = 0;
-            for (size_t lo = 0, hi; lo < sel2.size(); lo = hi) {
-                for (hi = lo + 1; hi < sel2.size() && rows[hi] == rows[lo];) hi++;
-                Part p{lo, hi, wb_all.size(), 0, nullptr, false};
-                if (rows[lo] != HNSW_MASK_NONE && set->W) {
-                    const hnsw_mask_set::Row &r = set->counted(h, rows[lo]);
-                    p.A = r.A;
-                    p.of_set = true;
-                    if (r.list_valid) p.d_list = r.d_ids;
-                    else wb_all.insert(wb_all.end(), r.wbase.begin(), r.wbase.end());
-                } else {
-                    p.A = count_admissible(h, nullptr, rows[lo] == HNSW_MASK_NONE ? len : bits, wb);
-                    wb_all.insert(wb_all.end(), wb.begin(), wb.end());
-                }
-                A_max = std::max(A_max, p.A);
-                parts.push_back(p);
-            }
-            const ExactScratch x(align256(sel2.size() * 4), sel2.size(), n, A_max, wb_all.size());
-            int r = lease.prepare(h->dev.device, x.end, pin_bytes);
-            if (r != HNSW_OK) return r;
-            unsigned char *dv = static_cast<unsigned char *>(lease.s->dev);
-            const uint32_t *d_sel = reinterpret_cast<const uint32_t *>(dv);
-            HIP_TRY(hipMemcpyAsync(dv, sel2.data(), sel2.size() * 4, hipMemcpyHostToDevice, stream));
-            if (!wb_all.empty()) HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, stream));
-            for (const Part &p : parts) {
-                FilterArgs ax = a;
-                ax.mask_of = nullptr;
-                const uint32_t row = rows[p.lo];
-                ax.allow = p.of_set ? a.allow + (size_t)row * set->W : nullptr;
-                ax.allow_bits = row == HNSW_MASK_NONE ? len : bits;
-                if (p.of_set && !p.d_list) h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
-                r = filtered_exact(v, ax, p.hi - p.lo, d_sel + p.lo, p.A, reinterpret_cast<const uint32_t *>(dv + x.o_wb) + p.wb,
-                                   p.hi - p.lo, x, dv, stream, p.d_list);
-                if (r != HNSW_OK) return r;
-            }
-            const hnsw_query_stats *unused;
-            return fetch(unused);  // (synchronises: `sel2` and `wb_all` live until then)
+            return path2(src, sel, path, nullptr, 0, ExactPlace{nullptr, ExactScratch(), stream, nullptr, nullptr, true},
+                         nullptr, 0, &lease, pin_bytes, fetch);
         },
         &n2);
     if (rc != HNSW_OK) return rc;
-    h->n_filt_graph.fetch_add(nq - n2, std::memory_order_relaxed);
-    h->n_filt_overflow.fetch_add(n2, std::memory_order_relaxed);
-    h->n_filt_set_calls.fetch_add(1, std::memory_order_relaxed);
+    (deleted ? h->n_del_graph : h->n_filt_graph).fetch_add(nq - n2, std::memory_order_relaxed);
+    (deleted ? h->n_del_overflow : h->n_filt_overflow).fetch_add(n2, std::memory_order_relaxed);
+    if (set) h->n_filt_set_calls.fetch_add(1, std::memory_order_relaxed);
+    if (ranged) {  // ... and the distinct ranges over all queries
+        std::vector<uint64_t> named(nq);
+        for (uint64_t i = 0; i < nq; i++) named[i] = src.key((uint32_t)i);
+        std::sort(named.begin(), named.end());
+        h->n_filt_range_calls.fetch_add(1, std::memory_order_relaxed);
+        h->n_filt_range_ranges.fetch_add((uint64_t)(std::unique(named.begin(), named.end()) - named.begin()), std::memory_order_relaxed);
+    }
     if (paths) memcpy(paths, path.data(), nq);
     for (uint64_t i = 0; i < nq; i++)
-        if (st[i].status == HNSW_ERR_ARG) {
+        if (set && st[i].status == HNSW_ERR_ARG) {  // (the kernel's check of d_mask_of)
             set_error("filtered device search: query %llu names mask %u of %u", (unsigned long long)i,
-                      mask_of ? mask_of[i] : 0u, set->n_masks);
+                      (uint32_t)src.key((uint32_t)i), set->n_masks);
             return HNSW_ERR_ARG;
         } else if (st[i].status != HNSW_OK) {
             return query_status_error(i, st[i].status);
         }
     return HNSW_OK;
-}
-
-int search_device_range(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, const uint32_t *d_lo,
-                        const uint32_t *d_hi, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
-                        hnsw_query_stats *d_stats, hipStream_t stream, bool finish, uint8_t *paths) {
-    const uint32_t efp = std::max(std::max(ef, n), 1u);
-    if (n > HX_FILT_MAX_N || efp > HX_FILT_MAX_EF) {
-        set_error("filtered device search: needs n <= %d and ef' = max(ef, n) <= %d", HX_FILT_MAX_N, HX_FILT_MAX_EF);
-        return HNSW_ERR_ARG;
-    }
-    int rc;
-    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h)) || (rc = sync_labels(h))) return rc;
-    const DevView &v = h->dev.view;
-    DeviceQueries dq;
-    if ((rc = dq.prepare(h, d_Q, nq, stream))) return rc;
-    // the kernels write distances and counts: stream-ordered stand-ins for the optional outputs
-    struct Tmp {
-        void *p = nullptr;
-        hipStream_t st = nullptr;
-        ~Tmp() {
-            if (p) (void)hipFreeAsync(p, st);
-        }
-    } t_dists, t_counts;
-    if (!d_dists) {
-        HIP_TRY(hipMallocAsync(&t_dists.p, nq * n * 4, stream));
-        t_dists.st = stream;
-        d_dists = static_cast<float *>(t_dists.p);
-    }
-    if (!d_counts) {
-        HIP_TRY(hipMallocAsync(&t_counts.p, nq * 4, stream));
-        t_counts.st = stream;
-        d_counts = static_cast<uint32_t *>(t_counts.p);
-    }
-    const uint64_t len = index_len(h);
-    FilterArgs a{};
-    a.Q = dq.q;
-    a.allow = nullptr;
-    a.allow_bits = len;
-    a.none_bits = len;
-    bind_labels(h, a);
-    a.range_lo = d_lo;
-    a.range_hi = d_hi;
-    a.deny = h->del.count ? h->del.d_words : nullptr;
-    a.deny_bits = h->del.count ? h->del.deny_bits() : 0;
-    a.n = n;
-    a.ef = efp;
-    a.out_ids = d_ids;
-    a.out_dists = d_dists;
-    a.out_counts = d_counts;
-    a.out_stats = d_stats;
-    const uint32_t slots = filt_first_slots_log2(v, efp, true);
-    if (!finish) return launch_filtered_graph(v, a, (uint32_t)nq, slots, stream);
-
-    // scratch: the selection on the device; the statuses and the ranges of the queries on the host; the exact path's
-    // part ([selection | its scratch]) is sized only when a query reaches it
-    const size_t st_bytes = align256(nq * sizeof(hnsw_query_stats)), r_bytes = align256(nq * 4);
-    const size_t pin_bytes = st_bytes + 2 * r_bytes;
-    ScratchLease lease(h);
-    if ((rc = lease.prepare(h->dev.device, align256(nq * 4), pin_bytes))) return rc;
-    const hnsw_query_stats *st = nullptr;
-    const uint32_t *lo = nullptr, *hi = nullptr;
-    auto fetch = [&](const hnsw_query_stats *&out) -> int {
-        unsigned char *pin = static_cast<unsigned char *>(lease.s->pin);
-        HIP_TRY(hipMemcpyAsync(pin, d_stats, nq * sizeof(hnsw_query_stats), hipMemcpyDeviceToHost, stream));
-        if (!lo) {
-            HIP_TRY(hipMemcpyAsync(pin + st_bytes, d_lo, nq * 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(pin + st_bytes + r_bytes, d_hi, nq * 4, hipMemcpyDeviceToHost, stream));
-        }
-        HIP_TRY(hipStreamSynchronize(stream));
-        out = st = reinterpret_cast<const hnsw_query_stats *>(pin);
-        lo = reinterpret_cast<const uint32_t *>(pin + st_bytes);
-        hi = reinterpret_cast<const uint32_t *>(pin + st_bytes + r_bytes);
-        return HNSW_OK;
-    };
-    auto key = [&](uint32_t i) { return ((uint64_t)lo[i] << 32) | hi[i]; };
-    std::vector<uint8_t> path(nq, 0);
-    uint64_t n2 = 0;
-    rc = rerun_overflowed(
-        v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v, true), static_cast<uint32_t *>(lease.s->dev), stream, fetch,
-        [&](const std::vector<uint32_t> &sel) -> int {  // path 2, range by range
-            std::vector<uint32_t> sel2 = sel;
-            std::stable_sort(sel2.begin(), sel2.end(), [&](uint32_t i, uint32_t j) { return key(i) < key(j); });
-            std::vector<uint64_t> keys(sel2.size());
-            for (size_t k = 0; k < sel2.size(); k++) keys[k] = key(sel2[k]);
-            for (uint32_t i : sel) path[i] = 2;
-            struct Part {
-                size_t lo, hi, wb;
-                uint64_t A;
-            };
-            std::vector<Part> parts;
-            std::vector<uint32_t> wb_all, wb;
-            uint64_t A_max = 0;
-            {
-                std::lock_guard<std::mutex> g(h->lab.mu);
-                h->lab.sort_for(h->del, len);
-                for (size_t p0 = 0, p1; p0 < sel2.size(); p0 = p1) {
-                    for (p1 = p0 + 1; p1 < sel2.size() && keys[p1] == keys[p0];) p1++;
-                    uint64_t first;
-                    const uint64_t A = h->lab.count((uint32_t)(keys[p0] >> 32), (uint32_t)keys[p0], &first);
-                    h->lab.word_base(first, A, len, wb);
-                    parts.push_back(Part{p0, p1, wb_all.size(), A});
-                    wb_all.insert(wb_all.end(), wb.begin(), wb.end());
-                    A_max = std::max(A_max, A);
-                }
-            }
-            const ExactScratch x(align256(sel2.size() * 4), sel2.size(), n, A_max, wb_all.size());
-            int r = lease.prepare(h->dev.device, x.end, pin_bytes);
-            if (r != HNSW_OK) return r;
-            unsigned char *dv = static_cast<unsigned char *>(lease.s->dev);
-            const uint32_t *d_sel = reinterpret_cast<const uint32_t *>(dv);
-            HIP_TRY(hipMemcpyAsync(dv, sel2.data(), sel2.size() * 4, hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(dv + x.o_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, stream));
-            for (const Part &p : parts) {
-                FilterArgs ax = a;
-                ax.range_lo = ax.range_hi = nullptr;
-                ax.lo = (uint32_t)(keys[p.lo] >> 32);
-                ax.hi = (uint32_t)keys[p.lo];
-                r = filtered_exact(v, ax, p.hi - p.lo, d_sel + p.lo, p.A, reinterpret_cast<const uint32_t *>(dv + x.o_wb) + p.wb,
-                                   p.hi - p.lo, x, dv, stream);
-                if (r != HNSW_OK) return r;
-            }
-            const hnsw_query_stats *unused;
-            return fetch(unused);  // (synchronises: `sel2` and `wb_all` live until then)
-        },
-        &n2);
-    if (rc != HNSW_OK) return rc;
-    std::vector<uint64_t> named(nq);
-    for (uint64_t i = 0; i < nq; i++) named[i] = key((uint32_t)i);
-    std::sort(named.begin(), named.end());
-    h->n_filt_graph.fetch_add(nq - n2, std::memory_order_relaxed);
-    h->n_filt_overflow.fetch_add(n2, std::memory_order_relaxed);
-    h->n_filt_range_calls.fetch_add(1, std::memory_order_relaxed);
-    h->n_filt_range_ranges.fetch_add((uint64_t)(std::unique(named.begin(), named.end()) - named.begin()), std::memory_order_relaxed);
-    if (paths) memcpy(paths, path.data(), nq);
-    return first_query_error(st, nq);
 }
 
 int search_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t *d_ids,

@@ -99,8 +99,10 @@ struct MaskSpec {
 // -> A, and the admissible ids before every block of 64 words (the compaction kernel's offsets)
 uint64_t count_admissible(const hnsw_index *h, const uint64_t *allow, uint64_t bits, std::vector<uint32_t> &wbase);
 
-// k-NN among the admissible ids (hnsw_search_batch_filtered's and _multi's contract): the planner runs per referenced
-// mask, the graph path's queries of all masks share one launch and one re-run loop, the exact path runs mask by mask.
+// k-NN among the admissible ids (hnsw_search_batch_filtered's, _multi's, _set's and _range's contract): the planner runs
+// per group -- the queries under one mask, row or range -- the graph path's queries of all groups share one launch and
+// one re-run loop, the exact path runs group by group; queries that fill the largest visited table are answered by the
+// exact path as well, each under its own filter (path 2).
 // exact_only: every query by the exact path (hnsw_brute_force).  The results go to the caller's buffers (per-query
 // statuses in stats: required), or, when pin_block is given, straight into that pinned ResultBlock(nq, n) and the
 // buffers are not read.  Returns argument and launch errors only.
@@ -112,30 +114,23 @@ int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t
                             bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
                             uint8_t *paths, const PathCounters *ctr);
 
-// hnsw_search_batch_device (finish = false) and _finish while ids are deleted: the filtered graph path over the
-// undeleted ids on the caller's stream; _finish re-runs the queries whose visited table filled up with larger tables,
-// up to the graph path's largest, and answers those that fill it by the exact path.  Equals the host form with
-// filter_exact_max = -1.
-int search_device_deleted(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t *d_ids,
-                          float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, hipStream_t stream, bool finish);
+// The filter of a device-pointer call, read on the device: a row of a resident set per query (d_mask_of; nullptr: row 0),
+// or a label range per query (d_lo / d_hi), or neither: the undeleted ids, while ids are deleted.
+struct DeviceFilter {
+    hnsw_mask_set *set = nullptr;
+    const uint32_t *d_mask_of = nullptr, *d_lo = nullptr, *d_hi = nullptr;
+};
 
-// hnsw_search_batch_filtered_device (finish = false) and _finish: every query by the filtered graph path under its row
-// of a resident set, d_mask_of read on the device (nullptr: row 0); the set is brought up to date on a stream of the
-// handle's own, then ONE launch goes to the caller's stream.  _finish waits, reads the statuses and d_mask_of back,
-// re-runs the queries whose visited table filled up, answers those that fill the largest by the exact path, each under
-// its own row, and returns the first per-query error.  Equals search_filtered under the set with filter_exact_max = -1.
-int search_device_set(hnsw_index *h, hnsw_mask_set *set, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
-                      const uint32_t *d_mask_of, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
-                      hnsw_query_stats *d_stats, hipStream_t stream, bool finish, uint8_t *paths);
-
-// hnsw_search_batch_filtered_range_device (finish = false) and _finish: the same under the label column, every query's
-// range read on the device from d_lo / d_hi.  The column is brought up to date on a stream of the handle's own, then ONE
-// launch goes to the caller's stream.  _finish reads d_lo / d_hi back with the statuses and answers the queries that
-// fill the largest table by the exact path, range by range.  Equals search_filtered under the ranges with
-// filter_exact_max = -1.
-int search_device_range(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, const uint32_t *d_lo,
-                        const uint32_t *d_hi, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
-                        hnsw_query_stats *d_stats, hipStream_t stream, bool finish, uint8_t *paths);
+// hnsw_search_batch_device while ids are deleted, hnsw_search_batch_filtered_device and _filtered_range_device
+// (finish = false), and their _finish: every query by the filtered graph path under its own filter.  The deleted set and
+// the set or the label column are brought up to date on a stream of the handle's own, then ONE launch goes to the
+// caller's stream.  _finish waits, reads the statuses back (and with them, once, d_mask_of or d_lo / d_hi), re-runs the
+// queries whose visited table filled up with larger tables, up to the graph path's largest, answers those that fill it
+// by the exact path, each under its own row or range (search_filtered's path 2), and returns the first per-query error:
+// a row the set does not have is HNSW_ERR_ARG.  Equals search_filtered under the same filter with filter_exact_max = -1.
+int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                           uint32_t *d_ids, float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
+                           hipStream_t stream, bool finish, uint8_t *paths);
 
 // hnsw_search_batch_device_finish while nothing is deleted: waits for the stream, reads the per-query statuses,
 // re-runs the queries whose visited table filled up with a table twice the size (same arithmetic, same result as

@@ -205,6 +205,73 @@ def test_three_paths_with_deleted_ids(three_paths):
         s.close()
 
 
+def check_all_path_2(index, ridx, mask_list, Q, mo, got, deleted, sizes, what):
+    """every query took path 2: the walk under the first key, restated, fills the largest table, and every row is the
+    exact restatement's under its own key"""
+    assert (got[4] == 2).all(), (what, got[4])
+    pred = predicates(index, mask_list, deleted)
+    for k, (g, size) in enumerate(sizes):
+        allowed, a_ids = pred(g)
+        assert a_ids.size == size, (what, g, a_ids.size)
+        rows = np.flatnonzero(mo == g)
+        if k == 0:
+            assert FR.graph(ridx, Q[rows[0]], 10, 64, allowed)["visited0"] > LIMIT
+        for qi in rows:
+            assert got[3][qi, 3] == 0
+            compare_row(got, qi, FR.exact(ridx, Q[qi], 10, a_ids), 10, (what, qi))
+
+
+def test_path_2_under_two_keys_in_one_call(three_paths):
+    """with filter_exact_max = -1 the queries under `six` fill the largest table as those under `sparse` do: path 2 row
+    by row in _multi, under the set and in the device form, where `six` has its list in the set and `sparse` has not"""
+    index, ridx, mask_list, Q, _ = three_paths
+    Q8, mo = Q[::4], np.tile(np.array([1, 2]), 4)
+    s = index.mask_set(mask_list)
+    index.set_option("filter_exact_max", 10)
+    index.search_batch_filtered_set(Q8, 10, 64, s, mo)  # (`six` is planned exact: its list is made in the set)
+    before = stats_of(index)
+    got = set_and_multi(index, s, Q8, 10, 64, mask_list, mo, -1, "two keys")
+    d = delta(index, before)  # (the _multi call counts the same queries once more)
+    assert (d["filtered_queries_graph"], d["filtered_queries_exact"], d["filtered_overflow_exact"]) == (0, 0, 16)
+    assert d["mask_set_compactions"] == 1 and d["mask_set_recounts"] == 0  # `sparse`, in the scratch
+    check_all_path_2(index, ridx, mask_list, Q8, mo, got, (), ((2, 6), (1, 16)), "two keys")
+    for optional in (True, False):  # ... and without d_dists and d_counts
+        before = stats_of(index)
+        with H.kernel_log() as log:
+            code, dev = device_call(index, s, Q8, 10, 64, mo, optional=optional)
+        assert code is None
+        same(dev if optional else dev[:1] + got[1:3] + dev[3:], got, "device form, two keys")
+        d = delta(index, before)
+        assert d["filtered_overflow_exact"] == 8 and d["mask_set_compactions"] == 1 and d["mask_set_recounts"] == 0
+        assert log["hx_filt_compact_kernel"] == 1, dict(log)
+    s.close()
+
+
+def test_path_2_without_a_mask_next_to_a_row(three_paths):
+    """with all but 20 ids deleted the walk of a query without a mask fills the largest table too: HNSW_MASK_NONE and
+    the sparse row on path 2 in one call, in _multi, under the set and in the device form"""
+    index, ridx, mask_list, Q, _ = three_paths
+    keep = np.union1d(np.flatnonzero(mask_list[1]), [5, 1000, 15000, 29000])
+    assert keep.size == 20
+    deleted = np.setdiff1d(np.arange(30000), keep)
+    Q8, mo = Q[::4], np.tile(np.array([NONE, 1]), 4)
+    s = index.mask_set(mask_list)
+    index.mark_deleted(deleted)
+    try:
+        before = stats_of(index)
+        got = set_and_multi(index, s, Q8, 10, 64, mask_list, mo, -1, "no mask next to a row")
+        d = delta(index, before)
+        assert (d["filtered_queries_graph"], d["filtered_queries_exact"], d["filtered_overflow_exact"]) == (0, 0, 16)
+        check_all_path_2(index, ridx, mask_list, Q8, mo, got, deleted, ((NONE, 20), (1, 16)), "no mask next to a row")
+        code, dev = device_call(index, s, Q8, 10, 64, mo)
+        assert code is None
+        same(dev, got, "device form, no mask next to a row")
+    finally:
+        index.unmark_deleted(deleted)
+        s.close()
+        index.set_option("filter_exact_max", 65536)
+
+
 # ---- 2. the other cases of the contract --------------------------------------------------------------------------
 @pytest.mark.parametrize("exact_max", [-1, 50])
 def test_reference_test_data_with_none_rows(glove, exact_max):
