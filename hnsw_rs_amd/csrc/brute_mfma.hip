@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_index.h"
+#include "launch.h"
 
 namespace hx {
 
@@ -183,9 +184,8 @@ hx_pair_distance_kernel(const float *X, uint32_t d, const float *Q, const uint32
 }
 
 int launch_row_norms(const DevView &v, float *d_xn, hipStream_t stream) {
-    HX_LAUNCH(hx_row_norms_kernel, dim3((v.n_points + 255) / 256), dim3(256), 0, stream,
-                       reinterpret_cast<const float *>(v.rows), v.n_points, v.dim, d_xn);
-    return hipGetLastError() == hipSuccess ? HNSW_OK : HNSW_ERR_HIP;
+    return launch_checked({nullptr}, hx_row_norms_kernel, dim3((v.n_points + 255) / 256), dim3(256), 0, stream,
+                          reinterpret_cast<const float *>(v.rows), v.n_points, v.dim, d_xn);
 }
 
 uint32_t brute_mfma_k2() { return MF_K2; }
@@ -198,36 +198,17 @@ int launch_brute_mfma(const DevView &v, const float *d_xn, const float *d_Q, uin
         return HNSW_ERR_ARG;
     }
     const size_t lds = ((size_t)MF_QT * (v.dim + 4) + 4 * 32) * 4;
-    if (lds > 160 * 1024) {
-        set_error("the MFMA scan stages 32 queries in LDS: dimension %u is too large", v.dim);
-        return HNSW_ERR_ARG;
-    }
-    auto kern = hx_brute_mfma_kernel;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-            return HNSW_ERR_HIP;
-        }
-    }
     const uint32_t ntiles = (nq + MF_QT - 1) / MF_QT;
-    HX_LAUNCH(kern, dim3(nseg, ntiles), dim3(256), lds, stream, reinterpret_cast<const float *>(v.rows), d_xn,
-                       v.n_points, v.dim, d_Q, nq, nseg, out_s, out_i);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("MFMA scan launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"MFMA scan launch", "the MFMA scan stages 32 queries in LDS: dimension %zu is too large", v.dim},
+                          hx_brute_mfma_kernel, dim3(nseg, ntiles), dim3(256), lds, stream, reinterpret_cast<const float *>(v.rows),
+                          d_xn, v.n_points, v.dim, d_Q, nq, nseg, out_s, out_i);
 }
 
 int launch_pair_distance(const DevView &v, const float *d_Q, const uint32_t *d_qidx, const uint32_t *d_pidx, uint64_t n,
                          float *d_out, hipStream_t stream) {
     if (n == 0) return HNSW_OK;
-    HX_LAUNCH(hx_pair_distance_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream,
-                       reinterpret_cast<const float *>(v.rows), v.dim, d_Q, d_qidx, d_pidx, n, d_out);
-    return hipGetLastError() == hipSuccess ? HNSW_OK : HNSW_ERR_HIP;
+    return launch_checked({nullptr}, hx_pair_distance_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream,
+                          reinterpret_cast<const float *>(v.rows), v.dim, d_Q, d_qidx, d_pidx, n, d_out);
 }
 
 }  // namespace hx

@@ -7,6 +7,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "device_index.h"
+#include "launch.h"
 #include "host_index.h"
 #include "shard_exchange.h"
 
@@ -82,14 +83,8 @@ int filter_edge_records(const uint64_t *keys, const uint32_t *vals, uint32_t n, 
                         uint64_t *out_keys, uint32_t *out_vals, uint32_t *out_count, uint32_t out_cap, int32_t *status,
                         hipStream_t stream) {
     if (n == 0) return HNSW_OK;
-    HX_LAUNCH(hx_filter_records_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, keys, vals, n, rank, world, out_keys,
-                       out_vals, out_count, out_cap, status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("record filter kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"record filter kernel launch"}, hx_filter_records_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream,
+                          keys, vals, n, rank, world, out_keys, out_vals, out_count, out_cap, status);
 }
 
 }  // namespace hx

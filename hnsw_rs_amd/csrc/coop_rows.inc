@@ -1,5 +1,5 @@
-// coop_rows.inc -- included inside namespace hx by search_kernels.hip (and by the standalone check
-// scripts/micro/coop_rows_check.hip): the cooperative whole-line gather of wide FullVec rows.
+// coop_rows.inc -- included inside namespace hx by search_common.h, once (the kernel files and the standalone check
+// scripts/micro/coop_rows_check.hip get it from there): the cooperative whole-line gather of wide FullVec rows.
 // ---------------------------------------------------------------------------------------------
 // FullVec rows of whole 128-byte lines (d a multiple of 32: 128, 256, 768), gathered COOPERATIVELY.
 //

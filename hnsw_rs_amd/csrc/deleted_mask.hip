@@ -7,7 +7,7 @@
 
 #include "deleted.h"
 #include "hip_util.h"
-#include "kernel_log.h"
+#include "launch.h"
 
 namespace hx {
 
@@ -98,9 +98,9 @@ int HbmWords::sync_words(const uint64_t *words, uint64_t nw, uint64_t slack, int
             pairs[2 * i + 1] = words[dirty[i]];
         }
         HIP_TRY(hipMemcpyAsync(d_stage, pairs.data(), np * 16, hipMemcpyHostToDevice, stream));
-        HX_LAUNCH(hx_deleted_scatter_kernel, dim3((uint32_t)((np + 255) / 256)), dim3(256), 0, stream, d_words,
-                           (const uint64_t *)d_stage, np);
-        HIP_TRY(hipGetLastError());
+        if (int rc = launch_checked({"hipGetLastError() failed"}, hx_deleted_scatter_kernel, dim3((uint32_t)((np + 255) / 256)),
+                                    dim3(256), 0, stream, d_words, (const uint64_t *)d_stage, np))
+            return rc;
         words_uploaded += np;
     }
     // (`pairs` and `words` are read by the copies, and searches on other streams read the mask next)

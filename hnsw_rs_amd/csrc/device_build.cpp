@@ -1,5 +1,5 @@
 // device_build.cpp -- the on-device builds behind insert_bulk ("gpu_build" = 1 / 2, hnsw_insert_bulk_device,
-// hnsw_insert_bulk_sharded).  Host logic only; the kernels are in search_kernels.hip, build_sort.hip and patch.hip.
+// hnsw_insert_bulk_sharded).  Host logic only; the kernels are in build_kernels.hip, build_sort.hip and patch.hip.
 
 #include "device_build.h"
 

@@ -1,5 +1,5 @@
 // device_index.cpp -- packs a HostIndex into the HBM layout described in device_index.h and
-// uploads it.  Host code only (HIP runtime API); the kernels are in search_kernels.hip.
+// uploads it.  Host code only (HIP runtime API); the kernels are in the .hip files.
 
 #include "device_index.h"
 #include "hip_util.h"

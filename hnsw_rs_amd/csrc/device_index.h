@@ -1,5 +1,5 @@
-// device_index.h -- the HBM-resident snapshot of a HostIndex and the launchers of the search
-// kernels (search_kernels.hip).  gfx950 only.
+// device_index.h -- the HBM-resident snapshot of a HostIndex and the launchers of the kernels (search_kernels.hip,
+// search_lean.hip, build_kernels.hip, exact_scan.hip, brute_mfma.hip, build_sort.hip, patch.hip, metric.hip).  gfx950 only.
 //
 // HBM layout (one allocation per array, all read-only during search):
 //
@@ -83,7 +83,7 @@ struct SearchArgs {
     uint32_t spill_log2, lds_limit;
 };
 
-// one batch of the on-device build: insertion searches for point_ids[0..n) (search_kernels.hip)
+// one batch of the on-device build: insertion searches for point_ids[0..n) (build_kernels.hip)
 struct InsertArgs {
     const uint32_t *point_ids;  // device
     const uint8_t *levels;      // device, level of every stored point

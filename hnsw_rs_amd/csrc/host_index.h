@@ -2,7 +2,7 @@
 // (points + layered graph + params) and the build path (insert_bulk / insert_vec).
 //
 // The search hot path does NOT live here: it runs on the GPU from an HBM-resident snapshot of
-// this structure (device_index.h, search_kernels.hip).  Citations are relative to the reference
+// this structure (device_index.h, search_kernels.hip, build_kernels.hip).  Citations are relative to the reference
 // repository root.
 #pragma once
 

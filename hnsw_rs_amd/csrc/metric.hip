@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_index.h"
+#include "launch.h"
 
 namespace hx {
 
@@ -31,13 +32,8 @@ __global__ void __launch_bounds__(64) hx_normalise_rows_kernel(float *rows, uint
 
 int launch_normalise_rows(float *d_rows, uint64_t n, uint32_t d, hipStream_t stream) {
     if (n == 0) return HNSW_OK;
-    HX_LAUNCH(hx_normalise_rows_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, d_rows, n, d);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("normalise kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"normalise kernel launch"}, hx_normalise_rows_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0,
+                          stream, d_rows, n, d);
 }
 
 }  // namespace hx

@@ -580,23 +580,6 @@ template <int DS, class LT>
 int launch_pair(const LeanArgs &a, uint32_t nblocks, hipStream_t stream) {
     constexpr int R = LT::NR;
     const size_t lds = (4ull << a.slots_log2) + (64ull * R + 64) * 8 + sizeof(PairBox);
-    auto kern = hx_pair_f32_kernel<DS, LT>;
-    if (lds > 160 * 1024) {
-        set_error("search needs %zu bytes of LDS (> 160 KiB)", lds);
-        return HNSW_ERR_ARG;
-    }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-            return HNSW_ERR_HIP;
-        }
-    }
-    HX_LAUNCH(kern, dim3(nblocks), dim3(128), lds, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("search kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"search kernel launch", "search needs %zu bytes of LDS (> 160 KiB)"}, hx_pair_f32_kernel<DS, LT>,
+                          dim3(nblocks), dim3(128), lds, stream, a);
 }

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_index.h"
+#include "launch.h"
 
 namespace hx {
 
@@ -80,48 +81,26 @@ int launch_pack_rows(const DevView &v, const uint32_t *adj0, const uint32_t *adj
                      const uint32_t *counts, uint32_t list_cap, uint32_t max_count, uint32_t ship_slots, unsigned char *out,
                      hipStream_t stream) {
     if (max_count == 0) return HNSW_OK;
-    HX_LAUNCH(hx_pack_rows_kernel, dim3(max_count, HX_CHG_LISTS), dim3(64), 0, stream, v, adj0, adj_up, keys, counts,
-                       list_cap, ship_slots, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("pack-rows kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"pack-rows kernel launch"}, hx_pack_rows_kernel, dim3(max_count, HX_CHG_LISTS), dim3(64), 0, stream, v,
+                          adj0, adj_up, keys, counts, list_cap, ship_slots, out);
 }
 
 int launch_apply_rows(const DevView &v, uint32_t *adj0, uint32_t *adj_up, const unsigned char *entries, uint32_t n,
                       uint32_t ship_slots, int32_t *status, hipStream_t stream) {
     if (n == 0) return HNSW_OK;
-    HX_LAUNCH(hx_apply_rows_kernel, dim3(n), dim3(64), 0, stream, v, adj0, adj_up, entries, n, ship_slots, status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("apply-rows kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"apply-rows kernel launch"}, hx_apply_rows_kernel, dim3(n), dim3(64), 0, stream, v, adj0, adj_up,
+                          entries, n, ship_slots, status);
 }
 
 int launch_patch(const PatchDesc *d_desc, const uint32_t *d_staging, uint32_t n, hipStream_t stream) {
     if (n == 0) return HNSW_OK;
-    HX_LAUNCH(hx_patch_kernel, dim3(n), dim3(64), 0, stream, d_desc, d_staging, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("patch kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"patch kernel launch"}, hx_patch_kernel, dim3(n), dim3(64), 0, stream, d_desc, d_staging, n);
 }
 
 int launch_fat_rebuild(const DevView &v, uint8_t *fat, const uint32_t *d_nodes, uint32_t n, hipStream_t stream) {
     if (n == 0) return HNSW_OK;
-    HX_LAUNCH(hx_fat_rebuild_kernel, dim3(n), dim3(64), 0, stream, v, fat, d_nodes, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("inline-rows rebuild kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"inline-rows rebuild kernel launch"}, hx_fat_rebuild_kernel, dim3(n), dim3(64), 0, stream, v, fat,
+                          d_nodes, n);
 }
 
 }  // namespace hx

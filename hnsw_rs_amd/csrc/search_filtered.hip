@@ -26,6 +26,7 @@
 
 #include <algorithm>
 
+#include "launch.h"
 #include "search_common.h"
 #include "search_filtered.h"
 
@@ -288,10 +289,6 @@ __device__ __forceinline__ float filt_dist(const DevView &v, uint32_t id, bool a
     }
 }
 
-__host__ __device__ inline uint32_t yq_bytes_of(const DevView &v) {
-    return ((v.kind == HNSW_VEC_QUANT8 ? 2u * (v.half_bytes - 8) * 4u : v.dim * 4u) + 15u) & ~15u;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Graph path.  LDS: visited table (4 << slots_log2 bytes) | merge buffer (64 R keys) | query | under a label range,
 // the wave's range (HX_FILT_RANGE_LDS bytes).
@@ -321,7 +318,7 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
     uint32_t *htab = reinterpret_cast<uint32_t *>(smem);
     u64 *perm = reinterpret_cast<u64 *>(smem + (4ull << slots_log2));
     float *yq = reinterpret_cast<float *>(perm + 64 * R);
-    uint32_t *range = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(yq) + yq_bytes_of(v));
+    uint32_t *range = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(yq) + query_lds_bytes(v));
     if (a.labels && lane == 0) {  // (read after the wave_fence of the first clear_visited)
         range[0] = lo;
         range[1] = hi - lo;
@@ -593,27 +590,9 @@ __global__ void __launch_bounds__(64) hx_filt_merge_kernel(const FilterArgs a, u
 
 template <int KIND, int P, int DS, int R>
 int launch_graph_r(const DevView &v, const FilterArgs &a, uint32_t nblocks, uint32_t slots_log2, hipStream_t stream) {
-    auto kern = hx_filt_graph_kernel<KIND, P, DS, R>;
-    const size_t lds = (4ull << slots_log2) + 64ull * R * 8 + yq_bytes_of(v) + (a.labels ? HX_FILT_RANGE_LDS : 0);
-    if (lds > 160 * 1024) {
-        set_error("filtered search needs %zu bytes of LDS (> 160 KiB)", lds);
-        return HNSW_ERR_ARG;
-    }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-            return HNSW_ERR_HIP;
-        }
-    }
-    HX_LAUNCH(kern, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("filtered search kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    const size_t lds = (4ull << slots_log2) + 64ull * R * 8 + query_lds_bytes(v) + (a.labels ? HX_FILT_RANGE_LDS : 0);
+    return launch_checked({"filtered search kernel launch", "filtered search needs %zu bytes of LDS (> 160 KiB)"},
+                          hx_filt_graph_kernel<KIND, P, DS, R>, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
 }
 
 template <int KIND, int P, int DS>
@@ -630,7 +609,7 @@ uint32_t filt_first_slots_log2(const DevView &v, uint32_t ef, bool ranged) {
 }
 
 uint32_t filt_max_slots_log2(const DevView &v, bool ranged) {
-    const uint32_t yqb = ((v.kind == HNSW_VEC_QUANT8 ? 2u * (v.half_bytes - 8) * 4u : v.dim * 4u) + 15u) & ~15u;
+    const uint32_t yqb = query_lds_bytes(v);
     uint32_t s = HX_FILT_MAX_SLOTS_LOG2;
     while (s > 12 && (4ull << s) + 64ull * 4 * 8 + yqb + (ranged ? HX_FILT_RANGE_LDS : 0) > 160 * 1024) s--;
     return s;
@@ -656,13 +635,8 @@ int launch_filter_compact(const FilterArgs &a, uint64_t n_words, const uint32_t 
                           hipStream_t stream) {
     if (n_words == 0) return HNSW_OK;
     const uint64_t nb = (n_words + 63) / 64;
-    HX_LAUNCH(hx_filt_compact_kernel, dim3((uint32_t)nb), dim3(64), 0, stream, a, n_words, word_base, ids);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("filter compaction kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"filter compaction kernel launch"}, hx_filt_compact_kernel, dim3((uint32_t)nb), dim3(64), 0, stream, a,
+                          n_words, word_base, ids);
 }
 
 uint32_t filt_exact_segments(uint64_t A, uint32_t nsel) {
@@ -679,23 +653,13 @@ int launch_filtered_exact(const DevView &v, const FilterArgs &a, uint32_t nsel, 
         set_error("filtered exact search: needs 1 <= n <= %d and at most 65535 queries per launch", HX_FILT_MAX_N);
         return HNSW_ERR_ARG;
     }
-    const size_t lds = 64 * 8 + (((v.kind == HNSW_VEC_QUANT8 ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4) + 15) & ~15ull);
-    if (v.kind == HNSW_VEC_QUANT8)
-        HX_LAUNCH(hx_filt_scan_kernel<HNSW_VEC_QUANT8>, dim3(nseg, nsel), dim3(64), lds, stream, v, a, ids, A,
-                           nseg, part, part_status);
-    else
-        HX_LAUNCH(hx_filt_scan_kernel<HNSW_VEC_F32>, dim3(nseg, nsel), dim3(64), lds, stream, v, a, ids, A,
-                           nseg, part, part_status);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        HX_LAUNCH(hx_filt_merge_kernel, dim3(nsel), dim3(64), 0, stream, a, A, nseg, part, part_status);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) {
-        set_error("filtered exact search launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    // scan, then merge: two launches back to back under one message, the second only after the first was accepted
+    const LaunchSite site{"filtered exact search launch"};
+    if (int rc = launch_checked(site, v.kind == HNSW_VEC_QUANT8 ? hx_filt_scan_kernel<HNSW_VEC_QUANT8> : hx_filt_scan_kernel<HNSW_VEC_F32>,
+                                dim3(nseg, nsel), dim3(64), 64 * 8 + (size_t)query_lds_bytes(v), stream, v, a, ids, A, nseg, part,
+                                part_status))
+        return rc;
+    return launch_checked(site, hx_filt_merge_kernel, dim3(nsel), dim3(64), 0, stream, a, A, nseg, part, part_status);
 }
 
 }  // namespace hx

@@ -33,20 +33,19 @@
 // Float fidelity: compiled with -ffp-contract=off; no FMA may fuse `code * delta + min` or
 // `acc += t * t`; sqrt and the quantiser's division are the correctly rounded forms hipcc emits
 // by default.  Accumulation order is the reference's (quant.rs:23-36, full.rs:24-28).
+//
+// This file: hx_search_kernel, hx_search2_kernel (opt-in two-wave form), hx_search_spill_kernel (ef > 1024), their
+// launchers and launch_search.  The wave primitives they share with the other kernel files are in search_common.h; the
+// on-device build is build_kernels.hip, the exact scans are exact_scan.hip, the lean kernels search_lean.hip.
 
+#include <cstdio>
 #include <cstdlib>
 
 #include "device_index.h"
+#include "launch.h"
 #include "search_common.h"
 
 namespace hx {
-
-static constexpr u64 KEY_INVALID = ~0ull;
-static constexpr u64 KEY_MASK = 0x7FFFFFFFFFFFFFFFull;  // drops the expanded flag
-static constexpr u64 KEY_EXPANDED = 1ull << 63;
-
-#define HX_MAX_R 8  // ef <= 64 * HX_MAX_R on the specialised kernels and in the on-device build
-#define HX_MAX_R_WIDE 16  // ef <= 1024 on the any-dimension search kernel
 
 // Diagnostic build only (make stamps): per-phase cycle shares of the inline-rows expansion loop,
 // written to a side buffer nothing else reads.  The shipped library is built without HX_STAMPS.
@@ -57,705 +56,6 @@ static constexpr u64 KEY_EXPANDED = 1ull << 63;
 #define STAMP(var)
 #define STAMP_ADD(slot, a, b)
 #endif
-
-// workgroup barrier that does not drain VMEM (LDS-DMA prefetches stay in flight across it)
-__device__ __forceinline__ void wg_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-// value held by lane q (0..3) of this lane's quad
-template <int Q>
-__device__ __forceinline__ float quad_bcast(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x),
-                                                                  Q * 0x55, 0xF, 0xF, true));
-}
-template <int Q>
-__device__ __forceinline__ int quad_bcast_i(int x) {
-    return __builtin_amdgcn_update_dpp(0, x, Q * 0x55, 0xF, 0xF, true);
-}
-// ---------------------------------------------------------------------------------------------
-// Four lanes per candidate (two-wave kernel): lane (h, sub) of the quad owns running sums
-// 4h + 2 sub and 4h + 2 sub + 1 of distance_unrolled, i.e. bytes 2 sub and 2 sub + 1 of every chunk
-// dword of half h; the d % 8 tail belongs to lane (0, 0) alone.  qc[2 c + kk] is this lane's query
-// value for chunk dword c, byte kk; qt[r] the tail values (lane (0,0) only).
-// ---------------------------------------------------------------------------------------------
-template <int P, int DS, typename QC, typename QT>
-__device__ __forceinline__ void quant_pair_sums(const uint4 (&w)[P], const QC &qc, const QT &qt,
-                                                int h, int sub, uint32_t nch4, uint32_t rem,
-                                                float (&acc)[2]) {
-    const float mn = __builtin_bit_cast(float, w[0].x);
-    const float delta = __builtin_bit_cast(float, w[0].y);
-    const bool tail_lane = (h == 0) && (sub == 0);
-    const uint32_t sh = 16u * (uint32_t)sub;
-#pragma unroll
-    for (int p = 0; p < P; p++) {
-        const uint32_t dw[4] = {w[p].x, w[p].y, w[p].z, w[p].w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (p == 0 && j < 2) continue;  // header
-            const int e0 = 16 * p + 4 * j - 8;  // element index of byte 0 of this dword
-            const int c = e0 / 4;               // chunk dword number
-            bool is_chunk, is_tail;
-            if (DS > 0) {
-                constexpr int N4 = 4 * (DS / 8), RM = DS % 8;
-                is_chunk = e0 < N4;
-                is_tail = !is_chunk && e0 < N4 + RM;
-                if (!is_chunk && !is_tail) continue;
-            } else {
-                is_chunk = (uint32_t)e0 < nch4;
-                is_tail = !is_chunk && (uint32_t)e0 < nch4 + rem;
-            }
-            if (DS > 0 ? is_chunk : true) {
-                const uint32_t u = dw[j] >> sh;
-#pragma unroll
-                for (int kk = 0; kk < 2; kk++) {
-                    const float x = ((float)((u >> (8 * kk)) & 0xFFu) * delta) + mn;
-                    const float t = x - qc[2 * c + kk];
-                    const float t2 = t * t;
-                    acc[kk] += (DS > 0 || is_chunk) ? t2 : 0.0f;
-                }
-            }
-            if (DS > 0 ? is_tail : true) {
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int e = e0 + k;
-                    bool in;
-                    if (DS > 0) {
-                        constexpr int N4 = 4 * (DS / 8), RM = DS % 8;
-                        if (e >= N4 + RM) continue;
-                        in = true;
-                    } else {
-                        in = is_tail && (uint32_t)e < nch4 + rem;
-                    }
-                    const float x = ((float)((dw[j] >> (8 * k)) & 0xFFu) * delta) + mn;
-                    const int r = DS > 0 ? e - 4 * (DS / 8) : (in ? e - (int)nch4 : 0);
-                    const float t = x - qt[r];
-                    const float t2 = t * t;
-                    acc[0] += (in && tail_lane) ? t2 : 0.0f;
-                }
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Stage a STORED point as the query (build path: Point::dist2other between two stored points,
-// points/src/points.rs:86-93).  QUANT8: the packed row already is in the half-row element order, so
-// yq[h * nq_half + e] = code * delta + min straight from the row.  F32: the row's floats.
-// ---------------------------------------------------------------------------------------------
-template <int KIND>
-__device__ __forceinline__ void stage_row(const DevView &v, uint32_t id, float *yq, int lane) {
-    if (KIND == HNSW_VEC_QUANT8) {
-        const uint32_t nq_half = v.half_bytes - 8;
-        const uint8_t *row = v.rows + (size_t)id * v.row_stride;
-        for (uint32_t i = lane; i < 2 * nq_half; i += 64) {
-            const uint32_t hh = i >= nq_half ? 1u : 0u, e = i - hh * nq_half;
-            const uint8_t *half = row + hh * v.half_bytes;
-            const float mn = *reinterpret_cast<const float *>(half);
-            const float delta = *reinterpret_cast<const float *>(half + 4);
-            const bool used = e < v.nch4 || (hh == 0 && e < v.nch4 + v.rem);
-            yq[i] = used ? ((float)half[8 + e] * delta) + mn : 0.0f;
-        }
-    } else {
-        const float *row = reinterpret_cast<const float *>(v.rows + (size_t)id * v.row_stride);
-        for (uint32_t e = lane; e < v.dim; e += 64) yq[e] = row[e];
-    }
-    wave_fence();
-}
-
-// ---------------------------------------------------------------------------------------------
-// QUANT8, any dimension: the pieces of a half row that hold nothing but chunk elements, without
-// per-element predicates, in stages of CH 16-byte pieces through two register buffers (the next
-// stage in flight while the current one is summed).  Starts at piece `first` >= 1 (piece 0 carries the
-// header); returns the number of pieces consumed (a multiple of CH).  Element e of the half sits at
-// byte 8 + e.
-// ---------------------------------------------------------------------------------------------
-template <int CH>
-__device__ __forceinline__ uint32_t quant_bulk_stages(const uint4 *src, const float *yh, float delta, float mn,
-                                                      uint32_t first, uint32_t n_pure, float (&acc)[4]) {
-    const uint32_t nst = n_pure / CH;
-    if (nst == 0) return 0;
-    uint4 a[CH], b[CH];
-    auto fetch_at = [&](uint4 (&w)[CH], uint32_t st) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < CH; i++) w[i] = src[first + st * CH + i];
-    };
-    auto consume_at = [&](const uint4 (&w)[CH], uint32_t st) __attribute__((always_inline)) {
-        const float *y = yh + 16 * (first + st * CH) - 8;  // query value of the stage's first element
-#pragma unroll
-        for (int i = 0; i < CH; i++) {
-            const uint32_t dw[4] = {w[i].x, w[i].y, w[i].z, w[i].w};
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-#pragma unroll
-                for (int k = 0; k < 4; k += 2) {
-                    const f32x2 c = {(float)((dw[j] >> (8 * k)) & 0xFFu), (float)((dw[j] >> (8 * (k + 1))) & 0xFFu)};
-                    const f32x2 x = c * delta + mn;
-                    const f32x2 yy = {y[16 * i + 4 * j + k], y[16 * i + 4 * j + k + 1]};
-                    const f32x2 t = x - yy;
-                    const f32x2 t2 = t * t;
-                    acc[k] += t2.x;
-                    acc[k + 1] += t2.y;
-                }
-            }
-        }
-    };
-    fetch_at(a, 0);
-#pragma unroll 1
-    for (uint32_t st = 0; st < nst; st += 2) {
-        if (st + 1 < nst) fetch_at(b, st + 1);
-        consume_at(a, st);
-        if (st + 2 < nst) fetch_at(a, st + 2);
-        if (st + 1 < nst) consume_at(b, st + 1);
-    }
-    return nst * CH;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Distance of one stored point to the staged query for ANY dimension (runtime loops): used by
-// the test-seam and brute-force kernels, and by the search kernel when no specialised variant
-// fits.  QUANT8: valid on the even lane of the pair; F32: per lane.
-// ---------------------------------------------------------------------------------------------
-template <int KIND>
-__device__ __forceinline__ float dist_any_dim(const DevView &v, uint32_t id, bool active, int h,
-                                              const float *yq) {
-    if (KIND == HNSW_VEC_QUANT8) {
-        const float *yh = yq + h * (v.half_bytes - 8);
-        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (active) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(
-                v.rows + (size_t)id * v.row_stride + (size_t)h * v.half_bytes);
-            const uint32_t np = v.half_bytes >> 4;
-            const uint4 w0 = src[0];
-            const float mn = __builtin_bit_cast(float, w0.x);
-            const float delta = __builtin_bit_cast(float, w0.y);
-            // Pieces [p_lo, p_hi) through the predicated element loop, 4 pieces (64 B) per group.
-            auto consume_pred = [&](uint32_t p_lo, uint32_t p_hi) __attribute__((always_inline)) {
-                for (uint32_t p0 = p_lo; p0 < p_hi; p0 += 4) {
-                    uint4 w[4];
-#pragma unroll
-                    for (int p = 0; p < 4; p++)
-                        w[p] = (p0 + p < p_hi) ? src[p0 + p] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-                    for (int p = 0; p < 4; p++) {
-                        if (p0 + p >= p_hi) continue;  // wave-uniform: a piece outside the range costs nothing
-                        const uint32_t dw[4] = {w[p].x, w[p].y, w[p].z, w[p].w};
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-#pragma unroll
-                            for (int k = 0; k < 4; k++) {
-                                const int e = 16 * (int)(p0 + p) + 4 * j + k - 8;
-                                const float x = ((float)((dw[j] >> (8 * k)) & 0xFFu) * delta) + mn;
-                                const bool chunk = e >= 0 && (uint32_t)e < v.nch4;
-                                const bool tail = e >= 0 && !chunk &&
-                                                  (uint32_t)e < v.nch4 + v.rem && h == 0;
-                                const float y = (chunk || tail) ? yh[e] : 0.0f;
-                                const float t = x - y;
-                                const float t2 = t * t;
-                                if (k == 0) {
-                                    acc[0] += (chunk || tail) ? t2 : 0.0f;
-                                } else {
-                                    acc[k] += chunk ? t2 : 0.0f;
-                                    acc[0] += tail ? t2 : 0.0f;
-                                }
-                            }
-                        }
-                    }
-                }
-            };
-            // Pieces 1 .. that hold nothing but chunk elements go through the predicate-free stages
-            // (quant_bulk_stages); piece 0 (header) before, the remainder after -- every running sum
-            // still sees its elements in ascending order.
-            const uint32_t n_pure = v.nch4 >= 24 ? (v.nch4 - 8) / 16 : 0;  // pieces [1, 1 + n_pure)
-            if (n_pure < 4) {
-                consume_pred(0, np);
-            } else {
-                consume_pred(0, 1);
-                // widest stages first, then narrower ones over what is left of the pure pieces
-                uint32_t used = 0;
-                if (n_pure >= 16) used += quant_bulk_stages<8>(src, yh, delta, mn, 1, n_pure, acc);
-                used += quant_bulk_stages<4>(src, yh, delta, mn, 1 + used, n_pure - used, acc);
-                used += quant_bulk_stages<1>(src, yh, delta, mn, 1 + used, n_pure - used, acc);
-                consume_pred(1 + used, np);
-            }
-        }
-        // acc.iter().sum(): ((((((a0+a1)+a2)+a3)+a4)+a5)+a6)+a7 with a4..a7 on the odd lane
-        const float b0 = pair_swap(acc[0]), b1 = pair_swap(acc[1]), b2 = pair_swap(acc[2]),
-                    b3 = pair_swap(acc[3]);
-        float s = 0.0f;
-        s += acc[0];
-        s += acc[1];
-        s += acc[2];
-        s += acc[3];
-        s += b0;
-        s += b1;
-        s += b2;
-        s += b3;
-        return __builtin_sqrtf(s);
-    } else {
-        // FullVec: one sequential sum per candidate, one candidate per lane (full.rs:24-28)
-        float s = 0.0f;
-        if (active) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(v.rows + (size_t)id * v.row_stride);
-            const uint32_t np = v.row_stride >> 4, d = v.dim;
-            // bulk: whole pairs of 16-piece stages, two register buffers, the next stage in flight
-            // while the current one is summed (one exposed round trip per 512 B instead of per 128 B);
-            // only pieces that lie entirely inside the row's d floats take this path
-            constexpr uint32_t CH = 16;
-            const uint32_t full_pieces = d >> 2;                      // pieces without padding floats
-            const uint32_t pairs = full_pieces / (2 * CH);
-            uint32_t p_done = 0;
-            if (pairs > 0) {
-                uint4 a[CH], b[CH];
-                auto fetch_at = [&](uint4 (&w)[CH], const uint4 *p) __attribute__((always_inline)) {
-#pragma unroll
-                    for (uint32_t i = 0; i < CH; i++) w[i] = p[i];
-                };
-                auto consume_at = [&](const uint4 (&w)[CH], const float *y) __attribute__((always_inline)) {
-#pragma unroll
-                    for (uint32_t i = 0; i < CH; i++) {
-                        const uint32_t dw[4] = {w[i].x, w[i].y, w[i].z, w[i].w};
-#pragma unroll
-                        for (int j = 0; j < 4; j += 2) {
-                            const f32x2 x = {__builtin_bit_cast(float, dw[j]), __builtin_bit_cast(float, dw[j + 1])};
-                            const f32x2 yy = {y[4 * i + j], y[4 * i + j + 1]};
-                            const f32x2 t = x - yy;
-                            const f32x2 t2 = t * t;
-                            s += t2.x;
-                            s += t2.y;
-                        }
-                    }
-                };
-                fetch_at(a, src);
-#pragma unroll 1
-                for (uint32_t pr = 0; pr < pairs; pr++) {
-                    const uint32_t st = 2 * pr;
-                    fetch_at(b, src + (st + 1) * CH);
-                    consume_at(a, yq + 4 * st * CH);
-                    if (pr + 1 < pairs) fetch_at(a, src + (st + 2) * CH);
-                    consume_at(b, yq + 4 * (st + 1) * CH);
-                }
-                p_done = pairs * 2 * CH;
-            }
-            for (uint32_t p0 = p_done; p0 < np; p0 += 8) {
-                uint4 w[8];
-#pragma unroll
-                for (int p = 0; p < 8; p++)
-                    w[p] = (p0 + p < np) ? src[p0 + p] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-                for (int p = 0; p < 8; p++) {
-                    const uint32_t dw[4] = {w[p].x, w[p].y, w[p].z, w[p].w};
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const uint32_t e = 4 * (p0 + p) + j;
-                        const bool in = e < d;
-                        const float y = in ? yq[e] : 0.0f;
-                        const float t = __builtin_bit_cast(float, dw[j]) - y;
-                        const float t2 = t * t;
-                        s += in ? t2 : 0.0f;  // +0.0 leaves a non-negative sum unchanged
-                    }
-                }
-            }
-        }
-        return __builtin_sqrtf(s);
-    }
-}
-
-// Asynchronous global -> LDS copy of one 1-KiB piece (64 lanes x 16 bytes): lane l's 16 bytes at
-// `gsrc` land at LDS byte address lds_dst + 16 l.  No VGPR destination, and -- being inline asm --
-// not part of the compiler's s_waitcnt bookkeeping, so the copy stays in flight across the loops
-// and LDS atomics of the expansion body (hipcc drains vmcnt(0) at every loop it cannot see
-// through).  The consumer issues its own `s_waitcnt vmcnt(0)` before reading the bytes back
-// (cdna_hip_programming.md section 5.7: M0 is written in the same statement that reads it).
-__device__ __forceinline__ void dma_piece_to_lds(const void *gsrc, uint32_t lds_dst) {
-    lds_dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_dst);  // provably wave-uniform
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst)
-        : "memory");
-}
-
-// Loads that the compiler's s_waitcnt bookkeeping does not see, each with its own wait.  They serve
-// the rare degree > 32 rows inside the inline-rows loops: a single compiler-visible VMEM load
-// anywhere in that loop nest makes hipcc drain vmcnt(0) at the loop header on EVERY iteration,
-// which would serialise the block prefetch (measured: the prefetch then gains nothing).
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint32_t asm_ld32(const void *p) {
-    uint32_t r;
-    asm volatile("global_load_dword %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=&v"(r) : "v"(p) : "memory");
-    return r;
-}
-__device__ __forceinline__ uint4 asm_ld128(const void *p) {
-    u32x4 r;
-    asm volatile("global_load_dwordx4 %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=&v"(r) : "v"(p) : "memory");
-    return make_uint4(r.x, r.y, r.z, r.w);
-}
-
-// FullVec row against the staged query when the dimension is a compile-time constant: all P
-// 16-byte pieces of the row are loaded up front (P x 16 bytes in flight per lane), the sum is the
-// reference's single left-to-right chain (full.rs:24-28).
-template <int P, int DS>
-__device__ __forceinline__ float f32_row_sum(const uint4 (&w)[P], const float *yq) {
-    // x - y and the square run two elements per instruction (v_pk_add_f32 / v_pk_mul_f32: each
-    // element is the same correctly rounded IEEE operation); the sum stays the one serial chain
-    float s = 0.0f;
-#pragma unroll
-    for (int p = 0; p < P; p++) {
-        const uint32_t dw[4] = {w[p].x, w[p].y, w[p].z, w[p].w};
-#pragma unroll
-        for (int j = 0; j < 4; j += 2) {
-            const int e = 4 * p + j;
-            if (e >= DS) continue;
-            if (e + 1 < DS) {
-                const f32x2 x = {__builtin_bit_cast(float, dw[j]), __builtin_bit_cast(float, dw[j + 1])};
-                const f32x2 y = {yq[e], yq[e + 1]};
-                const f32x2 t = x - y;
-                const f32x2 t2 = t * t;
-                s += t2.x;
-                s += t2.y;
-            } else {
-                const float t = __builtin_bit_cast(float, dw[j]) - yq[e];
-                s += t * t;
-            }
-        }
-    }
-    return s;
-}
-
-// Wide f32 rows (d > 192): the same single chain, with the row streamed through two register buffers
-// of CH 16-byte pieces each.  The stage loop has a compile-time trip count and is fully unrolled, so
-// the code is straight-line: the loads of stage s + 1 are in flight while stage s is summed and the
-// compiler's s_waitcnt counts are exact (a rolled loop drains them at its header).
-#ifndef HX_WIDE_CH
-#define HX_WIDE_CH 16  // 16-byte pieces per stage buffer of the wide-row loop (two buffers in flight per lane)
-#endif
-template <int DS, int CH, bool ROLLED>
-__device__ __forceinline__ float f32_row_sum_staged(const uint4 *src, const float *yq) {
-    constexpr int NP = (DS + 3) / 4, NST = (NP + CH - 1) / CH;
-    static_assert(!ROLLED || (NP % (2 * CH) == 0), "the rolled form needs whole stage pairs");
-    uint4 a[CH], b[CH];
-    float s = 0.0f;
-    auto fetch = [&](uint4 (&w)[CH], int st) __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < CH; p++)
-            if (st * CH + p < NP) w[p] = src[st * CH + p];
-    };
-    auto consume = [&](const uint4 (&w)[CH], int st) __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < CH; p++) {
-            if (st * CH + p >= NP) continue;
-            const uint32_t dw[4] = {w[p].x, w[p].y, w[p].z, w[p].w};
-#pragma unroll
-            for (int j = 0; j < 4; j += 2) {
-                const int e = 4 * (st * CH + p) + j;
-                if (e >= DS) continue;
-                if (e + 1 < DS) {
-                    const f32x2 x = {__builtin_bit_cast(float, dw[j]), __builtin_bit_cast(float, dw[j + 1])};
-                    const f32x2 y = {yq[e], yq[e + 1]};
-                    const f32x2 t = x - y;
-                    const f32x2 t2 = t * t;
-                    s += t2.x;
-                    s += t2.y;
-                } else {
-                    const float t = __builtin_bit_cast(float, dw[j]) - yq[e];
-                    s += t * t;
-                }
-            }
-        }
-    };
-    if constexpr (ROLLED) {
-        // very wide rows: the unrolled form outgrows the instruction cache (d = 768: 3.9 ms against
-        // 1.9 ms for the plain loop), so the stage pairs stay a loop -- one exposed round trip per
-        // 2 CH pieces instead of one per 8
-        auto fetch_at = [&](uint4 (&w)[CH], const uint4 *p) __attribute__((always_inline)) {
-#pragma unroll
-            for (int i = 0; i < CH; i++) w[i] = p[i];
-        };
-        auto consume_at = [&](const uint4 (&w)[CH], const float *y) __attribute__((always_inline)) {
-#pragma unroll
-            for (int i = 0; i < CH; i++) {
-                const uint32_t dw[4] = {w[i].x, w[i].y, w[i].z, w[i].w};
-#pragma unroll
-                for (int j = 0; j < 4; j += 2) {
-                    const f32x2 x = {__builtin_bit_cast(float, dw[j]), __builtin_bit_cast(float, dw[j + 1])};
-                    const f32x2 yy = {y[4 * i + j], y[4 * i + j + 1]};
-                    const f32x2 t = x - yy;
-                    const f32x2 t2 = t * t;
-                    s += t2.x;
-                    s += t2.y;
-                }
-            }
-        };
-        static_assert(DS % 4 == 0, "whole pieces");
-        fetch_at(a, src);
-#pragma unroll 1
-        for (int st = 0; st < NST; st += 2) {
-            fetch_at(b, src + (st + 1) * CH);
-            consume_at(a, yq + 4 * st * CH);
-            if (st + 2 < NST) fetch_at(a, src + (st + 2) * CH);
-            consume_at(b, yq + 4 * (st + 1) * CH);
-        }
-        return s;
-    }
-    fetch(a, 0);
-#pragma unroll
-    for (int st = 0; st < NST; st += 2) {
-        if (st + 1 < NST) fetch(b, st + 1);
-        consume(a, st);
-        if (st + 2 < NST) fetch(a, st + 2);
-        if (st + 1 < NST) consume(b, st + 1);
-    }
-    return s;
-}
-
-#include "coop_rows.inc"
-
-// ---------------------------------------------------------------------------------------------
-// Distance of a stored point to the staged row on the build path.  DS > 0: the dimension is a
-// compile-time constant (all row pieces in flight, dead elements vanish), otherwise the runtime
-// loops of dist_any_dim.  QUANT8: valid on the even lane of the pair; F32: per lane.
-// ---------------------------------------------------------------------------------------------
-// COOP (insert kernel, f32 rows of whole lines): the cooperative gather of coop_rows.inc through ids_s
-// (64 words) and img (4 KiB) -- the insertion searches of a 50-100M point build read rows scattered over
-// tens of GB, where the lane-per-row shape tops out at 1.2 TB/s (profiles/r03_gather_shapes_*.txt).
-template <int KIND, int DS, bool COOP = false>
-__device__ __forceinline__ float dist_build(const DevView &v, uint32_t id, bool active, int h, const float *yq,
-                                            uint32_t *ids_s = nullptr, unsigned char *img = nullptr, int lane = 0) {
-    if constexpr (COOP && coop_rows<KIND, DS>()) {
-        return __builtin_sqrtf(f32_rows_coop<(DS > 0 ? DS : 32), HX_COOP_K>(v.rows, id, active, yq, ids_s, img, lane));
-    } else if constexpr (DS > 0 && KIND == HNSW_VEC_QUANT8) {
-        constexpr int NQ = 4 * (DS / 8) + DS % 8;  // elements of half 0 (half 1 has DS % 8 fewer)
-        constexpr int P = (8 + NQ + 15) / 16;
-        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (active) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(
-                v.rows + (size_t)id * v.row_stride + (size_t)h * v.half_bytes);
-            uint4 w[P];
-#pragma unroll
-            for (int p = 0; p < P; p++) w[p] = src[p];
-            __builtin_amdgcn_sched_barrier(0);  // every piece requested before the arithmetic
-            const QLds q{yq + h * (v.half_bytes - 8)};
-            quant_half_sums<P, DS>(w, q, h, v.nch4, v.rem, acc);
-        }
-        const float b0 = pair_swap(acc[0]), b1 = pair_swap(acc[1]), b2 = pair_swap(acc[2]),
-                    b3 = pair_swap(acc[3]);
-        float s = 0.0f;
-        s += acc[0];
-        s += acc[1];
-        s += acc[2];
-        s += acc[3];
-        s += b0;
-        s += b1;
-        s += b2;
-        s += b3;
-        return __builtin_sqrtf(s);
-    } else if constexpr (DS > 0 && KIND == HNSW_VEC_F32) {
-        constexpr int P = (DS + 3) / 4;
-        float sm = 0.0f;
-        if (active) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(v.rows + (size_t)id * v.row_stride);
-            uint4 w[P];
-#pragma unroll
-            for (int p = 0; p < P; p++) w[p] = src[p];
-            __builtin_amdgcn_sched_barrier(0);
-            sm = f32_row_sum<P, DS>(w, yq);
-        }
-        return __builtin_sqrtf(sm);
-    } else {
-        return dist_any_dim<KIND>(v, id, active, h, yq);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Per-wave search state and the pieces of search_layer
-// ---------------------------------------------------------------------------------------------
-template <int R>
-struct WaveList {
-    u64 L[R];         // list[64 r + lane]; KEY_INVALID beyond n_cur
-    uint32_t n_cur;   // wave-uniform
-    u64 last_key;     // key (flag dropped) of position ef - 1 when the list is full
-
-    // Merge the wave's candidate keys (KEY_INVALID = none) into the sorted list, keeping the ef
-    // smallest: streaming top-ef of searcher.rs:74-94 for a whole batch (order-independent).
-    // new_flag (0 or KEY_EXPANDED) is OR-ed into every key that enters the list
-    __device__ __forceinline__ void merge(u64 key, uint32_t ef, u64 *perm, int lane, u64 new_flag = 0) {
-        const bool full = n_cur >= ef;
-        const bool surv = key != KEY_INVALID && (!full || key < last_key);
-        u64 smask = __ballot(surv);
-        if (smask == 0) return;
-        const uint32_t m = (uint32_t)__popcll(smask);
-        if (m <= (R == 1 ? 4u : 0u)) {
-            // few survivors (the usual case once the list is full): insert them one at a time by
-            // shifting the tail of the register-resident list one lane to the right (DPP
-            // wave_shr:1, no LDS round trip).  Insertion order is irrelevant (N2).  Only for one-
-            // register lists: with R > 1 every insert shifts R registers with a carry, and the
-            // rank-scatter below is cheaper even for a single survivor (f32 efSearch 68: 0.266 ->
-            // 0.255 ms; SQ counters had shown +33 % VALU instructions per query for R = 2 vs R = 1).
-            u64 it = smask;
-            while (it) {
-                const int j = __ffsll((long long)it) - 1;
-                it &= it - 1;
-                const u64 e = readlane64(key, j);
-                if (n_cur >= ef && !(e < last_key)) continue;  // an earlier insert tightened the bound
-                uint32_t pos = 0;
-#pragma unroll
-                for (int r = 0; r < R; r++)
-                    pos += (uint32_t)__popcll(__ballot((L[r] & KEY_MASK) < e));
-                u64 carry = 0;  // lane 63 of the previous register feeds lane 0 of the next
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    const uint32_t idx = 64u * r + lane;
-                    const uint32_t lo = (uint32_t)L[r], hi = (uint32_t)(L[r] >> 32);
-                    uint32_t slo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lo, 0x138, 0xF, 0xF, false);
-                    uint32_t shi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi, 0x138, 0xF, 0xF, false);
-                    u64 sh = ((u64)shi << 32) | slo;
-                    if (lane == 0) sh = carry;
-                    if (R > 1) carry = readlane64(L[r], 63);
-                    if (idx == pos)
-                        L[r] = e | new_flag;
-                    else if (idx > pos)
-                        L[r] = sh;
-                }
-                n_cur = min(n_cur + 1, ef);
-#pragma unroll
-                for (int r = 0; r < R; r++)
-                    if (64u * r + lane >= n_cur) L[r] = KEY_INVALID;
-                refresh_last(ef);
-            }
-            return;
-        }
-        uint32_t shift[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) shift[r] = 0;
-        uint32_t my_rank = 0;
-        u64 it = smask;
-        while (it) {  // wave-uniform loop over the survivors
-            const int j = __ffsll((long long)it) - 1;
-            it &= it - 1;
-            const u64 e = readlane64(key, j);
-            uint32_t below = 0;  // list entries smaller than e
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const bool lt = (L[r] & KEY_MASK) < e;  // invalid entries are the maximum
-                below += (uint32_t)__popcll(__ballot(lt));
-                shift[r] += lt ? 0u : 1u;
-            }
-            if (surv && e < key) my_rank++;
-            if (lane == j) my_rank += below;
-        }
-        // scatter to the new positions through LDS (all reads of L happened above)
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t idx = 64u * r + lane;
-            const uint32_t np = idx + shift[r];
-            if (idx < n_cur && np < ef) perm[np] = L[r];
-        }
-        if (surv && my_rank < ef) perm[my_rank] = key | new_flag;
-        n_cur = min(n_cur + m, ef);
-        wave_fence();  // single-wave workgroup: orders the LDS writes before the reads
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t idx = 64u * r + lane;
-            L[r] = idx < n_cur ? perm[idx] : KEY_INVALID;
-        }
-        wave_fence();
-        refresh_last(ef);
-    }
-
-    __device__ __forceinline__ void refresh_last(uint32_t ef) {
-        if (n_cur >= ef) {
-            const uint32_t pos = ef - 1;
-            u64 k = 0;
-#pragma unroll
-            for (int r = 0; r < R; r++)
-                if ((pos >> 6) == (uint32_t)r) k = readlane64(L[r], pos & 63);
-            last_key = k & KEY_MASK;
-        } else {
-            last_key = KEY_INVALID;
-        }
-    }
-
-    // position of the smallest entry not expanded yet, -1 if none (the loop of searcher.rs:35)
-    __device__ __forceinline__ int first_unexpanded(int lane) const {
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t idx = 64u * r + lane;
-            const u64 mk = __ballot(idx < n_cur && (L[r] & KEY_EXPANDED) == 0);
-            if (mk) return 64 * r + (__ffsll((long long)mk) - 1);
-        }
-        return -1;
-    }
-};
-
-// merge over the first RR registers of a wider list (every entry at 64 RR and beyond is invalid before and after)
-template <int RR, int R>
-__device__ __forceinline__ void merge_prefix(WaveList<R> &wl, u64 key, uint32_t ef, u64 *perm, int lane, u64 new_flag) {
-    static_assert(RR <= R, "prefix of the list");
-    WaveList<RR> t;
-#pragma unroll
-    for (int r = 0; r < RR; r++) t.L[r] = wl.L[r];
-    t.n_cur = wl.n_cur;
-    t.last_key = wl.last_key;
-    t.merge(key, ef, perm, lane, new_flag);
-#pragma unroll
-    for (int r = 0; r < RR; r++) wl.L[r] = t.L[r];
-    wl.n_cur = t.n_cur;
-    wl.last_key = t.last_key;
-}
-
-// LDS visited table (IntSet::insert, results.rs:101-103): open addressing over BUCKETS of four
-// 32-bit slots.  One ds_read_b128 fetches the home bucket, the four compares run in registers and
-// a single ds_cmpst claims the first empty slot, so an insert is two LDS round trips whatever the
-// load; the classic one-slot linear probe needed one round trip per probe and the wave iterated as
-// long as its unluckiest lane (4-5 rounds at 30 % load).  Slots fill left to right and never empty,
-// ids within one adjacency row are distinct, so "absent from the bucket, first empty slot claimed"
-// is an exact insert.  Returns true when id was not present.
-// read-only membership test of the same table (speculative evaluation: nothing may be inserted yet)
-__device__ __forceinline__ bool visited_contains(const uint32_t *tab, uint32_t hmask, uint32_t slots_log2,
-                                                 uint32_t id) {
-    const uint32_t bmask = hmask >> 2;
-    uint32_t b = (id * 0x9E3779B1u) >> (32 - (slots_log2 - 2));
-    while (true) {
-        const uint4 bk = *reinterpret_cast<const uint4 *>(tab + 4 * b);
-        if (bk.x == id || bk.y == id || bk.z == id || bk.w == id) return true;
-        if (bk.x == HX_EMPTY_SLOT || bk.y == HX_EMPTY_SLOT || bk.z == HX_EMPTY_SLOT || bk.w == HX_EMPTY_SLOT)
-            return false;
-        b = (b + 1) & bmask;
-    }
-}
-
-__device__ __forceinline__ bool visited_insert(uint32_t *tab, uint32_t hmask, uint32_t slots_log2,
-                                               uint32_t id) {
-    const uint32_t bmask = hmask >> 2;
-    uint32_t b = (id * 0x9E3779B1u) >> (32 - (slots_log2 - 2));
-    while (true) {
-        const uint4 bk = *reinterpret_cast<const uint4 *>(tab + 4 * b);
-        if (bk.x == id || bk.y == id || bk.z == id || bk.w == id) return false;
-        int j = -1;
-        if (bk.x == HX_EMPTY_SLOT)
-            j = 0;
-        else if (bk.y == HX_EMPTY_SLOT)
-            j = 1;
-        else if (bk.z == HX_EMPTY_SLOT)
-            j = 2;
-        else if (bk.w == HX_EMPTY_SLOT)
-            j = 3;
-        if (j < 0) {
-            b = (b + 1) & bmask;  // bucket full: next bucket
-            continue;
-        }
-        const uint32_t old = atomicCAS(&tab[4 * b + j], HX_EMPTY_SLOT, id);
-        if (old == HX_EMPTY_SLOT) return true;
-        // another lane of this wave took that slot in the same round: look at the bucket again
-    }
-}
 
 // bytes of the region the merge buffer shares with the cooperative gather's image (4 KiB + 64 rank words)
 template <int KIND, int DS, int R>
@@ -795,7 +95,7 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
     }
     const uint32_t vis_limit = lds_limit + (gtab != nullptr ? (gmask + 1) / 2 : 0u);
     // FAT: two 64 x 16 x P byte buffers for the prefetched block (after yq, 16-byte aligned)
-    const uint32_t yq_bytes =
+    const uint32_t yq_bytes =  // == query_lds_bytes(v) (launch.h), KIND being v.kind: the launcher reserves that
         ((KIND == HNSW_VEC_QUANT8 ? 2u * (v.half_bytes - 8) * 4u : v.dim * 4u) + 15u) & ~15u;
     unsigned char *spec_buf = reinterpret_cast<unsigned char *>(yq) + yq_bytes;
     const uint32_t spec_lds = __builtin_amdgcn_groupstaticsize() + 4u * hslots + PERM_BYTES + yq_bytes;
@@ -1472,7 +772,7 @@ hx_search2_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2
     const uint32_t q = a.qsel ? a.qsel[blockIdx.x] : blockIdx.x;
     const uint32_t hslots = 1u << slots_log2, hmask = hslots - 1;
     const uint32_t vis_limit = hslots - (hslots >> 2);
-    const uint32_t yq_bytes = ((2u * (v.half_bytes - 8) * 4u) + 15u) & ~15u;
+    const uint32_t yq_bytes = ((2u * (v.half_bytes - 8) * 4u) + 15u) & ~15u;  // == query_lds_bytes(v) (launch.h) for QUANT8
     constexpr uint32_t HALF_BLK = 16u * 32u * P;  // bytes of one wave's half block (16 rows)
     // LDS carve (all dynamic): visited table | per-wave perm | exchange | per-wave yq | per-wave images
     uint32_t off = 0;
@@ -1970,862 +1270,6 @@ hx_search2_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2
     }
 }
 
-// =============================================================================================
-// On-device insertion search (HNSW::insert's first half: Inserter::build_insertion_results,
-// hnsw/src/template/inserter.rs:40-126) for a BATCH of already stored points against the current
-// HBM graph, one wave per point:
-//   setup_insert            selected = {(ep, d(ep, p))}                      inserter.rs:53-68
-//   traverse_layers_above   search_layer(ef = 1) for layers > p.level       inserter.rs:70-89
-//   traverse_layers_below   per layer l <= p.level: search_layer(ef_cons), select_heuristic(m,
-//                           extend_cands = keep_pruned = true), save, and the selection seeds the
-//                           next layer                                       inserter.rs:91-126
-// The graph is read-only during a launch: points of one batch do not see each other (the reference's
-// multi-threaded insert_bulk is racy in the same way, template.rs:403-440), so a graph built this
-// way is judged by recall, not by identity with the sequential build.  Deviations, all documented
-// in DESIGN.md: the heuristic's candidate set is capped at the 512 nearest (the reference keeps
-// all of selected ∪ their neighbours); the un-popped heuristic candidates do not leak into the
-// next layer's frontier.  The edges themselves are applied by hx_connect_kernel /
-// hx_remove_kernel below from the edge records this kernel files (or, in the hybrid build, on the host
-// with the reference's make_connections / prune_connections / make_pruned_connections).
-// =============================================================================================
-template <int KIND, int DS>
-__global__ void __launch_bounds__(64)
-hx_insert_kernel(const DevView v, const InsertArgs a, const uint32_t slots_log2) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int R = HX_MAX_R;  // list capacity 512: the heuristic's candidate set lives in it
-    const int lane = threadIdx.x;
-    const uint32_t b = blockIdx.x;
-    const uint32_t p = a.point_ids[b];
-    uint32_t *htab = reinterpret_cast<uint32_t *>(smem);
-    const uint32_t hslots = 1u << slots_log2, hmask = hslots - 1;
-    const uint32_t vis_limit = hslots - (hslots >> 2);
-    u64 *perm = reinterpret_cast<u64 *>(smem + 4ull * hslots);
-    u64 *selk = perm + 64 * R;                                   // [128] selected keys (m <= 128)
-    const uint32_t yq_bytes =
-        ((KIND == HNSW_VEC_QUANT8 ? 2u * (v.half_bytes - 8) * 4u : v.dim * 4u) + 15u) & ~15u;
-    float *yq = reinterpret_cast<float *>(selk + 128);
-    float *yqe = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(yq) + yq_bytes);
-    // cooperative row gather (f32 rows of whole lines): the stage image lives in perm (4 KiB, used by the
-    // merges only, never during a distance pass), the rank -> id words behind the staged rows
-    unsigned char *coop_img = reinterpret_cast<unsigned char *>(perm);
-    uint32_t *coop_ids = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(yqe) + yq_bytes);
-    static_assert(!coop_rows<KIND, DS>() || 64 * R * 8 >= (int)HX_COOP_IMG_BYTES, "perm holds the stage image");
-
-    constexpr int LPC = (KIND == HNSW_VEC_QUANT8) ? 2 : 1;
-    constexpr int CHUNK = 64 / LPC;
-    const int h = (LPC == 2) ? (lane & 1) : 0;
-    const int cslot = lane / LPC;
-    const bool first = (LPC == 1) || (h == 0);
-    int32_t status = HNSW_OK;
-    uint32_t n_vis = 0;
-    // what this point's insertion reads (wave-uniform; summed into a.counters at the end): vector rows
-    // (distance evaluations + staged rows), adjacency rows and the ids in them -- the build's algorithmic bytes
-    uint32_t c_rows = 1, c_adj = 0, c_ids = 0;
-
-    const uint32_t level = min((uint32_t)a.levels[p], v.nb_layers - 1);
-    const uint32_t m = a.m, ef_cons = max(1u, a.ef_cons);
-    // outputs of this point: [max_layers][m], padded
-    uint32_t *o_ids = a.out_ids + (size_t)b * a.max_layers * m;
-    float *o_d = a.out_dists + (size_t)b * a.max_layers * m;
-    for (uint32_t i = lane; i < a.max_layers * m; i += 64) {
-        o_ids[i] = HX_EMPTY_SLOT;
-        o_d[i] = __builtin_inff();
-    }
-
-    stage_row<KIND>(v, p, yq, lane);
-
-    WaveList<R> wl;
-#pragma unroll
-    for (int r = 0; r < R; r++) wl.L[r] = KEY_INVALID;
-    wl.n_cur = 0;
-    wl.last_key = KEY_INVALID;
-
-    // one pass over up to CHUNK ids: optional visited filter, distance to the staged row, merge
-    auto process = [&](uint32_t id, bool valid, bool visit, uint32_t ef_l, u64 new_flag) __attribute__((always_inline)) {
-        bool fresh = valid;
-        if (visit) {
-            bool f = false;
-            if (valid && first) f = visited_insert(htab, hmask, slots_log2, id);
-            if (LPC == 2) f = (pair_swap_i(f ? 1 : 0) | (f ? 1 : 0)) != 0;
-            fresh = f;
-        }
-        const u64 fm = __ballot(fresh && first);
-        if (visit) n_vis += (uint32_t)__popcll(fm);  // what the table really holds
-        if (fm == 0) return;
-        c_rows += (uint32_t)__popcll(fm);
-        const float dist = dist_build<KIND, DS, true>(v, id, fresh, h, yq, coop_ids, coop_img, lane);
-        u64 key = KEY_INVALID;
-        bool nan = false;
-        if (fresh && first) {
-            nan = dist != dist;
-            if (!nan) key = ((u64)__builtin_bit_cast(uint32_t, dist) << 32) | id;
-        }
-        if (__ballot(nan)) status = HNSW_ERR_NAN_INPUT;
-        // The list has eight registers for the heuristic's 512 candidates, and a merge pays its rank / scatter
-        // work per register.  Entries beyond min(n_cur + batch, ef) cannot exist before or after this merge, so it
-        // runs over the registers that can hold something: one for the searches (ef = 1 above the point's level,
-        // ef_cons <= 64 below), two or four while the candidate set is filling.
-        const uint32_t reach = min(wl.n_cur + (uint32_t)__popcll(fm), ef_l);
-        if (reach <= 64u)
-            merge_prefix<1>(wl, key, ef_l, perm, lane, new_flag);
-        else if (reach <= 128u)
-            merge_prefix<2>(wl, key, ef_l, perm, lane, new_flag);
-        else if (reach <= 256u)
-            merge_prefix<4>(wl, key, ef_l, perm, lane, new_flag);
-        else
-            wl.merge(key, ef_l, perm, lane, new_flag);
-    };
-    // expand every unexpanded entry of the list on `layer` (search_layer's loop, searcher.rs:35-95)
-    auto expand_all = [&](int layer, uint32_t ef_l, u64 new_flag) __attribute__((always_inline)) {
-        const uint32_t S = layer == 0 ? v.S0 : v.S1;
-        // the entry at cpos: marked expanded, its id returned
-        auto take = [&](int cpos) __attribute__((always_inline)) -> uint32_t {
-            uint32_t cid = 0;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                if ((cpos >> 6) == r) {
-                    cid = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)wl.L[r], cpos & 63);
-                    if (lane == (cpos & 63)) wl.L[r] |= KEY_EXPANDED;
-                }
-            }
-            return cid;
-        };
-        auto row_of = [&](uint32_t cid) __attribute__((always_inline)) -> const uint32_t * {
-            if (layer == 0) return v.adj0 + (size_t)cid * S;
-            const uint32_t ub = v.upper_base[cid];
-            if (ub == HX_EMPTY_SLOT) {
-                status = HNSW_ERR_NODE_NOT_IN_GRAPH;
-                return nullptr;
-            }
-            return v.adj_up + ((size_t)ub + layer - 1) * S;
-        };
-        // The heuristic's extension (new entries are born expanded) expands a FIXED set -- the entries the search
-        // left -- and keeps the union of their neighbours: the order does not matter, so with one lane per row
-        // (f32) and rows of up to 32 slots TWO entries go through one pass, one per half wave, instead of
-        // leaving the upper half idle (the visited insert settles an id both rows hold).
-        const bool two = LPC == 1 && new_flag != 0 && S <= 32;
-        while (status == HNSW_OK) {
-            const int cpos = wl.first_unexpanded(lane);
-            if (cpos < 0) break;
-            const uint32_t cid = take(cpos);
-            const uint32_t *row = row_of(cid);
-            if (row == nullptr) break;
-            c_adj++;
-            if (two) {
-                const int cpos2 = wl.first_unexpanded(lane);
-                const uint32_t *row2 = nullptr;
-                if (cpos2 >= 0) {
-                    row2 = row_of(take(cpos2));
-                    if (row2 == nullptr) break;
-                    c_adj++;
-                }
-                const bool upper = lane >= 32;
-                const uint32_t slot = (uint32_t)lane & 31u;
-                uint32_t nb = HX_EMPTY_SLOT;
-                if (slot < S && (!upper || row2 != nullptr)) nb = (upper ? row2 : row)[slot];
-                const bool valid = nb != HX_EMPTY_SLOT && !(nb & HX_OVF_FLAG) && nb != p;
-                const uint32_t cnt = (uint32_t)__popcll(__ballot(valid));
-                c_ids += cnt;
-                if (cnt == 0) continue;
-                if (n_vis + cnt > vis_limit) {
-                    status = HNSW_ERR_OVERFLOW;
-                    break;
-                }
-                process(nb, valid, true, ef_l, new_flag);
-                continue;
-            }
-            for (uint32_t c0 = 0; c0 < S && status == HNSW_OK; c0 += CHUNK) {
-                const uint32_t slot = c0 + cslot;
-                uint32_t nb = HX_EMPTY_SLOT;
-                if (slot < S) nb = row[slot];
-                // during a build the device rows never carry overflow pointers (rows are truncated
-                // to the stride when they are scattered); a flagged id is skipped
-                const bool valid = nb != HX_EMPTY_SLOT && !(nb & HX_OVF_FLAG) && nb != p;
-                const uint32_t cnt = (uint32_t)__popcll(__ballot(valid && first));
-                c_ids += cnt;
-                if (cnt == 0) continue;
-                if (n_vis + cnt > vis_limit) {
-                    status = HNSW_ERR_OVERFLOW;
-                    break;
-                }
-                process(nb, valid, true, ef_l, new_flag);
-            }
-        }
-    };
-    // start a layer: visited.clear(), candidates ∪= selected, visited ∪= ids(selected)
-    auto begin_layer = [&](uint32_t ef_l) __attribute__((always_inline)) {
-        for (uint32_t s = lane; s < (hslots >> 2); s += 64)
-            reinterpret_cast<uint4 *>(htab)[s] =
-                make_uint4(HX_EMPTY_SLOT, HX_EMPTY_SLOT, HX_EMPTY_SLOT, HX_EMPTY_SLOT);
-        wave_fence();
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            if (64u * r + lane < wl.n_cur) {
-                wl.L[r] &= KEY_MASK;
-                visited_insert(htab, hmask, slots_log2, (uint32_t)wl.L[r]);
-            }
-        }
-        n_vis = wl.n_cur;
-        wl.refresh_last(ef_l);
-    };
-
-    if (p == v.ep || p >= v.n_points) status = HNSW_ERR_ARG;  // the host never sends the entry point
-    if (status == HNSW_OK) process(v.ep, lane < LPC, false, 1u, 0);  // setup_insert
-
-    for (int layer = (int)v.nb_layers - 1; status == HNSW_OK && layer >= 0; layer--) {
-        if ((uint32_t)layer > level) {  // traverse_layers_above
-            begin_layer(1u);
-            expand_all(layer, 1u, 0);
-            continue;
-        }
-        // ---- search_layer(ef_cons) ----
-        begin_layer(ef_cons);
-        expand_all(layer, ef_cons, 0);
-        if (status != HNSW_OK) break;
-        // ---- select_heuristic: candidates = selected ∪ neighbours(selected), distances to p
-        // (results.rs:105-146).  Every current entry is expanded once more, this time keeping ALL
-        // distinct neighbours (cap 512 nearest); entries that arrive now are born expanded.
-        begin_layer(64u * R);
-        expand_all(layer, 64u * R, KEY_EXPANDED);
-        if (status != HNSW_OK) break;
-        // The reference pops the candidates in ascending order and accepts e iff (d(e,p), e) <
-        // (d(e,s), s) for every s selected so far (searcher.rs:128-139).  Equivalent, and parallel:
-        // whenever a candidate s is selected, every LATER candidate e with (d(s,e), s) < (d(e,p), e)
-        // is marked rejected (d is bit-symmetric); the next selection is the first unmarked one.
-        // Each round stages s once and evaluates up to 64 / LPC candidates per pass.
-        const uint32_t n_c = wl.n_cur;
-        uint32_t ns = 0;
-        uint32_t selbits = 0;  // bit r: the candidate at position 64 r + lane was selected
-#pragma unroll
-        for (int r = 0; r < R; r++) wl.L[r] &= KEY_MASK;  // the flag now means "rejected"
-        uint32_t cursor = 0;
-        // One sweep: the staged selected point (yqe, id sid) against the open candidates at positions [lo, hi):
-        // those it dominates -- (d(s, e), s) < (d(e, p), e) -- are marked rejected.
-        // (a rolled loop over the list registers with static selects: one copy of the distance
-        // code instead of R x LPC, and the list stays in registers)
-        auto sweep = [&](uint32_t sid, uint32_t lo, uint32_t hi) __attribute__((always_inline)) {
-#pragma unroll 1
-            for (int rr = 0; rr < R; rr++) {
-                if (64u * rr + 64u <= lo || 64u * rr >= hi) continue;
-                u64 mine = KEY_INVALID;
-#pragma unroll
-                for (int r = 0; r < R; r++)
-                    if (r == rr) mine = wl.L[r];
-                const uint32_t idx = 64u * rr + lane;
-                const bool open = idx >= lo && idx < hi && (mine & KEY_EXPANDED) == 0;
-                if (__ballot(open) == 0) continue;
-                const uint32_t my_id = (uint32_t)mine, my_db = (uint32_t)(mine >> 32);
-                bool mark = false;
-#pragma unroll
-                for (int half = 0; half < LPC; half++) {
-                    const int src = half * CHUNK + cslot;  // the lane that owns this pass's candidate
-                    const uint32_t cid = (uint32_t)__shfl((int)my_id, src);
-                    const uint32_t cdb = (uint32_t)__shfl((int)my_db, src);
-                    const bool act = __shfl(open ? 1 : 0, src) != 0;
-                    if (__ballot(act) == 0) continue;
-                    c_rows += (uint32_t)__popcll(__ballot(act && first));
-                    const float dist = dist_build<KIND, DS, true>(v, cid, act, h, yqe, coop_ids, coop_img, lane);
-                    bool rej = false;
-                    if (act && first) {
-                        if (dist != dist) status = HNSW_ERR_NAN_INPUT;
-                        const u64 sk = ((u64)__builtin_bit_cast(uint32_t, dist) << 32) | sid;
-                        const u64 ck = ((u64)cdb << 32) | cid;
-                        rej = sk < ck;
-                    }
-                    const u64 rm = __ballot(rej);  // bit LPC * cslot of the pass <-> owner lane src
-                    const int own = lane - half * CHUNK;
-                    if (own >= 0 && own < CHUNK && ((rm >> (LPC * own)) & 1)) mark = true;
-                }
-#pragma unroll
-                for (int r = 0; r < R; r++)
-                    if (r == rr && mark) wl.L[r] |= KEY_EXPANDED;
-            }
-        };
-        // The candidate set holds up to 512 entries but m selections usually come out of the first hundred:
-        // a selected point sweeps only the WINDOW [0, win_end) of candidates; when the window holds nothing
-        // unpopped and fewer than m are selected, it grows by 64 and the points selected so far sweep the new
-        // part first.  Every candidate is still judged against every point selected before it is popped, so the
-        // selection is the one the whole-set sweep made (round 2: every selection swept all 512 -- eight distance
-        // passes per selection, most of them for candidates that are never reached).
-        uint32_t win_end = min(n_c, 128u);
-        while (ns < m && status == HNSW_OK) {
-            int pos = -1;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const uint32_t idx = 64u * r + lane;
-                const u64 mk = __ballot(idx >= cursor && idx < win_end && (wl.L[r] & KEY_EXPANDED) == 0);
-                if (pos < 0 && mk) pos = 64 * r + (__ffsll((long long)mk) - 1);
-            }
-            if (pos < 0) {
-                if (win_end >= n_c) break;  // every candidate was popped
-                const uint32_t new_end = min(n_c, win_end + 64u);
-                for (uint32_t k2 = 0; k2 < ns && status == HNSW_OK; k2++) {  // catch up: the new part against the selected
-                    const uint32_t sid2 = (uint32_t)selk[k2];
-                    c_rows++;
-                    stage_row<KIND>(v, sid2, yqe, lane);
-                    sweep(sid2, win_end, new_end);
-                }
-                cursor = win_end;
-                win_end = new_end;
-                if (__ballot(status != HNSW_OK)) status = HNSW_ERR_NAN_INPUT;
-                continue;
-            }
-            u64 sk_sel = 0;
-#pragma unroll
-            for (int r = 0; r < R; r++)
-                if ((pos >> 6) == r) {
-                    sk_sel = readlane64(wl.L[r], pos & 63);
-                    if (lane == (pos & 63)) selbits |= 1u << r;
-                }
-            if (lane == 0) selk[ns] = sk_sel;
-            ns++;
-            cursor = (uint32_t)pos + 1;
-            wave_fence();
-            if (ns >= m || (cursor >= win_end && win_end >= n_c)) continue;  // nothing left to decide
-            const uint32_t sid = (uint32_t)sk_sel;
-            c_rows++;
-            stage_row<KIND>(v, sid, yqe, lane);
-            sweep(sid, cursor, win_end);
-            if (__ballot(status != HNSW_OK)) status = HNSW_ERR_NAN_INPUT;
-        }
-        // keep_pruned: fill up from the rejected candidates in ascending order (searcher.rs:141-146);
-        // only reached with ns < m when every candidate was popped
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t idx = 64u * r + lane;
-            u64 mk = __ballot(idx < n_c && (wl.L[r] & KEY_EXPANDED) != 0 && ((selbits >> r) & 1u) == 0);
-            while (mk && ns < m && status == HNSW_OK) {
-                const int j = __ffsll((long long)mk) - 1;
-                mk &= mk - 1;
-                const u64 ek = readlane64(wl.L[r], j) & KEY_MASK;
-                if (lane == 0) selk[ns] = ek;
-                ns++;
-            }
-        }
-        wave_fence();
-        // save_layer_results + the selection seeds the next layer (up to 128 selected: two rounds of 64)
-#pragma unroll
-        for (int r = 0; r < R; r++) wl.L[r] = KEY_INVALID;
-        wl.n_cur = 0;
-        wl.last_key = KEY_INVALID;
-        for (uint32_t j0 = 0; j0 < max(ns, 1u); j0 += 64) {
-            const uint32_t j = j0 + (uint32_t)lane;
-            const u64 mine = j < ns ? selk[j] : KEY_INVALID;
-            if (j < ns) {
-                o_ids[(size_t)layer * m + j] = (uint32_t)mine;
-                o_d[(size_t)layer * m + j] = __builtin_bit_cast(float, (uint32_t)(mine >> 32));
-            }
-            wl.merge(mine, max(ns, 1u), perm, lane);
-        }
-    }
-    if (__ballot(status != HNSW_OK)) {
-        int32_t st = status;
-        for (int o = 32; o > 0; o >>= 1) st = min(st, __shfl_xor(st, o));
-        status = st;
-    }
-    if (a.req_keys != nullptr && status == HNSW_OK) {
-        // on-device connect: only a point whose every layer succeeded writes its own rows (nobody can
-        // reach p yet) and files one reverse-edge request per selected neighbour
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        uint32_t total = 0;
-        for (uint32_t l = 0; l <= level; l++) {
-            for (uint32_t j0 = 0; j0 < m; j0 += 64) {
-                const uint32_t j = j0 + (uint32_t)lane;
-                const uint32_t id = j < m ? o_ids[(size_t)l * m + j] : HX_EMPTY_SLOT;
-                total += (uint32_t)__popcll(__ballot(id != HX_EMPTY_SLOT));
-            }
-        }
-        // emit_own (sharded build): the point's own rows travel as records too -- (layer, p <- n) next
-        // to (layer, n <- p) -- so that the record list alone carries the whole batch to every replica
-        const uint32_t per_edge = a.emit_own ? 2u : 1u;
-        total *= per_edge;
-        // Reserve `total` record slots with ONE atomic add.  Round 2 reserved by compare-and-swap so that the counter
-        // never passed the last written record; 8192 waves retrying on one word made that loop 85 % of the insert
-        // kernel (1M points: 2.21 s against 0.34 s; 90 % of a wave's life in SQ_WAIT_ANY).  The add keeps the
-        // guarantee another way: once a reservation does not fit, the counter is beyond the capacity for good and
-        // every later one fails too, so the records written are exactly the prefix [0, B) where B is the base of the
-        // first failing reservation -- the smallest failing base, kept in *req_fail_base (atomic min; the host
-        // starts it at 0xFFFFFFFF and takes min(counter, B) as the record count).
-        uint32_t base = 0xFFFFFFFFu;
-        if (lane == 0) {
-            base = atomicAdd(a.req_count, total);
-            if ((uint64_t)base + total > a.req_cap) {
-                atomicMin(a.req_fail_base, base);
-                base = 0xFFFFFFFFu;
-            }
-        }
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        if (base == 0xFFFFFFFFu) {
-            status = HNSW_ERR_OVERFLOW;  // nothing written, nothing reserved: the point takes the CPU path
-        } else {
-            for (uint32_t l = 0; l <= level; l++) {
-                const uint32_t S = l == 0 ? v.S0 : v.S1;
-                // the layer's selection is a prefix of its m output slots: cnt of them are filled
-                uint32_t cnt = 0;
-                for (uint32_t j0 = 0; j0 < m; j0 += 64) {
-                    const uint32_t j = j0 + (uint32_t)lane;
-                    cnt += (uint32_t)__popcll(__ballot(j < m && o_ids[(size_t)l * m + j] != HX_EMPTY_SLOT));
-                }
-                for (uint32_t j0 = 0; j0 < max(S, m); j0 += 64) {
-                    const uint32_t j = j0 + (uint32_t)lane;
-                    const uint32_t id = j < m ? o_ids[(size_t)l * m + j] : HX_EMPTY_SLOT;
-                    if (!a.emit_own) {
-                        const size_t at = l == 0 ? (size_t)p * S : ((size_t)v.upper_base[p] + l - 1) * S;
-                        uint32_t *row = (l == 0 ? a.adj0_mut : a.adj_up_mut) + at;
-                        if (j < S) row[j] = id;
-                        uint32_t *rowd = l == 0 ? a.adjd0_mut : a.adjd_up_mut;
-                        if (rowd != nullptr && j < S)  // the edge's distance travels with it (ConnectArgs)
-                            rowd[at + j] = id != HX_EMPTY_SLOT ? __builtin_bit_cast(uint32_t, o_d[(size_t)l * m + j]) : 0xFFFFFFFFu;
-                    }
-                    if (id != HX_EMPTY_SLOT) {
-                        const uint32_t db = __builtin_bit_cast(uint32_t, o_d[(size_t)l * m + j]);
-                        a.req_keys[base + j] = hx_edge_key(l, id, p);
-                        a.req_vals[base + j] = db;
-                        if (a.emit_own) {
-                            a.req_keys[base + cnt + j] = hx_edge_key(l, p, id);
-                            a.req_vals[base + cnt + j] = db;
-                        }
-                    }
-                }
-                base += cnt * per_edge;
-            }
-        }
-    }
-    if (lane == 0) a.out_status[b] = status;
-    if (a.counters != nullptr && lane == 0) {
-        atomicAdd(a.counters + 0, (unsigned long long)c_rows);
-        atomicAdd(a.counters + 1, (unsigned long long)c_adj);
-        atomicAdd(a.counters + 2, (unsigned long long)c_ids);
-    }
-}
-
-// rows[row_index[i]] = data[i] for whole adjacency rows of S slots (dirty rows after a build batch)
-__global__ void __launch_bounds__(64)
-hx_scatter_rows_kernel(uint32_t *dst, uint32_t S, const uint32_t *row_index, const uint32_t *data,
-                       uint32_t n) {
-    const uint32_t i = blockIdx.x;
-    if (i >= n) return;
-    uint32_t *out = dst + (size_t)row_index[i] * S;
-    for (uint32_t k = threadIdx.x; k < S; k += 64) out[k] = data[(size_t)i * S + k];
-}
-
-// First-attempt size of the insert kernel's visited table, relative to the standard one: - 1 (2048 slots, 8 KiB)
-// for ef_construction <= 32 on 32-slot rows.  LDS is what limits the insert kernel's waves per CU (6 with the
-// standard 16-KiB table at d = 256, 10 with 8 KiB): 16M x 256d, insert kernel 12.3 -> 10.1 s with 29 points of
-// 16M filling the small table (they run again with adjust + 1; round 3).
-int insert_table_first_adjust(const DevView &v, const InsertArgs &a) {
-    if (const char *e = getenv("HNSW_MI355X_INSERT_TABLE_ADJUST")) return atoi(e);  // A/B runs
-    return (a.ef_cons <= 32 && v.S0 <= 32) ? -1 : 0;
-}
-
-int launch_insert(const DevView &v, const InsertArgs &a, uint32_t nblocks, hipStream_t stream, int table_adjust) {
-    if (nblocks == 0) return HNSW_OK;
-    if (a.m > 128 || a.m == 0 || a.ef_cons > 64 * HX_MAX_R) {
-        set_error("on-device build supports m <= 128 and ef_construction <= 512");
-        return HNSW_ERR_ARG;
-    }
-    // visited table: what ef_cons list entries with rows of S0 slots visit (m <= 32: 4096 / 8192 / 16384 slots as
-    // before; the 128- and 256-slot rows of m = 64 / 128 take up to 32768 slots = 128 KiB, one wave per CU -- a
-    // point that still fills it takes the CPU path after the build, like every point whose search fails)
-    uint32_t slots_log2 = 12 + (a.ef_cons > 64 ? 1 : 0) + (a.ef_cons > 160 ? 1 : 0);
-    if (v.S0 > 64) slots_log2 = std::max(slots_log2, std::min(15u, default_slots_log2(a.ef_cons, v.S0)));
-    // table_adjust: the device-connect build first runs a batch with HALF the table where that buys waves per
-    // CU (insert_table_first_adjust) and runs the few points that fill it again with a larger one
-    slots_log2 = (uint32_t)std::min(15, std::max(9, (int)slots_log2 + table_adjust));
-    const size_t yq_bytes =
-        ((v.kind == HNSW_VEC_QUANT8 ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4) + 15) & ~15ull;
-    const size_t lds = (4ull << slots_log2) + 64ull * HX_MAX_R * 8 + 128 * 8 + 2 * yq_bytes + 256 /* rank -> id words */;
-    if (lds > 160 * 1024) {
-        set_error("insert kernel needs %zu bytes of LDS", lds);
-        return HNSW_ERR_ARG;
-    }
-    // the configs[1] dimension gets compile-time row loops
-    void (*kfn)(const DevView, const InsertArgs, const uint32_t);
-    if (v.kind == HNSW_VEC_QUANT8)
-        kfn = v.dim == 100   ? hx_insert_kernel<HNSW_VEC_QUANT8, 100>
-              : v.dim == 128 ? hx_insert_kernel<HNSW_VEC_QUANT8, 128>
-              : v.dim == 256 ? hx_insert_kernel<HNSW_VEC_QUANT8, 256>
-              : v.dim == 768 ? hx_insert_kernel<HNSW_VEC_QUANT8, 768>
-                             : hx_insert_kernel<HNSW_VEC_QUANT8, 0>;
-    else
-        kfn = v.dim == 100                           ? hx_insert_kernel<HNSW_VEC_F32, 100>
-              : v.dim == 128                         ? hx_insert_kernel<HNSW_VEC_F32, 128>
-              : v.dim == 256 && v.row_stride == 1024 ? hx_insert_kernel<HNSW_VEC_F32, 256>  // the configs[4] dimension
-              : v.dim == 768 && v.row_stride == 3072 ? hx_insert_kernel<HNSW_VEC_F32, 768>  // the configs[2] dimension
-                                                     : hx_insert_kernel<HNSW_VEC_F32, 0>;
-    const void *kern = reinterpret_cast<const void *>(kfn);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-            return HNSW_ERR_HIP;
-        }
-    }
-    HX_LAUNCH(kfn, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("insert kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// On-device connect.  Edge records hx_edge_key(layer, row node, other node) arrive radix-sorted, so
-// the records of one adjacency row are adjacent; one wave is launched per record, the wave of a
-// row's first record owns the row for the phase and the others exit at once.  Rows are owned by
-// exactly one wave per phase: no locks, no atomics on rows, deterministic for a given batch.
-//
-// Phase 2 (hx_connect_kernel): make_connections adds the sources to the row (template.rs:196-207); a
-// row that would exceed the layer's cap is pruned to its `cap` nearest by (dist, id)
-// (prune_connections / select_simple, template.rs:209-238,614-621) -- distances of the existing
-// neighbours are evaluated here, the sources bring d(p, n) = d(n, p).  Every dropped neighbour x (and
-// every source that did not make it) is reported so that phase 3 removes the reverse edge
-// (remove_edge is symmetric, graph.rs:72-83).
-// ---------------------------------------------------------------------------------------------
-static constexpr uint64_t HX_EDGE_ID_MASK = (1ull << HX_EDGE_ID_BITS) - 1;
-
-// number of records of the row that starts at record i (0 if i is not the first of its row)
-__device__ __forceinline__ uint32_t edge_group_size(const uint64_t *keys, uint32_t count, uint32_t i, int lane) {
-    const uint64_t prefix = keys[i] >> HX_EDGE_ID_BITS;
-    if (i > 0 && (keys[i - 1] >> HX_EDGE_ID_BITS) == prefix) return 0;
-    uint32_t k = 1;
-    for (;;) {
-        const uint32_t j = i + k + lane;
-        const bool same = j < count && (keys[j] >> HX_EDGE_ID_BITS) == prefix;
-        const u64 diff = ~__ballot(same);
-        if (diff) return k + (uint32_t)(__ffsll((long long)diff) - 1);
-        k += 64;
-    }
-}
-
-// RS = registers per lane that hold one adjacency row (slot 64 r + lane): 1 for rows of up to 64 slots
-// (m <= 32), 2 / 4 for the 128- / 256-slot layer-0 rows of m = 64 / 128 (the reference's own build benches
-// use M in {32, 64, 128}, hnsw/benches/hnsw_benchmarks.rs:7)
-template <int KIND, int DS, int RS>
-__global__ void __launch_bounds__(64)
-hx_connect_kernel(const DevView v, const ConnectArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    u64 *perm = reinterpret_cast<u64 *>(smem);       // [64 RS]
-    u64 *ekeys = perm + 64 * RS;                      // [64 RS] keys of the existing neighbours
-    float *yq = reinterpret_cast<float *>(ekeys + 64 * RS);
-    const int lane = threadIdx.x;
-    const uint32_t lo = blockIdx.x;
-    if (lo >= a.count) return;
-    const uint32_t k = edge_group_size(a.keys, a.count, lo, lane);
-    if (k == 0) return;
-    const uint64_t head = a.keys[lo];
-    const uint32_t n = (uint32_t)((head >> HX_EDGE_ID_BITS) & HX_EDGE_ID_MASK);
-    const uint32_t layer = (uint32_t)(head >> (2 * HX_EDGE_ID_BITS));
-    const uint32_t S = layer == 0 ? v.S0 : v.S1;
-    const uint32_t cap = layer == 0 ? 2 * a.m : a.m;
-    if (n >= v.n_points || layer >= v.nb_layers || (layer > 0 && v.upper_base[n] == HX_EMPTY_SLOT) || S > 64u * RS) {
-        *a.status = HNSW_ERR_NODE_NOT_IN_GRAPH;  // a malformed record: never touch memory for it
-        return;
-    }
-    if (a.own_world > 1) {  // sharded build: this row has ONE owner among the ranks
-        if (n % a.own_world != a.own_rank) return;
-        if (lane == 0) {     // its new contents will travel to the other replicas (64 lists: one counter would serialise)
-            const uint32_t seg = blockIdx.x & (HX_CHG_LISTS - 1), at = atomicAdd(a.chg_count + seg, 1u);
-            if (at < a.chg_cap)
-                a.chg_keys[(size_t)seg * a.chg_cap + at] = hx_edge_key(layer, n, 0);
-            else
-                *a.status = HNSW_ERR_OVERFLOW;
-        }
-    }
-    const size_t row_at = layer == 0 ? (size_t)n * S : ((size_t)v.upper_base[n] + layer - 1) * S;
-    uint32_t *row = (layer == 0 ? a.adj0_mut : a.adj_up_mut) + row_at;
-    uint32_t *rowd = layer == 0 ? a.adjd0_mut : a.adjd_up_mut;  // the edges' distances, or null
-    if (rowd != nullptr) rowd += row_at;
-    constexpr int LPC = (KIND == HNSW_VEC_QUANT8) ? 2 : 1;
-    constexpr int CHUNK = 64 / LPC;
-    const int h = (LPC == 2) ? (lane & 1) : 0;
-    const int cslot = lane / LPC;
-    const bool first = (LPC == 1) || (h == 0);
-
-    uint32_t cur[RS], curd[RS];
-    u64 hm[RS];
-    uint32_t deg = 0;
-#pragma unroll
-    for (int r = 0; r < RS; r++) {
-        const uint32_t slot = 64u * r + (uint32_t)lane;
-        cur[r] = slot < S ? row[slot] : HX_EMPTY_SLOT;
-        curd[r] = (rowd != nullptr && slot < S) ? rowd[slot] : 0xFFFFFFFFu;
-        hm[r] = __ballot(cur[r] != HX_EMPTY_SLOT);
-        deg += (uint32_t)__popcll(hm[r]);
-    }
-    if (deg + k <= cap && deg + k <= S) {  // room for every source: append
-        uint32_t before = 0;               // (all reads of the row happened above)
-#pragma unroll
-        for (int r = 0; r < RS; r++) {
-            if (cur[r] != HX_EMPTY_SLOT) {
-                const uint32_t at = before + (uint32_t)__popcll(hm[r] & ((1ull << lane) - 1));
-                row[at] = cur[r];
-                if (rowd != nullptr) rowd[at] = curd[r];
-            }
-            before += (uint32_t)__popcll(hm[r]);
-        }
-        for (uint32_t j = lane; j < k; j += 64) {
-            row[deg + j] = (uint32_t)(a.keys[lo + j] & HX_EDGE_ID_MASK);
-            if (rowd != nullptr) rowd[deg + j] = a.vals[lo + j];  // d(source, n) = d(n, source)
-        }
-        for (uint32_t j = deg + k + lane; j < S; j += 64) {
-            row[j] = HX_EMPTY_SLOT;
-            if (rowd != nullptr) rowd[j] = 0xFFFFFFFFu;
-        }
-        return;
-    }
-    // ---- prune: keep the `cap` nearest of existing ∪ sources ----
-    // the node's own row is staged only when some existing neighbour's distance is not known yet
-    bool any_unknown = false;
-#pragma unroll
-    for (int r = 0; r < RS; r++) any_unknown |= __ballot(cur[r] != HX_EMPTY_SLOT && curd[r] == 0xFFFFFFFFu) != 0;
-    if (any_unknown) stage_row<KIND>(v, n, yq, lane);
-    WaveList<RS> wl;
-#pragma unroll
-    for (int r = 0; r < RS; r++) {
-        wl.L[r] = KEY_INVALID;
-        ekeys[64 * r + lane] = KEY_INVALID;
-    }
-    wl.n_cur = 0;
-    wl.last_key = KEY_INVALID;
-    wave_fence();
-    for (uint32_t c0 = 0; c0 < S; c0 += CHUNK) {  // existing neighbours, CHUNK at a time
-        const uint32_t slot = c0 + cslot;
-        uint32_t id = HX_EMPTY_SLOT, dbits = 0xFFFFFFFFu;
-#pragma unroll
-        for (int r = 0; r < RS; r++) {
-            const uint32_t t = (uint32_t)__shfl((int)cur[r], (int)(slot & 63));
-            const uint32_t td = (uint32_t)__shfl((int)curd[r], (int)(slot & 63));
-            if ((slot >> 6) == (uint32_t)r) {
-                id = t;
-                dbits = td;
-            }
-        }
-        const bool act = slot < S && id < v.n_points;
-        if (slot < S && id != HX_EMPTY_SLOT && id >= v.n_points) *a.status = HNSW_ERR_NODE_NOT_IN_GRAPH;
-        const bool need = act && dbits == 0xFFFFFFFFu;  // (an edge that predates the build: evaluated once, kept from here on)
-        if (__ballot(need) != 0) {
-            const float dist = dist_build<KIND, DS>(v, id, need, h, yq);
-            if (need) dbits = __builtin_bit_cast(uint32_t, dist);
-        }
-        u64 key = KEY_INVALID;
-        if (act && first) {
-            key = ((u64)dbits << 32) | id;
-            ekeys[slot] = key;
-        }
-        wl.merge(key, cap, perm, lane);
-    }
-    auto source_key = [&](uint32_t j) -> u64 {
-        return j < k ? ((u64)a.vals[lo + j] << 32) | (uint32_t)(a.keys[lo + j] & HX_EDGE_ID_MASK) : KEY_INVALID;
-    };
-    for (uint32_t j0 = 0; j0 < k; j0 += 64) wl.merge(source_key(j0 + lane), cap, perm, lane);
-    wave_fence();
-#pragma unroll
-    for (int r = 0; r < RS; r++) {
-        const uint32_t slot = 64u * r + (uint32_t)lane;
-        if (slot < S) {
-            row[slot] = slot < wl.n_cur ? (uint32_t)wl.L[r] : HX_EMPTY_SLOT;
-            if (rowd != nullptr) rowd[slot] = slot < wl.n_cur ? (uint32_t)(wl.L[r] >> 32) : 0xFFFFFFFFu;
-        }
-    }
-    // report what fell out: key > the last kept key (keys are distinct)
-    const u64 lastk = wl.n_cur >= cap ? wl.last_key : KEY_INVALID;
-    auto emit = [&](u64 key) {
-        const bool drop = key != KEY_INVALID && key > lastk;
-        const u64 dm = __ballot(drop);
-        if (dm == 0) return;
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(a.out_count, (uint32_t)__popcll(dm));
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        const uint32_t at = base + (uint32_t)__popcll(dm & ((1ull << lane) - 1));
-        if (drop) {
-            if (at < a.out_cap)
-                a.out_keys[at] = hx_edge_key(layer, (uint32_t)key, n);
-            else
-                *a.status = HNSW_ERR_OVERFLOW;
-        }
-    };
-#pragma unroll
-    for (int r = 0; r < RS; r++) emit(ekeys[64 * r + lane]);
-    for (uint32_t j0 = 0; j0 < k; j0 += 64) emit(source_key(j0 + lane));
-}
-
-// ---------------------------------------------------------------------------------------------
-// Phase 3 (hx_remove_kernel): the row of x drops the neighbours that dropped x in phase 2.  An edge
-// to x's LAST neighbour is kept (isolate_node, graph.rs:85-94): such a refusal is reported and the
-// host restores the reverse direction after the build.
-// ---------------------------------------------------------------------------------------------
-template <int RS>
-__global__ void __launch_bounds__(64)
-hx_remove_kernel(const DevView v, const ConnectArgs a) {
-    const int lane = threadIdx.x;
-    const uint32_t lo = blockIdx.x;
-    if (lo >= a.count) return;
-    const uint32_t k = edge_group_size(a.keys, a.count, lo, lane);
-    if (k == 0) return;
-    const uint64_t head = a.keys[lo];
-    const uint32_t x = (uint32_t)((head >> HX_EDGE_ID_BITS) & HX_EDGE_ID_MASK);
-    const uint32_t layer = (uint32_t)(head >> (2 * HX_EDGE_ID_BITS));
-    const uint32_t S = layer == 0 ? v.S0 : v.S1;
-    if (x >= v.n_points || layer >= v.nb_layers || (layer > 0 && v.upper_base[x] == HX_EMPTY_SLOT) || S > 64u * RS) {
-        *a.status = HNSW_ERR_NODE_NOT_IN_GRAPH;
-        return;
-    }
-    if (a.own_world > 1) {  // sharded build: x's row is dropped from by its owner only, and shipped afterwards
-        if (x % a.own_world != a.own_rank) return;
-        if (lane == 0) {
-            const uint32_t seg = blockIdx.x & (HX_CHG_LISTS - 1), at = atomicAdd(a.chg_count + seg, 1u);
-            if (at < a.chg_cap)
-                a.chg_keys[(size_t)seg * a.chg_cap + at] = hx_edge_key(layer, x, 0);
-            else
-                *a.status = HNSW_ERR_OVERFLOW;
-        }
-    }
-    const size_t row_at = layer == 0 ? (size_t)x * S : ((size_t)v.upper_base[x] + layer - 1) * S;
-    uint32_t *row = (layer == 0 ? a.adj0_mut : a.adj_up_mut) + row_at;
-    uint32_t *rowd = layer == 0 ? a.adjd0_mut : a.adjd_up_mut;  // the edges' distances move with their ids
-    if (rowd != nullptr) rowd += row_at;
-    uint32_t cur[RS], curd[RS];
-    uint32_t deg = 0;
-#pragma unroll
-    for (int r = 0; r < RS; r++) {
-        const uint32_t slot = 64u * r + (uint32_t)lane;
-        cur[r] = slot < S ? row[slot] : HX_EMPTY_SLOT;
-        curd[r] = (rowd != nullptr && slot < S) ? rowd[slot] : 0xFFFFFFFFu;
-        deg += (uint32_t)__popcll(__ballot(cur[r] != HX_EMPTY_SLOT));
-    }
-    for (uint32_t j = 0; j < k; j++) {
-        const uint32_t nb = (uint32_t)(a.keys[lo + j] & HX_EDGE_ID_MASK);
-        u64 hit = 0;
-#pragma unroll
-        for (int r = 0; r < RS; r++) hit |= __ballot(cur[r] == nb);
-        if (hit == 0) continue;
-        if (deg == 1) {  // the last edge stays
-            if (lane == 0) {
-                const uint32_t at = atomicAdd(a.out_count, 1u);
-                if (at < a.out_cap)
-                    a.out_keys[at] = hx_edge_key(layer, x, nb);
-                else
-                    *a.status = HNSW_ERR_OVERFLOW;
-            }
-            continue;
-        }
-#pragma unroll
-        for (int r = 0; r < RS; r++)
-            if (cur[r] == nb) cur[r] = HX_EMPTY_SLOT;
-        deg--;
-    }
-    // compact: survivors to the front, every slot written by exactly one lane
-    uint32_t before = 0;
-#pragma unroll
-    for (int r = 0; r < RS; r++) {
-        const u64 hm = __ballot(cur[r] != HX_EMPTY_SLOT);
-        if (cur[r] != HX_EMPTY_SLOT) {
-            const uint32_t at = before + (uint32_t)__popcll(hm & ((1ull << lane) - 1));
-            row[at] = cur[r];
-            if (rowd != nullptr) rowd[at] = curd[r];
-        }
-        before += (uint32_t)__popcll(hm);
-    }
-#pragma unroll
-    for (int r = 0; r < RS; r++) {
-        const uint32_t slot = 64u * r + (uint32_t)lane;
-        if (slot >= before && slot < S) {
-            row[slot] = HX_EMPTY_SLOT;
-            if (rowd != nullptr) rowd[slot] = 0xFFFFFFFFu;
-        }
-    }
-}
-
-template <int RS>
-static int launch_connect_rs(const DevView &v, const ConnectArgs &a, hipStream_t stream) {
-    const size_t yq_bytes =
-        ((v.kind == HNSW_VEC_QUANT8 ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4) + 15) & ~15ull;
-    const size_t lds = 2 * 64 * RS * 8 + yq_bytes;
-    void (*kfn)(const DevView, const ConnectArgs);
-    if (v.kind == HNSW_VEC_QUANT8)
-        kfn = v.dim == 100   ? hx_connect_kernel<HNSW_VEC_QUANT8, 100, RS>
-              : v.dim == 128 ? hx_connect_kernel<HNSW_VEC_QUANT8, 128, RS>
-              : v.dim == 256 ? hx_connect_kernel<HNSW_VEC_QUANT8, 256, RS>
-              : v.dim == 768 ? hx_connect_kernel<HNSW_VEC_QUANT8, 768, RS>
-                             : hx_connect_kernel<HNSW_VEC_QUANT8, 0, RS>;
-    else
-        kfn = v.dim == 100   ? hx_connect_kernel<HNSW_VEC_F32, 100, RS>
-              : v.dim == 128 ? hx_connect_kernel<HNSW_VEC_F32, 128, RS>
-                             : hx_connect_kernel<HNSW_VEC_F32, 0, RS>;
-    HX_LAUNCH(kfn, dim3(a.count), dim3(64), lds, stream, v, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("connect kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
-}
-
-// the wide-row instantiations (m = 64 / 128) exist for the dimension-generic loops only: one compile-time
-// dimension per row width would triple the build time of this file for shapes nobody has measured
-template <int RS>
-static int launch_connect_wide(const DevView &v, const ConnectArgs &a, hipStream_t stream) {
-    const size_t yq_bytes =
-        ((v.kind == HNSW_VEC_QUANT8 ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4) + 15) & ~15ull;
-    const size_t lds = 2 * 64 * RS * 8 + yq_bytes;
-    if (v.kind == HNSW_VEC_QUANT8)
-        HX_LAUNCH((hx_connect_kernel<HNSW_VEC_QUANT8, 0, RS>), dim3(a.count), dim3(64), lds, stream, v, a);
-    else
-        HX_LAUNCH((hx_connect_kernel<HNSW_VEC_F32, 0, RS>), dim3(a.count), dim3(64), lds, stream, v, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("connect kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
-}
-
-int launch_connect(const DevView &v, const ConnectArgs &a, hipStream_t stream) {
-    if (a.count == 0) return HNSW_OK;
-    const uint32_t S = std::max(v.S0, v.S1);
-    if (S <= 64) return launch_connect_rs<1>(v, a, stream);
-    if (S <= 128) return launch_connect_wide<2>(v, a, stream);
-    if (S <= 256) return launch_connect_wide<4>(v, a, stream);
-    set_error("on-device build: adjacency rows of %u slots (m > 128)", S);
-    return HNSW_ERR_ARG;
-}
-
-int launch_remove(const DevView &v, const ConnectArgs &a, hipStream_t stream) {
-    if (a.count == 0) return HNSW_OK;
-    const uint32_t S = std::max(v.S0, v.S1);
-    if (S <= 64)
-        HX_LAUNCH(hx_remove_kernel<1>, dim3(a.count), dim3(64), 0, stream, v, a);
-    else if (S <= 128)
-        HX_LAUNCH(hx_remove_kernel<2>, dim3(a.count), dim3(64), 0, stream, v, a);
-    else if (S <= 256)
-        HX_LAUNCH(hx_remove_kernel<4>, dim3(a.count), dim3(64), 0, stream, v, a);
-    else {
-        set_error("on-device build: adjacency rows of %u slots (m > 128)", S);
-        return HNSW_ERR_ARG;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("remove kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
-}
-
-int launch_scatter_rows(uint32_t *dst, uint32_t S, const uint32_t *d_row_index, const uint32_t *d_data,
-                        uint32_t n, hipStream_t stream) {
-    if (n == 0) return HNSW_OK;
-    HX_LAUNCH(hx_scatter_rows_kernel, dim3(n), dim3(64), 0, stream, dst, S, d_row_index, d_data, n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("scatter kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
@@ -2858,79 +1302,23 @@ uint32_t max_slots_log2(uint32_t ef) { return ef <= 64 * HX_MAX_R_WIDE ? 15 : 31
 template <int KIND, int P, int DS, int R, bool FAT>
 static int launch_one(const DevView &v, const SearchArgs &a_in, uint32_t nblocks, uint32_t slots_log2,
                       hipStream_t stream) {
-    const size_t yq_bytes =
-        (KIND == HNSW_VEC_QUANT8) ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4;
     SearchArgs a = a_in;
     // lists of eight / sixteen registers (ef > 320 asks for a 64- / 128-KiB table): 32 KiB of LDS + a second level in
     // HBM (stream-ordered scratch), see the kernel
-    struct Scratch {
-        void *p = nullptr;
-        hipStream_t st = nullptr;
-        ~Scratch() {
-            if (p) (void)hipFreeAsync(p, st);
-        }
-    } sp;
-    static const bool two_level = !(getenv("HNSW_MI355X_VISITED_2L") && atoi(getenv("HNSW_MI355X_VISITED_2L")) == 0);
-    if (R >= 8 && two_level && slots_log2 >= 14 && a.spill_tab == nullptr) {
-        const uint32_t glog2 = std::max(15u, slots_log2 + 1);
-        sp.st = stream;
-        if (hipMallocAsync(&sp.p, ((size_t)nblocks << glog2) * 4, stream) != hipSuccess) {
-            (void)hipGetLastError();
-            sp.p = nullptr;  // no scratch: the one-level table serves
-        } else {
-            a.spill_tab = static_cast<uint32_t *>(sp.p);
-            a.spill_log2 = glog2;
-            slots_log2 = 13;
-            if (const char *e = getenv("HNSW_MI355X_VISITED_2L_LIMIT")) a.lds_limit = (uint32_t)atoi(e);
-        }
-    }
-    size_t lds = (4ull << slots_log2) + scratch_region_bytes<KIND, DS, R>() + ((yq_bytes + 15) & ~15ull);
+    VisitedSpill sp(R >= 8 && slots_log2 >= 14 && a.spill_tab == nullptr, a, slots_log2, nblocks, stream);
+    size_t lds = (4ull << slots_log2) + scratch_region_bytes<KIND, DS, R>() + query_lds_bytes(v);
     if (FAT) lds += 2ull * 1024 * (P > 0 ? P : 1);
-    auto kern = hx_search_kernel<KIND, P, DS, R, FAT>;
-    if (lds > 160 * 1024) {
-        set_error("search needs %zu bytes of LDS (> 160 KiB)", lds);
-        return HNSW_ERR_ARG;
-    }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-            return HNSW_ERR_HIP;
-        }
-    }
-    HX_LAUNCH(kern, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("search kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"search kernel launch", "search needs %zu bytes of LDS (> 160 KiB)"},
+                          hx_search_kernel<KIND, P, DS, R, FAT>, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
 }
 
 template <int P, int DS, int R>
 static int launch_two(const DevView &v, const SearchArgs &a, uint32_t nblocks, uint32_t slots_log2,
                       hipStream_t stream) {
-    const size_t yq_bytes = ((2ull * (v.half_bytes - 8) * 4) + 15) & ~15ull;
     const size_t lds = (4ull << slots_log2) + 2ull * 64 * R * 8 + 2 * 32 * 8 + 2 * 2 * 4 * 4 +
-                       2 * yq_bytes + 2ull * 2 * (16ull * 32 * P);
-    auto kern = hx_search2_kernel<P, DS, R>;
-    if (lds > 160 * 1024) return HNSW_ERR_ARG;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-            return HNSW_ERR_HIP;
-        }
-    }
-    HX_LAUNCH(kern, dim3(nblocks), dim3(128), lds, stream, v, a, slots_log2);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("two-wave search kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+                       2 * (size_t)query_lds_bytes(v) + 2ull * 2 * (16ull * 32 * P);
+    return launch_checked({"two-wave search kernel launch", "search needs %zu bytes of LDS (> 160 KiB)"},
+                          hx_search2_kernel<P, DS, R>, dim3(nblocks), dim3(128), lds, stream, v, a, slots_log2);
 }
 
 // The two-wave kernel is opt-in (HNSW_MI355X_WAVES=2): measured on MI355X at 1M x 100d, batch 1024
@@ -2973,18 +1361,11 @@ static int launch_r(const DevView &v, const SearchArgs &a, uint32_t nblocks, uin
     // the compact layout wins (measured, 1M x 100d quant8, efSearch 68: 2048 queries 0.359 ms inline
     // rows vs 0.256 ms compact; 32768 queries 8.4 vs 10.6 M q/s) -- the block images halve the
     // resident waves and every slot of a block is read whether it is needed or not
-    static const uint32_t n_cu = [] {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        return (uint32_t)cus;
-    }();
     // (every caller's table has at least default_slots_log2(ef_max) slots -- 2^13 above ef 112 at S0 = 32 -- so
     // fat_lds fits at four list registers only for P <= 2 and at eight only for P = 1: the others are not built)
     constexpr bool FAT4 = CAN_FAT && P <= 2, FAT8 = CAN_FAT && P <= 1;
     if (CAN_FAT && v.fat != nullptr && v.S0 == 32 && a.layer_lo == 0 && fat_lds <= 40 * 1024 &&
-        nblocks <= 4 * n_cu) {
+        nblocks <= 4 * cu_count()) {
         if (ef_max <= 64) return launch_one<KIND, P, DS, 1, CAN_FAT>(v, a, nblocks, slots_log2, stream);
         if (ef_max <= 128) return launch_one<KIND, P, DS, 2, CAN_FAT>(v, a, nblocks, slots_log2, stream);
         if (ef_max <= 256) {
@@ -3276,8 +1657,8 @@ static int launch_spill(const DevView &v, const SearchArgs &a, uint32_t nblocks,
     const uint64_t per_q = list_cap * 8 + (4ull << tab_log2);
     const uint64_t budget = 1ull << 30;  // scratch per launch
     const uint32_t group = (uint32_t)std::min<uint64_t>(nblocks, std::max<uint64_t>(1, budget / per_q));
-    const size_t yq_bytes =
-        ((v.kind == HNSW_VEC_QUANT8 ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4) + 15) & ~15ull;
+    char site[64];
+    snprintf(site, sizeof site, "search kernel launch (ef = %u)", ef_max);
     for (uint32_t first = 0; first < nblocks; first += group) {
         const uint32_t n = std::min(group, nblocks - first);
         void *mem = nullptr;
@@ -3298,21 +1679,16 @@ static int launch_spill(const DevView &v, const SearchArgs &a, uint32_t nblocks,
         sp.list_cap = (uint32_t)list_cap;
         sp.tab_log2 = tab_log2;
         sp.q_first = first;
-        if (v.kind == HNSW_VEC_QUANT8)
-            HX_LAUNCH(hx_search_spill_kernel<HNSW_VEC_QUANT8>, dim3(n), dim3(64), yq_bytes, stream, v, a, sp);
-        else
-            HX_LAUNCH(hx_search_spill_kernel<HNSW_VEC_F32>, dim3(n), dim3(64), yq_bytes, stream, v, a, sp);
-        hipError_t e = hipGetLastError();
+        const int rc = launch_checked({site}, v.kind == HNSW_VEC_QUANT8 ? hx_search_spill_kernel<HNSW_VEC_QUANT8>
+                                                                          : hx_search_spill_kernel<HNSW_VEC_F32>,
+                                      dim3(n), dim3(64), query_lds_bytes(v), stream, v, a, sp);
         if (async) {
             (void)hipFreeAsync(mem, stream);
         } else {
             (void)hipStreamSynchronize(stream);
             (void)hipFree(mem);
         }
-        if (e != hipSuccess) {
-            set_error("search kernel launch (ef = %u): %s", ef_max, hipGetErrorString(e));
-            return HNSW_ERR_HIP;
-        }
+        if (rc != HNSW_OK) return rc;
     }
     return HNSW_OK;
 }
@@ -3362,129 +1738,6 @@ int launch_search(const DevView &v, const SearchArgs &a_in, uint32_t nblocks, ui
     if (v.dim == 768 && v.row_stride == 3072)
         return launch_r<HNSW_VEC_F32, 192, 768>(v, a, nblocks, slots_log2, stream, ef_max);
     return launch_r<HNSW_VEC_F32, 0, 0>(v, a, nblocks, slots_log2, stream, ef_max);
-}
-
-// ---------------------------------------------------------------------------------------------
-// distance_batch: VecBase::dist2many (vectors/src/lib.rs:17-22) for one query -- the search
-// kernel restricted to "evaluate these ids": every id is an entry, results come back in list
-// order, so this launcher runs the kernel with ef = n = k and then un-sorts on the host side.
-// (Kept simple on purpose: it is a test seam, not a hot path.)
-// ---------------------------------------------------------------------------------------------
-template <int KIND>
-__global__ void __launch_bounds__(64)
-hx_distance_kernel(const DevView v, const float *q, const uint32_t *ids, uint64_t k, float *out,
-                   int32_t *status_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float *yq = reinterpret_cast<float *>(smem);
-    const int lane = threadIdx.x;
-    constexpr int LPC = (KIND == HNSW_VEC_QUANT8) ? 2 : 1;
-    constexpr int CHUNK = 64 / LPC;
-    const int h = (LPC == 2) ? (lane & 1) : 0;
-    int32_t status = stage_query<KIND>(v, q, yq, lane) ? HNSW_OK : HNSW_ERR_NAN_INPUT;
-    for (uint64_t base = (uint64_t)blockIdx.x * CHUNK; base < k;
-         base += (uint64_t)gridDim.x * CHUNK) {
-        const uint64_t i = base + lane / LPC;
-        const bool active = i < k;
-        const uint32_t id = active ? ids[i] : 0;
-        const bool ok = active && id < v.n_points;
-        const float dist = dist_any_dim<KIND>(v, id, ok, h, yq);
-        if (active && h == 0) {
-            if (!ok) status = HNSW_ERR_ARG;
-            out[i] = ok ? dist : __builtin_nanf("");
-        }
-    }
-    if (status != HNSW_OK) atomicMin(status_out, status);
-}
-
-// ---------------------------------------------------------------------------------------------
-// brute force: exact top-k of every query over ALL points under the index's own metric (the
-// reference's ground truth: helpers/glove.rs:94-109, template.rs:531-541).  Block (seg, q) scans
-// one contiguous segment of the ids and keeps its k best in the same sorted list the search
-// uses; the host merges the nseg partial lists of a query.
-// ---------------------------------------------------------------------------------------------
-template <int KIND>
-__global__ void __launch_bounds__(64)
-hx_brute_kernel(const DevView v, const float *Q, uint32_t k, uint32_t nseg, uint32_t *part_ids,
-                float *part_dists, int32_t *status_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    u64 *perm = reinterpret_cast<u64 *>(smem);
-    float *yq = reinterpret_cast<float *>(perm + 64);
-    const int lane = threadIdx.x;
-    const uint32_t seg = blockIdx.x, q = blockIdx.y;
-    constexpr int LPC = (KIND == HNSW_VEC_QUANT8) ? 2 : 1;
-    constexpr int CHUNK = 64 / LPC;
-    const int h = (LPC == 2) ? (lane & 1) : 0;
-    int32_t status = stage_query<KIND>(v, Q + (size_t)q * v.dim, yq, lane) ? HNSW_OK : HNSW_ERR_NAN_INPUT;
-    WaveList<1> wl;
-    wl.L[0] = KEY_INVALID;
-    wl.n_cur = 0;
-    wl.last_key = KEY_INVALID;
-    const uint64_t per = ((uint64_t)v.n_points + nseg - 1) / nseg;
-    const uint64_t lo = per * seg, hi = min((uint64_t)v.n_points, lo + per);
-    for (uint64_t base = lo; base < hi; base += CHUNK) {
-        const uint64_t i = base + lane / LPC;
-        const bool active = i < hi;
-        const float dist = dist_any_dim<KIND>(v, (uint32_t)i, active, h, yq);
-        u64 key = KEY_INVALID;
-        if (active && h == 0) {
-            if (dist != dist)
-                status = HNSW_ERR_NAN_INPUT;
-            else
-                key = ((u64)__builtin_bit_cast(uint32_t, dist) << 32) | (uint32_t)i;
-        }
-        wl.merge(key, k, perm, lane);
-    }
-    if ((uint32_t)lane < k) {
-        const size_t o = ((size_t)q * nseg + seg) * k + lane;
-        const bool have = (uint32_t)lane < wl.n_cur;
-        part_ids[o] = have ? (uint32_t)wl.L[0] : HX_EMPTY_SLOT;
-        part_dists[o] = have ? __builtin_bit_cast(float, (uint32_t)(wl.L[0] >> 32)) : __builtin_inff();
-    }
-    if (__ballot(status != HNSW_OK) && lane == 0) atomicMin(status_out, HNSW_ERR_NAN_INPUT);
-}
-
-int launch_brute_force(const DevView &v, const float *d_Q, uint64_t nq, uint32_t k, uint32_t nseg,
-                       uint32_t *part_ids, float *part_dists, int32_t *d_status,
-                       hipStream_t stream) {
-    if (nq == 0) return HNSW_OK;
-    if (k == 0 || k > 64 || nq > 65535) {
-        set_error("brute force supports 1 <= k <= 64 and at most 65535 queries per call");
-        return HNSW_ERR_ARG;
-    }
-    const size_t lds =
-        64 * 8 + (((v.kind == HNSW_VEC_QUANT8 ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4) + 15) & ~15ull);
-    if (v.kind == HNSW_VEC_QUANT8)
-        HX_LAUNCH(hx_brute_kernel<HNSW_VEC_QUANT8>, dim3(nseg, (uint32_t)nq), dim3(64), lds,
-                           stream, v, d_Q, k, nseg, part_ids, part_dists, d_status);
-    else
-        HX_LAUNCH(hx_brute_kernel<HNSW_VEC_F32>, dim3(nseg, (uint32_t)nq), dim3(64), lds,
-                           stream, v, d_Q, k, nseg, part_ids, part_dists, d_status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("brute force kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
-}
-
-int launch_distance_batch(const DevView &v, const float *d_q, const uint32_t *d_ids, uint64_t k,
-                          float *d_out, int32_t *d_status, hipStream_t stream) {
-    if (k == 0) return HNSW_OK;
-    const size_t lds =
-        ((v.kind == HNSW_VEC_QUANT8 ? 2ull * (v.half_bytes - 8) * 4 : (size_t)v.dim * 4) + 15) & ~15ull;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(2048, (k + 31) / 32);
-    if (v.kind == HNSW_VEC_QUANT8)
-        HX_LAUNCH(hx_distance_kernel<HNSW_VEC_QUANT8>, dim3(grid), dim3(64), lds, stream, v,
-                           d_q, d_ids, k, d_out, d_status);
-    else
-        HX_LAUNCH(hx_distance_kernel<HNSW_VEC_F32>, dim3(grid), dim3(64), lds, stream, v,
-                           d_q, d_ids, k, d_out, d_status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("distance kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
 }
 
 }  // namespace hx

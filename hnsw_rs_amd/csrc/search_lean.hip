@@ -37,10 +37,10 @@
 #include <cstdlib>
 
 #include "device_index.h"
+#include "launch.h"
 #include "search_common.h"
 
 namespace hx {
-#include "coop_rows.inc"
 namespace {
 
 // block placement hints for the f32 kernel's pass (a taken branch costs a lone wave ~30 cycles of
@@ -1469,99 +1469,25 @@ int launch_lean_q8(const LeanArgs &a_in, uint32_t nblocks, hipStream_t stream) {
     constexpr int R = LT::NR;
     LeanArgs a = a_in;
     // six- to eight-register lists (320 < ef <= 512): 32 KiB of LDS table + a second level in HBM, as launch_lean_one
-    struct Scratch {
-        void *p = nullptr;
-        hipStream_t st = nullptr;
-        ~Scratch() {
-            if (p) (void)hipFreeAsync(p, st);
-        }
-    } sp;
-    static const bool two_level = !(getenv("HNSW_MI355X_VISITED_2L") && atoi(getenv("HNSW_MI355X_VISITED_2L")) == 0);
-    if (R >= 6 && two_level && a.slots_log2 >= 13) {  // (also where 32 KiB would do for most queries: the few that fill it go on in HBM instead of being run again)
-        const uint32_t glog2 = std::max(15u, a.slots_log2 + 1);
-        sp.st = stream;
-        if (hipMallocAsync(&sp.p, ((size_t)nblocks << glog2) * 4, stream) != hipSuccess) {
-            (void)hipGetLastError();
-            sp.p = nullptr;
-        } else {
-            a.spill_tab = static_cast<uint32_t *>(sp.p);
-            a.spill_log2 = glog2;
-            a.slots_log2 = 13;
-            if (const char *e = getenv("HNSW_MI355X_VISITED_2L_LIMIT")) a.lds_limit = (uint32_t)atoi(e);
-        }
-    }
+    VisitedSpill sp(R >= 6 && a.slots_log2 >= 13, a, a.slots_log2, nblocks, stream);
     const size_t lds = (4ull << a.slots_log2) + (64ull * R + 64) * 8 + 2 * 56 * 4;
-    auto kern = hx_lean_q8_kernel<LT>;
-    if (lds > 160 * 1024) {
-        set_error("search needs %zu bytes of LDS (> 160 KiB)", lds);
-        return HNSW_ERR_ARG;
-    }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-            return HNSW_ERR_HIP;
-        }
-    }
-    HX_LAUNCH(kern, dim3(nblocks), dim3(64), lds, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("search kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"search kernel launch", "search needs %zu bytes of LDS (> 160 KiB)"}, hx_lean_q8_kernel<LT>,
+                          dim3(nblocks), dim3(64), lds, stream, a);
 }
 
 template <int DS, class LT, int CK = 4>
 int launch_lean_one(const LeanArgs &a_in, uint32_t nblocks, hipStream_t stream) {
     constexpr int R = LT::NR;
     LeanArgs a = a_in;
-    // eight-register lists (320 < ef <= 512): the LDS table stays at 32 KiB -- four waves per CU, a batch of 1024 in
-    // one round -- and a second level in HBM (stream-ordered scratch, 128 KiB per query) takes the ids beyond it
-    struct Scratch {
-        void *p = nullptr;
-        hipStream_t st = nullptr;
-        ~Scratch() {
-            if (p) (void)hipFreeAsync(p, st);
-        }
-    } sp;
-    static const bool two_level = !(getenv("HNSW_MI355X_VISITED_2L") && atoi(getenv("HNSW_MI355X_VISITED_2L")) == 0);
-    if (R >= 6 && two_level && a.slots_log2 >= 13) {  // (also where 32 KiB would do for most queries: the few that fill it go on in HBM instead of being run again)
-        const uint32_t glog2 = std::max(15u, a.slots_log2 + 1);
-        sp.st = stream;
-        if (hipMallocAsync(&sp.p, ((size_t)nblocks << glog2) * 4, stream) != hipSuccess) {
-            (void)hipGetLastError();
-            sp.p = nullptr;  // no scratch: the one-level table serves (two waves per CU)
-        } else {
-            a.spill_tab = static_cast<uint32_t *>(sp.p);
-            a.spill_log2 = glog2;
-            a.slots_log2 = 13;
-            if (const char *e = getenv("HNSW_MI355X_VISITED_2L_LIMIT")) a.lds_limit = (uint32_t)atoi(e);  // (tests: close the LDS level early)
-        }
-    }
+    // six- to eight-register lists (320 < ef <= 512): the LDS table stays at 32 KiB -- four waves per CU, a batch of 1024
+    // in one round -- and a second level in HBM (stream-ordered scratch, 128 KiB per query) takes the ids beyond it.  Also
+    // where 32 KiB would do for most queries: the few that fill it go on in HBM instead of being run again.  Without the
+    // scratch the one-level table serves (two waves per CU)
+    VisitedSpill sp(R >= 6 && a.slots_log2 >= 13, a, a.slots_log2, nblocks, stream);
     const size_t lds = (4ull << a.slots_log2) +
                        std::max<size_t>((64ull * R + 64) * 8, coop_rows<HNSW_VEC_F32, DS>() ? HX_COOP_IMG_BYTES + 256 : 0);
-    auto kern = hx_lean_f32_kernel<DS, LT, CK>;
-    if (lds > 160 * 1024) {
-        set_error("search needs %zu bytes of LDS (> 160 KiB)", lds);
-        return HNSW_ERR_ARG;
-    }
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-            return HNSW_ERR_HIP;
-        }
-    }
-    HX_LAUNCH(kern, dim3(nblocks), dim3(64), lds, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("search kernel launch: %s", hipGetErrorString(e));
-        return HNSW_ERR_HIP;
-    }
-    return HNSW_OK;
+    return launch_checked({"search kernel launch", "search needs %zu bytes of LDS (> 160 KiB)"}, hx_lean_f32_kernel<DS, LT, CK>,
+                          dim3(nblocks), dim3(64), lds, stream, a);
 }
 
 }  // namespace
@@ -1626,14 +1552,7 @@ int launch_lean(const DevView &v, const SearchArgs &s, uint32_t nblocks, uint32_
         return launch_lean_q8<LstHT>(a, nblocks, stream);
     }
     if (v.dim == 128) {  // whole-line rows: the cooperative gather (HNSW_MI355X_LEAN_128=0: the generic kernel, for A/B runs)
-        static const uint32_t n_cu = [] {
-            int dev = 0, cus = 0;
-            if (hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-                cus = 256;
-            return (uint32_t)cus;
-        }();
-        const bool few = nblocks <= 4 * n_cu;  // at most one wave per SIMD: the four-stage build (see the kernel)
+        const bool few = nblocks <= 4 * cu_count();  // at most one wave per SIMD: the four-stage build (see the kernel)
         if (a.ef <= 64) return few ? launch_lean_one<128, Lst<1>, 4>(a, nblocks, stream) : launch_lean_one<128, Lst<1>, 2>(a, nblocks, stream);
         if (a.ef > 384) return launch_lean_one<128, Lst<8>, 2>(a, nblocks, stream);  // (round 4: 256 < ef <= 512, two-level visited set)
         if (a.ef > 256) return launch_lean_one<128, Lst<6>, 2>(a, nblocks, stream);

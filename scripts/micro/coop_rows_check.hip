@@ -1,4 +1,4 @@
-// coop_rows_check.hip -- standalone check of f32_rows_coop (search_kernels.hip) against a host loop in
+// coop_rows_check.hip -- standalone check of f32_rows_coop (coop_rows.inc, through search_common.h) against a host loop in
 // FullVec's order (vectors/src/full.rs:23-29): random tables, random wanted-lane patterns (0..64 lanes),
 // every lane's sum compared bit for bit.  Diagnostic, not part of the library.
 //   hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -Ihnsw_rs_amd/csrc -Iinclude \
@@ -10,11 +10,9 @@
 #include <cstring>
 #include <vector>
 
-#include "search_common.h"
+#include "search_common.h"  // (includes coop_rows.inc)
 namespace hx {
 
-
-#include "coop_rows.inc"
 template <int DS>
 __global__ void __launch_bounds__(64) tk(const uint8_t *rows, const uint32_t *ids, const float *q, float *out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
