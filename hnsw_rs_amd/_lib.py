@@ -102,6 +102,12 @@ SYMBOLS = {
                                                           vp, vp, vp]),
     "hnsw_search_batch_filtered_range_device_finish": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp,
                                                                  vp, vp, vp, vp, u8p]),
+    "hnsw_search_batch_filtered_set_range": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, vp, u32p, u32p, u32p,
+                                                       u32p, f32p, u32p, C.POINTER(QueryStats), u8p]),
+    "hnsw_search_batch_filtered_set_range_device": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp,
+                                                              vp, vp, vp, vp, vp]),
+    "hnsw_search_batch_filtered_set_range_device_finish": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp,
+                                                                     vp, vp, vp, vp, vp, vp, vp, u8p]),
     "hnsw_search_batch_device": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
     "hnsw_search_batch_device_finish": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
     "hnsw_distance_batch": (C.c_int, [vp, f32p, u32p, C.c_uint64, f32p]),

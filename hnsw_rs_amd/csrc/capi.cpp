@@ -481,6 +481,62 @@ int hnsw_search_batch_filtered_range_device_finish(hnsw_index *h, const float *d
     return range_device(h, d_Q, nq, n, ef, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
 }
 
+// ---- searches under a label range AND a row of a resident mask set ------------------------------------------------
+int hnsw_search_batch_filtered_set_range(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                         hnsw_mask_set *set, const uint32_t *mask_of, const uint32_t *lo,
+                                         const uint32_t *hi, uint32_t *ids, float *dists, uint32_t *counts,
+                                         hnsw_query_stats *stats, uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK || (rc = check_set(h, set))) return rc;
+    if (nq == 0) return HNSW_OK;
+    if (!lo || !hi) {
+        set_error("filtered search: needs the label range (lo and hi) of every query");
+        return HNSW_ERR_ARG;
+    }
+    std::vector<uint32_t> row0;
+    if (!mask_of && nq <= 0x7FFFFFFFull) {  // every query under row 0 (more queries are refused below)
+        row0.assign(nq, 0);
+        mask_of = row0.data();
+    }
+    hx::MaskSpec m{set->words.data(), set->allow_bits, set->n_masks, mask_of, set};
+    m.lo = lo;
+    m.hi = hi;
+    const hx::PathCounters ctr = hx::filt_counters(h);
+    return hx::search_filtered_checked(h, Q, nq, n, ef, m, false, ids, dists, counts, stats, paths, &ctr);
+}
+
+static int set_range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, hnsw_mask_set *set,
+                            const uint32_t *d_mask_of, const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
+                            float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream, bool finish,
+                            uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK || (rc = check_set(h, set))) return rc;
+    if (nq == 0 || n == 0) return HNSW_OK;
+    if (!d_Q || !d_ids || !d_stats || !d_lo || !d_hi || nq > 0x7FFFFFFFull) {
+        set_error("filtered device search: needs queries, their label ranges, an id buffer and a stats buffer in HBM");
+        return HNSW_ERR_ARG;
+    }
+    return hx::search_device_filtered(h, hx::DeviceFilter{set, d_mask_of, d_lo, d_hi}, d_Q, nq, n, ef, d_ids, d_dists,
+                                      d_counts, d_stats, static_cast<hipStream_t>(stream), finish, paths);
+}
+
+int hnsw_search_batch_filtered_set_range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                                hnsw_mask_set *set, const uint32_t *d_mask_of, const uint32_t *d_lo,
+                                                const uint32_t *d_hi, uint32_t *d_ids, float *d_dists,
+                                                uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream) {
+    return set_range_device(h, d_Q, nq, n, ef, set, d_mask_of, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, false,
+                            nullptr);
+}
+
+int hnsw_search_batch_filtered_set_range_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n,
+                                                       uint32_t ef, hnsw_mask_set *set, const uint32_t *d_mask_of,
+                                                       const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
+                                                       float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
+                                                       void *stream, uint8_t *paths) {
+    return set_range_device(h, d_Q, nq, n, ef, set, d_mask_of, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, true,
+                            paths);
+}
+
 int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
                              uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
                              hnsw_query_stats *d_stats, void *stream) {
@@ -1115,6 +1171,10 @@ int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
         *out = h->n_filt_range_calls.load();
     } else if (!strcmp(key, "filtered_range_ranges")) {
         *out = h->n_filt_range_ranges.load();
+    } else if (!strcmp(key, "filtered_set_range_calls")) {
+        *out = h->n_filt_set_range_calls.load();
+    } else if (!strcmp(key, "filtered_set_range_groups")) {
+        *out = h->n_filt_set_range_groups.load();
     } else if (!strcmp(key, "filtered_multi_calls")) {
         *out = h->n_filt_multi_calls.load();
     } else if (!strcmp(key, "filtered_multi_masks")) {

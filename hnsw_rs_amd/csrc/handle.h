@@ -61,6 +61,8 @@ struct hnsw_index {
     // calls (host calls and completed device calls) and the distinct ranges they named
     hx::LabelColumn lab;
     std::atomic<uint64_t> n_filt_range_calls{0}, n_filt_range_ranges{0};
+    // ... and hnsw_search_batch_filtered_set_range's: calls, and the distinct (row, lo, hi) triples they named
+    std::atomic<uint64_t> n_filt_set_range_calls{0}, n_filt_set_range_groups{0};
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")
 };
 

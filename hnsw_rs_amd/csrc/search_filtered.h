@@ -16,8 +16,13 @@
 // where label(i) is labels[i] for i < label_len and 0 beyond it (the host keeps label_len at or above the index length,
 // with zeros beyond the labels that were set: the graph kernel has one bound for the id and for the label read).  The
 // graph kernel's wave takes its query's range from range_lo[q] / range_hi[q] (they may be the caller's device memory);
-// the exact path's kernels are launched per range with the scalars lo and hi.  lo > hi is an empty range: nothing is allowed and no label is read.  A call
-// has a column or masks, not both (allow and mask_of are nullptr with a column).
+// the exact path's kernels are launched per range with the scalars lo and hi.  lo > hi is an empty range: nothing is allowed and no label is read.
+//
+// A call may have a column AND the rows of a resident set (hnsw_search_batch_filtered_set_range): id i is then allowed iff
+// i < allow_bits, lo <= label(i) <= hi and its bit is set in the query's row; a HNSW_MASK_NONE query has no bit test and
+// the bound none_bits.  The graph kernel's wave picks its row by mask_of[q] as in a call with rows alone and keeps the
+// row's pointer next to its range; the compaction of an exact-path launch ANDs allow's word onto the word it made from
+// the labels (allow == nullptr there: the range alone).
 #pragma once
 
 #include "device_index.h"
@@ -26,7 +31,7 @@ namespace hx {
 
 #define HX_FILT_MAX_EF 256  // ef' on the graph path: F and R are four registers per lane at most
 #define HX_FILT_MAX_N 64    // results per query (both paths)
-#define HX_FILT_RANGE_LDS 16  // bytes of LDS a wave under a label range keeps its range in
+#define HX_FILT_RANGE_LDS 16  // bytes of LDS a wave under a label range keeps its range in (lo, hi - lo, its mask row's pointer)
 #define HX_FILT_MAX_SLOTS_LOG2 15  // the largest visited table: 32768 slots, at most 24576 ids (75 %)
 
 struct FilterArgs {
@@ -65,7 +70,7 @@ int launch_filtered_graph(const DevView &v, const FilterArgs &a, uint32_t nblock
                           hipStream_t stream);
 // exact path, step 1: the ascending list of admissible ids (a.allow, a.allow_bits, a.deny, a.deny_bits) in the
 // n_words words below allow_bits; with a.labels, "allowed" is the range [a.lo, a.hi] over the column and the kernel
-// makes the words itself.  word_base[b] = admissible ids in words [0, 64 b) (computed by the caller, who counts A
+// makes the words itself (and ANDs a.allow's onto them when that is set as well).  word_base[b] = admissible ids in words [0, 64 b) (computed by the caller, who counts A
 // anyway); ids[A]
 int launch_filter_compact(const FilterArgs &a, uint64_t n_words, const uint32_t *word_base, uint32_t *ids,
                           hipStream_t stream);

@@ -15,10 +15,13 @@
 //
 // With a label range instead of an allow-list (FilterArgs::labels) the allow test of a key is lo <= label(id) <= hi
 // over the resident column, lo and hi the wave's own (picked once, as its mask pointer, and kept in LDS), one 4-byte
-// read per key that got as far as a mask word is read otherwise.
+// read per key that got as far as a mask word is read otherwise.  With a label range AND a row of a resident mask set
+// (FilterArgs::labels and ::allow together) a key is allowed when its label is in the wave's range and its bit is set in
+// the wave's row, the row pointer kept in LDS next to the range.
 //
 // Exact path: hx_filt_compact_kernel lists the allowed, undeleted ids in ascending order (the allowed bits of a word
-// read from the mask, or, under a label range, made from 64 coalesced reads of the column); hx_filt_scan_kernel scans
+// read from the mask, or, under a label range, made from 64 coalesced reads of the column, or that word ANDed with the
+// mask's under both); hx_filt_scan_kernel scans
 // one segment of that list per block and keeps its n best (the shape of hx_brute_kernel),
 // hx_filt_merge_kernel merges a query's segments.
 //
@@ -164,22 +167,29 @@ __device__ __forceinline__ bool filt_visit(uint32_t *tab, uint32_t slots_log2, u
 // admissible: allowed (below the query's bound, its label in the query's range when the call has a label column, and
 // its bit set when the query has a mask) and not deleted.  The pointer tests are uniform over the wave (a kernel
 // argument, and the wave's own filter: one query per wave); a label or a mask word is read only for an id that got
-// that far.  `filt` is the wave's one filter pointer: its mask row, or, with bit 0 set, the label column -- a call has
-// masks or a column, and the kernel has no scalar register to spare for a second pointer or for the range, which the
-// wave keeps in LDS (`range`: lo, hi - lo) and reads next to the label.  (Measured: the range in two more scalar
-// registers costs the f32 100d and 128d kernels with one list register 6 and 2 vector registers, and the 128d one a wave of
-// occupancy)  The bound of an empty range is 0: no label is read under it.
-__device__ __forceinline__ bool filt_allowed(const FilterArgs &a, const uint64_t *filt, uint64_t bound,
+// that far.  `filt` is the wave's one filter pointer: its mask row, or, with bit 0 set, the label column -- the kernel
+// has no scalar register to spare for a second pointer or for the range, which the wave keeps in LDS (`range`: lo,
+// hi - lo) and reads next to the label.  (Measured: the range in two more scalar registers costs the f32 100d and 128d
+// kernels with one list register 6 and 2 vector registers, and the 128d one a wave of occupancy; DESIGN.md section
+// 16.)  A wave under a range AND a mask row (hnsw_search_batch_filtered_set_range) keeps its row pointer in the other
+// half of the LDS slot, nullptr without a row: one 16-byte read brings the range and the row, and the mask word is read
+// for an id whose label passed.  The bound of an empty range is 0: no label is read under it.  The bound and the deleted
+// set's (deny_n: 0 when nothing is deleted, so there is no pointer test) are 32 bits, as an id is, and one scalar register
+// each: what the row costs in the prologue is paid for here.
+__device__ __forceinline__ bool filt_allowed(const uint64_t *deny, uint32_t deny_n, const uint64_t *filt, uint32_t bound,
                                              const uint32_t *range, uint32_t id) {
-    if ((uint64_t)id >= bound) return false;
+    if (id >= bound) return false;
     if ((uintptr_t)filt & 1) {
-        const uint2 r = *reinterpret_cast<const uint2 *>(range);
         const uint32_t label = reinterpret_cast<const uint32_t *>((uintptr_t)filt - 1)[id];
-        if (label - r.x > r.y) return false;  // lo <= label <= hi in one unsigned compare
+        const uint4 r = *reinterpret_cast<const uint4 *>(range);
+        bool in = label - r.x <= r.y;  // lo <= label <= hi in one unsigned compare
+        const uint64_t *row = reinterpret_cast<const uint64_t *>(((uint64_t)r.w << 32) | r.z);
+        if (in && row) in = ((row[id >> 6] >> (id & 63)) & 1ull) != 0;
+        if (!in) return false;
     } else if (filt && ((filt[id >> 6] >> (id & 63)) & 1ull) == 0) {
         return false;
     }
-    return !(a.deny && (uint64_t)id < a.deny_bits && ((a.deny[id >> 6] >> (id & 63)) & 1ull) != 0);
+    return !(id < deny_n && ((deny[id >> 6] >> (id & 63)) & 1ull) != 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -304,24 +314,27 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
     // own error, decided for the whole wave before a mask word is read: no walk (the status below), padded outputs,
     // and an id bound of 0, under which filt_allowed refuses every id before it touches the row pointer
     const bool bad_row = a.mask_of && g != HNSW_MASK_NONE && g >= a.n_masks;
-    const uint64_t *allow = a.labels              ? reinterpret_cast<const uint64_t *>((uintptr_t)a.labels | 1)
-                            : g == HNSW_MASK_NONE ? nullptr
-                                                  : a.allow + (size_t)g * a.mask_words;
+    // (without rows a.allow is nullptr and g * a.mask_words is 0: no row)
+    const uint64_t *row = g == HNSW_MASK_NONE ? nullptr : a.allow + (size_t)g * a.mask_words;
+    const uint64_t *allow = a.labels ? reinterpret_cast<const uint64_t *>((uintptr_t)a.labels | 1) : row;
     // the wave's label range, picked once as well; an empty one (lo > hi) allows nothing: an id bound of 0.  Under a
     // column the bound is also the bound of the label read: the host keeps the HBM copy at least as long as the index
     // (zeros beyond the labels that were set), so label_len never is the smaller one
     const uint32_t lo = a.labels ? a.range_lo[q] : 0u, hi = a.labels ? a.range_hi[q] : 0u;
-    const uint64_t bound = bad_row || lo > hi      ? 0
-                           : a.labels              ? min(a.allow_bits, a.label_len)
-                           : g == HNSW_MASK_NONE ? a.none_bits
-                                                   : a.allow_bits;
+    const uint64_t ids = g == HNSW_MASK_NONE ? a.none_bits : a.allow_bits;
+    // (an id is below 2^32 - 1, HX_EMPTY_SLOT: the bound fits 32 bits)
+    const uint32_t bound = bad_row || lo > hi ? 0u : (uint32_t)min(a.labels ? min(ids, a.label_len) : ids, (uint64_t)HX_EMPTY_SLOT);
+    // the ids the deleted set's mask covers, as the bound of its test: 0 when nothing is deleted
+    const uint32_t deny_n = a.deny ? (uint32_t)min(a.deny_bits, (uint64_t)HX_EMPTY_SLOT) : 0u;
     uint32_t *htab = reinterpret_cast<uint32_t *>(smem);
     u64 *perm = reinterpret_cast<u64 *>(smem + (4ull << slots_log2));
     float *yq = reinterpret_cast<float *>(perm + 64 * R);
-    uint32_t *range = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(yq) + query_lds_bytes(v));
+    // (the query's size is the template's where the dimension is: the range's slot at a constant offset, no scalar kept)
+    constexpr uint32_t YQ_BYTES = DS == 0 ? 0u : ((KIND == HNSW_VEC_QUANT8 ? 2u * (16u * P - 8u) * 4u : DS * 4u) + 15u) & ~15u;
+    uint32_t *range = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(yq) + (YQ_BYTES ? YQ_BYTES : query_lds_bytes(v)));
     if (a.labels && lane == 0) {  // (read after the wave_fence of the first clear_visited)
-        range[0] = lo;
-        range[1] = hi - lo;
+        // the wave's mask row, when the call has rows as well, next to its range: one 16-byte read brings both
+        *reinterpret_cast<uint4 *>(range) = make_uint4(lo, hi - lo, (uint32_t)(uintptr_t)row, (uint32_t)((uintptr_t)row >> 32));
     }
     const uint32_t vis_limit = filt_visited_limit(slots_log2);
 
@@ -437,7 +450,7 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
             wave_fence();
             n_vis = 1;
             F.merge(lane == 0 ? best : FKEY_INVALID, ef, perm, lane);
-            Rl.merge(lane == 0 && filt_allowed(a, allow, bound, range, (uint32_t)best) ? best : FKEY_INVALID, ef, perm, lane);
+            Rl.merge(lane == 0 && filt_allowed(a.deny, deny_n, allow, bound, range, (uint32_t)best) ? best : FKEY_INVALID, ef, perm, lane);
         }
         while (status == HNSW_OK && F.n_cur > 0) {
             const u64 c = F.front();
@@ -446,7 +459,7 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
             expand((uint32_t)c, 0, [&](u64 key) {
                 // admitted against the bound at the start of the pass; R takes the allowed ones
                 const bool adm = key != FKEY_INVALID && (!Rl.full(ef) || key < Rl.last);
-                const bool alw = adm && filt_allowed(a, allow, bound, range, (uint32_t)key);
+                const bool alw = adm && filt_allowed(a.deny, deny_n, allow, bound, range, (uint32_t)key);
                 F.merge(adm ? key : FKEY_INVALID, ef, perm, lane);
                 Rl.merge(alw ? key : FKEY_INVALID, ef, perm, lane);
             });
@@ -477,7 +490,8 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
 // word_base[b] + (admissible ids of the wave's lower lanes).  Under a label range there is no mask word to read: the
 // wave makes its 64 words together, word 64 b + j from the 64 consecutive labels of its ids -- one coalesced 256-byte
 // read by the 64 lanes, the range test balloted, the ballot kept by lane j.  (A lane that read the 64 labels of its
-// own word would touch 64 lines per wave instruction: the gather shape of DESIGN.md section 10.)
+// own word would touch 64 lines per wave instruction: the gather shape of DESIGN.md section 10.)  Under a range AND a
+// mask (a.labels and a.allow) the word made from the labels is ANDed with the mask's.
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) hx_filt_compact_kernel(const FilterArgs a, uint64_t n_words,
                                                              const uint32_t *word_base, uint32_t *ids) {
@@ -495,7 +509,10 @@ __global__ void __launch_bounds__(64) hx_filt_compact_kernel(const FilterArgs a,
                 if (lane == j) bits = in;
             }
         }
-        if (w >= n_words) bits = 0;
+        if (w >= n_words)
+            bits = 0;
+        else if (a.allow)  // a range AND a mask row: the word made from the labels, ANDed with the row's
+            bits &= a.allow[w];
     } else {
         bits = w < n_words ? (a.allow ? a.allow[w] : ~0ull) : 0;
     }

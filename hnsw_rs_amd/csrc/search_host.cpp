@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace hx {
@@ -284,15 +285,18 @@ int filtered_exact(const DevView &v, const FilterArgs &a, uint64_t nsel, const u
 }
 
 // ---- the filter of a call --------------------------------------------------------------------------------------
-// A query's filter is named by one 64-bit key: 0 in a call with one mask (or with none: the undeleted ids), the row or
-// HNSW_MASK_NONE in a call with rows (the caller's or a resident set's), (lo << 32) | hi in a call with label ranges.
-// The queries under one key are a group: the planner's unit, and that of the exact path's launches.
+// A query's filter is named by a key and a range.  The key: 0 in a call with one mask (or with none: the undeleted ids)
+// and in a call with label ranges alone, the row or HNSW_MASK_NONE in a call with rows (the caller's or a resident
+// set's).  The range: (lo << 32) | hi in a call with label ranges (alone, or next to the rows of a set), FULL_RANGE
+// otherwise.  The queries under one (key, range) are a group: the planner's unit, and that of the exact path's launches.
 constexpr uint64_t UNCOUNTED = ~0ull;
+constexpr uint64_t FULL_RANGE = 0xFFFFFFFFull;  // [0, UINT32_MAX]
 constexpr size_t NO_WB = ~(size_t)0;
 struct Group {
-    uint64_t key = 0;
+    uint64_t key = 0, range = FULL_RANGE;
     size_t q0 = 0, nq = 0;             // its queries: [q0, q0 + nq) of the sorted list it was cut from
-    uint64_t A = UNCOUNTED;            // admissible ids
+    uint64_t A = UNCOUNTED;            // admissible ids (a row AND a range planned on the graph path: not counted, at most A_ub)
+    uint64_t A_ub = 0;
     bool exact = false;                // A <= filter_exact_max: planned on the exact path
     size_t wb = NO_WB, n_wb = 0;       // its word offsets in the list they were counted into (NO_WB: not counted yet)
     const uint32_t *d_list = nullptr;  // a set row's cached list of admissible ids in HBM, when it is valid
@@ -301,26 +305,31 @@ struct Group {
 // What turns a key into what the exact path needs, one per call: the masks, set or label column behind the keys, the
 // key of every query (host memory) and the call's own arguments.
 struct FilterSource {
-    enum Kind { ONE, ROWS, SET, RANGE } kind;
+    enum Kind { ONE, ROWS, SET, RANGE, SET_RANGE } kind;
     hnsw_index *h;
     const uint64_t *masks;  // ONE, ROWS: the caller's words (nullptr: every id below bits)
     hnsw_mask_set *set;     // SET
     uint64_t len, bits, row_words;  // the index length, min(allow_bits, len), words of a row
-    const uint32_t *mask_of = nullptr, *lo = nullptr, *hi = nullptr;  // per query: ROWS and SET (nullptr: row 0), RANGE
+    const uint32_t *mask_of = nullptr, *lo = nullptr, *hi = nullptr;  // per query: ROWS, SET and SET_RANGE (nullptr: row 0); RANGE and SET_RANGE
     FilterArgs base{};      // every mask or range: the graph kernel's wave picks its query's
 
     FilterSource(hnsw_index *h_, Kind k, const uint64_t *masks_, hnsw_mask_set *set_, uint64_t allow_bits)
         : kind(k), h(h_), masks(masks_), set(set_), len(index_len(h_)), bits(std::min<uint64_t>(allow_bits, len)),
           row_words((allow_bits + 63) / 64) {}
 
-    uint64_t key(uint32_t i) const {
-        if (kind == RANGE) return ((uint64_t)lo[i] << 32) | hi[i];
-        return mask_of ? mask_of[i] : 0;
-    }
+    bool of_set() const { return kind == SET || kind == SET_RANGE; }
+    bool labelled() const { return kind == RANGE || kind == SET_RANGE; }
+    uint64_t key(uint32_t i) const { return kind != RANGE && mask_of ? mask_of[i] : 0; }
+    uint64_t range(uint32_t i) const { return labelled() ? ((uint64_t)lo[i] << 32) | hi[i] : FULL_RANGE; }
     // the key names a row with words (masks may be NULL when allow_bits is 0: nothing is allowed, no word is read)
     bool has_words(uint64_t key) const {
         if (kind == ONE) return masks != nullptr;
-        return key != HNSW_MASK_NONE && (kind == ROWS ? masks != nullptr : kind == SET && set->W != 0);
+        return key != HNSW_MASK_NONE && (kind == ROWS ? masks != nullptr : of_set() && set->W != 0);
+    }
+    // the group is under a label range.  Next to a set, [0, UINT32_MAX] is no range: the group is the plain row, with the
+    // set's caches (and so is a row of a set without words: nothing is allowed); under HNSW_MASK_NONE it is the plain range
+    bool ranged(const Group &g) const {
+        return kind == RANGE || (kind == SET_RANGE && g.range != FULL_RANGE && (g.key == HNSW_MASK_NONE || set->W != 0));
     }
     // its id bound (a range call's bits are the index length)
     uint64_t bound(uint64_t key) const { return key == HNSW_MASK_NONE ? len : bits; }
@@ -337,45 +346,100 @@ struct FilterSource {
         base.n_masks = n_masks;  // the kernel checks mask_of against it (the host may not have seen those words)
         base.deny = h->del.count ? h->del.d_words : nullptr;
         base.deny_bits = h->del.count ? h->del.deny_bits() : 0;
-        if (kind == RANGE) bind_labels(h, base);
+        if (labelled()) bind_labels(h, base);
         base.range_lo = d_lo;
         base.range_hi = d_hi;
         base.n = n;
         base.ef = efp;
     }
-    // the arguments of an exact-path launch: the group's mask or range alone
+    // the arguments of an exact-path launch: the group's mask, its range, or both, alone
     FilterArgs args(const Group &g) const {
         FilterArgs ax = base;
+        const bool rg = ranged(g);
         ax.mask_of = nullptr;
         ax.allow = has_words(g.key) ? base.allow + g.key * row_words : nullptr;
         ax.allow_bits = bound(g.key);
-        ax.range_lo = ax.range_hi = nullptr;  // (a range call: the group's range as scalars)
-        ax.lo = kind == RANGE ? (uint32_t)(g.key >> 32) : 0;
-        ax.hi = kind == RANGE ? (uint32_t)g.key : 0;
+        ax.range_lo = ax.range_hi = nullptr;  // (the group's range as scalars)
+        if (!rg) ax.labels = nullptr;         // (a plain row next to ranged groups: the compaction reads its words alone)
+        ax.lo = rg ? (uint32_t)(g.range >> 32) : 0;
+        ax.hi = rg ? (uint32_t)g.range : 0;
         return ax;
     }
 
     // What `resolve` reads is locked by this: a set's caches (a row is counted when it, the deleted set or the length
-    // changed), or the label column's sorted copy (made here when the column, the deleted set or the length changed)
-    std::unique_lock<std::mutex> lock() const {
-        std::unique_lock<std::mutex> l;
-        if (kind == SET) l = std::unique_lock<std::mutex>(set->mu);
-        if (kind == RANGE) {
-            l = std::unique_lock<std::mutex>(h->lab.mu);
-            h->lab.sort_for(h->del, len);
-        }
+    // changed), and the label column's sorted copy (made under the lock when the column, the deleted set or the length
+    // changed: here, or next to a set by the first group that has a range).  The set's first, then the column's
+    struct Locks {
+        std::unique_lock<std::mutex> set, lab;
+        bool held() const { return set.owns_lock() || lab.owns_lock(); }
+    };
+    Locks lock() const {
+        Locks l;
+        if (of_set()) l.set = std::unique_lock<std::mutex>(set->mu);
+        if (labelled()) l.lab = std::unique_lock<std::mutex>(h->lab.mu);
+        if (kind == RANGE) h->lab.sort_for(h->del, len);
         return l;
+    }
+    // The admissible ids of a row AND a range: the undeleted ids below `bits` whose bit is set in the row and whose
+    // label lies in [lo, hi].  Neither side's count says how many: the cheaper side is walked -- the range's slice of
+    // the sorted copy (undeleted ids already) testing the row's bits, or the row's set bits testing labels -- and only
+    // while the count stays within `limit`: beyond it the group is on the graph path and the count is not needed
+    // (UNCOUNTED; A_ub, the smaller side, bounds it).  The same walk gives the compaction's offsets, the admissible ids
+    // before every block of 64 words.  The row's own cached count is read; its offsets and its list are the row's alone
+    uint64_t count_both(uint32_t row, uint32_t lo, uint32_t hi, int64_t limit, std::vector<uint32_t> &wbase, uint64_t &A_ub) const {
+        uint64_t first = 0;
+        const uint64_t S = h->lab.count(lo, hi, &first), RA = set->counted(h, row).A;
+        A_ub = std::min(S, RA);
+        const uint64_t n_words = (bits + 63) / 64, n_wblk = std::max<uint64_t>(1, (n_words + 63) / 64);
+        const uint64_t *w = set->row_words(row);
+        uint64_t A = 0;
+        if (S <= RA) {
+            wbase.assign(n_wblk + 1, 0);  // ids per block, shifted by one
+            for (uint64_t i = first; i < first + S; i++) {
+                const uint32_t id = (uint32_t)h->lab.sorted[i];
+                if (id >= bits || ((w[id >> 6] >> (id & 63)) & 1ull) == 0) continue;
+                if ((int64_t)++A > limit) return UNCOUNTED;
+                wbase[(id >> 12) + 1]++;
+            }
+            for (size_t b = 1; b < wbase.size(); b++) wbase[b] += wbase[b - 1];
+            wbase.pop_back();
+        } else {
+            const std::vector<uint64_t> &deny = h->del.words;
+            const bool denies = h->del.count > 0;
+            wbase.assign(n_wblk, 0);
+            for (uint64_t ww = 0; ww < n_words; ww++) {
+                if (ww % 64 == 0) wbase[ww / 64] = (uint32_t)A;
+                uint64_t x = w[ww];
+                if (ww == n_words - 1 && bits % 64) x &= (1ull << (bits % 64)) - 1;
+                if (denies && ww < deny.size()) x &= ~deny[ww];
+                for (; x; x &= x - 1) {
+                    if (h->lab.get(ww * 64 + (uint64_t)__builtin_ctzll(x)) - lo > hi - lo) continue;
+                    if ((int64_t)++A > limit) return UNCOUNTED;
+                }
+            }
+        }
+        return A;
     }
     // Counts a group: A (kept when it is known already), exact = A <= exact_max, a set row's list while it is valid, and
     // its word offsets, appended to wbs.  A range's admissible ids are a slice of the sorted copy, found by two binary
-    // searches; its offsets cost a pass over the slice and are counted only when it is exact
+    // searches; its offsets cost a pass over the slice and are counted only when it is exact.  A row AND a range are
+    // counted by count_both, up to exact_max
     void resolve(Group &g, int64_t exact_max, std::vector<uint32_t> &wbs) const {
         std::vector<uint32_t> own;
         const std::vector<uint32_t> *wb = &own;
+        const bool rg = ranged(g), both = rg && has_words(g.key);
+        const uint32_t lo = (uint32_t)(g.range >> 32), hi = (uint32_t)g.range;
         uint64_t A, first = 0;
-        if (kind == RANGE) {
-            A = h->lab.count((uint32_t)(g.key >> 32), (uint32_t)g.key, &first);
-        } else if (kind == SET && has_words(g.key)) {
+        if (rg && kind == SET_RANGE) h->lab.sort_for(h->del, len);
+        if (both) {
+            A = lo > hi ? 0 : count_both((uint32_t)g.key, lo, hi, exact_max, own, g.A_ub);
+            if (A == UNCOUNTED) {
+                g.exact = false;
+                return;
+            }
+        } else if (rg) {
+            A = h->lab.count(lo, hi, &first);
+        } else if (of_set() && has_words(g.key)) {
             const hnsw_mask_set::Row &r = set->counted(h, (uint32_t)g.key);
             A = r.A;
             wb = &r.wbase;
@@ -385,26 +449,29 @@ struct FilterSource {
         }
         if (g.A == UNCOUNTED) g.A = A;
         g.exact = (int64_t)g.A <= exact_max;
-        if (kind == RANGE) {
-            if (!g.exact) return;
-            h->lab.word_base(first, g.A, len, own);
-        }
+        if (rg && !g.exact) return;
+        if (rg && !both) h->lab.word_base(first, g.A, len, own);
         g.wb = wbs.size();
         g.n_wb = wb->size();
         wbs.insert(wbs.end(), wb->begin(), wb->end());
     }
 };
 
-// stable-sorts query indices by key and cuts them into runs: ascending key (HNSW_MASK_NONE last among rows), the
-// caller's order within a key
+// stable-sorts query indices by (key, range) and cuts them into runs: ascending key (HNSW_MASK_NONE last among rows),
+// ascending range within a key, the caller's order within a run
+bool group_before(const Group &g, uint64_t key, uint64_t range) { return g.key != key ? g.key < key : g.range < range; }
 std::vector<Group> group_by_key(std::vector<uint32_t> &idx, const FilterSource &src) {
-    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t i, uint32_t j) { return src.key(i) < src.key(j); });
+    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t i, uint32_t j) {
+        const uint64_t ki = src.key(i), kj = src.key(j);
+        return ki != kj ? ki < kj : src.range(i) < src.range(j);
+    });
     std::vector<Group> runs;
     for (size_t k = 0; k < idx.size(); k++) {
-        const uint64_t key = src.key(idx[k]);
-        if (k == 0 || key != runs.back().key) {
+        const uint64_t key = src.key(idx[k]), range = src.range(idx[k]);
+        if (k == 0 || key != runs.back().key || range != runs.back().range) {
             runs.emplace_back();
             runs.back().key = key;
+            runs.back().range = range;
             runs.back().q0 = k;
         }
         runs.back().nq++;
@@ -428,7 +495,7 @@ struct ExactPlace {
 int exact_group(const FilterSource &src, const Group &g, const uint32_t *d_sel, uint64_t shape_nsel, const ExactPlace &at) {
     if (!g.d_list && at.send) {  // compacted in the scratch: a row beyond the set's budget, or no row of the set
         HIP_TRY(hipMemcpyAsync(at.d_wb + g.wb, at.wbs + g.wb, g.n_wb * 4, hipMemcpyHostToDevice, at.stream));
-        if (src.kind == FilterSource::SET && src.has_words(g.key)) src.h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
+        if (src.of_set() && src.has_words(g.key) && !src.ranged(g)) src.h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
     }
     return filtered_exact(src.h->dev.view, src.args(g), g.nq, d_sel, g.A, at.d_wb + g.wb, shape_nsel, at.x, at.dv, at.stream,
                           g.d_list);
@@ -448,26 +515,26 @@ int path2(const FilterSource &src, const std::vector<uint32_t> &sel, std::vector
     std::vector<uint32_t> sel2 = sel, wb_late;
     std::vector<Group> runs = group_by_key(sel2, src);
     for (uint32_t i : sel) path[i] = 2;
-    std::unique_lock<std::mutex> lock;  // (a set's stays until the end: its lists are read by the launches)
+    FilterSource::Locks lock;  // (a set's stays until the end: its lists are read by the launches)
     std::vector<bool> late(runs.size(), false);
     uint64_t A_max = 0;
     size_t n_wb = 0;
     for (size_t k = 0; k < runs.size(); k++) {
         Group &g = runs[k];
         if (planned) {
-            const Group &p = *std::lower_bound(planned->begin(), planned->end(), g.key,
-                                               [](const Group &x, uint64_t key) { return x.key < key; });
+            const Group &p = *std::lower_bound(planned->begin(), planned->end(), g,
+                                               [](const Group &x, const Group &y) { return group_before(x, y.key, y.range); });
             g.A = p.A, g.wb = p.wb, g.n_wb = p.n_wb, g.d_list = p.d_list;
         }
         if (g.wb == NO_WB) {
-            if (!lock.owns_lock()) lock = src.lock();
+            if (!lock.held()) lock = src.lock();
             src.resolve(g, INT64_MAX, wb_late);
             late[k] = true;
         }
         A_max = std::max(A_max, g.A);
         n_wb = std::max(n_wb, g.n_wb);
     }
-    if (src.kind == FilterSource::RANGE && lock.owns_lock()) lock.unlock();  // (the column's: never across a sync)
+    if (lock.lab.owns_lock()) lock.lab.unlock();  // (the column's: never across a sync)
     if (grow) {
         at.x = ExactScratch(align256(sel2.size() * 4), sel2.size(), src.base.n, A_max, n_wb);
         int r = grow->prepare(src.h->dev.device, at.x.end, pin_bytes);
@@ -528,11 +595,18 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     }
     const uint32_t efp = std::max(std::max(ef, n), 1u);
     // (the entry points see to hi with lo, and to mask_of with a set)
-    FilterSource src(h, m.lo ? FilterSource::RANGE : m.set ? FilterSource::SET : m.mask_of ? FilterSource::ROWS : FilterSource::ONE,
+    FilterSource src(h,
+                     m.lo && m.set ? FilterSource::SET_RANGE
+                     : m.lo        ? FilterSource::RANGE
+                     : m.set       ? FilterSource::SET
+                     : m.mask_of   ? FilterSource::ROWS
+                                   : FilterSource::ONE,
                      m.masks, m.set, m.allow_bits);
     src.mask_of = m.mask_of, src.lo = m.lo, src.hi = m.hi;
     hnsw_mask_set *const set = m.set;
-    const bool ranged = src.kind == FilterSource::RANGE, multi = src.kind != FilterSource::ONE;
+    // ranged: the call has a label column (next to a set: both); rowed: it has a row per query
+    const bool ranged = src.labelled(), both = src.kind == FilterSource::SET_RANGE, multi = src.kind != FilterSource::ONE;
+    const bool rowed = multi && src.kind != FilterSource::RANGE;
     const uint64_t len = src.len, bits = src.bits, row_words = src.row_words;
     // ---- the planner, per group: its admissible ids decide its queries' path.  A set stays locked until its HBM copy
     // is up to date and the lists this call needs are made; the label column only while the ranges are counted ----
@@ -546,13 +620,13 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     }
     std::vector<uint32_t> wb_all;
     uint64_t A_max = 0, n_graph = 0, n_exact = 0;
-    std::unique_lock<std::mutex> lock = src.lock();
+    FilterSource::Locks lock = src.lock();
     for (Group &g : groups) {
         src.resolve(g, exact_only ? INT64_MAX : h->filter_exact_max, wb_all);
-        A_max = std::max(A_max, g.A);
+        A_max = std::max(A_max, g.A == UNCOUNTED ? g.A_ub : g.A);  // (the scratch of a path 2 group is sized by it)
         (g.exact ? n_exact : n_graph) += g.nq;
     }
-    if (ranged) lock.unlock();
+    if (ranged) lock.lab.unlock();
     if (n_graph && efp > HX_FILT_MAX_EF) {
         set_error("filtered search: ef' = max(ef, n) = %u is above the graph path's maximum of %d", efp, HX_FILT_MAX_EF);
         return HNSW_ERR_ARG;
@@ -579,11 +653,12 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     // The result block comes back in one copy to pinned memory: the caller's block, or the scratch's and from there to
     // the caller's buffers
     // (a set's rows are in HBM already: nothing goes up, and the arena has no masks; a range call has no masks
-    // either: its "mask of every query" is the two arrays lo and hi, and its word offsets have room for one more range,
-    // that of a path 2 group, counted when a query gets there)
+    // either: its "mask of every query" is the two arrays lo and hi -- three arrays next to a set: row, lo, hi -- and its
+    // word offsets have room for one more range, that of a path 2 group, counted when a query gets there)
     const uint64_t up_words = !m.masks || set ? 0 : multi ? (uint64_t)m.n_masks * row_words : (bits + 63) / 64;
     const size_t o_q = 0, o_mask = o_q + align256(nq * d * 4), o_mof = o_mask + align256(up_words * 8);
-    const size_t o_sel = o_mof + (ranged ? 2 : 1) * align256(multi ? nq * 4 : 0), o_xsel = o_sel + align256(nq * 4);
+    const size_t o_lo = o_mof + (rowed ? align256(nq * 4) : 0), o_hi = o_lo + (ranged ? align256(nq * 4) : 0);
+    const size_t o_sel = o_hi + (ranged ? align256(nq * 4) : 0), o_xsel = o_sel + align256(nq * 4);
     const size_t wb_lazy = ranged ? std::max<uint64_t>(1, ((len + 63) / 64 + 63) / 64) : 0;
     const ExactScratch x(o_xsel + align256(multi ? nq * 4 : 0), nq, n, A_max, wb_all.size() + wb_lazy);
     const size_t o_out = x.end;
@@ -594,7 +669,8 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     unsigned char *dv = static_cast<unsigned char *>(s.dev);
     void *hv = pin_block ? pin_block : s.pin;
     uint32_t *d_sel = reinterpret_cast<uint32_t *>(dv + o_sel), *d_xsel = reinterpret_cast<uint32_t *>(dv + o_xsel);
-    uint32_t *d_mof = reinterpret_cast<uint32_t *>(dv + o_mof), *d_mof2 = reinterpret_cast<uint32_t *>(dv + o_mof + align256(nq * 4));
+    uint32_t *d_mof = reinterpret_cast<uint32_t *>(dv + o_mof), *d_lo = reinterpret_cast<uint32_t *>(dv + o_lo),
+             *d_hi = reinterpret_cast<uint32_t *>(dv + o_hi);
     HIP_TRY(hipMemcpyAsync(dv + o_q, Q, nq * d * 4, hipMemcpyHostToDevice, s.stream));
     if ((rc = cosine_queries(h, dv + o_q, nq, s.stream))) return rc;
     if (up_words) HIP_TRY(hipMemcpyAsync(dv + o_mask, m.masks, up_words * 8, hipMemcpyHostToDevice, s.stream));
@@ -604,17 +680,16 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         HIP_TRY(hipMemcpyAsync(at.d_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, s.stream));
     if (multi) {
         if (ranged) {
-            HIP_TRY(hipMemcpyAsync(d_mof, m.lo, nq * 4, hipMemcpyHostToDevice, s.stream));
-            HIP_TRY(hipMemcpyAsync(d_mof2, m.hi, nq * 4, hipMemcpyHostToDevice, s.stream));
-        } else {
-            HIP_TRY(hipMemcpyAsync(d_mof, m.mask_of, nq * 4, hipMemcpyHostToDevice, s.stream));
+            HIP_TRY(hipMemcpyAsync(d_lo, m.lo, nq * 4, hipMemcpyHostToDevice, s.stream));
+            HIP_TRY(hipMemcpyAsync(d_hi, m.hi, nq * 4, hipMemcpyHostToDevice, s.stream));
         }
+        if (rowed) HIP_TRY(hipMemcpyAsync(d_mof, m.mask_of, nq * 4, hipMemcpyHostToDevice, s.stream));
         if (!gsel.empty()) HIP_TRY(hipMemcpyAsync(d_sel, gsel.data(), gsel.size() * 4, hipMemcpyHostToDevice, s.stream));
         if (n_exact) HIP_TRY(hipMemcpyAsync(d_xsel, order.data(), nq * 4, hipMemcpyHostToDevice, s.stream));
     }
     src.bind(reinterpret_cast<const float *>(dv + o_q),
              set ? set->d_rows() : up_words ? reinterpret_cast<const uint64_t *>(dv + o_mask) : nullptr,
-             multi && !ranged ? d_mof : nullptr, ranged ? d_mof : nullptr, ranged ? d_mof2 : nullptr, m.n_masks, n, efp);
+             rowed ? d_mof : nullptr, ranged ? d_lo : nullptr, ranged ? d_hi : nullptr, m.n_masks, n, efp);
     FilterArgs &a = src.base;
     a.qsel = gsel.empty() ? nullptr : d_sel;
     out.bind(a, dv + o_out);
@@ -624,7 +699,7 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         const uint64_t budget = h->mask_set_cache_mb > 0 ? (uint64_t)h->mask_set_cache_mb << 20 : 0;
         std::vector<hnsw_mask_set::Row *> made;
         for (Group &g : groups) {
-            if (!src.has_words(g.key)) continue;
+            if (!src.has_words(g.key) || src.ranged(g)) continue;  // (a row AND a range: compacted in the scratch, not the row's list)
             hnsw_mask_set::Row &r = set->rows[(size_t)g.key];
             if (!r.list_valid && g.exact && set->reserve_list(r, budget)) {
                 HIP_TRY(hipMemcpyAsync(at.d_wb + g.wb, at.wbs + g.wb, g.n_wb * 4, hipMemcpyHostToDevice, s.stream));
@@ -638,7 +713,7 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
             HIP_TRY(hipStreamSynchronize(s.stream));
             for (hnsw_mask_set::Row *r : made) r->list_valid = true;
         }
-        lock.unlock();
+        lock.set.unlock();
     }
     auto fetch = [&](const hnsw_query_stats *&st) -> int {
         HIP_TRY(hipMemcpyAsync(hv, dv + o_out, out.bytes, hipMemcpyDeviceToHost, s.stream));
@@ -672,7 +747,10 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         ctr->graph->fetch_add(n_graph - n2, std::memory_order_relaxed);
         ctr->overflow->fetch_add(n2, std::memory_order_relaxed);
     }
-    if (set) {
+    if (both) {
+        h->n_filt_set_range_calls.fetch_add(1, std::memory_order_relaxed);
+        h->n_filt_set_range_groups.fetch_add(groups.size(), std::memory_order_relaxed);
+    } else if (set) {
         h->n_filt_set_calls.fetch_add(1, std::memory_order_relaxed);
     } else if (ranged) {
         h->n_filt_range_calls.fetch_add(1, std::memory_order_relaxed);
@@ -703,7 +781,7 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
                            uint32_t *d_ids, float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
                            hipStream_t stream, bool finish, uint8_t *paths) {
     hnsw_mask_set *const set = f.set;
-    const bool ranged = f.d_lo != nullptr, deleted = !set && !ranged;
+    const bool ranged = f.d_lo != nullptr, both = set && ranged, deleted = !set && !ranged;
     const uint32_t efp = std::max(std::max(ef, n), 1u);
     if (n > HX_FILT_MAX_N || efp > HX_FILT_MAX_EF) {
         set_error("%s: needs n <= %d and ef' = max(ef, n) <= %d", deleted ? "search with deleted ids" : "filtered device search",
@@ -741,8 +819,8 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
         t_counts.st = stream;
         d_counts = static_cast<uint32_t *>(t_counts.p);
     }
-    FilterSource src(h, set ? FilterSource::SET : ranged ? FilterSource::RANGE : FilterSource::ONE, nullptr, set,
-                     set ? set->allow_bits : index_len(h));
+    FilterSource src(h, both ? FilterSource::SET_RANGE : set ? FilterSource::SET : ranged ? FilterSource::RANGE : FilterSource::ONE,
+                     nullptr, set, set ? set->allow_bits : index_len(h));
     src.bind(dq.q, set ? set->d_rows() : nullptr, f.d_mask_of, f.d_lo, f.d_hi, set ? set->n_masks : 0, n, efp);
     FilterArgs &a = src.base;
     a.out_ids = d_ids;
@@ -752,28 +830,29 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
     const uint32_t slots = filt_first_slots_log2(v, efp, ranged);
     if (!finish) return launch_filtered_graph(v, a, (uint32_t)nq, slots, stream);
 
-    // scratch: the selection on the device; the statuses and the keys of the queries (the rows or ranges they name) on
-    // the host; the exact path's part ([selection | its scratch]) is sized only when a query reaches it
+    // scratch: the selection on the device; the statuses and the keys of the queries (the rows and ranges they name:
+    // [rows | lo | hi]) on the host; the exact path's part ([selection | its scratch]) is sized only when a query reaches it
     const size_t st_bytes = nq * sizeof(hnsw_query_stats), o_keys = align256(st_bytes), r_bytes = align256(nq * 4);
-    const size_t pin_bytes = deleted ? st_bytes : set ? o_keys + nq * 4 : o_keys + 2 * r_bytes;
+    const size_t pin_bytes = deleted ? st_bytes : o_keys + 3 * r_bytes;
     ScratchLease lease(h);
     if ((rc = lease.prepare(h->dev.device, align256(nq * 4), pin_bytes))) return rc;
     const hnsw_query_stats *st = nullptr;
     bool have_keys = false;  // they come back once, with the first fetch
     auto fetch = [&](const hnsw_query_stats *&out) -> int {
         unsigned char *pin = static_cast<unsigned char *>(lease.s->pin);
-        uint32_t *k0 = reinterpret_cast<uint32_t *>(pin + o_keys), *k1 = reinterpret_cast<uint32_t *>(pin + o_keys + r_bytes);
+        uint32_t *k0 = reinterpret_cast<uint32_t *>(pin + o_keys), *k1 = reinterpret_cast<uint32_t *>(pin + o_keys + r_bytes),
+                 *k2 = reinterpret_cast<uint32_t *>(pin + o_keys + 2 * r_bytes);
         HIP_TRY(hipMemcpyAsync(pin, d_stats, st_bytes, hipMemcpyDeviceToHost, stream));
         if (f.d_mask_of && !have_keys) HIP_TRY(hipMemcpyAsync(k0, f.d_mask_of, nq * 4, hipMemcpyDeviceToHost, stream));
         if (ranged && !have_keys) {
-            HIP_TRY(hipMemcpyAsync(k0, f.d_lo, nq * 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(k1, f.d_hi, nq * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(k1, f.d_lo, nq * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(k2, f.d_hi, nq * 4, hipMemcpyDeviceToHost, stream));
         }
         HIP_TRY(hipStreamSynchronize(stream));
         have_keys = true;
         out = st = reinterpret_cast<const hnsw_query_stats *>(pin);
         if (f.d_mask_of) src.mask_of = k0;
-        if (ranged) src.lo = k0, src.hi = k1;
+        if (ranged) src.lo = k1, src.hi = k2;
         return HNSW_OK;
     };
     std::vector<uint8_t> path(nq, 0);
@@ -790,13 +869,14 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
     if (rc != HNSW_OK) return rc;
     (deleted ? h->n_del_graph : h->n_filt_graph).fetch_add(nq - n2, std::memory_order_relaxed);
     (deleted ? h->n_del_overflow : h->n_filt_overflow).fetch_add(n2, std::memory_order_relaxed);
-    if (set) h->n_filt_set_calls.fetch_add(1, std::memory_order_relaxed);
-    if (ranged) {  // ... and the distinct ranges over all queries
-        std::vector<uint64_t> named(nq);
-        for (uint64_t i = 0; i < nq; i++) named[i] = src.key((uint32_t)i);
+    if (set && !both) h->n_filt_set_calls.fetch_add(1, std::memory_order_relaxed);
+    if (ranged) {  // ... and the distinct ranges, or (row, range) triples, over all queries
+        std::vector<std::pair<uint64_t, uint64_t>> named(nq);
+        for (uint64_t i = 0; i < nq; i++) named[i] = {src.key((uint32_t)i), src.range((uint32_t)i)};
         std::sort(named.begin(), named.end());
-        h->n_filt_range_calls.fetch_add(1, std::memory_order_relaxed);
-        h->n_filt_range_ranges.fetch_add((uint64_t)(std::unique(named.begin(), named.end()) - named.begin()), std::memory_order_relaxed);
+        const uint64_t distinct = (uint64_t)(std::unique(named.begin(), named.end()) - named.begin());
+        (both ? h->n_filt_set_range_calls : h->n_filt_range_calls).fetch_add(1, std::memory_order_relaxed);
+        (both ? h->n_filt_set_range_groups : h->n_filt_range_ranges).fetch_add(distinct, std::memory_order_relaxed);
     }
     if (paths) memcpy(paths, path.data(), nq);
     for (uint64_t i = 0; i < nq; i++)

@@ -85,7 +85,10 @@ int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, u
 // set's host words, mask_of is required): nothing is uploaded, the kernels read the set's HBM copy, and the admissible
 // ids of a row come from the set's caches.  Or the call has no masks but a closed range [lo[i], hi[i]] per query over
 // the handle's label column (hnsw_search_batch_filtered_range; allow_bits is the index length): the planner's unit is
-// then a distinct (lo, hi) pair, counted with the column's sorted copy.
+// then a distinct (lo, hi) pair, counted with the column's sorted copy.  Or it has a resident set AND a range per query
+// (hnsw_search_batch_filtered_set_range): query i is under the ids of row mask_of[i] whose label lies in [lo[i], hi[i]],
+// the planner's unit is a distinct (row, lo, hi) triple, counted by walking the cheaper of the range's slice of the
+// sorted copy and the row's set bits, and the set's per-row caches serve only the triples whose range is [0, UINT32_MAX].
 struct MaskSpec {
     const uint64_t *masks = nullptr;
     uint64_t allow_bits = 0;
@@ -99,8 +102,8 @@ struct MaskSpec {
 // -> A, and the admissible ids before every block of 64 words (the compaction kernel's offsets)
 uint64_t count_admissible(const hnsw_index *h, const uint64_t *allow, uint64_t bits, std::vector<uint32_t> &wbase);
 
-// k-NN among the admissible ids (hnsw_search_batch_filtered's, _multi's, _set's and _range's contract): the planner runs
-// per group -- the queries under one mask, row or range -- the graph path's queries of all groups share one launch and
+// k-NN among the admissible ids (hnsw_search_batch_filtered's, _multi's, _set's, _range's and _set_range's contract): the
+// planner runs per group -- the queries under one mask, row, range or (row, range) -- the graph path's queries of all groups share one launch and
 // one re-run loop, the exact path runs group by group; queries that fill the largest visited table are answered by the
 // exact path as well, each under its own filter (path 2).
 // exact_only: every query by the exact path (hnsw_brute_force).  The results go to the caller's buffers (per-query
@@ -115,18 +118,19 @@ int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t
                             uint8_t *paths, const PathCounters *ctr);
 
 // The filter of a device-pointer call, read on the device: a row of a resident set per query (d_mask_of; nullptr: row 0),
-// or a label range per query (d_lo / d_hi), or neither: the undeleted ids, while ids are deleted.
+// or a label range per query (d_lo / d_hi), or both (hnsw_search_batch_filtered_set_range_device), or neither: the
+// undeleted ids, while ids are deleted.
 struct DeviceFilter {
     hnsw_mask_set *set = nullptr;
     const uint32_t *d_mask_of = nullptr, *d_lo = nullptr, *d_hi = nullptr;
 };
 
-// hnsw_search_batch_device while ids are deleted, hnsw_search_batch_filtered_device and _filtered_range_device
-// (finish = false), and their _finish: every query by the filtered graph path under its own filter.  The deleted set and
+// hnsw_search_batch_device while ids are deleted, hnsw_search_batch_filtered_device, _filtered_range_device and
+// _filtered_set_range_device (finish = false), and their _finish: every query by the filtered graph path under its own filter.  The deleted set and
 // the set or the label column are brought up to date on a stream of the handle's own, then ONE launch goes to the
-// caller's stream.  _finish waits, reads the statuses back (and with them, once, d_mask_of or d_lo / d_hi), re-runs the
+// caller's stream.  _finish waits, reads the statuses back (and with them, once, d_mask_of and d_lo / d_hi), re-runs the
 // queries whose visited table filled up with larger tables, up to the graph path's largest, answers those that fill it
-// by the exact path, each under its own row or range (search_filtered's path 2), and returns the first per-query error:
+// by the exact path, each under its own row and range (search_filtered's path 2), and returns the first per-query error:
 // a row the set does not have is HNSW_ERR_ARG.  Equals search_filtered under the same filter with filter_exact_max = -1.
 int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
                            uint32_t *d_ids, float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,

@@ -447,6 +447,50 @@ class HNSW:
             None if out is None else _p(out, _u8p)))
         return out
 
+    # ---- a label range AND a row of a resident mask set (include/hnsw_mi355x.h) -----------------------------------
+    def search_batch_filtered_set_range(self, Q, n, ef, mask_set, mask_of, lo, hi):
+        """k-NN among the ids that row mask_of[i] of a resident MaskSet allows AND whose label lies in [lo[i], hi[i]]
+        (hnsw_search_batch_filtered_set_range).  mask_of [nq]: rows of the set, -1 or MASK_NONE (the range alone);
+        None: every query under row 0.  lo / hi: scalars broadcast, lo > hi is an empty range.
+        -> as search_batch_filtered"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        nq = Q.shape[0]
+        mo = self._mask_of(mask_of, nq)
+        lo, hi = self._range(lo, hi, nq)
+        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        paths = np.zeros(nq, dtype=np.uint8)
+        check(self._L.hnsw_search_batch_filtered_set_range(
+            self._h, _p(Q, _f32p), nq, n, ef, mask_set._s, None if mo is None else _p(mo, _u32p), _p(lo, _u32p),
+            _p(hi, _u32p), _p(ids, _u32p), _p(dists, _f32p), _p(counts, _u32p),
+            C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
+        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+
+    def search_batch_filtered_set_range_device(self, d_Q, nq, n, ef, mask_set, d_mask_of, d_lo, d_hi, d_ids, d_dists,
+                                               d_counts, d_stats, stream=0):
+        """hnsw_search_batch_filtered_set_range_device over torch device tensors (or raw device pointers): d_mask_of
+        (None / 0: row 0), d_lo / d_hi uint32 [nq] in HBM; one launch enqueued on `stream`, no sync."""
+        p = self._dptr
+        check(self._L.hnsw_search_batch_filtered_set_range_device(
+            self._h, p(d_Q), nq, n, ef, mask_set._s, p(d_mask_of), p(d_lo), p(d_hi), p(d_ids), p(d_dists), p(d_counts),
+            p(d_stats), stream or None))
+
+    def search_batch_filtered_set_range_device_finish(self, d_Q, nq, n, ef, mask_set, d_mask_of, d_lo, d_hi, d_ids,
+                                                      d_dists, d_counts, d_stats, stream=0, paths=False):
+        """Completes search_batch_filtered_set_range_device: synchronises, re-runs overflowed queries, answers those
+        that fill the largest table by the exact path, raises the first per-query error.
+        paths=True -> uint8 [nq] (0 / 2)"""
+        p = self._dptr
+        out = np.zeros(nq, dtype=np.uint8) if paths else None
+        check(self._L.hnsw_search_batch_filtered_set_range_device_finish(
+            self._h, p(d_Q), nq, n, ef, mask_set._s, p(d_mask_of), p(d_lo), p(d_hi), p(d_ids), p(d_dists), p(d_counts),
+            p(d_stats), stream or None, None if out is None else _p(out, _u8p)))
+        return out
+
     def ann_by_vector_filtered(self, vector, n, ef, allow):
         """ann_by_vector restricted to the allowed ids -> list of ids"""
         q = np.ascontiguousarray(vector, dtype=np.float32).reshape(1, -1)

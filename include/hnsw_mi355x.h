@@ -190,7 +190,8 @@ int hnsw_search_batch(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, ui
  * effective mask is allow AND NOT deleted, and the result equals the same call with that mask on a handle with
  * nothing deleted.  Masks resident in HBM across calls and a device-pointer form are hnsw_mask_set's, below.  Not
  * provided: coalescing of one-query filtered calls, filtered sharded search, the Rust shim's binding, and a label
- * range (hnsw_search_batch_filtered_range, below) combined with a mask or a mask set in one call. */
+ * range (hnsw_search_batch_filtered_range, below) combined with a per-call mask or a mask per query in one call (with a
+ * row of a resident set it is hnsw_search_batch_filtered_set_range, below). */
 int hnsw_search_batch_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
                                const uint64_t *allow, uint64_t allow_bits, uint32_t *ids, float *dists,
                                uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths /* 0/1/2 or NULL */);
@@ -297,8 +298,9 @@ int hnsw_search_batch_filtered_device_finish(hnsw_index *h, const float *d_Q, ui
  * hnsw_set_device carry the column, hnsw_save writes it as the file `labels` (see hnsw_save); hnsw_snapshot_describe /
  * _adopt do not carry it, but a device-only replica may set labels of its own (its length is the header's).
  * hnsw_set_labels must not run concurrently with a range search on the handle.
- * Not provided: a range combined with a mask set in one call, several label columns or labels that are not integers,
- * the Rust shim's binding, filtered sharded search. */
+ * A range combined with a row of a resident mask set in one call is hnsw_search_batch_filtered_set_range, below.
+ * Not provided: a range combined with a mask that is not in a set, several label columns or labels that are not
+ * integers, disjunctions, the Rust shim's binding, filtered sharded search. */
 /* labels[k] for ids[k]; ids == NULL: ids 0..k-1.  An id >= hnsw_len is HNSW_ERR_ARG and nothing changes.  Needs no GPU. */
 int hnsw_set_labels(hnsw_index *h, const uint32_t *ids, const uint32_t *labels, uint64_t k);
 /* out[k]: the labels of ids[k] (NULL: of ids 0..k-1); an id >= hnsw_len is HNSW_ERR_ARG */
@@ -340,6 +342,61 @@ int hnsw_search_batch_filtered_range_device_finish(hnsw_index *h, const float *d
                                                    uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
                                                    hnsw_query_stats *d_stats, void *stream,
                                                    uint8_t *paths /* host, nq, or NULL */);
+
+/* ---- a label range AND a row of a resident mask set ---------------------------------------------------------------
+ * The conjunction a filter usually is ("tenant == t AND visible under ACL row r", "timestamp in the last hour AND not
+ * in this user's seen list"), with both halves read where they already are, in HBM: no conjunction mask is built,
+ * uploaded or counted word by word on the host.  Query i's ids, distance bits, count, stats
+ * (status included) and path are exactly what hnsw_search_batch_filtered returns for that query alone, on the same
+ * handle with the same options, under the mask
+ *   { id < min(set.allow_bits, hnsw_len) : bit id of row mask_of[i] is set AND lo[i] <= label(id) <= hi[i] }
+ * -- for mask_of[i] == HNSW_MASK_NONE the first condition is id < hnsw_len -- with the deleted ids taken out, and
+ * everything else as in _set and _range: n <= 64, ef' = max(ef, n, 1), the cosine option, per-query errors, A == 0
+ * giving count 0, lo[i] > hi[i] an empty range and no error, path 2 on an overflow of the largest visited table.
+ * mask_of == NULL: every query under row 0.  With every range [0, UINT32_MAX] the call returns what
+ * hnsw_search_batch_filtered_set returns for the same mask_of, with every mask_of[i] == HNSW_MASK_NONE what
+ * hnsw_search_batch_filtered_range returns for the same ranges.
+ * The planner runs per distinct (row, lo, hi) triple named in the call and decides exactly: a triple takes the exact
+ * path (1) iff its admissible count A <= "filter_exact_max", so the paths are those of the equivalent
+ * hnsw_search_batch_filtered_multi call.  A is counted on the host by walking the cheaper side -- the range's slice of
+ * the column's sorted copy, testing the row's bits, or the row's set bits, testing labels -- and only until it exceeds
+ * "filter_exact_max": a triple on the graph path is not counted further (when one of its queries reaches path 2 it is
+ * counted then).  A triple whose range is [0, UINT32_MAX] is planned as the row alone, with the set's caches; a
+ * HNSW_MASK_NONE triple as the range alone.  The set's per-row caches (count, offsets, compacted list) describe the
+ * row alone: a triple with a proper range neither reads them as its own nor invalidates them, and is compacted in the
+ * call's scratch.  ef' > 256 is HNSW_ERR_ARG when some triple takes the graph path.  All graph-path queries of all
+ * triples share ONE launch of the filtered graph kernel, each wave testing labels against its own range and bits of
+ * its own row; the exact path runs once per exact-path triple.
+ * HNSW_ERR_ARG, decided before the device is touched: Q, ids, set, lo or hi NULL; a set of another handle; a
+ * mask_of[i] that is neither < n_masks nor HNSW_MASK_NONE; n > 64; nq > 2^31 - 1.  nq == 0 is HNSW_OK; n == 0 zeroes
+ * counts and launches nothing.  hnsw_get_stat: the three "filtered_*" path counters advance as for _multi,
+ * "filtered_set_range_calls" by one and "filtered_set_range_groups" by the distinct (row, lo, hi) triples named. */
+int hnsw_search_batch_filtered_set_range(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                         hnsw_mask_set *set, const uint32_t *mask_of /* nq; NULL: every query row 0 */,
+                                         const uint32_t *lo /* nq */, const uint32_t *hi /* nq */, uint32_t *ids,
+                                         float *dists, uint32_t *counts, hnsw_query_stats *stats,
+                                         uint8_t *paths /* 0/1/2 or NULL */);
+/* The same with every buffer in HBM on the handle's device, after hnsw_search_batch_filtered_device and
+ * _filtered_range_device: d_lo and d_hi are required, d_mask_of may be NULL (row 0).  The set and the column are
+ * brought up to date on a stream of the handle's own, then ONE launch of the filtered graph kernel is enqueued on
+ * `stream` and the call returns without synchronising.  Every query takes the graph path: n <= 64 and ef' <= 256, else
+ * HNSW_ERR_ARG.  d_stats is required; d_dists / d_counts may be NULL.  A query whose d_mask_of entry is neither
+ * < n_masks nor HNSW_MASK_NONE gets status HNSW_ERR_ARG, count 0 and padded outputs, and no mask word or label is read
+ * for it.  _finish (same arguments, and paths: host, nq, or NULL) waits for `stream`, reads the statuses and d_mask_of
+ * / d_lo / d_hi back, re-runs the queries whose visited table filled up with larger tables, answers those that fill the
+ * largest by the exact path under their own (row, range) (path 2) and returns the first per-query error.  After it
+ * the buffers hold what hnsw_search_batch_filtered_set_range returns with "filter_exact_max" = -1 (paths 0 or 2); the
+ * counters advance at _finish. */
+int hnsw_search_batch_filtered_set_range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                                hnsw_mask_set *set, const uint32_t *d_mask_of /* device, nq; NULL: row 0 */,
+                                                const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
+                                                float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
+                                                void *stream);
+int hnsw_search_batch_filtered_set_range_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n,
+                                                       uint32_t ef, hnsw_mask_set *set, const uint32_t *d_mask_of,
+                                                       const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
+                                                       float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
+                                                       void *stream, uint8_t *paths /* host, nq, or NULL */);
 
 /* hnsw_search_batch with every buffer already resident in HBM on the handle's device; enqueues on `stream`
  * (a hipStream_t, NULL = default stream) and returns without synchronising.  d_stats is
@@ -522,7 +579,9 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * launched for rows of a set), "filtered_set_calls" (hnsw_search_batch_filtered_set calls and completed
  * hnsw_search_batch_filtered_device calls); labels: "label_words_uploaded" (64-bit words of the label column copied
  * to HBM), "filtered_range_calls" (hnsw_search_batch_filtered_range calls and completed _range_device calls),
- * "filtered_range_ranges" (the distinct ranges they named); deletion:
+ * "filtered_range_ranges" (the distinct ranges they named), "filtered_set_range_calls"
+ * (hnsw_search_batch_filtered_set_range calls and completed _set_range_device calls), "filtered_set_range_groups" (the
+ * distinct (row, lo, hi) triples they named); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
