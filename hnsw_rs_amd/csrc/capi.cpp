@@ -1,7 +1,8 @@
 // capi.cpp -- the extern "C" surface of libhnsw_mi355x.so (include/hnsw_mi355x.h): argument checks, dispatch,
 // accessors, options and statistics, persistence, snapshots, the ground-truth scans.  Host logic only; the search
 // entry points upload the index snapshot to HBM on demand and hand over to search_host.cpp (batches) or coalesce.cpp
-// (hnsw_search), which launch the HIP kernels.  There is no CPU search path.
+// (hnsw_search), which launch the HIP kernels.  There is no CPU search path.  (The two entry points of partitioned
+// search are partition.cpp's.)
 
 #include <hip/hip_runtime.h>
 
@@ -1187,6 +1188,10 @@ int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
         *out = h->n_set_compactions.load();
     } else if (!strcmp(key, "filtered_set_calls")) {
         *out = h->n_filt_set_calls.load();
+    } else if (!strcmp(key, "shard_calls")) {
+        *out = h->n_shard_calls.load();
+    } else if (!strcmp(key, "shard_merges")) {
+        *out = h->n_shard_merges.load();
     } else if (!strcmp(key, "deleted")) {
         *out = h->del.count;
     } else if (!strcmp(key, "deleted_mask_words_uploaded")) {

@@ -57,6 +57,22 @@ struct FilterArgs {
     hnsw_query_stats *out_stats;  // nq
 };
 
+// The second source form of hx_filt_merge_kernel (hnsw_merge_topk_device): instead of the nseg partial key lists of one
+// index, the result lists of n_shards indexes, shard-major -- ids[s][q][j] (ids local to shard s, pad UINT32_MAX),
+// dists[s][q][j], counts[s][q] (nullptr: an entry is present iff its id is not the pad) and stats[s][q] (nullptr: none
+// are summed or written).  A present entry's key is (dist bits << 32) | (base[s] + stride[s] * id); the query's n smallest
+// distinct keys are written as the exact path writes them.  base and stride travel by value: the launch needs no
+// allocation, copy or synchronisation.  ids == nullptr: the kernel's first form.
+#define HX_MERGE_MAX_SHARDS 64
+struct MergeLists {
+    const uint32_t *ids;
+    const float *dists;
+    const uint32_t *counts;
+    const hnsw_query_stats *stats;
+    uint32_t n_shards, nq;
+    uint32_t base[HX_MERGE_MAX_SHARDS], stride[HX_MERGE_MAX_SHARDS];
+};
+
 // ids a layer-0 visited table of 2^slots_log2 slots holds before the graph path reports HNSW_ERR_OVERFLOW
 __host__ __device__ inline uint32_t filt_visited_limit(uint32_t slots_log2) { return (1u << slots_log2) - (1u << (slots_log2 - 2)); }
 // first table size for ef' (the generic kernel's choice) and the largest one the dimension leaves room for in LDS
@@ -79,5 +95,11 @@ int launch_filter_compact(const FilterArgs &a, uint64_t n_words, const uint32_t 
 uint32_t filt_exact_segments(uint64_t A, uint32_t nsel);
 int launch_filtered_exact(const DevView &v, const FilterArgs &a, uint32_t nsel, const uint32_t *ids, uint32_t A,
                           uint32_t nseg, unsigned long long *part, int32_t *part_status, hipStream_t stream);
+// the top n (1 <= n <= HX_FILT_MAX_N) by (distance bits, global id) of m.nq queries over the lists of m.n_shards shards:
+// ONE launch of hx_filt_merge_kernel in its shard-list form, one wave per query.  out_counts may be nullptr; out_stats
+// goes with m.stats.  A query some shard answered with a status other than HNSW_OK gets that status (the lowest-numbered
+// such shard's), count 0 and padded rows; n_dist, n_exp and sum_deg are the uint32 sums over the shards.
+int launch_merge_lists(const MergeLists &m, uint32_t n, uint32_t *out_ids, float *out_dists, uint32_t *out_counts,
+                       hnsw_query_stats *out_stats, hipStream_t stream);
 
 }  // namespace hx

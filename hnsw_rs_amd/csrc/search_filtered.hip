@@ -23,7 +23,9 @@
 // read from the mask, or, under a label range, made from 64 coalesced reads of the column, or that word ANDed with the
 // mask's under both); hx_filt_scan_kernel scans
 // one segment of that list per block and keeps its n best (the shape of hx_brute_kernel),
-// hx_filt_merge_kernel merges a query's segments.
+// hx_filt_merge_kernel merges a query's segments.  The same kernel has a second source form (MergeLists,
+// search_filtered.h): the result lists of the shards of a partitioned index, keyed by global id,
+// merged the same way but for keys that two shards may both hold.
 //
 // Float fidelity as everywhere: -ffp-contract=off, the reference's accumulation order.
 
@@ -110,6 +112,25 @@ struct FList {
         }
         wave_fence();
         refresh_last(cap);
+    }
+
+    // merge for keys that may repeat (result lists of shards that overlap): a key equal to one in the list, or to the
+    // key of a lower lane, is dropped first, so that what merge sees is distinct and new -- its ranks are then dense and
+    // every slot of perm it reads back was written in the same call
+    __device__ __forceinline__ void merge_unique(u64 key, uint32_t cap, u64 *perm, int lane) {
+        u64 it = __ballot(key != FKEY_INVALID && (n_cur < cap || key < last));
+        bool dup = false;
+        while (it) {
+            const int j = __ffsll((long long)it) - 1;
+            it &= it - 1;
+            const u64 e = readlane64(key, j);
+            bool known = lane < j && key == e;
+#pragma unroll
+            for (int r = 0; r < R; r++) known |= L[r] == e;
+            const bool any = __ballot(known) != 0;
+            if (lane == j) dup = any;
+        }
+        merge(dup ? FKEY_INVALID : key, cap, perm, lane);
     }
 
     // drop the head: every key moves one lane down, lane 63 of register r takes lane 0 of register r + 1
@@ -573,11 +594,73 @@ __global__ void __launch_bounds__(64) hx_filt_scan_kernel(const DevView v, const
     if (lane == 0) part_status[(size_t)y * nseg + seg] = bad ? HNSW_ERR_NAN_INPUT : HNSW_OK;
 }
 
-// Merge: one wave per query folds the nseg partial lists into its top n and writes the results.
+// The merge kernel's shard-list form (MergeLists, search_filtered.h): query blockIdx.x's lists of the m.n_shards shards,
+// lane j holding entry j of a list, folded into its top a.n by (distance bits, global id).  The steps depend on one
+// another only through the list: everything shard s + 1 holds for the query is requested before shard s is merged, the
+// ids and distances of a whole row whatever its count says (the row exists: presence is decided when they are there).
+__device__ __forceinline__ void merge_shard_lists(const FilterArgs &a, const MergeLists &m, u64 *perm, int lane) {
+    const uint32_t q = blockIdx.x, n = a.n;
+    const bool row = (uint32_t)lane < n;
+    const uint32_t *dist_bits = reinterpret_cast<const uint32_t *>(m.dists);
+    struct Piece {
+        uint32_t id, bits, cnt;
+        hnsw_query_stats st;
+    };
+    auto load = [&](uint32_t s) {
+        const size_t o = (size_t)s * m.nq + q;
+        Piece p;
+        p.id = row ? m.ids[o * n + lane] : HX_EMPTY_SLOT;
+        p.bits = row ? dist_bits[o * n + lane] : 0u;
+        p.cnt = m.counts ? m.counts[o] : 0u;
+        if (m.stats) {
+            p.st = m.stats[o];
+        } else {
+            p.st.n_dist = p.st.n_exp = p.st.sum_deg = 0;
+            p.st.status = HNSW_OK;
+        }
+        return p;
+    };
+    FList<1> wl;
+    wl.clear();
+    hnsw_query_stats st;
+    st.n_dist = st.n_exp = st.sum_deg = 0;
+    st.status = HNSW_OK;
+    Piece nx = load(0);
+    for (uint32_t s = 0; s < m.n_shards; s++) {
+        const Piece p = nx;
+        if (s + 1 < m.n_shards) nx = load(s + 1);
+        st.n_dist += p.st.n_dist;
+        st.n_exp += p.st.n_exp;
+        st.sum_deg += p.st.sum_deg;
+        if (st.status == HNSW_OK) st.status = p.st.status;  // the lowest-numbered shard that failed
+        const bool present = row && (m.counts ? (uint32_t)lane < p.cnt : p.id != HX_EMPTY_SLOT);
+        const uint32_t gid = m.base[s] + m.stride[s] * p.id;  // (all 32 bits: the list has no flag bit)
+        wl.merge_unique(present ? ((u64)p.bits << 32) | gid : FKEY_INVALID, n, perm, lane);
+    }
+    // a query some shard failed: the library's per-query error convention, count 0 and padded rows
+    const uint32_t count = st.status == HNSW_OK ? wl.n_cur : 0;
+    if (row) {
+        const bool have = (uint32_t)lane < count;
+        a.out_ids[(size_t)q * n + lane] = have ? (uint32_t)wl.L[0] : HX_EMPTY_SLOT;
+        a.out_dists[(size_t)q * n + lane] = have ? __builtin_bit_cast(float, (uint32_t)(wl.L[0] >> 32)) : __builtin_inff();
+    }
+    if (lane == 0) {
+        if (a.out_counts) a.out_counts[q] = count;
+        if (a.out_stats) a.out_stats[q] = st;
+    }
+}
+
+// Merge: one wave per query folds the nseg partial lists into its top n and writes the results.  With m.ids set the
+// lists are those of m.n_shards shards instead (merge_shard_lists; A, nseg, part and part_status are not read).
 __global__ void __launch_bounds__(64) hx_filt_merge_kernel(const FilterArgs a, uint32_t A, uint32_t nseg,
-                                                           const u64 *part, const int32_t *part_status) {
+                                                           const u64 *part, const int32_t *part_status,
+                                                           const MergeLists m) {
     __shared__ u64 perm[64];
     const int lane = threadIdx.x;
+    if (m.ids) {  // (a kernel argument: the branch is the wave's)
+        merge_shard_lists(a, m, perm, lane);
+        return;
+    }
     const uint32_t y = blockIdx.x;
     const uint32_t q = a.qsel ? a.qsel[y] : y;
     FList<1> wl;
@@ -676,7 +759,27 @@ int launch_filtered_exact(const DevView &v, const FilterArgs &a, uint32_t nsel, 
                                 dim3(nseg, nsel), dim3(64), 64 * 8 + (size_t)query_lds_bytes(v), stream, v, a, ids, A, nseg, part,
                                 part_status))
         return rc;
-    return launch_checked(site, hx_filt_merge_kernel, dim3(nsel), dim3(64), 0, stream, a, A, nseg, part, part_status);
+    return launch_checked(site, hx_filt_merge_kernel, dim3(nsel), dim3(64), 0, stream, a, A, nseg, part, part_status,
+                          MergeLists{});
+}
+
+int launch_merge_lists(const MergeLists &m, uint32_t n, uint32_t *out_ids, float *out_dists, uint32_t *out_counts,
+                       hnsw_query_stats *out_stats, hipStream_t stream) {
+    if (m.nq == 0) return HNSW_OK;
+    if (n == 0 || n > HX_FILT_MAX_N || m.n_shards == 0 || m.n_shards > HX_MERGE_MAX_SHARDS || m.nq > 0x7FFFFFFFu || !m.ids ||
+        !m.dists || !out_ids || !out_dists || (m.stats != nullptr) != (out_stats != nullptr)) {
+        set_error("shard merge: needs 1 <= n <= %d, 1 to %d shards, at most 2^31 - 1 queries, the lists and the outputs",
+                  HX_FILT_MAX_N, HX_MERGE_MAX_SHARDS);
+        return HNSW_ERR_ARG;
+    }
+    FilterArgs a{};  // the form reads n and the outputs
+    a.n = n;
+    a.out_ids = out_ids;
+    a.out_dists = out_dists;
+    a.out_counts = out_counts;
+    a.out_stats = out_stats;
+    return launch_checked({"shard merge kernel launch"}, hx_filt_merge_kernel, dim3(m.nq), dim3(64), 0, stream, a, 0u, 0u,
+                          static_cast<const u64 *>(nullptr), static_cast<const int32_t *>(nullptr), m);
 }
 
 }  // namespace hx

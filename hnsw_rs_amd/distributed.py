@@ -13,6 +13,17 @@ search by running on its own stream.
 `local_search` is a callable so that the plumbing can be exercised with gloo on CPU (tests) while
 production passes the HIP search (`make_device_search`).
 
+An index too large for one GPU's HBM is PARTITIONED instead (`PartitionedSearcher`): every rank holds one shard of
+the points, with ids local to it, and answers every query; the exchange is
+    broadcast root -> all   : Q                            (nq x dim f32)
+    gather    rank r -> root: ids / dists / counts / stats of its lists, into slice r of contiguous [W][nq][...] buffers
+and the root merges the W lists of every query into its n best by (distance bits, global id) -- on the device by
+hnsw_merge_topk_device (`make_device_merge`), whose input layout the gathers produce as they are.  Its `local_search`
+and `merge` are callables as well (tests: the CPU oracle and the numpy restatement over gloo; production:
+`make_shard_search` and `make_device_merge`).  The rule of `PipelinedShardedSearch` holds here too: a rank never raises
+between two collectives -- a per-query error travels in the stats, a search that failed outright as the status of
+every query of that rank, and the root raises after the gathers (the failing rank itself after its last one).
+
 Deleted ids (HNSW.mark_deleted) are not part of a replica: the set belongs to each handle, and neither
 HNSW.replicate nor hnsw_snapshot_describe / _adopt carries it.  A caller that deletes ids marks the same ids on
 every rank's replica.
@@ -101,6 +112,112 @@ def make_device_search(index, n, ef, max_queries, device):
     local_search.stats = stats
     local_search.counts = counts
     return local_search
+
+
+class PartitionedSearcher:
+    """One SHARD of the index per rank (ShardedSearcher's role for replicas): every rank answers every query from
+    its own points and the root merges the per-rank lists.
+
+    local_search(Q [nq, dim] f32 on `device`) -> (ids [nq, n] int32 local ids, pad -1 = UINT32_MAX; dists [nq, n] f32;
+        counts [nq] int32; stats [nq, 4] int32: n_dist, n_exp, sum_deg, status)
+    merge(ids [W, nq, n], dists [W, nq, n], counts [W, nq], stats [W, nq, 4], id_base, id_stride)
+        -> (ids [nq, n] global, dists, counts, stats): the merge of include/hnsw_mi355x.h, "partitioned search"
+
+    id_base / id_stride: one entry per rank (global id = id_base[r] + id_stride[r] * local id)."""
+
+    def __init__(self, local_search, merge, dim, n, device, id_base, id_stride, group=None, root=0):
+        self.local_search, self.merge = local_search, merge
+        self.dim, self.n, self.device, self.group, self.root = dim, n, device, group, root
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        self.id_base = [int(x) for x in id_base]
+        self.id_stride = [1] * self.world if id_stride is None else [int(x) for x in id_stride]
+        if len(self.id_base) != self.world or len(self.id_stride) != self.world:
+            raise ValueError("id_base / id_stride need one entry per rank")
+
+    def search(self, Q_root, nq):
+        """Q_root: [nq, dim] on the root (ignored elsewhere).  Returns (ids, dists, counts, stats) of the nq queries,
+        merged, on the root, (None, None, None, None) on the other ranks.  Collectives: one broadcast, four gathers;
+        a rank whose search failed raises only after its last gather, the root after the merge."""
+        W, n, dev = self.world, self.n, self.device
+        collective = dist.is_initialized()
+        q = torch.empty((nq, self.dim), dtype=torch.float32, device=dev)
+        if self.rank == self.root:
+            q.copy_(Q_root[:nq])
+        if collective:
+            dist.broadcast(q, src=self.root, group=self.group)
+        failure = None
+        try:
+            ids, dists, counts, stats = self.local_search(q)
+            parts = [ids.reshape(nq, n), dists.reshape(nq, n), counts.reshape(nq), stats.reshape(nq, 4)]
+        except Exception as e:  # never between two collectives: the failure travels as every query's status
+            failure = e
+            code = int(getattr(e, "code", -5)) or -5  # (HNSW_ERR_HIP for what has no status of its own)
+            parts = [torch.full((nq, n), -1, dtype=torch.int32, device=dev),
+                     torch.full((nq, n), float("inf"), dtype=torch.float32, device=dev),
+                     torch.zeros(nq, dtype=torch.int32, device=dev),
+                     torch.tensor([0, 0, 0, code], dtype=torch.int32, device=dev).repeat(nq, 1)]
+        shapes = [(nq, n), (nq, n), (nq,), (nq, 4)]
+        out = None
+        if self.rank == self.root:
+            # contiguous [W][nq][...] buffers: the gathers fill rank r's slice, the merge reads them as they are
+            out = [torch.empty((W,) + sh, dtype=p.dtype, device=dev) for sh, p in zip(shapes, parts)]
+        for k, p in enumerate(parts):
+            p = p.contiguous()
+            if not collective:
+                out[k][0].copy_(p)
+            elif self.rank == self.root:
+                dist.gather(p, list(out[k].unbind(0)), dst=self.root, group=self.group)
+            else:
+                dist.gather(p, None, dst=self.root, group=self.group)
+        if failure is not None:
+            raise failure
+        if self.rank != self.root:
+            return None, None, None, None
+        m_ids, m_dists, m_counts, m_stats = self.merge(out[0], out[1], out[2], out[3], self.id_base, self.id_stride)
+        status = m_stats.reshape(nq, 4)[:, 3]
+        bad = torch.nonzero(status).reshape(-1)
+        if bad.numel():
+            i = int(bad[0])
+            raise RuntimeError("query %d did not finish with status 0 on some shard (merged status %d)" % (i, int(status[i])))
+        return m_ids, m_dists, m_counts, m_stats
+
+
+def make_shard_search(index, n, ef, max_queries, device):
+    """PartitionedSearcher's local_search over the HIP path: make_device_search, completed (overflow re-runs) before
+    the lists travel; a per-query error stays in the stats, where the merge finds it."""
+    from ._lib import ERR_NAN_INPUT, ERR_NODE_NOT_IN_GRAPH, ERR_OVERFLOW, HnswError
+    inner = make_device_search(index, n, ef, max_queries, device)
+
+    def local_search(Q):
+        nq = Q.shape[0]
+        ids, dists = inner(Q)
+        try:
+            inner.check()
+        except HnswError as e:
+            if e.code not in (ERR_NAN_INPUT, ERR_NODE_NOT_IN_GRAPH, ERR_OVERFLOW):
+                raise
+        return ids, dists, inner.counts[:nq], inner.stats[:nq]
+
+    return local_search
+
+
+def make_device_merge(n, device):
+    """PartitionedSearcher's merge as the HIP kernel (hnsw_merge_topk_device), enqueued on torch's current stream"""
+    from .partitioned import merge_topk
+
+    def merge(ids, dists, counts, stats, id_base, id_stride):
+        W, nq = ids.shape[0], ids.shape[1]
+        o_ids = torch.empty((nq, n), dtype=torch.int32, device=device)
+        o_dists = torch.empty((nq, n), dtype=torch.float32, device=device)
+        o_counts = torch.empty(nq, dtype=torch.int32, device=device)
+        o_stats = torch.empty((nq, 4), dtype=torch.int32, device=device)
+        if nq:
+            merge_topk(W, nq, n, ids, dists, counts, stats, id_base, id_stride, o_ids, o_dists, o_counts, o_stats,
+                       torch.cuda.current_stream().cuda_stream)
+        return o_ids, o_dists, o_counts, o_stats
+
+    return merge
 
 
 class CudaLanes:

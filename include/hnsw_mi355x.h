@@ -415,6 +415,58 @@ int hnsw_search_batch_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq
                                     uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
                                     hnsw_query_stats *d_stats, void *stream);
 
+/* ---- partitioned search: one index cut into shards ------------------------------------------------------------------
+ * An extension (the reference keeps one index in one process's RAM, template.rs:35-40): the points are split over S
+ * shards, each an ordinary index with ids local to it; every shard answers every query and the S result lists of a
+ * query are merged into its n best.  Global id = id_base[s] + id_stride[s] * local id (contiguous blocks: base = the
+ * block's first id, stride 1; round robin: base = s, stride = S).  This serves an index larger than one GPU's HBM (one
+ * shard per rank; the lists arrive by RCCL's gather / all-gather, which produce the layout below) and segments on one
+ * GPU (new data in a new small index next to immutable old ones).
+ * THE MERGE of one query: over the present entries of all shards collect the pairs (distance bits as uint32, global
+ * id); drop duplicates of a pair (overlapping shards may hand in the same point twice: it appears once); sort ascending
+ * by the pair; keep n; pad the rest (ids UINT32_MAX, dists +inf).  Distances are non-negative, so bit order is value
+ * order.  n_dist, n_exp and sum_deg are the uint32 sums over the shards; status is that of the lowest-numbered shard
+ * whose status is not HNSW_OK, else HNSW_OK; a query whose merged status is not HNSW_OK gets count 0 and padded rows.
+ *
+ * hnsw_merge_topk_device is that merge alone, handle-free, on the current HIP device: every d_* pointer is device
+ * memory, id_base / id_stride are host arrays of n_shards entries (id_stride NULL: all 1) and travel by value in the
+ * kernel's arguments.  Inputs are shard-major: d_ids_in[S][nq][n] (local ids, pad UINT32_MAX), d_dists_in[S][nq][n],
+ * d_counts_in[S][nq] or NULL, d_stats_in[S][nq] or NULL.  Entry j of shard s's list is present iff j < min(count, n),
+ * or, without counts, iff its id is not UINT32_MAX.  The call enqueues ONE launch (the exact path's merge kernel in
+ * its shard-list form, one wave per query) on `stream` and returns: it allocates nothing, copies nothing and
+ * synchronises nothing, so it can be captured in a graph.  Outputs must not overlap inputs.  d_counts may be NULL;
+ * d_stats is required iff d_stats_in is given.  THE CALLER GUARANTEES id_base[s] + id_stride[s] * id < UINT32_MAX for
+ * every id shard s can return (the sum is taken in 32 bits and all 32 are used: ids at or above 2^31 are fine).
+ * HNSW_ERR_ARG, decided before the device is touched: n_shards 0 or > HNSW_MERGE_MAX_SHARDS; n 0 or > 64;
+ * nq > 2^31 - 1; d_ids_in, d_dists_in, id_base, d_ids or d_dists NULL; exactly one of d_stats_in / d_stats given.
+ * nq == 0 is HNSW_OK, whatever else is passed, and launches nothing.
+ *
+ * hnsw_search_batch_shards answers host-pointer queries from S handles of one dimension on one device as from one
+ * index: Q goes up once; each shard runs hnsw_search_batch_device into its slice of one [S][nq][n] scratch and then its
+ * _finish, so overflow re-runs and the cosine option are each shard's own, unchanged; one merge; one copy back.  A
+ * shard with deleted ids is answered by its hnsw_search_batch instead, the planner's choice of path ("filter_exact_max")
+ * included, and its lists go up into its slice: the device entry point always walks the graph under deletions, and
+ * the call is defined by the host form.  Query i's result is, by definition, THE MERGE of what each shard's
+ * hnsw_search_batch returns for it, on the same handles with the same options.  Returns
+ * the first per-query error; every other row is filled in.  Outputs as hnsw_search_batch (dists, counts, stats may be
+ * NULL).  HNSW_ERR_ARG, decided before the device is touched: shards or id_base NULL, n_shards 0 or > 64, a NULL
+ * handle, handles of differing dimension, handles bound to different devices (a handle not bound yet goes where the
+ * others are), n > 64, nq > 2^31 - 1, Q or ids NULL; an empty shard is HNSW_ERR_EMPTY.  nq == 0 is HNSW_OK; n == 0
+ * zeroes counts and launches nothing.  hnsw_get_stat on shard 0's handle: "shard_calls", "shard_merges".
+ * Not provided: shards of one process on several GPUs; a partitioned build (a caller builds S ordinary indexes);
+ * the filtered entry points over shards; n > 64; rebalancing; the Rust shim's binding. */
+#define HNSW_MERGE_MAX_SHARDS 64
+int hnsw_merge_topk_device(uint32_t n_shards, uint64_t nq, uint32_t n,
+                           const uint32_t *d_ids_in, const float *d_dists_in,
+                           const uint32_t *d_counts_in /* or NULL */, const hnsw_query_stats *d_stats_in /* or NULL */,
+                           const uint32_t *id_base /* S */, const uint32_t *id_stride /* S, or NULL: all 1 */,
+                           uint32_t *d_ids, float *d_dists, uint32_t *d_counts /* or NULL */,
+                           hnsw_query_stats *d_stats /* required iff d_stats_in */, void *stream);
+int hnsw_search_batch_shards(hnsw_index *const *shards, uint32_t n_shards,
+                             const uint32_t *id_base, const uint32_t *id_stride /* or NULL */,
+                             const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                             uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats);
+
 /* Test seams that mirror the reference's own units:
  * VecBase::dist2many (vectors/src/lib.rs:17-22): the query (quantised like ann_by_vector does,
  * template.rs:313) against stored ids, on the device, exact accumulation order. */
@@ -581,7 +633,8 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * to HBM), "filtered_range_calls" (hnsw_search_batch_filtered_range calls and completed _range_device calls),
  * "filtered_range_ranges" (the distinct ranges they named), "filtered_set_range_calls"
  * (hnsw_search_batch_filtered_set_range calls and completed _set_range_device calls), "filtered_set_range_groups" (the
- * distinct (row, lo, hi) triples they named); deletion:
+ * distinct (row, lo, hi) triples they named); partitioned search, on the handle passed as shard 0: "shard_calls"
+ * (hnsw_search_batch_shards calls whose shards were all searched), "shard_merges" (the merges they launched); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
