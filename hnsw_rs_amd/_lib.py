@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("HNSW_MI355X_LIB") or os.path.join(_HERE, "libhnsw_mi3
 VEC_QUANT8 = 0
 VEC_F32 = 1
 UINT32_MAX = 0xFFFFFFFF
+RANGES_MAX = 16  # HNSW_RANGES_MAX: members of a query's range list
 MASK_NONE = 0xFFFFFFFF  # HNSW_MASK_NONE: a query of hnsw_search_batch_filtered_multi without an allow-list
 
 OK = 0
@@ -102,6 +103,13 @@ SYMBOLS = {
                                                           vp, vp, vp]),
     "hnsw_search_batch_filtered_range_device_finish": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp,
                                                                  vp, vp, vp, vp, u8p]),
+    "hnsw_search_batch_filtered_ranges": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p,
+                                                    u32p, f32p, u32p, C.POINTER(QueryStats), u8p]),
+    "hnsw_search_batch_filtered_ranges_device": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
+                                                           vp, vp, vp, vp, vp]),
+    "hnsw_search_batch_filtered_ranges_device_finish": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                  vp, vp, vp, vp, vp, vp, vp, u8p]),
+    "hnsw_count_labels_in_ranges": (C.c_int, [vp, u32p, u32p, C.c_uint32, C.POINTER(C.c_uint64)]),
     "hnsw_search_batch_filtered_set_range": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, vp, u32p, u32p, u32p,
                                                        u32p, f32p, u32p, C.POINTER(QueryStats), u8p]),
     "hnsw_search_batch_filtered_set_range_device": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp,

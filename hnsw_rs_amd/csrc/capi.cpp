@@ -538,6 +538,80 @@ int hnsw_search_batch_filtered_set_range_device_finish(hnsw_index *h, const floa
                             paths);
 }
 
+// ---- searches under a list of label ranges per query ---------------------------------------------------------------
+static int check_range_list(uint32_t n_ranges) {
+    if (n_ranges == 0 || n_ranges > HNSW_RANGES_MAX) {
+        set_error("filtered search: needs 1 to %d label ranges per query, got %u", HNSW_RANGES_MAX, n_ranges);
+        return HNSW_ERR_ARG;
+    }
+    return HNSW_OK;
+}
+
+int hnsw_search_batch_filtered_ranges(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                      uint32_t n_ranges, const uint32_t *lo, const uint32_t *hi, uint32_t *ids,
+                                      float *dists, uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK) return rc;
+    if (nq == 0) return HNSW_OK;
+    if (!lo || !hi) {
+        set_error("filtered search: needs the label ranges (lo and hi) of every query");
+        return HNSW_ERR_ARG;
+    }
+    if ((rc = check_range_list(n_ranges))) return rc;
+    hx::MaskSpec m{nullptr, index_len(h)};
+    m.lo = lo;
+    m.hi = hi;
+    m.n_ranges = n_ranges;
+    const hx::PathCounters ctr = hx::filt_counters(h);
+    return hx::search_filtered_checked(h, Q, nq, n, ef, m, false, ids, dists, counts, stats, paths, &ctr);
+}
+
+static int ranges_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t n_ranges,
+                         const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                         hnsw_query_stats *d_stats, void *stream, bool finish, uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK) return rc;
+    if (nq == 0 || n == 0) return HNSW_OK;
+    if (!d_Q || !d_ids || !d_stats || !d_lo || !d_hi || nq > 0x7FFFFFFFull) {
+        set_error("filtered device search: needs queries, their label ranges, an id buffer and a stats buffer in HBM");
+        return HNSW_ERR_ARG;
+    }
+    if ((rc = check_range_list(n_ranges))) return rc;
+    return hx::search_device_filtered(h, hx::DeviceFilter{nullptr, nullptr, d_lo, d_hi, n_ranges}, d_Q, nq, n, ef, d_ids,
+                                      d_dists, d_counts, d_stats, static_cast<hipStream_t>(stream), finish, paths);
+}
+
+int hnsw_search_batch_filtered_ranges_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                             uint32_t n_ranges, const uint32_t *d_lo, const uint32_t *d_hi,
+                                             uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                                             hnsw_query_stats *d_stats, void *stream) {
+    return ranges_device(h, d_Q, nq, n, ef, n_ranges, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, false, nullptr);
+}
+
+int hnsw_search_batch_filtered_ranges_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n,
+                                                    uint32_t ef, uint32_t n_ranges, const uint32_t *d_lo,
+                                                    const uint32_t *d_hi, uint32_t *d_ids, float *d_dists,
+                                                    uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream,
+                                                    uint8_t *paths) {
+    return ranges_device(h, d_Q, nq, n, ef, n_ranges, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
+}
+
+int hnsw_count_labels_in_ranges(const hnsw_index *h, const uint32_t *lo, const uint32_t *hi, uint32_t k,
+                                uint64_t *count) {
+    if (!h || !count || (k && (!lo || !hi)) || k > HNSW_RANGES_MAX) {
+        set_error("hnsw_count_labels_in_ranges: needs a handle, a result and at most %d ranges", HNSW_RANGES_MAX);
+        return HNSW_ERR_ARG;
+    }
+    // the planner's count: the sorted copy of the undeleted ids' labels, the disjoint members' slices summed
+    hnsw_index *hm = const_cast<hnsw_index *>(h);  // (the sorted copy is a cache, made under its mutex)
+    std::lock_guard<std::mutex> lg(hm->lab.mu);
+    hm->lab.sort_for(hm->del, index_len(h));
+    uint64_t A = 0;
+    for (uint64_t m : hx::LabelColumn::canonical(lo, hi, k)) A += hm->lab.count((uint32_t)(m >> 32), (uint32_t)m);
+    *count = A;
+    return HNSW_OK;
+}
+
 int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
                              uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
                              hnsw_query_stats *d_stats, void *stream) {
@@ -1176,6 +1250,10 @@ int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
         *out = h->n_filt_set_range_calls.load();
     } else if (!strcmp(key, "filtered_set_range_groups")) {
         *out = h->n_filt_set_range_groups.load();
+    } else if (!strcmp(key, "filtered_ranges_calls")) {
+        *out = h->n_filt_ranges_calls.load();
+    } else if (!strcmp(key, "filtered_ranges_groups")) {
+        *out = h->n_filt_ranges_groups.load();
     } else if (!strcmp(key, "filtered_multi_calls")) {
         *out = h->n_filt_multi_calls.load();
     } else if (!strcmp(key, "filtered_multi_masks")) {

@@ -63,6 +63,8 @@ struct hnsw_index {
     std::atomic<uint64_t> n_filt_range_calls{0}, n_filt_range_ranges{0};
     // ... and hnsw_search_batch_filtered_set_range's: calls, and the distinct (row, lo, hi) triples they named
     std::atomic<uint64_t> n_filt_set_range_calls{0}, n_filt_set_range_groups{0};
+    // hnsw_search_batch_filtered_ranges: calls, and the distinct canonical range lists they named
+    std::atomic<uint64_t> n_filt_ranges_calls{0}, n_filt_ranges_groups{0};
     // hnsw_search_batch_shards with this handle as shard 0: calls whose shards were all searched, and their merges launched
     std::atomic<uint64_t> n_shard_calls{0}, n_shard_merges{0};
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")

@@ -61,11 +61,33 @@ uint64_t LabelColumn::count(uint32_t lo, uint32_t hi, uint64_t *first) const {
 }
 
 void LabelColumn::word_base(uint64_t first, uint64_t A, uint64_t len, std::vector<uint32_t> &wbase) const {
+    word_base(std::vector<std::pair<uint64_t, uint64_t>>{{first, A}}, len, wbase);
+}
+
+void LabelColumn::word_base(const std::vector<std::pair<uint64_t, uint64_t>> &slices, uint64_t len,
+                            std::vector<uint32_t> &wbase) const {
     const uint64_t n_words = (len + 63) / 64, n_wblk = (n_words + 63) / 64;
     wbase.assign(std::max<uint64_t>(1, n_wblk) + 1, 0);
-    for (uint64_t i = first; i < first + A; i++) wbase[((uint32_t)sorted[i] >> 12) + 1]++;  // ids per block, shifted by one
+    for (const auto &s : slices)
+        for (uint64_t i = s.first; i < s.first + s.second; i++) wbase[((uint32_t)sorted[i] >> 12) + 1]++;  // ids per block, shifted by one
     for (size_t b = 1; b < wbase.size(); b++) wbase[b] += wbase[b - 1];
     wbase.pop_back();  // wbase[b] = admissible ids in the blocks before b
+}
+
+std::vector<uint64_t> LabelColumn::canonical(const uint32_t *lo, const uint32_t *hi, uint32_t k) {
+    std::vector<uint64_t> in, out;
+    for (uint32_t j = 0; j < k; j++)
+        if (lo[j] <= hi[j]) in.push_back(((uint64_t)lo[j] << 32) | hi[j]);
+    std::sort(in.begin(), in.end());  // ascending lo
+    for (uint64_t m : in) {
+        const uint64_t l = m >> 32, h = m & 0xFFFFFFFFull;
+        // (64-bit: the end of the last member plus one does not wrap at UINT32_MAX)
+        if (!out.empty() && l <= (out.back() & 0xFFFFFFFFull) + 1)
+            out.back() = (out.back() & ~0xFFFFFFFFull) | std::max<uint64_t>(out.back() & 0xFFFFFFFFull, h);
+        else
+            out.push_back(m);
+    }
+    return out;
 }
 
 }  // namespace hx

@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "deleted.h"
@@ -54,6 +55,12 @@ struct LabelColumn : HbmWords {
     uint64_t count(uint32_t lo, uint32_t hi, uint64_t *first = nullptr) const;
     // ... and how many of them lie before every block of 64 words (4096 ids): the compaction kernel's offsets
     void word_base(uint64_t first, uint64_t A, uint64_t len, std::vector<uint32_t> &wbase) const;
+    // ... the same for the union of several disjoint ranges: the slices (first, A) of `sorted`, accumulated
+    void word_base(const std::vector<std::pair<uint64_t, uint64_t>> &slices, uint64_t len, std::vector<uint32_t> &wbase) const;
+    // the disjoint union of up to k closed ranges, ascending: empty members (lo > hi) dropped, the others sorted and
+    // merged where they overlap or touch ([1, 2], [3, 4] -> [1, 4]; hi = UINT32_MAX touches nothing above it).  The
+    // canonical form of a query's range list (hnsw_search_batch_filtered_ranges): members as (lo << 32) | hi
+    static std::vector<uint64_t> canonical(const uint32_t *lo, const uint32_t *hi, uint32_t k);
 };
 
 // the sidecar file <dir>/labels: u64 count, then the labels of ids 0..count-1 as u32, big-endian (trailing zero labels

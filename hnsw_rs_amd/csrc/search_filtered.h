@@ -23,6 +23,15 @@
 // the bound none_bits.  The graph kernel's wave picks its row by mask_of[q] as in a call with rows alone and keeps the
 // row's pointer next to its range; the compaction of an exact-path launch ANDs allow's word onto the word it made from
 // the labels (allow == nullptr there: the range alone).
+//
+// A query may be under SEVERAL ranges (hnsw_search_batch_filtered_ranges; n_ranges = K > 1, and no rows): id i is then
+// allowed iff i < allow_bits and label(i) lies in at least one of [range_lo[q K + j], range_hi[q K + j]], j < K.  A member
+// with lo > hi is empty; the members may overlap and come in any order (the caller's device memory, as it is).  The
+// graph kernel's wave keeps its K members in LDS behind its 16-byte slot, an empty one replaced by a copy of one that is
+// not (harmless under any-of; all empty: the id bound 0, as an empty range has today).  An exact-path launch gets its
+// list by value (RangeList: n members, disjoint and none of them empty: the host's canonical form), and the
+// compaction's word is made from `label in any of them`.  The list is the compaction kernel's own argument, not a part
+// of FilterArgs: see n_ranges there.
 #pragma once
 
 #include "device_index.h"
@@ -32,6 +41,7 @@ namespace hx {
 #define HX_FILT_MAX_EF 256  // ef' on the graph path: F and R are four registers per lane at most
 #define HX_FILT_MAX_N 64    // results per query (both paths)
 #define HX_FILT_RANGE_LDS 16  // bytes of LDS a wave under a label range keeps its range in (lo, hi - lo, its mask row's pointer)
+#define HX_FILT_MAX_RANGES 16   // members of a query's range list (HNSW_RANGES_MAX); each keeps 8 bytes more (lo, hi - lo)
 #define HX_FILT_MAX_SLOTS_LOG2 15  // the largest visited table: 32768 slots, at most 24576 ids (75 %)
 
 struct FilterArgs {
@@ -46,6 +56,10 @@ struct FilterArgs {
     uint64_t deny_bits;        // ids the deny mask covers (a multiple of 64); ids beyond it are not denied
     uint32_t n, ef;            // results per query, ef' = max(ef, n, 1)
     uint32_t n_masks;          // rows of allow (read with mask_of only): a mask_of entry is below it or HNSW_MASK_NONE
+    // K > 1: the graph kernel's query q is under the K ranges range_lo / range_hi [q K, q K + K); <= 1: under the one
+    // range [q].  (Here, in what was padding: the struct is the kernels' argument block, and the 128d graph kernel
+    // loses a wave of occupancy when it grows)
+    uint32_t n_ranges;
     const uint32_t *labels;    // the label column (device), or nullptr: the call has no label range
     uint64_t label_len;        // labels the column holds; an id at or beyond it has label 0
     const uint32_t *range_lo;  // with labels, the graph kernel (device): query q is under [range_lo[q], range_hi[q]] ...
@@ -55,6 +69,13 @@ struct FilterArgs {
     float *out_dists;          // nq x n
     uint32_t *out_counts;      // nq
     hnsw_query_stats *out_stats;  // nq
+};
+
+// The range list of an exact-path launch under several ranges (by value: the launch needs no allocation or copy);
+// n <= 1: the launch is under FilterArgs::lo / hi alone
+struct RangeList {
+    uint32_t n = 0;
+    uint32_t lo[HX_FILT_MAX_RANGES], hi[HX_FILT_MAX_RANGES];
 };
 
 // The second source form of hx_filt_merge_kernel (hnsw_merge_topk_device): instead of the nseg partial key lists of one
@@ -76,9 +97,12 @@ struct MergeLists {
 // ids a layer-0 visited table of 2^slots_log2 slots holds before the graph path reports HNSW_ERR_OVERFLOW
 __host__ __device__ inline uint32_t filt_visited_limit(uint32_t slots_log2) { return (1u << slots_log2) - (1u << (slots_log2 - 2)); }
 // first table size for ef' (the generic kernel's choice) and the largest one the dimension leaves room for in LDS
-// (ranged: a call under a label range, whose waves keep HX_FILT_RANGE_LDS bytes more)
-uint32_t filt_first_slots_log2(const DevView &v, uint32_t ef, bool ranged = false);
-uint32_t filt_max_slots_log2(const DevView &v, bool ranged = false);
+// (range_lds: the bytes a wave keeps its range or ranges in, filt_range_lds; 0 for a call without a label column)
+inline uint32_t filt_range_lds(bool ranged, uint32_t n_ranges = 1) {
+    return ranged ? HX_FILT_RANGE_LDS + (n_ranges > 1 ? 8u * n_ranges : 0u) : 0u;
+}
+uint32_t filt_first_slots_log2(const DevView &v, uint32_t ef, uint32_t range_lds = 0);
+uint32_t filt_max_slots_log2(const DevView &v, uint32_t range_lds = 0);
 
 // graph path: `nblocks` queries (a.qsel selects them when set); a query whose visited table fills up ends with
 // status HNSW_ERR_OVERFLOW and is run again by the caller with a larger table or answered by the exact path
@@ -88,8 +112,9 @@ int launch_filtered_graph(const DevView &v, const FilterArgs &a, uint32_t nblock
 // n_words words below allow_bits; with a.labels, "allowed" is the range [a.lo, a.hi] over the column and the kernel
 // makes the words itself (and ANDs a.allow's onto them when that is set as well).  word_base[b] = admissible ids in words [0, 64 b) (computed by the caller, who counts A
 // anyway); ids[A]
+// ; list (optional, with a.labels and without a.allow): the ids whose label lies in any of its ranges
 int launch_filter_compact(const FilterArgs &a, uint64_t n_words, const uint32_t *word_base, uint32_t *ids,
-                          hipStream_t stream);
+                          hipStream_t stream, const RangeList *list = nullptr);
 // exact path, step 2: top-n of the `nsel` queries (a.qsel, or the first nsel) over the A listed ids; part holds
 // nsel x nseg x n keys of scratch.  Writes ids, dists, counts and stats (n_dist = A, n_exp = sum_deg = 0).
 uint32_t filt_exact_segments(uint64_t A, uint32_t nsel);

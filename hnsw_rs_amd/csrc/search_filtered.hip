@@ -196,16 +196,28 @@ __device__ __forceinline__ bool filt_visit(uint32_t *tab, uint32_t slots_log2, u
 // half of the LDS slot, nullptr without a row: one 16-byte read brings the range and the row, and the mask word is read
 // for an id whose label passed.  The bound of an empty range is 0: no label is read under it.  The bound and the deleted
 // set's (deny_n: 0 when nothing is deleted, so there is no pointer test) are 32 bits, as an id is, and one scalar register
-// each: what the row costs in the prologue is paid for here.
+// each: what the row costs in the prologue is paid for here.  A wave under K > 1 ranges
+// (hnsw_search_batch_filtered_ranges; K is the kernel's argument, so the test is the wave's) has bit 1 of `filt` set as
+// well -- the column's copy is aligned far beyond 4 bytes, and a third scalar register for K costs the 128d kernel the
+// same wave of occupancy.  Its members (lo, hi - lo) are in LDS behind the slot, member j at
+// range[4 + 2 j]; the slot holds member 0 and, where the row's pointer is otherwise (a list has no row), K: a label that
+// member 0 refuses is tried against the others until one takes it.
 __device__ __forceinline__ bool filt_allowed(const uint64_t *deny, uint32_t deny_n, const uint64_t *filt, uint32_t bound,
                                              const uint32_t *range, uint32_t id) {
     if (id >= bound) return false;
     if ((uintptr_t)filt & 1) {
-        const uint32_t label = reinterpret_cast<const uint32_t *>((uintptr_t)filt - 1)[id];
+        const uint32_t label = reinterpret_cast<const uint32_t *>((uintptr_t)filt & ~(uintptr_t)3)[id];
         const uint4 r = *reinterpret_cast<const uint4 *>(range);
         bool in = label - r.x <= r.y;  // lo <= label <= hi in one unsigned compare
-        const uint64_t *row = reinterpret_cast<const uint64_t *>(((uint64_t)r.w << 32) | r.z);
-        if (in && row) in = ((row[id >> 6] >> (id & 63)) & 1ull) != 0;
+        if ((uintptr_t)filt & 2) {
+            for (uint32_t j = 1; j < r.z && !in; j++) {
+                const uint2 m = *reinterpret_cast<const uint2 *>(range + 4 + 2 * j);
+                in = label - m.x <= m.y;
+            }
+        } else {
+            const uint64_t *row = reinterpret_cast<const uint64_t *>(((uint64_t)r.w << 32) | r.z);
+            if (in && row) in = ((row[id >> 6] >> (id & 63)) & 1ull) != 0;
+        }
         if (!in) return false;
     } else if (filt && ((filt[id >> 6] >> (id & 63)) & 1ull) == 0) {
         return false;
@@ -322,7 +334,7 @@ __device__ __forceinline__ float filt_dist(const DevView &v, uint32_t id, bool a
 
 // ---------------------------------------------------------------------------------------------
 // Graph path.  LDS: visited table (4 << slots_log2 bytes) | merge buffer (64 R keys) | query | under a label range,
-// the wave's range (HX_FILT_RANGE_LDS bytes).
+// the wave's range (HX_FILT_RANGE_LDS bytes) | under K > 1 ranges, its K members (8 K bytes): filt_range_lds.
 // ---------------------------------------------------------------------------------------------
 template <int KIND, int P, int DS, int R>
 __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, const FilterArgs a, const uint32_t slots_log2) {
@@ -337,11 +349,38 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
     const bool bad_row = a.mask_of && g != HNSW_MASK_NONE && g >= a.n_masks;
     // (without rows a.allow is nullptr and g * a.mask_words is 0: no row)
     const uint64_t *row = g == HNSW_MASK_NONE ? nullptr : a.allow + (size_t)g * a.mask_words;
+    // (bit 0: the label column; bit 1, set by the launcher: the queries are under lists of ranges, filt_allowed)
     const uint64_t *allow = a.labels ? reinterpret_cast<const uint64_t *>((uintptr_t)a.labels | 1) : row;
     // the wave's label range, picked once as well; an empty one (lo > hi) allows nothing: an id bound of 0.  Under a
     // column the bound is also the bound of the label read: the host keeps the HBM copy at least as long as the index
     // (zeros beyond the labels that were set), so label_len never is the smaller one
-    const uint32_t lo = a.labels ? a.range_lo[q] : 0u, hi = a.labels ? a.range_hi[q] : 0u;
+    uint32_t lo = 0u, hi = 0u;
+    // (the query's size is the template's where the dimension is: the range's slot at a constant offset, no scalar kept)
+    constexpr uint32_t YQ_BYTES = DS == 0 ? 0u : ((KIND == HNSW_VEC_QUANT8 ? 2u * (16u * P - 8u) * 4u : DS * 4u) + 15u) & ~15u;
+    uint32_t *range = reinterpret_cast<uint32_t *>(smem + (4ull << slots_log2) + 64 * R * 8 + (YQ_BYTES ? YQ_BYTES : query_lds_bytes(v)));
+    if ((uintptr_t)a.labels & 2) {
+        // K ranges (the launcher set bit 1 of the column's pointer): lanes j < K read the query's members in one
+        // coalesced read each of lo and hi.  An empty member (lo > hi) must never match, and `label - lo <= hi - lo`
+        // has no such encoding: it becomes a copy of the first member that is not empty, which changes nothing under
+        // any-of.  All empty: the empty range (1, 0), bound 0.  (The first such lane is found by a min-reduction in
+        // vector registers: a ballot's scalar pair is one the kernel does not have here.)
+        const uint32_t K = a.n_ranges;
+        const bool mine = (uint32_t)lane < K;
+        const size_t o = (size_t)q * K + lane;
+        uint32_t l = mine ? a.range_lo[o] : 1u, h = mine ? a.range_hi[o] : 0u;
+        uint32_t f = l <= h ? (uint32_t)lane : 64u;
+#pragma unroll
+        for (int x = 32; x > 0; x >>= 1) f = min(f, (uint32_t)__shfl_xor((int)f, x));
+        const int src = (int)((f & 63u) << 2);
+        const uint32_t fl = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)l), fh = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)h);
+        if (l > h) l = fl, h = fh;
+        if (mine && f < 64u) *reinterpret_cast<uint2 *>(range + 4 + 2 * lane) = make_uint2(l, h - l);
+        // the slot's member: any that is not empty serves
+        lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(f < 64u ? fl : 1u));
+        hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(f < 64u ? fh : 0u));
+    } else if (a.labels) {
+        lo = a.range_lo[q], hi = a.range_hi[q];
+    }
     const uint64_t ids = g == HNSW_MASK_NONE ? a.none_bits : a.allow_bits;
     // (an id is below 2^32 - 1, HX_EMPTY_SLOT: the bound fits 32 bits)
     const uint32_t bound = bad_row || lo > hi ? 0u : (uint32_t)min(a.labels ? min(ids, a.label_len) : ids, (uint64_t)HX_EMPTY_SLOT);
@@ -350,12 +389,11 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
     uint32_t *htab = reinterpret_cast<uint32_t *>(smem);
     u64 *perm = reinterpret_cast<u64 *>(smem + (4ull << slots_log2));
     float *yq = reinterpret_cast<float *>(perm + 64 * R);
-    // (the query's size is the template's where the dimension is: the range's slot at a constant offset, no scalar kept)
-    constexpr uint32_t YQ_BYTES = DS == 0 ? 0u : ((KIND == HNSW_VEC_QUANT8 ? 2u * (16u * P - 8u) * 4u : DS * 4u) + 15u) & ~15u;
-    uint32_t *range = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(yq) + (YQ_BYTES ? YQ_BYTES : query_lds_bytes(v)));
     if (a.labels && lane == 0) {  // (read after the wave_fence of the first clear_visited)
         // the wave's mask row, when the call has rows as well, next to its range: one 16-byte read brings both
-        *reinterpret_cast<uint4 *>(range) = make_uint4(lo, hi - lo, (uint32_t)(uintptr_t)row, (uint32_t)((uintptr_t)row >> 32));
+        // (under a list of ranges there is no row: K takes its place)
+        const uintptr_t rw = (uintptr_t)a.labels & 2 ? (uintptr_t)a.n_ranges : (uintptr_t)row;
+        *reinterpret_cast<uint4 *>(range) = make_uint4(lo, hi - lo, (uint32_t)rw, (uint32_t)(rw >> 32));
     }
     const uint32_t vis_limit = filt_visited_limit(slots_log2);
 
@@ -515,12 +553,22 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
 // mask (a.labels and a.allow) the word made from the labels is ANDed with the mask's.
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(64) hx_filt_compact_kernel(const FilterArgs a, uint64_t n_words,
-                                                             const uint32_t *word_base, uint32_t *ids) {
+                                                             const uint32_t *word_base, uint32_t *ids, const RangeList rl) {
     const int lane = threadIdx.x;
     const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
     u64 bits = 0;
     if (a.labels) {
-        if (a.lo <= a.hi) {  // (an empty range reads no label)
+        if (rl.n > 1) {  // a list of ranges (none of them empty): the label in any of them, inside the same ballot
+            const uint64_t id0 = (uint64_t)blockIdx.x * 4096 + lane;
+            for (int j = 0; j < 64; j++) {
+                const uint64_t id = id0 + 64 * j;
+                const uint32_t label = id < a.label_len ? a.labels[id] : 0u;
+                bool any = false;
+                for (uint32_t k = 0; k < rl.n; k++) any |= label - rl.lo[k] <= rl.hi[k] - rl.lo[k];
+                const u64 in = __ballot(any);
+                if (lane == j) bits = in;
+            }
+        } else if (a.lo <= a.hi) {  // (an empty range reads no label)
             const uint64_t id0 = (uint64_t)blockIdx.x * 4096 + lane;
 #pragma unroll 8
             for (int j = 0; j < 64; j++) {
@@ -690,7 +738,7 @@ __global__ void __launch_bounds__(64) hx_filt_merge_kernel(const FilterArgs a, u
 
 template <int KIND, int P, int DS, int R>
 int launch_graph_r(const DevView &v, const FilterArgs &a, uint32_t nblocks, uint32_t slots_log2, hipStream_t stream) {
-    const size_t lds = (4ull << slots_log2) + 64ull * R * 8 + query_lds_bytes(v) + (a.labels ? HX_FILT_RANGE_LDS : 0);
+    const size_t lds = (4ull << slots_log2) + 64ull * R * 8 + query_lds_bytes(v) + filt_range_lds(a.labels != nullptr, a.n_ranges);
     return launch_checked({"filtered search kernel launch", "filtered search needs %zu bytes of LDS (> 160 KiB)"},
                           hx_filt_graph_kernel<KIND, P, DS, R>, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
 }
@@ -704,24 +752,33 @@ int launch_graph(const DevView &v, const FilterArgs &a, uint32_t nblocks, uint32
 
 }  // namespace
 
-uint32_t filt_first_slots_log2(const DevView &v, uint32_t ef, bool ranged) {
-    return std::min(default_slots_log2(ef, v.S0), filt_max_slots_log2(v, ranged));
+uint32_t filt_first_slots_log2(const DevView &v, uint32_t ef, uint32_t range_lds) {
+    return std::min(default_slots_log2(ef, v.S0), filt_max_slots_log2(v, range_lds));
 }
 
-uint32_t filt_max_slots_log2(const DevView &v, bool ranged) {
+uint32_t filt_max_slots_log2(const DevView &v, uint32_t range_lds) {
     const uint32_t yqb = query_lds_bytes(v);
     uint32_t s = HX_FILT_MAX_SLOTS_LOG2;
-    while (s > 12 && (4ull << s) + 64ull * 4 * 8 + yqb + (ranged ? HX_FILT_RANGE_LDS : 0) > 160 * 1024) s--;
+    while (s > 12 && (4ull << s) + 64ull * 4 * 8 + yqb + range_lds > 160 * 1024) s--;
     return s;
 }
 
-int launch_filtered_graph(const DevView &v, const FilterArgs &a, uint32_t nblocks, uint32_t slots_log2,
+int launch_filtered_graph(const DevView &v, const FilterArgs &args, uint32_t nblocks, uint32_t slots_log2,
                           hipStream_t stream) {
+    FilterArgs a = args;
     if (nblocks == 0) return HNSW_OK;
     if (a.ef == 0 || a.ef > HX_FILT_MAX_EF || a.n == 0 || a.n > HX_FILT_MAX_N || a.n > a.ef) {
         set_error("filtered search: needs 1 <= n <= %d and n <= ef' <= %d", HX_FILT_MAX_N, HX_FILT_MAX_EF);
         return HNSW_ERR_ARG;
     }
+    if (a.n_ranges > HX_FILT_MAX_RANGES || (a.n_ranges > 1 && (a.allow || !a.labels || ((uintptr_t)a.labels & 3)))) {
+        // (the LDS behind the slot holds that many, and no row)
+        set_error("filtered search: at most %d label ranges per query, over the label column alone", HX_FILT_MAX_RANGES);
+        return HNSW_ERR_ARG;
+    }
+    // K > 1 reaches the kernel as bit 1 of the column's pointer (its copy is aligned far beyond 4 bytes): the kernel has
+    // no scalar register to keep K or a flag in while it walks (filt_allowed)
+    if (a.n_ranges > 1) a.labels = reinterpret_cast<const uint32_t *>((uintptr_t)a.labels | 2);
     if (v.kind == HNSW_VEC_QUANT8) {
         if (v.dim == 100 && v.half_bytes == 64) return launch_graph<HNSW_VEC_QUANT8, 4, 100>(v, a, nblocks, slots_log2, stream);
         return launch_graph<HNSW_VEC_QUANT8, 0, 0>(v, a, nblocks, slots_log2, stream);
@@ -732,11 +789,15 @@ int launch_filtered_graph(const DevView &v, const FilterArgs &a, uint32_t nblock
 }
 
 int launch_filter_compact(const FilterArgs &a, uint64_t n_words, const uint32_t *word_base, uint32_t *ids,
-                          hipStream_t stream) {
+                          hipStream_t stream, const RangeList *list) {
     if (n_words == 0) return HNSW_OK;
+    if (list && (list->n > HX_FILT_MAX_RANGES || (list->n > 1 && (!a.labels || a.allow)))) {
+        set_error("filter compaction: at most %d label ranges, over the label column alone", HX_FILT_MAX_RANGES);
+        return HNSW_ERR_ARG;
+    }
     const uint64_t nb = (n_words + 63) / 64;
     return launch_checked({"filter compaction kernel launch"}, hx_filt_compact_kernel, dim3((uint32_t)nb), dim3(64), 0, stream, a,
-                          n_words, word_base, ids);
+                          n_words, word_base, ids, list ? *list : RangeList{});
 }
 
 uint32_t filt_exact_segments(uint64_t A, uint32_t nsel) {

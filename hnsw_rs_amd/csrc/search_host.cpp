@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
+#include <map>
 #include <mutex>
 #include <type_traits>
 #include <utility>
@@ -253,16 +254,17 @@ struct ExactScratch {
 // the exact path for nsel queries under ONE mask (a.allow, a.allow_bits; a.mask_of is not read): those of d_sel, or
 // the first nsel of the call; the mask's word offsets are at d_wb.  shape_nsel: the query count the launch shape
 // (queries per launch, segments) is chosen for.  d_list: the mask's admissible ids, already compacted (a resident
-// set's cached list) -- no compaction is launched and d_wb is not read; nullptr: compacted into the scratch
+// set's cached list) -- no compaction is launched and d_wb is not read; nullptr: compacted into the scratch, under
+// `ranges` when the mask is the union of several label ranges
 int filtered_exact(const DevView &v, const FilterArgs &a, uint64_t nsel, const uint32_t *d_sel, uint64_t A,
                    const uint32_t *d_wb, uint64_t shape_nsel, const ExactScratch &x, unsigned char *dv,
-                   hipStream_t stream, const uint32_t *d_list = nullptr) {
+                   hipStream_t stream, const uint32_t *d_list = nullptr, const RangeList *ranges = nullptr) {
     const uint32_t chunk = (uint32_t)std::min<uint64_t>(shape_nsel, 65535), nseg = filt_exact_segments(A, chunk);
     const uint32_t *d_ids = d_list;
     int r = HNSW_OK;
     if (!d_list) {
         uint32_t *d_scratch_ids = reinterpret_cast<uint32_t *>(dv + x.o_ids);
-        r = launch_filter_compact(a, (a.allow_bits + 63) / 64, d_wb, d_scratch_ids, stream);
+        r = launch_filter_compact(a, (a.allow_bits + 63) / 64, d_wb, d_scratch_ids, stream, ranges);
         d_ids = d_scratch_ids;
     }
     for (uint64_t c = 0; r == HNSW_OK && c < nsel; c += chunk) {
@@ -288,7 +290,9 @@ int filtered_exact(const DevView &v, const FilterArgs &a, uint64_t nsel, const u
 // A query's filter is named by a key and a range.  The key: 0 in a call with one mask (or with none: the undeleted ids)
 // and in a call with label ranges alone, the row or HNSW_MASK_NONE in a call with rows (the caller's or a resident
 // set's).  The range: (lo << 32) | hi in a call with label ranges (alone, or next to the rows of a set), FULL_RANGE
-// otherwise.  The queries under one (key, range) are a group: the planner's unit, and that of the exact path's launches.
+// otherwise.  In a call with a LIST of ranges per query (hnsw_search_batch_filtered_ranges) the range is the index of the
+// query's canonical list in the call's table of them (FilterSource::lists): two raw lists with one canonical form are one
+// group.  The queries under one (key, range) are a group: the planner's unit, and that of the exact path's launches.
 constexpr uint64_t UNCOUNTED = ~0ull;
 constexpr uint64_t FULL_RANGE = 0xFFFFFFFFull;  // [0, UINT32_MAX]
 constexpr size_t NO_WB = ~(size_t)0;
@@ -305,22 +309,49 @@ struct Group {
 // What turns a key into what the exact path needs, one per call: the masks, set or label column behind the keys, the
 // key of every query (host memory) and the call's own arguments.
 struct FilterSource {
-    enum Kind { ONE, ROWS, SET, RANGE, SET_RANGE } kind;
+    enum Kind { ONE, ROWS, SET, RANGE, SET_RANGE, RANGES } kind;
     hnsw_index *h;
     const uint64_t *masks;  // ONE, ROWS: the caller's words (nullptr: every id below bits)
     hnsw_mask_set *set;     // SET
     uint64_t len, bits, row_words;  // the index length, min(allow_bits, len), words of a row
     const uint32_t *mask_of = nullptr, *lo = nullptr, *hi = nullptr;  // per query: ROWS, SET and SET_RANGE (nullptr: row 0); RANGE and SET_RANGE
     FilterArgs base{};      // every mask or range: the graph kernel's wave picks its query's
+    // RANGES: query i is under the K members lo / hi [i K, i K + K); its canonical list (LabelColumn::canonical: disjoint,
+    // ascending, no empty member) is lists[list_of[i]].  The table is interned in ascending order of the lists, so the
+    // groups of a K == 1 call come in the order a RANGE call's do.  A list without members is the one empty range (1, 0);
+    // with K == 1 the member is the caller's pair as it is, and every launch is that of the RANGE call
+    uint32_t K = 1;
+    std::vector<uint32_t> list_of;
+    std::vector<std::vector<uint64_t>> lists;
+    void intern(uint64_t nq) {
+        std::map<std::vector<uint64_t>, uint32_t> table;
+        std::vector<std::map<std::vector<uint64_t>, uint32_t>::iterator> at(nq);
+        for (uint64_t i = 0; i < nq; i++) {
+            std::vector<uint64_t> c = K == 1 ? std::vector<uint64_t>{((uint64_t)lo[i] << 32) | hi[i]}
+                                             : LabelColumn::canonical(lo + i * K, hi + i * K, K);
+            if (c.empty()) c.push_back(1ull << 32);
+            at[i] = table.emplace(std::move(c), 0u).first;
+        }
+        lists.clear();
+        for (auto &e : table) {
+            e.second = (uint32_t)lists.size();
+            lists.push_back(e.first);
+        }
+        list_of.resize(nq);
+        for (uint64_t i = 0; i < nq; i++) list_of[i] = at[i]->second;
+    }
 
     FilterSource(hnsw_index *h_, Kind k, const uint64_t *masks_, hnsw_mask_set *set_, uint64_t allow_bits)
         : kind(k), h(h_), masks(masks_), set(set_), len(index_len(h_)), bits(std::min<uint64_t>(allow_bits, len)),
           row_words((allow_bits + 63) / 64) {}
 
     bool of_set() const { return kind == SET || kind == SET_RANGE; }
-    bool labelled() const { return kind == RANGE || kind == SET_RANGE; }
-    uint64_t key(uint32_t i) const { return kind != RANGE && mask_of ? mask_of[i] : 0; }
-    uint64_t range(uint32_t i) const { return labelled() ? ((uint64_t)lo[i] << 32) | hi[i] : FULL_RANGE; }
+    bool labelled() const { return kind == RANGE || kind == SET_RANGE || kind == RANGES; }
+    uint64_t key(uint32_t i) const { return kind != RANGE && kind != RANGES && mask_of ? mask_of[i] : 0; }
+    uint64_t range(uint32_t i) const {
+        if (kind == RANGES) return list_of[i];
+        return labelled() ? ((uint64_t)lo[i] << 32) | hi[i] : FULL_RANGE;
+    }
     // the key names a row with words (masks may be NULL when allow_bits is 0: nothing is allowed, no word is read)
     bool has_words(uint64_t key) const {
         if (kind == ONE) return masks != nullptr;
@@ -329,7 +360,7 @@ struct FilterSource {
     // the group is under a label range.  Next to a set, [0, UINT32_MAX] is no range: the group is the plain row, with the
     // set's caches (and so is a row of a set without words: nothing is allowed); under HNSW_MASK_NONE it is the plain range
     bool ranged(const Group &g) const {
-        return kind == RANGE || (kind == SET_RANGE && g.range != FULL_RANGE && (g.key == HNSW_MASK_NONE || set->W != 0));
+        return kind == RANGE || kind == RANGES || (kind == SET_RANGE && g.range != FULL_RANGE && (g.key == HNSW_MASK_NONE || set->W != 0));
     }
     // its id bound (a range call's bits are the index length)
     uint64_t bound(uint64_t key) const { return key == HNSW_MASK_NONE ? len : bits; }
@@ -349,6 +380,7 @@ struct FilterSource {
         if (labelled()) bind_labels(h, base);
         base.range_lo = d_lo;
         base.range_hi = d_hi;
+        base.n_ranges = kind == RANGES ? K : 0;
         base.n = n;
         base.ef = efp;
     }
@@ -363,7 +395,21 @@ struct FilterSource {
         if (!rg) ax.labels = nullptr;         // (a plain row next to ranged groups: the compaction reads its words alone)
         ax.lo = rg ? (uint32_t)(g.range >> 32) : 0;
         ax.hi = rg ? (uint32_t)g.range : 0;
+        ax.n_ranges = 0;
+        if (kind == RANGES) {  // (the first member of the group's list; one member: the launch of a RANGE group)
+            const uint64_t m0 = lists[(size_t)g.range][0];
+            ax.lo = (uint32_t)(m0 >> 32), ax.hi = (uint32_t)m0;
+        }
         return ax;
+    }
+    // ... and its canonical list, by value, for the compaction (n == 0: the group is under args' lo / hi alone)
+    RangeList list(const Group &g) const {
+        RangeList r{};
+        if (kind != RANGES || lists[(size_t)g.range].size() < 2) return r;
+        const std::vector<uint64_t> &l = lists[(size_t)g.range];
+        r.n = (uint32_t)l.size();
+        for (size_t j = 0; j < l.size(); j++) r.lo[j] = (uint32_t)(l[j] >> 32), r.hi[j] = (uint32_t)l[j];
+        return r;
     }
 
     // What `resolve` reads is locked by this: a set's caches (a row is counted when it, the deleted set or the length
@@ -377,7 +423,7 @@ struct FilterSource {
         Locks l;
         if (of_set()) l.set = std::unique_lock<std::mutex>(set->mu);
         if (labelled()) l.lab = std::unique_lock<std::mutex>(h->lab.mu);
-        if (kind == RANGE) h->lab.sort_for(h->del, len);
+        if (kind == RANGE || kind == RANGES) h->lab.sort_for(h->del, len);
         return l;
     }
     // The admissible ids of a row AND a range: the undeleted ids below `bits` whose bit is set in the row and whose
@@ -422,7 +468,8 @@ struct FilterSource {
     }
     // Counts a group: A (kept when it is known already), exact = A <= exact_max, a set row's list while it is valid, and
     // its word offsets, appended to wbs.  A range's admissible ids are a slice of the sorted copy, found by two binary
-    // searches; its offsets cost a pass over the slice and are counted only when it is exact.  A row AND a range are
+    // searches; its offsets cost a pass over the slice and are counted only when it is exact.  A list of ranges is
+    // disjoint: A is the sum over its members' slices, its offsets accumulate over them.  A row AND a range are
     // counted by count_both, up to exact_max
     void resolve(Group &g, int64_t exact_max, std::vector<uint32_t> &wbs) const {
         std::vector<uint32_t> own;
@@ -430,12 +477,20 @@ struct FilterSource {
         const bool rg = ranged(g), both = rg && has_words(g.key);
         const uint32_t lo = (uint32_t)(g.range >> 32), hi = (uint32_t)g.range;
         uint64_t A, first = 0;
+        std::vector<std::pair<uint64_t, uint64_t>> slices;  // RANGES: (first, count) of every member
         if (rg && kind == SET_RANGE) h->lab.sort_for(h->del, len);
         if (both) {
             A = lo > hi ? 0 : count_both((uint32_t)g.key, lo, hi, exact_max, own, g.A_ub);
             if (A == UNCOUNTED) {
                 g.exact = false;
                 return;
+            }
+        } else if (kind == RANGES) {
+            A = 0;
+            for (uint64_t m : lists[(size_t)g.range]) {
+                const uint64_t c = h->lab.count((uint32_t)(m >> 32), (uint32_t)m, &first);
+                slices.emplace_back(first, c);
+                A += c;
             }
         } else if (rg) {
             A = h->lab.count(lo, hi, &first);
@@ -450,7 +505,10 @@ struct FilterSource {
         if (g.A == UNCOUNTED) g.A = A;
         g.exact = (int64_t)g.A <= exact_max;
         if (rg && !g.exact) return;
-        if (rg && !both) h->lab.word_base(first, g.A, len, own);
+        if (kind == RANGES)
+            h->lab.word_base(slices, len, own);
+        else if (rg && !both)
+            h->lab.word_base(first, g.A, len, own);
         g.wb = wbs.size();
         g.n_wb = wb->size();
         wbs.insert(wbs.end(), wb->begin(), wb->end());
@@ -497,8 +555,9 @@ int exact_group(const FilterSource &src, const Group &g, const uint32_t *d_sel, 
         HIP_TRY(hipMemcpyAsync(at.d_wb + g.wb, at.wbs + g.wb, g.n_wb * 4, hipMemcpyHostToDevice, at.stream));
         if (src.of_set() && src.has_words(g.key) && !src.ranged(g)) src.h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
     }
+    const RangeList ranges = src.list(g);
     return filtered_exact(src.h->dev.view, src.args(g), g.nq, d_sel, g.A, at.d_wb + g.wb, shape_nsel, at.x, at.dv, at.stream,
-                          g.d_list);
+                          g.d_list, &ranges);
 }
 
 // Path 2: the queries of `sel` filled the largest visited table and are answered by the exact path, each under its own
@@ -597,16 +656,23 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     // (the entry points see to hi with lo, and to mask_of with a set)
     FilterSource src(h,
                      m.lo && m.set ? FilterSource::SET_RANGE
+                     : m.n_ranges  ? FilterSource::RANGES
                      : m.lo        ? FilterSource::RANGE
                      : m.set       ? FilterSource::SET
                      : m.mask_of   ? FilterSource::ROWS
                                    : FilterSource::ONE,
                      m.masks, m.set, m.allow_bits);
     src.mask_of = m.mask_of, src.lo = m.lo, src.hi = m.hi;
+    const bool listed = src.kind == FilterSource::RANGES;
+    const uint64_t rk = listed ? m.n_ranges : 1;  // ranges per query
+    if (listed) {
+        src.K = m.n_ranges;
+        src.intern(nq);
+    }
     hnsw_mask_set *const set = m.set;
     // ranged: the call has a label column (next to a set: both); rowed: it has a row per query
     const bool ranged = src.labelled(), both = src.kind == FilterSource::SET_RANGE, multi = src.kind != FilterSource::ONE;
-    const bool rowed = multi && src.kind != FilterSource::RANGE;
+    const bool rowed = multi && src.kind != FilterSource::RANGE && !listed;
     const uint64_t len = src.len, bits = src.bits, row_words = src.row_words;
     // ---- the planner, per group: its admissible ids decide its queries' path.  A set stays locked until its HBM copy
     // is up to date and the lists this call needs are made; the label column only while the ranges are counted ----
@@ -657,8 +723,8 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     // word offsets have room for one more range, that of a path 2 group, counted when a query gets there)
     const uint64_t up_words = !m.masks || set ? 0 : multi ? (uint64_t)m.n_masks * row_words : (bits + 63) / 64;
     const size_t o_q = 0, o_mask = o_q + align256(nq * d * 4), o_mof = o_mask + align256(up_words * 8);
-    const size_t o_lo = o_mof + (rowed ? align256(nq * 4) : 0), o_hi = o_lo + (ranged ? align256(nq * 4) : 0);
-    const size_t o_sel = o_hi + (ranged ? align256(nq * 4) : 0), o_xsel = o_sel + align256(nq * 4);
+    const size_t o_lo = o_mof + (rowed ? align256(nq * 4) : 0), o_hi = o_lo + (ranged ? align256(nq * rk * 4) : 0);
+    const size_t o_sel = o_hi + (ranged ? align256(nq * rk * 4) : 0), o_xsel = o_sel + align256(nq * 4);
     const size_t wb_lazy = ranged ? std::max<uint64_t>(1, ((len + 63) / 64 + 63) / 64) : 0;
     const ExactScratch x(o_xsel + align256(multi ? nq * 4 : 0), nq, n, A_max, wb_all.size() + wb_lazy);
     const size_t o_out = x.end;
@@ -680,8 +746,8 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         HIP_TRY(hipMemcpyAsync(at.d_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, s.stream));
     if (multi) {
         if (ranged) {
-            HIP_TRY(hipMemcpyAsync(d_lo, m.lo, nq * 4, hipMemcpyHostToDevice, s.stream));
-            HIP_TRY(hipMemcpyAsync(d_hi, m.hi, nq * 4, hipMemcpyHostToDevice, s.stream));
+            HIP_TRY(hipMemcpyAsync(d_lo, m.lo, nq * rk * 4, hipMemcpyHostToDevice, s.stream));
+            HIP_TRY(hipMemcpyAsync(d_hi, m.hi, nq * rk * 4, hipMemcpyHostToDevice, s.stream));
         }
         if (rowed) HIP_TRY(hipMemcpyAsync(d_mof, m.mask_of, nq * 4, hipMemcpyHostToDevice, s.stream));
         if (!gsel.empty()) HIP_TRY(hipMemcpyAsync(d_sel, gsel.data(), gsel.size() * 4, hipMemcpyHostToDevice, s.stream));
@@ -723,7 +789,8 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     };
     // ONE launch of the graph path for the queries of every group planned on it, then the exact path group by group
     // (its scratch reused in stream order), then the result block in one copy
-    const uint32_t slots = filt_first_slots_log2(v, efp, ranged);
+    const uint32_t range_lds = filt_range_lds(ranged, (uint32_t)rk);
+    const uint32_t slots = filt_first_slots_log2(v, efp, range_lds);
     if (n_graph && (rc = launch_filtered_graph(v, a, (uint32_t)n_graph, slots, s.stream))) return rc;
     for (const Group &g : groups)
         if (g.exact && (rc = exact_group(src, g, multi ? d_xsel + g.q0 : nullptr, g.nq, at))) return rc;
@@ -735,7 +802,7 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         // queries whose visited table filled up run again with a table twice the size, all groups together, and those
         // that fill the largest one take path 2
         rc = rerun_overflowed(
-            v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v, ranged), d_sel, s.stream, fetch,
+            v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v, range_lds), d_sel, s.stream, fetch,
             [&](const std::vector<uint32_t> &sel) -> int {
                 return path2(src, sel, path, &groups, multi ? 0 : nq, at, d_sel, wb_all.size(), nullptr, 0, fetch);
             },
@@ -752,6 +819,9 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         h->n_filt_set_range_groups.fetch_add(groups.size(), std::memory_order_relaxed);
     } else if (set) {
         h->n_filt_set_calls.fetch_add(1, std::memory_order_relaxed);
+    } else if (listed) {
+        h->n_filt_ranges_calls.fetch_add(1, std::memory_order_relaxed);
+        h->n_filt_ranges_groups.fetch_add(groups.size(), std::memory_order_relaxed);
     } else if (ranged) {
         h->n_filt_range_calls.fetch_add(1, std::memory_order_relaxed);
         h->n_filt_range_ranges.fetch_add(groups.size(), std::memory_order_relaxed);
@@ -781,7 +851,8 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
                            uint32_t *d_ids, float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
                            hipStream_t stream, bool finish, uint8_t *paths) {
     hnsw_mask_set *const set = f.set;
-    const bool ranged = f.d_lo != nullptr, both = set && ranged, deleted = !set && !ranged;
+    const bool ranged = f.d_lo != nullptr, both = set && ranged, deleted = !set && !ranged, listed = f.n_ranges != 0;
+    const uint64_t rk = listed ? f.n_ranges : 1;  // ranges per query
     const uint32_t efp = std::max(std::max(ef, n), 1u);
     if (n > HX_FILT_MAX_N || efp > HX_FILT_MAX_EF) {
         set_error("%s: needs n <= %d and ef' = max(ef, n) <= %d", deleted ? "search with deleted ids" : "filtered device search",
@@ -819,20 +890,27 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
         t_counts.st = stream;
         d_counts = static_cast<uint32_t *>(t_counts.p);
     }
-    FilterSource src(h, both ? FilterSource::SET_RANGE : set ? FilterSource::SET : ranged ? FilterSource::RANGE : FilterSource::ONE,
+    FilterSource src(h,
+                     both     ? FilterSource::SET_RANGE
+                     : set    ? FilterSource::SET
+                     : listed ? FilterSource::RANGES
+                     : ranged ? FilterSource::RANGE
+                              : FilterSource::ONE,
                      nullptr, set, set ? set->allow_bits : index_len(h));
+    src.K = (uint32_t)rk;
     src.bind(dq.q, set ? set->d_rows() : nullptr, f.d_mask_of, f.d_lo, f.d_hi, set ? set->n_masks : 0, n, efp);
     FilterArgs &a = src.base;
     a.out_ids = d_ids;
     a.out_dists = d_dists;
     a.out_counts = d_counts;
     a.out_stats = d_stats;
-    const uint32_t slots = filt_first_slots_log2(v, efp, ranged);
+    const uint32_t range_lds = filt_range_lds(ranged, (uint32_t)rk);
+    const uint32_t slots = filt_first_slots_log2(v, efp, range_lds);
     if (!finish) return launch_filtered_graph(v, a, (uint32_t)nq, slots, stream);
 
     // scratch: the selection on the device; the statuses and the keys of the queries (the rows and ranges they name:
     // [rows | lo | hi]) on the host; the exact path's part ([selection | its scratch]) is sized only when a query reaches it
-    const size_t st_bytes = nq * sizeof(hnsw_query_stats), o_keys = align256(st_bytes), r_bytes = align256(nq * 4);
+    const size_t st_bytes = nq * sizeof(hnsw_query_stats), o_keys = align256(st_bytes), r_bytes = align256(nq * rk * 4);
     const size_t pin_bytes = deleted ? st_bytes : o_keys + 3 * r_bytes;
     ScratchLease lease(h);
     if ((rc = lease.prepare(h->dev.device, align256(nq * 4), pin_bytes))) return rc;
@@ -845,20 +923,21 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
         HIP_TRY(hipMemcpyAsync(pin, d_stats, st_bytes, hipMemcpyDeviceToHost, stream));
         if (f.d_mask_of && !have_keys) HIP_TRY(hipMemcpyAsync(k0, f.d_mask_of, nq * 4, hipMemcpyDeviceToHost, stream));
         if (ranged && !have_keys) {
-            HIP_TRY(hipMemcpyAsync(k1, f.d_lo, nq * 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(k2, f.d_hi, nq * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(k1, f.d_lo, nq * rk * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(k2, f.d_hi, nq * rk * 4, hipMemcpyDeviceToHost, stream));
         }
         HIP_TRY(hipStreamSynchronize(stream));
-        have_keys = true;
         out = st = reinterpret_cast<const hnsw_query_stats *>(pin);
         if (f.d_mask_of) src.mask_of = k0;
         if (ranged) src.lo = k1, src.hi = k2;
+        if (listed && !have_keys) src.intern(nq);  // (the lists are seen here for the first time)
+        have_keys = true;
         return HNSW_OK;
     };
     std::vector<uint8_t> path(nq, 0);
     uint64_t n2 = 0;
     rc = rerun_overflowed(
-        v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v, ranged), static_cast<uint32_t *>(lease.s->dev), stream,
+        v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v, range_lds), static_cast<uint32_t *>(lease.s->dev), stream,
         fetch,
         [&](const std::vector<uint32_t> &sel) -> int {
             // (a query that names no row of the set ended with HNSW_ERR_ARG, not with an overflow: every row here exists)
@@ -875,8 +954,8 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
         for (uint64_t i = 0; i < nq; i++) named[i] = {src.key((uint32_t)i), src.range((uint32_t)i)};
         std::sort(named.begin(), named.end());
         const uint64_t distinct = (uint64_t)(std::unique(named.begin(), named.end()) - named.begin());
-        (both ? h->n_filt_set_range_calls : h->n_filt_range_calls).fetch_add(1, std::memory_order_relaxed);
-        (both ? h->n_filt_set_range_groups : h->n_filt_range_ranges).fetch_add(distinct, std::memory_order_relaxed);
+        (both ? h->n_filt_set_range_calls : listed ? h->n_filt_ranges_calls : h->n_filt_range_calls).fetch_add(1, std::memory_order_relaxed);
+        (both ? h->n_filt_set_range_groups : listed ? h->n_filt_ranges_groups : h->n_filt_range_ranges).fetch_add(distinct, std::memory_order_relaxed);
     }
     if (paths) memcpy(paths, path.data(), nq);
     for (uint64_t i = 0; i < nq; i++)

@@ -89,13 +89,17 @@ int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, u
 // (hnsw_search_batch_filtered_set_range): query i is under the ids of row mask_of[i] whose label lies in [lo[i], hi[i]],
 // the planner's unit is a distinct (row, lo, hi) triple, counted by walking the cheaper of the range's slice of the
 // sorted copy and the row's set bits, and the set's per-row caches serve only the triples whose range is [0, UINT32_MAX].
+// Or it has a LIST of n_ranges ranges per query (hnsw_search_batch_filtered_ranges; row-major, a member with lo > hi is
+// empty): the planner's unit is a distinct canonical list -- empties dropped, sorted, overlapping and adjacent members
+// merged -- counted exactly as the sum of its disjoint members' slices of the sorted copy.
 struct MaskSpec {
     const uint64_t *masks = nullptr;
     uint64_t allow_bits = 0;
     uint32_t n_masks = 1;
     const uint32_t *mask_of = nullptr;  // nq entries
     hnsw_mask_set *set = nullptr;
-    const uint32_t *lo = nullptr, *hi = nullptr;  // nq entries each
+    const uint32_t *lo = nullptr, *hi = nullptr;  // nq entries each (nq x n_ranges with a list per query)
+    uint32_t n_ranges = 0;  // K > 0: query i is under the union of [lo[i K + j], hi[i K + j]], j < K (no masks, no set)
 };
 
 // The admissible ids of a mask: below bits = min(allow_bits, len), allowed by `allow` (nullptr: all), not deleted.
@@ -123,6 +127,7 @@ int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t
 struct DeviceFilter {
     hnsw_mask_set *set = nullptr;
     const uint32_t *d_mask_of = nullptr, *d_lo = nullptr, *d_hi = nullptr;
+    uint32_t n_ranges = 0;  // K > 0: d_lo / d_hi hold nq x K members (hnsw_search_batch_filtered_ranges_device)
 };
 
 // hnsw_search_batch_device while ids are deleted, hnsw_search_batch_filtered_device, _filtered_range_device and

@@ -421,6 +421,59 @@ class HNSW:
             _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
         return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
 
+    # ---- label-set filtered search: several label ranges per query ------------------------------------------------
+    def search_batch_filtered_ranges(self, Q, n, ef, ranges):
+        """k-NN among the ids whose label lies in at least one of the query's ranges
+        (hnsw_search_batch_filtered_ranges).  ranges: one list per query, its members (lo, hi) or an int x meaning [x, x]; ragged
+        lists are padded with the empty range (1, 0) (pack_ranges).  -> as search_batch_filtered"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        nq = Q.shape[0]
+        lo, hi = pack_ranges(ranges, nq)
+        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        paths = np.zeros(nq, dtype=np.uint8)
+        check(self._L.hnsw_search_batch_filtered_ranges(
+            self._h, _p(Q, _f32p), nq, n, ef, lo.shape[1], _p(lo, _u32p), _p(hi, _u32p), _p(ids, _u32p), _p(dists, _f32p),
+            _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
+        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+
+    def search_batch_filtered_ranges_device(self, d_Q, nq, n, ef, n_ranges, d_lo, d_hi, d_ids, d_dists, d_counts,
+                                            d_stats, stream=0):
+        """hnsw_search_batch_filtered_ranges_device over torch device tensors (or raw device pointers): d_lo / d_hi
+        uint32 [nq, n_ranges] in HBM; one launch enqueued on `stream`, no sync."""
+        p = self._dptr
+        check(self._L.hnsw_search_batch_filtered_ranges_device(self._h, p(d_Q), nq, n, ef, n_ranges, p(d_lo), p(d_hi),
+                                                               p(d_ids), p(d_dists), p(d_counts), p(d_stats),
+                                                               stream or None))
+
+    def search_batch_filtered_ranges_device_finish(self, d_Q, nq, n, ef, n_ranges, d_lo, d_hi, d_ids, d_dists, d_counts,
+                                                   d_stats, stream=0, paths=False):
+        """Completes search_batch_filtered_ranges_device: synchronises, re-runs overflowed queries, answers those that
+        fill the largest table by the exact path, raises the first per-query error.  paths=True -> uint8 [nq] (0 / 2)"""
+        p = self._dptr
+        out = np.zeros(nq, dtype=np.uint8) if paths else None
+        check(self._L.hnsw_search_batch_filtered_ranges_device_finish(
+            self._h, p(d_Q), nq, n, ef, n_ranges, p(d_lo), p(d_hi), p(d_ids), p(d_dists), p(d_counts), p(d_stats),
+            stream or None, None if out is None else _p(out, _u8p)))
+        return out
+
+    def count_labels_in_ranges(self, ranges):
+        """hnsw_count_labels_in_ranges: the undeleted ids whose label lies in the union of `ranges` (members (lo, hi) or
+        an int x meaning [x, x]) -- the planner's own count.  Needs no GPU."""
+        ranges = list(ranges)
+        if not ranges:
+            lo = hi = np.zeros(0, dtype=np.uint32)
+        else:
+            lo, hi = pack_ranges([ranges], 1)
+        out = C.c_uint64(0)
+        check(self._L.hnsw_count_labels_in_ranges(self._h, _p(lo, _u32p) if lo.size else None,
+                                                  _p(hi, _u32p) if hi.size else None, lo.size, C.byref(out)))
+        return int(out.value)
+
     @staticmethod
     def _dptr(t):
         """a torch device tensor (or a raw device pointer, or None) -> the pointer as an int or None"""
@@ -818,6 +871,30 @@ def pack_allow(allow, n_points=None):
     if words.size == 0:
         words = np.zeros(1, dtype=np.uint64)
     return words, nbits
+
+
+def pack_ranges(ranges, nq=None):
+    """The range lists of a batch as hnsw_search_batch_filtered_ranges takes them -> (lo, hi), uint32 [nq, K], row-major.
+    ranges: one list per query, its members (lo, hi) pairs or an int x meaning [x, x]; K is the longest list's length
+    (at least 1) and shorter lists are padded with the empty range (1, 0)."""
+    def member(x):
+        if isinstance(x, (int, np.integer)):
+            l = h = int(x)
+        else:
+            l, h = (int(v) for v in x)
+        if not (0 <= l <= _lib.UINT32_MAX and 0 <= h <= _lib.UINT32_MAX):
+            raise ValueError("range bounds are labels: in [0, 2^32)")
+        return l, h
+    rows = [[member(x) for x in r] for r in ranges]
+    if nq is not None and len(rows) != nq:
+        raise ValueError("one range list per query")
+    K = max([len(r) for r in rows] + [1])
+    lo = np.ones((len(rows), K), dtype=np.uint32)
+    hi = np.zeros((len(rows), K), dtype=np.uint32)
+    for i, r in enumerate(rows):
+        for k, (l, h) in enumerate(r):
+            lo[i, k], hi[i, k] = l, h
+    return lo, hi
 
 
 def pack_allow_many(masks, n_points=None):

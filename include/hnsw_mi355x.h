@@ -191,7 +191,8 @@ int hnsw_search_batch(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, ui
  * nothing deleted.  Masks resident in HBM across calls and a device-pointer form are hnsw_mask_set's, below.  Not
  * provided: coalescing of one-query filtered calls, filtered sharded search, the Rust shim's binding, and a label
  * range (hnsw_search_batch_filtered_range, below) combined with a per-call mask or a mask per query in one call (with a
- * row of a resident set it is hnsw_search_batch_filtered_set_range, below). */
+ * row of a resident set it is hnsw_search_batch_filtered_set_range, below; a disjunction of label ranges is
+ * hnsw_search_batch_filtered_ranges, below). */
 int hnsw_search_batch_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
                                const uint64_t *allow, uint64_t allow_bits, uint32_t *ids, float *dists,
                                uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths /* 0/1/2 or NULL */);
@@ -298,9 +299,11 @@ int hnsw_search_batch_filtered_device_finish(hnsw_index *h, const float *d_Q, ui
  * hnsw_set_device carry the column, hnsw_save writes it as the file `labels` (see hnsw_save); hnsw_snapshot_describe /
  * _adopt do not carry it, but a device-only replica may set labels of its own (its length is the header's).
  * hnsw_set_labels must not run concurrently with a range search on the handle.
- * A range combined with a row of a resident mask set in one call is hnsw_search_batch_filtered_set_range, below.
+ * A range combined with a row of a resident mask set in one call is hnsw_search_batch_filtered_set_range, below; a
+ * disjunction of up to HNSW_RANGES_MAX ranges per query (an IN-list) is hnsw_search_batch_filtered_ranges, below.
  * Not provided: a range combined with a mask that is not in a set, several label columns or labels that are not
- * integers, disjunctions, the Rust shim's binding, filtered sharded search. */
+ * integers, a range list combined with a mask row, range lists over shards, the Rust shim's binding, filtered sharded
+ * search. */
 /* labels[k] for ids[k]; ids == NULL: ids 0..k-1.  An id >= hnsw_len is HNSW_ERR_ARG and nothing changes.  Needs no GPU. */
 int hnsw_set_labels(hnsw_index *h, const uint32_t *ids, const uint32_t *labels, uint64_t k);
 /* out[k]: the labels of ids[k] (NULL: of ids 0..k-1); an id >= hnsw_len is HNSW_ERR_ARG */
@@ -397,6 +400,61 @@ int hnsw_search_batch_filtered_set_range_device_finish(hnsw_index *h, const floa
                                                        const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
                                                        float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
                                                        void *stream, uint8_t *paths /* host, nq, or NULL */);
+
+/* ---- label-SET filtered search: several label ranges per query ---------------------------------------------------
+ * The disjunction over the label column -- `category IN (3, 7, 12)`, `tenant IN {a, b}`, "the last hour OR pinned" --
+ * without a union mask built on the host, uploaded or stored.  Every query has n_ranges = K
+ * closed ranges, fixed stride and row-major: query i is under [lo[i K + j], hi[i K + j]], j < K, and an id is allowed
+ * iff its label lies in AT LEAST ONE of them.  A member with lo > hi is empty and is the padding: a ragged batch pads
+ * its short lists with (1, 0).  Members may overlap, repeat, touch and come in any order; all members empty gives count
+ * 0 with status HNSW_OK.  Query i's ids, distance bits, count, stats (status included) and path are exactly what
+ * hnsw_search_batch_filtered returns for that query alone, on the same handle with the same options, under the mask
+ *   { id < hnsw_len : label(id) in the union of query i's ranges }
+ * and everything else is as in hnsw_search_batch_filtered_range: n <= 64, ef' = max(ef, n, 1), deleted ids taken out,
+ * the cosine option, per-query errors, path 2 on an overflow of the largest visited table, A == 0 giving count 0.  With
+ * n_ranges == 1 the call returns what hnsw_search_batch_filtered_range returns for the same lo / hi, launch for launch.
+ * The host brings every query's list into its canonical form -- empty members dropped, the others sorted, overlapping
+ * and adjacent ones merged ([1, 2], [3, 4] is [1, 4]; nothing is adjacent above UINT32_MAX) -- and the planner runs per
+ * distinct canonical list named in the call: two raw lists with one canonical form are one group, and a list equal to
+ * [0, UINT32_MAX] is no filter.  A is exact, the sum over the list's disjoint members of their slices of the column's
+ * sorted copy; a list takes the exact path (1) iff A <= "filter_exact_max", once, over its queries, so the paths are
+ * those of the equivalent hnsw_search_batch_filtered_multi call.  ef' > 256 is HNSW_ERR_ARG when some list takes the
+ * graph path.  All graph-path queries of all lists share ONE launch of the filtered graph kernel, each wave testing
+ * labels against its own list (the members as the caller gave them: no offsets, nothing canonical travels).
+ * HNSW_ERR_ARG, decided before the device is touched: Q, ids, lo or hi NULL; n_ranges 0 or > HNSW_RANGES_MAX; n > 64;
+ * nq > 2^31 - 1.  nq == 0 is HNSW_OK; n == 0 zeroes counts and launches nothing.  hnsw_get_stat: the three "filtered_*"
+ * path counters advance as for _multi, "filtered_ranges_calls" by one and "filtered_ranges_groups" by the distinct
+ * canonical lists named.
+ * Not provided: a range list combined with a mask row, range lists over shards, the Rust shim's binding. */
+#define HNSW_RANGES_MAX 16
+int hnsw_search_batch_filtered_ranges(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                      uint32_t n_ranges, const uint32_t *lo /* nq x n_ranges */,
+                                      const uint32_t *hi /* nq x n_ranges */, uint32_t *ids, float *dists,
+                                      uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths /* 0/1/2 or NULL */);
+/* The same with every buffer in HBM on the handle's device, d_lo and d_hi too (nq x n_ranges each, both required), after
+ * hnsw_search_batch_filtered_range_device: the column is brought up to date on a stream of the handle's own, then ONE
+ * launch of the filtered graph kernel is enqueued on `stream` and the call returns without synchronising.  There are
+ * no offsets, so the kernel has nothing to validate.  Every query takes the graph path: n <= 64 and ef' <= 256, else
+ * HNSW_ERR_ARG.  d_stats is required; d_dists / d_counts may be NULL.  _finish (same arguments, and paths: host, nq, or
+ * NULL) waits for `stream`, reads the statuses and d_lo / d_hi back, re-runs the queries whose visited table filled up
+ * with larger tables, answers those that fill the largest by the exact path under their own list (path 2) and returns
+ * the first per-query error.  After it the buffers hold what hnsw_search_batch_filtered_ranges returns with
+ * "filter_exact_max" = -1 (paths 0 or 2); the counters advance at _finish. */
+int hnsw_search_batch_filtered_ranges_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                             uint32_t n_ranges, const uint32_t *d_lo, const uint32_t *d_hi,
+                                             uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                                             hnsw_query_stats *d_stats, void *stream);
+int hnsw_search_batch_filtered_ranges_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n,
+                                                    uint32_t ef, uint32_t n_ranges, const uint32_t *d_lo,
+                                                    const uint32_t *d_hi, uint32_t *d_ids, float *d_dists,
+                                                    uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream,
+                                                    uint8_t *paths /* host, nq, or NULL */);
+/* The planner's own count: the undeleted ids below hnsw_len whose label lies in the union of the k <= HNSW_RANGES_MAX
+ * ranges [lo[j], hi[j]] (a member with lo > hi is empty; k == 0 or all members empty gives 0) -- the selectivity a
+ * caller wants before choosing ef.  Needs no GPU: it reads the column's sorted copy.  HNSW_ERR_ARG: h or count NULL,
+ * lo or hi NULL while k > 0, k > HNSW_RANGES_MAX. */
+int hnsw_count_labels_in_ranges(const hnsw_index *h, const uint32_t *lo, const uint32_t *hi, uint32_t k,
+                                uint64_t *count);
 
 /* hnsw_search_batch with every buffer already resident in HBM on the handle's device; enqueues on `stream`
  * (a hipStream_t, NULL = default stream) and returns without synchronising.  d_stats is
@@ -633,7 +691,9 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * to HBM), "filtered_range_calls" (hnsw_search_batch_filtered_range calls and completed _range_device calls),
  * "filtered_range_ranges" (the distinct ranges they named), "filtered_set_range_calls"
  * (hnsw_search_batch_filtered_set_range calls and completed _set_range_device calls), "filtered_set_range_groups" (the
- * distinct (row, lo, hi) triples they named); partitioned search, on the handle passed as shard 0: "shard_calls"
+ * distinct (row, lo, hi) triples they named), "filtered_ranges_calls" (hnsw_search_batch_filtered_ranges calls and
+ * completed _ranges_device calls), "filtered_ranges_groups" (the distinct canonical range lists they named);
+ * partitioned search, on the handle passed as shard 0: "shard_calls"
  * (hnsw_search_batch_shards calls whose shards were all searched), "shard_merges" (the merges they launched); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
