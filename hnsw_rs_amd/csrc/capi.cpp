@@ -340,9 +340,7 @@ int hnsw_search_batch(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, ui
         return HNSW_OK;
     }
     if (h->del.count) {  // ids are deleted: the filtered search over the undeleted ones (include/hnsw_mi355x.h)
-        const hx::PathCounters ctr = hx::del_counters(h);
-        return hx::search_filtered_checked(h, Q, nq, n, ef, hx::MaskSpec{nullptr, index_len(h)}, false, ids, dists, counts,
-                                           stats, nullptr, &ctr);
+        return hx::search_filtered_checked(h, Q, nq, n, ef, hx::Filter{}, false, ids, dists, counts, stats, nullptr);
     }
     hx::DevView dummy{};
     dummy.nb_layers = hnsw_layer_count(h);  // the host index's, or the adopted snapshot's for a replica
@@ -350,40 +348,17 @@ int hnsw_search_batch(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, ui
     return hx::search_host(h, a, Q, nq, ids, dists, counts, stats, nullptr);
 }
 
-int hnsw_search_batch_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
-                               const uint64_t *allow, uint64_t allow_bits, uint32_t *ids, float *dists,
-                               uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
-    int rc = check_search_args(h, ef);
-    if (rc != HNSW_OK) return rc;
-    if (nq == 0) return HNSW_OK;
-    if (!allow && allow_bits != 0) {
-        set_error("filtered search: needs queries, an id buffer, a mask when allow_bits > 0 and n <= %d",
-                  HX_FILT_MAX_N);
-        return HNSW_ERR_ARG;
-    }
-    // (a call without a mask allows nothing: kNoWords stands for its empty mask, nullptr would allow every id)
-    const hx::PathCounters ctr = hx::filt_counters(h);
-    return hx::search_filtered_checked(h, Q, nq, n, ef, hx::MaskSpec{allow ? allow : &kNoWords, allow ? allow_bits : 0},
-                                       false, ids, dists, counts, stats, paths, &ctr);
-}
+// ---- filtered searches -------------------------------------------------------------------------------------------
+// Every entry point states its Filter (search_host.h) and the text of its own missing-argument error, if it has one to
+// report; the two helpers below run the checks in one order -- the handle, the set, an empty call, the entry point's
+// own arguments, the length of a range list -- and make the one call.
+#define HX_STR2(x) #x
+#define HX_STR(x) HX_STR2(x)
+static const char *const kNeedsMask = "filtered search: needs queries, an id buffer, a mask when allow_bits > 0 and n <= " HX_STR(HX_FILT_MAX_N);
+static const char *const kNeedsMaskOf = "filtered search: needs the mask of every query";
+static const char *const kNeedsRange = "filtered search: needs the label range (lo and hi) of every query";
+static const char *const kNeedsRanges = "filtered search: needs the label ranges (lo and hi) of every query";
 
-int hnsw_search_batch_filtered_multi(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
-                                     const uint64_t *masks, uint32_t n_masks, uint64_t allow_bits,
-                                     const uint32_t *mask_of, uint32_t *ids, float *dists, uint32_t *counts,
-                                     hnsw_query_stats *stats, uint8_t *paths) {
-    int rc = check_search_args(h, ef);
-    if (rc != HNSW_OK) return rc;
-    if (nq == 0) return HNSW_OK;
-    if (!mask_of) {
-        set_error("filtered search: needs the mask of every query");
-        return HNSW_ERR_ARG;
-    }
-    const hx::PathCounters ctr = hx::filt_counters(h);
-    return hx::search_filtered_checked(h, Q, nq, n, ef, hx::MaskSpec{masks, allow_bits, n_masks, mask_of}, false, ids,
-                                       dists, counts, stats, paths, &ctr);
-}
-
-// ---- searches under a resident mask set (mask_set.h) --------------------------------------------------------
 static int check_set(const hnsw_index *h, const hnsw_mask_set *set) {
     if (!set || set->owner != h) {
         set_error(set ? "filtered search: the mask set belongs to another handle" : "filtered search: needs a mask set");
@@ -392,153 +367,6 @@ static int check_set(const hnsw_index *h, const hnsw_mask_set *set) {
     return HNSW_OK;
 }
 
-int hnsw_search_batch_filtered_set(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
-                                   hnsw_mask_set *set, const uint32_t *mask_of, uint32_t *ids, float *dists,
-                                   uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
-    int rc = check_search_args(h, ef);
-    if (rc != HNSW_OK || (rc = check_set(h, set))) return rc;
-    if (nq == 0) return HNSW_OK;
-    std::vector<uint32_t> row0;
-    if (!mask_of && nq <= 0x7FFFFFFFull) {  // every query under row 0 (more queries are refused below)
-        row0.assign(nq, 0);
-        mask_of = row0.data();
-    }
-    const hx::PathCounters ctr = hx::filt_counters(h);
-    return hx::search_filtered_checked(h, Q, nq, n, ef,
-                                       hx::MaskSpec{set->words.data(), set->allow_bits, set->n_masks, mask_of, set}, false,
-                                       ids, dists, counts, stats, paths, &ctr);
-}
-
-static int filtered_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, hnsw_mask_set *set,
-                           const uint32_t *d_mask_of, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
-                           hnsw_query_stats *d_stats, void *stream, bool finish, uint8_t *paths) {
-    int rc = check_search_args(h, ef);
-    if (rc != HNSW_OK || (rc = check_set(h, set))) return rc;
-    if (nq == 0 || n == 0) return HNSW_OK;
-    if (!d_Q || !d_ids || !d_stats || nq > 0x7FFFFFFFull) {
-        set_error("filtered device search: needs queries, an id buffer and a stats buffer in HBM");
-        return HNSW_ERR_ARG;
-    }
-    return hx::search_device_filtered(h, hx::DeviceFilter{set, d_mask_of}, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats,
-                                      static_cast<hipStream_t>(stream), finish, paths);
-}
-
-int hnsw_search_batch_filtered_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
-                                      hnsw_mask_set *set, const uint32_t *d_mask_of, uint32_t *d_ids, float *d_dists,
-                                      uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream) {
-    return filtered_device(h, d_Q, nq, n, ef, set, d_mask_of, d_ids, d_dists, d_counts, d_stats, stream, false, nullptr);
-}
-
-int hnsw_search_batch_filtered_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
-                                             hnsw_mask_set *set, const uint32_t *d_mask_of, uint32_t *d_ids,
-                                             float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream,
-                                             uint8_t *paths) {
-    return filtered_device(h, d_Q, nq, n, ef, set, d_mask_of, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
-}
-
-// ---- searches under a label range (labels.h) -----------------------------------------------------------------
-int hnsw_search_batch_filtered_range(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
-                                     const uint32_t *lo, const uint32_t *hi, uint32_t *ids, float *dists,
-                                     uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
-    int rc = check_search_args(h, ef);
-    if (rc != HNSW_OK) return rc;
-    if (nq == 0) return HNSW_OK;
-    if (!lo || !hi) {
-        set_error("filtered search: needs the label range (lo and hi) of every query");
-        return HNSW_ERR_ARG;
-    }
-    hx::MaskSpec m{nullptr, index_len(h)};
-    m.lo = lo;
-    m.hi = hi;
-    const hx::PathCounters ctr = hx::filt_counters(h);
-    return hx::search_filtered_checked(h, Q, nq, n, ef, m, false, ids, dists, counts, stats, paths, &ctr);
-}
-
-static int range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, const uint32_t *d_lo,
-                        const uint32_t *d_hi, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
-                        hnsw_query_stats *d_stats, void *stream, bool finish, uint8_t *paths) {
-    int rc = check_search_args(h, ef);
-    if (rc != HNSW_OK) return rc;
-    if (nq == 0 || n == 0) return HNSW_OK;
-    if (!d_Q || !d_ids || !d_stats || !d_lo || !d_hi || nq > 0x7FFFFFFFull) {
-        set_error("filtered device search: needs queries, their label ranges, an id buffer and a stats buffer in HBM");
-        return HNSW_ERR_ARG;
-    }
-    return hx::search_device_filtered(h, hx::DeviceFilter{nullptr, nullptr, d_lo, d_hi}, d_Q, nq, n, ef, d_ids, d_dists,
-                                      d_counts, d_stats, static_cast<hipStream_t>(stream), finish, paths);
-}
-
-int hnsw_search_batch_filtered_range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
-                                            const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
-                                            float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
-                                            void *stream) {
-    return range_device(h, d_Q, nq, n, ef, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, false, nullptr);
-}
-
-int hnsw_search_batch_filtered_range_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n,
-                                                   uint32_t ef, const uint32_t *d_lo, const uint32_t *d_hi,
-                                                   uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
-                                                   hnsw_query_stats *d_stats, void *stream, uint8_t *paths) {
-    return range_device(h, d_Q, nq, n, ef, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
-}
-
-// ---- searches under a label range AND a row of a resident mask set ------------------------------------------------
-int hnsw_search_batch_filtered_set_range(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
-                                         hnsw_mask_set *set, const uint32_t *mask_of, const uint32_t *lo,
-                                         const uint32_t *hi, uint32_t *ids, float *dists, uint32_t *counts,
-                                         hnsw_query_stats *stats, uint8_t *paths) {
-    int rc = check_search_args(h, ef);
-    if (rc != HNSW_OK || (rc = check_set(h, set))) return rc;
-    if (nq == 0) return HNSW_OK;
-    if (!lo || !hi) {
-        set_error("filtered search: needs the label range (lo and hi) of every query");
-        return HNSW_ERR_ARG;
-    }
-    std::vector<uint32_t> row0;
-    if (!mask_of && nq <= 0x7FFFFFFFull) {  // every query under row 0 (more queries are refused below)
-        row0.assign(nq, 0);
-        mask_of = row0.data();
-    }
-    hx::MaskSpec m{set->words.data(), set->allow_bits, set->n_masks, mask_of, set};
-    m.lo = lo;
-    m.hi = hi;
-    const hx::PathCounters ctr = hx::filt_counters(h);
-    return hx::search_filtered_checked(h, Q, nq, n, ef, m, false, ids, dists, counts, stats, paths, &ctr);
-}
-
-static int set_range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, hnsw_mask_set *set,
-                            const uint32_t *d_mask_of, const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
-                            float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream, bool finish,
-                            uint8_t *paths) {
-    int rc = check_search_args(h, ef);
-    if (rc != HNSW_OK || (rc = check_set(h, set))) return rc;
-    if (nq == 0 || n == 0) return HNSW_OK;
-    if (!d_Q || !d_ids || !d_stats || !d_lo || !d_hi || nq > 0x7FFFFFFFull) {
-        set_error("filtered device search: needs queries, their label ranges, an id buffer and a stats buffer in HBM");
-        return HNSW_ERR_ARG;
-    }
-    return hx::search_device_filtered(h, hx::DeviceFilter{set, d_mask_of, d_lo, d_hi}, d_Q, nq, n, ef, d_ids, d_dists,
-                                      d_counts, d_stats, static_cast<hipStream_t>(stream), finish, paths);
-}
-
-int hnsw_search_batch_filtered_set_range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
-                                                hnsw_mask_set *set, const uint32_t *d_mask_of, const uint32_t *d_lo,
-                                                const uint32_t *d_hi, uint32_t *d_ids, float *d_dists,
-                                                uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream) {
-    return set_range_device(h, d_Q, nq, n, ef, set, d_mask_of, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, false,
-                            nullptr);
-}
-
-int hnsw_search_batch_filtered_set_range_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n,
-                                                       uint32_t ef, hnsw_mask_set *set, const uint32_t *d_mask_of,
-                                                       const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
-                                                       float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
-                                                       void *stream, uint8_t *paths) {
-    return set_range_device(h, d_Q, nq, n, ef, set, d_mask_of, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, true,
-                            paths);
-}
-
-// ---- searches under a list of label ranges per query ---------------------------------------------------------------
 static int check_range_list(uint32_t n_ranges) {
     if (n_ranges == 0 || n_ranges > HNSW_RANGES_MAX) {
         set_error("filtered search: needs 1 to %d label ranges per query, got %u", HNSW_RANGES_MAX, n_ranges);
@@ -547,45 +375,155 @@ static int check_range_list(uint32_t n_ranges) {
     return HNSW_OK;
 }
 
+static hx::Filter make_filter(hx::Filter::Family family, hx::Filter::Rows rows, hnsw_mask_set *set, const uint32_t *mask_of,
+                              uint32_t K = 0, const uint32_t *lo = nullptr, const uint32_t *hi = nullptr) {
+    hx::Filter f;
+    f.family = family, f.rows = rows, f.set = set, f.mask_of = mask_of, f.K = K, f.lo = lo, f.hi = hi;
+    return f;
+}
+
+static int filtered_host(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, hx::Filter f, const char *missing,
+                         uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK || (f.rows == hx::Filter::SET && (rc = check_set(h, f.set)))) return rc;
+    if (nq == 0) return HNSW_OK;
+    if (missing) {
+        set_error("%s", missing);
+        return HNSW_ERR_ARG;
+    }
+    if (f.family == hx::Filter::RANGES && (rc = check_range_list(f.K))) return rc;
+    std::vector<uint32_t> row0;
+    if (f.rows == hx::Filter::SET && !f.mask_of && nq <= 0x7FFFFFFFull) {  // every query under row 0 (more queries are refused below)
+        row0.assign(nq, 0);
+        f.mask_of = row0.data();
+    }
+    return hx::search_filtered_checked(h, Q, nq, n, ef, f, false, ids, dists, counts, stats, paths);
+}
+
+// ... of a device-pointer call: mask_of, lo and hi are the caller's device memory (ranged: the entry point takes ranges)
+static int filtered_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, hx::Filter f, bool ranged,
+                           uint32_t *d_ids, float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream,
+                           bool finish, uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK || (f.rows == hx::Filter::SET && (rc = check_set(h, f.set)))) return rc;
+    if (nq == 0 || n == 0) return HNSW_OK;
+    if (!d_Q || !d_ids || !d_stats || (ranged && (!f.lo || !f.hi)) || nq > 0x7FFFFFFFull) {
+        set_error(ranged ? "filtered device search: needs queries, their label ranges, an id buffer and a stats buffer in HBM"
+                         : "filtered device search: needs queries, an id buffer and a stats buffer in HBM");
+        return HNSW_ERR_ARG;
+    }
+    if (f.family == hx::Filter::RANGES && (rc = check_range_list(f.K))) return rc;
+    f.on_device = true;
+    return hx::search_device_filtered(h, f, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats, static_cast<hipStream_t>(stream),
+                                      finish, paths);
+}
+
+int hnsw_search_batch_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                               const uint64_t *allow, uint64_t allow_bits, uint32_t *ids, float *dists,
+                               uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
+    // (a call without a mask allows nothing: kNoWords stands for its empty mask)
+    hx::Filter f = make_filter(hx::Filter::MASK, hx::Filter::ONE, nullptr, nullptr);
+    f.masks = allow ? allow : &kNoWords;
+    f.allow_bits = allow ? allow_bits : 0;
+    return filtered_host(h, Q, nq, n, ef, f, !allow && allow_bits != 0 ? kNeedsMask : nullptr, ids, dists, counts, stats, paths);
+}
+
+int hnsw_search_batch_filtered_multi(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                     const uint64_t *masks, uint32_t n_masks, uint64_t allow_bits,
+                                     const uint32_t *mask_of, uint32_t *ids, float *dists, uint32_t *counts,
+                                     hnsw_query_stats *stats, uint8_t *paths) {
+    hx::Filter f = make_filter(hx::Filter::MULTI, hx::Filter::MANY, nullptr, mask_of);
+    f.masks = masks, f.allow_bits = allow_bits, f.n_masks = n_masks;
+    return filtered_host(h, Q, nq, n, ef, f, !mask_of ? kNeedsMaskOf : nullptr, ids, dists, counts, stats, paths);
+}
+
+// ---- searches under a resident mask set (mask_set.h) --------------------------------------------------------
+int hnsw_search_batch_filtered_set(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                   hnsw_mask_set *set, const uint32_t *mask_of, uint32_t *ids, float *dists,
+                                   uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
+    return filtered_host(h, Q, nq, n, ef, make_filter(hx::Filter::OF_SET, hx::Filter::SET, set, mask_of), nullptr, ids, dists,
+                         counts, stats, paths);
+}
+
+int hnsw_search_batch_filtered_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                      hnsw_mask_set *set, const uint32_t *d_mask_of, uint32_t *d_ids, float *d_dists,
+                                      uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream) {
+    return filtered_device(h, d_Q, nq, n, ef, make_filter(hx::Filter::OF_SET, hx::Filter::SET, set, d_mask_of), false, d_ids,
+                           d_dists, d_counts, d_stats, stream, false, nullptr);
+}
+
+int hnsw_search_batch_filtered_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                             hnsw_mask_set *set, const uint32_t *d_mask_of, uint32_t *d_ids,
+                                             float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream,
+                                             uint8_t *paths) {
+    return filtered_device(h, d_Q, nq, n, ef, make_filter(hx::Filter::OF_SET, hx::Filter::SET, set, d_mask_of), false, d_ids,
+                           d_dists, d_counts, d_stats, stream, true, paths);
+}
+
+// ---- searches under a label range (labels.h) -----------------------------------------------------------------
+int hnsw_search_batch_filtered_range(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                     const uint32_t *lo, const uint32_t *hi, uint32_t *ids, float *dists,
+                                     uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
+    return filtered_host(h, Q, nq, n, ef, make_filter(hx::Filter::RANGE, hx::Filter::ALL, nullptr, nullptr, 1, lo, hi),
+                         !lo || !hi ? kNeedsRange : nullptr, ids, dists, counts, stats, paths);
+}
+
+int hnsw_search_batch_filtered_range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                            const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
+                                            float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
+                                            void *stream) {
+    return filtered_device(h, d_Q, nq, n, ef, make_filter(hx::Filter::RANGE, hx::Filter::ALL, nullptr, nullptr, 1, d_lo, d_hi),
+                           true, d_ids, d_dists, d_counts, d_stats, stream, false, nullptr);
+}
+
+int hnsw_search_batch_filtered_range_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n,
+                                                   uint32_t ef, const uint32_t *d_lo, const uint32_t *d_hi,
+                                                   uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
+                                                   hnsw_query_stats *d_stats, void *stream, uint8_t *paths) {
+    return filtered_device(h, d_Q, nq, n, ef, make_filter(hx::Filter::RANGE, hx::Filter::ALL, nullptr, nullptr, 1, d_lo, d_hi),
+                           true, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
+}
+
+// ---- searches under a label range AND a row of a resident mask set ------------------------------------------------
+int hnsw_search_batch_filtered_set_range(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                         hnsw_mask_set *set, const uint32_t *mask_of, const uint32_t *lo,
+                                         const uint32_t *hi, uint32_t *ids, float *dists, uint32_t *counts,
+                                         hnsw_query_stats *stats, uint8_t *paths) {
+    return filtered_host(h, Q, nq, n, ef, make_filter(hx::Filter::SET_RANGE, hx::Filter::SET, set, mask_of, 1, lo, hi),
+                         !lo || !hi ? kNeedsRange : nullptr, ids, dists, counts, stats, paths);
+}
+
+int hnsw_search_batch_filtered_set_range_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                                hnsw_mask_set *set, const uint32_t *d_mask_of, const uint32_t *d_lo,
+                                                const uint32_t *d_hi, uint32_t *d_ids, float *d_dists,
+                                                uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream) {
+    return filtered_device(h, d_Q, nq, n, ef, make_filter(hx::Filter::SET_RANGE, hx::Filter::SET, set, d_mask_of, 1, d_lo, d_hi),
+                           true, d_ids, d_dists, d_counts, d_stats, stream, false, nullptr);
+}
+
+int hnsw_search_batch_filtered_set_range_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n,
+                                                       uint32_t ef, hnsw_mask_set *set, const uint32_t *d_mask_of,
+                                                       const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids,
+                                                       float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
+                                                       void *stream, uint8_t *paths) {
+    return filtered_device(h, d_Q, nq, n, ef, make_filter(hx::Filter::SET_RANGE, hx::Filter::SET, set, d_mask_of, 1, d_lo, d_hi),
+                           true, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
+}
+
+// ---- searches under a list of label ranges per query ---------------------------------------------------------------
 int hnsw_search_batch_filtered_ranges(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
                                       uint32_t n_ranges, const uint32_t *lo, const uint32_t *hi, uint32_t *ids,
                                       float *dists, uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
-    int rc = check_search_args(h, ef);
-    if (rc != HNSW_OK) return rc;
-    if (nq == 0) return HNSW_OK;
-    if (!lo || !hi) {
-        set_error("filtered search: needs the label ranges (lo and hi) of every query");
-        return HNSW_ERR_ARG;
-    }
-    if ((rc = check_range_list(n_ranges))) return rc;
-    hx::MaskSpec m{nullptr, index_len(h)};
-    m.lo = lo;
-    m.hi = hi;
-    m.n_ranges = n_ranges;
-    const hx::PathCounters ctr = hx::filt_counters(h);
-    return hx::search_filtered_checked(h, Q, nq, n, ef, m, false, ids, dists, counts, stats, paths, &ctr);
-}
-
-static int ranges_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t n_ranges,
-                         const uint32_t *d_lo, const uint32_t *d_hi, uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
-                         hnsw_query_stats *d_stats, void *stream, bool finish, uint8_t *paths) {
-    int rc = check_search_args(h, ef);
-    if (rc != HNSW_OK) return rc;
-    if (nq == 0 || n == 0) return HNSW_OK;
-    if (!d_Q || !d_ids || !d_stats || !d_lo || !d_hi || nq > 0x7FFFFFFFull) {
-        set_error("filtered device search: needs queries, their label ranges, an id buffer and a stats buffer in HBM");
-        return HNSW_ERR_ARG;
-    }
-    if ((rc = check_range_list(n_ranges))) return rc;
-    return hx::search_device_filtered(h, hx::DeviceFilter{nullptr, nullptr, d_lo, d_hi, n_ranges}, d_Q, nq, n, ef, d_ids,
-                                      d_dists, d_counts, d_stats, static_cast<hipStream_t>(stream), finish, paths);
+    return filtered_host(h, Q, nq, n, ef, make_filter(hx::Filter::RANGES, hx::Filter::ALL, nullptr, nullptr, n_ranges, lo, hi),
+                         !lo || !hi ? kNeedsRanges : nullptr, ids, dists, counts, stats, paths);
 }
 
 int hnsw_search_batch_filtered_ranges_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
                                              uint32_t n_ranges, const uint32_t *d_lo, const uint32_t *d_hi,
                                              uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
                                              hnsw_query_stats *d_stats, void *stream) {
-    return ranges_device(h, d_Q, nq, n, ef, n_ranges, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, false, nullptr);
+    return filtered_device(h, d_Q, nq, n, ef, make_filter(hx::Filter::RANGES, hx::Filter::ALL, nullptr, nullptr, n_ranges, d_lo, d_hi),
+                           true, d_ids, d_dists, d_counts, d_stats, stream, false, nullptr);
 }
 
 int hnsw_search_batch_filtered_ranges_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n,
@@ -593,7 +531,8 @@ int hnsw_search_batch_filtered_ranges_device_finish(hnsw_index *h, const float *
                                                     const uint32_t *d_hi, uint32_t *d_ids, float *d_dists,
                                                     uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream,
                                                     uint8_t *paths) {
-    return ranges_device(h, d_Q, nq, n, ef, n_ranges, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
+    return filtered_device(h, d_Q, nq, n, ef, make_filter(hx::Filter::RANGES, hx::Filter::ALL, nullptr, nullptr, n_ranges, d_lo, d_hi),
+                           true, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
 }
 
 int hnsw_count_labels_in_ranges(const hnsw_index *h, const uint32_t *lo, const uint32_t *hi, uint32_t k,
@@ -620,7 +559,7 @@ int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint3
     if (nq == 0 || n == 0) return HNSW_OK;
     if (!d_Q || !d_ids || !d_stats || nq > 0x7FFFFFFFull) return HNSW_ERR_ARG;
     if (h->del.count)
-        return hx::search_device_filtered(h, hx::DeviceFilter{}, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats,
+        return hx::search_device_filtered(h, hx::Filter{}, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats,
                                           static_cast<hipStream_t>(stream), false, nullptr);
     rc = ensure_uploaded(h);
     if (rc != HNSW_OK) return rc;
@@ -643,7 +582,7 @@ int hnsw_search_batch_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq
     if (!d_Q || !d_ids || !d_stats || nq > 0x7FFFFFFFull) return HNSW_ERR_ARG;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     if (h->del.count)
-        return hx::search_device_filtered(h, hx::DeviceFilter{}, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats, stream, true, nullptr);
+        return hx::search_device_filtered(h, hx::Filter{}, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats, stream, true, nullptr);
     return hx::search_device_finish(h, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats, stream);
 }
 
@@ -736,8 +675,9 @@ int hnsw_brute_force(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uin
     if (h->del.count) {
         // the top k of the undeleted ids: the filtered search's exact path, in the same arithmetic and (dist, id) order
         std::vector<hnsw_query_stats> st(nq);
-        rc = hx::search_filtered(h, Q, nq, k, k, hx::MaskSpec{nullptr, index_len(h)}, true, ids, dists, nullptr, st.data(),
-                                 nullptr, nullptr);
+        hx::Filter scan;
+        scan.family = hx::Filter::SCAN;
+        rc = hx::search_filtered(h, Q, nq, k, k, scan, true, ids, dists, nullptr, st.data(), nullptr);
         if (rc != HNSW_OK) return rc;
         for (uint64_t i = 0; i < nq; i++)
             if (st[i].status != HNSW_OK) {

@@ -216,9 +216,8 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
     if (rc == HNSW_OK && h->del.count) {
         // ids are deleted: the batch is answered as hnsw_search_batch answers it then, into the same result block
         unsigned char *pin = static_cast<unsigned char *>(b->s.pin);
-        const PathCounters ctr = del_counters(h);
-        rc = search_filtered(h, reinterpret_cast<const float *>(pin + p.p_q), nq, n, ef, MaskSpec{nullptr, index_len(h)}, false,
-                             nullptr, nullptr, nullptr, nullptr, nullptr, &ctr, pin + p.p_out);
+        rc = search_filtered(h, reinterpret_cast<const float *>(pin + p.p_q), nq, n, ef, Filter{}, false, nullptr, nullptr,
+                             nullptr, nullptr, nullptr, pin + p.p_out);
     } else if (rc == HNSW_OK) {
         rc = search_staged(h, b->s, p, a, nq, nullptr, nullptr);
     }

@@ -81,13 +81,6 @@ int check_search_args(const hnsw_index *h, uint32_t ef);
 // the HBM snapshot is what the host index holds (uploaded if not) and its device is the calling thread's
 int ensure_uploaded(hnsw_index *h);
 
-// queries per path (0 graph, 1 exact, 2 exact after an overflow): the filtered_* or the deleted_* counters
-struct PathCounters {
-    std::atomic<uint64_t> *graph, *exact, *overflow;
-};
-inline PathCounters filt_counters(hnsw_index *h) { return {&h->n_filt_graph, &h->n_filt_exact, &h->n_filt_overflow}; }
-inline PathCounters del_counters(hnsw_index *h) { return {&h->n_del_graph, &h->n_del_exact, &h->n_del_overflow}; }
-
 struct ScratchLease {  // takes a scratch from the handle's pool, gives it back at scope exit
     hnsw_index *h;
     std::unique_ptr<SearchScratch> s;
@@ -115,23 +108,32 @@ inline int cosine_queries(const hnsw_index *h, void *d_Q, uint64_t nq, hipStream
     return launch_normalise_rows(static_cast<float *>(d_Q), nq, h->dev.view.dim, stream);
 }
 
+// a stream-ordered temporary in HBM, freed in stream order at scope exit
+struct StreamTmp {
+    void *p = nullptr;
+    hipStream_t st = nullptr;
+    int alloc(size_t bytes, hipStream_t stream) {
+        st = stream;
+        HIP_TRY(hipMallocAsync(&p, bytes, stream));
+        return HNSW_OK;
+    }
+    ~StreamTmp() {
+        if (p) (void)hipFreeAsync(p, st);
+    }
+};
+
 // ... and for queries the caller keeps in HBM (const to us): a stream-ordered unit-length copy
 struct DeviceQueries {
     const float *q = nullptr;
-    void *tmp = nullptr;
-    hipStream_t st = nullptr;
+    StreamTmp tmp;
     int prepare(const hnsw_index *h, const float *d_Q, uint64_t nq, hipStream_t stream) {
         q = d_Q;
-        st = stream;
         if (!h->cosine) return HNSW_OK;
         const size_t bytes = (size_t)nq * h->dev.view.dim * 4;
-        HIP_TRY(hipMallocAsync(&tmp, bytes, stream));
-        HIP_TRY(hipMemcpyAsync(tmp, d_Q, bytes, hipMemcpyDeviceToDevice, stream));
-        q = static_cast<const float *>(tmp);
-        return launch_normalise_rows(static_cast<float *>(tmp), nq, h->dev.view.dim, stream);
-    }
-    ~DeviceQueries() {
-        if (tmp) (void)hipFreeAsync(tmp, st);
+        if (int rc = tmp.alloc(bytes, stream)) return rc;
+        HIP_TRY(hipMemcpyAsync(tmp.p, d_Q, bytes, hipMemcpyDeviceToDevice, stream));
+        q = static_cast<const float *>(tmp.p);
+        return launch_normalise_rows(static_cast<float *>(tmp.p), nq, h->dev.view.dim, stream);
     }
 };
 

@@ -287,17 +287,17 @@ int filtered_exact(const DevView &v, const FilterArgs &a, uint64_t nsel, const u
 }
 
 // ---- the filter of a call --------------------------------------------------------------------------------------
-// A query's filter is named by a key and a range.  The key: 0 in a call with one mask (or with none: the undeleted ids)
-// and in a call with label ranges alone, the row or HNSW_MASK_NONE in a call with rows (the caller's or a resident
-// set's).  The range: (lo << 32) | hi in a call with label ranges (alone, or next to the rows of a set), FULL_RANGE
-// otherwise.  In a call with a LIST of ranges per query (hnsw_search_batch_filtered_ranges) the range is the index of the
-// query's canonical list in the call's table of them (FilterSource::lists): two raw lists with one canonical form are one
-// group.  The queries under one (key, range) are a group: the planner's unit, and that of the exact path's launches.
+// A query's filter is named by a key and a list.  The key: the query's row (or HNSW_MASK_NONE) in a call with a row per
+// query, 0 otherwise.  The list: the index of the query's canonical range list in the call's table of them
+// (FilterSource::intern), NO_LIST in a call without label ranges: two raw lists with one canonical form are one list.
+// The queries under one (key, list) are a group: the planner's unit, and that of the exact path's launches.
 constexpr uint64_t UNCOUNTED = ~0ull;
 constexpr uint64_t FULL_RANGE = 0xFFFFFFFFull;  // [0, UINT32_MAX]
+constexpr uint32_t NO_LIST = ~0u;
 constexpr size_t NO_WB = ~(size_t)0;
 struct Group {
-    uint64_t key = 0, range = FULL_RANGE;
+    uint64_t key = 0;
+    uint32_t list = NO_LIST;
     size_t q0 = 0, nq = 0;             // its queries: [q0, q0 + nq) of the sorted list it was cut from
     uint64_t A = UNCOUNTED;            // admissible ids (a row AND a range planned on the graph path: not counted, at most A_ub)
     uint64_t A_ub = 0;
@@ -306,68 +306,85 @@ struct Group {
     const uint32_t *d_list = nullptr;  // a set row's cached list of admissible ids in HBM, when it is valid
 };
 
-// What turns a key into what the exact path needs, one per call: the masks, set or label column behind the keys, the
-// key of every query (host memory) and the call's own arguments.
+// What turns a group into what the exact path needs, one per call, made from the call's Filter: the rows and the label
+// column behind the groups, the key and the ranges of every query (host memory) and the call's own arguments.  Beyond
+// the constructor nothing asks what kind of call it is, only whether a group has words and whether it has a range list.
 struct FilterSource {
-    enum Kind { ONE, ROWS, SET, RANGE, SET_RANGE, RANGES } kind;
     hnsw_index *h;
-    const uint64_t *masks;  // ONE, ROWS: the caller's words (nullptr: every id below bits)
-    hnsw_mask_set *set;     // SET
+    const Filter::Family family;
+    hnsw_mask_set *set;             // Filter::SET
+    const uint64_t *masks;          // the caller's words (Filter::ONE, MANY; nullptr: none)
+    bool rowed;                     // a row per query (MANY, SET), else key 0
+    uint32_t K, n_masks;            // ranges per query; rows
     uint64_t len, bits, row_words;  // the index length, min(allow_bits, len), words of a row
-    const uint32_t *mask_of = nullptr, *lo = nullptr, *hi = nullptr;  // per query: ROWS, SET and SET_RANGE (nullptr: row 0); RANGE and SET_RANGE
-    FilterArgs base{};      // every mask or range: the graph kernel's wave picks its query's
-    // RANGES: query i is under the K members lo / hi [i K, i K + K); its canonical list (LabelColumn::canonical: disjoint,
-    // ascending, no empty member) is lists[list_of[i]].  The table is interned in ascending order of the lists, so the
-    // groups of a K == 1 call come in the order a RANGE call's do.  A list without members is the one empty range (1, 0);
-    // with K == 1 the member is the caller's pair as it is, and every launch is that of the RANGE call
-    uint32_t K = 1;
-    std::vector<uint32_t> list_of;
-    std::vector<std::vector<uint64_t>> lists;
+    // per query, in host memory: a device-pointer call has them only once its _finish has fetched them
+    const uint32_t *mask_of = nullptr, *lo = nullptr, *hi = nullptr;
+    FilterArgs base{};  // every row and range: the graph kernel's wave picks its query's
+    // The call's canonical lists (LabelColumn::canonical: disjoint, ascending, no empty member; a list without members
+    // is the one empty range (1, 0)), ascending, list j's members at members[start[j] .. start[j + 1]); query i is under
+    // list_of[i].  With K == 1 the member is the caller's pair as it is, lo > hi included
+    std::vector<uint32_t> list_of, start;
+    std::vector<uint64_t> members;
+    bool interned() const { return !start.empty(); }
+    size_t n_lists() const { return start.size() - 1; }
+    uint64_t raw(uint64_t i) const { return ((uint64_t)lo[i] << 32) | hi[i]; }
     void intern(uint64_t nq) {
+        list_of.resize(nq);
+        members.clear();
+        start.assign(1, 0);
+        if (K == 1) {  // (no canonical form to make: the distinct pairs, sorted)
+            members.resize(nq);
+            for (uint64_t i = 0; i < nq; i++) members[i] = raw(i);
+            std::sort(members.begin(), members.end());
+            members.erase(std::unique(members.begin(), members.end()), members.end());
+            for (size_t j = 1; j <= members.size(); j++) start.push_back((uint32_t)j);
+            for (uint64_t i = 0; i < nq; i++)
+                list_of[i] = (uint32_t)(std::lower_bound(members.begin(), members.end(), raw(i)) - members.begin());
+            return;
+        }
         std::map<std::vector<uint64_t>, uint32_t> table;
         std::vector<std::map<std::vector<uint64_t>, uint32_t>::iterator> at(nq);
         for (uint64_t i = 0; i < nq; i++) {
-            std::vector<uint64_t> c = K == 1 ? std::vector<uint64_t>{((uint64_t)lo[i] << 32) | hi[i]}
-                                             : LabelColumn::canonical(lo + i * K, hi + i * K, K);
+            std::vector<uint64_t> c = LabelColumn::canonical(lo + i * K, hi + i * K, K);
             if (c.empty()) c.push_back(1ull << 32);
             at[i] = table.emplace(std::move(c), 0u).first;
         }
-        lists.clear();
         for (auto &e : table) {
-            e.second = (uint32_t)lists.size();
-            lists.push_back(e.first);
+            e.second = (uint32_t)n_lists();
+            members.insert(members.end(), e.first.begin(), e.first.end());
+            start.push_back((uint32_t)members.size());
         }
-        list_of.resize(nq);
         for (uint64_t i = 0; i < nq; i++) list_of[i] = at[i]->second;
     }
 
-    FilterSource(hnsw_index *h_, Kind k, const uint64_t *masks_, hnsw_mask_set *set_, uint64_t allow_bits)
-        : kind(k), h(h_), masks(masks_), set(set_), len(index_len(h_)), bits(std::min<uint64_t>(allow_bits, len)),
-          row_words((allow_bits + 63) / 64) {}
+    FilterSource(hnsw_index *h_, const Filter &f)
+        : h(h_), family(f.family), set(f.rows == Filter::SET ? f.set : nullptr),
+          masks(f.rows == Filter::ONE || f.rows == Filter::MANY ? f.masks : nullptr),
+          rowed(f.rows == Filter::MANY || f.rows == Filter::SET), K(f.K), n_masks(set ? set->n_masks : f.n_masks),
+          len(index_len(h_)) {
+        const uint64_t allow_bits = set ? set->allow_bits : f.rows == Filter::ALL ? len : f.allow_bits;
+        bits = std::min<uint64_t>(allow_bits, len);
+        row_words = (allow_bits + 63) / 64;
+        if (!f.on_device) mask_of = f.mask_of, lo = f.lo, hi = f.hi;
+    }
 
-    bool of_set() const { return kind == SET || kind == SET_RANGE; }
-    bool labelled() const { return kind == RANGE || kind == SET_RANGE || kind == RANGES; }
-    uint64_t key(uint32_t i) const { return kind != RANGE && kind != RANGES && mask_of ? mask_of[i] : 0; }
-    uint64_t range(uint32_t i) const {
-        if (kind == RANGES) return list_of[i];
-        return labelled() ? ((uint64_t)lo[i] << 32) | hi[i] : FULL_RANGE;
-    }
+    uint64_t key(uint32_t i) const { return rowed && mask_of ? mask_of[i] : 0; }
+    uint32_t list(uint32_t i) const { return K ? list_of[i] : NO_LIST; }
+    const uint64_t *members_of(const Group &g) const { return members.data() + start[g.list]; }
+    size_t n_members(const Group &g) const { return start[g.list + 1] - start[g.list]; }
     // the key names a row with words (masks may be NULL when allow_bits is 0: nothing is allowed, no word is read)
-    bool has_words(uint64_t key) const {
-        if (kind == ONE) return masks != nullptr;
-        return key != HNSW_MASK_NONE && (kind == ROWS ? masks != nullptr : of_set() && set->W != 0);
-    }
-    // the group is under a label range.  Next to a set, [0, UINT32_MAX] is no range: the group is the plain row, with the
+    bool has_words(uint64_t key) const { return key != HNSW_MASK_NONE && (set ? set->W != 0 : masks != nullptr); }
+    // the group is under its range list.  Next to a set, [0, UINT32_MAX] is no range: the group is the plain row, with the
     // set's caches (and so is a row of a set without words: nothing is allowed); under HNSW_MASK_NONE it is the plain range
     bool ranged(const Group &g) const {
-        return kind == RANGE || kind == RANGES || (kind == SET_RANGE && g.range != FULL_RANGE && (g.key == HNSW_MASK_NONE || set->W != 0));
+        return K && (!set || (members_of(g)[0] != FULL_RANGE && (g.key == HNSW_MASK_NONE || set->W != 0)));
     }
-    // its id bound (a range call's bits are the index length)
+    // its id bound (without rows of its own a call's bits are the index length)
     uint64_t bound(uint64_t key) const { return key == HNSW_MASK_NONE ? len : bits; }
 
     // base, but for the outputs and the selection; d_*: what the kernels read, on the device
     void bind(const float *d_Q, const uint64_t *d_allow, const uint32_t *d_mask_of, const uint32_t *d_lo,
-              const uint32_t *d_hi, uint32_t n_masks, uint32_t n, uint32_t efp) {
+              const uint32_t *d_hi, uint32_t n, uint32_t efp) {
         base.Q = d_Q;
         base.allow = d_allow;
         base.allow_bits = bits;
@@ -377,53 +394,46 @@ struct FilterSource {
         base.n_masks = n_masks;  // the kernel checks mask_of against it (the host may not have seen those words)
         base.deny = h->del.count ? h->del.d_words : nullptr;
         base.deny_bits = h->del.count ? h->del.deny_bits() : 0;
-        if (labelled()) bind_labels(h, base);
+        if (K) bind_labels(h, base);
         base.range_lo = d_lo;
         base.range_hi = d_hi;
-        base.n_ranges = kind == RANGES ? K : 0;
+        base.n_ranges = K;  // (the kernels read it above 1 only)
         base.n = n;
         base.ef = efp;
     }
-    // the arguments of an exact-path launch: the group's mask, its range, or both, alone
+    // the arguments of an exact-path launch: the group's row, its ranges, or both, alone
     FilterArgs args(const Group &g) const {
         FilterArgs ax = base;
-        const bool rg = ranged(g);
+        const uint64_t m0 = ranged(g) ? members_of(g)[0] : 0;  // (the first member; one member: the launch's whole range)
         ax.mask_of = nullptr;
         ax.allow = has_words(g.key) ? base.allow + g.key * row_words : nullptr;
         ax.allow_bits = bound(g.key);
-        ax.range_lo = ax.range_hi = nullptr;  // (the group's range as scalars)
-        if (!rg) ax.labels = nullptr;         // (a plain row next to ranged groups: the compaction reads its words alone)
-        ax.lo = rg ? (uint32_t)(g.range >> 32) : 0;
-        ax.hi = rg ? (uint32_t)g.range : 0;
+        ax.range_lo = ax.range_hi = nullptr;      // (the group's range as scalars)
+        if (!ranged(g)) ax.labels = nullptr;      // (a plain row next to ranged groups: the compaction reads its words alone)
+        ax.lo = (uint32_t)(m0 >> 32), ax.hi = (uint32_t)m0;
         ax.n_ranges = 0;
-        if (kind == RANGES) {  // (the first member of the group's list; one member: the launch of a RANGE group)
-            const uint64_t m0 = lists[(size_t)g.range][0];
-            ax.lo = (uint32_t)(m0 >> 32), ax.hi = (uint32_t)m0;
-        }
         return ax;
     }
     // ... and its canonical list, by value, for the compaction (n == 0: the group is under args' lo / hi alone)
-    RangeList list(const Group &g) const {
+    RangeList range_list(const Group &g) const {
         RangeList r{};
-        if (kind != RANGES || lists[(size_t)g.range].size() < 2) return r;
-        const std::vector<uint64_t> &l = lists[(size_t)g.range];
-        r.n = (uint32_t)l.size();
-        for (size_t j = 0; j < l.size(); j++) r.lo[j] = (uint32_t)(l[j] >> 32), r.hi[j] = (uint32_t)l[j];
+        if (!ranged(g) || n_members(g) < 2) return r;
+        r.n = (uint32_t)n_members(g);
+        for (uint32_t j = 0; j < r.n; j++) r.lo[j] = (uint32_t)(members_of(g)[j] >> 32), r.hi[j] = (uint32_t)members_of(g)[j];
         return r;
     }
 
     // What `resolve` reads is locked by this: a set's caches (a row is counted when it, the deleted set or the length
-    // changed), and the label column's sorted copy (made under the lock when the column, the deleted set or the length
-    // changed: here, or next to a set by the first group that has a range).  The set's first, then the column's
+    // changed), and the label column's sorted copy (made under the lock, by the first group that has a range, when the
+    // column, the deleted set or the length changed).  The set's first, then the column's
     struct Locks {
         std::unique_lock<std::mutex> set, lab;
         bool held() const { return set.owns_lock() || lab.owns_lock(); }
     };
     Locks lock() const {
         Locks l;
-        if (of_set()) l.set = std::unique_lock<std::mutex>(set->mu);
-        if (labelled()) l.lab = std::unique_lock<std::mutex>(h->lab.mu);
-        if (kind == RANGE || kind == RANGES) h->lab.sort_for(h->del, len);
+        if (set) l.set = std::unique_lock<std::mutex>(set->mu);
+        if (K) l.lab = std::unique_lock<std::mutex>(h->lab.mu);
         return l;
     }
     // The admissible ids of a row AND a range: the undeleted ids below `bits` whose bit is set in the row and whose
@@ -467,69 +477,72 @@ struct FilterSource {
         return A;
     }
     // Counts a group: A (kept when it is known already), exact = A <= exact_max, a set row's list while it is valid, and
-    // its word offsets, appended to wbs.  A range's admissible ids are a slice of the sorted copy, found by two binary
-    // searches; its offsets cost a pass over the slice and are counted only when it is exact.  A list of ranges is
-    // disjoint: A is the sum over its members' slices, its offsets accumulate over them.  A row AND a range are
-    // counted by count_both, up to exact_max
+    // its word offsets, appended to wbs.  The admissible ids of a range list are its disjoint members' slices of the
+    // sorted copy, each found by two binary searches: A is their sum; the offsets cost a pass over the slices and are
+    // counted only when the group is exact.  A row AND a range are counted by count_both, up to exact_max
     void resolve(Group &g, int64_t exact_max, std::vector<uint32_t> &wbs) const {
         std::vector<uint32_t> own;
         const std::vector<uint32_t> *wb = &own;
-        const bool rg = ranged(g), both = rg && has_words(g.key);
-        const uint32_t lo = (uint32_t)(g.range >> 32), hi = (uint32_t)g.range;
-        uint64_t A, first = 0;
-        std::vector<std::pair<uint64_t, uint64_t>> slices;  // RANGES: (first, count) of every member
-        if (rg && kind == SET_RANGE) h->lab.sort_for(h->del, len);
-        if (both) {
-            A = lo > hi ? 0 : count_both((uint32_t)g.key, lo, hi, exact_max, own, g.A_ub);
+        const bool rg = ranged(g), words = has_words(g.key);
+        uint64_t A = 0;
+        std::vector<std::pair<uint64_t, uint64_t>> slices;  // (first, count) of every member
+        if (rg) h->lab.sort_for(h->del, len);
+        if (rg && words) {
+            const uint32_t lo1 = (uint32_t)(members_of(g)[0] >> 32), hi1 = (uint32_t)members_of(g)[0];
+            A = lo1 > hi1 ? 0 : count_both((uint32_t)g.key, lo1, hi1, exact_max, own, g.A_ub);
             if (A == UNCOUNTED) {
                 g.exact = false;
                 return;
             }
-        } else if (kind == RANGES) {
-            A = 0;
-            for (uint64_t m : lists[(size_t)g.range]) {
-                const uint64_t c = h->lab.count((uint32_t)(m >> 32), (uint32_t)m, &first);
+        } else if (rg) {
+            for (size_t j = 0; j < n_members(g); j++) {
+                uint64_t first = 0;
+                const uint64_t c = h->lab.count((uint32_t)(members_of(g)[j] >> 32), (uint32_t)members_of(g)[j], &first);
                 slices.emplace_back(first, c);
                 A += c;
             }
-        } else if (rg) {
-            A = h->lab.count(lo, hi, &first);
-        } else if (of_set() && has_words(g.key)) {
+        } else if (set && words) {
             const hnsw_mask_set::Row &r = set->counted(h, (uint32_t)g.key);
             A = r.A;
             wb = &r.wbase;
             g.d_list = r.list_valid ? r.d_ids : nullptr;
         } else {
-            A = count_admissible(h, has_words(g.key) ? masks + g.key * row_words : nullptr, bound(g.key), own);
+            A = count_admissible(h, words ? masks + g.key * row_words : nullptr, bound(g.key), own);
         }
         if (g.A == UNCOUNTED) g.A = A;
         g.exact = (int64_t)g.A <= exact_max;
         if (rg && !g.exact) return;
-        if (kind == RANGES)
-            h->lab.word_base(slices, len, own);
-        else if (rg && !both)
-            h->lab.word_base(first, g.A, len, own);
+        if (rg && !words) h->lab.word_base(slices, len, own);
         g.wb = wbs.size();
         g.n_wb = wb->size();
         wbs.insert(wbs.end(), wb->begin(), wb->end());
     }
+    // the distinct groups of the call's nq queries, for its counters (a device-pointer call's, which cuts no groups)
+    uint64_t n_groups(uint64_t nq) const {
+        if (!(rowed && mask_of)) return n_lists();
+        std::vector<std::pair<uint64_t, uint64_t>> named(nq);  // (a row per query: K == 1, the pair is the list)
+        for (uint64_t i = 0; i < nq; i++) named[i] = {mask_of[i], raw(i)};
+        std::sort(named.begin(), named.end());
+        return (uint64_t)(std::unique(named.begin(), named.end()) - named.begin());
+    }
 };
 
-// stable-sorts query indices by (key, range) and cuts them into runs: ascending key (HNSW_MASK_NONE last among rows),
-// ascending range within a key, the caller's order within a run
-bool group_before(const Group &g, uint64_t key, uint64_t range) { return g.key != key ? g.key < key : g.range < range; }
+// stable-sorts query indices by (key, list) and cuts them into runs: ascending key (HNSW_MASK_NONE last among rows),
+// ascending list within a key, the caller's order within a run
+bool group_before(const Group &g, uint64_t key, uint32_t list) { return g.key != key ? g.key < key : g.list < list; }
 std::vector<Group> group_by_key(std::vector<uint32_t> &idx, const FilterSource &src) {
     std::stable_sort(idx.begin(), idx.end(), [&](uint32_t i, uint32_t j) {
         const uint64_t ki = src.key(i), kj = src.key(j);
-        return ki != kj ? ki < kj : src.range(i) < src.range(j);
+        return ki != kj ? ki < kj : src.list(i) < src.list(j);
     });
     std::vector<Group> runs;
     for (size_t k = 0; k < idx.size(); k++) {
-        const uint64_t key = src.key(idx[k]), range = src.range(idx[k]);
-        if (k == 0 || key != runs.back().key || range != runs.back().range) {
+        const uint64_t key = src.key(idx[k]);
+        const uint32_t list = src.list(idx[k]);
+        if (k == 0 || key != runs.back().key || list != runs.back().list) {
             runs.emplace_back();
             runs.back().key = key;
-            runs.back().range = range;
+            runs.back().list = list;
             runs.back().q0 = k;
         }
         runs.back().nq++;
@@ -553,9 +566,9 @@ struct ExactPlace {
 int exact_group(const FilterSource &src, const Group &g, const uint32_t *d_sel, uint64_t shape_nsel, const ExactPlace &at) {
     if (!g.d_list && at.send) {  // compacted in the scratch: a row beyond the set's budget, or no row of the set
         HIP_TRY(hipMemcpyAsync(at.d_wb + g.wb, at.wbs + g.wb, g.n_wb * 4, hipMemcpyHostToDevice, at.stream));
-        if (src.of_set() && src.has_words(g.key) && !src.ranged(g)) src.h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
+        if (src.set && src.has_words(g.key) && !src.ranged(g)) src.h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
     }
-    const RangeList ranges = src.list(g);
+    const RangeList ranges = src.range_list(g);
     return filtered_exact(src.h->dev.view, src.args(g), g.nq, d_sel, g.A, at.d_wb + g.wb, shape_nsel, at.x, at.dv, at.stream,
                           g.d_list, &ranges);
 }
@@ -582,7 +595,7 @@ int path2(const FilterSource &src, const std::vector<uint32_t> &sel, std::vector
         Group &g = runs[k];
         if (planned) {
             const Group &p = *std::lower_bound(planned->begin(), planned->end(), g,
-                                               [](const Group &x, const Group &y) { return group_before(x, y.key, y.range); });
+                                               [](const Group &x, const Group &y) { return group_before(x, y.key, y.list); });
             g.A = p.A, g.wb = p.wb, g.n_wb = p.n_wb, g.d_list = p.d_list;
         }
         if (g.wb == NO_WB) {
@@ -620,30 +633,60 @@ int path2(const FilterSource &src, const std::vector<uint32_t> &sel, std::vector
     return fetch(unused);  // (synchronises: `sel2` and `wb_late` live until then)
 }
 
+// The counters of a call that ended well, by the entry points that made it: its queries per path under filtered_* or
+// deleted_*, the call itself, and its groups
+void count_call(hnsw_index *h, Filter::Family family, uint64_t n_graph, uint64_t n_exact, uint64_t n_overflow, uint64_t n_groups) {
+    if (family == Filter::SCAN) return;  // (hnsw_brute_force counts nothing)
+    const bool del = family == Filter::DELETED;
+    (del ? h->n_del_graph : h->n_filt_graph).fetch_add(n_graph, std::memory_order_relaxed);
+    (del ? h->n_del_exact : h->n_filt_exact).fetch_add(n_exact, std::memory_order_relaxed);
+    (del ? h->n_del_overflow : h->n_filt_overflow).fetch_add(n_overflow, std::memory_order_relaxed);
+    std::atomic<uint64_t> *calls = nullptr, *groups = nullptr;
+    switch (family) {
+        case Filter::MULTI: calls = &h->n_filt_multi_calls, groups = &h->n_filt_multi_masks; break;
+        case Filter::OF_SET: calls = &h->n_filt_set_calls; break;
+        case Filter::RANGE: calls = &h->n_filt_range_calls, groups = &h->n_filt_range_ranges; break;
+        case Filter::SET_RANGE: calls = &h->n_filt_set_range_calls, groups = &h->n_filt_set_range_groups; break;
+        case Filter::RANGES: calls = &h->n_filt_ranges_calls, groups = &h->n_filt_ranges_groups; break;
+        default: break;
+    }
+    if (calls) calls->fetch_add(1, std::memory_order_relaxed);
+    if (groups) groups->fetch_add(n_groups, std::memory_order_relaxed);
+}
+
+// the combinations of rows and ranges no entry point offers (search_host.h's table)
+int check_filter(const Filter &f) {
+    if (f.K <= (f.rows == Filter::ALL ? (uint32_t)HX_FILT_MAX_RANGES : f.rows == Filter::SET ? 1u : 0u)) return HNSW_OK;
+    set_error("filtered search: no search under these rows and %u label ranges per query", f.K);
+    return HNSW_ERR_ARG;
+}
+
 }  // namespace
 
-int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const MaskSpec &m,
+int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f,
                     bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
-                    uint8_t *paths, const PathCounters *ctr, void *pin_block) {
+                    uint8_t *paths, void *pin_block) {
     int rc = check_search_args(h, ef);
-    if (rc != HNSW_OK) return rc;
+    if (rc != HNSW_OK || (rc = check_filter(f))) return rc;
     if (nq == 0) return HNSW_OK;
     if (!Q || (!ids && !pin_block) || nq > 0x7FFFFFFFull || n > HX_FILT_MAX_N) {
         set_error("filtered search: needs queries, an id buffer, a mask when allow_bits > 0 and n <= %d",
                   HX_FILT_MAX_N);
         return HNSW_ERR_ARG;
     }
-    if (m.mask_of) {
+    // (the entry points see to lo and hi with K, and to mask_of with rows per query)
+    FilterSource src(h, f);
+    if (src.rowed) {
         bool masked = false;
         for (uint64_t i = 0; i < nq; i++) {
-            if (m.mask_of[i] == HNSW_MASK_NONE) continue;
-            if (m.mask_of[i] >= m.n_masks) {
-                set_error("filtered search: query %llu names mask %u of %u", (unsigned long long)i, m.mask_of[i], m.n_masks);
+            if (src.mask_of[i] == HNSW_MASK_NONE) continue;
+            if (src.mask_of[i] >= src.n_masks) {
+                set_error("filtered search: query %llu names mask %u of %u", (unsigned long long)i, src.mask_of[i], src.n_masks);
                 return HNSW_ERR_ARG;
             }
             masked = true;
         }
-        if (masked && !m.masks && m.allow_bits != 0) {
+        if (masked && !src.set && !src.masks && f.allow_bits != 0) {
             set_error("filtered search: needs the masks its queries name when allow_bits > 0");
             return HNSW_ERR_ARG;
         }
@@ -653,27 +696,12 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         return HNSW_OK;
     }
     const uint32_t efp = std::max(std::max(ef, n), 1u);
-    // (the entry points see to hi with lo, and to mask_of with a set)
-    FilterSource src(h,
-                     m.lo && m.set ? FilterSource::SET_RANGE
-                     : m.n_ranges  ? FilterSource::RANGES
-                     : m.lo        ? FilterSource::RANGE
-                     : m.set       ? FilterSource::SET
-                     : m.mask_of   ? FilterSource::ROWS
-                                   : FilterSource::ONE,
-                     m.masks, m.set, m.allow_bits);
-    src.mask_of = m.mask_of, src.lo = m.lo, src.hi = m.hi;
-    const bool listed = src.kind == FilterSource::RANGES;
-    const uint64_t rk = listed ? m.n_ranges : 1;  // ranges per query
-    if (listed) {
-        src.K = m.n_ranges;
-        src.intern(nq);
-    }
-    hnsw_mask_set *const set = m.set;
-    // ranged: the call has a label column (next to a set: both); rowed: it has a row per query
-    const bool ranged = src.labelled(), both = src.kind == FilterSource::SET_RANGE, multi = src.kind != FilterSource::ONE;
-    const bool rowed = multi && src.kind != FilterSource::RANGE && !listed;
-    const uint64_t len = src.len, bits = src.bits, row_words = src.row_words;
+    if (src.K) src.intern(nq);
+    hnsw_mask_set *const set = src.set;
+    // The two facts the layout, the uploads and the kernels' arguments follow from: the call has a row per query; it has
+    // a label column, with rk ranges per query.  With neither it has one group and no use for an order of its queries
+    const bool rowed = src.rowed, ranged = src.K != 0, multi = rowed || ranged;
+    const uint64_t rk = ranged ? src.K : 1, bits = src.bits;
     // ---- the planner, per group: its admissible ids decide its queries' path.  A set stays locked until its HBM copy
     // is up to date and the lists this call needs are made; the label column only while the ranges are counted ----
     std::vector<uint32_t> order;  // the queries, group by group; a one-mask call has one group and no use for it
@@ -714,18 +742,17 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         return rc;
     const DevView &v = h->dev.view;
     const uint32_t d = v.dim;
-    // device arena: [queries | masks | mask of every query | selection | the exact path's selection | the exact path's
-    // scratch | result block].  All n_masks rows go up in one copy (a one-mask call sends the words below `bits` only).
-    // The result block comes back in one copy to pinned memory: the caller's block, or the scratch's and from there to
-    // the caller's buffers
-    // (a set's rows are in HBM already: nothing goes up, and the arena has no masks; a range call has no masks
-    // either: its "mask of every query" is the two arrays lo and hi -- three arrays next to a set: row, lo, hi -- and its
-    // word offsets have room for one more range, that of a path 2 group, counted when a query gets there)
-    const uint64_t up_words = !m.masks || set ? 0 : multi ? (uint64_t)m.n_masks * row_words : (bits + 63) / 64;
+    // device arena: [queries | masks | row of every query | lo | hi | selection | the exact path's selection | the exact
+    // path's scratch | result block]: the caller's masks when it brought any (all n_masks rows in one copy; a one-mask
+    // call sends the words below `bits` only; a set's rows are in HBM already), the rows with a row per query, lo and hi
+    // with ranges -- and then the word offsets have room for one more group, that of a path 2 group, counted when a
+    // query gets there.  The result block comes back in one copy to pinned memory: the caller's block, or the scratch's
+    // and from there to the caller's buffers
+    const uint64_t up_words = !src.masks ? 0 : rowed ? (uint64_t)src.n_masks * src.row_words : (bits + 63) / 64;
     const size_t o_q = 0, o_mask = o_q + align256(nq * d * 4), o_mof = o_mask + align256(up_words * 8);
     const size_t o_lo = o_mof + (rowed ? align256(nq * 4) : 0), o_hi = o_lo + (ranged ? align256(nq * rk * 4) : 0);
     const size_t o_sel = o_hi + (ranged ? align256(nq * rk * 4) : 0), o_xsel = o_sel + align256(nq * 4);
-    const size_t wb_lazy = ranged ? std::max<uint64_t>(1, ((len + 63) / 64 + 63) / 64) : 0;
+    const size_t wb_lazy = ranged ? std::max<uint64_t>(1, ((src.len + 63) / 64 + 63) / 64) : 0;
     const ExactScratch x(o_xsel + align256(multi ? nq * 4 : 0), nq, n, A_max, wb_all.size() + wb_lazy);
     const size_t o_out = x.end;
     const ResultBlock out(nq, n);
@@ -739,23 +766,21 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
              *d_hi = reinterpret_cast<uint32_t *>(dv + o_hi);
     HIP_TRY(hipMemcpyAsync(dv + o_q, Q, nq * d * 4, hipMemcpyHostToDevice, s.stream));
     if ((rc = cosine_queries(h, dv + o_q, nq, s.stream))) return rc;
-    if (up_words) HIP_TRY(hipMemcpyAsync(dv + o_mask, m.masks, up_words * 8, hipMemcpyHostToDevice, s.stream));
+    if (up_words) HIP_TRY(hipMemcpyAsync(dv + o_mask, src.masks, up_words * 8, hipMemcpyHostToDevice, s.stream));
     // (under a set the word offsets of a group go up only when a compaction of it runs)
     const ExactPlace at{dv, x, s.stream, wb_all.data(), reinterpret_cast<uint32_t *>(dv + x.o_wb), set != nullptr};
     if (!set && (bits || multi) && !wb_all.empty())
         HIP_TRY(hipMemcpyAsync(at.d_wb, wb_all.data(), wb_all.size() * 4, hipMemcpyHostToDevice, s.stream));
-    if (multi) {
-        if (ranged) {
-            HIP_TRY(hipMemcpyAsync(d_lo, m.lo, nq * rk * 4, hipMemcpyHostToDevice, s.stream));
-            HIP_TRY(hipMemcpyAsync(d_hi, m.hi, nq * rk * 4, hipMemcpyHostToDevice, s.stream));
-        }
-        if (rowed) HIP_TRY(hipMemcpyAsync(d_mof, m.mask_of, nq * 4, hipMemcpyHostToDevice, s.stream));
-        if (!gsel.empty()) HIP_TRY(hipMemcpyAsync(d_sel, gsel.data(), gsel.size() * 4, hipMemcpyHostToDevice, s.stream));
-        if (n_exact) HIP_TRY(hipMemcpyAsync(d_xsel, order.data(), nq * 4, hipMemcpyHostToDevice, s.stream));
+    if (ranged) {
+        HIP_TRY(hipMemcpyAsync(d_lo, src.lo, nq * rk * 4, hipMemcpyHostToDevice, s.stream));
+        HIP_TRY(hipMemcpyAsync(d_hi, src.hi, nq * rk * 4, hipMemcpyHostToDevice, s.stream));
     }
+    if (rowed) HIP_TRY(hipMemcpyAsync(d_mof, src.mask_of, nq * 4, hipMemcpyHostToDevice, s.stream));
+    if (!gsel.empty()) HIP_TRY(hipMemcpyAsync(d_sel, gsel.data(), gsel.size() * 4, hipMemcpyHostToDevice, s.stream));
+    if (multi && n_exact) HIP_TRY(hipMemcpyAsync(d_xsel, order.data(), nq * 4, hipMemcpyHostToDevice, s.stream));
     src.bind(reinterpret_cast<const float *>(dv + o_q),
              set ? set->d_rows() : up_words ? reinterpret_cast<const uint64_t *>(dv + o_mask) : nullptr,
-             rowed ? d_mof : nullptr, ranged ? d_lo : nullptr, ranged ? d_hi : nullptr, m.n_masks, n, efp);
+             rowed ? d_mof : nullptr, ranged ? d_lo : nullptr, ranged ? d_hi : nullptr, n, efp);
     FilterArgs &a = src.base;
     a.qsel = gsel.empty() ? nullptr : d_sel;
     out.bind(a, dv + o_out);
@@ -809,61 +834,43 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
             &n2);
         if (rc != HNSW_OK) return rc;
     }
-    if (ctr) {
-        ctr->exact->fetch_add(n_exact, std::memory_order_relaxed);
-        ctr->graph->fetch_add(n_graph - n2, std::memory_order_relaxed);
-        ctr->overflow->fetch_add(n2, std::memory_order_relaxed);
-    }
-    if (both) {
-        h->n_filt_set_range_calls.fetch_add(1, std::memory_order_relaxed);
-        h->n_filt_set_range_groups.fetch_add(groups.size(), std::memory_order_relaxed);
-    } else if (set) {
-        h->n_filt_set_calls.fetch_add(1, std::memory_order_relaxed);
-    } else if (listed) {
-        h->n_filt_ranges_calls.fetch_add(1, std::memory_order_relaxed);
-        h->n_filt_ranges_groups.fetch_add(groups.size(), std::memory_order_relaxed);
-    } else if (ranged) {
-        h->n_filt_range_calls.fetch_add(1, std::memory_order_relaxed);
-        h->n_filt_range_ranges.fetch_add(groups.size(), std::memory_order_relaxed);
-    } else if (multi) {
-        h->n_filt_multi_calls.fetch_add(1, std::memory_order_relaxed);
-        h->n_filt_multi_masks.fetch_add(groups.size(), std::memory_order_relaxed);
-    }
+    count_call(h, src.family, n_graph - n2, n_exact, n2, groups.size());
     if (!pin_block) out.copy_out(hv, ids, dists, counts, stats);
     if (paths) memcpy(paths, path.data(), nq);
     return HNSW_OK;
 }
 
-int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const MaskSpec &m,
+int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f,
                             bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
-                            uint8_t *paths, const PathCounters *ctr) {
+                            uint8_t *paths) {
     std::vector<hnsw_query_stats> local;
     if (!stats && nq <= 0x7FFFFFFFull) {  // (more queries are refused below, before anything is allocated for them)
         local.resize(nq);
         stats = local.data();
     }
-    int rc = search_filtered(h, Q, nq, n, ef, m, exact_only, ids, dists, counts, stats, paths, ctr);
+    int rc = search_filtered(h, Q, nq, n, ef, f, exact_only, ids, dists, counts, stats, paths);
     if (rc != HNSW_OK || n == 0) return rc;
     return first_query_error(stats, nq);
 }
 
-int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+int search_device_filtered(hnsw_index *h, const Filter &f, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
                            uint32_t *d_ids, float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
                            hipStream_t stream, bool finish, uint8_t *paths) {
-    hnsw_mask_set *const set = f.set;
-    const bool ranged = f.d_lo != nullptr, both = set && ranged, deleted = !set && !ranged, listed = f.n_ranges != 0;
-    const uint64_t rk = listed ? f.n_ranges : 1;  // ranges per query
+    int rc = check_filter(f);
+    if (rc != HNSW_OK) return rc;
+    hnsw_mask_set *const set = f.rows == Filter::SET ? f.set : nullptr;
+    const bool ranged = f.K != 0, keyed = f.mask_of || ranged;  // keyed: the queries name rows or ranges the host has not seen
+    const uint64_t rk = ranged ? f.K : 1;                       // ranges per query
     const uint32_t efp = std::max(std::max(ef, n), 1u);
     if (n > HX_FILT_MAX_N || efp > HX_FILT_MAX_EF) {
-        set_error("%s: needs n <= %d and ef' = max(ef, n) <= %d", deleted ? "search with deleted ids" : "filtered device search",
-                  HX_FILT_MAX_N, HX_FILT_MAX_EF);
+        set_error("%s: needs n <= %d and ef' = max(ef, n) <= %d",
+                  f.family == Filter::DELETED ? "search with deleted ids" : "filtered device search", HX_FILT_MAX_N, HX_FILT_MAX_EF);
         return HNSW_ERR_ARG;
     }
-    if (set && !f.d_mask_of && set->n_masks == 0) {
+    if (set && !f.mask_of && set->n_masks == 0) {
         set_error("filtered device search: every query names row 0 of a set without rows");
         return HNSW_ERR_ARG;
     }
-    int rc;
     if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h)) || (ranged && (rc = sync_labels(h)))) return rc;
     if (set) {
         std::lock_guard<std::mutex> g(set->mu);
@@ -872,33 +879,13 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
     const DevView &v = h->dev.view;
     DeviceQueries dq;
     if ((rc = dq.prepare(h, d_Q, nq, stream))) return rc;
-    // the kernels write distances and counts: stream-ordered stand-ins for the optional outputs
-    struct Tmp {
-        void *p = nullptr;
-        hipStream_t st = nullptr;
-        ~Tmp() {
-            if (p) (void)hipFreeAsync(p, st);
-        }
-    } t_dists, t_counts;
-    if (!d_dists) {
-        HIP_TRY(hipMallocAsync(&t_dists.p, nq * n * 4, stream));
-        t_dists.st = stream;
-        d_dists = static_cast<float *>(t_dists.p);
-    }
-    if (!d_counts) {
-        HIP_TRY(hipMallocAsync(&t_counts.p, nq * 4, stream));
-        t_counts.st = stream;
-        d_counts = static_cast<uint32_t *>(t_counts.p);
-    }
-    FilterSource src(h,
-                     both     ? FilterSource::SET_RANGE
-                     : set    ? FilterSource::SET
-                     : listed ? FilterSource::RANGES
-                     : ranged ? FilterSource::RANGE
-                              : FilterSource::ONE,
-                     nullptr, set, set ? set->allow_bits : index_len(h));
-    src.K = (uint32_t)rk;
-    src.bind(dq.q, set ? set->d_rows() : nullptr, f.d_mask_of, f.d_lo, f.d_hi, set ? set->n_masks : 0, n, efp);
+    StreamTmp t_dists, t_counts;  // the kernels write distances and counts: stand-ins for the optional outputs
+    if (!d_dists && (rc = t_dists.alloc(nq * n * 4, stream))) return rc;
+    if (!d_counts && (rc = t_counts.alloc(nq * 4, stream))) return rc;
+    if (!d_dists) d_dists = static_cast<float *>(t_dists.p);
+    if (!d_counts) d_counts = static_cast<uint32_t *>(t_counts.p);
+    FilterSource src(h, f);
+    src.bind(dq.q, set ? set->d_rows() : nullptr, f.mask_of, f.lo, f.hi, n, efp);
     FilterArgs &a = src.base;
     a.out_ids = d_ids;
     a.out_dists = d_dists;
@@ -911,7 +898,7 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
     // scratch: the selection on the device; the statuses and the keys of the queries (the rows and ranges they name:
     // [rows | lo | hi]) on the host; the exact path's part ([selection | its scratch]) is sized only when a query reaches it
     const size_t st_bytes = nq * sizeof(hnsw_query_stats), o_keys = align256(st_bytes), r_bytes = align256(nq * rk * 4);
-    const size_t pin_bytes = deleted ? st_bytes : o_keys + 3 * r_bytes;
+    const size_t pin_bytes = keyed ? o_keys + 3 * r_bytes : st_bytes;
     ScratchLease lease(h);
     if ((rc = lease.prepare(h->dev.device, align256(nq * 4), pin_bytes))) return rc;
     const hnsw_query_stats *st = nullptr;
@@ -921,16 +908,18 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
         uint32_t *k0 = reinterpret_cast<uint32_t *>(pin + o_keys), *k1 = reinterpret_cast<uint32_t *>(pin + o_keys + r_bytes),
                  *k2 = reinterpret_cast<uint32_t *>(pin + o_keys + 2 * r_bytes);
         HIP_TRY(hipMemcpyAsync(pin, d_stats, st_bytes, hipMemcpyDeviceToHost, stream));
-        if (f.d_mask_of && !have_keys) HIP_TRY(hipMemcpyAsync(k0, f.d_mask_of, nq * 4, hipMemcpyDeviceToHost, stream));
+        if (f.mask_of && !have_keys) HIP_TRY(hipMemcpyAsync(k0, f.mask_of, nq * 4, hipMemcpyDeviceToHost, stream));
         if (ranged && !have_keys) {
-            HIP_TRY(hipMemcpyAsync(k1, f.d_lo, nq * rk * 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(k2, f.d_hi, nq * rk * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(k1, f.lo, nq * rk * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(k2, f.hi, nq * rk * 4, hipMemcpyDeviceToHost, stream));
         }
         HIP_TRY(hipStreamSynchronize(stream));
         out = st = reinterpret_cast<const hnsw_query_stats *>(pin);
-        if (f.d_mask_of) src.mask_of = k0;
+        if (f.mask_of) src.mask_of = k0;
         if (ranged) src.lo = k1, src.hi = k2;
-        if (listed && !have_keys) src.intern(nq);  // (the lists are seen here for the first time)
+        // (the ranges are seen here for the first time.  Without a row per query their table is also the count of the
+        // call's groups and is made now; with one the groups are counted from the pairs, and the table waits for path 2)
+        if (ranged && !f.mask_of && !have_keys) src.intern(nq);
         have_keys = true;
         return HNSW_OK;
     };
@@ -941,22 +930,13 @@ int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_
         fetch,
         [&](const std::vector<uint32_t> &sel) -> int {
             // (a query that names no row of the set ended with HNSW_ERR_ARG, not with an overflow: every row here exists)
+            if (ranged && !src.interned()) src.intern(nq);
             return path2(src, sel, path, nullptr, 0, ExactPlace{nullptr, ExactScratch(), stream, nullptr, nullptr, true},
                          nullptr, 0, &lease, pin_bytes, fetch);
         },
         &n2);
     if (rc != HNSW_OK) return rc;
-    (deleted ? h->n_del_graph : h->n_filt_graph).fetch_add(nq - n2, std::memory_order_relaxed);
-    (deleted ? h->n_del_overflow : h->n_filt_overflow).fetch_add(n2, std::memory_order_relaxed);
-    if (set && !both) h->n_filt_set_calls.fetch_add(1, std::memory_order_relaxed);
-    if (ranged) {  // ... and the distinct ranges, or (row, range) triples, over all queries
-        std::vector<std::pair<uint64_t, uint64_t>> named(nq);
-        for (uint64_t i = 0; i < nq; i++) named[i] = {src.key((uint32_t)i), src.range((uint32_t)i)};
-        std::sort(named.begin(), named.end());
-        const uint64_t distinct = (uint64_t)(std::unique(named.begin(), named.end()) - named.begin());
-        (both ? h->n_filt_set_range_calls : listed ? h->n_filt_ranges_calls : h->n_filt_range_calls).fetch_add(1, std::memory_order_relaxed);
-        (both ? h->n_filt_set_range_groups : listed ? h->n_filt_ranges_groups : h->n_filt_range_ranges).fetch_add(distinct, std::memory_order_relaxed);
-    }
+    count_call(h, src.family, nq - n2, 0, n2, ranged ? src.n_groups(nq) : 0);
     if (paths) memcpy(paths, path.data(), nq);
     for (uint64_t i = 0; i < nq; i++)
         if (set && st[i].status == HNSW_ERR_ARG) {  // (the kernel's check of d_mask_of)

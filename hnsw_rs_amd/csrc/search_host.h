@@ -79,65 +79,63 @@ int search_staged(hnsw_index *h, SearchScratch &s, const HostSearchPlan &p, Sear
 int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, uint32_t *ids, float *dists,
                 uint32_t *counts, hnsw_query_stats *stats, const uint32_t *entries);
 
-// The allow-lists of a filtered call.  One mask for every query (mask_of == nullptr; masks == nullptr: every id below
-// allow_bits), or n_masks rows of ceil(allow_bits / 64) words and a row (or HNSW_MASK_NONE) per query.  The rows are
-// the caller's and go up with the call, or they are a resident set's (masks, allow_bits and n_masks are then the
-// set's host words, mask_of is required): nothing is uploaded, the kernels read the set's HBM copy, and the admissible
-// ids of a row come from the set's caches.  Or the call has no masks but a closed range [lo[i], hi[i]] per query over
-// the handle's label column (hnsw_search_batch_filtered_range; allow_bits is the index length): the planner's unit is
-// then a distinct (lo, hi) pair, counted with the column's sorted copy.  Or it has a resident set AND a range per query
-// (hnsw_search_batch_filtered_set_range): query i is under the ids of row mask_of[i] whose label lies in [lo[i], hi[i]],
-// the planner's unit is a distinct (row, lo, hi) triple, counted by walking the cheaper of the range's slice of the
-// sorted copy and the row's set bits, and the set's per-row caches serve only the triples whose range is [0, UINT32_MAX].
-// Or it has a LIST of n_ranges ranges per query (hnsw_search_batch_filtered_ranges; row-major, a member with lo > hi is
-// empty): the planner's unit is a distinct canonical list -- empties dropped, sorted, overlapping and adjacent members
-// merged -- counted exactly as the sum of its disjoint members' slices of the sorted copy.
-struct MaskSpec {
-    const uint64_t *masks = nullptr;
-    uint64_t allow_bits = 0;
-    uint32_t n_masks = 1;
-    const uint32_t *mask_of = nullptr;  // nq entries
-    hnsw_mask_set *set = nullptr;
-    const uint32_t *lo = nullptr, *hi = nullptr;  // nq entries each (nq x n_ranges with a list per query)
-    uint32_t n_ranges = 0;  // K > 0: query i is under the union of [lo[i K + j], hi[i K + j]], j < K (no masks, no set)
+// The filter of a call, stated once: which ROWS of mask words its queries are under, and how many label RANGES each
+// query has.  The two facts are independent; the legal combinations are
+//
+//   rows \ K   | 0                              | 1                                    | 2 .. HNSW_RANGES_MAX
+//   ALL        | the undeleted ids below len    | _filtered_range                      | _filtered_ranges
+//   ONE        | _filtered (masks: one row)     | refused                              | refused
+//   MANY       | _filtered_multi                | refused                              | refused
+//   SET        | _filtered_set, _device         | _filtered_set_range, _device         | refused (the kernel's LDS has no room)
+//
+// rows: ALL -- every undeleted id below the index length; ONE -- `masks` is one row of allow_bits bits for the whole
+// call; MANY -- the caller's n_masks rows of ceil(allow_bits / 64) words, and query i is under row mask_of[i] or
+// HNSW_MASK_NONE; SET -- the rows are a resident hnsw_mask_set's (nothing is uploaded, the kernels read its HBM copy,
+// the admissible ids of a row come from its caches), mask_of as under MANY, or nullptr in a device call: row 0.
+// ranges: query i is under the union of [lo[i K + j], hi[i K + j]], j < K, over the handle's label column; a member
+// with lo > hi is empty; K == 0: no label filter.  Next to a SET row a query is under the row AND its range.
+struct Filter {
+    // the entry points that made the call: picks the stat counters and the wording of errors, never a launch
+    enum Family { DELETED, SCAN, MASK, MULTI, OF_SET, RANGE, SET_RANGE, RANGES } family = DELETED;
+    enum Rows { ALL, ONE, MANY, SET } rows = ALL;
+    const uint64_t *masks = nullptr;  // ONE, MANY (host memory)
+    uint64_t allow_bits = 0;          // ONE, MANY
+    uint32_t n_masks = 0;             // MANY
+    hnsw_mask_set *set = nullptr;     // SET
+    const uint32_t *mask_of = nullptr;            // MANY, SET: nq entries
+    uint32_t K = 0;                               // ranges per query
+    const uint32_t *lo = nullptr, *hi = nullptr;  // nq x K entries each, row-major
+    bool on_device = false;  // mask_of, lo and hi are device memory (a device-pointer call), else host memory
 };
 
 // The admissible ids of a mask: below bits = min(allow_bits, len), allowed by `allow` (nullptr: all), not deleted.
 // -> A, and the admissible ids before every block of 64 words (the compaction kernel's offsets)
 uint64_t count_admissible(const hnsw_index *h, const uint64_t *allow, uint64_t bits, std::vector<uint32_t> &wbase);
 
-// k-NN among the admissible ids (hnsw_search_batch_filtered's, _multi's, _set's, _range's and _set_range's contract): the
-// planner runs per group -- the queries under one mask, row, range or (row, range) -- the graph path's queries of all groups share one launch and
-// one re-run loop, the exact path runs group by group; queries that fill the largest visited table are answered by the
+// k-NN among the admissible ids (the contract of every hnsw_search_batch_filtered*): the planner runs per group -- the
+// queries under one (row, canonical range list) -- the graph path's queries of all groups share one launch and one
+// re-run loop, the exact path runs group by group; queries that fill the largest visited table are answered by the
 // exact path as well, each under its own filter (path 2).
 // exact_only: every query by the exact path (hnsw_brute_force).  The results go to the caller's buffers (per-query
 // statuses in stats: required), or, when pin_block is given, straight into that pinned ResultBlock(nq, n) and the
 // buffers are not read.  Returns argument and launch errors only.
-int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const MaskSpec &m,
+int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f,
                     bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
-                    uint8_t *paths, const PathCounters *ctr, void *pin_block = nullptr);
+                    uint8_t *paths, void *pin_block = nullptr);
 // ... with the first per-query error as the status (stats may be NULL)
-int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const MaskSpec &m,
+int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f,
                             bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
-                            uint8_t *paths, const PathCounters *ctr);
+                            uint8_t *paths);
 
-// The filter of a device-pointer call, read on the device: a row of a resident set per query (d_mask_of; nullptr: row 0),
-// or a label range per query (d_lo / d_hi), or both (hnsw_search_batch_filtered_set_range_device), or neither: the
-// undeleted ids, while ids are deleted.
-struct DeviceFilter {
-    hnsw_mask_set *set = nullptr;
-    const uint32_t *d_mask_of = nullptr, *d_lo = nullptr, *d_hi = nullptr;
-    uint32_t n_ranges = 0;  // K > 0: d_lo / d_hi hold nq x K members (hnsw_search_batch_filtered_ranges_device)
-};
-
-// hnsw_search_batch_device while ids are deleted, hnsw_search_batch_filtered_device, _filtered_range_device and
-// _filtered_set_range_device (finish = false), and their _finish: every query by the filtered graph path under its own filter.  The deleted set and
+// A device-pointer call under a Filter whose mask_of / lo / hi are device memory (on_device): hnsw_search_batch_device
+// while ids are deleted and every hnsw_search_batch_filtered*_device (finish = false), and their _finish: every query by
+// the filtered graph path under its own filter.  The deleted set and
 // the set or the label column are brought up to date on a stream of the handle's own, then ONE launch goes to the
 // caller's stream.  _finish waits, reads the statuses back (and with them, once, d_mask_of and d_lo / d_hi), re-runs the
 // queries whose visited table filled up with larger tables, up to the graph path's largest, answers those that fill it
 // by the exact path, each under its own row and range (search_filtered's path 2), and returns the first per-query error:
 // a row the set does not have is HNSW_ERR_ARG.  Equals search_filtered under the same filter with filter_exact_max = -1.
-int search_device_filtered(hnsw_index *h, const DeviceFilter &f, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
+int search_device_filtered(hnsw_index *h, const Filter &f, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
                            uint32_t *d_ids, float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
                            hipStream_t stream, bool finish, uint8_t *paths);
 

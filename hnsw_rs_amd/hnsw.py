@@ -263,55 +263,61 @@ class HNSW:
                                         C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
         return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64)
 
+    def _filtered(self, fn, Q, n, ef, middle):
+        """A filtered host call: fn(handle, Q, nq, n, ef, *middle(nq), ids, dists, counts, stats, paths), where middle
+        makes the entry point's own arguments once the queries are checked (uint32 / uint64 arrays go as pointers, None
+        as NULL).  -> the five-tuple of search_batch_filtered"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        nq = Q.shape[0]
+        mid = middle(nq)  # (the arrays stay alive here for the length of the call)
+        args = [_p(x, _u64p if x.dtype == np.uint64 else _u32p) if isinstance(x, np.ndarray) else x for x in mid]
+        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        paths = np.zeros(nq, dtype=np.uint8)
+        check(fn(self._h, _p(Q, _f32p), nq, n, ef, *args, _p(ids, _u32p), _p(dists, _f32p), _p(counts, _u32p),
+                 C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
+        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+
+    def _filtered_device(self, fn, d_Q, nq, n, ef, middle, d_ids, d_dists, d_counts, d_stats, stream):
+        """A filtered device call: torch device tensors, raw device pointers (ints) or None / 0 for the buffers; `middle`:
+        the entry point's own arguments, as they go to fn"""
+        p = self._dptr
+        check(fn(self._h, p(d_Q), nq, n, ef, *middle, p(d_ids), p(d_dists), p(d_counts), p(d_stats), stream or None))
+
+    def _filtered_device_finish(self, fn, d_Q, nq, n, ef, middle, d_ids, d_dists, d_counts, d_stats, stream, paths):
+        """... and its _finish.  paths=True -> uint8 [nq] (0 / 2)"""
+        p = self._dptr
+        out = np.zeros(nq, dtype=np.uint8) if paths else None
+        check(fn(self._h, p(d_Q), nq, n, ef, *middle, p(d_ids), p(d_dists), p(d_counts), p(d_stats), stream or None,
+                 None if out is None else _p(out, _u8p)))
+        return out
+
     def search_batch_filtered(self, Q, n, ef, allow):
         """k-NN among the allowed ids (include/hnsw_mi355x.h, hnsw_search_batch_filtered).  allow: a bool array
         over ids (its length is allow_bits) or an array of allowed ids (see pack_allow).
         -> ids [nq, n] (pad UINT32_MAX), dists [nq, n], counts [nq], stats [nq, 4], paths [nq] (0 graph,
         1 exact, 2 exact after a visited-table overflow)"""
-        Q = np.ascontiguousarray(Q, dtype=np.float32)
-        if Q.ndim != 2 or Q.shape[1] != self.dim:
-            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
-        words, bits = pack_allow(allow, self.len())
-        nq = Q.shape[0]
-        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
-        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
-        counts = np.zeros(nq, dtype=np.uint32)
-        stats = np.zeros((nq, 4), dtype=np.int32)
-        paths = np.zeros(nq, dtype=np.uint8)
-        check(self._L.hnsw_search_batch_filtered(self._h, _p(Q, _f32p), nq, n, ef, _p(words, _u64p), bits,
-                                                 _p(ids, _u32p), _p(dists, _f32p), _p(counts, _u32p),
-                                                 C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
-        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+        def middle(nq):
+            return pack_allow(allow, self.len())
+
+        return self._filtered(self._L.hnsw_search_batch_filtered, Q, n, ef, middle)
 
     def search_batch_filtered_multi(self, Q, n, ef, masks, mask_of):
         """k-NN with an allow-list per query (include/hnsw_mi355x.h, hnsw_search_batch_filtered_multi).  masks: what
         pack_allow_many takes (None or empty when no query names a mask); mask_of [nq]: the row of masks each query
         searches under, -1 or MASK_NONE for no allow-list.  -> as search_batch_filtered"""
-        Q = np.ascontiguousarray(Q, dtype=np.float32)
-        if Q.ndim != 2 or Q.shape[1] != self.dim:
-            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
-        nq = Q.shape[0]
-        mo = np.asarray(mask_of).reshape(-1).astype(np.int64)
-        if mo.shape[0] != nq:
-            raise ValueError("mask_of must hold one entry per query")
-        if ((mo < -1) | (mo > _lib.MASK_NONE)).any():
-            raise ValueError("mask_of entries are rows of masks, -1 or MASK_NONE")
-        mo = np.ascontiguousarray(np.where(mo < 0, _lib.MASK_NONE, mo).astype(np.uint32))
-        if masks is None or len(masks) == 0:
-            words, bits, n_masks = None, 0, 0
-        else:
+        def middle(nq):
+            mo = self._mask_of(np.asarray(mask_of), nq)  # (required here: None is no "row 0")
+            if masks is None or len(masks) == 0:
+                return None, 0, 0, mo
             words, bits = pack_allow_many(masks, self.len())
-            n_masks = words.shape[0]
-        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
-        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
-        counts = np.zeros(nq, dtype=np.uint32)
-        stats = np.zeros((nq, 4), dtype=np.int32)
-        paths = np.zeros(nq, dtype=np.uint8)
-        check(self._L.hnsw_search_batch_filtered_multi(
-            self._h, _p(Q, _f32p), nq, n, ef, None if words is None else _p(words, _u64p), n_masks, bits,
-            _p(mo, _u32p), _p(ids, _u32p), _p(dists, _f32p), _p(counts, _u32p),
-            C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
-        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+            return words, words.shape[0], bits, mo
+
+        return self._filtered(self._L.hnsw_search_batch_filtered_multi, Q, n, ef, middle)
 
     def mask_set(self, masks_or_n_masks, n_points=None):
         """-> MaskSet: allow-lists resident with this index (include/hnsw_mi355x.h, hnsw_mask_set).  Either what
@@ -341,37 +347,23 @@ class HNSW:
         """search_batch_filtered_multi with the masks of a resident MaskSet (hnsw_search_batch_filtered_set): nothing
         is packed or uploaded per call.  mask_of [nq]: rows of the set, -1 or MASK_NONE; None: every query under row 0.
         -> as search_batch_filtered"""
-        Q = np.ascontiguousarray(Q, dtype=np.float32)
-        if Q.ndim != 2 or Q.shape[1] != self.dim:
-            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
-        nq = Q.shape[0]
-        mo = self._mask_of(mask_of, nq)
-        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
-        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
-        counts = np.zeros(nq, dtype=np.uint32)
-        stats = np.zeros((nq, 4), dtype=np.int32)
-        paths = np.zeros(nq, dtype=np.uint8)
-        check(self._L.hnsw_search_batch_filtered_set(
-            self._h, _p(Q, _f32p), nq, n, ef, mask_set._s, None if mo is None else _p(mo, _u32p), _p(ids, _u32p),
-            _p(dists, _f32p), _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
-        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+        return self._filtered(self._L.hnsw_search_batch_filtered_set, Q, n, ef,
+                              lambda nq: (mask_set._s, self._mask_of(mask_of, nq)))
 
     def search_batch_filtered_device(self, d_Q, nq, n, ef, mask_set, d_mask_of, d_ids, d_dists, d_counts, d_stats,
                                      stream=0):
         """hnsw_search_batch_filtered_device: raw device pointers (ints; d_mask_of 0 / None: row 0), one launch
         enqueued on `stream`, no sync."""
-        check(self._L.hnsw_search_batch_filtered_device(self._h, d_Q, nq, n, ef, mask_set._s, d_mask_of or None, d_ids,
-                                                        d_dists or None, d_counts or None, d_stats, stream or None))
+        self._filtered_device(self._L.hnsw_search_batch_filtered_device, d_Q, nq, n, ef,
+                              (mask_set._s, self._dptr(d_mask_of)), d_ids, d_dists, d_counts, d_stats, stream)
 
     def search_batch_filtered_device_finish(self, d_Q, nq, n, ef, mask_set, d_mask_of, d_ids, d_dists, d_counts, d_stats,
                                             stream=0, paths=False):
         """Completes search_batch_filtered_device: synchronises, re-runs overflowed queries, answers those that fill
         the largest table by the exact path, raises the first per-query error.  paths=True -> uint8 [nq] (0 / 2)"""
-        out = np.zeros(nq, dtype=np.uint8) if paths else None
-        check(self._L.hnsw_search_batch_filtered_device_finish(
-            self._h, d_Q, nq, n, ef, mask_set._s, d_mask_of or None, d_ids, d_dists or None, d_counts or None, d_stats,
-            stream or None, None if out is None else _p(out, _u8p)))
-        return out
+        return self._filtered_device_finish(self._L.hnsw_search_batch_filtered_device_finish, d_Q, nq, n, ef,
+                                            (mask_set._s, self._dptr(d_mask_of)), d_ids, d_dists, d_counts, d_stats,
+                                            stream, paths)
 
     # ---- labels and label-range filtered search (include/hnsw_mi355x.h) ------------------------------------------
     def set_labels(self, labels, ids=None):
@@ -406,60 +398,34 @@ class HNSW:
     def search_batch_filtered_range(self, Q, n, ef, lo, hi):
         """k-NN among the ids whose label lies in [lo[i], hi[i]] (hnsw_search_batch_filtered_range); scalars broadcast,
         lo > hi is an empty range.  -> as search_batch_filtered"""
-        Q = np.ascontiguousarray(Q, dtype=np.float32)
-        if Q.ndim != 2 or Q.shape[1] != self.dim:
-            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
-        nq = Q.shape[0]
-        lo, hi = self._range(lo, hi, nq)
-        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
-        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
-        counts = np.zeros(nq, dtype=np.uint32)
-        stats = np.zeros((nq, 4), dtype=np.int32)
-        paths = np.zeros(nq, dtype=np.uint8)
-        check(self._L.hnsw_search_batch_filtered_range(
-            self._h, _p(Q, _f32p), nq, n, ef, _p(lo, _u32p), _p(hi, _u32p), _p(ids, _u32p), _p(dists, _f32p),
-            _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
-        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+        return self._filtered(self._L.hnsw_search_batch_filtered_range, Q, n, ef, lambda nq: self._range(lo, hi, nq))
 
     # ---- label-set filtered search: several label ranges per query ------------------------------------------------
     def search_batch_filtered_ranges(self, Q, n, ef, ranges):
         """k-NN among the ids whose label lies in at least one of the query's ranges
         (hnsw_search_batch_filtered_ranges).  ranges: one list per query, its members (lo, hi) or an int x meaning [x, x]; ragged
         lists are padded with the empty range (1, 0) (pack_ranges).  -> as search_batch_filtered"""
-        Q = np.ascontiguousarray(Q, dtype=np.float32)
-        if Q.ndim != 2 or Q.shape[1] != self.dim:
-            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
-        nq = Q.shape[0]
-        lo, hi = pack_ranges(ranges, nq)
-        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
-        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
-        counts = np.zeros(nq, dtype=np.uint32)
-        stats = np.zeros((nq, 4), dtype=np.int32)
-        paths = np.zeros(nq, dtype=np.uint8)
-        check(self._L.hnsw_search_batch_filtered_ranges(
-            self._h, _p(Q, _f32p), nq, n, ef, lo.shape[1], _p(lo, _u32p), _p(hi, _u32p), _p(ids, _u32p), _p(dists, _f32p),
-            _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
-        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+        def middle(nq):
+            lo, hi = pack_ranges(ranges, nq)
+            return lo.shape[1], lo, hi
+
+        return self._filtered(self._L.hnsw_search_batch_filtered_ranges, Q, n, ef, middle)
 
     def search_batch_filtered_ranges_device(self, d_Q, nq, n, ef, n_ranges, d_lo, d_hi, d_ids, d_dists, d_counts,
                                             d_stats, stream=0):
         """hnsw_search_batch_filtered_ranges_device over torch device tensors (or raw device pointers): d_lo / d_hi
         uint32 [nq, n_ranges] in HBM; one launch enqueued on `stream`, no sync."""
         p = self._dptr
-        check(self._L.hnsw_search_batch_filtered_ranges_device(self._h, p(d_Q), nq, n, ef, n_ranges, p(d_lo), p(d_hi),
-                                                               p(d_ids), p(d_dists), p(d_counts), p(d_stats),
-                                                               stream or None))
+        self._filtered_device(self._L.hnsw_search_batch_filtered_ranges_device, d_Q, nq, n, ef,
+                              (n_ranges, p(d_lo), p(d_hi)), d_ids, d_dists, d_counts, d_stats, stream)
 
     def search_batch_filtered_ranges_device_finish(self, d_Q, nq, n, ef, n_ranges, d_lo, d_hi, d_ids, d_dists, d_counts,
                                                    d_stats, stream=0, paths=False):
         """Completes search_batch_filtered_ranges_device: synchronises, re-runs overflowed queries, answers those that
         fill the largest table by the exact path, raises the first per-query error.  paths=True -> uint8 [nq] (0 / 2)"""
         p = self._dptr
-        out = np.zeros(nq, dtype=np.uint8) if paths else None
-        check(self._L.hnsw_search_batch_filtered_ranges_device_finish(
-            self._h, p(d_Q), nq, n, ef, n_ranges, p(d_lo), p(d_hi), p(d_ids), p(d_dists), p(d_counts), p(d_stats),
-            stream or None, None if out is None else _p(out, _u8p)))
-        return out
+        return self._filtered_device_finish(self._L.hnsw_search_batch_filtered_ranges_device_finish, d_Q, nq, n, ef,
+                                            (n_ranges, p(d_lo), p(d_hi)), d_ids, d_dists, d_counts, d_stats, stream, paths)
 
     def count_labels_in_ranges(self, ranges):
         """hnsw_count_labels_in_ranges: the undeleted ids whose label lies in the union of `ranges` (members (lo, hi) or
@@ -486,19 +452,16 @@ class HNSW:
         """hnsw_search_batch_filtered_range_device over torch device tensors (or raw device pointers): d_lo / d_hi
         uint32 [nq] in HBM; one launch enqueued on `stream`, no sync."""
         p = self._dptr
-        check(self._L.hnsw_search_batch_filtered_range_device(self._h, p(d_Q), nq, n, ef, p(d_lo), p(d_hi), p(d_ids),
-                                                              p(d_dists), p(d_counts), p(d_stats), stream or None))
+        self._filtered_device(self._L.hnsw_search_batch_filtered_range_device, d_Q, nq, n, ef, (p(d_lo), p(d_hi)),
+                              d_ids, d_dists, d_counts, d_stats, stream)
 
     def search_batch_filtered_range_device_finish(self, d_Q, nq, n, ef, d_lo, d_hi, d_ids, d_dists, d_counts, d_stats,
                                                   stream=0, paths=False):
         """Completes search_batch_filtered_range_device: synchronises, re-runs overflowed queries, answers those that
         fill the largest table by the exact path, raises the first per-query error.  paths=True -> uint8 [nq] (0 / 2)"""
         p = self._dptr
-        out = np.zeros(nq, dtype=np.uint8) if paths else None
-        check(self._L.hnsw_search_batch_filtered_range_device_finish(
-            self._h, p(d_Q), nq, n, ef, p(d_lo), p(d_hi), p(d_ids), p(d_dists), p(d_counts), p(d_stats), stream or None,
-            None if out is None else _p(out, _u8p)))
-        return out
+        return self._filtered_device_finish(self._L.hnsw_search_batch_filtered_range_device_finish, d_Q, nq, n, ef,
+                                            (p(d_lo), p(d_hi)), d_ids, d_dists, d_counts, d_stats, stream, paths)
 
     # ---- a label range AND a row of a resident mask set (include/hnsw_mi355x.h) -----------------------------------
     def search_batch_filtered_set_range(self, Q, n, ef, mask_set, mask_of, lo, hi):
@@ -506,31 +469,16 @@ class HNSW:
         (hnsw_search_batch_filtered_set_range).  mask_of [nq]: rows of the set, -1 or MASK_NONE (the range alone);
         None: every query under row 0.  lo / hi: scalars broadcast, lo > hi is an empty range.
         -> as search_batch_filtered"""
-        Q = np.ascontiguousarray(Q, dtype=np.float32)
-        if Q.ndim != 2 or Q.shape[1] != self.dim:
-            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
-        nq = Q.shape[0]
-        mo = self._mask_of(mask_of, nq)
-        lo, hi = self._range(lo, hi, nq)
-        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
-        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
-        counts = np.zeros(nq, dtype=np.uint32)
-        stats = np.zeros((nq, 4), dtype=np.int32)
-        paths = np.zeros(nq, dtype=np.uint8)
-        check(self._L.hnsw_search_batch_filtered_set_range(
-            self._h, _p(Q, _f32p), nq, n, ef, mask_set._s, None if mo is None else _p(mo, _u32p), _p(lo, _u32p),
-            _p(hi, _u32p), _p(ids, _u32p), _p(dists, _f32p), _p(counts, _u32p),
-            C.cast(stats.ctypes.data, C.POINTER(QueryStats)), _p(paths, _u8p)))
-        return ids[:, :n], dists[:, :n], counts, stats.view(np.uint32).astype(np.int64), paths
+        return self._filtered(self._L.hnsw_search_batch_filtered_set_range, Q, n, ef,
+                              lambda nq: (mask_set._s, self._mask_of(mask_of, nq), *self._range(lo, hi, nq)))
 
     def search_batch_filtered_set_range_device(self, d_Q, nq, n, ef, mask_set, d_mask_of, d_lo, d_hi, d_ids, d_dists,
                                                d_counts, d_stats, stream=0):
         """hnsw_search_batch_filtered_set_range_device over torch device tensors (or raw device pointers): d_mask_of
         (None / 0: row 0), d_lo / d_hi uint32 [nq] in HBM; one launch enqueued on `stream`, no sync."""
         p = self._dptr
-        check(self._L.hnsw_search_batch_filtered_set_range_device(
-            self._h, p(d_Q), nq, n, ef, mask_set._s, p(d_mask_of), p(d_lo), p(d_hi), p(d_ids), p(d_dists), p(d_counts),
-            p(d_stats), stream or None))
+        self._filtered_device(self._L.hnsw_search_batch_filtered_set_range_device, d_Q, nq, n, ef,
+                              (mask_set._s, p(d_mask_of), p(d_lo), p(d_hi)), d_ids, d_dists, d_counts, d_stats, stream)
 
     def search_batch_filtered_set_range_device_finish(self, d_Q, nq, n, ef, mask_set, d_mask_of, d_lo, d_hi, d_ids,
                                                       d_dists, d_counts, d_stats, stream=0, paths=False):
@@ -538,11 +486,9 @@ class HNSW:
         that fill the largest table by the exact path, raises the first per-query error.
         paths=True -> uint8 [nq] (0 / 2)"""
         p = self._dptr
-        out = np.zeros(nq, dtype=np.uint8) if paths else None
-        check(self._L.hnsw_search_batch_filtered_set_range_device_finish(
-            self._h, p(d_Q), nq, n, ef, mask_set._s, p(d_mask_of), p(d_lo), p(d_hi), p(d_ids), p(d_dists), p(d_counts),
-            p(d_stats), stream or None, None if out is None else _p(out, _u8p)))
-        return out
+        return self._filtered_device_finish(self._L.hnsw_search_batch_filtered_set_range_device_finish, d_Q, nq, n, ef,
+                                            (mask_set._s, p(d_mask_of), p(d_lo), p(d_hi)), d_ids, d_dists, d_counts,
+                                            d_stats, stream, paths)
 
     def ann_by_vector_filtered(self, vector, n, ef, allow):
         """ann_by_vector restricted to the allowed ids -> list of ids"""
