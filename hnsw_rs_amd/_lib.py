@@ -116,6 +116,11 @@ SYMBOLS = {
                                                               vp, vp, vp, vp, vp]),
     "hnsw_search_batch_filtered_set_range_device_finish": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp,
                                                                      vp, vp, vp, vp, vp, vp, vp, u8p]),
+    "hnsw_search_filtered": (C.c_int, [vp, f32p, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, u32p, f32p,
+                                       u32p, u8p]),
+    "hnsw_bench_search_filtered_threads": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, vp, u32p, u32p, u32p,
+                                                     C.c_uint32, C.c_double, u32p, f32p, u32p, u8p, C.POINTER(C.c_int32),
+                                                     u64p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "hnsw_search_batch_device": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
     "hnsw_search_batch_device_finish": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
     "hnsw_merge_topk_device": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, u32p, u32p, vp, vp, vp, vp, vp]),

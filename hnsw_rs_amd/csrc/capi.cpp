@@ -510,6 +510,37 @@ int hnsw_search_batch_filtered_set_range_device_finish(hnsw_index *h, const floa
                            true, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
 }
 
+// ---- one query under a row of a resident set AND a label range, gathered with its concurrent callers (coalesce.h) -------
+int hnsw_search_filtered(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, hnsw_mask_set *set, uint32_t row,
+                         uint32_t lo, uint32_t hi, uint32_t *ids, float *dists, uint32_t *count, uint8_t *path) {
+    // every argument error before the device is touched
+    if (!h || !q || !ids || !count) {
+        set_error("filtered search: needs a handle, a query, an id buffer and a count");
+        return HNSW_ERR_ARG;
+    }
+    if (n > HX_FILT_MAX_N) {
+        set_error("filtered search: needs n <= %d", HX_FILT_MAX_N);
+        return HNSW_ERR_ARG;
+    }
+    if (!set && row != HNSW_MASK_NONE) {
+        set_error("filtered search: a row needs its mask set");
+        return HNSW_ERR_ARG;
+    }
+    int rc;
+    if (set && (rc = check_set(h, set))) return rc;
+    if (set && row != HNSW_MASK_NONE && row >= set->n_masks) {
+        set_error("filtered search: query 0 names mask %u of %u", row, set->n_masks);
+        return HNSW_ERR_ARG;
+    }
+    if ((rc = check_search_args(h, ef)) != HNSW_OK) return rc;
+    *count = 0;
+    if (n == 0) return HNSW_OK;
+    // alone: the window is off, or ef' is beyond the graph path's maximum -- an error of the calls on the graph path only,
+    // which the exact-path calls of the same batch must not see
+    const bool alone = h->co.window_us.load(std::memory_order_relaxed) < 0 || std::max(ef, n) > HX_FILT_MAX_EF;
+    return hx::search_filtered_coalesced(h, q, n, ef, set, row, lo, hi, ids, dists, count, path, alone);
+}
+
 // ---- searches under a list of label ranges per query ---------------------------------------------------------------
 int hnsw_search_batch_filtered_ranges(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
                                       uint32_t n_ranges, const uint32_t *lo, const uint32_t *hi, uint32_t *ids,
@@ -1095,6 +1126,13 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value) {
     } else if (!strcmp(key, "filter_exact_max")) {
         h->filter_exact_max = value;
         return HNSW_OK;
+    } else if (!strcmp(key, "filter_exact_grouped")) {
+        if (value != 0 && value != 1) {
+            set_error("filter_exact_grouped must be 0 or 1");
+            return HNSW_ERR_ARG;
+        }
+        h->filter_exact_grouped = (int)value;
+        return HNSW_OK;
     } else if (!strcmp(key, "mask_set_cache_mb")) {
         if (value < 0) {
             set_error("mask_set_cache_mb must not be negative");
@@ -1190,6 +1228,10 @@ int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
         *out = h->n_filt_set_range_calls.load();
     } else if (!strcmp(key, "filtered_set_range_groups")) {
         *out = h->n_filt_set_range_groups.load();
+    } else if (!strcmp(key, "filtered_one_calls")) {
+        *out = h->n_filt_one_calls.load();
+    } else if (!strcmp(key, "filtered_one_batches")) {
+        *out = h->n_filt_one_batches.load();
     } else if (!strcmp(key, "filtered_ranges_calls")) {
         *out = h->n_filt_ranges_calls.load();
     } else if (!strcmp(key, "filtered_ranges_groups")) {

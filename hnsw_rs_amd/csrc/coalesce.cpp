@@ -29,17 +29,43 @@ inline void futex_wake(std::atomic<uint32_t> *w, int n) {
 
 // a batch from the pool made ready for a new incarnation with `claimed` slots already taken (1: the caller leads
 // it; 0: a leaderless successor whose first joiner will); called under Coalescer::mu
-int cobatch_open(hnsw_index *h, CoBatch &b, uint32_t cap, uint32_t n, uint32_t ef, uint32_t claimed) {
-    const uint32_t d = h->dev.view.dim;
-    const HostSearchPlan p = plan_host_search(cap, d, n, 0);
-    int rc = b.s.reserve(h->dev.device, p.dev_bytes, p.pin_bytes, false);  // (exactly what the plan asks for)
-    if (rc != HNSW_OK) return rc;
-    b.p_q = p.p_q;
-    b.p_out = p.p_out;
+// what a batch is opened and joined by, and what a caller brings
+struct CoCall {
+    const float *q;
+    uint32_t n, ef;
+    uint32_t *ids, *count;
+    bool filtered = false;
+    hnsw_mask_set *set = nullptr;
+    uint32_t row = HNSW_MASK_NONE, lo = 0, hi = 0xFFFFFFFFu;
+    float *dists = nullptr;
+    uint8_t *path = nullptr;
+    bool alone = false;
+};
+
+int cobatch_open(hnsw_index *h, CoBatch &b, uint32_t cap, const CoCall &c, uint32_t claimed) {
+    const uint32_t d = h->dev.view.dim, n = c.n, ef = c.ef;
+    int rc;
+    if (c.filtered) {
+        // the device arena is search_filtered's own lease; pinned: [queries | rows | lo | hi | result block]
+        b.p_q = 0;
+        b.p_row = align256((size_t)cap * d * 4);
+        b.p_lo = b.p_row + align256((size_t)cap * 4);
+        b.p_hi = b.p_lo + align256((size_t)cap * 4);
+        b.p_out = b.p_hi + align256((size_t)cap * 4);
+        if ((rc = b.s.reserve(h->dev.device, 0, b.p_out + ResultBlock(cap, n).bytes, false)) != HNSW_OK) return rc;
+        if (b.paths.size() < cap) b.paths.resize(cap);
+    } else {
+        const HostSearchPlan p = plan_host_search(cap, d, n, 0);
+        if ((rc = b.s.reserve(h->dev.device, p.dev_bytes, p.pin_bytes, false)) != HNSW_OK) return rc;  // (exactly what the plan asks for)
+        b.p_q = p.p_q;
+        b.p_out = p.p_out;
+    }
     b.cap.store(cap, std::memory_order_relaxed);
     b.n.store(n, std::memory_order_relaxed);
     b.ef.store(ef, std::memory_order_relaxed);
     b.dim.store(d, std::memory_order_relaxed);
+    b.filtered.store(c.filtered ? 1 : 0, std::memory_order_relaxed);
+    b.set.store(c.set, std::memory_order_relaxed);
     b.filed.store(0, std::memory_order_relaxed);
     for (auto &w : b.done) w.v.store(0, std::memory_order_relaxed);
     b.readers.store(0, std::memory_order_relaxed);
@@ -53,12 +79,14 @@ int cobatch_open(hnsw_index *h, CoBatch &b, uint32_t cap, uint32_t n, uint32_t e
 }
 
 // claim a slot of an open batch with these parameters: the slot, or -1 (closed, full, other parameters)
-inline int cobatch_join(CoBatch *b, uint32_t n, uint32_t ef, uint32_t d) {
+inline int cobatch_join(CoBatch *b, const CoCall &c, uint32_t d) {
+    const uint32_t n = c.n, ef = c.ef;
     uint64_t w = b->word.load(std::memory_order_acquire);
     while (true) {
         if ((w & CoBatch::CLOSED) || (w & CoBatch::COUNT) >= b->cap.load(std::memory_order_relaxed)) return -1;
         if (b->n.load(std::memory_order_relaxed) != n || b->ef.load(std::memory_order_relaxed) != ef ||
-            b->dim.load(std::memory_order_relaxed) != d)
+            b->dim.load(std::memory_order_relaxed) != d || b->filtered.load(std::memory_order_relaxed) != (c.filtered ? 1u : 0u) ||
+            b->set.load(std::memory_order_relaxed) != (void *)c.set)
             return -1;
         // succeeds only if the word is still the one the parameters were read under (same generation, still open)
         if (b->word.compare_exchange_weak(w, w + 1, std::memory_order_acq_rel, std::memory_order_acquire))
@@ -99,19 +127,33 @@ void Coalescer::retire_unjoined() {
     }
 }
 
-int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uint32_t *ids, uint32_t *count) {
+namespace {
+
+int coalesced(hnsw_index *h, const CoCall &c) {
+    const float *q = c.q;
+    const uint32_t n = c.n, ef = c.ef;
+    uint32_t *ids = c.ids, *count = c.count;
     int rc;
     if (!snapshot_current(h) && (rc = ensure_uploaded(h)) != HNSW_OK) return rc;
     Coalescer &co = h->co;
     const uint32_t d = h->dev.view.dim;
     // ---- claim a slot: the open batch everybody looks at first, else (under the lock) any open batch with these
     // parameters, else a new batch which this caller leads ----
-    CoBatch *b = co.fast.load(std::memory_order_acquire);
-    int slot = b ? cobatch_join(b, n, ef, d) : -1;
-    if (slot < 0) {
+    CoBatch *b = c.alone ? nullptr : co.fast.load(std::memory_order_acquire);
+    int slot = b ? cobatch_join(b, c, d) : -1;
+    if (slot < 0 && c.alone) {
+        // a batch of its own, open to nobody: slot 0 of one, never listed
+        std::lock_guard<SpinLock> g(co.mu);
+        b = co.take();
+        if ((rc = cobatch_open(h, *b, 1, c, 1)) != HNSW_OK) {
+            co.idle.push_back(b);
+            return rc;
+        }
+        slot = 0;
+    } else if (slot < 0) {
         std::lock_guard<SpinLock> g(co.mu);
         for (CoBatch *o : co.open)
-            if ((slot = cobatch_join(o, n, ef, d)) >= 0) {
+            if ((slot = cobatch_join(o, c, d)) >= 0) {
                 b = o;
                 break;
             }
@@ -119,7 +161,7 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
             // a leaderless batch nobody joined (other parameters) is taken out of circulation rather than left open
             co.retire_unjoined();
             b = co.take();
-            if ((rc = cobatch_open(h, *b, co.cap, n, ef, 1)) != HNSW_OK) {
+            if ((rc = cobatch_open(h, *b, co.cap, c, 1)) != HNSW_OK) {
                 co.idle.push_back(b);
                 return rc;
             }
@@ -128,8 +170,14 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
             co.fast.store(b, std::memory_order_release);
         }
     }
-    memcpy(static_cast<unsigned char *>(b->s.pin) + b->p_q + (size_t)slot * d * 4, q, (size_t)d * 4);
-    b->reqs[slot] = CoBatch::Req{ids, count};
+    unsigned char *const pin = static_cast<unsigned char *>(b->s.pin);
+    memcpy(pin + b->p_q + (size_t)slot * d * 4, q, (size_t)d * 4);
+    if (c.filtered) {
+        reinterpret_cast<uint32_t *>(pin + b->p_row)[slot] = c.row;
+        reinterpret_cast<uint32_t *>(pin + b->p_lo)[slot] = c.lo;
+        reinterpret_cast<uint32_t *>(pin + b->p_hi)[slot] = c.hi;
+    }
+    b->reqs[slot] = CoBatch::Req{ids, count, c.dists, c.path};
     b->filed.fetch_add(1, std::memory_order_release);
 
     if (slot != 0) {
@@ -154,7 +202,7 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
     const auto t_lead = sclk::now();
     const int64_t window_us = co.window_us.load(std::memory_order_relaxed);
     const uint32_t last = co.last_size.load(std::memory_order_relaxed);
-    if (window_us > 0 && last > 1) {
+    if (window_us > 0 && last > 1 && !c.alone) {
         // callers woken together come back together: wait for as many as the previous batch held, at most the
         // window (spinning: a timed sleep of tens of microseconds wakes up 50 us late)
         const uint32_t target = std::min(last, b->cap.load(std::memory_order_relaxed));
@@ -167,7 +215,7 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
     }
     co.ns_window.fetch_add(ns_since(t_lead), std::memory_order_relaxed);
     const auto t_turn = sclk::now();
-    {
+    if (!c.alone) {
         std::unique_lock<SpinLock> lk(co.mu);
         while (co.in_flight >= co.depth) co.cv.wait(lk);
         co.in_flight++;
@@ -176,7 +224,7 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
             // the successor is published BEFORE this batch closes, so that arrivals always find an open batch without
             // the lock; it has no leader yet: whoever claims its slot 0 will be
             CoBatch *nx = co.take();
-            if (cobatch_open(h, *nx, co.cap, n, ef, 0) == HNSW_OK) {
+            if (cobatch_open(h, *nx, co.cap, c, 0) == HNSW_OK) {
                 co.open.push_back(nx);
                 co.fast.store(nx, std::memory_order_release);
             } else {
@@ -198,11 +246,13 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
             std::this_thread::yield();
         }
     }
-    co.last_size.store(nq, std::memory_order_relaxed);
-    co.n_batches.fetch_add(1, std::memory_order_relaxed);
-    co.n_queries.fetch_add(nq, std::memory_order_relaxed);
-    uint64_t mb = co.max_batch.load(std::memory_order_relaxed);
-    while (nq > mb && !co.max_batch.compare_exchange_weak(mb, nq)) {
+    if (!c.alone) co.last_size.store(nq, std::memory_order_relaxed);
+    if (!c.filtered) {  // (a filtered batch counts under filtered_one_calls / _batches, when it has been answered)
+        co.n_batches.fetch_add(1, std::memory_order_relaxed);
+        co.n_queries.fetch_add(nq, std::memory_order_relaxed);
+        uint64_t mb = co.max_batch.load(std::memory_order_relaxed);
+        while (nq > mb && !co.max_batch.compare_exchange_weak(mb, nq)) {
+        }
     }
     HostSearchPlan p = plan_host_search(nq, d, n, 0);  // the device arena and the result block are laid out for nq
     p.p_q = b->p_q;
@@ -213,9 +263,21 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
     const auto t_gpu = sclk::now();
     rc = hipSetDevice(h->dev.device) == hipSuccess ? HNSW_OK : HNSW_ERR_HIP;
     if (rc != HNSW_OK) set_error("hipSetDevice(%d) failed", h->dev.device);
-    if (rc == HNSW_OK && h->del.count) {
+    if (rc == HNSW_OK && c.filtered) {
+        // the batch's filter, stated once: the rows of the callers' set (or every id) and a label range per query, the
+        // staged arrays; the exact path of its groups in the grouped form
+        Filter f;
+        f.family = Filter::ONE_QUERY;
+        f.rows = c.set ? Filter::SET : Filter::ALL;
+        f.set = c.set;
+        f.mask_of = c.set ? reinterpret_cast<const uint32_t *>(pin + b->p_row) : nullptr;
+        f.K = 1;
+        f.lo = reinterpret_cast<const uint32_t *>(pin + b->p_lo);
+        f.hi = reinterpret_cast<const uint32_t *>(pin + b->p_hi);
+        rc = search_filtered(h, reinterpret_cast<const float *>(pin + p.p_q), nq, n, ef, f, false, nullptr, nullptr, nullptr,
+                             nullptr, b->paths.data(), pin + p.p_out, true);
+    } else if (rc == HNSW_OK && h->del.count) {
         // ids are deleted: the batch is answered as hnsw_search_batch answers it then, into the same result block
-        unsigned char *pin = static_cast<unsigned char *>(b->s.pin);
         rc = search_filtered(h, reinterpret_cast<const float *>(pin + p.p_q), nq, n, ef, Filter{}, false, nullptr, nullptr,
                              nullptr, nullptr, nullptr, pin + p.p_out);
     } else if (rc == HNSW_OK) {
@@ -223,11 +285,13 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
     }
     co.ns_gpu.fetch_add(ns_since(t_gpu), std::memory_order_relaxed);
     const auto t_hand = sclk::now();
-    {
-        std::lock_guard<SpinLock> g(co.mu);
-        co.in_flight--;
+    if (!c.alone) {
+        {
+            std::lock_guard<SpinLock> g(co.mu);
+            co.in_flight--;
+        }
+        co.cv.notify_all();
     }
-    co.cv.notify_all();
     int my;
     if (rc != HNSW_OK) {
         b->rc = rc;
@@ -238,6 +302,8 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
         for (uint32_t i = 0; i < nq; i++) {
             memcpy(b->reqs[i].ids, o.ids + (size_t)i * n, (size_t)n * 4);
             if (b->reqs[i].count) *b->reqs[i].count = o.counts[i];
+            if (b->reqs[i].dists) memcpy(b->reqs[i].dists, o.dists + (size_t)i * n, (size_t)n * 4);
+            if (b->reqs[i].path) *b->reqs[i].path = b->paths[i];
             b->status[i] = o.stats[i].status;
         }
         my = query_status_error(0, b->status[0]);
@@ -254,6 +320,23 @@ int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uin
     }
     co.ns_handout.fetch_add(ns_since(t_hand), std::memory_order_relaxed);
     return my;
+}
+
+}  // namespace
+
+int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uint32_t *ids, uint32_t *count) {
+    CoCall c{q, n, ef, ids, count};
+    return coalesced(h, c);
+}
+
+int search_filtered_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, hnsw_mask_set *set, uint32_t row,
+                              uint32_t lo, uint32_t hi, uint32_t *ids, float *dists, uint32_t *count, uint8_t *path, bool alone) {
+    CoCall c{q, n, ef, ids, count};
+    c.filtered = true;
+    c.set = set, c.row = row, c.lo = lo, c.hi = hi;
+    c.dists = dists, c.path = path;
+    c.alone = alone;
+    return coalesced(h, c);
 }
 
 }  // namespace hx

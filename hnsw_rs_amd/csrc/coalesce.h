@@ -13,6 +13,14 @@
 //   window:  a leader that has seen concurrency (the previous batch held more than one query) waits up to
 //            `window_us` for the callers that were woken together with it to come back; a lone caller never waits.
 //   depth:   at most `depth` batches are on the GPU at once; leaders beyond that keep collecting arrivals.
+//
+// One-query FILTERED calls (hnsw_search_filtered) gather the same way, in batches of their own: a batch's parameters
+// are (n, ef, dim, filtered?, set), and a caller joins only a batch whose parameters are its own.  A filtered slot
+// stages the caller's (row, lo, hi) next to its query; the leader states the batch's filter once -- the rows of `set`
+// (or every id), one label range per query, the staged arrays -- and answers it by search_filtered with the exact path
+// in its grouped form: the queries on the graph path share one launch whatever their filters, those on the exact path
+// three (search_host.cpp, exact_grouped).  With the window off (coalesce_us < 0) a filtered call still comes through
+// here, as a batch of its own that nobody else sees.
 #pragma once
 
 #include <linux/futex.h>
@@ -29,6 +37,7 @@
 #include "scratch.h"
 
 struct hnsw_index;
+struct hnsw_mask_set;
 
 namespace hx {
 
@@ -54,8 +63,10 @@ struct SpinLock {  // the slow paths' lock: a short spin, then sleep on the word
 struct CoBatch {
     SearchScratch s;
     size_t p_q = 0, p_out = 0;  // pinned arena offsets (HostSearchPlan for `cap` queries)
-    // (n, ef, dim, cap) of this incarnation; written before the word's generation is bumped, read by joiners
-    std::atomic<uint32_t> cap{0}, n{0}, ef{0}, dim{0};
+    size_t p_row = 0, p_lo = 0, p_hi = 0;  // a filtered batch: [queries | rows | lo | hi | result block]
+    // (n, ef, dim, cap, filtered, set) of this incarnation; written before the word's generation is bumped, read by joiners
+    std::atomic<uint32_t> cap{0}, n{0}, ef{0}, dim{0}, filtered{0};
+    std::atomic<void *> set{nullptr};
     // bits 0..15: slots claimed; bit 16: closed (no more joins); bits 32..63: generation (a batch is reused).
     // A joiner's compare-and-swap succeeds only on the word it read its parameters under.
     static constexpr uint64_t COUNT = 0xFFFFull, CLOSED = 1ull << 16, GEN = 1ull << 32;
@@ -66,6 +77,8 @@ struct CoBatch {
     std::atomic<uint32_t> filed{0};  // claimed slots whose query and request are in place
     struct Req {
         uint32_t *ids, *count;
+        float *dists;   // a filtered call's (or nullptr)
+        uint8_t *path;
     };
     std::vector<Req> reqs;
     // futex words, 0 = collecting / running, 1 = results handed out; callers spread over them by slot
@@ -78,6 +91,7 @@ struct CoBatch {
     int rc = HNSW_OK;                  // batch-level failure (launch, copy), with its text
     std::string err;
     std::vector<int32_t> status;       // per query
+    std::vector<uint8_t> paths;        // per query of a filtered batch
 };
 struct Coalescer {
     std::atomic<CoBatch *> fast{nullptr};  // the open batch callers try first (the latest parameters seen)
@@ -102,5 +116,10 @@ struct Coalescer {
 
 // hnsw_search through the coalescer (the arguments are checked by the caller)
 int search_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, uint32_t *ids, uint32_t *count);
+// hnsw_search_filtered through it: under row `row` of `set` (nullptr: no rows; HNSW_MASK_NONE: no row) AND the label range
+// [lo, hi].  alone: the call gathers nobody and waits for nobody (coalesce_us < 0, or parameters whose errors depend on
+// what else is in the batch)
+int search_filtered_coalesced(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, hnsw_mask_set *set, uint32_t row,
+                              uint32_t lo, uint32_t hi, uint32_t *ids, float *dists, uint32_t *count, uint8_t *path, bool alone);
 
 }  // namespace hx

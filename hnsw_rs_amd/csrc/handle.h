@@ -45,6 +45,9 @@ struct hnsw_index {
     // filtered search (hnsw_search_batch_filtered): a call whose allow-list holds at most filter_exact_max ids is
     // answered by the exact scan ("Filtered search", for the measured crossover); queries per path
     int64_t filter_exact_max = 65536;
+    // option "filter_exact_grouped": the batch entry points run a call's exact-path groups in the grouped form (three
+    // launches for all of them, search_host.cpp) instead of group by group; hnsw_search_filtered always does
+    int filter_exact_grouped = 0;
     std::atomic<uint64_t> n_filt_graph{0}, n_filt_exact{0}, n_filt_overflow{0};
     // hnsw_search_batch_filtered_multi: calls, and the masks their queries referenced (no mask counts as one)
     std::atomic<uint64_t> n_filt_multi_calls{0}, n_filt_multi_masks{0};
@@ -65,6 +68,8 @@ struct hnsw_index {
     std::atomic<uint64_t> n_filt_set_range_calls{0}, n_filt_set_range_groups{0};
     // hnsw_search_batch_filtered_ranges: calls, and the distinct canonical range lists they named
     std::atomic<uint64_t> n_filt_ranges_calls{0}, n_filt_ranges_groups{0};
+    // hnsw_search_filtered: calls answered, and the launches of their leaders (coalesce.h)
+    std::atomic<uint64_t> n_filt_one_calls{0}, n_filt_one_batches{0};
     // hnsw_search_batch_shards with this handle as shard 0: calls whose shards were all searched, and their merges launched
     std::atomic<uint64_t> n_shard_calls{0}, n_shard_merges{0};
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")

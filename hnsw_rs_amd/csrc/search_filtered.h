@@ -8,8 +8,9 @@
 // every id below none_bits.  The rows may be a resident mask set's (mask_set.h), and mask_of may then come from the
 // caller's device memory, unseen by the host: the graph kernel checks it against n_masks and answers a query that
 // names a row beyond it with status HNSW_ERR_ARG before it reads a mask word.  Only the graph kernel reads mask_of: the
-// exact path's kernels are launched per mask with allow at that mask's row.  The handle's deleted set (hnsw_mark_deleted) is a second mask of the same
-// layout, deny: an id is admissible iff it is allowed and not denied.
+// exact path's kernels are launched per mask with allow at that mask's row, or, in the grouped form (ExactGroup, below), once
+// for all masks with every group's row in its record.  The handle's deleted set (hnsw_mark_deleted) is a second mask of
+// the same layout, deny: an id is admissible iff it is allowed and not denied.
 //
 // A label range (hnsw_search_batch_filtered_range) is a third filter, in place of the allow-list: labels is the handle's
 // resident label column (labels.h), one uint32 per id, and id i is allowed iff i < allow_bits and lo <= label(i) <= hi,
@@ -94,6 +95,33 @@ struct MergeLists {
     uint32_t base[HX_MERGE_MAX_SHARDS], stride[HX_MERGE_MAX_SHARDS];
 };
 
+// The grouped form of the exact path: the exact-path groups of a call in ONE compaction, ONE scan
+// and ONE merge launch.  What differs from group to group travels in two device tables instead of the kernels' scalars;
+// with a nullptr table every kernel is the per-group form above.
+//   ExactGroup, one per compacted group (the compaction's blockIdx.y): the group's row of mask words (nullptr: none), its
+//   id bound, its label range (ranged == 0: the group has no range and no label is read), its word offsets and the list
+//   it writes.  A block at or beyond the group's words exits.
+//   ExactQuery, one per selected query (the scan's blockIdx.y, the merge's blockIdx.x): the list its group's admissible
+//   ids are in (compacted by this call, or a resident set's cached one), A, and where its partial lists are: nseg of them
+//   from row `part` of the call's partial keys and statuses, packed as (part << 9) | nseg (nseg <= 256, part < 2^23).  A
+//   scan block whose segment is at or beyond nseg exits.
+struct ExactGroup {
+    const uint64_t *allow;
+    const uint32_t *word_base;
+    uint32_t *ids;
+    uint64_t allow_bits;
+    uint32_t lo, hi;
+    uint32_t ranged, pad;
+};
+struct ExactQuery {
+    const uint32_t *ids;
+    uint32_t A;
+    uint32_t seg;
+};
+static_assert(sizeof(ExactQuery) == 16 && sizeof(ExactGroup) == 48, "the tables' records are read as they are laid out here");
+#define HX_FILT_SEG_BITS 9
+#define HX_FILT_MAX_PART_ROWS (1u << (32 - HX_FILT_SEG_BITS))
+
 // ids a layer-0 visited table of 2^slots_log2 slots holds before the graph path reports HNSW_ERR_OVERFLOW
 __host__ __device__ inline uint32_t filt_visited_limit(uint32_t slots_log2) { return (1u << slots_log2) - (1u << (slots_log2 - 2)); }
 // first table size for ef' (the generic kernel's choice) and the largest one the dimension leaves room for in LDS
@@ -120,6 +148,14 @@ int launch_filter_compact(const FilterArgs &a, uint64_t n_words, const uint32_t 
 uint32_t filt_exact_segments(uint64_t A, uint32_t nsel);
 int launch_filtered_exact(const DevView &v, const FilterArgs &a, uint32_t nsel, const uint32_t *ids, uint32_t A,
                           uint32_t nseg, unsigned long long *part, int32_t *part_status, hipStream_t stream);
+// the grouped form: `ngroups` groups compacted in one launch (the widest has max_words words), then the `nsel` queries of
+// a.qsel scanned and merged in one launch each, every query over its own list (qtab[y]; max_nseg: the most segments any
+// of them has).  a carries what the groups share: the rows' base is not read (a group's row is in its record), the label
+// column, the deleted set, n, Q, the outputs.
+int launch_filter_compact_grouped(const FilterArgs &a, const ExactGroup *gtab, uint32_t ngroups, uint64_t max_words,
+                                  hipStream_t stream);
+int launch_filtered_exact_grouped(const DevView &v, const FilterArgs &a, uint32_t nsel, const ExactQuery *qtab,
+                                  uint32_t max_nseg, unsigned long long *part, int32_t *part_status, hipStream_t stream);
 // the top n (1 <= n <= HX_FILT_MAX_N) by (distance bits, global id) of m.nq queries over the lists of m.n_shards shards:
 // ONE launch of hx_filt_merge_kernel in its shard-list form, one wave per query.  out_counts may be nullptr; out_stats
 // goes with m.stats.  A query some shard answered with a status other than HNSW_OK gets that status (the lowest-numbered

@@ -552,9 +552,34 @@ __global__ void __launch_bounds__(64) hx_filt_graph_kernel(const DevView v, cons
 // own word would touch 64 lines per wave instruction: the gather shape of DESIGN.md section 10.)  Under a range AND a
 // mask (a.labels and a.allow) the word made from the labels is ANDed with the mask's.
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) hx_filt_compact_kernel(const FilterArgs a, uint64_t n_words,
-                                                             const uint32_t *word_base, uint32_t *ids, const RangeList rl) {
+//
+// The grouped form (gtab set; search_filtered.h): blockIdx.y is the group, and what a launch of the per-group form has in
+// its arguments -- the row, the id bound, the range, the offsets and the list -- comes from the group's record, read once
+// with scalar loads (the block's own).  A block at or beyond its group's words exits before it reads an offset.
+struct CompactSite {
+    const uint64_t *allow;
+    const uint32_t *labels, *word_base;
+    uint32_t *ids;
+    uint64_t allow_bits, n_words;
+    uint32_t lo, hi;
+};
+__global__ void __launch_bounds__(64) hx_filt_compact_kernel(const FilterArgs fa, uint64_t n_words,
+                                                             const uint32_t *word_base, uint32_t *ids, const RangeList rl,
+                                                             const ExactGroup *gtab) {
     const int lane = threadIdx.x;
+    CompactSite a{fa.allow, fa.labels, word_base, ids, fa.allow_bits, n_words, fa.lo, fa.hi};
+    if (gtab) {
+        const ExactGroup g = gtab[blockIdx.y];
+        a.allow = g.allow;
+        a.labels = g.ranged ? fa.labels : nullptr;
+        a.word_base = g.word_base;
+        a.ids = g.ids;
+        a.allow_bits = g.allow_bits;
+        a.n_words = (g.allow_bits + 63) / 64;
+        a.lo = g.lo, a.hi = g.hi;
+        if ((uint64_t)blockIdx.x * 64 >= a.n_words) return;
+    }
+    n_words = a.n_words;
     const uint64_t w = (uint64_t)blockIdx.x * 64 + lane;
     u64 bits = 0;
     if (a.labels) {
@@ -562,7 +587,7 @@ __global__ void __launch_bounds__(64) hx_filt_compact_kernel(const FilterArgs a,
             const uint64_t id0 = (uint64_t)blockIdx.x * 4096 + lane;
             for (int j = 0; j < 64; j++) {
                 const uint64_t id = id0 + 64 * j;
-                const uint32_t label = id < a.label_len ? a.labels[id] : 0u;
+                const uint32_t label = id < fa.label_len ? a.labels[id] : 0u;
                 bool any = false;
                 for (uint32_t k = 0; k < rl.n; k++) any |= label - rl.lo[k] <= rl.hi[k] - rl.lo[k];
                 const u64 in = __ballot(any);
@@ -573,7 +598,7 @@ __global__ void __launch_bounds__(64) hx_filt_compact_kernel(const FilterArgs a,
 #pragma unroll 8
             for (int j = 0; j < 64; j++) {
                 const uint64_t id = id0 + 64 * j;
-                const uint32_t label = id < a.label_len ? a.labels[id] : 0u;
+                const uint32_t label = id < fa.label_len ? a.labels[id] : 0u;
                 const u64 in = __ballot(label >= a.lo && label <= a.hi);
                 if (lane == j) bits = in;
             }
@@ -589,7 +614,7 @@ __global__ void __launch_bounds__(64) hx_filt_compact_kernel(const FilterArgs a,
         const uint64_t keep = a.allow_bits > w * 64 ? a.allow_bits - w * 64 : 0;
         bits &= keep >= 64 ? ~0ull : ((1ull << keep) - 1);
     }
-    if (a.deny && w * 64 < a.deny_bits) bits &= ~a.deny[w];  // (deny_bits is a multiple of 64)
+    if (fa.deny && w * 64 < fa.deny_bits) bits &= ~fa.deny[w];  // (deny_bits is a multiple of 64)
     const uint32_t c = (uint32_t)__popcll(bits);
     uint32_t incl = c;  // inclusive prefix over the lanes
 #pragma unroll
@@ -597,23 +622,35 @@ __global__ void __launch_bounds__(64) hx_filt_compact_kernel(const FilterArgs a,
         const uint32_t y = (uint32_t)__shfl_up((int)incl, o);
         if (lane >= o) incl += y;
     }
-    uint32_t pos = word_base[blockIdx.x] + incl - c;
+    uint32_t pos = a.word_base[blockIdx.x] + incl - c;
     while (bits) {
         const int b = __ffsll((long long)bits) - 1;
         bits &= bits - 1;
-        ids[pos++] = (uint32_t)(w * 64 + b);
+        a.ids[pos++] = (uint32_t)(w * 64 + b);
     }
 }
 
-// Scan: block (seg, y) keeps the n best of query y's segment of the list; part[(y nseg + seg) n + i].
+// Scan: block (seg, y) keeps the n best of query y's segment of the list; part[(y nseg + seg) n + i].  The grouped form
+// (qtab set): the list, A and nseg are query y's own (its record, one 16-byte scalar read), its partial lists start at
+// row rec.seg >> HX_FILT_SEG_BITS instead of y nseg, and a block beyond its query's segments exits.
 template <int KIND>
 __global__ void __launch_bounds__(64) hx_filt_scan_kernel(const DevView v, const FilterArgs a, const uint32_t *ids,
-                                                          uint32_t A, uint32_t nseg, u64 *part, int32_t *part_status) {
+                                                          uint32_t A, uint32_t nseg, u64 *part, int32_t *part_status,
+                                                          const ExactQuery *qtab) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u64 *perm = reinterpret_cast<u64 *>(smem);
     float *yq = reinterpret_cast<float *>(perm + 64);
     const int lane = threadIdx.x;
     const uint32_t seg = blockIdx.x, y = blockIdx.y;
+    size_t row = (size_t)y * nseg + seg;  // of part and part_status
+    if (qtab) {
+        const ExactQuery rec = qtab[y];
+        ids = rec.ids;
+        A = rec.A;
+        nseg = rec.seg & ((1u << HX_FILT_SEG_BITS) - 1);
+        if (seg >= nseg) return;
+        row = (size_t)(rec.seg >> HX_FILT_SEG_BITS) + seg;
+    }
     const uint32_t q = a.qsel ? a.qsel[y] : y;
     constexpr int LPC = (KIND == HNSW_VEC_QUANT8) ? 2 : 1;
     constexpr int CHUNK = 64 / LPC;
@@ -638,8 +675,8 @@ __global__ void __launch_bounds__(64) hx_filt_scan_kernel(const DevView v, const
         bad = __ballot(bad) != 0;
         wl.merge(key, a.n, perm, lane);
     }
-    if ((uint32_t)lane < a.n) part[((size_t)y * nseg + seg) * a.n + lane] = wl.L[0];
-    if (lane == 0) part_status[(size_t)y * nseg + seg] = bad ? HNSW_ERR_NAN_INPUT : HNSW_OK;
+    if ((uint32_t)lane < a.n) part[row * a.n + lane] = wl.L[0];
+    if (lane == 0) part_status[row] = bad ? HNSW_ERR_NAN_INPUT : HNSW_OK;
 }
 
 // The merge kernel's shard-list form (MergeLists, search_filtered.h): query blockIdx.x's lists of the m.n_shards shards,
@@ -699,10 +736,11 @@ __device__ __forceinline__ void merge_shard_lists(const FilterArgs &a, const Mer
 }
 
 // Merge: one wave per query folds the nseg partial lists into its top n and writes the results.  With m.ids set the
-// lists are those of m.n_shards shards instead (merge_shard_lists; A, nseg, part and part_status are not read).
+// lists are those of m.n_shards shards instead (merge_shard_lists; A, nseg, part and part_status are not read).  With
+// qtab set (the grouped form) A, nseg and the first row of the query's partial lists are its record's.
 __global__ void __launch_bounds__(64) hx_filt_merge_kernel(const FilterArgs a, uint32_t A, uint32_t nseg,
                                                            const u64 *part, const int32_t *part_status,
-                                                           const MergeLists m) {
+                                                           const MergeLists m, const ExactQuery *qtab) {
     __shared__ u64 perm[64];
     const int lane = threadIdx.x;
     if (m.ids) {  // (a kernel argument: the branch is the wave's)
@@ -711,11 +749,18 @@ __global__ void __launch_bounds__(64) hx_filt_merge_kernel(const FilterArgs a, u
     }
     const uint32_t y = blockIdx.x;
     const uint32_t q = a.qsel ? a.qsel[y] : y;
+    size_t row0 = (size_t)y * nseg;
+    if (qtab) {
+        const ExactQuery rec = qtab[y];
+        A = rec.A;
+        nseg = rec.seg & ((1u << HX_FILT_SEG_BITS) - 1);
+        row0 = rec.seg >> HX_FILT_SEG_BITS;
+    }
     FList<1> wl;
     wl.clear();
     bool bad = false;
     for (uint32_t s = 0; s < nseg; s++) {
-        const size_t o = (size_t)y * nseg + s;
+        const size_t o = row0 + s;
         bad |= part_status[o] != HNSW_OK;
         wl.merge((uint32_t)lane < a.n ? part[o * a.n + lane] : FKEY_INVALID, a.n, perm, lane);
     }
@@ -797,7 +842,20 @@ int launch_filter_compact(const FilterArgs &a, uint64_t n_words, const uint32_t 
     }
     const uint64_t nb = (n_words + 63) / 64;
     return launch_checked({"filter compaction kernel launch"}, hx_filt_compact_kernel, dim3((uint32_t)nb), dim3(64), 0, stream, a,
-                          n_words, word_base, ids, list ? *list : RangeList{});
+                          n_words, word_base, ids, list ? *list : RangeList{}, static_cast<const ExactGroup *>(nullptr));
+}
+
+int launch_filter_compact_grouped(const FilterArgs &a, const ExactGroup *gtab, uint32_t ngroups, uint64_t max_words,
+                                  hipStream_t stream) {
+    if (ngroups == 0 || max_words == 0) return HNSW_OK;
+    if (!gtab || ngroups > 65535) {
+        set_error("filter compaction: the grouped form needs its table and at most 65535 groups per launch");
+        return HNSW_ERR_ARG;
+    }
+    const uint64_t nb = (max_words + 63) / 64;
+    return launch_checked({"filter compaction kernel launch"}, hx_filt_compact_kernel, dim3((uint32_t)nb, ngroups), dim3(64), 0,
+                          stream, a, (uint64_t)0, static_cast<const uint32_t *>(nullptr), static_cast<uint32_t *>(nullptr),
+                          RangeList{}, gtab);
 }
 
 uint32_t filt_exact_segments(uint64_t A, uint32_t nsel) {
@@ -818,10 +876,27 @@ int launch_filtered_exact(const DevView &v, const FilterArgs &a, uint32_t nsel, 
     const LaunchSite site{"filtered exact search launch"};
     if (int rc = launch_checked(site, v.kind == HNSW_VEC_QUANT8 ? hx_filt_scan_kernel<HNSW_VEC_QUANT8> : hx_filt_scan_kernel<HNSW_VEC_F32>,
                                 dim3(nseg, nsel), dim3(64), 64 * 8 + (size_t)query_lds_bytes(v), stream, v, a, ids, A, nseg, part,
-                                part_status))
+                                part_status, static_cast<const ExactQuery *>(nullptr)))
         return rc;
     return launch_checked(site, hx_filt_merge_kernel, dim3(nsel), dim3(64), 0, stream, a, A, nseg, part, part_status,
-                          MergeLists{});
+                          MergeLists{}, static_cast<const ExactQuery *>(nullptr));
+}
+
+int launch_filtered_exact_grouped(const DevView &v, const FilterArgs &a, uint32_t nsel, const ExactQuery *qtab,
+                                  uint32_t max_nseg, unsigned long long *part, int32_t *part_status, hipStream_t stream) {
+    if (nsel == 0) return HNSW_OK;
+    if (a.n == 0 || a.n > HX_FILT_MAX_N || nsel > 65535 || max_nseg == 0 || max_nseg >= (1u << HX_FILT_SEG_BITS) || !qtab || !a.qsel) {
+        set_error("filtered exact search: the grouped form needs 1 <= n <= %d, at most 65535 queries per launch and its table",
+                  HX_FILT_MAX_N);
+        return HNSW_ERR_ARG;
+    }
+    const LaunchSite site{"filtered exact search launch"};
+    if (int rc = launch_checked(site, v.kind == HNSW_VEC_QUANT8 ? hx_filt_scan_kernel<HNSW_VEC_QUANT8> : hx_filt_scan_kernel<HNSW_VEC_F32>,
+                                dim3(max_nseg, nsel), dim3(64), 64 * 8 + (size_t)query_lds_bytes(v), stream, v, a,
+                                static_cast<const uint32_t *>(nullptr), 0u, 0u, part, part_status, qtab))
+        return rc;
+    return launch_checked(site, hx_filt_merge_kernel, dim3(nsel), dim3(64), 0, stream, a, 0u, 0u, part, part_status,
+                          MergeLists{}, qtab);
 }
 
 int launch_merge_lists(const MergeLists &m, uint32_t n, uint32_t *out_ids, float *out_dists, uint32_t *out_counts,
@@ -840,7 +915,8 @@ int launch_merge_lists(const MergeLists &m, uint32_t n, uint32_t *out_ids, float
     a.out_counts = out_counts;
     a.out_stats = out_stats;
     return launch_checked({"shard merge kernel launch"}, hx_filt_merge_kernel, dim3(m.nq), dim3(64), 0, stream, a, 0u, 0u,
-                          static_cast<const u64 *>(nullptr), static_cast<const int32_t *>(nullptr), m);
+                          static_cast<const u64 *>(nullptr), static_cast<const int32_t *>(nullptr), m,
+                          static_cast<const ExactQuery *>(nullptr));
 }
 
 }  // namespace hx

@@ -235,19 +235,30 @@ void bind_labels(const hnsw_index *h, FilterArgs &a) {
 
 // The exact path's scratch from `base` in a device arena: [word offsets | admissible ids | partial keys | partial
 // statuses], for launches of up to nsel_max queries over up to A_max admissible ids (n_wbase word offsets in all)
+// The grouped form (exact_grouped) adds [the pass's tables], and its lists lie one behind the other in the ids' room:
+// ids_grouped, the ids a pass should have room for (0: the per-group form alone); a pass that needs more is cut in two.
 struct ExactScratch {
-    size_t o_wb = 0, o_ids = 0, o_part = 0, o_pst = 0, end = 0;
+    size_t o_wb = 0, o_ids = 0, o_part = 0, o_pst = 0, o_tab = 0, end = 0;
+    uint64_t ids_cap = 0, rows_cap = 0;
     ExactScratch() = default;
-    ExactScratch(size_t base, uint64_t nsel_max, uint32_t n, uint64_t A_max, size_t n_wbase) {
+    ExactScratch(size_t base, uint64_t nsel_max, uint32_t n, uint64_t A_max, size_t n_wbase, uint64_t ids_grouped = 0) {
         // chunk x nseg of any launch within those limits (filt_exact_segments: at most 256 segments, and at most
         // 262144 blocks unless the queries alone are more)
         const uint64_t N = std::min<uint64_t>(nsel_max, 65535), s = filt_exact_segments(A_max, 1);
+        // (a grouped pass of T <= N queries stays within them as well: every group's segments are chosen for T queries)
         const uint64_t rows = std::min<uint64_t>(N * s, std::max<uint64_t>(262144, N));
+        ids_cap = std::max(A_max, ids_grouped);
+        rows_cap = rows;
         o_wb = base;
         o_ids = o_wb + align256(n_wbase * 4);
-        o_part = o_ids + align256(A_max * 4);
+        o_part = o_ids + align256(ids_cap * 4);
         o_pst = o_part + align256((size_t)rows * n * 8);
-        end = o_pst + align256((size_t)rows * 4);
+        o_tab = o_pst + align256((size_t)rows * 4);
+        end = o_tab + (ids_grouped ? tab_bytes(N, N) : 0);
+    }
+    // a pass's tables: [a record per query | its selection | a record per compacted group]
+    static size_t tab_bytes(uint64_t nsel, uint64_t ngroups) {
+        return align256(nsel * sizeof(ExactQuery)) + align256(nsel * 4) + align256(ngroups * sizeof(ExactGroup));
     }
 };
 
@@ -573,6 +584,136 @@ int exact_group(const FilterSource &src, const Group &g, const uint32_t *d_sel, 
                           g.d_list, &ranges);
 }
 
+// ---- the grouped form of the exact path -----------------------------------------------------
+// Many small groups -- a coalesced batch of one-query calls, each under its tenant's filter -- cost three dependent
+// launches each in the form above.  Here the groups of a pass share them: ONE compaction whose blockIdx.y is the group,
+// ONE scan and ONE merge over every query of every group, each query under its own list.  What a launch has in its
+// scalars otherwise is in two tables in the arena (ExactGroup, ExactQuery: search_filtered.h), written on the host and
+// sent up in one copy with the pass's selection.  The lists lie one behind the other in the ids' room; a group whose
+// list a resident set holds contributes it by pointer and is not compacted; one without admissible ids is not either; one
+// under K > 1 ranges keeps a compaction launch of its own (its RangeList travels by value) and shares the other two.  The
+// results are those of the per-group form bit for bit: the top n keys of a list do not depend on how it was cut.
+struct PassItem {
+    Group g;                // (g.wb is not read: the offsets are wbs / d_wb)
+    const uint32_t *sel;    // its queries, on the host ...
+    const uint32_t *d_sel;  // ... and on the device (read when the group has to go by itself)
+    const uint32_t *wbs;    // its word offsets on the host, and their place on the device
+    uint32_t *d_wb;
+    bool send;              // they are not there yet ...
+    int from;               // ... and go up with those of the pass's other groups from the same host array (0 or 1)
+};
+
+int exact_grouped(const FilterSource &src, std::vector<PassItem> &items, const ExactPlace &at,
+                  std::vector<std::vector<unsigned char>> &keep) {
+    hnsw_index *h = src.h;
+    const DevView &v = h->dev.view;
+    uint64_t total = 0;
+    for (const PassItem &it : items) total += it.g.nq;
+    const uint32_t shape = (uint32_t)std::min<uint64_t>(total, 65535);
+    uint32_t *d_ids0 = reinterpret_cast<uint32_t *>(at.dv + at.x.o_ids);
+    auto compacts = [](const PassItem &it) { return !it.g.d_list && it.g.A > 0; };
+    size_t i0 = 0;
+    while (i0 < items.size()) {
+        // the pass: as many groups from i0 as the launch limits and the rooms take
+        uint64_t nsel = 0, rows = 0, ids = 0;
+        size_t i1 = i0;
+        for (; i1 < items.size(); i1++) {
+            const Group &g = items[i1].g;
+            const uint64_t r = g.nq * filt_exact_segments(g.A, shape), a = compacts(items[i1]) ? g.A : 0;
+            if (nsel + g.nq > 65535 || rows + r > std::min<uint64_t>(at.x.rows_cap, HX_FILT_MAX_PART_ROWS - 1) || ids + a > at.x.ids_cap) break;
+            nsel += g.nq, rows += r, ids += a;
+        }
+        if (i1 == i0) {  // a group no pass takes: by itself, in the per-group form
+            PassItem &it = items[i0++];
+            ExactPlace p = at;
+            p.wbs = it.wbs, p.d_wb = it.d_wb, p.send = it.send;
+            it.g.wb = 0;
+            if (int r = exact_group(src, it.g, it.d_sel, it.g.nq, p)) return r;
+            continue;
+        }
+        const size_t o_sel = align256(nsel * sizeof(ExactQuery)), o_gt = o_sel + align256(nsel * 4);
+        keep.emplace_back(o_gt + (i1 - i0) * sizeof(ExactGroup));
+        unsigned char *blob = keep.back().data();
+        ExactQuery *qt = reinterpret_cast<ExactQuery *>(blob);
+        uint32_t *sel = reinterpret_cast<uint32_t *>(blob + o_sel);
+        ExactGroup *gt = reinterpret_cast<ExactGroup *>(blob + o_gt);
+        uint32_t ngt = 0, max_nseg = 1;
+        uint64_t y = 0, row = 0, at_id = 0, max_words = 0;
+        // the spans of host offsets that go up, one copy per host array (its groups' places on the device mirror it)
+        const uint32_t *send_lo[2] = {nullptr, nullptr}, *send_hi[2] = {nullptr, nullptr};
+        uint32_t *send_to[2] = {nullptr, nullptr};
+        for (size_t i = i0; i < i1; i++) {
+            const PassItem &it = items[i];
+            const Group &g = it.g;
+            const uint32_t nseg = filt_exact_segments(g.A, shape);
+            const uint32_t *list = g.d_list ? g.d_list : d_ids0 + at_id;
+            max_nseg = std::max(max_nseg, nseg);
+            if (compacts(it)) {
+                const FilterArgs ax = src.args(g);
+                const RangeList ranges = src.range_list(g);
+                if (it.send) {
+                    // (the groups of a pass have their offsets in one host array, a place apart on the device as there)
+                    const int f = it.from;
+                    if (!send_lo[f] || it.wbs < send_lo[f]) send_lo[f] = it.wbs, send_to[f] = it.d_wb;
+                    if (!send_hi[f] || it.wbs + g.n_wb > send_hi[f]) send_hi[f] = it.wbs + g.n_wb;
+                    if (src.set && src.has_words(g.key) && !src.ranged(g)) h->n_set_compactions.fetch_add(1, std::memory_order_relaxed);
+                }
+                if (ranges.n > 1) {  // (after the offsets are up: below)
+                } else {
+                    ExactGroup &e = gt[ngt++];
+                    e.allow = ax.allow;
+                    e.word_base = it.d_wb;
+                    e.ids = d_ids0 + at_id;
+                    e.allow_bits = ax.allow_bits;
+                    e.lo = ax.lo, e.hi = ax.hi;
+                    e.ranged = ax.labels != nullptr;
+                    e.pad = 0;
+                    max_words = std::max<uint64_t>(max_words, (ax.allow_bits + 63) / 64);
+                }
+                at_id += g.A;
+            }
+            for (size_t k = 0; k < g.nq; k++, y++) {
+                qt[y].ids = list;
+                qt[y].A = (uint32_t)g.A;
+                qt[y].seg = (uint32_t)(row << HX_FILT_SEG_BITS) | nseg;
+                sel[y] = it.sel[k];
+                row += nseg;
+            }
+        }
+        unsigned char *d_tab = at.dv + at.x.o_tab;
+        HIP_TRY(hipMemcpyAsync(d_tab, blob, o_gt + ngt * sizeof(ExactGroup), hipMemcpyHostToDevice, at.stream));
+        for (int f = 0; f < 2; f++)
+            if (send_lo[f])
+                HIP_TRY(hipMemcpyAsync(send_to[f], send_lo[f], (size_t)(send_hi[f] - send_lo[f]) * 4, hipMemcpyHostToDevice, at.stream));
+        FilterArgs a = src.base;  // what the groups share; a group's row and range are in its record
+        a.mask_of = nullptr;
+        a.allow = nullptr;
+        a.range_lo = a.range_hi = nullptr;
+        a.lo = a.hi = 0;
+        a.n_ranges = 0;
+        a.qsel = reinterpret_cast<const uint32_t *>(d_tab + o_sel);
+        int r = launch_filter_compact_grouped(a, reinterpret_cast<const ExactGroup *>(d_tab + o_gt), ngt, max_words, at.stream);
+        at_id = 0;
+        for (size_t i = i0; r == HNSW_OK && i < i1; i++) {
+            if (!compacts(items[i])) continue;
+            const Group &g = items[i].g;
+            const RangeList ranges = src.range_list(g);
+            if (ranges.n > 1) {
+                const FilterArgs ax = src.args(g);
+                r = launch_filter_compact(ax, (ax.allow_bits + 63) / 64, items[i].d_wb, d_ids0 + at_id, at.stream, &ranges);
+            }
+            at_id += g.A;
+        }
+        if (r == HNSW_OK)
+            r = launch_filtered_exact_grouped(v, a, (uint32_t)nsel, reinterpret_cast<const ExactQuery *>(d_tab), max_nseg,
+                                              reinterpret_cast<unsigned long long *>(at.dv + at.x.o_part),
+                                              reinterpret_cast<int32_t *>(at.dv + at.x.o_pst), at.stream);
+        if (r != HNSW_OK) return r;
+        i0 = i1;
+    }
+    return HNSW_OK;
+}
+
 // Path 2: the queries of `sel` filled the largest visited table and are answered by the exact path, each under its own
 // filter, group by group; then `fetch`, which synchronises.  The host form comes with its plan (`planned`, ascending
 // key; shape_nsel; `at`: its arena, laid out up front because the queries and the result block live in it, with the
@@ -583,13 +724,14 @@ int exact_group(const FilterSource &src, const Group &g, const uint32_t *d_sel, 
 template <class Fetch>
 int path2(const FilterSource &src, const std::vector<uint32_t> &sel, std::vector<uint8_t> &path,
           const std::vector<Group> *planned, uint64_t shape_nsel, ExactPlace at, uint32_t *d_sel, size_t spare,
-          ScratchLease *grow, size_t pin_bytes, Fetch fetch) {
+          ScratchLease *grow, size_t pin_bytes, Fetch fetch, bool grouping) {
     std::vector<uint32_t> sel2 = sel, wb_late;
     std::vector<Group> runs = group_by_key(sel2, src);
     for (uint32_t i : sel) path[i] = 2;
     FilterSource::Locks lock;  // (a set's stays until the end: its lists are read by the launches)
     std::vector<bool> late(runs.size(), false);
-    uint64_t A_max = 0;
+    grouping = grouping && runs.size() > 1;  // (grouped: the late groups' offsets lie one behind the other, as in wb_late)
+    uint64_t A_max = 0, A_sum = 0;
     size_t n_wb = 0;
     for (size_t k = 0; k < runs.size(); k++) {
         Group &g = runs[k];
@@ -604,11 +746,13 @@ int path2(const FilterSource &src, const std::vector<uint32_t> &sel, std::vector
             late[k] = true;
         }
         A_max = std::max(A_max, g.A);
+        A_sum += g.d_list ? 0 : g.A;
         n_wb = std::max(n_wb, g.n_wb);
     }
     if (lock.lab.owns_lock()) lock.lab.unlock();  // (the column's: never across a sync)
     if (grow) {
-        at.x = ExactScratch(align256(sel2.size() * 4), sel2.size(), src.base.n, A_max, n_wb);
+        at.x = ExactScratch(align256(sel2.size() * 4), sel2.size(), src.base.n, A_max, grouping ? wb_late.size() : n_wb,
+                            grouping ? std::max<uint64_t>(A_sum, 1) : 0);
         int r = grow->prepare(src.h->dev.device, at.x.end, pin_bytes);
         if (r != HNSW_OK) return r;
         at.dv = static_cast<unsigned char *>(grow->s->dev);
@@ -617,6 +761,21 @@ int path2(const FilterSource &src, const std::vector<uint32_t> &sel, std::vector
         spare = 0;
     }
     HIP_TRY(hipMemcpyAsync(d_sel, sel2.data(), sel2.size() * 4, hipMemcpyHostToDevice, at.stream));
+    std::vector<std::vector<unsigned char>> keep;
+    if (grouping) {  // one more pass of the grouped form
+        std::vector<PassItem> items;
+        for (size_t k = 0; k < runs.size(); k++) {
+            const Group &g = runs[k];
+            if (late[k])
+                items.push_back({g, sel2.data() + g.q0, d_sel + g.q0, wb_late.data() + g.wb, at.d_wb + spare + g.wb, true, 1});
+            else
+                items.push_back({g, sel2.data() + g.q0, d_sel + g.q0, at.wbs + g.wb, at.d_wb + g.wb, at.send, 0});
+        }
+        int r = exact_grouped(src, items, at, keep);
+        if (r != HNSW_OK) return r;
+        const hnsw_query_stats *unused;
+        return fetch(unused);  // (synchronises: `sel2`, `wb_late` and the tables live until then)
+    }
     for (size_t k = 0; k < runs.size(); k++) {
         Group g = runs[k];
         ExactPlace p = at;
@@ -648,6 +807,11 @@ void count_call(hnsw_index *h, Filter::Family family, uint64_t n_graph, uint64_t
         case Filter::RANGE: calls = &h->n_filt_range_calls, groups = &h->n_filt_range_ranges; break;
         case Filter::SET_RANGE: calls = &h->n_filt_set_range_calls, groups = &h->n_filt_set_range_groups; break;
         case Filter::RANGES: calls = &h->n_filt_ranges_calls, groups = &h->n_filt_ranges_groups; break;
+        // (hnsw_search_filtered: `calls` are its leaders' launches, and every query of one is a call answered)
+        case Filter::ONE_QUERY:
+            calls = &h->n_filt_one_batches;
+            h->n_filt_one_calls.fetch_add(n_graph + n_exact + n_overflow, std::memory_order_relaxed);
+            break;
         default: break;
     }
     if (calls) calls->fetch_add(1, std::memory_order_relaxed);
@@ -665,7 +829,7 @@ int check_filter(const Filter &f) {
 
 int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f,
                     bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
-                    uint8_t *paths, void *pin_block) {
+                    uint8_t *paths, void *pin_block, bool grouped) {
     int rc = check_search_args(h, ef);
     if (rc != HNSW_OK || (rc = check_filter(f))) return rc;
     if (nq == 0) return HNSW_OK;
@@ -752,8 +916,19 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     const size_t o_q = 0, o_mask = o_q + align256(nq * d * 4), o_mof = o_mask + align256(up_words * 8);
     const size_t o_lo = o_mof + (rowed ? align256(nq * 4) : 0), o_hi = o_lo + (ranged ? align256(nq * rk * 4) : 0);
     const size_t o_sel = o_hi + (ranged ? align256(nq * rk * 4) : 0), o_xsel = o_sel + align256(nq * 4);
-    const size_t wb_lazy = ranged ? std::max<uint64_t>(1, ((src.len + 63) / 64 + 63) / 64) : 0;
-    const ExactScratch x(o_xsel + align256(multi ? nq * 4 : 0), nq, n, A_max, wb_all.size() + wb_lazy);
+    // The grouped form of the exact path (exact_grouped): the lists of a pass's groups lie one behind the other, so the
+    // ids' room is that of the planned pass, and of a path 2 pass up to 4 Mi ids (one that needs more is cut); the late
+    // offsets of a path 2 pass lie one behind the other as well, a group's worth for every group not counted yet
+    const bool grouping = multi && groups.size() > 1 && (grouped || h->filter_exact_grouped);
+    uint64_t ids_grouped = 0, ids_late = 0, n_late = 0, n_exact_groups = 0;
+    for (const Group &g : groups) {
+        if (g.exact) ids_grouped += g.A, n_exact_groups++;
+        if (!g.exact) ids_late += g.A == UNCOUNTED ? g.A_ub : g.A;
+        if (g.wb == NO_WB) n_late++;
+    }
+    ids_grouped = grouping ? std::max<uint64_t>({ids_grouped, std::min<uint64_t>(ids_late, 4u << 20), 1}) : 0;
+    const size_t wb_lazy = ranged ? std::max<uint64_t>(1, ((src.len + 63) / 64 + 63) / 64) * (grouping ? std::max<uint64_t>(1, n_late) : 1) : 0;
+    const ExactScratch x(o_xsel + align256(multi ? nq * 4 : 0), nq, n, A_max, wb_all.size() + wb_lazy, ids_grouped);
     const size_t o_out = x.end;
     const ResultBlock out(nq, n);
     ScratchLease lease(h);
@@ -817,8 +992,16 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     const uint32_t range_lds = filt_range_lds(ranged, (uint32_t)rk);
     const uint32_t slots = filt_first_slots_log2(v, efp, range_lds);
     if (n_graph && (rc = launch_filtered_graph(v, a, (uint32_t)n_graph, slots, s.stream))) return rc;
-    for (const Group &g : groups)
-        if (g.exact && (rc = exact_group(src, g, multi ? d_xsel + g.q0 : nullptr, g.nq, at))) return rc;
+    std::vector<std::vector<unsigned char>> keep;  // (the tables of the grouped passes, until the fetch has synchronised)
+    if (grouping && n_exact_groups > 1) {
+        std::vector<PassItem> items;
+        for (const Group &g : groups)
+            if (g.exact) items.push_back({g, order.data() + g.q0, d_xsel + g.q0, at.wbs + g.wb, at.d_wb + g.wb, at.send, 0});
+        if ((rc = exact_grouped(src, items, at, keep))) return rc;
+    } else {
+        for (const Group &g : groups)
+            if (g.exact && (rc = exact_group(src, g, multi ? d_xsel + g.q0 : nullptr, g.nq, at))) return rc;
+    }
     uint64_t n2 = 0;
     const hnsw_query_stats *st;
     if (!n_graph) {
@@ -829,7 +1012,7 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
         rc = rerun_overflowed(
             v, launch_filtered_graph, a, nq, slots, filt_max_slots_log2(v, range_lds), d_sel, s.stream, fetch,
             [&](const std::vector<uint32_t> &sel) -> int {
-                return path2(src, sel, path, &groups, multi ? 0 : nq, at, d_sel, wb_all.size(), nullptr, 0, fetch);
+                return path2(src, sel, path, &groups, multi ? 0 : nq, at, d_sel, wb_all.size(), nullptr, 0, fetch, grouping);
             },
             &n2);
         if (rc != HNSW_OK) return rc;
@@ -932,7 +1115,7 @@ int search_device_filtered(hnsw_index *h, const Filter &f, const float *d_Q, uin
             // (a query that names no row of the set ended with HNSW_ERR_ARG, not with an overflow: every row here exists)
             if (ranged && !src.interned()) src.intern(nq);
             return path2(src, sel, path, nullptr, 0, ExactPlace{nullptr, ExactScratch(), stream, nullptr, nullptr, true},
-                         nullptr, 0, &lease, pin_bytes, fetch);
+                         nullptr, 0, &lease, pin_bytes, fetch, h->filter_exact_grouped != 0);
         },
         &n2);
     if (rc != HNSW_OK) return rc;

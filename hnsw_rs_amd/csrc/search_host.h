@@ -96,7 +96,7 @@ int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, u
 // with lo > hi is empty; K == 0: no label filter.  Next to a SET row a query is under the row AND its range.
 struct Filter {
     // the entry points that made the call: picks the stat counters and the wording of errors, never a launch
-    enum Family { DELETED, SCAN, MASK, MULTI, OF_SET, RANGE, SET_RANGE, RANGES } family = DELETED;
+    enum Family { DELETED, SCAN, MASK, MULTI, OF_SET, RANGE, SET_RANGE, RANGES, ONE_QUERY } family = DELETED;
     enum Rows { ALL, ONE, MANY, SET } rows = ALL;
     const uint64_t *masks = nullptr;  // ONE, MANY (host memory)
     uint64_t allow_bits = 0;          // ONE, MANY
@@ -119,9 +119,12 @@ uint64_t count_admissible(const hnsw_index *h, const uint64_t *allow, uint64_t b
 // exact_only: every query by the exact path (hnsw_brute_force).  The results go to the caller's buffers (per-query
 // statuses in stats: required), or, when pin_block is given, straight into that pinned ResultBlock(nq, n) and the
 // buffers are not read.  Returns argument and launch errors only.
+// grouped: a call with two or more exact-path groups runs them in the grouped form, three launches for all of them
+// (search_host.cpp, exact_grouped), and its path 2 groups in one more such pass; false: as the handle's option
+// "filter_exact_grouped" says (0: group by group).  The results do not depend on it.
 int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f,
                     bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
-                    uint8_t *paths, void *pin_block = nullptr);
+                    uint8_t *paths, void *pin_block = nullptr, bool grouped = false);
 // ... with the first per-query error as the status (stats may be NULL)
 int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f,
                             bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,

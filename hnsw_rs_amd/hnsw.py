@@ -490,6 +490,50 @@ class HNSW:
                                             (mask_set._s, p(d_mask_of), p(d_lo), p(d_hi)), d_ids, d_dists, d_counts,
                                             d_stats, stream, paths)
 
+    def search_filtered(self, q, n, ef, lo=0, hi=0xFFFFFFFF, mask_set=None, row=None):
+        """ONE query under the label range [lo, hi] and, with a resident MaskSet, its row `row` (None, -1 or MASK_NONE: no
+        row): hnsw_search_filtered, whose concurrent callers on an index are gathered into one launch.
+        -> (ids [n], dists [n], count, path)"""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1)
+        if q.shape[0] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "the query must have %d values" % self.dim)
+        row = _lib.MASK_NONE if row is None or int(row) < 0 else int(row)
+        ids = np.full(max(n, 1), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full(max(n, 1), np.inf, dtype=np.float32)
+        count, path = C.c_uint32(), C.c_uint8()
+        check(self._L.hnsw_search_filtered(self._h, _p(q, _f32p), n, ef, mask_set._s if mask_set is not None else None, row,
+                                           int(lo), int(hi), _p(ids, _u32p), _p(dists, _f32p), C.byref(count), C.byref(path)))
+        return ids[:n], dists[:n], count.value, path.value
+
+    def search_filtered_threads(self, Q, n, ef, lo, hi, threads, seconds, mask_set=None, row=None):
+        """hnsw_bench_search_filtered_threads: `threads` host threads, each blocked in its own hnsw_search_filtered call;
+        query i under row[i] of mask_set (both None: no set; -1 or MASK_NONE: no row) and [lo[i], hi[i]] (scalars
+        broadcast).  -> (ids [nq, n], dists, counts, paths, rcs [nq]: every query's last answer and status, calls, wall
+        seconds, the latency dict of search_threads)"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        nq = Q.shape[0]
+        lo, hi = self._range(lo, hi, nq)
+        rows = None
+        if mask_set is not None:
+            rows = np.broadcast_to(np.asarray(-1 if row is None else row, dtype=np.int64), (nq,))
+            rows = np.ascontiguousarray(np.where(rows < 0, _lib.MASK_NONE, rows).astype(np.uint32))
+        ids = np.full((nq, max(n, 1)), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, max(n, 1)), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        paths = np.zeros(nq, dtype=np.uint8)
+        rcs = np.zeros(nq, dtype=np.int32)
+        calls, wall = C.c_uint64(), C.c_double()
+        lat = (C.c_double * 7)()
+        check(self._L.hnsw_bench_search_filtered_threads(
+            self._h, _p(Q, _f32p), nq, n, ef, mask_set._s if mask_set is not None else None,
+            _p(rows, _u32p) if rows is not None else None, _p(lo, _u32p), _p(hi, _u32p), int(threads), float(seconds),
+            _p(ids, _u32p), _p(dists, _f32p), _p(counts, _u32p), _p(paths, _lib.u8p), rcs.ctypes.data_as(C.POINTER(C.c_int32)),
+            C.byref(calls), C.byref(wall), lat))
+        return (ids[:, :n], dists[:, :n], counts, paths, rcs, calls.value, wall.value,
+                dict(zip(("p50", "p90", "p99", "max", "mean", "cpu_user_s", "cpu_sys_s"), list(lat))))
+
     def ann_by_vector_filtered(self, vector, n, ef, allow):
         """ann_by_vector restricted to the allowed ids -> list of ids"""
         q = np.ascontiguousarray(vector, dtype=np.float32).reshape(1, -1)

@@ -188,8 +188,10 @@ int hnsw_search_batch(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, ui
  * A == 0 gives count 0 for every query.  The cosine option applies to the queries first.  Per-query errors
  * (HNSW_ERR_NAN_INPUT) as hnsw_search_batch.  The handle's deleted ids (hnsw_mark_deleted) are never allowed: the
  * effective mask is allow AND NOT deleted, and the result equals the same call with that mask on a handle with
- * nothing deleted.  Masks resident in HBM across calls and a device-pointer form are hnsw_mask_set's, below.  Not
- * provided: coalescing of one-query filtered calls, filtered sharded search, the Rust shim's binding, and a label
+ * nothing deleted.  Masks resident in HBM across calls and a device-pointer form are hnsw_mask_set's, below; one-query
+ * calls under a set's row and a label range that gather into one launch are hnsw_search_filtered's, further below (a
+ * one-query call under a mask of its own, not in a set, does not gather).  Not
+ * provided: filtered sharded search, the Rust shim's binding, and a label
  * range (hnsw_search_batch_filtered_range, below) combined with a per-call mask or a mask per query in one call (with a
  * row of a resident set it is hnsw_search_batch_filtered_set_range, below; a disjunction of label ranges is
  * hnsw_search_batch_filtered_ranges, below). */
@@ -449,6 +451,29 @@ int hnsw_search_batch_filtered_ranges_device_finish(hnsw_index *h, const float *
                                                     const uint32_t *d_hi, uint32_t *d_ids, float *d_dists,
                                                     uint32_t *d_counts, hnsw_query_stats *d_stats, void *stream,
                                                     uint8_t *paths /* host, nq, or NULL */);
+/* ONE query under a filter, from many threads: the filtered form of hnsw_search.  The query is answered among the
+ * undeleted ids below hnsw_len whose label lies in [lo, hi] ([0, UINT32_MAX]: no label filter) and, with a set, whose bit
+ * is set in row `row` of it (HNSW_MASK_NONE: no row; set == NULL needs row == HNSW_MASK_NONE).  The ids, the distance
+ * bits, *count, *path and the return value are exactly those of the one-query batch call on the same handle with the same
+ * options -- set == NULL: hnsw_search_batch_filtered_range(h, q, 1, n, ef, &lo, &hi, ...); else
+ * hnsw_search_batch_filtered_set_range(h, q, 1, n, ef, set, &row, &lo, &hi, ...) -- whatever the call was gathered with:
+ * deleted ids, the cosine option, "filter_exact_max", ef' = max(ef, n, 1) <= 256 on the graph path, path 2 and A == 0
+ * as there.  Concurrent calls on a handle gather exactly as hnsw_search calls do ("coalesce_us", "coalesce_depth",
+ * "coalesce_max"; with "coalesce_us" < 0 every call launches by itself), in batches of their own: calls with equal
+ * (n, ef, set) share a batch whatever their rows and ranges, never with hnsw_search calls.  The leader answers its batch
+ * by one filtered search: the graph-path queries share ONE launch, the exact-path queries of ALL their groups one
+ * compaction, one scan and one merge (the grouped form of the exact path; the batch entry points
+ * use it with the option "filter_exact_grouped"), path 2 one more such pass.  A per-query error (HNSW_ERR_NAN_INPUT)
+ * reaches only its caller.  dists (n floats) and path may be NULL.
+ * HNSW_ERR_ARG, decided before the device is touched: h, q, ids or count NULL; n > 64; set == NULL with a row; a set of
+ * another handle; a row that is neither < n_masks nor HNSW_MASK_NONE.  n == 0 gives *count = 0 and launches nothing.
+ * hnsw_get_stat: "filtered_one_calls" (calls answered), "filtered_one_batches" (their leaders' launches); the three
+ * "filtered_*" path counters advance as for the batch forms, whose "*_calls" and "*_groups" keys do not.
+ * Not provided: one-query calls under a mask that is not in a set or under a list of ranges, the Rust shim's binding,
+ * filtered search over shards. */
+int hnsw_search_filtered(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, hnsw_mask_set *set /* or NULL */,
+                         uint32_t row /* HNSW_MASK_NONE: no row */, uint32_t lo, uint32_t hi, uint32_t *ids,
+                         float *dists /* or NULL */, uint32_t *count, uint8_t *path /* or NULL */);
 /* The planner's own count: the undeleted ids below hnsw_len whose label lies in the union of the k <= HNSW_RANGES_MAX
  * ranges [lo[j], hi[j]] (a member with lo > hi is empty; k == 0 or all members empty gives 0) -- the selectivity a
  * caller wants before choosing ef.  Needs no GPU: it reads the column's sorted copy.  HNSW_ERR_ARG: h or count NULL,
@@ -661,6 +686,9 @@ int hnsw_device_bytes(const hnsw_index *h, uint64_t *bytes);
  *                      the gathering of concurrent hnsw_search calls into one launch, see hnsw_search
  *   "filter_exact_max" hnsw_search_batch_filtered answers a call by the exact scan when its mask allows at most
  *                      this many ids (default 65536, from the crossover measured in DESIGN.md section 12; < 0: never)
+ *   "filter_exact_grouped" 1: the batch filtered entry points run the exact-path groups of a call in three launches
+ *                      for all of them instead of three per group (same results); 0, the default:
+ *                      group by group; anything else is HNSW_ERR_ARG.  hnsw_search_filtered always groups
  *   "mask_set_cache_mb" HBM a resident mask set may hold in compacted id lists of its exact-path rows (per set,
  *                      default 64 -- a design choice, not a measurement; at the default "filter_exact_max" a list is
  *                      at most 256 KiB; 0: no list is kept) */
@@ -692,7 +720,8 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * "filtered_range_ranges" (the distinct ranges they named), "filtered_set_range_calls"
  * (hnsw_search_batch_filtered_set_range calls and completed _set_range_device calls), "filtered_set_range_groups" (the
  * distinct (row, lo, hi) triples they named), "filtered_ranges_calls" (hnsw_search_batch_filtered_ranges calls and
- * completed _ranges_device calls), "filtered_ranges_groups" (the distinct canonical range lists they named);
+ * completed _ranges_device calls), "filtered_ranges_groups" (the distinct canonical range lists they named),
+ * "filtered_one_calls" / "filtered_one_batches" (hnsw_search_filtered calls answered, the launches of their leaders);
  * partitioned search, on the handle passed as shard 0: "shard_calls"
  * (hnsw_search_batch_shards calls whose shards were all searched), "shard_merges" (the merges they launched); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
@@ -754,6 +783,15 @@ int hnsw_draw_levels(uint32_t m, uint64_t n, uint8_t *out);
 int hnsw_bench_search_threads(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t threads,
                               double seconds, uint32_t *ids, uint32_t *counts, uint64_t *calls, double *wall_s,
                               double *lat_us);
+/* The same around hnsw_search_filtered: query i is answered under row[i] of `set` (set and row both NULL: no set) and
+ * the label range [lo[i], hi[i]].  dists (nq x n), counts, paths and rcs (nq each) may be NULL and receive each query's
+ * last answer with ids; with rcs a per-query error (HNSW_ERR_NAN_INPUT) is that query's answer and the run goes on,
+ * without it the first one ends the run.  Also the way to put real concurrency behind hnsw_search_filtered from a
+ * language whose threads share an interpreter lock. */
+int hnsw_bench_search_filtered_threads(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                       hnsw_mask_set *set, const uint32_t *row, const uint32_t *lo, const uint32_t *hi,
+                                       uint32_t threads, double seconds, uint32_t *ids, float *dists, uint32_t *counts,
+                                       uint8_t *paths, int32_t *rcs, uint64_t *calls, double *wall_s, double *lat_us);
 
 /* `callers` host threads, each calling hnsw_search_batch(nq queries, host pointers) `calls` times on its own slice
  * of Q (total x dim) into its own result buffers; *wall_s = first call to last return (two untimed calls per caller
