@@ -142,12 +142,22 @@ bool DeviceIndex::refresh_rows(const HostIndex &idx, const std::vector<uint64_t>
     if (wants_inline_rows(idx) || view.fat_stride != 0) return false;
     if (sizes_[4] != 4) return false;  // overflow lists already there: a fresh upload rebuilds them
     if (hipSetDevice(device) != hipSuccess) return false;
+    for (uint64_t key : layer_row)
+        if (!idx.in_layer((uint32_t)(key >> 32), (NodeID)key)) return false;
+    // the layout's order inside every row (ids ascending, empty slots behind them): the build wrote them as it
+    // appended and pruned.  On the null stream, which the copies below are ordered behind.
+    if (launch_sort_rows(adj0_mut(), view.S0, idx.len(), nullptr) != HNSW_OK ||
+        launch_sort_rows(adj_up_mut(), view.S1, idx.adj_up.size(), nullptr) != HNSW_OK ||
+        hipStreamSynchronize(nullptr) != hipSuccess) {
+        (void)hipGetLastError();
+        valid = false;  // rows half-sorted, or as the build left them: the next search uploads
+        return false;
+    }
     // rows in the order upload() files overflow lists: layer 0 by id, then the upper rows by row index
     std::vector<std::pair<uint64_t, uint32_t>> rows;  // (row index, 0 = adj0 / 1 = adj_up)
     for (uint64_t key : layer_row) {
         const uint32_t layer = (uint32_t)(key >> 32);
         const NodeID id = (NodeID)key;
-        if (!idx.in_layer(layer, id)) return false;
         rows.push_back(layer == 0 ? std::make_pair((uint64_t)id, 0u)
                                   : std::make_pair((uint64_t)idx.upper_base[id] + layer - 1, 1u));
     }

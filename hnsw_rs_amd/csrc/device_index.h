@@ -12,10 +12,11 @@
 //             (quant.rs:14-37: sum j takes elements 8c + j) from contiguous 16-byte pieces.
 //             d = 100: half = 8 + 48 + 4 -> 64 B, row = 128 B = one cache line.
 //             F32 (reference FullVec, vectors/src/full.rs): d floats, padded to 16 B.
-//   adj0      N x S0 u32: layer-0 adjacency in fixed-stride rows (S0 = pow2 >= 2m, 128 B at
-//             m = 16), row index = node id, neighbour ids ascending, empty slots 0xFFFFFFFF.
+//   adj0      N x S0 u32: layer-0 adjacency in fixed-stride rows (S0 = pow2 >= max(2m, 32), 128 B at
+//             m = 16), row index = node id, neighbour ids ascending, empty slots 0xFFFFFFFF behind them.
 //   adj_up    upper-layer rows, S1 = pow2 >= max(m, 8) slots each; the rows of one node for
 //             layers 1..level are contiguous: row(id, l) = upper_base[id] + l - 1.
+//             One all-empty row when no node has an upper layer.
 //   upper_base N u32 (0xFFFFFFFF for level-0 nodes).
 //   fat       (optional, "inline rows") layer-0 blocks of S0 x row_stride bytes, one per node: slot k
 //             of node i holds a COPY of the vector row of its k-th neighbour with that neighbour's
@@ -27,7 +28,13 @@
 //             otherwise the compact rows + adj0 path is used.  Empty slots: id 0xFFFFFFFF.
 //   ovf_off / ovf_nbrs  CSR of the neighbours that do not fit a row (degree > S happens:
 //             SURVEY.md H6).  Such a row keeps S - 1 ids and its last slot holds
-//             0x80000000 | overflow row.  Node ids are < 2^31 (enforced by the host index).
+//             0x80000000 | overflow row; list i is ovf_nbrs[ovf_off[i] .. ovf_off[i + 1]), the row's remaining ids
+//             ascending (ovf_off: lists + 1 words; ovf_nbrs: one dummy word 0xFFFFFFFF when there is no list).
+//             upload() files the lists of layer 0 by id, then those of the upper rows by row index; a patch
+//             appends a touched row's list behind them and leaves its old one unused.
+//             Node ids are < 2^31 (enforced by the host index).
+// Every writer of the snapshot -- upload(), append_point(), the on-device build through refresh_rows() -- leaves this
+// form; tests/snapshot_restate.py restates it and tests/test_gpu_snapshot.py holds HBM to it byte for byte.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -174,6 +181,8 @@ struct PatchDesc {
 };
 int launch_patch(const PatchDesc *d_desc, const uint32_t *d_staging, uint32_t n, hipStream_t stream);
 int launch_fat_rebuild(const DevView &v, uint8_t *fat, const uint32_t *d_nodes, uint32_t n, hipStream_t stream);
+// n_rows adjacency rows of S slots each, every one into ascending order of its words (patch.hip)
+int launch_sort_rows(uint32_t *adj, uint32_t S, uint64_t n_rows, hipStream_t stream);
 
 class DeviceIndex {
   public:
@@ -189,7 +198,9 @@ class DeviceIndex {
     bool current(const HostIndex &idx) const { return valid && (replica || version_seen == idx.version); }
     // After an on-device build the adjacency in HBM IS the graph the host just read back, except for the few
     // rows the host touched afterwards (kept-last-edge records): those rows are re-packed and copied, and the
-    // snapshot is declared current for idx.version -- instead of uploading tens of GB again.  Returns false
+    // snapshot is declared current for idx.version -- instead of uploading tens of GB again.  The build leaves a
+    // row's ids in the order of its appends and prunes; every row is first sorted in place (hx_sort_rows_kernel),
+    // so that the snapshot kept is word for word the one upload() would make of the same graph.  Returns false
     // (snapshot left as it was, the next search uploads) when that is not possible: inline rows wanted, or
     // overflow lists already present.  layer_row: (layer << 32) | node id.
     bool refresh_rows(const HostIndex &idx, const std::vector<uint64_t> &layer_row);

@@ -37,6 +37,28 @@ __global__ void __launch_bounds__(64) hx_fat_rebuild_kernel(DevView v, uint8_t *
     }
 }
 
+// one workgroup per adjacency row of S <= HX_SORT_ROW_MAX slots: the row's words into ascending order.  The on-device
+// build leaves a row in the order of its appends and prunes (build_kernels.hip); the layout (device_index.h) has the
+// ids ascending and the empty slots, 0xFFFFFFFF, behind them -- as words that is one ascending order.  Every word
+// is read into LDS before one is written, and word k goes to the slot of its rank (equal words keep their order):
+// a permutation of the row, whatever it held.
+static constexpr uint32_t HX_SORT_ROW_MAX = 256;
+
+__global__ void __launch_bounds__(64) hx_sort_rows_kernel(uint32_t *adj, uint32_t S, uint32_t n_rows) {
+    __shared__ uint32_t w[HX_SORT_ROW_MAX];
+    const uint32_t r = blockIdx.x;
+    if (r >= n_rows || S > HX_SORT_ROW_MAX) return;
+    uint32_t *row = adj + (size_t)r * S;
+    for (uint32_t k = threadIdx.x; k < S; k += 64) w[k] = row[k];
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < S; k += 64) {
+        const uint32_t x = w[k];
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < S; j++) rank += (w[j] < x || (w[j] == x && j < k)) ? 1u : 0u;
+        row[rank] = x;
+    }
+}
+
 // ---- sharded build: the rows their owner changed travel to the other replicas (ConnectArgs, device_index.h) ----
 static constexpr uint64_t PK_ID_MASK = (1ull << HX_EDGE_ID_BITS) - 1;
 
@@ -95,6 +117,16 @@ int launch_apply_rows(const DevView &v, uint32_t *adj0, uint32_t *adj_up, const 
 int launch_patch(const PatchDesc *d_desc, const uint32_t *d_staging, uint32_t n, hipStream_t stream) {
     if (n == 0) return HNSW_OK;
     return launch_checked({"patch kernel launch"}, hx_patch_kernel, dim3(n), dim3(64), 0, stream, d_desc, d_staging, n);
+}
+
+int launch_sort_rows(uint32_t *adj, uint32_t S, uint64_t n_rows, hipStream_t stream) {
+    if (n_rows == 0) return HNSW_OK;
+    if (S > HX_SORT_ROW_MAX || n_rows > 0x7FFFFFFFull) {
+        set_error("sort-rows kernel: rows of %u slots, %llu rows", S, (unsigned long long)n_rows);
+        return HNSW_ERR_ARG;
+    }
+    return launch_checked({"sort-rows kernel launch"}, hx_sort_rows_kernel, dim3((uint32_t)n_rows), dim3(64), 0, stream, adj, S,
+                          (uint32_t)n_rows);
 }
 
 int launch_fat_rebuild(const DevView &v, uint8_t *fat, const uint32_t *d_nodes, uint32_t n, hipStream_t stream) {

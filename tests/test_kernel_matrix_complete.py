@@ -18,8 +18,9 @@ from tests.test_gpu_build_restatement import BUILD_KERNELS
 ELSEWHERE = {
     "hx_deleted_scatter_kernel": "deletion's mask upload: test_gpu_deleted.py::test_search_batch_under_deletions",
     "hx_normalise_rows_kernel": "the metric_cosine option's query copy: test_gpu_configs.py::test_cosine_option_is_l2_on_unit_vectors",
-    "hx_patch_kernel": "insert_vec's live snapshot patch: test_gpu_call_pattern.py::test_insert_vec_then_search_patches_the_live_snapshot",
-    "hx_fat_rebuild_kernel": "insert_vec's inline-row patch: test_gpu_call_pattern.py::test_insert_vec_with_overflowing_rows_and_inline_rows",
+    "hx_patch_kernel": "insert_vec's live snapshot patch: test_gpu_snapshot.py::test_a_patched_snapshot_stays_canonical",
+    "hx_fat_rebuild_kernel": "insert_vec's inline-row patch: test_gpu_snapshot.py::test_a_patched_snapshot_stays_canonical",
+    "hx_sort_rows_kernel": "the snapshot a device build keeps: test_gpu_snapshot.py::test_the_snapshot_a_device_build_leaves_is_the_restatement_byte_for_byte",
     "hx_pack_rows_kernel": "sharded build, row ownership: test_gpu_parity.py::test_sharded_device_build_two_ranks",
     "hx_apply_rows_kernel": "sharded build, row ownership: test_gpu_parity.py::test_sharded_device_build_two_ranks",
     "hx_filter_records_kernel": "sharded build, record exchange: test_gpu_parity.py::test_sharded_device_build_two_ranks",
