@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("HNSW_MI355X_LIB") or os.path.join(_HERE, "libhnsw_mi3
 VEC_QUANT8 = 0
 VEC_F32 = 1
 UINT32_MAX = 0xFFFFFFFF
+GROUP_POOL_MAX = 256  # HNSW_GROUP_POOL_MAX: candidates per query of a grouped search
 RANGES_MAX = 16  # HNSW_RANGES_MAX: members of a query's range list
 MASK_NONE = 0xFFFFFFFF  # HNSW_MASK_NONE: a query of hnsw_search_batch_filtered_multi without an allow-list
 
@@ -126,6 +127,10 @@ SYMBOLS = {
     "hnsw_merge_topk_device": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, u32p, u32p, vp, vp, vp, vp, vp]),
     "hnsw_search_batch_shards": (C.c_int, [C.POINTER(vp), C.c_uint32, u32p, u32p, f32p, C.c_uint64, C.c_uint32, C.c_uint32,
                                            u32p, f32p, u32p, C.POINTER(QueryStats)]),
+    "hnsw_group_by_label_device": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp,
+                                             vp, vp, vp, vp]),
+    "hnsw_search_batch_grouped": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, u32p,
+                                            u32p, u32p, u32p, f32p, u32p, u32p, u32p, C.POINTER(QueryStats)]),
     "hnsw_distance_batch": (C.c_int, [vp, f32p, u32p, C.c_uint64, f32p]),
     "hnsw_search_layer": (C.c_int, [vp, C.c_uint32, f32p, u32p, C.c_uint32, C.c_uint32, u32p, f32p, u32p,
                                     C.POINTER(QueryStats)]),

@@ -1252,6 +1252,10 @@ int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
         *out = h->n_shard_calls.load();
     } else if (!strcmp(key, "shard_merges")) {
         *out = h->n_shard_merges.load();
+    } else if (!strcmp(key, "grouped_calls")) {
+        *out = h->n_grouped_calls.load();
+    } else if (!strcmp(key, "grouped_launches")) {
+        *out = h->n_grouped_launches.load();
     } else if (!strcmp(key, "deleted")) {
         *out = h->del.count;
     } else if (!strcmp(key, "deleted_mask_words_uploaded")) {

@@ -85,7 +85,17 @@ struct RangeList {
 // are summed or written).  A present entry's key is (dist bits << 32) | (base[s] + stride[s] * id); the query's n smallest
 // distinct keys are written as the exact path writes them.  base and stride travel by value: the launch needs no
 // allocation, copy or synchronisation.  ids == nullptr: the kernel's first form.
+//
+// The third source form (hnsw_group_by_label_device), selected by per_group != 0 -- not by
+// `labels`, which may be nullptr (label_len 0: every label is 0): ONE candidate list per query, ids[q][j] / dists[q][j],
+// j < pool, counts[q] and stats[q] as above (n_shards, base and stride are not read), collapsed by label into the
+// n_groups nearest groups of at most per_group entries each.  Nothing is sorted: the collapse is defined by position.
+// The ids and distances go to FilterArgs::out_ids / out_dists as [q][n_groups][per_group], the number of groups to
+// out_counts, the query's stats record to out_stats unchanged, the groups' labels and sizes to group_labels /
+// group_sizes [q][n_groups].  FilterArgs::n is not read.
 #define HX_MERGE_MAX_SHARDS 64
+#define HX_GROUP_POOL_MAX 256     // candidates per query: four per lane
+#define HX_GROUP_SLOTS_MAX 1024   // n_groups x per_group: the slot table in LDS
 struct MergeLists {
     const uint32_t *ids;
     const float *dists;
@@ -93,6 +103,10 @@ struct MergeLists {
     const hnsw_query_stats *stats;
     uint32_t n_shards, nq;
     uint32_t base[HX_MERGE_MAX_SHARDS], stride[HX_MERGE_MAX_SHARDS];
+    const uint32_t *labels;   // the label column (device), or nullptr
+    uint64_t label_len;       // labels the column holds; an id at or beyond it has label 0
+    uint32_t pool, n_groups, per_group, pad;
+    uint32_t *group_labels, *group_sizes;
 };
 
 // The grouped form of the exact path: the exact-path groups of a call in ONE compaction, ONE scan
@@ -162,5 +176,11 @@ int launch_filtered_exact_grouped(const DevView &v, const FilterArgs &a, uint32_
 // such shard's), count 0 and padded rows; n_dist, n_exp and sum_deg are the uint32 sums over the shards.
 int launch_merge_lists(const MergeLists &m, uint32_t n, uint32_t *out_ids, float *out_dists, uint32_t *out_counts,
                        hnsw_query_stats *out_stats, hipStream_t stream);
+// the collapse by label of m.nq candidate lists of m.pool entries (the third form; m.ids, m.dists, m.pool, m.n_groups,
+// m.per_group, m.group_labels and m.group_sizes set, 1 <= n_groups, per_group <= pool <= HX_GROUP_POOL_MAX and
+// n_groups x per_group <= HX_GROUP_SLOTS_MAX): ONE launch of hx_filt_merge_kernel, one wave per query.  out_counts may be
+// nullptr; out_stats goes with m.stats.
+int launch_group_by_label(const MergeLists &m, uint32_t *out_ids, float *out_dists, uint32_t *out_counts,
+                          hnsw_query_stats *out_stats, hipStream_t stream);
 
 }  // namespace hx

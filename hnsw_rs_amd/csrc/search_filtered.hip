@@ -735,15 +735,132 @@ __device__ __forceinline__ void merge_shard_lists(const FilterArgs &a, const Mer
     }
 }
 
+// The merge kernel's collapse form (MergeLists with per_group != 0, search_filtered.h): query
+// blockIdx.x's candidate list of m.pool entries, lane l holding entries l, l + 64, l + 128 and l + 192, collapsed by label
+// into its m.n_groups nearest groups of at most m.per_group entries.  Entry j has the rank r_j (present entries before
+// it with its label) and the first member f_j (the first present entry with its label), found in one pass over the
+// present entries with their labels broadcast from LDS; its group's number g_j is the number of first members before
+// f_j, a popcount prefix of their ballots.  A kept entry (r_j < per_group, g_j < n_groups) puts its index into the slot
+// table [n_groups][per_group] in LDS, and the lanes stream the table out, 64 slots at a time: every output word is
+// written once, a pad where its slot is empty.
+//   lab[256]  the entries' labels   slot[1024]  the slot table (HX_GROUP_NO_ENTRY: empty)   gsz[256]  the groups' sizes
+#define HX_GROUP_LDS (HX_GROUP_POOL_MAX * 4 + HX_GROUP_SLOTS_MAX * 2 + HX_GROUP_POOL_MAX * 2)
+#define HX_GROUP_NO_ENTRY 0xFFFFu
+__device__ __forceinline__ void collapse_by_label(const FilterArgs &a, const MergeLists &m, unsigned char *lds, int lane) {
+    uint32_t *lab = reinterpret_cast<uint32_t *>(lds);
+    uint16_t *slot = reinterpret_cast<uint16_t *>(lds + HX_GROUP_POOL_MAX * 4);
+    uint16_t *gsz = slot + HX_GROUP_SLOTS_MAX;
+    const uint32_t q = blockIdx.x, pool = m.pool, G = m.n_groups, P = m.per_group, GP = G * P;
+    if (pool > HX_GROUP_POOL_MAX || G > pool || P > pool || GP > HX_GROUP_SLOTS_MAX) return;  // (the launcher's limits)
+    const uint32_t *dist_bits = reinterpret_cast<const uint32_t *>(m.dists);
+    hnsw_query_stats st;
+    st.n_dist = st.n_exp = st.sum_deg = 0;
+    st.status = HNSW_OK;
+    if (m.stats) st = m.stats[q];
+    const uint32_t cnt = m.counts ? min(m.counts[q], pool) : pool;
+    const bool ok = st.status == HNSW_OK;  // a failed query has no present entry: count 0 and padded rows
+    uint32_t id[4], bits[4], mylab[4];
+    bool pres[4];
+    u64 pm[4];  // the present entries, one ballot per register
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint32_t j = 64u * k + lane;
+        const bool in = j < pool;
+        id[k] = in ? m.ids[(size_t)q * pool + j] : HX_EMPTY_SLOT;
+        bits[k] = in ? dist_bits[(size_t)q * pool + j] : 0u;
+        pres[k] = ok && in && (m.counts ? j < cnt : id[k] != HX_EMPTY_SLOT);
+        mylab[k] = pres[k] && id[k] < m.label_len ? m.labels[id[k]] : 0u;  // (label_len is 0 without a column)
+        lab[j] = mylab[k];
+        pm[k] = __ballot(pres[k]);
+    }
+    for (uint32_t s = lane; s < GP; s += 64) slot[s] = HX_GROUP_NO_ENTRY;
+    wave_fence();
+    uint32_t r[4], f[4], tot[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) r[k] = tot[k] = 0, f[k] = ~0u;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        u64 it = pm[w];
+        while (it) {  // (wave-uniform)
+            const uint32_t i = 64u * w + (uint32_t)(__ffsll((long long)it) - 1);
+            it &= it - 1;
+            const uint32_t li = lab[i];  // one address for the wave: a broadcast
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const bool same = li == mylab[k];
+                if (same && f[k] == ~0u) f[k] = i;
+                r[k] += same && i < 64u * k + lane ? 1u : 0u;
+                tot[k] += same ? 1u : 0u;
+            }
+        }
+    }
+    bool first[4];
+    u64 fm[4];  // the first members, one ballot per register
+    uint32_t before[4], n_all = 0;  // first members in the registers before w; groups in the pool
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        first[k] = pres[k] && r[k] == 0;
+        fm[k] = __ballot(first[k]);
+        before[k] = n_all;
+        n_all += (uint32_t)__popcll(fm[k]);
+    }
+    const uint32_t count = min(n_all, G);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (!pres[k]) continue;  // (f is an index below pool from here on)
+        const uint32_t fw = f[k] >> 6, fb = f[k] & 63;
+        const u64 mw = fw == 0 ? fm[0] : fw == 1 ? fm[1] : fw == 2 ? fm[2] : fm[3];
+        const uint32_t bw = fw == 0 ? before[0] : fw == 1 ? before[1] : fw == 2 ? before[2] : before[3];
+        const uint32_t g = bw + (uint32_t)__popcll(mw & ((1ull << fb) - 1));
+        if (g >= G) continue;
+        if (r[k] < P) slot[g * P + r[k]] = (uint16_t)(64u * k + lane);
+        if (first[k]) gsz[g] = (uint16_t)min(tot[k], P);
+    }
+    wave_fence();
+    // the table, streamed out: slot s of the query from entry slot[s]'s registers (every lane takes part in the shuffles)
+    for (uint32_t base = 0; base < GP; base += 64) {
+        const uint32_t s = base + lane;
+        const uint32_t src = s < GP ? slot[s] : HX_GROUP_NO_ENTRY;
+        uint32_t vi = HX_EMPTY_SLOT, vb = 0x7F800000u;  // the pads: no id, +inf
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t ti = (uint32_t)__shfl((int)id[k], (int)(src & 63));
+            const uint32_t tb = (uint32_t)__shfl((int)bits[k], (int)(src & 63));
+            if ((src >> 6) == (uint32_t)k) vi = ti, vb = tb;
+        }
+        if (s < GP) {
+            a.out_ids[(size_t)q * GP + s] = vi;
+            a.out_dists[(size_t)q * GP + s] = __builtin_bit_cast(float, vb);
+        }
+    }
+    for (uint32_t s = lane; s < G; s += 64) {
+        const bool have = s < count;
+        const uint32_t src = have ? slot[s * P] : 0u;  // (a group's best member is always kept)
+        m.group_labels[(size_t)q * G + s] = have ? lab[src & (HX_GROUP_POOL_MAX - 1)] : 0u;
+        m.group_sizes[(size_t)q * G + s] = have ? (uint32_t)gsz[s] : 0u;
+    }
+    if (lane == 0) {
+        if (a.out_counts) a.out_counts[q] = count;
+        if (a.out_stats) a.out_stats[q] = st;
+    }
+}
+
 // Merge: one wave per query folds the nseg partial lists into its top n and writes the results.  With m.ids set the
-// lists are those of m.n_shards shards instead (merge_shard_lists; A, nseg, part and part_status are not read).  With
+// lists are those of m.n_shards shards instead (merge_shard_lists; A, nseg, part and part_status are not read), or, with
+// m.per_group set as well, the query's one candidate list, collapsed by label (collapse_by_label).  With
 // qtab set (the grouped form) A, nseg and the first row of the query's partial lists are its record's.
 __global__ void __launch_bounds__(64) hx_filt_merge_kernel(const FilterArgs a, uint32_t A, uint32_t nseg,
                                                            const u64 *part, const int32_t *part_status,
                                                            const MergeLists m, const ExactQuery *qtab) {
-    __shared__ u64 perm[64];
+    // the merges' 64 keys of scatter room; the collapse form's labels, slot table and group sizes
+    __shared__ __attribute__((aligned(16))) unsigned char lds[HX_GROUP_LDS];
+    u64 *perm = reinterpret_cast<u64 *>(lds);
     const int lane = threadIdx.x;
-    if (m.ids) {  // (a kernel argument: the branch is the wave's)
+    if (m.per_group) {  // (kernel arguments: the branches are the wave's)
+        collapse_by_label(a, m, lds, lane);
+        return;
+    }
+    if (m.ids) {
         merge_shard_lists(a, m, perm, lane);
         return;
     }
@@ -915,6 +1032,29 @@ int launch_merge_lists(const MergeLists &m, uint32_t n, uint32_t *out_ids, float
     a.out_counts = out_counts;
     a.out_stats = out_stats;
     return launch_checked({"shard merge kernel launch"}, hx_filt_merge_kernel, dim3(m.nq), dim3(64), 0, stream, a, 0u, 0u,
+                          static_cast<const u64 *>(nullptr), static_cast<const int32_t *>(nullptr), m,
+                          static_cast<const ExactQuery *>(nullptr));
+}
+
+int launch_group_by_label(const MergeLists &lists, uint32_t *out_ids, float *out_dists, uint32_t *out_counts,
+                          hnsw_query_stats *out_stats, hipStream_t stream) {
+    MergeLists m = lists;
+    if (m.nq == 0) return HNSW_OK;
+    if (m.pool == 0 || m.pool > HX_GROUP_POOL_MAX || m.n_groups == 0 || m.n_groups > m.pool || m.per_group == 0 ||
+        m.per_group > m.pool || (uint64_t)m.n_groups * m.per_group > HX_GROUP_SLOTS_MAX || m.nq > 0x7FFFFFFFu || !m.ids ||
+        !m.dists || !m.group_labels || !m.group_sizes || !out_ids || !out_dists ||
+        (m.stats != nullptr) != (out_stats != nullptr)) {
+        set_error("group by label: needs 1 <= n_groups, per_group <= pool <= %d, n_groups x per_group <= %d, at most 2^31 - 1 "
+                  "queries, the lists and the outputs", HX_GROUP_POOL_MAX, HX_GROUP_SLOTS_MAX);
+        return HNSW_ERR_ARG;
+    }
+    if (!m.labels) m.label_len = 0;  // no column: every label is 0 and nothing is read
+    FilterArgs a{};  // the form reads the outputs
+    a.out_ids = out_ids;
+    a.out_dists = out_dists;
+    a.out_counts = out_counts;
+    a.out_stats = out_stats;
+    return launch_checked({"group by label kernel launch"}, hx_filt_merge_kernel, dim3(m.nq), dim3(64), 0, stream, a, 0u, 0u,
                           static_cast<const u64 *>(nullptr), static_cast<const int32_t *>(nullptr), m,
                           static_cast<const ExactQuery *>(nullptr));
 }

@@ -1023,6 +1023,15 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
     return HNSW_OK;
 }
 
+int labels_on_device(hnsw_index *h, const uint32_t **d_labels, uint64_t *label_len) {
+    if (int rc = sync_labels(h)) return rc;
+    FilterArgs a{};
+    bind_labels(h, a);
+    *d_labels = a.labels;
+    *label_len = a.label_len;
+    return HNSW_OK;
+}
+
 int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f,
                             bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
                             uint8_t *paths) {

@@ -142,6 +142,12 @@ int search_device_filtered(hnsw_index *h, const Filter &f, const float *d_Q, uin
                            uint32_t *d_ids, float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
                            hipStream_t stream, bool finish, uint8_t *paths);
 
+// The label column as the kernels read it, for a caller outside the filtered searches (grouped.cpp): the HBM copy is
+// brought up to date on a stream of the handle's own, exactly as a range search does it (a column no label was ever
+// set in gets its copy of zeros); -> the copy and the labels it holds.  The snapshot's device must be known
+// (ensure_uploaded).
+int labels_on_device(hnsw_index *h, const uint32_t **d_labels, uint64_t *label_len);
+
 // hnsw_search_batch_device_finish while nothing is deleted: waits for the stream, reads the per-query statuses,
 // re-runs the queries whose visited table filled up with a table twice the size (same arithmetic, same result as
 // if the larger table had been used from the start) and reports the first remaining per-query error.

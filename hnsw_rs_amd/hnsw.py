@@ -490,6 +490,46 @@ class HNSW:
                                             (mask_set._s, p(d_mask_of), p(d_lo), p(d_hi)), d_ids, d_dists, d_counts,
                                             d_stats, stream, paths)
 
+    # ---- grouped search: the nearest groups by label (include/hnsw_mi355x.h) ---------------------------------------
+    def search_batch_grouped(self, Q, n_groups, per_group, pool, ef, mask_set=None, mask_of=None, lo=None, hi=None):
+        """The n_groups nearest labels of every query with their per_group best hits each, out of the `pool` candidates
+        that search_batch (or, with mask_set / lo and hi, the filtered search of that kind) returns with n = pool
+        (hnsw_search_batch_grouped).  mask_of [nq]: rows of the set, -1 or MASK_NONE; None: row 0.  lo / hi: both or
+        neither, scalars broadcast.
+        -> ids [nq, n_groups, per_group] (pad UINT32_MAX), dists [nq, n_groups, per_group] (pad +inf), group_labels
+        [nq, n_groups], group_sizes [nq, n_groups], counts [nq] (groups found), stats [nq, 4] (the candidate call's)"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        if (lo is None) != (hi is None):
+            raise ValueError("a label range needs lo and hi, both or neither")
+        nq, G, P = Q.shape[0], max(int(n_groups), 1), max(int(per_group), 1)
+        mo = self._mask_of(mask_of, nq)
+        rng = (None, None) if lo is None else self._range(lo, hi, nq)
+        ids = np.full((nq, G, P), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, G, P), np.inf, dtype=np.float32)
+        labels = np.zeros((nq, G), dtype=np.uint32)
+        sizes = np.zeros((nq, G), dtype=np.uint32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        check(self._L.hnsw_search_batch_grouped(
+            self._h, _p(Q, _f32p), nq, n_groups, per_group, pool, ef, mask_set._s if mask_set is not None else None,
+            None if mo is None else _p(mo, _u32p), None if rng[0] is None else _p(rng[0], _u32p),
+            None if rng[1] is None else _p(rng[1], _u32p), _p(ids, _u32p), _p(dists, _f32p), _p(labels, _u32p),
+            _p(sizes, _u32p), _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
+        return ids, dists, labels, sizes, counts, stats.view(np.uint32).astype(np.int64)
+
+    def group_by_label_device(self, nq, pool, n_groups, per_group, d_ids_in, d_dists_in, d_counts_in, d_stats_in, d_ids,
+                              d_dists, d_group_labels, d_group_sizes, d_counts=None, d_stats=None, stream=0):
+        """hnsw_group_by_label_device over torch device tensors (or raw device pointers): the [nq, pool] candidate lists
+        a *_device search of this index left (d_counts_in / d_stats_in [nq] or None), collapsed by this index's labels
+        into d_ids / d_dists [nq, n_groups, per_group], d_group_labels / d_group_sizes [nq, n_groups] (/ d_counts /
+        d_stats).  ONE launch enqueued on `stream`, no sync of it."""
+        p = self._dptr
+        check(self._L.hnsw_group_by_label_device(
+            self._h, nq, pool, n_groups, per_group, p(d_ids_in), p(d_dists_in), p(d_counts_in), p(d_stats_in), p(d_ids),
+            p(d_dists), p(d_group_labels), p(d_group_sizes), p(d_counts), p(d_stats), stream or None))
+
     def search_filtered(self, q, n, ef, lo=0, hi=0xFFFFFFFF, mask_set=None, row=None):
         """ONE query under the label range [lo, hi] and, with a resident MaskSet, its row `row` (None, -1 or MASK_NONE: no
         row): hnsw_search_filtered, whose concurrent callers on an index are gathered into one launch.

@@ -550,6 +550,70 @@ int hnsw_search_batch_shards(hnsw_index *const *shards, uint32_t n_shards,
                              const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
                              uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats);
 
+/* ---- grouped search: the nearest groups by label, at most per_group hits per group --------------------------------
+ * An extension (the reference has no labels).  When the vectors are chunks, frames or sentences and the label
+ * (hnsw_set_labels) is the parent's id, the caller wants the n_groups nearest distinct labels with their per_group best
+ * hits each, not the nearest chunks (Qdrant's search groups, Milvus's grouping search, Elasticsearch's collapse).
+ * THE COLLAPSE of one query's candidate list of `pool` entries (id_j, dist_j), j < pool, in the order given (the search
+ * calls hand them over ascending by (distance bits, id), but the collapse is defined by position and sorts nothing):
+ *   - entry j is PRESENT iff j < min(count, pool), or, without counts, iff id_j != UINT32_MAX; absent entries take no
+ *     part, wherever they are;
+ *   - lab_j is the handle's label of id_j as of the call (an id at or beyond the column's length has label 0; a handle
+ *     on which no label was ever set has every label 0: one group);
+ *   - the RANK r_j is the number of present i < j with lab_i == lab_j; the FIRST MEMBER f_j the smallest present i with
+ *     lab_i == lab_j; the GROUP INDEX g_j the number of present i < f_j with r_i == 0 -- groups are numbered in the
+ *     order of their first, that is best, member;
+ *   - entry j is KEPT iff r_j < per_group and g_j < n_groups, and is written to slot [g_j][r_j].
+ * Per query: ids [n_groups][per_group] (pad UINT32_MAX), dists [n_groups][per_group] (the distance bits of the input,
+ * pad +inf), group_labels [n_groups] (pad 0), group_sizes [n_groups] (min(per_group, entries of that label in the
+ * pool), pad 0), counts = min(n_groups, distinct labels present).  A query's stats record passes through unchanged;
+ * a query whose incoming status is not HNSW_OK gets count 0 and fully padded rows.
+ * Limits: 1 <= pool <= HNSW_GROUP_POOL_MAX; 1 <= n_groups, per_group <= pool; n_groups * per_group <= 1024.
+ *
+ * hnsw_group_by_label_device is the collapse alone over lists in HBM: every d_* pointer is device memory, the inputs
+ * d_ids_in / d_dists_in [nq][pool], d_counts_in [nq] or NULL, d_stats_in [nq] or NULL are what any *_device search of
+ * the same handle leaves after its _finish (ids local to the handle; lists merged over shards carry global ids and are
+ * out of scope).  The label column's HBM copy is brought up to date on a stream of the handle's own, exactly as the
+ * _range_device entry points do it; then ONE launch (the exact path's merge kernel in its collapse form, one wave per
+ * query) is enqueued on `stream` and the call returns without synchronising `stream`.  Outputs must not overlap
+ * inputs.  d_counts may be NULL; d_stats is required iff d_stats_in is given.  HNSW_ERR_ARG, decided before the device
+ * is touched: h NULL; the limits above violated; nq > 2^31 - 1; d_ids_in, d_dists_in, d_ids, d_dists, d_group_labels
+ * or d_group_sizes NULL; exactly one of d_stats_in / d_stats given.  nq == 0 is HNSW_OK on any handle, whatever else is
+ * passed, and launches nothing; an empty index is HNSW_ERR_EMPTY.
+ *
+ * hnsw_search_batch_grouped answers host-pointer queries by their nearest groups.  By definition the result is THE
+ * COLLAPSE of the candidate lists that an existing call returns with n = pool, on the same handle with the same
+ * options: hnsw_search_batch (set NULL, lo and hi NULL), hnsw_search_batch_filtered_range (lo and hi), _filtered_set
+ * (set; mask_of NULL: row 0) or _filtered_set_range (both).  Everything of the candidate call is inherited: ef' =
+ * max(ef, n, 1), deleted ids taken out, the cosine option, the planner and "filter_exact_max", path 2, its stats, its
+ * per-query errors (the first is returned, every other row is filled in) and its limits -- pool <= 64 and, on the
+ * graph path, ef' <= 256 whenever the candidate call is a filtered one or the handle has deleted ids.  Unfiltered with
+ * nothing deleted the call runs on the device end to end: the queries go up once, hnsw_search_batch_device and its
+ * _finish, the collapse, one copy of the grouped block back.  Under a filter or deletions the candidates come from
+ * the candidate call's HOST form and their lists go up before the collapse: only the host form lets the planner choose
+ * the exact path, and the call is defined by it.  dists, group_sizes, counts and stats may be NULL.  HNSW_ERR_ARG,
+ * decided before the device is touched: the limits violated; mask_of without a set; exactly one of lo / hi; a set of
+ * another handle; Q, ids or group_labels NULL; nq > 2^31 - 1.  nq == 0 is HNSW_OK.  hnsw_get_stat: "grouped_calls",
+ * "grouped_launches".
+ * Not provided: grouping over shards; a refill loop when fewer than n_groups groups are in the pool (the caller raises
+ * pool); a group key other than the label column; a device-resident filtered path; one-query gathered calls; the Rust
+ * shim's binding. */
+#define HNSW_GROUP_POOL_MAX 256
+int hnsw_group_by_label_device(hnsw_index *h, uint64_t nq, uint32_t pool, uint32_t n_groups, uint32_t per_group,
+                               const uint32_t *d_ids_in /* nq x pool */, const float *d_dists_in,
+                               const uint32_t *d_counts_in /* or NULL */, const hnsw_query_stats *d_stats_in /* or NULL */,
+                               uint32_t *d_ids, float *d_dists /* nq x n_groups x per_group */,
+                               uint32_t *d_group_labels, uint32_t *d_group_sizes /* nq x n_groups */,
+                               uint32_t *d_counts /* or NULL */, hnsw_query_stats *d_stats /* required iff d_stats_in */,
+                               void *stream);
+int hnsw_search_batch_grouped(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n_groups, uint32_t per_group,
+                              uint32_t pool, uint32_t ef, hnsw_mask_set *set /* or NULL */,
+                              const uint32_t *mask_of /* nq, or NULL */,
+                              const uint32_t *lo, const uint32_t *hi /* nq each, or both NULL: no range */,
+                              uint32_t *ids, float *dists /* or NULL */, uint32_t *group_labels,
+                              uint32_t *group_sizes /* or NULL */, uint32_t *counts /* or NULL */,
+                              hnsw_query_stats *stats /* or NULL */);
+
 /* Test seams that mirror the reference's own units:
  * VecBase::dist2many (vectors/src/lib.rs:17-22): the query (quantised like ann_by_vector does,
  * template.rs:313) against stored ids, on the device, exact accumulation order. */
@@ -723,7 +787,9 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * completed _ranges_device calls), "filtered_ranges_groups" (the distinct canonical range lists they named),
  * "filtered_one_calls" / "filtered_one_batches" (hnsw_search_filtered calls answered, the launches of their leaders);
  * partitioned search, on the handle passed as shard 0: "shard_calls"
- * (hnsw_search_batch_shards calls whose shards were all searched), "shard_merges" (the merges they launched); deletion:
+ * (hnsw_search_batch_shards calls whose shards were all searched), "shard_merges" (the merges they launched); grouped
+ * search: "grouped_calls" (hnsw_search_batch_grouped calls answered), "grouped_launches" (collapses launched,
+ * hnsw_group_by_label_device's included); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
