@@ -18,6 +18,13 @@
 // tie-heavy integer rows on every query, and to that weaker contract beyond the bound.  hnsw_brute_force
 // stays the unconditionally exact, bit-for-bit one.  FullVec (f32) rows only.
 //
+// The bound E models RELATIVE rounding, so it holds only while products and sums stay in f32's normal range.  Below
+// it the error is absolute (or the matrix cores flush), above it a score is inf or inf - inf and `score < threshold`
+// keeps nothing.  hnsw_brute_force_fast therefore hands a call to the exact scan (hnsw_brute_force) when a stored row
+// or a query has a largest |component| that is not zero and lies outside [2^-48, 2^40]: inside, every |x|^2 is in
+// [2^-96, 2^91] (d < 2^11), every score below 2^93, and what flushing d subnormal products could lose (d 2^-126) is
+// at most 1/64 of E >= (d + 2) 2^-24 2^-96.  A row or query of zeros is exact as it is.  tests/numeric_range.py.
+//
 // Shape: a 256-thread workgroup owns a tile of 32 queries (staged once in LDS, rows padded by 16 B so that
 // the 16-byte operand reads are bank-conflict free) and one segment of the points; each of its four waves
 // walks its own quarter of the segment in tiles of 32 points.  Per 32 x 32 tile the wave issues d / 2
@@ -39,13 +46,21 @@ static constexpr int MF_K2 = 20;   // candidates kept per lane (two lanes and 4 
 static constexpr int MF_QT = 32;   // queries per workgroup
 static constexpr int MF_CH = 8;    // 16-byte pieces per lane in flight per stage
 
-__global__ void __launch_bounds__(256) hx_row_norms_kernel(const float *X, uint32_t N, uint32_t d, float *xn) {
+// xn[i] = |x_i|^2 (one left-to-right chain); xabs[i] = the largest |x_ie| as its bit pattern (an integer maximum:
+// exact whatever the denormal mode), by which the host tells rows outside the screen's range (see above)
+__global__ void __launch_bounds__(256)
+hx_row_norms_kernel(const float *X, uint32_t N, uint32_t d, float *xn, uint32_t *xabs) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     const float *r = X + (size_t)i * d;
     float s = 0.0f;
-    for (uint32_t e = 0; e < d; e++) s += r[e] * r[e];
+    uint32_t m = 0;
+    for (uint32_t e = 0; e < d; e++) {
+        s += r[e] * r[e];
+        m = max(m, __float_as_uint(r[e]) & 0x7FFFFFFFu);
+    }
     xn[i] = s;
+    xabs[i] = m;
 }
 
 __global__ void __launch_bounds__(256)
@@ -183,9 +198,9 @@ hx_pair_distance_kernel(const float *X, uint32_t d, const float *Q, const uint32
     out[i] = __builtin_sqrtf(s);
 }
 
-int launch_row_norms(const DevView &v, float *d_xn, hipStream_t stream) {
+int launch_row_norms(const DevView &v, float *d_xn, uint32_t *d_xabs, hipStream_t stream) {
     return launch_checked({nullptr}, hx_row_norms_kernel, dim3((v.n_points + 255) / 256), dim3(256), 0, stream,
-                          reinterpret_cast<const float *>(v.rows), v.n_points, v.dim, d_xn);
+                          reinterpret_cast<const float *>(v.rows), v.n_points, v.dim, d_xn, d_xabs);
 }
 
 uint32_t brute_mfma_k2() { return MF_K2; }

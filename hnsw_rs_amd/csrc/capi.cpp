@@ -814,8 +814,30 @@ int hnsw_brute_force_fast(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k
         (rc = dS.alloc(ntile_max * per_tile * 4)) || (rc = dI.alloc(ntile_max * per_tile * 4)) ||
         (rc = dQi.alloc(batch * M * 4)) || (rc = dPi.alloc(batch * M * 4)) || (rc = dOut.alloc(batch * M * 4)))
         return rc;
-    rc = hx::launch_row_norms(v, dXn.as<float>(), nullptr);
+    DevBuf dXa;
+    if ((rc = dXa.alloc((size_t)v.n_points * 4))) return rc;
+    rc = hx::launch_row_norms(v, dXn.as<float>(), dXa.as<uint32_t>(), nullptr);
     if (rc != HNSW_OK) return rc;
+    // The screen's guarantee models relative rounding and holds only inside f32's normal range (brute_mfma.hip): a
+    // call with a stored row or a query whose largest |component| is not zero and outside [2^-48, 2^40] is the exact
+    // scan's.  (Under the cosine option a query is a unit vector by the time the screen reads it.)
+    {
+        const uint32_t lo = 0x27800000u, hi = 0x53800000u;  // the bit patterns of 2^-48 and 2^40
+        auto outside = [&](uint32_t bits) { return bits != 0 && (bits < lo || bits > hi); };
+        std::vector<uint32_t> xa((size_t)v.n_points);
+        HIP_TRY(hipMemcpy(xa.data(), dXa.p, xa.size() * 4, hipMemcpyDeviceToHost));
+        bool exact = false;
+        for (size_t i = 0; i < xa.size() && !exact; i++) exact = outside(xa[i]);
+        for (uint64_t i = 0; i < nq && !exact && !h->cosine; i++) {
+            uint32_t m = 0, w;
+            for (uint32_t e = 0; e < v.dim; e++) {
+                memcpy(&w, &Q[i * v.dim + e], 4);
+                m = std::max(m, w & 0x7FFFFFFFu);
+            }
+            exact = outside(m);
+        }
+        if (exact) return hnsw_brute_force(h, Q, nq, k, ids, dists);
+    }
     std::vector<float> hs(ntile_max * per_tile), hd(batch * M);
     std::vector<uint32_t> hi(ntile_max * per_tile), qidx(batch * M), pidx(batch * M);
     std::vector<std::pair<float, uint32_t>> cand;

@@ -276,7 +276,7 @@ int launch_scatter_rows(uint32_t *dst, uint32_t S, const uint32_t *d_row_index, 
 // exhaustive scan on the matrix cores (brute_mfma.hip): a screen by MFMA scores, then exact distances of
 // the survivors.  f32 rows, dimension a multiple of 4.
 uint32_t brute_mfma_k2();
-int launch_row_norms(const DevView &v, float *d_xn, hipStream_t stream);
+int launch_row_norms(const DevView &v, float *d_xn, uint32_t *d_xabs, hipStream_t stream);
 int launch_brute_mfma(const DevView &v, const float *d_xn, const float *d_Q, uint32_t nq, uint32_t nseg,
                       float *out_s, uint32_t *out_i, hipStream_t stream);
 int launch_pair_distance(const DevView &v, const float *d_Q, const uint32_t *d_qidx, const uint32_t *d_pidx, uint64_t n,

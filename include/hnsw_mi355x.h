@@ -638,8 +638,10 @@ int hnsw_brute_force(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uin
  * smaller than that (rows far from the origin relative to their spread) the result is still k distinct
  * stored ids with the reference's own distances in (dist, id) order, but a neighbour can be missing.
  * tests/test_gpu_ground_truth.py holds both halves to the oracle, tests/ground_truth_inputs.py derives the
- * bound.  hnsw_brute_force is the unconditionally exact scan.  An extension: the reference has no
- * counterpart. */
+ * bound.  E models relative rounding and means nothing outside f32's normal range: a call in which a stored
+ * row or a query has a largest |component| that is not zero and lies outside [2^-48, 2^40] is handed to
+ * hnsw_brute_force whole (tests/test_gpu_numeric_range.py).  hnsw_brute_force is the unconditionally exact
+ * scan.  An extension: the reference has no counterpart. */
 int hnsw_brute_force_fast(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids,
                           float *dists);
 

@@ -710,6 +710,10 @@ int orc_brute_force(const orc_index *h, const float *Q, uint64_t nq, uint32_t k,
                 PointRef p;
                 h->points.get_point((NodeID)i, &p);
                 all[i] = Dist{(NodeID)i, dist2other(h->points, point.ref, p)};
+                if (std::isnan(all[i].dist)) {  // the reference's sort compares with Dist::cmp, which panics
+                    rcs[t] = ORC_ERR_NAN;
+                    return;
+                }
             }
             const uint64_t kk = std::min<uint64_t>(k, N);
             // full sort in the reference (glove.rs:107); partial_sort gives the same prefix

@@ -284,13 +284,14 @@ def _calls(c, idx, orc, vs, Q, n):
     raise ValueError(c.entry)
 
 
-def run_call(kernels, c):
+def run_call(kernels, c, on=None):
     """run one call of a row: the kernel log must hold exactly the row's instantiations (+ the call's `also`, + any of
-    its `may`), the answers must be the reference's"""
+    its `may`), the answers must be the reference's.  on: (index, oracle, vectors, queries) to run the call on instead
+    of the row's own fixture and queries (tests/numeric_range.py)"""
     import hnsw_rs_amd as H
-    idx, orc, vs = fixture(c.kind, c.d, c.m)
+    idx, orc, vs = on[:3] if on else fixture(c.kind, c.d, c.m)
     idx.set_option("inline_rows", c.inline)
-    Q = queries(c, vs)
+    Q = on[3] if on else queries(c, vs)
     want = set(kernels) | set(c.also)
     for n in sorted({10, c.n}) if c.entry != "distance" else (0,):
         run, check = _calls(c, idx, orc, vs, Q, n)

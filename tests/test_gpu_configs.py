@@ -493,3 +493,41 @@ def test_cosine_option_is_l2_on_unit_vectors(kind):
         best = np.argsort(-sims, axis=1)[:, :10]
         bf = cos.brute_force(qs[:8], 10)[0]
         assert np.mean([len(set(a.tolist()) & set(b.tolist())) for a, b in zip(bf, best)]) >= 9.9
+
+
+@pytest.mark.parametrize("kind", [H.VEC_QUANT8, H.VEC_F32])
+def test_cosine_option_on_queries_whose_sum_of_squares_is_subnormal(kind):
+    """stored rows times 2^-70 as queries: hx_normalise_rows_kernel's sum of squares is subnormal and not zero, its
+    square root and divisions take subnormal operands.  The answers are bit for bit those of the queries normalised in
+    numpy float32 by metric.hip's recipe (one left-to-right sum of squares, sqrt, division), and in ids those of the
+    unscaled queries.  A zero query and a query of 3e38s (a sum of squares that overflows) have no direction: each is
+    HNSW_ERR_NAN_INPUT with count 0 for that query alone."""
+    from tests.numeric_range import unchecked
+    from tests.test_host_build import _unit_rows
+    n, d, m = 1500, 100, 16
+    vs = H.synth_rows(0, 0x5EED0001, 0, n, d) * np.float32(2.5)
+    lv = H.draw_levels(m, n)
+    cos = H.HNSW.new(m, 32, d, kind)
+    cos.set_option("metric_cosine", 1)
+    cos.insert_bulk(vs, 1, False, levels=lv)
+    orc = oracle_from_product(cos, _unit_rows(vs), lv)
+    qs = vs[:64]
+    tiny = qs * np.float32(2.0 ** -70)
+    ss = np.cumsum(tiny * tiny, axis=1, dtype=np.float32)[:, -1]
+    assert ((ss > 0) & (ss < np.float32(2.0 ** -126))).all()
+    with H.kernel_log() as log:
+        got = cos.search_batch(tiny, 10, 64)
+    assert "hx_normalise_rows_kernel" in log, dict(log)
+    assert (got[3][:, 3] == 0).all()
+    assert_search_equal(got, orc.search_batch(_unit_rows(tiny), 10, 64), "cosine, subnormal sums of squares")
+    assert np.array_equal(got[0], cos.search_batch(qs, 10, 64)[0])
+    Q = tiny[:8].copy()
+    Q[2], Q[5] = 0.0, 3e38
+    with unchecked() as rcs:
+        ids, _, counts, stats = cos.search_batch(Q, 10, 64)
+    bad = np.zeros(8, dtype=bool)
+    bad[[2, 5]] = True
+    assert rcs == [H._lib.ERR_NAN_INPUT]
+    assert np.array_equal(stats[:, 3].astype(np.int32), np.where(bad, H._lib.ERR_NAN_INPUT, 0))
+    assert (counts[bad] == 0).all() and (ids[bad] == O.UINT32_MAX).all()
+    assert np.array_equal(ids[~bad], got[0][:8][~bad]) and np.array_equal(counts[~bad], got[2][:8][~bad])
