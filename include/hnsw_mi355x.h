@@ -483,7 +483,16 @@ int hnsw_count_labels_in_ranges(const hnsw_index *h, const uint32_t *lo, const u
 
 /* hnsw_search_batch with every buffer already resident in HBM on the handle's device; enqueues on `stream`
  * (a hipStream_t, NULL = default stream) and returns without synchronising.  d_stats is
- * required (its status field carries per-query errors); d_dists / d_counts may be NULL. */
+ * required (its status field carries per-query errors); d_dists / d_counts may be NULL.
+ * The call can be captured in a graph as ONE kernel launch -- it allocates nothing, copies nothing and synchronises
+ * nothing -- while all of these hold: the HBM snapshot is current (a search or hnsw_upload ran on the handle since the
+ * last insert or option change), no id is deleted, the cosine option is off, ef <= 256 (lists of at most four
+ * registers: longer ones take a second visited level in stream-ordered scratch on some paths) and the visited table
+ * the launch starts with is at most 32 KiB of LDS (ef * max(mmax0, 8) / 32 <= 320, which ef <= 256 implies up to
+ * mmax0 = 40, the default mmax0 = 2m at m <= 20).  Outside them the call brings state up to date, goes through the
+ * filtered kernel's path, opts into more LDS or takes stream-ordered scratch, and is not promised to be capturable.  A
+ * captured call cannot be completed by _finish inside the graph: the replaying caller inspects d_stats[i].status
+ * itself. */
 int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef,
                              uint32_t *d_ids, float *d_dists, uint32_t *d_counts,
                              hnsw_query_stats *d_stats, void *stream);
