@@ -15,6 +15,7 @@
 #include "device_index.h"
 #include "launch.h"
 #include "search_common.h"
+#include "switches.h"
 
 namespace hx {
 
@@ -463,8 +464,7 @@ hx_scatter_rows_kernel(uint32_t *dst, uint32_t S, const uint32_t *row_index, con
 // standard 16-KiB table at d = 256, 10 with 8 KiB): 16M x 256d, insert kernel 12.3 -> 10.1 s with 29 points of
 // 16M filling the small table (they run again with adjust + 1; round 3).
 int insert_table_first_adjust(const DevView &v, const InsertArgs &a) {
-    if (const char *e = getenv("HNSW_MI355X_INSERT_TABLE_ADJUST")) return atoi(e);  // A/B runs
-    return (a.ef_cons <= 32 && v.S0 <= 32) ? -1 : 0;
+    return sw::insert_table_adjust((a.ef_cons <= 32 && v.S0 <= 32) ? -1 : 0);  // (the switch: A/B runs)
 }
 
 int launch_insert(const DevView &v, const InsertArgs &a, uint32_t nblocks, hipStream_t stream, int table_adjust) {

@@ -22,6 +22,7 @@
 
 #include "handle.h"
 #include "search_host.h"
+#include "switches.h"
 
 using hx::check_search_args;
 using hx::cosine_queries;
@@ -283,8 +284,7 @@ int hnsw_insert_vec_level(hnsw_index *h, const float *v, int level, uint32_t *ou
     // was current before the insertion it is patched -- the new row and the adjacency rows the insertion touched --
     // instead of being thrown away and uploaded again by the next search (DeviceIndex::append_point).
     std::lock_guard<std::mutex> g(h->mu);
-    const bool live = h->dev.valid && h->dev.current(*h->host) &&
-                      !(getenv("HNSW_MI355X_REUPLOAD") && atoi(getenv("HNSW_MI355X_REUPLOAD")) != 0);
+    const bool live = h->dev.valid && h->dev.current(*h->host) && !hx::sw::reupload();
     std::vector<uint64_t> touched;
     uint32_t id = 0;
     int rc;
@@ -598,7 +598,7 @@ int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint3
     if ((rc = dq.prepare(h, d_Q, nq, static_cast<hipStream_t>(stream)))) return rc;
     hx::SearchArgs a = hx::ann_args(h->dev.view, dq.q, n, ef, d_ids, d_dists, d_counts, d_stats);
 #ifdef HX_STAMPS
-    a.dbg = reinterpret_cast<unsigned long long *>(getenv("HX_DBG_PTR") ? strtoull(getenv("HX_DBG_PTR"), nullptr, 0) : 0);
+    a.dbg = reinterpret_cast<unsigned long long *>(hx::sw::dbg_ptr());
 #endif
     return hx::launch_search(h->dev.view, a, (uint32_t)nq, 0, static_cast<hipStream_t>(stream));
 }

@@ -14,6 +14,7 @@
 
 #include "hip_util.h"
 #include "shard_exchange.h"
+#include "switches.h"
 
 namespace hx {
 namespace {
@@ -434,8 +435,7 @@ struct FullBuild {
         }
         temp_bytes = sort_temp_bytes(REQ_CAP);
         REC_BYTES = sh ? shard_record_bytes(m, W) : 0;
-        static const bool shard_connect_on = !(getenv("HNSW_MI355X_SHARD_CONNECT") && atoi(getenv("HNSW_MI355X_SHARD_CONNECT")) == 0);
-        own_rows = sh && W > 1 && shard_connect_on;
+        own_rows = sh && W > 1 && sw::shard_connect();
         CHG_CAP = own_rows ? shard_slot_rows(m, W) : 0;
         SHIP = shard_ship_slots(m);
         SHIP_UNIT = 8 + 4ull * SHIP;
@@ -458,9 +458,8 @@ struct FullBuild {
         // the edges' distances beside the adjacency for the length of this build (ConnectArgs: a prune then evaluates
         // nothing); 0xFFFFFFFF = not known yet (the rows that predate this build: evaluated at their first prune).  128 B
         // per point at m = 16; without the memory for it the build runs as before
-        static const bool keep_dists = !(getenv("HNSW_MI355X_BUILD_EDGE_DISTS") && atoi(getenv("HNSW_MI355X_BUILD_EDGE_DISTS")) == 0);
         const size_t b0 = (size_t)host.len() * v.S0 * 4, b1 = std::max<size_t>(1, host.adj_up.size()) * v.S1 * 4;
-        if (keep_dists && hipMalloc(&dAdjD0.p, b0) == hipSuccess && hipMalloc(&dAdjDUp.p, b1) == hipSuccess &&
+        if (sw::build_edge_dists() && hipMalloc(&dAdjD0.p, b0) == hipSuccess && hipMalloc(&dAdjDUp.p, b1) == hipSuccess &&
             hipMemset(dAdjD0.p, 0xFF, b0) == hipSuccess && hipMemset(dAdjDUp.p, 0xFF, b1) == hipSuccess) {
             a.adjd0_mut = ca.adjd0_mut = dAdjD0.as<uint32_t>();
             a.adjd_up_mut = ca.adjd_up_mut = dAdjDUp.as<uint32_t>();
@@ -1013,7 +1012,7 @@ int gpu_insert_bulk_full(const BuildTarget &t, const float *rows, uint64_t n, ui
     host.version++;
     // the adjacency in HBM is the graph just read back: patch the few rows changed since and keep the snapshot
     // (a build of tens of GB is otherwise followed by an upload of the same tens of GB)
-    if (device_is_the_graph && !(getenv("HNSW_MI355X_REUPLOAD") && atoi(getenv("HNSW_MI355X_REUPLOAD")) != 0))
+    if (device_is_the_graph && !sw::reupload())
         (void)t.dev.refresh_rows(host, touched);
     return HNSW_OK;
 }

@@ -3,6 +3,7 @@
 
 #include "device_index.h"
 #include "hip_util.h"
+#include "switches.h"
 
 #include <algorithm>
 #include <atomic>
@@ -112,16 +113,13 @@ static void parallel_rows(uint64_t n, F f) {
 // inline rows ("fat" layer-0 blocks, device_index.h): only small 8-bit indexes have them
 bool DeviceIndex::wants_inline_rows(const HostIndex &idx) const {
     if (idx.kind != HNSW_VEC_QUANT8) return false;
-    int want = inline_rows;
-    if (const char *e = getenv("HNSW_MI355X_INLINE_ROWS")) want = atoi(e);
+    int want = sw::inline_rows(inline_rows);
     const uint32_t half = quant_half_bytes(idx.dim), S0 = adj_stride(idx.layer_m(0), 32);
     const uint32_t used = 8 + 4 * (idx.dim / 8) + idx.dim % 8;
     const bool room = S0 == 32 && half >= used + 4;
     // d = 100 is served by the lean compact-layout kernel (search_lean.hip), faster at every launch size
     // than the inline-rows loop: the 4-GB copy is only built there when asked for explicitly
-    if (want < 0 && idx.dim == 100 && !(getenv("HNSW_MI355X_LEAN_Q8") && atoi(getenv("HNSW_MI355X_LEAN_Q8")) == 0) &&
-        !(getenv("HNSW_MI355X_LEAN") && atoi(getenv("HNSW_MI355X_LEAN")) == 0))
-        want = 0;
+    if (want < 0 && idx.dim == 100 && sw::lean_q8_enabled()) want = 0;
     const uint64_t need = (uint64_t)idx.len() * S0 * (2ull * half);
     return room && (want == 1 || (want < 0 && need <= fat_budget_bytes));
 }
@@ -409,12 +407,8 @@ static void parallel_span(uint64_t lo, uint64_t hi, F f) {
 namespace {
 constexpr size_t PIECE_BYTES = 64ull << 20;
 inline size_t piece_limit() {  // (HNSW_MI355X_UPLOAD_PIECE_MB: A/B runs of the staging piece size)
-    static const size_t v = [] {
-        const char *e = getenv("HNSW_MI355X_UPLOAD_PIECE_MB");
-        const long mb = e ? atol(e) : 0;
-        return mb > 0 ? (size_t)mb << 20 : PIECE_BYTES;
-    }();
-    return v;
+    const long mb = sw::upload_piece_mb();
+    return mb > 0 ? (size_t)mb << 20 : PIECE_BYTES;
 }
 struct PinnedPair {
     size_t piece_bytes;  // of each buffer: 64 MiB, less for a small index (pinning memory costs time too)
@@ -443,7 +437,7 @@ static int upload_pieces(PinnedPair &pp, void *dst, uint64_t n_rows, size_t unit
     if (!pp.stream) {
         HIP_TRY(hipStreamCreateWithFlags(&pp.stream, hipStreamNonBlocking));
         for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreateWithFlags(&pp.ev[i], hipEventDisableTiming));
-        const bool refuse = getenv("HNSW_MI355X_NO_PINNED") && atoi(getenv("HNSW_MI355X_NO_PINNED")) != 0;  // (tests)
+        const bool refuse = sw::no_pinned();  // (tests)
         if (refuse || hipHostMalloc(&pp.buf[0], pp.piece_bytes, hipHostMallocDefault) != hipSuccess ||
             hipHostMalloc(&pp.buf[1], pp.piece_bytes, hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
@@ -490,7 +484,7 @@ int DeviceIndex::read_adjacency(int which, uint64_t n_rows,
     PinnedPair pp(n_rows * unit);
     HIP_TRY(hipStreamCreateWithFlags(&pp.stream, hipStreamNonBlocking));
     for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreateWithFlags(&pp.ev[i], hipEventDisableTiming));
-    const bool refuse = getenv("HNSW_MI355X_NO_PINNED") && atoi(getenv("HNSW_MI355X_NO_PINNED")) != 0;
+    const bool refuse = sw::no_pinned();
     if (refuse || hipHostMalloc(&pp.buf[0], pp.piece_bytes, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc(&pp.buf[1], pp.piece_bytes, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();

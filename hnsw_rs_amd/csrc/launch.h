@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "device_index.h"
+#include "switches.h"
 
 namespace hx {
 
@@ -67,8 +68,7 @@ struct VisitedSpill {
     hipStream_t st = nullptr;
     template <class Args>
     VisitedSpill(bool wanted, Args &a, uint32_t &slots_log2, uint32_t nblocks, hipStream_t stream) : st(stream) {
-        static const bool two_level = !(getenv("HNSW_MI355X_VISITED_2L") && atoi(getenv("HNSW_MI355X_VISITED_2L")) == 0);
-        if (!wanted || !two_level) return;
+        if (!wanted || !sw::visited_2l()) return;
         const uint32_t glog2 = slots_log2 + 1 > 15u ? slots_log2 + 1 : 15u;
         if (hipMallocAsync(&p, ((size_t)nblocks << glog2) * 4, stream) != hipSuccess) {
             (void)hipGetLastError();
@@ -78,7 +78,7 @@ struct VisitedSpill {
         a.spill_tab = static_cast<uint32_t *>(p);
         a.spill_log2 = glog2;
         slots_log2 = 13;
-        if (const char *e = getenv("HNSW_MI355X_VISITED_2L_LIMIT")) a.lds_limit = (uint32_t)atoi(e);
+        a.lds_limit = sw::visited_2l_limit(a.lds_limit);
     }
     ~VisitedSpill() {
         if (p) (void)hipFreeAsync(p, st);

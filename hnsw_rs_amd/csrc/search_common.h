@@ -1,8 +1,8 @@
 // search_common.h -- the device primitives that more than one .hip uses (search_kernels.hip, search_lean.hip,
 // build_kernels.hip, exact_scan.hip, search_filtered.hip).  gfx950 only; include from .hip files.
-//   lanes        readlane64, pair_swap*, quad_bcast*, wave_fence, wg_barrier
+//   lanes        readlane64, pair_swap*, wave_fence
 //   quantiser    f32_as_u8, stage_query (a query), stage_row (a stored point as the query), QLds / QRegs
-//   distances    quant_half_sums / quant_pair_sums (QuantVec::distance_unrolled, two / four lanes per row),
+//   distances    quant_half_sums (QuantVec::distance_unrolled, two lanes per row),
 //                quant_bulk_stages, dist_any_dim (any dimension), f32_row_sum / f32_row_sum_staged (compile-time
 //                dimension), coop_rows.inc (the cooperative whole-line gather, included below), dist_build
 //   memory       dma_piece_to_lds (global -> LDS without a register), asm_ld32 / asm_ld128
@@ -183,87 +183,6 @@ static constexpr u64 KEY_EXPANDED = 1ull << 63;
 
 #define HX_MAX_R 8  // ef <= 64 * HX_MAX_R on the specialised kernels and in the on-device build
 #define HX_MAX_R_WIDE 16  // ef <= 1024 on the any-dimension search kernel
-
-// workgroup barrier that does not drain VMEM (LDS-DMA prefetches stay in flight across it)
-__device__ __forceinline__ void wg_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-// value held by lane q (0..3) of this lane's quad
-template <int Q>
-__device__ __forceinline__ float quad_bcast(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x),
-                                                                  Q * 0x55, 0xF, 0xF, true));
-}
-template <int Q>
-__device__ __forceinline__ int quad_bcast_i(int x) {
-    return __builtin_amdgcn_update_dpp(0, x, Q * 0x55, 0xF, 0xF, true);
-}
-// ---------------------------------------------------------------------------------------------
-// Four lanes per candidate (two-wave kernel): lane (h, sub) of the quad owns running sums
-// 4h + 2 sub and 4h + 2 sub + 1 of distance_unrolled, i.e. bytes 2 sub and 2 sub + 1 of every chunk
-// dword of half h; the d % 8 tail belongs to lane (0, 0) alone.  qc[2 c + kk] is this lane's query
-// value for chunk dword c, byte kk; qt[r] the tail values (lane (0,0) only).
-// ---------------------------------------------------------------------------------------------
-template <int P, int DS, typename QC, typename QT>
-__device__ __forceinline__ void quant_pair_sums(const uint4 (&w)[P], const QC &qc, const QT &qt,
-                                                int h, int sub, uint32_t nch4, uint32_t rem,
-                                                float (&acc)[2]) {
-    const float mn = __builtin_bit_cast(float, w[0].x);
-    const float delta = __builtin_bit_cast(float, w[0].y);
-    const bool tail_lane = (h == 0) && (sub == 0);
-    const uint32_t sh = 16u * (uint32_t)sub;
-#pragma unroll
-    for (int p = 0; p < P; p++) {
-        const uint32_t dw[4] = {w[p].x, w[p].y, w[p].z, w[p].w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (p == 0 && j < 2) continue;  // header
-            const int e0 = 16 * p + 4 * j - 8;  // element index of byte 0 of this dword
-            const int c = e0 / 4;               // chunk dword number
-            bool is_chunk, is_tail;
-            if (DS > 0) {
-                constexpr int N4 = 4 * (DS / 8), RM = DS % 8;
-                is_chunk = e0 < N4;
-                is_tail = !is_chunk && e0 < N4 + RM;
-                if (!is_chunk && !is_tail) continue;
-            } else {
-                is_chunk = (uint32_t)e0 < nch4;
-                is_tail = !is_chunk && (uint32_t)e0 < nch4 + rem;
-            }
-            if (DS > 0 ? is_chunk : true) {
-                const uint32_t u = dw[j] >> sh;
-#pragma unroll
-                for (int kk = 0; kk < 2; kk++) {
-                    const float x = ((float)((u >> (8 * kk)) & 0xFFu) * delta) + mn;
-                    const float t = x - qc[2 * c + kk];
-                    const float t2 = t * t;
-                    acc[kk] += (DS > 0 || is_chunk) ? t2 : 0.0f;
-                }
-            }
-            if (DS > 0 ? is_tail : true) {
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int e = e0 + k;
-                    bool in;
-                    if (DS > 0) {
-                        constexpr int N4 = 4 * (DS / 8), RM = DS % 8;
-                        if (e >= N4 + RM) continue;
-                        in = true;
-                    } else {
-                        in = is_tail && (uint32_t)e < nch4 + rem;
-                    }
-                    const float x = ((float)((dw[j] >> (8 * k)) & 0xFFu) * delta) + mn;
-                    const int r = DS > 0 ? e - 4 * (DS / 8) : (in ? e - (int)nch4 : 0);
-                    const float t = x - qt[r];
-                    const float t2 = t * t;
-                    acc[0] += (in && tail_lane) ? t2 : 0.0f;
-                }
-            }
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // Stage a STORED point as the query (build path: Point::dist2other between two stored points,

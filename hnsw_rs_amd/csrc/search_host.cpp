@@ -3,6 +3,7 @@
 // are search_kernels.hip, search_lean.hip and search_filtered.hip.
 
 #include "search_host.h"
+#include "switches.h"
 
 #include <algorithm>
 #include <cstddef>
@@ -130,9 +131,7 @@ int search_staged(hnsw_index *h, SearchScratch &s, const HostSearchPlan &p, Sear
     // caller's kernel, reads over the link from a busy kernel do not) -- so calls of up to 512 queries (every coalesced
     // batch of up to 512 callers) go without copies, larger ones, and calls whose queries are normalised on the
     // device first (the cosine option), keep them.
-    static const bool zc_allowed = !(getenv("HNSW_MI355X_ZERO_COPY") && atoi(getenv("HNSW_MI355X_ZERO_COPY")) == 0);
-    static const uint64_t zc_max = getenv("HNSW_MI355X_ZERO_COPY_MAX") ? strtoull(getenv("HNSW_MI355X_ZERO_COPY_MAX"), nullptr, 0) : 512;
-    const bool zc = zc_allowed && !Q_user && !h->cosine && nq <= zc_max;
+    const bool zc = sw::zero_copy() && !Q_user && !h->cosine && nq <= sw::zero_copy_max();
     SearchArgs a = a_host;
     if (zc) {
         a.Q = reinterpret_cast<const float *>(hv + p.p_q);

@@ -34,9 +34,9 @@
 // `acc += t * t`; sqrt and the quantiser's division are the correctly rounded forms hipcc emits
 // by default.  Accumulation order is the reference's (quant.rs:23-36, full.rs:24-28).
 //
-// This file: hx_search_kernel, hx_search2_kernel (opt-in two-wave form), hx_search_spill_kernel (ef > 1024), their
-// launchers and launch_search.  The wave primitives they share with the other kernel files are in search_common.h; the
-// on-device build is build_kernels.hip, the exact scans are exact_scan.hip, the lean kernels search_lean.hip.
+// This file: hx_search_kernel, hx_search_spill_kernel (ef > 1024), their launchers and launch_search.  The wave
+// primitives they share with the other kernel files are in search_common.h; the on-device build is build_kernels.hip,
+// the exact scans are exact_scan.hip, the lean kernels search_lean.hip.
 
 #include <cstdio>
 #include <cstdlib>
@@ -44,6 +44,7 @@
 #include "device_index.h"
 #include "launch.h"
 #include "search_common.h"
+#include "switches.h"
 
 namespace hx {
 
@@ -737,539 +738,6 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
     }
 }
 
-// =============================================================================================
-// Two-wave search kernel (QUANT8, inline-rows layout, m <= 16): ONE QUERY PER 128-THREAD
-// WORKGROUP.  A batch of 1024 queries is only one wave per SIMD for the one-wave kernel, and a
-// lone wave issues at most one vector instruction every four cycles; giving every query two
-// waves doubles the waves per SIMD and halves each wave's share of an expansion:
-//   - wave w owns adjacency slots 16w .. 16w+15, FOUR lanes per slot (lane (h, sub) of the quad:
-//     running sums 4h + 2 sub, 4h + 2 sub + 1 of distance_unrolled), DMA-stages only its half of
-//     the 4-KiB block, filters its 16 ids through the SHARED visited table;
-//   - both waves keep an identical copy of the sorted list in registers: after the distance step
-//     they exchange their <= 16 keys through LDS (one workgroup barrier per expansion) and each
-//     merges all 32, so pick / predict / merge never need another word of communication.
-// Wave 0 alone walks the entry point and the upper layers (ef = 1) on the compact layout, then
-// hands its list to wave 1.  Results are those of the one-wave kernel bit for bit (the batch a
-// merge sees is the same set of keys, and merging is order-independent).
-// =============================================================================================
-template <int N>
-struct QRegs2 {
-    float v[N];
-    __device__ __forceinline__ float operator[](int i) const { return v[i]; }
-};
-struct QcLds {  // chunk values of one (h, sub) lane: element 4 (i / 2) + 2 sub + i % 2 of the half
-    const float *p;
-    __device__ __forceinline__ float operator[](int i) const { return p[4 * (i >> 1) + (i & 1)]; }
-};
-
-template <int P, int DS, int R>
-__global__ void __launch_bounds__(128)
-hx_search2_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int KIND = HNSW_VEC_QUANT8;
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t q = a.qsel ? a.qsel[blockIdx.x] : blockIdx.x;
-    const uint32_t hslots = 1u << slots_log2, hmask = hslots - 1;
-    const uint32_t vis_limit = hslots - (hslots >> 2);
-    const uint32_t yq_bytes = ((2u * (v.half_bytes - 8) * 4u) + 15u) & ~15u;  // == query_lds_bytes(v) (launch.h) for QUANT8
-    constexpr uint32_t HALF_BLK = 16u * 32u * P;  // bytes of one wave's half block (16 rows)
-    // LDS carve (all dynamic): visited table | per-wave perm | exchange | per-wave yq | per-wave images
-    uint32_t off = 0;
-    uint32_t *htab = reinterpret_cast<uint32_t *>(smem);
-    off += 4u * hslots;
-    u64 *perm = reinterpret_cast<u64 *>(smem + off) + 64 * R * wv;
-    u64 *perm0 = reinterpret_cast<u64 *>(smem + off);
-    off += 2u * 64u * R * 8u;
-    u64 *xkeys = reinterpret_cast<u64 *>(smem + off);  // [2 parities][32 slots]
-    off += 2u * 32u * 8u;
-    uint32_t *xmeta = reinterpret_cast<uint32_t *>(smem + off);  // [2 parities][2 waves][4]
-    off += 2u * 2u * 4u * 4u;
-    float *yq = reinterpret_cast<float *>(smem + off + yq_bytes * wv);
-    off += 2u * yq_bytes;
-    unsigned char *img = smem + off + 2u * HALF_BLK * wv;  // this wave's two half-block images
-    const uint32_t img_lds = __builtin_amdgcn_groupstaticsize() + off + 2u * HALF_BLK * wv;
-
-    const uint32_t d = v.dim;
-    const float *qv = a.Q + (size_t)q * d;
-    uint32_t n_dist = 0, n_exp = 0, sum_deg = 0, n_vis = 0;
-    int32_t status = HNSW_OK;
-#ifdef HX_STAMPS
-    unsigned long long dbg_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long dbg_mid = 0;
-    const unsigned long long t_begin = __builtin_readcyclecounter();
-#endif
-
-    // every wave stages its own copy of the query
-    const uint32_t nq_half = v.half_bytes - 8;
-    if (!stage_query<KIND>(v, qv, yq, lane)) status = HNSW_ERR_NAN_INPUT;
-
-    WaveList<R> wl;
-#pragma unroll
-    for (int r = 0; r < R; r++) wl.L[r] = KEY_INVALID;
-    wl.n_cur = 0;
-    wl.last_key = KEY_INVALID;
-
-    // ------------------------------------------------------------------------------------------
-    // wave 0: entry point + upper layers (ef = 1), two lanes per candidate on the compact layout
-    // ------------------------------------------------------------------------------------------
-    if (wv == 0 && status == HNSW_OK) {
-        const int h2 = lane & 1, cslot2 = lane >> 1;
-        constexpr int NQR = DS > 0 ? (4 * (DS / 8) + DS % 8) : 1;
-        QRegs<NQR> qreg;
-        if (DS > 0) {
-#pragma unroll
-            for (int e = 0; e < NQR; e++) qreg.v[e] = yq[h2 * nq_half + e];
-        }
-        const QLds qlds{yq + h2 * nq_half};
-        auto eval2 = [&](uint32_t id, bool active) -> u64 {
-            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (active) {
-                const uint4 *src = reinterpret_cast<const uint4 *>(
-                    v.rows + (size_t)id * v.row_stride + (size_t)h2 * v.half_bytes);
-                uint4 w[P];
-#pragma unroll
-                for (int p = 0; p < P; p++) w[p] = src[p];
-                if (DS > 0)
-                    quant_half_sums<P, DS>(w, qreg, h2, v.nch4, v.rem, acc);
-                else
-                    quant_half_sums<P, 0>(w, qlds, h2, v.nch4, v.rem, acc);
-            }
-            const float b0 = pair_swap(acc[0]), b1 = pair_swap(acc[1]), b2 = pair_swap(acc[2]),
-                        b3 = pair_swap(acc[3]);
-            float s = 0.0f;
-            s += acc[0];
-            s += acc[1];
-            s += acc[2];
-            s += acc[3];
-            s += b0;
-            s += b1;
-            s += b2;
-            s += b3;
-            const float dist = __builtin_sqrtf(s);
-            if (!(active && h2 == 0)) return KEY_INVALID;
-            if (dist != dist) {
-                status = HNSW_ERR_NAN_INPUT;
-                return KEY_INVALID;
-            }
-            return ((u64)__builtin_bit_cast(uint32_t, dist) << 32) | id;
-        };
-        auto process2 = [&](uint32_t id, bool valid, bool visit) {
-            bool fresh = valid;
-            if (visit) {
-                bool f = false;
-                if (valid && h2 == 0) f = visited_insert(htab, hmask, slots_log2, id);
-                fresh = (pair_swap_i(f ? 1 : 0) | (f ? 1 : 0)) != 0;
-            }
-            const u64 fm = __ballot(fresh && h2 == 0);
-            if (fm == 0) return;
-            n_dist += (uint32_t)__popcll(fm);
-            u64 key = eval2(id, fresh);
-            if (__ballot(status != HNSW_OK)) status = HNSW_ERR_NAN_INPUT;
-            wl.merge(key, 1u, perm, lane);
-        };
-        // entry: {ep} (template.rs:316-319)
-        process2(v.ep, lane < 2, false);
-        for (int layer = (int)v.nb_layers - 1; status == HNSW_OK && layer >= 1; layer--) {
-            for (uint32_t s = lane; s < (hslots >> 2); s += 64)
-                reinterpret_cast<uint4 *>(htab)[s] =
-                    make_uint4(HX_EMPTY_SLOT, HX_EMPTY_SLOT, HX_EMPTY_SLOT, HX_EMPTY_SLOT);
-            wave_fence();
-            if (lane == 0 && wl.n_cur > 0) {
-                wl.L[0] &= KEY_MASK;
-                visited_insert(htab, hmask, slots_log2, (uint32_t)wl.L[0]);
-            }
-            n_vis = wl.n_cur;
-            wl.refresh_last(1u);
-            const uint32_t S = v.S1;
-            while (true) {
-                const int cpos = wl.first_unexpanded(lane);
-                if (cpos < 0) break;
-                const uint32_t cid = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)wl.L[0], 0);
-                if (lane == 0) wl.L[0] |= KEY_EXPANDED;
-                n_exp++;
-                const uint32_t ub = v.upper_base[cid];
-                if (ub == HX_EMPTY_SLOT) {
-                    status = HNSW_ERR_NODE_NOT_IN_GRAPH;
-                    break;
-                }
-                const uint32_t *row = v.adj_up + ((size_t)ub + layer - 1) * S;
-                uint32_t ovf = HX_EMPTY_SLOT;
-                for (uint32_t c0 = 0; c0 < S; c0 += 32) {
-                    const uint32_t slot = c0 + cslot2;
-                    uint32_t nb = HX_EMPTY_SLOT;
-                    if (slot < S) nb = row[slot];
-                    const bool is_ptr = nb != HX_EMPTY_SLOT && (nb & HX_OVF_FLAG);
-                    const bool valid = nb != HX_EMPTY_SLOT && !is_ptr;
-                    const u64 pm = __ballot(is_ptr);
-                    if (pm) ovf = (uint32_t)__builtin_amdgcn_readlane((int)nb, __ffsll((long long)pm) - 1) & ~HX_OVF_FLAG;
-                    const uint32_t cnt = (uint32_t)__popcll(__ballot(valid && h2 == 0));
-                    if (cnt == 0) continue;
-                    sum_deg += cnt;
-                    if (n_vis + cnt > vis_limit) {
-                        status = HNSW_ERR_OVERFLOW;
-                        break;
-                    }
-                    n_vis += cnt;
-                    process2(nb, valid, true);
-                    if (status != HNSW_OK) break;
-                }
-                if (status == HNSW_OK && ovf != HX_EMPTY_SLOT) {
-                    const uint32_t lo = v.ovf_off[ovf], hi = v.ovf_off[ovf + 1];
-                    for (uint32_t base = lo; base < hi; base += 32) {
-                        const uint32_t i = base + cslot2;
-                        const bool valid = i < hi;
-                        const uint32_t nb = valid ? v.ovf_nbrs[i] : HX_EMPTY_SLOT;
-                        const uint32_t cnt = (uint32_t)__popcll(__ballot(valid && h2 == 0));
-                        sum_deg += cnt;
-                        if (n_vis + cnt > vis_limit) {
-                            status = HNSW_ERR_OVERFLOW;
-                            break;
-                        }
-                        n_vis += cnt;
-                        process2(nb, valid, true);
-                        if (status != HNSW_OK) break;
-                    }
-                }
-                if (status != HNSW_OK) break;
-            }
-        }
-    }
-
-    // ------------------------------------------------------------------------------------------
-    // hand-over: wave 0 publishes (status, n_cur, list); both clear the visited table
-    // ------------------------------------------------------------------------------------------
-    wg_barrier();  // wave 1 must not touch the visited table while wave 0 walks the upper layers
-    if (wv == 0) {
-#pragma unroll
-        for (int r = 0; r < R; r++) perm0[64 * r + lane] = wl.L[r] & KEY_MASK;  // candidates ∪= selected
-        if (lane == 0) {
-            xmeta[0] = (uint32_t)status;
-            xmeta[1] = wl.n_cur;
-        }
-    }
-    for (uint32_t s = threadIdx.x; s < (hslots >> 2); s += 128)
-        reinterpret_cast<uint4 *>(htab)[s] =
-            make_uint4(HX_EMPTY_SLOT, HX_EMPTY_SLOT, HX_EMPTY_SLOT, HX_EMPTY_SLOT);
-    wg_barrier();
-    {
-        status = (int32_t)xmeta[0];  // wave 0's verdict is the workgroup's
-        wl.n_cur = xmeta[1];
-#pragma unroll
-        for (int r = 0; r < R; r++) wl.L[r] = perm0[64 * r + lane];
-    }
-    const uint32_t ef = max(1u, a.ef_bottom);
-    if (wv == 0) {  // visited ∪= ids(selected)  (searcher.rs:33)
-#pragma unroll
-        for (int r = 0; r < R; r++)
-            if (64u * r + lane < wl.n_cur) visited_insert(htab, hmask, slots_log2, (uint32_t)wl.L[r]);
-    }
-    n_vis = wl.n_cur;
-    wl.refresh_last(ef);
-    wg_barrier();  // also: xmeta / perm0 free for reuse
-
-    // ------------------------------------------------------------------------------------------
-    // layer 0: both waves, four lanes per slot, inline-rows blocks staged by LDS-DMA
-    // ------------------------------------------------------------------------------------------
-    if (status == HNSW_OK) {
-        const int g = lane >> 2, j4 = lane & 3, h = j4 >> 1, sub = j4 & 1;
-        const bool leader = j4 == 0;
-        constexpr int NCD = DS > 0 ? (DS / 8) : 1;    // chunk dwords per half
-        constexpr int NTL = DS > 0 ? (DS % 8) : 1;    // tail elements
-        QRegs2<2 * NCD> qc;
-        QRegs2<(NTL > 0 ? NTL : 1)> qt;
-        if (DS > 0) {
-#pragma unroll
-            for (int i = 0; i < 2 * NCD; i++) qc.v[i] = yq[h * nq_half + 4 * (i >> 1) + 2 * sub + (i & 1)];
-#pragma unroll
-            for (int r = 0; r < NTL; r++) qt.v[r] = yq[v.nch4 + r];
-        }
-        const QcLds qc_lds{yq + h * nq_half + 2 * sub};
-        const QLds qt_lds{yq + v.nch4};
-        uint4 w[P];
-        bool have_spec = false;
-        uint32_t spec_id = 0, spec_sel = 0, par = 0;
-        // DMA source of this lane within a block: this wave's 16 rows, 1-KiB pieces
-        const size_t dma_off = (size_t)wv * HALF_BLK + (size_t)lane * 16;
-        // where lane (g, h) reads its half row in an image
-        const uint32_t rd_off = (uint32_t)g * v.row_stride + (uint32_t)h * v.half_bytes;
-        constexpr int NPIECE = HALF_BLK / 1024;
-        // (the hot loop holds no compiler-visible VMEM load, see the one-wave kernel)
-        uint32_t ovf_pending = HX_EMPTY_SLOT;
-        bool done = false;
-        while (!done && status == HNSW_OK) {
-        while (true) {
-            STAMP(t0);
-            const int cpos = wl.first_unexpanded(lane);
-            if (cpos < 0) {
-                done = true;
-                break;
-            }
-            uint32_t cid = 0;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                if ((cpos >> 6) == r) {
-                    cid = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)wl.L[r], cpos & 63);
-                    if (lane == (cpos & 63)) wl.L[r] |= KEY_EXPANDED;
-                }
-            }
-            n_exp++;
-            const bool hit = have_spec && spec_id == cid;
-#ifdef HX_STAMPS
-            if (hit) dbg_acc[6]++;
-#endif
-            uint32_t cur_sel = spec_sel;
-            if (!hit) {
-                cur_sel = spec_sel ^ 1u;
-                const unsigned char *src = v.fat + (size_t)cid * v.fat_stride + dma_off;
-#pragma unroll
-                for (int p = 0; p < NPIECE; p++)
-                    dma_piece_to_lds(src + 1024 * p, img_lds + cur_sel * HALF_BLK + 1024u * p);
-            }
-            have_spec = false;
-            {
-                const int ppos = wl.first_unexpanded(lane);
-                if (ppos >= 0) {
-                    uint32_t pid = 0;
-#pragma unroll
-                    for (int r = 0; r < R; r++)
-                        if ((ppos >> 6) == r)
-                            pid = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)wl.L[r], ppos & 63);
-                    spec_sel = cur_sel ^ 1u;
-                    const unsigned char *src = v.fat + (size_t)pid * v.fat_stride + dma_off;
-#pragma unroll
-                    for (int p = 0; p < NPIECE; p++)
-                        dma_piece_to_lds(src + 1024 * p, img_lds + spec_sel * HALF_BLK + 1024u * p);
-                    spec_id = pid;
-                    have_spec = true;
-                }
-            }
-            if (have_spec)
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPIECE) : "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            {
-                const uint4 *src = reinterpret_cast<const uint4 *>(img + cur_sel * HALF_BLK + rd_off);
-#pragma unroll
-                for (int p = 0; p < P; p++) w[p] = src[p];
-            }
-            STAMP(t1);
-            STAMP_ADD(0, t0, t1);
-            // neighbour id: last 4 bytes of half 0, held by lanes h == 0 of the quad
-            const uint32_t nb = (uint32_t)quad_bcast_i<0>((int)w[P - 1].w);
-            const bool is_ptr = nb != HX_EMPTY_SLOT && (nb & HX_OVF_FLAG);
-            const bool valid = nb != HX_EMPTY_SLOT && !is_ptr;
-            uint32_t ovf = HX_EMPTY_SLOT;
-            {
-                const u64 pm = __ballot(is_ptr && leader);
-                if (pm) ovf = (uint32_t)__builtin_amdgcn_readlane((int)nb, __ffsll((long long)pm) - 1) & ~HX_OVF_FLAG;
-            }
-            const uint32_t cnt = (uint32_t)__popcll(__ballot(valid && leader));
-            sum_deg += cnt;
-            int32_t lstat = HNSW_OK;
-            if (n_vis + 32 > vis_limit) lstat = HNSW_ERR_OVERFLOW;  // both waves reach the same verdict
-            u64 key = KEY_INVALID;
-            if (lstat == HNSW_OK && cnt != 0) {
-                bool f = false;
-                if (valid && leader) f = visited_insert(htab, hmask, slots_log2, nb);
-                const bool fresh = quad_bcast_i<0>(f ? 1 : 0) != 0;
-                const u64 fm = __ballot(fresh && leader);
-                STAMP(t2);
-                STAMP_ADD(1, t1, t2);
-                if (fm != 0) {
-                    n_dist += (uint32_t)__popcll(fm);
-                    float acc[2] = {0.0f, 0.0f};
-                    if (fresh) {
-                        if (DS > 0)
-                            quant_pair_sums<P, DS>(w, qc, qt, h, sub, v.nch4, v.rem, acc);
-                        else
-                            quant_pair_sums<P, 0>(w, qc_lds, qt_lds, h, sub, v.nch4, v.rem, acc);
-                    }
-                    // a0 .. a7 in order: lane 0 holds a0 a1, lane 1 a2 a3, lane 2 a4 a5, lane 3 a6 a7
-                    float s = 0.0f;
-                    s += quad_bcast<0>(acc[0]);
-                    s += quad_bcast<0>(acc[1]);
-                    s += quad_bcast<1>(acc[0]);
-                    s += quad_bcast<1>(acc[1]);
-                    s += quad_bcast<2>(acc[0]);
-                    s += quad_bcast<2>(acc[1]);
-                    s += quad_bcast<3>(acc[0]);
-                    s += quad_bcast<3>(acc[1]);
-                    const float dist = __builtin_sqrtf(s);
-                    if (fresh && leader) {
-                        if (dist != dist)
-                            lstat = HNSW_ERR_NAN_INPUT;
-                        else
-                            key = ((u64)__builtin_bit_cast(uint32_t, dist) << 32) | nb;
-                    }
-                }
-            }
-            if (__ballot(lstat == HNSW_ERR_NAN_INPUT)) lstat = HNSW_ERR_NAN_INPUT;
-            STAMP(t3);
-            STAMP_ADD(2, t1, t3);
-            // ---- exchange: keys of my 16 slots, my counts / verdict / overflow pointer ----
-            u64 *xk = xkeys + 32 * par;
-            uint32_t *xm = xmeta + 8 * par;
-            if (leader) xk[16 * wv + g] = key;
-            if (lane == 0) {
-                xm[4 * wv + 0] = cnt;
-                xm[4 * wv + 1] = (uint32_t)lstat;
-                xm[4 * wv + 2] = ovf;
-            }
-            wg_barrier();
-            const uint32_t ow = 1u - (uint32_t)wv;
-            const u64 okey = (j4 == 1) ? xk[16 * ow + g] : KEY_INVALID;
-            const uint32_t ocnt = xm[4 * ow + 0];
-            const int32_t ostat = (int32_t)xm[4 * ow + 1];
-            const uint32_t oovf = xm[4 * ow + 2];
-            par ^= 1u;
-            if (lstat == HNSW_OK) lstat = ostat;
-            if (lstat != HNSW_OK) {
-                status = lstat;
-                break;
-            }
-            n_vis += cnt + ocnt;
-            STAMP(t4);
-            STAMP_ADD(3, t3, t4);
-            wl.merge(leader ? key : okey, ef, perm, lane);
-            STAMP(t5);
-            STAMP_ADD(5, t4, t5);
-            if (ovf == HX_EMPTY_SLOT) ovf = oovf;
-            if (ovf != HX_EMPTY_SLOT) {
-                ovf_pending = ovf;
-                break;
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no prefetch in flight outside the hot loop
-        have_spec = false;
-        if (done || status != HNSW_OK) break;
-            {
-                // degree > 32: the rest of the row lives in the overflow CSR (compact rows).  Wave 0
-                // evaluates it, two lanes per neighbour, and publishes the keys; both waves merge.
-                const uint32_t ovf = ovf_pending;
-                ovf_pending = HX_EMPTY_SLOT;
-                const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)asm_ld32(v.ovf_off + ovf));
-                const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)asm_ld32(v.ovf_off + ovf + 1));
-                for (uint32_t base = lo; base < hi; base += 32) {
-                    u64 *xk2 = xkeys + 32 * par;
-                    uint32_t *xm2 = xmeta + 8 * par;
-                    if (wv == 0) {
-                        const int h2 = lane & 1;
-                        const uint32_t i = base + (lane >> 1);
-                        const bool ov = i < hi;
-                        const uint32_t onb = ov ? asm_ld32(v.ovf_nbrs + i) : HX_EMPTY_SLOT;
-                        const uint32_t c2 = (uint32_t)__popcll(__ballot(ov && h2 == 0));
-                        int32_t st2 = HNSW_OK;
-                        u64 k2 = KEY_INVALID;
-                        if (n_vis + c2 > vis_limit) {
-                            st2 = HNSW_ERR_OVERFLOW;
-                        } else {
-                            bool f = false;
-                            if (ov && h2 == 0) f = visited_insert(htab, hmask, slots_log2, onb);
-                            const bool fresh = (pair_swap_i(f ? 1 : 0) | (f ? 1 : 0)) != 0;
-                            n_dist += (uint32_t)__popcll(__ballot(fresh && h2 == 0));
-                            float acc4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                            if (fresh) {
-                                const uint4 *src = reinterpret_cast<const uint4 *>(
-                                    v.rows + (size_t)onb * v.row_stride + (size_t)h2 * v.half_bytes);
-                                uint4 w2[P];
-#pragma unroll
-                                for (int p = 0; p < P; p++) w2[p] = asm_ld128(src + p);
-                                const QLds ql{yq + h2 * nq_half};
-                                quant_half_sums<P, 0>(w2, ql, h2, v.nch4, v.rem, acc4);
-                            }
-                            const float c0 = pair_swap(acc4[0]), c1 = pair_swap(acc4[1]),
-                                        c2b = pair_swap(acc4[2]), c3 = pair_swap(acc4[3]);
-                            float sm = 0.0f;
-                            sm += acc4[0];
-                            sm += acc4[1];
-                            sm += acc4[2];
-                            sm += acc4[3];
-                            sm += c0;
-                            sm += c1;
-                            sm += c2b;
-                            sm += c3;
-                            const float dist = __builtin_sqrtf(sm);
-                            if (fresh && h2 == 0) {
-                                if (dist != dist)
-                                    st2 = HNSW_ERR_NAN_INPUT;
-                                else
-                                    k2 = ((u64)__builtin_bit_cast(uint32_t, dist) << 32) | onb;
-                            }
-                            if (__ballot(st2 != HNSW_OK)) st2 = HNSW_ERR_NAN_INPUT;
-                        }
-                        sum_deg += c2;
-                        if (h2 == 0) xk2[lane >> 1] = k2;
-                        if (lane == 0) {
-                            xm2[0] = c2;
-                            xm2[1] = (uint32_t)st2;
-                        }
-                    }
-                    wg_barrier();
-                    const u64 k3 = ((lane & 1) == 0) ? xk2[lane >> 1] : KEY_INVALID;
-                    const uint32_t c3 = xm2[0];
-                    const int32_t st3 = (int32_t)xm2[1];
-                    par ^= 1u;
-                    if (st3 != HNSW_OK) {
-                        status = st3;
-                        break;
-                    }
-                    n_vis += c3;
-                    wl.merge(k3, ef, perm, lane);
-                }
-            }
-        }
-    }
-    // drain any prefetch still in flight before the LDS is released
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-    // ------------------------------------------------------------------------------------------
-    // results: wave 1 hands its counters over, wave 0 writes (results.rs:59-61)
-    // ------------------------------------------------------------------------------------------
-    wg_barrier();
-    if (wv == 1 && lane == 0) {
-        xmeta[0] = n_dist;
-        xmeta[1] = sum_deg;
-    }
-    wg_barrier();
-#ifdef HX_STAMPS
-    if (wv == 0 && lane == 0 && a.dbg) {
-        dbg_acc[4] = __builtin_readcyclecounter() - t_begin;
-        for (int i = 0; i < 8; i++) a.dbg[(size_t)q * 8 + i] = dbg_acc[i];
-    }
-#endif
-    if (wv == 0) {
-        n_dist += xmeta[0];
-        sum_deg += xmeta[1];
-        const uint32_t count = status == HNSW_OK ? min(a.n, wl.n_cur) : 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t idx = 64u * r + lane;
-            if (idx < a.n) {
-                const bool have = idx < count;
-                a.out_ids[(size_t)q * a.n + idx] = have ? (uint32_t)wl.L[r] : HX_EMPTY_SLOT;
-                if (a.out_dists)
-                    a.out_dists[(size_t)q * a.n + idx] =
-                        have ? __builtin_bit_cast(float, (uint32_t)((wl.L[r] & KEY_MASK) >> 32))
-                             : __builtin_inff();
-            }
-        }
-        for (uint32_t idx = 64u * R + lane; idx < a.n; idx += 64) {
-            a.out_ids[(size_t)q * a.n + idx] = HX_EMPTY_SLOT;
-            if (a.out_dists) a.out_dists[(size_t)q * a.n + idx] = __builtin_inff();
-        }
-        if (lane == 0) {
-            if (a.out_counts) a.out_counts[q] = count;
-            hnsw_query_stats st;
-            st.n_dist = n_dist;
-            st.n_exp = n_exp;
-            st.sum_deg = sum_deg;
-            st.status = status;
-            a.out_stats[q] = st;
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
@@ -1312,47 +780,12 @@ static int launch_one(const DevView &v, const SearchArgs &a_in, uint32_t nblocks
                           hx_search_kernel<KIND, P, DS, R, FAT>, dim3(nblocks), dim3(64), lds, stream, v, a, slots_log2);
 }
 
-template <int P, int DS, int R>
-static int launch_two(const DevView &v, const SearchArgs &a, uint32_t nblocks, uint32_t slots_log2,
-                      hipStream_t stream) {
-    const size_t lds = (4ull << slots_log2) + 2ull * 64 * R * 8 + 2 * 32 * 8 + 2 * 2 * 4 * 4 +
-                       2 * (size_t)query_lds_bytes(v) + 2ull * 2 * (16ull * 32 * P);
-    return launch_checked({"two-wave search kernel launch", "search needs %zu bytes of LDS (> 160 KiB)"},
-                          hx_search2_kernel<P, DS, R>, dim3(nblocks), dim3(128), lds, stream, v, a, slots_log2);
-}
-
-// The two-wave kernel is opt-in (HNSW_MI355X_WAVES=2): measured on MI355X at 1M x 100d, batch 1024
-// it takes 0.207 ms per batch against 0.185 ms for the one-wave kernel -- halving the distance work
-// per wave does not pay for the key exchange + barrier and the replicated merge, because the loop
-// is bound by instruction latency (about 750 instructions at ~5 cycles each per expansion), not by
-// issue bandwidth.  Kept because it is parity-tested and documents the design point.
-static bool want_two_waves(uint32_t) {
-    static int forced = -1;
-    if (forced < 0) {
-        const char *e = getenv("HNSW_MI355X_WAVES");
-        forced = e ? atoi(e) : 0;
-    }
-    return forced == 2;
-}
-
 template <int KIND, int P, int DS>
 static int launch_r(const DevView &v, const SearchArgs &a, uint32_t nblocks, uint32_t slots_log2,
                     hipStream_t stream, uint32_t ef_max) {
     // the inline-rows variant needs one pass to cover a whole layer-0 row
     // (block images of rows wider than 5 pieces per half would not leave 4 waves per CU: not built)
     constexpr bool CAN_FAT = (KIND == HNSW_VEC_QUANT8 && P > 0 && P <= 5);
-    // (row_stride == 32 P and 16 row_stride % 1024 == 0 together need an even P: the odd ones are not built)
-    if constexpr (CAN_FAT && P % 2 == 0) {
-        // 16 rows per wave must be whole 1-KiB DMA pieces: row_stride * 16 % 1024 == 0
-        if (v.fat != nullptr && v.S0 == 32 && a.layer_lo == 0 && a.entries == nullptr &&
-            a.layer_hi == (int32_t)v.nb_layers - 1 && a.ef_upper == 1 && (16u * v.row_stride) % 1024u == 0 &&
-            v.row_stride == 32u * P && want_two_waves(nblocks)) {
-            if (ef_max <= 64) return launch_two<P, DS, 1>(v, a, nblocks, slots_log2, stream);
-            if (ef_max <= 128) return launch_two<P, DS, 2>(v, a, nblocks, slots_log2, stream);
-            if (ef_max <= 256) return launch_two<P, DS, 4>(v, a, nblocks, slots_log2, stream);
-            if (ef_max <= 512) return launch_two<P, DS, 8>(v, a, nblocks, slots_log2, stream);
-        }
-    }
     // the inline-rows loop stages two block images in LDS; it is used while a wave still needs no more
     // than a quarter of the CU's LDS, so that 1024 waves fit the chip in one round
     const uint32_t r_list = ef_max <= 64 ? 1 : ef_max <= 128 ? 2 : ef_max <= 256 ? 4 : 8;
@@ -1697,8 +1130,7 @@ int launch_search(const DevView &v, const SearchArgs &a_in, uint32_t nblocks, ui
                   hipStream_t stream) {
     if (nblocks == 0) return HNSW_OK;
     SearchArgs a = a_in;
-    static const bool one_row = getenv("HNSW_MI355X_ONE_ROW") && atoi(getenv("HNSW_MI355X_ONE_ROW")) != 0;
-    if (one_row) a.flags |= 1u;
+    if (sw::one_row()) a.flags |= 1u;
     uint32_t ef_max = std::max(1u, a.ef_bottom);
     if (a.layer_hi > a.layer_lo) ef_max = std::max(ef_max, a.ef_upper);
     if (a.entries) ef_max = std::max(ef_max, a.n_entry);

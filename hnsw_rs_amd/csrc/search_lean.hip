@@ -39,6 +39,7 @@
 #include "device_index.h"
 #include "launch.h"
 #include "search_common.h"
+#include "switches.h"
 
 namespace hx {
 namespace {
@@ -1495,24 +1496,19 @@ int launch_lean_one(const LeanArgs &a_in, uint32_t nblocks, hipStream_t stream) 
 // Whether the lean kernel serves this search: the whole ann_by_vector descent over f32 rows of a
 // dimension it is built for, lists of up to four registers (ef <= 256).  HNSW_MI355X_LEAN=0 turns it off (A/B).
 bool lean_applicable(const DevView &v, const SearchArgs &a, uint32_t ef_max) {
-    static const bool enabled = !(getenv("HNSW_MI355X_LEAN") && atoi(getenv("HNSW_MI355X_LEAN")) == 0);
-    if (!enabled) return false;
-    static const bool q8_enabled = !(getenv("HNSW_MI355X_LEAN_Q8") && atoi(getenv("HNSW_MI355X_LEAN_Q8")) == 0);
-    static const bool coop128 = !(getenv("HNSW_MI355X_LEAN_128") && atoi(getenv("HNSW_MI355X_LEAN_128")) == 0);
+    if (!sw::lean()) return false;
     const bool f32_ok = v.kind == HNSW_VEC_F32 && ((v.dim == 100 && v.row_stride == 400) ||
-                                                     (coop128 && v.dim == 128 && v.row_stride == 512));
-    const bool q8_ok = q8_enabled && v.kind == HNSW_VEC_QUANT8 && v.dim == 100 && v.row_stride == 128 && v.half_bytes == 64;
+                                                     (sw::lean_128() && v.dim == 128 && v.row_stride == 512));
+    const bool q8_ok = sw::lean_q8_enabled() && v.kind == HNSW_VEC_QUANT8 && v.dim == 100 && v.row_stride == 128 && v.half_bytes == 64;
     if (!f32_ok && !q8_ok) return false;
     if (a.entries != nullptr || a.layer_lo != 0 || a.layer_hi != (int32_t)v.nb_layers - 1) return false;
     if (a.layer_hi > 0 && a.ef_upper != 1) return false;
     // lists: one register (ef <= 64), head + tail (<= 128), four interleaved registers (<= 256, HNSW_MI355X_LEAN_WIDE=0
     // sends those to the generic kernel, for A/B runs)
-    static const bool wide = !(getenv("HNSW_MI355X_LEAN_WIDE") && atoi(getenv("HNSW_MI355X_LEAN_WIDE")) == 0);
     // (five to eight registers, 256 < ef <= 512: d = 100, both kinds -- round 3: f32 only, x 1.28 against the generic kernel,
     // quant8 gained nothing with the one-level 64-KiB table; round 4: the two-level visited set keeps four waves per CU)
-    static const bool q8_wide = !(getenv("HNSW_MI355X_LEAN_Q8_WIDE") && atoi(getenv("HNSW_MI355X_LEAN_Q8_WIDE")) == 0);
-    const bool to512 = (v.dim == 100 && (v.kind == HNSW_VEC_F32 || q8_wide)) || (v.dim == 128 && v.kind == HNSW_VEC_F32);
-    if (v.S0 > 32 || v.S1 > 64 || ef_max > (wide ? (to512 ? 512u : 256u) : 128u) || (a.flags & 1u)) return false;
+    const bool to512 = (v.dim == 100 && (v.kind == HNSW_VEC_F32 || sw::lean_q8_wide())) || (v.dim == 128 && v.kind == HNSW_VEC_F32);
+    if (v.S0 > 32 || v.S1 > 64 || ef_max > (sw::lean_wide() ? (to512 ? 512u : 256u) : 128u) || (a.flags & 1u)) return false;
     return true;
 }
 
@@ -1539,8 +1535,7 @@ int launch_lean(const DevView &v, const SearchArgs &s, uint32_t nblocks, uint32_
     a.n = s.n;
     a.slots_log2 = slots_log2;
     a.dbg = s.dbg;
-    // 64 < ef <= 128: head + tail list (HNSW_MI355X_LIST=interleaved: round 2's two-register list, for A/B runs); 128 < ef <= 256: four interleaved registers
-    static const bool interleaved = getenv("HNSW_MI355X_LIST") && getenv("HNSW_MI355X_LIST")[0] == 'i';
+    // 64 < ef <= 128: head + tail list; 128 < ef <= 256: four interleaved registers
     if (v.kind == HNSW_VEC_QUANT8) {
         if (a.ef <= 64) return launch_lean_q8<Lst<1>>(a, nblocks, stream);
         if (a.ef > 448) return launch_lean_q8<Lst<8>>(a, nblocks, stream);  // (round 4: 256 < ef <= 512 with the two-level visited set)
@@ -1548,7 +1543,6 @@ int launch_lean(const DevView &v, const SearchArgs &s, uint32_t nblocks, uint32_
         if (a.ef > 320) return launch_lean_q8<Lst<6>>(a, nblocks, stream);
         if (a.ef > 256) return launch_lean_q8<Lst<5>>(a, nblocks, stream);
         if (a.ef > 128) return launch_lean_q8<Lst<4>>(a, nblocks, stream);
-        if (interleaved) return launch_lean_q8<Lst<2>>(a, nblocks, stream);
         return launch_lean_q8<LstHT>(a, nblocks, stream);
     }
     if (v.dim == 128) {  // whole-line rows: the cooperative gather (HNSW_MI355X_LEAN_128=0: the generic kernel, for A/B runs)
@@ -1560,9 +1554,8 @@ int launch_lean(const DevView &v, const SearchArgs &s, uint32_t nblocks, uint32_
         return few ? launch_lean_one<128, LstHT, 4>(a, nblocks, stream) : launch_lean_one<128, LstHT, 2>(a, nblocks, stream);
     }
     // two waves per query (pair_kernel.inc): launches that leave the SIMDs a wave or two each
-    static const int pair_mode = getenv("HNSW_MI355X_PAIR") ? atoi(getenv("HNSW_MI355X_PAIR")) : 0;
     // (a.qsel: a re-run of the queries a first launch gave up -- those take the one-wave kernel)
-    if (pair_mode != 0 && a.ef <= 128 && !interleaved && a.qsel == nullptr) {
+    if (sw::pair_mode() != 0 && a.ef <= 128 && a.qsel == nullptr) {
         if (a.ef <= 64) return launch_pair<100, Lst<1>>(a, nblocks, stream);
         return launch_pair<100, LstHT>(a, nblocks, stream);
     }
@@ -1574,7 +1567,6 @@ int launch_lean(const DevView &v, const SearchArgs &s, uint32_t nblocks, uint32_
     if (a.ef > 320) return launch_lean_one<100, Lst<6>>(a, nblocks, stream);
     if (a.ef > 256) return launch_lean_one<100, Lst<5>>(a, nblocks, stream);
     if (a.ef > 128) return launch_lean_one<100, Lst<4>>(a, nblocks, stream);
-    if (interleaved) return launch_lean_one<100, Lst<2>>(a, nblocks, stream);
     return launch_lean_one<100, LstHT>(a, nblocks, stream);
 }
 

@@ -30,10 +30,7 @@ MANY = 1100  # queries of a launch with more than 4 waves per CU on MI355X's 256
 
 GROUPS = {
     "default": {},
-    # the two-wave inline-rows kernel; at d = 100 only once the lean 8-bit kernel steps aside
-    "waves2": {"HNSW_MI355X_WAVES": "2", "HNSW_MI355X_LEAN_Q8": "0"},
     "pair": {"HNSW_MI355X_PAIR": "1"},
-    "list_i": {"HNSW_MI355X_LIST": "i"},
     # the LDS level of the two-level visited set closes after 300 ids: every wide search goes on in the HBM level
     "visited2l": {"HNSW_MI355X_VISITED_2L_LIMIT": "300"},
 }
@@ -128,19 +125,11 @@ for lst, ef, ck, nq in (("Lst<1>", 10, 4, N_QUERIES), ("LstHT", 100, 4, N_QUERIE
         case("hx_lean_f32_kernel<128, %s, %d>" % (lst, ck), F32, 128, 16, 0, "batch", ef, group="visited2l")
 
 # ---- opt-in forms (environment groups)
-for p, d in ((2, 40), (4, 104), (4, 100)):
-    ds = 100 if d == 100 else 0
-    for r in (1, 2, 4, 8):
-        case("hx_search2_kernel<%d, %d, %d>" % (p, ds, r), Q8, d, 16, 1, "batch", EF_R[r], group="waves2")
-        if r == 8:
-            case("hx_search2_kernel<%d, %d, %d>" % (p, ds, r), Q8, d, 16, 1, "batch", EF_TOP[8], group="waves2")
 # (a query the two-wave pair gives up -- HNSW_ERR_OVERFLOW, pair_kernel.inc -- runs again on the one-wave kernel)
 case("hx_pair_f32_kernel<100, Lst<1> >", F32, 100, 16, 0, "batch", 10, group="pair",
      may=["hx_lean_f32_kernel<100, Lst<1>, 4>"])
 case("hx_pair_f32_kernel<100, LstHT>", F32, 100, 16, 0, "batch", 100, group="pair",
      may=["hx_lean_f32_kernel<100, LstHT, 4>"])
-case("hx_lean_f32_kernel<100, Lst<2>, 4>", F32, 100, 16, 0, "batch", 100, group="list_i")
-case("hx_lean_q8_kernel<Lst<2> >", Q8, 100, 16, 0, "batch", 100, group="list_i")
 
 # ---- filtered search: the graph kernel at one, two and four list registers per (kind, dimension) form; the exact
 # path's compaction, scan and merge

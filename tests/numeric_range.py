@@ -53,8 +53,8 @@ OVER_P = {}
 # ---- the table -------------------------------------------------------------------------------------------------------
 # A distance routine is a kernel family with its template arguments minus the list width (the position below): the
 # distance code of hx_search_kernel<KIND, P, DS, R, FAT> is the same for every R.  A family not listed has no width.
-WIDTH_ARG = {"hx_search_kernel": 3, "hx_lean_q8_kernel": 0, "hx_lean_f32_kernel": 1, "hx_search2_kernel": 2,
-             "hx_pair_f32_kernel": 1, "hx_filt_graph_kernel": 3}
+WIDTH_ARG = {"hx_search_kernel": 3, "hx_lean_q8_kernel": 0, "hx_lean_f32_kernel": 1, "hx_pair_f32_kernel": 1,
+             "hx_filt_graph_kernel": 3}
 # entry points the runner knows (the selection takes no "device" call: its rows have a "batch" call at the same ef)
 ENTRIES = ("batch", "layer", "distance", "brute", "filtered", "filtered_exact", "brute_fast")
 

@@ -31,9 +31,9 @@ def test_lean_kernels_fit_two_waves_per_simd_without_agprs_or_scratch(tmp_path):
         if m and cur is not None:
             cur[m.group(1).strip()] = int(m.group(2))
     timed = {k: v for k, v in kernels.items() if "hx_lean_f32_kernel" in k or "hx_lean_q8_kernel" in k}
-    # f32 100d and quant8: one register, head + tail, interleaved two (A/B), interleaved four (ef 129..256); f32 128d
-    # (cooperative gather): one register and head + tail at two stage depths each, interleaved four
-    assert len(timed) == 23, sorted(kernels)  # (+ five to eight interleaved registers for ef 257..512: f32 100d, quant8; six / eight for f32 128d)
+    # f32 100d and quant8: one register, head + tail, interleaved four (ef 129..256); f32 128d (cooperative gather): one
+    # register and head + tail at two stage depths each, interleaved four
+    assert len(timed) == 21, sorted(kernels)  # (+ five to eight interleaved registers for ef 257..512: f32 100d, quant8; six / eight for f32 128d)
     # the two-wave form (pair_kernel.inc, opt-in): one register and head + tail; a workgroup is two waves, four
     # workgroups per CU by LDS, so it must stay within 256 registers without scratch
     pair = {k: v for k, v in kernels.items() if "hx_pair_f32_kernel" in k}
