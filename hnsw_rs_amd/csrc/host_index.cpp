@@ -903,21 +903,28 @@ int HostIndex::import_layer(uint32_t layer, uint64_t n_nodes, const NodeID *node
                   (unsigned long long)(layer < nb_layers() ? layer_nodes[layer].size() : 0));
         return HNSW_ERR_ARG;
     }
+    // every row is checked before the first is written: a refused call imports nothing
     for (uint64_t i = 0; i < n_nodes; i++) {
         const NodeID id = node_ids[i];
         if (!in_layer(layer, id)) {
             set_error("import_layer %u: node %u has a lower level", layer, id);
             return HNSW_ERR_NODE_NOT_IN_GRAPH;
         }
-        std::vector<NodeID> &r = row(layer, id);
-        r.clear();
         for (uint64_t k = offsets[i]; k < offsets[i + 1]; k++) {
+            if (nbrs[k] == id) {  // graph.rs:38-40: no Graph of the reference holds one (add_edge above)
+                set_error("import_layer %u: self connection on node %u", layer, id);
+                return HNSW_ERR_SELF_CONNECTION;
+            }
             if (!in_layer(layer, nbrs[k])) {
                 set_error("import_layer %u: neighbour %u of %u not in layer", layer, nbrs[k], id);
                 return HNSW_ERR_NODE_NOT_IN_GRAPH;
             }
-            row_insert(r, nbrs[k]);
         }
+    }
+    for (uint64_t i = 0; i < n_nodes; i++) {
+        std::vector<NodeID> &r = row(layer, node_ids[i]);
+        r.clear();
+        for (uint64_t k = offsets[i]; k < offsets[i + 1]; k++) row_insert(r, nbrs[k]);
     }
     version++;
     return HNSW_OK;

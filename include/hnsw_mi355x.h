@@ -144,7 +144,11 @@ int hnsw_insert_vec(hnsw_index *h, const float *v, uint32_t *out_id);
 int hnsw_insert_vec_level(hnsw_index *h, const float *v, int level /* < 0: draw */, uint32_t *out_id);
 
 /* Adopt a prebuilt graph (e.g. one built by another implementation of the reference) instead of
- * building: points first, then layers 0,1,2,... as CSR over ascending node ids, then the ep. */
+ * building: points first, then layers 0,1,2,... as CSR over ascending node ids, then the ep.
+ * hnsw_import_layer checks every row before it writes the first: a node or a neighbour that the levels do not
+ * put on the layer is HNSW_ERR_NODE_NOT_IN_GRAPH, a row that holds its own node is HNSW_ERR_SELF_CONNECTION
+ * (graph/src/graph.rs:38-40: no graph of the reference holds one; hnsw_last_error names the node), and a
+ * refused call imports nothing. */
 int hnsw_import_points(hnsw_index *h, const float *rows, uint64_t n, const uint8_t *levels);
 int hnsw_import_layer(hnsw_index *h, uint32_t layer, uint64_t n_nodes, const uint32_t *node_ids,
                       const uint64_t *offsets, const uint32_t *nbrs);

@@ -539,6 +539,10 @@ int orc_import_points_quant(orc_index *h, const uint8_t *codes, const float *min
 int orc_import_layer(orc_index *h, uint32_t layer, uint64_t n_nodes, const uint32_t *node_ids,
                      const uint64_t *offsets, const uint32_t *nbrs) {
     if (layer != h->layers.len()) return ORC_ERR_ARG;
+    // graph.rs:38-40: add_edge refuses a self connection, so no Graph of the reference holds one
+    for (uint64_t i = 0; i < n_nodes; i++)
+        for (uint64_t k = offsets[i]; k < offsets[i + 1]; k++)
+            if (nbrs[k] == node_ids[i]) return ORC_ERR_ARG;
     h->layers.add_level(layer);
     Graph &g = h->layers.levels[layer];
     g.nodes.reserve(n_nodes);

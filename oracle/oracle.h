@@ -93,7 +93,8 @@ int orc_insert_vec(orc_index *, const float *v, uint8_t level, uint32_t *out_id)
 int orc_import_points(orc_index *, const float *rows, uint64_t n, const uint8_t *levels);
 int orc_import_points_quant(orc_index *, const uint8_t *codes, const float *mins,
                             const float *deltas, uint64_t n, const uint8_t *levels);
-/* nodes of one layer with CSR adjacency; layers must be imported in order 0,1,2,... */
+/* nodes of one layer with CSR adjacency; layers must be imported in order 0,1,2,...  A row that holds its own
+ * node is ORC_ERR_ARG and nothing is imported (graph.rs:38-40: no Graph of the reference holds one). */
 int orc_import_layer(orc_index *, uint32_t layer, uint64_t n_nodes, const uint32_t *node_ids,
                      const uint64_t *offsets, const uint32_t *nbrs);
 void orc_set_ep(orc_index *, uint32_t ep);

@@ -204,12 +204,13 @@ def _calls(c, idx, orc, vs, Q, n):
     import hnsw_rs_amd as H
     from tests.util import assert_search_equal
     what = "%s n=%d" % (call_id(c), n)
+    n_points = vs.shape[0]  # (N_POINTS for the matrix's own fixtures)
     if c.entry == "batch":
         out = {}
         return (lambda: out.setdefault("r", idx.search_batch(Q, n, c.ef)),
                 lambda: assert_search_equal(out["r"], orc.search_batch(Q, n, c.ef, nthreads=8), what))
     if c.entry == "layer":
-        ent = np.arange(c.ent, dtype=np.uint32) * 3 % N_POINTS
+        ent = np.arange(c.ent, dtype=np.uint32) * 3 % n_points
         qs = Q[-8:]  # a few queries, the edge ones among them: every call is one launch
         out = []
 
@@ -242,7 +243,7 @@ def _calls(c, idx, orc, vs, Q, n):
             assert_search_equal(got, orc.search_batch(Q, n, c.ef, nthreads=8), what)
         return run, check
     if c.entry == "distance":
-        ids = (np.arange(N_POINTS, dtype=np.uint32)[::-1] * 7 % N_POINTS).astype(np.uint32)
+        ids = (np.arange(n_points, dtype=np.uint32)[::-1] * 7 % n_points).astype(np.uint32)
         out = []
 
         def check():
@@ -266,7 +267,7 @@ def _calls(c, idx, orc, vs, Q, n):
     if c.entry in ("filtered", "filtered_exact"):
         from tests.test_gpu_filtered import check as fcheck, restated
         rng = np.random.default_rng(c.d * 31 + c.ef)
-        allow = rng.random(N_POINTS) < 0.5
+        allow = rng.random(n_points) < 0.5
         exact_max = 10 ** 9 if c.entry == "filtered_exact" else -1
         ridx = restated(idx, vs)
         return (lambda: fcheck(idx, ridx, Q, n, c.ef, allow, exact_max=exact_max, what=what)), (lambda: None)
