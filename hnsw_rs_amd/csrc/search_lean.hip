@@ -89,6 +89,7 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 }
 #define STAMP(var) const unsigned long long var = stamp_now()
 #define STAMP_ADD(slot, a, b) dbg_acc[slot] += (b) - (a)
+constexpr int HX_LEAN_DBG_SLOTS = 26;  // values per query in the side buffer (scripts/stamps_lean.py allocates it)
 #else
 #define STAMP(var)
 #define STAMP_ADD(slot, a, b)
@@ -639,6 +640,11 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     // query's 128 values still fit beside the stage ring
     constexpr bool COOP = coop_rows<HNSW_VEC_F32, DS>();
     constexpr bool SPILLV = R >= 6;  // ef > 320: the visited set may continue in HBM (Visited::look2)
+    // a runner-up's miss is foreseen from the pass's keys and the follow-up pass's rows requested before c's merge
+    // (layer 0, below); the cooperative and the wide-list kernels keep their pass as it was
+    constexpr bool MISS_AHEAD = !COOP && !SPILLV;
+    // ... and where that runner-up is p again, p's lanes keep the distances they hold (lists of at most two registers)
+    constexpr bool MISS_KEEP = MISS_AHEAD && R <= 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
     const uint32_t q = a.qsel ? a.qsel[blockIdx.x] : blockIdx.x;
@@ -656,8 +662,11 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     uint32_t n_dist = 0, n_exp = 0, sum_deg = 0, n_vis = 0;
     int32_t status = HNSW_OK;
 #ifdef HX_STAMPS
-    unsigned long long dbg_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long dbg_acc[HX_LEAN_DBG_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long t_begin = __builtin_readcyclecounter();
+    // the runner-up's misses (slots 16 .. 24): what the last miss predicted for the pass that follows it
+    bool dbg_follow = false, dbg_took_pre = false;
+    uint32_t dbg_pred_c = HX_EMPTY_SLOT, dbg_pred_p = HX_EMPTY_SLOT, dbg_old_p = HX_EMPTY_SLOT;
 #endif
 
     // ---- the query: every lane holds all DS values (Point::new of a FullVec is the vector itself) ----
@@ -838,6 +847,9 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
         const uint32_t slot = (uint32_t)lane & 31u;
         // the adjacency rows fetched ahead for the pass after this one (see below)
         uint32_t pre_nb = HX_EMPTY_SLOT, pre_c = HX_EMPTY_SLOT, pre_p = HX_EMPTY_SLOT;
+        // a missed runner-up that is foreseen as the next pass's runner-up: the distances its lanes hold (MISS_KEEP)
+        bool carry = false;
+        float kdist = 0.0f;
 
         // the part of c's row that did not fit its S0 slots (degree > S0, rare), 32 ids per pass
         uint32_t ovf_lo = 0, ovf_hi = 0;
@@ -850,6 +862,8 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             }
             int ppos = -1;
             uint32_t pid = HX_EMPTY_SLOT;
+            u64 pkey = 0;  // p's key (MISS_AHEAD); 0 = no runner-up: no key is below it
+            bool kept = false;  // p's lanes hold p's row and its distances from the pass before (MISS_KEEP)
             uint32_t nb = HX_EMPTY_SLOT;
             const bool ovf_pass = ovf_lo < ovf_hi;
             if (HX_UNLIKELY(ovf_pass)) {
@@ -865,15 +879,32 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 if (HX_UNLIKELY(cpos < 0)) break;  // candidates exhausted / only worse ones left (searcher.rs:35,41-44)
                 ppos = lst.take_first(U);
                 const uint32_t cid = lst.id_at((uint32_t)cpos);
-                if (ppos >= 0) pid = lst.id_at((uint32_t)ppos);
+                if constexpr (MISS_AHEAD) {
+                    if (ppos >= 0) {
+                        pkey = lst.key_at((uint32_t)ppos);  // (unexpanded: no flag to drop)
+                        pid = (uint32_t)pkey;
+                    }
+                } else {
+                    if (ppos >= 0) pid = lst.id_at((uint32_t)ppos);
+                }
                 lst.mark((uint32_t)cpos, lane);
                 n_exp++;
+#ifdef HX_STAMPS
+                if (dbg_follow) {
+                    if (cid == dbg_pred_c && pid == dbg_pred_p) dbg_acc[19]++;
+                    if (pid == dbg_old_p) dbg_acc[20]++;
+                    dbg_follow = false;
+                }
+                dbg_took_pre = pre_c == cid && pre_p == pid;
+#endif
                 if (HX_LIKELY(pre_c == cid && pre_p == pid)) {
                     nb = pre_nb;  // both rows were requested during the previous pass
+                    if constexpr (MISS_KEEP) kept = carry;
                 } else {
                     if (slot < S0 && (!upper || ppos >= 0)) nb = a.adj0[(size_t)(upper ? pid : cid) * S0 + slot];
                 }
                 pre_c = HX_EMPTY_SLOT;
+                carry = false;
             }
 #ifdef HX_STAMPS
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -881,6 +912,12 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
 #endif
             STAMP(f1);
             STAMP_ADD(0, f0, f1);
+#ifdef HX_STAMPS
+            if (!ovf_pass && dbg_took_pre) {
+                dbg_acc[21] += f1 - f0;
+                dbg_acc[22]++;
+            }
+#endif
             // ---- classify the slots.  A row with an overflow pointer (degree > S0) is rare: c's is
             // finished after the merge, a runner-up with one is not speculated on ----
             const u64 pm = ovf_pass ? 0ull : __ballot((int32_t)nb < -1);  // 0x80000000 | overflow row
@@ -903,7 +940,12 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             const bool want_pre = vt != 4u;
             const uint32_t ct = upper ? 4u : vt;
             bool fresh = false;  // c's lanes that inserted their id
-            float dist = 0.0f;
+            // A kept runner-up: its lanes looked like every lane (the look is the whole wave's one bucket read), but
+            // they request no row and run no chain.  Whatever today's look calls absent, the kept pass's look called
+            // absent too -- a bucket's slots fill left to right and never empty -- so every lane that wants a distance
+            // holds one, and the commit below treats its bucket state as it does any other pass's.
+            const bool keptl = MISS_KEEP && kept && upper;
+            float dist = keptl ? kdist : 0.0f;
             // Request, claims and chain under ONE exec mask -- the lanes whose look said "absent"; the
             // claiming lanes are among them.  (Row registers defined under one mask and consumed under
             // another are live across the join for the allocator: it parked 68 of them in AGPRs, the chain
@@ -918,7 +960,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 const bool pend = (ct != 4u) & !fresh;
                 if (HX_UNLIKELY(__ballot(pend) != 0)) fresh = SPILLV ? vis.finish2(nb, vb, ct, pend, fresh) : vis.finish(nb, vb, ct, pend, fresh);
                 dist = dist_of(nb, upper ? want_pre : fresh);
-            } else if (want_pre) {
+            } else if (want_pre && !keptl) {
                 const uint4 *src = reinterpret_cast<const uint4 *>(a.rows + (size_t)nb * DS);
                 uint4 w[DS / 4];
 #pragma unroll
@@ -968,6 +1010,12 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             if (want && !nan) key = ((u64)__builtin_bit_cast(uint32_t, dist) << 32) | nb;
             STAMP(f2);
             STAMP_ADD(1, f1, f2);
+#ifdef HX_STAMPS
+            if (kept) {  // slot 1 on the passes whose runner-up kept its distances
+                dbg_acc[23] += f2 - f1;
+                dbg_acc[24]++;
+            }
+#endif
             STAMP(f3);
 #ifdef HX_STAMPS
             {
@@ -979,6 +1027,53 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             if (HX_UNLIKELY((nanm & 0xFFFFFFFFull) != 0)) {
                 status = HNSW_ERR_NAN_INPUT;  // Dist::cmp would panic (dist.rs:32)
                 break;
+            }
+            if constexpr (MISS_AHEAD) {
+                // ---- a miss foreseen.  A fresh key of c below p's key enters the list (p's key is at most the list's
+                // last) in front of p, the smallest unexpanded entry left: the next pick is the smallest such key and,
+                // as its runner-up, the second smallest or -- there being one only -- p again, unless this merge pushes
+                // that entry off the end of the list (tests/test_runner_up_miss_host.py holds the rule to a CPU replay).
+                // Their adjacency rows are requested now and land while c is merged; the next pick validates the pair
+                // as it does the commit path's and drops a wrong guess, so no result depends on this.  Not on an
+                // overflow pass (pkey is 0 there), not when either row carries an overflow pointer. ----
+                const u64 bm = __ballot(!upper && key < pkey);  // (LK_INVALID is below nothing)
+                if (HX_UNLIKELY(bm != 0) && spec_ok && pm == 0) {
+                    u64 k1 = rdlane64(key, (uint32_t)__ffsll((long long)bm) - 1), k2 = LK_INVALID;
+                    u64 rest = bm & (bm - 1);
+                    if (rest != 0) {
+                        const u64 t2 = rdlane64(key, (uint32_t)__ffsll((long long)rest) - 1);
+                        rest &= rest - 1;
+                        k2 = max(k1, t2);
+                        k1 = min(k1, t2);
+                        for (int i = 2; i < 32 && rest != 0; i++) {  // three or more: c's 32 lanes bound the loop
+                            const u64 t = rdlane64(key, (uint32_t)__ffsll((long long)rest) - 1);
+                            rest &= rest - 1;
+                            k2 = t < k1 ? k1 : min(k2, t);
+                            k1 = min(k1, t);
+                        }
+                    }
+                    const bool again = k2 == LK_INVALID;  // p is the runner-up again: its lanes hold its row already
+#ifdef HX_STAMPS
+                    {
+                        const uint32_t nbel = (uint32_t)__popcll(bm);
+                        if (nbel == 1) dbg_acc[16]++; else if (nbel == 2) dbg_acc[17]++; else dbg_acc[18]++;
+                        dbg_follow = true;
+                        dbg_pred_c = (uint32_t)k1;
+                        dbg_pred_p = again ? pid : (uint32_t)k2;
+                        dbg_old_p = pid;
+                    }
+#endif
+                    pre_c = (uint32_t)k1;
+                    pre_p = again ? pid : (uint32_t)k2;
+                    // (the load writes pre_nb itself: a select behind it would wait for the row here -- measured, 5 % slower)
+                    const bool held = upper && again;
+                    pre_nb = held ? nb : HX_EMPTY_SLOT;
+                    if (slot < S0 && !held) pre_nb = a.adj0[(size_t)(upper ? pre_p : pre_c) * S0 + slot];
+                    if constexpr (MISS_KEEP) {
+                        carry = again;
+                        kdist = dist;
+                    }
+                }
             }
             lst.merge(upper ? LK_INVALID : key, ef, perm, lane);
             STAMP(f3b);
@@ -1070,7 +1165,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
 #ifdef HX_STAMPS
     if (lane == 0 && a.dbg) {
         dbg_acc[4] = __builtin_readcyclecounter() - t_begin;
-        for (int i = 0; i < 16; i++) a.dbg[(size_t)q * 16 + i] = dbg_acc[i];
+        for (int i = 0; i < HX_LEAN_DBG_SLOTS; i++) a.dbg[(size_t)q * HX_LEAN_DBG_SLOTS + i] = dbg_acc[i];
     }
 #endif
     if (lane == 0) {
@@ -1449,7 +1544,7 @@ __global__ void __launch_bounds__(64) hx_lean_q8_kernel(const LeanArgs a) {
 #ifdef HX_STAMPS
     if (lane == 0 && a.dbg) {
         dbg_acc[4] = __builtin_readcyclecounter() - t_begin;
-        for (int i = 0; i < 16; i++) a.dbg[(size_t)q * 16 + i] = dbg_acc[i];
+        for (int i = 0; i < 16; i++) a.dbg[(size_t)q * HX_LEAN_DBG_SLOTS + i] = dbg_acc[i];
     }
 #endif
     if (lane == 0) {

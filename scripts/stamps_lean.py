@@ -18,7 +18,8 @@ dev = torch.device('cuda:0')
 dQ = torch.from_numpy(qs).to(dev)
 ids = torch.empty((nq, n), dtype=torch.int32, device=dev); dd = torch.empty((nq, n), dtype=torch.float32, device=dev)
 cnt = torch.empty(nq, dtype=torch.int32, device=dev); st = torch.empty((nq, 4), dtype=torch.int32, device=dev)
-dbg = torch.zeros((nq, 16), dtype=torch.int64, device=dev)
+SLOTS = 26  # HX_LEAN_DBG_SLOTS (search_lean.hip)
+dbg = torch.zeros((nq, SLOTS), dtype=torch.int64, device=dev)
 os.environ['HX_DBG_PTR'] = str(dbg.data_ptr())
 names = {0: 'pick c,p + adjacency row round trip', 1: 'visited: insert c, look up p', 2: 'row gather until landed',
          3: 'chain + sqrt + key', 8: 'merge c', 9: 'overflow rows + pick + is-p-next', 5: 'commit p: mark + visited insert',
@@ -35,6 +36,7 @@ for ef in efs:
     tot = D[:, 4]
     passes = D[:, 6]
     print('== ef %d: kernel %.4f ms; n_exp %.1f n_dist %.1f layer-0 passes %.1f' % (ef, ms, S[:, 1].mean(), S[:, 0].mean(), passes.mean()))
+    print('   max / mean of the per-query cycles: %.3f' % (tot.max() / tot.mean()))
     print('   total cycles per query: mean %.0f p50 %.0f p90 %.0f p99 %.0f max %.0f min %.0f ; implied clock if the max wave spans the kernel: %.2f GHz' % (
         tot.mean(), np.percentile(tot, 50), np.percentile(tot, 90), np.percentile(tot, 99), tot.max(), tot.min(), tot.max() / (ms * 1e6)))
     for i in (7, 0, 1, 2, 3, 8, 9, 5, 10, 4):
@@ -43,12 +45,24 @@ for ef in efs:
     print('   unaccounted %.1f%%' % (100 * (tot.mean() - acc) / tot.mean()))
     print('   per query: visited slow-loop rounds %.1f; merges with 0 / 1-2 / >=3 survivors: %.1f / %.1f / %.1f; p commits %.1f' % (
         D[:, 11].mean(), D[:, 12].mean(), D[:, 13].mean(), D[:, 14].mean(), D[:, 15].mean()))
+    # the runner-up's misses: c's merge puts a fresh key below p (slots 16 .. 22)
+    miss = D[:, 16:19].sum(1)
+    took = D[:, 22]
+    print('   per query: misses %.1f, with 1 / 2 / >=3 fresh keys of c below p: %.1f / %.1f / %.1f; follow-up pick is the predicted pair %.2f; follow-up runner-up is the old p %.1f' % (
+        miss.mean(), D[:, 16].mean(), D[:, 17].mean(), D[:, 18].mean(), D[:, 19].mean(), D[:, 20].mean()))
+    print('   pick + adjacency (slot 0) per pass: %.0f cycles on the %.1f passes whose rows were fetched ahead, %.0f on the %.1f others' % (
+        D[:, 21].sum() / max(1, took.sum()), took.mean(), (D[:, 0] - D[:, 21]).sum() / max(1, (passes - took).sum()), (passes - took).mean()))
+    print('   look + request + claims + chain (slot 1) per pass: %.0f cycles on the %.1f passes whose runner-up kept its distances, %.0f on the %.1f others' % (
+        D[:, 23].sum() / max(1, D[:, 24].sum()), D[:, 24].mean(), (D[:, 1] - D[:, 23]).sum() / max(1, (passes - D[:, 24]).sum()), (passes - D[:, 24]).mean()))
     # what do the slowest queries look like?  (the kernel lasts as long as its slowest wave)
     order = np.argsort(-tot)[:8]
     print('   slowest queries: total cycles, n_exp, n_dist, passes, cycles/pass, slow-loop rounds, merges 0/1-2/>=3, p commits')
     for qi in order:
         print('     q%-5d %8.0f  n_exp %4d n_dist %5d passes %4d  %6.0f/pass  slow %3d  merges %3d/%3d/%3d  pcommits %3d' % (
             qi, tot[qi], S[qi, 1], S[qi, 0], passes[qi], tot[qi] / max(1, passes[qi]), D[qi, 11], D[qi, 12], D[qi, 13], D[qi, 14], D[qi, 15]))
+        print('            misses 1/2/>=3 below p %3d/%3d/%3d  predicted %3d  old p again %3d  slot 0 per pass: ahead %5.0f (%3d passes), others %5.0f  slot 1 per pass %5.0f  kept %3d passes at %5.0f' % (
+            D[qi, 16], D[qi, 17], D[qi, 18], D[qi, 19], D[qi, 20], D[qi, 21] / max(1, took[qi]), took[qi],
+            (D[qi, 0] - D[qi, 21]) / max(1, passes[qi] - took[qi]), D[qi, 1] / max(1, passes[qi]), D[qi, 24], D[qi, 23] / max(1, D[qi, 24])))
     cc = np.corrcoef(tot, S[:, 1])[0, 1]
     fit = np.polyfit(S[:, 1].astype(np.float64), tot, 1)
     print('   corr(total cycles, n_exp) = %.3f; fit: cycles = %.0f * n_exp + %.0f; n_exp mean %.1f p99 %.0f max %d' % (
