@@ -180,22 +180,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
         const int32_t bst = (int32_t)uni(box_load(reinterpret_cast<const uint32_t *>(&box->b_status)));
         if (status == HNSW_OK) status = bst;
         const uint32_t count = status == HNSW_OK ? min(a.n, lst.n_cur) : 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t idx = LT::idx_of(r, lane);
-            if (idx < a.n) {
-                const bool have = idx < count;
-                a.out_ids[(size_t)q * a.n + idx] = have ? (uint32_t)lst.L[r] : HX_EMPTY_SLOT;
-                if (a.out_dists)
-                    a.out_dists[(size_t)q * a.n + idx] =
-                        have ? __builtin_bit_cast(float, (uint32_t)((lst.L[r] & LK_MASK) >> 32)) : __builtin_inff();
-            }
-        }
-        for (uint32_t idx = 64u * R + lane; idx < a.n; idx += 64) {
-            a.out_ids[(size_t)q * a.n + idx] = HX_EMPTY_SLOT;
-            if (a.out_dists) a.out_dists[(size_t)q * a.n + idx] = __builtin_inff();
-        }
-        if (lane == 0 && a.out_counts) a.out_counts[q] = count;
+        write_results(a, q, lst, count, lane);
 #ifdef HX_STAMPS
         if (lane == 0 && a.dbg)
             for (int i = 0; i < 3; i++) a.dbg[(size_t)q * 16 + 8 + i] = pp[i];
@@ -214,21 +199,9 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
     const unsigned long long t_begin = __builtin_readcyclecounter();
 #endif
 
-    const float *qp = a.Q + (size_t)q * DS;
     QueryRegs<DS> qreg;
     float(&qv)[DS] = qreg.v;
-#pragma unroll
-    for (int e = 0; e < DS; e++) qv[e] = qp[e];
-    {
-        bool bad = false;
-        for (int e = lane; e < DS; e += 64) {
-            const float x = qp[e];
-            bad |= (x != x);
-        }
-        if (__ballot(bad)) status = HNSW_ERR_NAN_INPUT;  // partial_cmp().unwrap() panics in the reference
-    }
-#pragma unroll
-    for (int e = 0; e < DS; e++) asm volatile("" : "+v"(qv[e]));
+    if (!load_query_f32<DS>(a.Q + (size_t)q * DS, qv, lane)) status = HNSW_ERR_NAN_INPUT;
 
     // ---- entry point (template.rs:316-319) ----
     u64 best = LK_INVALID;
@@ -346,12 +319,8 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
 
     // ---- layer 0 with ef (template.rs:326) ----
     if (status == HNSW_OK) {
-        vis.bshift = 32 - (a.slots_log2 - 2);
-        vis.bmask = (hslots >> 2) - 1;
-        const uint32_t vis_limit = hslots - (hslots >> 2);  // 75 % load at most
-        vis.clear(hslots, lane);
-        vis.insert(cur, lane == 0);
-        n_vis = 1;
+        const uint32_t vis_limit = layer0_table<false>(a, vis, hslots, cur, lane).all;
+        n_vis = 1;  // the entry point: what layer0_table put into the emptied table
         box->keys[lane] = best;
         asm volatile("" ::: "memory");
         box_store(&box->k_seq, 1u);
@@ -563,15 +532,8 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
         a.dbg[(size_t)q * 16 + 11] = pp[7];
     }
 #endif
-    if (lane == 0) {
-        box->b_status = status;
-        hnsw_query_stats st;
-        st.n_dist = n_dist;
-        st.n_exp = n_exp;
-        st.sum_deg = sum_deg;
-        st.status = status;
-        a.out_stats[q] = st;
-    }
+    if (lane == 0) box->b_status = status;
+    write_stats(a, q, n_dist, n_exp, sum_deg, status, lane);
     asm volatile("" ::: "memory");
     box_store(&box->b_done, 1u);
 }

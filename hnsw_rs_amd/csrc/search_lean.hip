@@ -626,6 +626,89 @@ __device__ __forceinline__ float row_dist(const float *rows, uint32_t id, bool w
     return __builtin_sqrtf(s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// What the three kernels of this file (hx_pair_f32_kernel, pair_kernel.inc, is the third) share around their
+// layer-0 loops: the f32 query load, the layer-0 table set-up and the write-out (the quant8 kernel keeps its own
+// write-out, see its end).  The entry point and the
+// upper-layer walk are NOT shared: one routine for all three (a lane or a lane pair per neighbour) was built,
+// passed every test and cost 0.5 to 0.7 % on five of seven timed shapes (DESIGN.md section 4a,
+// profiles/lean_shared_walk.txt section 3), so each kernel keeps its own copy: a fix to the walk goes into all three.
+// ---------------------------------------------------------------------------------------------
+// The query of a FullVec kernel: every lane holds all DS values (Point::new of a FullVec is the vector itself),
+// pinned to VGPRs for the whole kernel.  false = a NaN among them (partial_cmp().unwrap() panics in the reference).
+template <int DS>
+__device__ __forceinline__ bool load_query_f32(const float *qp, float (&qv)[DS], int lane) {
+#pragma unroll
+    for (int e = 0; e < DS; e++) qv[e] = qp[e];
+    bool bad = false;
+    for (int e = lane; e < DS; e += 64) {
+        const float x = qp[e];
+        bad |= (x != x);
+    }
+    const bool ok = __ballot(bad) == 0;
+#pragma unroll
+    for (int e = 0; e < DS; e++) asm volatile("" : "+v"(qv[e]));
+    return ok;
+}
+
+// ---- the layer-0 table: the whole LDS region at 75 % load at most, the entry point in it.  SPILLV: a second level in
+// HBM takes what the LDS table cannot (Visited, above), the LDS level then closes at lds (tests lower it) ----
+struct TableLimits {
+    uint32_t lds, all;  // ids the LDS level takes; ids both levels take
+};
+template <bool SPILLV>
+__device__ __forceinline__ TableLimits layer0_table(const LeanArgs &a, Visited &vis, uint32_t hslots, uint32_t cur, int lane) {
+    vis.bshift = 32 - (a.slots_log2 - 2);
+    vis.bmask = (hslots >> 2) - 1;
+    TableLimits lim;
+    lim.lds = hslots - (hslots >> 2);
+    lim.all = lim.lds;
+    if constexpr (SPILLV) {
+        if (a.spill_tab != nullptr) {
+            if (a.lds_limit != 0) lim.lds = min(lim.lds, max(128u, a.lds_limit));
+            vis.gtab = a.spill_tab + ((size_t)blockIdx.x << a.spill_log2);
+            vis.gmask = (1u << a.spill_log2) - 1;
+            vis.gshift = 32 - a.spill_log2;
+            lim.all = lim.lds + (1u << a.spill_log2) / 2;  // the HBM level at half load
+        }
+    }
+    vis.clear(hslots, lane);
+    vis.insert(cur, lane == 0);
+    return lim;
+}
+
+// ---- get_top_selected(n) (results.rs:59-61): the first n entries of the ascending list, padding behind them ----
+template <class LT>
+__device__ __forceinline__ void write_results(const LeanArgs &a, uint32_t q, const LT &lst, uint32_t count, int lane) {
+#pragma unroll
+    for (int r = 0; r < LT::NR; r++) {
+        const uint32_t idx = LT::idx_of(r, lane);
+        if (idx < a.n) {
+            const bool have = idx < count;
+            a.out_ids[(size_t)q * a.n + idx] = have ? (uint32_t)lst.L[r] : HX_EMPTY_SLOT;
+            if (a.out_dists)
+                a.out_dists[(size_t)q * a.n + idx] =
+                    have ? __builtin_bit_cast(float, (uint32_t)((lst.L[r] & LK_MASK) >> 32)) : __builtin_inff();
+        }
+    }
+    for (uint32_t idx = 64u * LT::NR + lane; idx < a.n; idx += 64) {  // n beyond the list capacity
+        a.out_ids[(size_t)q * a.n + idx] = HX_EMPTY_SLOT;
+        if (a.out_dists) a.out_dists[(size_t)q * a.n + idx] = __builtin_inff();
+    }
+    if (lane == 0 && a.out_counts) a.out_counts[q] = count;
+}
+__device__ __forceinline__ void write_stats(const LeanArgs &a, uint32_t q, uint32_t n_dist, uint32_t n_exp, uint32_t sum_deg,
+                                            int32_t status, int lane) {
+    if (lane == 0) {
+        hnsw_query_stats st;
+        st.n_dist = n_dist;
+        st.n_exp = n_exp;
+        st.sum_deg = sum_deg;
+        st.status = status;
+        a.out_stats[q] = st;
+    }
+}
+
 // CK: stages of the cooperative gather in flight (d = 128 only).  The query's 128 values, the stage ring and
 // both forms of the gather do not fit 256 registers with four stages: that build parks a few values in AGPRs
 // and runs one wave per SIMD -- right for launches of up to four waves per CU (4M x 128d, efSearch 64, batch
@@ -669,22 +752,9 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     uint32_t dbg_pred_c = HX_EMPTY_SLOT, dbg_pred_p = HX_EMPTY_SLOT, dbg_old_p = HX_EMPTY_SLOT;
 #endif
 
-    // ---- the query: every lane holds all DS values (Point::new of a FullVec is the vector itself) ----
-    const float *qp = a.Q + (size_t)q * DS;
     QueryRegs<DS> qreg;
     float(&qv)[DS] = qreg.v;
-#pragma unroll
-    for (int e = 0; e < DS; e++) qv[e] = qp[e];
-    {
-        bool bad = false;
-        for (int e = lane; e < DS; e += 64) {
-            const float x = qp[e];
-            bad |= (x != x);
-        }
-        if (__ballot(bad)) status = HNSW_ERR_NAN_INPUT;  // partial_cmp().unwrap() panics in the reference
-    }
-#pragma unroll
-    for (int e = 0; e < DS; e++) asm volatile("" : "+v"(qv[e]));  // pinned to VGPRs for the whole kernel
+    if (!load_query_f32<DS>(a.Q + (size_t)q * DS, qv, lane)) status = HNSW_ERR_NAN_INPUT;
 
     // distance of one row per wanting lane (every lane calls it: the cooperative form needs the whole wave)
     auto dist_of = [&](uint32_t id, bool want) __attribute__((always_inline)) -> float {
@@ -822,24 +892,9 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     LT lst;
     lst.init();
     if (status == HNSW_OK) {
-        vis.bshift = 32 - (a.slots_log2 - 2);
-        vis.bmask = (hslots >> 2) - 1;
-        uint32_t lds_limit = hslots - (hslots >> 2);  // 75 % load at most
-        if constexpr (SPILLV) {
-            if (a.spill_tab != nullptr && a.lds_limit != 0) lds_limit = min(lds_limit, max(128u, a.lds_limit));
-        }
-        uint32_t vis_limit = lds_limit;
-        if constexpr (SPILLV) {
-            if (a.spill_tab != nullptr) {  // a second level in HBM takes what the LDS table cannot (Visited, above)
-                vis.gtab = a.spill_tab + ((size_t)blockIdx.x << a.spill_log2);
-                vis.gmask = (1u << a.spill_log2) - 1;
-                vis.gshift = 32 - a.spill_log2;
-                vis_limit = lds_limit + (1u << a.spill_log2) / 2;  // the HBM level at half load
-            }
-        }
-        vis.clear(hslots, lane);
-        vis.insert(cur, lane == 0);
-        n_vis = 1;
+        const TableLimits lim = layer0_table<SPILLV>(a, vis, hslots, cur, lane);
+        const uint32_t lds_limit = lim.lds, vis_limit = lim.all;
+        n_vis = 1;  // the entry point: what layer0_table put into the emptied table
         lst.set_first(best, lane);
         lst.refresh_last(ef);
         const uint32_t S0 = a.S0;
@@ -1145,38 +1200,15 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
         }
     }
 
-    // ---- get_top_selected(n) (results.rs:59-61): the first n entries of the ascending list ----
     const uint32_t count = status == HNSW_OK ? min(a.n, lst.n_cur) : 0;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const uint32_t idx = LT::idx_of(r, lane);
-        if (idx < a.n) {
-            const bool have = idx < count;
-            a.out_ids[(size_t)q * a.n + idx] = have ? (uint32_t)lst.L[r] : HX_EMPTY_SLOT;
-            if (a.out_dists)
-                a.out_dists[(size_t)q * a.n + idx] =
-                    have ? __builtin_bit_cast(float, (uint32_t)((lst.L[r] & LK_MASK) >> 32)) : __builtin_inff();
-        }
-    }
-    for (uint32_t idx = 64u * R + lane; idx < a.n; idx += 64) {  // n beyond the list capacity: padding
-        a.out_ids[(size_t)q * a.n + idx] = HX_EMPTY_SLOT;
-        if (a.out_dists) a.out_dists[(size_t)q * a.n + idx] = __builtin_inff();
-    }
+    write_results(a, q, lst, count, lane);
 #ifdef HX_STAMPS
     if (lane == 0 && a.dbg) {
         dbg_acc[4] = __builtin_readcyclecounter() - t_begin;
         for (int i = 0; i < HX_LEAN_DBG_SLOTS; i++) a.dbg[(size_t)q * HX_LEAN_DBG_SLOTS + i] = dbg_acc[i];
     }
 #endif
-    if (lane == 0) {
-        if (a.out_counts) a.out_counts[q] = count;
-        hnsw_query_stats st;
-        st.n_dist = n_dist;
-        st.n_exp = n_exp;
-        st.sum_deg = sum_deg;
-        st.status = status;
-        a.out_stats[q] = st;
-    }
+    write_stats(a, q, n_dist, n_exp, sum_deg, status, lane);
 }
 
 // =============================================================================================
@@ -1185,7 +1217,8 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
 // distance_unrolled's eight running sums, quant.rs:14-37).  One adjacency row (32 slots) fills the wave,
 // so a pass expands one candidate; the adjacency row of the runner-up is requested at the pick and is
 // there when the runner-up is next (three times out of four).  Same list, visited set and upper-layer
-// walk as the f32 kernel above.  Against the inline-rows layout of hx_search_kernel this reads 128 B per
+// walk (a lane pair per neighbour, its own copy) as the f32 kernel above; the layer-0 table set-up is the routine
+// all three kernels share, the write-out this kernel's own copy.  Against the inline-rows layout of hx_search_kernel this reads 128 B per
 // evaluated neighbour instead of a whole 4-KiB block per expansion (measured traffic / algorithmic bytes
 // 2.1 there) and needs no 4-GB copy of the rows.
 // =============================================================================================
@@ -1383,24 +1416,9 @@ __global__ void __launch_bounds__(64) hx_lean_q8_kernel(const LeanArgs a) {
     LT lst;
     lst.init();
     if (status == HNSW_OK) {
-        vis.bshift = 32 - (a.slots_log2 - 2);
-        vis.bmask = (hslots >> 2) - 1;
-        uint32_t lds_limit = hslots - (hslots >> 2);  // 75 % load at most
-        if constexpr (SPILLV) {
-            if (a.spill_tab != nullptr && a.lds_limit != 0) lds_limit = min(lds_limit, max(128u, a.lds_limit));
-        }
-        uint32_t vis_limit = lds_limit;
-        if constexpr (SPILLV) {
-            if (a.spill_tab != nullptr) {  // a second level in HBM takes what the LDS table cannot (Visited)
-                vis.gtab = a.spill_tab + ((size_t)blockIdx.x << a.spill_log2);
-                vis.gmask = (1u << a.spill_log2) - 1;
-                vis.gshift = 32 - a.spill_log2;
-                vis_limit = lds_limit + (1u << a.spill_log2) / 2;
-            }
-        }
-        vis.clear(hslots, lane);
-        vis.insert(cur, lane == 0);
-        n_vis = 1;
+        const TableLimits lim = layer0_table<SPILLV>(a, vis, hslots, cur, lane);
+        const uint32_t lds_limit = lim.lds, vis_limit = lim.all;
+        n_vis = 1;  // the entry point: what layer0_table put into the emptied table
         lst.set_first(best, lane);
         lst.refresh_last(ef);
         const uint32_t S0 = a.S0;
@@ -1524,8 +1542,10 @@ __global__ void __launch_bounds__(64) hx_lean_q8_kernel(const LeanArgs a) {
         }
     }
 
-    // ---- get_top_selected(n) (results.rs:59-61): the first n entries of the ascending list ----
     const uint32_t count = status == HNSW_OK ? min(a.n, lst.n_cur) : 0;
+    // This kernel's OWN copy of write_results / write_stats, kept in step by hand: with the shared routines 729 of
+    // hx_lean_q8_kernel<LstHT>'s 2 996 opcode lines came out differently (49 with this copy) and efSearch 68 was
+    // 0.2 to 0.6 % slower in three sessions out of three (profiles/lean_shared_walk.txt).
 #pragma unroll
     for (int r = 0; r < R; r++) {
         const uint32_t idx = LT::idx_of(r, lane);
@@ -1559,6 +1579,28 @@ __global__ void __launch_bounds__(64) hx_lean_q8_kernel(const LeanArgs a) {
 }
 
 #include "pair_kernel.inc"
+
+// The list an ef takes: one register (ef <= 64), head + tail (<= 128), then as many interleaved registers as it needs
+// (every register costs each pick, mark and merge: 2.1 us per expansion with four, 2.9 with eight at the same ef).
+// FINE: every width from four to eight (quant8, f32 at d = 100); otherwise four, six, eight (f32 at d = 128).
+template <class T>
+struct ListTag {
+    using type = T;
+};
+template <bool FINE, class F>
+int with_list_type(uint32_t ef, F launch) {
+    if (ef <= 64) return launch(ListTag<Lst<1>>{});
+    if (ef <= 128) return launch(ListTag<LstHT>{});
+    if (ef <= 256) return launch(ListTag<Lst<4>>{});
+    if constexpr (FINE) {
+        if (ef <= 320) return launch(ListTag<Lst<5>>{});
+    }
+    if (ef <= 384) return launch(ListTag<Lst<6>>{});
+    if constexpr (FINE) {
+        if (ef <= 448) return launch(ListTag<Lst<7>>{});
+    }
+    return launch(ListTag<Lst<8>>{});
+}
 
 template <class LT>
 int launch_lean_q8(const LeanArgs &a_in, uint32_t nblocks, hipStream_t stream) {
@@ -1630,39 +1672,32 @@ int launch_lean(const DevView &v, const SearchArgs &s, uint32_t nblocks, uint32_
     a.n = s.n;
     a.slots_log2 = slots_log2;
     a.dbg = s.dbg;
-    // 64 < ef <= 128: head + tail list; 128 < ef <= 256: four interleaved registers
     if (v.kind == HNSW_VEC_QUANT8) {
-        if (a.ef <= 64) return launch_lean_q8<Lst<1>>(a, nblocks, stream);
-        if (a.ef > 448) return launch_lean_q8<Lst<8>>(a, nblocks, stream);  // (round 4: 256 < ef <= 512 with the two-level visited set)
-        if (a.ef > 384) return launch_lean_q8<Lst<7>>(a, nblocks, stream);
-        if (a.ef > 320) return launch_lean_q8<Lst<6>>(a, nblocks, stream);
-        if (a.ef > 256) return launch_lean_q8<Lst<5>>(a, nblocks, stream);
-        if (a.ef > 128) return launch_lean_q8<Lst<4>>(a, nblocks, stream);
-        return launch_lean_q8<LstHT>(a, nblocks, stream);
+        return with_list_type<true>(a.ef, [&](auto lt) {
+            using LT = typename decltype(lt)::type;
+            return launch_lean_q8<LT>(a, nblocks, stream);
+        });
     }
     if (v.dim == 128) {  // whole-line rows: the cooperative gather (HNSW_MI355X_LEAN_128=0: the generic kernel, for A/B runs)
         const bool few = nblocks <= 4 * cu_count();  // at most one wave per SIMD: the four-stage build (see the kernel)
-        if (a.ef <= 64) return few ? launch_lean_one<128, Lst<1>, 4>(a, nblocks, stream) : launch_lean_one<128, Lst<1>, 2>(a, nblocks, stream);
-        if (a.ef > 384) return launch_lean_one<128, Lst<8>, 2>(a, nblocks, stream);  // (round 4: 256 < ef <= 512, two-level visited set)
-        if (a.ef > 256) return launch_lean_one<128, Lst<6>, 2>(a, nblocks, stream);
-        if (a.ef > 128) return launch_lean_one<128, Lst<4>, 2>(a, nblocks, stream);
-        return few ? launch_lean_one<128, LstHT, 4>(a, nblocks, stream) : launch_lean_one<128, LstHT, 2>(a, nblocks, stream);
+        return with_list_type<false>(a.ef, [&](auto lt) {
+            using LT = typename decltype(lt)::type;
+            if constexpr (LT::NR <= 2) {
+                if (few) return launch_lean_one<128, LT, 4>(a, nblocks, stream);
+            }
+            return launch_lean_one<128, LT, 2>(a, nblocks, stream);
+        });
     }
     // two waves per query (pair_kernel.inc): launches that leave the SIMDs a wave or two each
     // (a.qsel: a re-run of the queries a first launch gave up -- those take the one-wave kernel)
-    if (sw::pair_mode() != 0 && a.ef <= 128 && a.qsel == nullptr) {
-        if (a.ef <= 64) return launch_pair<100, Lst<1>>(a, nblocks, stream);
-        return launch_pair<100, LstHT>(a, nblocks, stream);
-    }
-    if (a.ef <= 64) return launch_lean_one<100, Lst<1>>(a, nblocks, stream);
-    // 256 < ef <= 512: as many interleaved registers as the list needs (round 4: five to eight; every register costs
-    // each pick, mark and merge -- 2.1 us per expansion with four, 2.9 with eight at the same ef)
-    if (a.ef > 448) return launch_lean_one<100, Lst<8>>(a, nblocks, stream);
-    if (a.ef > 384) return launch_lean_one<100, Lst<7>>(a, nblocks, stream);
-    if (a.ef > 320) return launch_lean_one<100, Lst<6>>(a, nblocks, stream);
-    if (a.ef > 256) return launch_lean_one<100, Lst<5>>(a, nblocks, stream);
-    if (a.ef > 128) return launch_lean_one<100, Lst<4>>(a, nblocks, stream);
-    return launch_lean_one<100, LstHT>(a, nblocks, stream);
+    const bool pair = sw::pair_mode() != 0 && a.ef <= 128 && a.qsel == nullptr;
+    return with_list_type<true>(a.ef, [&](auto lt) {
+        using LT = typename decltype(lt)::type;
+        if constexpr (LT::NR <= 2) {
+            if (pair) return launch_pair<100, LT>(a, nblocks, stream);
+        }
+        return launch_lean_one<100, LT>(a, nblocks, stream);
+    });
 }
 
 }  // namespace hx

@@ -41,6 +41,14 @@ def test_lean_kernels_fit_two_waves_per_simd_without_agprs_or_scratch(tmp_path):
     for name, r in pair.items():
         assert r.get("ScratchSize", 0) == 0 and r.get("VGPRs Spill", 0) == 0 and r.get("AGPRs", 0) == 0, (name, r)
         assert r.get("VGPRs", 999) <= 256, (name, r)
+    # the two-stage d = 128 kernels with lists of at most two registers are the ones launches of more than one wave per
+    # SIMD take (launch_lean: `few` == false): they exist to run at two waves per SIMD, and sit at 252 / 256 VGPRs with
+    # nothing in AGPRs -- one parked value puts them over the line.  (Lst<1>, then LstHT, each with CK = 2.)
+    two_wave_128 = [k for k in timed if re.search(r"ILi128ENS0_(3LstILi1EEE|5LstHTE)Li2E", k)]
+    assert len(two_wave_128) == 2, sorted(timed)
+    for name in two_wave_128:
+        r = timed[name]
+        assert r.get("Occupancy", 0) >= 2 and r.get("AGPRs", 0) == 0 and r.get("ScratchSize", 0) == 0, (name, r)
     for name, r in timed.items():
         assert r.get("ScratchSize", 0) == 0 and r.get("VGPRs Spill", 0) == 0, (name, r)
         if "ILi128E" in name or ("hx_lean_f32_kernel" in name and re.search(r"LstILi[5678]E", name)):
