@@ -1,22 +1,18 @@
 // capi.cpp -- the extern "C" surface of libhnsw_mi355x.so (include/hnsw_mi355x.h): argument checks, dispatch,
-// accessors, options and statistics, persistence, snapshots, the ground-truth scans.  Host logic only; the search
-// entry points upload the index snapshot to HBM on demand and hand over to search_host.cpp (batches) or coalesce.cpp
-// (hnsw_search), which launch the HIP kernels.  There is no CPU search path.  (The two entry points of partitioned
-// search are partition.cpp's.)
+// accessors and persistence.  Host logic only; the search entry points upload the index snapshot to HBM on demand and
+// hand over to search_host.cpp (batches) or coalesce.cpp (hnsw_search), which launch the HIP kernels.  There is no CPU
+// search path.  Options and statistics are options.cpp's tables, the ground-truth scans ground_truth.cpp's, snapshot
+// replication snapshot.cpp's.  (The two entry points of partitioned search are partition.cpp's.)
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
-#include <climits>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
 #include <new>
-#include <string>
 #include <thread>
 #include <vector>
 
@@ -187,18 +183,9 @@ int hnsw_clone(const hnsw_index *h, hnsw_index **out) {
     if (!c) return HNSW_ERR_OOM;
     c->host.reset(new hx::HostIndex(*h->host));
     c->device = h->device;
-    // the handle's options travel with the clone (a cosine index that forgot its metric would stop normalising
-    // its queries)
-    c->cosine = h->cosine;
-    c->gpu_build = h->gpu_build;
-    c->build_batch_max = h->build_batch_max;
-    c->build_batch_div = h->build_batch_div;
-    c->dev.inline_rows = h->dev.inline_rows;
-    c->dev.fat_budget_bytes = h->dev.fat_budget_bytes;
-    c->co.window_us.store(h->co.window_us.load());
-    c->co.depth = h->co.depth;
-    c->co.cap = h->co.cap;
-    c->filter_exact_max = h->filter_exact_max;
+    // the handle's options travel with the clone, every one of them (a cosine index that forgot its metric would
+    // stop normalising its queries)
+    hx::copy_options(c, h);
     c->del.assign_host(h->del.words);
     c->lab.assign_host(h->lab.labels);
     *out = c;
@@ -694,8 +681,8 @@ int hnsw_search_layer(hnsw_index *h, uint32_t layer, const float *q, const uint3
     return HNSW_OK;
 }
 
-int hnsw_brute_force(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids,
-                     float *dists) {
+// ---- ground truth (ground_truth.cpp) ----------------------------------------------------------------------------
+int hnsw_brute_force(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids, float *dists) {
     int rc = check_search_args(h, 1);
     if (rc != HNSW_OK) return rc;
     if (nq == 0) return HNSW_OK;
@@ -703,70 +690,9 @@ int hnsw_brute_force(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uin
         set_error("brute force supports 1 <= k <= 64");
         return HNSW_ERR_ARG;
     }
-    if (h->del.count) {
-        // the top k of the undeleted ids: the filtered search's exact path, in the same arithmetic and (dist, id) order
-        std::vector<hnsw_query_stats> st(nq);
-        hx::Filter scan;
-        scan.family = hx::Filter::SCAN;
-        rc = hx::search_filtered(h, Q, nq, k, k, scan, true, ids, dists, nullptr, st.data(), nullptr);
-        if (rc != HNSW_OK) return rc;
-        for (uint64_t i = 0; i < nq; i++)
-            if (st[i].status != HNSW_OK) {
-                set_error("NaN in a query or a distance");
-                return st[i].status;
-            }
-        return HNSW_OK;
-    }
-    rc = ensure_uploaded(h);
-    if (rc != HNSW_OK) return rc;
-    const hx::DevView &v = h->dev.view;
-    const uint32_t nseg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(512, (v.n_points + 2047) / 2048));
-    const uint64_t batch = 2048;
-    DevBuf dQ, dIds, dDists, dSt;
-    if ((rc = dQ.alloc(batch * v.dim * 4)) || (rc = dIds.alloc(batch * nseg * k * 4)) ||
-        (rc = dDists.alloc(batch * nseg * k * 4)) || (rc = dSt.alloc(4)))
-        return rc;
-    std::vector<uint32_t> pid(batch * nseg * k);
-    std::vector<float> pd(batch * nseg * k);
-    std::vector<std::pair<float, uint32_t>> cand;
-    for (uint64_t q0 = 0; q0 < nq; q0 += batch) {
-        const uint64_t nb = std::min(batch, nq - q0);
-        HIP_TRY(hipMemcpy(dQ.p, Q + q0 * v.dim, nb * v.dim * 4, hipMemcpyHostToDevice));
-        if ((rc = cosine_queries(h, dQ.p, nb, nullptr))) return rc;
-        HIP_TRY(hipMemset(dSt.p, 0, 4));
-        rc = hx::launch_brute_force(v, dQ.as<float>(), nb, k, nseg, dIds.as<uint32_t>(),
-                                    dDists.as<float>(), dSt.as<int32_t>(), nullptr);
-        if (rc != HNSW_OK) return rc;
-        HIP_TRY(hipDeviceSynchronize());
-        int32_t st = 0;
-        HIP_TRY(hipMemcpy(&st, dSt.p, 4, hipMemcpyDeviceToHost));
-        if (st != HNSW_OK) {
-            set_error("NaN in a query or a distance");
-            return st;
-        }
-        HIP_TRY(hipMemcpy(pid.data(), dIds.p, nb * nseg * k * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(pd.data(), dDists.p, nb * nseg * k * 4, hipMemcpyDeviceToHost));
-        for (uint64_t qi = 0; qi < nb; qi++) {
-            cand.clear();
-            for (uint64_t j = 0; j < (uint64_t)nseg * k; j++) {
-                const uint32_t id = pid[qi * nseg * k + j];
-                if (id != UINT32_MAX) cand.emplace_back(pd[qi * nseg * k + j], id);
-            }
-            std::sort(cand.begin(), cand.end());  // (dist, id): Dist::cmp for non-NaN distances
-            for (uint32_t j = 0; j < k; j++) {
-                const bool have = j < cand.size();
-                ids[(q0 + qi) * k + j] = have ? cand[j].second : UINT32_MAX;
-                if (dists) dists[(q0 + qi) * k + j] = have ? cand[j].first : INFINITY;
-            }
-        }
-    }
-    return HNSW_OK;
+    return hx::exact_scan(h, Q, nq, k, ids, dists);
 }
 
-// Ground truth on the matrix cores (brute_mfma.hip): MFMA scores screen every point, the k + 8 best per
-// query are re-evaluated in the reference's exact arithmetic and sorted by (dist, id).  Not bit-exact by
-// construction (the screen could in principle lose a true neighbour to rounding): hnsw_brute_force is the
-// exact scan; this one is for ground truth at sizes where the exact scan takes minutes.
 int hnsw_brute_force_fast(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids, float *dists) {
     int rc = check_search_args(h, 1);
     if (rc != HNSW_OK) return rc;
@@ -776,126 +702,7 @@ int hnsw_brute_force_fast(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k
         set_error("the MFMA scan supports 1 <= k <= %u", K2 - 8);
         return HNSW_ERR_ARG;
     }
-    if (h->del.count) {  // the k + 8 re-rank cannot promise k undeleted ids: no ground truth rather than a wrong one
-        set_error("hnsw_brute_force_fast refuses while ids are deleted (%llu); hnsw_brute_force excludes them",
-                  (unsigned long long)h->del.count);
-        return HNSW_ERR_ARG;
-    }
-    rc = ensure_uploaded(h);
-    if (rc != HNSW_OK) return rc;
-    const hx::DevView &v = h->dev.view;
-    if (v.kind != HNSW_VEC_F32 || (v.dim & 3u)) {
-        set_error("the MFMA scan serves f32 rows whose dimension is a multiple of 4");
-        return HNSW_ERR_ARG;
-    }
-    // A NaN in a query makes every screen score NaN, and `score < threshold` is false for NaN: the screen would
-    // keep nothing and the call would return padding ids with status OK where the exact scan reports
-    // HNSW_ERR_NAN_INPUT (stored rows cannot hold one: insert rejects them)
-    for (uint64_t i = 0; i < nq * (uint64_t)v.dim; i++)
-        if (Q[i] != Q[i]) {
-            set_error("query %llu: NaN in the query", (unsigned long long)(i / v.dim));
-            return HNSW_ERR_NAN_INPUT;
-        }
-    const uint64_t batch = 2048;  // queries per launch: 64 tiles of 32
-    // (buffers sized for the tiles a launch really has: a 32-query call on a multi-million-point index has one
-    // tile and up to 768 segments, not 64 tiles of them)
-    const uint32_t ntile_max = (uint32_t)((std::min(batch, nq) + 31) / 32);
-    // enough workgroups for the chip (256 CUs, one 98-KB query tile each at d = 768) without cutting the
-    // points into segments shorter than a few tiles per wave
-    // about 768 workgroups per launch (256 CUs, up to three 32-query tiles of a small dimension each), but
-    // no segment shorter than a few point tiles per wave; fewer segments = fewer partial lists to merge
-    const uint32_t ntile_first = (uint32_t)((std::min(batch, nq) + 31) / 32);
-    const uint32_t nseg = (uint32_t)std::max<uint64_t>(
-        1, std::min<uint64_t>(std::max<uint32_t>(1, 768 / ntile_first), (uint64_t)v.n_points / 4096));
-    const uint32_t M = k + 8;
-    const size_t per_tile = (size_t)nseg * 4 * 64 * K2;
-    DevBuf dQ, dXn, dS, dI, dQi, dPi, dOut;
-    if ((rc = dQ.alloc(batch * v.dim * 4)) || (rc = dXn.alloc((size_t)v.n_points * 4)) ||
-        (rc = dS.alloc(ntile_max * per_tile * 4)) || (rc = dI.alloc(ntile_max * per_tile * 4)) ||
-        (rc = dQi.alloc(batch * M * 4)) || (rc = dPi.alloc(batch * M * 4)) || (rc = dOut.alloc(batch * M * 4)))
-        return rc;
-    DevBuf dXa;
-    if ((rc = dXa.alloc((size_t)v.n_points * 4))) return rc;
-    rc = hx::launch_row_norms(v, dXn.as<float>(), dXa.as<uint32_t>(), nullptr);
-    if (rc != HNSW_OK) return rc;
-    // The screen's guarantee models relative rounding and holds only inside f32's normal range (brute_mfma.hip): a
-    // call with a stored row or a query whose largest |component| is not zero and outside [2^-48, 2^40] is the exact
-    // scan's.  (Under the cosine option a query is a unit vector by the time the screen reads it.)
-    {
-        const uint32_t lo = 0x27800000u, hi = 0x53800000u;  // the bit patterns of 2^-48 and 2^40
-        auto outside = [&](uint32_t bits) { return bits != 0 && (bits < lo || bits > hi); };
-        std::vector<uint32_t> xa((size_t)v.n_points);
-        HIP_TRY(hipMemcpy(xa.data(), dXa.p, xa.size() * 4, hipMemcpyDeviceToHost));
-        bool exact = false;
-        for (size_t i = 0; i < xa.size() && !exact; i++) exact = outside(xa[i]);
-        for (uint64_t i = 0; i < nq && !exact && !h->cosine; i++) {
-            uint32_t m = 0, w;
-            for (uint32_t e = 0; e < v.dim; e++) {
-                memcpy(&w, &Q[i * v.dim + e], 4);
-                m = std::max(m, w & 0x7FFFFFFFu);
-            }
-            exact = outside(m);
-        }
-        if (exact) return hnsw_brute_force(h, Q, nq, k, ids, dists);
-    }
-    std::vector<float> hs(ntile_max * per_tile), hd(batch * M);
-    std::vector<uint32_t> hi(ntile_max * per_tile), qidx(batch * M), pidx(batch * M);
-    std::vector<std::pair<float, uint32_t>> cand;
-    for (uint64_t q0 = 0; q0 < nq; q0 += batch) {
-        const uint64_t nb = std::min(batch, nq - q0);
-        const uint32_t ntile = (uint32_t)((nb + 31) / 32);
-        HIP_TRY(hipMemcpy(dQ.p, Q + q0 * v.dim, nb * v.dim * 4, hipMemcpyHostToDevice));
-        if ((rc = cosine_queries(h, dQ.p, nb, nullptr))) return rc;
-        rc = hx::launch_brute_mfma(v, dXn.as<float>(), dQ.as<float>(), (uint32_t)nb, nseg, dS.as<float>(),
-                                   dI.as<uint32_t>(), nullptr);
-        if (rc != HNSW_OK) return rc;
-        HIP_TRY(hipMemcpy(hs.data(), dS.p, ntile * per_tile * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hi.data(), dI.p, ntile * per_tile * 4, hipMemcpyDeviceToHost));
-        // per query: the lists of lanes j and j + 32 of every (segment, wave); keep the M best scores
-        for (uint64_t qi = 0; qi < nb; qi++) {
-            const uint32_t tile = (uint32_t)(qi / 32), j = (uint32_t)(qi % 32);
-            cand.clear();
-            for (uint32_t sw = 0; sw < nseg * 4; sw++)
-                for (uint32_t half = 0; half < 2; half++) {
-                    const size_t o = (((size_t)tile * nseg * 4 + sw) * 64 + j + 32 * half) * K2;
-                    for (uint32_t t = 0; t < K2; t++)
-                        if (hi[o + t] != UINT32_MAX) cand.emplace_back(hs[o + t], hi[o + t]);
-                }
-            const size_t keep = std::min<size_t>(M, cand.size());
-            std::partial_sort(cand.begin(), cand.begin() + keep, cand.end());
-            for (uint32_t t = 0; t < M; t++) {
-                qidx[qi * M + t] = (uint32_t)qi;
-                pidx[qi * M + t] = t < keep ? cand[t].second : UINT32_MAX;
-            }
-        }
-        // exact distances of the survivors, in the reference's arithmetic
-        HIP_TRY(hipMemcpy(dQi.p, qidx.data(), nb * M * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dPi.p, pidx.data(), nb * M * 4, hipMemcpyHostToDevice));
-        rc = hx::launch_pair_distance(v, dQ.as<float>(), dQi.as<uint32_t>(), dPi.as<uint32_t>(), nb * M,
-                                      dOut.as<float>(), nullptr);
-        if (rc != HNSW_OK) return rc;
-        HIP_TRY(hipMemcpy(hd.data(), dOut.p, nb * M * 4, hipMemcpyDeviceToHost));
-        for (uint64_t qi = 0; qi < nb; qi++) {
-            cand.clear();
-            for (uint32_t t = 0; t < M; t++) {
-                const uint32_t id = pidx[qi * M + t];
-                if (id == UINT32_MAX) continue;
-                const float dd = hd[qi * M + t];
-                if (dd != dd) {
-                    set_error("NaN in a query or a distance");
-                    return HNSW_ERR_NAN_INPUT;
-                }
-                cand.emplace_back(dd, id);
-            }
-            std::sort(cand.begin(), cand.end());  // (dist, id): Dist::cmp for non-NaN distances
-            for (uint32_t t = 0; t < k; t++) {
-                const bool have = t < cand.size();
-                ids[(q0 + qi) * k + t] = have ? cand[t].second : UINT32_MAX;
-                if (dists) dists[(q0 + qi) * k + t] = have ? cand[t].first : INFINITY;
-            }
-        }
-    }
-    return HNSW_OK;
+    return hx::mfma_scan(h, Q, nq, k, ids, dists);
 }
 
 // ---- accessors -----------------------------------------------------------------------------------
@@ -1130,317 +937,22 @@ int hnsw_upload(hnsw_index *h) {
     if (!h) return HNSW_ERR_ARG;
     return ensure_uploaded(h);
 }
-int hnsw_set_option(hnsw_index *h, const char *key, int64_t value) {
-    if (!h || !key) return HNSW_ERR_ARG;
-    std::lock_guard<std::mutex> g(h->mu);
-    if (!strcmp(key, "inline_rows")) {
-        h->dev.inline_rows = (int)value;
-    } else if (!strcmp(key, "inline_budget_mb")) {
-        h->dev.fat_budget_bytes = (uint64_t)value << 20;
-    } else if (!strcmp(key, "gpu_build")) {
-        h->gpu_build = (int)value;
-        return HNSW_OK;
-    } else if (!strcmp(key, "metric_cosine")) {
-        // points already stored stay as they are: set it before the first insert (or on a loaded index whose
-        // rows were stored under it -- the reference's file format has no field for a metric)
-        h->cosine = value != 0;
-        return HNSW_OK;
-    } else if (!strcmp(key, "filter_exact_max")) {
-        h->filter_exact_max = value;
-        return HNSW_OK;
-    } else if (!strcmp(key, "filter_exact_grouped")) {
-        if (value != 0 && value != 1) {
-            set_error("filter_exact_grouped must be 0 or 1");
-            return HNSW_ERR_ARG;
-        }
-        h->filter_exact_grouped = (int)value;
-        return HNSW_OK;
-    } else if (!strcmp(key, "mask_set_cache_mb")) {
-        if (value < 0) {
-            set_error("mask_set_cache_mb must not be negative");
-            return HNSW_ERR_ARG;
-        }
-        h->mask_set_cache_mb = std::min<int64_t>(value, 1 << 20);
-        return HNSW_OK;
-    } else if (!strcmp(key, "gpu_build_batch_max")) {
-        if (value < 1) {
-            set_error("gpu_build_batch_max must be positive");
-            return HNSW_ERR_ARG;
-        }
-        h->build_batch_max = (uint32_t)std::min<int64_t>(value, 1 << 20);
-        return HNSW_OK;
-    } else if (!strcmp(key, "gpu_build_batch_div")) {
-        if (value < 1) {
-            set_error("gpu_build_batch_div must be positive");
-            return HNSW_ERR_ARG;
-        }
-        h->build_batch_div = (uint32_t)std::min<int64_t>(value, 1 << 20);
-        return HNSW_OK;
-    } else if (!strcmp(key, "coalesce_us") || !strcmp(key, "coalesce_depth") || !strcmp(key, "coalesce_max")) {
-        std::lock_guard<hx::SpinLock> cg(h->co.mu);
-        if (!strcmp(key, "coalesce_us")) {
-            h->co.window_us.store(std::min<int64_t>(value, 100000));
-        } else if (value < 1) {
-            set_error("%s must be positive", key);
-            return HNSW_ERR_ARG;
-        } else if (!strcmp(key, "coalesce_depth")) {
-            h->co.depth = (uint32_t)std::min<int64_t>(value, 64);
-        } else {
-            h->co.cap = (uint32_t)std::min<int64_t>(value, hx::CoBatch::COUNT);  // (what a batch's word can count)
-        }
-        return HNSW_OK;
-    } else {
-        set_error("unknown option %s", key);
-        return HNSW_ERR_ARG;
-    }
-    if (!is_replica(h)) h->dev.release();  // rebuilt by the next upload
-    return HNSW_OK;
-}
+int hnsw_set_option(hnsw_index *h, const char *key, int64_t value) { return h && key ? hx::set_option(h, key, value) : HNSW_ERR_ARG; }
 int hnsw_device_bytes(const hnsw_index *h, uint64_t *bytes) {
     if (!h || !bytes) return HNSW_ERR_ARG;
     *bytes = h->dev.valid ? h->dev.bytes : 0;
     return HNSW_OK;
 }
-int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) {
-    if (!h || !key || !out) return HNSW_ERR_ARG;
-    if (!strcmp(key, "uploads")) {
-        *out = h->n_uploads.load();
-    } else if (!strcmp(key, "point_patches")) {
-        *out = h->n_point_patches.load();
-    } else if (!strcmp(key, "patch_fallbacks")) {
-        *out = h->n_patch_fallbacks.load();
-    } else if (!strncmp(key, "build_", 6)) {
-        const hx::BuildStats &bs = h->build;
-        const char *k = key + 6;
-        if (!strcmp(k, "points")) *out = bs.points;
-        else if (!strcmp(k, "batches")) *out = bs.batches;
-        else if (!strcmp(k, "rows_read")) *out = bs.rows_read;
-        else if (!strcmp(k, "adj_rows")) *out = bs.adj_rows;
-        else if (!strcmp(k, "adj_ids")) *out = bs.adj_ids;
-        else if (!strcmp(k, "records")) *out = bs.records;
-        else if (!strcmp(k, "removals")) *out = bs.removals;
-        else if (!strcmp(k, "insert_kernel_us")) *out = (uint64_t)(bs.insert_kernel_s * 1e6);
-        else if (!strcmp(k, "insert_phase_us")) *out = (uint64_t)(bs.insert_phase_s * 1e6);
-        else if (!strcmp(k, "connect_us")) *out = (uint64_t)(bs.connect_s * 1e6);
-        else if (!strcmp(k, "connect_kernel_us")) *out = (uint64_t)(bs.connect_kernel_s * 1e6);
-        else if (!strcmp(k, "rows_owned")) *out = bs.rows_owned;
-        else if (!strcmp(k, "rows_received")) *out = bs.rows_received;
-        else if (!strcmp(k, "exchange_bytes")) *out = bs.exchange_bytes;
-        else if (!strcmp(k, "exchange_us")) *out = (uint64_t)(bs.exchange_s * 1e6);
-        else if (!strcmp(k, "cpu_path_points")) *out = bs.cpu_path_points;
-        else if (!strcmp(k, "rerun_points")) *out = bs.rerun_points;
-        else if (!strcmp(k, "kept_last_edges")) *out = bs.kept_last_edges;
-        else {
-            set_error("unknown statistic %s", key);
-            return HNSW_ERR_ARG;
-        }
-    } else if (!strcmp(key, "filtered_queries_graph")) {
-        *out = h->n_filt_graph.load();
-    } else if (!strcmp(key, "filtered_queries_exact")) {
-        *out = h->n_filt_exact.load();
-    } else if (!strcmp(key, "filtered_overflow_exact")) {
-        *out = h->n_filt_overflow.load();
-    } else if (!strcmp(key, "label_words_uploaded")) {
-        *out = h->lab.words_uploaded;
-    } else if (!strcmp(key, "filtered_range_calls")) {
-        *out = h->n_filt_range_calls.load();
-    } else if (!strcmp(key, "filtered_range_ranges")) {
-        *out = h->n_filt_range_ranges.load();
-    } else if (!strcmp(key, "filtered_set_range_calls")) {
-        *out = h->n_filt_set_range_calls.load();
-    } else if (!strcmp(key, "filtered_set_range_groups")) {
-        *out = h->n_filt_set_range_groups.load();
-    } else if (!strcmp(key, "filtered_one_calls")) {
-        *out = h->n_filt_one_calls.load();
-    } else if (!strcmp(key, "filtered_one_batches")) {
-        *out = h->n_filt_one_batches.load();
-    } else if (!strcmp(key, "filtered_ranges_calls")) {
-        *out = h->n_filt_ranges_calls.load();
-    } else if (!strcmp(key, "filtered_ranges_groups")) {
-        *out = h->n_filt_ranges_groups.load();
-    } else if (!strcmp(key, "filtered_multi_calls")) {
-        *out = h->n_filt_multi_calls.load();
-    } else if (!strcmp(key, "filtered_multi_masks")) {
-        *out = h->n_filt_multi_masks.load();
-    } else if (!strcmp(key, "mask_set_words_uploaded")) {
-        *out = h->n_set_words_uploaded.load();
-    } else if (!strcmp(key, "mask_set_recounts")) {
-        *out = h->n_set_recounts.load();
-    } else if (!strcmp(key, "mask_set_compactions")) {
-        *out = h->n_set_compactions.load();
-    } else if (!strcmp(key, "filtered_set_calls")) {
-        *out = h->n_filt_set_calls.load();
-    } else if (!strcmp(key, "shard_calls")) {
-        *out = h->n_shard_calls.load();
-    } else if (!strcmp(key, "shard_merges")) {
-        *out = h->n_shard_merges.load();
-    } else if (!strcmp(key, "grouped_calls")) {
-        *out = h->n_grouped_calls.load();
-    } else if (!strcmp(key, "grouped_launches")) {
-        *out = h->n_grouped_launches.load();
-    } else if (!strcmp(key, "deleted")) {
-        *out = h->del.count;
-    } else if (!strcmp(key, "deleted_mask_words_uploaded")) {
-        *out = h->del.words_uploaded;
-    } else if (!strcmp(key, "deleted_queries_graph")) {
-        *out = h->n_del_graph.load();
-    } else if (!strcmp(key, "deleted_queries_exact")) {
-        *out = h->n_del_exact.load();
-    } else if (!strcmp(key, "deleted_overflow_exact")) {
-        *out = h->n_del_overflow.load();
-    } else if (!strcmp(key, "coalesced_batches")) {
-        *out = h->co.n_batches.load();
-    } else if (!strcmp(key, "coalesced_queries")) {
-        *out = h->co.n_queries.load();
-    } else if (!strcmp(key, "coalesced_max_batch")) {
-        *out = h->co.max_batch.load();
-    } else if (!strcmp(key, "coalesce_ns_window")) {
-        *out = h->co.ns_window.load();
-    } else if (!strcmp(key, "coalesce_ns_turn")) {
-        *out = h->co.ns_turn.load();
-    } else if (!strcmp(key, "coalesce_ns_gpu")) {
-        *out = h->co.ns_gpu.load();
-    } else if (!strcmp(key, "coalesce_ns_handout")) {
-        *out = h->co.ns_handout.load();
-    } else {
-        set_error("unknown statistic %s", key);
-        return HNSW_ERR_ARG;
-    }
-    return HNSW_OK;
-}
+int hnsw_get_stat(const hnsw_index *h, const char *key, uint64_t *out) { return h && key && out ? hx::get_stat(h, key, out) : HNSW_ERR_ARG; }
 
 // ---- snapshot replication ------------------------------------------------------------------------------
-namespace {
-struct SnapHeader {  // what travels in hnsw_snapshot_desc.header (32 words)
-    uint32_t magic, version;
-    int32_t kind;
-    uint32_t dim, n_points, nb_layers, ep, S0, S1, row_stride, half_bytes, nch4, rem;
-    uint32_t fat_stride_lo, fat_stride_hi;
-    uint32_t m, ef_cons;
-    uint32_t flags;  // bit 0: the cosine option (queries are normalised on arrival)
-    uint32_t reserved[14];
-};
-static_assert(sizeof(SnapHeader) == 32 * 4, "snapshot header is 32 words");
-constexpr uint32_t SNAP_MAGIC = 0x48584E53u;  // "SNXH"
-}  // namespace
-
 int hnsw_snapshot_describe(hnsw_index *h, hnsw_snapshot_desc *out) {
     if (!h || !out) return HNSW_ERR_ARG;
-    int rc = check_search_args(h, 1);
-    if (rc != HNSW_OK) return rc;
-    if ((rc = ensure_uploaded(h))) return rc;
-    const hx::DevView &v = h->dev.view;
-    memset(out, 0, sizeof(*out));
-    uint64_t nb[7];
-    void *pp[7];
-    h->dev.describe(nb, pp);
-    for (int i = 0; i < HNSW_SNAPSHOT_ARRAYS; i++) {
-        out->bytes[i] = nb[i];
-        out->ptr[i] = pp[i];
-    }
-    SnapHeader hd{};
-    hd.magic = SNAP_MAGIC;
-    hd.version = 1;
-    hd.kind = v.kind;
-    hd.dim = v.dim;
-    hd.n_points = v.n_points;
-    hd.nb_layers = v.nb_layers;
-    hd.ep = v.ep;
-    hd.S0 = v.S0;
-    hd.S1 = v.S1;
-    hd.row_stride = v.row_stride;
-    hd.half_bytes = v.half_bytes;
-    hd.nch4 = v.nch4;
-    hd.rem = v.rem;
-    hd.fat_stride_lo = (uint32_t)v.fat_stride;
-    hd.fat_stride_hi = (uint32_t)(v.fat_stride >> 32);
-    hd.m = (uint32_t)h->host->params.m;
-    hd.ef_cons = (uint32_t)h->host->params.ef_cons;
-    hd.flags = h->cosine ? 1u : 0u;
-    memcpy(out->header, &hd, sizeof(hd));
-    return HNSW_OK;
+    const int rc = check_search_args(h, 1);
+    return rc != HNSW_OK ? rc : hx::snapshot_describe(h, out);
 }
-
-int hnsw_snapshot_adopt(hnsw_index *h, hnsw_snapshot_desc *d) {
-    if (!h || !d) return HNSW_ERR_ARG;
-    SnapHeader hd;
-    memcpy(&hd, d->header, sizeof(hd));
-    if (hd.magic != SNAP_MAGIC || hd.version != 1) {
-        set_error("hnsw_snapshot_adopt: not a snapshot header");
-        return HNSW_ERR_ARG;
-    }
-    if (h->host->len() != 0 || is_replica(h)) {
-        set_error("hnsw_snapshot_adopt: the receiving handle must be empty (fresh from hnsw_create)");
-        return HNSW_ERR_ARG;
-    }
-    if (hd.kind != h->host->kind || hd.dim != h->host->dim || hd.m != (uint32_t)h->host->params.m) {
-        set_error("hnsw_snapshot_adopt: snapshot of a %ud kind-%d m=%u index offered to a %ud kind-%d m=%u handle", hd.dim,
-                  hd.kind, hd.m, h->host->dim, h->host->kind, (uint32_t)h->host->params.m);
-        return HNSW_ERR_BAD_DIM;
-    }
-    // Every stride in the header is recomputed from the receiving handle's own m, dim and kind and must agree (the
-    // kernels index the arrays by id without a range check, and a zero stride must never reach a division), then
-    // the array sizes must be what the header implies.
-    const bool q8 = h->host->kind == HNSW_VEC_QUANT8;
-    const uint32_t half = q8 ? hx::quant_half_bytes(hd.dim) : 0, stride = q8 ? 2 * half : hx::f32_row_stride(hd.dim);
-    const uint32_t S0 = hx::adj_stride(h->host->layer_m(0), 32), S1 = hx::adj_stride(h->host->params.m, 8);
-    const uint64_t fat_stride = ((uint64_t)hd.fat_stride_hi << 32) | hd.fat_stride_lo;
-    if (hd.S0 != S0 || hd.S1 != S1 || hd.row_stride != stride || hd.half_bytes != half || hd.nch4 != 4 * (hd.dim / 8) ||
-        hd.rem != hd.dim % 8 || (fat_stride != 0 && fat_stride != (uint64_t)S0 * stride)) {
-        set_error("hnsw_snapshot_adopt: the header's strides are not those of a %ud kind-%d m=%u index", hd.dim, hd.kind, hd.m);
-        return HNSW_ERR_ARG;
-    }
-    const uint64_t N = hd.n_points;
-    if (N == 0 || N > 0x7FFFFFFFull || d->bytes[0] != N * stride || d->bytes[1] != N * S0 * 4ull || d->bytes[3] != N * 4ull ||
-        d->bytes[2] == 0 || d->bytes[2] % (S1 * 4ull) != 0 || d->bytes[4] < 4 || d->bytes[4] % 4 != 0 || d->bytes[5] < 4 ||
-        (d->bytes[6] != 0) != (fat_stride != 0) || (fat_stride != 0 && d->bytes[6] != N * fat_stride) || hd.ep >= N ||
-        hd.nb_layers == 0) {
-        set_error("hnsw_snapshot_adopt: array sizes do not match the header");
-        return HNSW_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> g(h->mu);
-    uint64_t nb[7];
-    void *pp[7];
-    for (int i = 0; i < 7; i++) nb[i] = d->bytes[i];
-    int rc = h->dev.adopt_alloc(h->device, nb, pp);
-    if (rc != HNSW_OK) {
-        h->dev.release();
-        return rc;
-    }
-    h->device = h->dev.device;
-    for (int i = 0; i < 7; i++) d->ptr[i] = pp[i];
-    hx::DevView v{};
-    v.kind = hd.kind;
-    v.dim = hd.dim;
-    v.n_points = hd.n_points;
-    v.nb_layers = hd.nb_layers;
-    v.ep = hd.ep;
-    v.S0 = hd.S0;
-    v.S1 = hd.S1;
-    v.row_stride = hd.row_stride;
-    v.half_bytes = hd.half_bytes;
-    v.nch4 = hd.nch4;
-    v.rem = hd.rem;
-    v.fat_stride = ((uint64_t)hd.fat_stride_hi << 32) | hd.fat_stride_lo;
-    h->dev.view = v;     // scalars now, pointers at commit
-    h->dev.replica = true;
-    h->cosine = (hd.flags & 1u) != 0;
-    return HNSW_OK;
-}
-
-int hnsw_snapshot_commit(hnsw_index *h) {
-    if (!h) return HNSW_ERR_ARG;
-    std::lock_guard<std::mutex> g(h->mu);
-    if (!h->dev.replica || h->dev.valid) {
-        set_error("hnsw_snapshot_commit: no adopted snapshot waiting");
-        return HNSW_ERR_ARG;
-    }
-    HIP_TRY(hipSetDevice(h->dev.device));
-    HIP_TRY(hipDeviceSynchronize());  // whatever filled the arrays has finished
-    h->dev.adopt_commit(h->dev.view);
-    h->host->params.ep = h->dev.view.ep;
-    return HNSW_OK;
-}
+int hnsw_snapshot_adopt(hnsw_index *h, hnsw_snapshot_desc *d) { return h && d ? hx::snapshot_adopt(h, d) : HNSW_ERR_ARG; }
+int hnsw_snapshot_commit(hnsw_index *h) { return h ? hx::snapshot_commit(h) : HNSW_ERR_ARG; }
 
 // ---- harness helpers -----------------------------------------------------------------------------------
 int hnsw_synth_rows(int recipe, uint64_t seed, uint64_t first_row, uint64_t n, uint32_t d, float *out,

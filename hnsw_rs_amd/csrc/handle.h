@@ -88,6 +88,15 @@ int check_search_args(const hnsw_index *h, uint32_t ef);
 // the HBM snapshot is what the host index holds (uploaded if not) and its device is the calling thread's
 int ensure_uploaded(hnsw_index *h);
 
+// options.cpp: one table of the options, one of the statistics; a clone takes every option as its parent stores it
+int set_option(hnsw_index *h, const char *key, int64_t value);
+void copy_options(hnsw_index *to, const hnsw_index *from);
+int get_stat(const hnsw_index *h, const char *key, uint64_t *out);
+// snapshot.cpp: hnsw_snapshot_describe (of a handle that passed check_search_args), _adopt and _commit
+int snapshot_describe(hnsw_index *h, hnsw_snapshot_desc *out);
+int snapshot_adopt(hnsw_index *h, hnsw_snapshot_desc *d);
+int snapshot_commit(hnsw_index *h);
+
 struct ScratchLease {  // takes a scratch from the handle's pool, gives it back at scope exit
     hnsw_index *h;
     std::unique_ptr<SearchScratch> s;

@@ -154,4 +154,10 @@ int labels_on_device(hnsw_index *h, const uint32_t **d_labels, uint64_t *label_l
 int search_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t *d_ids,
                          float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, hipStream_t stream);
 
+// The two ground-truth scans (ground_truth.cpp) behind hnsw_brute_force and hnsw_brute_force_fast, which have checked
+// the handle and the arguments: every point in the reference's arithmetic (while ids are deleted, the undeleted ones);
+// the screen on the matrix cores with the exact re-rank of its k + 8 survivors (k + 8 <= brute_mfma_k2())
+int exact_scan(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids, float *dists);
+int mfma_scan(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids, float *dists);
+
 }  // namespace hx

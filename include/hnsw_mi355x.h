@@ -86,7 +86,9 @@ const char *hnsw_version(void);
  * (defaults ef_cons = 2m, mmax = m, mmax0 = 2m, ml = 1/ln(m): params.rs:20-42). */
 int hnsw_create(uint32_t m, uint32_t ef_cons, uint32_t dim, int vec_kind, hnsw_index **out);
 void hnsw_free(hnsw_index *h);
-/* #[derive(Clone)] on HNSW, template.rs:35 (benches clone the index, hnsw_benchmarks.rs:23) */
+/* #[derive(Clone)] on HNSW, template.rs:35 (benches clone the index, hnsw_benchmarks.rs:23).  The clone starts with
+ * every option of hnsw_set_option as its parent holds it ("filter_exact_grouped" and "mask_set_cache_mb" included), on
+ * the parent's device, with the parent's deleted ids and labels; its HBM snapshot and its counters are its own. */
 int hnsw_clone(const hnsw_index *h, hnsw_index **out);
 
 int hnsw_get_params(const hnsw_index *h, hnsw_params *out);
@@ -737,7 +739,8 @@ int hnsw_set_device(hnsw_index *h, int device);
 /* make the HBM snapshot current now (otherwise done lazily by the first search after a mutation) */
 int hnsw_upload(hnsw_index *h);
 int hnsw_device_bytes(const hnsw_index *h, uint64_t *bytes);
-/* tuning knobs of the HBM snapshot (take effect at the next upload):
+/* options of a handle; hnsw_clone copies every one of them to the clone.  The first two are tuning knobs of the HBM
+ * snapshot (take effect at the next upload):
  *   "inline_rows"      -1 auto (default) / 0 never / 1 always: the layer-0 "inline rows" layout (a
  *                      copy of every neighbour's vector row next to the adjacency slot, so that one
  *                      expansion is one coalesced read; costs 2m x the row bytes of HBM)

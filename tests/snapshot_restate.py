@@ -1,5 +1,5 @@
 """The HBM snapshot restated in numpy from the layout comment of hnsw_rs_amd/csrc/device_index.h (and the header words
-of hnsw_snapshot_desc, capi.cpp), and the checks that hold a live snapshot to it.  Nothing here calls product code
+of hnsw_snapshot_desc, snapshot.cpp), and the checks that hold a live snapshot to it.  Nothing here calls product code
 beyond the C ABI's accessors: hnsw_snapshot_describe to read a snapshot back, hnsw_get_params / hnsw_get_level /
 hnsw_get_quant / hnsw_get_vector / hnsw_export_layer (Graph.csr) to restate one.
 

@@ -340,6 +340,29 @@ def test_grouped_path_2_is_one_further_pass(three_paths):
         index.set_option("filter_exact_max", 65536)
 
 
+def test_a_clone_takes_filter_exact_grouped_from_its_parent():
+    """hnsw_clone copies every option: a clone of a parent under "filter_exact_grouped" = 1 runs its two exact-path groups
+    in three launches, a clone of a parent left at 0 in three per group, and both return the same"""
+    n_pts, d, G = 600, 16, 2
+    vs = rand_vectors(n_pts, d, 21)
+    parent = H.HNSW.new(16, 32, d, H.VEC_F32).insert_bulk(vs, 4, False, levels=O.draw_levels(n_pts, 16, 5))
+    parent.set_labels(np.arange(n_pts, dtype=np.uint32))
+    parent.set_option("filter_exact_max", n_pts + 1)  # every query by the exact path
+    Q = rand_vectors(6, d, 22)
+    rg = [(10, 300), (250, 599)]
+    lo = np.array([rg[i % G][0] for i in range(6)], dtype=np.uint32)
+    hi = np.array([rg[i % G][1] for i in range(6)], dtype=np.uint32)
+    got = {}
+    for grouped, want in ((0, (G, G, G)), (1, (1, 1, 1))):
+        parent.set_option("filter_exact_grouped", grouped)
+        clone = parent.clone()
+        with H.kernel_log() as log:
+            got[grouped] = clone.search_batch_filtered_range(Q, 10, 64, lo, hi)
+        assert (compacts(log), scans(log), merges(log)) == want, (grouped, dict(log))
+        assert (got[grouped][4] == 1).all() and (got[grouped][2] == 10).all()
+    same(got[0], got[1], "a clone of a grouped parent against a clone of a per-group parent")
+
+
 # ---- 4. unfiltered hnsw_search next to filtered callers -----------------------------------------------------------------
 def test_unfiltered_calls_keep_their_batches():
     index, orc, _, _ = build(N, 60, 16, H.VEC_F32)

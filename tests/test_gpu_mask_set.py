@@ -583,3 +583,34 @@ def test_cache_budget_zero_compacts_every_call(glove):
         index.set_option("mask_set_cache_mb", 64)
         index.set_option("filter_exact_max", 65536)
     check_rows(index, ridx, Q, 10, 64, list(masks_b), mo, 10 ** 9, kept, what="budget")
+
+
+def test_a_clone_takes_the_cache_budget_from_its_parent():
+    """hnsw_clone copies every option: under a parent's "mask_set_cache_mb" = 0 a clone keeps no list and compacts every
+    row at every call; a clone of a default parent keeps them (test_cache_budget_zero_compacts_every_call, on one handle)"""
+    n_pts, d, G = 600, 16, 2
+    vs = rand_vectors(n_pts, d, 23)
+    parent = H.HNSW.new(16, 32, d, H.VEC_F32).insert_bulk(vs, 4, False, levels=O.draw_levels(n_pts, 16, 5))
+    parent.set_labels(np.arange(n_pts, dtype=np.uint32))
+    parent.set_option("filter_exact_max", n_pts + 1)  # every query by the exact path
+    masks_b = np.random.default_rng(24).random((G, n_pts)) < 0.3
+    Q, mo = rand_vectors(6, d, 25), dealt(6, G)
+    got = {}
+    for budget in (None, 0):  # the default first
+        if budget is not None:
+            parent.set_option("mask_set_cache_mb", budget)
+        clone = parent.clone()
+        s = clone.mask_set(masks_b)
+        advance = []
+        for call in range(2):
+            before = stats_of(clone, SET_STATS)
+            got[budget, call] = clone.search_batch_filtered_set(Q, 10, 64, s, mo)
+            advance.append(delta(clone, before)["mask_set_compactions"])
+        assert (got[budget, 0][4] == 1).all()
+        if budget == 0:
+            assert advance == [G, G], advance
+        else:
+            assert advance[1] < G, advance
+        s.close()
+    for key in got:
+        same(got[key], got[None, 0], "clone %s" % (key,))
