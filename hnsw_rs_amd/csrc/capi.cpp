@@ -1,6 +1,6 @@
 // capi.cpp -- the extern "C" surface of libhnsw_mi355x.so (include/hnsw_mi355x.h): argument checks, dispatch,
 // accessors and persistence.  Host logic only; the search entry points upload the index snapshot to HBM on demand and
-// hand over to search_host.cpp (batches) or coalesce.cpp (hnsw_search), which launch the HIP kernels.  There is no CPU
+// hand over to search_host.cpp / filter_host.cpp (batches) or coalesce.cpp (hnsw_search), which launch the HIP kernels.  There is no CPU
 // search path.  Options and statistics are options.cpp's tables, the ground-truth scans ground_truth.cpp's, snapshot
 // replication snapshot.cpp's.  (The two entry points of partitioned search are partition.cpp's.)
 

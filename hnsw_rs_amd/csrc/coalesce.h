@@ -19,7 +19,7 @@
 // stages the caller's (row, lo, hi) next to its query; the leader states the batch's filter once -- the rows of `set`
 // (or every id), one label range per query, the staged arrays -- and answers it by search_filtered with the exact path
 // in its grouped form: the queries on the graph path share one launch whatever their filters, those on the exact path
-// three (search_host.cpp, exact_grouped).  With the window off (coalesce_us < 0) a filtered call still comes through
+// three (filter_exact.cpp, exact_grouped).  With the window off (coalesce_us < 0) a filtered call still comes through
 // here, as a batch of its own that nobody else sees.
 #pragma once
 

@@ -46,7 +46,7 @@ struct hnsw_index {
     // answered by the exact scan ("Filtered search", for the measured crossover); queries per path
     int64_t filter_exact_max = 65536;
     // option "filter_exact_grouped": the batch entry points run a call's exact-path groups in the grouped form (three
-    // launches for all of them, search_host.cpp) instead of group by group; hnsw_search_filtered always does
+    // launches for all of them, filter_exact.cpp) instead of group by group; hnsw_search_filtered always does
     int filter_exact_grouped = 0;
     std::atomic<uint64_t> n_filt_graph{0}, n_filt_exact{0}, n_filt_overflow{0};
     // hnsw_search_batch_filtered_multi: calls, and the masks their queries referenced (no mask counts as one)

@@ -1,5 +1,5 @@
 // labels.cpp -- the label column of a handle (labels.h): the host mirror and the sorted copy the range planner counts
-// with.  Host logic only; the HBM copy is HbmWords' (deleted_mask.hip), the searches are search_host.cpp's.
+// with.  Host logic only; the HBM copy is HbmWords' (deleted_mask.hip), the searches are filter_host.cpp's, their planner filter_plan.cpp.
 
 #include "labels.h"
 

@@ -1,6 +1,6 @@
 // mask_set.cpp -- hnsw_mask_set (mask_set.h): the C entry points that manage a set on the host, and what a search
 // asks of it: the HBM copy brought up to date, a row's admissible ids counted once, room for its compacted list.
-// Host logic only; the searches under a set are search_host.cpp's.
+// Host logic only; the searches under a set are filter_host.cpp's, the counting of a row next to a range filter_plan.cpp's.
 
 #include "mask_set.h"
 

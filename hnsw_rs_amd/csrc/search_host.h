@@ -1,5 +1,5 @@
-// search_host.h -- the host side of the search entry points (search_host.cpp): the host-pointer path, the
-// filtered / deleted orchestration and the completion of a device-pointer call (internal)
+// search_host.h -- the host side of the search entry points: the host-pointer path and the completion of a
+// device-pointer call (search_host.cpp), the filtered / deleted orchestration (filter_host.cpp) (internal)
 #pragma once
 
 #include <cstring>
@@ -120,7 +120,7 @@ uint64_t count_admissible(const hnsw_index *h, const uint64_t *allow, uint64_t b
 // statuses in stats: required), or, when pin_block is given, straight into that pinned ResultBlock(nq, n) and the
 // buffers are not read.  Returns argument and launch errors only.
 // grouped: a call with two or more exact-path groups runs them in the grouped form, three launches for all of them
-// (search_host.cpp, exact_grouped), and its path 2 groups in one more such pass; false: as the handle's option
+// (filter_exact.cpp, exact_grouped), and its path 2 groups in one more such pass; false: as the handle's option
 // "filter_exact_grouped" says (0: group by group).  The results do not depend on it.
 int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f,
                     bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,

@@ -17,7 +17,7 @@ import hnsw_rs_amd as H
 from hnsw_rs_amd import _lib
 from oracle import oracle_py as O
 from tests.test_gpu_call_pattern import build
-from tests.test_gpu_labels import glove_ranges, three_path_labels
+from tests.test_gpu_labels import device_call, glove_ranges, three_path_labels
 from tests.test_gpu_mask_set import same, three_paths  # noqa: F401
 from tests.util import rand_vectors
 
@@ -338,6 +338,31 @@ def test_grouped_path_2_is_one_further_pass(three_paths):
         assert (compacts(log0), scans(log0), merges(log0)) == (2, 2, 2) == (compacts(log1), scans(log1), merges(log1))
     finally:
         index.set_option("filter_exact_max", 65536)
+
+
+def test_grouped_path_2_of_a_device_finish(three_paths):
+    """the device form's _finish has counted nothing when a query reaches path 2: its late groups' offsets lie one behind
+    the other in a lease sized on the spot, and the grouped form answers them in one pass"""
+    index, ridx, mask_list, Q, _ = three_paths
+    index.set_labels(three_path_labels(mask_list))
+    lo = np.tile(np.array([1, 3, 5, 0, 3, 5, 1, 0], dtype=np.uint32), 4)
+    hi = np.tile(np.array([1, 3, 5, MAX, 4, 6, 1, MAX], dtype=np.uint32), 4)
+
+    def call():
+        code, dev = device_call(index, Q, 10, 64, lo, hi)
+        assert code is None
+        return dev
+    got, log0, log1 = both(index, call)
+    index.set_option("filter_exact_max", -1)
+    try:
+        want = index.search_batch_filtered_range(Q, 10, 64, lo, hi)
+    finally:
+        index.set_option("filter_exact_max", 65536)
+    same(got, want, "device form against the host form")
+    late = {(int(l), int(h_)) for l, h_, p in zip(lo, hi, got[4]) if p == 2}
+    assert len(late) >= 2, got[4]
+    assert (compacts(log0), scans(log0), merges(log0)) == (len(late),) * 3, log0
+    assert (compacts(log1), scans(log1), merges(log1)) == (1, 1, 1), log1
 
 
 def test_a_clone_takes_filter_exact_grouped_from_its_parent():
