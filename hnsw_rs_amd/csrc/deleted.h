@@ -43,8 +43,8 @@ struct HbmWords {
     bool current(int device) const { return d_words && d_device == device && dirty.empty(); }
     // brings the HBM copy of host[nw] on `device` up to date: the changed words as (index, value) pairs scattered by
     // hx_deleted_scatter_kernel, or one whole copy when there is no copy yet (made with room for `slack` more words,
-    // zeroed), the device changed or more than an eighth of the words changed.  Synchronises `stream` before
-    // returning.
+    // zeroed), the device changed, the host words have outgrown it (d_cap < nw: made afresh, whether or not a word is
+    // listed) or more than an eighth of the words changed.  Synchronises `stream` before returning.
     int sync_words(const uint64_t *host, uint64_t nw, uint64_t slack, int device, hipStream_t stream);
     void release_device();
 };

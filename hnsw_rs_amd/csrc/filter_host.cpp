@@ -21,7 +21,9 @@ namespace {
 int sync_deleted(hnsw_index *h) {
     if (h->del.count == 0) return HNSW_OK;
     std::lock_guard<std::mutex> g(h->mu);
-    if (h->del.d_words && h->del.d_device == h->dev.device && h->del.dirty.empty()) return HNSW_OK;
+    // (a mark or unmark that changed no id still grows the host words to the index length: a copy they have outgrown is
+    // made afresh even with no word listed, as the label column's is -- the kernels read deny_bits = all host words)
+    if (h->del.current(h->dev.device) && h->del.words.size() <= h->del.d_cap) return HNSW_OK;
     ScratchLease lease(h);
     int rc = lease.prepare(h->dev.device, 0, 0);
     if (rc != HNSW_OK) return rc;
