@@ -106,6 +106,9 @@ const Stat kStats[] = {
     HX_STAT("shard_merges", h.n_shard_merges),
     HX_STAT("grouped_calls", h.n_grouped_calls),
     HX_STAT("grouped_launches", h.n_grouped_launches),
+    HX_STAT("radius_calls", h.n_radius_calls),
+    HX_STAT("radius_rungs", h.n_radius_rungs),
+    HX_STAT("radius_launches", h.n_radius_launches),
     HX_STAT("deleted", h.del.count),
     HX_STAT("deleted_mask_words_uploaded", h.del.words_uploaded),
     HX_STAT("deleted_queries_graph", h.n_del_graph),

@@ -93,9 +93,19 @@ struct RangeList {
 // The ids and distances go to FilterArgs::out_ids / out_dists as [q][n_groups][per_group], the number of groups to
 // out_counts, the query's stats record to out_stats unchanged, the groups' labels and sizes to group_labels /
 // group_sizes [q][n_groups].  FilterArgs::n is not read.
+//
+// The fourth source form (hnsw_radius_cut_device), selected by cut_out != 0 next to ids (zero in
+// every other launch): ONE candidate list per query, ids[q][j] / dists[q][j], j < pool, counts[q] and stats[q] as above,
+// cut at radius[q] -- the present entries with dist <= radius[q] (an f32 compare: a NaN on either side keeps nothing), in
+// their input order, to FilterArgs::out_ids / out_dists as [q][cut_out], padded behind; their number to out_counts, the
+// stats record to out_stats unchanged, HX_RADIUS_MORE to flags[q] iff the status is HNSW_OK, all pool entries are
+// present and all of them were kept.  Block b serves query FilterArgs::qsel[b] when that is set (an entry at or beyond
+// nq is not served); the rows of other queries are not touched.  Nothing is sorted and no LDS is used.
 #define HX_MERGE_MAX_SHARDS 64
 #define HX_GROUP_POOL_MAX 256     // candidates per query: four per lane
 #define HX_GROUP_SLOTS_MAX 1024   // n_groups x per_group: the slot table in LDS
+#define HX_RADIUS_MAX_N 1024      // entries per list of the cut: a search's register-resident list
+#define HX_RADIUS_MORE 1u
 struct MergeLists {
     const uint32_t *ids;
     const float *dists;
@@ -105,8 +115,11 @@ struct MergeLists {
     uint32_t base[HX_MERGE_MAX_SHARDS], stride[HX_MERGE_MAX_SHARDS];
     const uint32_t *labels;   // the label column (device), or nullptr
     uint64_t label_len;       // labels the column holds; an id at or beyond it has label 0
-    uint32_t pool, n_groups, per_group, pad;
+    uint32_t pool, n_groups, per_group;
+    uint32_t cut_out;         // != 0: the cut form, and the stride of its output rows (pool <= cut_out)
     uint32_t *group_labels, *group_sizes;
+    const float *radius;      // the cut form: nq radii (device)
+    uint32_t *flags;          // the cut form: nq flag words, or nullptr
 };
 
 // The grouped form of the exact path: the exact-path groups of a call in ONE compaction, ONE scan
@@ -182,5 +195,11 @@ int launch_merge_lists(const MergeLists &m, uint32_t n, uint32_t *out_ids, float
 // nullptr; out_stats goes with m.stats.
 int launch_group_by_label(const MergeLists &m, uint32_t *out_ids, float *out_dists, uint32_t *out_counts,
                           hnsw_query_stats *out_stats, hipStream_t stream);
+// the cut at a radius of candidate lists of m.pool entries into rows of m.cut_out (the fourth form; m.ids, m.dists,
+// m.radius, m.pool and m.cut_out set, 1 <= pool <= cut_out <= HX_RADIUS_MAX_N): ONE launch of hx_filt_merge_kernel, one
+// wave per served query -- the n_sel queries of sel (device), or, with sel == nullptr, all m.nq.  out_counts and m.flags
+// may be nullptr; out_stats goes with m.stats.
+int launch_radius_cut(const MergeLists &m, const uint32_t *sel, uint32_t n_sel, uint32_t *out_ids, float *out_dists,
+                      uint32_t *out_counts, hnsw_query_stats *out_stats, hipStream_t stream);
 
 }  // namespace hx

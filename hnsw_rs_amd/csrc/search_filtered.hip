@@ -845,9 +845,60 @@ __device__ __forceinline__ void collapse_by_label(const FilterArgs &a, const Mer
     }
 }
 
+// The merge kernel's cut form (MergeLists with cut_out != 0, search_filtered.h): the candidate
+// list of m.pool entries of query a.qsel[blockIdx.x] (or blockIdx.x), walked 64 entries at a time with the next 64
+// already requested, cut at the query's radius.  A kept entry's slot is the number kept before it: the running total of
+// the steps behind plus the popcount of this step's ballot below the lane, so the kept entries stay in their input
+// order.  Then the lanes stream the pad from the count to the end of the row: every output word is written once.  No
+// LDS, no list registers.
+__device__ __forceinline__ void cut_at_radius(const FilterArgs &a, const MergeLists &m, int lane) {
+    const uint32_t q = a.qsel ? a.qsel[blockIdx.x] : blockIdx.x;
+    const uint32_t n_in = m.pool, n_out = m.cut_out;
+    if (q >= m.nq || n_in > n_out || n_out > HX_RADIUS_MAX_N) return;  // (the launcher's limits; a selection's bound)
+    const uint32_t *dist_bits = reinterpret_cast<const uint32_t *>(m.dists);
+    hnsw_query_stats st;
+    st.n_dist = st.n_exp = st.sum_deg = 0;
+    st.status = HNSW_OK;
+    if (m.stats) st = m.stats[q];
+    const float radius = m.radius[q];
+    const uint32_t cnt = m.counts ? min(m.counts[q], n_in) : n_in;
+    const bool ok = st.status == HNSW_OK;  // a failed query has no present entry: count 0, a padded row, no flag
+    const size_t in0 = (size_t)q * n_in, out0 = (size_t)q * n_out;
+    uint32_t w = 0, n_present = 0;  // wave-uniform
+    uint32_t nx_id = (uint32_t)lane < n_in ? m.ids[in0 + lane] : HX_EMPTY_SLOT;
+    uint32_t nx_bits = (uint32_t)lane < n_in ? dist_bits[in0 + lane] : 0u;
+    for (uint32_t base = 0; base < n_in; base += 64) {
+        const uint32_t j = base + lane, id = nx_id, bits = nx_bits;
+        if (j + 64 < n_in) {
+            nx_id = m.ids[in0 + j + 64];
+            nx_bits = dist_bits[in0 + j + 64];
+        }
+        const bool present = ok && j < n_in && (m.counts ? j < cnt : id != HX_EMPTY_SLOT);
+        const bool kept = present && __builtin_bit_cast(float, bits) <= radius;  // (false for a NaN on either side)
+        const u64 km = __ballot(kept);
+        n_present += (uint32_t)__popcll(__ballot(present));
+        if (kept) {
+            const uint32_t slot = w + (uint32_t)__popcll(km & ((1ull << lane) - 1));  // < n_in <= n_out
+            a.out_ids[out0 + slot] = id;
+            a.out_dists[out0 + slot] = __builtin_bit_cast(float, bits);
+        }
+        w += (uint32_t)__popcll(km);
+    }
+    for (uint32_t s = w + lane; s < n_out; s += 64) {
+        a.out_ids[out0 + s] = HX_EMPTY_SLOT;
+        a.out_dists[out0 + s] = __builtin_inff();
+    }
+    if (lane == 0) {
+        if (a.out_counts) a.out_counts[q] = w;
+        if (m.flags) m.flags[q] = ok && n_present == n_in && w == n_present ? HX_RADIUS_MORE : 0u;
+        if (a.out_stats) a.out_stats[q] = st;
+    }
+}
+
 // Merge: one wave per query folds the nseg partial lists into its top n and writes the results.  With m.ids set the
 // lists are those of m.n_shards shards instead (merge_shard_lists; A, nseg, part and part_status are not read), or, with
-// m.per_group set as well, the query's one candidate list, collapsed by label (collapse_by_label).  With
+// m.per_group set as well, the query's one candidate list, collapsed by label (collapse_by_label), or, with m.cut_out
+// set instead, that list cut at the query's radius (cut_at_radius).  With
 // qtab set (the grouped form) A, nseg and the first row of the query's partial lists are its record's.
 __global__ void __launch_bounds__(64) hx_filt_merge_kernel(const FilterArgs a, uint32_t A, uint32_t nseg,
                                                            const u64 *part, const int32_t *part_status,
@@ -861,7 +912,10 @@ __global__ void __launch_bounds__(64) hx_filt_merge_kernel(const FilterArgs a, u
         return;
     }
     if (m.ids) {
-        merge_shard_lists(a, m, perm, lane);
+        if (m.cut_out)
+            cut_at_radius(a, m, lane);
+        else
+            merge_shard_lists(a, m, perm, lane);
         return;
     }
     const uint32_t y = blockIdx.x;
@@ -1055,6 +1109,29 @@ int launch_group_by_label(const MergeLists &lists, uint32_t *out_ids, float *out
     a.out_counts = out_counts;
     a.out_stats = out_stats;
     return launch_checked({"group by label kernel launch"}, hx_filt_merge_kernel, dim3(m.nq), dim3(64), 0, stream, a, 0u, 0u,
+                          static_cast<const u64 *>(nullptr), static_cast<const int32_t *>(nullptr), m,
+                          static_cast<const ExactQuery *>(nullptr));
+}
+
+int launch_radius_cut(const MergeLists &lists, const uint32_t *sel, uint32_t n_sel, uint32_t *out_ids, float *out_dists,
+                      uint32_t *out_counts, hnsw_query_stats *out_stats, hipStream_t stream) {
+    MergeLists m = lists;
+    const uint32_t nblocks = sel ? n_sel : m.nq;
+    if (nblocks == 0) return HNSW_OK;
+    if (m.pool == 0 || m.pool > m.cut_out || m.cut_out > HX_RADIUS_MAX_N || m.nq > 0x7FFFFFFFu || nblocks > m.nq || !m.ids ||
+        !m.dists || !m.radius || !out_ids || !out_dists || (m.stats != nullptr) != (out_stats != nullptr)) {
+        set_error("radius cut: needs 1 <= n_in <= n_out <= %d, at most 2^31 - 1 queries, a selection no longer than that, "
+                  "the lists, the radii and the outputs", HX_RADIUS_MAX_N);
+        return HNSW_ERR_ARG;
+    }
+    m.per_group = 0;  // (the collapse form's selector)
+    FilterArgs a{};   // the form reads the selection and the outputs
+    a.qsel = sel;
+    a.out_ids = out_ids;
+    a.out_dists = out_dists;
+    a.out_counts = out_counts;
+    a.out_stats = out_stats;
+    return launch_checked({"radius cut kernel launch"}, hx_filt_merge_kernel, dim3(nblocks), dim3(64), 0, stream, a, 0u, 0u,
                           static_cast<const u64 *>(nullptr), static_cast<const int32_t *>(nullptr), m,
                           static_cast<const ExactQuery *>(nullptr));
 }

@@ -530,6 +530,44 @@ class HNSW:
             self._h, nq, pool, n_groups, per_group, p(d_ids_in), p(d_dists_in), p(d_counts_in), p(d_stats_in), p(d_ids),
             p(d_dists), p(d_group_labels), p(d_group_sizes), p(d_counts), p(d_stats), stream or None))
 
+    # ---- radius search: every neighbour within a distance (include/hnsw_mi355x.h) ----------------------------------
+    def search_batch_radius(self, Q, radius, n_first=16, max_n=256, ef=0):
+        """Every neighbour of a query within its radius, out of the candidate lists that search_batch returns on a
+        ladder of n = n_first, 2 n_first, ... up to max_n with ef = max(ef, n) (hnsw_search_batch_radius).  radius:
+        [nq], or a scalar broadcast to all queries; in the unit of the returned distances, >= 0, +inf is legal.
+        -> ids [nq, max_n] (pad UINT32_MAX), dists [nq, max_n] (pad +inf), counts [nq], flags [nq] (RADIUS_MORE:
+        truncated at max_n), rungs [nq] (searches the query took part in), stats [nq, 4] (its last rung's)"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        nq, width = Q.shape[0], max(int(max_n), 1)
+        radius = np.asarray(radius, dtype=np.float32)
+        if radius.ndim > 1 or (radius.ndim == 1 and radius.shape[0] != nq):
+            raise ValueError("radius is a scalar or one value per query")
+        radius = np.ascontiguousarray(np.broadcast_to(radius, (nq,)))
+        ids = np.full((nq, width), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, width), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        flags = np.zeros(nq, dtype=np.uint32)
+        rungs = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        check(self._L.hnsw_search_batch_radius(
+            self._h, _p(Q, _f32p), nq, _p(radius, _f32p), n_first, max_n, ef, _p(ids, _u32p), _p(dists, _f32p),
+            _p(counts, _u32p), _p(flags, _u32p), _p(rungs, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
+        return ids, dists, counts, flags, rungs, stats.view(np.uint32).astype(np.int64)
+
+    @staticmethod
+    def radius_cut_device(nq, n_in, n_out, d_radius, d_ids_in, d_dists_in, d_counts_in, d_stats_in, d_ids, d_dists,
+                          d_counts=None, d_flags=None, d_stats=None, d_sel=None, n_sel=0, stream=0):
+        """hnsw_radius_cut_device over torch device tensors (or raw device pointers): the [nq, n_in] candidate lists a
+        *_device search left (d_counts_in / d_stats_in [nq] or None), cut at d_radius [nq] into d_ids / d_dists
+        [nq, n_out] (/ d_counts / d_flags / d_stats), for the n_sel queries of d_sel or, with d_sel None, for all.
+        ONE launch enqueued on `stream` of the current device, no sync of it; needs no index."""
+        p = HNSW._dptr
+        check(_lib.lib().hnsw_radius_cut_device(
+            nq, n_in, n_out, p(d_radius), p(d_sel), n_sel, p(d_ids_in), p(d_dists_in), p(d_counts_in), p(d_stats_in),
+            p(d_ids), p(d_dists), p(d_counts), p(d_flags), p(d_stats), stream or None))
+
     def search_filtered(self, q, n, ef, lo=0, hi=0xFFFFFFFF, mask_set=None, row=None):
         """ONE query under the label range [lo, hi] and, with a resident MaskSet, its row `row` (None, -1 or MASK_NONE: no
         row): hnsw_search_filtered, whose concurrent callers on an index are gathered into one launch.

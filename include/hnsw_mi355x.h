@@ -629,6 +629,72 @@ int hnsw_search_batch_grouped(hnsw_index *h, const float *Q, uint64_t nq, uint32
                               uint32_t *group_sizes /* or NULL */, uint32_t *counts /* or NULL */,
                               hnsw_query_stats *stats /* or NULL */);
 
+/* ---- radius search: every neighbour within a distance, found by a doubling ladder ---------------------------------
+ * An extension (the reference answers "the n nearest" only): near-duplicate detection, score-threshold retrieval
+ * (Qdrant's score_threshold, FAISS's range_search), clustering.
+ * THE CUT of one query's candidate list of n_in entries (id_j, dist_j), j < n_in, at its radius, in the order given (the
+ * cut is defined by position and sorts nothing):
+ *   - entry j is PRESENT iff j < min(count, n_in), or, without counts, iff id_j != UINT32_MAX; absent entries take no
+ *     part, wherever they are;
+ *   - a present entry is KEPT iff dist_j <= radius, an f32 compare: a NaN distance is never kept, a NaN radius keeps
+ *     nothing;
+ *   - the w kept entries go to ids [0, w) and dists [0, w) in their input order, with the input's distance bits; slots
+ *     [w, n_out) are padded with UINT32_MAX and +inf; counts = w;
+ *   - flags has HNSW_RADIUS_MORE set iff the status is HNSW_OK, the number of present entries equals n_in and every
+ *     present entry was kept: the list was full and showed nothing outside the radius, so there may be more.
+ * A query's stats record passes through unchanged; a query whose incoming status is not HNSW_OK gets count 0, a padded
+ * row and flags 0.  Limits: 1 <= n_in <= n_out <= HNSW_RADIUS_MAX_N (beyond 1024 entries the candidate list of a search
+ * leaves the wave's registers for the spill kernel, orders of magnitude slower).
+ *
+ * hnsw_radius_cut_device is THE CUT alone over lists in HBM: every d_* pointer is device memory on the current device
+ * (the call needs no handle, as hnsw_merge_topk_device), the inputs d_ids_in / d_dists_in [nq][n_in], d_counts_in [nq]
+ * or NULL, d_stats_in [nq] or NULL are what any *_device search leaves after its _finish, d_radius [nq] the radii.  With
+ * d_sel, n_sel entries naming queries below nq, launch block b serves query d_sel[b] and the rows of every other query
+ * are not touched (an entry at or beyond nq is not served; a query named twice is written twice with the same words);
+ * without, all nq are served.  Every output word of a served query is written exactly once.  ONE launch (the exact
+ * path's merge kernel in its cut form, one wave per served query) is enqueued on `stream`; nothing is allocated, copied
+ * or synchronised.  Outputs must not overlap inputs.  d_counts and d_flags may be NULL; d_stats is required iff
+ * d_stats_in is given.  HNSW_ERR_ARG, decided before the device is touched: the limits violated; nq > 2^31 - 1;
+ * d_radius, d_ids_in, d_dists_in, d_ids or d_dists NULL; d_sel given together with n_sel > nq; exactly one of d_stats_in
+ * / d_stats given.  nq == 0 is HNSW_OK and launches nothing; so is d_sel given with n_sel == 0.
+ *
+ * hnsw_search_batch_radius answers host-pointer queries by THE LADDER, defined by existing calls.  Rung k has n_k =
+ * min(n_first << k, max_n) and ef_k = max(ef, n_k); L_k(q) is what hnsw_search_batch returns for the original query
+ * with n = n_k and ef = ef_k on the same handle with the same options: its ids, distance bits, count and stats.  Query q
+ * stops at the first rung k at which its status is not HNSW_OK, or THE CUT of L_k(q) does not set HNSW_RADIUS_MORE, or
+ * n_k == max_n.  Its answer is THE CUT of that L_k(q) at stride max_n: ids and dists [nq][max_n], counts = w, stats that
+ * rung's record, rungs = k + 1, and flags keeps HNSW_RADIUS_MORE only in the third case, where it means "truncated at
+ * max_n".  The first per-query error is returned, every other row is filled in.  Everything of the candidate call is
+ * inherited: the cosine option (the radius is in the unit of the returned distances), deletions, overflow re-runs.
+ * While ids are deleted hnsw_search_batch is the filtered search: max_n <= 64 is required, and max(ef, n_k) <= 256
+ * whenever the graph path is taken.  Unfiltered with nothing deleted the call stays on the device: the queries go up
+ * once (their unit-length copy under the cosine option is made once), every rung is one search launch over the
+ * unfinished queries, its overflow re-runs and one cut launch over the same queries into the final block, only the nq
+ * flag words come back between rungs, and the final block comes back in one copy.  While ids are deleted each rung's
+ * candidates come from the HOST form of hnsw_search_batch on the unfinished queries and their lists go up before the
+ * same cut: only the host form lets the planner choose the exact path.  dists, counts, flags, rungs and stats may be
+ * NULL.  HNSW_ERR_ARG, decided before the device is touched: 1 <= n_first <= max_n <= HNSW_RADIUS_MAX_N violated (a
+ * call has at most 11 rungs); Q, radius or ids NULL; nq > 2^31 - 1; a radius that is negative or NaN (+inf is legal);
+ * max_n > 64 while ids are deleted.  nq == 0 is HNSW_OK; an empty index is HNSW_ERR_EMPTY.  hnsw_get_stat:
+ * "radius_calls", "radius_rungs", "radius_launches".
+ * Not provided: a radius inside the walk (the walk is the candidate call's, unchanged); CSR output from C (the Python
+ * package's to_csr makes it); filters other than deletions; radius search over shards; one-query gathered calls; the
+ * Rust shim's binding. */
+#define HNSW_RADIUS_MAX_N 1024
+#define HNSW_RADIUS_MORE  1u
+int hnsw_radius_cut_device(uint64_t nq, uint32_t n_in, uint32_t n_out,
+                           const float *d_radius /* nq */, const uint32_t *d_sel /* or NULL */, uint64_t n_sel,
+                           const uint32_t *d_ids_in, const float *d_dists_in /* nq x n_in */,
+                           const uint32_t *d_counts_in /* or NULL */, const hnsw_query_stats *d_stats_in /* or NULL */,
+                           uint32_t *d_ids, float *d_dists /* nq x n_out */, uint32_t *d_counts /* or NULL */,
+                           uint32_t *d_flags /* or NULL */, hnsw_query_stats *d_stats /* required iff d_stats_in */,
+                           void *stream);
+int hnsw_search_batch_radius(hnsw_index *h, const float *Q, uint64_t nq, const float *radius /* nq */,
+                             uint32_t n_first, uint32_t max_n, uint32_t ef,
+                             uint32_t *ids /* nq x max_n */, float *dists /* or NULL */, uint32_t *counts /* or NULL */,
+                             uint32_t *flags /* or NULL */, uint32_t *rungs /* or NULL */,
+                             hnsw_query_stats *stats /* or NULL */);
+
 /* Test seams that mirror the reference's own units:
  * VecBase::dist2many (vectors/src/lib.rs:17-22): the query (quantised like ann_by_vector does,
  * template.rs:313) against stored ids, on the device, exact accumulation order. */
@@ -807,7 +873,8 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * partitioned search, on the handle passed as shard 0: "shard_calls"
  * (hnsw_search_batch_shards calls whose shards were all searched), "shard_merges" (the merges they launched); grouped
  * search: "grouped_calls" (hnsw_search_batch_grouped calls answered), "grouped_launches" (collapses launched,
- * hnsw_group_by_label_device's included); deletion:
+ * hnsw_group_by_label_device's included); radius search: "radius_calls" (hnsw_search_batch_radius calls answered),
+ * "radius_rungs" (the search rungs they launched), "radius_launches" (the cuts they launched); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
