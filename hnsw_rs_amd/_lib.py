@@ -14,6 +14,7 @@ VEC_QUANT8 = 0
 VEC_F32 = 1
 UINT32_MAX = 0xFFFFFFFF
 GROUP_POOL_MAX = 256  # HNSW_GROUP_POOL_MAX: candidates per query of a grouped search
+DIVERSE_POOL_MAX = 256  # HNSW_DIVERSE_POOL_MAX: candidates per query of a diversified search
 RADIUS_MAX_N = 1024  # HNSW_RADIUS_MAX_N: entries per list of a radius search
 RADIUS_MORE = 1  # HNSW_RADIUS_MORE: the list was full and showed nothing outside the radius
 RANGES_MAX = 16  # HNSW_RANGES_MAX: members of a query's range list
@@ -137,6 +138,10 @@ SYMBOLS = {
                                          vp, vp, vp]),
     "hnsw_search_batch_radius": (C.c_int, [vp, f32p, C.c_uint64, f32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, f32p, u32p,
                                            u32p, u32p, C.POINTER(QueryStats)]),
+    "hnsw_diversify_device": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                        vp]),
+    "hnsw_search_batch_diverse": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, u32p,
+                                            u32p, u32p, u32p, f32p, f32p, u32p, C.POINTER(QueryStats)]),
     "hnsw_distance_batch": (C.c_int, [vp, f32p, u32p, C.c_uint64, f32p]),
     "hnsw_search_layer": (C.c_int, [vp, C.c_uint32, f32p, u32p, C.c_uint32, C.c_uint32, u32p, f32p, u32p,
                                     C.POINTER(QueryStats)]),

@@ -289,6 +289,31 @@ int launch_normalise_rows(float *d_rows, uint64_t n, uint32_t d, hipStream_t str
 int launch_distance_batch(const DevView &v, const float *d_q, const uint32_t *d_ids, uint64_t k,
                           float *d_out, int32_t *d_status, hipStream_t stream);
 
+// The second source form of hx_distance_kernel (hnsw_diversify_device), selected by n_out != 0
+// (zero in launch_distance_batch's launches, which read nothing of this record): ONE candidate list per query,
+// ids[q][j] / dists[q][j], j < pool, counts[q] (nullptr: an entry is present iff its id is not the pad) and stats[q]
+// (nullptr: none are read or written), re-ranked by maximal marginal relevance -- THE SELECTION of
+// include/hnsw_mi355x.h -- into out_ids / out_dists / out_gaps [q][n_out] (out_gaps may be nullptr), the number selected
+// into out_counts[q] (may be nullptr), the stats record into out_stats[q] (with stats), its status HNSW_ERR_ARG when a
+// present id is at or beyond the index length.  The kernel's q, ids, k, out and status_out are not read.
+#define HX_DIVERSE_POOL_MAX 256  // candidates per query: ids, distance bits and running minima in 3 KiB of LDS
+struct DiverseLists {
+    const uint32_t *ids;
+    const float *dists;
+    const uint32_t *counts;
+    const hnsw_query_stats *stats;
+    uint32_t pool, n_out;
+    float lambda;
+    uint32_t nq;
+    uint32_t *out_ids;
+    float *out_dists, *out_gaps;
+    uint32_t *out_counts;
+    hnsw_query_stats *out_stats;
+};
+// the selection of d.nq candidate lists (1 <= n_out <= pool <= HX_DIVERSE_POOL_MAX, lambda in [0, 1]): ONE launch of
+// hx_distance_kernel in its second form, one wave per query
+int launch_diversify(const DevView &v, const DiverseLists &d, hipStream_t stream);
+
 // exhaustive scan: every query against every point; partial top-k per (query, segment):
 // part_ids / part_dists are nq x nseg x k.  The host merges the segments.
 int launch_brute_force(const DevView &v, const float *d_Q, uint64_t nq, uint32_t k, uint32_t nseg,

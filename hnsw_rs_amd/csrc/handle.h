@@ -76,6 +76,8 @@ struct hnsw_index {
     std::atomic<uint64_t> n_grouped_calls{0}, n_grouped_launches{0};
     // radius search: hnsw_search_batch_radius calls answered, the search rungs they launched, and their cuts launched
     std::atomic<uint64_t> n_radius_calls{0}, n_radius_rungs{0}, n_radius_launches{0};
+    // diversified search: hnsw_search_batch_diverse calls answered, and the selections launched (hnsw_diversify_device's too)
+    std::atomic<uint64_t> n_diverse_calls{0}, n_diverse_launches{0};
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")
 };
 

@@ -109,6 +109,8 @@ const Stat kStats[] = {
     HX_STAT("radius_calls", h.n_radius_calls),
     HX_STAT("radius_rungs", h.n_radius_rungs),
     HX_STAT("radius_launches", h.n_radius_launches),
+    HX_STAT("diverse_calls", h.n_diverse_calls),
+    HX_STAT("diverse_launches", h.n_diverse_launches),
     HX_STAT("deleted", h.del.count),
     HX_STAT("deleted_mask_words_uploaded", h.del.words_uploaded),
     HX_STAT("deleted_queries_graph", h.n_del_graph),

@@ -568,6 +568,46 @@ class HNSW:
             nq, n_in, n_out, p(d_radius), p(d_sel), n_sel, p(d_ids_in), p(d_dists_in), p(d_counts_in), p(d_stats_in),
             p(d_ids), p(d_dists), p(d_counts), p(d_flags), p(d_stats), stream or None))
 
+    # ---- diversified search: maximal marginal relevance (include/hnsw_mi355x.h) ------------------------------------
+    def search_batch_diverse(self, Q, n, pool, ef, lam=0.5, mask_set=None, mask_of=None, lo=None, hi=None):
+        """n hits per query that are near the query and not near each other: the MMR selection (diverse.mmr_select,
+        lambda = lam in [0, 1]) out of the `pool` candidates that search_batch (or, with mask_set / lo and hi, the
+        filtered search of that kind) returns with n = pool (hnsw_search_batch_diverse).  mask_of [nq]: rows of the
+        set, -1 or MASK_NONE; None: row 0.  lo / hi: both or neither, scalars broadcast.
+        -> ids [nq, n] (pad UINT32_MAX), dists [nq, n] (pad +inf), gaps [nq, n] (a hit's distance to the nearest hit
+        before it; +inf for the first and the pad), counts [nq], stats [nq, 4] (the candidate call's), all in
+        selection order"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        if (lo is None) != (hi is None):
+            raise ValueError("a label range needs lo and hi, both or neither")
+        nq, width = Q.shape[0], max(int(n), 1)
+        mo = self._mask_of(mask_of, nq)
+        rng = (None, None) if lo is None else self._range(lo, hi, nq)
+        ids = np.full((nq, width), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, width), np.inf, dtype=np.float32)
+        gaps = np.full((nq, width), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        check(self._L.hnsw_search_batch_diverse(
+            self._h, _p(Q, _f32p), nq, n, pool, ef, float(lam), mask_set._s if mask_set is not None else None,
+            None if mo is None else _p(mo, _u32p), None if rng[0] is None else _p(rng[0], _u32p),
+            None if rng[1] is None else _p(rng[1], _u32p), _p(ids, _u32p), _p(dists, _f32p), _p(gaps, _f32p),
+            _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
+        return ids, dists, gaps, counts, stats.view(np.uint32).astype(np.int64)
+
+    def diversify_device(self, nq, pool, n_out, lam, d_ids_in, d_dists_in, d_counts_in, d_stats_in, d_ids, d_dists,
+                         d_gaps=None, d_counts=None, d_stats=None, stream=0):
+        """hnsw_diversify_device over torch device tensors (or raw device pointers): the [nq, pool] candidate lists a
+        *_device search of this index left (d_counts_in / d_stats_in [nq] or None), re-ranked by MMR over this index's
+        stored rows into d_ids / d_dists [nq, n_out] (/ d_gaps / d_counts / d_stats).  ONE launch enqueued on `stream`,
+        no sync of it."""
+        p = self._dptr
+        check(self._L.hnsw_diversify_device(
+            self._h, nq, pool, n_out, float(lam), p(d_ids_in), p(d_dists_in), p(d_counts_in), p(d_stats_in), p(d_ids),
+            p(d_dists), p(d_gaps), p(d_counts), p(d_stats), stream or None))
+
     def search_filtered(self, q, n, ef, lo=0, hi=0xFFFFFFFF, mask_set=None, row=None):
         """ONE query under the label range [lo, hi] and, with a resident MaskSet, its row `row` (None, -1 or MASK_NONE: no
         row): hnsw_search_filtered, whose concurrent callers on an index are gathered into one launch.

@@ -695,6 +695,77 @@ int hnsw_search_batch_radius(hnsw_index *h, const float *Q, uint64_t nq, const f
                              uint32_t *flags /* or NULL */, uint32_t *rungs /* or NULL */,
                              hnsw_query_stats *stats /* or NULL */);
 
+/* ---- diversified search: hits near the query and not near each other (maximal marginal relevance) -----------------
+ * An extension (the reference answers "the n nearest" only): near-duplicate rows, re-posts and boilerplate chunks fill a
+ * top n with one answer n times; a retrieval caller wants MMR (LangChain's max_marginal_relevance_search, Qdrant's and
+ * OpenSearch's MMR re-rank).  Grouped search removes duplicates by label; this removes them by distance, and it is the
+ * one post-processing form that reads stored rows.
+ * THE SELECTION out of one query's candidate list of `pool` entries (id_j, dist_j), j < pool, in the order given (the
+ * selection sorts nothing), with the call's lambda in [0, 1] (f32) and output length n_out:
+ *   - entry j is PRESENT iff j < min(count, pool), or, without counts, iff id_j != UINT32_MAX; absent entries take no
+ *     part, wherever they are;
+ *   - a present id at or beyond the index length gives the query status HNSW_ERR_ARG, count 0 and padded rows, and no row
+ *     of the index is read for it;
+ *   - the PAIR DISTANCE D(s, j) is the index's own distance between the stored rows id_s and id_j, the selected row s as
+ *     the first argument: the bits of hnsw_distance(h, id_s, id_j) (Point::dist2other; under the cosine option the
+ *     stored rows are the unit rows).  The routine is bit-symmetric for both vector kinds, but
+ *     the argument order is part of the contract either way;
+ *   - r_t(j) is the running minimum of D(s, j) over the entries s selected before step t, folded in selection order as
+ *     `r = D < r ? D : r` from +inf (a NaN pair distance leaves it as it is); m_0(j) = 0 and m_t(j) = r_t(j) for t >= 1;
+ *   - score_t(j) = (lambda * dist_j) - ((1.0f - lambda) * m_t(j)): three separately rounded f32 operations, never
+ *     contracted, so numpy float32 restates them;
+ *   - step t = 0, 1, ... < n_out selects the present, not yet selected entry with the smallest score under f32 `<`;
+ *     entries equal under `==` (-0 == +0) go to the lower position j.  An entry whose score is NaN is never selected;
+ *     when nothing is selectable the selection ends.
+ * So lambda = 1 returns the first n_out present entries by (dist, position), and lambda = 0 starts at the first present
+ * position and then walks farthest-point-first.  Per query, in selection order: ids [n_out] (pad UINT32_MAX), dists
+ * [n_out] (the distance bits of the input, pad +inf), gaps [n_out] (r_t of the entry at the step t it was selected:
+ * its distance to the nearest hit returned before it; gaps[0] = +inf; pad +inf), counts = entries selected.  A query's
+ * stats record passes through unchanged (but for the status above); a query whose incoming status is not HNSW_OK gets
+ * count 0 and padded rows.  Limits: 1 <= n_out <= pool <= HNSW_DIVERSE_POOL_MAX.
+ *
+ * hnsw_diversify_device is THE SELECTION alone over lists in HBM: every d_* pointer is device memory, the inputs
+ * d_ids_in / d_dists_in [nq][pool], d_counts_in [nq] or NULL, d_stats_in [nq] or NULL are what any *_device search of
+ * the same handle leaves after its _finish (ids local to the handle, so a replica handle serves as well: the rows read
+ * are the snapshot's).  ONE launch (the distance seam's kernel in its selection form, one wave per query) is enqueued on
+ * `stream` and the call returns without synchronising it; nothing is allocated or copied on it.  The status of an
+ * out-of-range id is written to d_stats only (the call cannot see it).  Outputs must not overlap inputs.  d_gaps and
+ * d_counts may be NULL; d_stats is required iff d_stats_in is given.  HNSW_ERR_ARG, decided before the device is
+ * touched: h NULL; the limits violated; lambda outside [0, 1] or NaN; nq > 2^31 - 1; d_ids_in, d_dists_in, d_ids or
+ * d_dists NULL; exactly one of d_stats_in / d_stats given.  nq == 0 is HNSW_OK on any handle, whatever else is passed,
+ * and launches nothing; an empty index is HNSW_ERR_EMPTY.
+ *
+ * hnsw_search_batch_diverse answers host-pointer queries by n diverse hits each.  By definition the result is THE
+ * SELECTION, with n_out = n, of the candidate lists that an existing call returns with n = pool, on the same handle
+ * with the same options: hnsw_search_batch (set NULL, lo and hi NULL), hnsw_search_batch_filtered_range (lo and hi),
+ * _filtered_set (set; mask_of NULL: row 0) or _filtered_set_range (both) -- the table of hnsw_search_batch_grouped, and
+ * everything of the candidate call is inherited in the same way: ef' = max(ef, pool, 1), deleted ids taken out, the
+ * cosine option, the planner and "filter_exact_max", its stats, its per-query errors (the first is returned, every
+ * other row is filled in) and its limits -- pool <= 64 and, on the graph path, ef' <= 256 whenever the candidate call is
+ * a filtered one or the handle has deleted ids.  Unfiltered with nothing deleted the call stays on the device: the
+ * queries go up once, hnsw_search_batch_device and its _finish, one selection launch, one copy of the result block
+ * back.  Under a filter or deletions the candidates come from the candidate call's HOST form and their lists go up
+ * before the selection: only the host form lets the planner choose the exact path, and the call is defined by it.
+ * dists, gaps, counts and stats may be NULL.  HNSW_ERR_ARG, decided before the device is touched: the limits violated;
+ * lambda outside [0, 1] or NaN; mask_of without a set; exactly one of lo / hi; a set of another handle; Q or ids NULL;
+ * nq > 2^31 - 1.  nq == 0 is HNSW_OK.  hnsw_get_stat: "diverse_calls" (hnsw_search_batch_diverse calls answered),
+ * "diverse_launches" (selections launched, hnsw_diversify_device's included).
+ * Not provided: compile-time-dimension distance routines inside the selection (it runs the any-dimension routine);
+ * a lambda per query; MMR over shards (merged lists carry global ids); one-query gathered calls; the Rust shim's
+ * binding. */
+#define HNSW_DIVERSE_POOL_MAX 256
+int hnsw_diversify_device(hnsw_index *h, uint64_t nq, uint32_t pool, uint32_t n_out, float lambda,
+                          const uint32_t *d_ids_in /* nq x pool */, const float *d_dists_in,
+                          const uint32_t *d_counts_in /* or NULL */, const hnsw_query_stats *d_stats_in /* or NULL */,
+                          uint32_t *d_ids, float *d_dists /* nq x n_out */, float *d_gaps /* or NULL */,
+                          uint32_t *d_counts /* or NULL */, hnsw_query_stats *d_stats /* required iff d_stats_in */,
+                          void *stream);
+int hnsw_search_batch_diverse(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t pool, uint32_t ef,
+                              float lambda, hnsw_mask_set *set /* or NULL */, const uint32_t *mask_of /* nq, or NULL */,
+                              const uint32_t *lo, const uint32_t *hi /* nq each, or both NULL: no range */,
+                              uint32_t *ids /* nq x n */, float *dists /* or NULL */, float *gaps /* or NULL */,
+                              uint32_t *counts /* or NULL */, hnsw_query_stats *stats /* or NULL */);
+
 /* Test seams that mirror the reference's own units:
  * VecBase::dist2many (vectors/src/lib.rs:17-22): the query (quantised like ann_by_vector does,
  * template.rs:313) against stored ids, on the device, exact accumulation order. */
@@ -874,7 +945,9 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * (hnsw_search_batch_shards calls whose shards were all searched), "shard_merges" (the merges they launched); grouped
  * search: "grouped_calls" (hnsw_search_batch_grouped calls answered), "grouped_launches" (collapses launched,
  * hnsw_group_by_label_device's included); radius search: "radius_calls" (hnsw_search_batch_radius calls answered),
- * "radius_rungs" (the search rungs they launched), "radius_launches" (the cuts they launched); deletion:
+ * "radius_rungs" (the search rungs they launched), "radius_launches" (the cuts they launched); diversified
+ * search: "diverse_calls" (hnsw_search_batch_diverse calls answered), "diverse_launches" (selections launched,
+ * hnsw_diversify_device's included); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
