@@ -15,6 +15,8 @@ VEC_F32 = 1
 UINT32_MAX = 0xFFFFFFFF
 GROUP_POOL_MAX = 256  # HNSW_GROUP_POOL_MAX: candidates per query of a grouped search
 DIVERSE_POOL_MAX = 256  # HNSW_DIVERSE_POOL_MAX: candidates per query of a diversified search
+FROM_ROWS_MAX_TERMS = 64  # HNSW_FROM_ROWS_MAX_TERMS: slots per query of a search from stored rows
+DROP_MAX_N = 1024  # HNSW_DROP_MAX_N: entries per list of the drop
 RADIUS_MAX_N = 1024  # HNSW_RADIUS_MAX_N: entries per list of a radius search
 RADIUS_MORE = 1  # HNSW_RADIUS_MORE: the list was full and showed nothing outside the radius
 RANGES_MAX = 16  # HNSW_RANGES_MAX: members of a query's range list
@@ -142,6 +144,13 @@ SYMBOLS = {
                                         vp]),
     "hnsw_search_batch_diverse": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, vp, u32p,
                                             u32p, u32p, u32p, f32p, f32p, u32p, C.POINTER(QueryStats)]),
+    "hnsw_compose_rows_device": (C.c_int, [vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp]),
+    "hnsw_drop_ids_device": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                       vp, vp, vp]),
+    "hnsw_search_batch_from_rows": (C.c_int, [vp, u32p, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                              u32p, f32p, u32p, C.POINTER(QueryStats)]),
+    "hnsw_search_batch_by_id": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, u32p, f32p, u32p,
+                                          C.POINTER(QueryStats)]),
     "hnsw_distance_batch": (C.c_int, [vp, f32p, u32p, C.c_uint64, f32p]),
     "hnsw_search_layer": (C.c_int, [vp, C.c_uint32, f32p, u32p, C.c_uint32, C.c_uint32, u32p, f32p, u32p,
                                     C.POINTER(QueryStats)]),

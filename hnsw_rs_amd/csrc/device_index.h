@@ -309,10 +309,25 @@ struct DiverseLists {
     float *out_dists, *out_gaps;
     uint32_t *out_counts;
     hnsw_query_stats *out_stats;
+    // The third source form (hnsw_compose_rows_device), selected by width != 0 (zero in every
+    // other launch, whose kernels read nothing below): query q's row rows_out[q][dim] is THE COMPOSED QUERY of
+    // include/hnsw_mi355x.h over the stored rows ids[q][s], s < width (pad HX_EMPTY_SLOT), with weights[q][s] (nullptr:
+    // every weight 1.0f); row_status[q] (may be nullptr) is HNSW_OK, or HNSW_ERR_ARG for a query without a present slot
+    // or with a present id at or beyond the index length, whose row is all zeros.  Of the fields above the form reads
+    // ids and nq alone.
+    uint32_t width, _pad;
+    const float *weights;
+    float *rows_out;
+    int32_t *row_status;
 };
+#define HX_FROM_ROWS_MAX_TERMS 64  // slots per composed query: one lane each
 // the selection of d.nq candidate lists (1 <= n_out <= pool <= HX_DIVERSE_POOL_MAX, lambda in [0, 1]): ONE launch of
 // hx_distance_kernel in its second form, one wave per query
 int launch_diversify(const DevView &v, const DiverseLists &d, hipStream_t stream);
+// nq composed queries of `width` slots each (1 <= width <= HX_FROM_ROWS_MAX_TERMS) into d_rows [nq][v.dim]: ONE launch of
+// hx_distance_kernel in its third form, one wave per query.  d_weights and d_status may be nullptr.
+int launch_compose_rows(const DevView &v, uint32_t nq, uint32_t width, const uint32_t *d_src_ids, const float *d_weights,
+                        float *d_rows, int32_t *d_status, hipStream_t stream);
 
 // exhaustive scan: every query against every point; partial top-k per (query, segment):
 // part_ids / part_dists are nq x nseg x k.  The host merges the segments.

@@ -78,6 +78,9 @@ struct hnsw_index {
     std::atomic<uint64_t> n_radius_calls{0}, n_radius_rungs{0}, n_radius_launches{0};
     // diversified search: hnsw_search_batch_diverse calls answered, and the selections launched (hnsw_diversify_device's too)
     std::atomic<uint64_t> n_diverse_calls{0}, n_diverse_launches{0};
+    // search from stored rows: hnsw_search_batch_from_rows / _by_id calls answered, the compose launches (those of
+    // hnsw_compose_rows_device too) and the drop launches of those calls (hnsw_drop_ids_device takes no handle)
+    std::atomic<uint64_t> n_from_rows_calls{0}, n_from_rows_compose{0}, n_from_rows_drop{0};
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")
 };
 

@@ -111,6 +111,9 @@ const Stat kStats[] = {
     HX_STAT("radius_launches", h.n_radius_launches),
     HX_STAT("diverse_calls", h.n_diverse_calls),
     HX_STAT("diverse_launches", h.n_diverse_launches),
+    HX_STAT("from_rows_calls", h.n_from_rows_calls),
+    HX_STAT("from_rows_compose_launches", h.n_from_rows_compose),
+    HX_STAT("from_rows_drop_launches", h.n_from_rows_drop),
     HX_STAT("deleted", h.del.count),
     HX_STAT("deleted_mask_words_uploaded", h.del.words_uploaded),
     HX_STAT("deleted_queries_graph", h.n_del_graph),

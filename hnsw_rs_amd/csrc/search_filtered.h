@@ -101,6 +101,15 @@ struct RangeList {
 // stats record to out_stats unchanged, HX_RADIUS_MORE to flags[q] iff the status is HNSW_OK, all pool entries are
 // present and all of them were kept.  Block b serves query FilterArgs::qsel[b] when that is set (an entry at or beyond
 // nq is not served); the rows of other queries are not touched.  Nothing is sorted and no LDS is used.
+//
+// The fifth source form (hnsw_drop_ids_device), selected by drop_out != 0 next to ids (zero in every
+// other launch): ONE candidate list per query, ids[q][j] / dists[q][j], j < pool, counts[q] and stats[q] as above, and
+// ex[q][s], s < ex_width -- THE DROP of include/hnsw_mi355x.h: the present entries whose id equals no present exclusion
+// id, in their input order, the first drop_out of them to FilterArgs::out_ids / out_dists as [q][drop_out], padded
+// behind; the number written to out_counts, the present entries removed over all of pool to dropped[q], the stats record
+// to out_stats unchanged unless src_status[q] is not HNSW_OK: then the query has no present entry and the record carries
+// that status.  FilterArgs::qsel is honoured as in the cut form.  Nothing is sorted and no LDS is used.
+#define HX_DROP_MAX_WIDTH 64      // exclusion ids per query: one lane each
 #define HX_MERGE_MAX_SHARDS 64
 #define HX_GROUP_POOL_MAX 256     // candidates per query: four per lane
 #define HX_GROUP_SLOTS_MAX 1024   // n_groups x per_group: the slot table in LDS
@@ -120,6 +129,12 @@ struct MergeLists {
     uint32_t *group_labels, *group_sizes;
     const float *radius;      // the cut form: nq radii (device)
     uint32_t *flags;          // the cut form: nq flag words, or nullptr
+    // the drop form (drop_out != 0; zero in every other launch, which reads nothing below)
+    const uint32_t *ex;         // nq x ex_width exclusion ids (device), pad UINT32_MAX
+    const int32_t *src_status;  // nq compose statuses (device), or nullptr
+    uint32_t *dropped;          // nq words: present entries removed by the exclusion, or nullptr
+    uint32_t drop_out;          // != 0: the drop form, and the stride of its output rows (drop_out <= pool)
+    uint32_t ex_width;          // exclusion slots per query, 1 .. HX_DROP_MAX_WIDTH: one lane each
 };
 
 // The grouped form of the exact path: the exact-path groups of a call in ONE compaction, ONE scan
@@ -201,5 +216,11 @@ int launch_group_by_label(const MergeLists &m, uint32_t *out_ids, float *out_dis
 // may be nullptr; out_stats goes with m.stats.
 int launch_radius_cut(const MergeLists &m, const uint32_t *sel, uint32_t n_sel, uint32_t *out_ids, float *out_dists,
                       uint32_t *out_counts, hnsw_query_stats *out_stats, hipStream_t stream);
+// the drop of exclusion ids from candidate lists of m.pool entries into rows of m.drop_out (the fifth form; m.ids, m.dists,
+// m.ex, m.ex_width, m.pool and m.drop_out set, 1 <= drop_out <= pool <= HX_RADIUS_MAX_N, 1 <= ex_width <=
+// HX_DROP_MAX_WIDTH): ONE launch of hx_filt_merge_kernel, one wave per served query, selected as launch_radius_cut's.
+// out_counts, m.src_status and m.dropped may be nullptr; out_stats goes with m.stats.
+int launch_drop_ids(const MergeLists &m, const uint32_t *sel, uint32_t n_sel, uint32_t *out_ids, float *out_dists,
+                    uint32_t *out_counts, hnsw_query_stats *out_stats, hipStream_t stream);
 
 }  // namespace hx

@@ -895,10 +895,73 @@ __device__ __forceinline__ void cut_at_radius(const FilterArgs &a, const MergeLi
     }
 }
 
+// The merge kernel's drop form (MergeLists with drop_out != 0, search_filtered.h): the candidate
+// list of m.pool entries of query a.qsel[blockIdx.x] (or blockIdx.x), walked as the cut form walks it, without the
+// entries whose id one of the query's exclusion ids names.  The exclusion ids sit one per lane; a step compares its 64
+// entries with each present one, broadcast by readlane (the walk of the ballot's set bits is the wave's).  A kept
+// entry's slot is the number kept before it; the wave stops storing at drop_out but walks on, so that `dropped` covers
+// all of pool.  Then the lanes stream the pad: every output word is written once.  No LDS, no list registers.
+__device__ __forceinline__ void drop_excluded(const FilterArgs &a, const MergeLists &m, int lane) {
+    const uint32_t q = a.qsel ? a.qsel[blockIdx.x] : blockIdx.x;
+    const uint32_t n_in = m.pool, n_out = m.drop_out, width = m.ex_width;
+    if (q >= m.nq || n_out > n_in || n_in > HX_RADIUS_MAX_N || width > HX_DROP_MAX_WIDTH) return;  // (the launcher's limits)
+    const uint32_t *dist_bits = reinterpret_cast<const uint32_t *>(m.dists);
+    hnsw_query_stats st;
+    st.n_dist = st.n_exp = st.sum_deg = 0;
+    st.status = HNSW_OK;
+    if (m.stats) st = m.stats[q];
+    bool ok = st.status == HNSW_OK;  // a failed query has no present entry: count 0, a padded row, nothing dropped
+    if (m.src_status) {
+        const int32_t src = m.src_status[q];
+        if (src != HNSW_OK) {
+            ok = false;
+            st.status = src;
+        }
+    }
+    const uint32_t cnt = m.counts ? min(m.counts[q], n_in) : n_in;
+    const uint32_t ex = (uint32_t)lane < width ? m.ex[(size_t)q * width + lane] : HX_EMPTY_SLOT;
+    const u64 exm = __ballot(ex != HX_EMPTY_SLOT);
+    const size_t in0 = (size_t)q * n_in, out0 = (size_t)q * n_out;
+    uint32_t w = 0, gone = 0;  // wave-uniform
+    uint32_t nx_id = (uint32_t)lane < n_in ? m.ids[in0 + lane] : HX_EMPTY_SLOT;
+    uint32_t nx_bits = (uint32_t)lane < n_in ? dist_bits[in0 + lane] : 0u;
+    for (uint32_t base = 0; base < n_in; base += 64) {
+        const uint32_t j = base + lane, id = nx_id, bits = nx_bits;
+        if (j + 64 < n_in) {
+            nx_id = m.ids[in0 + j + 64];
+            nx_bits = dist_bits[in0 + j + 64];
+        }
+        const bool present = ok && j < n_in && (m.counts ? j < cnt : id != HX_EMPTY_SLOT);
+        bool hit = false;
+        for (u64 rest = exm; rest; rest &= rest - 1)
+            hit |= id == (uint32_t)__builtin_amdgcn_readlane((int)ex, __builtin_ctzll(rest));
+        const bool kept = present && !hit;
+        const u64 km = __ballot(kept);
+        gone += (uint32_t)__popcll(__ballot(present && hit));
+        const uint32_t slot = w + (uint32_t)__popcll(km & ((1ull << lane) - 1));
+        if (kept && slot < n_out) {
+            a.out_ids[out0 + slot] = id;
+            a.out_dists[out0 + slot] = __builtin_bit_cast(float, bits);
+        }
+        w += (uint32_t)__popcll(km);
+    }
+    w = min(w, n_out);
+    for (uint32_t s = w + lane; s < n_out; s += 64) {
+        a.out_ids[out0 + s] = HX_EMPTY_SLOT;
+        a.out_dists[out0 + s] = __builtin_inff();
+    }
+    if (lane == 0) {
+        if (a.out_counts) a.out_counts[q] = w;
+        if (m.dropped) m.dropped[q] = gone;
+        if (a.out_stats) a.out_stats[q] = st;
+    }
+}
+
 // Merge: one wave per query folds the nseg partial lists into its top n and writes the results.  With m.ids set the
 // lists are those of m.n_shards shards instead (merge_shard_lists; A, nseg, part and part_status are not read), or, with
 // m.per_group set as well, the query's one candidate list, collapsed by label (collapse_by_label), or, with m.cut_out
-// set instead, that list cut at the query's radius (cut_at_radius).  With
+// set instead, that list cut at the query's radius (cut_at_radius), or, with m.drop_out set instead, that list without
+// the query's exclusion ids (drop_excluded).  With
 // qtab set (the grouped form) A, nseg and the first row of the query's partial lists are its record's.
 __global__ void __launch_bounds__(64) hx_filt_merge_kernel(const FilterArgs a, uint32_t A, uint32_t nseg,
                                                            const u64 *part, const int32_t *part_status,
@@ -914,6 +977,8 @@ __global__ void __launch_bounds__(64) hx_filt_merge_kernel(const FilterArgs a, u
     if (m.ids) {
         if (m.cut_out)
             cut_at_radius(a, m, lane);
+        else if (m.drop_out)
+            drop_excluded(a, m, lane);
         else
             merge_shard_lists(a, m, perm, lane);
         return;
@@ -1132,6 +1197,31 @@ int launch_radius_cut(const MergeLists &lists, const uint32_t *sel, uint32_t n_s
     a.out_counts = out_counts;
     a.out_stats = out_stats;
     return launch_checked({"radius cut kernel launch"}, hx_filt_merge_kernel, dim3(nblocks), dim3(64), 0, stream, a, 0u, 0u,
+                          static_cast<const u64 *>(nullptr), static_cast<const int32_t *>(nullptr), m,
+                          static_cast<const ExactQuery *>(nullptr));
+}
+
+int launch_drop_ids(const MergeLists &lists, const uint32_t *sel, uint32_t n_sel, uint32_t *out_ids, float *out_dists,
+                    uint32_t *out_counts, hnsw_query_stats *out_stats, hipStream_t stream) {
+    MergeLists m = lists;
+    const uint32_t nblocks = sel ? n_sel : m.nq;
+    if (nblocks == 0) return HNSW_OK;
+    if (m.drop_out == 0 || m.drop_out > m.pool || m.pool > HX_RADIUS_MAX_N || m.ex_width == 0 || m.ex_width > HX_DROP_MAX_WIDTH ||
+        m.nq > 0x7FFFFFFFu || nblocks > m.nq || !m.ids || !m.dists || !m.ex || !out_ids || !out_dists ||
+        (m.stats != nullptr) != (out_stats != nullptr)) {
+        set_error("drop ids: needs 1 <= n_out <= n_in <= %d, 1 <= width <= %d, at most 2^31 - 1 queries, a selection no longer "
+                  "than that, the lists, the exclusion ids and the outputs", HX_RADIUS_MAX_N, HX_DROP_MAX_WIDTH);
+        return HNSW_ERR_ARG;
+    }
+    m.per_group = 0;  // (the collapse form's selector)
+    m.cut_out = 0;    // (the cut form's)
+    FilterArgs a{};   // the form reads the selection and the outputs
+    a.qsel = sel;
+    a.out_ids = out_ids;
+    a.out_dists = out_dists;
+    a.out_counts = out_counts;
+    a.out_stats = out_stats;
+    return launch_checked({"drop ids kernel launch"}, hx_filt_merge_kernel, dim3(nblocks), dim3(64), 0, stream, a, 0u, 0u,
                           static_cast<const u64 *>(nullptr), static_cast<const int32_t *>(nullptr), m,
                           static_cast<const ExactQuery *>(nullptr));
 }

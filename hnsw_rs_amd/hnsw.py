@@ -608,6 +608,79 @@ class HNSW:
             self._h, nq, pool, n_out, float(lam), p(d_ids_in), p(d_dists_in), p(d_counts_in), p(d_stats_in), p(d_ids),
             p(d_dists), p(d_gaps), p(d_counts), p(d_stats), stream or None))
 
+    # ---- search from stored rows: queries by id and by weighted ids (include/hnsw_mi355x.h) ------------------------
+    def search_batch_from_rows(self, src_ids, weights, n, ef, exclude=True):
+        """The n nearest of queries composed out of stored rows (from_rows.compose_rows): src_ids [nq, width] (a slot
+        holding UINT32_MAX is absent), weights [nq, width] float32 or None (every weight 1.0).  exclude: the sources
+        are taken out of their own lists (from_rows.drop_ids over the search with n + width); False: they stay, and the
+        call is search_batch of the composed rows (hnsw_search_batch_from_rows).
+        -> ids [nq, n] (pad UINT32_MAX), dists [nq, n] (pad +inf), counts [nq], stats [nq, 4]"""
+        src = np.ascontiguousarray(src_ids, dtype=np.uint32)
+        if src.ndim != 2:
+            raise ValueError("src_ids is [nq, width]")
+        nq, width = src.shape
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != src.shape:
+                raise ValueError("weights has the shape of src_ids")
+        ids = np.full((nq, max(int(n), 1)), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, max(int(n), 1)), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        check(self._L.hnsw_search_batch_from_rows(
+            self._h, _p(src, _u32p), None if w is None else _p(w, _f32p), nq, width, n, ef, 1 if exclude else 0,
+            _p(ids, _u32p), _p(dists, _f32p), _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
+        return ids, dists, counts, stats.view(np.uint32).astype(np.int64)
+
+    def search_batch_by_id(self, src_ids, n, ef, exclude_self=True):
+        """The n nearest of the stored rows src_ids [nq], each without itself unless exclude_self is False
+        (hnsw_search_batch_by_id: search_batch_from_rows with one slot and no weights).
+        -> ids [nq, n] (pad UINT32_MAX), dists [nq, n] (pad +inf), counts [nq], stats [nq, 4]"""
+        src = np.ascontiguousarray(src_ids, dtype=np.uint32).reshape(-1)
+        nq = src.shape[0]
+        ids = np.full((nq, max(int(n), 1)), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, max(int(n), 1)), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        check(self._L.hnsw_search_batch_by_id(
+            self._h, _p(src, _u32p), nq, n, ef, 1 if exclude_self else 0, _p(ids, _u32p), _p(dists, _f32p),
+            _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
+        return ids, dists, counts, stats.view(np.uint32).astype(np.int64)
+
+    def knn_graph(self, n, ef, chunk=65536, ids=None, exclude_self=True):
+        """The k-NN graph of the index: search_batch_by_id over all ids (or the given ones), `chunk` sources a call.
+        -> ids [N, n] (pad UINT32_MAX), dists [N, n] (pad +inf), counts [N]"""
+        src = np.arange(self.len(), dtype=np.uint32) if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        chunk = max(int(chunk), 1)
+        o_ids = np.full((src.shape[0], max(int(n), 1)), _lib.UINT32_MAX, dtype=np.uint32)
+        o_dists = np.full((src.shape[0], max(int(n), 1)), np.inf, dtype=np.float32)
+        o_counts = np.zeros(src.shape[0], dtype=np.uint32)
+        for a in range(0, src.shape[0], chunk):
+            b = min(a + chunk, src.shape[0])
+            o_ids[a:b], o_dists[a:b], o_counts[a:b], _ = self.search_batch_by_id(src[a:b], n, ef, exclude_self)
+        return o_ids, o_dists, o_counts
+
+    def compose_rows_device(self, nq, width, d_src_ids, d_weights, d_Q, d_status=None, stream=0):
+        """hnsw_compose_rows_device over torch device tensors (or raw device pointers): d_src_ids uint32 [nq, width],
+        d_weights float32 [nq, width] or None, composed out of this index's stored rows into d_Q float32 [nq, dim]
+        (/ d_status int32 [nq]).  ONE launch enqueued on `stream`, no sync of it."""
+        p = self._dptr
+        check(self._L.hnsw_compose_rows_device(self._h, nq, width, p(d_src_ids), p(d_weights), p(d_Q), p(d_status),
+                                               stream or None))
+
+    @staticmethod
+    def drop_ids_device(nq, n_in, n_out, width, d_ex, d_src_status, d_ids_in, d_dists_in, d_counts_in, d_stats_in, d_ids,
+                        d_dists, d_counts=None, d_dropped=None, d_stats=None, stream=0):
+        """hnsw_drop_ids_device over torch device tensors (or raw device pointers): the [nq, n_in] candidate lists a
+        *_device search left (d_counts_in / d_stats_in [nq] or None) without the ids of d_ex uint32 [nq, width]
+        (d_src_status int32 [nq] or None: the compose statuses), into d_ids / d_dists [nq, n_out] (/ d_counts /
+        d_dropped / d_stats).  ONE launch enqueued on `stream` of the current device, no sync of it; needs no index."""
+        p = HNSW._dptr
+        check(_lib.lib().hnsw_drop_ids_device(
+            nq, n_in, n_out, width, p(d_ex), p(d_src_status), p(d_ids_in), p(d_dists_in), p(d_counts_in), p(d_stats_in),
+            p(d_ids), p(d_dists), p(d_counts), p(d_dropped), p(d_stats), stream or None))
+
     def search_filtered(self, q, n, ef, lo=0, hi=0xFFFFFFFF, mask_set=None, row=None):
         """ONE query under the label range [lo, hi] and, with a resident MaskSet, its row `row` (None, -1 or MASK_NONE: no
         row): hnsw_search_filtered, whose concurrent callers on an index are gathered into one launch.

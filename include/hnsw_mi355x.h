@@ -766,6 +766,91 @@ int hnsw_search_batch_diverse(hnsw_index *h, const float *Q, uint64_t nq, uint32
                               uint32_t *ids /* nq x n */, float *dists /* or NULL */, float *gaps /* or NULL */,
                               uint32_t *counts /* or NULL */, hnsw_query_stats *stats /* or NULL */);
 
+/* ---- search from stored rows: queries by id and by weighted ids -------------------------------------------------------
+ * An extension (the reference searches by vector only): "nearest to this item I already stored" -- more like this,
+ * recommendation from liked and disliked items, the centroid of a few stored rows, the k-NN graph of the whole index,
+ * a near-duplicate sweep.  The rows are in HBM next to the graph, so the query rows are made there and the sources are
+ * taken back out of the result lists there; a replica handle, which has no host rows, serves as well.
+ * A call has nq queries of `width` slots each, 1 <= width <= HNSW_FROM_ROWS_MAX_TERMS: src_ids [nq][width], a slot
+ * holding UINT32_MAX is absent (pads may sit anywhere), and weights [nq][width] f32, NULL: every weight is 1.0f.
+ * THE ROW of an id is exactly what hnsw_get_vector returns: the stored bits (f32 kind), ((float)code * delta) + min, two
+ * separately rounded operations (8-bit kind); under the metric_cosine option the stored unit row.
+ * THE COMPOSED QUERY: element e of query q is folded over the present slots in slot order, acc = w * x for the first
+ * present slot and acc = acc + (w * x) for every later one: plain f32 operations, never fused, so numpy float32
+ * restates them.  Starting from the first product keeps a -0 element -0; with width = 1 and no weights the row is bit
+ * for bit hnsw_get_vector's.  A NaN or infinite weight is no argument error: it makes a NaN query, and that query gets
+ * the search's own HNSW_ERR_NAN_INPUT.  The bit pattern of a NaN element is not part of the contract.
+ * THE COMPOSE STATUS (int32 per query) is HNSW_ERR_ARG when the query has no present slot or a present id at or beyond
+ * the index length, else HNSW_OK.  For a failed query no stored row is read (the check precedes the first read) and its
+ * output row is all zeros.  Every output word is written exactly once.
+ * THE DROP out of one query's candidate list (id_j, dist_j), j < n_in, with an exclusion list ex [width] (UINT32_MAX:
+ * absent) and output length n_out:
+ *   - entry j is PRESENT iff j < min(count, n_in), or, without counts, iff id_j != UINT32_MAX; a query whose incoming
+ *     status is not HNSW_OK has no present entry; nor has a query whose optional compose status (src_status) is not
+ *     HNSW_OK, and its stats record then carries that status (it takes precedence over the incoming one);
+ *   - the output is the present entries whose id equals no present exclusion id, in input order, cut to the first n_out,
+ *     with the input's distance bits; ids are padded with UINT32_MAX and dists with +inf; counts = the number written;
+ *   - dropped (optional) = the present entries removed by the exclusion over all n_in; an entry listed twice counts
+ *     twice.  An absent exclusion slot never matches an absent entry.  Nothing is sorted;
+ *   - the stats record passes through otherwise unchanged.
+ * Limits: 1 <= n_out <= n_in <= HNSW_DROP_MAX_N (the register-resident list, as HNSW_RADIUS_MAX_N).
+ *
+ * hnsw_compose_rows_device writes THE COMPOSED QUERY of nq queries to d_Q [nq][dim] and THE COMPOSE STATUS to d_status
+ * [nq] (or NULL); every d_* pointer is device memory.  It reads the snapshot only, so a replica handle serves.  After
+ * the snapshot is brought up to date ONE launch (the distance seam's kernel in its compose form, one wave per query) is
+ * enqueued on `stream`; nothing is allocated, copied or synchronised on it.  HNSW_ERR_ARG, decided before the device is
+ * touched: h NULL; width outside its limits; nq > 2^31 - 1; d_src_ids or d_Q NULL.  nq == 0 is HNSW_OK on any handle and
+ * launches nothing; an empty index is HNSW_ERR_EMPTY.
+ * hnsw_drop_ids_device is THE DROP alone over lists in HBM (no handle, as hnsw_radius_cut_device): the inputs are what
+ * any *_device search leaves after its _finish, d_ex [nq][width] the exclusion ids, d_src_status [nq] or NULL.  ONE
+ * launch (the exact path's merge kernel in its drop form, one wave per query) is enqueued on `stream`; nothing is
+ * allocated, copied or synchronised.  Outputs must not overlap inputs.  d_counts and d_dropped may be NULL; d_stats is
+ * required iff d_stats_in is given.  HNSW_ERR_ARG, decided before the device is touched: the limits violated; width
+ * outside its limits; nq > 2^31 - 1; d_ex, d_ids_in, d_dists_in, d_ids or d_dists NULL; exactly one of d_stats_in /
+ * d_stats given.  nq == 0 is HNSW_OK and launches nothing.
+ * With these two and the *_device searches (the filtered ones included) a caller chains compose, search and drop
+ * without leaving HBM; inside the capture conditions of hnsw_search_batch_device the three launches are one chain of a
+ * captured graph.
+ *
+ * hnsw_search_batch_from_rows: with exclude != 0 the result is THE DROP, with the sources as exclusion list and n_out =
+ * n, of what hnsw_search_batch returns for the composed queries with n' = n + width, on the same handle with the same
+ * options; with exclude == 0 it is that call with n' = n and no drop is launched.  Everything of the candidate call is
+ * inherited: the cosine option applied to the composed query, the counters, count < n when ef is small, deletions,
+ * per-query errors (the first is returned, every other row is filled in).  The walk uses the QUERY-side arithmetic, as
+ * any query does: an 8-bit row is re-quantised as a query, so distances are not promised to equal hnsw_distance(src,
+ * hit) for that kind.  A deleted source is a legal source: its row is still stored, and no search returns it.  Limits:
+ * n >= 1 and n + width <= HNSW_DROP_MAX_N.  All arrays are the host's, so a present source id at or beyond the index
+ * length, or a query without a present slot, fails the WHOLE call with HNSW_ERR_ARG (the message names the query) before
+ * the device is touched.  With nothing deleted the call stays on the device: ids and weights go up once, one compose
+ * launch, hnsw_search_batch_device and its _finish on the composed rows, one drop launch, one copy of the result block
+ * back.  While ids are deleted the candidates are the HOST form's (the composed rows are copied back, hnsw_search_batch
+ * runs on them, its lists go up before the drop) and n + width <= 64 is required.  dists, counts and stats may be NULL.
+ * hnsw_search_batch_by_id is the same call with width = 1 and no weights.  nq == 0 is HNSW_OK; an empty index is
+ * HNSW_ERR_EMPTY.  hnsw_get_stat: "from_rows_calls" (calls answered), "from_rows_compose_launches"
+ * (hnsw_compose_rows_device's included), "from_rows_drop_launches" (those of the two search calls; hnsw_drop_ids_device
+ * takes no handle to count on).
+ * Not provided: a label range or mask row in the host entry point (the primitives compose with the filtered *_device
+ * entries); stored-against-stored arithmetic in the walk; one-query gathered calls; the Rust shim's binding. */
+#define HNSW_FROM_ROWS_MAX_TERMS 64
+#define HNSW_DROP_MAX_N 1024
+int hnsw_compose_rows_device(hnsw_index *h, uint64_t nq, uint32_t width, const uint32_t *d_src_ids /* nq x width */,
+                             const float *d_weights /* nq x width, or NULL */, float *d_Q /* nq x dim */,
+                             int32_t *d_status /* nq, or NULL */, void *stream);
+int hnsw_drop_ids_device(uint64_t nq, uint32_t n_in, uint32_t n_out, uint32_t width,
+                         const uint32_t *d_ex /* nq x width */, const int32_t *d_src_status /* nq, or NULL */,
+                         const uint32_t *d_ids_in, const float *d_dists_in /* nq x n_in */,
+                         const uint32_t *d_counts_in /* or NULL */, const hnsw_query_stats *d_stats_in /* or NULL */,
+                         uint32_t *d_ids, float *d_dists /* nq x n_out */, uint32_t *d_counts /* or NULL */,
+                         uint32_t *d_dropped /* or NULL */, hnsw_query_stats *d_stats /* required iff d_stats_in */,
+                         void *stream);
+int hnsw_search_batch_from_rows(hnsw_index *h, const uint32_t *src_ids /* nq x width */,
+                                const float *weights /* nq x width, or NULL */, uint64_t nq, uint32_t width, uint32_t n,
+                                uint32_t ef, int exclude, uint32_t *ids /* nq x n */, float *dists /* or NULL */,
+                                uint32_t *counts /* or NULL */, hnsw_query_stats *stats /* or NULL */);
+int hnsw_search_batch_by_id(hnsw_index *h, const uint32_t *src_ids /* nq */, uint64_t nq, uint32_t n, uint32_t ef,
+                            int exclude_self, uint32_t *ids /* nq x n */, float *dists /* or NULL */,
+                            uint32_t *counts /* or NULL */, hnsw_query_stats *stats /* or NULL */);
+
 /* Test seams that mirror the reference's own units:
  * VecBase::dist2many (vectors/src/lib.rs:17-22): the query (quantised like ann_by_vector does,
  * template.rs:313) against stored ids, on the device, exact accumulation order. */
@@ -947,7 +1032,9 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * hnsw_group_by_label_device's included); radius search: "radius_calls" (hnsw_search_batch_radius calls answered),
  * "radius_rungs" (the search rungs they launched), "radius_launches" (the cuts they launched); diversified
  * search: "diverse_calls" (hnsw_search_batch_diverse calls answered), "diverse_launches" (selections launched,
- * hnsw_diversify_device's included); deletion:
+ * hnsw_diversify_device's included); search from stored rows: "from_rows_calls" (hnsw_search_batch_from_rows and
+ * _by_id calls answered), "from_rows_compose_launches" (hnsw_compose_rows_device's included), "from_rows_drop_launches"
+ * (the drops those calls launched); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
