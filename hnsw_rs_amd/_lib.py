@@ -17,6 +17,10 @@ GROUP_POOL_MAX = 256  # HNSW_GROUP_POOL_MAX: candidates per query of a grouped s
 DIVERSE_POOL_MAX = 256  # HNSW_DIVERSE_POOL_MAX: candidates per query of a diversified search
 FROM_ROWS_MAX_TERMS = 64  # HNSW_FROM_ROWS_MAX_TERMS: slots per query of a search from stored rows
 DROP_MAX_N = 1024  # HNSW_DROP_MAX_N: entries per list of the drop
+MULTI_MAX_VECS = 16  # HNSW_MULTI_MAX_VECS: vectors per query of a multi-vector search
+FUSE_MAX_CANDS = 256  # HNSW_FUSE_MAX_CANDS: n_vecs * pool, the candidates of one fused query
+FUSE_SUM = 0  # HNSW_FUSE_SUM: a candidate's score is the sum of its weighted distances to the query's vectors
+FUSE_MIN = 1  # HNSW_FUSE_MIN: ... the smallest of them
 RADIUS_MAX_N = 1024  # HNSW_RADIUS_MAX_N: entries per list of a radius search
 RADIUS_MORE = 1  # HNSW_RADIUS_MORE: the list was full and showed nothing outside the radius
 RANGES_MAX = 16  # HNSW_RANGES_MAX: members of a query's range list
@@ -151,6 +155,10 @@ SYMBOLS = {
                                               u32p, f32p, u32p, C.POINTER(QueryStats)]),
     "hnsw_search_batch_by_id": (C.c_int, [vp, u32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, u32p, f32p, u32p,
                                           C.POINTER(QueryStats)]),
+    "hnsw_fuse_lists_device": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp,
+                                         vp, vp, vp, vp, vp, vp]),
+    "hnsw_search_batch_multi": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, f32p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.c_uint32, u32p, f32p, u32p, u32p, C.POINTER(QueryStats)]),
     "hnsw_distance_batch": (C.c_int, [vp, f32p, u32p, C.c_uint64, f32p]),
     "hnsw_search_layer": (C.c_int, [vp, C.c_uint32, f32p, u32p, C.c_uint32, C.c_uint32, u32p, f32p, u32p,
                                     C.POINTER(QueryStats)]),

@@ -315,12 +315,23 @@ struct DiverseLists {
     // every weight 1.0f); row_status[q] (may be nullptr) is HNSW_OK, or HNSW_ERR_ARG for a query without a present slot
     // or with a present id at or beyond the index length, whose row is all zeros.  Of the fields above the form reads
     // ids and nq alone.
-    uint32_t width, _pad;
+    uint32_t width;
+    // The fourth source form (hnsw_fuse_lists_device), selected by n_vecs != 0 (zero in every other
+    // launch) and looked at before n_out: query q has n_vecs vectors queries[q][t][dim] with weights[q][t] (nullptr: no
+    // multiply) and n_vecs candidate lists ids[q][t][j], j < pool, counts[q][t] and stats[q][t] (either may be nullptr),
+    // n_vecs * pool <= HX_DIVERSE_POOL_MAX.  THE FUSION of include/hnsw_mi355x.h under `mode` goes to out_ids / out_dists
+    // (the scores) [q][n_out], out_counts[q], unique_out[q] (either may be nullptr) and out_stats[q] (with stats).  dists,
+    // lambda, out_gaps and the third form's outputs are not read.
+    uint32_t n_vecs;
     const float *weights;
     float *rows_out;
     int32_t *row_status;
+    uint32_t mode, _pad;
+    const float *queries;
+    uint32_t *unique_out;
 };
 #define HX_FROM_ROWS_MAX_TERMS 64  // slots per composed query: one lane each
+#define HX_MULTI_MAX_VECS 16       // vectors per fused query
 // the selection of d.nq candidate lists (1 <= n_out <= pool <= HX_DIVERSE_POOL_MAX, lambda in [0, 1]): ONE launch of
 // hx_distance_kernel in its second form, one wave per query
 int launch_diversify(const DevView &v, const DiverseLists &d, hipStream_t stream);
@@ -328,6 +339,9 @@ int launch_diversify(const DevView &v, const DiverseLists &d, hipStream_t stream
 // hx_distance_kernel in its third form, one wave per query.  d_weights and d_status may be nullptr.
 int launch_compose_rows(const DevView &v, uint32_t nq, uint32_t width, const uint32_t *d_src_ids, const float *d_weights,
                         float *d_rows, int32_t *d_status, hipStream_t stream);
+// the fusion of d.nq queries of d.n_vecs lists each (1 <= n_vecs <= HX_MULTI_MAX_VECS, 1 <= n_out <= pool, n_vecs * pool <=
+// HX_DIVERSE_POOL_MAX, mode 0 or 1): ONE launch of hx_distance_kernel in its fourth form, one wave per query
+int launch_fuse_lists(const DevView &v, const DiverseLists &d, hipStream_t stream);
 
 // exhaustive scan: every query against every point; partial top-k per (query, segment):
 // part_ids / part_dists are nq x nseg x k.  The host merges the segments.

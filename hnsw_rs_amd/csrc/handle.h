@@ -81,6 +81,8 @@ struct hnsw_index {
     // search from stored rows: hnsw_search_batch_from_rows / _by_id calls answered, the compose launches (those of
     // hnsw_compose_rows_device too) and the drop launches of those calls (hnsw_drop_ids_device takes no handle)
     std::atomic<uint64_t> n_from_rows_calls{0}, n_from_rows_compose{0}, n_from_rows_drop{0};
+    // multi-vector search: hnsw_search_batch_multi calls answered, and the fusions launched (hnsw_fuse_lists_device's too)
+    std::atomic<uint64_t> n_multi_calls{0}, n_multi_fuse{0};
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")
 };
 

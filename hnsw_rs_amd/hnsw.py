@@ -681,6 +681,48 @@ class HNSW:
             nq, n_in, n_out, width, p(d_ex), p(d_src_status), p(d_ids_in), p(d_dists_in), p(d_counts_in), p(d_stats_in),
             p(d_ids), p(d_dists), p(d_counts), p(d_dropped), p(d_stats), stream or None))
 
+    # ---- multi-vector search: several vectors per query, their lists fused (include/hnsw_mi355x.h) -----------------
+    def search_batch_multi(self, Q, n, pool, ef, weights=None, mode="sum"):
+        """The n best of queries of T vectors each, Q [nq, T, dim]: every vector is searched with n = pool, and the
+        distinct ids of a query's T lists are scored against all T vectors -- mode "sum": the sum of weights[q, t] *
+        distance, "min": the smallest of them -- and ranked by (score, id): multi.fuse_lists over search_batch of the
+        nq * T rows (hnsw_search_batch_multi).  weights [nq, T] float32 or None (no multiply).  The answer is the best n
+        of the UNION of the per-vector pools, not of the whole index.
+        -> ids [nq, n] (pad UINT32_MAX), scores [nq, n] (pad +inf), counts [nq], unique [nq] (distinct candidates),
+        stats [nq, 4] (the summed counters of the T searches)"""
+        from .multi import mode_of
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 3 or Q.shape[2] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x T x %d" % self.dim)
+        nq, T = Q.shape[0], Q.shape[1]
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != (nq, T):
+                raise ValueError("weights is [nq, T]")
+        width = max(int(n), 1)
+        ids = np.full((nq, width), _lib.UINT32_MAX, dtype=np.uint32)
+        scores = np.full((nq, width), np.inf, dtype=np.float32)
+        counts, unique = np.zeros(nq, dtype=np.uint32), np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        check(self._L.hnsw_search_batch_multi(
+            self._h, _p(Q, _f32p), nq, T, None if w is None else _p(w, _f32p), mode_of(mode), n, pool, ef, _p(ids, _u32p),
+            _p(scores, _f32p), _p(counts, _u32p), _p(unique, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
+        return ids, scores, counts, unique, stats.view(np.uint32).astype(np.int64)
+
+    def fuse_lists_device(self, nq, n_vecs, pool, n_out, mode, d_Q, d_weights, d_ids_in, d_counts_in, d_stats_in, d_ids,
+                          d_scores, d_counts=None, d_unique=None, d_stats=None, stream=0):
+        """hnsw_fuse_lists_device over torch device tensors (or raw device pointers): d_Q float32 [nq, n_vecs, dim],
+        d_weights float32 [nq, n_vecs] or None, and the [nq, n_vecs, pool] candidate ids a *_device search of this index
+        left for the nq * n_vecs rows of d_Q (d_counts_in / d_stats_in [nq, n_vecs] or None), fused over this index's
+        stored rows into d_ids / d_scores [nq, n_out] (/ d_counts / d_unique / d_stats).  ONE launch enqueued on
+        `stream`, no sync of it."""
+        from .multi import mode_of
+        p = self._dptr
+        check(self._L.hnsw_fuse_lists_device(
+            self._h, nq, n_vecs, pool, n_out, mode_of(mode), p(d_Q), p(d_weights), p(d_ids_in), p(d_counts_in), p(d_stats_in),
+            p(d_ids), p(d_scores), p(d_counts), p(d_unique), p(d_stats), stream or None))
+
     def search_filtered(self, q, n, ef, lo=0, hi=0xFFFFFFFF, mask_set=None, row=None):
         """ONE query under the label range [lo, hi] and, with a resident MaskSet, its row `row` (None, -1 or MASK_NONE: no
         row): hnsw_search_filtered, whose concurrent callers on an index are gathered into one launch.

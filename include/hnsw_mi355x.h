@@ -851,6 +851,82 @@ int hnsw_search_batch_by_id(hnsw_index *h, const uint32_t *src_ids /* nq */, uin
                             int exclude_self, uint32_t *ids /* nq x n */, float *dists /* or NULL */,
                             uint32_t *counts /* or NULL */, hnsw_query_stats *stats /* or NULL */);
 
+/* ---- multi-vector search: several vectors per query, their result lists fused on the device ---------------------------
+ * An extension (the reference takes one vector per query): a text and an image embedding of one request, three rewrites
+ * of one question, "near any of these examples" -- Weaviate's multi-target vectors (sum / min / manual weights), Qdrant's
+ * multi-query, Milvus's weighted hybrid search.  This is not the composed query of the block above: a centroid's
+ * neighbours are not the points with the smallest summed distance to the parts, and "nearest to any of them" has no
+ * composed form.
+ * A call has nq queries of T = n_vecs vectors each: Q [nq][T][dim], weights [nq][T] f32 (NULL: every weight 1.0f and no
+ * multiply), candidate ids ids_in [nq][T][pool], counts_in [nq][T] or NULL, stats_in [nq][T] or NULL.  Limits: 1 <= T <=
+ * HNSW_MULTI_MAX_VECS, 1 <= n_out <= pool, T * pool <= HNSW_FUSE_MAX_CANDS.  mode is HNSW_FUSE_SUM or HNSW_FUSE_MIN.
+ * THE FUSION of one query:
+ *   - entry j of list t is PRESENT iff j < min(counts_in[t], pool), or, without counts, iff its id is not UINT32_MAX.  If
+ *     any of the query's T incoming statuses is not HNSW_OK the query has no present entry: its status is the first one
+ *     that is not HNSW_OK in vector order, its count 0 and its rows padded;
+ *   - a present id at or beyond the index length gives the query HNSW_ERR_ARG, count 0 and padded rows, and no stored row
+ *     is read for it;
+ *   - a vector with a NaN element gives the query HNSW_ERR_NAN_INPUT, count 0 and padded rows.  Precedence: the incoming
+ *     status, then HNSW_ERR_ARG, then HNSW_ERR_NAN_INPUT;
+ *   - the candidate set C is the DISTINCT present ids over all T lists: an id listed several times, inside one list or
+ *     across lists, is one candidate; unique = |C| (0 for a failed query);
+ *   - D_t(c), for every t < T and every c in C whether or not list t holds c, is the bits of hnsw_distance_batch(h, q_t,
+ *     {c}): the query-side arithmetic (an 8-bit query is quantised as any query is; under the metric_cosine option the
+ *     vector is normalised once from the caller's raw row).  The lists' own distances are not an input;
+ *   - the fold, with p_t = w_t * D_t(c) one f32 multiply (omitted when weights is NULL).  HNSW_FUSE_SUM: s = p_0, then
+ *     s = s + p_t for t = 1 .. T-1 in vector order, each operation rounded separately and never contracted.
+ *     HNSW_FUSE_MIN: s = +inf, then s = p_t < s ? p_t : s in vector order (a NaN term leaves s as it is).  Negative and
+ *     zero weights are legal; a NaN or infinite weight is no argument error;
+ *   - a candidate whose score is NaN is never returned; the others are ranked by (score under f32 <, -0 == +0; then id
+ *     ascending), so the answer depends neither on the order of the lists nor on which duplicate was kept.
+ * Per query: ids [n_out] (pad UINT32_MAX), scores [n_out] (the fold's own bits, pad +inf), counts = entries written,
+ * unique (optional), stats (optional): n_dist, n_exp and sum_deg the wrapping uint32 sums of the T incoming records (the
+ * fusion's own evaluations are not counted), the status as above.  Every output word is written exactly once.
+ * The answer is the best n_out of the UNION of the per-vector pools, not of the whole index: a point that is in no
+ * vector's pool is not a candidate, however small its summed distance.  A caller who wants more raises `pool`.
+ *
+ * hnsw_fuse_lists_device is THE FUSION alone over buffers in HBM: every d_* pointer is device memory, the lists are what
+ * any *_device search of the same handle leaves after its _finish for the nq * T rows of d_Q taken as one batch (ids
+ * local to the handle, so a replica handle serves).  After the snapshot is brought up to date ONE launch (the distance
+ * seam's kernel in its fusion form, one wave per query) is enqueued on `stream` and the call returns without
+ * synchronising it.  Under the metric_cosine option it reads a stream-ordered unit-length copy of d_Q, exactly as
+ * hnsw_search_batch_device does; otherwise nothing is allocated or copied, and the call is capturable under that call's
+ * conditions.  The status of a failed query is written to d_stats only (the call cannot see it).  Outputs must not
+ * overlap inputs.  d_weights, d_counts_in, d_counts and d_unique may be NULL; d_stats is required iff d_stats_in is
+ * given.  HNSW_ERR_ARG, decided before the device is touched: h NULL; the limits violated; a mode other than the two;
+ * nq > 2^31 - 1; d_Q, d_ids_in, d_ids or d_scores NULL; exactly one of d_stats_in / d_stats given.  nq == 0 is HNSW_OK on
+ * any handle, whatever else is passed, and launches nothing; an empty index is HNSW_ERR_EMPTY.
+ *
+ * hnsw_search_batch_multi answers host-pointer queries of T vectors each by their n best.  By definition the result is
+ * THE FUSION, with n_out = n, of the lists that hnsw_search_batch returns for the nq * T rows of Q taken as one batch
+ * with n = pool and ef' = max(ef, pool, 1), on the same handle with the same options.  Everything of that call is
+ * inherited: deletions, the cosine option, per-query errors (the first is returned with the QUERY named, not the row;
+ * every other row is filled in).  With nothing deleted the call stays on the device: Q and the weights go up once (the
+ * cosine option's unit copy made once, for the search and the fusion), the launch of hnsw_search_batch_device and the
+ * re-run loop of its _finish over nq * T queries, one fusion launch, ONE copy of the block [ids | scores | counts | unique | stats] back.  While ids are deleted the candidates are the host
+ * form's and go up before the fusion; pool <= 64 is then required.  scores, counts, unique and stats may be NULL.
+ * HNSW_ERR_ARG, decided before the device is touched: the limits violated; a mode other than the two; Q or ids NULL;
+ * nq * T > 2^31 - 1.  nq == 0 is HNSW_OK; an empty index is HNSW_ERR_EMPTY.  hnsw_get_stat: "multi_calls"
+ * (hnsw_search_batch_multi calls answered), "multi_fuse_launches" (fusions launched, hnsw_fuse_lists_device's included).
+ * Not provided: per-hit per-vector distances; a different T per query; filters other than deletions in the host entry
+ * (the primitive chains with the filtered *_device searches); rank fusion; fusion over shards (merged lists carry global
+ * ids); one-query gathered calls; the Rust shim's binding. */
+#define HNSW_MULTI_MAX_VECS 16
+#define HNSW_FUSE_MAX_CANDS 256
+#define HNSW_FUSE_SUM 0
+#define HNSW_FUSE_MIN 1
+int hnsw_fuse_lists_device(hnsw_index *h, uint64_t nq, uint32_t n_vecs, uint32_t pool, uint32_t n_out, uint32_t mode,
+                           const float *d_Q /* nq x n_vecs x dim */, const float *d_weights /* nq x n_vecs, or NULL */,
+                           const uint32_t *d_ids_in /* nq x n_vecs x pool */, const uint32_t *d_counts_in /* or NULL */,
+                           const hnsw_query_stats *d_stats_in /* or NULL */, uint32_t *d_ids, float *d_scores /* nq x n_out */,
+                           uint32_t *d_counts /* or NULL */, uint32_t *d_unique /* or NULL */,
+                           hnsw_query_stats *d_stats /* required iff d_stats_in */, void *stream);
+int hnsw_search_batch_multi(hnsw_index *h, const float *Q /* nq x n_vecs x dim */, uint64_t nq, uint32_t n_vecs,
+                            const float *weights /* nq x n_vecs, or NULL */, uint32_t mode, uint32_t n, uint32_t pool,
+                            uint32_t ef, uint32_t *ids /* nq x n */, float *scores /* or NULL */,
+                            uint32_t *counts /* or NULL */, uint32_t *unique /* or NULL */,
+                            hnsw_query_stats *stats /* or NULL */);
+
 /* Test seams that mirror the reference's own units:
  * VecBase::dist2many (vectors/src/lib.rs:17-22): the query (quantised like ann_by_vector does,
  * template.rs:313) against stored ids, on the device, exact accumulation order. */
@@ -1034,7 +1110,8 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * search: "diverse_calls" (hnsw_search_batch_diverse calls answered), "diverse_launches" (selections launched,
  * hnsw_diversify_device's included); search from stored rows: "from_rows_calls" (hnsw_search_batch_from_rows and
  * _by_id calls answered), "from_rows_compose_launches" (hnsw_compose_rows_device's included), "from_rows_drop_launches"
- * (the drops those calls launched); deletion:
+ * (the drops those calls launched); multi-vector search: "multi_calls" (hnsw_search_batch_multi calls answered),
+ * "multi_fuse_launches" (fusions launched, hnsw_fuse_lists_device's included); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
