@@ -2,7 +2,7 @@
 Gumo-A/hnsw_rs.  The product is libhnsw_mi355x.so (HIP kernels for gfx950 + host index, C ABI in
 include/hnsw_mi355x.h); this package is its thin host-side mirror of the reference's interface.
 """
-from ._lib import (DIVERSE_POOL_MAX, DROP_MAX_N, FROM_ROWS_MAX_TERMS, FUSE_MAX_CANDS, FUSE_MIN, FUSE_SUM, GROUP_POOL_MAX, MASK_NONE, MULTI_MAX_VECS, RADIUS_MAX_N, RADIUS_MORE, RANGES_MAX, VEC_F32, VEC_QUANT8, UINT32_MAX,  # noqa: F401
+from ._lib import (DIVERSE_POOL_MAX, DROP_MAX_N, FROM_ROWS_MAX_TERMS, FUSE_MAX_CANDS, FUSE_MIN, FUSE_SUM, GROUP_POOL_MAX, LATE_MAX_CANDS, LATE_MAX_DOCS, LATE_MAX_VECS, LATE_SUM, LATE_SUM_SQ, MASK_NONE, MULTI_MAX_VECS, RADIUS_MAX_N, RADIUS_MORE, RANGES_MAX, VEC_F32, VEC_QUANT8, UINT32_MAX,  # noqa: F401
                    HnswError, lib)
 from .hnsw import (HNSW, Graph, MaskSet, Point, device_count, draw_levels, kernel_log, kernel_name, pack_allow,  # noqa: F401
                    pack_allow_many, pack_ranges, synth_rows)
@@ -10,5 +10,6 @@ from .grouped import group_by_label  # noqa: F401
 from .diverse import mmr_select  # noqa: F401
 from .from_rows import compose_rows, drop_ids  # noqa: F401
 from .multi import fuse_lists  # noqa: F401
+from .late import late_interaction  # noqa: F401
 from .radius import radius_cut, radius_ladder, to_csr  # noqa: F401
 from .partitioned import PartitionedIndex, merge_topk  # noqa: F401

@@ -21,6 +21,11 @@ MULTI_MAX_VECS = 16  # HNSW_MULTI_MAX_VECS: vectors per query of a multi-vector 
 FUSE_MAX_CANDS = 256  # HNSW_FUSE_MAX_CANDS: n_vecs * pool, the candidates of one fused query
 FUSE_SUM = 0  # HNSW_FUSE_SUM: a candidate's score is the sum of its weighted distances to the query's vectors
 FUSE_MIN = 1  # HNSW_FUSE_MIN: ... the smallest of them
+LATE_MAX_VECS = 32  # HNSW_LATE_MAX_VECS: vectors per query of a late-interaction search
+LATE_MAX_CANDS = 1024  # HNSW_LATE_MAX_CANDS: n_vecs * pool, the candidates of one late-interaction query
+LATE_MAX_DOCS = 256  # HNSW_LATE_MAX_DOCS: documents returned per query
+LATE_SUM = 0  # HNSW_LATE_SUM: a document's score is the sum over the query's vectors of the distance to its nearest row
+LATE_SUM_SQ = 1  # HNSW_LATE_SUM_SQ: ... of that distance squared (MaxSim's ranking on unit-length rows)
 RADIUS_MAX_N = 1024  # HNSW_RADIUS_MAX_N: entries per list of a radius search
 RADIUS_MORE = 1  # HNSW_RADIUS_MORE: the list was full and showed nothing outside the radius
 RANGES_MAX = 16  # HNSW_RANGES_MAX: members of a query's range list
@@ -159,6 +164,10 @@ SYMBOLS = {
                                          vp, vp, vp, vp, vp, vp]),
     "hnsw_search_batch_multi": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, f32p, C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.c_uint32, u32p, f32p, u32p, u32p, C.POINTER(QueryStats)]),
+    "hnsw_late_interaction_device": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp,
+                                               vp, vp, vp, vp, vp, vp, vp, vp]),
+    "hnsw_search_batch_late": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         u32p, f32p, u32p, u32p, u32p, u32p, C.POINTER(QueryStats)]),
     "hnsw_distance_batch": (C.c_int, [vp, f32p, u32p, C.c_uint64, f32p]),
     "hnsw_search_layer": (C.c_int, [vp, C.c_uint32, f32p, u32p, C.c_uint32, C.c_uint32, u32p, f32p, u32p,
                                     C.POINTER(QueryStats)]),

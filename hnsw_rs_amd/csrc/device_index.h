@@ -326,12 +326,26 @@ struct DiverseLists {
     const float *weights;
     float *rows_out;
     int32_t *row_status;
-    uint32_t mode, _pad;
+    uint32_t mode;
+    // The fifth source form (hnsw_late_interaction_device), selected by late != 0 (zero in every
+    // other launch) and looked at FIRST: query q has n_vecs vectors queries[q][t][dim] and n_vecs candidate lists
+    // ids[q][t][j], j < pool, counts[q][t] and stats[q][t] (either may be nullptr), n_vecs * pool <= HX_LATE_MAX_CANDS;
+    // labels[id], id < label_len, is the label column (nullptr: every label 0).  THE LATE INTERACTION of
+    // include/hnsw_mi355x.h under `mode` goes to out_ids (the documents' labels) / out_dists (their scores) [q][n_out],
+    // best_out / sizes_out [q][n_out], out_counts[q], n_docs_out[q] (all four may be nullptr) and out_stats[q] (with
+    // stats).  dists, lambda, weights, out_gaps, unique_out and the third form's outputs are not read.
+    uint32_t late;
     const float *queries;
     uint32_t *unique_out;
+    const uint32_t *labels;
+    uint64_t label_len;
+    uint32_t *best_out, *sizes_out, *n_docs_out;
 };
 #define HX_FROM_ROWS_MAX_TERMS 64  // slots per composed query: one lane each
 #define HX_MULTI_MAX_VECS 16       // vectors per fused query
+#define HX_LATE_MAX_VECS 32        // vectors per late-interaction query
+#define HX_LATE_MAX_CANDS 1024     // its candidates, n_vecs * pool: 36 bytes of LDS each
+#define HX_LATE_MAX_DOCS 256       // the documents it returns
 // the selection of d.nq candidate lists (1 <= n_out <= pool <= HX_DIVERSE_POOL_MAX, lambda in [0, 1]): ONE launch of
 // hx_distance_kernel in its second form, one wave per query
 int launch_diversify(const DevView &v, const DiverseLists &d, hipStream_t stream);
@@ -342,6 +356,10 @@ int launch_compose_rows(const DevView &v, uint32_t nq, uint32_t width, const uin
 // the fusion of d.nq queries of d.n_vecs lists each (1 <= n_vecs <= HX_MULTI_MAX_VECS, 1 <= n_out <= pool, n_vecs * pool <=
 // HX_DIVERSE_POOL_MAX, mode 0 or 1): ONE launch of hx_distance_kernel in its fourth form, one wave per query
 int launch_fuse_lists(const DevView &v, const DiverseLists &d, hipStream_t stream);
+// the late interaction of d.nq queries of d.n_vecs lists each (1 <= n_vecs <= HX_LATE_MAX_VECS, n_vecs * pool <=
+// HX_LATE_MAX_CANDS, 1 <= n_out <= min(n_vecs * pool, HX_LATE_MAX_DOCS), mode 0 or 1): ONE launch of hx_distance_kernel in
+// its fifth form, one wave per query; sets d.late itself
+int launch_late_interaction(const DevView &v, DiverseLists d, hipStream_t stream);
 
 // exhaustive scan: every query against every point; partial top-k per (query, segment):
 // part_ids / part_dists are nq x nseg x k.  The host merges the segments.

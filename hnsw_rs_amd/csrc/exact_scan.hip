@@ -1,7 +1,8 @@
 // exact_scan.hip -- the exact scans under the index's own metric, gfx950: hx_brute_kernel (the reference's ground truth,
 // every query against all points) and hx_distance_kernel (dist2many for one query, a test seam; in its second form the
 // MMR selection of diversified search: stored rows against a stored row; in its third the query rows composed out of
-// stored rows; in its fourth the fusion of a query's per-vector candidate lists), with their launchers.
+// stored rows; in its fourth the fusion of a query's per-vector candidate lists; in its fifth the late interaction that
+// scores those candidates as documents), with their launchers.
 // Same staged query, same row distance (dist_any_dim) and same sorted list (WaveList) as the search kernels:
 // search_common.h.  The MFMA screen of hnsw_brute_force_fast is brute_mfma.hip.
 
@@ -364,6 +365,200 @@ __device__ __forceinline__ void fuse_lists(const DevView &v, const DiverseLists 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The kernel's fifth form (DiverseLists with late != 0, device_index.h): query blockIdx.x's
+// n_vecs candidate lists of d.pool ids each scored as DOCUMENTS -- the candidates that share a label -- by the sum over
+// the query's vectors of the distance to the document's nearest candidate, one wave per query.  Behind the staged vector
+// the LDS table holds, with cap = n_vecs * pool rounded up to 64, seven arrays of cap words and one of cap double words:
+//   sid    the entries as loaded, absent ones as HX_EMPTY_SLOT; once the ids are compacted, compacted candidate j's label
+//   cid    the distinct present ids, compacted            cdoc   candidate j's document, an index into the arrays below
+//   dlab   the distinct labels, compacted                 dmin   document g's minimum under the vector in hand, as bits
+//   dsum   its running fold                               dsize  its candidates
+//   dbest  the smallest (distance bits << 32 | id) any of its candidates had under any vector
+// Nothing of it lives in registers: every step is a loop over the table, 64 entries a turn.  Presence, range and the
+// incoming statuses are decided (a ballot) before any row is read.  Duplicates go by fuse_lists' all-pairs compare -- four
+// words a read, the same address in every lane -- over the entries before an entry's own turn; the labels are numbered
+// the same way, the compare keeping the first equal entry's index so that a later candidate finds its document.  Per
+// vector: stage_query, then fuse_lists' pass loop (QUANT8 a lane pair per entry and 32 entries a pass, F32 a lane per
+// entry and 64; a pass's row reads all in flight together), each distance folded into its document by LDS atomic
+// minima on the bits -- distances are >= +0 or NaN and a NaN is skipped, so the bits order as the floats do and the
+// result does not depend on the order of arrival -- and after the pass e_t into dsum.  The emission takes n_out times
+// the wave's minimum of (orderable score, label); labels are distinct, so one lane owns it.  Plain vector stores.
+// ---------------------------------------------------------------------------------------------
+#define HX_LATE_LDS(cap) ((size_t)(cap) * 36)
+template <int KIND>
+__device__ __forceinline__ void late_interaction(const DevView &v, const DiverseLists &d, float *yq, unsigned char *tab, int lane) {
+    constexpr int LPC = (KIND == HNSW_VEC_QUANT8) ? 2 : 1;
+    constexpr int CHUNK = 64 / LPC;
+    constexpr uint32_t INF_BITS = 0x7F800000u, NONE = 0xFFFFFFFFu, LATER = 0x80000000u;
+    const int h = (LPC == 2) ? (lane & 1) : 0;
+    const uint32_t q = blockIdx.x, T = d.n_vecs, pool = d.pool, n_out = d.n_out;
+    if (q >= d.nq || T > HX_LATE_MAX_VECS || pool > HX_LATE_MAX_CANDS || T * pool > HX_LATE_MAX_CANDS ||
+        n_out > HX_LATE_MAX_DOCS || n_out > T * pool)
+        return;  // (the launcher's limits)
+    const uint32_t total = T * pool, cap = (total + 63u) & ~63u;
+    uint32_t *sid = reinterpret_cast<uint32_t *>(tab);
+    uint32_t *cid = sid + cap, *cdoc = cid + cap, *dlab = cdoc + cap, *dmin = dlab + cap;
+    float *dsum = reinterpret_cast<float *>(dmin + cap);
+    uint32_t *dsize = dmin + 2 * cap;
+    u64 *dbest = reinterpret_cast<u64 *>(dsize + cap);  // (28 * cap bytes in: 8-byte aligned)
+    const size_t l0 = (size_t)q * T, in0 = (size_t)q * total, out0 = (size_t)q * n_out;
+    hnsw_query_stats st;
+    st.n_dist = st.n_exp = st.sum_deg = 0;
+    st.status = HNSW_OK;
+    if (d.stats)
+        for (uint32_t t = 0; t < T; t++) {  // (wave-uniform: the wrapping sums, the first status that is not OK)
+            const hnsw_query_stats s = d.stats[l0 + t];
+            st.n_dist += s.n_dist, st.n_exp += s.n_exp, st.sum_deg += s.sum_deg;
+            if (st.status == HNSW_OK) st.status = s.status;
+        }
+    const bool ok = st.status == HNSW_OK;  // a failed query has no present entry: count 0 and padded rows
+    bool beyond = false;
+    for (uint32_t j = lane; j < cap; j += 64) {
+        uint32_t id = HX_EMPTY_SLOT;
+        if (j < total) {
+            const uint32_t t = j / pool, jj = j - t * pool;
+            const uint32_t raw = d.ids[in0 + j];
+            const bool present = ok && (d.counts ? jj < min(d.counts[l0 + t], pool) : raw != HX_EMPTY_SLOT);
+            beyond |= present && raw >= v.n_points;
+            id = present ? raw : HX_EMPTY_SLOT;
+        }
+        sid[j] = id;
+    }
+    wave_fence();
+    uint32_t count = 0, unique = 0, n_docs = 0;  // wave-uniform
+    if (__ballot(beyond)) {
+        st.status = HNSW_ERR_ARG;  // no row of the index is read for this query
+    } else if (ok) {
+        for (uint32_t base = 0; base < total; base += 64) {  // the distinct present ids, in table order, to cid[0 .. unique)
+            const uint32_t j = base + lane, id = sid[j], end = min(total, base + 64);
+            bool dup = false;
+            for (uint32_t i = 0; i < end; i += 4) {  // (the table is EMPTY from `total` to cap)
+                const uint4 w = *reinterpret_cast<const uint4 *>(sid + i);
+                dup |= (w.x == id && i < j) | (w.y == id && i + 1 < j) | (w.z == id && i + 2 < j) | (w.w == id && i + 3 < j);
+            }
+            const bool live = id != HX_EMPTY_SLOT && !dup;
+            const u64 b = __ballot(live);
+            if (live) cid[unique + __builtin_popcountll(b & ((1ull << lane) - 1))] = id;
+            unique += (uint32_t)__builtin_popcountll(b);
+        }
+        wave_fence();
+        uint32_t *clab = sid;  // (the entries have served)
+        const uint64_t label_len = d.labels ? d.label_len : 0;
+        for (uint32_t j = lane; j < unique; j += 64) {
+            const uint32_t c = cid[j];
+            clab[j] = c < label_len ? d.labels[c] : 0u;
+        }
+        wave_fence();
+        for (uint32_t base = 0; base < unique; base += 64) {  // the distinct labels, in candidate order, to dlab[0 .. n_docs)
+            const uint32_t j = base + lane, lab = clab[j], end = min(unique, base + 64);
+            const bool live = j < unique;
+            uint32_t fi = NONE;  // the first candidate before j with j's label
+            for (uint32_t i = 0; i < end; i += 4) {  // (a word at or behind `unique` is never before a live j)
+                const uint4 w = *reinterpret_cast<const uint4 *>(clab + i);
+                fi = min(fi, w.x == lab && i < j ? i : NONE);
+                fi = min(fi, w.y == lab && i + 1 < j ? i + 1 : NONE);
+                fi = min(fi, w.z == lab && i + 2 < j ? i + 2 : NONE);
+                fi = min(fi, w.w == lab && i + 3 < j ? i + 3 : NONE);
+            }
+            const bool first = live && fi == NONE;
+            const u64 b = __ballot(first);
+            if (first) {
+                const uint32_t g = n_docs + (uint32_t)__builtin_popcountll(b & ((1ull << lane) - 1));
+                cdoc[j] = g;
+                dlab[g] = lab;
+                dmin[g] = INF_BITS;
+                dsum[g] = 0.0f;
+                dsize[g] = 0u;
+                dbest[g] = KEY_INVALID;
+            } else if (live) {
+                cdoc[j] = fi | LATER;  // (resolved below, once the first's document is numbered)
+            }
+            n_docs += (uint32_t)__builtin_popcountll(b);
+        }
+        wave_fence();
+        for (uint32_t j = lane; j < unique; j += 64) {
+            uint32_t g = cdoc[j];
+            if (g & LATER) {
+                g = cdoc[g & ~LATER];  // (a first's entry: not rewritten here)
+                cdoc[j] = g;
+            }
+            atomicAdd(&dsize[g], 1u);
+        }
+        wave_fence();
+        bool nan = false;  // wave-uniform
+        for (uint32_t t = 0; t < T; t++) {
+            if (!stage_query<KIND>(v, d.queries + (l0 + t) * v.dim, yq, lane)) {
+                nan = true;
+                break;
+            }
+            for (uint32_t base = 0; base < unique; base += CHUNK) {
+                const uint32_t j = base + lane / LPC;
+                const bool active = j < unique;
+                const uint32_t id = active ? cid[j] : 0u;
+                const float dist = dist_any_dim<KIND>(v, id, active, h, yq);
+                if (active && h == 0 && dist == dist) {  // (a NaN leaves the minimum and the best row as they are)
+                    const uint32_t bits = __builtin_bit_cast(uint32_t, dist), g = cdoc[j];
+                    atomicMin(&dmin[g], bits);
+                    atomicMin(&dbest[g], ((u64)bits << 32) | id);
+                }
+            }
+            wave_fence();
+            for (uint32_t g = lane; g < n_docs; g += 64) {
+                const float m = __builtin_bit_cast(float, dmin[g]);
+                const float e = d.mode == HNSW_LATE_SUM_SQ ? m * m : m;
+                dsum[g] = t == 0 ? e : dsum[g] + e;
+                dmin[g] = INF_BITS;
+            }
+            wave_fence();
+        }
+        if (nan) {
+            st.status = HNSW_ERR_NAN_INPUT;
+            n_docs = 0;
+        } else {
+            for (uint32_t t = 0; t < n_out; t++) {
+                u64 mine = KEY_INVALID;
+                uint32_t mg = 0;
+                for (uint32_t g = lane; g < n_docs; g += 64) {
+                    const float score = dsum[g];
+                    if (score != score) continue;  // a NaN score is never returned (nor is a document twice: below)
+                    const uint32_t u = __builtin_bit_cast(uint32_t, score == 0.0f ? 0.0f : score);  // -0 == +0: one key
+                    const u64 key = ((u64)((u & 0x80000000u) ? ~u : (u | 0x80000000u)) << 32) | dlab[g];
+                    if (key < mine) mine = key, mg = g;
+                }
+                u64 best = mine;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const u64 other = ((u64)(uint32_t)__shfl_xor((int)(uint32_t)(best >> 32), o) << 32) |
+                                      (uint32_t)__shfl_xor((int)(uint32_t)best, o);
+                    best = other < best ? other : best;
+                }
+                if (best == KEY_INVALID) break;  // nothing left
+                if (mine == best) {  // (labels are distinct: one document of one lane)
+                    d.out_ids[out0 + t] = (uint32_t)best;
+                    d.out_dists[out0 + t] = dsum[mg];
+                    if (d.best_out) d.best_out[out0 + t] = (uint32_t)dbest[mg];
+                    if (d.sizes_out) d.sizes_out[out0 + t] = dsize[mg];
+                    dsum[mg] = __builtin_nanf("");
+                }
+                wave_fence();
+                count = t + 1;
+            }
+        }
+    }
+    for (uint32_t s = count + lane; s < n_out; s += 64) {
+        d.out_ids[out0 + s] = 0u;
+        d.out_dists[out0 + s] = __builtin_inff();
+        if (d.best_out) d.best_out[out0 + s] = HX_EMPTY_SLOT;
+        if (d.sizes_out) d.sizes_out[out0 + s] = 0u;
+    }
+    if (lane == 0) {
+        if (d.out_counts) d.out_counts[q] = count;
+        if (d.n_docs_out) d.n_docs_out[q] = n_docs;
+        if (d.out_stats) d.out_stats[q] = st;
+    }
+}
+
 template <int KIND>
 __global__ void __launch_bounds__(64)
 hx_distance_kernel(const DevView v, const float *q, const uint32_t *ids, uint64_t k, float *out,
@@ -371,6 +566,10 @@ hx_distance_kernel(const DevView v, const float *q, const uint32_t *ids, uint64_
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *yq = reinterpret_cast<float *>(smem);
     const int lane = threadIdx.x;
+    if (dv.late) {  // (looked at first: this form sets n_vecs and n_out too)
+        late_interaction<KIND>(v, dv, yq, smem + query_lds_bytes(v), lane);
+        return;
+    }
     if (dv.n_vecs) {  // (a kernel argument: the branch is the wave's; looked at before n_out, which this form sets too)
         fuse_lists<KIND>(v, dv, yq, smem + query_lds_bytes(v), lane);
         return;
@@ -523,6 +722,27 @@ int launch_fuse_lists(const DevView &v, const DiverseLists &d, hipStream_t strea
     return launch_checked({"fuse lists kernel launch"},
                           v.kind == HNSW_VEC_QUANT8 ? hx_distance_kernel<HNSW_VEC_QUANT8> : hx_distance_kernel<HNSW_VEC_F32>,
                           dim3(d.nq), dim3(64), query_lds_bytes(v) + HX_DIVERSE_LDS, stream, v, static_cast<const float *>(nullptr),
+                          static_cast<const uint32_t *>(nullptr), (uint64_t)0, static_cast<float *>(nullptr),
+                          static_cast<int32_t *>(nullptr), d);
+}
+
+int launch_late_interaction(const DevView &v, DiverseLists d, hipStream_t stream) {
+    if (d.nq == 0) return HNSW_OK;
+    const uint64_t total = (uint64_t)d.n_vecs * d.pool;
+    if (d.n_vecs == 0 || d.n_vecs > HX_LATE_MAX_VECS || d.pool == 0 || total > HX_LATE_MAX_CANDS || d.n_out == 0 ||
+        d.n_out > total || d.n_out > HX_LATE_MAX_DOCS || d.mode > HNSW_LATE_SUM_SQ || d.nq > 0x7FFFFFFFu || !d.queries ||
+        !d.ids || !d.out_ids || !d.out_dists || (d.stats != nullptr) != (d.out_stats != nullptr)) {
+        set_error("late interaction: needs 1 <= n_vecs <= %d, n_vecs * pool <= %d, 1 <= n_out <= min(n_vecs * pool, %d), a "
+                  "mode, at most 2^31 - 1 queries, the vectors, the lists and the outputs", HX_LATE_MAX_VECS, HX_LATE_MAX_CANDS,
+                  HX_LATE_MAX_DOCS);
+        return HNSW_ERR_ARG;
+    }
+    d.late = 1;
+    if (!d.labels) d.label_len = 0;  // no column: every label is 0 and nothing is read
+    const size_t cap = ((size_t)total + 63) & ~(size_t)63;
+    return launch_checked({"late interaction kernel launch", "late interaction: the staged vector and the table need %zu bytes of LDS"},
+                          v.kind == HNSW_VEC_QUANT8 ? hx_distance_kernel<HNSW_VEC_QUANT8> : hx_distance_kernel<HNSW_VEC_F32>,
+                          dim3(d.nq), dim3(64), query_lds_bytes(v) + HX_LATE_LDS(cap), stream, v, static_cast<const float *>(nullptr),
                           static_cast<const uint32_t *>(nullptr), (uint64_t)0, static_cast<float *>(nullptr),
                           static_cast<int32_t *>(nullptr), d);
 }

@@ -83,6 +83,9 @@ struct hnsw_index {
     std::atomic<uint64_t> n_from_rows_calls{0}, n_from_rows_compose{0}, n_from_rows_drop{0};
     // multi-vector search: hnsw_search_batch_multi calls answered, and the fusions launched (hnsw_fuse_lists_device's too)
     std::atomic<uint64_t> n_multi_calls{0}, n_multi_fuse{0};
+    // late-interaction search: hnsw_search_batch_late calls answered, and the late interactions launched
+    // (hnsw_late_interaction_device's too)
+    std::atomic<uint64_t> n_late_calls{0}, n_late_launches{0};
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")
 };
 

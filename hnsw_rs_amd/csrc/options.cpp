@@ -116,6 +116,8 @@ const Stat kStats[] = {
     HX_STAT("from_rows_drop_launches", h.n_from_rows_drop),
     HX_STAT("multi_calls", h.n_multi_calls),
     HX_STAT("multi_fuse_launches", h.n_multi_fuse),
+    HX_STAT("late_calls", h.n_late_calls),
+    HX_STAT("late_launches", h.n_late_launches),
     HX_STAT("deleted", h.del.count),
     HX_STAT("deleted_mask_words_uploaded", h.del.words_uploaded),
     HX_STAT("deleted_queries_graph", h.n_del_graph),

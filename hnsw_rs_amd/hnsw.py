@@ -723,6 +723,47 @@ class HNSW:
             self._h, nq, n_vecs, pool, n_out, mode_of(mode), p(d_Q), p(d_weights), p(d_ids_in), p(d_counts_in), p(d_stats_in),
             p(d_ids), p(d_scores), p(d_counts), p(d_unique), p(d_stats), stream or None))
 
+    # ---- late-interaction search: documents of several rows scored by summed min distance (include/hnsw_mi355x.h) ----
+    def search_batch_late(self, Q, n, pool, ef, mode="sum"):
+        """The n best DOCUMENTS -- the rows that share a label (set_labels) -- of queries of T vectors each, Q [nq, T, dim]:
+        every vector is searched with n = pool, and a document with a row among the distinct ids of a query's T lists is
+        scored by the sum over the vectors of the distance (mode "sum"; "sum_sq": its square, MaxSim's ranking on
+        unit-length rows) to its nearest row among them: late.late_interaction over search_batch of the nq * T rows
+        (hnsw_search_batch_late).  A document's minimum runs over its rows in the pools, not over all its stored rows.
+        -> doc_labels [nq, n] (pad 0), scores [nq, n] (pad +inf), best_ids [nq, n] (pad UINT32_MAX: the row to show as
+        the hit), doc_sizes [nq, n] (pad 0), counts [nq], n_docs [nq], stats [nq, 4] (the summed counters of the T
+        searches)"""
+        from .late import mode_of
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 3 or Q.shape[2] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x T x %d" % self.dim)
+        nq, T = Q.shape[0], Q.shape[1]
+        width = max(int(n), 1)
+        labels = np.zeros((nq, width), dtype=np.uint32)
+        scores = np.full((nq, width), np.inf, dtype=np.float32)
+        best = np.full((nq, width), _lib.UINT32_MAX, dtype=np.uint32)
+        sizes = np.zeros((nq, width), dtype=np.uint32)
+        counts, n_docs = np.zeros(nq, dtype=np.uint32), np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        check(self._L.hnsw_search_batch_late(
+            self._h, _p(Q, _f32p), nq, T, mode_of(mode), n, pool, ef, _p(labels, _u32p), _p(scores, _f32p), _p(best, _u32p),
+            _p(sizes, _u32p), _p(counts, _u32p), _p(n_docs, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
+        return labels, scores, best, sizes, counts, n_docs, stats.view(np.uint32).astype(np.int64)
+
+    def late_interaction_device(self, nq, n_vecs, pool, n_out, mode, d_Q, d_ids_in, d_counts_in, d_stats_in, d_doc_labels,
+                                d_scores, d_best_ids=None, d_doc_sizes=None, d_counts=None, d_n_docs=None, d_stats=None,
+                                stream=0):
+        """hnsw_late_interaction_device over torch device tensors (or raw device pointers): d_Q float32 [nq, n_vecs, dim]
+        and the [nq, n_vecs, pool] candidate ids a *_device search of this index left for the nq * n_vecs rows of d_Q
+        (d_counts_in / d_stats_in [nq, n_vecs] or None), scored as documents over this index's stored rows and labels
+        into d_doc_labels / d_scores [nq, n_out] (/ d_best_ids / d_doc_sizes / d_counts / d_n_docs / d_stats).  ONE launch
+        enqueued on `stream`, no sync of it."""
+        from .late import mode_of
+        p = self._dptr
+        check(self._L.hnsw_late_interaction_device(
+            self._h, nq, n_vecs, pool, n_out, mode_of(mode), p(d_Q), p(d_ids_in), p(d_counts_in), p(d_stats_in),
+            p(d_doc_labels), p(d_scores), p(d_best_ids), p(d_doc_sizes), p(d_counts), p(d_n_docs), p(d_stats), stream or None))
+
     def search_filtered(self, q, n, ef, lo=0, hi=0xFFFFFFFF, mask_set=None, row=None):
         """ONE query under the label range [lo, hi] and, with a resident MaskSet, its row `row` (None, -1 or MASK_NONE: no
         row): hnsw_search_filtered, whose concurrent callers on an index are gathered into one launch.

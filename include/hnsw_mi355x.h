@@ -927,6 +927,90 @@ int hnsw_search_batch_multi(hnsw_index *h, const float *Q /* nq x n_vecs x dim *
                             uint32_t *counts /* or NULL */, uint32_t *unique /* or NULL */,
                             hnsw_query_stats *stats /* or NULL */);
 
+/* ---- late-interaction search: documents of several rows scored by summed min distance, on the device -------------------
+ * An extension (the reference scores rows, one vector per query): the way multi-vector retrieval models (ColBERT,
+ * ColPali and their kin) are served.  A document is the rows that share a label (hnsw_set_labels); a query of T vectors
+ * is scored against it by taking, for every query vector, the distance to the document's nearest row, and adding those up
+ * (MaxSim / Chamfer).  Neither hnsw_search_batch_multi (it scores rows: the row with the smallest summed distance to all
+ * vectors is not the document whose rows cover the vectors best) nor hnsw_search_batch_grouped (it collapses one list by
+ * rank and never looks at a second vector) answers this.
+ * A call has nq queries of T = n_vecs vectors each: Q [nq][T][dim], candidate ids ids_in [nq][T][pool], counts_in [nq][T]
+ * or NULL, stats_in [nq][T] or NULL.  Limits: 1 <= T <= HNSW_LATE_MAX_VECS, T * pool <= HNSW_LATE_MAX_CANDS, 1 <= n_out
+ * <= min(T * pool, HNSW_LATE_MAX_DOCS).  mode is HNSW_LATE_SUM or HNSW_LATE_SUM_SQ.
+ * THE LATE INTERACTION of one query:
+ *   - presence, the incoming statuses, the range and NaN vectors are THE FUSION's rules, word for word: entry j of list t
+ *     is PRESENT iff j < min(counts_in[t], pool), or, without counts, iff its id is not UINT32_MAX; the first incoming
+ *     status that is not HNSW_OK fails the query with that status; otherwise a present id at or beyond the index length
+ *     gives HNSW_ERR_ARG, and no stored row is read for the query; otherwise a NaN element in any vector gives
+ *     HNSW_ERR_NAN_INPUT.  A failed query has count 0, n_docs 0 and padded rows;
+ *   - the candidate set C is the DISTINCT present ids over all T lists;
+ *   - lab(c) is the handle's label of c as of the call: 0 at or beyond the column's length, and 0 everywhere on a handle
+ *     that never had a label set (which makes one document);
+ *   - the documents are the distinct labels over C; n_docs is their number, doc_size(g) the number of c in C with
+ *     lab(c) == g;
+ *   - D_t(c), for every t < T and every c in C, is the bits of hnsw_distance_batch(h, q_t, {c}), as in THE FUSION (an 8-bit
+ *     query is quantised as any query is; under the metric_cosine option the vector is normalised once from the caller's
+ *     raw row).  The lists' own distances are not an input;
+ *   - the per-vector minimum m_t(g) starts at +inf and becomes D_t(c) wherever D_t(c) < m_t(g) under f32 <, over the c of
+ *     document g (a NaN leaves it as it is): a minimum, so the order of the c does not matter;
+ *   - the fold: e_t = m_t(g) under HNSW_LATE_SUM, e_t = m_t(g) * m_t(g), one f32 multiply, under HNSW_LATE_SUM_SQ; s = e_0,
+ *     then s = s + e_t for t = 1 .. T-1 in vector order, each operation rounded separately and never contracted.  On
+ *     unit-length rows (what the cosine option gives) SUM_SQ is 2T - 2 * sum_t max_c cos(q_t, c): exactly MaxSim's
+ *     ranking.  SUM is the Chamfer distance in the index's own metric;
+ *   - best(g) is the c of document g with the smallest (bits of D_t(c), c) over all t and all c of g, NaN distances left
+ *     out; UINT32_MAX if there is none.  It is the row a caller shows as the hit;
+ *   - a document whose score is NaN is never returned; the others are ranked by (score under f32 <, -0 == +0; then label
+ *     ascending).
+ * Per query: doc_labels [n_out] (pad 0), scores [n_out] (the fold's own bits, pad +inf), best_ids [n_out] (optional, pad
+ * UINT32_MAX), doc_sizes [n_out] (optional, pad 0), counts (optional) = entries written, n_docs (optional), stats
+ * (required iff stats_in is given): n_dist, n_exp and sum_deg the wrapping uint32 sums of the T incoming records, the
+ * status as above.  Every output word is written exactly once.
+ * The documents scored are those with a row in some vector's pool, and a document's minimum runs over its rows IN C, not
+ * over all its stored rows: a row that is in no vector's pool does not lower its document's score, however near it is.
+ * A caller who wants more raises `pool`.
+ *
+ * hnsw_late_interaction_device is THE LATE INTERACTION alone over buffers in HBM, exactly as hnsw_fuse_lists_device is THE
+ * FUSION: the snapshot is brought up to date, the label column's HBM copy as hnsw_group_by_label_device does it; under the
+ * metric_cosine option a stream-ordered unit-length copy of d_Q is made; then ONE launch (the distance seam's kernel in
+ * its late-interaction form, one wave per query) is enqueued on `stream`, which is not synchronised.  Outputs must not
+ * overlap inputs.  The status of a failed query is written to d_stats only.  HNSW_ERR_ARG, decided before the device is
+ * touched: h NULL; a limit violated; a mode other than the two; nq > 2^31 - 1; d_Q, d_ids_in, d_doc_labels or d_scores
+ * NULL; exactly one of d_stats_in / d_stats given.  nq == 0 is HNSW_OK on any handle, whatever else is passed, and
+ * launches nothing; an empty index is HNSW_ERR_EMPTY.
+ *
+ * hnsw_search_batch_late answers host-pointer queries of T vectors each by their n best documents.  By definition the
+ * result is THE LATE INTERACTION, with n_out = n, of the lists that hnsw_search_batch returns for the nq * T rows of Q
+ * taken as one batch with n = pool and ef' = max(ef, pool, 1), on the same handle with the same options.  With nothing
+ * deleted the call stays on the device: Q goes up once (the cosine option's unit copy made once, for the search and the
+ * late interaction), the launch of hnsw_search_batch_device and the re-run loop of its _finish over nq * T queries, one
+ * late-interaction launch, ONE copy of the block [labels | scores | best ids | sizes | counts | n_docs | stats] back.
+ * While ids are deleted the candidates are the host form's and go up before the launch; pool <= 64 is then required.
+ * Per-query errors are inherited: the first is returned with the QUERY named, not the row, and every other row is filled
+ * in.  scores, best_ids, doc_sizes, counts, n_docs and stats may be NULL.  HNSW_ERR_ARG, decided before the device is
+ * touched: the limits violated; a mode other than the two; Q or doc_labels NULL; nq * T > 2^31 - 1.  nq == 0 is HNSW_OK;
+ * an empty index is HNSW_ERR_EMPTY.  hnsw_get_stat: "late_calls" (hnsw_search_batch_late calls answered), "late_launches"
+ * (late interactions launched, hnsw_late_interaction_device's included).
+ * Not provided: completing a document with its rows that are in no pool; a different T per query, or a mask over a
+ * query's vectors; weights per vector; filters other than deletions in the host entry (the primitive chains with the
+ * filtered *_device searches); late interaction over shards; one-query gathered calls; the Rust shim's binding. */
+#define HNSW_LATE_MAX_VECS 32
+#define HNSW_LATE_MAX_CANDS 1024
+#define HNSW_LATE_MAX_DOCS 256
+#define HNSW_LATE_SUM 0
+#define HNSW_LATE_SUM_SQ 1
+int hnsw_late_interaction_device(hnsw_index *h, uint64_t nq, uint32_t n_vecs, uint32_t pool, uint32_t n_out, uint32_t mode,
+                                 const float *d_Q /* nq x n_vecs x dim */, const uint32_t *d_ids_in /* nq x n_vecs x pool */,
+                                 const uint32_t *d_counts_in /* or NULL */, const hnsw_query_stats *d_stats_in /* or NULL */,
+                                 uint32_t *d_doc_labels, float *d_scores /* nq x n_out */, uint32_t *d_best_ids /* or NULL */,
+                                 uint32_t *d_doc_sizes /* or NULL */, uint32_t *d_counts /* or NULL */,
+                                 uint32_t *d_n_docs /* or NULL */, hnsw_query_stats *d_stats /* required iff d_stats_in */,
+                                 void *stream);
+int hnsw_search_batch_late(hnsw_index *h, const float *Q /* nq x n_vecs x dim */, uint64_t nq, uint32_t n_vecs, uint32_t mode,
+                           uint32_t n, uint32_t pool, uint32_t ef, uint32_t *doc_labels /* nq x n */,
+                           float *scores /* or NULL */, uint32_t *best_ids /* or NULL */, uint32_t *doc_sizes /* or NULL */,
+                           uint32_t *counts /* or NULL */, uint32_t *n_docs /* or NULL */,
+                           hnsw_query_stats *stats /* or NULL */);
+
 /* Test seams that mirror the reference's own units:
  * VecBase::dist2many (vectors/src/lib.rs:17-22): the query (quantised like ann_by_vector does,
  * template.rs:313) against stored ids, on the device, exact accumulation order. */
@@ -1111,7 +1195,8 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * hnsw_diversify_device's included); search from stored rows: "from_rows_calls" (hnsw_search_batch_from_rows and
  * _by_id calls answered), "from_rows_compose_launches" (hnsw_compose_rows_device's included), "from_rows_drop_launches"
  * (the drops those calls launched); multi-vector search: "multi_calls" (hnsw_search_batch_multi calls answered),
- * "multi_fuse_launches" (fusions launched, hnsw_fuse_lists_device's included); deletion:
+ * "multi_fuse_launches" (fusions launched, hnsw_fuse_lists_device's included); late-interaction search: "late_calls"
+ * (hnsw_search_batch_late calls answered), "late_launches" (hnsw_late_interaction_device's included); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
