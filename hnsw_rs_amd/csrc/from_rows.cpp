@@ -1,14 +1,10 @@
 // from_rows.cpp -- search from stored rows (include/hnsw_mi355x.h, "search from stored rows"): query rows composed out
 // of stored rows on the device, the sources taken back out of the result lists there, and a search answered from ids and
 // weighted ids.  Host logic only; the compose is hx_distance_kernel's third source form (exact_scan.hip), the drop
-// hx_filt_merge_kernel's fifth (search_filtered.hip).
+// hx_filt_merge_kernel's fifth (search_filtered.hip), the candidate stage between them lists_host.h.
 
-#include <cstring>
-#include <vector>
-
-#include "handle.h"
-#include "search_filtered.h"
-#include "search_host.h"
+#include "lists_host.h"
+#include "rerun.h"
 
 using hx::set_error;
 
@@ -17,10 +13,6 @@ static_assert(HX_DROP_MAX_WIDTH == HNSW_FROM_ROWS_MAX_TERMS, "the drop form's la
 static_assert(HX_RADIUS_MAX_N == HNSW_DROP_MAX_N, "the drop form's list limit is the ABI's");
 
 namespace {
-
-bool per_query_status(int rc) {
-    return rc == HNSW_ERR_NAN_INPUT || rc == HNSW_ERR_NODE_NOT_IN_GRAPH || rc == HNSW_ERR_OVERFLOW;
-}
 
 int check_width(const char *what, uint32_t width) {
     if (width == 0 || width > HNSW_FROM_ROWS_MAX_TERMS) {
@@ -65,22 +57,15 @@ extern "C" {
 
 int hnsw_compose_rows_device(hnsw_index *h, uint64_t nq, uint32_t width, const uint32_t *d_src_ids, const float *d_weights,
                              float *d_Q, int32_t *d_status, void *stream) {
-    if (!h) {
-        set_error("compose rows: null handle");
-        return HNSW_ERR_ARG;
-    }
+    if (int rc = hx::need_handle("compose rows", h)) return rc;
     if (nq == 0) return HNSW_OK;
     if (int rc = check_width("compose rows", width)) return rc;
-    if (nq > 0x7FFFFFFFull) {
-        set_error("compose rows: at most 2^31 - 1 queries");
-        return HNSW_ERR_ARG;
-    }
+    if (int rc = hx::check_nq("compose rows", nq)) return rc;
     if (!d_src_ids || !d_Q) {
         set_error("compose rows: needs the source ids and the query rows");
         return HNSW_ERR_ARG;
     }
-    int rc = hx::check_search_args(h, 0);  // (the rows are a search's queries: the handle has points and a complete build)
-    if (rc != HNSW_OK || (rc = hx::ensure_uploaded(h))) return rc;
+    if (int rc = hx::ready_for_lists(h)) return rc;  // (the rows are a search's queries)
     return compose(h, nq, width, d_src_ids, d_weights, d_Q, d_status, static_cast<hipStream_t>(stream));
 }
 
@@ -94,18 +79,12 @@ int hnsw_drop_ids_device(uint64_t nq, uint32_t n_in, uint32_t n_out, uint32_t wi
         return HNSW_ERR_ARG;
     }
     if (int rc = check_width("drop ids", width)) return rc;
-    if (nq > 0x7FFFFFFFull) {
-        set_error("drop ids: at most 2^31 - 1 queries");
-        return HNSW_ERR_ARG;
-    }
+    if (int rc = hx::check_nq("drop ids", nq)) return rc;
     if (!d_ex || !d_ids_in || !d_dists_in || !d_ids || !d_dists) {
         set_error("drop ids: needs the exclusion ids, the candidates' ids and distances and the id and distance outputs");
         return HNSW_ERR_ARG;
     }
-    if ((d_stats_in != nullptr) != (d_stats != nullptr)) {
-        set_error("drop ids: the stats output goes with the candidates' stats, both or neither");
-        return HNSW_ERR_ARG;
-    }
+    if (int rc = hx::check_stats_pair("drop ids", "candidates'", d_stats_in, d_stats)) return rc;
     return drop(nq, n_in, n_out, width, d_ex, d_src_status, d_ids_in, d_dists_in, d_counts_in, d_stats_in, d_ids, d_dists,
                 d_counts, d_dropped, d_stats, static_cast<hipStream_t>(stream));
 }
@@ -149,59 +128,51 @@ int hnsw_search_batch_from_rows(hnsw_index *h, const uint32_t *src_ids, const fl
             return HNSW_ERR_ARG;
         }
     }
-    const uint64_t dim = h->dev.replica ? h->dev.view.dim : h->host->dim;
-    // device arena: [source ids [nq][width] | weights | query rows [nq][dim] | candidate block (nq, n_cand) | result block
-    // (nq, n)]; without the drop the search writes the result block itself.  The result block comes back in one copy.
+    if ((rc = hx::ensure_uploaded(h))) return rc;
+    const hx::DevView &v = h->dev.view;
+    // device arena: [source ids [nq][width] | weights | query rows [nq][dim] | re-run selection | candidate block (nq,
+    // n_cand) | result block (nq, n)]; without the drop the search writes the result block itself.  Pinned arena: [the
+    // candidates' stats | result block]
     const hx::ResultBlock cand(nq, n_cand), out(nq, n);
     const size_t o_src = 0, o_w = o_src + hx::align256(nq * width * 4), o_q = o_w + hx::align256(nq * width * 4);
-    const size_t o_cand = o_q + hx::align256(nq * dim * 4), o_out = exclude ? o_cand + cand.bytes : o_cand;
-    if ((rc = hx::ensure_uploaded(h))) return rc;
+    const size_t o_resel = o_q + hx::align256(nq * v.dim * 4), o_cand = o_resel + hx::align256(nq * 4);
+    const size_t o_out = exclude ? o_cand + cand.bytes : o_cand, p_out = hx::align256(nq * sizeof(hnsw_query_stats));
     hx::ScratchLease lease(h);
-    if ((rc = lease.prepare(h->dev.device, o_out + out.bytes, out.bytes))) return rc;
+    if ((rc = lease.prepare(h->dev.device, o_out + out.bytes, p_out + out.bytes))) return rc;
     hx::SearchScratch &sc = *lease.s;
-    unsigned char *dv = static_cast<unsigned char *>(sc.dev);
-    uint32_t *d_src = reinterpret_cast<uint32_t *>(dv + o_src);
-    float *d_w = weights ? reinterpret_cast<float *>(dv + o_w) : nullptr, *d_Q = reinterpret_cast<float *>(dv + o_q);
+    unsigned char *dv = static_cast<unsigned char *>(sc.dev), *hv = static_cast<unsigned char *>(sc.pin);
+    uint32_t *d_src = hx::at<uint32_t>(dv, o_src);
+    float *d_w = weights ? hx::at<float>(dv, o_w) : nullptr, *d_Q = hx::at<float>(dv, o_q);
     const hx::ResultBlock::Ptrs c = cand.at(dv + o_cand), o = out.at(dv + o_out);
     HIP_TRY(hipMemcpyAsync(d_src, src_ids, nq * width * 4, hipMemcpyHostToDevice, sc.stream));
     if (weights) HIP_TRY(hipMemcpyAsync(d_w, weights, nq * width * 4, hipMemcpyHostToDevice, sc.stream));
     if ((rc = compose(h, nq, width, d_src, d_w, d_Q, nullptr, sc.stream))) return rc;
-    // The candidates.  While ids are deleted they are the HOST form's, over the composed rows copied back: only it lets
-    // the planner choose the exact path, and the call is defined by it (as diverse.cpp)
-    std::vector<float> h_Q, h_dists;
-    std::vector<uint32_t> h_ids, h_counts;
-    std::vector<hnsw_query_stats> h_stats;
+    std::vector<float> h_Q;
+    hx::HostLists lists;
     if (host_form) {
-        h_Q.resize(nq * dim), h_ids.resize(nq * n_cand), h_dists.resize(nq * n_cand), h_counts.resize(nq), h_stats.resize(nq);
-        HIP_TRY(hipMemcpyAsync(h_Q.data(), d_Q, nq * dim * 4, hipMemcpyDeviceToHost, sc.stream));
+        // over the composed rows copied back, RAW: hnsw_search_batch makes their unit-length copy itself, and a row
+        // normalised twice is not the row normalised once
+        h_Q.resize(nq * v.dim);
+        HIP_TRY(hipMemcpyAsync(h_Q.data(), d_Q, nq * v.dim * 4, hipMemcpyDeviceToHost, sc.stream));
         HIP_TRY(hipStreamSynchronize(sc.stream));
-        rc = hnsw_search_batch(h, h_Q.data(), nq, n_cand, ef, h_ids.data(), h_dists.data(), h_counts.data(), h_stats.data());
-        if (rc != HNSW_OK && !per_query_status(rc)) return rc;
-        // (the host vectors outlive the copies: the stream is synchronised below)
-        HIP_TRY(hipMemcpyAsync(c.ids, h_ids.data(), nq * n_cand * 4, hipMemcpyHostToDevice, sc.stream));
-        HIP_TRY(hipMemcpyAsync(c.dists, h_dists.data(), nq * n_cand * 4, hipMemcpyHostToDevice, sc.stream));
-        HIP_TRY(hipMemcpyAsync(c.counts, h_counts.data(), nq * 4, hipMemcpyHostToDevice, sc.stream));
-        HIP_TRY(hipMemcpyAsync(c.stats, h_stats.data(), nq * sizeof(hnsw_query_stats), hipMemcpyHostToDevice, sc.stream));
-    } else {  // as a caller of the device entry point would run it: launch, then _finish
-        rc = hnsw_search_batch_device(h, d_Q, nq, n_cand, ef, c.ids, c.dists, c.counts, c.stats, sc.stream);
-        if (rc != HNSW_OK) return rc;
-        rc = hnsw_search_batch_device_finish(h, d_Q, nq, n_cand, ef, c.ids, c.dists, c.counts, c.stats, sc.stream);
-        if (rc != HNSW_OK && !per_query_status(rc)) return rc;
+        if ((rc = hx::host_candidates(h, h_Q.data(), nq, n_cand, ef, {}, lists))) return rc;
+        rc = hx::upload(lists, c, sc.stream, true);
+    } else {  // the composed rows to unit length in place under the cosine option: nothing else reads them
+        if ((rc = hx::cosine_queries(h, d_Q, nq, sc.stream))) return rc;
+        rc = hx::device_candidates(v, d_Q, nq, n_cand, ef, nullptr, 0, c, hx::at<uint32_t>(dv, o_resel), sc.stream, hv);
     }
+    if (rc != HNSW_OK) return rc;
     if (exclude) {
         rc = drop(nq, n_cand, n, width, d_src, nullptr, c.ids, c.dists, c.counts, c.stats, o.ids, o.dists, o.counts, nullptr,
                   o.stats, sc.stream);
         if (rc != HNSW_OK) return rc;
         h->n_from_rows_drop.fetch_add(1, std::memory_order_relaxed);
     }
-    HIP_TRY(hipMemcpyAsync(sc.pin, dv + o_out, out.bytes, hipMemcpyDeviceToHost, sc.stream));
+    HIP_TRY(hipMemcpyAsync(hv + p_out, dv + o_out, out.bytes, hipMemcpyDeviceToHost, sc.stream));
     HIP_TRY(hipStreamSynchronize(sc.stream));
     h->n_from_rows_calls.fetch_add(1, std::memory_order_relaxed);
-    out.copy_out(sc.pin, ids, dists, counts, stats);
-    const hnsw_query_stats *st = out.at(sc.pin).stats;
-    for (uint64_t i = 0; i < nq; i++)
-        if (st[i].status != HNSW_OK) return hx::query_status_error(i, st[i].status);
-    return HNSW_OK;
+    out.copy_out(hv + p_out, ids, dists, counts, stats);
+    return hx::first_query_error(out.at(hv + p_out).stats, nq);
 }
 
 int hnsw_search_batch_by_id(hnsw_index *h, const uint32_t *src_ids, uint64_t nq, uint32_t n, uint32_t ef, int exclude_self,

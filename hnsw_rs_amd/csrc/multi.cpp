@@ -1,15 +1,10 @@
 // multi.cpp -- multi-vector search (include/hnsw_mi355x.h, "multi-vector search"): the fusion of a query's per-vector
 // candidate lists on the device, and a search answered from several vectors per query.  Host logic only; the fusion is
-// hx_distance_kernel's fourth source form (exact_scan.hip).
+// hx_distance_kernel's fourth source form (exact_scan.hip), the candidate stage around it lists_host.h.
 
 #include <algorithm>
-#include <cstring>
-#include <vector>
 
-#include "handle.h"
-#include "rerun.h"
-#include "search_filtered.h"
-#include "search_host.h"
+#include "lists_host.h"
 
 using hx::set_error;
 
@@ -17,10 +12,6 @@ static_assert(HX_MULTI_MAX_VECS == HNSW_MULTI_MAX_VECS, "the kernel's vector lim
 static_assert(HX_DIVERSE_POOL_MAX == HNSW_FUSE_MAX_CANDS, "the kernel's LDS table holds the ABI's candidate limit");
 
 namespace {
-
-bool per_query_status(int rc) {
-    return rc == HNSW_ERR_NAN_INPUT || rc == HNSW_ERR_NODE_NOT_IN_GRAPH || rc == HNSW_ERR_OVERFLOW;
-}
 
 // the limits of the fusion (`what`: the entry point, `n`: its name for the output length, for the text)
 int check_fuse_shape(const char *what, const char *n, uint32_t n_vecs, uint32_t pool, uint32_t n_out, uint32_t mode) {
@@ -38,23 +29,6 @@ int check_fuse_shape(const char *what, const char *n, uint32_t n_vecs, uint32_t 
     }
     return HNSW_OK;
 }
-
-// The fused block of nq queries x n: [ids | scores | counts | unique | stats], the same layout in the device arena and in
-// pinned memory, so it comes back in ONE copy (as DiverseBlock, diverse.cpp).
-struct FusedBlock {
-    size_t ids = 0, scores, counts, unique, stats, bytes;
-    FusedBlock(uint64_t nq, uint32_t n) {
-        scores = ids + hx::align256(nq * n * 4);
-        counts = scores + hx::align256(nq * n * 4);
-        unique = counts + hx::align256(nq * 4);
-        stats = unique + hx::align256(nq * 4);
-        bytes = stats + hx::align256(nq * sizeof(hnsw_query_stats));
-    }
-    template <class T>
-    T *at(void *base, size_t off) const {
-        return reinterpret_cast<T *>(static_cast<unsigned char *>(base) + off);
-    }
-};
 
 // the fusion over lists already in HBM, d_Q as the kernel stages it (unit length under the cosine option): the one launch
 int fuse(hnsw_index *h, uint64_t nq, uint32_t n_vecs, uint32_t pool, uint32_t n_out, uint32_t mode, const float *d_Q,
@@ -90,29 +64,19 @@ int hnsw_fuse_lists_device(hnsw_index *h, uint64_t nq, uint32_t n_vecs, uint32_t
                            const float *d_Q, const float *d_weights, const uint32_t *d_ids_in, const uint32_t *d_counts_in,
                            const hnsw_query_stats *d_stats_in, uint32_t *d_ids, float *d_scores, uint32_t *d_counts,
                            uint32_t *d_unique, hnsw_query_stats *d_stats, void *stream_v) {
-    if (!h) {
-        set_error("fuse lists: null handle");
-        return HNSW_ERR_ARG;
-    }
+    if (int rc = hx::need_handle("fuse lists", h)) return rc;
     if (nq == 0) return HNSW_OK;
     if (int rc = check_fuse_shape("fuse lists", "n_out", n_vecs, pool, n_out, mode)) return rc;
-    if (nq > 0x7FFFFFFFull) {
-        set_error("fuse lists: at most 2^31 - 1 queries");
-        return HNSW_ERR_ARG;
-    }
+    if (int rc = hx::check_nq("fuse lists", nq)) return rc;
     if (!d_Q || !d_ids_in || !d_ids || !d_scores) {
         set_error("fuse lists: needs the vectors, the candidates' ids and the id and score outputs");
         return HNSW_ERR_ARG;
     }
-    if ((d_stats_in != nullptr) != (d_stats != nullptr)) {
-        set_error("fuse lists: the stats output goes with the candidates' stats, both or neither");
-        return HNSW_ERR_ARG;
-    }
-    int rc = hx::check_search_args(h, 0);  // (the lists are a search's: the handle has points and a complete build)
-    if (rc != HNSW_OK || (rc = hx::ensure_uploaded(h))) return rc;
+    if (int rc = hx::check_stats_pair("fuse lists", "candidates'", d_stats_in, d_stats)) return rc;
+    if (int rc = hx::ready_for_lists(h)) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     hx::DeviceQueries dq;  // the caller's vectors are const to us: the unit-length copy under the cosine option
-    if ((rc = dq.prepare(h, d_Q, nq * n_vecs, stream))) return rc;
+    if (int rc = dq.prepare(h, d_Q, nq * n_vecs, stream)) return rc;
     return fuse(h, nq, n_vecs, pool, n_out, mode, dq.q, d_weights, d_ids_in, d_counts_in, d_stats_in, d_ids, d_scores, d_counts,
                 d_unique, d_stats, stream);
 }
@@ -135,73 +99,39 @@ int hnsw_search_batch_multi(hnsw_index *h, const float *Q, uint64_t nq, uint32_t
     }
     const uint64_t rows = nq * n_vecs;  // the vectors, taken as one batch of queries
     const uint32_t efp = std::max(std::max(ef, pool), 1u);
-    // The candidates while ids are deleted are the HOST form's: only it lets the planner choose the exact path, and the
-    // call is defined by it (as diverse.cpp)
-    std::vector<uint32_t> h_ids, h_counts;
-    std::vector<float> h_dists;  // (not an input of the fusion)
-    std::vector<hnsw_query_stats> h_stats;
-    if (host_form) {
-        h_ids.resize(rows * pool), h_dists.resize(rows * pool), h_counts.resize(rows), h_stats.resize(rows);
-        rc = hnsw_search_batch(h, Q, rows, pool, efp, h_ids.data(), h_dists.data(), h_counts.data(), h_stats.data());
-        if (rc != HNSW_OK && !per_query_status(rc)) return rc;
-    }
+    hx::HostLists lists;
+    if (host_form && (rc = hx::host_candidates(h, Q, rows, pool, efp, {}, lists))) return rc;
     if ((rc = hx::ensure_uploaded(h))) return rc;
     const hx::DevView &v = h->dev.view;
-    const uint64_t dim = v.dim;
     // device arena: [vectors [rows][dim] | weights [rows] | re-run selection | candidate block (rows, pool) | fused block];
-    // pinned arena: [the candidates' stats | fused block].  The fused block comes back in one copy.
+    // pinned arena: [the candidates' stats | fused block]
     const hx::ResultBlock cand(rows, pool);
-    const FusedBlock out(nq, n);
-    const size_t o_q = 0, o_w = o_q + hx::align256(rows * dim * 4), o_resel = o_w + hx::align256(rows * 4);
+    hx::ColumnBlock out;  // [ids | scores | counts | unique | stats]
+    const size_t c_ids = out.add(nq * n * 4), c_scores = out.add(nq * n * 4), c_counts = out.add(nq * 4);
+    const size_t c_unique = out.add(nq * 4), c_stats = out.add(nq * sizeof(hnsw_query_stats));
+    const size_t o_q = 0, o_w = o_q + hx::align256(rows * v.dim * 4), o_resel = o_w + hx::align256(rows * 4);
     const size_t o_cand = o_resel + hx::align256(rows * 4), o_out = o_cand + cand.bytes;
     const size_t p_out = hx::align256(rows * sizeof(hnsw_query_stats));
     hx::ScratchLease lease(h);
     if ((rc = lease.prepare(h->dev.device, o_out + out.bytes, p_out + out.bytes))) return rc;
     hx::SearchScratch &sc = *lease.s;
     unsigned char *dv = static_cast<unsigned char *>(sc.dev), *hv = static_cast<unsigned char *>(sc.pin);
-    float *d_Q = reinterpret_cast<float *>(dv + o_q), *d_w = weights ? reinterpret_cast<float *>(dv + o_w) : nullptr;
+    float *d_Q = hx::at<float>(dv, o_q), *d_w = weights ? hx::at<float>(dv, o_w) : nullptr;
     const hx::ResultBlock::Ptrs c = cand.at(dv + o_cand);
-    // Q and the weights go up once; the unit-length copy of the cosine option is made once, from the caller's vectors,
-    // and serves the search and the fusion (as radius.cpp)
-    HIP_TRY(hipMemcpyAsync(d_Q, Q, rows * dim * 4, hipMemcpyHostToDevice, sc.stream));
-    if ((rc = hx::cosine_queries(h, d_Q, rows, sc.stream))) return rc;
+    // the one copy of the vectors serves the search AND the fusion
+    if ((rc = hx::queries_up(h, d_Q, Q, rows, sc.stream))) return rc;
     if (weights) HIP_TRY(hipMemcpyAsync(d_w, weights, rows * 4, hipMemcpyHostToDevice, sc.stream));
-    if (host_form) {  // (the host vectors outlive the copies: the stream is synchronised below)
-        HIP_TRY(hipMemcpyAsync(c.ids, h_ids.data(), rows * pool * 4, hipMemcpyHostToDevice, sc.stream));
-        HIP_TRY(hipMemcpyAsync(c.counts, h_counts.data(), rows * 4, hipMemcpyHostToDevice, sc.stream));
-        HIP_TRY(hipMemcpyAsync(c.stats, h_stats.data(), rows * sizeof(hnsw_query_stats), hipMemcpyHostToDevice, sc.stream));
-    } else {  // the launch of hnsw_search_batch_device and the re-run loop of its _finish, over the unit copy made above
-        hx::SearchArgs a = hx::ann_args(v, d_Q, pool, efp, c.ids, c.dists, c.counts, c.stats);
-        const uint32_t slots = hx::default_slots_log2(efp, v.S0);
-        if ((rc = hx::launch_search(v, a, (uint32_t)rows, slots, sc.stream))) return rc;
-        rc = hx::rerun_overflowed(
-            v, hx::launch_search, a, rows, slots, hx::max_slots_log2(efp), reinterpret_cast<uint32_t *>(dv + o_resel), sc.stream,
-            [&](const hnsw_query_stats *&st) -> int {
-                HIP_TRY(hipMemcpyAsync(hv, c.stats, rows * sizeof(hnsw_query_stats), hipMemcpyDeviceToHost, sc.stream));
-                HIP_TRY(hipStreamSynchronize(sc.stream));
-                st = reinterpret_cast<const hnsw_query_stats *>(hv);
-                return HNSW_OK;
-            },
-            nullptr);
-        if (rc != HNSW_OK) return rc;
-    }
-    unsigned char *d_out = dv + o_out;
-    rc = fuse(h, nq, n_vecs, pool, n, mode, d_Q, d_w, c.ids, c.counts, c.stats, out.at<uint32_t>(d_out, out.ids),
-              out.at<float>(d_out, out.scores), out.at<uint32_t>(d_out, out.counts), out.at<uint32_t>(d_out, out.unique),
-              out.at<hnsw_query_stats>(d_out, out.stats), sc.stream);
+    if (host_form)  // (the distances are not an input of the fusion)
+        rc = hx::upload(lists, c, sc.stream, false);
+    else
+        rc = hx::device_candidates(v, d_Q, rows, pool, efp, nullptr, 0, c, hx::at<uint32_t>(dv, o_resel), sc.stream, hv);
     if (rc != HNSW_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(hv + p_out, d_out, out.bytes, hipMemcpyDeviceToHost, sc.stream));
-    HIP_TRY(hipStreamSynchronize(sc.stream));
-    h->n_multi_calls.fetch_add(1, std::memory_order_relaxed);
-    memcpy(ids, out.at<uint32_t>(hv + p_out, out.ids), nq * n * 4);
-    if (scores) memcpy(scores, out.at<float>(hv + p_out, out.scores), nq * n * 4);
-    if (counts) memcpy(counts, out.at<uint32_t>(hv + p_out, out.counts), nq * 4);
-    if (unique) memcpy(unique, out.at<uint32_t>(hv + p_out, out.unique), nq * 4);
-    const hnsw_query_stats *st = out.at<hnsw_query_stats>(hv + p_out, out.stats);
-    if (stats) memcpy(stats, st, nq * sizeof(hnsw_query_stats));
-    for (uint64_t i = 0; i < nq; i++)
-        if (st[i].status != HNSW_OK) return hx::query_status_error(i, st[i].status);
-    return HNSW_OK;
+    unsigned char *d_out = dv + o_out;
+    rc = fuse(h, nq, n_vecs, pool, n, mode, d_Q, d_w, c.ids, c.counts, c.stats, hx::at<uint32_t>(d_out, c_ids),
+              hx::at<float>(d_out, c_scores), hx::at<uint32_t>(d_out, c_counts), hx::at<uint32_t>(d_out, c_unique),
+              hx::at<hnsw_query_stats>(d_out, c_stats), sc.stream);
+    if (rc != HNSW_OK) return rc;
+    return hx::bring_back(out, d_out, hv + p_out, sc.stream, h->n_multi_calls, {ids, scores, counts, unique, stats}, nq);
 }
 
 }  // extern "C"

@@ -1,13 +1,11 @@
 // partition.cpp -- partitioned search (include/hnsw_mi355x.h, "partitioned search"): the top-n merge of per-shard
 // result lists on the device, and S handles on one device answered as one index.  Host logic only; the merge is
-// hx_filt_merge_kernel's shard-list form (search_filtered.hip).
+// hx_filt_merge_kernel's shard-list form (search_filtered.hip), the candidate stage before it lists_host.h.
 
-#include <algorithm>
 #include <cstring>
-#include <vector>
 
-#include "handle.h"
-#include "search_host.h"
+#include "lists_host.h"
+#include "rerun.h"
 
 using hx::set_error;
 
@@ -15,16 +13,23 @@ static_assert(HX_MERGE_MAX_SHARDS == HNSW_MERGE_MAX_SHARDS, "the kernel's id map
 
 namespace {
 
-// base / stride of every shard, by value, into the kernel's arguments (stride NULL: all 1)
-void fill_id_map(hx::MergeLists &m, uint32_t n_shards, const uint32_t *id_base, const uint32_t *id_stride) {
+// the merge of the shards' lists [S][nq][n] already in HBM: the one launch.  base / stride of every shard travel by
+// value in the kernel's arguments (stride NULL: all 1)
+int merge(uint32_t n_shards, uint64_t nq, uint32_t n, const uint32_t *d_ids_in, const float *d_dists_in,
+          const uint32_t *d_counts_in, const hnsw_query_stats *d_stats_in, const uint32_t *id_base, const uint32_t *id_stride,
+          uint32_t *d_ids, float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, hipStream_t stream) {
+    hx::MergeLists m{};
+    m.ids = d_ids_in;
+    m.dists = d_dists_in;
+    m.counts = d_counts_in;
+    m.stats = d_stats_in;
+    m.n_shards = n_shards;
+    m.nq = (uint32_t)nq;
     for (uint32_t s = 0; s < n_shards; s++) {
         m.base[s] = id_base[s];
         m.stride[s] = id_stride ? id_stride[s] : 1u;
     }
-}
-
-bool per_query_status(int rc) {
-    return rc == HNSW_ERR_NAN_INPUT || rc == HNSW_ERR_NODE_NOT_IN_GRAPH || rc == HNSW_ERR_OVERFLOW;
+    return hx::launch_merge_lists(m, n, d_ids, d_dists, d_counts, d_stats, stream);
 }
 
 }  // namespace
@@ -45,19 +50,9 @@ int hnsw_merge_topk_device(uint32_t n_shards, uint64_t nq, uint32_t n, const uin
         set_error("shard merge: needs the shards' ids and distances, their id bases and the id and distance outputs");
         return HNSW_ERR_ARG;
     }
-    if ((d_stats_in != nullptr) != (d_stats != nullptr)) {
-        set_error("shard merge: the stats output goes with the shards' stats, both or neither");
-        return HNSW_ERR_ARG;
-    }
-    hx::MergeLists m{};
-    m.ids = d_ids_in;
-    m.dists = d_dists_in;
-    m.counts = d_counts_in;
-    m.stats = d_stats_in;
-    m.n_shards = n_shards;
-    m.nq = (uint32_t)nq;
-    fill_id_map(m, n_shards, id_base, id_stride);
-    return hx::launch_merge_lists(m, n, d_ids, d_dists, d_counts, d_stats, static_cast<hipStream_t>(stream));
+    if (int rc = hx::check_stats_pair("shard merge", "shards'", d_stats_in, d_stats)) return rc;
+    return merge(n_shards, nq, n, d_ids_in, d_dists_in, d_counts_in, d_stats_in, id_base, id_stride, d_ids, d_dists, d_counts,
+                 d_stats, static_cast<hipStream_t>(stream));
 }
 
 int hnsw_search_batch_shards(hnsw_index *const *shards, uint32_t n_shards, const uint32_t *id_base,
@@ -134,58 +129,40 @@ int hnsw_search_batch_shards(hnsw_index *const *shards, uint32_t n_shards, const
     if (int rc = lease.prepare(h0->dev.device, o_out + out.bytes, out.bytes)) return rc;
     hx::SearchScratch &sc = *lease.s;
     unsigned char *dv = static_cast<unsigned char *>(sc.dev);
-    float *d_Q = reinterpret_cast<float *>(dv + o_q);
-    uint32_t *d_ids_in = reinterpret_cast<uint32_t *>(dv + o_ids), *d_counts_in = reinterpret_cast<uint32_t *>(dv + o_counts);
-    float *d_dists_in = reinterpret_cast<float *>(dv + o_dists);
-    hnsw_query_stats *d_stats_in = reinterpret_cast<hnsw_query_stats *>(dv + o_stats);
+    float *d_Q = hx::at<float>(dv, o_q), *d_dists_in = hx::at<float>(dv, o_dists);
+    uint32_t *d_ids_in = hx::at<uint32_t>(dv, o_ids), *d_counts_in = hx::at<uint32_t>(dv, o_counts);
+    hnsw_query_stats *d_stats_in = hx::at<hnsw_query_stats>(dv, o_stats);
     HIP_TRY(hipMemcpyAsync(d_Q, Q, nq * dim * 4, hipMemcpyHostToDevice, sc.stream));
     // each shard as a caller of its own device entry point would run it: launch, then _finish (overflow re-runs and the
     // cosine option are the shard's).  A per-query error stays in the shard's stats and reaches the merged row; anything
     // else ends the call.  A shard with deleted ids is the exception: its device entry point always walks the graph,
     // while its hnsw_search_batch lets the planner choose ("filter_exact_max"), and the call is defined by the latter --
-    // so such a shard is answered by its host form and its lists go up into its slice
-    std::vector<uint32_t> h_ids, h_counts;
-    std::vector<float> h_dists;
-    std::vector<hnsw_query_stats> h_stats;
+    // so such a shard is answered by its host form and its lists go up into its slice.  (Not device_candidates, which
+    // wants the unit-length queries in place: the shards share one d_Q and each has its own cosine option, so the unit
+    // copy has to stay the shard's own, as its device entry point makes it.)
+    std::vector<hx::HostLists> lists(S);  // one per shard: each outlives its asynchronous copies, until the merge is back
     for (uint64_t s = 0; s < S; s++) {
-        uint32_t *si = d_ids_in + s * nq * n, *scn = d_counts_in + s * nq;
-        float *sd = d_dists_in + s * nq * n;
-        hnsw_query_stats *sst = d_stats_in + s * nq;
+        const hx::ResultBlock::Ptrs c{d_ids_in + s * nq * n, d_dists_in + s * nq * n, d_counts_in + s * nq, d_stats_in + s * nq};
         if (shards[s]->del.count) {
-            h_ids.resize(nq * n), h_dists.resize(nq * n), h_counts.resize(nq), h_stats.resize(nq);
-            int rc = hnsw_search_batch(shards[s], Q, nq, n, ef, h_ids.data(), h_dists.data(), h_counts.data(), h_stats.data());
-            if (rc != HNSW_OK && !per_query_status(rc)) return rc;
-            // (synchronous copies: the host buffers are reused by the next such shard)
-            HIP_TRY(hipMemcpy(si, h_ids.data(), nq * n * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(sd, h_dists.data(), nq * n * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(scn, h_counts.data(), nq * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(sst, h_stats.data(), nq * sizeof(hnsw_query_stats), hipMemcpyHostToDevice));
+            if (int rc = hx::host_candidates(shards[s], Q, nq, n, ef, {}, lists[s])) return rc;
+            if (int rc = hx::upload(lists[s], c, sc.stream, true)) return rc;
             continue;
         }
-        int rc = hnsw_search_batch_device(shards[s], d_Q, nq, n, ef, si, sd, scn, sst, sc.stream);
+        int rc = hnsw_search_batch_device(shards[s], d_Q, nq, n, ef, c.ids, c.dists, c.counts, c.stats, sc.stream);
         if (rc != HNSW_OK) return rc;
-        rc = hnsw_search_batch_device_finish(shards[s], d_Q, nq, n, ef, si, sd, scn, sst, sc.stream);
-        if (rc != HNSW_OK && !per_query_status(rc)) return rc;
+        rc = hnsw_search_batch_device_finish(shards[s], d_Q, nq, n, ef, c.ids, c.dists, c.counts, c.stats, sc.stream);
+        if (rc != HNSW_OK && !hx::per_query_status(rc)) return rc;
     }
     h0->n_shard_calls.fetch_add(1, std::memory_order_relaxed);
-    hx::MergeLists m{};
-    m.ids = d_ids_in;
-    m.dists = d_dists_in;
-    m.counts = d_counts_in;
-    m.stats = d_stats_in;
-    m.n_shards = n_shards;
-    m.nq = (uint32_t)nq;
-    fill_id_map(m, n_shards, id_base, id_stride);
     const hx::ResultBlock::Ptrs o = out.at(dv + o_out);
-    if (int rc = hx::launch_merge_lists(m, n, o.ids, o.dists, o.counts, o.stats, sc.stream)) return rc;
+    if (int rc = merge(n_shards, nq, n, d_ids_in, d_dists_in, d_counts_in, d_stats_in, id_base, id_stride, o.ids, o.dists,
+                       o.counts, o.stats, sc.stream))
+        return rc;
     h0->n_shard_merges.fetch_add(1, std::memory_order_relaxed);
     HIP_TRY(hipMemcpyAsync(sc.pin, dv + o_out, out.bytes, hipMemcpyDeviceToHost, sc.stream));
     HIP_TRY(hipStreamSynchronize(sc.stream));
     out.copy_out(sc.pin, ids, dists, counts, stats);
-    const hnsw_query_stats *st = out.at(sc.pin).stats;
-    for (uint64_t i = 0; i < nq; i++)
-        if (st[i].status != HNSW_OK) return hx::query_status_error(i, st[i].status);
-    return HNSW_OK;
+    return hx::first_query_error(out.at(sc.pin).stats, nq);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// rerun.h -- the re-run loop every search path ends in (search_host.cpp, filter_host.cpp), and the first per-query
-// failure of a call (internal)
+// rerun.h -- the re-run loop every search path ends in (search_host.cpp, filter_host.cpp, lists_host.cpp), and the
+// first per-query failure of a call (internal)
 #pragma once
 
 #include <type_traits>
