@@ -28,7 +28,12 @@
 //     v_accvgpr_read per element), and the pass's uniform branches carry likely / unlikely hints;
 //   - the upper layers (ef = 1, searcher.rs:23-103 degenerates to a greedy walk) keep just the best
 //     key, and the next node's adjacency base (upper_base) is fetched together with the vector rows of
-//     the neighbours, so an expansion is two dependent round trips instead of three.
+//     the neighbours, so an expansion is two dependent round trips instead of three.  The f32 kernels
+//     with lists of one or two registers at d = 100 also request the front of the walk ahead
+//     (WALK_AHEAD): the entry point's upper_base before the query load and its top row in front of its
+//     own chain, so that the first expansion finds its row in a register -- two dependent round trips
+//     in front of it instead of four -- and the row the walk ends on goes to the first layer-0 pass as
+//     a row fetched ahead.
 //
 // Float fidelity: -ffp-contract=off; the sum is FullVec's single left-to-right chain; sqrt is the
 // correctly rounded one.
@@ -728,6 +733,12 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     constexpr bool MISS_AHEAD = !COOP && !SPILLV;
     // ... and where that runner-up is p again, p's lanes keep the distances they hold (lists of at most two registers)
     constexpr bool MISS_KEEP = MISS_AHEAD && R <= 2;
+    // the entry point's upper_base and top row are requested under the query load and the entry point's chain, and
+    // the walk keeps the row it expands next in a register from the moment its address is known; the row it ends on
+    // goes to the first layer-0 pass as a row fetched ahead (upper layers, below).  The d = 128 kernels sit at the
+    // register line and the wide lists hold the second level's state: both keep the walk that loads a row when it
+    // expands it.
+    constexpr bool WALK_AHEAD = !COOP && R <= 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
     const uint32_t q = a.qsel ? a.qsel[blockIdx.x] : blockIdx.x;
@@ -752,6 +763,29 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     uint32_t dbg_pred_c = HX_EMPTY_SLOT, dbg_pred_p = HX_EMPTY_SLOT, dbg_old_p = HX_EMPTY_SLOT;
 #endif
 
+    // WALK_AHEAD: this lane's slot of row `layer` of node id (base = upper_base[id]): lanes 0 .. S1 - 1 on an upper
+    // layer, c's lanes of the layer-0 pass on layer 0; HX_EMPTY_SLOT elsewhere, and on an upper layer for a node
+    // without upper rows (no address is formed from its base; the walk reports the node when it gets there)
+    auto row_ahead = [&](uint32_t id, uint32_t base, int layer) __attribute__((always_inline)) -> uint32_t {
+        // one masked load behind selects (a branch per layer kind cost the lone wave more than the load saves)
+        const bool up = layer >= 1, has = base != HX_EMPTY_SLOT;
+        const size_t r = up ? (size_t)(has ? base : 0u) + (uint32_t)max(layer, 1) - 1 : (size_t)id;
+        const uint32_t *src = (up ? a.adj_up + r * a.S1 : a.adj0 + r * a.S0) + lane;
+        const bool mine = (uint32_t)lane < (up ? (has ? a.S1 : 0u) : min(a.S0, 32u));
+        uint32_t v = HX_EMPTY_SLOT;
+        if (mine) v = *src;
+        return v;
+    };
+    // the entry point's upper_base depends on nothing the query brings: requested first, it lands under the query load
+    uint32_t ub_cur = HX_EMPTY_SLOT;
+    bool have_ub = false;
+    if constexpr (WALK_AHEAD) {
+        if (a.ep < a.n_points) {
+            ub_cur = a.upper_base[a.ep];
+            have_ub = true;
+        }
+    }
+
     QueryRegs<DS> qreg;
     float(&qv)[DS] = qreg.v;
     if (!load_query_f32<DS>(a.Q + (size_t)q * DS, qv, lane)) status = HNSW_ERR_NAN_INPUT;
@@ -769,10 +803,15 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     // ---- entry point (template.rs:316-319) ----
     u64 best = LK_INVALID;
     uint32_t cur = a.ep;
+    // WALK_AHEAD: the row of cur on the layer the walk is on (after the last layer: on layer 0), requested when cur was
+    // chosen or the layer above ended
+    uint32_t row_now = HX_EMPTY_SLOT;
     if (status == HNSW_OK) {
         if (cur >= a.n_points) {
             status = HNSW_ERR_ARG;
         } else {
+            // the entry point's top row lands under its own distance chain
+            if constexpr (WALK_AHEAD) row_now = row_ahead(cur, ub_cur, max((int)a.nb_layers - 1, 0));
             const float d0 = dist_of(cur, lane == 0);
             const uint32_t bits = rdlane(__builtin_bit_cast(uint32_t, d0), 0);
             n_dist = 1;
@@ -783,14 +822,20 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
         }
     }
 
+#ifdef HX_STAMPS
+    dbg_acc[25] = __builtin_readcyclecounter() - t_begin;  // query staging + entry point alone (slot 7 minus this: the walk)
+#endif
     // ---- upper layers, ef = 1 (template.rs:322-324): a greedy walk.  With one slot in `selected`
     // every fresh neighbour below the running best replaces it (searcher.rs:74-94), the next pop is
     // the best found so far, and once an expansion improves nothing the next pop is a leftover above
     // the best and the loop breaks (searcher.rs:41-44).  visited (cleared per layer, searcher.rs:101)
     // only keeps the distance counter honest here. ----
+    // WALK_AHEAD: the first expansion takes the entry point's top row from row_now; an improvement requests the
+    // winner's row and a descent the row of cur one layer down (on layer 1: its layer-0 row, which the first layer-0
+    // pass takes as a row fetched ahead) into the same register.  Requesting the row below a whole expansion before
+    // the descent was measured in three places -- with the winner's row, behind the landed row, in front of the
+    // neighbours' vector rows -- and lost each time ("The front of the query").
     const uint32_t up_slots = max(hslots >> 2, 64u);
-    uint32_t ub_cur = HX_EMPTY_SLOT;
-    bool have_ub = false;
     for (int layer = (int)a.nb_layers - 1; layer >= 1 && status == HNSW_OK; layer--) {
         vis.bshift = 32 - (__ffs((int)up_slots) - 1 - 2);
         vis.bmask = (up_slots >> 2) - 1;
@@ -810,13 +855,16 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             n_exp++;
             bool improved = false;
             uint32_t new_cur = cur, new_ub = ub_cur;
-            const uint32_t *row = a.adj_up + ((size_t)ub_cur + (uint32_t)layer - 1) * a.S1;
             uint32_t ovf_lo = 0, ovf_hi = 0;
             bool first = true;
             while (true) {
                 uint32_t nb = HX_EMPTY_SLOT;
                 if (first) {
-                    if ((uint32_t)lane < a.S1) nb = row[lane];
+                    if constexpr (WALK_AHEAD) {
+                        nb = row_now;
+                    } else {
+                        if ((uint32_t)lane < a.S1) nb = a.adj_up[((size_t)ub_cur + (uint32_t)layer - 1) * a.S1 + lane];
+                    }
                 } else {
                     if (ovf_lo + lane < ovf_hi) nb = a.ovf_nbrs[ovf_lo + lane];
                     ovf_lo += 64;
@@ -881,7 +929,9 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             if (!improved || status != HNSW_OK) break;
             cur = new_cur;
             ub_cur = new_ub;
+            if constexpr (WALK_AHEAD) row_now = row_ahead(cur, ub_cur, layer);
         }
+        if constexpr (WALK_AHEAD) row_now = row_ahead(cur, ub_cur, layer - 1);  // the descent
     }
 
     // ---- layer 0 with ef (template.rs:326) ----
@@ -902,6 +952,12 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
         const uint32_t slot = (uint32_t)lane & 31u;
         // the adjacency rows fetched ahead for the pass after this one (see below)
         uint32_t pre_nb = HX_EMPTY_SLOT, pre_c = HX_EMPTY_SLOT, pre_p = HX_EMPTY_SLOT;
+        if constexpr (WALK_AHEAD) {
+            // the walk requested the layer-0 row of the node it ended on: the first pick (that node, no runner-up)
+            // takes it as it takes any pair of rows requested during the pass before
+            pre_nb = row_now;
+            pre_c = cur;
+        }
         // a missed runner-up that is foreseen as the next pass's runner-up: the distances its lanes hold (MISS_KEEP)
         bool carry = false;
         float kdist = 0.0f;

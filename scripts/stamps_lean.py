@@ -41,6 +41,8 @@ for ef in efs:
         tot.mean(), np.percentile(tot, 50), np.percentile(tot, 90), np.percentile(tot, 99), tot.max(), tot.min(), tot.max() / (ms * 1e6)))
     for i in (7, 0, 1, 2, 3, 8, 9, 5, 10, 4):
         print('   %-45s %9.0f cycles/query %5.1f%%   per pass %7.0f' % (names[i], D[:, i].mean(), 100 * D[:, i].mean() / tot.mean(), D[:, i].mean() / passes.mean()))
+    print('   of slot 7: staging + entry point %.0f cycles/query (the entry point\'s distance is waited for at its end), the walk %.0f' % (
+        D[:, 25].mean(), (D[:, 7] - D[:, 25]).mean()))
     acc = D[:, [0, 1, 2, 3, 5, 7, 8, 9, 10]].sum(1).mean()
     print('   unaccounted %.1f%%' % (100 * (tot.mean() - acc) / tot.mean()))
     print('   per query: visited slow-loop rounds %.1f; merges with 0 / 1-2 / >=3 survivors: %.1f / %.1f / %.1f; p commits %.1f' % (
