@@ -15,8 +15,16 @@ Machine   drives the product and the model through a schedule: product None (the
           on the GPU one drawn search family is then held to the CPU restatements (tests/filtered_restate.py,
           oracle/restate_np.py, the oracle) under the model's predicate, and the upload / recount counters to the model.
 replay    replay(seed, kind, upto) re-runs the first `upto` ops: a failure names its step, the prefix is found by hand.
+composite schedule(..., families="composite") keeps the ops and draws the checks from the search-then-post-process entry
+          points (radius, diverse, from_rows / by_id, multi, late: COMPOSITE_FAMILIES) and two anchors.  A composite check
+          predicts the candidate lists as check_grouped does, passes them through the feature's own restatement
+          (hnsw_rs_amd.radius / diverse / from_rows / multi / late) and holds ids, distance / score / gap bits, counts,
+          stats, the upload counters and the per-feature counters to it (Machine.check_composite).  What its lists go
+          through is noted twice: as the model alone predicts it, and, product "host" or "gpu", as the restated lists show
+          it ("seen:"; the graph is the host's, no GPU is needed for that).
 """
 import collections
+import hashlib
 import os
 import shutil
 import tempfile
@@ -43,6 +51,18 @@ SEARCH_FAMILIES = ("search_batch", "filtered", "multi", "set", "range", "ranges"
 PATH0_FAMILIES = tuple(f for f in SEARCH_FAMILIES if f != "brute_force")
 PATH1_FAMILIES = ("filtered", "multi", "set", "range", "ranges", "set_range", "one", "one_threads", "grouped_range",
                   "grouped_row")
+# the search-then-post-process entry points (lists_host.h) have schedules of their own: schedule(..., families="composite")
+# draws its checks from these and the two anchors, and leaves every draw of the committed schedules where it is
+COMPOSITE_SEEDS, COMPOSITE_STEPS = (11, 12), 150
+COMPOSITE_FAMILIES = ("radius", "diverse", "diverse_range", "diverse_row", "from_rows", "by_id", "multi_vec", "late")
+ANCHORS = ("search_batch", "brute_force")
+FILTERED_COMPOSITES = ("diverse_range", "diverse_row")  # the host form whatever is deleted: their candidates are filtered
+FEATURE_COUNTERS = ("radius_calls", "radius_rungs", "radius_launches", "diverse_calls", "diverse_launches",
+                    "from_rows_calls", "from_rows_compose_launches", "from_rows_drop_launches", "multi_calls",
+                    "multi_fuse_launches", "late_calls", "late_launches")
+HOST_POOLS, DEVICE_POOLS, REFUSED_POOL = (8, 24, 64), (8, 64, 65, 200), 65
+FUSE_MAX_CANDS, LATE_MAX_CANDS = 256, 1024  # (HNSW_FUSE_MAX_CANDS, HNSW_LATE_MAX_CANDS: T * pool of a call)
+SURE = 3  # the model's nearest live rows of a vector, in float64: candidates of its list whatever the graph walk does
 
 
 def words_of(n_bits):
@@ -198,7 +218,13 @@ class Model:
         self.graph_version = 0
         self.seen_zero = False  # deleted_count went to 0 after having been above it
         self.after = None       # "clone" / "load": the next check is the first on the new handle
+        self.inline_rows = -1
+        self.step, self.first = -1, {}  # the step a noted event was first seen at (Machine.run sets `step`)
         self._new_handle(0, 0)
+
+    def note(self, event):
+        self.ev[event] += 1
+        self.first.setdefault(event, self.step)
 
     @property
     def len(self):
@@ -211,6 +237,8 @@ class Model:
         self.del_version, self.lab_version = 1, 1
         self.sort = Cache("sort", ("version", "del", "len"), self.ev)
         self.snap_valid = False
+        self.patched = set()      # ids insert_vec patched into the live snapshot since the last whole upload
+        self.lab_changed = set()  # ids whose label changed since the label column last went to HBM
 
     # ---- mutating ops ----
     def insert(self, vecs, levels):
@@ -227,7 +255,10 @@ class Model:
 
     def insert_vec(self, vecs, levels):
         """-> the point patches the inserts make (one each while the snapshot is live)"""
+        before = self.len
         self.insert(vecs, levels)
+        if self.snap_valid:
+            self.patched.update(range(before, self.len))
         return len(levels) if self.snap_valid else 0
 
     def insert_bulk(self, vecs, levels):
@@ -261,6 +292,7 @@ class Model:
                 self.labels[i] = v
                 self.lab_version += 1
                 self.lab_copy.touch(int(i) >> 1)
+                self.lab_changed.add(int(i))
                 changed = True
         if not changed:
             self.ev["noop:lab"] += 1
@@ -277,6 +309,7 @@ class Model:
         elif key == "mask_set_cache_mb":
             self.cache_mb = value
         elif key == "inline_rows":
+            self.inline_rows = value
             self.snap_valid = False  # (the snapshot is released and rebuilt by the next search)
 
     def clone(self):
@@ -290,7 +323,7 @@ class Model:
         """... on the loaded handle: the file `deleted` gives words for every id when an id is deleted, none otherwise;
         the options are the defaults"""
         self._new_handle(words_of(self.len) if self.deleted.any() else 0, 0)
-        self.exact_max, self.cache_mb = DEFAULT_EXACT_MAX, DEFAULT_CACHE_MB
+        self.exact_max, self.cache_mb, self.inline_rows = DEFAULT_EXACT_MAX, DEFAULT_CACHE_MB, -1
         self._remake_sets()
         self.after = "load"
 
@@ -302,6 +335,7 @@ class Model:
         if self.snap_valid:
             return 0
         self.snap_valid = True
+        self.patched.clear()
         return 1
 
     def sync_deleted(self):
@@ -311,6 +345,7 @@ class Model:
 
     def sync_labels(self):
         self.lab_nw = max(self.lab_nw, (self.len + 1) // 2)  # (the mirror covers every id of the index)
+        self.lab_changed.clear()
         return self.lab_copy.sync(self.lab_nw, self.lab_nw // 8 + 16)
 
     def sort_for(self):
@@ -406,6 +441,22 @@ class Model:
         """hnsw_count_labels_in_ranges: the planner's count, over its sorted copy"""
         self.sort_for()
         return int((self.in_ranges(members) & self.live()).sum())
+
+    def dist64(self, q, cosine=False):
+        """the distances of a vector to every row, in float64 from the model's own vectors (under the cosine option:
+        between the unit vectors)"""
+        rows, q = self.vecs.astype(np.float64), np.asarray(q, dtype=np.float64)
+        if cosine:
+            rows = rows / np.maximum(np.linalg.norm(rows, axis=1), 1e-300)[:, None]
+            q = q / max(np.linalg.norm(q), 1e-300)
+        return np.sqrt(((rows - q[None, :]) ** 2).sum(axis=1))
+
+    def nearest(self, q, k, adm=None, cosine=False):
+        """the k nearest admissible (None: live) ids of a vector by dist64, ascending"""
+        adm = self.live() if adm is None else adm
+        ids = np.flatnonzero(adm)
+        d = self.dist64(q, cosine)[ids]
+        return ids[np.argsort(d, kind="stable")[:k]]
 
 
 # ---- the schedule -----------------------------------------------------------------------------------------------
@@ -505,19 +556,175 @@ def draw_set_bits(rng, L, allow_bits):
     return bits
 
 
-def schedule(seed, kind, steps=STEPS, cosine=False):
+def draw_multi_vectors(rng, m, cosine, nq, T, recent):
+    """[nq, T, d]: draw_queries per query; sometimes one vector twice in a query (its two lists hold the same ids),
+    sometimes a stored row as a vector (often one that insert_vec appended lately)"""
+    Q = np.stack([draw_queries(rng, m, T, cosine) for _ in range(nq)])
+    for q in range(nq):
+        if T > 1 and rng.random() < 0.4:
+            Q[q, 1] = Q[q, 0]
+        if rng.random() < 0.5:
+            i = recent[int(rng.integers(len(recent)))] if recent and rng.random() < 0.7 else int(rng.integers(m.len))
+            Q[q, T - 1] = m.vecs[i]
+    return np.ascontiguousarray(Q, dtype=np.float32)
+
+
+def draw_sources(rng, m, nq, width, recent):
+    """[nq, width] source ids: old rows, rows inserted during the run (often one that insert_vec appended lately), the id
+    len - 1 and absent slots; no query with every slot absent"""
+    src = np.full((nq, width), MAX, dtype=np.uint32)
+    for q in range(nq):
+        for s in range(width):
+            k = rng.random()
+            if k < 0.15:
+                continue
+            if k < 0.4:
+                src[q, s] = int(rng.integers(min(m.len, N0)))
+            elif k < 0.75 and recent:
+                src[q, s] = recent[int(rng.integers(len(recent)))]
+            elif k < 0.85:
+                src[q, s] = m.len - 1
+            else:
+                src[q, s] = int(rng.integers(m.len))
+        if (src[q] == MAX).all():
+            src[q, int(rng.integers(width))] = m.len - 1
+    return src
+
+
+def draw_radii(rng, m, cosine, c, turn):
+    """the radii of a radius check, from the model alone (Model.dist64): a scalar that no row lies within (the queries
+    are then fresh vectors, none of them a stored row), per query twice the distance of its j-th nearest live row (the
+    nearest few lie within whatever f32 or the 8-bit codes round), +inf, or one of the three per query"""
+    nq = c["Q"].shape[0]
+    kind = ("none", "few", "inf", "mixed")[turn % 4]
+    if kind == "none":
+        c["Q"] = draw_vectors(rng, nq, m.d, cosine)
+    live = m.live()
+    near = [np.sort(m.dist64(q, cosine)[live])[:4] for q in c["Q"]]
+    if kind == "none":
+        c["radius"] = float(np.float32(0.5 * min(d[0] for d in near)))
+    elif kind == "inf":
+        c["radius"] = float("inf")
+    else:
+        r = np.zeros(nq, dtype=np.float32)
+        for q in range(nq):
+            k = "few" if kind == "few" else ("none", "few", "inf")[int(rng.integers(3))]
+            j = int(rng.choice([1, 2, 4]))
+            r[q] = np.inf if k == "inf" else 0.5 * near[q][0] if k == "none" else 2.0 * near[q][min(j, len(near[q])) - 1]
+        c["radius"] = r
+    c["radius_kind"] = kind
+
+
+def draw_composite_check(rng, m, cosine, used, recent, hint=None, family=None, anchors=True):
+    """the check after an op of a composite schedule: one of COMPOSITE_FAMILIES or an anchor, the least drawn (in the
+    state: ids deleted or none) first.  While the call takes the host form -- ids are deleted, or the family brings a
+    filter -- a family's draws take turns: filter_exact_max -1 (the graph path), beyond every count (the exact path), a
+    REFUSED call at the host form's limit + 1, a drawn filter_exact_max"""
+    deleted = bool(m.deleted.any())
+    state = "del" if deleted else "nodel"
+    fams = list(COMPOSITE_FAMILIES) + (list(ANCHORS) if anchors else [])
+    if not m.sets:
+        fams.remove("diverse_row")
+    if family is None:
+        least = min(used[f, state] for f in fams)
+        fams = [f for f in fams if used[f, state] == least]
+        family = fams[int(rng.integers(len(fams)))]
+    used[family, state] += 1
+    if family in ANCHORS:
+        return draw_check(rng, m, cosine, family, used["anchors"])
+    host_form = deleted or family in FILTERED_COMPOSITES
+    turn = used[family, "turn", host_form]
+    used[family, "turn", host_form] += 1
+    c = {"family": family}
+    live = int(m.live().sum())
+    c["ef"] = int(rng.choice([8, 32, 64, 200]))
+    c["exact_max"] = (-1, HUGE, -1, int(rng.integers(10, max(11, live // 2))))[turn % 4] if host_form else -1
+    refused = host_form and turn % 4 == 2
+    if refused:
+        c["refused"] = True
+    pool = REFUSED_POOL if refused else int(rng.choice(HOST_POOLS if host_form else DEVICE_POOLS))
+    if family in ("multi_vec", "late"):
+        nq = int(rng.integers(2, 4))
+        T = int(rng.choice([1, 2, 3] if refused else [1, 2, 3, 5]))
+        limit = FUSE_MAX_CANDS if family == "multi_vec" else LATE_MAX_CANDS
+        if not refused:
+            pool = int(rng.choice([p for p in (HOST_POOLS if host_form else DEVICE_POOLS) if T * p <= limit]))
+        c["Q"] = draw_multi_vectors(rng, m, cosine, nq, T, recent)
+        c["mode"] = int(rng.integers(2))
+        c["n"] = int(rng.integers(1, min(pool, 10) + 1))
+        if family == "multi_vec" and rng.random() < 0.6:
+            c["weights"] = (rng.random((nq, T), dtype=np.float32) * np.float32(2.0) + np.float32(0.25)).astype(np.float32)
+    elif family in ("from_rows", "by_id"):
+        nq = int(rng.integers(3, 6))
+        width = 1 if family == "by_id" else int(rng.choice([1, 3, 8]))
+        c["src"] = draw_sources(rng, m, nq, width, recent)
+        c["n"] = max(pool - width, 1)  # (the call's limit is on n + width)
+        c["exclude"] = bool(rng.random() < 0.5)
+        if family == "from_rows" and rng.random() < 0.6:
+            c["weights"] = ((rng.random((nq, width), dtype=np.float32) - np.float32(0.25)) * np.float32(2.0)).astype(np.float32)
+        if refused:
+            c["n"] = REFUSED_POOL - width
+    else:
+        nq = int(rng.integers(3, 6))
+        c["Q"] = draw_queries(rng, m, nq, cosine)
+    c["pool"] = pool
+    if family == "radius":
+        c["n_first"] = int(rng.choice([f for f in (1, 4, 16) if f <= pool]))
+        draw_radii(rng, m, cosine, c, turn)
+    if family.startswith("diverse"):
+        c["n"] = int(rng.integers(1, min(pool, 10) + 1))
+        c["lam"] = float(rng.choice([0.0, 0.3, 0.5, 1.0]))
+    if family == "diverse_row":
+        name = hint[0] if hint and hint[0] in m.sets else sorted(m.sets)[int(rng.integers(len(m.sets)))]
+        c["set"] = name
+        c["keys"] = [int(x) for x in rng.choice(list(range(m.sets[name].G)) + [NONE], nq)]
+    if family == "diverse_range" or (family == "diverse_row" and rng.random() < 0.3):
+        c["ranges"] = [[draw_range(rng)] for _ in range(nq)]
+    return c
+
+
+def schedule(seed, kind, steps=None, cosine=False, families="default"):
     """-> the ops of a run, each {"op": ..., its arguments, "check": the check that follows it}.  (`kind` does not change
-    the draws: both vector kinds run the same ops.)"""
+    the draws: both vector kinds run the same ops.)  families "default": the committed schedules (SEEDS, STEPS), whose
+    draws tests/test_update_machine_host.py pins by a digest.  "composite": the same ops, weights and forced events, the
+    checks drawn by draw_composite_check, and two more forced events: every id unmarked and then QUIET ops that mark
+    nothing (the composite calls take their device form on a handle that has held deletions), with inline_rows set to 1
+    between two composite checks of that stretch; and the check after the clone and after the save / load is one of
+    every family, the anchors included, in turn ("more")."""
+    composite = families == "composite"
+    assert composite or families == "default", families
+    steps = (COMPOSITE_STEPS if composite else STEPS) if steps is None else steps
     rng = np.random.default_rng([int(seed), 0x5EED])
     m = Model(D)
     ops = []
 
     used = collections.Counter()
+    if composite:
+        used = collections.defaultdict(int)
+        used["anchors"] = collections.Counter()
+    recent = []  # (composite) the ids insert_vec appended since the snapshot was last made whole
 
     def emit(op, family=None, hint=None):
         apply_op(m, op)
-        op["check"] = draw_check(rng, m, cosine, family, used, hint)
+        if not composite:
+            op["check"] = draw_check(rng, m, cosine, family, used, hint)
+        else:
+            o = op["op"]
+            if o == "insert_vec":
+                recent.extend(range(m.len - len(op["levels"]), m.len))
+            elif o in ("insert_bulk", "clone", "save_load") or (o == "option" and op["key"] == "inline_rows"):
+                del recent[:]
+            if o in ("clone", "save_load"):
+                fams = [f for f in COMPOSITE_FAMILIES + ANCHORS if m.sets or f != "diverse_row"]
+                k = (int(seed) + (o == "save_load")) % len(fams)
+                cs = [draw_composite_check(rng, m, cosine, used, recent, family=f) for f in fams[k:] + fams[:k]]
+                op["check"] = dict(cs[0], more=cs[1:])
+            else:
+                op["check"] = draw_composite_check(rng, m, cosine, used, recent, hint, anchors=not quiet["composite_only"])
         ops.append(op)
+
+    QUIET = 17  # ops after the unmark of everything that mark nothing
+    quiet = {"start": None, "flipped": False, "inserts": 0, "composite_only": False}
 
     emit({"op": "insert_bulk", "vecs": draw_vectors(rng, N0, D, cosine), "levels": draw_levels(rng, N0)})
     emit({"op": "set_create", "name": "A", "bits": draw_set_bits(rng, m.len, m.len + 24)})  # above len: passed by inserts
@@ -531,13 +738,41 @@ def schedule(seed, kind, steps=STEPS, cosine=False):
     names, p = list(weights), np.array(list(weights.values()), dtype=np.float64)
     p /= p.sum()
     last_labelled = N0
+    if composite:
+        forced.insert(3, (int(steps * 0.47), "quiet"))
     while len(ops) < steps:
-        what = forced.pop(0)[1] if forced and len(ops) >= forced[0][0] else names[int(rng.choice(len(names), p=p))]
+        in_quiet = quiet["start"] is not None and len(ops) - quiet["start"] < QUIET
+        if in_quiet:
+            # nothing is marked; after five ops inline_rows is set to 1 between two composite checks, and two inserts follow
+            # it, patched into the snapshot that the check after the flip made
+            pos = len(ops) - quiet["start"]
+            quiet["composite_only"] = pos >= 2 and not quiet["flipped"]  # (an op may bring two checks: from 2 on)
+            if pos >= 5 and not quiet["flipped"]:
+                what = "inline_on"
+            elif quiet["flipped"] and quiet["inserts"] < 2:
+                what = "insert_vec"
+                quiet["inserts"] += 1
+            else:
+                what = names[int(rng.choice(len(names), p=p))]
+                if "mark" in what or what == "inline_rows":
+                    continue
+        else:
+            quiet["composite_only"] = False
+            what = forced.pop(0)[1] if forced and len(ops) >= forced[0][0] else names[int(rng.choice(len(names), p=p))]
         L = m.len
         dele = np.flatnonzero(m.deleted)
         if what.startswith("mark") and dele.size > L // 4:
             continue  # (most ids stay live)
-        if what == "insert_vec":
+        if composite and what in ("clone", "save_load") and not m.sets:  # (diverse_row is among the checks that follow)
+            emit({"op": "set_create", "name": "A", "bits": draw_set_bits(rng, L, L + 24)})
+        if what == "quiet":
+            if dele.size:
+                emit({"op": "unmark", "ids": dele})
+            quiet["start"] = len(ops)
+        elif what == "inline_on":
+            emit({"op": "option", "key": "inline_rows", "value": 1})
+            quiet["flipped"] = True
+        elif what == "insert_vec":
             k = int(rng.integers(1, 9))
             emit({"op": "insert_vec", "vecs": draw_vectors(rng, k, D, cosine), "levels": draw_levels(rng, k)})
         elif what == "grow_within":
@@ -697,6 +932,35 @@ def describe(op):
     return " ".join(out)
 
 
+def _canon(v, h):
+    if isinstance(v, dict):
+        h.update(b"{")
+        for k in sorted(v):
+            h.update(str(k).encode())
+            _canon(v[k], h)
+        h.update(b"}")
+    elif isinstance(v, np.ndarray):
+        h.update(("%s%s" % (v.dtype.str, list(v.shape))).encode())
+        h.update(np.ascontiguousarray(v).tobytes())
+    elif isinstance(v, (list, tuple)):
+        h.update(b"[")
+        for x in v:
+            _canon(x, h)
+        h.update(b"]")
+    else:
+        h.update(repr(v.item() if isinstance(v, np.generic) else v).encode())
+
+
+def digest(ops):
+    """sha256 over describe(op), the check (every key, arrays by their bytes) and the query bytes of every op of a schedule"""
+    h = hashlib.sha256()
+    for op in ops:
+        h.update(describe(op).encode())
+        _canon(op["check"], h)
+        h.update(np.ascontiguousarray(op["check"].get("Q", np.zeros(0, dtype=np.float32))).tobytes())
+    return h.hexdigest()
+
+
 # ---- the machine ------------------------------------------------------------------------------------------------
 def unit(x):
     """rows / their norm, the sum of squares taken in order in float32 (as the library normalises under cosine)"""
@@ -708,9 +972,13 @@ def unit(x):
 
 
 class Machine:
-    def __init__(self, seed, kind, product=None, steps=STEPS, cosine=False):
+    def __init__(self, seed, kind, product=None, steps=None, cosine=False, families="default"):
         self.seed, self.kind, self.product, self.cosine = seed, kind, product, cosine
-        self.ops = schedule(seed, kind, steps, cosine)
+        self.ops = schedule(seed, kind, steps, cosine, families)
+        self.n_expected = sum(1 + len(op["check"].get("more", ())) for op in self.ops)
+        # what the composite restatements read of the model, changed on purpose by the sensitivity tests alone
+        # (tests/test_gpu_update_machine.py): id -> label, id -> (component, ulps)
+        self.tamper_labels, self.tamper_rows = {}, {}
         self.m = Model(D)
         self.index, self.sets = None, {}
         self.step, self.family, self.qi = -1, None, None
@@ -724,11 +992,16 @@ class Machine:
         try:
             for self.step, op in enumerate(self.ops[: upto]):
                 self.family, self.qi = None, None
+                self.m.step = self.step
                 try:
                     self.apply(op)
                     self.check_host_state()
-                    self.family = op["check"]["family"]
-                    self.check(op["check"])
+                    after = self.m.after
+                    for c in [op["check"]] + list(op["check"].get("more", ())):
+                        self.family, self.qi = c["family"], None
+                        if after:
+                            self.m.note("check_after:%s:%s" % (after, self.family))
+                        self.check(c)
                 except AssertionError as e:
                     raise AssertionError("seed %d kind %d step %d op [%s] check family %s query %s: %s" % (
                         self.seed, self.kind, self.step, describe(op), self.family, self.qi, e)) from e
@@ -915,6 +1188,13 @@ class Machine:
         fam = c["family"]
         if fam in HOST_FAMILIES:
             return self.check_host_family(c)
+        if fam in ANCHORS:
+            m.note("state:%s:%s" % (fam, "del" if m.deleted.any() else "nodel"))
+        if fam in COMPOSITE_FAMILIES:
+            if self.product == "gpu":
+                self.index.set_option("filter_exact_max", c["exact_max"])
+            m.option("filter_exact_max", c["exact_max"])
+            return self.check_composite(c)
         nq = c["Q"].shape[0]
         setname, keys, ranges, masks = c.get("set"), c.get("keys"), c.get("ranges"), c.get("masks")
         exact_max = c["exact_max"]
@@ -1112,6 +1392,297 @@ class Machine:
         want = group_by_label(c_ids, c_d, c_n, self.m.labels, G, P)
         GC.assert_grouped_equal(got, want, c["family"])
 
+    # ---- the search-then-post-process entry points (lists_host.h) ----
+    def feature_stats(self):
+        return {k: self.index.stat(k) for k in FEATURE_COUNTERS}
+
+    def expect_features(self, before, want, what):
+        got = {k: self.index.stat(k) - v for k, v in before.items()}
+        full = {k: want.get(k, 0) for k in FEATURE_COUNTERS}
+        assert got == full, "%s: the feature counters moved by %s, expected %s" % (what, got, full)
+
+    def stored_row(self, i):
+        """the row of an id as hnsw_get_vector returns it, by the oracle (under the cosine option: the stored unit row)"""
+        v = self.orc().get_vals(i).copy()
+        if i in self.tamper_rows:
+            e, ulps = self.tamper_rows[i]
+            for _ in range(ulps):
+                v[e] = np.nextafter(v[e], np.float32(np.inf))
+        return v
+
+    def late_labels(self):
+        lab = self.m.labels.copy()
+        for i, v in self.tamper_labels.items():
+            if i < lab.size:
+                lab[i] = v
+        return lab
+
+    def cand_lists(self, V, n, ef, adms, paths, host_form):
+        """the candidate lists of the rows of V (as the search stages them: unit length under the cosine option) with
+        n and ef as the entry point hands them on: under the model's predicate and planned path in the host form, the
+        reference's own walk otherwise -> ids [rows, n], dists, counts, stats int64 [rows, 4]"""
+        from oracle import restate_np as R
+        from tests import filtered_restate as FR
+        rows = V.shape[0]
+        ids = np.full((rows, n), MAX, dtype=np.uint32)
+        dists = np.full((rows, n), np.inf, dtype=np.float32)
+        counts = np.zeros(rows, dtype=np.uint32)
+        stats = np.zeros((rows, 4), dtype=np.int64)
+        seen = {}
+        for r in range(rows):
+            key = (V[r].tobytes(), paths[r], adms[r].tobytes() if host_form else b"")
+            if key not in seen:
+                if host_form:
+                    w = self.want(V[r], n, ef, adms[r], paths[r])
+                else:
+                    w_ids, w_d, w_c = R.ann_by_vector(self.ridx(), V[r], n, ef)
+                    w = dict(ids=w_ids, dists=w_d, counters=w_c)
+                seen[key] = w
+            w = seen[key]
+            ids[r], dists[r], counts[r] = FR.padded(w, n)
+            stats[r, :3] = w["counters"]
+        return ids, dists, counts, stats
+
+    def composite_call(self, c):
+        """the product's call of a composite check"""
+        index, fam, pool, ef = self.index, c["family"], c["pool"], c["ef"]
+        if fam == "radius":
+            return index.search_batch_radius(c["Q"], c["radius"], c["n_first"], pool, ef)
+        if fam.startswith("diverse"):
+            s, ranges = self.sets.get(c.get("set")), c.get("ranges")
+            lo = None if ranges is None else np.array([r[0][0] for r in ranges], dtype=np.uint32)
+            hi = None if ranges is None else np.array([r[0][1] for r in ranges], dtype=np.uint32)
+            return index.search_batch_diverse(c["Q"], c["n"], pool, ef, c["lam"], s,
+                                              np.array(c["keys"]) if s is not None else None, lo, hi)
+        if fam == "from_rows":
+            return index.search_batch_from_rows(c["src"], c.get("weights"), c["n"], ef, c["exclude"])
+        if fam == "by_id":
+            return index.search_batch_by_id(c["src"][:, 0], c["n"], ef, c["exclude"])
+        if fam == "multi_vec":
+            return index.search_batch_multi(c["Q"], c["n"], pool, ef, c.get("weights"), ("sum", "min")[c["mode"]])
+        if fam == "late":
+            return index.search_batch_late(c["Q"], c["n"], pool, ef, ("sum", "sum_sq")[c["mode"]])
+        raise ValueError(fam)
+
+    def refused_call(self, c):
+        """the call at the host form's limit + 1: HnswError with ERR_ARG, and no counter moves"""
+        import hnsw_rs_amd as H
+        from hnsw_rs_amd import _lib
+        before, f_before = self.stats(), self.feature_stats()
+        raised = None
+        try:
+            self.composite_call(c)
+        except H.HnswError as e:
+            raised = e
+        assert raised is not None, "the call beyond the host form's limit was answered"
+        assert raised.code == _lib.ERR_ARG, "the refused call raised %s" % raised
+        self.expect_delta(before, zero_delta(), "refused call")
+        self.expect_features(f_before, {}, "refused call")
+        self.m.note("held_refused:%s" % c["family"])
+
+    def check_composite(self, c):
+        m, fam, gpu = self.m, c["family"], self.product == "gpu"
+        deleted = bool(m.deleted.any())
+        host_form = deleted or fam in FILTERED_COMPOSITES
+        if c.get("refused"):
+            assert host_form, "a refused call was drawn for the device form"
+            m.note("refused:%s" % fam)
+            if gpu:
+                self.refused_call(c)
+            return
+        m.note("state:%s:%s" % (fam, "del" if deleted else "nodel"))
+        if not deleted and m.seen_zero:
+            m.note("none_deleted_after_some:%s" % fam)
+        d_total = zero_delta()
+
+        def plan(n_rows):
+            """the candidate call of n_rows queries through the model -> admissible, paths; its deltas are added up"""
+            if host_form:
+                adms, paths, d = m.plan(n_rows, c.get("set"), c.get("keys") if c.get("set") else None, c.get("ranges"))
+                for p in set(paths):
+                    m.note("hpath%d:%s" % (p, fam))
+            else:
+                adms, paths, d = [m.live()] * n_rows, [0] * n_rows, zero_delta()
+                d["uploads"] = m.ensure_uploaded()
+            for k in COUNTERS:
+                d_total[k] += d[k]
+            return adms, paths
+
+        def note_patched(ids, seen=""):
+            if any(int(i) in m.patched for i in ids):
+                m.note("%spatched:%s" % (seen, fam))
+                if m.inline_rows == 1:
+                    m.note("%spatched_inline:%s" % (seen, fam))
+
+        if fam == "radius":
+            return self.check_radius(c, host_form, plan, note_patched, d_total)
+        pool, ef = c["pool"], c["ef"]
+        rows_m = unit(m.vecs) if self.cosine and m.len else m.vecs
+        src = weights = None
+        if fam in ("from_rows", "by_id"):
+            src, weights = c["src"], c.get("weights")
+            nq, width = src.shape
+            n_cand, ef_c = (c["n"] + width if c["exclude"] else c["n"]), ef
+            if self.product is not None:
+                from hnsw_rs_amd.from_rows import compose_rows
+                V, st = compose_rows(src, weights, self.stored_row, m.len)
+                assert (st == 0).all(), "a drawn query has no legal source"
+            else:  # (for the model's events alone: the rows composed out of the model's vectors)
+                V = np.zeros((nq, m.d), dtype=np.float32)
+                for q in range(nq):
+                    for s in range(width):
+                        if src[q, s] != MAX:
+                            V[q] += (np.float32(1) if weights is None else weights[q, s]) * rows_m[src[q, s]]
+        elif fam in ("multi_vec", "late"):
+            nq, T = c["Q"].shape[:2]
+            V = c["Q"].reshape(nq * T, -1)
+            n_cand, ef_c = pool, max(ef, pool, 1)
+        else:
+            nq, V = c["Q"].shape[0], c["Q"]
+            n_cand, ef_c = pool, ef
+        adms, paths = plan(V.shape[0])
+        sure = [m.nearest(V[r], min(SURE, n_cand), adms[r], self.cosine) for r in range(V.shape[0])]
+        patched = set(m.patched)
+
+        def note_lists(lists, seen=""):
+            """what the lists of a check go through: `lists` one set of candidate ids per row"""
+            if any(i in patched for s in lists for i in s) or (src is not None and set(src[src != MAX].tolist()) & patched):
+                m.note("%spatched:%s" % (seen, fam))
+                if m.inline_rows == 1:
+                    m.note("%spatched_inline:%s" % (seen, fam))
+            if fam not in ("multi_vec", "late"):
+                return
+            for q in range(nq):
+                per = lists[q * T:(q + 1) * T]
+                pairs = [(per[a], per[b]) for a in range(T) for b in range(a + 1, T)]
+                if fam == "multi_vec" and any(a & b for a, b in pairs):
+                    m.note("%smulti_vec:one_id_in_two_lists" % seen)
+                if fam == "late" and any(i != j and m.labels[i] == m.labels[j] for a, b in pairs for i in a for j in b):
+                    m.note("%slate:shared_document" % seen)
+            if fam == "late":
+                every = {i for s in lists for i in s}
+                if any(i >= column for i in every):
+                    m.note("%slate:beyond_the_column" % seen)
+                if label_copy_moved and every & changed:
+                    m.note("%slate:label_changed" % seen)
+
+        if fam == "late":
+            # the label column as the call finds it: the ids its words cover, the ids whose label changed since it last
+            # went to HBM, and whether this call's sync sends changed words (lab:scatter, lab:whole)
+            column, changed = 2 * m.lab_nw, set(m.lab_changed)
+            moved = (m.ev["lab:scatter"], m.ev["lab:whole"])
+            d_total["label_words_uploaded"] += m.sync_labels()  # (the scoring reads the labels)
+            label_copy_moved = moved != (m.ev["lab:scatter"], m.ev["lab:whole"])
+        note_lists([{int(i) for i in s} for s in sure])
+        if self.product is None:
+            return
+        # with the library at hand the candidate lists are known without a GPU (the graph is the host's): what they go
+        # through is noted a second time, as seen
+        Vr = unit(V) if self.cosine else V
+        ids, dists, counts, stats = self.cand_lists(Vr, n_cand, ef_c, adms, paths, host_form)
+        note_lists([{int(i) for i in ids[r, :counts[r]]} for r in range(ids.shape[0])], "seen:")
+        if not gpu:
+            return
+        from hnsw_rs_amd import diverse, from_rows, late, multi
+        from tests import diverse_cases as DC
+        from tests import from_rows_cases as FC
+        from tests import late_cases as LC
+        from tests import multi_cases as MC
+        orc = self.orc()
+        if fam.startswith("diverse"):
+            want = diverse.mmr_select(ids, dists, counts, None, orc.distance, c["lam"], c["n"])
+            features = {"diverse_calls": 1, "diverse_launches": 1}
+        elif src is not None:
+            want = from_rows.drop_ids(ids, dists, counts, None, src, c["n"]) if c["exclude"] else (ids, dists, counts)
+            features = {"from_rows_calls": 1, "from_rows_compose_launches": 1, "from_rows_drop_launches": int(c["exclude"])}
+        elif fam == "multi_vec":
+            want = multi.fuse_lists(Vr.reshape(nq, T, -1), c.get("weights"), ("sum", "min")[c["mode"]],
+                                    ids.reshape(nq, T, pool), counts.reshape(nq, T), None, orc.distance_batch, c["n"], m.len)
+            features = {"multi_calls": 1, "multi_fuse_launches": 1}
+        else:
+            want = late.late_interaction(Vr.reshape(nq, T, -1), ("sum", "sum_sq")[c["mode"]], ids.reshape(nq, T, pool),
+                                         counts.reshape(nq, T), None, orc.distance_batch, self.late_labels(), c["n"], m.len)
+            features = {"late_calls": 1, "late_launches": 1}
+        before, f_before = self.stats(), self.feature_stats()
+        got = self.composite_call(c)
+        self.expect_delta(before, d_total, fam)
+        self.expect_features(f_before, features, fam)
+        g_stats = got[-1]
+        if fam.startswith("diverse"):
+            DC.assert_diverse_equal(got, want, fam)
+        elif src is not None:
+            FC.assert_drop_equal(got[:3], want[:3], fam)
+        elif fam == "multi_vec":
+            MC.assert_fused_equal(got[:4] + (g_stats[:, 3],), want, fam)
+        else:
+            LC.assert_late_equal(got[:6] + (g_stats[:, 3],), want, fam)
+        if fam in ("multi_vec", "late"):  # (the counters of a query's T searches, summed)
+            stats = stats.reshape(nq, T, 4).sum(axis=1)
+        assert np.array_equal(g_stats[:, :3], stats[:, :3]), "%s: counters %s, the candidates' %s" % (fam, g_stats[:, :3], stats[:, :3])
+        assert (g_stats[:, 3] == 0).all(), "%s: statuses %s" % (fam, g_stats[:, 3])
+        m.note("held:%s" % fam)
+
+    def check_radius(self, c, host_form, plan, note_patched, d_total):
+        m, gpu = self.m, self.product == "gpu"
+        Q, n_first, max_n, ef = c["Q"], c["n_first"], c["pool"], c["ef"]
+        nq = Q.shape[0]
+        radius = np.broadcast_to(np.asarray(c["radius"], dtype=np.float32), (nq,))
+        n_of = [n_first]  # the n of every rung of the ladder
+        while n_of[-1] < max_n:
+            n_of.append(min(2 * n_of[-1], max_n))
+        K = len(n_of)
+        # what the model alone says of the ladder: the rows within a radius counted in float64, with a margin on both
+        # sides for what f32 and the 8-bit codes round; a query whose two counts leave at the same rung is predicted
+        live = m.live()
+        n_live = int(live.sum())
+        exits = []
+        for q in range(nq):
+            d, r = m.dist64(Q[q], self.cosine)[live], float(radius[q])
+            with np.errstate(invalid="ignore"):
+                w = [min(n_live, int((d <= x).sum())) for x in (max(r * 0.95 - 0.02, 0.0), r * 1.05 + 0.02)]
+            a, b = [next(k for k in range(K) if x < n_of[k] or k == K - 1) for x in w]
+            exits.append(b)
+            if a == b and K >= 3:
+                m.note("radius:leaves_%s" % ("first" if a == 0 else "last" if a == K - 1 else "middle"))
+            if a == b == K - 1 and w[0] >= max_n:
+                m.note("radius:truncated")
+        if self.product is None:
+            for k in range(max(exits) + 1):  # (every rung is a search of its own under the planner)
+                adms, _ = plan(nq)
+                if k == 0:
+                    note_patched([i for q in range(nq) for i in m.nearest(Q[q], min(SURE, n_first), adms[q], self.cosine)])
+            return
+        # with the library at hand the ladder is known without a GPU (the graph is the host's): what it goes through is
+        # noted a second time, as seen
+        from hnsw_rs_amd.radius import radius_ladder
+        from tests import radius_cases as RC
+        rung = [0]
+
+        def search(Qs, n, ef_k):
+            adms, paths = plan(Qs.shape[0])
+            lists = self.cand_lists(Qs, n, ef_k, adms, paths, host_form)
+            if rung[0] == 0:
+                note_patched([i for q in range(nq) for i in m.nearest(Q[q], min(SURE, n_first), adms[q], self.cosine)])
+                note_patched([i for q in range(nq) for i in lists[0][q, :lists[2][q]]], "seen:")
+            rung[0] += 1
+            return lists
+
+        want = radius_ladder(search, unit(Q) if self.cosine else Q, radius, n_first, max_n, ef)
+        for q in range(nq):
+            k = int(want[4][q]) - 1
+            if K >= 3:
+                m.note("seen:radius:leaves_%s" % ("first" if k == 0 else "last" if k == K - 1 else "middle"))
+            if want[3][q] & 1:
+                m.note("seen:radius:truncated")
+        if not gpu:
+            return
+        before, f_before = self.stats(), self.feature_stats()
+        got = self.composite_call(c)
+        self.expect_delta(before, d_total, "radius")
+        self.expect_features(f_before, {"radius_calls": 1, "radius_rungs": rung[0], "radius_launches": rung[0]}, "radius")
+        RC.assert_ladder_equal(got, want, "radius")
+        m.note("held:radius")
+
     def check_host_family(self, c):
         m, fam = self.m, c["family"]
         if fam == "count_labels":
@@ -1122,6 +1693,6 @@ class Machine:
         # (deleted_ids, get_labels, MaskSet.read and MaskSet.count are held to the model after every op: check_host_state)
 
 
-def replay(seed, kind, upto, product="gpu", steps=STEPS, cosine=False):
+def replay(seed, kind, upto, product="gpu", steps=None, cosine=False, families="default"):
     """re-runs the first `upto` ops of a schedule (a failure names its step index: the prefix is found by hand)"""
-    return Machine(seed, kind, product, steps, cosine).run(upto)
+    return Machine(seed, kind, product, steps, cosine, families).run(upto)
