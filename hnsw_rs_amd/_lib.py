@@ -26,6 +26,10 @@ LATE_MAX_CANDS = 1024  # HNSW_LATE_MAX_CANDS: n_vecs * pool, the candidates of o
 LATE_MAX_DOCS = 256  # HNSW_LATE_MAX_DOCS: documents returned per query
 LATE_SUM = 0  # HNSW_LATE_SUM: a document's score is the sum over the query's vectors of the distance to its nearest row
 LATE_SUM_SQ = 1  # HNSW_LATE_SUM_SQ: ... of that distance squared (MaxSim's ranking on unit-length rows)
+ROWS_F32 = 0  # HNSW_ROWS_F32: a row table of f32 elements
+ROWS_F16 = 1  # HNSW_ROWS_F16: ... of IEEE binary16 elements, widened exactly where they are read
+REFINE_POOL_MAX = 1024  # HNSW_REFINE_POOL_MAX: candidates per query of a refined search
+REFINE_MAX_DIM = 4096  # HNSW_REFINE_MAX_DIM: elements of a full row
 RADIUS_MAX_N = 1024  # HNSW_RADIUS_MAX_N: entries per list of a radius search
 RADIUS_MORE = 1  # HNSW_RADIUS_MORE: the list was full and showed nothing outside the radius
 RANGES_MAX = 16  # HNSW_RANGES_MAX: members of a query's range list
@@ -63,6 +67,7 @@ class SnapshotDesc(C.Structure):
 
 
 u8p = C.POINTER(C.c_uint8)
+u16p = C.POINTER(C.c_uint16)
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
 f32p = C.POINTER(C.c_float)
@@ -168,6 +173,18 @@ SYMBOLS = {
                                                vp, vp, vp, vp, vp, vp, vp, vp]),
     "hnsw_search_batch_late": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          u32p, f32p, u32p, u32p, u32p, u32p, C.POINTER(QueryStats)]),
+    "hnsw_row_table_create": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "hnsw_row_table_free": (None, [vp]),
+    "hnsw_row_table_info": (C.c_int, [vp, u32p, u32p, u64p]),
+    "hnsw_row_table_write": (C.c_int, [vp, C.c_uint64, C.c_uint64, f32p]),
+    "hnsw_row_table_write_raw": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp]),
+    "hnsw_row_table_read": (C.c_int, [vp, C.c_uint64, C.c_uint64, f32p]),
+    "hnsw_row_table_device": (C.c_int, [vp, C.POINTER(vp), u64p]),
+    "hnsw_f32_to_f16": (C.c_int, [f32p, C.c_uint64, u16p]),
+    "hnsw_refine_device": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, vp,
+                                     vp, vp, vp, vp, vp, vp]),
+    "hnsw_search_batch_refined": (C.c_int, [vp, vp, f32p, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, u32p,
+                                            u32p, u32p, u32p, f32p, u32p, C.POINTER(QueryStats)]),
     "hnsw_distance_batch": (C.c_int, [vp, f32p, u32p, C.c_uint64, f32p]),
     "hnsw_search_layer": (C.c_int, [vp, C.c_uint32, f32p, u32p, C.c_uint32, C.c_uint32, u32p, f32p, u32p,
                                     C.POINTER(QueryStats)]),

@@ -340,7 +340,21 @@ struct DiverseLists {
     const uint32_t *labels;
     uint64_t label_len;
     uint32_t *best_out, *sizes_out, *n_docs_out;
+    // The sixth source form (hnsw_refine_device), selected by table != nullptr (null in every other
+    // launch) and looked at FIRST; it reads nothing of the DevView.  Query q has ONE candidate list ids[q][j], j < pool,
+    // counts[q] and stats[q] (either may be nullptr) and a full row queries[q][full_dim]; table is table_rows rows of
+    // full_dim elements of table_dtype (HX_ROWS_F32: f32, HX_ROWS_F16: IEEE binary16, widened exactly).  THE REFINEMENT of
+    // include/hnsw_mi355x.h goes to out_ids / out_dists [q][n_out], out_counts[q] (may be nullptr) and out_stats[q] (with
+    // stats).  lane_rows != 0: a lane per row whatever the width (the switch HNSW_MI355X_REFINE_LANE_ROWS, A/B runs).
+    // Nothing else above is read.
+    const void *table;
+    uint64_t table_rows;
+    uint32_t full_dim, table_dtype, lane_rows;
 };
+#define HX_ROWS_F32 0
+#define HX_ROWS_F16 1
+#define HX_REFINE_POOL_MAX 1024  // candidates per refined query: a key of 8 bytes each in LDS
+#define HX_REFINE_MAX_DIM 4096   // elements of a full row: the staged query is at most 16 KiB of LDS
 #define HX_FROM_ROWS_MAX_TERMS 64  // slots per composed query: one lane each
 #define HX_MULTI_MAX_VECS 16       // vectors per fused query
 #define HX_LATE_MAX_VECS 32        // vectors per late-interaction query
@@ -360,6 +374,10 @@ int launch_fuse_lists(const DevView &v, const DiverseLists &d, hipStream_t strea
 // HX_LATE_MAX_CANDS, 1 <= n_out <= min(n_vecs * pool, HX_LATE_MAX_DOCS), mode 0 or 1): ONE launch of hx_distance_kernel in
 // its fifth form, one wave per query; sets d.late itself
 int launch_late_interaction(const DevView &v, DiverseLists d, hipStream_t stream);
+// the refinement of d.nq candidate lists against d.table (1 <= n_out <= pool <= HX_REFINE_POOL_MAX, 1 <= full_dim <=
+// HX_REFINE_MAX_DIM, a dtype of the two): ONE launch of hx_distance_kernel<HNSW_VEC_F32> in its sixth form under a zeroed
+// view, one wave per query; takes no handle and sets d.lane_rows from the switch itself
+int launch_refine(DiverseLists d, hipStream_t stream);
 
 // exhaustive scan: every query against every point; partial top-k per (query, segment):
 // part_ids / part_dists are nq x nseg x k.  The host merges the segments.

@@ -118,6 +118,9 @@ const Stat kStats[] = {
     HX_STAT("multi_fuse_launches", h.n_multi_fuse),
     HX_STAT("late_calls", h.n_late_calls),
     HX_STAT("late_launches", h.n_late_launches),
+    HX_STAT("refine_calls", h.n_refine_calls),
+    HX_STAT("refine_launches", h.n_refine_launches),
+    HX_STAT("row_table_writes", h.n_row_table_writes),
     HX_STAT("deleted", h.del.count),
     HX_STAT("deleted_mask_words_uploaded", h.del.words_uploaded),
     HX_STAT("deleted_queries_graph", h.n_del_graph),

@@ -41,6 +41,10 @@ inline bool visited_2l() { static const bool v = on_unless_0("HNSW_MI355X_VISITE
 // ids after which the LDS level of that set closes (tests).  Default: `unset`, the kernel's own limit.  Live.
 inline uint32_t visited_2l_limit(uint32_t unset) { return (uint32_t)env_int("HNSW_MI355X_VISITED_2L_LIMIT", unset); }
 
+// ---- refined search ----
+// the refinement gathers every width of table row with a lane per row, never cooperatively (A/B runs).  Default off.  Live.
+inline bool refine_lane_rows() { return off_unless_set("HNSW_MI355X_REFINE_LANE_ROWS"); }
+
 // ---- the HBM snapshot ----
 // inline rows for 8-bit indexes: 1 builds them, 0 never does.  Default -1: the handle's own setting.  Live.
 inline int inline_rows(int unset) { return (int)env_int("HNSW_MI355X_INLINE_ROWS", unset); }

@@ -764,6 +764,54 @@ class HNSW:
             self._h, nq, n_vecs, pool, n_out, mode_of(mode), p(d_Q), p(d_ids_in), p(d_counts_in), p(d_stats_in),
             p(d_doc_labels), p(d_scores), p(d_best_ids), p(d_doc_sizes), p(d_counts), p(d_n_docs), p(d_stats), stream or None))
 
+    # ---- refined search: the pool re-scored against full rows kept in HBM (include/hnsw_mi355x.h) -------------------
+    def row_table(self, full_dim, dtype="f32"):
+        """-> refine.RowTable: full rows of full_dim elements, "f32" or "f16", that live in HBM beside this index, row id =
+        index id (hnsw_row_table).  Making one needs no GPU; the first write allocates."""
+        from .refine import RowTable, dtype_of
+        t = C.c_void_p()
+        check(self._L.hnsw_row_table_create(self._h, int(full_dim), dtype_of(dtype), C.byref(t)))
+        return RowTable(self, t)
+
+    def search_batch_refined(self, table, Q, Qfull, n, pool, ef, mask_set=None, mask_of=None, lo=None, hi=None):
+        """The n nearest by the FULL rows of `table` (a RowTable of this index) out of the `pool` candidates that
+        search_batch (or, with mask_set / lo and hi, the filtered search of that kind) returns for Q with n = pool:
+        refine.refine_lists of those lists with Qfull [nq, full_dim] (hnsw_search_batch_refined).  Q None: the index's
+        queries are the first dim elements of each Qfull row.  The cosine option applies to Q alone.
+        -> ids [nq, n] (pad UINT32_MAX), dists [nq, n] (the full rows' distances, pad +inf), counts [nq], stats [nq, 4]
+        (the candidate call's)"""
+        Qfull = np.ascontiguousarray(Qfull, dtype=np.float32)
+        if Qfull.ndim != 2 or Qfull.shape[1] != table.full_dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "full queries must be nq x %d" % table.full_dim)
+        nq, width = Qfull.shape[0], max(int(n), 1)
+        if Q is not None:
+            Q = np.ascontiguousarray(Q, dtype=np.float32)
+            if Q.ndim != 2 or Q.shape[1] != self.dim or Q.shape[0] != nq:
+                raise HnswError(_lib.ERR_BAD_DIM, "queries must be %d x %d" % (nq, self.dim))
+        if (lo is None) != (hi is None):
+            raise ValueError("a label range needs lo and hi, both or neither")
+        mo = self._mask_of(mask_of, nq)
+        rng = (None, None) if lo is None else self._range(lo, hi, nq)
+        ids = np.full((nq, width), _lib.UINT32_MAX, dtype=np.uint32)
+        dists = np.full((nq, width), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        check(self._L.hnsw_search_batch_refined(
+            self._h, table._t, None if Q is None else _p(Q, _f32p), _p(Qfull, _f32p), nq, n, pool, ef,
+            mask_set._s if mask_set is not None else None, None if mo is None else _p(mo, _u32p),
+            None if rng[0] is None else _p(rng[0], _u32p), None if rng[1] is None else _p(rng[1], _u32p), _p(ids, _u32p),
+            _p(dists, _f32p), _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
+        return ids, dists, counts, stats.view(np.uint32).astype(np.int64)
+
+    @staticmethod
+    def refine_device(nq, pool, n_out, full_dim, dtype, d_table, table_rows, d_Qfull, d_ids_in, d_counts_in, d_stats_in,
+                      d_ids, d_dists, d_counts=None, d_stats=None, stream=0):
+        """hnsw_refine_device over torch device tensors (or raw device pointers): refine.refine_device.  ONE launch
+        enqueued on `stream` of the current device, no sync of it; needs no index."""
+        from .refine import refine_device
+        refine_device(nq, pool, n_out, full_dim, dtype, d_table, table_rows, d_Qfull, d_ids_in, d_counts_in, d_stats_in,
+                      d_ids, d_dists, d_counts, d_stats, stream)
+
     def search_filtered(self, q, n, ef, lo=0, hi=0xFFFFFFFF, mask_set=None, row=None):
         """ONE query under the label range [lo, hi] and, with a resident MaskSet, its row `row` (None, -1 or MASK_NONE: no
         row): hnsw_search_filtered, whose concurrent callers on an index are gathered into one launch.

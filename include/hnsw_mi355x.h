@@ -1011,6 +1011,97 @@ int hnsw_search_batch_late(hnsw_index *h, const float *Q /* nq x n_vecs x dim */
                            uint32_t *counts /* or NULL */, uint32_t *n_docs /* or NULL */,
                            hnsw_query_stats *stats /* or NULL */);
 
+/* ---- refined search: the pool re-scored against full rows kept in HBM ------------------------------------------------
+ * An extension (the reference ranks by the rows it stores).  Every search above ranks by the distance the INDEX stores:
+ * its 8-bit rows, or its f32 rows of the index's own dimension.  A caller who also holds a better representation of the
+ * same ids -- the full 768-d embedding while the index was built over the first 128 coordinates (Matryoshka-style
+ * "funnel" retrieval), full-precision rows behind the 8-bit kind, any second-stage vector -- keeps it in a ROW TABLE in
+ * HBM, and a search is answered by a walk over the index's short rows followed by an exact re-score of a small pool
+ * against the long ones.
+ *
+ * A row table (hnsw_row_table) is rows x full_dim elements of dtype HNSW_ROWS_F32 or HNSW_ROWS_F16 (IEEE binary16,
+ * widened exactly to f32 where it is read), row id = index id, 1 <= full_dim <= HNSW_REFINE_MAX_DIM.  It lives in HBM
+ * ONLY, on its handle's device: the host keeps no copy, the caller owns the full rows.  It is NOT saved by hnsw_save, NOT
+ * cloned by hnsw_clone and NOT part of the snapshot exchange.
+ *   hnsw_row_table_create   touches no device; the first write allocates on the handle's device (its snapshot's, else the
+ *                           one it is bound to, else the calling thread's) and fixes it.
+ *   hnsw_row_table_write    n rows of f32 to ids first_id .. first_id + n - 1.  An f16 table rounds to nearest, ties to
+ *                           even, on the host.  A NaN, an infinity or a value that rounds to one is HNSW_ERR_NAN_INPUT and
+ *                           nothing is written.  first_id <= rows: there are no holes (HNSW_ERR_ARG).  A write past the
+ *                           capacity grows the array by a device-to-device copy (capacity + 1/8).
+ *   hnsw_row_table_write_raw  the same with rows in the table's own dtype; every element must be finite.
+ *   hnsw_row_table_read     rows back as f32, widened exactly.
+ *   hnsw_row_table_device   the array in HBM (NULL before the first write) and its rows, for hnsw_refine_device.  A later
+ *                           write that grows the table moves it.
+ *   hnsw_f32_to_f16         the rounding routine itself, device-free: HNSW_ERR_NAN_INPUT, and nothing written, when a
+ *                           value is a NaN or rounds to an infinity (65520 is the first that does).
+ * Writes to one table are serialised; a write must not run while a search names the table.
+ *
+ * THE REFINEMENT of one query, with a candidate list ids_in [pool], counts_in or NULL, stats_in or NULL, a full query row
+ * qf [full_dim] of f32 and a table of table_rows rows:
+ *   - entry j is PRESENT iff j < min(count, pool), or, without counts, iff its id is not UINT32_MAX (THE SELECTION's rule);
+ *   - an incoming status that is not HNSW_OK fails the query with that status; otherwise a present id at or beyond
+ *     table_rows gives HNSW_ERR_ARG, and no table row is read for the query; otherwise a NaN element of qf gives
+ *     HNSW_ERR_NAN_INPUT.  A failed query has count 0 and padded rows;
+ *   - the distance of a present entry with row x is sqrt(s), where s = 0.0f, then t = x[e] - qf[e]; s = s + t * t for
+ *     e = 0 .. full_dim - 1: ONE left-to-right f32 chain, every operation rounded separately and never contracted, the
+ *     correctly rounded square root -- FullVec::distance's own arithmetic (vectors/src/full.rs:23-29).  An f16 element is
+ *     widened exactly before the subtraction: subnormals, +-0 and 65504 survive;
+ *   - the present entries are ranked ascending by (distance bits, id); duplicate ids in a list are separate entries; an
+ *     entry whose distance is +inf is an ordinary entry and ranks last; one whose distance is NaN is never returned.
+ * Per query: ids [n_out] (pad UINT32_MAX), dists [n_out] (pad +inf), counts (optional) = entries written, stats (required
+ * iff stats_in is given): the incoming record unchanged but for the status above.  Every output word is written exactly
+ * once.  Limits: 1 <= n_out <= pool <= HNSW_REFINE_POOL_MAX, 1 <= full_dim <= HNSW_REFINE_MAX_DIM, nq <= 2^31 - 1.
+ *
+ * hnsw_refine_device is THE REFINEMENT alone over buffers in HBM.  It takes no handle, as hnsw_merge_topk_device and
+ * hnsw_radius_cut_device take none: ONE launch (the distance seam's kernel in its refinement form, one wave per query) is
+ * enqueued on `stream` -- no synchronise, no allocation, no copy.  d_table holds table_rows x full_dim elements of dtype,
+ * d_Qfull nq x full_dim floats; outputs must not overlap inputs.  The status of a failed query is written to d_stats
+ * only.  HNSW_ERR_ARG, decided before the device is touched: a limit violated; a dtype other than the two; nq > 2^31 - 1;
+ * d_table, d_Qfull, d_ids_in, d_ids or d_dists NULL; exactly one of d_stats_in / d_stats given.  nq == 0 is HNSW_OK
+ * whatever else is passed.
+ *
+ * hnsw_search_batch_refined answers host-pointer queries.  By definition the result is THE REFINEMENT, with n_out = n
+ * and the rows of Qfull, of the lists that the candidate call of hnsw_search_batch_diverse's table returns for Q with
+ * n = pool and ef' = max(ef, pool, 1), and everything is inherited exactly as there: the filter (set / mask_of / lo / hi),
+ * deleted ids taken out, the planner, per-query errors, pool <= 64 and ef' <= 256 under a filter or deletions.  The
+ * metric_cosine option applies to Q alone; Qfull is used as given.  Q == NULL: the index's queries are the first dim
+ * elements of each Qfull row (full_dim >= dim is then required), taken by one strided upload.  Unfiltered and with nothing
+ * deleted the call stays on the device: both query blocks go up once, the launch of hnsw_search_batch_device and the
+ * re-run loop of its _finish, one refinement launch, ONE copy of the block [ids | dists | counts | stats] back.  dists,
+ * counts and stats may be NULL.  HNSW_ERR_ARG, decided before the device is touched: the filter's own refusals; t NULL or
+ * of another handle; a limit violated; Qfull or ids NULL; nq > 2^31 - 1; Q NULL with full_dim < dim; a table with fewer
+ * rows than the index.  nq == 0 is HNSW_OK; an empty index is HNSW_ERR_EMPTY.  hnsw_get_stat: "refine_calls"
+ * (hnsw_search_batch_refined calls answered), "refine_launches" (the refinements they launched), "row_table_writes"
+ * (writes that reached a table of the handle).
+ * Not provided: bf16 rows; a table per shard and a refined partitioned search; persistence of the table; one-query
+ * gathered calls; the Rust shim's binding; a place in the update machine (an inserted id needs its full row written
+ * before a search may return it: the table must cover the index). */
+#define HNSW_ROWS_F32 0
+#define HNSW_ROWS_F16 1
+#define HNSW_REFINE_POOL_MAX 1024
+#define HNSW_REFINE_MAX_DIM 4096
+typedef struct hnsw_row_table hnsw_row_table;
+int hnsw_row_table_create(hnsw_index *h, uint32_t full_dim, uint32_t dtype, hnsw_row_table **out);
+void hnsw_row_table_free(hnsw_row_table *t);
+int hnsw_row_table_info(const hnsw_row_table *t, uint32_t *full_dim, uint32_t *dtype, uint64_t *rows);
+int hnsw_row_table_write(hnsw_row_table *t, uint64_t first_id, uint64_t n, const float *rows /* n x full_dim */);
+int hnsw_row_table_write_raw(hnsw_row_table *t, uint64_t first_id, uint64_t n, const void *rows /* in the table's dtype */);
+int hnsw_row_table_read(hnsw_row_table *t, uint64_t first_id, uint64_t n, float *out /* n x full_dim */);
+int hnsw_row_table_device(const hnsw_row_table *t, const void **d_ptr, uint64_t *rows /* or NULL */);
+int hnsw_f32_to_f16(const float *in, uint64_t n, uint16_t *out);
+int hnsw_refine_device(uint64_t nq, uint32_t pool, uint32_t n_out, uint32_t full_dim, uint32_t dtype,
+                       const void *d_table /* table_rows x full_dim of dtype */, uint64_t table_rows,
+                       const float *d_Qfull /* nq x full_dim */, const uint32_t *d_ids_in /* nq x pool */,
+                       const uint32_t *d_counts_in /* or NULL */, const hnsw_query_stats *d_stats_in /* or NULL */,
+                       uint32_t *d_ids, float *d_dists /* nq x n_out */, uint32_t *d_counts /* or NULL */,
+                       hnsw_query_stats *d_stats /* required iff d_stats_in */, void *stream);
+int hnsw_search_batch_refined(hnsw_index *h, hnsw_row_table *t, const float *Q /* nq x dim, or NULL */,
+                              const float *Qfull /* nq x full_dim */, uint64_t nq, uint32_t n, uint32_t pool, uint32_t ef,
+                              hnsw_mask_set *set /* or NULL */, const uint32_t *mask_of /* or NULL */,
+                              const uint32_t *lo /* or NULL */, const uint32_t *hi /* or NULL */, uint32_t *ids /* nq x n */,
+                              float *dists /* or NULL */, uint32_t *counts /* or NULL */, hnsw_query_stats *stats /* or NULL */);
+
 /* Test seams that mirror the reference's own units:
  * VecBase::dist2many (vectors/src/lib.rs:17-22): the query (quantised like ann_by_vector does,
  * template.rs:313) against stored ids, on the device, exact accumulation order. */
