@@ -11,6 +11,8 @@ from .diverse import mmr_select  # noqa: F401
 from .from_rows import compose_rows, drop_ids  # noqa: F401
 from .multi import fuse_lists  # noqa: F401
 from .late import late_interaction  # noqa: F401
+from .docs import score_documents  # noqa: F401
+from ._lib import DOCS_MAX_IN, DOCS_MAX_ROWS  # noqa: F401
 from .refine import RowTable, f32_to_f16, refine_device, refine_lists  # noqa: F401
 from ._lib import REFINE_MAX_DIM, REFINE_POOL_MAX, ROWS_F16, ROWS_F32  # noqa: F401
 from .radius import radius_cut, radius_ladder, to_csr  # noqa: F401

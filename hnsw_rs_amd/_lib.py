@@ -26,6 +26,8 @@ LATE_MAX_CANDS = 1024  # HNSW_LATE_MAX_CANDS: n_vecs * pool, the candidates of o
 LATE_MAX_DOCS = 256  # HNSW_LATE_MAX_DOCS: documents returned per query
 LATE_SUM = 0  # HNSW_LATE_SUM: a document's score is the sum over the query's vectors of the distance to its nearest row
 LATE_SUM_SQ = 1  # HNSW_LATE_SUM_SQ: ... of that distance squared (MaxSim's ranking on unit-length rows)
+DOCS_MAX_IN = 256  # HNSW_DOCS_MAX_IN: labels per list of a document scoring
+DOCS_MAX_ROWS = 1048576  # HNSW_DOCS_MAX_ROWS: rows scored per document
 ROWS_F32 = 0  # HNSW_ROWS_F32: a row table of f32 elements
 ROWS_F16 = 1  # HNSW_ROWS_F16: ... of IEEE binary16 elements, widened exactly where they are read
 REFINE_POOL_MAX = 1024  # HNSW_REFINE_POOL_MAX: candidates per query of a refined search
@@ -173,7 +175,12 @@ SYMBOLS = {
                                                vp, vp, vp, vp, vp, vp, vp, vp]),
     "hnsw_search_batch_late": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                          u32p, f32p, u32p, u32p, u32p, u32p, C.POINTER(QueryStats)]),
-    "hnsw_row_table_create": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "hnsw_score_documents_device": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
+                                              vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "hnsw_search_batch_late_exact": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.c_uint32, C.c_uint32, u32p, f32p, u32p, u32p, u32p, u32p,
+                                               C.POINTER(QueryStats)]),
+    "hnsw_row_table_create":(C.c_int, [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
     "hnsw_row_table_free": (None, [vp]),
     "hnsw_row_table_info": (C.c_int, [vp, u32p, u32p, u64p]),
     "hnsw_row_table_write": (C.c_int, [vp, C.c_uint64, C.c_uint64, f32p]),

@@ -350,6 +350,16 @@ struct DiverseLists {
     const void *table;
     uint64_t table_rows;
     uint32_t full_dim, table_dtype, lane_rows;
+    // The seventh source form (hnsw_score_documents_device), selected by docs != 0 (zero in every
+    // other launch) and looked at FIRST of all: query q has n_vecs vectors queries[q][t][dim] and ONE list of labels
+    // ids[q][j], j < pool (the list's length n_in), counts[q] (nullptr: every entry is present -- every uint32 is a label)
+    // and stats[q] (may be nullptr); doc_keys[i], i < n_doc_keys, is the document index: the keys label << 32 | id of the
+    // undeleted ids, ascending, so that a label's rows are a slice of it.  THE DOCUMENT SCORING of include/hnsw_mi355x.h
+    // under `mode`, every document over its min(size, rows_cap) lowest ids, goes to the fifth form's outputs.  labels,
+    // label_len and everything the fifth form does not read are not read.
+    uint32_t docs, rows_cap;
+    const uint64_t *doc_keys;
+    uint64_t n_doc_keys;
 };
 #define HX_ROWS_F32 0
 #define HX_ROWS_F16 1
@@ -360,6 +370,10 @@ struct DiverseLists {
 #define HX_LATE_MAX_VECS 32        // vectors per late-interaction query
 #define HX_LATE_MAX_CANDS 1024     // its candidates, n_vecs * pool: 36 bytes of LDS each
 #define HX_LATE_MAX_DOCS 256       // the documents it returns
+#define HX_DOCS_MAX_IN 256         // labels per list of the document scoring: 28 bytes of LDS each, and n_vecs minima
+// rows scored per document: the prefix sums of the scored sizes are 32-bit words in LDS, and HX_DOCS_MAX_IN documents of
+// this many rows total 2^28
+#define HX_DOCS_MAX_ROWS (1u << 20)
 // the selection of d.nq candidate lists (1 <= n_out <= pool <= HX_DIVERSE_POOL_MAX, lambda in [0, 1]): ONE launch of
 // hx_distance_kernel in its second form, one wave per query
 int launch_diversify(const DevView &v, const DiverseLists &d, hipStream_t stream);
@@ -374,6 +388,10 @@ int launch_fuse_lists(const DevView &v, const DiverseLists &d, hipStream_t strea
 // HX_LATE_MAX_CANDS, 1 <= n_out <= min(n_vecs * pool, HX_LATE_MAX_DOCS), mode 0 or 1): ONE launch of hx_distance_kernel in
 // its fifth form, one wave per query; sets d.late itself
 int launch_late_interaction(const DevView &v, DiverseLists d, hipStream_t stream);
+// the document scoring of d.nq lists of d.pool labels each (1 <= n_vecs <= HX_LATE_MAX_VECS, 1 <= n_out <= pool <=
+// HX_DOCS_MAX_IN, 1 <= rows_cap <= HX_DOCS_MAX_ROWS, mode 0 or 1) over d.doc_keys: ONE launch of hx_distance_kernel in its
+// seventh form, one wave per query; sets d.docs itself
+int launch_score_documents(const DevView &v, DiverseLists d, hipStream_t stream);
 // the refinement of d.nq candidate lists against d.table (1 <= n_out <= pool <= HX_REFINE_POOL_MAX, 1 <= full_dim <=
 // HX_REFINE_MAX_DIM, a dtype of the two): ONE launch of hx_distance_kernel<HNSW_VEC_F32> in its sixth form under a zeroed
 // view, one wave per query; takes no handle and sets d.lane_rows from the switch itself

@@ -2,8 +2,8 @@
 // every query against all points) and hx_distance_kernel (dist2many for one query, a test seam; in its second form the
 // MMR selection of diversified search: stored rows against a stored row; in its third the query rows composed out of
 // stored rows; in its fourth the fusion of a query's per-vector candidate lists; in its fifth the late interaction that
-// scores those candidates as documents; in its sixth the refinement of a candidate list against a table of full rows),
-// with their launchers.
+// scores those candidates as documents; in its sixth the refinement of a candidate list against a table of full rows; in
+// its seventh the scoring of named documents over every stored row they have), with their launchers.
 // Same staged query, same row distance (dist_any_dim) and same sorted list (WaveList) as the search kernels:
 // search_common.h.  The MFMA screen of hnsw_brute_force_fast is brute_mfma.hip.
 
@@ -385,138 +385,282 @@ __device__ __forceinline__ void fuse_lists(const DevView &v, const DiverseLists 
 // minima on the bits -- distances are >= +0 or NaN and a NaN is skipped, so the bits order as the floats do and the
 // result does not depend on the order of arrival -- and after the pass e_t into dsum.  The emission takes n_out times
 // the wave's minimum of (orderable score, label); labels are distinct, so one lane owns it.  Plain vector stores.
+//
+// The kernel's seventh form (DiverseLists with docs != 0) is the same function: query blockIdx.x's
+// ONE list of d.pool LABELS scored as documents over EVERY undeleted row they have -- a label's rows are a slice of the
+// document index d.doc_keys (label << 32 | id, ascending).  It shares everything from the per-vector pass loop on -- one
+// call site of dist_any_dim -- and differs before it.  Its LDS table is HX_DOCS_LDS(n_in, n_vecs):
+//   dbest  256 double words   dlab, dstart, dsize, dpre, dsum  256 words each: a document's label, the index of its first
+//   key, its FULL size, the scored rows before it (the prefix sums of min(size, rows_cap)), its fold
+//   cid, cdoc  HX_DOCS_CHUNK words each: a chunk's row ids and their documents (cid first holds the labels as loaded)
+//   dmin   n_in * n_vecs words: the minima of document g under vector t at g * n_vecs + t, kept ACROSS chunks
+// The incoming status, presence (a prefix of the list: there is no pad) and the NaN check of all n_vecs vectors are decided
+// before any index row is read.  The distinct labels go by the same all-pairs compare; one lane per distinct label runs
+// the two binary searches over the keys in HBM; labels without a row drop out in the ballot compaction.  The scored rows
+// of all documents, in document order, are walked in chunks of HX_DOCS_CHUNK entries: every lane finds its entry's
+// document by a binary search over dpre and reads the id from the key's low word; then, per vector, stage_query and the
+// pass loop.  A document may straddle chunks or be larger than one: its minima wait in dmin.  After the last chunk the
+// owner lane of a document folds e_t in vector order, and the emission is the fifth form's.
 // ---------------------------------------------------------------------------------------------
 #define HX_LATE_LDS(cap) ((size_t)(cap) * 36)
+#define HX_DOCS_CHUNK 1024
+#define HX_DOCS_LDS(n_in, n_vecs) ((size_t)HX_DOCS_MAX_IN * 28 + (size_t)HX_DOCS_CHUNK * 8 + (size_t)(n_in) * (n_vecs) * 4)
 template <int KIND>
 __device__ __forceinline__ void late_interaction(const DevView &v, const DiverseLists &d, float *yq, unsigned char *tab, int lane) {
     constexpr int LPC = (KIND == HNSW_VEC_QUANT8) ? 2 : 1;
     constexpr int CHUNK = 64 / LPC;
     constexpr uint32_t INF_BITS = 0x7F800000u, NONE = 0xFFFFFFFFu, LATER = 0x80000000u;
     const int h = (LPC == 2) ? (lane & 1) : 0;
+    const bool docs = d.docs != 0;  // (a kernel argument: every branch on it is the wave's)
     const uint32_t q = blockIdx.x, T = d.n_vecs, pool = d.pool, n_out = d.n_out;
-    if (q >= d.nq || T > HX_LATE_MAX_VECS || pool > HX_LATE_MAX_CANDS || T * pool > HX_LATE_MAX_CANDS ||
-        n_out > HX_LATE_MAX_DOCS || n_out > T * pool)
-        return;  // (the launcher's limits)
-    const uint32_t total = T * pool, cap = (total + 63u) & ~63u;
-    uint32_t *sid = reinterpret_cast<uint32_t *>(tab);
-    uint32_t *cid = sid + cap, *cdoc = cid + cap, *dlab = cdoc + cap, *dmin = dlab + cap;
-    float *dsum = reinterpret_cast<float *>(dmin + cap);
-    uint32_t *dsize = dmin + 2 * cap;
-    u64 *dbest = reinterpret_cast<u64 *>(dsize + cap);  // (28 * cap bytes in: 8-byte aligned)
+    if (q >= d.nq || T > HX_LATE_MAX_VECS) return;  // (the launcher's limits, here and below)
+    if (docs ? (pool > HX_DOCS_MAX_IN || n_out > pool || d.rows_cap == 0 || d.rows_cap > HX_DOCS_MAX_ROWS)
+             : (pool > HX_LATE_MAX_CANDS || T * pool > HX_LATE_MAX_CANDS || n_out > HX_LATE_MAX_DOCS || n_out > T * pool))
+        return;
+    const uint32_t total = docs ? pool : T * pool, cap = (total + 63u) & ~63u;
+    uint32_t *sid, *cid, *cdoc, *dlab, *dmin, *dsize, *dstart, *dpre;
+    float *dsum;
+    u64 *dbest;
+    if (docs) {
+        dbest = reinterpret_cast<u64 *>(tab);
+        dlab = reinterpret_cast<uint32_t *>(dbest + HX_DOCS_MAX_IN);
+        dstart = dlab + HX_DOCS_MAX_IN, dsize = dstart + HX_DOCS_MAX_IN, dpre = dsize + HX_DOCS_MAX_IN;
+        dsum = reinterpret_cast<float *>(dpre + HX_DOCS_MAX_IN);
+        cid = dpre + 2 * HX_DOCS_MAX_IN, cdoc = cid + HX_DOCS_CHUNK, dmin = cdoc + HX_DOCS_CHUNK;
+        sid = cid;  // (the labels as loaded: they have served before the first chunk is laid out)
+    } else {
+        sid = reinterpret_cast<uint32_t *>(tab);
+        cid = sid + cap, cdoc = cid + cap, dlab = cdoc + cap, dmin = dlab + cap;
+        dsum = reinterpret_cast<float *>(dmin + cap);
+        dsize = dmin + 2 * cap;
+        dbest = reinterpret_cast<u64 *>(dsize + cap);  // (28 * cap bytes in: 8-byte aligned)
+        dstart = dpre = nullptr;
+    }
     const size_t l0 = (size_t)q * T, in0 = (size_t)q * total, out0 = (size_t)q * n_out;
     hnsw_query_stats st;
     st.n_dist = st.n_exp = st.sum_deg = 0;
     st.status = HNSW_OK;
-    if (d.stats)
-        for (uint32_t t = 0; t < T; t++) {  // (wave-uniform: the wrapping sums, the first status that is not OK)
-            const hnsw_query_stats s = d.stats[l0 + t];
-            st.n_dist += s.n_dist, st.n_exp += s.n_exp, st.sum_deg += s.sum_deg;
-            if (st.status == HNSW_OK) st.status = s.status;
+    if (d.stats) {
+        if (docs) {
+            st = d.stats[q];  // (one record per list)
+        } else {
+            for (uint32_t t = 0; t < T; t++) {  // (wave-uniform: the wrapping sums, the first status that is not OK)
+                const hnsw_query_stats s = d.stats[l0 + t];
+                st.n_dist += s.n_dist, st.n_exp += s.n_exp, st.sum_deg += s.sum_deg;
+                if (st.status == HNSW_OK) st.status = s.status;
+            }
         }
-    const bool ok = st.status == HNSW_OK;  // a failed query has no present entry: count 0 and padded rows
-    bool beyond = false;
-    for (uint32_t j = lane; j < cap; j += 64) {
-        uint32_t id = HX_EMPTY_SLOT;
-        if (j < total) {
-            const uint32_t t = j / pool, jj = j - t * pool;
-            const uint32_t raw = d.ids[in0 + j];
-            const bool present = ok && (d.counts ? jj < min(d.counts[l0 + t], pool) : raw != HX_EMPTY_SLOT);
-            beyond |= present && raw >= v.n_points;
-            id = present ? raw : HX_EMPTY_SLOT;
-        }
-        sid[j] = id;
     }
-    wave_fence();
-    uint32_t count = 0, unique = 0, n_docs = 0;  // wave-uniform
-    if (__ballot(beyond)) {
-        st.status = HNSW_ERR_ARG;  // no row of the index is read for this query
-    } else if (ok) {
-        for (uint32_t base = 0; base < total; base += 64) {  // the distinct present ids, in table order, to cid[0 .. unique)
-            const uint32_t j = base + lane, id = sid[j], end = min(total, base + 64);
+    const bool ok = st.status == HNSW_OK;  // a failed query has no present entry: count 0 and padded rows
+    uint32_t count = 0, unique = 0, n_docs = 0, n_rows = 0;  // wave-uniform
+    bool walk = false;                                       // the passes run
+    if (docs) {
+        bool bad = false;  // a NaN in any of the T vectors, before any index row is read
+        if (ok) {
+            const float *qv = d.queries + l0 * v.dim;
+            for (uint32_t e = lane; e < T * v.dim; e += 64) {
+                const float x = qv[e];
+                bad |= (x != x);
+            }
+        }
+        const bool nan = __ballot(bad) != 0;
+        if (nan) st.status = HNSW_ERR_NAN_INPUT;
+        const uint32_t cnt = ok && !nan ? (d.counts ? min(d.counts[q], pool) : pool) : 0u;  // the present entries: a prefix
+        for (uint32_t j = lane; j < cap; j += 64) sid[j] = j < cnt ? d.ids[in0 + j] : 0u;
+        wave_fence();
+        const uint64_t *keys = d.doc_keys;
+        for (uint32_t base = 0; base < cnt; base += 64) {  // the distinct present labels that have a row, in list order
+            const uint32_t j = base + lane, lab = sid[j], end = min(cnt, base + 64);
             bool dup = false;
-            for (uint32_t i = 0; i < end; i += 4) {  // (the table is EMPTY from `total` to cap)
+            for (uint32_t i = 0; i < end; i += 4) {  // (a word at or behind cnt is never before a present j)
                 const uint4 w = *reinterpret_cast<const uint4 *>(sid + i);
-                dup |= (w.x == id && i < j) | (w.y == id && i + 1 < j) | (w.z == id && i + 2 < j) | (w.w == id && i + 3 < j);
+                dup |= (w.x == lab && i < j) | (w.y == lab && i + 1 < j) | (w.z == lab && i + 2 < j) | (w.w == lab && i + 3 < j);
             }
-            const bool live = id != HX_EMPTY_SLOT && !dup;
-            const u64 b = __ballot(live);
-            if (live) cid[unique + __builtin_popcountll(b & ((1ull << lane) - 1))] = id;
-            unique += (uint32_t)__builtin_popcountll(b);
-        }
-        wave_fence();
-        uint32_t *clab = sid;  // (the entries have served)
-        const uint64_t label_len = d.labels ? d.label_len : 0;
-        for (uint32_t j = lane; j < unique; j += 64) {
-            const uint32_t c = cid[j];
-            clab[j] = c < label_len ? d.labels[c] : 0u;
-        }
-        wave_fence();
-        for (uint32_t base = 0; base < unique; base += 64) {  // the distinct labels, in candidate order, to dlab[0 .. n_docs)
-            const uint32_t j = base + lane, lab = clab[j], end = min(unique, base + 64);
-            const bool live = j < unique;
-            uint32_t fi = NONE;  // the first candidate before j with j's label
-            for (uint32_t i = 0; i < end; i += 4) {  // (a word at or behind `unique` is never before a live j)
-                const uint4 w = *reinterpret_cast<const uint4 *>(clab + i);
-                fi = min(fi, w.x == lab && i < j ? i : NONE);
-                fi = min(fi, w.y == lab && i + 1 < j ? i + 1 : NONE);
-                fi = min(fi, w.z == lab && i + 2 < j ? i + 2 : NONE);
-                fi = min(fi, w.w == lab && i + 3 < j ? i + 3 : NONE);
+            const bool live = j < cnt && !dup;
+            // the slice of the label's keys: [first key >= label << 32, first key > label << 32 | 0xFFFFFFFF)
+            const u64 klo = (u64)lab << 32, khi = klo | 0xFFFFFFFFull;
+            u64 a = 0, b = live ? d.n_doc_keys : 0;
+            while (a < b) {
+                const u64 m = (a + b) >> 1;
+                if (keys[m] < klo) a = m + 1; else b = m;
             }
-            const bool first = live && fi == NONE;
-            const u64 b = __ballot(first);
-            if (first) {
-                const uint32_t g = n_docs + (uint32_t)__builtin_popcountll(b & ((1ull << lane) - 1));
-                cdoc[j] = g;
+            const u64 first = a;
+            b = live ? d.n_doc_keys : first;
+            while (a < b) {
+                const u64 m = (a + b) >> 1;
+                if (keys[m] <= khi) a = m + 1; else b = m;
+            }
+            const uint32_t size = (uint32_t)(a - first);  // (ids are 32-bit and distinct: below 2^32)
+            const bool has = live && size != 0;           // a label without a row is not a document
+            const u64 bal = __ballot(has);
+            if (has) {
+                const uint32_t g = n_docs + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1));
                 dlab[g] = lab;
-                dmin[g] = INF_BITS;
-                dsum[g] = 0.0f;
-                dsize[g] = 0u;
+                dstart[g] = (uint32_t)first;
+                dsize[g] = size;
+                dpre[g] = min(size, d.rows_cap);  // (summed below)
                 dbest[g] = KEY_INVALID;
-            } else if (live) {
-                cdoc[j] = fi | LATER;  // (resolved below, once the first's document is numbered)
             }
-            n_docs += (uint32_t)__builtin_popcountll(b);
+            n_docs += (uint32_t)__builtin_popcountll(bal);
         }
         wave_fence();
-        for (uint32_t j = lane; j < unique; j += 64) {
-            uint32_t g = cdoc[j];
-            if (g & LATER) {
-                g = cdoc[g & ~LATER];  // (a first's entry: not rewritten here)
-                cdoc[j] = g;
+        for (uint32_t base = 0; base < n_docs; base += 64) {  // dpre[g] = the scored rows of the documents before g
+            const uint32_t g = base + lane, x = g < n_docs ? dpre[g] : 0u;
+            uint32_t incl = x;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t y = (uint32_t)__shfl_up((int)incl, o);
+                if (lane >= o) incl += y;
             }
-            atomicAdd(&dsize[g], 1u);
+            if (g < n_docs) dpre[g] = n_rows + incl - x;
+            n_rows += (uint32_t)__shfl((int)incl, 63);
+        }
+        for (uint32_t i = lane; i < n_docs * T; i += 64) dmin[i] = INF_BITS;
+        wave_fence();
+        walk = n_rows != 0;
+    } else {
+        bool beyond = false;
+        for (uint32_t j = lane; j < cap; j += 64) {
+            uint32_t id = HX_EMPTY_SLOT;
+            if (j < total) {
+                const uint32_t t = j / pool, jj = j - t * pool;
+                const uint32_t raw = d.ids[in0 + j];
+                const bool present = ok && (d.counts ? jj < min(d.counts[l0 + t], pool) : raw != HX_EMPTY_SLOT);
+                beyond |= present && raw >= v.n_points;
+                id = present ? raw : HX_EMPTY_SLOT;
+            }
+            sid[j] = id;
         }
         wave_fence();
-        bool nan = false;  // wave-uniform
-        for (uint32_t t = 0; t < T; t++) {
-            if (!stage_query<KIND>(v, d.queries + (l0 + t) * v.dim, yq, lane)) {
-                nan = true;
-                break;
+        if (__ballot(beyond)) {
+            st.status = HNSW_ERR_ARG;  // no row of the index is read for this query
+        } else if (ok) {
+            walk = true;
+            for (uint32_t base = 0; base < total; base += 64) {  // the distinct present ids, in table order, to cid[0 .. unique)
+                const uint32_t j = base + lane, id = sid[j], end = min(total, base + 64);
+                bool dup = false;
+                for (uint32_t i = 0; i < end; i += 4) {  // (the table is EMPTY from `total` to cap)
+                    const uint4 w = *reinterpret_cast<const uint4 *>(sid + i);
+                    dup |= (w.x == id && i < j) | (w.y == id && i + 1 < j) | (w.z == id && i + 2 < j) | (w.w == id && i + 3 < j);
+                }
+                const bool live = id != HX_EMPTY_SLOT && !dup;
+                const u64 b = __ballot(live);
+                if (live) cid[unique + __builtin_popcountll(b & ((1ull << lane) - 1))] = id;
+                unique += (uint32_t)__builtin_popcountll(b);
             }
-            for (uint32_t base = 0; base < unique; base += CHUNK) {
-                const uint32_t j = base + lane / LPC;
-                const bool active = j < unique;
-                const uint32_t id = active ? cid[j] : 0u;
-                const float dist = dist_any_dim<KIND>(v, id, active, h, yq);
-                if (active && h == 0 && dist == dist) {  // (a NaN leaves the minimum and the best row as they are)
-                    const uint32_t bits = __builtin_bit_cast(uint32_t, dist), g = cdoc[j];
-                    atomicMin(&dmin[g], bits);
-                    atomicMin(&dbest[g], ((u64)bits << 32) | id);
+            wave_fence();
+            uint32_t *clab = sid;  // (the entries have served)
+            const uint64_t label_len = d.labels ? d.label_len : 0;
+            for (uint32_t j = lane; j < unique; j += 64) {
+                const uint32_t c = cid[j];
+                clab[j] = c < label_len ? d.labels[c] : 0u;
+            }
+            wave_fence();
+            for (uint32_t base = 0; base < unique; base += 64) {  // the distinct labels, in candidate order, to dlab[0 .. n_docs)
+                const uint32_t j = base + lane, lab = clab[j], end = min(unique, base + 64);
+                const bool live = j < unique;
+                uint32_t fi = NONE;  // the first candidate before j with j's label
+                for (uint32_t i = 0; i < end; i += 4) {  // (a word at or behind `unique` is never before a live j)
+                    const uint4 w = *reinterpret_cast<const uint4 *>(clab + i);
+                    fi = min(fi, w.x == lab && i < j ? i : NONE);
+                    fi = min(fi, w.y == lab && i + 1 < j ? i + 1 : NONE);
+                    fi = min(fi, w.z == lab && i + 2 < j ? i + 2 : NONE);
+                    fi = min(fi, w.w == lab && i + 3 < j ? i + 3 : NONE);
+                }
+                const bool first = live && fi == NONE;
+                const u64 b = __ballot(first);
+                if (first) {
+                    const uint32_t g = n_docs + (uint32_t)__builtin_popcountll(b & ((1ull << lane) - 1));
+                    cdoc[j] = g;
+                    dlab[g] = lab;
+                    dmin[g] = INF_BITS;
+                    dsum[g] = 0.0f;
+                    dsize[g] = 0u;
+                    dbest[g] = KEY_INVALID;
+                } else if (live) {
+                    cdoc[j] = fi | LATER;  // (resolved below, once the first's document is numbered)
+                }
+                n_docs += (uint32_t)__builtin_popcountll(b);
+            }
+            wave_fence();
+            for (uint32_t j = lane; j < unique; j += 64) {
+                uint32_t g = cdoc[j];
+                if (g & LATER) {
+                    g = cdoc[g & ~LATER];  // (a first's entry: not rewritten here)
+                    cdoc[j] = g;
+                }
+                atomicAdd(&dsize[g], 1u);
+            }
+            wave_fence();
+        }
+    }
+    if (walk) {
+        bool nan = false;                // wave-uniform
+        uint32_t c0 = 0, n_e = unique;  // the entries of cid / cdoc: the candidates, or the chunk in hand
+        do {
+            if (docs) {  // rows c0 .. c0 + n_e of the documents' scored rows, in document order
+                n_e = min((uint32_t)HX_DOCS_CHUNK, n_rows - c0);
+                for (uint32_t j = lane; j < n_e; j += 64) {
+                    const uint32_t r = c0 + j;
+                    uint32_t lo = 0, hi = n_docs;  // the last document with dpre <= r (dpre[0] is 0; no scored size is 0)
+                    while (hi - lo > 1) {
+                        const uint32_t m = (lo + hi) >> 1;
+                        if (dpre[m] <= r) lo = m; else hi = m;
+                    }
+                    cdoc[j] = lo;
+                    // the id is the key's low word (little-endian)
+                    cid[j] = reinterpret_cast<const uint32_t *>(d.doc_keys)[2 * ((u64)dstart[lo] + (r - dpre[lo]))];
+                }
+                wave_fence();
+            }
+            const uint32_t stride = docs ? T : 1u;
+            for (uint32_t t = 0; t < T; t++) {
+                if (!stage_query<KIND>(v, d.queries + (l0 + t) * v.dim, yq, lane)) {  // (never in the seventh form)
+                    nan = true;
+                    break;
+                }
+                const uint32_t col = docs ? t : 0u;
+                for (uint32_t base = 0; base < n_e; base += CHUNK) {
+                    const uint32_t j = base + lane / LPC;
+                    const uint32_t id = j < n_e ? cid[j] : 0u;
+                    // (a key's id is below the index length the keys were made for: the snapshot's)
+                    const bool active = j < n_e && id < v.n_points;
+                    const float dist = dist_any_dim<KIND>(v, active ? id : 0u, active, h, yq);
+                    if (active && h == 0 && dist == dist) {  // (a NaN leaves the minimum and the best row as they are)
+                        const uint32_t bits = __builtin_bit_cast(uint32_t, dist), g = cdoc[j];
+                        atomicMin(&dmin[g * stride + col], bits);
+                        atomicMin(&dbest[g], ((u64)bits << 32) | id);
+                    }
+                }
+                wave_fence();
+                if (!docs) {
+                    for (uint32_t g = lane; g < n_docs; g += 64) {
+                        const float m = __builtin_bit_cast(float, dmin[g]);
+                        const float e = d.mode == HNSW_LATE_SUM_SQ ? m * m : m;
+                        dsum[g] = t == 0 ? e : dsum[g] + e;
+                        dmin[g] = INF_BITS;
+                    }
+                    wave_fence();
                 }
             }
-            wave_fence();
-            for (uint32_t g = lane; g < n_docs; g += 64) {
-                const float m = __builtin_bit_cast(float, dmin[g]);
-                const float e = d.mode == HNSW_LATE_SUM_SQ ? m * m : m;
-                dsum[g] = t == 0 ? e : dsum[g] + e;
-                dmin[g] = INF_BITS;
-            }
-            wave_fence();
-        }
+            c0 += HX_DOCS_CHUNK;
+        } while (docs && !nan && c0 < n_rows);
         if (nan) {
             st.status = HNSW_ERR_NAN_INPUT;
             n_docs = 0;
         } else {
+            if (docs) {  // the owner lane of a document folds its minima in vector order
+                for (uint32_t g = lane; g < n_docs; g += 64) {
+                    float s = 0.0f;
+                    for (uint32_t t = 0; t < T; t++) {
+                        const float m = __builtin_bit_cast(float, dmin[g * T + t]);
+                        const float e = d.mode == HNSW_LATE_SUM_SQ ? m * m : m;
+                        s = t == 0 ? e : s + e;
+                    }
+                    dsum[g] = s;
+                }
+                wave_fence();
+            }
             for (uint32_t t = 0; t < n_out; t++) {
                 u64 mine = KEY_INVALID;
                 uint32_t mg = 0;
@@ -835,11 +979,12 @@ hx_distance_kernel(const DevView v, const float *q, const uint32_t *ids, uint64_
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float *yq = reinterpret_cast<float *>(smem);
     const int lane = threadIdx.x;
-    if (dv.table) {  // (looked at first of all: this form sets n_out too, and reads nothing of v)
+    const bool docs = dv.docs != 0;  // (looked at first of all: the document scoring, late_interaction's other half)
+    if (!docs && dv.table) {  // (looked at first of the others: this form sets n_out too, and reads nothing of v)
         refine_lists(dv, smem, lane);
         return;
     }
-    if (dv.late) {  // (looked at first: this form sets n_vecs and n_out too)
+    if (docs || dv.late) {  // (looked at first: these forms set n_vecs and n_out too)
         late_interaction<KIND>(v, dv, yq, smem + query_lds_bytes(v), lane);
         return;
     }
@@ -1018,6 +1163,25 @@ int launch_late_interaction(const DevView &v, DiverseLists d, hipStream_t stream
                           dim3(d.nq), dim3(64), query_lds_bytes(v) + HX_LATE_LDS(cap), stream, v, static_cast<const float *>(nullptr),
                           static_cast<const uint32_t *>(nullptr), (uint64_t)0, static_cast<float *>(nullptr),
                           static_cast<int32_t *>(nullptr), d);
+}
+
+int launch_score_documents(const DevView &v, DiverseLists d, hipStream_t stream) {
+    if (d.nq == 0) return HNSW_OK;
+    if (d.n_vecs == 0 || d.n_vecs > HX_LATE_MAX_VECS || d.n_out == 0 || d.n_out > d.pool || d.pool > HX_DOCS_MAX_IN ||
+        d.rows_cap == 0 || d.rows_cap > HX_DOCS_MAX_ROWS || d.mode > HNSW_LATE_SUM_SQ || d.nq > 0x7FFFFFFFu || !d.queries ||
+        !d.ids || !d.doc_keys || !d.out_ids || !d.out_dists || (d.stats != nullptr) != (d.out_stats != nullptr)) {
+        set_error("score documents: needs 1 <= n_vecs <= %d, 1 <= n_out <= n_in <= %d, 1 <= rows_cap <= %u, a mode, at most "
+                  "2^31 - 1 queries, the vectors, the labels, the document index and the outputs", HX_LATE_MAX_VECS,
+                  HX_DOCS_MAX_IN, HX_DOCS_MAX_ROWS);
+        return HNSW_ERR_ARG;
+    }
+    d.docs = 1;
+    d.late = 0, d.table = nullptr;
+    return launch_checked({"score documents kernel launch", "score documents: the staged vector and the tables need %zu bytes of LDS"},
+                          v.kind == HNSW_VEC_QUANT8 ? hx_distance_kernel<HNSW_VEC_QUANT8> : hx_distance_kernel<HNSW_VEC_F32>,
+                          dim3(d.nq), dim3(64), query_lds_bytes(v) + HX_DOCS_LDS(d.pool, d.n_vecs), stream, v,
+                          static_cast<const float *>(nullptr), static_cast<const uint32_t *>(nullptr), (uint64_t)0,
+                          static_cast<float *>(nullptr), static_cast<int32_t *>(nullptr), d);
 }
 
 int launch_refine(DiverseLists d, hipStream_t stream) {

@@ -86,6 +86,9 @@ struct hnsw_index {
     // late-interaction search: hnsw_search_batch_late calls answered, and the late interactions launched
     // (hnsw_late_interaction_device's too)
     std::atomic<uint64_t> n_late_calls{0}, n_late_launches{0};
+    // exact document scoring: hnsw_search_batch_late_exact calls answered, and the scorings launched
+    // (hnsw_score_documents_device's too)
+    std::atomic<uint64_t> n_docs_calls{0}, n_docs_launches{0};
     // refined search: hnsw_search_batch_refined calls answered and the refinements they launched (hnsw_refine_device takes
     // no handle), and the writes that reached a row table of this handle
     std::atomic<uint64_t> n_refine_calls{0}, n_refine_launches{0}, n_row_table_writes{0};

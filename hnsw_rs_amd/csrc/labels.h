@@ -19,6 +19,27 @@
 
 namespace hx {
 
+// The document index in HBM (docs.cpp): a copy of LabelColumn::sorted, 8 bytes per undeleted id, made whole whenever the
+// (label version, deleted version, length) it was made for is no longer the sorted copy's.  Derived from the column and
+// the deleted set: not saved, no part of the snapshot exchange.
+struct DocIndex {
+    uint64_t *d_keys = nullptr;
+    uint64_t cap = 0, n = 0;  // keys allocated, keys held
+    int device = -1;
+    uint64_t version = ~0ull, del = 0, len = 0;  // what the copy was made for
+    uint64_t uploads = 0, keys_uploaded = 0;     // hnsw_get_stat "doc_index_uploads", "doc_index_keys_uploaded"
+    DocIndex() = default;
+    DocIndex(const DocIndex &) = delete;
+    DocIndex &operator=(const DocIndex &) = delete;
+    ~DocIndex() { release(); }
+    void release() {
+        if (d_keys) (void)hipFree(d_keys);
+        d_keys = nullptr;
+        cap = n = 0;
+        device = -1;
+    }
+};
+
 struct LabelColumn : HbmWords {
     // label of id i is labels[i], 0 at and beyond labels.size(); the size is even: word w of the HBM copy is
     // labels[2 w] | labels[2 w + 1] << 32 (little-endian), so the device reads the copy as a plain uint32 array
@@ -43,6 +64,11 @@ struct LabelColumn : HbmWords {
                           stream);  // room for later inserts
     }
     const uint32_t *d_labels() const { return reinterpret_cast<const uint32_t *>(d_words); }
+    // both HBM copies go (hnsw_set_device, assign_host): each is made afresh on its first use
+    void release_device() {
+        HbmWords::release_device();
+        doc.release();
+    }
 
     // ---- the range planner's view (mu held): the keys label << 32 | id of the undeleted ids below len, ascending.
     // Made by one sort when the column, the deleted set or the length changed; then the admissible ids of a range are
@@ -51,6 +77,7 @@ struct LabelColumn : HbmWords {
     std::vector<uint64_t> sorted;
     uint64_t s_version = ~0ull, s_del = 0, s_len = 0;
     void sort_for(const DeletedSet &del, uint64_t len);
+    DocIndex doc;  // the HBM copy of `sorted` (mu held)
     // admissible ids of [lo, hi] (sort_for first): the slice [first, first + A) of `sorted`
     uint64_t count(uint32_t lo, uint32_t hi, uint64_t *first = nullptr) const;
     // ... and how many of them lie before every block of 64 words (4096 ids): the compaction kernel's offsets

@@ -34,12 +34,15 @@ int check_late_shape(const char *what, const char *n, uint32_t n_vecs, uint32_t 
     return HNSW_OK;
 }
 
+}  // namespace
+
 // the late interaction over lists already in HBM, d_Q as the kernel stages it (unit length under the cosine option): the
-// label column brought up to date, then the one launch
-int score(hnsw_index *h, uint64_t nq, uint32_t n_vecs, uint32_t pool, uint32_t n_out, uint32_t mode, const float *d_Q,
-          const uint32_t *d_ids_in, const uint32_t *d_counts_in, const hnsw_query_stats *d_stats_in, uint32_t *d_doc_labels,
-          float *d_scores, uint32_t *d_best_ids, uint32_t *d_doc_sizes, uint32_t *d_counts, uint32_t *d_n_docs,
-          hnsw_query_stats *d_stats, hipStream_t stream) {
+// label column brought up to date, then the one launch (lists_host.h: docs.cpp's composed search launches it too)
+int hx::late_interaction_lists(hnsw_index *h, uint64_t nq, uint32_t n_vecs, uint32_t pool, uint32_t n_out, uint32_t mode,
+                               const float *d_Q, const uint32_t *d_ids_in, const uint32_t *d_counts_in,
+                               const hnsw_query_stats *d_stats_in, uint32_t *d_doc_labels, float *d_scores,
+                               uint32_t *d_best_ids, uint32_t *d_doc_sizes, uint32_t *d_counts, uint32_t *d_n_docs,
+                               hnsw_query_stats *d_stats, hipStream_t stream) {
     hx::DiverseLists d{};
     if (int rc = hx::labels_on_device(h, &d.labels, &d.label_len)) return rc;
     d.ids = d_ids_in;
@@ -63,8 +66,6 @@ int score(hnsw_index *h, uint64_t nq, uint32_t n_vecs, uint32_t pool, uint32_t n
     return HNSW_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 int hnsw_late_interaction_device(hnsw_index *h, uint64_t nq, uint32_t n_vecs, uint32_t pool, uint32_t n_out, uint32_t mode,
@@ -85,8 +86,8 @@ int hnsw_late_interaction_device(hnsw_index *h, uint64_t nq, uint32_t n_vecs, ui
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     hx::DeviceQueries dq;  // the caller's vectors are const to us: the unit-length copy under the cosine option
     if (int rc = dq.prepare(h, d_Q, nq * n_vecs, stream)) return rc;
-    return score(h, nq, n_vecs, pool, n_out, mode, dq.q, d_ids_in, d_counts_in, d_stats_in, d_doc_labels, d_scores, d_best_ids,
-                 d_doc_sizes, d_counts, d_n_docs, d_stats, stream);
+    return hx::late_interaction_lists(h, nq, n_vecs, pool, n_out, mode, dq.q, d_ids_in, d_counts_in, d_stats_in, d_doc_labels,
+                                      d_scores, d_best_ids, d_doc_sizes, d_counts, d_n_docs, d_stats, stream);
 }
 
 int hnsw_search_batch_late(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n_vecs, uint32_t mode, uint32_t n,
@@ -135,10 +136,11 @@ int hnsw_search_batch_late(hnsw_index *h, const float *Q, uint64_t nq, uint32_t 
         rc = hx::device_candidates(v, d_Q, rows, pool, efp, nullptr, 0, c, hx::at<uint32_t>(dv, o_resel), sc.stream, hv);
     if (rc != HNSW_OK) return rc;
     unsigned char *d_out = dv + o_out;
-    rc = score(h, nq, n_vecs, pool, n, mode, d_Q, c.ids, c.counts, c.stats, hx::at<uint32_t>(d_out, c_labels),
-               hx::at<float>(d_out, c_scores), hx::at<uint32_t>(d_out, c_best), hx::at<uint32_t>(d_out, c_sizes),
-               hx::at<uint32_t>(d_out, c_counts), hx::at<uint32_t>(d_out, c_n_docs), hx::at<hnsw_query_stats>(d_out, c_stats),
-               sc.stream);
+    rc = hx::late_interaction_lists(h, nq, n_vecs, pool, n, mode, d_Q, c.ids, c.counts, c.stats,
+                                    hx::at<uint32_t>(d_out, c_labels), hx::at<float>(d_out, c_scores),
+                                    hx::at<uint32_t>(d_out, c_best), hx::at<uint32_t>(d_out, c_sizes),
+                                    hx::at<uint32_t>(d_out, c_counts), hx::at<uint32_t>(d_out, c_n_docs),
+                                    hx::at<hnsw_query_stats>(d_out, c_stats), sc.stream);
     if (rc != HNSW_OK) return rc;
     return hx::bring_back(out, d_out, hv + p_out, sc.stream, h->n_late_calls,
                           {doc_labels, scores, best_ids, doc_sizes, counts, n_docs, stats}, nq);

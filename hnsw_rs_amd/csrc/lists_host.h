@@ -1,5 +1,5 @@
 // lists_host.h -- the candidate stage of the search-then-post-process entry points (grouped, radius, diverse,
-// from_rows, multi, late, refine, partition .cpp): every one of them checks the call, gets candidate lists of rows x pool into
+// from_rows, multi, late, docs, refine, partition .cpp): every one of them checks the call, gets candidate lists of rows x pool into
 // HBM, runs ONE post-process launch, brings a column block back in one copy and scatters its columns into the caller's
 // buffers.  Everything but the launch is here, once (internal; DESIGN.md, "The candidate stage")
 #pragma once
@@ -63,6 +63,15 @@ int queries_up(const hnsw_index *h, float *d_Q, const float *Q, uint64_t rows, h
 int device_candidates(const DevView &v, const float *d_Q, uint64_t rows, uint32_t n, uint32_t ef, const uint32_t *d_qsel,
                       uint32_t n_launched, const ResultBlock::Ptrs &c, uint32_t *d_resel, hipStream_t stream,
                       void *pin_stats);
+
+// ---- a post-process stage two entry points launch ----------------------------------------------------------------
+// late.cpp: THE LATE INTERACTION over lists already in HBM, d_Q as the kernel stages it (unit length under the cosine
+// option): the label column brought up to date, ONE launch on `stream`, "late_launches" bumped
+int late_interaction_lists(hnsw_index *h, uint64_t nq, uint32_t n_vecs, uint32_t pool, uint32_t n_out, uint32_t mode,
+                           const float *d_Q, const uint32_t *d_ids_in, const uint32_t *d_counts_in,
+                           const hnsw_query_stats *d_stats_in, uint32_t *d_doc_labels, float *d_scores, uint32_t *d_best_ids,
+                           uint32_t *d_doc_sizes, uint32_t *d_counts, uint32_t *d_n_docs, hnsw_query_stats *d_stats,
+                           hipStream_t stream);
 
 // ---- the column block a post-process launch writes -----------------------------------------------------------------
 // Columns of any length, each aligned to 256 bytes, the same layout in the device arena and in pinned memory, so the

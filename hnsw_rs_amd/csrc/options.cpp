@@ -118,6 +118,10 @@ const Stat kStats[] = {
     HX_STAT("multi_fuse_launches", h.n_multi_fuse),
     HX_STAT("late_calls", h.n_late_calls),
     HX_STAT("late_launches", h.n_late_launches),
+    HX_STAT("docs_calls", h.n_docs_calls),
+    HX_STAT("docs_launches", h.n_docs_launches),
+    HX_STAT("doc_index_uploads", h.lab.doc.uploads),
+    HX_STAT("doc_index_keys_uploaded", h.lab.doc.keys_uploaded),
     HX_STAT("refine_calls", h.n_refine_calls),
     HX_STAT("refine_launches", h.n_refine_launches),
     HX_STAT("row_table_writes", h.n_row_table_writes),

@@ -764,6 +764,44 @@ class HNSW:
             self._h, nq, n_vecs, pool, n_out, mode_of(mode), p(d_Q), p(d_ids_in), p(d_counts_in), p(d_stats_in),
             p(d_doc_labels), p(d_scores), p(d_best_ids), p(d_doc_sizes), p(d_counts), p(d_n_docs), p(d_stats), stream or None))
 
+    # ---- exact document scoring: late interaction over every stored row (include/hnsw_mi355x.h) ----------------------
+    def search_batch_late_exact(self, Q, n, n_cand, pool, ef, mode="sum", rows_cap=_lib.DOCS_MAX_ROWS):
+        """search_batch_late with every returned document scored over ALL its undeleted rows: the n_cand best documents
+        of the late interaction over the pools are scored again over their min(size, rows_cap) lowest ids, and the n best
+        of them returned: docs.score_documents of late.late_interaction's labels (hnsw_search_batch_late_exact).
+        -> doc_labels [nq, n] (pad 0), scores [nq, n] (pad +inf), best_ids [nq, n] (pad UINT32_MAX), doc_sizes [nq, n]
+        (pad 0: the full size), counts [nq], n_docs [nq], stats [nq, 4] (the summed counters of the T searches)"""
+        from .late import mode_of
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 3 or Q.shape[2] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x T x %d" % self.dim)
+        nq, T = Q.shape[0], Q.shape[1]
+        width = max(int(n), 1)
+        labels = np.zeros((nq, width), dtype=np.uint32)
+        scores = np.full((nq, width), np.inf, dtype=np.float32)
+        best = np.full((nq, width), _lib.UINT32_MAX, dtype=np.uint32)
+        sizes = np.zeros((nq, width), dtype=np.uint32)
+        counts, n_docs = np.zeros(nq, dtype=np.uint32), np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        check(self._L.hnsw_search_batch_late_exact(
+            self._h, _p(Q, _f32p), nq, T, mode_of(mode), n, n_cand, rows_cap, pool, ef, _p(labels, _u32p), _p(scores, _f32p),
+            _p(best, _u32p), _p(sizes, _u32p), _p(counts, _u32p), _p(n_docs, _u32p),
+            C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
+        return labels, scores, best, sizes, counts, n_docs, stats.view(np.uint32).astype(np.int64)
+
+    def score_documents_device(self, nq, n_vecs, n_in, n_out, rows_cap, mode, d_Q, d_docs_in, d_counts_in, d_stats_in,
+                               d_doc_labels, d_scores, d_best_ids=None, d_doc_sizes=None, d_counts=None, d_n_docs=None,
+                               d_stats=None, stream=0):
+        """hnsw_score_documents_device over torch device tensors (or raw device pointers): d_Q float32 [nq, n_vecs, dim]
+        and the [nq, n_in] document LABELS (d_counts_in / d_stats_in [nq] or None), every document scored over its
+        min(size, rows_cap) lowest undeleted ids into d_doc_labels / d_scores [nq, n_out] (/ d_best_ids / d_doc_sizes /
+        d_counts / d_n_docs / d_stats).  ONE launch enqueued on `stream`, no sync of it."""
+        from .late import mode_of
+        p = self._dptr
+        check(self._L.hnsw_score_documents_device(
+            self._h, nq, n_vecs, n_in, n_out, rows_cap, mode_of(mode), p(d_Q), p(d_docs_in), p(d_counts_in), p(d_stats_in),
+            p(d_doc_labels), p(d_scores), p(d_best_ids), p(d_doc_sizes), p(d_counts), p(d_n_docs), p(d_stats), stream or None))
+
     # ---- refined search: the pool re-scored against full rows kept in HBM (include/hnsw_mi355x.h) -------------------
     def row_table(self, full_dim, dtype="f32"):
         """-> refine.RowTable: full rows of full_dim elements, "f32" or "f16", that live in HBM beside this index, row id =

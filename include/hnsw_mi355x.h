@@ -990,9 +990,10 @@ int hnsw_search_batch_multi(hnsw_index *h, const float *Q /* nq x n_vecs x dim *
  * touched: the limits violated; a mode other than the two; Q or doc_labels NULL; nq * T > 2^31 - 1.  nq == 0 is HNSW_OK;
  * an empty index is HNSW_ERR_EMPTY.  hnsw_get_stat: "late_calls" (hnsw_search_batch_late calls answered), "late_launches"
  * (late interactions launched, hnsw_late_interaction_device's included).
- * Not provided: completing a document with its rows that are in no pool; a different T per query, or a mask over a
- * query's vectors; weights per vector; filters other than deletions in the host entry (the primitive chains with the
- * filtered *_device searches); late interaction over shards; one-query gathered calls; the Rust shim's binding. */
+ * Completing a document with its rows that are in no pool is hnsw_search_batch_late_exact ("exact document scoring").
+ * Not provided: a different T per query, or a mask over a query's vectors; weights per vector; filters other than
+ * deletions in the host entry (the primitive chains with the filtered *_device searches); late interaction over shards;
+ * one-query gathered calls; the Rust shim's binding. */
 #define HNSW_LATE_MAX_VECS 32
 #define HNSW_LATE_MAX_CANDS 1024
 #define HNSW_LATE_MAX_DOCS 256
@@ -1010,6 +1011,72 @@ int hnsw_search_batch_late(hnsw_index *h, const float *Q /* nq x n_vecs x dim */
                            float *scores /* or NULL */, uint32_t *best_ids /* or NULL */, uint32_t *doc_sizes /* or NULL */,
                            uint32_t *counts /* or NULL */, uint32_t *n_docs /* or NULL */,
                            hnsw_query_stats *stats /* or NULL */);
+
+/* ---- exact document scoring: late interaction over every stored row ------------------------------------------------------
+ * An extension, and the stage late-interaction search leaves open: there a document's minimum runs over its rows that
+ * landed in some vector's pool.  Here the documents a list names are scored over EVERY stored row they have, the way
+ * ColBERT-style serving (PLAID's last stage) completes its approximate candidates -- and the way documents that come from
+ * elsewhere (a lexical retriever, a grouped search) are scored against a multi-vector query.
+ * A call has nq queries of T = n_vecs vectors each: Q [nq][T][dim], ONE list of document labels docs_in [nq][n_in],
+ * counts_in [nq] or NULL, stats_in [nq] or NULL.  Limits: 1 <= T <= HNSW_LATE_MAX_VECS, 1 <= n_out <= n_in <=
+ * HNSW_DOCS_MAX_IN, 1 <= rows_cap <= HNSW_DOCS_MAX_ROWS (the kernel keeps the running totals of the scored rows as 32-bit
+ * words: HNSW_DOCS_MAX_IN documents of HNSW_DOCS_MAX_ROWS rows are 2^28).  mode is HNSW_LATE_SUM or HNSW_LATE_SUM_SQ.
+ * THE DOCUMENT SCORING of one query:
+ *   - entry j of the list is PRESENT iff j < min(counts_in, n_in); without counts every one of the n_in entries is present:
+ *     every uint32 is a label, so there is no pad value.  Duplicate labels in a list are one document;
+ *   - an incoming status that is not HNSW_OK fails the query with that status; otherwise a NaN element in any vector gives
+ *     HNSW_ERR_NAN_INPUT.  A failed query has count 0, n_docs 0 and padded rows, and no stored row is read for it;
+ *   - R(g), the rows of label g, is the ids below hnsw_len that are not deleted and whose label is g as of the call: the
+ *     label is 0 at or beyond the column's length, and 0 everywhere on a handle that never had a label set.
+ *     doc_size(g) = |R(g)|.  A label with doc_size 0 is not a document: it is dropped and not counted in n_docs;
+ *   - the rows scored are the min(doc_size(g), rows_cap) lowest ids of R(g); doc_sizes reports the full doc_size(g), so a
+ *     caller sees that a document was cut;
+ *   - D_t(c), m_t(g), the fold, best(g) and the order are THE LATE INTERACTION's, word for word, with one change: the
+ *     minimum, and best(g), run over the rows scored instead of the candidates of g.
+ * Outputs and pads are THE LATE INTERACTION's: doc_labels [n_out] (pad 0), scores [n_out] (pad +inf), best_ids [n_out]
+ * (optional, pad UINT32_MAX), doc_sizes [n_out] (optional, pad 0), counts (optional), n_docs (optional), stats (required
+ * iff stats_in is given): the incoming record with the status as above.  Every output word is written exactly once.
+ *
+ * hnsw_score_documents_device is THE DOCUMENT SCORING alone over buffers in HBM, under the stream contract of
+ * hnsw_late_interaction_device: the snapshot is brought up to date; under the metric_cosine option a stream-ordered
+ * unit-length copy of d_Q is made; the DOCUMENT INDEX -- the keys label << 32 | id of the undeleted ids, ascending, 8 bytes
+ * each in HBM -- is brought up to date on a stream of the handle's own, which is synchronised: one whole copy when the
+ * labels, the deleted set or the length changed since it was made, nothing otherwise; then ONE launch (the distance seam's
+ * kernel in its document-scoring form, one wave per query) is enqueued on `stream`, which is not synchronised.  The index is
+ * derived from the label column and the deleted set: it is not saved and no part of the snapshot exchange, and hnsw_clone
+ * and hnsw_set_device make it afresh on first use.  Outputs must not overlap inputs.  The status of a failed query is
+ * written to d_stats only.  HNSW_ERR_ARG, decided before the device is touched: h NULL; a limit violated; a mode other
+ * than the two; nq > 2^31 - 1; d_Q, d_docs_in, d_doc_labels or d_scores NULL; exactly one of d_stats_in / d_stats given.
+ * nq == 0 is HNSW_OK on any handle, whatever else is passed, and launches nothing; an empty index is HNSW_ERR_EMPTY.
+ *
+ * hnsw_search_batch_late_exact answers host-pointer queries of T vectors each by their n best documents, every returned
+ * document scored over all its rows.  By definition the result is THE DOCUMENT SCORING, with n_out = n, of the labels,
+ * counts and stats that THE LATE INTERACTION returns with n_out = n_cand over the lists of hnsw_search_batch_late's own
+ * candidate call (n = pool, ef' = max(ef, pool, 1)).  Limits: T * pool <= HNSW_LATE_MAX_CANDS, 1 <= n <= n_cand <=
+ * min(T * pool, HNSW_DOCS_MAX_IN).  Q goes up once, then the search and its re-run loop, one late-interaction launch, one
+ * scoring launch, ONE copy of the block [labels | scores | best ids | sizes | counts | n_docs | stats] back.  While ids are
+ * deleted the candidates are the host form's, as in hnsw_search_batch_late; pool <= 64 is then required.  Per-query errors
+ * and the optional outputs are hnsw_search_batch_late's.  nq == 0 is HNSW_OK; an empty index is HNSW_ERR_EMPTY.
+ * hnsw_get_stat: "docs_calls" (hnsw_search_batch_late_exact calls answered), "docs_launches" (scorings launched,
+ * hnsw_score_documents_device's included; the composed call also counts its late interaction in "late_launches"),
+ * "doc_index_uploads" and "doc_index_keys_uploaded" (whole copies of the document index, and the keys they carried).
+ * Not provided: incremental maintenance of the document index; a different T per query; weights per vector; scoring over
+ * shards; filters other than deletions in the host entry; one-query gathered calls; the Rust shim's binding. */
+#define HNSW_DOCS_MAX_IN 256
+#define HNSW_DOCS_MAX_ROWS 1048576
+int hnsw_score_documents_device(hnsw_index *h, uint64_t nq, uint32_t n_vecs, uint32_t n_in, uint32_t n_out, uint32_t rows_cap,
+                                uint32_t mode, const float *d_Q /* nq x n_vecs x dim */,
+                                const uint32_t *d_docs_in /* nq x n_in labels */, const uint32_t *d_counts_in /* nq, or NULL */,
+                                const hnsw_query_stats *d_stats_in /* nq, or NULL */, uint32_t *d_doc_labels,
+                                float *d_scores /* nq x n_out */, uint32_t *d_best_ids /* or NULL */,
+                                uint32_t *d_doc_sizes /* or NULL */, uint32_t *d_counts /* or NULL */,
+                                uint32_t *d_n_docs /* or NULL */, hnsw_query_stats *d_stats /* required iff d_stats_in */,
+                                void *stream);
+int hnsw_search_batch_late_exact(hnsw_index *h, const float *Q /* nq x n_vecs x dim */, uint64_t nq, uint32_t n_vecs,
+                                 uint32_t mode, uint32_t n, uint32_t n_cand, uint32_t rows_cap, uint32_t pool, uint32_t ef,
+                                 uint32_t *doc_labels /* nq x n */, float *scores /* or NULL */, uint32_t *best_ids /* or NULL */,
+                                 uint32_t *doc_sizes /* or NULL */, uint32_t *counts /* or NULL */,
+                                 uint32_t *n_docs /* or NULL */, hnsw_query_stats *stats /* or NULL */);
 
 /* ---- refined search: the pool re-scored against full rows kept in HBM ------------------------------------------------
  * An extension (the reference ranks by the rows it stores).  Every search above ranks by the distance the INDEX stores:
@@ -1287,7 +1354,10 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * _by_id calls answered), "from_rows_compose_launches" (hnsw_compose_rows_device's included), "from_rows_drop_launches"
  * (the drops those calls launched); multi-vector search: "multi_calls" (hnsw_search_batch_multi calls answered),
  * "multi_fuse_launches" (fusions launched, hnsw_fuse_lists_device's included); late-interaction search: "late_calls"
- * (hnsw_search_batch_late calls answered), "late_launches" (hnsw_late_interaction_device's included); deletion:
+ * (hnsw_search_batch_late calls answered), "late_launches" (hnsw_late_interaction_device's included, and the composed
+ * exact call's); exact document scoring: "docs_calls" (hnsw_search_batch_late_exact calls answered), "docs_launches"
+ * (hnsw_score_documents_device's included), "doc_index_uploads" and "doc_index_keys_uploaded" (whole copies of the
+ * document index to HBM, and the 8-byte keys they carried); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
