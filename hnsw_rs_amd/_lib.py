@@ -30,6 +30,9 @@ DOCS_MAX_IN = 256  # HNSW_DOCS_MAX_IN: labels per list of a document scoring
 DOCS_MAX_ROWS = 1048576  # HNSW_DOCS_MAX_ROWS: rows scored per document
 ROWS_F32 = 0  # HNSW_ROWS_F32: a row table of f32 elements
 ROWS_F16 = 1  # HNSW_ROWS_F16: ... of IEEE binary16 elements, widened exactly where they are read
+HYBRID_MAX_EXT = 7  # HNSW_HYBRID_MAX_EXT: external ranked lists per query of a hybrid search
+HYBRID_RRF = 0  # HNSW_HYBRID_RRF: reciprocal rank fusion, larger is better
+HYBRID_LINEAR = 1  # HNSW_HYBRID_LINEAR: a weighted sum of the dense distance and the external scores, smaller is better
 REFINE_POOL_MAX = 1024  # HNSW_REFINE_POOL_MAX: candidates per query of a refined search
 REFINE_MAX_DIM = 4096  # HNSW_REFINE_MAX_DIM: elements of a full row
 RADIUS_MAX_N = 1024  # HNSW_RADIUS_MAX_N: entries per list of a radius search
@@ -192,6 +195,11 @@ SYMBOLS = {
                                      vp, vp, vp, vp, vp, vp]),
     "hnsw_search_batch_refined": (C.c_int, [vp, vp, f32p, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, u32p,
                                             u32p, u32p, u32p, f32p, u32p, C.POINTER(QueryStats)]),
+    "hnsw_fuse_ranked_device": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32,
+                                          C.c_uint32, vp, vp, vp, vp, f32p, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "hnsw_search_batch_hybrid": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.c_uint32, u32p, f32p, u32p, f32p, f32p, vp, u32p, u32p, u32p, u32p,
+                                           f32p, f32p, u32p, u32p, u32p, C.POINTER(QueryStats)]),
     "hnsw_distance_batch": (C.c_int, [vp, f32p, u32p, C.c_uint64, f32p]),
     "hnsw_search_layer": (C.c_int, [vp, C.c_uint32, f32p, u32p, C.c_uint32, C.c_uint32, u32p, f32p, u32p,
                                     C.POINTER(QueryStats)]),

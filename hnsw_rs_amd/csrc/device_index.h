@@ -360,7 +360,29 @@ struct DiverseLists {
     uint32_t docs, rows_cap;
     const uint64_t *doc_keys;
     uint64_t n_doc_keys;
+    // The eighth source form (hnsw_fuse_ranked_device), selected by hybrid != 0 (zero in every other
+    // launch; 1 + the mode) and looked at before ALL others: query q has up to 1 + HX_HYBRID_MAX_EXT ranked lists -- the
+    // optional dense one ids[q][j], j < pool, counts[q] and stats[q] (ids nullptr: none; either of the others may be
+    // nullptr), then n_ext external ones ext_ids / ext_scores [q][e][j], j < ext_width, ext_counts[q][e] (scores and counts
+    // may be nullptr) -- weights[q][1 + n_ext] (nullptr: none), absent[e] by value, rank_constant, and optionally its row
+    // queries[q][dim].  The filter: deny / deny_bits (the deleted ids' mask, nullptr: nothing deleted), rowed != 0: the
+    // rows `allow` of mask_words words each, n_masks of them, allow_bits ids each, query q under row mask_of[q] (nullptr:
+    // row 0) or HNSW_MASK_NONE; range_lo / range_hi [q] (nullptr: no range) over labels / label_len.  THE RANK FUSION of
+    // include/hnsw_mi355x.h goes to out_ids / out_dists (the scores) / out_gaps (D of every hit; may be nullptr)
+    // [q][n_out], out_counts[q], unique_out[q], dropped_out[q] (all three may be nullptr) and out_stats[q] (with stats).
+    uint32_t hybrid, n_ext, ext_width, rank_constant;
+    const uint32_t *ext_ids;
+    const float *ext_scores;
+    const uint32_t *ext_counts;
+    float absent[7];  // (HX_HYBRID_MAX_EXT)
+    uint32_t rowed;
+    const uint64_t *deny, *allow;
+    uint64_t deny_bits, allow_bits, mask_words;
+    const uint32_t *mask_of, *range_lo, *range_hi;
+    uint32_t n_masks;
+    uint32_t *dropped_out;
 };
+#define HX_HYBRID_MAX_EXT 7  // external lists per query of the rank fusion
 #define HX_ROWS_F32 0
 #define HX_ROWS_F16 1
 #define HX_REFINE_POOL_MAX 1024  // candidates per refined query: a key of 8 bytes each in LDS
@@ -392,6 +414,10 @@ int launch_late_interaction(const DevView &v, DiverseLists d, hipStream_t stream
 // HX_DOCS_MAX_IN, 1 <= rows_cap <= HX_DOCS_MAX_ROWS, mode 0 or 1) over d.doc_keys: ONE launch of hx_distance_kernel in its
 // seventh form, one wave per query; sets d.docs itself
 int launch_score_documents(const DevView &v, DiverseLists d, hipStream_t stream);
+// the rank fusion of d.nq queries (d.mode 0: reciprocal rank fusion, 1: linear; total = (d.ids ? pool : 0) + n_ext *
+// ext_width <= HX_DIVERSE_POOL_MAX, n_ext <= HX_HYBRID_MAX_EXT, 1 <= n_out <= total): ONE launch of hx_distance_kernel in
+// its eighth form, one wave per query; sets d.hybrid from d.mode itself
+int launch_fuse_ranked(const DevView &v, DiverseLists d, hipStream_t stream);
 // the refinement of d.nq candidate lists against d.table (1 <= n_out <= pool <= HX_REFINE_POOL_MAX, 1 <= full_dim <=
 // HX_REFINE_MAX_DIM, a dtype of the two): ONE launch of hx_distance_kernel<HNSW_VEC_F32> in its sixth form under a zeroed
 // view, one wave per query; takes no handle and sets d.lane_rows from the switch itself

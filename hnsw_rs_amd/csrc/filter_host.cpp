@@ -267,6 +267,13 @@ int labels_on_device(hnsw_index *h, const uint32_t **d_labels, uint64_t *label_l
     return HNSW_OK;
 }
 
+int deleted_on_device(hnsw_index *h, const uint64_t **d_deny, uint64_t *deny_bits) {
+    if (int rc = sync_deleted(h)) return rc;
+    *d_deny = h->del.count ? h->del.d_words : nullptr;
+    *deny_bits = h->del.count ? h->del.deny_bits() : 0;
+    return HNSW_OK;
+}
+
 int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f,
                             bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
                             uint8_t *paths) {

@@ -92,6 +92,8 @@ struct hnsw_index {
     // refined search: hnsw_search_batch_refined calls answered and the refinements they launched (hnsw_refine_device takes
     // no handle), and the writes that reached a row table of this handle
     std::atomic<uint64_t> n_refine_calls{0}, n_refine_launches{0}, n_row_table_writes{0};
+    // hybrid search: hnsw_search_batch_hybrid calls answered, and the rank fusions launched (hnsw_fuse_ranked_device's too)
+    std::atomic<uint64_t> n_hybrid_calls{0}, n_hybrid_fuse{0};
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")
 };
 

@@ -1,5 +1,5 @@
 // lists_host.h -- the candidate stage of the search-then-post-process entry points (grouped, radius, diverse,
-// from_rows, multi, late, docs, refine, partition .cpp): every one of them checks the call, gets candidate lists of rows x pool into
+// from_rows, multi, late, docs, refine, hybrid, partition .cpp): every one of them checks the call, gets candidate lists of rows x pool into
 // HBM, runs ONE post-process launch, brings a column block back in one copy and scatters its columns into the caller's
 // buffers.  Everything but the launch is here, once (internal; DESIGN.md, "The candidate stage")
 #pragma once

@@ -147,6 +147,9 @@ int search_device_filtered(hnsw_index *h, const Filter &f, const float *d_Q, uin
 // set in gets its copy of zeros); -> the copy and the labels it holds.  The snapshot's device must be known
 // (ensure_uploaded).
 int labels_on_device(hnsw_index *h, const uint32_t **d_labels, uint64_t *label_len);
+// ... and the deleted set as the kernels read it (FilterArgs::deny, deny_bits), for the rank fusion (hybrid.cpp): brought
+// up to date the same way; nullptr and 0 while nothing is deleted
+int deleted_on_device(hnsw_index *h, const uint64_t **d_deny, uint64_t *deny_bits);
 
 // hnsw_search_batch_device_finish while nothing is deleted: waits for the stream, reads the per-query statuses,
 // re-runs the queries whose visited table filled up with a table twice the size (same arithmetic, same result as

@@ -723,6 +723,85 @@ class HNSW:
             self._h, nq, n_vecs, pool, n_out, mode_of(mode), p(d_Q), p(d_weights), p(d_ids_in), p(d_counts_in), p(d_stats_in),
             p(d_ids), p(d_scores), p(d_counts), p(d_unique), p(d_stats), stream or None))
 
+    # ---- hybrid search: rank fusion of the index's hits with external ranked lists (include/hnsw_mi355x.h) -----------
+    @staticmethod
+    def _hybrid_weights(weights, nq, E):
+        """None, [1 + E] (broadcast over the queries) or [nq, 1 + E] -> float32 [nq, 1 + E] or None"""
+        if weights is None:
+            return None
+        w = np.asarray(weights, dtype=np.float32)
+        if w.shape == (1 + E,):
+            w = np.broadcast_to(w, (nq, 1 + E))
+        if w.shape != (nq, 1 + E):
+            raise ValueError("weights is [1 + E] or [nq, 1 + E]: slot 0 is the dense slot")
+        return np.ascontiguousarray(w, dtype=np.float32)
+
+    def search_batch_hybrid(self, Q, n, pool, ef, ext_ids=None, ext_scores=None, ext_counts=None, mode="rrf", rank_constant=60,
+                            weights=None, absent=None, mask_set=None, mask_of=None, lo=None, hi=None):
+        """The n best of the index's own `pool` hits fused with E external ranked lists per query -- BM25, a sparse model,
+        another index -- by reciprocal rank ("rrf": larger is better) or by a weighted sum of the dense distance and the
+        external scores ("linear": smaller is better), every list under this index's deletions and, with mask_set / lo
+        and hi, its mask rows and label range: hybrid.fuse_ranked over search_batch (or the filtered search of that
+        kind) with n = pool (hnsw_search_batch_hybrid).  ext_ids [nq, E, W] uint32 (pad UINT32_MAX) or None, ext_scores
+        [nq, E, W] float32 (required under "linear" with E > 0), ext_counts [nq, E] or None, weights [1 + E] or
+        [nq, 1 + E] or None, absent [E] or None.
+        -> ids [nq, n] (pad UINT32_MAX), scores [nq, n] (pad -inf / +inf), dists [nq, n] (each hit's own distance, pad
+        +inf), counts [nq], unique [nq], dropped [nq] (entries the filter removed), stats [nq, 4] (the dense call's)"""
+        from .hybrid import mode_of
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        if (lo is None) != (hi is None):
+            raise ValueError("a label range needs lo and hi, both or neither")
+        nq, width = Q.shape[0], max(int(n), 1)
+        E, W, e_ids, e_sc, e_cnt = 0, 0, None, None, None
+        if ext_ids is not None:
+            e_ids = np.ascontiguousarray(ext_ids, dtype=np.uint32)
+            if e_ids.ndim != 3 or e_ids.shape[0] != nq:
+                raise ValueError("ext_ids is [nq, E, ext_width]")
+            E, W = e_ids.shape[1], e_ids.shape[2]
+            if ext_scores is not None:
+                e_sc = np.ascontiguousarray(ext_scores, dtype=np.float32)
+                if e_sc.shape != e_ids.shape:
+                    raise ValueError("ext_scores has the shape of ext_ids")
+            if ext_counts is not None:
+                e_cnt = np.ascontiguousarray(ext_counts, dtype=np.uint32).reshape(nq, E)
+        w = self._hybrid_weights(weights, nq, E)
+        ab = None if absent is None else np.ascontiguousarray(absent, dtype=np.float32).reshape(E)
+        mo = self._mask_of(mask_of, nq)
+        rng = (None, None) if lo is None else self._range(lo, hi, nq)
+        ids = np.full((nq, width), _lib.UINT32_MAX, dtype=np.uint32)
+        scores = np.zeros((nq, width), dtype=np.float32)
+        dists = np.full((nq, width), np.inf, dtype=np.float32)
+        counts, unique, dropped = (np.zeros(nq, dtype=np.uint32) for _ in range(3))
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        opt = lambda a, t: None if a is None else _p(a, t)  # noqa: E731
+        check(self._L.hnsw_search_batch_hybrid(
+            self._h, _p(Q, _f32p), nq, n, pool, ef, mode_of(mode), rank_constant, E, W, opt(e_ids, _u32p), opt(e_sc, _f32p),
+            opt(e_cnt, _u32p), opt(w, _f32p), opt(ab, _f32p), mask_set._s if mask_set is not None else None, opt(mo, _u32p),
+            opt(rng[0], _u32p), opt(rng[1], _u32p), _p(ids, _u32p), _p(scores, _f32p), _p(dists, _f32p), _p(counts, _u32p),
+            _p(unique, _u32p), _p(dropped, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
+        return ids, scores, dists, counts, unique, dropped, stats.view(np.uint32).astype(np.int64)
+
+    def fuse_ranked_device(self, nq, mode, rank_constant, n_out, pool, d_ids0, d_counts0, d_stats0, n_ext, ext_width, d_ext_ids,
+                           d_ext_scores, d_ext_counts, d_weights, absent, d_Q, d_ids, d_scores, d_dists=None, d_counts=None,
+                           d_unique=None, d_dropped=None, d_stats=None, mask_set=None, d_mask_of=None, d_lo=None, d_hi=None,
+                           stream=0):
+        """hnsw_fuse_ranked_device over torch device tensors (or raw device pointers): the dense list d_ids0 [nq, pool]
+        (/ d_counts0 / d_stats0 [nq]; None: no dense list) a *_device search of this index left, fused with the n_ext
+        external lists d_ext_ids / d_ext_scores [nq, n_ext, ext_width] (/ d_ext_counts [nq, n_ext]) under d_weights
+        [nq, 1 + n_ext] (or None), `absent` (HOST: [n_ext] floats or None), optionally d_Q float32 [nq, dim], and the
+        filter (mask_set, d_mask_of / d_lo / d_hi [nq]), into d_ids / d_scores [nq, n_out] (/ d_dists / d_counts /
+        d_unique / d_dropped / d_stats).  ONE launch enqueued on `stream`, no sync of it."""
+        from .hybrid import mode_of
+        p = self._dptr
+        ab = None if absent is None else np.ascontiguousarray(absent, dtype=np.float32).reshape(n_ext)
+        check(self._L.hnsw_fuse_ranked_device(
+            self._h, nq, mode_of(mode), rank_constant, n_out, pool, p(d_ids0), p(d_counts0), p(d_stats0), n_ext, ext_width,
+            p(d_ext_ids), p(d_ext_scores), p(d_ext_counts), p(d_weights), None if ab is None else _p(ab, _f32p), p(d_Q),
+            mask_set._s if mask_set is not None else None, p(d_mask_of), p(d_lo), p(d_hi), p(d_ids), p(d_scores), p(d_dists),
+            p(d_counts), p(d_unique), p(d_dropped), p(d_stats), stream or None))
+
     # ---- late-interaction search: documents of several rows scored by summed min distance (include/hnsw_mi355x.h) ----
     def search_batch_late(self, Q, n, pool, ef, mode="sum"):
         """The n best DOCUMENTS -- the rows that share a label (set_labels) -- of queries of T vectors each, Q [nq, T, dim]:

@@ -909,7 +909,8 @@ int hnsw_search_batch_by_id(hnsw_index *h, const uint32_t *src_ids /* nq */, uin
  * nq * T > 2^31 - 1.  nq == 0 is HNSW_OK; an empty index is HNSW_ERR_EMPTY.  hnsw_get_stat: "multi_calls"
  * (hnsw_search_batch_multi calls answered), "multi_fuse_launches" (fusions launched, hnsw_fuse_lists_device's included).
  * Not provided: per-hit per-vector distances; a different T per query; filters other than deletions in the host entry
- * (the primitive chains with the filtered *_device searches); rank fusion; fusion over shards (merged lists carry global
+ * (the primitive chains with the filtered *_device searches); rank fusion (see "hybrid search" below:
+ * hnsw_fuse_ranked_device); fusion over shards (merged lists carry global
  * ids); one-query gathered calls; the Rust shim's binding. */
 #define HNSW_MULTI_MAX_VECS 16
 #define HNSW_FUSE_MAX_CANDS 256
@@ -1169,6 +1170,112 @@ int hnsw_search_batch_refined(hnsw_index *h, hnsw_row_table *t, const float *Q /
                               const uint32_t *lo /* or NULL */, const uint32_t *hi /* or NULL */, uint32_t *ids /* nq x n */,
                               float *dists /* or NULL */, uint32_t *counts /* or NULL */, hnsw_query_stats *stats /* or NULL */);
 
+/* ---- hybrid search: rank fusion of the index's hits with external ranked lists, on the device ---------------------------
+ * An extension (the reference has one retriever): what Weaviate, Qdrant, Milvus and Elasticsearch call hybrid search.  The
+ * dense index's hits are combined with ranked lists from other retrievers -- BM25, a sparse model, a second index over
+ * another embedding -- by reciprocal rank fusion or by a weighted sum of scores.  The deletions, mask rows and label
+ * ranges of this library live in its HBM and nowhere else, so the fusion applies them to EVERY list: an external
+ * candidate this index holds as deleted, outside the query's label range or not visible under its mask row does not come
+ * back, whichever retriever proposed it.  This is not hnsw_fuse_lists_device, which scores by distances to several
+ * vectors and knows nothing of ranks, external scores or filters.
+ * THE RANK FUSION of one query.
+ * Lists.  A query has up to 8 ranked lists, in this order: the optional DENSE list, the index's own -- ids0 [nq][pool],
+ * counts0 [nq] or NULL, stats0 [nq] or NULL; its distances are not an input -- then E EXTERNAL lists, 0 <= E <=
+ * HNSW_HYBRID_MAX_EXT: ext_ids [nq][E][ext_width], ext_scores [nq][E][ext_width] f32 or NULL, ext_counts [nq][E] or NULL.
+ * At least one list is given; total = (dense given ? pool : 0) + E * ext_width <= HNSW_FUSE_MAX_CANDS; 1 <= n_out <=
+ * total.  weights [nq][1 + E] f32 or NULL: slot 0 is always the dense slot.  absent [E] f32 or NULL (every value 0.0f): a
+ * HOST pointer in both entry points, read before the call returns.  Optionally the query's row Q [nq][dim], and
+ * optionally a filter, the four arguments hnsw_search_batch_diverse takes: set, mask_of [nq], lo [nq], hi [nq].
+ *   - entry j of a list is PRESENT as in THE FUSION: j < min(count, width), or, without counts, iff its id is not
+ *     UINT32_MAX;
+ *   - a FAILED query has count 0, unique 0, dropped 0 and padded rows.  The causes, in order of precedence: (1) the dense
+ *     list's incoming status, if it is not HNSW_OK; (2) HNSW_ERR_ARG when mask_of[q] is neither HNSW_MASK_NONE nor below
+ *     the set's n_masks (no mask word is read; mask_of NULL names row 0); (3) HNSW_ERR_ARG when any present id of any list
+ *     is at or beyond the index length (no stored row, mask word or label is read for that query); (4)
+ *     HNSW_ERR_NAN_INPUT when Q is given and Q[q] has a NaN element;
+ *   - id i is ADMISSIBLE iff it is not deleted on the handle (ids beyond the deleted mask are not denied); and, with a
+ *     set row, i < allow_bits and its bit is set (a HNSW_MASK_NONE query has no bit test); and, with a range, lo <=
+ *     label(i) <= hi, where label(i) = 0 at or beyond the column's length (lo > hi admits nothing and reads no label):
+ *     the predicate of the filtered searches;
+ *   - the EFFECTIVE list: a list's present entries in order, the inadmissible ones removed, then every entry removed
+ *     whose id an earlier kept entry of the same list already has.  rank(c) in a list is the 1-based position of c in
+ *     what is left: what the caller would get had the other retriever applied the filter itself.  dropped = the present
+ *     entries, over all lists, removed as inadmissible (repeats are not counted).  C = the distinct ids over all
+ *     effective lists; unique = |C|;
+ *   - mode HNSW_HYBRID_RRF: 1 <= rank_constant <= 2^20 (customarily 60; rank_constant + rank is then exact in f32).  For
+ *     c in C, for each list that holds c, in list order (dense first): t = w / (float)(rank_constant + rank(c)), ONE
+ *     correctly rounded f32 division, w the list's weight or 1.0f without weights; s is the first such term, then s = s +
+ *     t, each add rounded on its own and never contracted; lists that do not hold c contribute nothing.  LARGER IS
+ *     BETTER: ranked by (s descending under f32 >, -0 == +0; then id ascending).  Q does not enter the score;
+ *   - mode HNSW_HYBRID_LINEAR: ext_scores is required when E > 0, and Q when E == 0; rank_constant is not read.  For c in
+ *     C: x_dense = D(c), the bits of hnsw_distance_batch(h, Q[q], {c}) (the query-side arithmetic of the index's kind;
+ *     under metric_cosine the unit copy, as THE FUSION does), evaluated for EVERY candidate whether or not the dense list
+ *     holds it; x_e = the score of c's kept entry in external list e if that list holds c, else absent[e]; p = w * x one
+ *     f32 multiply, omitted when weights is NULL.  With Q: s = p_dense, then s = s + p_e for e = 0 .. E-1.  With Q NULL
+ *     the dense term is left out entirely and s starts at p_0: the dense list then only proposes candidates.  SMALLER IS
+ *     BETTER: ranked by (s ascending under f32 <, -0 == +0; then id ascending); a caller gives similarity scores a
+ *     negative weight;
+ *   - both modes: a candidate whose score is NaN is never returned; infinite, zero and negative weights are legal; a NaN
+ *     weight or a NaN external score is no argument error; the answer depends neither on which duplicate was kept nor on
+ *     anything but (score, id).
+ * Per query: ids [n_out] (pad UINT32_MAX), scores [n_out] (pad the mode's worst value: -inf under RRF, +inf under
+ * LINEAR), dists [n_out] (optional, requires Q: D of each returned hit in either mode, pad +inf), counts, unique, dropped
+ * (all optional), stats (required iff stats0 is given: the dense record with the status as above).  Every output word is
+ * written exactly once.
+ *
+ * hnsw_fuse_ranked_device is THE RANK FUSION alone over buffers in HBM: every d_* pointer is device memory (`absent` is
+ * host memory and travels by value), ids are local to the handle, so a replica handle serves.  After the snapshot -- and
+ * whichever of the deleted mask, the label column and the set's words the call needs -- is brought up to date, ONE launch
+ * (the distance seam's kernel in its rank-fusion form, one wave per query) is enqueued on `stream` and the call returns
+ * without synchronising it.  Under the metric_cosine option it reads a stream-ordered unit-length copy of d_Q; otherwise
+ * nothing is allocated or copied, and the call is capturable under hnsw_fuse_lists_device's conditions.  The status of a
+ * failed query is written to d_stats only.  Outputs must not overlap inputs.  HNSW_ERR_ARG, decided before the device is
+ * touched: h NULL; n_ext > HNSW_HYBRID_MAX_EXT; no list at all; total or n_out outside the limits; a mode other than the
+ * two; RRF with rank_constant 0 or above 2^20; LINEAR without d_ext_scores when n_ext > 0, or without d_Q when n_ext ==
+ * 0; d_ext_ids NULL with n_ext > 0; d_dists without d_Q; nq > 2^31 - 1; d_ids or d_scores NULL; exactly one of d_stats0 /
+ * d_stats given; a set of another handle, d_mask_of without a set, one of d_lo / d_hi without the other; a set without
+ * rows when d_mask_of is NULL.  nq == 0 is HNSW_OK on any handle, whatever else is passed, and launches nothing; an
+ * empty index is HNSW_ERR_EMPTY.
+ *
+ * hnsw_search_batch_hybrid answers host-pointer queries.  By definition the result is THE RANK FUSION, with n_out = n,
+ * Q given, of the dense list and the caller's external lists under the same filter, where the dense list is whatever the
+ * right one of hnsw_search_batch / _filtered_set / _filtered_range / _filtered_set_range returns for Q with n = pool and
+ * ef handed on exactly as hnsw_search_batch_diverse hands it on.  Everything of that call is inherited: deletions, the
+ * cosine option, per-query errors (the first is returned with the query named; every other row is filled in).  With no
+ * filter and nothing deleted the call stays on the device: Q and the external lists go up once, the launch of
+ * hnsw_search_batch_device and the re-run loop of its _finish, one fusion launch, ONE copy of the block [ids | scores |
+ * dists | counts | unique | dropped | stats] back.  Otherwise the candidates are the host form's and go up before the
+ * fusion; pool <= 64 is then required.  scores, dists, counts, unique, dropped and stats may be NULL.  HNSW_ERR_ARG as the
+ * primitive's, with 1 <= n <= pool + n_ext * ext_width, pool >= 1, Q and ids required.  hnsw_get_stat: "hybrid_calls"
+ * (hnsw_search_batch_hybrid calls answered), "hybrid_fuse_launches" (rank fusions launched, hnsw_fuse_ranked_device's
+ * included).
+ * Not provided: min-max / z-score normalisation of scores; a different width per external list; label range lists;
+ * fusion over shards; one-query gathered calls; the Rust shim's binding. */
+#define HNSW_HYBRID_MAX_EXT 7
+#define HNSW_HYBRID_RRF 0
+#define HNSW_HYBRID_LINEAR 1
+int hnsw_fuse_ranked_device(hnsw_index *h, uint64_t nq, uint32_t mode, uint32_t rank_constant, uint32_t n_out, uint32_t pool,
+                            const uint32_t *d_ids0 /* nq x pool, or NULL */, const uint32_t *d_counts0 /* or NULL */,
+                            const hnsw_query_stats *d_stats0 /* or NULL */, uint32_t n_ext, uint32_t ext_width,
+                            const uint32_t *d_ext_ids /* nq x n_ext x ext_width */, const float *d_ext_scores /* or NULL */,
+                            const uint32_t *d_ext_counts /* nq x n_ext, or NULL */,
+                            const float *d_weights /* nq x (1 + n_ext), or NULL */, const float *absent /* host: n_ext, or NULL */,
+                            const float *d_Q /* nq x dim, or NULL */, hnsw_mask_set *set /* or NULL */,
+                            const uint32_t *d_mask_of /* or NULL */, const uint32_t *d_lo /* or NULL */,
+                            const uint32_t *d_hi /* or NULL */, uint32_t *d_ids, float *d_scores /* nq x n_out */,
+                            float *d_dists /* or NULL */, uint32_t *d_counts /* or NULL */, uint32_t *d_unique /* or NULL */,
+                            uint32_t *d_dropped /* or NULL */, hnsw_query_stats *d_stats /* required iff d_stats0 */,
+                            void *stream);
+int hnsw_search_batch_hybrid(hnsw_index *h, const float *Q /* nq x dim */, uint64_t nq, uint32_t n, uint32_t pool, uint32_t ef,
+                             uint32_t mode, uint32_t rank_constant, uint32_t n_ext, uint32_t ext_width,
+                             const uint32_t *ext_ids /* nq x n_ext x ext_width */, const float *ext_scores /* or NULL */,
+                             const uint32_t *ext_counts /* or NULL */, const float *weights /* nq x (1 + n_ext), or NULL */,
+                             const float *absent /* n_ext, or NULL */, hnsw_mask_set *set /* or NULL */,
+                             const uint32_t *mask_of /* or NULL */, const uint32_t *lo /* or NULL */,
+                             const uint32_t *hi /* or NULL */, uint32_t *ids /* nq x n */, float *scores /* or NULL */,
+                             float *dists /* or NULL */, uint32_t *counts /* or NULL */, uint32_t *unique /* or NULL */,
+                             uint32_t *dropped /* or NULL */, hnsw_query_stats *stats /* or NULL */);
+
 /* Test seams that mirror the reference's own units:
  * VecBase::dist2many (vectors/src/lib.rs:17-22): the query (quantised like ann_by_vector does,
  * template.rs:313) against stored ids, on the device, exact accumulation order. */
@@ -1357,7 +1464,8 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * (hnsw_search_batch_late calls answered), "late_launches" (hnsw_late_interaction_device's included, and the composed
  * exact call's); exact document scoring: "docs_calls" (hnsw_search_batch_late_exact calls answered), "docs_launches"
  * (hnsw_score_documents_device's included), "doc_index_uploads" and "doc_index_keys_uploaded" (whole copies of the
- * document index to HBM, and the 8-byte keys they carried); deletion:
+ * document index to HBM, and the 8-byte keys they carried); hybrid search: "hybrid_calls" (hnsw_search_batch_hybrid
+ * calls answered), "hybrid_fuse_launches" (rank fusions launched, hnsw_fuse_ranked_device's included); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
