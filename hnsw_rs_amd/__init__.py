@@ -17,5 +17,7 @@ from .refine import RowTable, f32_to_f16, refine_device, refine_lists  # noqa: F
 from ._lib import REFINE_MAX_DIM, REFINE_POOL_MAX, ROWS_F16, ROWS_F32  # noqa: F401
 from .hybrid import admissible_of, filters_of, fuse_ranked  # noqa: F401
 from ._lib import HYBRID_LINEAR, HYBRID_MAX_EXT, HYBRID_RRF  # noqa: F401
+from .boost import boost_device, boost_lists  # noqa: F401
+from ._lib import BOOST_MAX_ATTRS, BOOST_POOL_MAX  # noqa: F401
 from .radius import radius_cut, radius_ladder, to_csr  # noqa: F401
 from .partitioned import PartitionedIndex, merge_topk  # noqa: F401

@@ -35,6 +35,8 @@ HYBRID_RRF = 0  # HNSW_HYBRID_RRF: reciprocal rank fusion, larger is better
 HYBRID_LINEAR = 1  # HNSW_HYBRID_LINEAR: a weighted sum of the dense distance and the external scores, smaller is better
 REFINE_POOL_MAX = 1024  # HNSW_REFINE_POOL_MAX: candidates per query of a refined search
 REFINE_MAX_DIM = 4096  # HNSW_REFINE_MAX_DIM: elements of a full row
+BOOST_POOL_MAX = 1024  # HNSW_BOOST_POOL_MAX: candidates per query of a boosted search
+BOOST_MAX_ATTRS = 32  # HNSW_BOOST_MAX_ATTRS: attributes per id
 RADIUS_MAX_N = 1024  # HNSW_RADIUS_MAX_N: entries per list of a radius search
 RADIUS_MORE = 1  # HNSW_RADIUS_MORE: the list was full and showed nothing outside the radius
 RANGES_MAX = 16  # HNSW_RANGES_MAX: members of a query's range list
@@ -195,6 +197,12 @@ SYMBOLS = {
                                      vp, vp, vp, vp, vp, vp]),
     "hnsw_search_batch_refined": (C.c_int, [vp, vp, f32p, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, u32p,
                                             u32p, u32p, u32p, f32p, u32p, C.POINTER(QueryStats)]),
+    "hnsw_boost_device": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp,
+                                    C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "hnsw_search_batch_boosted": (C.c_int, [vp, vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint64,
+                                            vp, u32p, u32p, u32p, u32p, f32p, f32p, u32p, C.POINTER(QueryStats)]),
+    "hnsw_row_table_save": (C.c_int, [vp, C.c_char_p]),
+    "hnsw_row_table_load": (C.c_int, [vp, C.c_char_p, C.POINTER(vp)]),
     "hnsw_fuse_ranked_device": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_uint32,
                                           C.c_uint32, vp, vp, vp, vp, f32p, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "hnsw_search_batch_hybrid": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

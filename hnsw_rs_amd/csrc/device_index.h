@@ -381,8 +381,18 @@ struct DiverseLists {
     const uint32_t *mask_of, *range_lo, *range_hi;
     uint32_t n_masks;
     uint32_t *dropped_out;
+    // The ninth source form (hnsw_boost_device), selected by boost != 0 (zero in every other launch:
+    // no other launcher sets it, and every record starts zeroed; 1: one weight row for all queries, 2: a row per query)
+    // and looked at before ALL others; it reads nothing of the DevView.  Query q has ONE candidate list ids[q][j] /
+    // dists[q][j], j < pool, counts[q] and stats[q] (either may be nullptr) and a weight row weights[1 + full_dim]; table
+    // is table_rows rows of full_dim attributes of table_dtype, as in the sixth form.  THE BOOST of
+    // include/hnsw_mi355x.h goes to out_ids / out_dists (the scores) / out_gaps (the incoming distance of every hit; may
+    // be nullptr) [q][n_out], out_counts[q] (may be nullptr) and out_stats[q] (with stats).  Nothing else above is read.
+    uint32_t boost;
 };
 #define HX_HYBRID_MAX_EXT 7  // external lists per query of the rank fusion
+#define HX_BOOST_POOL_MAX 1024  // candidates per boosted query: a key of 8 bytes each in LDS
+#define HX_BOOST_MAX_ATTRS 32   // attributes per id: an f32 row is at most one 128-byte line
 #define HX_ROWS_F32 0
 #define HX_ROWS_F16 1
 #define HX_REFINE_POOL_MAX 1024  // candidates per refined query: a key of 8 bytes each in LDS
@@ -422,6 +432,11 @@ int launch_fuse_ranked(const DevView &v, DiverseLists d, hipStream_t stream);
 // HX_REFINE_MAX_DIM, a dtype of the two): ONE launch of hx_distance_kernel<HNSW_VEC_F32> in its sixth form under a zeroed
 // view, one wave per query; takes no handle and sets d.lane_rows from the switch itself
 int launch_refine(DiverseLists d, hipStream_t stream);
+// the boost of d.nq candidate lists by the attributes of d.table (1 <= n_out <= pool <= HX_BOOST_POOL_MAX, 1 <= full_dim <=
+// HX_BOOST_MAX_ATTRS, a dtype of the two; d.mode 0: d.weights is one row of 1 + full_dim for every query, 1: a row per
+// query): ONE launch of hx_distance_kernel<HNSW_VEC_F32> in its ninth form under a zeroed view, one wave per query; takes
+// no handle and sets d.boost from d.mode itself
+int launch_boost(DiverseLists d, hipStream_t stream);
 
 // exhaustive scan: every query against every point; partial top-k per (query, segment):
 // part_ids / part_dists are nq x nseg x k.  The host merges the segments.

@@ -94,10 +94,16 @@ struct hnsw_index {
     std::atomic<uint64_t> n_refine_calls{0}, n_refine_launches{0}, n_row_table_writes{0};
     // hybrid search: hnsw_search_batch_hybrid calls answered, and the rank fusions launched (hnsw_fuse_ranked_device's too)
     std::atomic<uint64_t> n_hybrid_calls{0}, n_hybrid_fuse{0};
+    // boosted search: hnsw_search_batch_boosted calls answered and the boosts they launched (hnsw_boost_device takes no
+    // handle: its launches are counted for the process, boost.cpp, and "boost_launches" reads the sum)
+    std::atomic<uint64_t> n_boost_calls{0}, n_boost_launches{0};
     hx::BuildStats build;  // the on-device builds of this handle, summed (hnsw_get_stat "build_*")
 };
 
 namespace hx {
+
+// the launches of hnsw_boost_device, which takes no handle, in this process (boost.cpp)
+uint64_t boost_device_launches();
 
 // a device-only replica (hnsw_snapshot_adopt / _commit) has no host index behind its snapshot
 inline bool is_replica(const hnsw_index *h) { return h->dev.replica; }

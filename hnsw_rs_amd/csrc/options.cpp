@@ -127,6 +127,8 @@ const Stat kStats[] = {
     HX_STAT("row_table_writes", h.n_row_table_writes),
     HX_STAT("hybrid_calls", h.n_hybrid_calls),
     HX_STAT("hybrid_fuse_launches", h.n_hybrid_fuse),
+    HX_STAT("boost_calls", h.n_boost_calls),
+    HX_STAT("boost_launches", h.n_boost_launches + hx::boost_device_launches()),
     HX_STAT("deleted", h.del.count),
     HX_STAT("deleted_mask_words_uploaded", h.del.words_uploaded),
     HX_STAT("deleted_queries_graph", h.n_del_graph),

@@ -1,9 +1,13 @@
 // row_table.cpp -- hnsw_row_table (row_table.h): the C entry points that manage a table of full rows in HBM, and the
-// host's binary16 rounding.  Host logic only; the refinement that reads the table is refine.cpp's and exact_scan.hip's.
+// host's binary16 rounding, and the table's file.  Host logic only; the refinement and the boost that read the table are
+// refine.cpp's, boost.cpp's and exact_scan.hip's.
 
 #include "row_table.h"
 
+#include <sys/stat.h>
+
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -147,6 +151,32 @@ int check_write(const hnsw_row_table *t, uint64_t first_id, uint64_t n) {
     return HNSW_OK;
 }
 
+// ---- the table's file (hnsw_row_table_save / _load): big-endian like the index's own format (persist.cpp) ----
+//   magic "HXRT" u32, version u32 = 1, full_dim u32, dtype u32, rows u64, then rows x full_dim elements of the dtype
+constexpr uint32_t FILE_MAGIC = 0x48585254u, FILE_VERSION = 1;
+constexpr size_t FILE_HEADER = 24;
+constexpr uint64_t STAGE_BYTES = 64ull << 20;  // rows travel between HBM and the file in chunks of at most this
+
+void put_be(uint8_t *p, uint64_t v, int bytes) {
+    for (int i = 0; i < bytes; i++) p[i] = (uint8_t)(v >> (8 * (bytes - 1 - i)));
+}
+uint64_t get_be(const uint8_t *p, int bytes) {
+    uint64_t v = 0;
+    for (int i = 0; i < bytes; i++) v = (v << 8) | p[i];
+    return v;
+}
+// n elements of es bytes between the host's order (little-endian) and the file's, in place
+void swap_elements(uint8_t *p, uint64_t n, size_t es) {
+    for (uint64_t i = 0; i < n; i++, p += es) std::reverse(p, p + es);
+}
+uint64_t chunk_rows(uint64_t row_bytes) { return std::max<uint64_t>(1, STAGE_BYTES / row_bytes); }
+struct FileCloser {
+    FILE *f;
+    ~FileCloser() {
+        if (f) fclose(f);
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -271,6 +301,107 @@ int hnsw_row_table_device(const hnsw_row_table *t, const void **d_ptr, uint64_t 
     }
     *d_ptr = t->d_rows;
     if (rows) *rows = t->rows;
+    return HNSW_OK;
+}
+
+int hnsw_row_table_save(hnsw_row_table *t, const char *path) {
+    if (!t || !path) {
+        set_error("row table: saving needs a table and a path");
+        return HNSW_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> g(t->mu);
+    FILE *f = fopen(path, "wb");
+    if (!f) {
+        set_error("row table: could not create %s", path);
+        return HNSW_ERR_IO;
+    }
+    FileCloser closer{f};
+    uint8_t head[FILE_HEADER];
+    put_be(head, FILE_MAGIC, 4), put_be(head + 4, FILE_VERSION, 4), put_be(head + 8, t->full_dim, 4);
+    put_be(head + 12, t->dtype, 4), put_be(head + 16, t->rows, 8);
+    bool ok = fwrite(head, 1, FILE_HEADER, f) == FILE_HEADER;
+    if (t->rows) {  // (a table that was never written touches no device)
+        HIP_TRY(hipSetDevice(t->device));
+        const uint64_t rb = t->row_bytes(), per = chunk_rows(rb);
+        const size_t es = t->dtype == HNSW_ROWS_F16 ? 2 : 4;
+        std::vector<uint8_t> stage;
+        try {
+            stage.resize(std::min(per, t->rows) * rb);
+        } catch (const std::bad_alloc &) {
+            set_error("row table: out of memory for the staging of %s", path);
+            return HNSW_ERR_OOM;
+        }
+        for (uint64_t r0 = 0; ok && r0 < t->rows; r0 += per) {
+            const uint64_t n = std::min(per, t->rows - r0);
+            HIP_TRY(hipMemcpy(stage.data(), static_cast<const unsigned char *>(t->d_rows) + r0 * rb, n * rb,
+                              hipMemcpyDeviceToHost));
+            swap_elements(stage.data(), n * t->full_dim, es);
+            ok = fwrite(stage.data(), 1, n * rb, f) == n * rb;
+        }
+    }
+    closer.f = nullptr;
+    if (fclose(f) != 0 || !ok) {
+        set_error("row table: could not write %s", path);
+        return HNSW_ERR_IO;
+    }
+    return HNSW_OK;
+}
+
+int hnsw_row_table_load(hnsw_index *h, const char *path, hnsw_row_table **out) {
+    if (!h || !path || !out) {
+        set_error("row table: loading needs a handle, a path and a place for the table");
+        return HNSW_ERR_ARG;
+    }
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        set_error("row table: could not open %s", path);
+        return HNSW_ERR_IO;
+    }
+    FileCloser closer{f};
+    auto corrupt = [&](const char *why) {
+        set_error("row table: %s: %s", path, why);
+        return HNSW_ERR_IO;
+    };
+    uint8_t head[FILE_HEADER];
+    if (fread(head, 1, FILE_HEADER, f) != FILE_HEADER) return corrupt("shorter than its header");
+    if (get_be(head, 4) != FILE_MAGIC) return corrupt("not a row table (magic)");
+    if (get_be(head + 4, 4) != FILE_VERSION) return corrupt("a version this library does not read");
+    const uint64_t full_dim = get_be(head + 8, 4), dtype = get_be(head + 12, 4), rows = get_be(head + 16, 8);
+    if (full_dim == 0 || full_dim > HNSW_REFINE_MAX_DIM) return corrupt("full_dim out of range");
+    if (dtype != HNSW_ROWS_F32 && dtype != HNSW_ROWS_F16) return corrupt("an unknown dtype");
+    if (rows > 0xFFFFFFFFull) return corrupt("more than 2^32 - 1 rows");
+    const uint64_t rb = full_dim * (dtype == HNSW_ROWS_F16 ? 2 : 4);
+    struct stat st;
+    if (fstat(fileno(f), &st) != 0 || (uint64_t)st.st_size != FILE_HEADER + rows * rb)
+        return corrupt("its length is not what its header says");
+    hnsw_row_table *t = nullptr;
+    if (int rc = hnsw_row_table_create(h, (uint32_t)full_dim, (uint32_t)dtype, &t)) return rc;
+    auto fail = [&](int rc) {
+        delete t;
+        return rc;
+    };
+    if (rows) {
+        const uint64_t per = chunk_rows(rb);
+        const size_t es = dtype == HNSW_ROWS_F16 ? 2 : 4;
+        std::vector<uint8_t> stage;
+        try {
+            stage.resize(std::min(per, rows) * rb);
+        } catch (const std::bad_alloc &) {
+            set_error("row table: out of memory for the staging of %s", path);
+            return fail(HNSW_ERR_OOM);
+        }
+        for (uint64_t r0 = 0; r0 < rows; r0 += per) {  // (nobody else has the table yet: no lock)
+            const uint64_t n = std::min(per, rows - r0), total = n * full_dim;
+            if (fread(stage.data(), 1, n * rb, f) != n * rb) return fail(corrupt("could not be read"));
+            swap_elements(stage.data(), total, es);
+            uint64_t bad = 0;
+            const bool fine = dtype == HNSW_ROWS_F32 ? finite_f32(reinterpret_cast<const float *>(stage.data()), total, &bad)
+                                                     : finite_f16(reinterpret_cast<const uint16_t *>(stage.data()), total, &bad);
+            if (!fine) return fail(corrupt("holds a NaN or an infinity"));
+            if (int rc = store(t, r0, n, stage.data())) return fail(rc);
+        }
+    }
+    *out = t;
     return HNSW_OK;
 }
 

@@ -2,7 +2,8 @@
 // handle, in HBM ONLY: rows x full_dim elements of f32 or IEEE binary16, row id = index id, what the refinement
 // (hx_distance_kernel's sixth source form, exact_scan.hip) scores a candidate list against.  The host keeps no copy: the
 // caller owns the full rows.  The table is not saved by hnsw_save, not cloned by hnsw_clone and not part of the snapshot
-// exchange.  Host logic only (row_table.cpp).
+// exchange; hnsw_row_table_save / _load carry it in a file of its own.  With full_dim <= 32 it is the attribute table of
+// boosted search (the kernel's ninth form).  Host logic only (row_table.cpp).
 //
 // Create touches no device; the first write allocates on the handle's device and fixes it.  A write past the capacity
 // grows the array by a device-to-device copy (capacity + 1/8, as DeviceIndex::append_point grows its arrays).  Writes are

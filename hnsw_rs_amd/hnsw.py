@@ -929,6 +929,57 @@ class HNSW:
         refine_device(nq, pool, n_out, full_dim, dtype, d_table, table_rows, d_Qfull, d_ids_in, d_counts_in, d_stats_in,
                       d_ids, d_dists, d_counts, d_stats, stream)
 
+    # ---- boosted search: the pool re-ranked by per-id attributes kept in HBM (include/hnsw_mi355x.h) ----------------
+    def search_batch_boosted(self, table, Q, weights, n, pool, ef, mask_set=None, mask_of=None, lo=None, hi=None):
+        """The n best by w[0] * distance + sum_k w[1 + k] * attribute k (SMALLER is better) out of the `pool` candidates
+        that search_batch (or, with mask_set / lo and hi, the filtered search of that kind) returns for Q with n = pool:
+        boost.boost_lists of those lists over `table` (a RowTable of this index with at most 32 columns) under weights
+        [1 + A] (one row for every query) or [nq, 1 + A] (hnsw_search_batch_boosted).
+        -> ids [nq, n] (pad UINT32_MAX), scores [nq, n] (pad +inf), dists [nq, n] (the hits' own distances, pad +inf),
+        counts [nq], stats [nq, 4] (the candidate call's)"""
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        if Q.ndim != 2 or Q.shape[1] != self.dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "queries must be nq x %d" % self.dim)
+        nq, width = Q.shape[0], max(int(n), 1)
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        if weights.ndim == 1:
+            weights = weights.reshape(1, -1)
+        if weights.ndim != 2 or weights.shape[1] != 1 + table.full_dim:
+            raise HnswError(_lib.ERR_BAD_DIM, "weights must be [1 + %d] or nq x (1 + %d)" % (table.full_dim, table.full_dim))
+        if (lo is None) != (hi is None):
+            raise ValueError("a label range needs lo and hi, both or neither")
+        mo = self._mask_of(mask_of, nq)
+        rng = (None, None) if lo is None else self._range(lo, hi, nq)
+        ids = np.full((nq, width), _lib.UINT32_MAX, dtype=np.uint32)
+        scores = np.full((nq, width), np.inf, dtype=np.float32)
+        dists = np.full((nq, width), np.inf, dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        stats = np.zeros((nq, 4), dtype=np.int32)
+        check(self._L.hnsw_search_batch_boosted(
+            self._h, table._t, _p(Q, _f32p), nq, n, pool, ef, _p(weights, _f32p), weights.shape[0],
+            mask_set._s if mask_set is not None else None, None if mo is None else _p(mo, _u32p),
+            None if rng[0] is None else _p(rng[0], _u32p), None if rng[1] is None else _p(rng[1], _u32p), _p(ids, _u32p),
+            _p(scores, _f32p), _p(dists, _f32p), _p(counts, _u32p), C.cast(stats.ctypes.data, C.POINTER(QueryStats))))
+        return ids, scores, dists, counts, stats.view(np.uint32).astype(np.int64)
+
+    @staticmethod
+    def boost_device(nq, pool, n_out, n_attrs, dtype, d_table, table_rows, d_weights, weights_rows, d_ids_in, d_dists_in,
+                     d_counts_in, d_stats_in, d_ids, d_scores, d_dists=None, d_counts=None, d_stats=None, stream=0):
+        """hnsw_boost_device over torch device tensors (or raw device pointers): boost.boost_device.  ONE launch enqueued
+        on `stream` of the current device, no sync of it; needs no index."""
+        from .boost import boost_device
+        boost_device(nq, pool, n_out, n_attrs, dtype, d_table, table_rows, d_weights, weights_rows, d_ids_in, d_dists_in,
+                     d_counts_in, d_stats_in, d_ids, d_scores, d_dists, d_counts, d_stats, stream)
+
+    def load_row_table(self, path):
+        """-> refine.RowTable: the table RowTable.save wrote to `path`, created on this index and written to its device
+        (hnsw_row_table_load).  A file that is not a whole, finite row table raises (ERR_IO) before any device is touched,
+        but for a NaN or an infinity among its elements."""
+        from .refine import RowTable
+        t = C.c_void_p()
+        check(self._L.hnsw_row_table_load(self._h, str(path).encode(), C.byref(t)))
+        return RowTable(self, t)
+
     def search_filtered(self, q, n, ef, lo=0, hi=0xFFFFFFFF, mask_set=None, row=None):
         """ONE query under the label range [lo, hi] and, with a resident MaskSet, its row `row` (None, -1 or MASK_NONE: no
         row): hnsw_search_filtered, whose concurrent callers on an index are gathered into one launch.

@@ -110,8 +110,8 @@ def refine_device(nq, pool, n_out, full_dim, dtype, d_table, table_rows, d_Qfull
 
 class RowTable:
     """hnsw_row_table: full rows -- float32 or float16 -- that live in HBM beside an index, row id = index id
-    (HNSW.row_table makes one).  The host keeps no copy; the table is not saved, cloned or replicated with the index.
-    Keeps its index alive; close() (or garbage collection) frees it."""
+    (HNSW.row_table makes one).  The host keeps no copy; the table is not saved, cloned or replicated with the index
+    (save and HNSW.load_row_table carry it in a file of its own).  Keeps its index alive; close() (or garbage collection) frees it."""
 
     def __init__(self, index, handle):
         self._index = index
@@ -159,6 +159,11 @@ class RowTable:
         out = np.zeros((int(n), self.full_dim), dtype=np.float32)
         check(self._L.hnsw_row_table_read(self._t, int(first_id), int(n), out.ctypes.data_as(_lib.f32p)))
         return out
+
+    def save(self, path):
+        """the table into one file at `path` (hnsw_row_table_save: a big-endian header and the rows in the table's dtype,
+        bit for bit); HNSW.load_row_table reads it back.  A table that was never written needs no GPU."""
+        check(self._L.hnsw_row_table_save(self._t, str(path).encode()))
 
     def device(self):
         """-> (device pointer of the array in HBM or None before the first write, rows): what refine_device takes"""

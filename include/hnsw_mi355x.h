@@ -1142,7 +1142,7 @@ int hnsw_search_batch_late_exact(hnsw_index *h, const float *Q /* nq x n_vecs x 
  * rows than the index.  nq == 0 is HNSW_OK; an empty index is HNSW_ERR_EMPTY.  hnsw_get_stat: "refine_calls"
  * (hnsw_search_batch_refined calls answered), "refine_launches" (the refinements they launched), "row_table_writes"
  * (writes that reached a table of the handle).
- * Not provided: bf16 rows; a table per shard and a refined partitioned search; persistence of the table; one-query
+ * Not provided: bf16 rows; a table per shard and a refined partitioned search; the table inside hnsw_save (hnsw_row_table_save, below, writes it to a file of its own); one-query
  * gathered calls; the Rust shim's binding; a place in the update machine (an inserted id needs its full row written
  * before a search may return it: the table must cover the index). */
 #define HNSW_ROWS_F32 0
@@ -1275,6 +1275,87 @@ int hnsw_search_batch_hybrid(hnsw_index *h, const float *Q /* nq x dim */, uint6
                              const uint32_t *hi /* or NULL */, uint32_t *ids /* nq x n */, float *scores /* or NULL */,
                              float *dists /* or NULL */, uint32_t *counts /* or NULL */, uint32_t *unique /* or NULL */,
                              uint32_t *dropped /* or NULL */, hnsw_query_stats *stats /* or NULL */);
+
+/* ---- boosted search: the pool re-ranked by per-id attributes kept in HBM ------------------------------------------------
+ * An extension (the reference ranks by distance alone): what Elasticsearch calls function_score and Vespa a first-phase
+ * rank profile.  "Near the query, but newer, more popular, in stock and not demoted" is a ranking by
+ * w0 * distance + w1 * attr1[id] + w2 * attr2[id] + ...  The attributes belong to the id, so they live in HBM beside it:
+ * a row table (refined search, above) with full_dim = A is an attribute table of A columns, written, read and grown by
+ * the same calls.  This is not the rank fusion's linear mode, whose scores are per query and per list and go up with
+ * every call.
+ *
+ * THE BOOST of one query, with a candidate list ids_in [pool] and dists_in [pool] (the distances ARE an input here),
+ * counts_in or NULL, stats_in or NULL, a weight row w [1 + A] of f32 and a table of table_rows rows of A elements,
+ * HNSW_ROWS_F32 or HNSW_ROWS_F16 (an f16 element is widened exactly where it is read):
+ *   - entry j is PRESENT exactly as in THE REFINEMENT: iff j < min(count, pool), or, without counts, iff its id is not
+ *     UINT32_MAX;
+ *   - an incoming status that is not HNSW_OK fails the query with that status; otherwise a present id at or beyond
+ *     table_rows gives HNSW_ERR_ARG, and no table row is read for the query.  A failed query has count 0 and padded rows;
+ *   - the score of a present entry with distance d and row a is s = w[0] * d, then p = w[k + 1] * a[k]; s = s + p for
+ *     k = 0 .. A - 1: ONE left-to-right f32 chain, every multiply and every add rounded on its own and never contracted
+ *     into a fused multiply-add.  A result of -0.0f is taken as +0.0f and returned as +0.0f.  Infinite, zero and negative
+ *     weights are legal, and a NaN weight is no argument error; an entry whose score is NaN is never returned, so a NaN
+ *     weight returns nothing, and w[0] == 0 with d == +inf (0 * inf) DROPS the entry: pass a small positive w[0], not
+ *     zero, to ignore finite distances while keeping unreachable candidates out of the way;
+ *   - SMALLER IS BETTER: the present entries are ranked ascending by (s under f32 <, then id, then position in the
+ *     incoming list); duplicate ids in a list are separate entries; -inf ranks first and +inf last, both returned.
+ * Per query: ids [n_out] (pad UINT32_MAX), scores [n_out] (pad +inf), dists [n_out] (optional: the incoming distance of
+ * each returned hit, pad +inf), counts (optional) = entries written, stats (required iff stats_in is given): the incoming
+ * record unchanged but for the status above.  Every output word is written exactly once.  Limits: 1 <= n_out <= pool <=
+ * HNSW_BOOST_POOL_MAX, 1 <= A <= HNSW_BOOST_MAX_ATTRS, nq <= 2^31 - 1; weights_rows is 1 (one row shared by every query)
+ * or nq (weights [nq][1 + A]).
+ *
+ * hnsw_boost_device is THE BOOST alone over buffers in HBM.  It takes no handle, as hnsw_refine_device takes none: ONE
+ * launch (the distance seam's kernel in its boost form, one wave per query) is enqueued on `stream` -- no synchronise, no
+ * allocation, no copy.  d_table holds table_rows x n_attrs elements of dtype; outputs must not overlap inputs.  The status
+ * of a failed query is written to d_stats only.  HNSW_ERR_ARG, decided before the device is touched: a limit violated; a
+ * dtype other than the two; nq > 2^31 - 1; weights_rows not 1 or nq; d_table, d_weights, d_ids_in, d_dists_in, d_ids or
+ * d_scores NULL; exactly one of d_stats_in / d_stats given.  nq == 0 is HNSW_OK whatever else is passed.
+ *
+ * hnsw_search_batch_boosted answers host-pointer queries.  By definition the result is THE BOOST, with n_out = n and A =
+ * the table's full_dim, of the lists that the candidate call of hnsw_search_batch_diverse's table returns for Q with
+ * n = pool and ef' = max(ef, pool, 1), and everything is inherited exactly as in hnsw_search_batch_refined: the filter
+ * (set / mask_of / lo / hi), deleted ids taken out, the metric_cosine option, the planner, per-query errors, pool <= 64
+ * and ef' <= 256 under a filter or deletions.  Unfiltered and with nothing deleted the call stays on the device: the
+ * queries and the weights go up once, the launch of hnsw_search_batch_device and the re-run loop of its _finish, one boost
+ * launch, ONE copy of the block [ids | scores | dists | counts | stats] back.  scores, dists, counts and stats may be
+ * NULL.  HNSW_ERR_ARG, decided before the device is touched: the filter's own refusals; t NULL or of another handle; a
+ * limit violated (a table of more than HNSW_BOOST_MAX_ATTRS columns is one); Q, weights or ids NULL; nq > 2^31 - 1;
+ * weights_rows not 1 or nq; a table with fewer rows than the index; and, once the snapshot's device is known, a table on
+ * another device.  nq == 0 is HNSW_OK; an empty index is HNSW_ERR_EMPTY.  hnsw_get_stat: "boost_calls"
+ * (hnsw_search_batch_boosted calls answered), "boost_launches" (the boosts they launched, and hnsw_boost_device's: that
+ * call has no handle, so its launches are counted for the process and every handle's key includes them).
+ *
+ * A row table in a file.  hnsw_save and hnsw_load do not carry a table; these two calls do, one file per table:
+ *   hnsw_row_table_save   big-endian like the index's format: magic "HXRT" u32, version u32 = 1, full_dim u32, dtype u32,
+ *                         rows u64, then rows x full_dim elements in the table's dtype.  The rows are read back from HBM
+ *                         in chunks of at most 64 MiB.  A table that was never written saves rows = 0 and touches no
+ *                         device.  HNSW_ERR_IO when the file cannot be created or written.
+ *   hnsw_row_table_load   creates a table on h and writes the rows to it (the first chunk allocates, as a first write
+ *                         does).  HNSW_ERR_IO for a file that cannot be opened, a bad magic or version, a full_dim or
+ *                         dtype out of range, a file shorter or longer than its header says -- all decided before any
+ *                         device is touched -- and for a NaN or infinite element; *out is then left alone.  The round
+ *                         trip is bit-exact: -0, f16 subnormals and 65504 survive.
+ * Not provided: more than 32 attributes; combiners other than the weighted sum (products, decay functions, clamps); a
+ * boost over shards; one-query gathered calls; the Rust shim's binding; carrying a table through hnsw_clone or the
+ * snapshot exchange (save it and load it on the other handle). */
+#define HNSW_BOOST_POOL_MAX 1024
+#define HNSW_BOOST_MAX_ATTRS 32
+int hnsw_boost_device(uint64_t nq, uint32_t pool, uint32_t n_out, uint32_t n_attrs, uint32_t dtype,
+                      const void *d_table /* table_rows x n_attrs of dtype */, uint64_t table_rows,
+                      const float *d_weights /* weights_rows x (1 + n_attrs) */, uint64_t weights_rows /* 1 or nq */,
+                      const uint32_t *d_ids_in /* nq x pool */, const float *d_dists_in /* nq x pool */,
+                      const uint32_t *d_counts_in /* or NULL */, const hnsw_query_stats *d_stats_in /* or NULL */,
+                      uint32_t *d_ids, float *d_scores /* nq x n_out */, float *d_dists /* or NULL */,
+                      uint32_t *d_counts /* or NULL */, hnsw_query_stats *d_stats /* required iff d_stats_in */, void *stream);
+int hnsw_search_batch_boosted(hnsw_index *h, hnsw_row_table *t, const float *Q /* nq x dim */, uint64_t nq, uint32_t n,
+                              uint32_t pool, uint32_t ef, const float *weights /* weights_rows x (1 + full_dim) */,
+                              uint64_t weights_rows /* 1 or nq */, hnsw_mask_set *set /* or NULL */,
+                              const uint32_t *mask_of /* or NULL */, const uint32_t *lo /* or NULL */,
+                              const uint32_t *hi /* or NULL */, uint32_t *ids /* nq x n */, float *scores /* or NULL */,
+                              float *dists /* or NULL */, uint32_t *counts /* or NULL */, hnsw_query_stats *stats /* or NULL */);
+int hnsw_row_table_save(hnsw_row_table *t, const char *path);
+int hnsw_row_table_load(hnsw_index *h, const char *path, hnsw_row_table **out);
 
 /* Test seams that mirror the reference's own units:
  * VecBase::dist2many (vectors/src/lib.rs:17-22): the query (quantised like ann_by_vector does,
@@ -1465,7 +1546,9 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * exact call's); exact document scoring: "docs_calls" (hnsw_search_batch_late_exact calls answered), "docs_launches"
  * (hnsw_score_documents_device's included), "doc_index_uploads" and "doc_index_keys_uploaded" (whole copies of the
  * document index to HBM, and the 8-byte keys they carried); hybrid search: "hybrid_calls" (hnsw_search_batch_hybrid
- * calls answered), "hybrid_fuse_launches" (rank fusions launched, hnsw_fuse_ranked_device's included); deletion:
+ * calls answered), "hybrid_fuse_launches" (rank fusions launched, hnsw_fuse_ranked_device's included); boosted search:
+ * "boost_calls" (hnsw_search_batch_boosted calls answered), "boost_launches" (the boosts they launched, and every
+ * hnsw_boost_device launch of the process: that call has no handle); deletion:
  * "deleted" (ids deleted now), "deleted_mask_words_uploaded" (64-id words of the deleted set copied to HBM), and the
  * unfiltered entry points' queries answered under deletions by path, "deleted_queries_graph" (0),
  * "deleted_queries_exact" (1), "deleted_overflow_exact" (2) */
