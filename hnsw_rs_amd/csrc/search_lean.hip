@@ -94,10 +94,25 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 }
 #define STAMP(var) const unsigned long long var = stamp_now()
 #define STAMP_ADD(slot, a, b) dbg_acc[slot] += (b) - (a)
-constexpr int HX_LEAN_DBG_SLOTS = 26;  // values per query in the side buffer (scripts/stamps_lean.py allocates it)
+constexpr int HX_LEAN_DBG_SLOTS = 36;  // values per query in the side buffer (scripts/stamps_lean.py allocates it)
+// A merge's own split: five values from `dbg` on (the f32 kernel passes dbg_acc + 26 for c's merge, + 31 for p's; a
+// caller without a side buffer passes nothing and its merges carry no stamp) -- cycles of the survivor loop, of the
+// LDS phase (scatter, read back, holes, refresh_last) and of the shift path, the survivors of the big merges, the big
+// merges.  Static offsets: a computed index would move the caller's array to scratch.
+#define MERGE_DBG_PARAM , unsigned long long *dbg = nullptr
+#define MERGE_DBG_ARG(first) , dbg_acc + (first)
+#define MERGE_STAMP(var) const unsigned long long var = dbg ? stamp_now() : 0ull
+#define MERGE_ADD(off, v) \
+    do {                  \
+        if (dbg) dbg[off] += (v); \
+    } while (0)
 #else
 #define STAMP(var)
 #define STAMP_ADD(slot, a, b)
+#define MERGE_DBG_PARAM
+#define MERGE_DBG_ARG(first)
+#define MERGE_STAMP(var)
+#define MERGE_ADD(off, v)
 #endif
 
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) {
@@ -269,6 +284,15 @@ struct Visited {
 #ifndef HX_MERGE_SHIFT_MAX
 #define HX_MERGE_SHIFT_MAX 2  // survivors merged one at a time by shifting the list; more go through LDS
 #endif
+// A big merge's survivors, compacted: every survivor lane writes its key at its rank among the set bits of
+// smask.  One LK_INVALID pad goes behind the last key, so that the readers, which take two keys per trip, need
+// no guard at an odd count (LK_INVALID is below nothing: a pad counts nowhere; behind an even count nobody reads it).
+__device__ __forceinline__ void stage_survivors(u64 key, bool surv, u64 smask, uint32_t m, u64 *perm) {
+    const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(smask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)smask, 0u));
+    if (surv) perm[rk] = key;
+    if (surv && rk + 1 == m) perm[m] = LK_INVALID;
+    asm volatile("" ::: "memory");  // LDS serves a wave's requests in order: written before they are read
+}
 template <int R>
 struct Lst {
     static constexpr int NR = R;  // list registers per lane
@@ -350,11 +374,12 @@ struct Lst {
 
     // Merge the wave's keys (LK_INVALID = none) into the list, keeping the ef smallest: the streaming
     // top-ef of searcher.rs:74-94 applied to a whole batch (order-independent).
-    __device__ __forceinline__ void merge(u64 key, uint32_t ef, u64 *perm, int lane) {
+    __device__ __forceinline__ void merge(u64 key, uint32_t ef, u64 *perm, int lane MERGE_DBG_PARAM) {
         const bool surv = key < last_key;  // last_key is LK_INVALID while the list is not full
         const u64 smask = __ballot(surv);
         if (smask == 0) return;
         const uint32_t m = (uint32_t)__popcll(smask);
+        MERGE_STAMP(m0);
         if (m <= HX_MERGE_SHIFT_MAX) {
             u64 it = smask;
             while (it) {
@@ -384,13 +409,14 @@ struct Lst {
                 }
                 refresh_last(ef);
             }
+            MERGE_STAMP(m1);
+            MERGE_ADD(2, m1 - m0);
             return;
         }
-        // Three or more.  One loop over the survivors, no vector -> scalar hand-off in it: every list
-        // entry counts the survivors that sort before it (its shift), every survivor its rank among the
-        // survivors.  The list entries then go to their final places through LDS; the places nobody wrote
-        // are the survivors', in order: the s-th hole takes the survivor of rank s (sv[], filled on the
-        // way).  perm holds 64 R entries, sv the 64 behind them.
+        // Three or more.  Every list entry counts the survivors that sort before it (its shift), every
+        // survivor its rank among the survivors.  The list entries then go to their final places through
+        // LDS; the places nobody wrote are the survivors', in order: the s-th hole takes the survivor of
+        // rank s (sv[], filled on the way).  perm holds 64 R entries, sv the 64 behind them.
         u64 *sv = perm + 64 * R;
         u64 Lm[R];
         uint32_t shift[R];
@@ -400,15 +426,29 @@ struct Lst {
             shift[r] = 0;
         }
         uint32_t srank = 0;
-        u64 it = smask;
-        while (it) {
-            const uint32_t j = (uint32_t)__ffsll((long long)it) - 1;
-            it &= it - 1;
-            const u64 e = rdlane64(key, j);
+        // The survivors are compacted into the front of perm (free until the scatter below initialises it;
+        // m <= 64, so the pad at most touches sv[0]) and read back two per trip from a wave-uniform address,
+        // a broadcast: no vector -> scalar hand-off, no find-first, no read-lane per survivor.  The next
+        // pair is requested before this one is counted.  (LDS serves a wave's requests in order.)
+        stage_survivors(key, surv, smask, m, perm);
+        {
+            const ulonglong2 *st = reinterpret_cast<const ulonglong2 *>(perm);
+            const uint32_t trips = (m + 1) >> 1;
+            ulonglong2 e = st[0];
+            for (uint32_t t = 1; t < trips; t++) {
+                const ulonglong2 nx = st[t];
 #pragma unroll
-            for (int r = 0; r < R; r++) shift[r] += e < Lm[r] ? 1u : 0u;
-            srank += e < key ? 1u : 0u;
+                for (int r = 0; r < R; r++) shift[r] += (e.x < Lm[r] ? 1u : 0u) + (e.y < Lm[r] ? 1u : 0u);
+                srank += (e.x < key ? 1u : 0u) + (e.y < key ? 1u : 0u);
+                e = nx;
+            }
+#pragma unroll
+            for (int r = 0; r < R; r++) shift[r] += (e.x < Lm[r] ? 1u : 0u) + (e.y < Lm[r] ? 1u : 0u);
+            srank += (e.x < key ? 1u : 0u) + (e.y < key ? 1u : 0u);
         }
+        asm volatile("" ::: "memory");  // every staged key has been requested before perm is initialised
+        MERGE_STAMP(m2);
+        MERGE_ADD(0, m2 - m0);
         const uint32_t n_new = min(n_cur + m, ef);
 #pragma unroll
         for (int r = 0; r < R; r++) perm[R * lane + r] = LK_INVALID;
@@ -445,6 +485,10 @@ struct Lst {
         n_cur = n_new;
         lds_fence();
         refresh_last(ef);
+        MERGE_STAMP(m3);
+        MERGE_ADD(1, m3 - m2);
+        MERGE_ADD(3, m);
+        MERGE_ADD(4, 1);
     }
 };
 
@@ -521,11 +565,12 @@ struct LstHT {
         return ((u64)hi << 32) | lo;
     }
 
-    __device__ __forceinline__ void merge(u64 key, uint32_t ef, u64 *perm, int lane) {
+    __device__ __forceinline__ void merge(u64 key, uint32_t ef, u64 *perm, int lane MERGE_DBG_PARAM) {
         const bool surv = key < last_key;  // last_key is LK_INVALID while the list is not full
         const u64 smask = __ballot(surv);
         if (smask == 0) return;
         const uint32_t m = (uint32_t)__popcll(smask);
+        MERGE_STAMP(m0);
         if (m <= HX_MERGE_SHIFT_MAX) {
             u64 it = smask;
             while (it) {
@@ -550,6 +595,8 @@ struct LstHT {
                 if (64u + (uint32_t)lane >= ef) L[1] = LK_INVALID;
                 refresh_last(ef);
             }
+            MERGE_STAMP(m1);
+            MERGE_ADD(2, m1 - m0);
             return;
         }
         // Three or more: the rank / scatter merge of Lst<R> over the two registers (perm: 128 entries,
@@ -557,15 +604,26 @@ struct LstHT {
         u64 *sv = perm + 128;
         const u64 Mm = L[0] & LK_MASK, Tm = L[1] & LK_MASK;
         uint32_t sh0 = 0, sh1 = 0, srank = 0;
-        u64 it = smask;
-        while (it) {
-            const uint32_t j = (uint32_t)__ffsll((long long)it) - 1;
-            it &= it - 1;
-            const u64 e = rdlane64(key, j);
-            sh0 += e < Mm ? 1u : 0u;
-            sh1 += e < Tm ? 1u : 0u;
-            srank += e < key ? 1u : 0u;
+        // the survivors compacted into the front of perm and read back two per trip by broadcast, as in Lst<R>
+        stage_survivors(key, surv, smask, m, perm);
+        {
+            const ulonglong2 *st = reinterpret_cast<const ulonglong2 *>(perm);
+            const uint32_t trips = (m + 1) >> 1;
+            ulonglong2 e = st[0];
+            for (uint32_t t = 1; t < trips; t++) {
+                const ulonglong2 nx = st[t];
+                sh0 += (e.x < Mm ? 1u : 0u) + (e.y < Mm ? 1u : 0u);
+                sh1 += (e.x < Tm ? 1u : 0u) + (e.y < Tm ? 1u : 0u);
+                srank += (e.x < key ? 1u : 0u) + (e.y < key ? 1u : 0u);
+                e = nx;
+            }
+            sh0 += (e.x < Mm ? 1u : 0u) + (e.y < Mm ? 1u : 0u);
+            sh1 += (e.x < Tm ? 1u : 0u) + (e.y < Tm ? 1u : 0u);
+            srank += (e.x < key ? 1u : 0u) + (e.y < key ? 1u : 0u);
         }
+        asm volatile("" ::: "memory");  // every staged key has been requested before perm is initialised
+        MERGE_STAMP(m2);
+        MERGE_ADD(0, m2 - m0);
         const uint32_t n_new = min(n_cur + m, ef);
         perm[lane] = LK_INVALID;
         perm[64 + lane] = LK_INVALID;
@@ -591,6 +649,10 @@ struct LstHT {
         n_cur = n_new;
         lds_fence();
         refresh_last(ef);
+        MERGE_STAMP(m3);
+        MERGE_ADD(1, m3 - m2);
+        MERGE_ADD(3, m);
+        MERGE_ADD(4, 1);
     }
 };
 
@@ -756,7 +818,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     uint32_t n_dist = 0, n_exp = 0, sum_deg = 0, n_vis = 0;
     int32_t status = HNSW_OK;
 #ifdef HX_STAMPS
-    unsigned long long dbg_acc[HX_LEAN_DBG_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long dbg_acc[HX_LEAN_DBG_SLOTS] = {};
     const unsigned long long t_begin = __builtin_readcyclecounter();
     // the runner-up's misses (slots 16 .. 24): what the last miss predicted for the pass that follows it
     bool dbg_follow = false, dbg_took_pre = false;
@@ -1186,7 +1248,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                     }
                 }
             }
-            lst.merge(upper ? LK_INVALID : key, ef, perm, lane);
+            lst.merge(upper ? LK_INVALID : key, ef, perm, lane MERGE_DBG_ARG(26));
             STAMP(f3b);
             STAMP_ADD(8, f3, f3b);
             if (HX_UNLIKELY((pm & 0xFFFFFFFFull) != 0)) {  // degree > S0: the rest of c's row goes through the next passes (rare)
@@ -1250,7 +1312,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 dbg_acc[15]++;
             }
 #endif
-            lst.merge(pfresh ? key : LK_INVALID, ef, perm, lane);
+            lst.merge(pfresh ? key : LK_INVALID, ef, perm, lane MERGE_DBG_ARG(31));
             STAMP(f5);
             STAMP_ADD(10, f4b, f5);
         }

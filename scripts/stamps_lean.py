@@ -18,7 +18,7 @@ dev = torch.device('cuda:0')
 dQ = torch.from_numpy(qs).to(dev)
 ids = torch.empty((nq, n), dtype=torch.int32, device=dev); dd = torch.empty((nq, n), dtype=torch.float32, device=dev)
 cnt = torch.empty(nq, dtype=torch.int32, device=dev); st = torch.empty((nq, 4), dtype=torch.int32, device=dev)
-SLOTS = 26  # HX_LEAN_DBG_SLOTS (search_lean.hip)
+SLOTS = 36  # HX_LEAN_DBG_SLOTS (search_lean.hip)
 dbg = torch.zeros((nq, SLOTS), dtype=torch.int64, device=dev)
 os.environ['HX_DBG_PTR'] = str(dbg.data_ptr())
 names = {0: 'pick c,p + adjacency row round trip', 1: 'visited: insert c, look up p', 2: 'row gather until landed',
@@ -47,6 +47,13 @@ for ef in efs:
     print('   unaccounted %.1f%%' % (100 * (tot.mean() - acc) / tot.mean()))
     print('   per query: visited slow-loop rounds %.1f; merges with 0 / 1-2 / >=3 survivors: %.1f / %.1f / %.1f; p commits %.1f' % (
         D[:, 11].mean(), D[:, 12].mean(), D[:, 13].mean(), D[:, 14].mean(), D[:, 15].mean()))
+    # the merges' own split (slots 26 .. 30 c's merge, 31 .. 35 p's): cycles of the survivor loop, of the LDS phase and of
+    # the shift path, the survivors of the big merges, the big merges.  (The split's own stamps lengthen slots 8 and 10.)
+    for nm, b in (('merge c', 26), ('merge p', 31)):
+        nbig, nsv = D[:, b + 4].sum(), D[:, b + 3].sum()
+        print('   %s: survivor loop %.0f, LDS phase %.0f, shift path %.0f cycles/query; %.1f big merges of %.1f survivors: loop %.0f + LDS phase %.0f cycles per big merge, loop %.1f per survivor' % (
+            nm, D[:, b].mean(), D[:, b + 1].mean(), D[:, b + 2].mean(), D[:, b + 4].mean(), nsv / max(1, nbig),
+            D[:, b].sum() / max(1, nbig), D[:, b + 1].sum() / max(1, nbig), D[:, b].sum() / max(1, nsv)))
     # the runner-up's misses: c's merge puts a fresh key below p (slots 16 .. 22)
     miss = D[:, 16:19].sum(1)
     took = D[:, 22]
@@ -65,6 +72,8 @@ for ef in efs:
         print('            misses 1/2/>=3 below p %3d/%3d/%3d  predicted %3d  old p again %3d  slot 0 per pass: ahead %5.0f (%3d passes), others %5.0f  slot 1 per pass %5.0f  kept %3d passes at %5.0f' % (
             D[qi, 16], D[qi, 17], D[qi, 18], D[qi, 19], D[qi, 20], D[qi, 21] / max(1, took[qi]), took[qi],
             (D[qi, 0] - D[qi, 21]) / max(1, passes[qi] - took[qi]), D[qi, 1] / max(1, passes[qi]), D[qi, 24], D[qi, 23] / max(1, D[qi, 24])))
+        print('            merge c + p: survivor loop %6.0f  LDS phase %6.0f  shift path %6.0f cycles; big merges %3d with %4d survivors' % (
+            D[qi, 26] + D[qi, 31], D[qi, 27] + D[qi, 32], D[qi, 28] + D[qi, 33], D[qi, 30] + D[qi, 35], D[qi, 29] + D[qi, 34]))
     cc = np.corrcoef(tot, S[:, 1])[0, 1]
     fit = np.polyfit(S[:, 1].astype(np.float64), tot, 1)
     print('   corr(total cycles, n_exp) = %.3f; fit: cycles = %.0f * n_exp + %.0f; n_exp mean %.1f p99 %.0f max %d' % (
