@@ -94,7 +94,7 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 }
 #define STAMP(var) const unsigned long long var = stamp_now()
 #define STAMP_ADD(slot, a, b) dbg_acc[slot] += (b) - (a)
-constexpr int HX_LEAN_DBG_SLOTS = 36;  // values per query in the side buffer (scripts/stamps_lean.py allocates it)
+constexpr int HX_LEAN_DBG_SLOTS = 40;  // values per query in the side buffer (scripts/stamps_lean.py allocates it)
 // A merge's own split: five values from `dbg` on (the f32 kernel passes dbg_acc + 26 for c's merge, + 31 for p's; a
 // caller without a side buffer passes nothing and its merges carry no stamp) -- cycles of the survivor loop, of the
 // LDS phase (scatter, read back, holes, refresh_last) and of the shift path, the survivors of the big merges, the big
@@ -386,29 +386,36 @@ struct Lst {
                 const uint32_t j = (uint32_t)__ffsll((long long)it) - 1;
                 it &= it - 1;
                 const u64 e = rdlane64(key, j);
-                if (!(e < last_key)) continue;  // the first insert tightened the bound
-                uint32_t pos = 0;
-#pragma unroll
-                for (int r = 0; r < R; r++) pos += (uint32_t)__popcll(__ballot((L[r] & LK_MASK) < e));
-                // entries from pos on move up by one: entry i takes entry i - 1, i.e. register r takes
-                // register r - 1 of the same lane, register 0 takes register R - 1 of the lane below
+                // Keys are unique and the list ascends, so "entry i lies above e" holds from e's place on and
+                // nowhere before it: the place never becomes a number.  An entry above e takes the entry before
+                // it (register r - 1 of the same lane; for register 0, register R - 1 of the lane below) if that
+                // one lies above e too, else e; the others stay.  Compares feeding selects: no ballot, no
+                // popcount, nothing handed to the scalar unit.  (Lane 0 has no lane below: the row reads 0 there,
+                // which is above nothing.  LK_INVALID without its flag is above every key.)
                 const uint32_t plo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)L[R - 1], 0x138, 0xF, 0xF, false);
                 const uint32_t phi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(L[R - 1] >> 32), 0x138, 0xF, 0xF, false);
-                u64 below = ((u64)phi << 32) | plo;
+                const u64 below = ((u64)phi << 32) | plo;
+                bool g[R];
+#pragma unroll
+                for (int r = 0; r < R; r++) g[r] = (L[r] & LK_MASK) > e;
+                const bool gb = (below & LK_MASK) > e;
 #pragma unroll
                 for (int r = R - 1; r >= 0; r--) {
-                    const uint32_t idx = (uint32_t)(R * lane + r);
                     const u64 from = r > 0 ? L[r > 0 ? r - 1 : 0] : below;
-                    L[r] = idx < pos ? L[r] : (idx == pos ? e : from);
+                    const bool gp = r > 0 ? g[r > 0 ? r - 1 : 0] : gb;
+                    L[r] = g[r] ? (gp ? from : e) : L[r];
                 }
-                n_cur = min(n_cur + 1, ef);
-                if (ef < 64u * R) {
-#pragma unroll
-                    for (int r = 0; r < R; r++)
-                        if ((uint32_t)(R * lane + r) >= ef) L[r] = LK_INVALID;
-                }
-                refresh_last(ef);
             }
+            // The bound is not tightened between two keys: a key that is not below the tightened bound lands at
+            // place ef or beyond, as does every entry pushed there, and one cut removes them all (still the ef
+            // smallest of list and survivors: order-independent).
+            n_cur = min(n_cur + m, ef);
+            if (ef < 64u * R) {
+#pragma unroll
+                for (int r = 0; r < R; r++)
+                    if ((uint32_t)(R * lane + r) >= ef) L[r] = LK_INVALID;
+            }
+            refresh_last(ef);
             MERGE_STAMP(m1);
             MERGE_ADD(2, m1 - m0);
             return;
@@ -564,6 +571,15 @@ struct LstHT {
         const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), 0x138, 0xF, 0xF, false);
         return ((u64)hi << 32) | lo;
     }
+    // lane i takes lane i - 1's value of v, lane 0 takes lane 63's value of w: v's row behind w's (wave_ror:1 puts w's
+    // last lane into lane 0; the shift has no source there and keeps it)
+    static __device__ __forceinline__ u64 shr1_behind(u64 v, u64 w) {
+        const int wlo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)w, 0x13C, 0xF, 0xF, false);
+        const int whi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(w >> 32), 0x13C, 0xF, 0xF, false);
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(wlo, (int)(uint32_t)v, 0x138, 0xF, 0xF, false);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(whi, (int)(uint32_t)(v >> 32), 0x138, 0xF, 0xF, false);
+        return ((u64)hi << 32) | lo;
+    }
 
     __device__ __forceinline__ void merge(u64 key, uint32_t ef, u64 *perm, int lane MERGE_DBG_PARAM) {
         const bool surv = key < last_key;  // last_key is LK_INVALID while the list is not full
@@ -577,24 +593,21 @@ struct LstHT {
                 const uint32_t j = (uint32_t)__ffsll((long long)it) - 1;
                 it &= it - 1;
                 const u64 e = rdlane64(key, j);
-                if (!(e < last_key)) continue;  // the first insert tightened the bound
-                const uint32_t pos = (uint32_t)__popcll(__ballot((L[0] & LK_MASK) < e));
-                if (pos < 64u) {
-                    // into the head: its last entry moves to the front of the tail
-                    const u64 carry = rdlane64(L[0], 63);
-                    const u64 below = shr1(L[0]);
-                    L[0] = (uint32_t)lane < pos ? L[0] : ((uint32_t)lane == pos ? e : below);
-                    const u64 tb = shr1(L[1]);
-                    L[1] = lane == 0 ? carry : tb;
-                } else {
-                    const uint32_t tpos = (uint32_t)__popcll(__ballot((L[1] & LK_MASK) < e));
-                    const u64 tb = shr1(L[1]);
-                    L[1] = (uint32_t)lane < tpos ? L[1] : ((uint32_t)lane == tpos ? e : tb);
-                }
-                n_cur = min(n_cur + 1, ef);
-                if (64u + (uint32_t)lane >= ef) L[1] = LK_INVALID;
-                refresh_last(ef);
+                // As in Lst<R>: an entry above e takes the entry before it if that one lies above e too, else e.
+                // The entry before the tail's first is the head's last (b1's lane 0), so the head's carry needs no
+                // case of its own: into the head, the whole tail lies above e and above the head's last entry and
+                // moves up by one behind it; beyond entry 63, the head has nothing above e and stays.  Both
+                // registers run the same few instructions every time.
+                const u64 b0 = shr1(L[0]), b1 = shr1_behind(L[1], L[0]);
+                const bool g0 = (L[0] & LK_MASK) > e, p0 = (b0 & LK_MASK) > e;
+                const bool g1 = (L[1] & LK_MASK) > e, p1 = (b1 & LK_MASK) > e;
+                L[0] = g0 ? (p0 ? b0 : e) : L[0];
+                L[1] = g1 ? (p1 ? b1 : e) : L[1];
             }
+            // one cut and one bound for all keys (see Lst<R>::merge)
+            n_cur = min(n_cur + m, ef);
+            if (64u + (uint32_t)lane >= ef) L[1] = LK_INVALID;
+            refresh_last(ef);
             MERGE_STAMP(m1);
             MERGE_ADD(2, m1 - m0);
             return;
@@ -1194,6 +1207,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             {
                 const uint32_t mm = (uint32_t)__popcll(__ballot(!upper && key < lst.last_key));
                 if (mm == 0) dbg_acc[12]++; else if (mm <= 2) dbg_acc[13]++; else dbg_acc[14]++;  // static slots: a computed index would move the array to scratch
+                if (mm != 0 && mm <= HX_MERGE_SHIFT_MAX) { dbg_acc[36]++; dbg_acc[37] += mm; }  // c's small merges, their keys
             }
 #endif
             const u64 nanm = __ballot(nan);
@@ -1309,6 +1323,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             {
                 const uint32_t mm = (uint32_t)__popcll(__ballot(pfresh && key < lst.last_key));
                 if (mm == 0) dbg_acc[12]++; else if (mm <= 2) dbg_acc[13]++; else dbg_acc[14]++;  // static slots: a computed index would move the array to scratch
+                if (mm != 0 && mm <= HX_MERGE_SHIFT_MAX) { dbg_acc[38]++; dbg_acc[39] += mm; }  // p's small merges, their keys
                 dbg_acc[15]++;
             }
 #endif

@@ -18,7 +18,7 @@ dev = torch.device('cuda:0')
 dQ = torch.from_numpy(qs).to(dev)
 ids = torch.empty((nq, n), dtype=torch.int32, device=dev); dd = torch.empty((nq, n), dtype=torch.float32, device=dev)
 cnt = torch.empty(nq, dtype=torch.int32, device=dev); st = torch.empty((nq, 4), dtype=torch.int32, device=dev)
-SLOTS = 36  # HX_LEAN_DBG_SLOTS (search_lean.hip)
+SLOTS = 40  # HX_LEAN_DBG_SLOTS (search_lean.hip)
 dbg = torch.zeros((nq, SLOTS), dtype=torch.int64, device=dev)
 os.environ['HX_DBG_PTR'] = str(dbg.data_ptr())
 names = {0: 'pick c,p + adjacency row round trip', 1: 'visited: insert c, look up p', 2: 'row gather until landed',
@@ -54,6 +54,17 @@ for ef in efs:
         print('   %s: survivor loop %.0f, LDS phase %.0f, shift path %.0f cycles/query; %.1f big merges of %.1f survivors: loop %.0f + LDS phase %.0f cycles per big merge, loop %.1f per survivor' % (
             nm, D[:, b].mean(), D[:, b + 1].mean(), D[:, b + 2].mean(), D[:, b + 4].mean(), nsv / max(1, nbig),
             D[:, b].sum() / max(1, nbig), D[:, b + 1].sum() / max(1, nbig), D[:, b].sum() / max(1, nsv)))
+    # the small merges (slots 36 / 37 c's, 38 / 39 p's: merges that took the shift path, the keys they inserted); a small
+    # merge holds one or two keys while HX_MERGE_SHIFT_MAX is 2: two-key merges = keys - merges
+    for nm, b, c in (('merge c', 28, 36), ('merge p', 33, 38)):
+        ns, nk = D[:, c].sum(), D[:, c + 1].sum()
+        print('   %s: %.1f small merges of %.2f keys per query (with one key %.1f, with more %.1f): shift path %.0f cycles per small merge, %.0f per inserted key' % (
+            nm, D[:, c].mean(), nk / max(1, ns), (2 * D[:, c] - D[:, c + 1]).clip(0).mean(), (D[:, c + 1] - D[:, c]).clip(None, D[:, c]).mean(),
+            D[:, b].sum() / max(1, ns), D[:, b].sum() / max(1, nk)))
+    # ... and what a merge costs by itself and what every key adds: least squares over the queries
+    A = np.stack([D[:, 36] + D[:, 38], D[:, 37] + D[:, 39]], axis=1)
+    fx, fk = np.linalg.lstsq(A, D[:, 28] + D[:, 33], rcond=None)[0]
+    print('   shift path over the queries, least squares: %.0f cycles per small merge + %.0f per inserted key' % (fx, fk))
     # the runner-up's misses: c's merge puts a fresh key below p (slots 16 .. 22)
     miss = D[:, 16:19].sum(1)
     took = D[:, 22]
@@ -74,6 +85,9 @@ for ef in efs:
             (D[qi, 0] - D[qi, 21]) / max(1, passes[qi] - took[qi]), D[qi, 1] / max(1, passes[qi]), D[qi, 24], D[qi, 23] / max(1, D[qi, 24])))
         print('            merge c + p: survivor loop %6.0f  LDS phase %6.0f  shift path %6.0f cycles; big merges %3d with %4d survivors' % (
             D[qi, 26] + D[qi, 31], D[qi, 27] + D[qi, 32], D[qi, 28] + D[qi, 33], D[qi, 30] + D[qi, 35], D[qi, 29] + D[qi, 34]))
+        print('            small merges %3d with %3d keys: shift path %5.0f cycles per small merge, %5.0f per key, %.1f%% of the query' % (
+            D[qi, 36] + D[qi, 38], D[qi, 37] + D[qi, 39], (D[qi, 28] + D[qi, 33]) / max(1, D[qi, 36] + D[qi, 38]),
+            (D[qi, 28] + D[qi, 33]) / max(1, D[qi, 37] + D[qi, 39]), 100 * (D[qi, 28] + D[qi, 33]) / tot[qi]))
     cc = np.corrcoef(tot, S[:, 1])[0, 1]
     fit = np.polyfit(S[:, 1].astype(np.float64), tot, 1)
     print('   corr(total cycles, n_exp) = %.3f; fit: cycles = %.0f * n_exp + %.0f; n_exp mean %.1f p99 %.0f max %d' % (
