@@ -94,7 +94,21 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 }
 #define STAMP(var) const unsigned long long var = stamp_now()
 #define STAMP_ADD(slot, a, b) dbg_acc[slot] += (b) - (a)
+#ifdef HX_STAMPS_FRONT
+// (make stamps EXTRA=-DHX_STAMPS_FRONT) the front of the query split further, slots 40 .. 48: its stamps lengthen slot 7
+// by a fifth, so the plain stamps build, whose slot 7 the recorded profiles compare, does without them
+constexpr int HX_LEAN_DBG_SLOTS = 50;
+#define FSTAMP(var) STAMP(var)
+#define FSTAMP_ADD(slot, a, b) STAMP_ADD(slot, a, b)
+// the clock once the LDS requests are back, whatever is still in flight from memory (stamp_now would wait for it)
+#define FSTAMP_LDS(var)                                   \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
+    const unsigned long long var = __builtin_readcyclecounter(); \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+#define FSTAMP_SINCE_BEGIN(slot) dbg_acc[slot] = __builtin_readcyclecounter() - t_begin
+#else
 constexpr int HX_LEAN_DBG_SLOTS = 40;  // values per query in the side buffer (scripts/stamps_lean.py allocates it)
+#endif
 // A merge's own split: five values from `dbg` on (the f32 kernel passes dbg_acc + 26 for c's merge, + 31 for p's; a
 // caller without a side buffer passes nothing and its merges carry no stamp) -- cycles of the survivor loop, of the
 // LDS phase (scatter, read back, holes, refresh_last) and of the shift path, the survivors of the big merges, the big
@@ -113,6 +127,12 @@ constexpr int HX_LEAN_DBG_SLOTS = 40;  // values per query in the side buffer (s
 #define MERGE_DBG_ARG(first)
 #define MERGE_STAMP(var)
 #define MERGE_ADD(off, v)
+#endif
+#if !defined(HX_STAMPS) || !defined(HX_STAMPS_FRONT)
+#define FSTAMP(var)
+#define FSTAMP_ADD(slot, a, b)
+#define FSTAMP_LDS(var)
+#define FSTAMP_SINCE_BEGIN(slot)
 #endif
 
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) {
@@ -705,6 +725,26 @@ __device__ __forceinline__ float row_dist(const float *rows, uint32_t id, bool w
     }
     return __builtin_sqrtf(s);
 }
+// The best of an upper-layer row's fresh lanes (at least one): the smallest distance, on equal distance bits the
+// smaller id (dist.rs:30-38).  Returns its key; j is its lane.
+__device__ __forceinline__ u64 walk_winner(uint32_t nb, bool fresh, float dist, uint32_t &j) {
+    const uint32_t db = fresh ? __builtin_bit_cast(uint32_t, dist) : 0xFFFFFFFFu;
+    const uint32_t mn = wave_min_u32(db);
+    u64 tie = __ballot(fresh && db == mn);
+    j = (uint32_t)__ffsll((long long)tie) - 1;
+    uint32_t bid = rdlane(nb, j);
+    tie &= tie - 1;
+    while (tie) {
+        const uint32_t j2 = (uint32_t)__ffsll((long long)tie) - 1;
+        tie &= tie - 1;
+        const uint32_t id2 = rdlane(nb, j2);
+        if (id2 < bid) {
+            bid = id2;
+            j = j2;
+        }
+    }
+    return ((u64)mn << 32) | bid;
+}
 
 // ---------------------------------------------------------------------------------------------
 // What the three kernels of this file (hx_pair_f32_kernel, pair_kernel.inc, is the third) share around their
@@ -716,15 +756,28 @@ __device__ __forceinline__ float row_dist(const float *rows, uint32_t id, bool w
 // ---------------------------------------------------------------------------------------------
 // The query of a FullVec kernel: every lane holds all DS values (Point::new of a FullVec is the vector itself),
 // pinned to VGPRs for the whole kernel.  false = a NaN among them (partial_cmp().unwrap() panics in the reference).
+// The values arrive by vector loads from an address that is the same in every lane: DS / 4 requests that land in the
+// registers they stay in.  (Read through the wave-uniform pointer they were scalar loads: 100 values do not fit the
+// scalar file, the compiler parked 62 of them in the lanes of a vector register and moved every one of them across.)
+// The NaN scan is one more request, a 16-byte piece per lane.  A query need only be aligned as its floats are.
+typedef float QueryPiece __attribute__((ext_vector_type(4), aligned(4)));
 template <int DS>
 __device__ __forceinline__ bool load_query_f32(const float *qp, float (&qv)[DS], int lane) {
+    static_assert(DS % 4 == 0 && DS / 4 <= 64, "one 16-byte piece per lane in the NaN scan");
+    // (global address space by name: behind the asm statement the compiler cannot infer it and would load flat)
+    typedef const __attribute__((address_space(1))) QueryPiece *GlobalPieces;
+    GlobalPieces src = (GlobalPieces) reinterpret_cast<const QueryPiece *>(qp);
+    // no exec mask around the scan's request (the compiler waits for a masked load inside its mask, in front of
+    // everything else): the lanes behind the last piece look at the last piece again
+    const QueryPiece mine = src[min(lane, DS / 4 - 1)];
+    asm volatile("" : "+v"(src));  // (the compiler no longer knows the address to be uniform)
 #pragma unroll
-    for (int e = 0; e < DS; e++) qv[e] = qp[e];
-    bool bad = false;
-    for (int e = lane; e < DS; e += 64) {
-        const float x = qp[e];
-        bad |= (x != x);
+    for (int p = 0; p < DS / 4; p++) {
+        const QueryPiece t = src[p];
+#pragma unroll
+        for (int j = 0; j < 4; j++) qv[4 * p + j] = t[j];
     }
+    const bool bad = (mine[0] != mine[0]) | (mine[1] != mine[1]) | (mine[2] != mine[2]) | (mine[3] != mine[3]);
     const bool ok = __ballot(bad) == 0;
 #pragma unroll
     for (int e = 0; e < DS; e++) asm volatile("" : "+v"(qv[e]));
@@ -864,6 +917,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     QueryRegs<DS> qreg;
     float(&qv)[DS] = qreg.v;
     if (!load_query_f32<DS>(a.Q + (size_t)q * DS, qv, lane)) status = HNSW_ERR_NAN_INPUT;
+    FSTAMP_SINCE_BEGIN(40);  // query staging alone
 
     // distance of one row per wanting lane (every lane calls it: the cooperative form needs the whole wave)
     auto dist_of = [&](uint32_t id, bool want) __attribute__((always_inline)) -> float {
@@ -896,6 +950,55 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 best = ((u64)bits << 32) | cur;
         }
     }
+    // The lanes with act == true of an upper-layer expansion through the visited filter and the distance; ubn is
+    // upper_base[id], the adjacency base of the node the walk may go to, in flight together with the vector row.
+    // WALK_AHEAD: look, then upper_base[id] and the row's pieces for every lane whose look does not say "present", then the
+    // claims while the loads are in flight, then the chain -- request, claims and chain under ONE exec mask, as on layer
+    // 0.  A lane that turns out not to be fresh (its id sat in a later bucket) evaluated a distance for nothing.
+    // Otherwise: the whole insert first, then the rows of the fresh lanes.
+    struct WalkLane {
+        bool fresh;  // the lane inserted its id: only these count and compete
+        uint32_t ubn;
+        float dist;
+    };
+    auto walk_eval = [&](uint32_t id, bool act) __attribute__((always_inline)) -> WalkLane {
+        WalkLane r = {false, HX_EMPTY_SLOT, 0.0f};
+        if constexpr (WALK_AHEAD) {
+            FSTAMP(w0);
+            const uint32_t vb = vis.home(id);
+            const uint32_t vt0 = vis.look(id, vb);
+            const uint32_t vt = act ? vt0 : 4u;
+            FSTAMP(w1);
+            FSTAMP_ADD(43, w0, w1);
+            if (vt != 4u) {
+                r.ubn = a.upper_base[id];
+                const uint4 *src = reinterpret_cast<const uint4 *>(a.rows + (size_t)id * DS);
+                uint4 w[DS / 4];
+#pragma unroll
+                for (int p = 0; p < DS / 4; p++) w[p] = src[p];
+                __builtin_amdgcn_sched_barrier(0);
+                const uint32_t old = vis.claim(id, vb, vt);
+                r.fresh = old == HX_EMPTY_SLOT;
+                const bool pend = !r.fresh;
+                if (HX_UNLIKELY(__ballot(pend) != 0)) r.fresh = vis.finish(id, vb, vt, pend, r.fresh);
+                __builtin_amdgcn_sched_barrier(0);
+                FSTAMP_LDS(g0);
+                FSTAMP(g1);
+                FSTAMP_ADD(43, w1, g0);
+                FSTAMP_ADD(44, g0, g1);
+                r.dist = __builtin_sqrtf(chain_sum<DS>(w, qv));
+                FSTAMP(g2);
+                FSTAMP_ADD(45, g1, g2);
+            }
+        } else {
+            r.fresh = vis.insert(id, act);
+            if (HX_LIKELY(__ballot(r.fresh) != 0)) {
+                if (r.fresh) r.ubn = a.upper_base[id];
+                r.dist = dist_of(id, r.fresh);
+            }
+        }
+        return r;
+    };
 
 #ifdef HX_STAMPS
     dbg_acc[25] = __builtin_readcyclecounter() - t_begin;  // query staging + entry point alone (slot 7 minus this: the walk)
@@ -912,12 +1015,15 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     // neighbours' vector rows -- and lost each time ("The front of the query").
     const uint32_t up_slots = max(hslots >> 2, 64u);
     for (int layer = (int)a.nb_layers - 1; layer >= 1 && status == HNSW_OK; layer--) {
+        FSTAMP(l0);
         vis.bshift = 32 - (__ffs((int)up_slots) - 1 - 2);
         vis.bmask = (up_slots >> 2) - 1;
         const uint32_t vis_limit = up_slots - (up_slots >> 2);
         vis.clear(up_slots, lane);
         vis.insert(cur, lane == 0);
         n_vis = 1;
+        FSTAMP(l1);
+        FSTAMP_ADD(41, l0, l1);
         if (!have_ub) {
             ub_cur = uni(a.upper_base[cur]);
             have_ub = true;
@@ -928,6 +1034,10 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 break;
             }
             n_exp++;
+            FSTAMP_LDS(x0);
+            FSTAMP(x1);
+            FSTAMP_ADD(42, x0, x1);  // what is left of the wait for row_now
+            FSTAMP_ADD(48, 0, 1);    // upper-layer expansions
             bool improved = false;
             uint32_t new_cur = cur, new_ub = ub_cur;
             uint32_t ovf_lo = 0, ovf_hi = 0;
@@ -961,40 +1071,25 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                         status = HNSW_ERR_OVERFLOW;
                         break;
                     }
-                    const bool fresh = vis.insert(nb, valid);
+                    const WalkLane wl = walk_eval(nb, valid);
+                    const bool fresh = wl.fresh;
+                    const float dist = wl.dist;
                     const u64 fm = __ballot(fresh);
                     const uint32_t nf = (uint32_t)__popcll(fm);
                     n_vis += nf;
                     n_dist += nf;
                     if (HX_LIKELY(fm != 0)) {
-                        uint32_t ubn = HX_EMPTY_SLOT;
-                        if (fresh) ubn = a.upper_base[nb];  // in flight together with the vector row
-                        const float dist = dist_of(nb, fresh);
                         const bool nan = fresh && dist != dist;
                         if (HX_UNLIKELY(__ballot(nan) != 0)) {
                             status = HNSW_ERR_NAN_INPUT;  // Dist::cmp would panic (dist.rs:32)
                             break;
                         }
-                        const uint32_t db = fresh ? __builtin_bit_cast(uint32_t, dist) : 0xFFFFFFFFu;
-                        const uint32_t mn = wave_min_u32(db);
-                        u64 tie = __ballot(fresh && db == mn);
-                        uint32_t j = (uint32_t)__ffsll((long long)tie) - 1;
-                        uint32_t bid = rdlane(nb, j);
-                        tie &= tie - 1;
-                        while (tie) {  // equal distances: the smaller id wins (dist.rs:30-38)
-                            const uint32_t j2 = (uint32_t)__ffsll((long long)tie) - 1;
-                            tie &= tie - 1;
-                            const uint32_t id2 = rdlane(nb, j2);
-                            if (id2 < bid) {
-                                bid = id2;
-                                j = j2;
-                            }
-                        }
-                        const u64 k = ((u64)mn << 32) | bid;
+                        uint32_t j;
+                        const u64 k = walk_winner(nb, fresh, dist, j);
                         if (k < best) {
                             best = k;
-                            new_cur = bid;
-                            new_ub = rdlane(ubn, j);
+                            new_cur = (uint32_t)k;
+                            new_ub = rdlane(wl.ubn, j);
                             improved = true;
                         }
                     }
@@ -1017,7 +1112,10 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     LT lst;
     lst.init();
     if (status == HNSW_OK) {
+        FSTAMP(t0);
         const TableLimits lim = layer0_table<SPILLV>(a, vis, hslots, cur, lane);
+        FSTAMP(t1);
+        FSTAMP_ADD(47, t0, t1);
         const uint32_t lds_limit = lim.lds, vis_limit = lim.all;
         n_vis = 1;  // the entry point: what layer0_table put into the emptied table
         lst.set_first(best, lane);

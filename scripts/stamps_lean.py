@@ -1,5 +1,7 @@
 """Diagnostic: per-phase cycle shares of the lean f32 kernel (stamps build).
-   HNSW_MI355X_LIB=hnsw_rs_amd/libhnsw_mi355x_stamps.so python scripts/stamps_lean.py [N] [ef ...]"""
+   HNSW_MI355X_LIB=hnsw_rs_amd/libhnsw_mi355x_stamps.so python scripts/stamps_lean.py [N] [ef ...]
+   HX_STAMPS_FRONT=1 with a library built by `make stamps EXTRA=-DHX_STAMPS_FRONT`: the front of the query split further
+   (50 values per query instead of 40; those stamps lengthen slot 7, so the figures of the two builds do not compare)."""
 import os, sys
 sys.path.insert(0, '.')
 import numpy as np
@@ -18,7 +20,8 @@ dev = torch.device('cuda:0')
 dQ = torch.from_numpy(qs).to(dev)
 ids = torch.empty((nq, n), dtype=torch.int32, device=dev); dd = torch.empty((nq, n), dtype=torch.float32, device=dev)
 cnt = torch.empty(nq, dtype=torch.int32, device=dev); st = torch.empty((nq, 4), dtype=torch.int32, device=dev)
-SLOTS = 40  # HX_LEAN_DBG_SLOTS (search_lean.hip)
+FRONT = os.environ.get('HX_STAMPS_FRONT') == '1'
+SLOTS = 50 if FRONT else 40  # HX_LEAN_DBG_SLOTS (search_lean.hip)
 dbg = torch.zeros((nq, SLOTS), dtype=torch.int64, device=dev)
 os.environ['HX_DBG_PTR'] = str(dbg.data_ptr())
 names = {0: 'pick c,p + adjacency row round trip', 1: 'visited: insert c, look up p', 2: 'row gather until landed',
@@ -43,6 +46,16 @@ for ef in efs:
         print('   %-45s %9.0f cycles/query %5.1f%%   per pass %7.0f' % (names[i], D[:, i].mean(), 100 * D[:, i].mean() / tot.mean(), D[:, i].mean() / passes.mean()))
     print('   of slot 7: staging + entry point %.0f cycles/query (the entry point\'s distance is waited for at its end), the walk %.0f' % (
         D[:, 25].mean(), (D[:, 7] - D[:, 25]).mean()))
+    # the front's own split (slots 40 .. 48; its stamps lengthen slot 7): staging alone, the per-layer clear, and per
+    # upper-layer expansion the wait for the row it expands, the filter (look, claims), what is left of the row round
+    # trip once the filter is done, and the chain; the rest of the walk is the winner, the next row's request, the branches
+    if FRONT:
+        nx = max(1.0, D[:, 48].mean())
+        walk = (D[:, 7] - D[:, 25]).mean()
+        parts = D[:, 41].mean() + D[:, 42].mean() + D[:, 43].mean() + D[:, 44].mean() + D[:, 45].mean()
+        print('   front: staging %.0f, entry point %.0f, per-layer clear %.0f cycles/query; %.1f upper expansions, per expansion: wait for the row %.0f, look + claims %.0f, row round trip left %.0f, chain %.0f, winner + next request + rest %.0f; layer-0 table set-up %.0f cycles/query' % (
+            D[:, 40].mean(), (D[:, 25] - D[:, 40]).mean(), D[:, 41].mean(), D[:, 48].mean(), D[:, 42].mean() / nx, D[:, 43].mean() / nx,
+            D[:, 44].mean() / nx, D[:, 45].mean() / nx, (walk - parts) / nx, D[:, 47].mean()))
     acc = D[:, [0, 1, 2, 3, 5, 7, 8, 9, 10]].sum(1).mean()
     print('   unaccounted %.1f%%' % (100 * (tot.mean() - acc) / tot.mean()))
     print('   per query: visited slow-loop rounds %.1f; merges with 0 / 1-2 / >=3 survivors: %.1f / %.1f / %.1f; p commits %.1f' % (
