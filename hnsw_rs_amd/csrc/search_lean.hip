@@ -97,7 +97,7 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 #ifdef HX_STAMPS_FRONT
 // (make stamps EXTRA=-DHX_STAMPS_FRONT) the front of the query split further, slots 40 .. 48: its stamps lengthen slot 7
 // by a fifth, so the plain stamps build, whose slot 7 the recorded profiles compare, does without them
-constexpr int HX_LEAN_DBG_SLOTS = 50;
+constexpr int HX_LEAN_DBG_SLOTS = 53;
 #define FSTAMP(var) STAMP(var)
 #define FSTAMP_ADD(slot, a, b) STAMP_ADD(slot, a, b)
 // the clock once the LDS requests are back, whatever is still in flight from memory (stamp_now would wait for it)
@@ -107,7 +107,7 @@ constexpr int HX_LEAN_DBG_SLOTS = 50;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define FSTAMP_SINCE_BEGIN(slot) dbg_acc[slot] = __builtin_readcyclecounter() - t_begin
 #else
-constexpr int HX_LEAN_DBG_SLOTS = 40;  // values per query in the side buffer (scripts/stamps_lean.py allocates it)
+constexpr int HX_LEAN_DBG_SLOTS = 43;  // values per query in the side buffer (scripts/stamps_lean.py allocates it)
 #endif
 // A merge's own split: five values from `dbg` on (the f32 kernel passes dbg_acc + 26 for c's merge, + 31 for p's; a
 // caller without a side buffer passes nothing and its merges carry no stamp) -- cycles of the survivor loop, of the
@@ -127,6 +127,11 @@ constexpr int HX_LEAN_DBG_SLOTS = 40;  // values per query in the side buffer (s
 #define MERGE_DBG_ARG(first)
 #define MERGE_STAMP(var)
 #define MERGE_ADD(off, v)
+#endif
+#ifdef HX_STAMPS
+// the last three values are the frontier's: its cycles (inside slot 0, which its own stamp lengthens), its runs and the
+// runs after c's merge (a survivor went in front of b)
+constexpr int HX_DBG_FRONTIER = HX_LEAN_DBG_SLOTS - 3;
 #endif
 #if !defined(HX_STAMPS) || !defined(HX_STAMPS_FRONT)
 #define FSTAMP(var)
@@ -313,6 +318,37 @@ __device__ __forceinline__ void stage_survivors(u64 key, bool surv, u64 smask, u
     if (surv && rk + 1 == m) perm[m] = LK_INVALID;
     asm volatile("" ::: "memory");  // LDS serves a wave's requests in order: written before they are read
 }
+// ---- the frontier: the keys of the first four unexpanded entries (c, p, a, b), LK_INVALID where the list has fewer,
+// the same four values in every lane's vector registers.  No position is formed and nothing is handed to the scalar
+// unit: an entry's rank among the unexpanded ones is the mbcnt of the ballot below its lane, ranks 0 .. 3 write their
+// key at their rank into the front of perm (dead outside a merge, as the big merge's staging uses it) and two
+// wave-uniform 16-byte reads broadcast the four keys.  The four places are preset by ONE pad write of the whole wave
+// (perm[lane] = LK_INVALID: no exec mask to form; cheaper than a write of four lanes), and a lane that has nothing to
+// publish writes its entry to perm[64 + lane], which nobody reads, instead of being masked off: the address is a select,
+// not a compare -> exec hand-off.  (LDS serves a wave's requests in order.) ----
+__device__ __forceinline__ bool lk_unexp(u64 k) { return (int32_t)(uint32_t)(k >> 32) >= 0; }  // (LK_INVALID: flag set)
+__device__ __forceinline__ uint32_t lanes_below(u64 mask, uint32_t base) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, base));
+}
+// popcount of a wave-uniform mask on the vector unit (the compiler's own is s_bcnt1: a hand-off behind the ballot)
+__device__ __forceinline__ uint32_t vpopc64(u64 mask) {
+    uint32_t r;
+    asm("v_bcnt_u32_b32 %0, %1, 0\n\tv_bcnt_u32_b32 %0, %2, %0" : "=&v"(r) : "s"((uint32_t)mask), "s"((uint32_t)(mask >> 32)));
+    return r;
+}
+__device__ __forceinline__ void frontier_publish(u64 e, bool unexp, uint32_t rank, u64 *perm, int lane) {
+    perm[(unexp && rank < 4u) ? rank : 64u + (uint32_t)lane] = e;
+}
+__device__ __forceinline__ void frontier_read(u64 (&F)[4], const u64 *perm) {
+    asm volatile("" ::: "memory");
+    const ulonglong2 *f = reinterpret_cast<const ulonglong2 *>(perm);
+    const ulonglong2 x = f[0], y = f[1];
+    F[0] = x.x;
+    F[1] = x.y;
+    F[2] = y.x;
+    F[3] = y.y;
+}
+
 template <int R>
 struct Lst {
     static constexpr int NR = R;  // list registers per lane
@@ -387,6 +423,20 @@ struct Lst {
 #pragma unroll
         for (int r = 0; r < R; r++)
             if ((pos % R) == (uint32_t)r && (uint32_t)lane == pos / R) L[r] |= LK_EXPANDED;
+    }
+    // the first four unexpanded keys (see frontier_publish); one register: entry i is lane i
+    __device__ __forceinline__ void frontier(u64 (&F)[4], u64 *perm, int lane) const {
+        static_assert(R == 1, "the interleaved lists pick by unexp_masks / take_first");
+        perm[lane] = LK_INVALID;
+        asm volatile("" ::: "memory");
+        const bool u = lk_unexp(L[0]);
+        frontier_publish(L[0], u, lanes_below(__ballot(u), 0u), perm, lane);
+        frontier_read(F, perm);
+    }
+    // mark the entry that holds key k (unexpanded, so no flag to drop; keys are unique)
+    __device__ __forceinline__ void mark_key(u64 k) {
+#pragma unroll
+        for (int r = 0; r < R; r++) L[r] |= L[r] == k ? LK_EXPANDED : 0ull;
     }
     __device__ __forceinline__ void refresh_last(uint32_t ef) {
         last_key = n_cur >= ef ? (key_at(ef - 1) & LK_MASK) : LK_INVALID;
@@ -581,6 +631,21 @@ struct LstHT {
     __device__ __forceinline__ void mark(uint32_t pos, int lane) {
         if ((uint32_t)lane == pos) L[0] |= LK_EXPANDED;
         if ((uint32_t)lane + 64u == pos) L[1] |= LK_EXPANDED;
+    }
+    // the first four unexpanded keys (see frontier_publish): the tail's ranks start at the head's count, head and tail
+    // run the same instructions and nothing branches on where the entries are
+    __device__ __forceinline__ void frontier(u64 (&F)[4], u64 *perm, int lane) const {
+        perm[lane] = LK_INVALID;
+        asm volatile("" ::: "memory");
+        const bool u0 = lk_unexp(L[0]), u1 = lk_unexp(L[1]);
+        const u64 B0 = __ballot(u0), B1 = __ballot(u1);
+        frontier_publish(L[0], u0, lanes_below(B0, 0u), perm, lane);
+        frontier_publish(L[1], u1, lanes_below(B1, vpopc64(B0)), perm, lane);
+        frontier_read(F, perm);
+    }
+    __device__ __forceinline__ void mark_key(u64 k) {
+        L[0] |= L[0] == k ? LK_EXPANDED : 0ull;
+        L[1] |= L[1] == k ? LK_EXPANDED : 0ull;
     }
     __device__ __forceinline__ void refresh_last(uint32_t ef) {
         // ef > 64: entry ef - 1 lives in the tail
@@ -867,6 +932,11 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     // register line and the wide lists hold the second level's state: both keep the walk that loads a row when it
     // expands it.
     constexpr bool WALK_AHEAD = !COOP && R <= 2;
+    // the same kernels find a pass's candidates once, in the vector domain: the list's frontier (c, p and the two
+    // entries behind them) gives the pick, the runner-up and -- while c's merge puts nothing in front of them -- the
+    // pair whose rows are requested for the next pass (layer 0, below).  The others pick by ballots and positions.
+    constexpr bool FRONTIER = WALK_AHEAD;
+    static_assert(!FRONTIER || MISS_AHEAD, "the frontier's commit test is the foreseen miss's ballot");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
     const uint32_t q = a.qsel ? a.qsel[blockIdx.x] : blockIdx.x;
@@ -1144,9 +1214,10 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 // the LDS table has reached its limit (it may hold 64 more: one pass): closed from this pass on
                 if (HX_UNLIKELY(!vis.spill && vis.gtab != nullptr && n_vis + 64u > lds_limit)) vis.open_second_level(lane);
             }
-            int ppos = -1;
+            bool has_p = false;  // wave-uniform: the pass has a runner-up
             uint32_t pid = HX_EMPTY_SLOT;
             u64 pkey = 0;  // p's key (MISS_AHEAD); 0 = no runner-up: no key is below it
+            u64 akey = LK_INVALID, bkey = LK_INVALID;  // FRONTIER: the two unexpanded entries behind p
             bool kept = false;  // p's lanes hold p's row and its distances from the pass before (MISS_KEEP)
             uint32_t nb = HX_EMPTY_SLOT;
             const bool ovf_pass = ovf_lo < ovf_hi;
@@ -1155,13 +1226,53 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 // a runner-up (one body for both keeps a single set of row registers in the loop) ----
                 if (lane < 32 && ovf_lo + (uint32_t)lane < ovf_hi) nb = a.ovf_nbrs[ovf_lo + (uint32_t)lane];
                 ovf_lo += 32;
+            } else if constexpr (FRONTIER) {
+                // ---- c and p are the frontier's first two keys; ids and keys stay vector values (the adjacency
+                // address selects per lane anyway), c is marked by its key ----
+                u64 F[4];
+                STAMP(fr0);
+                lst.frontier(F, perm, lane);
+#ifdef HX_STAMPS
+                asm volatile("" ::"v"(F[0]), "v"(F[1]), "v"(F[2]), "v"(F[3]) : "memory");
+                dbg_acc[HX_DBG_FRONTIER] += stamp_now() - fr0;
+                dbg_acc[HX_DBG_FRONTIER + 1]++;
+#endif
+                // candidates exhausted / only worse ones left (searcher.rs:35,41-44)
+                if (HX_UNLIKELY(__ballot(lk_unexp(F[0])) == 0)) break;
+                has_p = __ballot(lk_unexp(F[1])) != 0;
+                const uint32_t cid = (uint32_t)F[0];
+                pkey = F[1];  // (LK_INVALID without a runner-up: what it is compared for is used under spec_ok alone)
+                pid = (uint32_t)F[1];  // (HX_EMPTY_SLOT without one)
+                akey = F[2];
+                bkey = F[3];
+                lst.mark_key(F[0]);
+                n_exp++;
+#ifdef HX_STAMPS
+                if (dbg_follow) {
+                    if (cid == dbg_pred_c && pid == dbg_pred_p) dbg_acc[19]++;
+                    if (pid == dbg_old_p) dbg_acc[20]++;
+                    dbg_follow = false;
+                }
+                dbg_took_pre = pre_c == cid && pre_p == pid;
+#endif
+                // the rows requested during the previous pass are this pair's: one compare, one branch
+                if (HX_LIKELY(__ballot(pre_c == cid && pre_p == pid) != 0)) {
+                    nb = pre_nb;
+                    if constexpr (MISS_KEEP) kept = carry;
+                } else {
+                    if (slot < S0 && (!upper || lk_unexp(F[1]))) nb = a.adj0[(size_t)(upper ? pid : cid) * S0 + slot];
+                }
+                pre_c = HX_EMPTY_SLOT;
+                carry = false;
             } else {
+                int ppos;
                 // ---- pick c (the smallest unexpanded entry) and the runner-up p: one set of ballots ----
                 typename LT::Masks U;
                 lst.unexp_masks(U);
                 const int cpos = lst.take_first(U);
                 if (HX_UNLIKELY(cpos < 0)) break;  // candidates exhausted / only worse ones left (searcher.rs:35,41-44)
                 ppos = lst.take_first(U);
+                has_p = ppos >= 0;
                 const uint32_t cid = lst.id_at((uint32_t)cpos);
                 if constexpr (MISS_AHEAD) {
                     if (ppos >= 0) {
@@ -1205,7 +1316,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             // ---- classify the slots.  A row with an overflow pointer (degree > S0) is rare: c's is
             // finished after the merge, a runner-up with one is not speculated on ----
             const u64 pm = ovf_pass ? 0ull : __ballot((int32_t)nb < -1);  // 0x80000000 | overflow row
-            const bool spec_ok = ppos >= 0 && (pm >> 32) == 0;
+            const bool spec_ok = has_p && (pm >> 32) == 0;
             const bool valid = (int32_t)nb >= 0 && (!upper || spec_ok);
             // ---- visited: every lane looks at its home bucket; c's lanes claim a slot, p's lanes only
             // look (p's real insert happens at its commit, after everything c inserted; a stale "absent"
@@ -1313,6 +1424,14 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 status = HNSW_ERR_NAN_INPUT;  // Dist::cmp would panic (dist.rs:32)
                 break;
             }
+            u64 bm = 0;  // c's fresh keys below p's key (MISS_AHEAD)
+            u64 am = 0;  // FRONTIER: c's survivors that sort in front of b
+            if constexpr (FRONTIER) {
+                // The two entries behind p stay the frontier's a and b through c's merge unless a survivor -- a fresh
+                // key below the bound as it stands before the merge -- sorts in front of b.  Without a b (LK_INVALID)
+                // any survivor counts: it may be the new a or b.  Known before the merge, asked for after it.
+                am = __ballot(!upper && key < min(bkey, lst.last_key));
+            }
             if constexpr (MISS_AHEAD) {
                 // ---- a miss foreseen.  A fresh key of c below p's key enters the list (p's key is at most the list's
                 // last) in front of p, the smallest unexpanded entry left: the next pick is the smallest such key and,
@@ -1321,7 +1440,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 // Their adjacency rows are requested now and land while c is merged; the next pick validates the pair
                 // as it does the commit path's and drops a wrong guess, so no result depends on this.  Not on an
                 // overflow pass (pkey is 0 there), not when either row carries an overflow pointer. ----
-                const u64 bm = __ballot(!upper && key < pkey);  // (LK_INVALID is below nothing)
+                bm = __ballot(!upper && key < pkey);  // (LK_INVALID is below nothing)
                 if (HX_UNLIKELY(bm != 0) && spec_ok && pm == 0) {
                     u64 k1 = rdlane64(key, (uint32_t)__ffsll((long long)bm) - 1), k2 = LK_INVALID;
                     u64 rest = bm & (bm - 1);
@@ -1371,27 +1490,56 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             }
             // ---- is p the next candidate?  then commit it from the registers ----
             if (HX_UNLIKELY(!spec_ok)) continue;
-            typename LT::Masks V;
-            lst.unexp_masks(V);
-            const int npos = lst.take_first(V);
-            if (HX_UNLIKELY(npos < 0)) break;
-            if (HX_UNLIKELY(lst.id_at((uint32_t)npos) != pid)) continue;
-            // The pass after this one will most likely expand the two entries that follow p (measured:
-            // three times out of four when p is committed).  Their adjacency rows are requested now and
-            // land while p is being committed; if the next pick is a different pair they are dropped.
-            {
-                const int apos = lst.take_first(V);
-                if (HX_LIKELY(apos >= 0)) {
-                    const int bpos = lst.take_first(V);
-                    pre_c = lst.id_at((uint32_t)apos);
-                    pre_p = bpos >= 0 ? lst.id_at((uint32_t)bpos) : HX_EMPTY_SLOT;
-                    pre_nb = HX_EMPTY_SLOT;
-                    if (slot < S0 && (!upper || bpos >= 0)) pre_nb = a.adj0[(size_t)(upper ? pre_p : pre_c) * S0 + slot];
+            int npos = -1;
+            if constexpr (FRONTIER) {
+                // p was the first unexpanded entry behind c, c is marked and every older entry in front of p is
+                // expanded: p is next exactly when no fresh key of c sorts below it -- the foreseen miss's ballot,
+                // nothing new (such a key is below the bound, so it went in; with none, p kept its place and cannot
+                // have left the list).  A pass whose c carried an overflow pointer picks again instead.
+                if (HX_UNLIKELY((bm | pm) != 0)) continue;
+                // The pass after this one will most likely expand the two entries that follow p (measured: three
+                // times out of four when p is committed).  Their adjacency rows are requested now and land while p
+                // is being committed; if the next pick is a different pair they are dropped.  The pair is the
+                // frontier's a and b unless a survivor of c went in front of b: then the frontier of the merged
+                // list, whose first entry is p.
+                if (HX_UNLIKELY(am != 0)) {
+                    u64 G[4];
+                    lst.frontier(G, perm, lane);
+                    akey = G[1];
+                    bkey = G[2];
+#ifdef HX_STAMPS
+                    dbg_acc[HX_DBG_FRONTIER + 1]++;
+                    dbg_acc[HX_DBG_FRONTIER + 2]++;
+#endif
+                }
+                pre_c = (uint32_t)akey;  // (HX_EMPTY_SLOT where there is none: matches no candidate)
+                pre_p = (uint32_t)bkey;
+                pre_nb = HX_EMPTY_SLOT;
+                if (slot < S0 && lk_unexp(upper ? bkey : akey)) pre_nb = a.adj0[(size_t)(upper ? pre_p : pre_c) * S0 + slot];
+            } else {
+                typename LT::Masks V;
+                lst.unexp_masks(V);
+                npos = lst.take_first(V);
+                if (HX_UNLIKELY(npos < 0)) break;
+                if (HX_UNLIKELY(lst.id_at((uint32_t)npos) != pid)) continue;
+                // (the two entries that follow p: see above)
+                {
+                    const int apos = lst.take_first(V);
+                    if (HX_LIKELY(apos >= 0)) {
+                        const int bpos = lst.take_first(V);
+                        pre_c = lst.id_at((uint32_t)apos);
+                        pre_p = bpos >= 0 ? lst.id_at((uint32_t)bpos) : HX_EMPTY_SLOT;
+                        pre_nb = HX_EMPTY_SLOT;
+                        if (slot < S0 && (!upper || bpos >= 0)) pre_nb = a.adj0[(size_t)(upper ? pre_p : pre_c) * S0 + slot];
+                    }
                 }
             }
             STAMP(f4);
             STAMP_ADD(9, f3b, f4);
-            lst.mark((uint32_t)npos, lane);
+            if constexpr (FRONTIER)
+                lst.mark_key(pkey);
+            else
+                lst.mark((uint32_t)npos, lane);
             n_exp++;
             // Every valid neighbour of p goes through the filter now.  The bucket state seen while
             // speculating is still good for a direct claim: slots fill left to right, so if slot vt is

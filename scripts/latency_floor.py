@@ -36,7 +36,7 @@ for nq in (64, 1024):
     dd = torch.empty((nq, n), dtype=torch.float32, device=dev)
     cnt = torch.empty(nq, dtype=torch.int32, device=dev)
     st = torch.empty((nq, 4), dtype=torch.int32, device=dev)
-    dbg = torch.zeros((nq, 40), dtype=torch.int64, device=dev)  # HX_LEAN_DBG_SLOTS values per query
+    dbg = torch.zeros((nq, 43), dtype=torch.int64, device=dev)  # HX_LEAN_DBG_SLOTS values per query
     os.environ["HX_DBG_PTR"] = str(dbg.data_ptr())
     for _ in range(3):
         idx.search_batch_device(dQ.data_ptr(), nq, n, ef, ids.data_ptr(), dd.data_ptr(), cnt.data_ptr(), st.data_ptr(), 0)

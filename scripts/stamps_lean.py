@@ -21,7 +21,7 @@ dQ = torch.from_numpy(qs).to(dev)
 ids = torch.empty((nq, n), dtype=torch.int32, device=dev); dd = torch.empty((nq, n), dtype=torch.float32, device=dev)
 cnt = torch.empty(nq, dtype=torch.int32, device=dev); st = torch.empty((nq, 4), dtype=torch.int32, device=dev)
 FRONT = os.environ.get('HX_STAMPS_FRONT') == '1'
-SLOTS = 50 if FRONT else 40  # HX_LEAN_DBG_SLOTS (search_lean.hip)
+SLOTS = 53 if FRONT else 43  # HX_LEAN_DBG_SLOTS (search_lean.hip)
 dbg = torch.zeros((nq, SLOTS), dtype=torch.int64, device=dev)
 os.environ['HX_DBG_PTR'] = str(dbg.data_ptr())
 names = {0: 'pick c,p + adjacency row round trip', 1: 'visited: insert c, look up p', 2: 'row gather until landed',
@@ -83,6 +83,12 @@ for ef in efs:
     took = D[:, 22]
     print('   per query: misses %.1f, with 1 / 2 / >=3 fresh keys of c below p: %.1f / %.1f / %.1f; follow-up pick is the predicted pair %.2f; follow-up runner-up is the old p %.1f' % (
         miss.mean(), D[:, 16].mean(), D[:, 17].mean(), D[:, 18].mean(), D[:, 19].mean(), D[:, 20].mean()))
+    # the frontier (the last three values: its cycles -- inside slot 0, which its own stamp lengthens --, its runs, and the
+    # runs after c's merge: a survivor went in front of b, so the pair requested ahead is not the frontier's a and b)
+    fr = D[:, SLOTS - 3:]
+    print('   frontier: %.2f runs per pass, %.0f cycles per run at the pick; %.1f p commits per query, %.1f of them (%.1f%%) took the pair from the pick\'s frontier, %.1f ran it again' % (
+        fr[:, 1].sum() / max(1, passes.sum()), fr[:, 0].sum() / max(1, (fr[:, 1] - fr[:, 2]).sum()), D[:, 15].mean(),
+        (D[:, 15] - fr[:, 2]).mean(), 100 * (D[:, 15] - fr[:, 2]).sum() / max(1, D[:, 15].sum()), fr[:, 2].mean()))
     print('   pick + adjacency (slot 0) per pass: %.0f cycles on the %.1f passes whose rows were fetched ahead, %.0f on the %.1f others' % (
         D[:, 21].sum() / max(1, took.sum()), took.mean(), (D[:, 0] - D[:, 21]).sum() / max(1, (passes - took).sum()), (passes - took).mean()))
     print('   look + request + claims + chain (slot 1) per pass: %.0f cycles on the %.1f passes whose runner-up kept its distances, %.0f on the %.1f others' % (

@@ -19,7 +19,7 @@ dev = torch.device('cuda:0')
 dQ = torch.from_numpy(qs).to(dev)
 ids = torch.empty((nq, n), dtype=torch.int32, device=dev); dd = torch.empty((nq, n), dtype=torch.float32, device=dev)
 cnt = torch.empty(nq, dtype=torch.int32, device=dev); st = torch.empty((nq, 4), dtype=torch.int32, device=dev)
-dbg = torch.zeros((nq, 40), dtype=torch.int64, device=dev)  # HX_LEAN_DBG_SLOTS values per query
+dbg = torch.zeros((nq, 43), dtype=torch.int64, device=dev)  # HX_LEAN_DBG_SLOTS values per query
 os.environ['HX_DBG_PTR'] = str(dbg.data_ptr())
 names = {7: 'staging + entry + upper layers', 0: 'pick + adjacency row (prefetch waited for here)', 1: 'visited look + claim + counts',
          3: 'rows + chain + key', 8: 'merge', 4: 'TOTAL (whole query)'}
