@@ -33,13 +33,6 @@
 #else
 #define HX_PAIR_EXIT(code) HNSW_ERR_OVERFLOW
 #endif
-#ifdef HX_STAMPS
-#define PP_NOW() __builtin_readcyclecounter()
-#define PP_ADD(slot, t0) pp[slot] += __builtin_readcyclecounter() - (t0)
-#else
-#define PP_NOW() 0ull
-#define PP_ADD(slot, t0)
-#endif
 struct PairBox {
     u64 keys[64];       // walker -> keeper: this pass's keys (LK_INVALID = none); lanes 0..31 c's, 32..63 p's
     // keeper -> walker: the list's smallest unexpanded entries before pass f_seq - 1 (0 of them: the search is over)
@@ -94,9 +87,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
         LT lst;
         lst.init();
         int32_t status = HNSW_OK;
-#ifdef HX_STAMPS
-        unsigned long long pp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+        PP_STATE();
         bool is_p[2] = {false, false};  // this lane's entry (of register r) is the pass's runner-up
         for (uint32_t k = 0;; k++) {  // message k: 0 = the entry point's key, k >= 1 = the keys of pass k - 1
             [[maybe_unused]] const unsigned long long w0 = PP_NOW();
@@ -120,7 +111,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
                 box_store(&box->abort, 1u);
                 break;
             }
-            PP_ADD(0, w0);  // keeper: waiting for keys
+            PP_ADD(PAIR_K_WAIT_KEYS, w0);
             [[maybe_unused]] const unsigned long long m0 = PP_NOW();
             flags = uni(flags);
             [[maybe_unused]] const bool upper = lane >= 32;
@@ -138,7 +129,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
                 }
                 lst.merge((upper && !(flags & 1u)) ? LK_INVALID : key, ef, perm, lane);
             }
-            PP_ADD(1, m0);  // keeper: merges
+            PP_ADD(PAIR_K_MERGES, m0);
             [[maybe_unused]] const unsigned long long f0 = PP_NOW();
             // The list's four smallest unexpanded entries, written by the lanes that hold them (no read-lanes): the next
             // pass's c -- marked expanded here and now -- and p, and the two behind them.
@@ -165,7 +156,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
             if (lane == 0) box->f_n = nf;
             asm volatile("" ::: "memory");
             box_store(&box->f_seq, k + 1u);  // F of pass k
-            PP_ADD(2, f0);  // keeper: F
+            PP_ADD(PAIR_K_F, f0);
             if (nf == 0) break;  // candidates exhausted / only worse ones left (searcher.rs:35, 41-44)
         }
         // the walker's verdict, then get_top_selected(n) (results.rs:59-61)
@@ -181,10 +172,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
         if (status == HNSW_OK) status = bst;
         const uint32_t count = status == HNSW_OK ? min(a.n, lst.n_cur) : 0;
         write_results(a, q, lst, count, lane);
-#ifdef HX_STAMPS
-        if (lane == 0 && a.dbg)
-            for (int i = 0; i < 3; i++) a.dbg[(size_t)q * 16 + 8 + i] = pp[i];
-#endif
+        PP_WRITE_KEEPER();
         return;
     }
 
@@ -194,10 +182,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
     vis.tab = reinterpret_cast<uint32_t *>(smem);
     uint32_t n_dist = 0, n_exp = 0, sum_deg = 0, n_vis = 0;
     int32_t status = HNSW_OK;
-#ifdef HX_STAMPS
-    unsigned long long pp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long t_begin = __builtin_readcyclecounter();
-#endif
+    PP_STATE_WALKER();
 
     QueryRegs<DS> qreg;
     float(&qv)[DS] = qreg.v;
@@ -334,9 +319,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
         [[maybe_unused]] const unsigned long long t_l0 = PP_NOW();
         for (uint32_t k = 0;; k++) {
             [[maybe_unused]] const unsigned long long g0 = PP_NOW();
-#ifdef HX_STAMPS
-            pp[6]++;
-#endif
+            PP_COUNT(PAIR_W_PASSES);
             // ---- the gather for (cid, pid): nothing of it is counted before the keeper's F confirms the pair ----
             const bool have_p = pid != HX_EMPTY_SLOT;
             if (HX_UNLIKELY(__ballot((int32_t)nb < -1) != 0)) {  // degree > S0: the one-wave kernel
@@ -374,7 +357,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
             const uint32_t cnt_p = (uint32_t)__popcll(vmask >> 32);
             const uint32_t nf_c = (uint32_t)__popcll(fmask);
             n_vis += nf_c;  // (the table holds them whether or not the pass counts)
-            PP_ADD(0, g0);  // walker: gather (look .. chain)
+            PP_ADD(PAIR_W_GATHER, g0);  // (look .. chain)
             [[maybe_unused]] const unsigned long long w0 = PP_NOW();
 
             // ---- the keeper's view of the list before this pass: the word first, F behind it, one round trip ----
@@ -400,7 +383,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
                 status = HNSW_ERR_HIP;
                 break;
             }
-            PP_ADD(1, w0);  // walker: waiting for F
+            PP_ADD(PAIR_W_WAIT_F, w0);
             [[maybe_unused]] const unsigned long long c0 = PP_NOW();
             nF = uni(nF);
             if (nF == 0) break;  // the search is over; the gather above is dropped
@@ -428,9 +411,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
             // (A p lane whose home bucket was full cannot tell "absent" from "in a later bucket" before its claim: a pass
             // with such a lane decides after p's claims, on exact keys.)
             const bool late = p_commits && __ballot(upper && vt == 5u) != 0;
-#ifdef HX_STAMPS
-            pp[7] += __builtin_readcyclecounter() - c0;  // walker: check alone
-#endif
+            PP_ADD(PAIR_W_CHECK, c0);
             uint32_t ncid = HX_EMPTY_SLOT, npid = HX_EMPTY_SLOT, nnb = HX_EMPTY_SLOT;
             auto next_pair = [&](u64 pk) __attribute__((always_inline)) {
                 // The two smallest of the wave's keys by two wave-wide minima over the distance words (DPP; a loop over
@@ -487,7 +468,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
             const uint32_t pt = (upper && p_commits) ? vt : 4u;
             const uint32_t pold = vis.claim(nb, vb, pt);
             if (HX_LIKELY(!late)) next_pair(key);
-            PP_ADD(4, c0);  // walker: check + next pair
+            PP_ADD(PAIR_W_CHECK_NEXT, c0);
             [[maybe_unused]] const unsigned long long s0 = PP_NOW();
             bool pfresh = false;
             if (p_commits) {
@@ -509,7 +490,7 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
                 }
             }
             if (HX_UNLIKELY(late)) next_pair(upper ? (pfresh ? key : LK_INVALID) : key);
-            PP_ADD(2, s0);  // walker: claims of p
+            PP_ADD(PAIR_W_CLAIMS_P, s0);
             [[maybe_unused]] const unsigned long long n0 = PP_NOW();
             // ---- this pass's keys to the keeper (it took the previous ones out before it published this pass's F) ----
             box->keys[lane] = upper ? (pfresh ? key : LK_INVALID) : key;
@@ -517,21 +498,15 @@ __global__ void __launch_bounds__(128) hx_pair_f32_kernel(const LeanArgs a) {
             asm volatile("" ::: "memory");
             box_store(&box->k_seq, k + 2u);
             __builtin_amdgcn_sched_barrier(0);  // (the copy below waits for the rows just requested: after the send, not before)
-            PP_ADD(3, n0);  // walker: send
+            PP_ADD(PAIR_W_SEND, n0);
             cid = ncid;
             pid = npid;
             nb = nnb;
         }
-        PP_ADD(5, t_l0);  // walker: layer 0
+        PP_ADD(PAIR_W_LAYER0, t_l0);
     }
     if (status != HNSW_OK) box_store(&box->abort, 1u);
-#ifdef HX_STAMPS
-    if (lane == 0 && a.dbg) {
-        for (int i = 0; i < 7; i++) a.dbg[(size_t)q * 16 + i] = pp[i];
-        a.dbg[(size_t)q * 16 + 7] = __builtin_readcyclecounter() - t_begin;
-        a.dbg[(size_t)q * 16 + 11] = pp[7];
-    }
-#endif
+    PP_WRITE_WALKER();
     if (lane == 0) box->b_status = status;
     write_stats(a, q, n_dist, n_exp, sum_deg, status, lane);
     asm volatile("" ::: "memory");

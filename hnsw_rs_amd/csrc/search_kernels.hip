@@ -44,19 +44,10 @@
 #include "device_index.h"
 #include "launch.h"
 #include "search_common.h"
+#include "stamps.h"
 #include "switches.h"
 
 namespace hx {
-
-// Diagnostic build only (make stamps): per-phase cycle shares of the inline-rows expansion loop,
-// written to a side buffer nothing else reads.  The shipped library is built without HX_STAMPS.
-#ifdef HX_STAMPS
-#define STAMP(var) const unsigned long long var = __builtin_readcyclecounter()
-#define STAMP_ADD(slot, a, b) dbg_acc[slot] += (b) - (a)
-#else
-#define STAMP(var)
-#define STAMP_ADD(slot, a, b)
-#endif
 
 // bytes of the region the merge buffer shares with the cooperative gather's image (4 KiB + 64 rank words)
 template <int KIND, int DS, int R>
@@ -112,11 +103,7 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
     const float *qv = a.Q + (size_t)q * d;
     uint32_t n_dist = 0, n_exp = 0, sum_deg = 0;
     int32_t status = HNSW_OK;
-#ifdef HX_STAMPS
-    unsigned long long dbg_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long dbg_mid = 0;
-    const unsigned long long t_begin = __builtin_readcyclecounter();
-#endif
+    STAMP_STATE_GENERIC();
 
     // ---- stage the query (Point::new -> QuantVec::new for QUANT8, template.rs:313) ----
     const uint32_t nq_half = (KIND == HNSW_VEC_QUANT8) ? (v.half_bytes - 8) : 0;
@@ -190,10 +177,7 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
 #pragma unroll
                     for (int p = 0; p < P; p++) w[p] = src[p];
                     __builtin_amdgcn_sched_barrier(0);  // every piece requested before the chain starts
-#ifdef HX_STAMPS
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    dbg_mid = __builtin_readcyclecounter();
-#endif
+                    STAMP_ROWS_LANDED();
                     sm = f32_row_sum<(P > 0 ? P : 1), (DS > 0 ? DS : 1)>(w, yq);
                 }
             }
@@ -341,7 +325,7 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
             bool done = false;
             while (!done && status == HNSW_OK) {
             while (true) {
-                STAMP(t0);
+                STAMP_RAW(t0);
                 const int cpos = wl.first_unexpanded(lane);
                 if (cpos < 0) {
                     done = true;
@@ -356,10 +340,7 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
                     }
                 }
                 n_exp++;
-#ifdef HX_STAMPS
-                const bool dbg_hit = have_spec && spec_id == cid;
-                if (dbg_hit) dbg_acc[6]++;
-#endif
+                STAMP_NOTE_HIT(have_spec && spec_id == cid);
                 // Every block is staged through LDS by DMA (no compiler-visible VMEM load in this
                 // loop, so hipcc inserts no vmcnt wait that would also drain the prefetch): the
                 // current block is either the image prefetched one expansion ago or is fetched now;
@@ -401,8 +382,8 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
 #pragma unroll
                     for (int p = 0; p < PP; p++) w[p] = img[64 * p];
                 }
-                STAMP(t1);
-                STAMP_ADD(0, t0, t1);
+                STAMP_RAW(t1);
+                STAMP_ADD(FAT_PICK, t0, t1);
                 // the neighbour id travels in the last 4 bytes of half 0
                 const uint32_t raw = w[PP - 1].w;
                 const uint32_t nb = h ? (uint32_t)pair_swap_i((int)raw) : raw;
@@ -423,13 +404,8 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
                     const bool fresh = (pair_swap_i(f ? 1 : 0) | (f ? 1 : 0)) != 0;
                     const u64 fm = __ballot(fresh && h == 0);
                     n_vis += (uint32_t)__popcll(fm);  // what the table really holds
-                    STAMP(t2);
-#ifdef HX_STAMPS
-                    if (dbg_hit)
-                        dbg_acc[1] += t2 - t1;
-                    else
-                        dbg_acc[5] += t2 - t1;
-#endif
+                    STAMP_RAW(t2);
+                    STAMP_ADD_BY_HIT(FAT_FILTER_HIT, FAT_FILTER_MISS, t1, t2);
                     if (fm != 0) {
                         n_dist += (uint32_t)__popcll(fm);
                         float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -461,11 +437,11 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
                             status = HNSW_ERR_NAN_INPUT;
                             break;
                         }
-                        STAMP(t3);
-                        STAMP_ADD(2, t2, t3);
+                        STAMP_RAW(t3);
+                        STAMP_ADD(FAT_CHAIN, t2, t3);
                         wl.merge(key, ef_l, perm, lane);
-                        STAMP(t4);
-                        STAMP_ADD(3, t3, t4);
+                        STAMP_RAW(t4);
+                        STAMP_ADD(FAT_MERGE, t3, t4);
                     }
                 }
                 if (ovf != HX_EMPTY_SLOT) {
@@ -515,7 +491,7 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
             int cpos = wl.first_unexpanded(lane);  // carried: the pick after a merge is the next c
             while (status == HNSW_OK) {
                 if (cpos < 0) break;
-                STAMP(f0);
+                STAMP_RAW(f0);
                 uint32_t cid = 0;
 #pragma unroll
                 for (int r = 0; r < R; r++) {
@@ -535,12 +511,10 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
                 const uint32_t slot = (uint32_t)lane & 31u;
                 uint32_t nb = HX_EMPTY_SLOT;
                 if (slot < S && (!upper || ppos >= 0)) nb = v.adj0[(size_t)(upper ? pid : cid) * S + slot];
-#ifdef HX_STAMPS
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                STAMP(f1);
-                STAMP_ADD(0, f0, f1);
-                dbg_acc[7]++;
-#endif
+                STAMP_WAIT_VMEM();
+                STAMP_RAW(f1);
+                STAMP_ADD(GENERIC_PICK, f0, f1);
+                STAMP_COUNT(GENERIC_PASSES);
                 const bool is_ptr = nb != HX_EMPTY_SLOT && (nb & HX_OVF_FLAG);
                 const bool valid = nb != HX_EMPTY_SLOT && !is_ptr;
                 const u64 pm = __ballot(is_ptr);
@@ -566,16 +540,13 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
                 wave_fence();
                 if (valid && upper && spec_ok) want = !vhas(nb);
                 n_dist += (uint32_t)__popcll(__ballot(want && !upper));
-                STAMP(f2);
-                STAMP_ADD(1, f1, f2);
-#ifdef HX_STAMPS
-                dbg_mid = f2;
-#endif
+                STAMP_RAW(f2);
+                STAMP_ADD(GENERIC_FILTER, f1, f2);
+                STAMP_ROWS_LANDED_DEFAULT(f2);
                 float dist = 0.0f;
                 if (__ballot(want)) dist = eval_dist(nb, want, false);
-                STAMP(f3);
-                STAMP_ADD(2, f2, dbg_mid);
-                STAMP_ADD(3, dbg_mid, f3);
+                STAMP_RAW(f3);
+                STAMP_ADD_AROUND_ROWS_LANDED(GENERIC_ROW_WAIT, GENERIC_CHAIN, f2, f3);
                 const bool nan = want && dist != dist;
                 if (__ballot(nan && !upper)) {
                     status = HNSW_ERR_NAN_INPUT;
@@ -601,8 +572,8 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
                     if (status != HNSW_OK) break;
                 }
                 // ---- is p the next candidate?  then commit it from the registers
-                STAMP(f4);
-                STAMP_ADD(5, f3, f4);
+                STAMP_RAW(f4);
+                STAMP_ADD(GENERIC_MERGE_C, f3, f4);
                 const int npos = wl.first_unexpanded(lane);
                 cpos = npos;
                 if (npos < 0) break;
@@ -634,8 +605,8 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
                 }
                 wl.merge((fresh && upper) ? key : KEY_INVALID, ef_l, perm, lane);
                 cpos = wl.first_unexpanded(lane);
-                STAMP(f5);
-                STAMP_ADD(6, f4, f5);
+                STAMP_RAW(f5);
+                STAMP_ADD(GENERIC_COMMIT_P, f4, f5);
             }
             continue;
         }
@@ -721,12 +692,7 @@ hx_search_kernel(const DevView v, const SearchArgs a, const uint32_t slots_log2)
         a.out_ids[(size_t)q * a.n + idx] = HX_EMPTY_SLOT;
         if (a.out_dists) a.out_dists[(size_t)q * a.n + idx] = __builtin_inff();
     }
-#ifdef HX_STAMPS
-    if (lane == 0 && a.dbg) {
-        dbg_acc[4] = __builtin_readcyclecounter() - t_begin;
-        for (int i = 0; i < 8; i++) a.dbg[(size_t)q * 8 + i] = dbg_acc[i];
-    }
-#endif
+    STAMP_WRITE_GENERIC();
     if (lane == 0) {
         if (a.out_counts) a.out_counts[q] = count;
         hnsw_query_stats st;

@@ -44,6 +44,7 @@
 #include "device_index.h"
 #include "launch.h"
 #include "search_common.h"
+#include "stamps.h"
 #include "switches.h"
 
 namespace hx {
@@ -79,66 +80,6 @@ struct LeanArgs {
     uint32_t spill_log2;
     uint32_t lds_limit;  // ids the LDS level takes before it is closed; 0 = 75 % of its slots (tests lower it)
 };
-
-// Diagnostic build only (make stamps): per-phase cycle sums, written to a side buffer nothing else reads.
-#ifdef HX_STAMPS
-// a stamp drains the wave's memory counters and is a scheduling barrier, so that what lies between two
-// stamps is exactly the code written between them
-__device__ __forceinline__ unsigned long long stamp_now() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long t = __builtin_readcyclecounter();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define STAMP(var) const unsigned long long var = stamp_now()
-#define STAMP_ADD(slot, a, b) dbg_acc[slot] += (b) - (a)
-#ifdef HX_STAMPS_FRONT
-// (make stamps EXTRA=-DHX_STAMPS_FRONT) the front of the query split further, slots 40 .. 48: its stamps lengthen slot 7
-// by a fifth, so the plain stamps build, whose slot 7 the recorded profiles compare, does without them
-constexpr int HX_LEAN_DBG_SLOTS = 53;
-#define FSTAMP(var) STAMP(var)
-#define FSTAMP_ADD(slot, a, b) STAMP_ADD(slot, a, b)
-// the clock once the LDS requests are back, whatever is still in flight from memory (stamp_now would wait for it)
-#define FSTAMP_LDS(var)                                   \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
-    const unsigned long long var = __builtin_readcyclecounter(); \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define FSTAMP_SINCE_BEGIN(slot) dbg_acc[slot] = __builtin_readcyclecounter() - t_begin
-#else
-constexpr int HX_LEAN_DBG_SLOTS = 43;  // values per query in the side buffer (scripts/stamps_lean.py allocates it)
-#endif
-// A merge's own split: five values from `dbg` on (the f32 kernel passes dbg_acc + 26 for c's merge, + 31 for p's; a
-// caller without a side buffer passes nothing and its merges carry no stamp) -- cycles of the survivor loop, of the
-// LDS phase (scatter, read back, holes, refresh_last) and of the shift path, the survivors of the big merges, the big
-// merges.  Static offsets: a computed index would move the caller's array to scratch.
-#define MERGE_DBG_PARAM , unsigned long long *dbg = nullptr
-#define MERGE_DBG_ARG(first) , dbg_acc + (first)
-#define MERGE_STAMP(var) const unsigned long long var = dbg ? stamp_now() : 0ull
-#define MERGE_ADD(off, v) \
-    do {                  \
-        if (dbg) dbg[off] += (v); \
-    } while (0)
-#else
-#define STAMP(var)
-#define STAMP_ADD(slot, a, b)
-#define MERGE_DBG_PARAM
-#define MERGE_DBG_ARG(first)
-#define MERGE_STAMP(var)
-#define MERGE_ADD(off, v)
-#endif
-#ifdef HX_STAMPS
-// the last three values are the frontier's: its cycles (inside slot 0, which its own stamp lengthens), its runs and the
-// runs after c's merge (a survivor went in front of b)
-constexpr int HX_DBG_FRONTIER = HX_LEAN_DBG_SLOTS - 3;
-#endif
-#if !defined(HX_STAMPS) || !defined(HX_STAMPS_FRONT)
-#define FSTAMP(var)
-#define FSTAMP_ADD(slot, a, b)
-#define FSTAMP_LDS(var)
-#define FSTAMP_SINCE_BEGIN(slot)
-#endif
 
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t l) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
@@ -487,7 +428,7 @@ struct Lst {
             }
             refresh_last(ef);
             MERGE_STAMP(m1);
-            MERGE_ADD(2, m1 - m0);
+            MERGE_ADD(MERGE_SHIFT, m1 - m0);
             return;
         }
         // Three or more.  Every list entry counts the survivors that sort before it (its shift), every
@@ -525,7 +466,7 @@ struct Lst {
         }
         asm volatile("" ::: "memory");  // every staged key has been requested before perm is initialised
         MERGE_STAMP(m2);
-        MERGE_ADD(0, m2 - m0);
+        MERGE_ADD(MERGE_LOOP, m2 - m0);
         const uint32_t n_new = min(n_cur + m, ef);
 #pragma unroll
         for (int r = 0; r < R; r++) perm[R * lane + r] = LK_INVALID;
@@ -563,9 +504,9 @@ struct Lst {
         lds_fence();
         refresh_last(ef);
         MERGE_STAMP(m3);
-        MERGE_ADD(1, m3 - m2);
-        MERGE_ADD(3, m);
-        MERGE_ADD(4, 1);
+        MERGE_ADD(MERGE_LDS, m3 - m2);
+        MERGE_ADD(MERGE_SURVIVORS, m);
+        MERGE_ADD(MERGE_BIG, 1);
     }
 };
 
@@ -694,7 +635,7 @@ struct LstHT {
             if (64u + (uint32_t)lane >= ef) L[1] = LK_INVALID;
             refresh_last(ef);
             MERGE_STAMP(m1);
-            MERGE_ADD(2, m1 - m0);
+            MERGE_ADD(MERGE_SHIFT, m1 - m0);
             return;
         }
         // Three or more: the rank / scatter merge of Lst<R> over the two registers (perm: 128 entries,
@@ -721,7 +662,7 @@ struct LstHT {
         }
         asm volatile("" ::: "memory");  // every staged key has been requested before perm is initialised
         MERGE_STAMP(m2);
-        MERGE_ADD(0, m2 - m0);
+        MERGE_ADD(MERGE_LOOP, m2 - m0);
         const uint32_t n_new = min(n_cur + m, ef);
         perm[lane] = LK_INVALID;
         perm[64 + lane] = LK_INVALID;
@@ -748,9 +689,9 @@ struct LstHT {
         lds_fence();
         refresh_last(ef);
         MERGE_STAMP(m3);
-        MERGE_ADD(1, m3 - m2);
-        MERGE_ADD(3, m);
-        MERGE_ADD(4, 1);
+        MERGE_ADD(MERGE_LDS, m3 - m2);
+        MERGE_ADD(MERGE_SURVIVORS, m);
+        MERGE_ADD(MERGE_BIG, 1);
     }
 };
 
@@ -953,13 +894,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
 
     uint32_t n_dist = 0, n_exp = 0, sum_deg = 0, n_vis = 0;
     int32_t status = HNSW_OK;
-#ifdef HX_STAMPS
-    unsigned long long dbg_acc[HX_LEAN_DBG_SLOTS] = {};
-    const unsigned long long t_begin = __builtin_readcyclecounter();
-    // the runner-up's misses (slots 16 .. 24): what the last miss predicted for the pass that follows it
-    bool dbg_follow = false, dbg_took_pre = false;
-    uint32_t dbg_pred_c = HX_EMPTY_SLOT, dbg_pred_p = HX_EMPTY_SLOT, dbg_old_p = HX_EMPTY_SLOT;
-#endif
+    STAMP_STATE_LEAN_F32();
 
     // WALK_AHEAD: this lane's slot of row `layer` of node id (base = upper_base[id]): lanes 0 .. S1 - 1 on an upper
     // layer, c's lanes of the layer-0 pass on layer 0; HX_EMPTY_SLOT elsewhere, and on an upper layer for a node
@@ -987,7 +922,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     QueryRegs<DS> qreg;
     float(&qv)[DS] = qreg.v;
     if (!load_query_f32<DS>(a.Q + (size_t)q * DS, qv, lane)) status = HNSW_ERR_NAN_INPUT;
-    FSTAMP_SINCE_BEGIN(40);  // query staging alone
+    FSTAMP_SINCE_BEGIN(LEAN_F_STAGING);
 
     // distance of one row per wanting lane (every lane calls it: the cooperative form needs the whole wave)
     auto dist_of = [&](uint32_t id, bool want) __attribute__((always_inline)) -> float {
@@ -1039,7 +974,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             const uint32_t vt0 = vis.look(id, vb);
             const uint32_t vt = act ? vt0 : 4u;
             FSTAMP(w1);
-            FSTAMP_ADD(43, w0, w1);
+            FSTAMP_ADD(LEAN_F_FILTER, w0, w1);
             if (vt != 4u) {
                 r.ubn = a.upper_base[id];
                 const uint4 *src = reinterpret_cast<const uint4 *>(a.rows + (size_t)id * DS);
@@ -1054,11 +989,11 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
                 FSTAMP_LDS(g0);
                 FSTAMP(g1);
-                FSTAMP_ADD(43, w1, g0);
-                FSTAMP_ADD(44, g0, g1);
+                FSTAMP_ADD(LEAN_F_FILTER, w1, g0);
+                FSTAMP_ADD(LEAN_F_ROWS_LEFT, g0, g1);
                 r.dist = __builtin_sqrtf(chain_sum<DS>(w, qv));
                 FSTAMP(g2);
-                FSTAMP_ADD(45, g1, g2);
+                FSTAMP_ADD(LEAN_F_CHAIN, g1, g2);
             }
         } else {
             r.fresh = vis.insert(id, act);
@@ -1070,9 +1005,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
         return r;
     };
 
-#ifdef HX_STAMPS
-    dbg_acc[25] = __builtin_readcyclecounter() - t_begin;  // query staging + entry point alone (slot 7 minus this: the walk)
-#endif
+    STAMP_SINCE_BEGIN(LEAN_ENTRY);
     // ---- upper layers, ef = 1 (template.rs:322-324): a greedy walk.  With one slot in `selected`
     // every fresh neighbour below the running best replaces it (searcher.rs:74-94), the next pop is
     // the best found so far, and once an expansion improves nothing the next pop is a leftover above
@@ -1093,7 +1026,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
         vis.insert(cur, lane == 0);
         n_vis = 1;
         FSTAMP(l1);
-        FSTAMP_ADD(41, l0, l1);
+        FSTAMP_ADD(LEAN_F_CLEAR, l0, l1);
         if (!have_ub) {
             ub_cur = uni(a.upper_base[cur]);
             have_ub = true;
@@ -1106,8 +1039,8 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             n_exp++;
             FSTAMP_LDS(x0);
             FSTAMP(x1);
-            FSTAMP_ADD(42, x0, x1);  // what is left of the wait for row_now
-            FSTAMP_ADD(48, 0, 1);    // upper-layer expansions
+            FSTAMP_ADD(LEAN_F_ROW_WAIT, x0, x1);  // (row_now)
+            FSTAMP_COUNT(LEAN_F_EXPANSIONS);
             bool improved = false;
             uint32_t new_cur = cur, new_ub = ub_cur;
             uint32_t ovf_lo = 0, ovf_hi = 0;
@@ -1175,9 +1108,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
     }
 
     // ---- layer 0 with ef (template.rs:326) ----
-#ifdef HX_STAMPS
-    dbg_acc[7] = __builtin_readcyclecounter() - t_begin;  // query staging + entry point + upper layers
-#endif
+    STAMP_SINCE_BEGIN(LEAN_FRONT);
     const uint32_t ef = max(1u, a.ef);
     LT lst;
     lst.init();
@@ -1185,7 +1116,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
         FSTAMP(t0);
         const TableLimits lim = layer0_table<SPILLV>(a, vis, hslots, cur, lane);
         FSTAMP(t1);
-        FSTAMP_ADD(47, t0, t1);
+        FSTAMP_ADD(LEAN_F_TABLE, t0, t1);
         const uint32_t lds_limit = lim.lds, vis_limit = lim.all;
         n_vis = 1;  // the entry point: what layer0_table put into the emptied table
         lst.set_first(best, lane);
@@ -1232,11 +1163,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 u64 F[4];
                 STAMP(fr0);
                 lst.frontier(F, perm, lane);
-#ifdef HX_STAMPS
-                asm volatile("" ::"v"(F[0]), "v"(F[1]), "v"(F[2]), "v"(F[3]) : "memory");
-                dbg_acc[HX_DBG_FRONTIER] += stamp_now() - fr0;
-                dbg_acc[HX_DBG_FRONTIER + 1]++;
-#endif
+                STAMP_FRONTIER_AT_PICK(fr0, F);
                 // candidates exhausted / only worse ones left (searcher.rs:35,41-44)
                 if (HX_UNLIKELY(__ballot(lk_unexp(F[0])) == 0)) break;
                 has_p = __ballot(lk_unexp(F[1])) != 0;
@@ -1247,14 +1174,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 bkey = F[3];
                 lst.mark_key(F[0]);
                 n_exp++;
-#ifdef HX_STAMPS
-                if (dbg_follow) {
-                    if (cid == dbg_pred_c && pid == dbg_pred_p) dbg_acc[19]++;
-                    if (pid == dbg_old_p) dbg_acc[20]++;
-                    dbg_follow = false;
-                }
-                dbg_took_pre = pre_c == cid && pre_p == pid;
-#endif
+                STAMP_NOTE_PICK(cid, pid, pre_c, pre_p);
                 // the rows requested during the previous pass are this pair's: one compare, one branch
                 if (HX_LIKELY(__ballot(pre_c == cid && pre_p == pid) != 0)) {
                     nb = pre_nb;
@@ -1284,14 +1204,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 }
                 lst.mark((uint32_t)cpos, lane);
                 n_exp++;
-#ifdef HX_STAMPS
-                if (dbg_follow) {
-                    if (cid == dbg_pred_c && pid == dbg_pred_p) dbg_acc[19]++;
-                    if (pid == dbg_old_p) dbg_acc[20]++;
-                    dbg_follow = false;
-                }
-                dbg_took_pre = pre_c == cid && pre_p == pid;
-#endif
+                STAMP_NOTE_PICK(cid, pid, pre_c, pre_p);
                 if (HX_LIKELY(pre_c == cid && pre_p == pid)) {
                     nb = pre_nb;  // both rows were requested during the previous pass
                     if constexpr (MISS_KEEP) kept = carry;
@@ -1301,18 +1214,10 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 pre_c = HX_EMPTY_SLOT;
                 carry = false;
             }
-#ifdef HX_STAMPS
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            dbg_acc[6]++;
-#endif
+            STAMP_PASS_PICKED();
             STAMP(f1);
-            STAMP_ADD(0, f0, f1);
-#ifdef HX_STAMPS
-            if (!ovf_pass && dbg_took_pre) {
-                dbg_acc[21] += f1 - f0;
-                dbg_acc[22]++;
-            }
-#endif
+            STAMP_ADD(LEAN_PICK, f0, f1);
+            STAMP_PICK_AHEAD(ovf_pass, f0, f1);
             // ---- classify the slots.  A row with an overflow pointer (degree > S0) is rare: c's is
             // finished after the merge, a runner-up with one is not speculated on ----
             const u64 pm = ovf_pass ? 0ull : __ballot((int32_t)nb < -1);  // 0x80000000 | overflow row
@@ -1366,26 +1271,13 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 const bool pend = (ct != 4u) & !fresh;
                 if (HX_UNLIKELY(__ballot(pend) != 0)) {
                     fresh = SPILLV ? vis.finish2(nb, vb, ct, pend, fresh) : vis.finish(nb, vb, ct, pend, fresh);
-#ifdef HX_STAMPS
-                    dbg_acc[11]++;
-#endif
+                    STAMP_COUNT(LEAN_SLOW_ROUNDS);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-#ifdef HX_STAMPS
-                // (diagnostic build) what is left of the row round trip once the claims are done, then the chain alone
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                const unsigned long long g0 = __builtin_readcyclecounter();  // (not stamp_now: that would wait for the rows)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                const unsigned long long g1 = stamp_now();
-                dbg_acc[2] += g1 - g0;
-#endif
+                STAMP_ROW_WAIT(g1);
                 const float s = chain_sum<DS>(w, qv);
                 dist = __builtin_sqrtf(s);
-#ifdef HX_STAMPS
-                asm volatile("" ::"v"(dist) : "memory");
-                dbg_acc[3] += stamp_now() - g1;
-#endif
+                STAMP_CHAIN(g1, dist);
             }
             const bool want = upper ? want_pre : fresh;
             const u64 vmask = __ballot(valid), fmask = __ballot(fresh);
@@ -1404,21 +1296,10 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             u64 key = LK_INVALID;
             if (want && !nan) key = ((u64)__builtin_bit_cast(uint32_t, dist) << 32) | nb;
             STAMP(f2);
-            STAMP_ADD(1, f1, f2);
-#ifdef HX_STAMPS
-            if (kept) {  // slot 1 on the passes whose runner-up kept its distances
-                dbg_acc[23] += f2 - f1;
-                dbg_acc[24]++;
-            }
-#endif
+            STAMP_ADD(LEAN_FILTER, f1, f2);
+            STAMP_FILTER_KEPT(kept, f1, f2);
             STAMP(f3);
-#ifdef HX_STAMPS
-            {
-                const uint32_t mm = (uint32_t)__popcll(__ballot(!upper && key < lst.last_key));
-                if (mm == 0) dbg_acc[12]++; else if (mm <= 2) dbg_acc[13]++; else dbg_acc[14]++;  // static slots: a computed index would move the array to scratch
-                if (mm != 0 && mm <= HX_MERGE_SHIFT_MAX) { dbg_acc[36]++; dbg_acc[37] += mm; }  // c's small merges, their keys
-            }
-#endif
+            STAMP_MERGE_SIZE(!upper && key < lst.last_key, LEAN_SMALL_C, LEAN_SMALL_C_KEYS);
             const u64 nanm = __ballot(nan);
             if (HX_UNLIKELY((nanm & 0xFFFFFFFFull) != 0)) {
                 status = HNSW_ERR_NAN_INPUT;  // Dist::cmp would panic (dist.rs:32)
@@ -1457,16 +1338,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                         }
                     }
                     const bool again = k2 == LK_INVALID;  // p is the runner-up again: its lanes hold its row already
-#ifdef HX_STAMPS
-                    {
-                        const uint32_t nbel = (uint32_t)__popcll(bm);
-                        if (nbel == 1) dbg_acc[16]++; else if (nbel == 2) dbg_acc[17]++; else dbg_acc[18]++;
-                        dbg_follow = true;
-                        dbg_pred_c = (uint32_t)k1;
-                        dbg_pred_p = again ? pid : (uint32_t)k2;
-                        dbg_old_p = pid;
-                    }
-#endif
+                    STAMP_NOTE_MISS(bm, (uint32_t)k1, again ? pid : (uint32_t)k2, pid);
                     pre_c = (uint32_t)k1;
                     pre_p = again ? pid : (uint32_t)k2;
                     // (the load writes pre_nb itself: a select behind it would wait for the row here -- measured, 5 % slower)
@@ -1479,9 +1351,9 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                     }
                 }
             }
-            lst.merge(upper ? LK_INVALID : key, ef, perm, lane MERGE_DBG_ARG(26));
+            lst.merge(upper ? LK_INVALID : key, ef, perm, lane MERGE_DBG_ARG(LEAN_MERGE_C));
             STAMP(f3b);
-            STAMP_ADD(8, f3, f3b);
+            STAMP_ADD(LEAN_MERGE_C_ALL, f3, f3b);
             if (HX_UNLIKELY((pm & 0xFFFFFFFFull) != 0)) {  // degree > S0: the rest of c's row goes through the next passes (rare)
                 const uint32_t c_ovf = rdlane(nb, (uint32_t)__ffsll((long long)(pm & 0xFFFFFFFFull)) - 1) & ~HX_OVF_FLAG;
                 ovf_lo = uni(a.ovf_off[c_ovf]);
@@ -1507,10 +1379,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                     lst.frontier(G, perm, lane);
                     akey = G[1];
                     bkey = G[2];
-#ifdef HX_STAMPS
-                    dbg_acc[HX_DBG_FRONTIER + 1]++;
-                    dbg_acc[HX_DBG_FRONTIER + 2]++;
-#endif
+                    STAMP_FRONTIER_RERUN();
                 }
                 pre_c = (uint32_t)akey;  // (HX_EMPTY_SLOT where there is none: matches no candidate)
                 pre_p = (uint32_t)bkey;
@@ -1535,7 +1404,7 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 }
             }
             STAMP(f4);
-            STAMP_ADD(9, f3b, f4);
+            STAMP_ADD(LEAN_IS_P_NEXT, f3b, f4);
             if constexpr (FRONTIER)
                 lst.mark_key(pkey);
             else
@@ -1564,29 +1433,18 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                 break;
             }
             STAMP(f4b);
-            STAMP_ADD(5, f4, f4b);
-#ifdef HX_STAMPS
-            {
-                const uint32_t mm = (uint32_t)__popcll(__ballot(pfresh && key < lst.last_key));
-                if (mm == 0) dbg_acc[12]++; else if (mm <= 2) dbg_acc[13]++; else dbg_acc[14]++;  // static slots: a computed index would move the array to scratch
-                if (mm != 0 && mm <= HX_MERGE_SHIFT_MAX) { dbg_acc[38]++; dbg_acc[39] += mm; }  // p's small merges, their keys
-                dbg_acc[15]++;
-            }
-#endif
-            lst.merge(pfresh ? key : LK_INVALID, ef, perm, lane MERGE_DBG_ARG(31));
+            STAMP_ADD(LEAN_COMMIT_P, f4, f4b);
+            STAMP_MERGE_SIZE(pfresh && key < lst.last_key, LEAN_SMALL_P, LEAN_SMALL_P_KEYS);
+            STAMP_COUNT(LEAN_P_COMMITS);
+            lst.merge(pfresh ? key : LK_INVALID, ef, perm, lane MERGE_DBG_ARG(LEAN_MERGE_P));
             STAMP(f5);
-            STAMP_ADD(10, f4b, f5);
+            STAMP_ADD(LEAN_MERGE_P_ALL, f4b, f5);
         }
     }
 
     const uint32_t count = status == HNSW_OK ? min(a.n, lst.n_cur) : 0;
     write_results(a, q, lst, count, lane);
-#ifdef HX_STAMPS
-    if (lane == 0 && a.dbg) {
-        dbg_acc[4] = __builtin_readcyclecounter() - t_begin;
-        for (int i = 0; i < HX_LEAN_DBG_SLOTS; i++) a.dbg[(size_t)q * HX_LEAN_DBG_SLOTS + i] = dbg_acc[i];
-    }
-#endif
+    STAMP_WRITE_LEAN_F32();
     write_stats(a, q, n_dist, n_exp, sum_deg, status, lane);
 }
 
@@ -1621,10 +1479,7 @@ __global__ void __launch_bounds__(64) hx_lean_q8_kernel(const LeanArgs a) {
 
     uint32_t n_dist = 0, n_exp = 0, sum_deg = 0, n_vis = 0;
     int32_t status = HNSW_OK;
-#ifdef HX_STAMPS
-    unsigned long long dbg_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long t_begin = __builtin_readcyclecounter();
-#endif
+    STAMP_STATE();
 
     // ---- the query goes through the same quantiser as a stored vector (Point::new -> QuantVec::new,
     // template.rs:313, quant.rs:41-66) and is kept dequantised, in this lane's half order, in registers ----
@@ -1788,9 +1643,7 @@ __global__ void __launch_bounds__(64) hx_lean_q8_kernel(const LeanArgs a) {
     }
 
     // ---- layer 0 with ef (template.rs:326) ----
-#ifdef HX_STAMPS
-    dbg_acc[7] = __builtin_readcyclecounter() - t_begin;
-#endif
+    STAMP_SINCE_BEGIN(Q8_FRONT);
     const uint32_t ef = max(1u, a.ef);
     LT lst;
     lst.init();
@@ -1839,11 +1692,9 @@ __global__ void __launch_bounds__(64) hx_lean_q8_kernel(const LeanArgs a) {
                 if (cslot < S0) pre_nb = a.adj0[(size_t)pre_c * S0 + cslot];
             }
             const u64 pm = __ballot((int32_t)nb < -1);  // 0x80000000 | overflow row (degree > S0, rare)
-#ifdef HX_STAMPS
-            dbg_acc[6]++;
-#endif
+            STAMP_COUNT(Q8_PASSES);
             STAMP(f1);
-            STAMP_ADD(0, f0, f1);
+            STAMP_ADD(Q8_PICK, f0, f1);
             const bool valid = (int32_t)nb >= 0;
             // ---- visited: the pair looks at the id's home bucket, the even lane claims a slot ----
             const uint32_t vb = vis.home(nb);
@@ -1868,7 +1719,7 @@ __global__ void __launch_bounds__(64) hx_lean_q8_kernel(const LeanArgs a) {
                 break;
             }
             STAMP(f2);
-            STAMP_ADD(1, f1, f2);
+            STAMP_ADD(Q8_FILTER, f1, f2);
             u64 key = LK_INVALID;
             if (fmask) {
                 const float dist = eval(nb, fresh);
@@ -1880,10 +1731,10 @@ __global__ void __launch_bounds__(64) hx_lean_q8_kernel(const LeanArgs a) {
                 if (mine) key = ((u64)__builtin_bit_cast(uint32_t, dist) << 32) | nb;
             }
             STAMP(f3);
-            STAMP_ADD(3, f2, f3);
+            STAMP_ADD(Q8_CHAIN, f2, f3);
             lst.merge(key, ef, perm, lane);
             STAMP(f4);
-            STAMP_ADD(8, f3, f4);
+            STAMP_ADD(Q8_MERGE, f3, f4);
             if (pm) {  // degree > S0: the rest of the row
                 const uint32_t c_ovf = rdlane(nb, (uint32_t)__ffsll((long long)pm) - 1) & ~HX_OVF_FLAG;
                 const uint32_t lo = uni(a.ovf_off[c_ovf]), hi = uni(a.ovf_off[c_ovf + 1]);
@@ -1940,12 +1791,7 @@ __global__ void __launch_bounds__(64) hx_lean_q8_kernel(const LeanArgs a) {
         a.out_ids[(size_t)q * a.n + idx] = HX_EMPTY_SLOT;
         if (a.out_dists) a.out_dists[(size_t)q * a.n + idx] = __builtin_inff();
     }
-#ifdef HX_STAMPS
-    if (lane == 0 && a.dbg) {
-        dbg_acc[4] = __builtin_readcyclecounter() - t_begin;
-        for (int i = 0; i < 16; i++) a.dbg[(size_t)q * HX_LEAN_DBG_SLOTS + i] = dbg_acc[i];
-    }
-#endif
+    STAMP_WRITE_LEAN_Q8();
     if (lane == 0) {
         if (a.out_counts) a.out_counts[q] = count;
         hnsw_query_stats st;

@@ -18,6 +18,9 @@ import torch
 
 sys.path.insert(0, ".")
 import hnsw_rs_amd as H
+from stamp_slots import STRIDE, slots
+
+L = slots("LEAN")  # hnsw_rs_amd/csrc/stamp_slots.inc
 
 ef = int(sys.argv[1]) if len(sys.argv) > 1 else 68
 outp = sys.argv[2] if len(sys.argv) > 2 else None
@@ -36,7 +39,7 @@ for nq in (64, 1024):
     dd = torch.empty((nq, n), dtype=torch.float32, device=dev)
     cnt = torch.empty(nq, dtype=torch.int32, device=dev)
     st = torch.empty((nq, 4), dtype=torch.int32, device=dev)
-    dbg = torch.zeros((nq, 43), dtype=torch.int64, device=dev)  # HX_LEAN_DBG_SLOTS values per query
+    dbg = torch.zeros((nq, STRIDE), dtype=torch.int64, device=dev)
     os.environ["HX_DBG_PTR"] = str(dbg.data_ptr())
     for _ in range(3):
         idx.search_batch_device(dQ.data_ptr(), nq, n, ef, ids.data_ptr(), dd.data_ptr(), cnt.data_ptr(), st.data_ptr(), 0)
@@ -49,32 +52,34 @@ for nq in (64, 1024):
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1)
     D = dbg.cpu().numpy().astype(np.float64)
-    tot, passes = D[:, 4], D[:, 6]
+    def C(name):
+        return D[:, L[name]]
+    tot, passes = C("TOTAL"), C("PASSES")
     ghz = tot.max() / (ms * 1e6)  # the slowest wave spans the kernel
-    # stamp 1 spans look + row request + claims + what is left of the row round trip + chain; 2 and 3 are the last two alone
-    per_pass = {"pick_and_adjacency_round_trip": D[:, 0].mean() / passes.mean(),
-                "visited_look_row_request_claims (the rows are in flight underneath)": (D[:, 1] - D[:, 2] - D[:, 3]).mean() / passes.mean(),
-                "row_round_trip_left_after_the_claims": D[:, 2].mean() / passes.mean(),
-                "chain_and_sqrt": D[:, 3].mean() / passes.mean(),
-                "merges_commits_overflow_rows": (D[:, 8] + D[:, 9] + D[:, 5] + D[:, 10]).mean() / passes.mean()}
+    # FILTER spans look + row request + claims + what is left of the row round trip + chain; ROW_WAIT and CHAIN are the last two alone
+    per_pass = {"pick_and_adjacency_round_trip": C("PICK").mean() / passes.mean(),
+                "visited_look_row_request_claims (the rows are in flight underneath)": (C("FILTER") - C("ROW_WAIT") - C("CHAIN")).mean() / passes.mean(),
+                "row_round_trip_left_after_the_claims": C("ROW_WAIT").mean() / passes.mean(),
+                "chain_and_sqrt": C("CHAIN").mean() / passes.mean(),
+                "merges_commits_overflow_rows": (C("MERGE_C_ALL") + C("IS_P_NEXT") + C("COMMIT_P") + C("MERGE_P_ALL")).mean() / passes.mean()}
     # per query: staging / upper layers + per pass the adjacency round trip, the row round trip measured alone
     # (scripts/micro/gather_latency.hip: a wave alone on its CU, 25 x 16 B per lane from 64 random rows) and the chain
     ROW_GATHER_ALONE = 1850.0
-    floor_cyc = D[:, 7] + D[:, 0] + passes * ROW_GATHER_ALONE + D[:, 3]
+    floor_cyc = C("FRONT") + C("PICK") + passes * ROW_GATHER_ALONE + C("CHAIN")
     r = {"queries": nq, "kernel_ms_under_stamps": round(ms, 4), "implied_clock_ghz": round(ghz, 3),
          "passes_per_query": round(passes.mean(), 2), "cycles_per_query_mean": round(tot.mean()), "cycles_per_query_max": round(tot.max()),
-         "staging_and_upper_layers_cycles": round(D[:, 7].mean()),
+         "staging_and_upper_layers_cycles": round(C("FRONT").mean()),
          "cycles_per_pass": {k: round(v) for k, v in per_pass.items()},
          "row_gather_alone_cycles (profiles/r02_gather_microbench_cache_resident.txt)": 1850,
          "floor_cycles_mean": round(floor_cyc.mean()), "floor_cycles_of_the_slowest_query": round(floor_cyc[np.argmax(tot)]),
          "floor_ms_slowest_query": round(floor_cyc[np.argmax(tot)] / ghz / 1e6, 4), "floor_ms_mean_query": round(floor_cyc.mean() / ghz / 1e6, 4),
          "floor_over_kernel": round(floor_cyc[np.argmax(tot)] / tot.max(), 3)}
-    # the bookkeeping term in its parts (stamps 8, 9, 5, 10), per pass, and how many merges inserted 0 / 1-2 / more keys
-    r["bookkeeping_cycles_per_pass"] = {"merge_of_c": round(D[:, 8].mean() / passes.mean()), "is_p_next_and_prefetch": round(D[:, 9].mean() / passes.mean()),
-                                        "claims_of_p": round(D[:, 5].mean() / passes.mean()), "merge_of_p": round(D[:, 10].mean() / passes.mean())}
-    r["per_query_counts"] = {"p_commits": round(D[:, 15].mean(), 2), "merges_inserting_0": round(D[:, 12].mean(), 2),
-                             "merges_inserting_1_or_2": round(D[:, 13].mean(), 2), "merges_inserting_more": round(D[:, 14].mean(), 2),
-                             "passes_with_a_second_claim_round": round(D[:, 11].mean(), 2)}
+    # the bookkeeping term in its parts, per pass, and how many merges inserted 0 / 1-2 / more keys
+    r["bookkeeping_cycles_per_pass"] = {"merge_of_c": round(C("MERGE_C_ALL").mean() / passes.mean()), "is_p_next_and_prefetch": round(C("IS_P_NEXT").mean() / passes.mean()),
+                                        "claims_of_p": round(C("COMMIT_P").mean() / passes.mean()), "merge_of_p": round(C("MERGE_P_ALL").mean() / passes.mean())}
+    r["per_query_counts"] = {"p_commits": round(C("P_COMMITS").mean(), 2), "merges_inserting_0": round(C("MERGES_0").mean(), 2),
+                             "merges_inserting_1_or_2": round(C("MERGES_1_2").mean(), 2), "merges_inserting_more": round(C("MERGES_3_UP").mean(), 2),
+                             "passes_with_a_second_claim_round": round(C("SLOW_ROUNDS").mean(), 2)}
     res[str(nq)] = r
     print(json.dumps(r))
 if outp:
