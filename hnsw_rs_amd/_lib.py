@@ -143,6 +143,8 @@ SYMBOLS = {
                                                               vp, vp, vp, vp, vp]),
     "hnsw_search_batch_filtered_set_range_device_finish": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp,
                                                                      vp, vp, vp, vp, vp, vp, vp, u8p]),
+    "hnsw_search_batch_filtered_wide": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, vp, u32p, u32p, u32p, u32p,
+                                                  f32p, u32p, C.POINTER(QueryStats), u8p]),
     "hnsw_search_filtered": (C.c_int, [vp, f32p, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, u32p, f32p,
                                        u32p, u8p]),
     "hnsw_bench_search_filtered_threads": (C.c_int, [vp, f32p, C.c_uint64, C.c_uint32, C.c_uint32, vp, u32p, u32p, u32p,

@@ -497,6 +497,22 @@ int hnsw_search_batch_filtered_set_range_device_finish(hnsw_index *h, const floa
                            true, d_ids, d_dists, d_counts, d_stats, stream, true, paths);
 }
 
+// ---- wide filtered search: n and ef' up to 1024 under a row of a resident set, a label range, both or neither ----------
+int hnsw_search_batch_filtered_wide(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, hnsw_mask_set *set,
+                                    const uint32_t *mask_of, const uint32_t *lo, const uint32_t *hi, uint32_t *ids,
+                                    float *dists, uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
+    int rc = check_search_args(h, ef);
+    if (rc != HNSW_OK || (set && (rc = check_set(h, set)))) return rc;
+    hx::Filter f = make_filter(hx::Filter::WIDE, set ? hx::Filter::SET : hx::Filter::ALL, set, set ? mask_of : nullptr,
+                               lo || hi ? 1 : 0, lo, hi);
+    std::vector<uint32_t> row0;
+    if (set && !mask_of && nq <= 0x7FFFFFFFull) {  // every query under row 0 (more queries are refused below)
+        row0.assign(nq, 0);
+        f.mask_of = row0.data();
+    }
+    return hx::search_filtered_wide(h, Q, nq, n, ef, f, ids, dists, counts, stats, paths);
+}
+
 // ---- one query under a row of a resident set AND a label range, gathered with its concurrent callers (coalesce.h) -------
 int hnsw_search_filtered(hnsw_index *h, const float *q, uint32_t n, uint32_t ef, hnsw_mask_set *set, uint32_t row,
                          uint32_t lo, uint32_t hi, uint32_t *ids, float *dists, uint32_t *count, uint8_t *path) {

@@ -68,6 +68,11 @@ struct hnsw_index {
     std::atomic<uint64_t> n_filt_set_range_calls{0}, n_filt_set_range_groups{0};
     // hnsw_search_batch_filtered_ranges: calls, and the distinct canonical range lists they named
     std::atomic<uint64_t> n_filt_ranges_calls{0}, n_filt_ranges_groups{0};
+    // hnsw_search_batch_filtered_wide: calls, and their queries per path; options "filter_wide_lds_log2" (slots of the LDS
+    // level of the visited set; 0: the launcher's choice) and "filter_wide_hbm_log2" (words of its HBM level per
+    // launched query; 0: no second level)
+    std::atomic<uint64_t> n_wide_calls{0}, n_wide_graph{0}, n_wide_exact{0}, n_wide_overflow{0};
+    int filter_wide_lds_log2 = 0, filter_wide_hbm_log2 = 18;
     // hnsw_search_filtered: calls answered, and the launches of their leaders (coalesce.h)
     std::atomic<uint64_t> n_filt_one_calls{0}, n_filt_one_batches{0};
     // hnsw_search_batch_shards with this handle as shard 0: calls whose shards were all searched, and their merges launched

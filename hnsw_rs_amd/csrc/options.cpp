@@ -14,11 +14,13 @@ template <class T> T stored(const T &x) { return x; }
 template <class T> T stored(const std::atomic<T> &x) { return x.load(); }
 
 // what a value has to be, with the text of the refusal (after the option's name)
-enum Bound { ANY, POSITIVE, NOT_NEGATIVE, ZERO_OR_ONE };
+enum Bound { ANY, POSITIVE, NOT_NEGATIVE, ZERO_OR_ONE, WIDE_LDS_LOG2, WIDE_HBM_LOG2 };
 const char *refusal(Bound b, int64_t value) {
     if (b == POSITIVE && value < 1) return "must be positive";
     if (b == NOT_NEGATIVE && value < 0) return "must not be negative";
     if (b == ZERO_OR_ONE && value != 0 && value != 1) return "must be 0 or 1";
+    if (b == WIDE_LDS_LOG2 && value != 0 && (value < 10 || value > 15)) return "must be 10 to 15 (or 0: the launcher's choice)";
+    if (b == WIDE_HBM_LOG2 && value != 0 && (value < 10 || value > 22)) return "must be 10 to 22 (or 0: no second level)";
     return nullptr;
 }
 
@@ -48,6 +50,8 @@ const Option kOptions[] = {
     HX_OPTION("metric_cosine", ANY, NO_CLAMP, 0, cosine, value != 0),
     HX_OPTION("filter_exact_max", ANY, NO_CLAMP, 0, filter_exact_max, value),
     HX_OPTION("filter_exact_grouped", ZERO_OR_ONE, NO_CLAMP, 0, filter_exact_grouped, (int)value),
+    HX_OPTION("filter_wide_lds_log2", WIDE_LDS_LOG2, NO_CLAMP, 0, filter_wide_lds_log2, (int)value),
+    HX_OPTION("filter_wide_hbm_log2", WIDE_HBM_LOG2, NO_CLAMP, 0, filter_wide_hbm_log2, (int)value),
     HX_OPTION("mask_set_cache_mb", NOT_NEGATIVE, 1 << 20, 0, mask_set_cache_mb, value),
     HX_OPTION("gpu_build_batch_max", POSITIVE, 1 << 20, 0, build_batch_max, (uint32_t)value),
     HX_OPTION("gpu_build_batch_div", POSITIVE, 1 << 20, 0, build_batch_div, (uint32_t)value),
@@ -87,6 +91,10 @@ const Stat kStats[] = {
     HX_STAT("filtered_queries_graph", h.n_filt_graph),
     HX_STAT("filtered_queries_exact", h.n_filt_exact),
     HX_STAT("filtered_overflow_exact", h.n_filt_overflow),
+    HX_STAT("filtered_wide_calls", h.n_wide_calls),
+    HX_STAT("filtered_wide_queries_graph", h.n_wide_graph),
+    HX_STAT("filtered_wide_queries_exact", h.n_wide_exact),
+    HX_STAT("filtered_wide_overflow_exact", h.n_wide_overflow),
     HX_STAT("label_words_uploaded", h.lab.words_uploaded),
     HX_STAT("filtered_range_calls", h.n_filt_range_calls),
     HX_STAT("filtered_range_ranges", h.n_filt_range_ranges),

@@ -96,7 +96,7 @@ int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, u
 // with lo > hi is empty; K == 0: no label filter.  Next to a SET row a query is under the row AND its range.
 struct Filter {
     // the entry points that made the call: picks the stat counters and the wording of errors, never a launch
-    enum Family { DELETED, SCAN, MASK, MULTI, OF_SET, RANGE, SET_RANGE, RANGES, ONE_QUERY } family = DELETED;
+    enum Family { DELETED, SCAN, MASK, MULTI, OF_SET, RANGE, SET_RANGE, RANGES, ONE_QUERY, WIDE } family = DELETED;
     enum Rows { ALL, ONE, MANY, SET } rows = ALL;
     const uint64_t *masks = nullptr;  // ONE, MANY (host memory)
     uint64_t allow_bits = 0;          // ONE, MANY
@@ -129,6 +129,12 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
 int search_filtered_checked(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f,
                             bool exact_only, uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
                             uint8_t *paths);
+
+// hnsw_search_batch_filtered_wide (filter_wide_host.cpp): search_filtered's contract for 1 <= n <= 1024 and ef' <= 1024, by
+// the kernels of search_filtered_wide.hip -- the same planner, the same paths, the first per-query error as the status
+// (stats may be NULL).  f: rows ALL or SET, K 0 or 1.  Counts under "filtered_wide_*" alone.
+int search_filtered_wide(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef, const Filter &f, uint32_t *ids,
+                         float *dists, uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths);
 
 // A device-pointer call under a Filter whose mask_of / lo / hi are device memory (on_device): hnsw_search_batch_device
 // while ids are deleted and every hnsw_search_batch_filtered*_device (finish = false), and their _finish: every query by

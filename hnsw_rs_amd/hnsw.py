@@ -472,6 +472,18 @@ class HNSW:
         return self._filtered(self._L.hnsw_search_batch_filtered_set_range, Q, n, ef,
                               lambda nq: (mask_set._s, self._mask_of(mask_of, nq), *self._range(lo, hi, nq)))
 
+    def search_batch_filtered_wide(self, Q, n, ef, mask_set=None, mask_of=None, lo=None, hi=None):
+        """search_batch_filtered_set_range for 1 <= n <= 1024 and max(ef, n) <= 1024 (hnsw_search_batch_filtered_wide):
+        under a row of a resident MaskSet, a label range, both, or neither (mask_set None and lo None: the plain search
+        over the undeleted ids).  mask_of [nq]: rows of the set, -1 or MASK_NONE; None: row 0.  lo / hi: both or
+        neither, scalars broadcast.  -> as search_batch_filtered"""
+        if (lo is None) != (hi is None):
+            raise HnswError(_lib.ERR_ARG, "lo and hi come together")
+        return self._filtered(self._L.hnsw_search_batch_filtered_wide, Q, n, ef,
+                              lambda nq: (None if mask_set is None else mask_set._s,
+                                          None if mask_set is None else self._mask_of(mask_of, nq),
+                                          *((None, None) if lo is None else self._range(lo, hi, nq))))
+
     def search_batch_filtered_set_range_device(self, d_Q, nq, n, ef, mask_set, d_mask_of, d_lo, d_hi, d_ids, d_dists,
                                                d_counts, d_stats, stream=0):
         """hnsw_search_batch_filtered_set_range_device over torch device tensors (or raw device pointers): d_mask_of

@@ -409,6 +409,34 @@ int hnsw_search_batch_filtered_set_range_device_finish(hnsw_index *h, const floa
                                                        float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats,
                                                        void *stream, uint8_t *paths /* host, nq, or NULL */);
 
+/* ---- wide filtered search: up to 1024 results and ef' up to 1024 under a filter -----------------------------------
+ * The filtered entry points above stop at n <= 64 and ef' <= 256, because their kernels keep the walk's two lists in
+ * registers; a re-ranker's pool of hundreds, a page deep into a result list or a radius query on an index with
+ * tombstones needs more.  This call has the semantics of hnsw_search_batch_filtered_set_range, word for word, for
+ * 1 <= n <= 1024 and ef' = max(ef, n, 1) <= 1024, by a second family of kernels that keeps the lists as sorted arrays
+ * in LDS and the visited set in two levels, LDS and HBM.  An id is admissible iff it is below
+ * the bound (min(set.allow_bits, hnsw_len) under a row, hnsw_len otherwise), not deleted, allowed by row mask_of[i]
+ * when the call has a set and mask_of[i] is not HNSW_MASK_NONE, and lo[i] <= label(id) <= hi[i] when the call has
+ * ranges.  set == NULL: no rows (mask_of is not read); mask_of == NULL with a set: row 0; lo == hi == NULL: no label
+ * range; both NULL: the plain search over the undeleted ids -- with nothing deleted, hnsw_search_batch's ids, distances
+ * and counters.  ids are padded with UINT32_MAX, dists with +inf; counts, stats, paths (0 graph, 1 exact, 2 exact after
+ * the visited set filled up), the per-query errors (the first is returned, every other query is answered), the cosine
+ * option, the planner per distinct (row, lo, hi) with "filter_exact_max", and A == 0 giving count 0 are those of
+ * _set_range.  Where both calls accept n and ef the outputs are equal bit for bit, paths included, unless a query
+ * fills one call's visited set and not the other's (path 0 against 2; then the ids and distances still are the exact
+ * ones on the side that overflowed).  The visited set holds three quarters of 2^"filter_wide_lds_log2" ids in LDS plus
+ * three quarters of 2^"filter_wide_hbm_log2" ids in HBM (196608 at the default); a query that needs more takes path 2.
+ * HNSW_ERR_ARG, decided before the device is touched: n == 0 or n > 1024; ef' > 1024; one of lo and hi without the
+ * other; Q or ids NULL; a set of another handle; a mask_of[i] that is neither < n_masks nor HNSW_MASK_NONE; nq > 2^31
+ * - 1.  nq == 0 is HNSW_OK.  hnsw_get_stat: "filtered_wide_calls", and the queries per path under
+ * "filtered_wide_queries_graph", "filtered_wide_queries_exact" and "filtered_wide_overflow_exact"; no other counter of
+ * the filtered searches moves.  The existing entry points keep their limits and their kernels. */
+int hnsw_search_batch_filtered_wide(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
+                                    hnsw_mask_set *set /* or NULL */, const uint32_t *mask_of /* nq, or NULL: row 0 */,
+                                    const uint32_t *lo /* nq, or NULL: no label range */, const uint32_t *hi,
+                                    uint32_t *ids, float *dists, uint32_t *counts, hnsw_query_stats *stats,
+                                    uint8_t *paths /* 0/1/2 or NULL */);
+
 /* ---- label-SET filtered search: several label ranges per query ---------------------------------------------------
  * The disjunction over the label column -- `category IN (3, 7, 12)`, `tenant IN {a, b}`, "the last hour OR pinned" --
  * without a union mask built on the host, uploaded or stored.  Every query has n_ranges = K
@@ -1499,6 +1527,11 @@ int hnsw_device_bytes(const hnsw_index *h, uint64_t *bytes);
  *   "filter_exact_grouped" 1: the batch filtered entry points run the exact-path groups of a call in three launches
  *                      for all of them instead of three per group (same results); 0, the default:
  *                      group by group; anything else is HNSW_ERR_ARG.  hnsw_search_filtered always groups
+ *   "filter_wide_lds_log2", "filter_wide_hbm_log2"
+ *                      the visited set of hnsw_search_batch_filtered_wide: log2 of the slots of its LDS level (10 to 15;
+ *                      0, the default: the launcher's choice, 12 or 13 with a second level, 15 without) and of the words
+ *                      of its HBM level per launched query (10 to 22, default 18; 0: no second level); anything else is
+ *                      HNSW_ERR_ARG.  A smaller LDS level leaves more waves on a CU, a larger one fewer trips to HBM
  *   "mask_set_cache_mb" HBM a resident mask set may hold in compacted id lists of its exact-path rows (per set,
  *                      default 64 -- a design choice, not a measurement; at the default "filter_exact_max" a list is
  *                      at most 256 KiB; 0: no list is kept) */
@@ -1532,6 +1565,8 @@ int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
  * distinct (row, lo, hi) triples they named), "filtered_ranges_calls" (hnsw_search_batch_filtered_ranges calls and
  * completed _ranges_device calls), "filtered_ranges_groups" (the distinct canonical range lists they named),
  * "filtered_one_calls" / "filtered_one_batches" (hnsw_search_filtered calls answered, the launches of their leaders);
+ * "filtered_wide_calls" (hnsw_search_batch_filtered_wide calls answered) and their queries by path:
+ * "filtered_wide_queries_graph" (0), "filtered_wide_queries_exact" (1), "filtered_wide_overflow_exact" (2);
  * partitioned search, on the handle passed as shard 0: "shard_calls"
  * (hnsw_search_batch_shards calls whose shards were all searched), "shard_merges" (the merges they launched); grouped
  * search: "grouped_calls" (hnsw_search_batch_grouped calls answered), "grouped_launches" (collapses launched,
