@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "handle.h"
+#include "row_table.h"
 #include "search_host.h"
 #include "switches.h"
 
@@ -37,7 +38,18 @@ int reject_replica(const hnsw_index *h, const char *what) {
     return HNSW_ERR_ARG;
 }
 
+// Default deny: every row reader but hx_search16_kernel takes "not QUANT8" for f32, so a handle under "rows_f16" gets no
+// snapshot through here; the entry points that kernel serves call ensure_uploaded_rows16 instead.
 int ensure_uploaded(hnsw_index *h) {
+    if (h->dev.rows_f16) {
+        set_error("this entry point is not available with rows_f16 yet (hnsw_search, hnsw_search_batch and "
+                  "hnsw_search_batch_device are)");
+        return HNSW_ERR_ARG;
+    }
+    return ensure_uploaded_rows16(h);
+}
+
+int ensure_uploaded_rows16(hnsw_index *h) {
     std::lock_guard<std::mutex> g(h->mu);
     if (is_replica(h) && !h->dev.valid) {
         set_error("replica snapshot not committed (hnsw_snapshot_commit)");
@@ -142,6 +154,28 @@ int cosine_rows(const hnsw_index *h, const float *&rows, uint64_t n, std::vector
     return HNSW_OK;
 }
 
+// The rows_f16 option on the way in, after cosine_rows: every element to the nearest binary16 value (ties to even),
+// kept as that value widened back to f32 -- the host index, the files and the oracle see an ordinary f32 index.  A NaN
+// passes through (the insert reports it as it always has); an element that rounds to +-inf refuses the call.  `keep`
+// is cosine_rows' copy when there is one.  Returns rows itself when the option is off.
+int f16_rows(const hnsw_index *h, const float *&rows, uint64_t n, std::vector<float> &keep) {
+    if (!h->dev.rows_f16 || !rows) return HNSW_OK;
+    const size_t total = (size_t)n * h->host->dim;
+    if (rows != keep.data()) keep.assign(rows, rows + total);
+    for (size_t i = 0; i < total; i++) {
+        if (keep[i] != keep[i]) continue;
+        const uint16_t hv = hx::f16_from_f32(keep[i]);
+        if ((hv & 0x7FFFu) == 0x7C00u) {
+            set_error("rows_f16: row %llu holds %g, beyond binary16's range (|x| < 65520)", (unsigned long long)(i / h->host->dim),
+                      (double)keep[i]);
+            return HNSW_ERR_ARG;
+        }
+        keep[i] = hx::f32_from_f16(hv);
+    }
+    rows = keep.data();
+    return HNSW_OK;
+}
+
 const uint64_t kNoWords = 0;  // the mask of a filtered call with allow_bits 0 (never read)
 
 // An on-device build that returns an error after it stored the points leaves some of them unconnected
@@ -228,6 +262,7 @@ int hnsw_insert_bulk_levels(hnsw_index *h, const float *rows, uint64_t n, uint32
     if (h->incomplete_build) return check_search_args(h, 1);
     std::vector<float> unit;
     if (int crc = cosine_rows(h, rows, n, unit, nb_threads)) return crc;
+    if (int frc = f16_rows(h, rows, n, unit)) return frc;
     if (h->gpu_build == 2) return device_build_guard(h, [&] { return hx::gpu_insert_bulk_full(build_target(h), rows, n, nb_threads, verbose, levels); });
     if (h->gpu_build) return device_build_guard(h, [&] { return hx::gpu_insert_bulk(build_target(h), rows, n, nb_threads, verbose, levels); });
     return h->host->insert_bulk(rows, n, nb_threads, verbose != 0, levels);
@@ -243,6 +278,7 @@ int hnsw_insert_bulk_sharded(hnsw_index *h, const float *rows, uint64_t n, uint3
     if (is_replica(h)) return reject_replica(h, "hnsw_insert_bulk_sharded");
     std::vector<float> unit;
     if (int crc = cosine_rows(h, rows, n, unit, nb_threads)) return crc;
+    if (int frc = f16_rows(h, rows, n, unit)) return frc;
     hx::ShardCtx sh{rank, world, static_cast<unsigned char *>(d_send), static_cast<unsigned char *>(d_recv), slot_bytes,
                 allgather, ctx};
     if (h->incomplete_build) return check_search_args(h, 1);
@@ -255,6 +291,7 @@ int hnsw_insert_bulk_device(hnsw_index *h, const float *rows, uint64_t n, uint32
     if (h->incomplete_build) return check_search_args(h, 1);
     std::vector<float> unit;
     if (int crc = cosine_rows(h, rows, n, unit, nb_threads)) return crc;
+    if (int frc = f16_rows(h, rows, n, unit)) return frc;
     if (h->gpu_build == 1) return device_build_guard(h, [&] { return hx::gpu_insert_bulk(build_target(h), rows, n, nb_threads, verbose, levels); });
     return device_build_guard(h, [&] { return hx::gpu_insert_bulk_full(build_target(h), rows, n, nb_threads, verbose, levels); });
 }
@@ -267,6 +304,7 @@ int hnsw_insert_vec_level(hnsw_index *h, const float *v, int level, uint32_t *ou
     if (h->incomplete_build) return check_search_args(h, 1);
     std::vector<float> unit;
     if (int crc = cosine_rows(h, v, 1, unit)) return crc;
+    if (int frc = f16_rows(h, v, 1, unit)) return frc;
     // The reference's callers search right after an insert_vec (eval_glove/src/main.rs:37-41).  When the HBM snapshot
     // was current before the insertion it is patched -- the new row and the adjacency rows the insertion touched --
     // instead of being thrown away and uploaded again by the next search (DeviceIndex::append_point).
@@ -294,6 +332,7 @@ int hnsw_import_points(hnsw_index *h, const float *rows, uint64_t n, const uint8
     if (is_replica(h)) return reject_replica(h, "hnsw_import_points");
     std::vector<float> unit;
     if (int crc = cosine_rows(h, rows, n, unit)) return crc;
+    if (int frc = f16_rows(h, rows, n, unit)) return frc;
     return h->host->import_points(rows, n, levels);
 }
 int hnsw_import_layer(hnsw_index *h, uint32_t layer, uint64_t n_nodes, const uint32_t *node_ids,
@@ -595,7 +634,7 @@ int hnsw_search_batch_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint3
     if (h->del.count)
         return hx::search_device_filtered(h, hx::Filter{}, d_Q, nq, n, ef, d_ids, d_dists, d_counts, d_stats,
                                           static_cast<hipStream_t>(stream), false, nullptr);
-    rc = ensure_uploaded(h);
+    rc = hx::ensure_uploaded_rows16(h);
     if (rc != HNSW_OK) return rc;
     hx::DeviceQueries dq;
     if ((rc = dq.prepare(h, d_Q, nq, static_cast<hipStream_t>(stream)))) return rc;
@@ -657,6 +696,10 @@ int hnsw_search_layer(hnsw_index *h, uint32_t layer, const float *q, const uint3
     if (rc != HNSW_OK) return rc;
     if (!q || !entry_ids || !out_ids || !out_count || n_entry == 0 || ef == 0) return HNSW_ERR_ARG;
     if (is_replica(h)) return reject_replica(h, "hnsw_search_layer (the seam checks its entry set against the host graph)");
+    if (h->dev.rows_f16) {
+        set_error("hnsw_search_layer is not available with rows_f16 yet");
+        return HNSW_ERR_ARG;
+    }
     if (layer >= hnsw_layer_count(h)) {
         set_error("Layer %u not found in the structure.", layer);  // layers.rs:25-30 panics
         return HNSW_ERR_ARG;
@@ -951,7 +994,7 @@ int hnsw_set_device(hnsw_index *h, int device) {
 }
 int hnsw_upload(hnsw_index *h) {
     if (!h) return HNSW_ERR_ARG;
-    return ensure_uploaded(h);
+    return hx::ensure_uploaded_rows16(h);  // (launches nothing: an f16 snapshot is as good as any)
 }
 int hnsw_set_option(hnsw_index *h, const char *key, int64_t value) { return h && key ? hx::set_option(h, key, value) : HNSW_ERR_ARG; }
 int hnsw_device_bytes(const hnsw_index *h, uint64_t *bytes) {

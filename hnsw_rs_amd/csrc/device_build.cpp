@@ -66,13 +66,17 @@ int check_build_params(const HostIndex &host) {
     set_error("on-device build supports m <= 128 and ef_construction <= 512");
     return HNSW_ERR_ARG;
 }
-// the device snapshot a build starts from: without the search-only extras (inline rows)
+// the device snapshot a build starts from: without the search-only extras (inline rows), and with f32 rows whatever
+// "rows_f16" says -- the build kernels read nothing else (their results are the same: the rows hold binary16 values)
 int upload_for_build(const BuildTarget &t, const std::function<int()> &meanwhile = {}) {
     const int saved_inline = t.dev.inline_rows;
+    const bool saved_f16 = t.dev.rows_f16;
     t.dev.inline_rows = 0;
+    t.dev.rows_f16 = false;
     t.dev.release();
     const int rc = t.dev.upload(t.host, t.device, meanwhile);
     t.dev.inline_rows = saved_inline;
+    t.dev.rows_f16 = saved_f16;
     if (rc != HNSW_OK) return rc;
     t.device = t.dev.device;
     HIP_TRY(hipSetDevice(t.dev.device));
@@ -1012,7 +1016,10 @@ int gpu_insert_bulk_full(const BuildTarget &t, const float *rows, uint64_t n, ui
     host.version++;
     // the adjacency in HBM is the graph just read back: patch the few rows changed since and keep the snapshot
     // (a build of tens of GB is otherwise followed by an upload of the same tens of GB)
-    if (device_is_the_graph && !sw::reupload())
+    // (under "rows_f16" the build's f32 snapshot is dropped instead: the next search uploads the f16 one)
+    if (t.dev.rows_f16)
+        t.dev.release();
+    else if (device_is_the_graph && !sw::reupload())
         (void)t.dev.refresh_rows(host, touched);
     return HNSW_OK;
 }

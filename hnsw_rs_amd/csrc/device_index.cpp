@@ -3,6 +3,7 @@
 
 #include "device_index.h"
 #include "hip_util.h"
+#include "row_table.h"
 #include "switches.h"
 
 #include <algorithm>
@@ -22,6 +23,19 @@ uint32_t quant_half_bytes(uint32_t dim) {
     return (need + 15) & ~15u;
 }
 uint32_t f32_row_stride(uint32_t dim) { return (4 * dim + 15) & ~15u; }
+uint32_t f16_row_stride(uint32_t dim) { return (2 * dim + 15) & ~15u; }
+
+// d f32 values narrowed to binary16 at o (the rows_f16 layout); false when one of them is not a binary16 value
+static bool pack_f16_row(const float *x, uint32_t d, uint8_t *o) {
+    bool exact = true;
+    for (uint32_t e = 0; e < d; e++) {
+        const uint16_t hv = f16_from_f32(x[e]);
+        memcpy(o + 2 * (size_t)e, &hv, 2);
+        const float back = f32_from_f16(hv);
+        exact &= memcmp(&x[e], &back, 4) == 0;  // bit for bit: -0.0 stays -0.0, a NaN never passes
+    }
+    return exact;
+}
 uint32_t adj_stride(uint64_t cap, uint32_t min_slots) {
     uint32_t s = min_slots;
     while (s < cap) s <<= 1;
@@ -271,6 +285,8 @@ bool DeviceIndex::append_point(const HostIndex &idx, NodeID id, const std::vecto
                 for (uint32_t ch = 0; ch < nch; ch++) memcpy(oh + 8 + 4 * ch, c + 8 * ch + 4 * h, 4);
                 if (h == 0) memcpy(oh + 8 + 4 * nch, c + 8 * nch, rem);
             }
+        } else if (view.rows16) {
+            if (!pack_f16_row(&idx.vals[(size_t)id * idx.dim], idx.dim, o)) return false;  // (the next upload says why)
         } else {
             memcpy(o, &idx.vals[(size_t)id * idx.dim], 4 * (size_t)idx.dim);
         }
@@ -565,13 +581,23 @@ int DeviceIndex::upload(const HostIndex &idx, int dev, const std::function<int()
     v.rem = idx.dim % 8;
     const bool q8 = idx.kind == HNSW_VEC_QUANT8;
     v.half_bytes = q8 ? quant_half_bytes(idx.dim) : 0;
-    v.row_stride = q8 ? 2 * v.half_bytes : f32_row_stride(idx.dim);
+    const bool r16 = rows_f16 && !q8;
+    v.rows16 = r16 ? 1u : 0u;
+    v.row_stride = q8 ? 2 * v.half_bytes : r16 ? f16_row_stride(idx.dim) : f32_row_stride(idx.dim);
     v.S0 = adj_stride(idx.layer_m(0), 32);
     v.S1 = adj_stride(idx.params.m, 8);
 
     // ---- one vector row / one adjacency row in the device layout ----
+    std::atomic<uint64_t> not_f16{UINT64_MAX};  // rows_f16: the lowest row that holds a value binary16 does not
     auto pack_vector = [&](uint64_t i, uint8_t *o) {
-        if (q8) {
+        if (r16) {
+            memset(o, 0, v.row_stride);
+            if (!pack_f16_row(&idx.vals[i * idx.dim], idx.dim, o)) {
+                uint64_t cur = not_f16.load();
+                while (i < cur && !not_f16.compare_exchange_weak(cur, i)) {
+                }
+            }
+        } else if (q8) {
             const uint32_t d = idx.dim, nch = d / 8, rem = d % 8, half = v.half_bytes;
             const uint8_t *c = &idx.codes[i * d];
             memset(o, 0, v.row_stride);
@@ -615,6 +641,11 @@ int DeviceIndex::upload(const HostIndex &idx, int dev, const std::function<int()
             if (want_fat) memcpy(&rows_h[lo * v.row_stride], dst, (hi - lo) * v.row_stride);
         });
         if (rc != HNSW_OK) return rc;
+        if (not_f16.load() != UINT64_MAX) {
+            set_error("rows_f16: row %llu holds a value that is not a binary16 value; the rows were not stored under the option",
+                      (unsigned long long)not_f16.load());
+            return HNSW_ERR_ARG;
+        }
         side.join();
         if (side.rc != HNSW_OK) {
             set_error("%s", side.err.c_str());

@@ -1,5 +1,5 @@
 // device_index.h -- the HBM-resident snapshot of a HostIndex and the launchers of the kernels (search_kernels.hip,
-// search_lean.hip, build_kernels.hip, exact_scan.hip, brute_mfma.hip, build_sort.hip, patch.hip, metric.hip).  gfx950 only.
+// search_lean.hip, search_rows16.hip, build_kernels.hip, exact_scan.hip, brute_mfma.hip, build_sort.hip, patch.hip, metric.hip).  gfx950 only.
 //
 // HBM layout (one allocation per array, all read-only during search):
 //
@@ -12,6 +12,11 @@
 //             (quant.rs:14-37: sum j takes elements 8c + j) from contiguous 16-byte pieces.
 //             d = 100: half = 8 + 48 + 4 -> 64 B, row = 128 B = one cache line.
 //             F32 (reference FullVec, vectors/src/full.rs): d floats, padded to 16 B.
+//             F32 under the option "rows_f16" (DevView::rows16 = 1): d IEEE binary16 values, element
+//             e at byte 2 e, zero-padded to 16 B -- row_stride = f16_row_stride(d) = 2 d rounded up to 16.  Every value
+//             is the host's f32 element exactly (upload() refuses a row that does not survive the round trip).  No
+//             inline-rows copy.  ONLY hx_search16_kernel (search_rows16.hip) reads such rows: every other kernel takes
+//             "not QUANT8" for f32, and ensure_uploaded keeps such a snapshot from them.
 //   adj0      N x S0 u32: layer-0 adjacency in fixed-stride rows (S0 = pow2 >= max(2m, 32), 128 B at
 //             m = 16), row index = node id, neighbour ids ascending, empty slots 0xFFFFFFFF behind them.
 //   adj_up    upper-layer rows, S1 = pow2 >= max(m, 8) slots each; the rows of one node for
@@ -67,7 +72,7 @@ struct DevView {  // kernel argument, passed by value
     uint32_t nch4, rem;   // QUANT8: 4 * (dim / 8), dim % 8
     uint32_t nb_layers, ep;
     int32_t kind;
-    uint32_t _pad;
+    uint32_t rows16;      // 1: an F32 index whose rows are stored as binary16 (layout above), else 0
 };
 
 struct SearchArgs {
@@ -193,6 +198,8 @@ class DeviceIndex {
     int upload(const HostIndex &idx, int device, const std::function<int()> &meanwhile = {});
     // inline-rows layout: -1 = auto (build it when it fits fat_budget_bytes), 0 = never, 1 = always
     int inline_rows = -1;
+    // option "rows_f16": upload() stores the rows of an F32 index as binary16 (layout above) and builds no inline rows
+    bool rows_f16 = false;
     uint64_t fat_budget_bytes = 64ull << 30;
     void release();
     bool current(const HostIndex &idx) const { return valid && (replica || version_seen == idx.version); }
@@ -252,6 +259,7 @@ class DeviceIndex {
 // row packing helpers shared by upload and tests
 uint32_t quant_half_bytes(uint32_t dim);
 uint32_t f32_row_stride(uint32_t dim);
+uint32_t f16_row_stride(uint32_t dim);
 uint32_t adj_stride(uint64_t cap, uint32_t min_slots);
 
 // Launch the search kernel for `nblocks` queries on `stream`.  slots_log2 = log2 of the visited
@@ -262,6 +270,10 @@ int launch_search(const DevView &v, const SearchArgs &a, uint32_t nblocks, uint3
 // f32 rows; launch_search routes to it when it applies
 bool lean_applicable(const DevView &v, const SearchArgs &a, uint32_t ef_max);
 int launch_lean(const DevView &v, const SearchArgs &a, uint32_t nblocks, uint32_t slots_log2, hipStream_t stream);
+// the same search over a view with f16 rows (search_rows16.hip; launch_search routes to it): ef_max <= 1024, else
+// HNSW_ERR_ARG
+int launch_search_rows16(const DevView &v, const SearchArgs &a, uint32_t nblocks, uint32_t slots_log2, hipStream_t stream,
+                         uint32_t ef_max);
 uint32_t default_slots_log2(uint32_t ef);
 uint32_t default_slots_log2(uint32_t ef, uint32_t s0);
 uint32_t max_slots_log2(uint32_t ef);

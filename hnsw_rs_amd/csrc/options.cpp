@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "handle.h"
+#include "row_table.h"
 
 namespace hx {
 
@@ -36,7 +37,30 @@ struct Option {
     int flags;
     void (*store)(hnsw_index &h, int64_t value);
     void (*copy)(hnsw_index &to, const hnsw_index &from);  // the stored field itself, not a value parsed again
+    int (*admit)(const hnsw_index &h, int64_t value) = nullptr;  // optional: what the handle's state has to say (sets the error)
 };
+
+// "rows_f16" (DESIGN.md section 36): only an f32 index with a host copy can narrow its rows, and only while every stored
+// element is a binary16 value already -- which lets a loaded index through whose rows were stored under the option (the
+// reference's file format has no field for it)
+int rows_f16_admissible(const hnsw_index &h, int64_t value) {
+    if (value == 0) return HNSW_OK;
+    if (is_replica(&h)) return reject_replica(&h, "rows_f16");
+    if (h.host->kind != HNSW_VEC_F32) {
+        set_error("rows_f16 needs an HNSW_VEC_F32 index");
+        return HNSW_ERR_ARG;
+    }
+    const auto &x = h.host->vals;
+    for (size_t i = 0; i < x.size(); i++) {
+        const float back = f32_from_f16(f16_from_f32(x[i]));
+        if (memcmp(&x[i], &back, 4) != 0) {
+            set_error("rows_f16: point %llu is stored with a value that is not a binary16 value; set the option before the first insert",
+                      (unsigned long long)(i / h.host->dim));
+            return HNSW_ERR_ARG;
+        }
+    }
+    return HNSW_OK;
+}
 // FIELD: the member of the handle that holds the option; STORED: what `value` becomes in it
 #define HX_OPTION(NAME, BOUND, CLAMP, FLAGS, FIELD, STORED)                            \
     {NAME, BOUND, CLAMP, FLAGS, [](hnsw_index &h, int64_t value) { h.FIELD = STORED; }, \
@@ -48,6 +72,9 @@ const Option kOptions[] = {
     // points already stored stay as they are: set it before the first insert (or on a loaded index whose
     // rows were stored under it -- the reference's file format has no field for a metric)
     HX_OPTION("metric_cosine", ANY, NO_CLAMP, 0, cosine, value != 0),
+    // rows rounded to binary16 as they are inserted, stored as binary16 in HBM (an extension; capi.cpp rounds)
+    {"rows_f16", ZERO_OR_ONE, NO_CLAMP, RELEASES, [](hnsw_index &h, int64_t value) { h.dev.rows_f16 = value != 0; },
+     [](hnsw_index &to, const hnsw_index &from) { to.dev.rows_f16 = from.dev.rows_f16; }, rows_f16_admissible},
     HX_OPTION("filter_exact_max", ANY, NO_CLAMP, 0, filter_exact_max, value),
     HX_OPTION("filter_exact_grouped", ZERO_OR_ONE, NO_CLAMP, 0, filter_exact_grouped, (int)value),
     HX_OPTION("filter_wide_lds_log2", WIDE_LDS_LOG2, NO_CLAMP, 0, filter_wide_lds_log2, (int)value),
@@ -68,6 +95,7 @@ struct Stat {
 #define HX_STAT(NAME, VALUE) {NAME, [](const hnsw_index &h) -> uint64_t { return VALUE; }}
 const Stat kStats[] = {
     HX_STAT("uploads", h.n_uploads),
+    HX_STAT("snapshot_bytes", h.dev.bytes),
     HX_STAT("point_patches", h.n_point_patches),
     HX_STAT("patch_fallbacks", h.n_patch_fallbacks),
     HX_STAT("build_points", h.build.points),
@@ -172,6 +200,8 @@ int set_option(hnsw_index *h, const char *key, int64_t value) {
         set_error("%s %s", key, why);
         return HNSW_ERR_ARG;
     }
+    if (o->admit)
+        if (int rc = o->admit(*h, value)) return rc;
     value = std::min(value, o->clamp);
     std::unique_lock<SpinLock> cg(h->co.mu, std::defer_lock);
     if (o->flags & CO_LOCKED) cg.lock();

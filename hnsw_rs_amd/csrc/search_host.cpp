@@ -107,7 +107,7 @@ int search_staged(hnsw_index *h, SearchScratch &s, const HostSearchPlan &p, Sear
 
 int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, uint32_t *ids, float *dists,
                 uint32_t *counts, hnsw_query_stats *stats, const uint32_t *entries) {
-    int rc = ensure_uploaded(h);
+    int rc = ensure_uploaded_rows16(h);
     if (rc != HNSW_OK) return rc;
     const uint32_t d = h->dev.view.dim;
     HostSearchPlan p = plan_host_search(nq, d, a_host.n, entries ? a_host.n_entry : 0);
@@ -127,7 +127,7 @@ int search_host(hnsw_index *h, SearchArgs a_host, const float *Q, uint64_t nq, u
 
 int search_device_finish(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_t n, uint32_t ef, uint32_t *d_ids,
                          float *d_dists, uint32_t *d_counts, hnsw_query_stats *d_stats, hipStream_t stream) {
-    int rc = ensure_uploaded(h);
+    int rc = ensure_uploaded_rows16(h);
     if (rc != HNSW_OK) return rc;
     const DevView &v = h->dev.view;
     const size_t st_bytes = nq * sizeof(hnsw_query_stats);

@@ -1101,6 +1101,7 @@ int launch_search(const DevView &v, const SearchArgs &a_in, uint32_t nblocks, ui
     if (a.layer_hi > a.layer_lo) ef_max = std::max(ef_max, a.ef_upper);
     if (a.entries) ef_max = std::max(ef_max, a.n_entry);
     if (slots_log2 == 0) slots_log2 = default_slots_log2(ef_max, v.S0);
+    if (v.rows16) return launch_search_rows16(v, a, nblocks, slots_log2, stream, ef_max);  // f16 rows: no kernel below reads them
     if (lean_applicable(v, a, ef_max)) return launch_lean(v, a, nblocks, slots_log2, stream);
     if (ef_max > 64 * HX_MAX_R) {
         // beyond 512 entries: the any-dimension kernel with sixteen list registers per lane (ef <= 1024;

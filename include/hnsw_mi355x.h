@@ -1513,6 +1513,16 @@ int hnsw_device_bytes(const hnsw_index *h, uint64_t *bytes);
  *                      of the unit vectors (d^2 = 2 - 2 cos); hnsw_get_vector returns the stored unit rows; a
  *                      zero vector is HNSW_ERR_NAN_INPUT.  Set it before the first insert; save / load do not
  *                      carry it (the reference's file format has no such field): set it again after a load.
+ *   "rows_f16"         0 (default) / 1, on an HNSW_VEC_F32 handle.  AN EXTENSION.  With 1, every
+ *                      element of every inserted row is rounded to the nearest IEEE binary16 value (ties to even; after
+ *                      the cosine normalisation when both are set) and kept on the host as that value widened back to
+ *                      f32, and the HBM snapshot stores 2 bytes per element.  The index IS the plain f32 index over
+ *                      X.astype(float16).astype(float32): same graph, ids, distance bits, counters and files.  An element
+ *                      that rounds to +-inf (|x| >= 65520) is HNSW_ERR_ARG, a NaN stays HNSW_ERR_NAN_INPUT.  Refused with
+ *                      HNSW_ERR_ARG on an 8-bit handle, on a replica, and once a stored element is not a binary16 value
+ *                      -- so it can be set again after a load (the file has no field for it).  Served under it:
+ *                      hnsw_search, hnsw_search_batch, hnsw_search_batch_device(_finish), ef <= 1024, nothing deleted;
+ *                      every other entry point that needs the snapshot returns HNSW_ERR_ARG.  Queries stay f32
  *   "gpu_build_batch_max", "gpu_build_batch_div"
  *                      the on-device build inserts min(max, connected / div) points at a time (defaults
  *                      8192 and 8; max is capped at 32768); 256 and 64 stand closer to the reference's
@@ -1536,7 +1546,8 @@ int hnsw_device_bytes(const hnsw_index *h, uint64_t *bytes);
  *                      default 64 -- a design choice, not a measurement; at the default "filter_exact_max" a list is
  *                      at most 256 KiB; 0: no list is kept) */
 int hnsw_set_option(hnsw_index *h, const char *key, int64_t value);
-/* counters of the handle: "uploads" (whole-snapshot uploads), "point_patches" (insert_vec calls that patched the
+/* counters of the handle: "uploads" (whole-snapshot uploads), "snapshot_bytes" (HBM the snapshot holds now; 0: none),
+ * "point_patches" (insert_vec calls that patched the
  * live snapshot), "patch_fallbacks" (those that could not: the next search uploads), "coalesced_batches" /
  * "coalesced_queries" / "coalesced_max_batch" (launches made for hnsw_search calls, the calls they answered, the
  * largest batch), "coalesce_ns_window" / "_turn" / "_gpu" / "_handout" (where the batch leaders' time went);
