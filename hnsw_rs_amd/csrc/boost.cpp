@@ -1,10 +1,11 @@
 // boost.cpp -- boosted search (include/hnsw_mi355x.h, "boosted search"): a candidate list re-ranked by a weighted sum of
 // its distances and of per-id attributes kept in a row table in HBM, on the device, and a search answered from the index
-// and then ranked that way.  Host logic only; the boost is hx_distance_kernel's ninth source form (exact_scan.hip), the
+// and then ranked that way.  Host logic only; the boost is hx_distance_kernel's ninth source form (form_boost.inc), the
 // table row_table.h, the candidate stage around it lists_host.h.
 
 #include <algorithm>
 
+#include "list_forms.h"
 #include "lists_host.h"
 #include "row_table.h"
 

@@ -1,8 +1,9 @@
 // diverse.cpp -- diversified search (include/hnsw_mi355x.h, "diversified search"): the re-ranking of candidate lists by
 // maximal marginal relevance on the device, and a search answered as hits that are near the query and not near each
-// other.  Host logic only; the selection is hx_distance_kernel's second source form (exact_scan.hip), the candidate
-// stage around it lists_host.h.
+// other.  Host logic only; the selection is hx_distance_kernel's second source form (form_diversify.inc), the
+// candidate stage around it lists_host.h.
 
+#include "list_forms.h"
 #include "lists_host.h"
 
 using hx::set_error;

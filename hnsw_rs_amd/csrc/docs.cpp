@@ -1,11 +1,12 @@
 // docs.cpp -- exact document scoring (include/hnsw_mi355x.h, "exact document scoring"): the documents a list names -- the
 // undeleted rows that share a label -- scored against a query's vectors by summed min distance over EVERY stored row of
 // the document, and a late-interaction search whose returned documents are completed that way.  Host logic only; the
-// scoring is hx_distance_kernel's seventh source form (exact_scan.hip), the document index it walks the HBM copy of
+// scoring is hx_distance_kernel's seventh source form (form_late.inc), the document index it walks the HBM copy of
 // LabelColumn::sorted (labels.h), the candidate stage around it lists_host.h.
 
 #include <algorithm>
 
+#include "list_forms.h"
 #include "lists_host.h"
 
 using hx::set_error;

@@ -1,8 +1,9 @@
 // from_rows.cpp -- search from stored rows (include/hnsw_mi355x.h, "search from stored rows"): query rows composed out
 // of stored rows on the device, the sources taken back out of the result lists there, and a search answered from ids and
-// weighted ids.  Host logic only; the compose is hx_distance_kernel's third source form (exact_scan.hip), the drop
+// weighted ids.  Host logic only; the compose is hx_distance_kernel's third source form (form_compose.inc), the drop
 // hx_filt_merge_kernel's fifth (search_filtered.hip), the candidate stage between them lists_host.h.
 
+#include "list_forms.h"
 #include "lists_host.h"
 #include "rerun.h"
 

@@ -1,10 +1,11 @@
 // hybrid.cpp -- hybrid search (include/hnsw_mi355x.h, "hybrid search"): the rank fusion of the index's own hits with
 // external ranked lists on the device, under the handle's deletions, mask rows and label ranges, and a search answered by
-// it.  Host logic only; the fusion is hx_distance_kernel's eighth source form (exact_scan.hip), the candidate stage around
-// it lists_host.h.
+// it.  Host logic only; the fusion is hx_distance_kernel's eighth source form (form_fuse_ranked.inc), the candidate
+// stage around it lists_host.h.
 
 #include <mutex>
 
+#include "list_forms.h"
 #include "lists_host.h"
 
 using hx::set_error;

@@ -1,10 +1,11 @@
 // late.cpp -- late-interaction search (include/hnsw_mi355x.h, "late-interaction search"): a query's per-vector candidate
 // lists scored as documents -- the candidates that share a label -- by summed min distance on the device, and a search
 // answered by its nearest documents.  Host logic only; the scoring is hx_distance_kernel's fifth source form
-// (exact_scan.hip), the candidate stage around it lists_host.h.
+// (form_late.inc), the candidate stage around it lists_host.h.
 
 #include <algorithm>
 
+#include "list_forms.h"
 #include "lists_host.h"
 
 using hx::set_error;

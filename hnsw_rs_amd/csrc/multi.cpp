@@ -1,9 +1,10 @@
 // multi.cpp -- multi-vector search (include/hnsw_mi355x.h, "multi-vector search"): the fusion of a query's per-vector
 // candidate lists on the device, and a search answered from several vectors per query.  Host logic only; the fusion is
-// hx_distance_kernel's fourth source form (exact_scan.hip), the candidate stage around it lists_host.h.
+// hx_distance_kernel's fourth source form (form_fuse_lists.inc), the candidate stage around it lists_host.h.
 
 #include <algorithm>
 
+#include "list_forms.h"
 #include "lists_host.h"
 
 using hx::set_error;

@@ -1,11 +1,12 @@
 // refine.cpp -- refined search (include/hnsw_mi355x.h, "refined search"): a candidate list re-scored against full rows
 // kept in HBM and cut to the nearest, on the device, and a search answered from the index's own rows and then ranked by
-// the full ones.  Host logic only; the refinement is hx_distance_kernel's sixth source form (exact_scan.hip), the table
+// the full ones.  Host logic only; the refinement is hx_distance_kernel's sixth source form (form_refine.inc), the table
 // row_table.h, the candidate stage around it lists_host.h.
 
 #include <algorithm>
 #include <cstring>
 
+#include "list_forms.h"
 #include "lists_host.h"
 #include "row_table.h"
 

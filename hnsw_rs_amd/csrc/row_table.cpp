@@ -1,6 +1,6 @@
 // row_table.cpp -- hnsw_row_table (row_table.h): the C entry points that manage a table of full rows in HBM, and the
 // host's binary16 rounding, and the table's file.  Host logic only; the refinement and the boost that read the table are
-// refine.cpp's, boost.cpp's and exact_scan.hip's.
+// refine.cpp's, boost.cpp's, form_refine.inc's and form_boost.inc's.
 
 #include "row_table.h"
 
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "handle.h"
+#include "list_forms.h"
 
 using hx::set_error;
 

@@ -1,7 +1,7 @@
 // row_table.h -- hnsw_row_table (include/hnsw_mi355x.h, "refined search"): a table of full rows that lives with a
 // handle, in HBM ONLY: rows x full_dim elements of f32 or IEEE binary16, row id = index id, what the refinement
-// (hx_distance_kernel's sixth source form, exact_scan.hip) scores a candidate list against.  The host keeps no copy: the
-// caller owns the full rows.  The table is not saved by hnsw_save, not cloned by hnsw_clone and not part of the snapshot
+// (hx_distance_kernel's sixth source form, form_refine.inc) scores a candidate list against.  The host keeps no copy:
+// the caller owns the full rows.  The table is not saved by hnsw_save, not cloned by hnsw_clone and not part of the snapshot
 // exchange; hnsw_row_table_save / _load carry it in a file of its own.  With full_dim <= 32 it is the attribute table of
 // boosted search (the kernel's ninth form).  Host logic only (row_table.cpp).
 //

@@ -9,7 +9,6 @@ import os
 import re
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +17,7 @@ import hnsw_rs_amd as H
 from hnsw_rs_amd import _lib
 from oracle import oracle_py as O
 from tests import boost_cases as BC
+from tests.kernel_resources import resource_usage
 from tests.util import rand_vectors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -399,7 +399,7 @@ def test_corrupt_files_are_io_errors_before_any_device(tmp_path):
 
 # ---- the kernel that carries the new form ------------------------------------------------------------------------------
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_distance_kernel_carries_the_boost_without_scratch_spills_or_lost_occupancy(tmp_path):
+def test_distance_kernel_carries_the_boost_without_scratch_spills_or_lost_occupancy():
     """exact_scan.hip compiled for gfx950 with the Makefile's flags: the boost is a source form of hx_distance_kernel,
     selected by a field of its own that launch_boost alone sets and looked at before every other form; the kernel's two
     instantiations stay the only ones, and run without scratch, without spilled vector registers and at the occupancy
@@ -410,20 +410,7 @@ def test_distance_kernel_carries_the_boost_without_scratch_spills_or_lost_occupa
     assert text.index("if (dv.boost)") < text.index("if (dv.hybrid)"), "looked at before every other form"
     assert len(re.findall(r"\bd\.boost = ", text)) == 1 and "d.boost = 1 + d.mode" in text, "one launcher sets the selector"
     assert len(re.findall(r"__global__", text)) == 2, "no kernel was added beside the two"
-    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950",
-           "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / "exact_scan.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    kernels, _ = resource_usage("exact_scan.hip")
     seam = {k: v for k, v in kernels.items() if "hx_distance_kernel" in k}
     assert len(seam) == 2 and sum("ILi0E" in k for k in seam) == 1 and sum("ILi1E" in k for k in seam) == 1, sorted(kernels)
     for name, r in seam.items():

@@ -5,7 +5,6 @@ import os
 import re
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import pytest
 import hnsw_rs_amd as H
 from hnsw_rs_amd import _lib
 from oracle import oracle_py as O
+from tests.kernel_resources import resource_usage
 from tests.util import rand_vectors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -156,22 +156,8 @@ def test_deletion_entry_points_are_declared_and_bound():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_mask_scatter_kernel_has_no_scratch_or_spills(tmp_path):
-    src = os.path.join(ROOT, "hnsw_rs_amd", "csrc", "deleted_mask.hip")
-    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950",
-           "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / "deleted_mask.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+def test_mask_scatter_kernel_has_no_scratch_or_spills():
+    kernels, _ = resource_usage("deleted_mask.hip")
     scatter = {k: v for k, v in kernels.items() if "hx_deleted_scatter_kernel" in k}
     assert len(scatter) == 1, sorted(kernels)
     for name, r in scatter.items():

@@ -8,7 +8,6 @@ import ctypes as C
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,6 +18,7 @@ from oracle import oracle_py as O
 from tests import docs_cases as DC
 from tests import multi_cases as MC
 from tests.test_late_host import c_type_of, explicit_dist
+from tests.kernel_resources import resource_usage
 from tests.util import rand_vectors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -309,29 +309,17 @@ def test_symbols_are_exported_and_prototypes_match_the_binding():
 
 # ---- the kernel that carries the new form ------------------------------------------------------------------------------
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_distance_kernel_carries_the_document_scoring_without_scratch_or_vgpr_spills(tmp_path):
+def test_distance_kernel_carries_the_document_scoring_without_scratch_or_vgpr_spills():
     """exact_scan.hip compiled for gfx950 with the Makefile's flags: the document scoring is a source form of
-    hx_distance_kernel that shares the late interaction's pass loop -- ONE call site of the row distance in it -- whose two
-    instantiations stay the only ones and run without scratch and without spilled vector registers"""
+    hx_distance_kernel (form_late.inc) that shares the late interaction's pass loop -- ONE call site of the row distance
+    in it -- whose two instantiations stay the only ones and run without scratch and without spilled vector registers"""
     src = os.path.join(ROOT, "hnsw_rs_amd", "csrc", "exact_scan.hip")
     text = open(src).read()
     assert "dv.docs" in text and text.count("late_interaction<KIND>(") == 1, "the scoring is late_interaction's other half"
-    body = text[text.index("void late_interaction("):text.index("The kernel's sixth form")]
+    form = open(os.path.join(ROOT, "hnsw_rs_amd", "csrc", "form_late.inc")).read()
+    body = form[form.index("void late_interaction("):]  # (to the end of the form's file)
     assert body.count("dist_any_dim<KIND>(") == 1 and "d.doc_keys" in body
-    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950",
-           "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / "exact_scan.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+    kernels, _ = resource_usage("exact_scan.hip")
     seam = {k: v for k, v in kernels.items() if "hx_distance_kernel" in k}
     assert len(seam) == 2 and sum("ILi0E" in k for k in seam) == 1 and sum("ILi1E" in k for k in seam) == 1, sorted(kernels)
     for name, r in seam.items():

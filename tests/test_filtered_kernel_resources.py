@@ -1,33 +1,15 @@
 """The filtered-search kernels (search_filtered.hip) compiled for gfx950: every instantiation runs without scratch
 and without spilled vector registers (no GPU needed: hipcc cross-compiles)."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from tests.kernel_resources import HIPCC, resource_usage
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_filtered_kernels_have_no_scratch_or_spills(tmp_path):
-    src = os.path.join(ROOT, "hnsw_rs_amd", "csrc", "search_filtered.hip")
-    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950",
-           "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / "filtered.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+def test_filtered_kernels_have_no_scratch_or_spills():
+    kernels, _ = resource_usage("search_filtered.hip")
     graph = {k: v for k, v in kernels.items() if "hx_filt_graph_kernel" in k}
     # f32 100d, f32 128d, quant8 100d and the any-dimension forms of both kinds, at one, two and four list registers
     assert len(graph) == 15, sorted(kernels)

@@ -7,7 +7,6 @@ import ctypes as C
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ import pytest
 import hnsw_rs_amd as H
 from hnsw_rs_amd import _lib
 from oracle import oracle_py as O
+from tests.kernel_resources import resource_usage
 from tests.util import rand_vectors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -252,7 +252,7 @@ def test_symbols_are_exported_and_prototypes_match_the_binding():
 
 # ---- the kernels' resources ------------------------------------------------------------------------------------------
 # Occupancy [waves/SIMD] of every instantiation of search_filtered.hip as compiled BEFORE the graph kernel read a mask
-# row next to a label range (the same flags, -Rpass-analysis=kernel-resource-usage): the floor for every later compile.
+# row next to a label range (the same flags: kernel_resources.py): the floor for every later compile.
 # Keys: the template arguments as they are mangled -- <KIND, P, DS, R> of hx_filt_graph_kernel (KIND 1: f32, 0: 8-bit),
 # <KIND> of hx_filt_scan_kernel.
 OCCUPANCY_BEFORE = {
@@ -271,22 +271,9 @@ OCCUPANCY_BEFORE = {
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_filtered_kernels_keep_their_occupancy(tmp_path):
-    src = os.path.join(ROOT, "hnsw_rs_amd", "csrc", "search_filtered.hip")
-    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950",
-           "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / "filtered.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    occ, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            continue
-        m = re.search(r"remark:\s+Occupancy \[waves/SIMD\]: (\d+)", line)
-        if m and cur is not None and "hx_filt_" in cur:
-            occ[cur] = int(m.group(1))
+def test_filtered_kernels_keep_their_occupancy():
+    kernels, _ = resource_usage("search_filtered.hip")
+    occ = {k: r["Occupancy"] for k, r in kernels.items() if "hx_filt_" in k and "Occupancy" in r}
     assert len(occ) == len(OCCUPANCY_BEFORE) == 19, sorted(occ)  # no new kernel, no new instantiation
     for tag, floor in OCCUPANCY_BEFORE.items():
         names = [k for k in occ if tag in k]

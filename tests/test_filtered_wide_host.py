@@ -5,7 +5,6 @@ import ctypes as C
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import pytest
 import hnsw_rs_amd as H
 from hnsw_rs_amd import _lib
 from oracle import oracle_py as O
+from tests.kernel_resources import resource_usage
 from tests.util import rand_vectors
 
 NQ, D = 3, 8
@@ -59,17 +59,11 @@ def test_the_counters_exist_and_start_at_zero(index):
 
 
 @pytest.mark.skipif(not os.path.exists(shutil.which("hipcc") or "/opt/rocm/bin/hipcc"), reason="hipcc not available")
-def test_wide_kernels_have_no_scratch_or_spills(tmp_path):
+def test_wide_kernels_have_no_scratch_or_spills():
     """search_filtered_wide.hip compiled for gfx950 with the Makefile's flags: five forms of the graph kernel, the scan
     for both kinds and the merge, none with scratch or spilled vector registers"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [shutil.which("hipcc") or "/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-           "--offload-arch=gfx950", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
-           "-I" + os.path.join(root, "include"), "-c", os.path.join(root, "hnsw_rs_amd", "csrc", "search_filtered_wide.hip"),
-           "-o", str(tmp_path / "wide.o"), "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    blocks = re.split(r"Function Name: ", out.stderr)[1:]
+    _, stderr = resource_usage("search_filtered_wide.hip", ("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"))
+    blocks = re.split(r"Function Name: ", stderr)[1:]
     assert sum("hx_filt_wide_kernel" in b for b in blocks) == 5 and len(blocks) == 8, [b.split()[0] for b in blocks]
     for b in blocks:
         assert int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1)) == 0, b

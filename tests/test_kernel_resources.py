@@ -4,32 +4,15 @@ v_accvgpr_read per element in its distance chain, because its row registers were
 consumed under another; this test keeps that from coming back unnoticed."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from tests.kernel_resources import HIPCC, resource_usage
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_lean_kernels_fit_two_waves_per_simd_without_agprs_or_scratch(tmp_path):
-    src = os.path.join(ROOT, "hnsw_rs_amd", "csrc", "search_lean.hip")
-    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950",
-           "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / "lean.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+def test_lean_kernels_fit_two_waves_per_simd_without_agprs_or_scratch():
+    kernels, _ = resource_usage("search_lean.hip")
     timed = {k: v for k, v in kernels.items() if "hx_lean_f32_kernel" in k or "hx_lean_q8_kernel" in k}
     # f32 100d and quant8: one register, head + tail, interleaved four (ef 129..256); f32 128d (cooperative gather): one
     # register and head + tail at two stage depths each, interleaved four

@@ -5,16 +5,12 @@ fit two waves per SIMD (the method of tests/test_kernel_resources.py: hipcc cros
 kernel's registers)."""
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import upper_walk as UW
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from tests.kernel_resources import HIPCC, resource_usage
 
 
 KINDS = (UW.F32, UW.QUANT8)
@@ -91,22 +87,8 @@ def test_product_import_refuses_a_neighbour_below_its_layer():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_walk_ahead_kernels_fit_two_waves_per_simd(tmp_path):
-    src = os.path.join(ROOT, "hnsw_rs_amd", "csrc", "search_lean.hip")
-    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950",
-           "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / "lean.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
+def test_walk_ahead_kernels_fit_two_waves_per_simd():
+    kernels, _ = resource_usage("search_lean.hip")
     # <100, Lst<1>> and <100, LstHT> of the f32 kernel, Lst<1> and LstHT of the quant8 kernel
     want = [r"hx_lean_f32_kernelILi100ENS0_3LstILi1EEE", r"hx_lean_f32_kernelILi100ENS0_5LstHTE",
             r"hx_lean_q8_kernelINS0_3LstILi1EEE", r"hx_lean_q8_kernelINS0_5LstHTE"]
