@@ -38,12 +38,14 @@ int reject_replica(const hnsw_index *h, const char *what) {
     return HNSW_ERR_ARG;
 }
 
-// Default deny: every row reader but hx_search16_kernel takes "not QUANT8" for f32, so a handle under "rows_f16" gets no
-// snapshot through here; the entry points that kernel serves call ensure_uploaded_rows16 instead.
+// Default deny: every row reader but hx_search16_kernel and the two hx_filt16 kernels takes "not QUANT8" for f32, so a
+// handle under "rows_f16" gets no snapshot through here; the entry points those kernels serve call ensure_uploaded_rows16
+// instead.
 int ensure_uploaded(hnsw_index *h) {
     if (h->dev.rows_f16) {
-        set_error("this entry point is not available with rows_f16 yet (hnsw_search, hnsw_search_batch and "
-                  "hnsw_search_batch_device are)");
+        set_error("this entry point is not available with rows_f16 yet (hnsw_search, hnsw_search_batch, "
+                  "hnsw_search_batch_device, hnsw_search_filtered and hnsw_search_batch_filtered_multi, _set, _range, "
+                  "_set_range and _ranges with their _device forms are, with or without deleted ids)");
         return HNSW_ERR_ARG;
     }
     return ensure_uploaded_rows16(h);
@@ -447,6 +449,13 @@ static int filtered_device(hnsw_index *h, const float *d_Q, uint64_t nq, uint32_
 int hnsw_search_batch_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint32_t ef,
                                const uint64_t *allow, uint64_t allow_bits, uint32_t *ids, float *dists,
                                uint32_t *counts, hnsw_query_stats *stats, uint8_t *paths) {
+    // the one family of filtered calls that is not open under "rows_f16" yet (hnsw_search_batch_filtered_multi with one
+    // row for all queries is the same search): refused here, before the planner and any device call
+    if (h && h->dev.rows_f16) {
+        set_error("hnsw_search_batch_filtered is not available with rows_f16 yet (hnsw_search_batch_filtered_multi with one "
+                  "mask for every query is the same search)");
+        return HNSW_ERR_ARG;
+    }
     // (a call without a mask allows nothing: kNoWords stands for its empty mask)
     hx::Filter f = make_filter(hx::Filter::MASK, hx::Filter::ONE, nullptr, nullptr);
     f.masks = allow ? allow : &kNoWords;

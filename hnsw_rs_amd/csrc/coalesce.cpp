@@ -134,7 +134,7 @@ int coalesced(hnsw_index *h, const CoCall &c) {
     const uint32_t n = c.n, ef = c.ef;
     uint32_t *ids = c.ids, *count = c.count;
     int rc;
-    if (!snapshot_current(h) && (rc = c.filtered ? ensure_uploaded(h) : ensure_uploaded_rows16(h)) != HNSW_OK) return rc;
+    if (!snapshot_current(h) && (rc = ensure_uploaded_rows16(h)) != HNSW_OK) return rc;
     Coalescer &co = h->co;
     const uint32_t d = h->dev.view.dim;
     // ---- claim a slot: the open batch everybody looks at first, else (under the lock) any open batch with these

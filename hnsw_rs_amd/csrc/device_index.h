@@ -1,5 +1,5 @@
 // device_index.h -- the HBM-resident snapshot of a HostIndex and the launchers of the kernels (search_kernels.hip,
-// search_lean.hip, search_rows16.hip, build_kernels.hip, exact_scan.hip, brute_mfma.hip, build_sort.hip, patch.hip, metric.hip).  gfx950 only.
+// search_lean.hip, search_rows16.hip, search_filtered16.hip, build_kernels.hip, exact_scan.hip, brute_mfma.hip, build_sort.hip, patch.hip, metric.hip).  gfx950 only.
 // (The record and the launchers of hx_distance_kernel's list forms are list_forms.h.)
 //
 // HBM layout (one allocation per array, all read-only during search):
@@ -16,8 +16,9 @@
 //             F32 under the option "rows_f16" (DevView::rows16 = 1): d IEEE binary16 values, element
 //             e at byte 2 e, zero-padded to 16 B -- row_stride = f16_row_stride(d) = 2 d rounded up to 16.  Every value
 //             is the host's f32 element exactly (upload() refuses a row that does not survive the round trip).  No
-//             inline-rows copy.  ONLY hx_search16_kernel (search_rows16.hip) reads such rows: every other kernel takes
-//             "not QUANT8" for f32, and ensure_uploaded keeps such a snapshot from them.
+//             inline-rows copy.  ONLY hx_search16_kernel (search_rows16.hip) and hx_filt16_graph_kernel /
+//             hx_filt16_scan_kernel (search_filtered16.hip) read such rows: every other kernel
+//             takes "not QUANT8" for f32, and ensure_uploaded keeps such a snapshot from them.
 //   adj0      N x S0 u32: layer-0 adjacency in fixed-stride rows (S0 = pow2 >= max(2m, 32), 128 B at
 //             m = 16), row index = node id, neighbour ids ascending, empty slots 0xFFFFFFFF behind them.
 //   adj_up    upper-layer rows, S1 = pow2 >= max(m, 8) slots each; the rows of one node for

@@ -136,7 +136,7 @@ int search_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t n, uint
                 if (!path[i]) gsel.push_back((uint32_t)i);
         }
     }
-    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h)) || (set && (rc = set->sync(h))) ||
+    if ((rc = ensure_uploaded_rows16(h)) || (rc = sync_deleted(h)) || (set && (rc = set->sync(h))) ||
         (ranged && (rc = sync_labels(h))))
         return rc;
     const DevView &v = h->dev.view;
@@ -305,7 +305,7 @@ int search_device_filtered(hnsw_index *h, const Filter &f, const float *d_Q, uin
         set_error("filtered device search: every query names row 0 of a set without rows");
         return HNSW_ERR_ARG;
     }
-    if ((rc = ensure_uploaded(h)) || (rc = sync_deleted(h)) || (ranged && (rc = sync_labels(h)))) return rc;
+    if ((rc = ensure_uploaded_rows16(h)) || (rc = sync_deleted(h)) || (ranged && (rc = sync_labels(h)))) return rc;
     if (set) {
         std::lock_guard<std::mutex> g(set->mu);
         if ((rc = set->sync(h))) return rc;

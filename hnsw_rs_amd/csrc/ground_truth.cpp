@@ -35,6 +35,7 @@ int nan_error(int status) {
 
 int exact_scan(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids, float *dists) {
     int rc;
+    if (h->dev.rows_f16) return ensure_uploaded(h);  // (refused: the scans are not open under "rows_f16", deleted ids or not)
     if (h->del.count) {
         // the top k of the undeleted ids: the filtered search's exact path, in the same arithmetic and (dist, id) order
         std::vector<hnsw_query_stats> st(nq);

@@ -1,4 +1,4 @@
-// rows16.inc -- included inside namespace hx by search_rows16.hip, after search_common.h: how a row stored as IEEE
+// rows16.inc -- included inside namespace hx by search_rows16.hip and search_filtered16.hip, after search_common.h: how a row stored as IEEE
 // binary16 ("rows_f16", DESIGN.md section 36) reaches its sum.  The arithmetic is FullVec's (full.rs:23-29) on the row
 // widened back to f32: every row is one lane's single left-to-right f32 chain over all d elements, x = (float)h (exact),
 // t = x - y, t = t * t, s = s + t, no contraction (-ffp-contract=off), and the caller takes the correctly rounded square

@@ -44,6 +44,9 @@ namespace hx {
 #define HX_FILT_RANGE_LDS 16  // bytes of LDS a wave under a label range keeps its range in (lo, hi - lo, its mask row's pointer)
 #define HX_FILT_MAX_RANGES 16   // members of a query's range list (HNSW_RANGES_MAX); each keeps 8 bytes more (lo, hi - lo)
 #define HX_FILT_MAX_SLOTS_LOG2 15  // the largest visited table: 32768 slots, at most 24576 ids (75 %)
+// bytes the cooperative gather of f16 rows keeps in LDS (rows16.inc: the 4-KiB stage image + 64 rank words), in the
+// room of the merges' permutation buffer
+#define HX_FILT16_GATHER_LDS (4096 + 256)
 
 struct FilterArgs {
     const float *Q;            // nq x dim (device)
@@ -171,6 +174,12 @@ __host__ __device__ inline uint32_t filt_visited_limit(uint32_t slots_log2) { re
 inline uint32_t filt_range_lds(bool ranged, uint32_t n_ranges = 1) {
     return ranged ? HX_FILT_RANGE_LDS + (n_ranges > 1 ? 8u * n_ranges : 0u) : 0u;
 }
+// bytes of the region behind the visited table: the merges' permutation buffer of 64 R keys, which over f16 rows of whole
+// lines (hx_filt16_graph_kernel's cooperative forms, search_filtered16.hip) shares its room with the gather
+inline uint32_t filt_region_bytes(const DevView &v, uint32_t R) {
+    const bool gathered = v.rows16 && (v.dim == 128 || v.dim == 256 || v.dim == 768);
+    return gathered && 64u * R * 8u < HX_FILT16_GATHER_LDS ? (uint32_t)HX_FILT16_GATHER_LDS : 64u * R * 8u;
+}
 uint32_t filt_first_slots_log2(const DevView &v, uint32_t ef, uint32_t range_lds = 0);
 uint32_t filt_max_slots_log2(const DevView &v, uint32_t range_lds = 0);
 
@@ -198,6 +207,15 @@ int launch_filter_compact_grouped(const FilterArgs &a, const ExactGroup *gtab, u
                                   hipStream_t stream);
 int launch_filtered_exact_grouped(const DevView &v, const FilterArgs &a, uint32_t nsel, const ExactQuery *qtab,
                                   uint32_t max_nseg, unsigned long long *part, int32_t *part_status, hipStream_t stream);
+// The same over a view with f16 rows (v.rows16; search_filtered16.hip, libhnsw_mi355x_filt16.so): the three launchers
+// above route there in front of everything else.  The graph walk as launch_filtered_graph's, its arguments checked and
+// the column's pointer tagged by it; the scan of launch_filtered_exact (qtab == nullptr: grid_seg = nseg) or of its
+// grouped form (ids, A and nseg from qtab: grid_seg = max_nseg), the merge launched by the caller behind it.
+int launch_filtered_graph_rows16(const DevView &v, const FilterArgs &a, uint32_t nblocks, uint32_t slots_log2,
+                                 hipStream_t stream);
+int launch_filtered_scan_rows16(const DevView &v, const FilterArgs &a, uint32_t grid_seg, uint32_t nsel, const uint32_t *ids,
+                                uint32_t A, uint32_t nseg, unsigned long long *part, int32_t *part_status,
+                                const ExactQuery *qtab, hipStream_t stream);
 // the top n (1 <= n <= HX_FILT_MAX_N) by (distance bits, global id) of m.nq queries over the lists of m.n_shards shards:
 // ONE launch of hx_filt_merge_kernel in its shard-list form, one wave per query.  out_counts may be nullptr; out_stats
 // goes with m.stats.  A query some shard answered with a status other than HNSW_OK gets that status (the lowest-numbered

@@ -39,114 +39,6 @@ namespace hx {
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// A sorted register list of up to 64 R keys (list[64 r + lane]), FKEY_INVALID beyond n_cur.
-// ---------------------------------------------------------------------------------------------
-template <int R>
-struct FList {
-    u64 L[R];
-    uint32_t n_cur;  // wave-uniform
-    u64 last;        // the largest key when the list holds cap keys, else FKEY_INVALID
-
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int r = 0; r < R; r++) L[r] = FKEY_INVALID;
-        n_cur = 0;
-        last = FKEY_INVALID;
-    }
-    __device__ __forceinline__ bool full(uint32_t cap) const { return n_cur >= cap; }
-    __device__ __forceinline__ u64 front() const { return readlane64(L[0], 0); }
-
-    __device__ __forceinline__ void refresh_last(uint32_t cap) {
-        u64 k = FKEY_INVALID;
-        if (n_cur >= cap) {
-            const uint32_t pos = cap - 1;
-#pragma unroll
-            for (int r = 0; r < R; r++)
-                if ((pos >> 6) == (uint32_t)r) k = readlane64(L[r], pos & 63);
-        }
-        last = k;
-    }
-
-    // Merge the wave's keys (FKEY_INVALID = none; distinct and not in the list) and keep the cap smallest:
-    // rank of every survivor by ballot + popcount, scatter through the LDS buffer perm (64 R keys).
-    __device__ __forceinline__ void merge(u64 key, uint32_t cap, u64 *perm, int lane) {
-        const bool surv = key != FKEY_INVALID && (n_cur < cap || key < last);
-        const u64 smask = __ballot(surv);
-        if (smask == 0) return;
-        const uint32_t m = (uint32_t)__popcll(smask);
-        uint32_t shift[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) shift[r] = 0;
-        uint32_t my_rank = 0;
-        u64 it = smask;
-        while (it) {
-            const int j = __ffsll((long long)it) - 1;
-            it &= it - 1;
-            const u64 e = readlane64(key, j);
-            uint32_t below = 0;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const bool lt = L[r] < e;  // invalid entries are the maximum
-                below += (uint32_t)__popcll(__ballot(lt));
-                shift[r] += lt ? 0u : 1u;
-            }
-            if (surv && e < key) my_rank++;
-            if (lane == j) my_rank += below;
-        }
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t idx = 64u * r + lane;
-            const uint32_t np = idx + shift[r];
-            if (idx < n_cur && np < cap) perm[np] = L[r];
-        }
-        if (surv && my_rank < cap) perm[my_rank] = key;
-        n_cur = min(n_cur + m, cap);
-        wave_fence();
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t idx = 64u * r + lane;
-            L[r] = idx < n_cur ? perm[idx] : FKEY_INVALID;
-        }
-        wave_fence();
-        refresh_last(cap);
-    }
-
-    // merge for keys that may repeat (result lists of shards that overlap): a key equal to one in the list, or to the
-    // key of a lower lane, is dropped first, so that what merge sees is distinct and new -- its ranks are then dense and
-    // every slot of perm it reads back was written in the same call
-    __device__ __forceinline__ void merge_unique(u64 key, uint32_t cap, u64 *perm, int lane) {
-        u64 it = __ballot(key != FKEY_INVALID && (n_cur < cap || key < last));
-        bool dup = false;
-        while (it) {
-            const int j = __ffsll((long long)it) - 1;
-            it &= it - 1;
-            const u64 e = readlane64(key, j);
-            bool known = lane < j && key == e;
-#pragma unroll
-            for (int r = 0; r < R; r++) known |= L[r] == e;
-            const bool any = __ballot(known) != 0;
-            if (lane == j) dup = any;
-        }
-        merge(dup ? FKEY_INVALID : key, cap, perm, lane);
-    }
-
-    // drop the head: every key moves one lane down, lane 63 of register r takes lane 0 of register r + 1
-    __device__ __forceinline__ void pop_front(uint32_t cap, int lane) {
-        const int src = ((lane + 1) & 63) << 2;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)L[r]);
-            const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)(L[r] >> 32));
-            u64 nx = FKEY_INVALID;
-            if (r + 1 < R) nx = readlane64(L[r + 1 < R ? r + 1 : r], 0);
-            L[r] = lane == 63 ? nx : (((u64)hi << 32) | lo);
-        }
-        n_cur--;
-        refresh_last(cap);
-    }
-};
-
-// ---------------------------------------------------------------------------------------------
 // Graph path.  LDS: visited table (4 << slots_log2 bytes) | merge buffer (64 R keys) | query | under a label range,
 // the wave's range (HX_FILT_RANGE_LDS bytes) | under K > 1 ranges, its K members (8 K bytes): filt_range_lds.
 // ---------------------------------------------------------------------------------------------
@@ -854,7 +746,7 @@ uint32_t filt_first_slots_log2(const DevView &v, uint32_t ef, uint32_t range_lds
 uint32_t filt_max_slots_log2(const DevView &v, uint32_t range_lds) {
     const uint32_t yqb = query_lds_bytes(v);
     uint32_t s = HX_FILT_MAX_SLOTS_LOG2;
-    while (s > 12 && (4ull << s) + 64ull * 4 * 8 + yqb + range_lds > 160 * 1024) s--;
+    while (s > 12 && (4ull << s) + filt_region_bytes(v, 4) + yqb + range_lds > 160 * 1024) s--;
     return s;
 }
 
@@ -874,6 +766,7 @@ int launch_filtered_graph(const DevView &v, const FilterArgs &args, uint32_t nbl
     // K > 1 reaches the kernel as bit 1 of the column's pointer (its copy is aligned far beyond 4 bytes): the kernel has
     // no scalar register to keep K or a flag in while it walks (filt_allowed)
     if (a.n_ranges > 1) a.labels = reinterpret_cast<const uint32_t *>((uintptr_t)a.labels | 2);
+    if (v.rows16) return launch_filtered_graph_rows16(v, a, nblocks, slots_log2, stream);  // f16 rows: no kernel below reads them
     if (v.kind == HNSW_VEC_QUANT8) {
         if (v.dim == 100 && v.half_bytes == 64) return launch_graph<HNSW_VEC_QUANT8, 4, 100>(v, a, nblocks, slots_log2, stream);
         return launch_graph<HNSW_VEC_QUANT8, 0, 0>(v, a, nblocks, slots_log2, stream);
@@ -924,9 +817,11 @@ int launch_filtered_exact(const DevView &v, const FilterArgs &a, uint32_t nsel, 
     }
     // scan, then merge: two launches back to back under one message, the second only after the first was accepted
     const LaunchSite site{"filtered exact search launch"};
-    if (int rc = launch_checked(site, v.kind == HNSW_VEC_QUANT8 ? hx_filt_scan_kernel<HNSW_VEC_QUANT8> : hx_filt_scan_kernel<HNSW_VEC_F32>,
-                                dim3(nseg, nsel), dim3(64), 64 * 8 + (size_t)query_lds_bytes(v), stream, v, a, ids, A, nseg, part,
-                                part_status, static_cast<const ExactQuery *>(nullptr)))
+    if (int rc = v.rows16
+                     ? launch_filtered_scan_rows16(v, a, nseg, nsel, ids, A, nseg, part, part_status, nullptr, stream)
+                     : launch_checked(site, v.kind == HNSW_VEC_QUANT8 ? hx_filt_scan_kernel<HNSW_VEC_QUANT8> : hx_filt_scan_kernel<HNSW_VEC_F32>,
+                                      dim3(nseg, nsel), dim3(64), 64 * 8 + (size_t)query_lds_bytes(v), stream, v, a, ids, A, nseg, part,
+                                      part_status, static_cast<const ExactQuery *>(nullptr)))
         return rc;
     return launch_checked(site, hx_filt_merge_kernel, dim3(nsel), dim3(64), 0, stream, a, A, nseg, part, part_status,
                           MergeLists{}, static_cast<const ExactQuery *>(nullptr));
@@ -941,9 +836,11 @@ int launch_filtered_exact_grouped(const DevView &v, const FilterArgs &a, uint32_
         return HNSW_ERR_ARG;
     }
     const LaunchSite site{"filtered exact search launch"};
-    if (int rc = launch_checked(site, v.kind == HNSW_VEC_QUANT8 ? hx_filt_scan_kernel<HNSW_VEC_QUANT8> : hx_filt_scan_kernel<HNSW_VEC_F32>,
-                                dim3(max_nseg, nsel), dim3(64), 64 * 8 + (size_t)query_lds_bytes(v), stream, v, a,
-                                static_cast<const uint32_t *>(nullptr), 0u, 0u, part, part_status, qtab))
+    if (int rc = v.rows16
+                     ? launch_filtered_scan_rows16(v, a, max_nseg, nsel, nullptr, 0u, 0u, part, part_status, qtab, stream)
+                     : launch_checked(site, v.kind == HNSW_VEC_QUANT8 ? hx_filt_scan_kernel<HNSW_VEC_QUANT8> : hx_filt_scan_kernel<HNSW_VEC_F32>,
+                                      dim3(max_nseg, nsel), dim3(64), 64 * 8 + (size_t)query_lds_bytes(v), stream, v, a,
+                                      static_cast<const uint32_t *>(nullptr), 0u, 0u, part, part_status, qtab))
         return rc;
     return launch_checked(site, hx_filt_merge_kernel, dim3(nsel), dim3(64), 0, stream, a, 0u, 0u, part, part_status,
                           MergeLists{}, qtab);

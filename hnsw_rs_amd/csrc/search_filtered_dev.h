@@ -1,6 +1,7 @@
-// search_filtered_dev.h -- the device pieces that both families of filtered-search kernels use (search_filtered.hip,
-// search_filtered_wide.hip): the key of an empty lane, the wave's smallest key, the LDS visited table, the admissibility
-// test of an id under a FilterArgs block and the distance of a stored row.  gfx950 only; include from .hip files.
+// search_filtered_dev.h -- the device pieces that the families of filtered-search kernels share (search_filtered.hip,
+// search_filtered_wide.hip, search_filtered16.hip): the key of an empty lane, the wave's smallest key, the sorted
+// register list FList, the LDS visited table, the admissibility test of an id under a FilterArgs block and the distance
+// of a stored row.  gfx950 only; include from .hip files.
 #pragma once
 
 #include "search_common.h"
@@ -20,6 +21,114 @@ __device__ __forceinline__ u64 wave_min64(u64 x) {
     }
     return x;
 }
+
+// ---------------------------------------------------------------------------------------------
+// A sorted register list of up to 64 R keys (list[64 r + lane]), FKEY_INVALID beyond n_cur.
+// ---------------------------------------------------------------------------------------------
+template <int R>
+struct FList {
+    u64 L[R];
+    uint32_t n_cur;  // wave-uniform
+    u64 last;        // the largest key when the list holds cap keys, else FKEY_INVALID
+
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int r = 0; r < R; r++) L[r] = FKEY_INVALID;
+        n_cur = 0;
+        last = FKEY_INVALID;
+    }
+    __device__ __forceinline__ bool full(uint32_t cap) const { return n_cur >= cap; }
+    __device__ __forceinline__ u64 front() const { return readlane64(L[0], 0); }
+
+    __device__ __forceinline__ void refresh_last(uint32_t cap) {
+        u64 k = FKEY_INVALID;
+        if (n_cur >= cap) {
+            const uint32_t pos = cap - 1;
+#pragma unroll
+            for (int r = 0; r < R; r++)
+                if ((pos >> 6) == (uint32_t)r) k = readlane64(L[r], pos & 63);
+        }
+        last = k;
+    }
+
+    // Merge the wave's keys (FKEY_INVALID = none; distinct and not in the list) and keep the cap smallest:
+    // rank of every survivor by ballot + popcount, scatter through the LDS buffer perm (64 R keys).
+    __device__ __forceinline__ void merge(u64 key, uint32_t cap, u64 *perm, int lane) {
+        const bool surv = key != FKEY_INVALID && (n_cur < cap || key < last);
+        const u64 smask = __ballot(surv);
+        if (smask == 0) return;
+        const uint32_t m = (uint32_t)__popcll(smask);
+        uint32_t shift[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) shift[r] = 0;
+        uint32_t my_rank = 0;
+        u64 it = smask;
+        while (it) {
+            const int j = __ffsll((long long)it) - 1;
+            it &= it - 1;
+            const u64 e = readlane64(key, j);
+            uint32_t below = 0;
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const bool lt = L[r] < e;  // invalid entries are the maximum
+                below += (uint32_t)__popcll(__ballot(lt));
+                shift[r] += lt ? 0u : 1u;
+            }
+            if (surv && e < key) my_rank++;
+            if (lane == j) my_rank += below;
+        }
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const uint32_t idx = 64u * r + lane;
+            const uint32_t np = idx + shift[r];
+            if (idx < n_cur && np < cap) perm[np] = L[r];
+        }
+        if (surv && my_rank < cap) perm[my_rank] = key;
+        n_cur = min(n_cur + m, cap);
+        wave_fence();
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const uint32_t idx = 64u * r + lane;
+            L[r] = idx < n_cur ? perm[idx] : FKEY_INVALID;
+        }
+        wave_fence();
+        refresh_last(cap);
+    }
+
+    // merge for keys that may repeat (result lists of shards that overlap): a key equal to one in the list, or to the
+    // key of a lower lane, is dropped first, so that what merge sees is distinct and new -- its ranks are then dense and
+    // every slot of perm it reads back was written in the same call
+    __device__ __forceinline__ void merge_unique(u64 key, uint32_t cap, u64 *perm, int lane) {
+        u64 it = __ballot(key != FKEY_INVALID && (n_cur < cap || key < last));
+        bool dup = false;
+        while (it) {
+            const int j = __ffsll((long long)it) - 1;
+            it &= it - 1;
+            const u64 e = readlane64(key, j);
+            bool known = lane < j && key == e;
+#pragma unroll
+            for (int r = 0; r < R; r++) known |= L[r] == e;
+            const bool any = __ballot(known) != 0;
+            if (lane == j) dup = any;
+        }
+        merge(dup ? FKEY_INVALID : key, cap, perm, lane);
+    }
+
+    // drop the head: every key moves one lane down, lane 63 of register r takes lane 0 of register r + 1
+    __device__ __forceinline__ void pop_front(uint32_t cap, int lane) {
+        const int src = ((lane + 1) & 63) << 2;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)L[r]);
+            const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)(L[r] >> 32));
+            u64 nx = FKEY_INVALID;
+            if (r + 1 < R) nx = readlane64(L[r + 1 < R ? r + 1 : r], 0);
+            L[r] = lane == 63 ? nx : (((u64)hi << 32) | lo);
+        }
+        n_cur--;
+        refresh_last(cap);
+    }
+};
 
 // LDS visited table: buckets of four slots, ds_read_b128 + one compare-and-swap (the generic kernel's table).
 // Returns true when id was absent (and is now present).

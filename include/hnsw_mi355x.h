@@ -1521,8 +1521,12 @@ int hnsw_device_bytes(const hnsw_index *h, uint64_t *bytes);
  *                      that rounds to +-inf (|x| >= 65520) is HNSW_ERR_ARG, a NaN stays HNSW_ERR_NAN_INPUT.  Refused with
  *                      HNSW_ERR_ARG on an 8-bit handle, on a replica, and once a stored element is not a binary16 value
  *                      -- so it can be set again after a load (the file has no field for it).  Served under it:
- *                      hnsw_search, hnsw_search_batch, hnsw_search_batch_device(_finish), ef <= 1024, nothing deleted;
- *                      every other entry point that needs the snapshot returns HNSW_ERR_ARG.  Queries stay f32
+ *                      hnsw_search, hnsw_search_batch, hnsw_search_batch_device(_finish), ef <= 1024 -- and, while ids
+ *                      are deleted, the same three as the filtered search over the undeleted ids (n <= 64, ef' <= 256);
+ *                      hnsw_search_filtered and hnsw_search_batch_filtered_multi, _set, _range, _set_range and _ranges
+ *                      with their _device(_finish) forms.  Every other entry point that needs
+ *                      the snapshot returns HNSW_ERR_ARG, hnsw_search_batch_filtered among them (_filtered_multi with
+ *                      one mask for every query is the same search).  Queries stay f32
  *   "gpu_build_batch_max", "gpu_build_batch_div"
  *                      the on-device build inserts min(max, connected / div) points at a time (defaults
  *                      8192 and 8; max is capped at 32768); 256 and 64 stand closer to the reference's
