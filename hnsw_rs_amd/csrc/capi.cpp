@@ -38,14 +38,15 @@ int reject_replica(const hnsw_index *h, const char *what) {
     return HNSW_ERR_ARG;
 }
 
-// Default deny: every row reader but hx_search16_kernel and the two hx_filt16 kernels takes "not QUANT8" for f32, so a
+// Default deny: every row reader but hx_search16_kernel, the two hx_filt16 kernels and brute_mfma16.hip's three takes "not QUANT8" for f32, so a
 // handle under "rows_f16" gets no snapshot through here; the entry points those kernels serve call ensure_uploaded_rows16
 // instead.
 int ensure_uploaded(hnsw_index *h) {
     if (h->dev.rows_f16) {
         set_error("this entry point is not available with rows_f16 yet (hnsw_search, hnsw_search_batch, "
                   "hnsw_search_batch_device, hnsw_search_filtered and hnsw_search_batch_filtered_multi, _set, _range, "
-                  "_set_range and _ranges with their _device forms are, with or without deleted ids)");
+                  "_set_range and _ranges with their _device forms are, with or without deleted ids, and "
+                  "hnsw_brute_force_fast without)");
         return HNSW_ERR_ARG;
     }
     return ensure_uploaded_rows16(h);

@@ -16,8 +16,9 @@
 //             F32 under the option "rows_f16" (DevView::rows16 = 1): d IEEE binary16 values, element
 //             e at byte 2 e, zero-padded to 16 B -- row_stride = f16_row_stride(d) = 2 d rounded up to 16.  Every value
 //             is the host's f32 element exactly (upload() refuses a row that does not survive the round trip).  No
-//             inline-rows copy.  ONLY hx_search16_kernel (search_rows16.hip) and hx_filt16_graph_kernel /
-//             hx_filt16_scan_kernel (search_filtered16.hip) read such rows: every other kernel
+//             inline-rows copy.  ONLY hx_search16_kernel (search_rows16.hip), hx_filt16_graph_kernel /
+//             hx_filt16_scan_kernel (search_filtered16.hip) and the three ground-truth kernels of
+//             brute_mfma16.hip (section 38) read such rows: every other kernel
 //             takes "not QUANT8" for f32, and ensure_uploaded keeps such a snapshot from them.
 //   adj0      N x S0 u32: layer-0 adjacency in fixed-stride rows (S0 = pow2 >= max(2m, 32), 128 B at
 //             m = 16), row index = node id, neighbour ids ascending, empty slots 0xFFFFFFFF behind them.
@@ -295,6 +296,14 @@ int launch_brute_mfma(const DevView &v, const float *d_xn, const float *d_Q, uin
                       float *out_s, uint32_t *out_i, hipStream_t stream);
 int launch_pair_distance(const DevView &v, const float *d_Q, const uint32_t *d_qidx, const uint32_t *d_pidx, uint64_t n,
                          float *d_out, hipStream_t stream);
+// the same three phases over a view with f16 rows (brute_mfma16.hip, libhnsw_mi355x_truth16.so):
+// d_xinfo is a row's largest |element| widened, bit 31 set when the row holds a binary16 subnormal; the screen's lists
+// have launch_brute_mfma's layout.  Any dimension whose three query planes fit in LDS (d <= 832).
+int launch_row_norms16(const DevView &v, float *d_xn, uint32_t *d_xinfo, hipStream_t stream);
+int launch_brute_mfma16(const DevView &v, const float *d_xn, const float *d_Q, uint32_t nq, uint32_t nseg, float *out_s,
+                        uint32_t *out_i, hipStream_t stream);
+int launch_pair_distance16(const DevView &v, const float *d_Q, const uint32_t *d_qidx, const uint32_t *d_pidx, uint64_t n,
+                           float *d_out, hipStream_t stream);
 
 // the cosine option: rows (queries) normalised in place to unit length (metric.hip)
 int launch_normalise_rows(float *d_rows, uint64_t n, uint32_t d, hipStream_t stream);

@@ -31,21 +31,27 @@ int nan_error(int status) {
     return status;
 }
 
+// the top k of the undeleted ids by the filtered search's exact path, in the reference's arithmetic and (dist, id)
+// order: the exact scan under deletions, and the exact scan of f16 rows (hx_filt16_scan_kernel), deleted ids or not
+int scan_filtered(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids, float *dists) {
+    std::vector<hnsw_query_stats> st(nq);
+    Filter scan;
+    scan.family = Filter::SCAN;
+    if (int rc = search_filtered(h, Q, nq, k, k, scan, true, ids, dists, nullptr, st.data(), nullptr)) return rc;
+    for (uint64_t i = 0; i < nq; i++)
+        if (st[i].status != HNSW_OK) return nan_error(st[i].status);
+    return HNSW_OK;
+}
+
 }  // namespace
 
 int exact_scan(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids, float *dists) {
     int rc;
-    if (h->dev.rows_f16) return ensure_uploaded(h);  // (refused: the scans are not open under "rows_f16", deleted ids or not)
-    if (h->del.count) {
-        // the top k of the undeleted ids: the filtered search's exact path, in the same arithmetic and (dist, id) order
-        std::vector<hnsw_query_stats> st(nq);
-        Filter scan;
-        scan.family = Filter::SCAN;
-        if ((rc = search_filtered(h, Q, nq, k, k, scan, true, ids, dists, nullptr, st.data(), nullptr))) return rc;
-        for (uint64_t i = 0; i < nq; i++)
-            if (st[i].status != HNSW_OK) return nan_error(st[i].status);
-        return HNSW_OK;
+    if (h->dev.rows_f16) {  // (deleted ids or not)
+        set_error("hnsw_brute_force is not available with rows_f16 yet; hnsw_brute_force_fast answers (k <= 12)");
+        return HNSW_ERR_ARG;
     }
+    if (h->del.count) return scan_filtered(h, Q, nq, k, ids, dists);
     if ((rc = ensure_uploaded(h))) return rc;
     const DevView &v = h->dev.view;
     const uint32_t nseg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(512, (v.n_points + 2047) / 2048));
@@ -85,16 +91,19 @@ int exact_scan(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t 
 // query are re-evaluated in the reference's exact arithmetic and sorted by (dist, id).  Not bit-exact by
 // construction (the screen could in principle lose a true neighbour to rounding): exact_scan is the
 // exact scan; this one is for ground truth at sizes where the exact scan takes minutes.
+// Under "rows_f16" the three phases are brute_mfma16.hip's over the f16 rows: the same lists, the
+// same merge, any dimension; the answer is the plain f32 index's over the widened rows.
 int mfma_scan(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids, float *dists) {
     if (h->del.count) {  // the k + 8 re-rank cannot promise k undeleted ids: no ground truth rather than a wrong one
         set_error("hnsw_brute_force_fast refuses while ids are deleted (%llu); hnsw_brute_force excludes them",
                   (unsigned long long)h->del.count);
         return HNSW_ERR_ARG;
     }
-    int rc = ensure_uploaded(h);
+    const bool r16 = h->dev.rows_f16;
+    int rc = r16 ? ensure_uploaded_rows16(h) : ensure_uploaded(h);
     if (rc != HNSW_OK) return rc;
     const DevView &v = h->dev.view;
-    if (v.kind != HNSW_VEC_F32 || (v.dim & 3u)) {
+    if (!r16 && (v.kind != HNSW_VEC_F32 || (v.dim & 3u))) {
         set_error("the MFMA scan serves f32 rows whose dimension is a multiple of 4");
         return HNSW_ERR_ARG;
     }
@@ -119,11 +128,15 @@ int mfma_scan(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *
     if ((rc = dQ.alloc(BATCH * v.dim * 4)) || (rc = dXn.alloc((size_t)v.n_points * 4)) ||
         (rc = dS.alloc(ntile_max * per_tile * 4)) || (rc = dI.alloc(ntile_max * per_tile * 4)) ||
         (rc = dQi.alloc(BATCH * M * 4)) || (rc = dPi.alloc(BATCH * M * 4)) || (rc = dOut.alloc(BATCH * M * 4)) ||
-        (rc = dXa.alloc((size_t)v.n_points * 4)) || (rc = launch_row_norms(v, dXn.as<float>(), dXa.as<uint32_t>(), nullptr)))
+        (rc = dXa.alloc((size_t)v.n_points * 4)) ||
+        (rc = r16 ? launch_row_norms16(v, dXn.as<float>(), dXa.as<uint32_t>(), nullptr)
+                  : launch_row_norms(v, dXn.as<float>(), dXa.as<uint32_t>(), nullptr)))
         return rc;
     // The screen's guarantee models relative rounding and holds only inside f32's normal range (brute_mfma.hip): a
     // call with a stored row or a query whose largest |component| is not zero and outside [2^-48, 2^40] is the exact
-    // scan's.  (Under the cosine option a query is a unit vector by the time the screen reads it.)
+    // scan's.  (Under the cosine option a query is a unit vector by the time the screen reads it.)  Over f16 rows a
+    // stored row that holds a binary16 subnormal (bit 31 of its word, above every |value|) does the same: whether the
+    // f16 matrix instruction flushes such an operand is not assumed.
     {
         const uint32_t lo = 0x27800000u, hi = 0x53800000u;  // the bit patterns of 2^-48 and 2^40
         auto outside = [&](uint32_t bits) { return bits != 0 && (bits < lo || bits > hi); };
@@ -139,7 +152,7 @@ int mfma_scan(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *
             }
             exact = outside(m);
         }
-        if (exact) return exact_scan(h, Q, nq, k, ids, dists);
+        if (exact) return r16 ? scan_filtered(h, Q, nq, k, ids, dists) : exact_scan(h, Q, nq, k, ids, dists);
     }
     std::vector<float> hs(ntile_max * per_tile), hd(BATCH * M);
     std::vector<uint32_t> hi(ntile_max * per_tile), qidx(BATCH * M), pidx(BATCH * M);
@@ -149,8 +162,8 @@ int mfma_scan(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *
         const uint32_t ntile = (uint32_t)((nb + 31) / 32);
         HIP_TRY(hipMemcpy(dQ.p, Q + q0 * v.dim, nb * v.dim * 4, hipMemcpyHostToDevice));
         if ((rc = cosine_queries(h, dQ.p, nb, nullptr))) return rc;
-        if ((rc = launch_brute_mfma(v, dXn.as<float>(), dQ.as<float>(), (uint32_t)nb, nseg, dS.as<float>(), dI.as<uint32_t>(),
-                                    nullptr)))
+        if ((rc = (r16 ? launch_brute_mfma16 : launch_brute_mfma)(v, dXn.as<float>(), dQ.as<float>(), (uint32_t)nb, nseg,
+                                                                  dS.as<float>(), dI.as<uint32_t>(), nullptr)))
             return rc;
         HIP_TRY(hipMemcpy(hs.data(), dS.p, ntile * per_tile * 4, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(hi.data(), dI.p, ntile * per_tile * 4, hipMemcpyDeviceToHost));
@@ -170,7 +183,8 @@ int mfma_scan(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *
         // exact distances of the survivors, in the reference's arithmetic
         HIP_TRY(hipMemcpy(dQi.p, qidx.data(), nb * M * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dPi.p, pidx.data(), nb * M * 4, hipMemcpyHostToDevice));
-        if ((rc = launch_pair_distance(v, dQ.as<float>(), dQi.as<uint32_t>(), dPi.as<uint32_t>(), nb * M, dOut.as<float>(), nullptr)))
+        if ((rc = (r16 ? launch_pair_distance16 : launch_pair_distance)(v, dQ.as<float>(), dQi.as<uint32_t>(), dPi.as<uint32_t>(),
+                                                                        nb * M, dOut.as<float>(), nullptr)))
             return rc;
         HIP_TRY(hipMemcpy(hd.data(), dOut.p, nb * M * 4, hipMemcpyDeviceToHost));
         for (uint64_t qi = 0; qi < nb; qi++) {

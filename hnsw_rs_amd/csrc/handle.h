@@ -119,8 +119,8 @@ int check_search_args(const hnsw_index *h, uint32_t ef);
 // the HBM snapshot is what the host index holds (uploaded if not) and its device is the calling thread's
 // (refused with HNSW_ERR_ARG under the option "rows_f16": no kernel behind this call reads f16 rows)
 int ensure_uploaded(hnsw_index *h);
-// the same for the entry points that end in launch_search or in the filtered launchers, which serve a snapshot of f16
-// rows too (search_rows16.hip, search_filtered16.hip)
+// the same for the entry points that end in launch_search, in the filtered launchers or in the MFMA scan, which serve
+// a snapshot of f16 rows too (search_rows16.hip, search_filtered16.hip, brute_mfma16.hip)
 int ensure_uploaded_rows16(hnsw_index *h);
 
 // options.cpp: one table of the options, one of the statistics; a clone takes every option as its parent stores it

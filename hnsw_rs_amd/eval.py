@@ -74,8 +74,9 @@ def load_glove_array(lim, path, verbose=False):
 
 
 def recall_at(index, queries, n, ef):
-    """hits / (nq * n) of ann_by_vector(q, n, ef) against the exhaustive top-n (template.rs:543-552)"""
-    truth, _ = index.brute_force(queries, n)
+    """hits / (nq * n) of ann_by_vector(q, n, ef) against the exhaustive top-n (template.rs:543-552).  An index under
+    "rows_f16" takes its truth from brute_force_fast, the scan that reads f16 rows (n <= 12)"""
+    truth, _ = (index.brute_force_fast if index.rows_f16 else index.brute_force)(queries, n)
     ids, _, _, _ = index.search_batch(queries, n, ef)
     hits = sum(len(set(a.tolist()) & set(b.tolist())) for a, b in zip(ids, truth))
     return hits / float(len(queries) * n)

@@ -105,6 +105,7 @@ class HNSW:
         self._h = handle
         self.dim = dim
         self.vec_kind = vec_kind
+        self.rows_f16 = False  # the option "rows_f16" as set through this object (the C ABI has no getter)
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -123,7 +124,9 @@ class HNSW:
     def clone(self):
         h = C.c_void_p()
         check(self._L.hnsw_clone(self._h, C.byref(h)))
-        return HNSW(h, self.dim, self.vec_kind)
+        c = HNSW(h, self.dim, self.vec_kind)
+        c.rows_f16 = self.rows_f16  # (a clone takes every option)
+        return c
 
     @property
     def params(self):
@@ -1084,8 +1087,9 @@ class HNSW:
         return ids, dists
 
     def brute_force_fast(self, Q, k):
-        """ground truth on the matrix cores (MFMA screen + exact re-rank of the k + 8 best): f32 rows only;
-        not bit-exact by construction, see include/hnsw_mi355x.h"""
+        """ground truth on the matrix cores (MFMA screen + exact re-rank of the k + 8 best): f32 rows, also under
+        "rows_f16" (the binary16 matrix cores, any dimension up to 832); not bit-exact by construction, see
+        include/hnsw_mi355x.h"""
         Q = np.ascontiguousarray(Q, dtype=np.float32)
         nq = Q.shape[0]
         ids = np.zeros((nq, k), dtype=np.uint32)
@@ -1179,6 +1183,8 @@ class HNSW:
 
     def set_option(self, key, value):
         check(self._L.hnsw_set_option(self._h, key.encode(), int(value)))
+        if key == "rows_f16":
+            self.rows_f16 = bool(value)
 
     def upload(self):
         check(self._L.hnsw_upload(self._h))

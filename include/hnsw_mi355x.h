@@ -1412,7 +1412,20 @@ int hnsw_brute_force(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uin
  * bound.  E models relative rounding and means nothing outside f32's normal range: a call in which a stored
  * row or a query has a largest |component| that is not zero and lies outside [2^-48, 2^40] is handed to
  * hnsw_brute_force whole (tests/test_gpu_numeric_range.py).  hnsw_brute_force is the unconditionally exact
- * scan.  An extension: the reference has no counterpart. */
+ * scan.  An extension: the reference has no counterpart.
+ * On a handle under the option "rows_f16" the same call screens the f16 rows on the binary16 matrix cores
+ * (v_mfma_f32_32x32x16_f16; brute_mfma16.hip): any dimension up to 832, k <= 12, the same
+ * statuses.  The stored row is the instruction's A operand as it lies in HBM; the f32 query is not rounded but scaled
+ * by a power of two and split into three binary16 planes (what they leave of a component is below 2^-33 of the query's
+ * largest), three f32 accumulators are recombined, and the k + 8 best are re-evaluated over the exactly widened rows in
+ * the reference's arithmetic.  The answer is the plain f32 index's over X.astype(float16).astype(float32): ids and
+ * distance bits of its hnsw_brute_force wherever the condition above holds with 4 E in E's place (the factor 4 is an
+ * allowance for the instruction's undocumented rounding of its 16-term sums and for the recombination, not a
+ * measurement); beyond it, k distinct stored ids with the reference's distances in order.  A call in which a stored row
+ * holds a nonzero binary16 subnormal, or a query falls outside the range above, is answered whole by the exact scan of
+ * f16 rows (whether the instruction flushes such operands is not assumed) -- about one element in 20 000 of a
+ * standard normal is one, so large sets of such rows take that path.
+ * tests/test_gpu_ground_truth_f16.py. */
 int hnsw_brute_force_fast(hnsw_index *h, const float *Q, uint64_t nq, uint32_t k, uint32_t *ids,
                           float *dists);
 
