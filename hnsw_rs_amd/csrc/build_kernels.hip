@@ -482,6 +482,7 @@ int launch_insert(const DevView &v, const InsertArgs &a, uint32_t nblocks, hipSt
     // CU (insert_table_first_adjust) and runs the few points that fill it again with a larger one
     slots_log2 = (uint32_t)std::min(15, std::max(9, (int)slots_log2 + table_adjust));
     const size_t lds = (4ull << slots_log2) + 64ull * HX_MAX_R * 8 + 128 * 8 + 2 * (size_t)query_lds_bytes(v) + 256 /* rank -> id words */;
+    if (v.rows16) return launch_insert_rows16(v, a, nblocks, slots_log2, lds, stream);  // f16 rows: no kernel below reads them
     // the configs[1] dimension gets compile-time row loops
     void (*kfn)(const DevView, const InsertArgs, const uint32_t);
     if (v.kind == HNSW_VEC_QUANT8)
@@ -796,6 +797,8 @@ static int launch_connect_rs(const DevView &v, const ConnectArgs &a, hipStream_t
 int launch_connect(const DevView &v, const ConnectArgs &a, hipStream_t stream) {
     if (a.count == 0) return HNSW_OK;
     const uint32_t S = std::max(v.S0, v.S1);
+    if (v.rows16 && S <= 256)  // f16 rows: no kernel below reads them
+        return launch_connect_rows16(v, a, S <= 64 ? 1 : S <= 128 ? 2 : 4, stream);
     if (S <= 64) return launch_connect_rs<1>(v, a, stream);
     if (S <= 128) return launch_connect_rs<2>(v, a, stream);
     if (S <= 256) return launch_connect_rs<4>(v, a, stream);

@@ -38,7 +38,8 @@ int reject_replica(const hnsw_index *h, const char *what) {
     return HNSW_ERR_ARG;
 }
 
-// Default deny: every row reader but hx_search16_kernel, the two hx_filt16 kernels and brute_mfma16.hip's three takes "not QUANT8" for f32, so a
+// Default deny: every row reader but hx_search16_kernel, the two hx_filt16 kernels and brute_mfma16.hip's three (and the
+// on-device build's hx_insert16_kernel / hx_connect16_kernel, which upload for themselves) takes "not QUANT8" for f32, so a
 // handle under "rows_f16" gets no snapshot through here; the entry points those kernels serve call ensure_uploaded_rows16
 // instead.
 int ensure_uploaded(hnsw_index *h) {
@@ -160,20 +161,39 @@ int cosine_rows(const hnsw_index *h, const float *&rows, uint64_t n, std::vector
 // The rows_f16 option on the way in, after cosine_rows: every element to the nearest binary16 value (ties to even),
 // kept as that value widened back to f32 -- the host index, the files and the oracle see an ordinary f32 index.  A NaN
 // passes through (the insert reports it as it always has); an element that rounds to +-inf refuses the call.  `keep`
-// is cosine_rows' copy when there is one.  Returns rows itself when the option is off.
-int f16_rows(const hnsw_index *h, const float *&rows, uint64_t n, std::vector<float> &keep) {
+// is cosine_rows' copy when there is one.  Returns rows itself when the option is off.  The pass is split over nb_threads
+// as cosine_rows splits its own; the element named by a refusal is the lowest offending one whatever the split.
+int f16_rows(const hnsw_index *h, const float *&rows, uint64_t n, std::vector<float> &keep, uint32_t nb_threads = 1) {
     if (!h->dev.rows_f16 || !rows) return HNSW_OK;
-    const size_t total = (size_t)n * h->host->dim;
+    const uint32_t d = h->host->dim;
+    const size_t total = (size_t)n * d;
     if (rows != keep.data()) keep.assign(rows, rows + total);
-    for (size_t i = 0; i < total; i++) {
-        if (keep[i] != keep[i]) continue;
-        const uint16_t hv = hx::f16_from_f32(keep[i]);
-        if ((hv & 0x7FFFu) == 0x7C00u) {
-            set_error("rows_f16: row %llu holds %g, beyond binary16's range (|x| < 65520)", (unsigned long long)(i / h->host->dim),
-                      (double)keep[i]);
-            return HNSW_ERR_ARG;
+    std::atomic<uint64_t> bad{UINT64_MAX};  // the lowest element that rounds to an infinity (left as it came)
+    auto work = [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t i = lo * d; i < hi * d; i++) {
+            if (keep[i] != keep[i]) continue;
+            const uint16_t hv = hx::f16_from_f32(keep[i]);
+            if ((hv & 0x7FFFu) == 0x7C00u) {
+                uint64_t cur = bad.load();
+                while (i < cur && !bad.compare_exchange_weak(cur, i)) {
+                }
+                return;
+            }
+            keep[i] = hx::f32_from_f16(hv);
         }
-        keep[i] = hx::f32_from_f16(hv);
+    };
+    const unsigned nt = (unsigned)std::min<uint64_t>(std::max(1u, nb_threads), std::max<uint64_t>(1, n / 4096));
+    if (nt <= 1) {
+        work(0, n);
+    } else {
+        std::vector<std::thread> th;
+        for (unsigned t = 0; t < nt; t++) th.emplace_back(work, n * t / nt, n * (t + 1) / nt);
+        for (auto &t : th) t.join();
+    }
+    if (bad.load() != UINT64_MAX) {
+        set_error("rows_f16: row %llu holds %g, beyond binary16's range (|x| < 65520)", (unsigned long long)(bad.load() / d),
+                  (double)keep[bad.load()]);
+        return HNSW_ERR_ARG;
     }
     rows = keep.data();
     return HNSW_OK;
@@ -265,7 +285,7 @@ int hnsw_insert_bulk_levels(hnsw_index *h, const float *rows, uint64_t n, uint32
     if (h->incomplete_build) return check_search_args(h, 1);
     std::vector<float> unit;
     if (int crc = cosine_rows(h, rows, n, unit, nb_threads)) return crc;
-    if (int frc = f16_rows(h, rows, n, unit)) return frc;
+    if (int frc = f16_rows(h, rows, n, unit, nb_threads)) return frc;
     if (h->gpu_build == 2) return device_build_guard(h, [&] { return hx::gpu_insert_bulk_full(build_target(h), rows, n, nb_threads, verbose, levels); });
     if (h->gpu_build) return device_build_guard(h, [&] { return hx::gpu_insert_bulk(build_target(h), rows, n, nb_threads, verbose, levels); });
     return h->host->insert_bulk(rows, n, nb_threads, verbose != 0, levels);
@@ -281,7 +301,7 @@ int hnsw_insert_bulk_sharded(hnsw_index *h, const float *rows, uint64_t n, uint3
     if (is_replica(h)) return reject_replica(h, "hnsw_insert_bulk_sharded");
     std::vector<float> unit;
     if (int crc = cosine_rows(h, rows, n, unit, nb_threads)) return crc;
-    if (int frc = f16_rows(h, rows, n, unit)) return frc;
+    if (int frc = f16_rows(h, rows, n, unit, nb_threads)) return frc;
     hx::ShardCtx sh{rank, world, static_cast<unsigned char *>(d_send), static_cast<unsigned char *>(d_recv), slot_bytes,
                 allgather, ctx};
     if (h->incomplete_build) return check_search_args(h, 1);
@@ -294,7 +314,7 @@ int hnsw_insert_bulk_device(hnsw_index *h, const float *rows, uint64_t n, uint32
     if (h->incomplete_build) return check_search_args(h, 1);
     std::vector<float> unit;
     if (int crc = cosine_rows(h, rows, n, unit, nb_threads)) return crc;
-    if (int frc = f16_rows(h, rows, n, unit)) return frc;
+    if (int frc = f16_rows(h, rows, n, unit, nb_threads)) return frc;
     if (h->gpu_build == 1) return device_build_guard(h, [&] { return hx::gpu_insert_bulk(build_target(h), rows, n, nb_threads, verbose, levels); });
     return device_build_guard(h, [&] { return hx::gpu_insert_bulk_full(build_target(h), rows, n, nb_threads, verbose, levels); });
 }

@@ -66,13 +66,15 @@ int check_build_params(const HostIndex &host) {
     set_error("on-device build supports m <= 128 and ef_construction <= 512");
     return HNSW_ERR_ARG;
 }
-// the device snapshot a build starts from: without the search-only extras (inline rows), and with f32 rows whatever
-// "rows_f16" says -- the build kernels read nothing else (their results are the same: the rows hold binary16 values)
-int upload_for_build(const BuildTarget &t, const std::function<int()> &meanwhile = {}) {
+// the device snapshot a build starts from: without the search-only extras (inline rows).  f32_rows: with f32 rows whatever
+// "rows_f16" says -- the host-connect build and the sharded build, whose kernels read nothing else (their results are the
+// same: the rows hold binary16 values).  Otherwise the option holds: under it the only vector rows in HBM are binary16
+// rows, upload() narrows while it packs, and the build runs hx_insert16_kernel / hx_connect16_kernel
+int upload_for_build(const BuildTarget &t, bool f32_rows, const std::function<int()> &meanwhile = {}) {
     const int saved_inline = t.dev.inline_rows;
     const bool saved_f16 = t.dev.rows_f16;
     t.dev.inline_rows = 0;
-    t.dev.rows_f16 = false;
+    if (f32_rows) t.dev.rows_f16 = false;
     t.dev.release();
     const int rc = t.dev.upload(t.host, t.device, meanwhile);
     t.dev.inline_rows = saved_inline;
@@ -187,7 +189,7 @@ int gpu_insert_bulk(const BuildTarget &t, const float *rows, uint64_t n, uint32_
         host.version++;
         return HNSW_OK;
     }
-    if ((rc = upload_for_build(t))) return rc;
+    if ((rc = upload_for_build(t, /*f32_rows=*/true))) return rc;
     const DevView v = t.dev.view;
     const uint32_t m = (uint32_t)host.params.m, L = host.nb_layers();
     const uint32_t BMAX = 4096;
@@ -961,7 +963,7 @@ int gpu_insert_bulk_full(const BuildTarget &t, const float *rows, uint64_t n, ui
     }
     size_t pos = take;
     const auto t_start = Clock::now();
-    if ((rc = upload_for_build(t, seed_and_clamp))) return rc;
+    if ((rc = upload_for_build(t, /*f32_rows=*/sh != nullptr, seed_and_clamp))) return rc;
     const auto t_uploaded = Clock::now();
     FullBuild b(t, sh, nb_threads, verbose);
     uint64_t connected = n_before + pos;
@@ -1016,8 +1018,9 @@ int gpu_insert_bulk_full(const BuildTarget &t, const float *rows, uint64_t n, ui
     host.version++;
     // the adjacency in HBM is the graph just read back: patch the few rows changed since and keep the snapshot
     // (a build of tens of GB is otherwise followed by an upload of the same tens of GB)
-    // (under "rows_f16" the build's f32 snapshot is dropped instead: the next search uploads the f16 one)
-    if (t.dev.rows_f16)
+    // (under "rows_f16" that snapshot holds the f16 rows the build itself read: refresh_rows touches adjacency only.  The
+    // sharded build ran on f32 rows: its snapshot is dropped and the next search uploads the f16 one)
+    if (t.dev.rows_f16 && !t.dev.view.rows16)
         t.dev.release();
     else if (device_is_the_graph && !sw::reupload())
         (void)t.dev.refresh_rows(host, touched);

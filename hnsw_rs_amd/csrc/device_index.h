@@ -1,5 +1,5 @@
 // device_index.h -- the HBM-resident snapshot of a HostIndex and the launchers of the kernels (search_kernels.hip,
-// search_lean.hip, search_rows16.hip, search_filtered16.hip, build_kernels.hip, exact_scan.hip, brute_mfma.hip, build_sort.hip, patch.hip, metric.hip).  gfx950 only.
+// search_lean.hip, search_rows16.hip, search_filtered16.hip, build_kernels.hip, build_kernels16.hip, exact_scan.hip, brute_mfma.hip, build_sort.hip, patch.hip, metric.hip).  gfx950 only.
 // (The record and the launchers of hx_distance_kernel's list forms are list_forms.h.)
 //
 // HBM layout (one allocation per array, all read-only during search):
@@ -17,8 +17,9 @@
 //             e at byte 2 e, zero-padded to 16 B -- row_stride = f16_row_stride(d) = 2 d rounded up to 16.  Every value
 //             is the host's f32 element exactly (upload() refuses a row that does not survive the round trip).  No
 //             inline-rows copy.  ONLY hx_search16_kernel (search_rows16.hip), hx_filt16_graph_kernel /
-//             hx_filt16_scan_kernel (search_filtered16.hip) and the three ground-truth kernels of
-//             brute_mfma16.hip (section 38) read such rows: every other kernel
+//             hx_filt16_scan_kernel (search_filtered16.hip), the three ground-truth kernels of
+//             brute_mfma16.hip (section 38) and hx_insert16_kernel / hx_connect16_kernel (build_kernels16.hip; section 39)
+//             read such rows: every other kernel
 //             takes "not QUANT8" for f32, and ensure_uploaded keeps such a snapshot from them.
 //   adj0      N x S0 u32: layer-0 adjacency in fixed-stride rows (S0 = pow2 >= max(2m, 32), 128 B at
 //             m = 16), row index = node id, neighbour ids ascending, empty slots 0xFFFFFFFF behind them.
@@ -287,6 +288,12 @@ int launch_connect(const DevView &v, const ConnectArgs &a, hipStream_t stream);
 int launch_remove(const DevView &v, const ConnectArgs &a, hipStream_t stream);
 int launch_scatter_rows(uint32_t *dst, uint32_t S, const uint32_t *d_row_index, const uint32_t *d_data,
                         uint32_t n, hipStream_t stream);
+// the insert and connect kernels over a view with f16 rows (build_kernels16.hip, libhnsw_mi355x_build16.so; DESIGN.md
+// section 39).  launch_insert / launch_connect route to them after their own checks: slots_log2 and lds are
+// launch_insert's, rs (1 / 2 / 4) the list registers an adjacency row takes
+int launch_insert_rows16(const DevView &v, const InsertArgs &a, uint32_t nblocks, uint32_t slots_log2, size_t lds,
+                         hipStream_t stream);
+int launch_connect_rows16(const DevView &v, const ConnectArgs &a, int rs, hipStream_t stream);
 
 // exhaustive scan on the matrix cores (brute_mfma.hip): a screen by MFMA scores, then exact distances of
 // the survivors.  f32 rows, dimension a multiple of 4.

@@ -118,7 +118,11 @@ int hnsw_insert_bulk_levels(hnsw_index *h, const float *rows, uint64_t n, uint32
  * is judged by recall and invariants, not by identity with the sequential build.  Needs m <= 128 and
  * ef_construction <= 512; nb_threads is used for the host-side parts (store, seed, read-back).
  * hnsw_set_option(h, "gpu_build", 2) routes hnsw_insert_bulk here; "gpu_build" = 1 selects the older
- * hybrid form (GPU searches, connect / prune on nb_threads host threads with the reference's locks). */
+ * hybrid form (GPU searches, connect / prune on nb_threads host threads with the reference's locks).
+ * On a handle under the option "rows_f16" the build reads binary16 rows (hx_insert16_kernel / hx_connect16_kernel,
+ * DESIGN.md section 39): the only vector rows in HBM are the 2-byte ones, the graph is edge for edge the one this call
+ * builds on a plain handle over X.astype(float16).astype(float32), and the snapshot it leaves is the one the next
+ * search reads.  The sharded build and "gpu_build" = 1 build from an f32 snapshot of their own under the option. */
 int hnsw_insert_bulk_device(hnsw_index *h, const float *rows, uint64_t n, uint32_t nb_threads,
                             int verbose, const uint8_t *levels);
 /* The on-device build sharded over the GPUs of a node (BASELINE configs[4]): every rank calls this with
@@ -1539,7 +1543,9 @@ int hnsw_device_bytes(const hnsw_index *h, uint64_t *bytes);
  *                      hnsw_search_filtered and hnsw_search_batch_filtered_multi, _set, _range, _set_range and _ranges
  *                      with their _device(_finish) forms.  Every other entry point that needs
  *                      the snapshot returns HNSW_ERR_ARG, hnsw_search_batch_filtered among them (_filtered_multi with
- *                      one mask for every query is the same search).  Queries stay f32
+ *                      one mask for every query is the same search).  Queries stay f32.  hnsw_insert_bulk_device (and
+ *                      hnsw_insert_bulk with "gpu_build" = 2) builds from the binary16 rows and keeps that snapshot
+ *                      (DESIGN.md section 39); hnsw_insert_bulk_sharded and "gpu_build" = 1 build from f32 rows
  *   "gpu_build_batch_max", "gpu_build_batch_div"
  *                      the on-device build inserts min(max, connected / div) points at a time (defaults
  *                      8192 and 8; max is capped at 32768); 256 and 64 stand closer to the reference's
