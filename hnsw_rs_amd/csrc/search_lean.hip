@@ -1299,20 +1299,12 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             STAMP_ADD(LEAN_FILTER, f1, f2);
             STAMP_FILTER_KEPT(kept, f1, f2);
             STAMP(f3);
-            STAMP_MERGE_SIZE(!upper && key < lst.last_key, LEAN_SMALL_C, LEAN_SMALL_C_KEYS);
             const u64 nanm = __ballot(nan);
             if (HX_UNLIKELY((nanm & 0xFFFFFFFFull) != 0)) {
                 status = HNSW_ERR_NAN_INPUT;  // Dist::cmp would panic (dist.rs:32)
                 break;
             }
             u64 bm = 0;  // c's fresh keys below p's key (MISS_AHEAD)
-            u64 am = 0;  // FRONTIER: c's survivors that sort in front of b
-            if constexpr (FRONTIER) {
-                // The two entries behind p stay the frontier's a and b through c's merge unless a survivor -- a fresh
-                // key below the bound as it stands before the merge -- sorts in front of b.  Without a b (LK_INVALID)
-                // any survivor counts: it may be the new a or b.  Known before the merge, asked for after it.
-                am = __ballot(!upper && key < min(bkey, lst.last_key));
-            }
             if constexpr (MISS_AHEAD) {
                 // ---- a miss foreseen.  A fresh key of c below p's key enters the list (p's key is at most the list's
                 // last) in front of p, the smallest unexpanded entry left: the next pick is the smallest such key and,
@@ -1351,41 +1343,52 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                     }
                 }
             }
-            lst.merge(upper ? LK_INVALID : key, ef, perm, lane MERGE_DBG_ARG(LEAN_MERGE_C));
-            STAMP(f3b);
-            STAMP_ADD(LEAN_MERGE_C_ALL, f3, f3b);
-            if (HX_UNLIKELY((pm & 0xFFFFFFFFull) != 0)) {  // degree > S0: the rest of c's row goes through the next passes (rare)
-                const uint32_t c_ovf = rdlane(nb, (uint32_t)__ffsll((long long)(pm & 0xFFFFFFFFull)) - 1) & ~HX_OVF_FLAG;
-                ovf_lo = uni(a.ovf_off[c_ovf]);
-                ovf_hi = uni(a.ovf_off[c_ovf + 1]);
-                if (ovf_lo < ovf_hi) continue;  // (the runner-up is picked again afterwards)
-            }
             // ---- is p the next candidate?  then commit it from the registers ----
-            if (HX_UNLIKELY(!spec_ok)) continue;
+            // FRONTIER: p was the first unexpanded entry behind c, c is marked and every older entry in front of p is
+            // expanded: p is next exactly when no fresh key of c sorts below it -- the foreseen miss's ballot, nothing
+            // new (such a key is below the bound, so it would go in; with none, p keeps its place and cannot leave the
+            // list).  The verdict is formed from the pass's own keys, so it needs no merge of c's first: a pass that
+            // commits p merges the keys of both rows ONCE, behind p's claims.  The list after both expansions is the
+            // ef smallest of list, c's fresh keys and p's fresh keys however they are grouped (order-independent,
+            // SURVEY.md N2), p sits at or below the bound, so the termination test at its pick could not fire, and
+            // the counters count fresh ids, not insertions.  A pass whose c carried an overflow pointer, or whose p
+            // may not be speculated on, merges c's keys alone and picks again.
+            const bool fold = FRONTIER && spec_ok && (bm | pm) == 0;
             int npos = -1;
-            if constexpr (FRONTIER) {
-                // p was the first unexpanded entry behind c, c is marked and every older entry in front of p is
-                // expanded: p is next exactly when no fresh key of c sorts below it -- the foreseen miss's ballot,
-                // nothing new (such a key is below the bound, so it went in; with none, p kept its place and cannot
-                // have left the list).  A pass whose c carried an overflow pointer picks again instead.
-                if (HX_UNLIKELY((bm | pm) != 0)) continue;
+            if (fold) {
                 // The pass after this one will most likely expand the two entries that follow p (measured: three
                 // times out of four when p is committed).  Their adjacency rows are requested now and land while p
                 // is being committed; if the next pick is a different pair they are dropped.  The pair is the
-                // frontier's a and b unless a survivor of c went in front of b: then the frontier of the merged
-                // list, whose first entry is p.
-                if (HX_UNLIKELY(am != 0)) {
-                    u64 G[4];
-                    lst.frontier(G, perm, lane);
-                    akey = G[1];
-                    bkey = G[2];
-                    STAMP_FRONTIER_RERUN();
+                // frontier's a and b unless a key of the pass sorts in front of b and below the bound as it stands
+                // (without a b, LK_INVALID, any key below the bound): then the two smallest of a, b and those keys,
+                // taken from the key register.  p's lanes count with the keys their look called absent: a guess, as the
+                // whole pair is -- the next pick validates it.
+                u64 it = __ballot(key < min(bkey, lst.last_key));
+                while (HX_UNLIKELY(it != 0)) {
+                    const u64 t = rdlane64(key, (uint32_t)__ffsll((long long)it) - 1);
+                    it &= it - 1;
+                    if (t == akey) continue;  // (an id in both rows: c's lane and p's lane hold the same key)
+                    bkey = t < akey ? akey : min(bkey, t);
+                    akey = min(akey, t);
+                    STAMP_COUNT(LEAN_FRONTIER_RERUNS);
                 }
                 pre_c = (uint32_t)akey;  // (HX_EMPTY_SLOT where there is none: matches no candidate)
                 pre_p = (uint32_t)bkey;
                 pre_nb = HX_EMPTY_SLOT;
                 if (slot < S0 && lk_unexp(upper ? bkey : akey)) pre_nb = a.adj0[(size_t)(upper ? pre_p : pre_c) * S0 + slot];
+                STAMP_ADD_NOW(LEAN_IS_P_NEXT, f3);  // (with the NaN ballot and the miss block's test in front of it)
             } else {
+                STAMP_MERGE_SIZE(!upper && key < lst.last_key, LEAN_SMALL_C, LEAN_SMALL_C_KEYS);
+                lst.merge(upper ? LK_INVALID : key, ef, perm, lane MERGE_DBG_ARG(LEAN_MERGE_C));
+                STAMP(f3b);
+                STAMP_ADD(LEAN_MERGE_C_ALL, f3, f3b);
+                if (HX_UNLIKELY((pm & 0xFFFFFFFFull) != 0)) {  // degree > S0: the rest of c's row goes through the next passes (rare)
+                    const uint32_t c_ovf = rdlane(nb, (uint32_t)__ffsll((long long)(pm & 0xFFFFFFFFull)) - 1) & ~HX_OVF_FLAG;
+                    ovf_lo = uni(a.ovf_off[c_ovf]);
+                    ovf_hi = uni(a.ovf_off[c_ovf + 1]);
+                    if (ovf_lo < ovf_hi) continue;  // (the runner-up is picked again afterwards)
+                }
+                if (HX_UNLIKELY(!spec_ok) || FRONTIER) continue;
                 typename LT::Masks V;
                 lst.unexp_masks(V);
                 npos = lst.take_first(V);
@@ -1402,9 +1405,9 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
                         if (slot < S0 && (!upper || bpos >= 0)) pre_nb = a.adj0[(size_t)(upper ? pre_p : pre_c) * S0 + slot];
                     }
                 }
+                STAMP_ADD_NOW(LEAN_IS_P_NEXT, f3b);
             }
             STAMP(f4);
-            STAMP_ADD(LEAN_IS_P_NEXT, f3b, f4);
             if constexpr (FRONTIER)
                 lst.mark_key(pkey);
             else
@@ -1434,9 +1437,11 @@ __global__ void __launch_bounds__(64) hx_lean_f32_kernel(const LeanArgs a) {
             }
             STAMP(f4b);
             STAMP_ADD(LEAN_COMMIT_P, f4, f4b);
-            STAMP_MERGE_SIZE(pfresh && key < lst.last_key, LEAN_SMALL_P, LEAN_SMALL_P_KEYS);
+            // p's fresh keys -- and, where the verdict came before c's merge, c's with them
+            const u64 ckey = (pfresh || (fold && !upper)) ? key : LK_INVALID;
+            STAMP_MERGE_SIZE(ckey < lst.last_key, LEAN_SMALL_P, LEAN_SMALL_P_KEYS);
             STAMP_COUNT(LEAN_P_COMMITS);
-            lst.merge(pfresh ? key : LK_INVALID, ef, perm, lane MERGE_DBG_ARG(LEAN_MERGE_P));
+            lst.merge(ckey, ef, perm, lane MERGE_DBG_ARG(LEAN_MERGE_P));
             STAMP(f5);
             STAMP_ADD(LEAN_MERGE_P_ALL, f4b, f5);
         }

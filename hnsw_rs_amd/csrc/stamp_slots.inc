@@ -22,9 +22,9 @@
     X(LEAN, COMMIT_P, 5, "commit p: mark + visited insert")                                                     \
     X(LEAN, PASSES, 6, "layer-0 passes (count)")                                                                \
     X(LEAN, FRONT, 7, "staging + entry + upper layers")                                                         \
-    X(LEAN, MERGE_C_ALL, 8, "merge c")                                                                          \
-    X(LEAN, IS_P_NEXT, 9, "overflow rows + pick + is-p-next")                                                   \
-    X(LEAN, MERGE_P_ALL, 10, "commit p: merge + pick")                                                          \
+    X(LEAN, MERGE_C_ALL, 8, "merge c alone (passes that do not commit p)")                                      \
+    X(LEAN, IS_P_NEXT, 9, "overflow rows + the pair requested ahead")                                           \
+    X(LEAN, MERGE_P_ALL, 10, "commit p: the pass's one merge (c's and p's keys)")                               \
     X(LEAN, SLOW_ROUNDS, 11, "visited slow-loop rounds: passes with a second claim round (count)")              \
     X(LEAN, MERGES_0, 12, "merges with no survivor (count)")                                                    \
     X(LEAN, MERGES_1_2, 13, "merges with one or two survivors (count)")                                         \
@@ -56,7 +56,7 @@
     X(LEAN, F_EXPANSIONS, 48, "HX_STAMPS_FRONT: upper-layer expansions (count)")                                \
     X(LEAN, FRONTIER, 50, "the frontier at the pick (inside slot 0, which its own stamp lengthens)")            \
     X(LEAN, FRONTIER_RUNS, 51, "frontier runs (count)")                                                         \
-    X(LEAN, FRONTIER_RERUNS, 52, "frontier runs after c's merge: a survivor went in front of b (count)")
+    X(LEAN, FRONTIER_RERUNS, 52, "keys in front of b that went into the pair requested ahead (count)")
 
 #define HX_STAMP_SLOTS_MERGE(X)                                             \
     X(MERGE, LOOP, 0, "survivor loop of the big merges")                    \

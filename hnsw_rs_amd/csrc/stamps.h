@@ -74,11 +74,6 @@ __device__ __forceinline__ unsigned long long stamp_now() {
         STAMP_ADD_NOW(LEAN_FRONTIER, t0);                                                    \
         STAMP_COUNT(LEAN_FRONTIER_RUNS);                                                     \
     } while (0)
-#define STAMP_FRONTIER_RERUN()              \
-    do {                                    \
-        STAMP_COUNT(LEAN_FRONTIER_RUNS);    \
-        STAMP_COUNT(LEAN_FRONTIER_RERUNS);  \
-    } while (0)
 // the pick (cid, pid): was it what the last miss foresaw, and is it the pair whose rows were fetched ahead?
 #define STAMP_NOTE_PICK(cid, pid, pre_c, pre_p)                                                 \
     do {                                                                                        \
@@ -264,7 +259,6 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 #define STAMP_COUNT_N(slot, n)
 #define STAMP_STATE_LEAN_F32()
 #define STAMP_FRONTIER_AT_PICK(t0, F)
-#define STAMP_FRONTIER_RERUN()
 #define STAMP_NOTE_PICK(cid, pid, pre_c, pre_p)
 #define STAMP_NOTE_MISS(bm, pred_c, pred_p, old_p)
 #define STAMP_PASS_PICKED()

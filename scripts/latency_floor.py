@@ -75,8 +75,8 @@ for nq in (64, 1024):
          "floor_ms_slowest_query": round(floor_cyc[np.argmax(tot)] / ghz / 1e6, 4), "floor_ms_mean_query": round(floor_cyc.mean() / ghz / 1e6, 4),
          "floor_over_kernel": round(floor_cyc[np.argmax(tot)] / tot.max(), 3)}
     # the bookkeeping term in its parts, per pass, and how many merges inserted 0 / 1-2 / more keys
-    r["bookkeeping_cycles_per_pass"] = {"merge_of_c": round(C("MERGE_C_ALL").mean() / passes.mean()), "is_p_next_and_prefetch": round(C("IS_P_NEXT").mean() / passes.mean()),
-                                        "claims_of_p": round(C("COMMIT_P").mean() / passes.mean()), "merge_of_p": round(C("MERGE_P_ALL").mean() / passes.mean())}
+    r["bookkeeping_cycles_per_pass"] = {"merge_of_c_alone": round(C("MERGE_C_ALL").mean() / passes.mean()), "pair_ahead_and_overflow_rows": round(C("IS_P_NEXT").mean() / passes.mean()),
+                                        "claims_of_p": round(C("COMMIT_P").mean() / passes.mean()), "commit_merge": round(C("MERGE_P_ALL").mean() / passes.mean())}
     r["per_query_counts"] = {"p_commits": round(C("P_COMMITS").mean(), 2), "merges_inserting_0": round(C("MERGES_0").mean(), 2),
                              "merges_inserting_1_or_2": round(C("MERGES_1_2").mean(), 2), "merges_inserting_more": round(C("MERGES_3_UP").mean(), 2),
                              "passes_with_a_second_claim_round": round(C("SLOW_ROUNDS").mean(), 2)}

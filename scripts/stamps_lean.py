@@ -63,16 +63,18 @@ for ef in efs:
     print('   unaccounted %.1f%%' % (100 * (tot.mean() - acc) / tot.mean()))
     print('   per query: visited slow-loop rounds %.1f; merges with 0 / 1-2 / >=3 survivors: %.1f / %.1f / %.1f; p commits %.1f' % (
         C('SLOW_ROUNDS').mean(), C('MERGES_0').mean(), C('MERGES_1_2').mean(), C('MERGES_3_UP').mean(), C('P_COMMITS').mean()))
-    # the merges' own split (slots 26 .. 30 c's merge, 31 .. 35 p's): cycles of the survivor loop, of the LDS phase and of
-    # the shift path, the survivors of the big merges, the big merges.  (The split's own stamps lengthen slots 8 and 10.)
-    for nm, b in (('merge c', 'MERGE_C'), ('merge p', 'MERGE_P')):
+    # the merges' own split (slots 26 .. 30 the merge of c's keys alone, on a pass that does not commit p; 31 .. 35 the one
+    # merge of a pass that commits p, c's and p's keys together): cycles of the survivor loop, of the LDS phase and of the
+    # shift path, the survivors of the big merges, the big merges.  (The split's own stamps lengthen slots 8 and 10.)
+    MERGES = (('merge c alone', 'MERGE_C'), ('commit merge', 'MERGE_P'))
+    for nm, b in MERGES:
         nbig, nsv = C(b, 'BIG').sum(), C(b, 'SURVIVORS').sum()
         print('   %s: survivor loop %.0f, LDS phase %.0f, shift path %.0f cycles/query; %.1f big merges of %.1f survivors: loop %.0f + LDS phase %.0f cycles per big merge, loop %.1f per survivor' % (
             nm, C(b, 'LOOP').mean(), C(b, 'LDS').mean(), C(b, 'SHIFT').mean(), C(b, 'BIG').mean(), nsv / max(1, nbig),
             C(b, 'LOOP').sum() / max(1, nbig), C(b, 'LDS').sum() / max(1, nbig), C(b, 'LOOP').sum() / max(1, nsv)))
     # the small merges (slots 36 / 37 c's, 38 / 39 p's: merges that took the shift path, the keys they inserted); a small
     # merge holds one or two keys while HX_MERGE_SHIFT_MAX is 2: two-key merges = keys - merges
-    for nm, b, c, ck in (('merge c', 'MERGE_C', 'SMALL_C', 'SMALL_C_KEYS'), ('merge p', 'MERGE_P', 'SMALL_P', 'SMALL_P_KEYS')):
+    for nm, b, c, ck in ((MERGES[0][0], 'MERGE_C', 'SMALL_C', 'SMALL_C_KEYS'), (MERGES[1][0], 'MERGE_P', 'SMALL_P', 'SMALL_P_KEYS')):
         sh, sm, sk = C(b, 'SHIFT'), C(c), C(ck)
         ns, nk = sm.sum(), sk.sum()
         print('   %s: %.1f small merges of %.2f keys per query (with one key %.1f, with more %.1f): shift path %.0f cycles per small merge, %.0f per inserted key' % (
@@ -88,12 +90,18 @@ for ef in efs:
     took = C('PASSES_AHEAD')
     print('   per query: misses %.1f, with 1 / 2 / >=3 fresh keys of c below p: %.1f / %.1f / %.1f; follow-up pick is the predicted pair %.2f; follow-up runner-up is the old p %.1f' % (
         miss.mean(), C('MISS_1').mean(), C('MISS_2').mean(), C('MISS_3_UP').mean(), C('MISS_PREDICTED').mean(), C('MISS_OLD_P').mean()))
-    # the frontier (its cycles -- inside slot 0, which its own stamp lengthens --, its runs, and the
-    # runs after c's merge: a survivor went in front of b, so the pair requested ahead is not the frontier's a and b)
-    fr_cyc, fr_runs, fr_again = C('FRONTIER'), C('FRONTIER_RUNS'), C('FRONTIER_RERUNS')
-    print('   frontier: %.2f runs per pass, %.0f cycles per run at the pick; %.1f p commits per query, %.1f of them (%.1f%%) took the pair from the pick\'s frontier, %.1f ran it again' % (
-        fr_runs.sum() / max(1, passes.sum()), fr_cyc.sum() / max(1, (fr_runs - fr_again).sum()), C('P_COMMITS').mean(),
-        (C('P_COMMITS') - fr_again).mean(), 100 * (C('P_COMMITS') - fr_again).sum() / max(1, C('P_COMMITS').sum()), fr_again.mean()))
+    # the frontier (its cycles -- inside slot 0, which its own stamp lengthens -- and its runs: one per pick), and the
+    # keys of committing passes that sort in front of b and below the bound: each costs one read-lane step and goes into
+    # the pair requested ahead
+    fr_cyc, fr_runs, fr_keys = C('FRONTIER'), C('FRONTIER_RUNS'), C('FRONTIER_RERUNS')
+    print('   frontier: %.2f runs per pass, %.0f cycles per run; %.1f p commits per query; keys in front of b read for the pair ahead: %.1f per query, %.2f per commit, at most %.0f in a query' % (
+        fr_runs.sum() / max(1, passes.sum()), fr_cyc.sum() / max(1, fr_runs.sum()), C('P_COMMITS').mean(),
+        fr_keys.mean(), fr_keys.sum() / max(1, C('P_COMMITS').sum()), fr_keys.max()))
+    # a committing pass by itself: the pair ahead (slot 9), p's claim block (slot 5) and the one merge (slot 10)
+    pc = max(1, C('P_COMMITS').sum())
+    print('   per p commit: pair ahead %.0f, mark + claims of p %.0f, the merge %.0f cycles; merge of c alone %.0f cycles per pass that does not commit' % (
+        C('IS_P_NEXT').sum() / pc, C('COMMIT_P').sum() / pc, C('MERGE_P_ALL').sum() / pc,
+        C('MERGE_C_ALL').sum() / max(1, (passes - C('P_COMMITS')).sum())))
     print('   pick + adjacency (slot 0) per pass: %.0f cycles on the %.1f passes whose rows were fetched ahead, %.0f on the %.1f others' % (
         C('PICK_AHEAD').sum() / max(1, took.sum()), took.mean(), (C('PICK') - C('PICK_AHEAD')).sum() / max(1, (passes - took).sum()), (passes - took).mean()))
     print('   look + request + claims + chain (slot 1) per pass: %.0f cycles on the %.1f passes whose runner-up kept its distances, %.0f on the %.1f others' % (
@@ -107,10 +115,13 @@ for ef in efs:
         print('            misses 1/2/>=3 below p %3d/%3d/%3d  predicted %3d  old p again %3d  slot 0 per pass: ahead %5.0f (%3d passes), others %5.0f  slot 1 per pass %5.0f  kept %3d passes at %5.0f' % (
             C('MISS_1')[qi], C('MISS_2')[qi], C('MISS_3_UP')[qi], C('MISS_PREDICTED')[qi], C('MISS_OLD_P')[qi], C('PICK_AHEAD')[qi] / max(1, took[qi]), took[qi],
             (C('PICK')[qi] - C('PICK_AHEAD')[qi]) / max(1, passes[qi] - took[qi]), C('FILTER')[qi] / max(1, passes[qi]), C('PASSES_KEPT')[qi], C('FILTER_KEPT')[qi] / max(1, C('PASSES_KEPT')[qi])))
-        print('            merge c + p: survivor loop %6.0f  LDS phase %6.0f  shift path %6.0f cycles; big merges %3d with %4d survivors' % tuple(
+        print('            all merges: survivor loop %6.0f  LDS phase %6.0f  shift path %6.0f cycles; big merges %3d with %4d survivors' % tuple(
             (C('MERGE_C', o) + C('MERGE_P', o))[qi] for o in ('LOOP', 'LDS', 'SHIFT', 'BIG', 'SURVIVORS')))
         print('            small merges %3d with %3d keys: shift path %5.0f cycles per small merge, %5.0f per key, %.1f%% of the query' % (
             small[qi], small_keys[qi], shift[qi] / max(1, small[qi]), shift[qi] / max(1, small_keys[qi]), 100 * shift[qi] / tot[qi]))
+        print('            mark + claims of p %6.0f cycles (%4.0f per commit)  commit merges %6.0f (%4.0f per commit)  merges of c alone %6.0f  keys read for the pair ahead %3d' % (
+            C('COMMIT_P')[qi], C('COMMIT_P')[qi] / max(1, C('P_COMMITS')[qi]), C('MERGE_P_ALL')[qi], C('MERGE_P_ALL')[qi] / max(1, C('P_COMMITS')[qi]),
+            C('MERGE_C_ALL')[qi], fr_keys[qi]))
     cc = np.corrcoef(tot, S[:, 1])[0, 1]
     fit = np.polyfit(S[:, 1].astype(np.float64), tot, 1)
     print('   corr(total cycles, n_exp) = %.3f; fit: cycles = %.0f * n_exp + %.0f; n_exp mean %.1f p99 %.0f max %d' % (
